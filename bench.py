@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- EM-iteration throughput of the EVO hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 may be called bare: the parent starts N fresh child processes (one per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set) before anything touches the GPU, waits
@@ -21,12 +21,20 @@ step keep the timed region of the driver's 20 steps above one second of GPU time
 Metric = candidate-state evaluations per second counted as N x S per EM iteration (BASELINE.json's headline;
 the candidate evaluations are done but not counted), whole job, all ranks.
 
-The JSON line carries
+A plain run sets up, warms up, times the steps, writes the outputs if asked to and prints the JSON line:
+metric / value / unit / higher_is_better / dtype, ms_per_step (milliseconds per timed step) and the workload.
+
+--full adds, after the timed region (and HIP-event spans of the two passes inside it):
   roofline        the WHOLE pass over the resident K^n (main kernel + every overflow level it spawns, one
                   HIP-event span on the library's stream inside the timed region) against the HBM roof
   roofline_stats  the whole statistics pass (scatter kernels + overflow levels + column sums) likewise
+  mfma, levels    the contractions against the MFMA peak; the overflow levels by number of active latents
+  config          + kernel_ms (per-class times of extra instrumented iterations), the eager-Theta loop, E-step counters
+  per_rank        (N > 1) every rank's view of the timed loop
   cpu_baseline    the loop-faithful NumPy restatement of the reference (oracle/, "port") timed on every host
-                  core this process may use, on a bounded sample of the same workload (N=1 only)
+                  core this process may use, on a bounded sample of the same workload (N=1 only; --no-cpu-baseline)
+
+--dump-outputs DIR writes what the last timed step handed its caller (dump_outputs) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -448,6 +456,231 @@ def launch_ranks(n, argv, worker=None, timeout_s=None, poll_s=0.05, grace_s=5.0)
 
 
 # ---------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed in its last step
+# ---------------------------------------------------------------------------------------------
+DUMP_MAX_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE_BYTES = 32 * 10 ** 6  # K^n / lpj sample
+DUMP_MAX_ROWS = 256  # datapoints of the K^n / lpj sample
+DUMP_SEED = 8191
+
+
+def dump_outputs(path, eng, F, nu, nsub, theta):
+    """Write what step() handed its caller in the last timed step, as <path>/<name>.npy (float64; float32 where Theta
+    is float32), at most DUMP_MAX_BYTES in all:
+      free_energy, S_nunique, S_sub    step()'s three scalars
+      theta_<key>                      every numeric entry of Theta^new (a LazyTheta downloads here)
+      Kn_sample, lpj_sample            my_suff_stat["ss"] / ["lpj"] as sync_to_host would hand them over, for a fixed
+                                       seeded sample of this rank's datapoints (Kn_sample_rows): K^n as 0/1 floats
+                                       (rows, S, H), the S states of each datapoint sorted by their bits (K^n is a
+                                       set) and lpj permuted alike
+    The sample takes DUMP_SAMPLE_BYTES at most, DUMP_MAX_ROWS datapoints at most."""
+    os.makedirs(path, exist_ok=True)
+    out = {"free_energy": F, "S_nunique": nu, "S_sub": nsub}
+    for k in sorted(theta.keys()):
+        v = np.asarray(theta[k])
+        if v.dtype.kind in "biuf":
+            out["theta_" + k] = v
+    out = {k: np.asarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in out.items()}
+    N, S, H = eng.N, eng.S, eng.H
+    per_row = S * H * 4 + eng.L * 8 + 8
+    n_rows = max(1, min(N, DUMP_MAX_ROWS, DUMP_SAMPLE_BYTES // per_row))
+    rows = np.sort(np.random.RandomState(DUMP_SEED).choice(N, n_rows, replace=False))
+    lpj = eng.download_lpj()[rows]
+    packed = np.concatenate([eng.download_states_packed(int(r), 1) for r in rows])  # (rows, S, ceil(H/8))
+    ss = np.unpackbits(packed, axis=-1)[..., :H]
+    for i in range(n_rows):
+        order = np.lexsort(packed[i].T[::-1])  # states by their bit words, first byte most significant
+        ss[i] = ss[i][order]
+        lpj[i, eng.S_perm:] = lpj[i, eng.S_perm:][order]
+    out["Kn_sample"] = ss.astype(np.float32)
+    out["lpj_sample"] = lpj
+    out["Kn_sample_rows"] = rows.astype(np.float64)
+    assert sum(v.nbytes for v in out.values()) <= DUMP_MAX_BYTES
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return sorted(out)
+
+
+def full_measurements(args, cfg, eng, comm, model, theta, suff, my_data, barrier, world, rank, n_loc, iters, dt_own):
+    """--full, after the timed region: the roofline spans recorded inside it, the per-rank view, the eager-Theta loop and
+    the instrumented iterations.  Rank 0 gets what it adds to the JSON line ("config" entries apart), the others None."""
+    lpj_ms, lpj_n = eng.kernel_time_ms("lpj_pass")
+    st_ms, st_n = eng.kernel_time_ms("stats_pass")
+    # per-rank view of the timed loop in rank 0's line (a first multi-GPU run must be diagnosable from it): every rank fills
+    # its slot of a zero vector, the sum is the gather
+    per_rank = None
+    if world > 1:
+        ar_ms, ar_n = eng.kernel_time_ms("allreduce")
+        mine = np.zeros((world, 5))
+        mine[rank] = [1e3 * dt_own / (args.steps * iters), lpj_ms, st_ms, ar_ms * (ar_n / max(1.0, float(st_n))), n_loc]
+        allr = comm.allreduce_array(mine)
+        per_rank = {"ms_per_em_iteration_own_queue": [round(v, 5) for v in allr[:, 0]],
+                    "lpj_pass_ms": [round(v, 5) for v in allr[:, 1]], "stats_pass_ms": [round(v, 5) for v in allr[:, 2]],
+                    "allreduce_ms_per_iteration": [round(v, 5) for v in allr[:, 3]], "datapoints": [int(v) for v in allr[:, 4]],
+                    "note": "allreduce_ms_per_iteration = HIP-event span(s) around the RCCL all-reduce(s) of the packed accumulator "
+                            "on each rank's stream: from the rank's own statistics being done to the sum being delivered, i.e. "
+                            "waiting for the slowest rank + the collective; the SMALLEST entry is the closest to the collective "
+                            "itself (the last rank to arrive waits for nobody)"}
+    # the reference's step() returns Theta^new as host arrays every epoch: the same loop with the per-iteration download
+    eager_ms = None
+    if not args.eager_theta and not args.host_mstep:
+        eager_iters = max(10, min(50, args.steps * iters // 4))
+        model.lazy_theta = False
+        for _ in range(3):
+            F2, nu2, nsub2, theta = model.step(theta, suff, my_data)
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(eager_iters):
+            F2, nu2, nsub2, theta = model.step(theta, suff, my_data)
+        barrier()
+        eager_ms = 1e3 * (time.perf_counter() - t1) / eager_iters
+        if world > 1:
+            eager_ms = comm.allreduce_max(eager_ms)
+        model.lazy_theta = True
+        F2, nu2, nsub2, theta = model.step(theta, suff, my_data)
+    n_gt2 = float(getattr(model, "last_dpar", {}).get("n_gt2", float("nan")))
+    # instrumented pass (not part of `value`): per-class device time of a few more iterations
+    prof_iters = 5
+    eng.timing(True)
+    eng.timing_reset()
+    for _ in range(prof_iters):
+        _F, _nu, _nsub, theta = model.step(theta, suff, my_data)
+    barrier()
+    kernel_ms = {}
+    for name in ("lpj_resident", "lpj_candidates", "lpj_overflow", "row_lse", "vary_kn", "stats", "stats_overflow",
+                 "gemm_f64", "evolve", "misc", "mstep_device", "lpj_pass", "stats_pass", "lpj_k3_4", "lpj_k5_8", "lpj_k9plus",
+                 "stats_k3_4", "stats_k5_8", "stats_k9plus", "estep_fused", "allreduce"):
+        avg, n = eng.kernel_time_ms(name)
+        if n:
+            kernel_ms[name] = {"avg_ms": round(avg, 6), "launches_per_iteration": n / prof_iters}
+    # the contractions once more with ONLY their own class timed: the K = N product then runs forked beside the
+    # Theta-update chain exactly as in the timed loop (the fully instrumented pass above runs it alone on the main stream,
+    # between event records that idle the GPU), its span recorded on the stream it runs on
+    eng.timing(["gemm_f64"])
+    eng.timing_reset()
+    for _ in range(prof_iters):
+        _F, _nu, _nsub, theta = model.step(theta, suff, my_data)
+    barrier()
+    g_avg, g_n = eng.kernel_time_ms("gemm_f64")
+    gemm_loop = {"avg_ms": round(g_avg, 6), "launches_per_iteration": g_n / prof_iters} if g_n else None
+    eng.timing(False)
+
+    estep_diag = eng.estep_counters() if cfg["algo"] == "es3c" else None
+    if rank != 0:
+        return None
+    alg_bytes = algorithmic_bytes_pass(cfg, n_loc)  # per launch = this rank's shard
+    lay_bytes = layout_bytes_lpj(cfg, n_loc)
+
+    def roof(ms, launches, kernels, what):
+        ach = (alg_bytes / (ms * 1e-3) / 1e9) if ms > 0 else 0.0
+        return {"bound": "hbm", "kernel": what, "kernels_in_span": kernels,
+                "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                "traffic": pmc_traffic(traffic_key(args), kernels),
+                "traffic_note": "HBM bytes per pass, rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes, read "
+                                "side corrected for gfx950 (2 x FETCH_SIZE: an upper bound for kernels whose loads are 8 bytes per lane), "
+                                "summed over the kernels of the span; counters of this workload from "
+                                + str(getattr(pmc_traffic, "source", None)),
+                "algorithmic_bytes_per_launch": alg_bytes,
+                "algorithmic_bytes_note": "SURVEY 8d: N_rank x (D*8 + S*(ceil(H/8) + 8)), states priced bit-packed",
+                "avg_launch_ms": ms, "launches_timed": launches}
+
+    r_lpj = roof(lpj_ms, lpj_n, pass_kernels(cfg), "whole pass over the resident K^n: lpj of all N x S states "
+                 "(main kernel + every overflow level it spawns), one HIP-event span per pass")
+    r_lpj["states_in_main_kernel"] = (1.0 - n_gt2 / (float(n_loc) * cfg["S"])) if n_gt2 == n_gt2 else None
+    ld = getattr(model, "last_dpar", {})
+    r_lpj["overflow_census"] = {k: ld.get(k) for k in ("n_gt2", "n_gt4", "n_gt8") if k in ld}
+    r_lpj["layout_bytes_per_launch"] = lay_bytes
+    r_lpj["frac_of_layout_bytes"] = (lay_bytes / (lpj_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if lpj_ms > 0 else 0.0
+    r_lpj["layout_note"] = ("`achieved` / `frac` price SURVEY 8d's algorithmic bytes (bit-packed states + y_n); the kernels "
+                            "read an 8-byte digest per state and the row of B = Y W instead: frac_of_layout_bytes prices that")
+    if r_lpj["frac"] > 1.0:
+        # at large H the digest layout moves fewer bytes than SURVEY 8d prices: a fraction above 1 says nothing
+        # about the kernel, so the headline fraction becomes the layout one and the other keeps its own name
+        r_lpj["frac_algorithmic_bytes_over_roof"] = r_lpj["frac"]
+        r_lpj["frac"] = r_lpj["frac_of_layout_bytes"]
+        r_lpj["frac_basis"] = "layout bytes (algorithmic-byte pricing exceeds the roof for this layout)"
+    r_st = roof(st_ms, st_n, stats_kernels(cfg), "whole statistics pass over the resident K^n (scatter kernel + overflow "
+                "levels + column sums + finish; the MFMA contraction is priced under `mfma`)")
+    tr = r_st.get("traffic")
+    lay_st = layout_bytes_stats(cfg, n_loc)
+    r_st["layout_bytes_per_launch"] = lay_st
+    r_st["frac_of_layout_bytes"] = (lay_st / (st_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if st_ms > 0 else 0.0
+    if tr is None and lay_st < alg_bytes:
+        # no counters for this workload and the layout moves fewer bytes than SURVEY 8d prices: the algorithmic-byte
+        # fraction would flatter the kernel (c5 float32 mode: 0.99) -- the headline fraction prices the layout bytes
+        r_st["frac_algorithmic_bytes_over_roof"] = r_st["frac"]
+        r_st["frac"] = r_st["frac_of_layout_bytes"]
+        r_st["frac_basis"] = "layout bytes (no PMC counters committed for this workload; below the algorithmic bytes of SURVEY 8d)"
+    if tr is not None and tr < alg_bytes:
+        # the digest layout moves fewer bytes than SURVEY 8d prices (H = 1024: 8-byte digests for 128-byte bit words):
+        # a fraction of algorithmic bytes then flatters the kernel -- the headline fraction prices the measured traffic
+        r_st["frac_algorithmic_bytes_over_roof"] = r_st["frac"]
+        r_st["frac"] = (tr / (st_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if st_ms > 0 else 0.0
+        r_st["frac_basis"] = "measured HBM traffic (below the algorithmic bytes of SURVEY 8d for this layout)"
+    # states above two active latents, level by level (census of the last statistics pass) and what the levels cost
+    lv = {}
+    if all(k in ld for k in ("n_gt2", "n_gt4", "n_gt8")):
+        cnt = {"k3_4": ld["n_gt2"] - ld["n_gt4"], "k5_8": ld["n_gt4"] - ld["n_gt8"], "k9plus": ld["n_gt8"]}
+        for name, n_states in cnt.items():
+            e = {"states": n_states, "fraction_of_K": n_states / (float(n_loc) * cfg["S"])}
+            for pas in ("lpj", "stats"):
+                km = kernel_ms.get("%s_%s" % (pas, name))
+                if km:
+                    e["%s_ms_per_pass" % pas] = km["avg_ms"] * km["launches_per_iteration"]
+            lv[name] = e
+    above2 = {}
+    for pas, span in (("lpj", "lpj_pass"), ("stats", "stats_pass")):
+        tot = kernel_ms.get(span)
+        if tot and lv:
+            t_lv = sum(e.get("%s_ms_per_pass" % pas, 0.0) for e in lv.values())
+            above2[pas] = {"ms_levels": t_lv, "ms_pass": tot["avg_ms"] * tot["launches_per_iteration"],
+                           "fraction_of_pass_above_k2": t_lv / max(1e-12, tot["avg_ms"] * tot["launches_per_iteration"])}
+    out = {
+        "config": {"ms_per_em_iteration_eager_theta": eager_ms,
+                   "eager_theta_note": "the same loop with Theta^new copied to host arrays every iteration, as the reference's "
+                                       "step() returns it (a short second loop after the timed region; not `value`)",
+                   "estep": estep_diag,
+                   "kernel_ms": kernel_ms,
+                   "kernel_ms_note": "per-class HIP-event times from %d extra instrumented iterations after the timed region" % prof_iters},
+        "roofline": r_lpj, "roofline_stats": r_st,
+        "levels": {"by_active_latents": lv, "above_two_latents": above2,
+                   "note": "ES3C states by number of active latents (census lists, one pass over the digests per K^n): "
+                           "per-level HIP-event times from the instrumented iterations after the timed region"},
+    }
+    g = gemm_loop or kernel_ms.get("gemm_f64")
+    if g:
+        t_ms = g["avg_ms"] * g["launches_per_iteration"]
+        gi = kernel_ms.get("gemm_f64")
+        fl_nom = gemm_flops_per_iteration(cfg, n_loc)
+        fl = gemm_flops_per_iteration(cfg, n_loc, executed=True)
+        f32 = bool(cfg.get("f32"))
+        peak = F32_MFMA_PEAK_TFLOPS if f32 else F64_MFMA_PEAK_TFLOPS
+        out["mfma"] = {"kernels": ("gemm_tn128_gk<float> (grouped split-K) / gemm_tn128_sk_f32 / gemm_tn128_store_f32 (v_mfma_f32_16x16x4_f32)" if f32 else
+                                   "gemm_tn128_gk (grouped split-K; gemm_tn128_sk_f64 where chunks do not fill the grid) / gemm_tn128_rows_f64 / gemm_tn_f64 / gemm_nn_f64 (v_mfma_f64_16x16x4_f64)"),
+                       "flops_per_iteration": fl,
+                       "flops_note": "EXECUTED flops: 2 M N K of every product, the symmetric block of the ES3C contraction "
+                                     "counted with the upper tiles it really runs (34 of 40 tiles at H = 512); "
+                                     "`frac_nominal` prices all tiles",
+                       "slots_note": "the K = N contraction, forked beside the Theta-update chain, runs on 14 (30 at H = 1024) of the 15 (32) K "
+                                     "chunks per tile a full resident grid would hold (option sk_spare, automatic): the product takes ~6 % "
+                                     "longer, the chain hides inside it and the iteration is 2-6 % shorter (DESIGN 3); on all slots "
+                                     "the same kernels reach 0.87 of the peak at the north-star shape",
+                       "ms_per_iteration": t_ms,
+                       "ms_note": "HIP-event spans of the products on the streams they run on, %d iterations after the timed region "
+                                  "with only this class timed (the K = N product forked beside the Theta-update chain as in the "
+                                  "timed loop); `ms_per_iteration_instrumented`: the same products in the fully instrumented "
+                                  "iterations of `kernel_ms` (alone on the main stream between event records)" % prof_iters,
+                       "ms_per_iteration_instrumented": (gi["avg_ms"] * gi["launches_per_iteration"]) if gi else None,
+                       "achieved": fl / (t_ms * 1e-3) / 1e12, "peak": peak, "unit": "TFLOP/s",
+                       "frac": fl / (t_ms * 1e-3) / 1e12 / peak,
+                       "flops_per_iteration_nominal": fl_nom,
+                       "frac_nominal": fl_nom / (t_ms * 1e-3) / 1e12 / peak}
+    if per_rank is not None:
+        out["per_rank"] = per_rank
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -467,7 +700,14 @@ def main():
                     help="draw K^n(0) in this process instead of a worker pool (runs under rocprofv3)")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="evoamd_set_option before the run (A/B of a kernel path, e.g. overlap_gemm=0)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: CPU baseline, roofline spans, per-class kernel "
+                         "times, eager-Theta loop, per-rank view")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # bare `bench.py --gpus N`: this parent never initialises HIP; it only starts the ranks and relays rank 0
         stub = os.environ.get("EVO_AMD_BENCH_WORKER")  # tests: a stand-in rank program (no GPU)
@@ -483,7 +723,7 @@ def main():
 
     # CPU baseline first: it forks worker processes and must run before HIP is initialised
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("CPU baseline (oracle on %d cores, ~%.0f s) ..." % (host_cores(), args.cpu_seconds))
         cpu = cpu_baseline(cfg, args.cpu_seconds)
         log("CPU baseline: %.3g evals/s" % cpu["value"])
@@ -532,10 +772,11 @@ def main():
     F = nu = nsub = None
     for _ in range(args.warmup * iters):
         F, nu, nsub, theta = model.step(theta, suff, my_data)
-    # Timed region: HIP events only around the two roofline spans (every timed span costs ~10 us of stream
-    # time, so the per-kernel classes are measured in a separate instrumented pass below).
-    eng.timing(["lpj_pass", "stats_pass"] + (["allreduce"] if world > 1 else []))
-    eng.timing_reset()
+    if args.full:
+        # Timed region: HIP events only around the two roofline spans (every timed span costs ~10 us of stream
+        # time, so the per-kernel classes are measured in a separate instrumented pass afterwards).
+        eng.timing(["lpj_pass", "stats_pass"] + (["allreduce"] if world > 1 else []))
+        eng.timing_reset()
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps * iters):
@@ -547,153 +788,27 @@ def main():
     if world > 1:
         dt = comm.allreduce_max(dt)
     log("timed region %.3f s" % dt)
-    lpj_ms, lpj_n = eng.kernel_time_ms("lpj_pass")
-    st_ms, st_n = eng.kernel_time_ms("stats_pass")
-    # per-rank view of the timed loop in rank 0's line (a first multi-GPU run must be diagnosable from it): every rank fills
-    # its slot of a zero vector, the sum is the gather
-    per_rank = None
-    if world > 1:
-        ar_ms, ar_n = eng.kernel_time_ms("allreduce")
-        mine = np.zeros((world, 5))
-        mine[rank] = [1e3 * dt_own / (args.steps * iters), lpj_ms, st_ms, ar_ms * (ar_n / max(1.0, float(st_n))), n_loc]
-        allr = comm.allreduce_array(mine)
-        per_rank = {"ms_per_em_iteration_own_queue": [round(v, 5) for v in allr[:, 0]],
-                    "lpj_pass_ms": [round(v, 5) for v in allr[:, 1]], "stats_pass_ms": [round(v, 5) for v in allr[:, 2]],
-                    "allreduce_ms_per_iteration": [round(v, 5) for v in allr[:, 3]], "datapoints": [int(v) for v in allr[:, 4]],
-                    "note": "allreduce_ms_per_iteration = HIP-event span(s) around the RCCL all-reduce(s) of the packed accumulator "
-                            "on each rank's stream: from the rank's own statistics being done to the sum being delivered, i.e. "
-                            "waiting for the slowest rank + the collective; the SMALLEST entry is the closest to the collective "
-                            "itself (the last rank to arrive waits for nobody)"}
-    # the reference's step() returns Theta^new as host arrays every epoch: the same loop with the per-iteration download
-    eager_ms = None
-    if not args.eager_theta and not args.host_mstep:
-        eager_iters = max(10, min(50, args.steps * iters // 4))
-        model.lazy_theta = False
-        for _ in range(3):
-            F2, nu2, nsub2, theta = model.step(theta, suff, my_data)
-        barrier()
-        t1 = time.perf_counter()
-        for _ in range(eager_iters):
-            F2, nu2, nsub2, theta = model.step(theta, suff, my_data)
-        barrier()
-        eager_ms = 1e3 * (time.perf_counter() - t1) / eager_iters
-        if world > 1:
-            eager_ms = comm.allreduce_max(eager_ms)
-        model.lazy_theta = True
-        F2, nu2, nsub2, theta = model.step(theta, suff, my_data)
-    n_gt2 = float(getattr(model, "last_dpar", {}).get("n_gt2", float("nan")))
-    F_timed, nu_timed, nsub_timed = F, nu, nsub
-    # instrumented pass (not part of `value`): per-class device time of a few more iterations
-    prof_iters = 5
-    eng.timing(True)
-    eng.timing_reset()
-    for _ in range(prof_iters):
-        _F, _nu, _nsub, theta = model.step(theta, suff, my_data)
-    barrier()
-    kernel_ms = {}
-    for name in ("lpj_resident", "lpj_candidates", "lpj_overflow", "row_lse", "vary_kn", "stats", "stats_overflow",
-                 "gemm_f64", "evolve", "misc", "mstep_device", "lpj_pass", "stats_pass", "lpj_k3_4", "lpj_k5_8", "lpj_k9plus",
-                 "stats_k3_4", "stats_k5_8", "stats_k9plus", "estep_fused", "allreduce"):
-        avg, n = eng.kernel_time_ms(name)
-        if n:
-            kernel_ms[name] = {"avg_ms": round(avg, 6), "launches_per_iteration": n / prof_iters}
-    # the contractions once more with ONLY their own class timed: the K = N product then runs forked beside the
-    # Theta-update chain exactly as in the timed loop (the fully instrumented pass above runs it alone on the main stream,
-    # between event records that idle the GPU), its span recorded on the stream it runs on
-    eng.timing(["gemm_f64"])
-    eng.timing_reset()
-    for _ in range(prof_iters):
-        _F, _nu, _nsub, theta = model.step(theta, suff, my_data)
-    barrier()
-    g_avg, g_n = eng.kernel_time_ms("gemm_f64")
-    gemm_loop = {"avg_ms": round(g_avg, 6), "launches_per_iteration": g_n / prof_iters} if g_n else None
-    eng.timing(False)
-    F, nu, nsub = F_timed, nu_timed, nsub_timed
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(args.dump_outputs, eng, F, nu, nsub, theta)
+        log("outputs of the last timed step: %d arrays in %s" % (len(names), args.dump_outputs))
+    full = None
+    if args.full:
+        full = full_measurements(args, cfg, eng, comm, model, theta, suff, my_data, barrier, world, rank, n_loc, iters,
+                                 dt_own)
 
-    estep_diag = eng.estep_counters() if cfg["algo"] == "es3c" else None
     if rank == 0:
         total_iters = args.steps * iters
         evals = float(cfg["N"]) * cfg["S"] * total_iters
-        alg_bytes = algorithmic_bytes_pass(cfg, n_loc)  # per launch = this rank's shard
-        lay_bytes = layout_bytes_lpj(cfg, n_loc)
-
-        def roof(ms, launches, kernels, what):
-            ach = (alg_bytes / (ms * 1e-3) / 1e9) if ms > 0 else 0.0
-            return {"bound": "hbm", "kernel": what, "kernels_in_span": kernels,
-                    "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                    "traffic": pmc_traffic(traffic_key(args), kernels),
-                    "traffic_note": "HBM bytes per pass, rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes, read "
-                                    "side corrected for gfx950 (2 x FETCH_SIZE: an upper bound for kernels whose loads are 8 bytes per lane), "
-                                    "summed over the kernels of the span; counters of this workload from "
-                                    + str(getattr(pmc_traffic, "source", None)),
-                    "algorithmic_bytes_per_launch": alg_bytes,
-                    "algorithmic_bytes_note": "SURVEY 8d: N_rank x (D*8 + S*(ceil(H/8) + 8)), states priced bit-packed",
-                    "avg_launch_ms": ms, "launches_timed": launches}
-
-        r_lpj = roof(lpj_ms, lpj_n, pass_kernels(cfg), "whole pass over the resident K^n: lpj of all N x S states "
-                     "(main kernel + every overflow level it spawns), one HIP-event span per pass")
-        r_lpj["states_in_main_kernel"] = (1.0 - n_gt2 / (float(n_loc) * cfg["S"])) if n_gt2 == n_gt2 else None
-        ld = getattr(model, "last_dpar", {})
-        r_lpj["overflow_census"] = {k: ld.get(k) for k in ("n_gt2", "n_gt4", "n_gt8") if k in ld}
-        r_lpj["layout_bytes_per_launch"] = lay_bytes
-        r_lpj["frac_of_layout_bytes"] = (lay_bytes / (lpj_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if lpj_ms > 0 else 0.0
-        r_lpj["layout_note"] = ("`achieved` / `frac` price SURVEY 8d's algorithmic bytes (bit-packed states + y_n); the kernels "
-                                "read an 8-byte digest per state and the row of B = Y W instead: frac_of_layout_bytes prices that")
-        if r_lpj["frac"] > 1.0:
-            # at large H the digest layout moves fewer bytes than SURVEY 8d prices: a fraction above 1 says nothing
-            # about the kernel, so the headline fraction becomes the layout one and the other keeps its own name
-            r_lpj["frac_algorithmic_bytes_over_roof"] = r_lpj["frac"]
-            r_lpj["frac"] = r_lpj["frac_of_layout_bytes"]
-            r_lpj["frac_basis"] = "layout bytes (algorithmic-byte pricing exceeds the roof for this layout)"
-        r_st = roof(st_ms, st_n, stats_kernels(cfg), "whole statistics pass over the resident K^n (scatter kernel + overflow "
-                    "levels + column sums + finish; the MFMA contraction is priced under `mfma`)")
-        tr = r_st.get("traffic")
-        lay_st = layout_bytes_stats(cfg, n_loc)
-        r_st["layout_bytes_per_launch"] = lay_st
-        r_st["frac_of_layout_bytes"] = (lay_st / (st_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if st_ms > 0 else 0.0
-        if tr is None and lay_st < alg_bytes:
-            # no counters for this workload and the layout moves fewer bytes than SURVEY 8d prices: the algorithmic-byte
-            # fraction would flatter the kernel (c5 float32 mode: 0.99) -- the headline fraction prices the layout bytes
-            r_st["frac_algorithmic_bytes_over_roof"] = r_st["frac"]
-            r_st["frac"] = r_st["frac_of_layout_bytes"]
-            r_st["frac_basis"] = "layout bytes (no PMC counters committed for this workload; below the algorithmic bytes of SURVEY 8d)"
-        if tr is not None and tr < alg_bytes:
-            # the digest layout moves fewer bytes than SURVEY 8d prices (H = 1024: 8-byte digests for 128-byte bit words):
-            # a fraction of algorithmic bytes then flatters the kernel -- the headline fraction prices the measured traffic
-            r_st["frac_algorithmic_bytes_over_roof"] = r_st["frac"]
-            r_st["frac"] = (tr / (st_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if st_ms > 0 else 0.0
-            r_st["frac_basis"] = "measured HBM traffic (below the algorithmic bytes of SURVEY 8d for this layout)"
-        # states above two active latents, level by level (census of the last statistics pass) and what the levels cost
-        lv = {}
-        if all(k in ld for k in ("n_gt2", "n_gt4", "n_gt8")):
-            cnt = {"k3_4": ld["n_gt2"] - ld["n_gt4"], "k5_8": ld["n_gt4"] - ld["n_gt8"], "k9plus": ld["n_gt8"]}
-            for name, n_states in cnt.items():
-                e = {"states": n_states, "fraction_of_K": n_states / (float(n_loc) * cfg["S"])}
-                for pas in ("lpj", "stats"):
-                    km = kernel_ms.get("%s_%s" % (pas, name))
-                    if km:
-                        e["%s_ms_per_pass" % pas] = km["avg_ms"] * km["launches_per_iteration"]
-                lv[name] = e
-        above2 = {}
-        for pas, span in (("lpj", "lpj_pass"), ("stats", "stats_pass")):
-            tot = kernel_ms.get(span)
-            if tot and lv:
-                t_lv = sum(e.get("%s_ms_per_pass" % pas, 0.0) for e in lv.values())
-                above2[pas] = {"ms_levels": t_lv, "ms_pass": tot["avg_ms"] * tot["launches_per_iteration"],
-                               "fraction_of_pass_above_k2": t_lv / max(1e-12, tot["avg_ms"] * tot["launches_per_iteration"])}
         out = {
             "metric": "E-step candidate-state evals/sec (NxS), full EM iteration", "value": evals / dt,
             "unit": "state evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * dt / max(1, args.steps), "higher_is_better": True,
+            "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None, "dtype": "f32 data + contractions, f64 lpj / sums" if cfg.get("f32") else "f64",
             "data": "synthetic",
             "config": {"workload": cfg["name"], "algo": cfg["algo"], "N_total": cfg["N"], "N_rank0": n_loc,
                        "D": cfg["D"], "H": cfg["H"], "S": cfg["S"],
                        "step": "%d full EM iterations" % iters, "em_iterations_per_step": iters,
                        "em_iterations_timed": total_iters, "ms_per_em_iteration": 1e3 * dt / total_iters,
-                       "ms_per_em_iteration_eager_theta": eager_ms,
-                       "eager_theta_note": "the same loop with Theta^new copied to host arrays every iteration, as the reference's "
-                                           "step() returns it (a short second loop after the timed region; not `value`)",
                        "timed_region_s": dt, "world_size_rccl": comm.size,
                        "ea": "fit/randflip 10 parents x 1 child x 1 gen",
                        "states": "p_init_Kn=8/H (dense stress variant)" if args.dense_states else "p_init_Kn=1/H (init_states default)",
@@ -701,45 +816,11 @@ def main():
                        "theta": "eager (host copy every iteration)" if args.eager_theta else
                                 "lazy view (resident on the device; downloaded when read, never in the timed loop)",
                        "sharding": "np.array_split over N (evo/utils/parallel.py:102-112), one packed RCCL all-reduce per iteration",
-                       "free_energy_last": F, "S_nunique_last": nu, "S_sub_last": nsub, "setup_s": round(t_setup, 1),
-                       "estep": estep_diag,
-                       "kernel_ms": kernel_ms,
-                       "kernel_ms_note": "per-class HIP-event times from %d extra instrumented iterations after the timed region" % prof_iters},
-            "roofline": r_lpj, "roofline_stats": r_st,
-            "levels": {"by_active_latents": lv, "above_two_latents": above2,
-                       "note": "ES3C states by number of active latents (census lists, one pass over the digests per K^n): "
-                               "per-level HIP-event times from the instrumented iterations after the timed region"},
+                       "free_energy_last": F, "S_nunique_last": nu, "S_sub_last": nsub, "setup_s": round(t_setup, 1)},
         }
-        g = gemm_loop or kernel_ms.get("gemm_f64")
-        if g:
-            t_ms = g["avg_ms"] * g["launches_per_iteration"]
-            gi = kernel_ms.get("gemm_f64")
-            fl_nom = gemm_flops_per_iteration(cfg, n_loc)
-            fl = gemm_flops_per_iteration(cfg, n_loc, executed=True)
-            f32 = bool(cfg.get("f32"))
-            peak = F32_MFMA_PEAK_TFLOPS if f32 else F64_MFMA_PEAK_TFLOPS
-            out["mfma"] = {"kernels": ("gemm_tn128_gk<float> (grouped split-K) / gemm_tn128_sk_f32 / gemm_tn128_store_f32 (v_mfma_f32_16x16x4_f32)" if f32 else
-                                       "gemm_tn128_gk (grouped split-K; gemm_tn128_sk_f64 where chunks do not fill the grid) / gemm_tn128_rows_f64 / gemm_tn_f64 / gemm_nn_f64 (v_mfma_f64_16x16x4_f64)"),
-                           "flops_per_iteration": fl,
-                           "flops_note": "EXECUTED flops: 2 M N K of every product, the symmetric block of the ES3C contraction "
-                                         "counted with the upper tiles it really runs (34 of 40 tiles at H = 512); "
-                                         "`frac_nominal` prices all tiles",
-                           "slots_note": "the K = N contraction, forked beside the Theta-update chain, runs on 14 (30 at H = 1024) of the 15 (32) K "
-                                         "chunks per tile a full resident grid would hold (option sk_spare, automatic): the product takes ~6 % "
-                                         "longer, the chain hides inside it and the iteration is 2-6 % shorter (DESIGN 3); on all slots "
-                                         "the same kernels reach 0.87 of the peak at the north-star shape",
-                           "ms_per_iteration": t_ms,
-                           "ms_note": "HIP-event spans of the products on the streams they run on, %d iterations after the timed region "
-                                      "with only this class timed (the K = N product forked beside the Theta-update chain as in the "
-                                      "timed loop); `ms_per_iteration_instrumented`: the same products in the fully instrumented "
-                                      "iterations of `kernel_ms` (alone on the main stream between event records)" % prof_iters,
-                           "ms_per_iteration_instrumented": (gi["avg_ms"] * gi["launches_per_iteration"]) if gi else None,
-                           "achieved": fl / (t_ms * 1e-3) / 1e12, "peak": peak, "unit": "TFLOP/s",
-                           "frac": fl / (t_ms * 1e-3) / 1e12 / peak,
-                           "flops_per_iteration_nominal": fl_nom,
-                           "frac_nominal": fl_nom / (t_ms * 1e-3) / 1e12 / peak}
-        if per_rank is not None:
-            out["per_rank"] = per_rank
+        if full is not None:
+            out["config"].update(full.pop("config"))
+            out.update(full)
         if cpu is not None:
             out["cpu_baseline"] = cpu
         print(json.dumps(out))
@@ -748,7 +829,6 @@ def main():
         comm.Barrier()
         comm.close()
     eng.close()
-
 
 if __name__ == "__main__":
     main()

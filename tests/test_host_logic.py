@@ -451,6 +451,58 @@ def test_autotable_numpy_container_flushes_and_warns(tmp_path):
     np.testing.assert_array_equal(np.load(tmp_path / "t.npz")["F"], [0.0, 1.0, 2.0, 3.0, 4.0])
 
 
+class _FakeResidentEngine:
+    """What bench.dump_outputs reads of an Engine: geometry, lpj and packed K^n rows."""
+
+    def __init__(self, N, S, H, seed=0):
+        rs = np.random.RandomState(seed)
+        self.N, self.S, self.H, self.S_perm, self.L = N, S, H, 0, S
+        self.packed = rs.randint(0, 256, size=(N, S, (H + 7) // 8)).astype(np.uint8)
+        self.lpj = rs.normal(size=(N, S))
+
+    def download_lpj(self):
+        return self.lpj.copy()
+
+    def download_states_packed(self, n0=0, n=None):
+        return self.packed[n0:n0 + (self.N - n0 if n is None else n)].copy()
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR`: step()'s scalars, every numeric Theta entry and a fixed sample of K^n / lpj as
+    float .npy files within the size budget; the same for the same engine contents whatever the order of the states."""
+    import bench
+    N, S, H = 5000, 200, 512
+    eng = _FakeResidentEngine(N, S, H)
+    theta = {"W": np.arange(6.0).reshape(2, 3), "pies": np.full(3, 0.1, dtype=np.float32), "sigma2": np.float64(2.0),
+             "note": "not numeric"}
+    names = bench.dump_outputs(str(tmp_path / "a"), eng, -1.5, 3.0, 2.0, theta)
+    assert set(names) == {"free_energy", "S_nunique", "S_sub", "theta_W", "theta_pies", "theta_sigma2",
+                          "Kn_sample", "lpj_sample", "Kn_sample_rows"}
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(os.path.getsize(tmp_path / "a" / (n + ".npy")) for n in names) <= 64 * 10 ** 6
+    assert float(got["free_energy"]) == -1.5 and got["theta_pies"].dtype == np.float32
+    rows = got["Kn_sample_rows"].astype(np.int64)
+    assert 1 <= rows.size < N and np.all(np.diff(rows) > 0)
+    ss, lpj = got["Kn_sample"], got["lpj_sample"]
+    assert ss.shape == (rows.size, S, H) and lpj.shape == (rows.size, S)
+    for i, n in enumerate(rows[:5]):
+        # the states of a datapoint in canonical order, each still paired with its own lpj
+        want = unpack_bits(eng.packed[n], H)
+        pos = {want[s].tobytes(): s for s in range(S)}
+        for s in range(S):
+            assert lpj[i, s] == eng.lpj[n, pos[ss[i, s].astype(bool).tobytes()]]
+        keys = [tuple(r) for r in np.packbits(ss[i].astype(bool), axis=-1)]
+        assert keys == sorted(keys)
+    # the device may hold a datapoint's states in another order: the files do not change
+    for n in range(N):
+        p = np.random.RandomState(n).permutation(S)
+        eng.packed[n], eng.lpj[n] = eng.packed[n][p], eng.lpj[n][p]
+    bench.dump_outputs(str(tmp_path / "b"), eng, -1.5, 3.0, 2.0, theta)
+    for n in names:
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / (n + ".npy")), got[n], err_msg=n)
+
+
 def test_bench_host_cores_respects_cgroup_quota():
     import bench
     n = bench.host_cores()

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 CFG=$1; REP=$2; STEPS=$3; shift 3
 for r in $(seq 1 $REP); do
   for set in "$@"; do
-    args=""
+    args="--full"  # kernel_ms is a --full entry
     if [ "$set" != "-" ]; then for o in $set; do args="$args --option $o"; done; fi
     python3 $R/bench.py --config $CFG --steps $STEPS --warmup 5 --no-cpu-baseline $args 2> /dev/null | python3 -c "
 import json,sys

@@ -19,8 +19,8 @@ rm -rf $OUT
 mkdir -p $OUT
 cd /tmp
 TS=${TRACE_STEPS:-25}
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --config $CFG --steps $TS --warmup 1 --em-per-step 10 --no-cpu-baseline --inprocess-init "$@" > $OUT/bench_trace.json 2> $OUT/trace.log
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 $R/bench.py --config $CFG --steps 2 --warmup 1 --em-per-step 3 --no-cpu-baseline --inprocess-init "$@" > $OUT/bench_fetch.json 2> $OUT/fetch.log
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 $R/bench.py --config $CFG --steps 2 --warmup 1 --em-per-step 3 --no-cpu-baseline --inprocess-init "$@" > $OUT/bench_write.json 2> $OUT/write.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --config $CFG --steps $TS --warmup 1 --em-per-step 10 --full --no-cpu-baseline --inprocess-init "$@" > $OUT/bench_trace.json 2> $OUT/trace.log
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 $R/bench.py --config $CFG --steps 2 --warmup 1 --em-per-step 3 --full --no-cpu-baseline --inprocess-init "$@" > $OUT/bench_fetch.json 2> $OUT/fetch.log
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 $R/bench.py --config $CFG --steps 2 --warmup 1 --em-per-step 3 --full --no-cpu-baseline --inprocess-init "$@" > $OUT/bench_write.json 2> $OUT/write.log
 python3 $R/tools/summarize_prof.py $OUT > $OUT/summary.md
 head -60 $OUT/summary.md

@@ -2,6 +2,7 @@
 # default-length bench of one config with the per-class kernel times printed: tools/quick_bench.sh <config> <tag> [bench options...]
 R=${GRAFT_REPO_ROOT:-/root/repo}
 CFG=${1:-c4}; TAG=${2:-q}; shift 2
+set -- --full "$@"  # the kernel_ms and roofline entries printed below are --full ones
 python3 $R/bench.py --config $CFG --steps 20 --warmup 5 --no-cpu-baseline "$@" > $R/gpurun_out/qb_${TAG}.json 2> $R/gpurun_out/qb_${TAG}.log || { tail -5 $R/gpurun_out/qb_${TAG}.log; exit 1; }
 python3 - $R/gpurun_out/qb_${TAG}.json <<'PY'
 import json, sys
