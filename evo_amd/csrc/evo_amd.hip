@@ -200,6 +200,8 @@ struct evoamd_ctx {
                        // state leaves 10..28 pairs per state: the dense bench asks for 12 = 7.7 GB at the north-star shape)
   int bins_scale_cur = 0;  // what the bins are allocated for right now (ensure_bins_capacity re-cuts them when K^n densifies)
   int bins_auto = 1;       // option "pair_bins_auto": grow the bins from the census of the last statistics pass
+  bool bins_dirty = false;  // a binned producer was enqueued and the reduce kernel that zeroes pbins.gcnt was not (a pass
+                            // that returned part-way): the next pass clears the region counters before it appends
   int bins_nwg = 2048;  // option "pair_bins_nwg" (read by evoamd_configure): producer workgroups = private regions per bin
   int bsc_wave_opt = 1;  // option "bsc_stats_wave": EBSC statistics on the wave-per-datapoint kernel (0: round-1 kernel)
   int gemm_ws_opt = 1;  // option "gemm_workspace": stream-K partial tiles through a workspace + reduce kernel (0: f64 atomics)
@@ -360,6 +362,8 @@ struct evoamd_ctx {
   bool reduce_pending = false;  // fused E-step: rowF / rowcnt not yet summed into the scalar block (fused_reduce3_kernel)
   long fused_calls = 0, unfused_calls = 0;
   int debug_poison_list = 0;  // option "debug_poison_list" (tests): the next census gets an out-of-range entry
+  int debug_fail_stats = 0;   // option "debug_fail_stats" (tests): the next statistics pass (ES3C, complete data) returns
+                              // after its main kernel; any other pass disarms it
   int census_skip = 0;  // levels that passes over the CURRENT census did not launch (checked when it is rebuilt)
   size_t list_words = 0;  // capacity of each overflow list (ints)
   // scratch for single / shared evaluations
@@ -758,6 +762,10 @@ extern "C" int evoamd_set_option(evoamd_ctx *c, const char *name, int value) {
     c->debug_poison_list = value != 0;
     return 0;
   }
+  if (strcmp(name, "debug_fail_stats") == 0) {
+    c->debug_fail_stats = value != 0;
+    return 0;
+  }
   if (strcmp(name, "state_digest") == 0) {
     c->use_digest = value != 0;
     return 0;
@@ -846,6 +854,7 @@ static int alloc_pair_bins(evoamd_ctx *c, int scale) {
       HIP_TRY(hipMemsetAsync(pb.gcnt, 0, (size_t)pb.nb * pb.nwg * sizeof(int), c->stream));
       c->pbins = pb;
       c->bins_scale_cur = scale;
+      c->bins_dirty = false;
     } else {
       (void)hipGetLastError();
       if (pb.ent) (void)hipFree(pb.ent);
@@ -1879,6 +1888,14 @@ static unsigned quad_grid(const evoamd_ctx *c, int level, int tag, i64 total, un
   return level_grid(c, level, tag, total * 4, cap, 64);
 }
 
+// A producer kernel that appends to the pair bins owns region (bin, blockIdx.x) of every bin and counter
+// gcnt[bin * nwg + blockIdx.x]: its grid must not exceed pb.nwg (the kernels grid-stride, so a smaller grid is correct).
+static unsigned pb_clamp(const PairBins &pb, unsigned grid) {
+  return pb.ent && grid > (unsigned)pb.nwg ? (unsigned)pb.nwg : grid;
+}
+#define PB_GRID_CHECK(pb, grid) \
+  REQUIRE(!(pb).ent || (i64)(grid) <= (i64)(pb).nwg, "pair bins: producer grid exceeds the regions per bin (pb.nwg)")
+
 #define MAIN_LPJ_LDS_MAX (48 * 1024)  // three 512-thread workgroups (3072 pairs) per CU at the limit
 
 template <int TAG>
@@ -2789,6 +2806,12 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
     int rb = ensure_bins_capacity(c);
     if (rb) return rb;
   }
+  if (c->bins_dirty && c->pbins.gcnt)  // an earlier pass returned between its producers and the reduce: stale region counts
+    HIP_TRY(hipMemsetAsync(c->pbins.gcnt, 0, (size_t)c->pbins.nb * c->pbins.nwg * sizeof(int), c->stream));
+  c->bins_dirty = false;
+  // test hook: consumed by every pass (it stops only an ES3C pass on complete data, after its main kernel)
+  const bool debug_fail = c->debug_fail_stats != 0;
+  c->debug_fail_stats = 0;
   const AccLayout a = acc_layout(c);
   const i64 N = c->N;
   const int H = c->H, D = c->D;
@@ -2910,6 +2933,8 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
         int sgrid = (int)std::min<i64>(cdiv(nc, 4), (i64)c->n_cu * per_cu * 2);
         if (sgrid > 2048) sgrid = 2048;  // the size of the sigma partials
         if (bsc_pb.ent && sgrid > bsc_pb.nwg) sgrid = bsc_pb.nwg;  // one private region per producer workgroup and bin
+        PB_GRID_CHECK(bsc_pb, sgrid);
+        if (bsc_pb.ent) c->bins_dirty = true;
         bsc_grid = sgrid;
         void *EsP = c->f32 ? (void *)c->Esf : (void *)c->Es;
         double *csb = c->acc_base + 4;
@@ -2931,6 +2956,7 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
           pair_bins_reduce_kernel<<<bsc_pb.nb * bsc_pb.nsh, PB_RTHREADS, (size_t)3 * 2 * bsc_pb.rf * H * sizeof(double), c->stream>>>(
               bsc_pb, H, 0);
           HIP_TRY(hipGetLastError());
+          c->bins_dirty = false;
         }
       } else {
       {
@@ -3007,6 +3033,7 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
       sc.Ed = sa.Ed + (size_t)n0 * sa.ldE;
       sc.N = nc;
       const i64 total = nc * (i64)c->S;
+      if (pb.ent) c->bins_dirty = true;  // this block's producers append; until its reduce (which zeroes the counters)
       if (ci > 0) {  // the previous block's overflow census joins the running sum; fresh lists for this block
         census_lists_kernel<<<1, 256, 0, c->stream>>>(c->list_n, LIST_SHARDS, skip_mask(need), c->err, c->census);
         HIP_TRY(hipGetLastError());
@@ -3045,11 +3072,15 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
           // (the bins' region counters are zero here: pair_bins_reduce_kernel clears what it reads)
           if (need[0]) {
             SpanGuard gl(c, KID_STATS_K34);
-            sssc_quad_kernel<1, 1, 2><<<quad_grid(c, 0, tg, total, gcap), 256, dl, c->stream>>>(sc, cA, none_out, o3, pb, c->ovf_rec);
+            const unsigned qg = quad_grid(c, 0, tg, total, gcap);
+            PB_GRID_CHECK(pb, qg);
+            sssc_quad_kernel<1, 1, 2><<<qg, 256, dl, c->stream>>>(sc, cA, none_out, o3, pb, c->ovf_rec);
           }
           if (need[1] && !few4) {
             SpanGuard gl(c, KID_STATS_K58);
-            sssc_quad_kernel<2, 1, 2><<<quad_grid(c, 1, tg, total, gcap), 256, dl, c->stream>>>(sc, cB, none_out, o3, pb, c->ovf_rec);
+            const unsigned qg = quad_grid(c, 1, tg, total, gcap);
+            PB_GRID_CHECK(pb, qg);
+            sssc_quad_kernel<2, 1, 2><<<qg, 256, dl, c->stream>>>(sc, cB, none_out, o3, pb, c->ovf_rec);
           }
           HIP_TRY(hipGetLastError());
           DBG_SYNC(c, "sssc stats quad levels");
@@ -3059,6 +3090,7 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
         SpanGuard g(c, KID_STATS);
         int fgrid = (int)std::min<i64>(cdiv(nc, flatG), (i64)c->n_cu);
         if (pb.ent && fgrid > pb.nwg) fgrid = pb.nwg;
+        PB_GRID_CHECK(pb, fgrid);
         sssc_stats_flat_kernel<<<fgrid, FLAT_T, flat_lds, c->stream>>>(sc, pb, c->ovf_rec, flatG);
         HIP_TRY(hipGetLastError());
         DBG_SYNC(c, "sssc stats main (flat)");
@@ -3084,6 +3116,7 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
         // doubles the kernel's critical path at small N), a persistent grid-stride loop beyond
         int sgrid = (int)std::min<i64>(cdiv(nc, Wv), (i64)c->n_cu * per_cu * 4);
         if (pb.ent && sgrid > pb.nwg) sgrid = pb.nwg;  // one private region per producer workgroup and bin
+        PB_GRID_CHECK(pb, sgrid);
 #define STATS_WAVE(HWT)                                                                                  \
   do {                                                                                                   \
     if (census)                                                                                          \
@@ -3114,6 +3147,8 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
         HIP_TRY(hipGetLastError());
         DBG_SYNC(c, "sssc stats main");
       }
+      if (debug_fail)  // test hook: a pass that returns between its producers and the pair-bin reduce
+        return fail(EVOAMD_E_INVALID, "debug_fail_stats: statistics pass stopped after its main kernel");
       if (census) {
         if (need[0] || need[1] || need[2]) {  // resident states above eight latents + what the quads passed on (atomics)
           SpanGuard g(c, KID_STATS_OVF);
@@ -3141,14 +3176,20 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
         const int tg = c->cand_from_device ? 1 : 2;  // how much is known about the final K^n
         const size_t cs_lds = sc.cs ? (size_t)3 * H * sizeof(double) : 0;  // in-kernel column sums (LDS)
         bool merged23 = false;
-        if (need[0])
-          sssc_small_kernel<4, 1, 2, 256><<<level_grid(c, 0, tg, total, 1024, 256), 256, cs_lds, c->stream>>>(sc, i1, o2, pb, o3);
+        if (need[0]) {
+          const unsigned g4 = pb_clamp(pb, level_grid(c, 0, tg, total, 1024, 256));
+          PB_GRID_CHECK(pb, g4);
+          sssc_small_kernel<4, 1, 2, 256><<<g4, 256, cs_lds, c->stream>>>(sc, i1, o2, pb, o3);
+        }
         // (statistics mode of the K = 8 register kernel: 256 registers + 736 bytes of scratch per lane, one wave per
         // SIMD -- measured slower than the wavefront kernel at every size seen: 187 vs ~110 us at 5k states, 0.32
         // vs 0.25 ms for the pass's levels at the north-star shape; only when forced by option "sssc_k8" = 1)
         if (c->k8_mode == 1) {
-          if (need[1])
-            sssc_small_kernel<8, 1, 2, 256><<<level_grid(c, 1, tg, total, 256, 256), 256, cs_lds, c->stream>>>(sc, i2, o3, pb, o3);
+          if (need[1]) {
+            const unsigned g8 = pb_clamp(pb, level_grid(c, 1, tg, total, 256, 256));
+            PB_GRID_CHECK(pb, g8);
+            sssc_small_kernel<8, 1, 2, 256><<<g8, 256, cs_lds, c->stream>>>(sc, i2, o3, pb, o3);
+          }
         } else if (need[1] && few_dense_states(c, tg)) {
           sssc_big_kernel<1><<<level_grid(c, 1, tg, total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
               sc, i2, none_out, SSSC_KCAP, i3);  // one launch for both wavefront levels (see launch_sssc_lpj)
@@ -3174,6 +3215,7 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
         SpanGuard g(c, KID_STATS);
         pair_bins_reduce_kernel<<<pb.nb * pb.nsh, PB_RTHREADS, (size_t)3 * 2 * pb.rf * H * sizeof(double), c->stream>>>(pb, H, ci > 0);
         HIP_TRY(hipGetLastError());
+        c->bins_dirty = false;
         DBG_SYNC(c, "pair bins reduce");
       }
       // a skipped level must have found its input list empty (census_lists_kernel / tail_kernel check)

@@ -171,7 +171,10 @@ int evoamd_synchronize(evoamd_ctx *ctx);
  * shape (the chain is bound by vector-instruction issue and per-wave latency, not by the HBM bytes fusion saves: DESIGN 3).
  * "debug_poison_list" (one-shot, tests): the next census of the resident K^n gets an out-of-range entry.  Every list entry
  * and every latent index that crosses LDS is range-checked before it becomes an address, so the pass that reads the entry
- * ends in EVOAMD_E_INVALID ("... out of range") instead of a memory fault; the census is rebuilt afterwards. */
+ * ends in EVOAMD_E_INVALID ("... out of range") instead of a memory fault; the census is rebuilt afterwards.
+ * "debug_fail_stats" (one-shot, tests): the next statistics pass, if it is an ES3C pass on complete data, returns
+ * EVOAMD_E_INVALID right after its main kernel, between the producers that append to the pair bins and the reduce that
+ * clears their counters; the next pass must start from clean bins.  Any statistics pass consumes the option. */
 int evoamd_set_option(evoamd_ctx *ctx, const char *name, int value);
 
 /* ---- problem geometry -------------------------------------------------------------- */
