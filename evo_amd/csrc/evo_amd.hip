@@ -23,6 +23,7 @@
 #include "kernels_sssc.hpp"
 #include "kernels_sssc_quad.hpp"
 #include "kernels_fused.hpp"
+#include "kernels_patches.hpp"
 
 // ---------------------------------------------------------------------------------------
 // error handling
@@ -133,6 +134,7 @@ enum {  // internal kernel ids (see evoamd_kernel_name)
   KID_STATS_K9P,
   KID_ALLREDUCE,    // the RCCL all-reduce(s) of the packed accumulator: local statistics done -> sum delivered
   KID_ESTEP_FUSED,  // the fused per-datapoint E-step kernel (lpj of K^n -> candidates -> their lpj -> vary_Kn -> census)
+  KID_PATCHES,      // overlapping image patches: extract / mean merge / median merge kernels
   KID_COUNT
 };
 
@@ -370,6 +372,9 @@ struct evoamd_ctx {
   double *tmp_y = nullptr, *tmp_lpj = nullptr;
   u64 *tmp_states = nullptr;
   size_t tmp_states_words = 0, tmp_lpj_n = 0;
+  // evoamd_patches_*: image and patch rows on the device, grown on demand (never the EM state above)
+  double *patch_img = nullptr, *patch_Y = nullptr;
+  size_t patch_img_n = 0, patch_Y_n = 0;
   // rccl
   void *comm = nullptr;
   int rank = 0, world = 1;
@@ -573,7 +578,8 @@ static void free_all(evoamd_ctx *c) {
                   c->acc_base, c->Es,     c->list1,   c->list2,    c->list3,    c->list_n,    c->err,
                   c->tmp_y,  c->tmp_lpj, c->tmp_states, c->dig, c->cand_dig, c->lpj_alt, c->cand_raw, c->dupold, c->gen_start,
                   c->pbins.ent, c->pbins.part, c->pbins.gcnt, c->gemm_ws, c->Yt, c->Yf, c->Ytf, c->Wf, c->Bf, c->Esf,
-                  c->clist, c->clist_n, c->ovf_rec, c->theta_bak, c->rowF, c->rowcnt, c->defer, c->fpart, c->huge, c->huge_ctl};
+                  c->clist, c->clist_n, c->ovf_rec, c->theta_bak, c->rowF, c->rowcnt, c->defer, c->fpart, c->huge, c->huge_ctl,
+                  c->patch_img, c->patch_Y};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (c->h_acc) (void)hipHostFree(c->h_acc);
@@ -4005,6 +4011,81 @@ extern "C" int evoamd_free_energy(evoamd_ctx *c, const double *lpj, int64_t N, i
 }
 
 // ---------------------------------------------------------------------------------------
+// overlapping image patches (kernels_patches.hpp): own scratch, no EM state touched
+// ---------------------------------------------------------------------------------------
+static int ensure_patch_scratch(evoamd_ctx *c, size_t img_n, size_t y_n) {
+  if (img_n > c->patch_img_n) {
+    ALLOC(c->patch_img, img_n);
+    c->patch_img_n = img_n;
+  }
+  if (y_n > c->patch_Y_n) {
+    ALLOC(c->patch_Y, y_n);
+    c->patch_Y_n = y_n;
+  }
+  return 0;
+}
+
+extern "C" int evoamd_patches_extract(evoamd_ctx *c, const double *img, int H, int W, int C, int ph, int pw, int shift,
+                                      double *Y_out) {
+  REQUIRE(c && img && Y_out, "evoamd_patches_extract: NULL argument");
+  PatchGeom g;
+  if (const char *msg = patch_geom_make(H, W, C, ph, pw, shift, &g)) return fail(EVOAMD_E_INVALID, "evoamd_patches_extract: %s", msg);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t img_n = (size_t)H * W * C, y_n = (size_t)g.N * g.D;
+  int r = ensure_patch_scratch(c, img_n, y_n);
+  if (r) return r;
+  HIP_TRY(hipMemcpyAsync(c->patch_img, img, img_n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  {
+    SpanGuard sg(c, KID_PATCHES);
+    const i64 blocks = (i64)((y_n + 255) / 256);
+    patches_extract_kernel<<<(unsigned)(blocks < 65536 ? blocks : 65536), 256, 0, c->stream>>>(c->patch_img, g, c->patch_Y);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(Y_out, c->patch_Y, y_n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+extern "C" int evoamd_patches_merge(evoamd_ctx *c, const double *Y, int H, int W, int C, int ph, int pw, int shift,
+                                    int method, double *img_out) {
+  REQUIRE(c && Y && img_out, "evoamd_patches_merge: NULL argument");
+  PatchGeom g;
+  if (const char *msg = patch_geom_make(H, W, C, ph, pw, shift, &g)) return fail(EVOAMD_E_INVALID, "evoamd_patches_merge: %s", msg);
+  REQUIRE(method == 0 || method == 1, "evoamd_patches_merge: method must be 0 (mean) or 1 (median)");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t img_n = (size_t)H * W * C, y_n = (size_t)g.N * g.D;
+  int r = ensure_patch_scratch(c, img_n, y_n);
+  if (r) return r;
+  HIP_TRY(hipMemcpyAsync(c->patch_Y, Y, y_n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  {
+    SpanGuard sg(c, KID_PATCHES);
+    if (method == 0) {
+      patches_mean_kernel<<<cdiv((i64)img_n, 256), 256, 0, c->stream>>>(c->patch_Y, g, c->patch_img);
+    } else {
+      const int K = patch_max_cover(g);  // <= ph * pw <= 1024
+      int P = 1;
+      while (P < K) P <<= 1;
+      if (P <= 64) {
+        const i64 waves = ((i64)img_n + 64 / P - 1) / (64 / P);
+        patches_median_kernel<1><<<cdiv(waves, 4), 256, 0, c->stream>>>(c->patch_Y, g, P, c->patch_img);
+      } else {
+        const unsigned blocks = cdiv((i64)img_n, 4);  // one wave per output element
+        switch (P) {
+          case 128: patches_median_kernel<2><<<blocks, 256, 0, c->stream>>>(c->patch_Y, g, P, c->patch_img); break;
+          case 256: patches_median_kernel<4><<<blocks, 256, 0, c->stream>>>(c->patch_Y, g, P, c->patch_img); break;
+          case 512: patches_median_kernel<8><<<blocks, 256, 0, c->stream>>>(c->patch_Y, g, P, c->patch_img); break;
+          default: patches_median_kernel<16><<<blocks, 256, 0, c->stream>>>(c->patch_Y, g, P, c->patch_img); break;
+        }
+      }
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(img_out, c->patch_img, img_n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
 // RCCL
 // ---------------------------------------------------------------------------------------
 extern "C" int evoamd_comm_unique_id(uint8_t id_out[128]) {
@@ -4099,6 +4180,7 @@ extern "C" const char *evoamd_kernel_name(int kid) {
   static const char *names[KID_COUNT] = {"lpj_resident", "lpj_candidates", "lpj_overflow", "row_lse",  "vary_kn",
                                          "stats",        "stats_overflow", "gemm_f64",     "evolve",   "misc", "mstep_device",
                                          "lpj_pass",     "stats_pass",     "lpj_k3_4",     "lpj_k5_8", "lpj_k9plus",
-                                         "stats_k3_4",   "stats_k5_8",     "stats_k9plus", "allreduce",    "estep_fused"};
+                                         "stats_k3_4",   "stats_k5_8",     "stats_k9plus", "allreduce",    "estep_fused",
+                                         "patches"};
   return (kid >= 0 && kid < KID_COUNT) ? names[kid] : "?";
 }

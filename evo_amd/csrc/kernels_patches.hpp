@@ -1,0 +1,215 @@
+// Overlapping image patches: extract an image into patch rows and merge patch rows back into an image by the mean or
+// the median of every pixel's estimates (the image workflows of the reference's examples: image-denoising /
+// image-inpainting main.py, OverlappingPatches.get / set_and_merge with mean_merger / median_merger).
+//
+// Conventions (ours; evo_amd/utils/prepost.py states the same):
+//   image   f64 (H, W, C) row-major, C innermost (C = 1 for grey images).
+//   tops    0, s, 2s, ... while <= H - ph, plus H - ph appended if that value was not reached (every pixel is covered);
+//           lefts the same with W, pw.  Patch top of grid row i = min(i s, H - ph).
+//   n       = ir * nc + ic, row-major over the (top row, left column) grid; N = nr * nc.
+//   d       = (dy * pw + dx) * C + c; D = ph * pw * C.
+//   mean    the covering estimates summed in increasing n (NaN skipped), divided by their count: bit-identical to
+//           np.nanmean(stack, axis=0) over the NaN-padded (K, H, W[, C]) stack of estimates in increasing n (NumPy adds
+//           the slices of axis 0 one after another).  Adds only: no contraction.
+//   median  bit-identical to np.nanmedian(stack, axis=0): odd count -> the middle value, even -> (lo + hi) / 2.
+//   no valid estimate -> NaN.
+//   limits  ph pw <= 1024, ph <= H, pw <= W, s >= 1.
+#pragma once
+#include "common.hpp"
+
+#define PATCH_MAX_ELEMS 1024  // ph * pw
+
+struct PatchGeom {
+  int H, W, C, ph, pw, s;
+  int nr, nc;  // grid rows / columns
+  int D;       // ph * pw * C
+  i64 N;       // nr * nc
+};
+
+// patch tops along one axis of length L: ceil((L - p) / s) + 1 of them
+__host__ __device__ __forceinline__ int patch_grid_count(int L, int p, int s) { return (L - p) / s + 1 + ((L - p) % s != 0); }
+__host__ __device__ __forceinline__ int patch_top(int i, int L, int p, int s) {
+  const int t = i * s;
+  return t < L - p ? t : L - p;
+}
+// grid indices [lo, hi] of the patches covering coordinate y (tops strictly increase, so every index between covers)
+__host__ __device__ __forceinline__ void patch_cover(int y, int L, int p, int s, int n, int &lo, int &hi) {
+  const int a = y - p + 1;
+  lo = a > 0 ? (a + s - 1) / s : 0;
+  hi = y >= L - p ? n - 1 : y / s;
+}
+
+// Validates the arguments and fills g; returns NULL or a message.
+static inline const char *patch_geom_make(int H, int W, int C, int ph, int pw, int s, PatchGeom *g) {
+  if (H < 1 || W < 1 || C < 1) return "image dimensions H, W, C must be >= 1";
+  if (ph < 1 || pw < 1) return "patch height and width must be >= 1";
+  if (ph > H || pw > W) return "patch larger than the image (ph > H or pw > W)";
+  if (s < 1) return "patch shift must be >= 1";
+  if ((i64)ph * pw > PATCH_MAX_ELEMS) return "ph * pw > 1024 (patches above 32 x 32 elements are not supported)";
+  if ((i64)ph * pw * C > (1 << 30)) return "ph * pw * C too large";
+  g->H = H, g->W = W, g->C = C, g->ph = ph, g->pw = pw, g->s = s;
+  g->nr = patch_grid_count(H, ph, s);
+  g->nc = patch_grid_count(W, pw, s);
+  g->D = ph * pw * C;
+  g->N = (i64)g->nr * g->nc;
+  return nullptr;
+}
+
+// Largest number of estimates of one pixel: (most covering rows) x (most covering columns).
+static inline int patch_max_cover(const PatchGeom &g) {
+  int kr = 0, kc = 0, lo, hi;
+  for (int y = 0; y < g.H; y++) {
+    patch_cover(y, g.H, g.ph, g.s, g.nr, lo, hi);
+    kr = hi - lo + 1 > kr ? hi - lo + 1 : kr;
+  }
+  for (int x = 0; x < g.W; x++) {
+    patch_cover(x, g.W, g.pw, g.s, g.nc, lo, hi);
+    kc = hi - lo + 1 > kc ? hi - lo + 1 : kc;
+  }
+  return kr * kc;
+}
+
+// Y[n, d] = img[top + dy, left + dx, c]: one thread per element of Y (coalesced stores; the image is small and cached).
+__global__ void __launch_bounds__(256) patches_extract_kernel(const double *__restrict__ img, PatchGeom g,
+                                                              double *__restrict__ Y) {
+  const i64 total = g.N * g.D;
+  for (i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (i64)gridDim.x * blockDim.x) {
+    const i64 n = e / g.D;
+    const int d = (int)(e - n * g.D);
+    const int ir = (int)(n / g.nc), ic = (int)(n - (i64)ir * g.nc);
+    const int c = d % g.C, t = d / g.C;
+    const int dy = t / g.pw, dx = t - dy * g.pw;
+    const int y = patch_top(ir, g.H, g.ph, g.s) + dy, x = patch_top(ic, g.W, g.pw, g.s) + dx;
+    Y[e] = img[((i64)y * g.W + x) * g.C + c];
+  }
+}
+
+// Flat index in Y of the estimate of pixel (y, x, c) held by patch (ir, ic).
+__device__ __forceinline__ i64 patch_elem(const PatchGeom &g, int ir, int ic, int y, int x, int c) {
+  const int dy = y - patch_top(ir, g.H, g.ph, g.s), dx = x - patch_top(ic, g.W, g.pw, g.s);
+  return ((i64)ir * g.nc + ic) * g.D + (dy * g.pw + dx) * g.C + c;
+}
+
+// Mean merge: one thread per output element, its estimates summed in increasing n (NumPy's order for axis 0).
+__global__ void __launch_bounds__(256) patches_mean_kernel(const double *__restrict__ Y, PatchGeom g,
+                                                           double *__restrict__ out) {
+#pragma clang fp contract(off)
+  const i64 total = (i64)g.H * g.W * g.C;
+  const i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const int c = (int)(e % g.C);
+  const i64 px = e / g.C;
+  const int y = (int)(px / g.W), x = (int)(px - (i64)y * g.W);
+  int r0, r1, c0, c1;
+  patch_cover(y, g.H, g.ph, g.s, g.nr, r0, r1);
+  patch_cover(x, g.W, g.pw, g.s, g.nc, c0, c1);
+  double sum = 0.0;
+  int cnt = 0;
+  for (int ir = r0; ir <= r1; ir++)
+    for (int ic = c0; ic <= c1; ic++) {
+      const double v = Y[patch_elem(g, ir, ic, y, x, c)];
+      if (v == v) {
+        sum += v;
+        cnt++;
+      }
+    }
+  out[e] = cnt ? sum / (double)cnt : __builtin_nan("");
+}
+
+// Median merge: a bitonic sort of every output element's estimates across the lanes of a wave (and, for more than 64
+// estimates, across R registers per lane: element index = r * 64 + lane).  R = 1: segments of P lanes (P = the power of
+// two >= the largest estimate count, <= 64), 64 / P output elements per wave; R > 1: P = 64 R, one element per wave.
+// NaN and the padding sort as +inf; the count of valid estimates picks the middle ones.  Registers: R doubles per lane.
+template <int R>
+__global__ void __launch_bounds__(256) patches_median_kernel(const double *__restrict__ Y, PatchGeom g, int P,
+                                                             double *__restrict__ out) {
+#pragma clang fp contract(off)
+  const int lane = lane_id();
+  const int seg = R == 1 ? P : 64;  // lanes per output element
+  const int sl = lane % seg;        // lane within the segment
+  const i64 total = (i64)g.H * g.W * g.C;
+  const i64 wave = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const i64 e = wave * (64 / seg) + lane / seg;
+  const bool live = e < total;
+  int y = 0, x = 0, c = 0, r0 = 0, c0 = 0, kc = 1, K = 0;
+  if (live) {
+    c = (int)(e % g.C);
+    const i64 px = e / g.C;
+    y = (int)(px / g.W), x = (int)(px - (i64)y * g.W);
+    int r1, c1;
+    patch_cover(y, g.H, g.ph, g.s, g.nr, r0, r1);
+    patch_cover(x, g.W, g.pw, g.s, g.nc, c0, c1);
+    kc = c1 - c0 + 1;
+    K = (r1 - r0 + 1) * kc;
+  }
+  const double inf = __builtin_inf();
+  double v[R];
+  int nvalid = 0;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int k = r * 64 + sl;
+    double t = inf;
+    bool ok = false;
+    if (k < K) {
+      const int ir = r0 + k / kc, ic = c0 + k % kc;
+      t = Y[patch_elem(g, ir, ic, y, x, c)];
+      ok = t == t;
+      if (!ok) t = inf;
+    }
+    v[r] = t;
+    const u64 segmask = seg == 64 ? ~0ull : (((1ull << seg) - 1) << (lane - sl));
+    nvalid += __popcll(__ballot(ok) & segmask);
+  }
+  // bitonic network over P elements
+  for (int k2 = 2; k2 <= (R == 1 ? P : 64 * R); k2 <<= 1) {
+    for (int j = k2 >> 1; j > 0; j >>= 1) {
+      if (j >= 64) {
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+          const int jr = j >> 6;
+          if (r & jr) continue;
+          const bool asc = ((r * 64) & k2) == 0;
+          // partner register r | jr, selected without a dynamic register index
+#pragma unroll
+          for (int r2 = 0; r2 < R; r2++) {
+            if (r2 != (r | jr)) continue;
+            const double a = v[r], b = v[r2];
+            const bool sw = asc ? (b < a) : (a < b);
+            v[r] = sw ? b : a;
+            v[r2] = sw ? a : b;
+          }
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+          const double p = __shfl_xor(v[r], j, 64);
+          const bool asc = (((r * 64) + sl) & k2) == 0;
+          const bool lower = (sl & j) == 0;
+          const bool keep_min = asc == lower;
+          v[r] = keep_min ? (p < v[r] ? p : v[r]) : (p > v[r] ? p : v[r]);
+        }
+      }
+    }
+  }
+  // sorted element i lives in register i / 64 of lane (segment base + i % 64)
+  const int base = lane - sl;
+  const int ilo = nvalid > 0 ? (nvalid - 1) / 2 : 0, ihi = nvalid / 2;
+  double tlo = v[0], thi = v[0];
+#pragma unroll
+  for (int r = 1; r < R; r++) {
+    if (r == ilo / 64) tlo = v[r];
+    if (r == ihi / 64) thi = v[r];
+  }
+  const double lo = __shfl(tlo, base + ilo % 64, 64);
+  const double hi = __shfl(thi, base + (ihi < (R == 1 ? P : 64 * R) ? ihi : 0) % 64, 64);
+  if (live && sl == 0) {
+    double m;
+    if (nvalid == 0)
+      m = __builtin_nan("");
+    else if (nvalid & 1)
+      m = lo;
+    else
+      m = (lo + hi) / 2.0;
+    out[e] = m;
+  }
+}

@@ -349,6 +349,31 @@ class Engine:
         check(self.lib.evoamd_comm_destroy(self._h))
         self.world, self.rank = 1, 0
 
+    # ---- overlapping image patches (evo_amd.utils.prepost) --------------------------------
+    def patches_extract(self, img, ph, pw, shift=1):
+        """img (H, W) or (H, W, C) -> Y (N, D) float64, the overlapping patches (conventions: evo_amd.utils.prepost)."""
+        from .utils.prepost import patch_geometry
+        img = as_f64(img)
+        H, W, C = _image_hwc(img.shape)
+        N, D = patch_geometry(H, W, C, ph, pw, shift)
+        Y = np.empty((N, D), dtype=np.float64)
+        check(self.lib.evoamd_patches_extract(self._h, dptr(img), H, W, C, int(ph), int(pw), int(shift), dptr(Y)))
+        return Y
+
+    def patches_merge(self, Y, shape, ph, pw, shift=1, method="mean"):
+        """Y (N, D) -> image of ``shape`` ((H, W) or (H, W, C)), every element the NaN-skipping mean / median of its
+        estimates.  A C-contiguous float64 Y (e.g. the transpose of an F-ordered (D, N) array) is passed without a copy."""
+        from .utils.prepost import patch_geometry
+        H, W, C = _image_hwc(shape)
+        N, D = patch_geometry(H, W, C, ph, pw, shift)
+        Y = as_f64(Y)
+        if Y.shape != (N, D):
+            raise ValueError("patches_merge: Y has shape %s, the geometry needs (%d, %d)" % (Y.shape, N, D))
+        m = {"mean": 0, "median": 1}[method]
+        out = np.empty(tuple(shape), dtype=np.float64)
+        check(self.lib.evoamd_patches_merge(self._h, dptr(Y), H, W, C, int(ph), int(pw), int(shift), m, dptr(out)))
+        return out
+
     # ---- timing --------------------------------------------------------------------------
     def timing(self, on=True):
         """on: True (all kernel classes), False, or an iterable of class names (_lib.KERNEL_IDS)."""
@@ -370,6 +395,14 @@ class Engine:
         n = ctypes.c_int64()
         check(self.lib.evoamd_kernel_time_ms(self._h, _lib.KERNEL_IDS[name], ctypes.byref(avg), ctypes.byref(n)))
         return avg.value, n.value
+
+
+def _image_hwc(shape):
+    if len(shape) == 2:
+        return int(shape[0]), int(shape[1]), 1
+    if len(shape) == 3:
+        return int(shape[0]), int(shape[1]), int(shape[2])
+    raise ValueError("image shape must be (H, W) or (H, W, C), got %s" % (tuple(shape),))
 
 
 TAIL = ("Fs", "sum_nunique", "sum_sub", "N", "reset_isnan", "reset_smaller_eps", "reset_isinf", "pad")

@@ -1,0 +1,177 @@
+"""Overlapping image patches: the pre- and post-processing of the reference's image workflows
+(examples/image-denoising/main.py, examples/image-inpainting/main.py), which import
+
+    from tvutil.prepost import OverlappingPatches, MultiDimOverlappingPatches, mean_merger, median_merger
+
+With evo_amd that import reads ``from evo_amd.utils.prepost import ...`` and the loops run unchanged.  Extraction and
+the two standard merges run as HIP kernels on the GPU (``Engine.patches_extract`` / ``Engine.patches_merge``); any other
+merge callable runs on the host over the stack of estimates.
+
+Conventions (ours; tvutil is not a dependency and bit parity with it is not claimed):
+
+- image (H, W) or (H, W, C), cast to float64; NaN marks missing pixels and passes through.
+- patch tops 0, s, 2s, ... while <= H - ph, plus H - ph appended if that value was not reached, so every pixel is
+  covered while s <= ph; lefts the same with W, pw.
+- patch n = ir * nc + ic, row-major over the (top, left) grid; with s = 1, N = (H - ph + 1) (W - pw + 1).
+- element d = (dy * pw + dx) * C + c (channel innermost, as in the image's memory); D = ph * pw * C.
+- ``get()`` returns the patches as (D, N) -- what the examples transpose into (N, D) data.
+- merging: every output element gathers one estimate from each patch that covers it, in increasing n; the stack of
+  estimates is (K, H, W[, C]) with NaN padding.  ``mean_merger`` is np.nanmean over it and ``median_merger``
+  np.nanmedian (even counts: (lo + hi) / 2); the GPU kernels reproduce both bit for bit.  No valid estimate: NaN.
+- limits: ph * pw <= 1024, ph <= H, pw <= W, patch_shift >= 1.
+"""
+import warnings
+
+import numpy as np
+
+MAX_PATCH_ELEMS = 1024
+
+
+def mean_merger(stack, axis=0):
+    """np.nanmean along ``axis``; all-NaN slices give NaN without a warning."""
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        return np.nanmean(stack, axis=axis)
+
+
+def median_merger(stack, axis=0):
+    """np.nanmedian along ``axis``; all-NaN slices give NaN without a warning."""
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        return np.nanmedian(stack, axis=axis)
+
+
+def patch_tops(L, p, s):
+    """Top rows (or left columns) of the patches along an axis of length L: 0, s, 2s, ... <= L - p, plus L - p."""
+    tops = list(range(0, L - p + 1, s))
+    if tops[-1] != L - p:
+        tops.append(L - p)
+    return np.asarray(tops, dtype=np.int64)
+
+
+def patch_geometry(H, W, C, ph, pw, shift):
+    """(N, D) of the patches of an (H, W, C) image; ValueError for arguments outside the limits."""
+    H, W, C, ph, pw, shift = (int(v) for v in (H, W, C, ph, pw, shift))
+    if min(H, W, C) < 1:
+        raise ValueError("image dimensions must be >= 1, got %s" % ((H, W, C),))
+    if ph < 1 or pw < 1:
+        raise ValueError("patch height and width must be >= 1, got %d x %d" % (ph, pw))
+    if ph > H or pw > W:
+        raise ValueError("patch %d x %d larger than the image %d x %d" % (ph, pw, H, W))
+    if shift < 1:
+        raise ValueError("patch_shift must be >= 1, got %d" % shift)
+    if ph * pw > MAX_PATCH_ELEMS:
+        raise ValueError("patches of %d x %d elements exceed the limit of %d" % (ph, pw, MAX_PATCH_ELEMS))
+    N = len(patch_tops(H, ph, shift)) * len(patch_tops(W, pw, shift))
+    return N, ph * pw * C
+
+
+def estimate_stack(Y, H, W, C, ph, pw, shift):
+    """Host form of the merge input: the (K, H, W, C) stack of every element's estimates in increasing n, NaN-padded.
+    Y is (N, D).  Estimate of element (y, x) from patch (ir, ic) sits in slot (ir - ir0(y)) kc(x) + (ic - ic0(x)),
+    where [ir0(y), ..] / [ic0(x), ..] are the first grid rows / columns that cover y / x and kc(x) how many cover x."""
+    tops, lefts = patch_tops(H, ph, shift), patch_tops(W, pw, shift)
+    nc = len(lefts)
+
+    def cover(L, p, starts):
+        ys = np.arange(L)
+        lo = np.searchsorted(starts, ys - p + 1, side="left")
+        hi = np.searchsorted(starts, ys, side="right") - 1
+        return lo, hi - lo + 1
+
+    r0, kr = cover(H, ph, tops)
+    c0, kc = cover(W, pw, lefts)
+    K = int(kr.max()) * int(kc.max())
+    stack = np.full((K, H, W, C), np.nan)
+    Y4 = np.asarray(Y, dtype=np.float64).reshape(len(tops), nc, ph, pw, C)
+    ir = np.arange(len(tops))[:, None]
+    ic = np.arange(nc)[None, :]
+    for dy in range(ph):
+        y = tops[:, None] + dy
+        for dx in range(pw):
+            x = lefts[None, :] + dx
+            k = (ir - r0[y]) * kc[x] + (ic - c0[x])
+            stack[k, y, x] = Y4[:, :, dy, dx]
+    return stack
+
+
+_shared = None
+
+
+def shared_engine():
+    """The process-wide Engine() on default_device(), created on first use."""
+    global _shared
+    if _shared is None:
+        from ..engine import Engine
+        _shared = Engine()
+    return _shared
+
+
+class OverlappingPatches:
+    """Overlapping patches of a grey (H, W) image (conventions: module docstring)."""
+
+    _ndim = 2
+
+    def __init__(self, image, patch_height, patch_width, patch_shift=1, engine=None):
+        image = np.asarray(image)
+        if image.ndim != self._ndim:
+            raise ValueError("%s takes a %d-D image, got shape %s" % (type(self).__name__, self._ndim, image.shape))
+        self.image = image.astype(np.float64)
+        self.shape = self.image.shape
+        H, W = self.shape[:2]
+        self.C = self.shape[2] if self._ndim == 3 else 1
+        self.ph, self.pw, self.shift = int(patch_height), int(patch_width), int(patch_shift)
+        self.N, self.D = patch_geometry(H, W, self.C, self.ph, self.pw, self.shift)
+        self._engine = engine
+        self._Y = None  # (N, D) patches: extracted on first use, replaced by set()
+
+    @property
+    def engine(self):
+        return self._engine if self._engine is not None else shared_engine()
+
+    def _patches(self):
+        if self._Y is None:
+            self._Y = self.engine.patches_extract(self.image, self.ph, self.pw, self.shift)
+        return self._Y
+
+    def get(self):
+        """The patches as (D, N) float64 (a transposed view of the (N, D) rows), NaN preserved."""
+        return self._patches().T
+
+    def set(self, Y_T):
+        """Store new patches, (D, N) like get() returns them."""
+        Y_T = np.asarray(Y_T)
+        if Y_T.shape != (self.D, self.N):
+            raise ValueError("set: expected patches of shape (D, N) = %s, got %s" % ((self.D, self.N), Y_T.shape))
+        self._Y = Y_T.T  # (N, D); C-contiguous when Y_T is the transpose of C-ordered rows, passed on without a copy
+
+    def merge(self, merge_method=mean_merger):
+        """Image of the input's shape from the current patches.  mean_merger / median_merger run on the GPU; any other
+        callable f is applied on the host as f(stack, axis=0) to the NaN-padded (K, H, W[, C]) estimate stack."""
+        Y = self._patches()
+        if merge_method is mean_merger or merge_method is median_merger:
+            method = "mean" if merge_method is mean_merger else "median"
+            return self.engine.patches_merge(Y, self.shape, self.ph, self.pw, self.shift, method)
+        stack = estimate_stack(Y, self.shape[0], self.shape[1], self.C, self.ph, self.pw, self.shift)
+        return np.asarray(merge_method(stack, axis=0)).reshape(self.shape)
+
+    def set_and_merge(self, Y_T, merge_method=mean_merger):
+        self.set(Y_T)
+        return self.merge(merge_method)
+
+
+class MultiDimOverlappingPatches(OverlappingPatches):
+    """Overlapping patches of an (H, W, C) image, e.g. RGB (conventions: module docstring)."""
+
+    _ndim = 3
+
+
+def psnr(target, reco, data_range=255):
+    """10 log10(data_range^2 / mean((target - reco)^2)) in float64: the skimage.metrics.peak_signal_noise_ratio call
+    of the reference's examples (eval_fn in their utils.py)."""
+    t = np.asarray(target, dtype=np.float64)
+    r = np.asarray(reco, dtype=np.float64)
+    if t.shape != r.shape:
+        raise ValueError("psnr: shapes differ, %s vs %s" % (t.shape, r.shape))
+    mse = np.mean((t - r) ** 2, dtype=np.float64)
+    return 10.0 * np.log10(float(data_range) ** 2 / mse)

@@ -378,6 +378,22 @@ int evoamd_free_energy(evoamd_ctx *ctx, const double *lpj, int64_t N, int C, dou
  * into the accumulator tail before the all-reduce. */
 int evoamd_set_estep_counts(evoamd_ctx *ctx, double sum_nunique, double sum_sub);
 
+/* ---- overlapping image patches (examples/image-denoising, image-inpainting: OverlappingPatches) ------ */
+/* img (H, W, C) float64 row-major, C innermost (C = 1: grey).  Patch tops 0, s, 2s, ... while <= H - ph, plus H - ph
+ * if that value was not reached (lefts alike with W, pw), so every pixel is covered; patch n = ir * nc + ic row-major
+ * over the (top, left) grid, element d = (dy * pw + dx) * C + c, D = ph * pw * C.  Limits: ph * pw <= 1024, ph <= H,
+ * pw <= W, shift >= 1 (else EVOAMD_E_INVALID).  Both calls take host pointers and have completed on return; they work
+ * on an unconfigured context, use device scratch of their own (grown on demand, freed by evoamd_ctx_destroy) and
+ * leave the EM state of a configured context (Y, K^n, Theta, masks, y_hat) untouched.
+ * extract: Y_out (N, D) = the patches of img, NaN passed through. */
+int evoamd_patches_extract(evoamd_ctx *ctx, const double *img, int H, int W, int C, int ph, int pw, int shift,
+                           double *Y_out);
+/* merge: Y (N, D) -> img_out (H, W, C), every element from the estimates of the patches that cover it, NaN skipped:
+ * method 0 mean (summed in increasing n, divided by the count: np.nanmean of the NaN-padded estimate stack, bit for
+ * bit), 1 median (np.nanmedian of that stack, bit for bit: even counts give (lo + hi) / 2).  No valid estimate: NaN. */
+int evoamd_patches_merge(evoamd_ctx *ctx, const double *Y, int H, int W, int C, int ph, int pw, int shift, int method,
+                         double *img_out);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------------- */
 /* 128-byte opaque id made by rank 0 and distributed by the caller (file / socket / MPI). */
 int evoamd_comm_unique_id(uint8_t id_out[128]);
@@ -413,7 +429,8 @@ enum {
   EVOAMD_K_ALLREDUCE = 19,     /* RCCL all-reduce(s) of the packed accumulator (sssc.py:671-691 / bsc.py:230-274 in one call): from
                                   this rank's statistics being done to the sum being delivered, i.e. wait for the slowest rank + transfer */
   EVOAMD_K_ESTEP_FUSED = 20,   /* fused per-datapoint E-step kernel (option "fused_estep") */
-  EVOAMD_K_COUNT = 21
+  EVOAMD_K_PATCHES = 21,       /* evoamd_patches_extract / evoamd_patches_merge kernels (transfers excluded) */
+  EVOAMD_K_COUNT = 22
 };
 /* on = bit mask of kernel classes to time (bit k = class k; -1 = all, 0 = off).  Each timed span
  * records two HIP events on the compute stream, which costs about 10 us of stream time per span:
