@@ -12,6 +12,7 @@
 #include <chrono>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -1902,6 +1903,20 @@ static unsigned pb_clamp(const PairBins &pb, unsigned grid) {
 #define PB_GRID_CHECK(pb, grid) \
   REQUIRE(!(pb).ent || (i64)(grid) <= (i64)(pb).nwg, "pair bins: producer grid exceeds the regions per bin (pb.nwg)")
 
+// The kernels that walk a state word by word are instantiated for HW = 1, 2, 4, 8, 16 words and, as 0, with a runtime
+// loop for any other count: calls f with the runtime hw as a compile-time constant (std::integral_constant) of that set.
+template <class F>
+static void with_hw(int hw, F &&f) {
+  switch (hw) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    default: f(std::integral_constant<int, 0>{}); break;
+  }
+}
+
 #define MAIN_LPJ_LDS_MAX (48 * 1024)  // three 512-thread workgroups (3072 pairs) per CU at the limit
 
 template <int TAG>
@@ -1946,16 +1961,9 @@ static int launch_sssc_lpj(evoamd_ctx *c, const SsscArgs &a, int kid_main, const
       const size_t lds = ((size_t)rows_cap * a.H + (stage_dg ? (size_t)4 * a.H : 0)) * sizeof(double);
       const int grid = (int)cdiv(total, 1024);
       REQUIRE(lds <= MAIN_LPJ_LDS_MAX, "ES3C lpj: H too large for the staged B rows");
-#define MAIN_NOAPP(HWT) sssc_main_lpj_kernel<TAG, 512, HWT, 2, false><<<grid, 512, lds, c->stream>>>(a, none_o, rows_cap, stage_dg)
-      switch (a.HW) {
-        case 1: MAIN_NOAPP(1); break;
-        case 2: MAIN_NOAPP(2); break;
-        case 4: MAIN_NOAPP(4); break;
-        case 8: MAIN_NOAPP(8); break;
-        case 16: MAIN_NOAPP(16); break;
-        default: MAIN_NOAPP(0); break;
-      }
-#undef MAIN_NOAPP
+      with_hw(a.HW, [&](auto hw) {
+        sssc_main_lpj_kernel<TAG, 512, decltype(hw)::value, 2, false><<<grid, 512, lds, c->stream>>>(a, none_o, rows_cap, stage_dg);
+      });
       HIP_TRY(hipGetLastError());
       DBG_SYNC(c, "sssc lpj main (census)");
     }
@@ -2011,26 +2019,16 @@ static int launch_sssc_lpj(evoamd_ctx *c, const SsscArgs &a, int kid_main, const
     const size_t lds = ((size_t)rows_cap * a.H + (stage_dg ? (size_t)4 * a.H : 0)) * sizeof(double);
     const int grid = (int)cdiv(total, 1024);
     if (!a.shared && (a.H % 2) == 0 && lds <= MAIN_LPJ_LDS_MAX) {
-      switch (a.HW) {
-        case 1: sssc_main_lpj_kernel<TAG, 512, 1, 2><<<grid, 512, lds, c->stream>>>(a, o1, rows_cap, stage_dg); break;
-        case 2: sssc_main_lpj_kernel<TAG, 512, 2, 2><<<grid, 512, lds, c->stream>>>(a, o1, rows_cap, stage_dg); break;
-        case 4: sssc_main_lpj_kernel<TAG, 512, 4, 2><<<grid, 512, lds, c->stream>>>(a, o1, rows_cap, stage_dg); break;
-        case 8: sssc_main_lpj_kernel<TAG, 512, 8, 2><<<grid, 512, lds, c->stream>>>(a, o1, rows_cap, stage_dg); break;
-        case 16: sssc_main_lpj_kernel<TAG, 512, 16, 2><<<grid, 512, lds, c->stream>>>(a, o1, rows_cap, stage_dg); break;
-        default: sssc_main_lpj_kernel<TAG, 512, 0, 2><<<grid, 512, lds, c->stream>>>(a, o1, rows_cap, stage_dg); break;
-      }
+      with_hw(a.HW, [&](auto hw) {
+        sssc_main_lpj_kernel<TAG, 512, decltype(hw)::value, 2><<<grid, 512, lds, c->stream>>>(a, o1, rows_cap, stage_dg);
+      });
     } else if (!a.shared && (a.H % 2) == 0 && a.dig && c->main_unstaged) {
       // the rows of the workgroup's datapoints do not fit the LDS (candidate batches: 1024 / Cmax datapoints per
       // workgroup): the same table-driven kernel with the B values gathered from global memory
       const size_t lds_u = (stage_dg ? (size_t)4 * a.H : 0) * sizeof(double);
-      switch (a.HW) {
-        case 1: sssc_main_lpj_kernel<TAG, 512, 1, 2, true, false><<<grid, 512, lds_u, c->stream>>>(a, o1, 0, stage_dg); break;
-        case 2: sssc_main_lpj_kernel<TAG, 512, 2, 2, true, false><<<grid, 512, lds_u, c->stream>>>(a, o1, 0, stage_dg); break;
-        case 4: sssc_main_lpj_kernel<TAG, 512, 4, 2, true, false><<<grid, 512, lds_u, c->stream>>>(a, o1, 0, stage_dg); break;
-        case 8: sssc_main_lpj_kernel<TAG, 512, 8, 2, true, false><<<grid, 512, lds_u, c->stream>>>(a, o1, 0, stage_dg); break;
-        case 16: sssc_main_lpj_kernel<TAG, 512, 16, 2, true, false><<<grid, 512, lds_u, c->stream>>>(a, o1, 0, stage_dg); break;
-        default: sssc_main_lpj_kernel<TAG, 512, 0, 2, true, false><<<grid, 512, lds_u, c->stream>>>(a, o1, 0, stage_dg); break;
-      }
+      with_hw(a.HW, [&](auto hw) {
+        sssc_main_lpj_kernel<TAG, 512, decltype(hw)::value, 2, true, false><<<grid, 512, lds_u, c->stream>>>(a, o1, 0, stage_dg);
+      });
     } else
       sssc_small_kernel<2, 0, TAG, 512><<<cdiv(total, 512), 512, 0, c->stream>>>(a, none, o1, PairBins{});
     HIP_TRY(hipGetLastError());
@@ -2721,10 +2719,7 @@ static int row_lse(evoamd_ctx *c, const double *lpj, i64 N, int L, double *rowma
   return 0;
 }
 
-// Everything of evoamd_stats up to (and including) the all-reduce; the packed accumulator stays on
-// the device.  tail[7] receives ljc of the Theta the E-step ran with.
 static int compute_reconstruction(evoamd_ctx *c);
-static int flush_reduce(evoamd_ctx *c);
 
 // the forked statistics contraction must have finished before anything reads its part of acc
 static int join_fork(evoamd_ctx *c) {
@@ -2742,11 +2737,6 @@ static int join_fork(evoamd_ctx *c) {
   return 0;
 }
 
-// fork_gemm: the caller promises to call join_fork before it reads the contraction's block of acc
-// (evoamd_mstep_device: after the H x H inverses).  With a communicator (ES3C) the packed accumulator is
-// all-reduced in two pieces: everything the inverses read here, the contraction's block at the join --
-// all RCCL calls stay on the main stream, in the same order on every rank.  Not while kernels are being
-// timed on the main stream.
 static TailArgs make_tail_args(evoamd_ctx *c, const AccLayout &a, i64 N, bool census, int skipped) {
   TailArgs ta = {};
   ta.tail = c->acc + a.tail;
@@ -2766,22 +2756,136 @@ static TailArgs make_tail_args(evoamd_ctx *c, const AccLayout &a, i64 N, bool ce
   return ta;
 }
 
-static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
-  REQUIRE(c && c->configured && c->have_data && c->have_params, "configure, upload_data and set_params first");
+// flops of the K = N contraction of the statistics pass: [Y | Es | Ez]^T Ez (ES3C), Es^T Y (EBSC)
+static double contraction_flops(const evoamd_ctx *c) {
+  return c->model == EVOAMD_MODEL_SSSC ? 2.0 * (double)c->N * (c->D + 2.0 * c->H) * c->H : 2.0 * (double)c->N * c->D * c->H;
+}
+
+// What a statistics pass decides before it enqueues anything (stats_plan); the stages only read it.
+struct StatsPlan {
+  AccLayout a;
+  i64 N;
+  int H, D;
+  hipStream_t main_stream;  // c->stream at entry (the contraction borrows c->stream for stream2 and gives it back)
+  bool masked;              // incomplete data
+  int tg;                   // how much is known about the final K^n (tag of level_grid / few_above4 / few_dense_states)
+  bool gemm_timed;          // a class on the main stream is being timed: no second stream
+  double gemm_flops;
+  bool pays;       // the contraction is worth a second stream (agreed over the ranks)
+  bool early;      // its stream branches off behind the last writer of the rows, not behind the finish kernel
+  bool fork_gemm;  // the contraction is still running when stats_compute returns; the caller joins
+  i64 rpb;         // datapoints per column-sum partial
+  int nblk;        // number of those
+  int nchunks;     // blocks of datapoints, each followed by its part of the contraction
+  i64 rows_per_chunk;
+  bool second_stream;
+  int fork_spare;  // what c->fork_spare becomes for this pass
+  int waves;       // waves per workgroup of the ES3C wave-per-datapoint kernel
+  bool census;     // ES3C: the levels read the census lists
+  bool bsc_wave;   // EBSC: the wave-per-datapoint kernel (else the round-1 kernel + column-sum pass)
+};
+
+// One block of datapoints: rows [n0, n0 + nc) = column-sum partials [blk0, blk0 + nblk_c)
+struct StatsBlock {
+  int ci;
+  i64 n0, nc;
+  int blk0, nblk_c;
+};
+
+// What a later stage of the pass learns from an earlier one.
+struct StatsFlow {
+  bool early_recorded = false;  // the contraction's branch point has been recorded (rows_written)
+  bool tail_done = false;       // the accumulator tail rode in the finish launch
+  bool served3 = false;  // the wavefront level ran on list 3 although the census did not ask for it (exact-mode hand-over)
+  int skipped = 0;       // levels not launched: their input lists must be found empty
+  int bsc_grid = 0;      // grid of the EBSC wave kernel = number of its sigma partials
+  PairBins bsc_pb = {};  // EBSC: the bins its wave kernel appended to
+  PairBins pb = {};      // ES3C: the bins of this pass (re-cut for the flat kernel)
+};
+
+// ES3C: argument block shared by the scatter kernels, the levels K^n needs and the on-the-fly lists
+struct Es3cPass {
+  double *Es, *Ez, *Ed;  // columns of [Y | Es | Ez | Ed] (ES3C)
+  SsscArgs sa = {};
+  bool need[3] = {true, true, true};
+  ListOut o1 = {}, o2 = {}, o3 = {};
+  ListIn i1 = {}, i2 = {}, i3 = {};
+  const ListOut none_out = {nullptr, nullptr, 0};
+};
+
+// ES3C on complete data, one block: its rows of the argument block, its census lists, the form of its main kernel
+struct Es3cBlock {
+  SsscArgs sc;
+  i64 total;
+  ListIn cA, cB, cC;
+  int flatG = 0;  // census mode, thread-per-state form of the main kernel: G datapoints per 1024-thread workgroup and round
+  size_t flat_lds = 0;
+  bool few4;  // few states above four latents: no quad launch for them, the wavefront kernel behind the main kernel adds them
+};
+
+// Pair bins (asked once per pass and model): they pay when the fixed cost of the reduce pass (zero + store nb x PB_NSH
+// tiles, ~20 us) is less than the global atomics they absorb -- from ~256k resident states on (N = 12.5k x S = 200:
+// statistics pass 0.63 -> 0.40 ms).  ES3C needs complete data as well, EBSC its wave kernel.
+// Not a member of StatsPlan: ensure_bins_capacity, in the preamble of the pass, may re-cut or drop c->pbins.
+static bool stats_bins_pay(const evoamd_ctx *c) {
+  return c->pbins.ent && (c->pair_bins == 2 || (c->pair_bins == 1 && c->N * (i64)c->S >= (i64)c->bins_min * 1024));
+}
+
+// resident workgroups per CU of a wave-per-datapoint statistics kernel: what its LDS leaves, the CU's waves, 1 .. 8
+static int stats_per_cu(size_t lds_per_wg, int wave_lim) {
+  int per_cu = (int)((160 * 1024) / lds_per_wg);
+  if (per_cu > wave_lim) per_cu = wave_lim;
+  if (per_cu > 8) per_cu = 8;
+  if (per_cu < 1) per_cu = 1;
+  return per_cu;
+}
+
+// every kernel that writes the E_q rows of the (only) block has been enqueued: the contraction's stream branches off here
+static int rows_written(evoamd_ctx *c, const StatsPlan &p, StatsFlow &fl) {
+  if (p.second_stream && p.nchunks == 1 && p.early && !p.masked) {
+    HIP_TRY(hipEventRecord(c->ev_chunk[0], p.main_stream));
+    fl.early_recorded = true;
+  }
+  return 0;
+}
+
+// incomplete data: y_hat = E W^T under the Theta of this E-step, and y_reconstructed from it -- the rows the Wp
+// contraction reads.  `asked_msg`: ES3C requires rec_in_stats, and says so between the two launches.
+static int reconstruct_rows(evoamd_ctx *c, const char *asked_msg = nullptr) {
+  int r = compute_reconstruction(c);
+  if (r) return r;
+  if (asked_msg) REQUIRE(c->rec_in_stats, asked_msg);
+  select_rec_kernel<<<cdiv(c->N, 4), 256, 0, c->stream>>>(c->Y, c->ldY, c->mask_x, c->mask_infr, c->yhat, c->N, c->D, c->Yrec);
+  HIP_TRY(hipGetLastError());
+  c->yrec_valid = true;
+  c->rec_in_stats = false;
+  return 0;
+}
+
+// Fills the plan from the context as it is at entry.  Enqueues nothing; with a communicator it may talk to the other
+// ranks once per geometry (pays_agreed), at the same point on every rank.
+static int stats_plan(evoamd_ctx *c, bool fork_gemm, StatsPlan &p) {
+  p = StatsPlan{};
+  p.a = acc_layout(c);
+  p.N = c->N;
+  p.H = c->H;
+  p.D = c->D;
+  p.main_stream = c->stream;
+  p.masked = c->mask_infr != nullptr;
+  p.tg = c->cand_from_device ? 1 : 2;
   // (the contraction's own class alone does not count: its span is recorded on the stream the product runs on, so it
   // can be timed forked, as the timed loop runs it -- bench.py's `mfma` block)
-  const bool gemm_timed = c->timing && (c->timing_mask & ((1u << KID_MSTEP) | (1u << KID_MISC) |
-                                                          (1u << KID_STATS) | (1u << KID_STATS_OVF)));
+  p.gemm_timed = c->timing && (c->timing_mask & ((1u << KID_MSTEP) | (1u << KID_MISC) |
+                                                 (1u << KID_STATS) | (1u << KID_STATS_OVF)));
   // the K = N contraction is worth a second stream when it is big (measured, tools/ab.sh, MI355X: ES3C H = 512 gains;
   // ES3C H = 128 and the EBSC shapes at N <= 50k lose ~1 %: the fork / join events cost ~10 us)
-  const double gemm_flops = c->model == EVOAMD_MODEL_SSSC ? 2.0 * (double)c->N * (c->D + 2.0 * c->H) * c->H
-                                                          : 2.0 * (double)c->N * c->D * c->H;
+  const double gemm_flops = p.gemm_flops = contraction_flops(c);
   // (EBSC: from ~5e10 flops on and without a communicator -- c5 on one GPU 6.47 -> 6.24 ms per iteration with eight
   // slots per XCD left to its 32 block steps of 256 workgroups; its accumulator is all-reduced in one piece)
   bool pays = (c->model == EVOAMD_MODEL_SSSC && gemm_flops >= 8e9) || (c->model == EVOAMD_MODEL_BSC && !c->comm && gemm_flops >= 5e10);
   // branching off early (option "early_fork") makes the fork pay for small ES3C products too: the product then runs
   // beside the pair-bin reduce, the finish kernel and the register-resident inverse instead of in front of them
-  const bool early = c->early_fork == 1 || (c->early_fork < 0 && gemm_flops < 2e10);
+  const bool early = p.early = c->early_fork == 1 || (c->early_fork < 0 && gemm_flops < 2e10);
   if (c->model == EVOAMD_MODEL_SSSC && !c->comm && early && gemm_flops >= 5e8 && !c->mask_infr) pays = true;
   // EBSC the same (c3: the 48 us product beside the reduce, the finish kernel and the 9-launch elimination chain) where
   // the wave-per-datapoint statistics kernel runs (the branch point sits behind it)
@@ -2799,61 +2903,32 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
     }
     pays = c->pays_agreed == 1;
   }
+  p.pays = pays;
   // fork_gemm: the contraction is still running when this function returns (beside the H x H inverses); the caller
   // joins.  With a communicator only ES3C does that (its accumulator is all-reduced in pieces).
-  fork_gemm = fork_gemm && (c->overlap_gemm == 2 || (c->overlap_gemm == 1 && pays)) &&
-              (!c->comm || c->model == EVOAMD_MODEL_SSSC) && !gemm_timed && !c->mask_infr;
-  {
-    int rj = join_fork(c);  // a previous call that failed between fork and join must not race with the memset below
-    if (rj) return rj;
-  }
-  HIP_TRY(hipSetDevice(c->device));
-  {
-    int rb = ensure_bins_capacity(c);
-    if (rb) return rb;
-  }
-  if (c->bins_dirty && c->pbins.gcnt)  // an earlier pass returned between its producers and the reduce: stale region counts
-    HIP_TRY(hipMemsetAsync(c->pbins.gcnt, 0, (size_t)c->pbins.nb * c->pbins.nwg * sizeof(int), c->stream));
-  c->bins_dirty = false;
-  // test hook: consumed by every pass (it stops only an ES3C pass on complete data, after its main kernel)
-  const bool debug_fail = c->debug_fail_stats != 0;
-  c->debug_fail_stats = 0;
-  const AccLayout a = acc_layout(c);
-  const i64 N = c->N;
-  const int H = c->H, D = c->D;
-  const bool masked = c->mask_infr != nullptr;
-  if (!c->acc_clean)  // (else: zeroed by the selection kernel on its way)
-    HIP_TRY(hipMemsetAsync(c->acc_base, 0, (size_t)(c->ovf_n + c->acc_n) * sizeof(double), c->stream));
-  c->acc_clean = false;
-  c->yhat_valid = c->stats_rows_valid = false;
-  int r = ensure_B(c);
-  if (r) return r;
-  if (!c->rows_fresh) {  // otherwise vary_kn left rowmax / rowsum / dpar[DP_FS] behind
-    r = row_lse(c, c->lpj, N, c->L, c->rowmax, c->rowsum, c->dpar + DP_FS);
-    if (r) return r;
-  }
+  p.fork_gemm = fork_gemm && (c->overlap_gemm == 2 || (c->overlap_gemm == 1 && pays)) &&
+                (!c->comm || c->model == EVOAMD_MODEL_SSSC) && !p.gemm_timed && !c->mask_infr;
   // column-sum partials: at most ~128 of them (the finish kernels add them serially per column); a multiple of
   // four rows so that a block boundary is a workgroup boundary of the EBSC kernel (four datapoints each)
-  const i64 rpb = ((std::max<i64>(256, cdiv(N, 128)) + 3) / 4) * 4;
-  const int nblk = (int)cdiv(N, rpb);
+  p.rpb = ((std::max<i64>(256, cdiv(p.N, 128)) + 3) / 4) * 4;
+  p.nblk = (int)cdiv(p.N, p.rpb);
   // Blocks of datapoints: the scatter kernels of block i + 1 (bound by the f64 atomic rate, executed at the memory
   // side) run beside the MFMA contraction of block i on the second stream.  Same kernels, same sums; the
   // contraction accumulates with its atomic epilogue.  Not while the classes involved are being timed one by one.
   int nchunks = 1;
-  if (!masked && !gemm_timed && c->overlap_gemm != 0 && c->stats_chunks > 1 && (gemm_flops >= 8e9 || c->overlap_gemm == 2))
-    nchunks = std::min<int>(c->stats_chunks, nblk);
+  if (!p.masked && !p.gemm_timed && c->overlap_gemm != 0 && c->stats_chunks > 1 && (gemm_flops >= 8e9 || c->overlap_gemm == 2))
+    nchunks = std::min<int>(c->stats_chunks, p.nblk);
   // census lists need the 4-wave statistics kernel (rows of four datapoints + column sums in LDS: 11 H doubles); larger
   // H -- or a waves-per-workgroup measurement option -- takes the round-2 level chains, decided BEFORE any level runs
-  const int stats_wv = (c->stats_waves == 4 || c->stats_waves == 8 || c->stats_waves == 16)
-                           ? c->stats_waves
-                           : ((size_t)(4 * 2 + 3) * H * sizeof(double) <= 150 * 1024 ? 4 : 1);
-  const bool census = census_mode(c) && !masked && stats_wv == 4;
-  if (census) nchunks = 1;  // the census lists cover the whole shard
-  const i64 rows_per_chunk = (i64)cdiv(nblk, nchunks) * rpb;
-  nchunks = (int)cdiv(N, rows_per_chunk);
-  const bool second_stream = fork_gemm || nchunks > 1;
-  bool early_recorded = false, tail_done = false;
-  hipStream_t main_stream = c->stream;
+  // (8 / 16 waves per workgroup were measured: c4 8 waves -4 %, 16 waves 2x slower; c2 16 waves 112 vs 74 us)
+  p.waves = (c->stats_waves == 4 || c->stats_waves == 8 || c->stats_waves == 16)
+                ? c->stats_waves  // measurement option
+                : ((size_t)(4 * 2 + 3) * p.H * sizeof(double) <= 150 * 1024 ? 4 : 1);
+  p.census = census_mode(c) && !p.masked && p.waves == 4;
+  if (p.census) nchunks = 1;  // the census lists cover the whole shard
+  p.rows_per_chunk = (i64)cdiv(p.nblk, nchunks) * p.rpb;
+  p.nchunks = nchunks = (int)cdiv(p.N, p.rows_per_chunk);
+  p.second_stream = p.fork_gemm || nchunks > 1;
   // Forked beside the elimination chain: a resident-sized grid holds every workgroup slot until it has drained, and the
   // grouped split-K drains all at once -- the chain (H / 32 block steps of 128 workgroups each) then runs entirely BEHIND
   // the product (0.25 ms at the north-star shape).  Four slots per XCD left free (34 tiles x 14 chunks = 476 workgroups
@@ -2862,455 +2937,461 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
   // 1.14 -> 1.09 with 4 and 1.065 with 8 (12 / 16: the same): 4 where the product is long against the chain, else 8.
   {
     const double chain_us = c->H >= 256 ? 15.0 * cdiv(c->H, 32) : 8.5 * cdiv(c->H, 16);
-    c->fork_spare = !(fork_gemm && nchunks == 1) ? 0 : ((gemm_flops / 65e6 >= 3.0 * chain_us && c->H <= 512) ? 4 : 8);
+    p.fork_spare = !(p.fork_gemm && nchunks == 1) ? 0 : ((gemm_flops / 65e6 >= 3.0 * chain_us && c->H <= 512) ? 4 : 8);
   }
-  int skipped = 0;
-  bool served3 = false;  // the wavefront level ran on list 3 although the census did not ask for it (exact-mode hand-over)
-  // the whole statistics pass (everything that reads K^n + lpj and leaves the M-step sums, the GEMM aside)
-  std::unique_ptr<SpanGuard> pass(new SpanGuard(c, KID_STATS_PASS));
-  const int cols = c->model == EVOAMD_MODEL_BSC ? H : 3 * H;
-  r = ensure_colpart(c, (size_t)nblk * cols);
-  if (r) return r;
-  // ---- ES3C: argument block shared by the scatter kernels
-  double *Es = c->model == EVOAMD_MODEL_SSSC ? c->Y + D : c->Es;
-  double *Ez = c->Y + D + H, *Ed = c->Y + D + 2 * H;  // columns of [Y | Es | Ez | Ed] (ES3C)
-  SsscArgs sa = {};
-  bool need[3] = {true, true, true};
-  int cap = 0;
-  if (c->model == EVOAMD_MODEL_SSSC) {
-    Batch b = {c->states, nullptr, c->Y, c->Bm, c->yy, N, c->S, 0, nullptr, c->L, c->S_perm, c->flags, KID_STATS, 0};
-    b.mask = c->mask_infr;
-    sa = sssc_args(c, b);
-    sa.lpj_in = c->lpj;
-    sa.rowmax = c->rowmax;
-    sa.rowsum = c->rowsum;
-    sa.Es = Es;
-    sa.Ez = Ez;
-    sa.Ed = Ed;
-    sa.ldE = c->ldY;
-    sa.xss = c->acc + a.xss;
-    sa.xszsz = c->acc + a.xszsz;
-    sa.xss_o = c->acc_base + c->pre_n;
-    sa.xszsz_o = c->acc_base + c->pre_n + (size_t)H * H;
-    if (!masked) sa.cs = c->acc_base + 4;  // the kernels sum the columns of [Es | Ez] and the diagonal second moments themselves
-    cap = (int)list_cap(N * (i64)c->S);
-    // the final K^n is made of resident states and accepted candidates: same levels as the candidates
-    levels_for(c, 1, need);
-    r = zero_lists(c);
-    if (r) return r;
-  }
-  const ListOut o1 = {c->list1, c->list_n + 0 * LIST_SHARDS, cap}, o2 = {c->list2, c->list_n + 1 * LIST_SHARDS, cap},
-                o3 = {c->list3, c->list_n + 2 * LIST_SHARDS, cap};
-  const ListIn i1 = {o1.items, o1.counts, cap}, i2 = {o2.items, o2.counts, cap}, i3 = {o3.items, o3.counts, cap};
-  const ListOut none_out = {nullptr, nullptr, 0};
-  const double *Ywp = c->Y;  // EBSC: what the Wp contraction reads
-  int ldwp = c->ldY;
-  // ES3C pair bins (decided once per pass): they pay when the fixed cost of the reduce pass (zero + store nb x PB_NSH
-  // tiles, ~20 us) is less than the global atomics they absorb -- from ~256k resident states on (N = 12.5k x S = 200:
-  // statistics pass 0.63 -> 0.40 ms)
-  PairBins pb = {};
-  if (c->model == EVOAMD_MODEL_SSSC && !masked && c->pbins.ent &&
-      (c->pair_bins == 2 || (c->pair_bins == 1 && N * (i64)c->S >= (i64)c->bins_min * 1024)))
-    pb = c->pbins;
+  // EBSC: wave-per-datapoint kernel with prefetch, pair bins and in-kernel column sums where it applies (digests, S <= 256,
+  // one block); else the round-1 kernel + column-sum pass
+  const int SRb = (int)cdiv(c->S, 64);
+  p.bsc_wave = c->model == EVOAMD_MODEL_BSC && c->bsc_wave_opt && dig_for(c, c->states) &&
+               (SRb == 1 || SRb == 2 || SRb == 4 || SRb == 3) && nchunks == 1 && (size_t)5 * p.H * sizeof(double) <= 150 * 1024;
+  return 0;
+}
 
-  bool bsc_wave = false;
-  int bsc_grid = 0;
-  PairBins bsc_pb = {};
-  for (int ci = 0; ci < nchunks; ci++) {
-    const i64 n0 = (i64)ci * rows_per_chunk;
-    const i64 nc = std::min<i64>(rows_per_chunk, N - n0);
-    const int blk0 = (int)(n0 / rpb), nblk_c = (int)cdiv(nc, rpb);
-    c->grid_scale = (double)nc / (double)N;
-    if (c->model == EVOAMD_MODEL_BSC) {
-      // wave-per-datapoint kernel with prefetch, pair bins and in-kernel column sums where it applies (digests, S <= 256,
-      // one block); else the round-1 kernel + column-sum pass
-      const u64 *bdig = dig_for(c, c->states);
-      const int SRb = (int)cdiv(c->S, 64);
-      bsc_wave = c->bsc_wave_opt && bdig && (SRb == 1 || SRb == 2 || SRb == 4 || SRb == 3) && nchunks == 1 &&
-                 (size_t)5 * H * sizeof(double) <= 150 * 1024;
-      if (bsc_wave) {
-        SpanGuard g(c, KID_STATS);
-        const size_t ldsb = (size_t)5 * H * sizeof(double);
-        int per_cu = (int)((160 * 1024) / (ldsb + 2048));
-        if (per_cu > 8) per_cu = 8;
-        if (per_cu < 1) per_cu = 1;
-        bsc_pb = PairBins{};
-        if (c->pbins.ent && (c->pair_bins == 2 || (c->pair_bins == 1 && N * (i64)c->S >= (i64)c->bins_min * 1024))) bsc_pb = c->pbins;
-        int sgrid = (int)std::min<i64>(cdiv(nc, 4), (i64)c->n_cu * per_cu * 2);
-        if (sgrid > 2048) sgrid = 2048;  // the size of the sigma partials
-        if (bsc_pb.ent && sgrid > bsc_pb.nwg) sgrid = bsc_pb.nwg;  // one private region per producer workgroup and bin
-        PB_GRID_CHECK(bsc_pb, sgrid);
-        if (bsc_pb.ent) c->bins_dirty = true;
-        bsc_grid = sgrid;
-        void *EsP = c->f32 ? (void *)c->Esf : (void *)c->Es;
-        double *csb = c->acc_base + 4;
+// ---- EBSC producer of the (only) block: the wave-per-datapoint kernel and the reduce of its pair bins
+static int stats_bsc_wave(evoamd_ctx *c, const StatsPlan &p, const StatsBlock &blk, StatsFlow &fl) {
+  const AccLayout &a = p.a;
+  const i64 nc = blk.nc;
+  const int H = p.H;
+  const u64 *bdig = dig_for(c, c->states);
+  const int SRb = (int)cdiv(c->S, 64);
+  SpanGuard g(c, KID_STATS);
+  const size_t ldsb = (size_t)5 * H * sizeof(double);
+  const int per_cu = stats_per_cu(ldsb + 2048, 8);  // (four waves per workgroup)
+  PairBins &bsc_pb = fl.bsc_pb;
+  bsc_pb = PairBins{};
+  if (stats_bins_pay(c)) bsc_pb = c->pbins;
+  int sgrid = (int)std::min<i64>(cdiv(nc, 4), (i64)c->n_cu * per_cu * 2);
+  if (sgrid > 2048) sgrid = 2048;  // the size of the sigma partials
+  if (bsc_pb.ent && sgrid > bsc_pb.nwg) sgrid = bsc_pb.nwg;  // one private region per producer workgroup and bin
+  PB_GRID_CHECK(bsc_pb, sgrid);
+  if (bsc_pb.ent) c->bins_dirty = true;
+  fl.bsc_grid = sgrid;
+  void *EsP = c->f32 ? (void *)c->Esf : (void *)c->Es;
+  double *csb = c->acc_base + 4;
 #define BSC_WAVE(SR)                                                                                                      \
   bsc_stats_wave_kernel<SR><<<sgrid, 256, ldsb, c->stream>>>(c->states, c->lpj, c->rowmax, c->rowsum, c->yy, nc, c->S,     \
                                                             c->S_perm, H, c->HW, c->dpar, EsP, c->acc + a.Wq, c->partial2, \
                                                             bdig, c->f32 ? 1 : 0, bsc_pb, csb)
-        if (SRb == 1) BSC_WAVE(1);
-        else if (SRb == 2) BSC_WAVE(2);
-        else BSC_WAVE(4);
+  if (SRb == 1) BSC_WAVE(1);
+  else if (SRb == 2) BSC_WAVE(2);
+  else BSC_WAVE(4);
 #undef BSC_WAVE
-        HIP_TRY(hipGetLastError());
-        DBG_SYNC(c, "bsc stats (wave)");
-        if (second_stream && nchunks == 1 && early && !masked) {  // the E_q[s] rows are written: the product may start
-          HIP_TRY(hipEventRecord(c->ev_chunk[0], main_stream));
-          early_recorded = true;
-        }
-        if (bsc_pb.ent) {
-          pair_bins_reduce_kernel<<<bsc_pb.nb * bsc_pb.nsh, PB_RTHREADS, (size_t)3 * 2 * bsc_pb.rf * H * sizeof(double), c->stream>>>(
-              bsc_pb, H, 0);
-          HIP_TRY(hipGetLastError());
-          c->bins_dirty = false;
-        }
-      } else {
-      {
-        SpanGuard g(c, KID_STATS);
-  #define BSC_STATS(HWT)                                                                                              \
-    bsc_stats_kernel<HWT><<<cdiv(nc, 4), 256, (size_t)4 * H * sizeof(double), c->stream>>>(                           \
-        c->states + (size_t)n0 * c->S * c->HW, c->lpj + (size_t)n0 * c->L, c->rowmax + n0, c->rowsum + n0, c->yy + n0, nc, \
-        c->S, c->S_perm, H, c->HW, c->dpar,                                                                           \
-        c->f32 ? (void *)(c->Esf + (size_t)n0 * H) : (void *)(c->Es + (size_t)n0 * H), c->acc + a.Wq, c->partial2 + n0 / 4, \
-        dig_for(c, c->states) ? dig_for(c, c->states) + (size_t)n0 * c->S : nullptr, c->f32 ? 1 : 0)
-          switch (c->HW) {
-            case 1: BSC_STATS(1); break;
-            case 2: BSC_STATS(2); break;
-            case 4: BSC_STATS(4); break;
-            case 8: BSC_STATS(8); break;
-            case 16: BSC_STATS(16); break;
-            default: BSC_STATS(0); break;
-          }
-  #undef BSC_STATS
-          HIP_TRY(hipGetLastError());
-          DBG_SYNC(c, "bsc stats");
-        }
-        {
-          SpanGuard g(c, KID_MISC);
-          if (c->f32)
-            colsum_partial_f32_kernel<<<dim3(cdiv(H, 64), nblk_c), 256, 0, c->stream>>>(c->Esf + (size_t)n0 * H, H, nc, H, rpb,
-                                                                                        c->colpart + (size_t)blk0 * H);
-          else
-            colsum_partial_kernel<<<dim3(cdiv(H, 64), nblk_c), 256, 0, c->stream>>>(c->Es + (size_t)n0 * H, H, nc, H, rpb,
-                                                                                    c->colpart + (size_t)blk0 * H);
-          HIP_TRY(hipGetLastError());
-        }
-      }
-      if (masked) {  // incomplete data: the Wp contraction reads y_reconstructed (bsc.py:184-189,211); one block only
-        if (c->rec_in_stats) {
-          r = compute_reconstruction(c);  // y_hat = Es W^T under the Theta of this E-step (_models.py:193-194)
-          if (r) return r;
-          select_rec_kernel<<<cdiv(N, 4), 256, 0, c->stream>>>(c->Y, c->ldY, c->mask_x, c->mask_infr, c->yhat, N, D, c->Yrec);
-          HIP_TRY(hipGetLastError());
-          c->yrec_valid = true;
-          c->rec_in_stats = false;
-        }
-        REQUIRE(c->yrec_valid, "incomplete data: the M-step needs y_reconstructed (bsc.py:186); reconstruct or upload it");
-        Ywp = c->Yrec;
-        ldwp = D;
-      }
-    } else if (masked) {
-      // incomplete data (sssc.py:276: W[this_x_infr, :]): the state terms belong to the datapoint, so every
-      // state goes through the wavefront kernel, which forms W_obs^T W_obs itself and ADDS its moments to
-      // the rows (they start from zero here)
-      const i64 total = N * (i64)c->S;
-      HIP_TRY(hipMemset2DAsync(Es, (size_t)c->ldY * sizeof(double), 0, (size_t)3 * H * sizeof(double), (size_t)N, c->stream));
-      const ListIn nat = {nullptr, nullptr, 0};
-      {
-        SpanGuard g(c, KID_STATS);
-        sssc_big_kernel<1><<<(int)std::min<i64>(total, 65536), 64, big_lds(8), c->stream>>>(sa, nat, o3, 8);
-        sssc_big_kernel<1><<<1024, 64, big_lds(SSSC_KCAP), c->stream>>>(sa, i3, none_out, SSSC_KCAP);
-        HIP_TRY(hipGetLastError());
-      }
-      SpanGuard g(c, KID_MISC);
-      colsum_partial_kernel<<<dim3(cdiv(3 * H, 64), nblk), 256, 0, c->stream>>>(Es, c->ldY, N, 3 * H, rpb, c->colpart);
-      HIP_TRY(hipGetLastError());
-    } else {
-      SsscArgs sc = sa;  // this block's rows
-      sc.states = sa.states + (size_t)n0 * c->S * c->HW;
-      if (sa.dig) sc.dig = sa.dig + (size_t)n0 * c->S;
-      sc.Bm = sa.Bm + (size_t)n0 * H;
-      sc.yy = sa.yy + n0;
-      sc.lpj_in = sa.lpj_in + (size_t)n0 * sa.ldo;
-      sc.rowmax = sa.rowmax + n0;
-      sc.rowsum = sa.rowsum + n0;
-      sc.Es = sa.Es + (size_t)n0 * sa.ldE;
-      sc.Ez = sa.Ez + (size_t)n0 * sa.ldE;
-      sc.Ed = sa.Ed + (size_t)n0 * sa.ldE;
-      sc.N = nc;
-      const i64 total = nc * (i64)c->S;
-      if (pb.ent) c->bins_dirty = true;  // this block's producers append; until its reduce (which zeroes the counters)
-      if (ci > 0) {  // the previous block's overflow census joins the running sum; fresh lists for this block
-        census_lists_kernel<<<1, 256, 0, c->stream>>>(c->list_n, LIST_SHARDS, skip_mask(need), c->err, c->census);
-        HIP_TRY(hipGetLastError());
-      }
-      const int ccap = (int)list_cap(total);
-      const ListIn cA = {c->clist, c->clist_n, ccap}, cB = {c->clist + c->clist_words, c->clist_n + LIST_SHARDS, ccap},
-                   cC = {c->clist + 2 * c->clist_words, c->clist_n + 2 * LIST_SHARDS, ccap};
-      // census mode, thread-per-state form of the main kernel: G datapoints per 1024-thread workgroup and round
-      int flatG = 0;
-      size_t flat_lds = 0;
-      if (census && c->stats_flat && c->S <= FLAT_T && (H % 2) == 0 && (D % 2) == 0 && sc.Ez == sc.Es + H && c->stats_waves == 0) {
-        flatG = FLAT_T / c->S;
-        const int gmax = (int)(((size_t)140 * 1024 / sizeof(double) - (size_t)7 * H) / ((size_t)4 * H + 4));
-        if (flatG > gmax) flatG = gmax;
-        if (flatG > 4 * FLAT_T / H) flatG = 4 * FLAT_T / H;  // the round's B rows: at most two 16-byte pieces per thread
-        if (flatG >= 1) flat_lds = ((size_t)H * (4 * flatG + 7) + 4 * flatG) * sizeof(double);
-      }
-      // few states above four latents: no quad launch for them, the wavefront kernel behind the main kernel adds them
-      const bool few4 = census && flatG < 1 && few_above4(c, c->cand_from_device ? 1 : 2);
-      if (flatG >= 1 && pb.ent) {
-        // one resident workgroup per CU produces: the bins' entry space re-cut into n_cu regions per bin
-        const i64 per_bin = (i64)pb.nwg * pb.cap;
-        pb.nwg = std::min(pb.nwg, c->n_cu);
-        pb.cap = (int)std::min<i64>(per_bin / pb.nwg, 1 << 30);
-      }
-      if (census) {
-        // the quad levels FIRST: records of the listed states (read back by the wave-per-datapoint kernel), their
-        // diagonal second moments into the column-sum slices, their pairs into the bins (regions shared by workgroup index)
-        r = ensure_census(c);
-        if (r) return r;
-        if (need[0] || need[1]) {
-          SpanGuard g(c, KID_STATS_OVF);
-          const int tg = c->cand_from_device ? 1 : 2;
-          const unsigned gcap = pb.ent ? (unsigned)std::min(2048, pb.nwg) : 2048u;
-          const size_t dl = (size_t)H * sizeof(double);
-          // (the bins' region counters are zero here: pair_bins_reduce_kernel clears what it reads)
-          if (need[0]) {
-            SpanGuard gl(c, KID_STATS_K34);
-            const unsigned qg = quad_grid(c, 0, tg, total, gcap);
-            PB_GRID_CHECK(pb, qg);
-            sssc_quad_kernel<1, 1, 2><<<qg, 256, dl, c->stream>>>(sc, cA, none_out, o3, pb, c->ovf_rec);
-          }
-          if (need[1] && !few4) {
-            SpanGuard gl(c, KID_STATS_K58);
-            const unsigned qg = quad_grid(c, 1, tg, total, gcap);
-            PB_GRID_CHECK(pb, qg);
-            sssc_quad_kernel<2, 1, 2><<<qg, 256, dl, c->stream>>>(sc, cB, none_out, o3, pb, c->ovf_rec);
-          }
-          HIP_TRY(hipGetLastError());
-          DBG_SYNC(c, "sssc stats quad levels");
-        }
-      }
-      if (flatG >= 1) {
-        SpanGuard g(c, KID_STATS);
-        int fgrid = (int)std::min<i64>(cdiv(nc, flatG), (i64)c->n_cu);
-        if (pb.ent && fgrid > pb.nwg) fgrid = pb.nwg;
-        PB_GRID_CHECK(pb, fgrid);
-        sssc_stats_flat_kernel<<<fgrid, FLAT_T, flat_lds, c->stream>>>(sc, pb, c->ovf_rec, flatG);
-        HIP_TRY(hipGetLastError());
-        DBG_SYNC(c, "sssc stats main (flat)");
-      } else {
-        // one wave per datapoint, persistent workgroups: W x 2 H doubles of rows + 3 H of column accumulators in LDS
-        int Wv = (size_t)(4 * 2 + 3) * H * sizeof(double) <= 150 * 1024 ? 4 : 1;
-        // (8 / 16 waves per workgroup were measured: c4 8 waves -4 %, 16 waves 2x slower; c2 16 waves 112 vs 74 us)
-        if (c->stats_waves == 4 || c->stats_waves == 8 || c->stats_waves == 16) Wv = c->stats_waves;  // measurement option
-        size_t lds = (size_t)(Wv * 2 + 3) * H * sizeof(double);
-        const size_t lds_static = 1024 + (size_t)Wv * 512 + 128;  // the kernel's bin counters and overflow buffers
-        REQUIRE(lds <= 150 * 1024, "ES3C statistics: H too large for the LDS rows (H <= 3800)");
-        // B row of each wave's datapoint + the singleton table in LDS too when that still leaves two workgroups per CU
-        const size_t lds_staged = lds + (size_t)(Wv + 4) * H * sizeof(double);
-        const int stage = (H % 2) == 0 && 2 * (lds_staged + lds_static) <= 160 * 1024 && c->stats_stage != 0;
-        if (stage) lds = lds_staged;
-        int per_cu = (int)((160 * 1024) / (lds + lds_static));
-        const int wave_lim = 32 / Wv;  // 32 waves per CU
-        if (per_cu > wave_lim) per_cu = wave_lim;
-        if (per_cu > 8) per_cu = 8;
-        if (per_cu < 1) per_cu = 1;
-        SpanGuard g(c, KID_STATS);
-        // a wave per datapoint while that is at most a few rounds of resident workgroups (a second datapoint per wave
-        // doubles the kernel's critical path at small N), a persistent grid-stride loop beyond
-        int sgrid = (int)std::min<i64>(cdiv(nc, Wv), (i64)c->n_cu * per_cu * 4);
-        if (pb.ent && sgrid > pb.nwg) sgrid = pb.nwg;  // one private region per producer workgroup and bin
-        PB_GRID_CHECK(pb, sgrid);
-#define STATS_WAVE(HWT)                                                                                  \
-  do {                                                                                                   \
-    if (census)                                                                                          \
-      sssc_stats_wave_kernel<HWT, 4, true><<<sgrid, 256, lds, c->stream>>>(sc, o1, pb, stage, c->ovf_rec, few4 ? 4 : 8); \
-    else                                                                                                 \
-      sssc_stats_wave_kernel<HWT, 4><<<sgrid, 256, lds, c->stream>>>(sc, o1, pb, stage);                  \
-  } while (0)
-        REQUIRE(!census || Wv == 4, "census lists need the 4-wave statistics kernel (option stats_waves)");
-        if (Wv == 1) {
-          sssc_stats_wave_kernel<0, 1><<<sgrid, 64, lds, c->stream>>>(sc, o1, pb, stage);
-        } else if (Wv == 8) {
-          sssc_stats_wave_kernel<0, 8><<<sgrid, 512, lds, c->stream>>>(sc, o1, pb, stage);
-        } else if (Wv == 16) {
-          sssc_stats_wave_kernel<0, 16><<<sgrid, 1024, lds, c->stream>>>(sc, o1, pb, stage);
-        } else if (!stage || !sc.dig) {
-          STATS_WAVE(0);
-        } else {
-          switch (c->HW) {  // digests + staging: the instantiations that prefetch the next datapoint
-            case 1: STATS_WAVE(1); break;
-            case 2: STATS_WAVE(2); break;
-            case 4: STATS_WAVE(4); break;
-            case 8: STATS_WAVE(8); break;
-            case 16: STATS_WAVE(16); break;
-            default: STATS_WAVE(0); break;
-          }
-        }
-#undef STATS_WAVE
-        HIP_TRY(hipGetLastError());
-        DBG_SYNC(c, "sssc stats main");
-      }
-      if (debug_fail)  // test hook: a pass that returns between its producers and the pair-bin reduce
-        return fail(EVOAMD_E_INVALID, "debug_fail_stats: statistics pass stopped after its main kernel");
-      if (census) {
-        if (need[0] || need[1] || need[2]) {  // resident states above eight latents + what the quads passed on (atomics)
-          SpanGuard g(c, KID_STATS_OVF);
-          const int tg = c->cand_from_device ? 1 : 2;
-          SpanGuard gl(c, KID_STATS_K9P);
-          const ListIn empty = {c->clist, c->clist_n + 3 * LIST_SHARDS, 0};
-          if (few4) {
-            sssc_big_kernel<1><<<std::max(64u, level_grid(c, 1, tg, total * 256, 1024, 1)), 64, big_lds(SSSC_KCAP), c->stream>>>(
-                sc, need[1] ? cB : empty, none_out, SSSC_KCAP, need[2] ? cC : empty, i3);
-            c->pending_skip |= 2;
-          } else {
-          sssc_big_kernel<1><<<std::max(256u, level_grid(c, 2, tg, total * 256, 8192, 1)), 64, big_lds(16), c->stream>>>(
-              sc, need[2] ? cC : empty, o2, 16, i3);
-          if (need[2])
-            sssc_big_kernel<1><<<level_grid(c, 2, tg, total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
-                sc, i2, none_out, SSSC_KCAP);
-          else
-            c->pending_skip |= 2;
-          }
-          HIP_TRY(hipGetLastError());
-          DBG_SYNC(c, "sssc stats wavefront level (census)");
-        }
-      } else if (need[0] || need[1] || need[2]) {
-        SpanGuard g(c, KID_STATS_OVF);
-        const int tg = c->cand_from_device ? 1 : 2;  // how much is known about the final K^n
-        const size_t cs_lds = sc.cs ? (size_t)3 * H * sizeof(double) : 0;  // in-kernel column sums (LDS)
-        bool merged23 = false;
-        if (need[0]) {
-          const unsigned g4 = pb_clamp(pb, level_grid(c, 0, tg, total, 1024, 256));
-          PB_GRID_CHECK(pb, g4);
-          sssc_small_kernel<4, 1, 2, 256><<<g4, 256, cs_lds, c->stream>>>(sc, i1, o2, pb, o3);
-        }
-        // (statistics mode of the K = 8 register kernel: 256 registers + 736 bytes of scratch per lane, one wave per
-        // SIMD -- measured slower than the wavefront kernel at every size seen: 187 vs ~110 us at 5k states, 0.32
-        // vs 0.25 ms for the pass's levels at the north-star shape; only when forced by option "sssc_k8" = 1)
-        if (c->k8_mode == 1) {
-          if (need[1]) {
-            const unsigned g8 = pb_clamp(pb, level_grid(c, 1, tg, total, 256, 256));
-            PB_GRID_CHECK(pb, g8);
-            sssc_small_kernel<8, 1, 2, 256><<<g8, 256, cs_lds, c->stream>>>(sc, i2, o3, pb, o3);
-          }
-        } else if (need[1] && few_dense_states(c, tg)) {
-          sssc_big_kernel<1><<<level_grid(c, 1, tg, total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
-              sc, i2, none_out, SSSC_KCAP, i3);  // one launch for both wavefront levels (see launch_sssc_lpj)
-          served3 = true;
-          merged23 = true;
-        } else if (need[1]) {
-          sssc_big_kernel<1><<<level_grid(c, 1, tg, total * 256, 4096, 1), 64, big_lds(8), c->stream>>>(sc, i2, o3, 8);
-        }
-        if ((need[2] || c->sing_screen) && !merged23) {
-          sssc_big_kernel<1><<<level_grid(c, 2, tg, total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
-              sc, i3, none_out, SSSC_KCAP);
-          served3 = true;
-        }
-        HIP_TRY(hipGetLastError());
-        DBG_SYNC(c, "sssc stats overflow levels");
-      }
-      if (second_stream && nchunks == 1 && early && !masked) {
-        // every kernel that writes the [Es | Ez] rows has been enqueued: the contraction's stream branches off here
-        HIP_TRY(hipEventRecord(c->ev_chunk[0], main_stream));
-        early_recorded = true;
-      }
-      if (pb.ent) {  // the entries of the main kernel and of the register-kernel levels: one tile pass per block
-        SpanGuard g(c, KID_STATS);
-        pair_bins_reduce_kernel<<<pb.nb * pb.nsh, PB_RTHREADS, (size_t)3 * 2 * pb.rf * H * sizeof(double), c->stream>>>(pb, H, ci > 0);
-        HIP_TRY(hipGetLastError());
-        c->bins_dirty = false;
-        DBG_SYNC(c, "pair bins reduce");
-      }
-      // a skipped level must have found its input list empty (census_lists_kernel / tail_kernel check)
-      skipped = skip_mask(need) & ~(served3 ? 4 : 0);
-    }
-    c->grid_scale = 1.0;
-    if (ci == nchunks - 1) {
-      // (before this block's contraction is enqueued: on one stream the span of the statistics pass must not cover it)
-      // ---- the sums of the scattered moments are complete: mirror / diagonals / column sums
-      {
-        SpanGuard g(c, KID_MISC);
-        if (c->model == EVOAMD_MODEL_BSC) {
-          TailArgs ta = {};  // (as for ES3C below) + a copy of Wq where the device update's inverse wants it
-          if (nchunks == 1 && !masked && !c->reduce_pending) {
-            ta = make_tail_args(c, a, N, false, skipped);
-            tail_done = true;
-          }
-          double *wq_copy = (!c->comm && !masked && c->tmpA) ? c->tmpA : nullptr;
-          c->wq_copy_valid = wq_copy != nullptr;
-          const unsigned fgrid = cdiv((i64)H * H, 256) + (tail_done ? 1 : 0);
-          if (bsc_wave)
-            bsc_finish_kernel<<<fgrid, 256, 0, c->stream>>>(c->acc + a.Wq, c->acc + a.pies, c->acc_base + 4, BSC_CS_SLICES, H,
-                                                             c->partial2, bsc_grid, c->acc + a.sigma, bsc_pb, ta, wq_copy);
-          else
-            bsc_finish_kernel<<<fgrid, 256, 0, c->stream>>>(c->acc + a.Wq, c->acc + a.pies, c->colpart, nblk, H, c->partial2,
-                                                             cdiv(N, 4), c->acc + a.sigma, PairBins{}, ta, wq_copy);
-        } else {
-          const i64 nthr = (i64)H * H > D ? (i64)H * H : D;
-          // the accumulator tail (counters, census, list checks) as one more workgroup of this launch: one block of
-          // datapoints, complete data, no fused E-step reduction pending (that one writes the scalars the tail reads)
-          TailArgs ta = {};
-          if (nchunks == 1 && !masked && !c->reduce_pending) {
-            ta = make_tail_args(c, a, N, census, skipped);
-            tail_done = true;
-          }
-          // complete data: the kernels left the column sums in CS_SLICES slices; else per-block partials of the rows
-          sssc_finish_kernel<<<cdiv(nthr, 256) + (tail_done ? 1 : 0), 256, 0, c->stream>>>(
-              c->acc + a.xss, c->acc + a.xszsz, c->acc + a.xs, c->acc + a.xsz, masked ? c->colpart : sa.cs,
-              masked ? nblk : CS_SLICES, H, c->y2sum, c->acc + a.y2, D, sa.xss_o, sa.xszsz_o, masked ? nullptr : c->PT, pb, ta);
-        }
-        HIP_TRY(hipGetLastError());
-        DBG_SYNC(c, "colsum + finish");
-      }
-      pass.reset();
-    }
-    // ---- this block's part of the K = N contraction
-    if (c->model == EVOAMD_MODEL_SSSC && masked) continue;  // two products from the reconstructed rows, below
-    if (second_stream) {
-      if (!early_recorded) HIP_TRY(hipEventRecord(c->ev_chunk[ci], main_stream));
-      HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_chunk[ci], 0));
-      c->stream = c->stream2;
-    }
-    const bool acc_mode = nchunks > 1, last = ci == nchunks - 1;
-    if (c->model == EVOAMD_MODEL_BSC && c->f32)
-      r = launch_gemm_tn_f32(c, c->Esf + (size_t)n0 * H, H, c->Yf + (size_t)n0 * D, D, c->acc + a.Wp, D, H, D, nc);
-    else if (c->model == EVOAMD_MODEL_BSC)  // Wp = Es^T Y  (H,D); acc was cleared at the top of stats_compute
-      r = launch_gemm_tn(c, c->Es + (size_t)n0 * H, H, Ywp + (size_t)n0 * ldwp, ldwp, c->acc + a.Wp, D, H, D, nc, false, -1,
-                         /*c_is_zero=*/true, acc_mode, last);
-    else
-      // [Y | Es | Ez]^T Ez  ->  Wp (D,H) | sum_n xpt_s (x) xpt_sz (H,H) | sum_n xpt_sz (x) xpt_sz (H,H)
-      // (the last block is Ez^T Ez: symmetric, upper tiles only when its first row is tile-aligned;
-      // launch_gemm_tn drops the hint if its tile does not divide it)
-      r = launch_gemm_tn(c, c->Y + (size_t)n0 * c->ldY, c->ldY, Ez + (size_t)n0 * c->ldY, c->ldY, c->acc + a.sWp, H,
-                         D + 2 * H, H, nc, false, ((D + H) % GEMM_BM) == 0 ? D + H : -1, /*c_is_zero=*/true, acc_mode, last);
-    c->stream = main_stream;
-    if (r) return r;
-  }
-  if (c->model == EVOAMD_MODEL_SSSC && masked) {
-    // y_hat = Ez W^T with the Theta of this E-step: the reconstruction (sssc.py:613-627), the rows the Wp
-    // contraction reads (:631) and, squared over the reliable entries, the trace term of sigma2 (:640-645,751)
-    r = compute_reconstruction(c);
-    if (r) return r;
-    REQUIRE(c->rec_in_stats, "ES3C on incomplete data needs do_reconstruction in every step (sssc.py:630-633)");
-    select_rec_kernel<<<cdiv(N, 4), 256, 0, c->stream>>>(c->Y, c->ldY, c->mask_x, c->mask_infr, c->yhat, N, D, c->Yrec);
+  HIP_TRY(hipGetLastError());
+  DBG_SYNC(c, "bsc stats (wave)");
+  int r = rows_written(c, p, fl);  // the E_q[s] rows are written: the product may start
+  if (r) return r;
+  if (bsc_pb.ent) {
+    pair_bins_reduce_kernel<<<bsc_pb.nb * bsc_pb.nsh, PB_RTHREADS, (size_t)3 * 2 * bsc_pb.rf * H * sizeof(double), c->stream>>>(
+        bsc_pb, H, 0);
     HIP_TRY(hipGetLastError());
-    c->yrec_valid = true;
-    c->rec_in_stats = false;
-    r = launch_gemm_tn(c, Es, c->ldY, Ez, c->ldY, c->acc + a.sWp + (size_t)D * H, H, 2 * H, H, N, false,
-                       (H % GEMM_BM) == 0 ? H : -1, /*c_is_zero=*/true);
-    if (r) return r;
-    r = launch_gemm_tn(c, c->Yrec, D, Ez, c->ldY, c->acc + a.sWp, H, D, H, N, false, -1, /*c_is_zero=*/true);
+    c->bins_dirty = false;
+  }
+  return 0;
+}
+
+// ---- EBSC producers of one block: the round-1 kernel + column-sum pass
+static int stats_bsc_classic(evoamd_ctx *c, const StatsPlan &p, const StatsBlock &blk) {
+  const AccLayout &a = p.a;
+  const i64 n0 = blk.n0, nc = blk.nc;
+  const int H = p.H;
+  {
+    SpanGuard g(c, KID_STATS);
+    with_hw(c->HW, [&](auto hw) {
+      bsc_stats_kernel<decltype(hw)::value><<<cdiv(nc, 4), 256, (size_t)4 * H * sizeof(double), c->stream>>>(
+          c->states + (size_t)n0 * c->S * c->HW, c->lpj + (size_t)n0 * c->L, c->rowmax + n0, c->rowsum + n0, c->yy + n0, nc,
+          c->S, c->S_perm, H, c->HW, c->dpar,
+          c->f32 ? (void *)(c->Esf + (size_t)n0 * H) : (void *)(c->Es + (size_t)n0 * H), c->acc + a.Wq, c->partial2 + n0 / 4,
+          dig_for(c, c->states) ? dig_for(c, c->states) + (size_t)n0 * c->S : nullptr, c->f32 ? 1 : 0);
+    });
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "bsc stats");
+  }
+  {
+    SpanGuard g(c, KID_MISC);
+    if (c->f32)
+      colsum_partial_f32_kernel<<<dim3(cdiv(H, 64), blk.nblk_c), 256, 0, c->stream>>>(c->Esf + (size_t)n0 * H, H, nc, H, p.rpb,
+                                                                                      c->colpart + (size_t)blk.blk0 * H);
+    else
+      colsum_partial_kernel<<<dim3(cdiv(H, 64), blk.nblk_c), 256, 0, c->stream>>>(c->Es + (size_t)n0 * H, H, nc, H, p.rpb,
+                                                                                  c->colpart + (size_t)blk.blk0 * H);
+    HIP_TRY(hipGetLastError());
+  }
+  return 0;
+}
+
+// ---- EBSC producers of one block, then (incomplete data) the rows the Wp contraction reads instead of Y
+static int stats_bsc_block(evoamd_ctx *c, const StatsPlan &p, const StatsBlock &blk, StatsFlow &fl, const double *&Ywp, int &ldwp) {
+  int r = p.bsc_wave ? stats_bsc_wave(c, p, blk, fl) : stats_bsc_classic(c, p, blk);
+  if (r) return r;
+  if (p.masked) {  // incomplete data: the Wp contraction reads y_reconstructed (bsc.py:184-189,211); one block only
+    if (c->rec_in_stats) {
+      r = reconstruct_rows(c);  // y_hat = Es W^T under the Theta of this E-step (_models.py:193-194)
+      if (r) return r;
+    }
+    REQUIRE(c->yrec_valid, "incomplete data: the M-step needs y_reconstructed (bsc.py:186); reconstruct or upload it");
+    Ywp = c->Yrec;
+    ldwp = p.D;
+  }
+  return 0;
+}
+
+// ---- ES3C on incomplete data (sssc.py:276: W[this_x_infr, :]): the state terms belong to the datapoint, so every
+// state goes through the wavefront kernel, which forms W_obs^T W_obs itself and ADDS its moments to the rows (they
+// start from zero here)
+static int stats_sssc_masked_block(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep) {
+  const i64 N = p.N;
+  const int H = p.H;
+  const i64 total = N * (i64)c->S;
+  HIP_TRY(hipMemset2DAsync(ep.Es, (size_t)c->ldY * sizeof(double), 0, (size_t)3 * H * sizeof(double), (size_t)N, c->stream));
+  const ListIn nat = {nullptr, nullptr, 0};
+  {
+    SpanGuard g(c, KID_STATS);
+    sssc_big_kernel<1><<<(int)std::min<i64>(total, 65536), 64, big_lds(8), c->stream>>>(ep.sa, nat, ep.o3, 8);
+    sssc_big_kernel<1><<<1024, 64, big_lds(SSSC_KCAP), c->stream>>>(ep.sa, ep.i3, ep.none_out, SSSC_KCAP);
+    HIP_TRY(hipGetLastError());
+  }
+  SpanGuard g(c, KID_MISC);
+  colsum_partial_kernel<<<dim3(cdiv(3 * H, 64), p.nblk), 256, 0, c->stream>>>(ep.Es, c->ldY, N, 3 * H, p.rpb, c->colpart);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ES3C on complete data: this block's rows of the argument block, its census lists and the form of its main kernel
+static Es3cBlock sssc_block_setup(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep, const StatsBlock &blk) {
+  const SsscArgs &sa = ep.sa;
+  const i64 n0 = blk.n0;
+  const int H = p.H, D = p.D;
+  Es3cBlock eb = {};
+  SsscArgs &sc = eb.sc;
+  sc = sa;  // this block's rows
+  sc.states = sa.states + (size_t)n0 * c->S * c->HW;
+  if (sa.dig) sc.dig = sa.dig + (size_t)n0 * c->S;
+  sc.Bm = sa.Bm + (size_t)n0 * H;
+  sc.yy = sa.yy + n0;
+  sc.lpj_in = sa.lpj_in + (size_t)n0 * sa.ldo;
+  sc.rowmax = sa.rowmax + n0;
+  sc.rowsum = sa.rowsum + n0;
+  sc.Es = sa.Es + (size_t)n0 * sa.ldE;
+  sc.Ez = sa.Ez + (size_t)n0 * sa.ldE;
+  sc.Ed = sa.Ed + (size_t)n0 * sa.ldE;
+  sc.N = blk.nc;
+  eb.total = blk.nc * (i64)c->S;
+  const int ccap = (int)list_cap(eb.total);
+  eb.cA = {c->clist, c->clist_n, ccap};
+  eb.cB = {c->clist + c->clist_words, c->clist_n + LIST_SHARDS, ccap};
+  eb.cC = {c->clist + 2 * c->clist_words, c->clist_n + 2 * LIST_SHARDS, ccap};
+  if (p.census && c->stats_flat && c->S <= FLAT_T && (H % 2) == 0 && (D % 2) == 0 && sc.Ez == sc.Es + H && c->stats_waves == 0) {
+    int flatG = FLAT_T / c->S;
+    const int gmax = (int)(((size_t)140 * 1024 / sizeof(double) - (size_t)7 * H) / ((size_t)4 * H + 4));
+    if (flatG > gmax) flatG = gmax;
+    if (flatG > 4 * FLAT_T / H) flatG = 4 * FLAT_T / H;  // the round's B rows: at most two 16-byte pieces per thread
+    if (flatG >= 1) eb.flat_lds = ((size_t)H * (4 * flatG + 7) + 4 * flatG) * sizeof(double);
+    eb.flatG = flatG;
+  }
+  eb.few4 = p.census && eb.flatG < 1 && few_above4(c, p.tg);
+  return eb;
+}
+
+// ---- census mode, the quad levels FIRST: records of the listed states (read back by the wave-per-datapoint kernel), their
+// diagonal second moments into the column-sum slices, their pairs into the bins (regions shared by workgroup index)
+static int stats_sssc_census_quads(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep, const Es3cBlock &eb, StatsFlow &fl) {
+  const bool *need = ep.need;
+  const PairBins &pb = fl.pb;
+  int r = ensure_census(c);
+  if (r) return r;
+  if (need[0] || need[1]) {
+    SpanGuard g(c, KID_STATS_OVF);
+    const unsigned gcap = pb.ent ? (unsigned)std::min(2048, pb.nwg) : 2048u;
+    const size_t dl = (size_t)p.H * sizeof(double);
+    // (the bins' region counters are zero here: pair_bins_reduce_kernel clears what it reads)
+    if (need[0]) {
+      SpanGuard gl(c, KID_STATS_K34);
+      const unsigned qg = quad_grid(c, 0, p.tg, eb.total, gcap);
+      PB_GRID_CHECK(pb, qg);
+      sssc_quad_kernel<1, 1, 2><<<qg, 256, dl, c->stream>>>(eb.sc, eb.cA, ep.none_out, ep.o3, pb, c->ovf_rec);
+    }
+    if (need[1] && !eb.few4) {
+      SpanGuard gl(c, KID_STATS_K58);
+      const unsigned qg = quad_grid(c, 1, p.tg, eb.total, gcap);
+      PB_GRID_CHECK(pb, qg);
+      sssc_quad_kernel<2, 1, 2><<<qg, 256, dl, c->stream>>>(eb.sc, eb.cB, ep.none_out, ep.o3, pb, c->ovf_rec);
+    }
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "sssc stats quad levels");
+  }
+  return 0;
+}
+
+// ---- the main kernel of an ES3C block on complete data: thread-per-state (flat) or wave-per-datapoint
+static int stats_sssc_main(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep, const Es3cBlock &eb, const StatsBlock &blk,
+                           StatsFlow &fl) {
+  const PairBins &pb = fl.pb;
+  const SsscArgs &sc = eb.sc;
+  const ListOut &o1 = ep.o1;
+  const i64 nc = blk.nc;
+  const int H = p.H;
+  const bool census = p.census;
+  if (eb.flatG >= 1) {
+    SpanGuard g(c, KID_STATS);
+    int fgrid = (int)std::min<i64>(cdiv(nc, eb.flatG), (i64)c->n_cu);
+    if (pb.ent && fgrid > pb.nwg) fgrid = pb.nwg;
+    PB_GRID_CHECK(pb, fgrid);
+    sssc_stats_flat_kernel<<<fgrid, FLAT_T, eb.flat_lds, c->stream>>>(sc, pb, c->ovf_rec, eb.flatG);
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "sssc stats main (flat)");
+    return 0;
+  }
+  // one wave per datapoint, persistent workgroups: W x 2 H doubles of rows + 3 H of column accumulators in LDS
+  const int Wv = p.waves;
+  size_t lds = (size_t)(Wv * 2 + 3) * H * sizeof(double);
+  const size_t lds_static = 1024 + (size_t)Wv * 512 + 128;  // the kernel's bin counters and overflow buffers
+  REQUIRE(lds <= 150 * 1024, "ES3C statistics: H too large for the LDS rows (H <= 3800)");
+  // B row of each wave's datapoint + the singleton table in LDS too when that still leaves two workgroups per CU
+  const size_t lds_staged = lds + (size_t)(Wv + 4) * H * sizeof(double);
+  const int stage = (H % 2) == 0 && 2 * (lds_staged + lds_static) <= 160 * 1024 && c->stats_stage != 0;
+  if (stage) lds = lds_staged;
+  const int per_cu = stats_per_cu(lds + lds_static, 32 / Wv);  // 32 waves per CU
+  SpanGuard g(c, KID_STATS);
+  // a wave per datapoint while that is at most a few rounds of resident workgroups (a second datapoint per wave
+  // doubles the kernel's critical path at small N), a persistent grid-stride loop beyond
+  int sgrid = (int)std::min<i64>(cdiv(nc, Wv), (i64)c->n_cu * per_cu * 4);
+  if (pb.ent && sgrid > pb.nwg) sgrid = pb.nwg;  // one private region per producer workgroup and bin
+  PB_GRID_CHECK(pb, sgrid);
+  auto wave4 = [&](auto hw) {
+    constexpr int HWT = decltype(hw)::value;
+    if (census)
+      sssc_stats_wave_kernel<HWT, 4, true><<<sgrid, 256, lds, c->stream>>>(sc, o1, pb, stage, c->ovf_rec, eb.few4 ? 4 : 8);
+    else
+      sssc_stats_wave_kernel<HWT, 4><<<sgrid, 256, lds, c->stream>>>(sc, o1, pb, stage);
+  };
+  REQUIRE(!census || Wv == 4, "census lists need the 4-wave statistics kernel (option stats_waves)");
+  if (Wv == 1) {
+    sssc_stats_wave_kernel<0, 1><<<sgrid, 64, lds, c->stream>>>(sc, o1, pb, stage);
+  } else if (Wv == 8) {
+    sssc_stats_wave_kernel<0, 8><<<sgrid, 512, lds, c->stream>>>(sc, o1, pb, stage);
+  } else if (Wv == 16) {
+    sssc_stats_wave_kernel<0, 16><<<sgrid, 1024, lds, c->stream>>>(sc, o1, pb, stage);
+  } else if (!stage || !sc.dig) {
+    wave4(std::integral_constant<int, 0>{});
+  } else {
+    with_hw(c->HW, wave4);  // digests + staging: the instantiations that prefetch the next datapoint
+  }
+  HIP_TRY(hipGetLastError());
+  DBG_SYNC(c, "sssc stats main");
+  return 0;
+}
+
+// ---- the levels behind the main kernel, census form: resident states above eight latents + what the quads passed on
+// (atomics)
+static int stats_sssc_census_levels(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep, const Es3cBlock &eb) {
+  const bool *need = ep.need;
+  const SsscArgs &sc = eb.sc;
+  const i64 total = eb.total;
+  const int tg = p.tg;
+  if (need[0] || need[1] || need[2]) {
+    SpanGuard g(c, KID_STATS_OVF);
+    SpanGuard gl(c, KID_STATS_K9P);
+    const ListIn empty = {c->clist, c->clist_n + 3 * LIST_SHARDS, 0};
+    if (eb.few4) {
+      sssc_big_kernel<1><<<std::max(64u, level_grid(c, 1, tg, total * 256, 1024, 1)), 64, big_lds(SSSC_KCAP), c->stream>>>(
+          sc, need[1] ? eb.cB : empty, ep.none_out, SSSC_KCAP, need[2] ? eb.cC : empty, ep.i3);
+      c->pending_skip |= 2;
+    } else {
+      sssc_big_kernel<1><<<std::max(256u, level_grid(c, 2, tg, total * 256, 8192, 1)), 64, big_lds(16), c->stream>>>(
+          sc, need[2] ? eb.cC : empty, ep.o2, 16, ep.i3);
+      if (need[2])
+        sssc_big_kernel<1><<<level_grid(c, 2, tg, total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
+            sc, ep.i2, ep.none_out, SSSC_KCAP);
+      else
+        c->pending_skip |= 2;
+    }
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "sssc stats wavefront level (census)");
+  }
+  return 0;
+}
+
+// ---- the levels behind the main kernel, chains form: list 1 -> K = 4 -> list 2 -> K = 8 / wavefront -> list 3 -> wavefront
+static int stats_sssc_chain_levels(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep, const Es3cBlock &eb, StatsFlow &fl) {
+  const bool *need = ep.need;
+  const PairBins &pb = fl.pb;
+  const SsscArgs &sc = eb.sc;
+  const i64 total = eb.total;
+  const int tg = p.tg;
+  if (need[0] || need[1] || need[2]) {
+    SpanGuard g(c, KID_STATS_OVF);
+    const size_t cs_lds = sc.cs ? (size_t)3 * p.H * sizeof(double) : 0;  // in-kernel column sums (LDS)
+    bool merged23 = false;
+    if (need[0]) {
+      const unsigned g4 = pb_clamp(pb, level_grid(c, 0, tg, total, 1024, 256));
+      PB_GRID_CHECK(pb, g4);
+      sssc_small_kernel<4, 1, 2, 256><<<g4, 256, cs_lds, c->stream>>>(sc, ep.i1, ep.o2, pb, ep.o3);
+    }
+    // (statistics mode of the K = 8 register kernel: 256 registers + 736 bytes of scratch per lane, one wave per
+    // SIMD -- measured slower than the wavefront kernel at every size seen: 187 vs ~110 us at 5k states, 0.32
+    // vs 0.25 ms for the pass's levels at the north-star shape; only when forced by option "sssc_k8" = 1)
+    if (c->k8_mode == 1) {
+      if (need[1]) {
+        const unsigned g8 = pb_clamp(pb, level_grid(c, 1, tg, total, 256, 256));
+        PB_GRID_CHECK(pb, g8);
+        sssc_small_kernel<8, 1, 2, 256><<<g8, 256, cs_lds, c->stream>>>(sc, ep.i2, ep.o3, pb, ep.o3);
+      }
+    } else if (need[1] && few_dense_states(c, tg)) {
+      sssc_big_kernel<1><<<level_grid(c, 1, tg, total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
+          sc, ep.i2, ep.none_out, SSSC_KCAP, ep.i3);  // one launch for both wavefront levels (see launch_sssc_lpj)
+      fl.served3 = true;
+      merged23 = true;
+    } else if (need[1]) {
+      sssc_big_kernel<1><<<level_grid(c, 1, tg, total * 256, 4096, 1), 64, big_lds(8), c->stream>>>(sc, ep.i2, ep.o3, 8);
+    }
+    if ((need[2] || c->sing_screen) && !merged23) {
+      sssc_big_kernel<1><<<level_grid(c, 2, tg, total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
+          sc, ep.i3, ep.none_out, SSSC_KCAP);
+      fl.served3 = true;
+    }
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "sssc stats overflow levels");
+  }
+  return 0;
+}
+
+// ---- ES3C on complete data, one block: census quad levels, main kernel, the levels behind it, pair-bin reduce
+static int stats_sssc_block(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep, const StatsBlock &blk, StatsFlow &fl,
+                            bool debug_fail) {
+  PairBins &pb = fl.pb;
+  const Es3cBlock eb = sssc_block_setup(c, p, ep, blk);
+  int r;
+  if (pb.ent) c->bins_dirty = true;  // this block's producers append; until its reduce (which zeroes the counters)
+  if (blk.ci > 0) {  // the previous block's overflow census joins the running sum; fresh lists for this block
+    census_lists_kernel<<<1, 256, 0, c->stream>>>(c->list_n, LIST_SHARDS, skip_mask(ep.need), c->err, c->census);
+    HIP_TRY(hipGetLastError());
+  }
+  if (eb.flatG >= 1 && pb.ent) {
+    // one resident workgroup per CU produces: the bins' entry space re-cut into n_cu regions per bin
+    const i64 per_bin = (i64)pb.nwg * pb.cap;
+    pb.nwg = std::min(pb.nwg, c->n_cu);
+    pb.cap = (int)std::min<i64>(per_bin / pb.nwg, 1 << 30);
+  }
+  if (p.census) {
+    r = stats_sssc_census_quads(c, p, ep, eb, fl);
     if (r) return r;
   }
-  if (second_stream) {
+  r = stats_sssc_main(c, p, ep, eb, blk, fl);
+  if (r) return r;
+  if (debug_fail)  // test hook: a pass that returns between its producers and the pair-bin reduce
+    return fail(EVOAMD_E_INVALID, "debug_fail_stats: statistics pass stopped after its main kernel");
+  r = p.census ? stats_sssc_census_levels(c, p, ep, eb) : stats_sssc_chain_levels(c, p, ep, eb, fl);
+  if (r) return r;
+  r = rows_written(c, p, fl);
+  if (r) return r;
+  if (pb.ent) {  // the entries of the main kernel and of the register-kernel levels: one tile pass per block
+    SpanGuard g(c, KID_STATS);
+    pair_bins_reduce_kernel<<<pb.nb * pb.nsh, PB_RTHREADS, (size_t)3 * 2 * pb.rf * p.H * sizeof(double), c->stream>>>(pb, p.H, blk.ci > 0);
+    HIP_TRY(hipGetLastError());
+    c->bins_dirty = false;
+    DBG_SYNC(c, "pair bins reduce");
+  }
+  // a skipped level must have found its input list empty (census_lists_kernel / tail_kernel check)
+  fl.skipped = skip_mask(ep.need) & ~(fl.served3 ? 4 : 0);
+  return 0;
+}
+
+// ---- the sums of the scattered moments are complete: mirror / diagonals / column sums, with the accumulator tail riding
+// in the launch where it can
+static int stats_finish(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep, StatsFlow &fl) {
+  const AccLayout &a = p.a;
+  const i64 N = p.N;
+  const int H = p.H, D = p.D;
+  const bool masked = p.masked;
+  SpanGuard g(c, KID_MISC);
+  if (c->model == EVOAMD_MODEL_BSC) {
+    TailArgs ta = {};  // (as for ES3C below) + a copy of Wq where the device update's inverse wants it
+    if (p.nchunks == 1 && !masked && !c->reduce_pending) {
+      ta = make_tail_args(c, a, N, false, fl.skipped);
+      fl.tail_done = true;
+    }
+    double *wq_copy = (!c->comm && !masked && c->tmpA) ? c->tmpA : nullptr;
+    c->wq_copy_valid = wq_copy != nullptr;
+    const unsigned fgrid = cdiv((i64)H * H, 256) + (fl.tail_done ? 1 : 0);
+    if (p.bsc_wave)
+      bsc_finish_kernel<<<fgrid, 256, 0, c->stream>>>(c->acc + a.Wq, c->acc + a.pies, c->acc_base + 4, BSC_CS_SLICES, H,
+                                                       c->partial2, fl.bsc_grid, c->acc + a.sigma, fl.bsc_pb, ta, wq_copy);
+    else
+      bsc_finish_kernel<<<fgrid, 256, 0, c->stream>>>(c->acc + a.Wq, c->acc + a.pies, c->colpart, p.nblk, H, c->partial2,
+                                                       cdiv(N, 4), c->acc + a.sigma, PairBins{}, ta, wq_copy);
+  } else {
+    const SsscArgs &sa = ep.sa;
+    const i64 nthr = (i64)H * H > D ? (i64)H * H : D;
+    // the accumulator tail (counters, census, list checks) as one more workgroup of this launch: one block of
+    // datapoints, complete data, no fused E-step reduction pending (that one writes the scalars the tail reads)
+    TailArgs ta = {};
+    if (p.nchunks == 1 && !masked && !c->reduce_pending) {
+      ta = make_tail_args(c, a, N, p.census, fl.skipped);
+      fl.tail_done = true;
+    }
+    // complete data: the kernels left the column sums in CS_SLICES slices; else per-block partials of the rows
+    sssc_finish_kernel<<<cdiv(nthr, 256) + (fl.tail_done ? 1 : 0), 256, 0, c->stream>>>(
+        c->acc + a.xss, c->acc + a.xszsz, c->acc + a.xs, c->acc + a.xsz, masked ? c->colpart : sa.cs,
+        masked ? p.nblk : CS_SLICES, H, c->y2sum, c->acc + a.y2, D, sa.xss_o, sa.xszsz_o, masked ? nullptr : c->PT, fl.pb, ta);
+  }
+  HIP_TRY(hipGetLastError());
+  DBG_SYNC(c, "colsum + finish");
+  return 0;
+}
+
+// ---- one block's part of the K = N contraction (on stream2 where the pass has a second stream)
+static int stats_contract_block(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep, const StatsBlock &blk, const StatsFlow &fl,
+                                const double *Ywp, int ldwp) {
+  const AccLayout &a = p.a;
+  const i64 n0 = blk.n0, nc = blk.nc;
+  const int H = p.H, D = p.D, ci = blk.ci;
+  int r;
+  if (p.second_stream) {
+    if (!fl.early_recorded) HIP_TRY(hipEventRecord(c->ev_chunk[ci], p.main_stream));
+    HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_chunk[ci], 0));
+    c->stream = c->stream2;
+  }
+  const bool acc_mode = p.nchunks > 1, last = ci == p.nchunks - 1;
+  if (c->model == EVOAMD_MODEL_BSC && c->f32)
+    r = launch_gemm_tn_f32(c, c->Esf + (size_t)n0 * H, H, c->Yf + (size_t)n0 * D, D, c->acc + a.Wp, D, H, D, nc);
+  else if (c->model == EVOAMD_MODEL_BSC)  // Wp = Es^T Y  (H,D); acc was cleared at the top of stats_compute
+    r = launch_gemm_tn(c, c->Es + (size_t)n0 * H, H, Ywp + (size_t)n0 * ldwp, ldwp, c->acc + a.Wp, D, H, D, nc, false, -1,
+                       /*c_is_zero=*/true, acc_mode, last);
+  else
+    // [Y | Es | Ez]^T Ez  ->  Wp (D,H) | sum_n xpt_s (x) xpt_sz (H,H) | sum_n xpt_sz (x) xpt_sz (H,H)
+    // (the last block is Ez^T Ez: symmetric, upper tiles only when its first row is tile-aligned;
+    // launch_gemm_tn drops the hint if its tile does not divide it)
+    r = launch_gemm_tn(c, c->Y + (size_t)n0 * c->ldY, c->ldY, ep.Ez + (size_t)n0 * c->ldY, c->ldY, c->acc + a.sWp, H,
+                       D + 2 * H, H, nc, false, ((D + H) % GEMM_BM) == 0 ? D + H : -1, /*c_is_zero=*/true, acc_mode, last);
+  c->stream = p.main_stream;
+  return r;
+}
+
+// ---- ES3C on incomplete data: y_hat = Ez W^T with the Theta of this E-step: the reconstruction (sssc.py:613-627), the
+// rows the Wp contraction reads (:631) and, squared over the reliable entries, the trace term of sigma2 (:640-645,751);
+// then the two products from the reconstructed rows
+static int stats_sssc_masked_products(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep) {
+  const AccLayout &a = p.a;
+  const int H = p.H, D = p.D;
+  int r = reconstruct_rows(c, "ES3C on incomplete data needs do_reconstruction in every step (sssc.py:630-633)");
+  if (r) return r;
+  r = launch_gemm_tn(c, ep.Es, c->ldY, ep.Ez, c->ldY, c->acc + a.sWp + (size_t)D * H, H, 2 * H, H, p.N, false,
+                     (H % GEMM_BM) == 0 ? H : -1, /*c_is_zero=*/true);
+  if (r) return r;
+  return launch_gemm_tn(c, c->Yrec, D, ep.Ez, c->ldY, c->acc + a.sWp, H, D, H, p.N, false, -1, /*c_is_zero=*/true);
+}
+
+// ---- the second stream joins (or the caller will), the fused E-step's reduction, the accumulator tail where it did not
+// ride in the finish launch, the all-reduce
+static int stats_epilogue(evoamd_ctx *c, const StatsPlan &p, const StatsFlow &fl) {
+  const AccLayout &a = p.a;
+  const i64 N = p.N;
+  if (p.second_stream) {
     HIP_TRY(hipEventRecord(c->ev_join, c->stream2));
-    if (fork_gemm)
+    if (p.fork_gemm)
       c->gemm_forked = true;  // the caller joins (after the H x H inverses)
     else
-      HIP_TRY(hipStreamWaitEvent(main_stream, c->ev_join, 0));
+      HIP_TRY(hipStreamWaitEvent(p.main_stream, c->ev_join, 0));
   }
   {
     int rfr = flush_reduce(c);  // fused E-step: free-energy term and counters into the scalar block (beside the forked contraction)
@@ -3318,13 +3399,13 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
   }
   {
     SpanGuard g(c, KID_MISC);
-    if (!tail_done) tail_kernel<<<1, 256, 0, c->stream>>>(make_tail_args(c, a, N, census, skipped));
+    if (!fl.tail_done) tail_kernel<<<1, 256, 0, c->stream>>>(make_tail_args(c, a, N, p.census, fl.skipped));
     HIP_TRY(hipGetLastError());
     DBG_SYNC(c, "stats contraction + tail");
     c->lists_clean = c->model == EVOAMD_MODEL_SSSC;
     if (c->lists_clean) c->pending_skip = 0;
     if (c->model == EVOAMD_MODEL_SSSC && c->mask_infr) {  // tail[7] = sum over reliable entries of y_hat^2
-      masked_sqsum_kernel<<<256, 256, 0, c->stream>>>(c->yhat, c->mask_infr, N * (i64)D, c->acc + a.tail + 7);
+      masked_sqsum_kernel<<<256, 256, 0, c->stream>>>(c->yhat, c->mask_infr, N * (i64)p.D, c->acc + a.tail + 7);
       HIP_TRY(hipGetLastError());
     }
   }
@@ -3338,6 +3419,123 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
     SpanGuard g(c, KID_ALLREDUCE);
     RCCL_TRY(g_rccl.AllReduce(c->acc, c->acc, (size_t)c->acc_n, /*ncclDouble*/ 8, /*ncclSum*/ 0, c->comm, c->stream));
   }
+  return 0;
+}
+
+// ES3C: the argument block of the scatter kernels, the levels the final K^n needs, fresh on-the-fly lists
+static int stats_sssc_pass(evoamd_ctx *c, const StatsPlan &p, Es3cPass &ep) {
+  const AccLayout &a = p.a;
+  const i64 N = p.N;
+  const int H = p.H, D = p.D;
+  ep.Es = c->model == EVOAMD_MODEL_SSSC ? c->Y + D : c->Es;
+  ep.Ez = c->Y + D + H;
+  ep.Ed = c->Y + D + 2 * H;
+  if (c->model != EVOAMD_MODEL_SSSC) return 0;
+  SsscArgs &sa = ep.sa;
+  Batch b = {c->states, nullptr, c->Y, c->Bm, c->yy, N, c->S, 0, nullptr, c->L, c->S_perm, c->flags, KID_STATS, 0};
+  b.mask = c->mask_infr;
+  sa = sssc_args(c, b);
+  sa.lpj_in = c->lpj;
+  sa.rowmax = c->rowmax;
+  sa.rowsum = c->rowsum;
+  sa.Es = ep.Es;
+  sa.Ez = ep.Ez;
+  sa.Ed = ep.Ed;
+  sa.ldE = c->ldY;
+  sa.xss = c->acc + a.xss;
+  sa.xszsz = c->acc + a.xszsz;
+  sa.xss_o = c->acc_base + c->pre_n;
+  sa.xszsz_o = c->acc_base + c->pre_n + (size_t)H * H;
+  if (!p.masked) sa.cs = c->acc_base + 4;  // the kernels sum the columns of [Es | Ez] and the diagonal second moments themselves
+  const int cap = (int)list_cap(N * (i64)c->S);
+  ep.o1 = {c->list1, c->list_n + 0 * LIST_SHARDS, cap};
+  ep.o2 = {c->list2, c->list_n + 1 * LIST_SHARDS, cap};
+  ep.o3 = {c->list3, c->list_n + 2 * LIST_SHARDS, cap};
+  ep.i1 = {ep.o1.items, ep.o1.counts, cap};
+  ep.i2 = {ep.o2.items, ep.o2.counts, cap};
+  ep.i3 = {ep.o3.items, ep.o3.counts, cap};
+  // the final K^n is made of resident states and accepted candidates: same levels as the candidates
+  levels_for(c, 1, ep.need);
+  return zero_lists(c);
+}
+
+// Everything of evoamd_stats up to (and including) the all-reduce; the packed accumulator stays on
+// the device.  tail[7] receives ljc of the Theta the E-step ran with.
+// fork_gemm: the caller promises to call join_fork before it reads the contraction's block of acc
+// (evoamd_mstep_device: after the H x H inverses).  With a communicator (ES3C) the packed accumulator is
+// all-reduced in two pieces: everything the inverses read here, the contraction's block at the join --
+// all RCCL calls stay on the main stream, in the same order on every rank.  Not while kernels are being
+// timed on the main stream.
+static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
+  REQUIRE(c && c->configured && c->have_data && c->have_params, "configure, upload_data and set_params first");
+  StatsPlan p;
+  int r = stats_plan(c, fork_gemm, p);
+  if (r) return r;
+  // ---- preamble
+  r = join_fork(c);  // a previous call that failed between fork and join must not race with the memset below
+  if (r) return r;
+  HIP_TRY(hipSetDevice(c->device));
+  r = ensure_bins_capacity(c);
+  if (r) return r;
+  if (c->bins_dirty && c->pbins.gcnt)  // an earlier pass returned between its producers and the reduce: stale region counts
+    HIP_TRY(hipMemsetAsync(c->pbins.gcnt, 0, (size_t)c->pbins.nb * c->pbins.nwg * sizeof(int), c->stream));
+  c->bins_dirty = false;
+  // test hook: consumed by every pass (it stops only an ES3C pass on complete data, after its main kernel)
+  const bool debug_fail = c->debug_fail_stats != 0;
+  c->debug_fail_stats = 0;
+  if (!c->acc_clean)  // (else: zeroed by the selection kernel on its way)
+    HIP_TRY(hipMemsetAsync(c->acc_base, 0, (size_t)(c->ovf_n + c->acc_n) * sizeof(double), c->stream));
+  c->acc_clean = false;
+  c->yhat_valid = c->stats_rows_valid = false;
+  r = ensure_B(c);
+  if (r) return r;
+  if (!c->rows_fresh) {  // otherwise vary_kn left rowmax / rowsum / dpar[DP_FS] behind
+    r = row_lse(c, c->lpj, p.N, c->L, c->rowmax, c->rowsum, c->dpar + DP_FS);
+    if (r) return r;
+  }
+  c->fork_spare = p.fork_spare;
+  StatsFlow fl;
+  // the whole statistics pass (everything that reads K^n + lpj and leaves the M-step sums, the GEMM aside)
+  std::unique_ptr<SpanGuard> pass(new SpanGuard(c, KID_STATS_PASS));
+  r = ensure_colpart(c, (size_t)p.nblk * (c->model == EVOAMD_MODEL_BSC ? p.H : 3 * p.H));
+  if (r) return r;
+  Es3cPass ep;
+  r = stats_sssc_pass(c, p, ep);
+  if (r) return r;
+  const double *Ywp = c->Y;  // EBSC: what the Wp contraction reads
+  int ldwp = c->ldY;
+  if (c->model == EVOAMD_MODEL_SSSC && !p.masked && stats_bins_pay(c)) fl.pb = c->pbins;
+  // ---- the blocks of datapoints
+  for (int ci = 0; ci < p.nchunks; ci++) {
+    const i64 n0 = (i64)ci * p.rows_per_chunk;
+    const i64 nc = std::min<i64>(p.rows_per_chunk, p.N - n0);
+    const StatsBlock blk = {ci, n0, nc, (int)(n0 / p.rpb), (int)cdiv(nc, p.rpb)};
+    c->grid_scale = (double)nc / (double)p.N;
+    if (c->model == EVOAMD_MODEL_BSC)
+      r = stats_bsc_block(c, p, blk, fl, Ywp, ldwp);
+    else if (p.masked)
+      r = stats_sssc_masked_block(c, p, ep);
+    else
+      r = stats_sssc_block(c, p, ep, blk, fl, debug_fail);
+    if (r) return r;
+    c->grid_scale = 1.0;
+    if (ci == p.nchunks - 1) {
+      // (before this block's contraction is enqueued: on one stream the span of the statistics pass must not cover it)
+      r = stats_finish(c, p, ep, fl);
+      if (r) return r;
+      pass.reset();
+    }
+    if (c->model == EVOAMD_MODEL_SSSC && p.masked) continue;  // two products from the reconstructed rows, below
+    r = stats_contract_block(c, p, ep, blk, fl, Ywp, ldwp);
+    if (r) return r;
+  }
+  // ---- epilogue
+  if (c->model == EVOAMD_MODEL_SSSC && p.masked) {
+    r = stats_sssc_masked_products(c, p, ep);
+    if (r) return r;
+  }
+  r = stats_epilogue(c, p, fl);
+  if (r) return r;
   c->stats_rows_valid = true;
   return 0;
 }
@@ -3677,7 +3875,7 @@ static int mailbox_roundtrip(evoamd_ctx *c, bool with_theta, bool prefetch = fal
   // (measured, ms per iteration lazy / eager Theta: c4 3.94 -> 3.88 / 4.43 -> 4.05, N / 8 shard 1.13 -> 1.08 / 1.37 -> 1.60,
   // c2 0.386 -> 0.404: the event pair costs ~10 us, and a 3 MB Theta copy beside the refresh only delays the host -- so
   // only the mailbox of a long iteration goes there, with Theta on board only at the north-star size)
-  const double it_flops = c->model == EVOAMD_MODEL_SSSC ? 2.0 * (double)c->N * (c->D + 2.0 * c->H) * c->H : 2.0 * (double)c->N * c->D * c->H;
+  const double it_flops = contraction_flops(c);
   if (!folded && c->mbox_side && !dma && it_flops >= (with_theta ? 8e10 : 8e9)) {
     HIP_TRY(hipEventRecord(c->ev_mbox, c->stream));
     HIP_TRY(hipStreamWaitEvent(c->stream_copy, c->ev_mbox, 0));
@@ -3824,8 +4022,7 @@ extern "C" int evoamd_mstep_device(evoamd_ctx *c, int learn_mask, double *tail_o
   if (learn_mask) {
     {
       // lazy Theta with the mailbox on the main stream: the header rides in the update's last kernel
-      const double it_flops = c->model == EVOAMD_MODEL_SSSC ? 2.0 * (double)c->N * (c->D + 2.0 * c->H) * c->H
-                                                            : 2.0 * (double)c->N * c->D * c->H;
+      const double it_flops = contraction_flops(c);
       c->mbox_fold_req = theta_home && !(c->mbox_side && it_flops >= 8e9);
     }
     r = update_params_device(c, learn_mask, false, /*defer_refresh=*/true, bak_inline);

@@ -197,4 +197,4 @@ def test_every_binned_producer_launch_has_its_grid_checked():
         assert re.fullmatch(r"\w+", grid), (kern, grid)
         before = hip[:at].splitlines()[-45:]
         assert any(re.search(r"PB_GRID_CHECK\(%s, %s\)" % (pbs[0], grid), l) for l in before), (kern, grid)
-    assert n >= 10, n
+    assert n >= 11, n
