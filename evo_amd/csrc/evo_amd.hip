@@ -229,7 +229,6 @@ struct evoamd_ctx {
   int theta_gen = 0;        // stamp of the current Theta (one per sssc_tables_kernel launch)
   int gemm_grouped = 1;  // option "gemm_grouped": grouped split-K instead of stream-K where whole chunks fill the grid
   int gemm_per_xcd = 0;  // option "gemm_per_xcd" (experiments): K chunks per XCD of the 128-tile contraction, 0 = automatic
-  double grid_scale = 1.0;  // share of the datapoints the launch being prepared covers (level_grid expectations)
   double *census = nullptr;  // 4 doubles at the head of acc_base: overflow census of the earlier blocks of a chunked statistics pass
   i64 pre_n = 4;
   hipEvent_t ev_chunk[16] = {};
@@ -243,8 +242,6 @@ struct evoamd_ctx {
   bool lists_clean = false;       // overflow counters are zero (a previous kernel cleared them)
   int pending_skip = 0;           // overflow levels the last lpj chain(s) did not launch: the kernel that clears the
                                   // list counters next checks that their lists stayed empty (err |= 4 otherwise)
-  bool conservative_levels = false;  // the pass being enqueued runs before the host has seen the counts of the
-                                     // K^n it evaluates (prefetched pass): choose its levels like a candidate batch
   int pays_agreed = -1;           // split all-reduce: -1 not yet agreed over the ranks, else the common decision
   int k8_mode = -1;  // ES3C states with 5..8 active latents: 1 = K=8 register kernel, 0 = LDS wavefront
                      // kernel, -1 = choose per launch from the counts of the last statistics pass
@@ -361,7 +358,6 @@ struct evoamd_ctx {
   double *fpart = nullptr;  // 3 x 1024 chain sums of fused_reduce3_kernel
   unsigned long long *fprof = nullptr;  // -DFUSED_PROFILE builds
   bool last_estep_fused = false;
-  bool levels_only = false;  // launch_sssc_lpj<0>: the census levels without the main kernel (the fused E-step evaluates <= 2 latents itself)
   bool reduce_pending = false;  // fused E-step: rowF / rowcnt not yet summed into the scalar block (fused_reduce3_kernel)
   long fused_calls = 0, unfused_calls = 0;
   int debug_poison_list = 0;  // option "debug_poison_list" (tests): the next census gets an out-of-range entry
@@ -1671,7 +1667,7 @@ struct Batch {
   int ldo, col0;
   unsigned *flags;
   int kid;
-  int tag;  // 0 resident K^n, 1 candidate batch, 2 anything else (names the kernel instantiation)
+  int tag;  // 0 resident K^n, 1 candidate batch, 2 anything else: names the kernel instantiations (batch_hints)
   const uint8_t *mask = nullptr;  // EBSC incomplete data: x_infr rows of this batch's datapoints
 };
 
@@ -1785,11 +1781,47 @@ static SsscArgs sssc_args(evoamd_ctx *c, const Batch &b) {
 
 static size_t big_lds(int kc) { return (size_t)(4 * kc * kc + 5 * kc) * sizeof(double) + (size_t)kc * sizeof(int); }
 
-// ES3C lpj of a batch: states are binned by their number of active latents on the fly.  The main
-// launch walks the pairs in natural (coalesced) order, evaluates every state with k <= 2 in
-// registers and appends the rest to a list; the list is then served by the K = 4 and K = 8
-// register kernels and finally by the LDS wavefront kernel.  Each level only sees what the
-// previous one could not hold, so waves stay homogeneous in k.
+// What the caller of an ES3C pass knows about its states beyond the context, and how much of the pass it wants.
+// The overflow counts of the last statistics pass (res_need / res_cnt, valid while need_known) describe
+//   known_tag 0: exactly these states (the pass over K^n itself): the levels and grids they say;
+//   known_tag 1: these states' parents -- the counted K^n plus candidates (a candidate batch, the final K^n of the
+//                statistics pass, a prefetched pass over a K^n whose counts the host has not seen yet): grids sized
+//                like children; with one_bit, every state not counted differs from a counted one in one bit, so it can
+//                exceed a level only if some counted state exceeded the level below;
+//   known_tag 2: nothing: every level, worst-case grids.
+// The kernel instantiations keep the name of the batch (Batch::tag) whatever is known about it.
+struct LevelHints {
+  int known_tag = 2;
+  bool one_bit = false;
+  double scale = 1.0;        // share of the counted datapoints the launches cover (a block of a chunked statistics pass)
+  bool levels_only = false;  // census route: no main kernel (the fused E-step evaluates <= 2 latents itself)
+};
+
+// Hints of the lpj pass over a batch.  prefetched: enqueued before the host has seen the counts of the K^n it evaluates
+// (they still describe the previous one), so a pass over K^n chooses its levels like a candidate batch.
+static LevelHints batch_hints(const evoamd_ctx *c, int tag, bool prefetched = false) {
+  LevelHints lv;
+  const bool stale = tag == 0 && prefetched;
+  lv.known_tag = stale ? 1 : tag;
+  lv.one_bit = stale || (tag == 1 && c->cand_from_device);
+  return lv;
+}
+
+// Overflow levels (3..4, 5..8, above 8 latents) a pass needs.
+static void levels_for(const evoamd_ctx *c, const LevelHints &lv, bool need[3]) {
+  need[0] = need[1] = need[2] = true;
+  if (!c->need_known) return;
+  if (lv.known_tag == 0) {
+    need[0] = c->res_need[0];
+    need[1] = c->res_need[1];
+    need[2] = c->res_need[2];
+  } else if (lv.known_tag == 1 && lv.one_bit) {
+    need[0] = true;
+    need[1] = c->res_need[0];
+    need[2] = c->res_need[1];
+  }
+}
+
 static unsigned list_grid(i64 total, unsigned cap) {
   unsigned g = cdiv(total, 256);
   return g > cap ? cap : (g < 1 ? 1 : g);
@@ -1799,13 +1831,13 @@ static unsigned list_grid(i64 total, unsigned cap) {
 // only has to be big enough to be fast: when the last statistics pass counted the resident states
 // above each level, launch about twice that many threads instead of the worst case (the K = 8
 // kernel needs 256 VGPRs + scratch per wave; an oversized, mostly idle grid cost 20-70 us).
-static unsigned level_grid(const evoamd_ctx *c, int level, int tag, i64 total, unsigned cap, unsigned per_block) {
+static unsigned level_grid(const evoamd_ctx *c, const LevelHints &lv, int level, i64 total, unsigned cap, unsigned per_block) {
   unsigned g = list_grid(total, cap);
+  const int tag = lv.known_tag;
   if (!c->need_known || tag == 2) return g;
-  if (tag == 0 && c->conservative_levels) tag = 1;  // counts describe the previous K^n: size it like its children
   // candidates / final K^n can exceed a level if a resident state exceeds the level below
   const int src = (tag == 0) ? level : (level > 0 ? level - 1 : 0);
-  double expect = c->grid_scale * c->res_cnt[src] * ((tag == 0) ? 1.0 : 1.0 + (double)c->Cmax / (double)c->S);
+  double expect = lv.scale * c->res_cnt[src] * ((tag == 0) ? 1.0 : 1.0 + (double)c->Cmax / (double)c->S);
   if (tag != 0 && level == 0) expect = (double)total;  // unknown: children of k = 2 parents
   unsigned want = (unsigned)(2.0 * expect / per_block) + 4;
   return want < g ? want : g;
@@ -1814,10 +1846,10 @@ static unsigned level_grid(const evoamd_ctx *c, int level, int tag, i64 total, u
 // A few thousand states above 4 active latents are served fastest by the wavefront-per-state
 // kernel (64 lanes share one k x k system: short latency, 53 vs 100 us at 2.5k states), a large
 // population by the K=8 register kernel (one state per thread: 244 us vs 15 ms at 640k states).
-static bool use_k8_kernel(const evoamd_ctx *c, int tag) {
+static bool use_k8_kernel(const evoamd_ctx *c, const LevelHints &lv) {
+  const int tag = lv.known_tag;
   if (c->k8_mode >= 0) return c->k8_mode != 0;
   if (!c->need_known || tag == 2) return true;
-  if (tag == 0 && c->conservative_levels) tag = 1;
   const double expect = c->res_cnt[tag == 0 ? 1 : 0] * (tag == 0 ? 1.0 : (double)c->Cmax / (double)c->S) +
                         (tag == 0 ? 0.0 : c->res_cnt[1]);
   return expect > 8192.0;
@@ -1825,10 +1857,10 @@ static bool use_k8_kernel(const evoamd_ctx *c, int tag) {
 
 // Few enough states above 4 active latents (known from the last statistics pass) that the two wavefront levels
 // (k <= 8, then k <= KCAP) are better served by one launch at full capacity.
-static bool few_dense_states(const evoamd_ctx *c, int tag) {
+static bool few_dense_states(const evoamd_ctx *c, const LevelHints &lv) {
+  const int tag = lv.known_tag;
   if (!c->need_known || tag == 2) return false;
-  if (tag == 0 && c->conservative_levels) tag = 1;
-  const double expect = c->grid_scale * (tag == 0 ? c->res_cnt[1] : c->res_cnt[1] + c->res_cnt[0] * (double)c->Cmax / (double)c->S);
+  const double expect = lv.scale * (tag == 0 ? c->res_cnt[1] : c->res_cnt[1] + c->res_cnt[0] * (double)c->Cmax / (double)c->S);
   return expect <= 1024.0;
 }
 
@@ -1837,9 +1869,9 @@ static bool few_dense_states(const evoamd_ctx *c, int tag) {
 // wavefront kernel, which runs behind the quad levels anyway, then serves that list as well, at full LDS capacity.
 // K^n is close to stationary from one iteration to the next, so the candidates and the final K^n are expected to hold
 // about as many such states as the census of the last statistics pass found (x 4 for slack); a wrong guess is only slower.
-static bool few_above4(const evoamd_ctx *c, int tag) {
-  if (!c->merge_small || !c->need_known || tag == 2) return false;
-  const double expect = c->grid_scale * c->res_cnt[1] * (1.0 + 4.0 * (double)c->Cmax / (double)std::max(1, c->S));
+static bool few_above4(const evoamd_ctx *c, const LevelHints &lv) {
+  if (!c->merge_small || !c->need_known || lv.known_tag == 2) return false;
+  const double expect = lv.scale * c->res_cnt[1] * (1.0 + 4.0 * (double)c->Cmax / (double)std::max(1, c->S));
   return expect <= 256.0;
 }
 
@@ -1891,8 +1923,8 @@ static int ensure_census(evoamd_ctx *c) {
 }
 
 // grid of a quad level (16 states per wave, 64 per workgroup) from the expected number of listed states
-static unsigned quad_grid(const evoamd_ctx *c, int level, int tag, i64 total, unsigned cap) {
-  return level_grid(c, level, tag, total * 4, cap, 64);
+static unsigned quad_grid(const evoamd_ctx *c, const LevelHints &lv, int level, i64 total, unsigned cap) {
+  return level_grid(c, lv, level, total * 4, cap, 64);
 }
 
 // A producer kernel that appends to the pair bins owns region (bin, blockIdx.x) of every bin and counter
@@ -1917,215 +1949,321 @@ static void with_hw(int hw, F &&f) {
   }
 }
 
+// The on-the-fly lists 1..3 of a pass as the kernels append to them (o) and read them (i), the census lists of the resident
+// K^n (3..4 / 5..8 / > 8 latents), a list that is always empty (nobody appends to the fourth row of the census counters),
+// and "no list".  `cap` is the shard stride: what appended with one capacity is read with the same.
+struct Es3cLists {
+  ListOut o1, o2, o3;
+  ListIn i1, i2, i3;
+  ListIn cA, cB, cC;
+  ListIn empty;
+  ListOut none_out;
+  ListIn none_in;
+};
+
+static Es3cLists es3c_lists(const evoamd_ctx *c, int cap) {
+  Es3cLists ls = {};
+  ls.o1 = {c->list1, c->list_n + 0 * LIST_SHARDS, cap};
+  ls.o2 = {c->list2, c->list_n + 1 * LIST_SHARDS, cap};
+  ls.o3 = {c->list3, c->list_n + 2 * LIST_SHARDS, cap};
+  ls.i1 = {ls.o1.items, ls.o1.counts, cap};
+  ls.i2 = {ls.o2.items, ls.o2.counts, cap};
+  ls.i3 = {ls.o3.items, ls.o3.counts, cap};
+  if (c->clist && c->clist_n) {
+    ls.cA = {c->clist, c->clist_n, cap};
+    ls.cB = {c->clist + c->clist_words, c->clist_n + LIST_SHARDS, cap};
+    ls.cC = {c->clist + 2 * c->clist_words, c->clist_n + 2 * LIST_SHARDS, cap};
+    ls.empty = {c->clist, c->clist_n + 3 * LIST_SHARDS, 0};
+  }
+  return ls;
+}
+
+// ---- the wavefront levels behind the quads of a pass over the census lists, the same launches for the lpj pass (MODE 0,
+// the pass's TAG) and the statistics pass (MODE 1): resident states above eight latents + what the quads passed on (list 3).
+// Returns the on-the-fly lists it served (bit k - 1 = list k).
+template <int MODE, int TAG>
+static int census_wavefront_levels(evoamd_ctx *c, const SsscArgs &a, const Es3cLists &ls, const bool need[3], bool few4,
+                                   const LevelHints &lv, i64 total) {
+  if (few4) {
+    // ONE wavefront launch at full capacity: the 5..8 list, the states above eight, what the 3..4 level passed on
+    // (nobody appends to list 2)
+    sssc_big_kernel<MODE, TAG><<<std::max(64u, level_grid(c, lv, 1, total * 256, 1024, 1)), 64, big_lds(SSSC_KCAP), c->stream>>>(
+        a, need[1] ? ls.cB : ls.empty, ls.none_out, SSSC_KCAP, need[2] ? ls.cC : ls.empty, ls.i3);
+    return 4;
+  }
+  // the pivoting wavefront kernel: resident states above eight latents, then what the quads passed on -- sized for
+  // 16 latents (6.8 KB of LDS per state: ~20 workgroups per CU; at the full 64 it is 98 KB, ONE per CU, and a dense
+  // K^n(0) with 40 % of its states above eight latents took 0.5 s in it), the few states beyond go on to list 2
+  sssc_big_kernel<MODE, TAG><<<std::max(256u, level_grid(c, lv, 2, total * 256, 8192, 1)), 64, big_lds(16), c->stream>>>(
+      a, need[2] ? ls.cC : ls.empty, ls.o2, 16, ls.i3);
+  if (!need[2]) return 4;  // nobody serves list 2: it must be found empty when the counters are cleared
+  sssc_big_kernel<MODE, TAG><<<level_grid(c, lv, 2, total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
+      a, ls.i2, ls.none_out, SSSC_KCAP);
+  return 2 | 4;
+}
+
 #define MAIN_LPJ_LDS_MAX (48 * 1024)  // three 512-thread workgroups (3072 pairs) per CU at the limit
 
+// LDS of the table-driven main kernel with the B rows of its workgroup's datapoints staged (1024 pairs per workgroup)
+static size_t main_lpj_lds(int C, int H) {
+  return ((size_t)(1024 / C + 2) * H + (H <= 512 ? (size_t)4 * H : 0)) * sizeof(double);
+}
+
+enum LpjRoute {
+  LPJ_MASKED,  // incomplete data: the wavefront kernel for every pair
+  LPJ_CENSUS,  // pass over the resident K^n with census lists: the main kernel appends nothing, the levels read the lists
+  LPJ_CHAINS,  // on-the-fly lists, quad levels (option "census_lists" = 1: candidate batches, shared / transient sets)
+  LPJ_ROUND2   // on-the-fly lists, register-kernel levels (option "census_lists" = 0)
+};
+enum LpjMain {
+  LPJ_MAIN_NONE,      // levels only
+  LPJ_MAIN_CENSUS,    // staged B rows, appends nothing
+  LPJ_MAIN_STAGED,    // staged B rows, appends to list 1
+  LPJ_MAIN_UNSTAGED,  // the same table-driven kernel with the B values gathered from global memory
+  LPJ_MAIN_SMALL      // K = 2 register kernel
+};
+
+// What an ES3C lpj pass decides before it enqueues anything (lpj_plan); the stages only read it.
+struct LpjPlan {
+  LpjRoute route;
+  LevelHints lv;
+  int kid_main;
+  i64 total;
+  int cap;
+  Es3cLists ls;
+  bool need[3];  // overflow levels the batch needs (levels_for)
+  bool any;      // ... and whether any runs
+  LpjMain main;
+  int rows_cap, stage_dg;
+  size_t lds;
+  unsigned grid;
+  bool few4;       // census / chains: the wavefront launch serves the 5..8 list too (few_above4)
+  bool k8;         // round 2: K = 8 register kernel (use_k8_kernel)
+  bool few_dense;  // round 2: one wavefront launch for lists 2 and 3 (few_dense_states)
+};
+
+// Fills the plan from the context as it is at entry.  Enqueues nothing.  `tag` (Batch::tag) names the kernel
+// instantiations of the pass in a trace; what is known about its states is in `lv`.
+static void lpj_plan(const evoamd_ctx *c, const SsscArgs &a, int tag, const LevelHints &lv, int kid_main, LpjPlan &p) {
+  p = LpjPlan{};
+  p.lv = lv;
+  p.kid_main = kid_main;
+  p.total = a.N * (i64)a.C;
+  p.cap = (int)list_cap(p.total);
+  p.ls = es3c_lists(c, p.cap);
+  levels_for(c, lv, p.need);
+  p.any = p.need[0] || p.need[1] || p.need[2];
+  const bool tables = !a.shared && (a.H % 2) == 0;  // the table-driven main kernel applies
+  const bool staged = tables && main_lpj_lds(a.C, a.H) <= MAIN_LPJ_LDS_MAX;
+  if (a.mask)
+    p.route = LPJ_MASKED;
+  else if (tag == 0 && a.states == c->states && census_mode(c) && staged)
+    p.route = LPJ_CENSUS;
+  else
+    p.route = c->census_opt ? LPJ_CHAINS : LPJ_ROUND2;
+  // 512-thread workgroups: measured 13.8-17.5 us without overflow and 20.0 us at 8 % overflow on
+  // the c2 shape (256: 13.0 / 24.3 us, 1024: 16.3 / 20.5 us).  The B rows of the workgroup's
+  // datapoints (and the per-latent table while it is small) are staged in LDS when they fit.
+  // two pairs per thread: 1024 pairs per workgroup
+  p.stage_dg = a.H <= 512;
+  p.grid = cdiv(p.total, 1024);
+  if (staged) {
+    p.main = p.route == LPJ_CENSUS ? (lv.levels_only ? LPJ_MAIN_NONE : LPJ_MAIN_CENSUS) : LPJ_MAIN_STAGED;
+    p.rows_cap = 1024 / a.C + 2;
+    p.lds = main_lpj_lds(a.C, a.H);
+  } else if (tables && a.dig && c->main_unstaged) {
+    // the rows of the workgroup's datapoints do not fit the LDS (candidate batches: 1024 / Cmax datapoints per workgroup)
+    p.main = LPJ_MAIN_UNSTAGED;
+    p.lds = (p.stage_dg ? (size_t)4 * a.H : 0) * sizeof(double);
+  } else {
+    p.main = LPJ_MAIN_SMALL;
+    p.grid = cdiv(p.total, 512);
+  }
+  p.few4 = p.route != LPJ_ROUND2 && few_above4(c, lv);
+  p.k8 = p.route == LPJ_ROUND2 && use_k8_kernel(c, lv);
+  p.few_dense = p.route == LPJ_ROUND2 && few_dense_states(c, lv);
+}
+
+// ---- incomplete data: G_A belongs to the datapoint, so no tables and no Gram gathers: the wavefront-per-state kernel
+// forms W_obs^T W_obs for every pair (k <= 8 first, the rest via list 3)
+static int lpj_sssc_masked(evoamd_ctx *c, const SsscArgs &a, const LpjPlan &p) {
+  SpanGuard g(c, p.kid_main);
+  const int gridm = (int)std::min<i64>(p.total, 65536);
+  sssc_big_kernel<0><<<gridm, 64, big_lds(8), c->stream>>>(a, p.ls.none_in, p.ls.o3, 8);
+  sssc_big_kernel<0><<<1024, 64, big_lds(SSSC_KCAP), c->stream>>>(a, p.ls.i3, p.ls.none_out, SSSC_KCAP);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---- the main kernel: every state with at most two active latents, the rest appended to list 1 (not in census form)
 template <int TAG>
-static int launch_sssc_lpj(evoamd_ctx *c, const SsscArgs &a, int kid_main, const bool need[3]) {
-  const i64 total = a.N * (i64)a.C;
-  const int cap = (int)list_cap(total);
+static int lpj_sssc_main(evoamd_ctx *c, const SsscArgs &a, const LpjPlan &p) {
+  if (p.main == LPJ_MAIN_NONE) return 0;
+  SpanGuard g(c, p.kid_main);
+  if (p.main == LPJ_MAIN_SMALL)
+    sssc_small_kernel<2, 0, TAG, 512><<<p.grid, 512, 0, c->stream>>>(a, p.ls.none_in, p.ls.o1, PairBins{});
+  else
+    with_hw(a.HW, [&](auto hw) {
+      constexpr int HWT = decltype(hw)::value;
+      if (p.main == LPJ_MAIN_CENSUS)
+        sssc_main_lpj_kernel<TAG, 512, HWT, 2, false><<<p.grid, 512, p.lds, c->stream>>>(a, p.ls.none_out, p.rows_cap, p.stage_dg);
+      else if (p.main == LPJ_MAIN_STAGED)
+        sssc_main_lpj_kernel<TAG, 512, HWT, 2><<<p.grid, 512, p.lds, c->stream>>>(a, p.ls.o1, p.rows_cap, p.stage_dg);
+      else
+        sssc_main_lpj_kernel<TAG, 512, HWT, 2, true, false><<<p.grid, 512, p.lds, c->stream>>>(a, p.ls.o1, 0, p.stage_dg);
+    });
+  HIP_TRY(hipGetLastError());
+  DBG_SYNC(c, p.main == LPJ_MAIN_CENSUS ? "sssc lpj main (census)" : "sssc lpj main");
+  return 0;
+}
+
+// ---- the levels of a pass over the census lists: quads on the 3..4 and 5..8 lists, then the wavefront levels
+// (the levels carry the pass's TAG in their names, so a kernel trace separates the pass over K^n from the candidate batch
+// level by level)
+template <int TAG>
+static int lpj_sssc_census_levels(evoamd_ctx *c, const SsscArgs &a, const LpjPlan &p, int &served) {
+  const Es3cLists &ls = p.ls;
+  SpanGuard g(c, KID_LPJ_OVF);
+  if (p.need[0]) {
+    SpanGuard gl(c, KID_LPJ_K34);
+    sssc_quad_kernel<1, 0, TAG><<<quad_grid(c, p.lv, 0, p.total, 2048), 256, 0, c->stream>>>(a, ls.cA, ls.none_out, ls.o3, PairBins{}, nullptr);
+  }
+  DBG_SYNC(c, "sssc lpj quad level 3..4");
+  if (p.need[1] && !p.few4) {
+    SpanGuard gl(c, KID_LPJ_K58);
+    sssc_quad_kernel<2, 0, TAG><<<quad_grid(c, p.lv, 1, p.total, 2048), 256, 0, c->stream>>>(a, ls.cB, ls.none_out, ls.o3, PairBins{}, nullptr);
+  }
+  DBG_SYNC(c, "sssc lpj quad level 5..8");
+  SpanGuard gl(c, KID_LPJ_K9P);
+  served = census_wavefront_levels<0, TAG>(c, a, ls, p.need, p.few4, p.lv, p.total);
+  HIP_TRY(hipGetLastError());
+  DBG_SYNC(c, p.few4 ? "sssc lpj census levels (merged)" : "sssc lpj census levels");
+  return 0;
+}
+
+// ---- the levels of an on-the-fly chain: list 1 -> 3..4 latents -> list 2 -> 5..8 latents (four-lanes-per-state kernel)
+// -> list 3 = the pivoting wavefront kernel, which also takes the states the quads pass on and therefore always runs
+// behind them
+template <int TAG>
+static int lpj_sssc_chain_levels(evoamd_ctx *c, const SsscArgs &a, const LpjPlan &p, int &served) {
+  const Es3cLists &ls = p.ls;
+  SpanGuard g(c, KID_LPJ_OVF);
+  // (3..4 latents of a chain: the quad kernel too since round 4 -- the K = 4 thread-per-state register kernel was faster
+  // on the ~400k listed candidates of the north-star shape (58 against 77 us), but it eliminates with row exchanges, so a
+  // candidate's lpj changed in the last bits when it became a resident state; now every state with 3..4 latents has ONE
+  // arithmetic, the one the fused per-datapoint E-step (kernels_fused.hpp) uses as well)
+  if (p.need[0])
+    sssc_quad_kernel<1, 0, TAG><<<quad_grid(c, p.lv, 0, p.total, 2048), 256, 0, c->stream>>>(a, ls.i1, ls.o2, ls.o3, PairBins{}, nullptr);
+  DBG_SYNC(c, "sssc lpj chain 3..4");
+  if (p.few4) {
+    // (few states above four latents: the wavefront launch serves list 2 as well -- one launch less)
+    sssc_big_kernel<0, TAG><<<std::max(64u, level_grid(c, p.lv, 1, p.total * 256, 1024, 1)), 64, big_lds(SSSC_KCAP), c->stream>>>(
+        a, ls.i2, ls.none_out, SSSC_KCAP, ls.i3);
+    served = 2 | 4;
+  } else {
+    if (p.need[1])
+      sssc_quad_kernel<2, 0, TAG><<<quad_grid(c, p.lv, 1, p.total, 2048), 256, 0, c->stream>>>(a, ls.i2, ls.o3, ls.o3, PairBins{}, nullptr);
+    DBG_SYNC(c, "sssc lpj chain 5..8");
+    sssc_big_kernel<0, TAG><<<level_grid(c, p.lv, 2, p.total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
+        a, ls.i3, ls.none_out, SSSC_KCAP);
+    served = 4;
+  }
+  HIP_TRY(hipGetLastError());
+  DBG_SYNC(c, p.few4 ? "sssc lpj chain wavefront level (merged)" : "sssc lpj chain wavefront level");
+  return 0;
+}
+
+// ---- the round-2 levels: list 1 -> K = 4 -> list 2 -> K = 8 / wavefront -> list 3 -> wavefront (stage for stage the
+// ladder of stats_sssc_chain_levels, which adds pair bins, in-kernel column sums and its own K = 8 rule)
+template <int TAG>
+static int lpj_sssc_round2_levels(evoamd_ctx *c, const SsscArgs &a, const LpjPlan &p, int &served) {
+  const Es3cLists &ls = p.ls;
+  SpanGuard g(c, KID_LPJ_OVF);
+  if (p.need[0])
+    sssc_small_kernel<4, 0, TAG, 256><<<level_grid(c, p.lv, 0, p.total, 1024, 256), 256, 0, c->stream>>>(a, ls.i1, ls.o2, PairBins{}, ls.o3);
+  DBG_SYNC(c, "sssc lpj K=4 level");
+  bool merged23 = false;
+  if (p.k8) {
+    if (p.need[1])
+      sssc_small_kernel<8, 0, TAG, 256><<<level_grid(c, p.lv, 1, p.total, 256, 256), 256, 0, c->stream>>>(a, ls.i2, ls.o3, PairBins{}, ls.o3);
+  } else if (p.need[1] && p.few_dense) {
+    // a handful of states above 4 active latents: ONE launch of the wavefront kernel at full capacity serves list 2
+    // (a launch costs ~8 us however little it does; the k <= 8 sizing only pays for thousands of states)
+    sssc_big_kernel<0, TAG><<<level_grid(c, p.lv, 1, p.total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
+        a, ls.i2, ls.none_out, SSSC_KCAP, ls.i3);  // (list 3: what the K = 4 level passed on in exact mode)
+    merged23 = true;
+  } else if (p.need[1]) {
+    // a few thousand states above 4 active latents: the wavefront-per-state kernel, sized for k <= 8
+    // (1.9 KiB of LDS, many workgroups per CU); anything denser moves on to list 3
+    sssc_big_kernel<0, TAG><<<level_grid(c, p.lv, 1, p.total * 256, 4096, 1), 64, big_lds(8), c->stream>>>(a, ls.i2, ls.o3, 8);
+  }
+  DBG_SYNC(c, "sssc lpj K=8 level");
+  // (with the screen on, list 3 is served whenever a level ran: in exact mode the register kernels pass their states on)
+  if ((p.need[2] || c->sing_screen) && !merged23)
+    sssc_big_kernel<0, TAG><<<level_grid(c, p.lv, 2, p.total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
+        a, ls.i3, ls.none_out, SSSC_KCAP);
+  served = (merged23 || p.need[2] || c->sing_screen) ? 4 : 0;
+  HIP_TRY(hipGetLastError());
+  DBG_SYNC(c, "sssc lpj wavefront level");
+  return 0;
+}
+
+// ES3C lpj of a batch.  The main kernel walks the pairs in natural (coalesced) order and evaluates every state with at
+// most two active latents; the states above come from lists -- the census of the resident K^n, or lists the main kernel
+// and the levels append to on the fly -- and each level only sees what the previous one could not hold, so waves stay
+// homogeneous in k.
+//
+// A level that is not launched must find its input list empty: the pass leaves in c->pending_skip (on-the-fly lists 1..3 =
+// bits 1, 2, 4) and c->census_skip (census lists) what the kernel that clears the counters next has to check
+// (check_lists_kernel, census_lists_kernel, tail_kernel).  With skip = skip_mask(need), `levels` = any of need[]:
+//
+//   route    levels  pending_skip                                                          census_skip
+//   masked   -       unchanged                                                             unchanged
+//   census   no      unchanged                                                             |= skip (= 7)
+//   census   yes     |= 2 unless !few4 && need[2] (the 16-latent launch feeds list 2,      |= skip
+//                    only the full-capacity launch behind it serves it)
+//   chains   no      |= skip (= 7)                                                         unchanged
+//   chains   yes     (|= skip) & ~4, with few4 & ~(2 | 4): the merged launch serves both   unchanged
+//   round 2  no      |= skip (= 7)                                                         unchanged
+//   round 2  yes     (|= skip), & ~4 if list 3 was served: need[2] || sing_screen ||       unchanged
+//                    (!k8 && need[1] && few_dense)
+//
+// (zero_lists has checked and cleared what the chain before left, so pending_skip is 0 when the table is applied.)
+template <int TAG>
+static int launch_sssc_lpj(evoamd_ctx *c, const SsscArgs &a, int kid_main, const LevelHints &lv) {
   int r = zero_lists(c);
   if (r) return r;
-  if (a.mask) {
-    // incomplete data: G_A belongs to the datapoint, so no tables and no Gram gathers: the
-    // wavefront-per-state kernel forms W_obs^T W_obs for every pair (k <= 8 first, the rest via list 3)
-    const ListIn nat = {nullptr, nullptr, 0};
-    const ListOut l3 = {c->list3, c->list_n + 2 * LIST_SHARDS, cap};
-    const ListIn i3m = {l3.items, l3.counts, cap};
-    const ListOut none_out = {nullptr, nullptr, 0};
-    SpanGuard g(c, kid_main);
-    const int gridm = (int)std::min<i64>(total, 65536);
-    sssc_big_kernel<0><<<gridm, 64, big_lds(8), c->stream>>>(a, nat, l3, 8);
-    sssc_big_kernel<0><<<1024, 64, big_lds(SSSC_KCAP), c->stream>>>(a, i3m, none_out, SSSC_KCAP);
-    HIP_TRY(hipGetLastError());
-    return 0;
-  }
-  const ListIn none = {nullptr, nullptr, 0};
-  const ListOut o1 = {c->list1, c->list_n + 0 * LIST_SHARDS, cap}, o2 = {c->list2, c->list_n + 1 * LIST_SHARDS, cap},
-                o3 = {c->list3, c->list_n + 2 * LIST_SHARDS, cap};
-  const ListIn i1 = {o1.items, o1.counts, cap}, i2 = {o2.items, o2.counts, cap}, i3 = {o3.items, o3.counts, cap};
-  const ListOut none_o = {nullptr, nullptr, 0};
-  // pass over the resident K^n with census lists: the main kernel appends nothing, the quad levels read the lists
-  const bool census = TAG == 0 && a.states == c->states && !a.shared && census_mode(c) && (a.H % 2) == 0 &&
-                      ((size_t)(1024 / a.C + 2) * a.H + (a.H <= 512 ? (size_t)4 * a.H : 0)) * sizeof(double) <= MAIN_LPJ_LDS_MAX;
-  if (census) {
+  LpjPlan p;
+  lpj_plan(c, a, TAG, lv, kid_main, p);
+  if (p.route == LPJ_MASKED) return lpj_sssc_masked(c, a, p);
+  if (p.route == LPJ_CENSUS) {
     r = ensure_census(c);
     if (r) return r;
-    c->census_skip |= skip_mask(need);
-    const int ccap = (int)list_cap(total);
-    const ListIn cA = {c->clist, c->clist_n, ccap}, cB = {c->clist + c->clist_words, c->clist_n + LIST_SHARDS, ccap},
-                 cC = {c->clist + 2 * c->clist_words, c->clist_n + 2 * LIST_SHARDS, ccap};
-    if (!c->levels_only) {
-      SpanGuard g(c, kid_main);
-      const int rows_cap = 1024 / a.C + 2;
-      const int stage_dg = a.H <= 512;
-      const size_t lds = ((size_t)rows_cap * a.H + (stage_dg ? (size_t)4 * a.H : 0)) * sizeof(double);
-      const int grid = (int)cdiv(total, 1024);
-      REQUIRE(lds <= MAIN_LPJ_LDS_MAX, "ES3C lpj: H too large for the staged B rows");
-      with_hw(a.HW, [&](auto hw) {
-        sssc_main_lpj_kernel<TAG, 512, decltype(hw)::value, 2, false><<<grid, 512, lds, c->stream>>>(a, none_o, rows_cap, stage_dg);
-      });
-      HIP_TRY(hipGetLastError());
-      DBG_SYNC(c, "sssc lpj main (census)");
-    }
-    if (need[0] || need[1] || need[2]) {
-      SpanGuard g(c, KID_LPJ_OVF);
-      if (need[0]) {
-        SpanGuard gl(c, KID_LPJ_K34);
-        sssc_quad_kernel<1, 0, TAG><<<quad_grid(c, 0, TAG, total, 2048), 256, 0, c->stream>>>(a, cA, none_o, o3, PairBins{}, nullptr);
-      }
-      DBG_SYNC(c, "sssc lpj quad level 3..4");
-      const bool few = few_above4(c, TAG);
-      const ListIn empty = {c->clist, c->clist_n + 3 * LIST_SHARDS, 0};
-      if (need[1] && !few) {
-        SpanGuard gl(c, KID_LPJ_K58);
-        sssc_quad_kernel<2, 0, TAG><<<quad_grid(c, 1, TAG, total, 2048), 256, 0, c->stream>>>(a, cB, none_o, o3, PairBins{}, nullptr);
-      }
-      DBG_SYNC(c, "sssc lpj quad level 5..8");
-      if (few) {
-        // ONE wavefront launch at full capacity: the 5..8 list, the states above eight, what the 3..4 level passed on
-        SpanGuard gl(c, KID_LPJ_K9P);
-        sssc_big_kernel<0, TAG><<<std::max(64u, level_grid(c, 1, TAG, total * 256, 1024, 1)), 64, big_lds(SSSC_KCAP), c->stream>>>(
-            a, need[1] ? cB : empty, none_o, SSSC_KCAP, need[2] ? cC : empty, i3);
-        c->pending_skip |= 2;  // nobody appends to list 2
-        HIP_TRY(hipGetLastError());
-        DBG_SYNC(c, "sssc lpj census levels (merged)");
-        return 0;
-      }
-      // the pivoting wavefront kernel: resident states above eight latents, then what the quads passed on -- sized for
-      // 16 latents (6.8 KB of LDS per state: ~20 workgroups per CU; at the full 64 it is 98 KB, ONE per CU, and a dense
-      // K^n(0) with 40 % of its states above eight latents took 0.5 s in it), the few states beyond go on to list 2
-      SpanGuard gl(c, KID_LPJ_K9P);
-      sssc_big_kernel<0, TAG><<<std::max(256u, level_grid(c, 2, TAG, total * 256, 8192, 1)), 64, big_lds(16), c->stream>>>(
-          a, need[2] ? cC : ListIn{c->clist, c->clist_n + 3 * LIST_SHARDS, 0}, o2, 16, i3);
-      if (need[2])
-        sssc_big_kernel<0, TAG><<<level_grid(c, 2, TAG, total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
-            a, i2, none_o, SSSC_KCAP);
-      else
-        c->pending_skip |= 2;  // nobody serves list 2: it must be found empty when the counters are cleared
-      HIP_TRY(hipGetLastError());
-      DBG_SYNC(c, "sssc lpj census levels");
-    }
-    return 0;
   }
-  c->pending_skip |= skip_mask(need);
-  {
-    SpanGuard g(c, kid_main);
-    // 512-thread workgroups: measured 13.8-17.5 us without overflow and 20.0 us at 8 % overflow on
-    // the c2 shape (256: 13.0 / 24.3 us, 1024: 16.3 / 20.5 us).  The B rows of the workgroup's
-    // datapoints (and the per-latent table while it is small) are staged in LDS when they fit.
-    // two pairs per thread: 1024 pairs per workgroup
-    const int rows_cap = 1024 / a.C + 2;
-    const int stage_dg = a.H <= 512;
-    const size_t lds = ((size_t)rows_cap * a.H + (stage_dg ? (size_t)4 * a.H : 0)) * sizeof(double);
-    const int grid = (int)cdiv(total, 1024);
-    if (!a.shared && (a.H % 2) == 0 && lds <= MAIN_LPJ_LDS_MAX) {
-      with_hw(a.HW, [&](auto hw) {
-        sssc_main_lpj_kernel<TAG, 512, decltype(hw)::value, 2><<<grid, 512, lds, c->stream>>>(a, o1, rows_cap, stage_dg);
-      });
-    } else if (!a.shared && (a.H % 2) == 0 && a.dig && c->main_unstaged) {
-      // the rows of the workgroup's datapoints do not fit the LDS (candidate batches: 1024 / Cmax datapoints per
-      // workgroup): the same table-driven kernel with the B values gathered from global memory
-      const size_t lds_u = (stage_dg ? (size_t)4 * a.H : 0) * sizeof(double);
-      with_hw(a.HW, [&](auto hw) {
-        sssc_main_lpj_kernel<TAG, 512, decltype(hw)::value, 2, true, false><<<grid, 512, lds_u, c->stream>>>(a, o1, 0, stage_dg);
-      });
-    } else
-      sssc_small_kernel<2, 0, TAG, 512><<<cdiv(total, 512), 512, 0, c->stream>>>(a, none, o1, PairBins{});
-    HIP_TRY(hipGetLastError());
-    DBG_SYNC(c, "sssc lpj main");
+  r = lpj_sssc_main<TAG>(c, a, p);
+  if (r) return r;
+  int served = 0;  // on-the-fly lists the levels read to the end (bit k - 1 = list k)
+  if (p.any) {
+    r = p.route == LPJ_CENSUS   ? lpj_sssc_census_levels<TAG>(c, a, p, served)
+        : p.route == LPJ_CHAINS ? lpj_sssc_chain_levels<TAG>(c, a, p, served)
+                                : lpj_sssc_round2_levels<TAG>(c, a, p, served);
+    if (r) return r;
   }
-  if (c->census_opt && (need[0] || need[1] || need[2])) {
-    // on-the-fly chains (candidate batches, shared / transient sets): list 1 -> 3..4 latents -> list 2 -> 5..8 latents
-    // (four-lanes-per-state kernel) -> list 3 = the pivoting wavefront kernel, which also takes the states the quads
-    // pass on and therefore always runs behind them
-    SpanGuard g(c, KID_LPJ_OVF);
-    // (3..4 latents of a chain: the quad kernel too since round 4 -- the K = 4 thread-per-state register kernel was faster
-    // on the ~400k listed candidates of the north-star shape (58 against 77 us), but it eliminates with row exchanges, so a
-    // candidate's lpj changed in the last bits when it became a resident state; now every state with 3..4 latents has ONE
-    // arithmetic, the one the fused per-datapoint E-step (kernels_fused.hpp) uses as well)
-    if (need[0])
-      sssc_quad_kernel<1, 0, TAG><<<quad_grid(c, 0, TAG, total, 2048), 256, 0, c->stream>>>(a, i1, o2, o3, PairBins{}, nullptr);
-    DBG_SYNC(c, "sssc lpj chain 3..4");
-    if (few_above4(c, TAG)) {
-      // (few states above four latents: the wavefront launch serves list 2 as well -- one launch less)
-      sssc_big_kernel<0, TAG><<<std::max(64u, level_grid(c, 1, TAG, total * 256, 1024, 1)), 64, big_lds(SSSC_KCAP), c->stream>>>(
-          a, i2, none_o, SSSC_KCAP, i3);
-      c->pending_skip &= ~(2 | 4);  // lists 2 and 3 have been served
-      HIP_TRY(hipGetLastError());
-      DBG_SYNC(c, "sssc lpj chain wavefront level (merged)");
-      return 0;
-    }
-    if (need[1]) sssc_quad_kernel<2, 0, TAG><<<quad_grid(c, 1, TAG, total, 2048), 256, 0, c->stream>>>(a, i2, o3, o3, PairBins{}, nullptr);
-    DBG_SYNC(c, "sssc lpj chain 5..8");
-    sssc_big_kernel<0, TAG><<<level_grid(c, 2, TAG, total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
-        a, i3, none_o, SSSC_KCAP);
-    c->pending_skip &= ~4;  // list 3 has been served
-    HIP_TRY(hipGetLastError());
-    DBG_SYNC(c, "sssc lpj chain wavefront level");
-  } else if (need[0] || need[1] || need[2]) {
-    SpanGuard g(c, KID_LPJ_OVF);
-    // the levels carry the pass's TAG in their names, so a kernel trace separates the pass over K^n from the
-    // candidate batch level by level
-    bool merged23 = false;
-    if (need[0])
-      sssc_small_kernel<4, 0, TAG, 256><<<level_grid(c, 0, TAG, total, 1024, 256), 256, 0, c->stream>>>(a, i1, o2, PairBins{}, o3);
-    DBG_SYNC(c, "sssc lpj K=4 level");
-    const ListOut none_out = {nullptr, nullptr, 0};
-    if (use_k8_kernel(c, TAG)) {
-      if (need[1])
-        sssc_small_kernel<8, 0, TAG, 256><<<level_grid(c, 1, TAG, total, 256, 256), 256, 0, c->stream>>>(a, i2, o3, PairBins{}, o3);
-    } else if (need[1] && few_dense_states(c, TAG)) {
-      // a handful of states above 4 active latents: ONE launch of the wavefront kernel at full capacity serves list 2
-      // (a launch costs ~8 us however little it does; the k <= 8 sizing only pays for thousands of states)
-      sssc_big_kernel<0, TAG><<<level_grid(c, 1, TAG, total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
-          a, i2, none_out, SSSC_KCAP, i3);  // (list 3: what the K = 4 level passed on in exact mode)
-      c->pending_skip &= ~4;
-      merged23 = true;
-    } else if (need[1]) {
-      // a few thousand states above 4 active latents: the wavefront-per-state kernel, sized for k <= 8
-      // (1.9 KiB of LDS, many workgroups per CU); anything denser moves on to list 3
-      sssc_big_kernel<0, TAG><<<level_grid(c, 1, TAG, total * 256, 4096, 1), 64, big_lds(8), c->stream>>>(a, i2, o3, 8);
-    }
-    DBG_SYNC(c, "sssc lpj K=8 level");
-    // (with the screen on, list 3 is served whenever a level ran: in exact mode the register kernels pass their states on)
-    if ((need[2] || c->sing_screen) && !merged23) {
-      sssc_big_kernel<0, TAG><<<level_grid(c, 2, TAG, total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
-          a, i3, none_out, SSSC_KCAP);
-      c->pending_skip &= ~4;
-    }
-    HIP_TRY(hipGetLastError());
-    DBG_SYNC(c, "sssc lpj wavefront level");
+  if (p.route == LPJ_CENSUS) {
+    c->census_skip |= skip_mask(p.need);
+    if (p.any && !(served & 2)) c->pending_skip |= 2;
+  } else {
+    c->pending_skip = (c->pending_skip | skip_mask(p.need)) & ~served;
   }
   return 0;
 }
 
-// Overflow levels a batch needs.  tag 0 (K^n itself): exactly what the last statistics pass
-// counted.  tag 1 with device-generated candidates: a child differs from its parent in one bit, so
-// it can exceed a level only if some resident state exceeds the level below.  Anything else: all.
-static void levels_for(const evoamd_ctx *c, int tag, bool need[3]) {
-  need[0] = need[1] = need[2] = true;
-  if (!c->need_known) return;
-  if (tag == 0 && !c->conservative_levels) {
-    need[0] = c->res_need[0];
-    need[1] = c->res_need[1];
-    need[2] = c->res_need[2];
-  } else if (tag == 0 || (tag == 1 && c->cand_from_device)) {
-    // K^n(k) = K^n(k-1) + one-bit children (and a prefetched pass only knows the counts of K^n(k-1)): a state
-    // can exceed a level only if some state the counts describe exceeded the level below
-    need[0] = true;
-    need[1] = c->res_need[0];
-    need[2] = c->res_need[1];
-  }
-}
-
-static int launch_lpj(evoamd_ctx *c, const Batch &b) {
+static int launch_lpj(evoamd_ctx *c, const Batch &b, const LevelHints &lv) {
   if (c->model == EVOAMD_MODEL_BSC) return launch_bsc_lpj(c, b);
   SsscArgs a = sssc_args(c, b);
-  bool need[3];
-  levels_for(c, b.tag, need);
-  if (b.tag == 0) return launch_sssc_lpj<0>(c, a, b.kid, need);
-  if (b.tag == 1) return launch_sssc_lpj<1>(c, a, b.kid, need);
-  return launch_sssc_lpj<2>(c, a, b.kid, need);
+  if (b.tag == 0) return launch_sssc_lpj<0>(c, a, b.kid, lv);
+  if (b.tag == 1) return launch_sssc_lpj<1>(c, a, b.kid, lv);
+  return launch_sssc_lpj<2>(c, a, b.kid, lv);
 }
 
 static int check_err(evoamd_ctx *c) {
@@ -2143,7 +2281,7 @@ static int check_err(evoamd_ctx *c) {
   return 0;
 }
 
-static int lpj_resident_launch(evoamd_ctx *c, double *out);
+static int lpj_resident_launch(evoamd_ctx *c, double *out, const LevelHints &lv);
 
 extern "C" int evoamd_lpj_resident(evoamd_ctx *c) {
   REQUIRE(c && c->configured && c->have_data && c->have_params, "configure, upload_data and set_params first");
@@ -2153,10 +2291,10 @@ extern "C" int evoamd_lpj_resident(evoamd_ctx *c) {
     std::swap(c->lpj, c->lpj_alt);
     return 0;
   }
-  return lpj_resident_launch(c, c->lpj);
+  return lpj_resident_launch(c, c->lpj, batch_hints(c, 0));
 }
 
-static int lpj_resident_launch(evoamd_ctx *c, double *out) {
+static int lpj_resident_launch(evoamd_ctx *c, double *out, const LevelHints &lv) {
   {
     int rb = ensure_B(c);
     if (rb) return rb;
@@ -2170,7 +2308,7 @@ static int lpj_resident_launch(evoamd_ctx *c, double *out) {
   Batch b = {c->states, nullptr, c->Y, c->Bm, c->yy, c->N, c->S, 0, out, c->L, c->S_perm, c->flags, KID_LPJ_RES, 0};
   b.mask = c->mask_infr;
   SpanGuard pass(c, KID_LPJ_PASS);  // main kernel + every overflow level: everything that produces the N x S lpj
-  return launch_lpj(c, b);  // stream-ordered; device-side errors surface at the next host-returning call
+  return launch_lpj(c, b, lv);  // stream-ordered; device-side errors surface at the next host-returning call
 }
 
 static int eval_candidates(evoamd_ctx *c) {
@@ -2181,7 +2319,7 @@ static int eval_candidates(evoamd_ctx *c) {
   Batch b = {c->cand, c->cand_counts, c->Y, c->Bm, c->yy, c->N, c->Cmax, 0, c->cand_lpj, c->Cmax, 0,
              c->flags + c->N, KID_LPJ_CAND, 1};
   b.mask = c->mask_infr;
-  return launch_lpj(c, b);
+  return launch_lpj(c, b, batch_hints(c, b.tag));
 }
 
 extern "C" int evoamd_lpj_candidates(evoamd_ctx *c, const uint8_t *cand_bool, const int32_t *counts, int Cmax,
@@ -2265,7 +2403,7 @@ extern "C" int evoamd_lpj_shared(evoamd_ctx *c, const uint8_t *states_bool, int 
   }
   Batch b = {c->tmp_states, nullptr, c->Y, c->Bm, c->yy, c->N, C, 1, c->tmp_lpj, C, 0, c->flags + c->N, KID_MISC, 2};
   b.mask = c->mask_infr;
-  r = launch_lpj(c, b);
+  r = launch_lpj(c, b, batch_hints(c, b.tag));
   if (!r) {
     hipError_t e = hipMemcpyAsync(lpj_out, c->tmp_lpj, (size_t)c->N * C * sizeof(double), hipMemcpyDeviceToHost,
                                   c->stream);
@@ -2313,7 +2451,7 @@ static int lpj_single_impl(evoamd_ctx *c, const double *y, const uint8_t *x_infr
   }
   Batch b = {c->tmp_states, nullptr, dy, db, dyy, 1, C, 1, c->tmp_lpj, C, 0, dfl, KID_MISC, 2};
   b.mask = dmask;
-  r = launch_lpj(c, b);
+  r = launch_lpj(c, b, batch_hints(c, b.tag));
   if (r) return r;
   unsigned fl = 0;
   HIP_TRY(hipMemcpyAsync(lpj_out, c->tmp_lpj, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -2483,9 +2621,9 @@ static int launch_estep_fused(evoamd_ctx *c, int n_parents, int n_children, uint
   // resident states above two latents: the list kernels over the census of THIS K^n (built by the last fused call or by
   // census_kernel), sixteen states per wave pass; their values land in the lpj row the fused kernel reads
   {
-    c->levels_only = true;
-    const int rl = lpj_resident_launch(c, c->lpj);
-    c->levels_only = false;
+    LevelHints lv = batch_hints(c, 0);
+    lv.levels_only = true;
+    const int rl = lpj_resident_launch(c, c->lpj, lv);
     if (rl) return rl;
   }
   HIP_TRY(hipMemsetAsync(cnt1, 0, sizeof(int), c->stream));
@@ -2768,7 +2906,7 @@ struct StatsPlan {
   int H, D;
   hipStream_t main_stream;  // c->stream at entry (the contraction borrows c->stream for stream2 and gives it back)
   bool masked;              // incomplete data
-  int tg;                   // how much is known about the final K^n (tag of level_grid / few_above4 / few_dense_states)
+  LevelHints lv;            // how much is known about the final K^n (resident states and accepted candidates)
   bool gemm_timed;          // a class on the main stream is being timed: no second stream
   double gemm_flops;
   bool pays;       // the contraction is worth a second stream (agreed over the ranks)
@@ -2808,16 +2946,14 @@ struct Es3cPass {
   double *Es, *Ez, *Ed;  // columns of [Y | Es | Ez | Ed] (ES3C)
   SsscArgs sa = {};
   bool need[3] = {true, true, true};
-  ListOut o1 = {}, o2 = {}, o3 = {};
-  ListIn i1 = {}, i2 = {}, i3 = {};
-  const ListOut none_out = {nullptr, nullptr, 0};
+  Es3cLists ls = {};  // (census mode means one block, so the census lists are read with the pass's capacity too)
 };
 
-// ES3C on complete data, one block: its rows of the argument block, its census lists, the form of its main kernel
+// ES3C on complete data, one block: its rows of the argument block, its share of the counts, the form of its main kernel
 struct Es3cBlock {
   SsscArgs sc;
   i64 total;
-  ListIn cA, cB, cC;
+  LevelHints lv;  // the pass's, scaled to the block's share of the datapoints
   int flatG = 0;  // census mode, thread-per-state form of the main kernel: G datapoints per 1024-thread workgroup and round
   size_t flat_lds = 0;
   bool few4;  // few states above four latents: no quad launch for them, the wavefront kernel behind the main kernel adds them
@@ -2872,7 +3008,8 @@ static int stats_plan(evoamd_ctx *c, bool fork_gemm, StatsPlan &p) {
   p.D = c->D;
   p.main_stream = c->stream;
   p.masked = c->mask_infr != nullptr;
-  p.tg = c->cand_from_device ? 1 : 2;
+  p.lv.known_tag = c->cand_from_device ? 1 : 2;
+  p.lv.one_bit = c->cand_from_device;
   // (the contraction's own class alone does not count: its span is recorded on the stream the product runs on, so it
   // can be timed forked, as the timed loop runs it -- bench.py's `mfma` block)
   p.gemm_timed = c->timing && (c->timing_mask & ((1u << KID_MSTEP) | (1u << KID_MISC) |
@@ -3043,11 +3180,10 @@ static int stats_sssc_masked_block(evoamd_ctx *c, const StatsPlan &p, const Es3c
   const int H = p.H;
   const i64 total = N * (i64)c->S;
   HIP_TRY(hipMemset2DAsync(ep.Es, (size_t)c->ldY * sizeof(double), 0, (size_t)3 * H * sizeof(double), (size_t)N, c->stream));
-  const ListIn nat = {nullptr, nullptr, 0};
   {
     SpanGuard g(c, KID_STATS);
-    sssc_big_kernel<1><<<(int)std::min<i64>(total, 65536), 64, big_lds(8), c->stream>>>(ep.sa, nat, ep.o3, 8);
-    sssc_big_kernel<1><<<1024, 64, big_lds(SSSC_KCAP), c->stream>>>(ep.sa, ep.i3, ep.none_out, SSSC_KCAP);
+    sssc_big_kernel<1><<<(int)std::min<i64>(total, 65536), 64, big_lds(8), c->stream>>>(ep.sa, ep.ls.none_in, ep.ls.o3, 8);
+    sssc_big_kernel<1><<<1024, 64, big_lds(SSSC_KCAP), c->stream>>>(ep.sa, ep.ls.i3, ep.ls.none_out, SSSC_KCAP);
     HIP_TRY(hipGetLastError());
   }
   SpanGuard g(c, KID_MISC);
@@ -3056,7 +3192,7 @@ static int stats_sssc_masked_block(evoamd_ctx *c, const StatsPlan &p, const Es3c
   return 0;
 }
 
-// ES3C on complete data: this block's rows of the argument block, its census lists and the form of its main kernel
+// ES3C on complete data: this block's rows of the argument block, its level hints and the form of its main kernel
 static Es3cBlock sssc_block_setup(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep, const StatsBlock &blk) {
   const SsscArgs &sa = ep.sa;
   const i64 n0 = blk.n0;
@@ -3076,10 +3212,8 @@ static Es3cBlock sssc_block_setup(evoamd_ctx *c, const StatsPlan &p, const Es3cP
   sc.Ed = sa.Ed + (size_t)n0 * sa.ldE;
   sc.N = blk.nc;
   eb.total = blk.nc * (i64)c->S;
-  const int ccap = (int)list_cap(eb.total);
-  eb.cA = {c->clist, c->clist_n, ccap};
-  eb.cB = {c->clist + c->clist_words, c->clist_n + LIST_SHARDS, ccap};
-  eb.cC = {c->clist + 2 * c->clist_words, c->clist_n + 2 * LIST_SHARDS, ccap};
+  eb.lv = p.lv;
+  eb.lv.scale = (double)blk.nc / (double)p.N;
   if (p.census && c->stats_flat && c->S <= FLAT_T && (H % 2) == 0 && (D % 2) == 0 && sc.Ez == sc.Es + H && c->stats_waves == 0) {
     int flatG = FLAT_T / c->S;
     const int gmax = (int)(((size_t)140 * 1024 / sizeof(double) - (size_t)7 * H) / ((size_t)4 * H + 4));
@@ -3088,7 +3222,7 @@ static Es3cBlock sssc_block_setup(evoamd_ctx *c, const StatsPlan &p, const Es3cP
     if (flatG >= 1) eb.flat_lds = ((size_t)H * (4 * flatG + 7) + 4 * flatG) * sizeof(double);
     eb.flatG = flatG;
   }
-  eb.few4 = p.census && eb.flatG < 1 && few_above4(c, p.tg);
+  eb.few4 = p.census && eb.flatG < 1 && few_above4(c, eb.lv);
   return eb;
 }
 
@@ -3106,15 +3240,15 @@ static int stats_sssc_census_quads(evoamd_ctx *c, const StatsPlan &p, const Es3c
     // (the bins' region counters are zero here: pair_bins_reduce_kernel clears what it reads)
     if (need[0]) {
       SpanGuard gl(c, KID_STATS_K34);
-      const unsigned qg = quad_grid(c, 0, p.tg, eb.total, gcap);
+      const unsigned qg = quad_grid(c, eb.lv, 0, eb.total, gcap);
       PB_GRID_CHECK(pb, qg);
-      sssc_quad_kernel<1, 1, 2><<<qg, 256, dl, c->stream>>>(eb.sc, eb.cA, ep.none_out, ep.o3, pb, c->ovf_rec);
+      sssc_quad_kernel<1, 1, 2><<<qg, 256, dl, c->stream>>>(eb.sc, ep.ls.cA, ep.ls.none_out, ep.ls.o3, pb, c->ovf_rec);
     }
     if (need[1] && !eb.few4) {
       SpanGuard gl(c, KID_STATS_K58);
-      const unsigned qg = quad_grid(c, 1, p.tg, eb.total, gcap);
+      const unsigned qg = quad_grid(c, eb.lv, 1, eb.total, gcap);
       PB_GRID_CHECK(pb, qg);
-      sssc_quad_kernel<2, 1, 2><<<qg, 256, dl, c->stream>>>(eb.sc, eb.cB, ep.none_out, ep.o3, pb, c->ovf_rec);
+      sssc_quad_kernel<2, 1, 2><<<qg, 256, dl, c->stream>>>(eb.sc, ep.ls.cB, ep.ls.none_out, ep.ls.o3, pb, c->ovf_rec);
     }
     HIP_TRY(hipGetLastError());
     DBG_SYNC(c, "sssc stats quad levels");
@@ -3127,7 +3261,7 @@ static int stats_sssc_main(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep
                            StatsFlow &fl) {
   const PairBins &pb = fl.pb;
   const SsscArgs &sc = eb.sc;
-  const ListOut &o1 = ep.o1;
+  const ListOut &o1 = ep.ls.o1;
   const i64 nc = blk.nc;
   const int H = p.H;
   const bool census = p.census;
@@ -3183,28 +3317,13 @@ static int stats_sssc_main(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep
 
 // ---- the levels behind the main kernel, census form: resident states above eight latents + what the quads passed on
 // (atomics)
-static int stats_sssc_census_levels(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep, const Es3cBlock &eb) {
+static int stats_sssc_census_levels(evoamd_ctx *c, const Es3cPass &ep, const Es3cBlock &eb) {
   const bool *need = ep.need;
-  const SsscArgs &sc = eb.sc;
-  const i64 total = eb.total;
-  const int tg = p.tg;
   if (need[0] || need[1] || need[2]) {
     SpanGuard g(c, KID_STATS_OVF);
     SpanGuard gl(c, KID_STATS_K9P);
-    const ListIn empty = {c->clist, c->clist_n + 3 * LIST_SHARDS, 0};
-    if (eb.few4) {
-      sssc_big_kernel<1><<<std::max(64u, level_grid(c, 1, tg, total * 256, 1024, 1)), 64, big_lds(SSSC_KCAP), c->stream>>>(
-          sc, need[1] ? eb.cB : empty, ep.none_out, SSSC_KCAP, need[2] ? eb.cC : empty, ep.i3);
-      c->pending_skip |= 2;
-    } else {
-      sssc_big_kernel<1><<<std::max(256u, level_grid(c, 2, tg, total * 256, 8192, 1)), 64, big_lds(16), c->stream>>>(
-          sc, need[2] ? eb.cC : empty, ep.o2, 16, ep.i3);
-      if (need[2])
-        sssc_big_kernel<1><<<level_grid(c, 2, tg, total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
-            sc, ep.i2, ep.none_out, SSSC_KCAP);
-      else
-        c->pending_skip |= 2;
-    }
+    const int served = census_wavefront_levels<1, 2>(c, eb.sc, ep.ls, need, eb.few4, eb.lv, eb.total);
+    if (!(served & 2)) c->pending_skip |= 2;  // (as in launch_sssc_lpj: nobody serves the on-the-fly list 2)
     HIP_TRY(hipGetLastError());
     DBG_SYNC(c, "sssc stats wavefront level (census)");
   }
@@ -3217,36 +3336,36 @@ static int stats_sssc_chain_levels(evoamd_ctx *c, const StatsPlan &p, const Es3c
   const PairBins &pb = fl.pb;
   const SsscArgs &sc = eb.sc;
   const i64 total = eb.total;
-  const int tg = p.tg;
+  const LevelHints &lv = eb.lv;
   if (need[0] || need[1] || need[2]) {
     SpanGuard g(c, KID_STATS_OVF);
     const size_t cs_lds = sc.cs ? (size_t)3 * p.H * sizeof(double) : 0;  // in-kernel column sums (LDS)
     bool merged23 = false;
     if (need[0]) {
-      const unsigned g4 = pb_clamp(pb, level_grid(c, 0, tg, total, 1024, 256));
+      const unsigned g4 = pb_clamp(pb, level_grid(c, lv, 0, total, 1024, 256));
       PB_GRID_CHECK(pb, g4);
-      sssc_small_kernel<4, 1, 2, 256><<<g4, 256, cs_lds, c->stream>>>(sc, ep.i1, ep.o2, pb, ep.o3);
+      sssc_small_kernel<4, 1, 2, 256><<<g4, 256, cs_lds, c->stream>>>(sc, ep.ls.i1, ep.ls.o2, pb, ep.ls.o3);
     }
     // (statistics mode of the K = 8 register kernel: 256 registers + 736 bytes of scratch per lane, one wave per
     // SIMD -- measured slower than the wavefront kernel at every size seen: 187 vs ~110 us at 5k states, 0.32
     // vs 0.25 ms for the pass's levels at the north-star shape; only when forced by option "sssc_k8" = 1)
     if (c->k8_mode == 1) {
       if (need[1]) {
-        const unsigned g8 = pb_clamp(pb, level_grid(c, 1, tg, total, 256, 256));
+        const unsigned g8 = pb_clamp(pb, level_grid(c, lv, 1, total, 256, 256));
         PB_GRID_CHECK(pb, g8);
-        sssc_small_kernel<8, 1, 2, 256><<<g8, 256, cs_lds, c->stream>>>(sc, ep.i2, ep.o3, pb, ep.o3);
+        sssc_small_kernel<8, 1, 2, 256><<<g8, 256, cs_lds, c->stream>>>(sc, ep.ls.i2, ep.ls.o3, pb, ep.ls.o3);
       }
-    } else if (need[1] && few_dense_states(c, tg)) {
-      sssc_big_kernel<1><<<level_grid(c, 1, tg, total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
-          sc, ep.i2, ep.none_out, SSSC_KCAP, ep.i3);  // one launch for both wavefront levels (see launch_sssc_lpj)
+    } else if (need[1] && few_dense_states(c, lv)) {
+      sssc_big_kernel<1><<<level_grid(c, lv, 1, total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
+          sc, ep.ls.i2, ep.ls.none_out, SSSC_KCAP, ep.ls.i3);  // one launch for both wavefront levels (see lpj_sssc_round2_levels)
       fl.served3 = true;
       merged23 = true;
     } else if (need[1]) {
-      sssc_big_kernel<1><<<level_grid(c, 1, tg, total * 256, 4096, 1), 64, big_lds(8), c->stream>>>(sc, ep.i2, ep.o3, 8);
+      sssc_big_kernel<1><<<level_grid(c, lv, 1, total * 256, 4096, 1), 64, big_lds(8), c->stream>>>(sc, ep.ls.i2, ep.ls.o3, 8);
     }
     if ((need[2] || c->sing_screen) && !merged23) {
-      sssc_big_kernel<1><<<level_grid(c, 2, tg, total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
-          sc, ep.i3, ep.none_out, SSSC_KCAP);
+      sssc_big_kernel<1><<<level_grid(c, lv, 2, total * 256, 1024, 1), 64, big_lds(SSSC_KCAP), c->stream>>>(
+          sc, ep.ls.i3, ep.ls.none_out, SSSC_KCAP);
       fl.served3 = true;
     }
     HIP_TRY(hipGetLastError());
@@ -3280,7 +3399,7 @@ static int stats_sssc_block(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &e
   if (r) return r;
   if (debug_fail)  // test hook: a pass that returns between its producers and the pair-bin reduce
     return fail(EVOAMD_E_INVALID, "debug_fail_stats: statistics pass stopped after its main kernel");
-  r = p.census ? stats_sssc_census_levels(c, p, ep, eb) : stats_sssc_chain_levels(c, p, ep, eb, fl);
+  r = p.census ? stats_sssc_census_levels(c, ep, eb) : stats_sssc_chain_levels(c, p, ep, eb, fl);
   if (r) return r;
   r = rows_written(c, p, fl);
   if (r) return r;
@@ -3447,15 +3566,9 @@ static int stats_sssc_pass(evoamd_ctx *c, const StatsPlan &p, Es3cPass &ep) {
   sa.xss_o = c->acc_base + c->pre_n;
   sa.xszsz_o = c->acc_base + c->pre_n + (size_t)H * H;
   if (!p.masked) sa.cs = c->acc_base + 4;  // the kernels sum the columns of [Es | Ez] and the diagonal second moments themselves
-  const int cap = (int)list_cap(N * (i64)c->S);
-  ep.o1 = {c->list1, c->list_n + 0 * LIST_SHARDS, cap};
-  ep.o2 = {c->list2, c->list_n + 1 * LIST_SHARDS, cap};
-  ep.o3 = {c->list3, c->list_n + 2 * LIST_SHARDS, cap};
-  ep.i1 = {ep.o1.items, ep.o1.counts, cap};
-  ep.i2 = {ep.o2.items, ep.o2.counts, cap};
-  ep.i3 = {ep.o3.items, ep.o3.counts, cap};
+  ep.ls = es3c_lists(c, (int)list_cap(N * (i64)c->S));
   // the final K^n is made of resident states and accepted candidates: same levels as the candidates
-  levels_for(c, 1, ep.need);
+  levels_for(c, p.lv, ep.need);
   return zero_lists(c);
 }
 
@@ -3510,7 +3623,6 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
     const i64 n0 = (i64)ci * p.rows_per_chunk;
     const i64 nc = std::min<i64>(p.rows_per_chunk, p.N - n0);
     const StatsBlock blk = {ci, n0, nc, (int)(n0 / p.rpb), (int)cdiv(nc, p.rpb)};
-    c->grid_scale = (double)nc / (double)p.N;
     if (c->model == EVOAMD_MODEL_BSC)
       r = stats_bsc_block(c, p, blk, fl, Ywp, ldwp);
     else if (p.masked)
@@ -3518,7 +3630,6 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
     else
       r = stats_sssc_block(c, p, ep, blk, fl, debug_fail);
     if (r) return r;
-    c->grid_scale = 1.0;
     if (ci == p.nchunks - 1) {
       // (before this block's contraction is enqueued: on one stream the span of the statistics pass must not cover it)
       r = stats_finish(c, p, ep, fl);
@@ -3894,9 +4005,7 @@ static int mailbox_roundtrip(evoamd_ctx *c, bool with_theta, bool prefetch = fal
     // the host has not read this iteration's overflow counts yet (they arrive with the mailbox being polled
     // below), so res_need / res_cnt still describe the K^n of the PREVIOUS iteration: conservative levels
     c->prefetch_gen = ~0ull;
-    c->conservative_levels = true;
-    const int rp = lpj_resident_launch(c, c->lpj_alt);
-    c->conservative_levels = false;
+    const int rp = lpj_resident_launch(c, c->lpj_alt, batch_hints(c, 0, /*prefetched=*/true));
     if (rp == 0) c->prefetch_gen = c->gen;
   }
   volatile unsigned long long *flag = (volatile unsigned long long *)c->h_theta;
