@@ -77,6 +77,9 @@ SIGNATURES = {
     "evoamd_set_estep_counts": (_I, [_vp, _DBL, _DBL]),
     "evoamd_patches_extract": (_I, [_vp, _c_dp, _I, _I, _I, _I, _I, _I, _c_dp]),
     "evoamd_patches_merge": (_I, [_vp, _c_dp, _I, _I, _I, _I, _I, _I, _I, _c_dp]),
+    "evoamd_reconstruct_resident": (_I, [_vp, _c_u8p]),
+    "evoamd_patches_merge_resident": (_I, [_vp, _I, _I, _I, _I, _I, _I, _I, _c_dp]),
+    "evoamd_download_reconstruction": (_I, [_vp, _c_dp]),
     "evoamd_comm_unique_id": (_I, [_c_u8p]),
     "evoamd_comm_init": (_I, [_vp, _c_u8p, _I, _I]),
     "evoamd_comm_allreduce_host": (_I, [_vp, _c_dp, _I64, _I]),

@@ -262,6 +262,14 @@ struct evoamd_ctx {
   size_t yhat_n = 0;
   bool yhat_valid = false;
   bool stats_rows_valid = false;  // Es / Ez rows describe the current K^n and Theta
+  // evoamd_reconstruct_resident: the selected reconstruction stays on the device for evoamd_patches_merge_resident.
+  // rec_resident: y_hat (complete data) / Yrec (incomplete) + the masks below describe it; dropped with yhat_valid and by
+  // every upload of data, masks or y_reconstructed.  yrec_from_pass: Yrec was written by the statistics pass y_hat is from.
+  bool rec_resident = false, yrec_from_pass = false;
+  uint8_t *keep_x = nullptr;   // complete data: the caller's keep-mask (N x D), uploaded by evoamd_reconstruct_resident
+  bool keep_x_valid = false, rec_uses_keep = false;
+  uint8_t *row_any = nullptr;  // incomplete data: datapoint has a reliable entry (N), written by evoamd_upload_masks
+  int merge_select_fused = 0;  // option "merge_select_fused" (0: select kernel, then the merge kernels over dense rows -- measured faster)
   // software pipelining across the API boundary: evoamd_mstep_device enqueues the NEXT iteration's pass
   // over the resident K^n behind the mailbox kernel, so the GPU works through the ~40 us the host needs
   // between two iterations; evoamd_lpj_resident then finds it done.  `gen` is bumped by everything that
@@ -576,7 +584,7 @@ static void free_all(evoamd_ctx *c) {
                   c->tmp_y,  c->tmp_lpj, c->tmp_states, c->dig, c->cand_dig, c->lpj_alt, c->cand_raw, c->dupold, c->gen_start,
                   c->pbins.ent, c->pbins.part, c->pbins.gcnt, c->gemm_ws, c->Yt, c->Yf, c->Ytf, c->Wf, c->Bf, c->Esf,
                   c->clist, c->clist_n, c->ovf_rec, c->theta_bak, c->rowF, c->rowcnt, c->defer, c->fpart, c->huge, c->huge_ctl,
-                  c->patch_img, c->patch_Y};
+                  c->patch_img, c->patch_Y, c->keep_x, c->row_any};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (c->h_acc) (void)hipHostFree(c->h_acc);
@@ -631,6 +639,10 @@ extern "C" int evoamd_set_option(evoamd_ctx *c, const char *name, int value) {
   }
   if (strcmp(name, "reconstruct_in_stats") == 0) {  // one-shot: the next statistics pass forms y_reconstructed first
     c->rec_in_stats = value != 0;
+    return 0;
+  }
+  if (strcmp(name, "merge_select_fused") == 0) {
+    c->merge_select_fused = value != 0;
     return 0;
   }
   if (strcmp(name, "prefetch_lpj") == 0) {
@@ -1083,6 +1095,10 @@ extern "C" int evoamd_configure(evoamd_ctx *c, int model, int64_t N, int D, int 
   c->mask_infr = c->mask_x = nullptr;
   c->Yrec = nullptr;
   c->yrec_valid = c->rec_in_stats = false;
+  if (c->keep_x) (void)hipFree(c->keep_x);
+  if (c->row_any) (void)hipFree(c->row_any);
+  c->keep_x = c->row_any = nullptr;
+  c->keep_x_valid = false;
   c->rel_frac = -1.0;
   if (c->cand_raw) (void)hipFree(c->cand_raw);  // sized by the geometry: rebuilt on demand (evoamd_evolve_states)
   if (c->dupold) (void)hipFree(c->dupold);
@@ -1099,7 +1115,7 @@ extern "C" int evoamd_configure(evoamd_ctx *c, int model, int64_t N, int D, int 
   c->have_data = c->have_params = c->have_cand = c->rows_fresh = false;
   if (c->tmpWt) (void)hipFree(c->tmpWt);  // sized by (H, D): rebuilt on demand
   c->tmpWt = nullptr;
-  c->yhat_valid = c->stats_rows_valid = false;
+  c->yhat_valid = c->stats_rows_valid = c->rec_resident = c->yrec_from_pass = false;
   c->theta_bak_valid = false;
   c->lists_clean = c->need_known = c->cand_from_device = false;  // fresh (uninitialised) overflow counters
   return 0;
@@ -1128,6 +1144,7 @@ extern "C" int evoamd_upload_data(evoamd_ctx *c, const double *Y) {
   c->have_data = true;
   c->gen++;
   c->B_valid = false;
+  c->rec_resident = false;
   return 0;
 }
 
@@ -1139,18 +1156,20 @@ extern "C" int evoamd_upload_masks(evoamd_ctx *c, const uint8_t *x_infr, const u
     if (c->mask_infr) (void)hipFree(c->mask_infr);
     if (c->mask_x) (void)hipFree(c->mask_x);
     c->mask_infr = c->mask_x = nullptr;
-    c->yrec_valid = false;
+    c->yrec_valid = c->rec_resident = c->yrec_from_pass = false;
     return 0;
   }
   const size_t nd = (size_t)c->N * c->D;
   ALLOC(c->mask_infr, nd);
   ALLOC(c->mask_x, nd);
   ALLOC(c->Yrec, nd);
+  ALLOC(c->row_any, (size_t)c->N);
   HIP_TRY(hipMemcpyAsync(c->mask_infr, x_infr, nd, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->mask_x, x ? x : x_infr, nd, hipMemcpyHostToDevice, c->stream));
   // missing entries (NaN in the reference's data) become zeros: they then drop out of ||y_obs||^2
   mask_apply_kernel<<<cdiv((i64)nd, 256), 256, 0, c->stream>>>(c->Y, c->ldY, c->mask_infr, c->N, c->D);
   row_sqnorm_kernel<<<cdiv(c->N, 4), 256, 0, c->stream>>>(c->Y, c->ldY, c->N, c->D, c->yy);
+  patches_row_any_kernel<<<cdiv(c->N, 4), 256, 0, c->stream>>>(c->mask_infr, c->N, c->D, c->row_any);
   HIP_TRY(hipMemsetAsync(c->y2sum, 0, (size_t)c->D * sizeof(double), c->stream));
   launch_colsum<true>(c, c->Y, c->ldY, c->N, c->D, c->y2sum);
   if (c->model == EVOAMD_MODEL_SSSC) {  // W^T (H, D) for the per-datapoint Gram blocks
@@ -1160,7 +1179,7 @@ extern "C" int evoamd_upload_masks(evoamd_ctx *c, const uint8_t *x_infr, const u
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->yrec_valid = false;
+  c->yrec_valid = c->rec_resident = c->yrec_from_pass = false;
   c->B_valid = false;
   return 0;
 }
@@ -1177,6 +1196,7 @@ extern "C" int evoamd_upload_yrec(evoamd_ctx *c, const double *y_rec) {
   HIP_TRY(hipMemcpyAsync(c->Yrec, y_rec, (size_t)c->N * c->D * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->yrec_valid = true;
+  c->rec_resident = c->yrec_from_pass = false;
   return 0;
 }
 
@@ -1510,7 +1530,7 @@ extern "C" int evoamd_set_params_bsc(evoamd_ctx *c, const double *W, double pi, 
   c->have_params = true;
   c->gen++;
   c->h_theta_fresh = false;
-  c->yhat_valid = c->stats_rows_valid = false;
+  c->yhat_valid = c->stats_rows_valid = c->rec_resident = c->yrec_from_pass = false;
   return 0;
 }
 
@@ -1589,7 +1609,7 @@ extern "C" int evoamd_set_params_sssc(evoamd_ctx *c, const double *W, const doub
   c->have_params = true;
   c->gen++;
   c->h_theta_fresh = false;
-  c->yhat_valid = c->stats_rows_valid = false;
+  c->yhat_valid = c->stats_rows_valid = c->rec_resident = c->yrec_from_pass = false;
   return 0;
 }
 
@@ -2993,7 +3013,7 @@ static int reconstruct_rows(evoamd_ctx *c, const char *asked_msg = nullptr) {
   if (asked_msg) REQUIRE(c->rec_in_stats, asked_msg);
   select_rec_kernel<<<cdiv(c->N, 4), 256, 0, c->stream>>>(c->Y, c->ldY, c->mask_x, c->mask_infr, c->yhat, c->N, c->D, c->Yrec);
   HIP_TRY(hipGetLastError());
-  c->yrec_valid = true;
+  c->yrec_valid = c->yrec_from_pass = true;
   c->rec_in_stats = false;
   return 0;
 }
@@ -3599,7 +3619,7 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
   if (!c->acc_clean)  // (else: zeroed by the selection kernel on its way)
     HIP_TRY(hipMemsetAsync(c->acc_base, 0, (size_t)(c->ovf_n + c->acc_n) * sizeof(double), c->stream));
   c->acc_clean = false;
-  c->yhat_valid = c->stats_rows_valid = false;
+  c->yhat_valid = c->stats_rows_valid = c->rec_resident = c->yrec_from_pass = false;
   r = ensure_B(c);
   if (r) return r;
   if (!c->rows_fresh) {  // otherwise vary_kn left rowmax / rowsum / dpar[DP_FS] behind
@@ -4352,6 +4372,39 @@ extern "C" int evoamd_patches_extract(evoamd_ctx *c, const double *img, int H, i
   return 0;
 }
 
+// The merge kernels over the estimates `src` serves (PatchRows: dense device rows; PatchSelect: the resident selected
+// reconstruction), into c->patch_img, then the image to the host.  c->patch_img holds img_n doubles.
+template <class Src>
+static int launch_patches_merge(evoamd_ctx *c, const Src &src, const PatchGeom &g, int method, double *img_out) {
+  const size_t img_n = (size_t)g.H * g.W * g.C;
+  {
+    SpanGuard sg(c, KID_PATCHES);
+    if (method == 0) {
+      patches_mean_kernel<<<cdiv((i64)img_n, 256), 256, 0, c->stream>>>(src, g, c->patch_img);
+    } else {
+      const int K = patch_max_cover(g);  // <= ph * pw <= 1024
+      int P = 1;
+      while (P < K) P <<= 1;
+      if (P <= 64) {
+        const i64 waves = ((i64)img_n + 64 / P - 1) / (64 / P);
+        patches_median_kernel<1><<<cdiv(waves, 4), 256, 0, c->stream>>>(src, g, P, c->patch_img);
+      } else {
+        const unsigned blocks = cdiv((i64)img_n, 4);  // one wave per output element
+        switch (P) {
+          case 128: patches_median_kernel<2><<<blocks, 256, 0, c->stream>>>(src, g, P, c->patch_img); break;
+          case 256: patches_median_kernel<4><<<blocks, 256, 0, c->stream>>>(src, g, P, c->patch_img); break;
+          case 512: patches_median_kernel<8><<<blocks, 256, 0, c->stream>>>(src, g, P, c->patch_img); break;
+          default: patches_median_kernel<16><<<blocks, 256, 0, c->stream>>>(src, g, P, c->patch_img); break;
+        }
+      }
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(img_out, c->patch_img, img_n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 extern "C" int evoamd_patches_merge(evoamd_ctx *c, const double *Y, int H, int W, int C, int ph, int pw, int shift,
                                     int method, double *img_out) {
   REQUIRE(c && Y && img_out, "evoamd_patches_merge: NULL argument");
@@ -4363,32 +4416,96 @@ extern "C" int evoamd_patches_merge(evoamd_ctx *c, const double *Y, int H, int W
   int r = ensure_patch_scratch(c, img_n, y_n);
   if (r) return r;
   HIP_TRY(hipMemcpyAsync(c->patch_Y, Y, y_n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  {
-    SpanGuard sg(c, KID_PATCHES);
-    if (method == 0) {
-      patches_mean_kernel<<<cdiv((i64)img_n, 256), 256, 0, c->stream>>>(c->patch_Y, g, c->patch_img);
-    } else {
-      const int K = patch_max_cover(g);  // <= ph * pw <= 1024
-      int P = 1;
-      while (P < K) P <<= 1;
-      if (P <= 64) {
-        const i64 waves = ((i64)img_n + 64 / P - 1) / (64 / P);
-        patches_median_kernel<1><<<cdiv(waves, 4), 256, 0, c->stream>>>(c->patch_Y, g, P, c->patch_img);
-      } else {
-        const unsigned blocks = cdiv((i64)img_n, 4);  // one wave per output element
-        switch (P) {
-          case 128: patches_median_kernel<2><<<blocks, 256, 0, c->stream>>>(c->patch_Y, g, P, c->patch_img); break;
-          case 256: patches_median_kernel<4><<<blocks, 256, 0, c->stream>>>(c->patch_Y, g, P, c->patch_img); break;
-          case 512: patches_median_kernel<8><<<blocks, 256, 0, c->stream>>>(c->patch_Y, g, P, c->patch_img); break;
-          default: patches_median_kernel<16><<<blocks, 256, 0, c->stream>>>(c->patch_Y, g, P, c->patch_img); break;
-        }
-      }
-    }
+  return launch_patches_merge(c, PatchRows{c->patch_Y}, g, method, img_out);
+}
+
+// ---- the selected reconstruction, resident (evoamd_reconstruct_resident / evoamd_patches_merge_resident) ----
+static const char *const REC_OUTDATED =
+    "no current resident reconstruction: call evoamd_reconstruct_resident after the statistics pass (a later statistics "
+    "pass, new parameters, or an upload of data, masks or y_reconstructed outdate it)";
+
+extern "C" int evoamd_reconstruct_resident(evoamd_ctx *c, const uint8_t *x) {
+  REQUIRE(c && c->configured && c->have_data && c->have_params, "evoamd_reconstruct_resident: configure, upload data and set parameters first");
+  REQUIRE(!c->f32, "reconstruction is not available in the float32 mode");
+  HIP_TRY(hipSetDevice(c->device));
+  c->rec_resident = false;
+  if (!c->yhat_valid) {
+    REQUIRE(c->stats_rows_valid, "evoamd_reconstruct_resident: call evoamd_stats first (and before setting new parameters)");
+    int r = compute_reconstruction(c);
+    if (r) return r;
   }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(img_out, c->patch_img, img_n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (c->mask_infr) {  // incomplete data: the masks are resident, x is not read
+    if (!c->yrec_from_pass) {  // the pass ran without reconstruct_in_stats (its M-step read an older y_reconstructed)
+      select_rec_kernel<<<cdiv(c->N, 4), 256, 0, c->stream>>>(c->Y, c->ldY, c->mask_x, c->mask_infr, c->yhat, c->N, c->D, c->Yrec);
+      HIP_TRY(hipGetLastError());
+      c->yrec_valid = c->yrec_from_pass = true;
+    }
+    c->rec_uses_keep = false;
+  } else if (x == EVOAMD_KEEP_RESIDENT) {
+    REQUIRE(c->keep_x_valid, "evoamd_reconstruct_resident: EVOAMD_KEEP_RESIDENT, but no keep-mask was uploaded for this geometry");
+    c->rec_uses_keep = true;
+  } else if (x) {
+    const size_t nd = (size_t)c->N * c->D;
+    if (!c->keep_x) ALLOC(c->keep_x, nd);
+    c->keep_x_valid = false;
+    HIP_TRY(hipMemcpyAsync(c->keep_x, x, nd, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // x is pageable host memory of the caller
+    c->keep_x_valid = c->rec_uses_keep = true;
+  } else {
+    c->rec_uses_keep = false;
+  }
+  c->rec_resident = true;
+  return 0;
+}
+
+// what the merge gathers from; valid while c->rec_resident
+static PatchSelect resident_select(const evoamd_ctx *c) {
+  PatchSelect s;
+  s.rec = c->mask_infr ? c->Yrec : c->yhat;
+  s.Y = c->Y;
+  s.ldY = c->ldY;
+  s.x = c->mask_infr ? c->mask_x : (c->rec_uses_keep ? c->keep_x : nullptr);
+  s.infr = c->mask_infr;
+  s.any = c->row_any;
+  return s;
+}
+
+extern "C" int evoamd_download_reconstruction(evoamd_ctx *c, double *y_hat) {
+  REQUIRE(c && y_hat, "evoamd_download_reconstruction: NULL argument");
+  if (!(c->configured && c->rec_resident && c->yhat_valid)) return fail(EVOAMD_E_INVALID, "evoamd_download_reconstruction: %s", REC_OUTDATED);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(y_hat, c->yhat, (size_t)c->N * c->D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
+}
+
+extern "C" int evoamd_patches_merge_resident(evoamd_ctx *c, int H, int W, int C, int ph, int pw, int shift, int method,
+                                             double *img_out) {
+  REQUIRE(c && img_out, "evoamd_patches_merge_resident: NULL argument");
+  PatchGeom g;
+  if (const char *msg = patch_geom_make(H, W, C, ph, pw, shift, &g)) return fail(EVOAMD_E_INVALID, "evoamd_patches_merge_resident: %s", msg);
+  REQUIRE(method == 0 || method == 1, "evoamd_patches_merge_resident: method must be 0 (mean) or 1 (median)");
+  if (!(c->configured && c->rec_resident)) return fail(EVOAMD_E_INVALID, "evoamd_patches_merge_resident: %s", REC_OUTDATED);
+  if (g.N != c->N || g.D != c->D)
+    return fail(EVOAMD_E_INVALID, "evoamd_patches_merge_resident: the patch geometry is (N, D) = (%lld, %d), the context holds (%lld, %d)",
+                (long long)g.N, g.D, (long long)c->N, c->D);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t img_n = (size_t)H * W * C, y_n = (size_t)g.N * g.D;
+  const PatchSelect sel = resident_select(c);
+  if (c->merge_select_fused) {
+    int r = ensure_patch_scratch(c, img_n, 0);
+    if (r) return r;
+    return launch_patches_merge(c, sel, g, method, img_out);
+  }
+  int r = ensure_patch_scratch(c, img_n, y_n);  // select-then-merge (default): y_rec as dense rows, then the kernels of evoamd_patches_merge
+  if (r) return r;
+  {
+    SpanGuard sg(c, KID_PATCHES);
+    const i64 blocks = (i64)((y_n + 255) / 256);
+    patches_select_kernel<<<(unsigned)(blocks < 65536 ? blocks : 65536), 256, 0, c->stream>>>(sel, g.N, g.D, c->patch_Y);
+  }
+  HIP_TRY(hipGetLastError());
+  return launch_patches_merge(c, PatchRows{c->patch_Y}, g, method, img_out);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -84,15 +84,67 @@ __global__ void __launch_bounds__(256) patches_extract_kernel(const double *__re
   }
 }
 
-// Flat index in Y of the estimate of pixel (y, x, c) held by patch (ir, ic).
-__device__ __forceinline__ i64 patch_elem(const PatchGeom &g, int ir, int ic, int y, int x, int c) {
+// Where the merge kernels read an estimate: element d of patch row n.
+// PatchRows: a dense (N, D) matrix of patch rows.
+struct PatchRows {
+  const double *__restrict__ Y;
+  __device__ __forceinline__ double load(i64 n, int d, int D) const { return Y[n * D + d]; }
+};
+// PatchSelect: the selected reconstruction of a configured context, formed while it is gathered (evoamd_reconstruct_resident):
+//   complete data    x[n, d] ? Y[n, d] : y_hat[n, d]   (x == NULL: y_hat everywhere); rec = y_hat, infr == NULL
+//   incomplete data  rec = y_reconstructed as select_rec_kernel left it for the M-step, in which a kept entry without a
+//                    reliable value holds the 0 that mask_apply_kernel put into Y: it reads as NaN here (kept =
+//                    x[n, d], or patch n has no reliable entry at all: any[n] == 0).  Precondition for parity with a
+//                    merge of the host array: the caller's y is NaN wherever infr is 0 (evo_amd.h)
+struct PatchSelect {
+  const double *rec;    // (N, D)
+  const double *Y;      // (N, ldY) resident data
+  i64 ldY;
+  const uint8_t *x;     // (N, D) keep-mask or NULL
+  const uint8_t *infr;  // (N, D) reliable entries, NULL for complete data
+  const uint8_t *any;   // (N) patch has a reliable entry (incomplete data)
+  __device__ __forceinline__ double load(i64 n, int d, int D) const {
+    const i64 e = n * D + d;
+    if (infr) {
+      const bool lost = !infr[e] && (x[e] || !any[n]);
+      return lost ? __builtin_nan("") : rec[e];
+    }
+    return (x && x[e]) ? Y[n * ldY + d] : rec[e];
+  }
+};
+
+// The estimate of pixel (y, x, c) held by patch (ir, ic).
+template <class Src>
+__device__ __forceinline__ double patch_estimate(const Src &src, const PatchGeom &g, int ir, int ic, int y, int x, int c) {
   const int dy = y - patch_top(ir, g.H, g.ph, g.s), dx = x - patch_top(ic, g.W, g.pw, g.s);
-  return ((i64)ir * g.nc + ic) * g.D + (dy * g.pw + dx) * g.C + c;
+  return src.load((i64)ir * g.nc + ic, (dy * g.pw + dx) * g.C + c, g.D);
+}
+
+// out[n, d] = src(n, d): the selected reconstruction written out as dense patch rows (the select-then-merge route of
+// evoamd_patches_merge_resident; the fused route gathers through PatchSelect instead).
+__global__ void __launch_bounds__(256) patches_select_kernel(PatchSelect src, i64 N, int D, double *__restrict__ out) {
+  const i64 total = N * D;
+  for (i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (i64)gridDim.x * blockDim.x) {
+    const i64 n = e / D;
+    out[e] = src.load(n, (int)(e - n * D), D);
+  }
+}
+
+// any[n] = row n of the (N, D) byte mask has a non-zero entry; one wave per row.
+__global__ void __launch_bounds__(256) patches_row_any_kernel(const uint8_t *__restrict__ mask, i64 N, int D,
+                                                              uint8_t *__restrict__ any) {
+  const int lane = lane_id();
+  const i64 n = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (n >= N) return;
+  bool a = false;
+  for (int d = lane; d < D; d += 64) a = a || mask[n * D + d] != 0;
+  a = __any(a);
+  if (lane == 0) any[n] = a ? 1 : 0;
 }
 
 // Mean merge: one thread per output element, its estimates summed in increasing n (NumPy's order for axis 0).
-__global__ void __launch_bounds__(256) patches_mean_kernel(const double *__restrict__ Y, PatchGeom g,
-                                                           double *__restrict__ out) {
+template <class Src>
+__global__ void __launch_bounds__(256) patches_mean_kernel(Src src, PatchGeom g, double *__restrict__ out) {
 #pragma clang fp contract(off)
   const i64 total = (i64)g.H * g.W * g.C;
   const i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -107,7 +159,7 @@ __global__ void __launch_bounds__(256) patches_mean_kernel(const double *__restr
   int cnt = 0;
   for (int ir = r0; ir <= r1; ir++)
     for (int ic = c0; ic <= c1; ic++) {
-      const double v = Y[patch_elem(g, ir, ic, y, x, c)];
+      const double v = patch_estimate(src, g, ir, ic, y, x, c);
       if (v == v) {
         sum += v;
         cnt++;
@@ -120,9 +172,8 @@ __global__ void __launch_bounds__(256) patches_mean_kernel(const double *__restr
 // estimates, across R registers per lane: element index = r * 64 + lane).  R = 1: segments of P lanes (P = the power of
 // two >= the largest estimate count, <= 64), 64 / P output elements per wave; R > 1: P = 64 R, one element per wave.
 // NaN and the padding sort as +inf; the count of valid estimates picks the middle ones.  Registers: R doubles per lane.
-template <int R>
-__global__ void __launch_bounds__(256) patches_median_kernel(const double *__restrict__ Y, PatchGeom g, int P,
-                                                             double *__restrict__ out) {
+template <int R, class Src>
+__global__ void __launch_bounds__(256) patches_median_kernel(Src src, PatchGeom g, int P, double *__restrict__ out) {
 #pragma clang fp contract(off)
   const int lane = lane_id();
   const int seg = R == 1 ? P : 64;  // lanes per output element
@@ -152,7 +203,7 @@ __global__ void __launch_bounds__(256) patches_median_kernel(const double *__res
     bool ok = false;
     if (k < K) {
       const int ir = r0 + k / kc, ic = c0 + k % kc;
-      t = Y[patch_elem(g, ir, ic, y, x, c)];
+      t = patch_estimate(src, g, ir, ic, y, x, c);
       ok = t == t;
       if (!ok) t = inf;
     }

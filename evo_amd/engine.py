@@ -43,6 +43,9 @@ class Engine:
         self.f32 = False  # EBSC float32 mode of the configured geometry (option "ebsc_f32")
         self.world = 1
         self.rank = 0
+        self._configures = 0  # evoamd_configure calls: a keep-mask uploaded for an earlier geometry is gone
+        self._keep_token = None  # (x object, geometry, _configures, any(x)) of the keep-mask on the device
+        self._rec_serial = 0     # counts reconstruct_resident calls: names the reconstruction the device holds
 
     # ---- lifetime ------------------------------------------------------------------------
     def close(self):
@@ -69,6 +72,7 @@ class Engine:
         self.N, self.D, self.H, self.S, self.S_perm, self.Cmax = int(N), int(D), int(H), int(S), int(S_perm), int(Cmax)
         self.L = self.S + self.S_perm
         self.has_masks = False  # evoamd_configure drops the masks of the previous geometry
+        self._configures += 1
 
     def same_geometry(self, model, N, D, H, S, S_perm, Cmax):
         m = MODEL_BSC if model in (MODEL_BSC, "bsc", "BSC") else MODEL_SSSC
@@ -374,6 +378,58 @@ class Engine:
         check(self.lib.evoamd_patches_merge(self._h, dptr(Y), H, W, C, int(ph), int(pw), int(shift), m, dptr(out)))
         return out
 
+    # ---- the reconstruction kept on the device (evo_amd.models: resident_reconstruction=True) ----------
+    def reconstruct_resident(self, x=None):
+        """Make the selected reconstruction of the last statistics pass resident (nothing comes to the host): y where it
+        is kept, the posterior-predictive estimate elsewhere.  ``x``: the (N, D) keep-mask of complete data (None or all
+        False: every entry is estimated), uploaded once per array object; with incomplete data the masks of
+        upload_masks are used and ``x`` is not read.  Like every resident array the mask is keyed on the array OBJECT: after
+        an in-place edit of ``x`` the device keeps the old mask (while np.asarray of a handle reads the edited one) until
+        Model.invalidate() / a new array object.  Returns a serial number: patches_merge_resident /
+        download_reconstruction given another one refuse to hand out a newer reconstruction."""
+        if x is None or self.has_masks:
+            ptr = None
+        else:
+            tok = self._keep_token
+            geom = (self.model, self.N, self.D)
+            if tok is not None and tok[0] is x and tok[1] == geom and tok[2] == self._configures:
+                ptr = _KEEP_RESIDENT if tok[3] else None
+            else:
+                mx = as_bool_bytes(x)
+                assert mx.shape == (self.N, self.D), (mx.shape, self.N, self.D)
+                used = bool(mx.any())
+                self._keep_token = (x, geom, self._configures, used)
+                ptr = u8ptr(mx) if used else None
+        check(self.lib.evoamd_reconstruct_resident(self._h, ptr))
+        self._rec_serial += 1
+        return self._rec_serial
+
+    def _check_serial(self, serial):
+        if serial is not None and serial != self._rec_serial:
+            raise EvoAmdError("the resident reconstruction on the device is a newer one (a later reconstruct_resident)")
+
+    def download_reconstruction(self, serial=None):
+        """y_hat (N, D) of the resident reconstruction; EvoAmdError once it is outdated."""
+        self._check_serial(serial)
+        out = np.empty((self.N, self.D))
+        check(self.lib.evoamd_download_reconstruction(self._h, dptr(out)))
+        return out
+
+    def patches_merge_resident(self, shape, ph, pw, shift=1, method="mean", serial=None):
+        """patches_merge over the resident selected reconstruction: only the image crosses to the host.  The geometry must
+        give (N, D) of the configured context (ValueError)."""
+        from .utils.prepost import patch_geometry
+        H, W, C = _image_hwc(shape)
+        N, D = patch_geometry(H, W, C, ph, pw, shift)
+        if (N, D) != (self.N, self.D):
+            raise ValueError("patches_merge_resident: the geometry needs (%d, %d), the resident reconstruction is (%d, %d)"
+                             % (N, D, self.N, self.D))
+        self._check_serial(serial)
+        m = {"mean": 0, "median": 1}[method]
+        out = np.empty(tuple(shape), dtype=np.float64)
+        check(self.lib.evoamd_patches_merge_resident(self._h, H, W, C, int(ph), int(pw), int(shift), m, dptr(out)))
+        return out
+
     # ---- timing --------------------------------------------------------------------------
     def timing(self, on=True):
         """on: True (all kernel classes), False, or an iterable of class names (_lib.KERNEL_IDS)."""
@@ -395,6 +451,9 @@ class Engine:
         n = ctypes.c_int64()
         check(self.lib.evoamd_kernel_time_ms(self._h, _lib.KERNEL_IDS[name], ctypes.byref(avg), ctypes.byref(n)))
         return avg.value, n.value
+
+
+_KEEP_RESIDENT = ctypes.cast(1, _lib._c_u8p)  # EVOAMD_KEEP_RESIDENT of include/evo_amd.h
 
 
 def _image_hwc(shape):

@@ -23,6 +23,7 @@ N datapoints of this rank (see evo_amd/engine.py and csrc/).  Two candidate-gene
 import numpy as np
 
 from .. import engine as _engine
+from ..resident import ResidentReconstruction
 from ..utils import parallel
 from ..variational import eas
 from ..variational.utils import vary_Kn  # noqa: F401  (re-exported like the reference module does)
@@ -158,7 +159,8 @@ class Model:
     model_name = None  # "bsc" | "sssc"
 
     def __init__(self, D, H, S, to_learn=("W", "pi", "sigma"), comm=None, rng="reference", sync_host=True,
-                 device=None, engine=None, seed=0, device_mstep=False, dtype=np.float64, lazy_theta=False):
+                 device=None, engine=None, seed=0, device_mstep=False, dtype=np.float64, lazy_theta=False,
+                 resident_reconstruction=False):
         """``D, H, S, to_learn, comm`` as in the reference (_models.py:20-56).  ``comm`` may be an
         mpi4py communicator or one of evo_amd.utils.parallel; None means one rank."""
         if rng not in ("reference", "device"):
@@ -179,6 +181,13 @@ class Model:
         # iteration whether or not the caller looks at it.  Off by default: the returned object is then the caller's
         # own dict, mutated in place like the reference does.
         self.lazy_theta = bool(lazy_theta)
+        # resident_reconstruction: wherever my_data["y_reconstructed"] is written (step / E_step / reconstruct with
+        # do_reconstruction), the selected reconstruction stays on the device and the entry is a ResidentReconstruction
+        # handle (evo_amd/resident.py) instead of an N x D ndarray: OverlappingPatches.set_and_merge(handle.T) merges it
+        # there and only the image crosses to the host; np.asarray(handle) downloads what the default path stores.
+        # Off by default: the reference's loop reads an ndarray every epoch.
+        self.resident_reconstruction = bool(resident_reconstruction)
+        self._rec_handle = None
         # dtype=np.float32 (EBSC only): the data, B = Y W and the E_q[s] rows are kept in float and the two long
         # contractions run on the f32 matrix cores; lpj arithmetic, selection, sums and Theta stay float64.  The reference
         # is float64-only -- this is BASELINE.json configs[4]'s "float32"; agreement with the float64 path ~1e-6 in lpj / F.
@@ -233,6 +242,8 @@ class Model:
         my_data every step; here an unchanged array object is taken to hold unchanged data)."""
         self._y_token = self._x_infr_token = self._yrec_token = None
         self._xi_all_token = None
+        if self._engine is not None:
+            self._engine._keep_token = None  # the keep-mask of reconstruct_resident (my_data["x"], complete data)
         self._resident = False
         self._dev_theta = None
 
@@ -269,6 +280,13 @@ class Model:
         new_masks = not self._same_objects(self._x_infr_token, *xi_objs)
         if new_masks:  # checked once per array object, like the Y upload below
             self._incomplete = not self._complete(my_data)
+        yr = my_data.get("y_reconstructed")
+        if (isinstance(yr, ResidentReconstruction) and yr.resident and not yr.materialised
+                and (new_masks or not self._same_objects(self._y_token, Y))):
+            # the uploads below drop the device copy of an older reconstruction that the M-step may still have to read
+            # (bsc.py:186): fetch it first -- the default path holds it as an ndarray and uploads that
+            yr.rows()
+        reuploaded = False
         N, D = Y.shape
         assert D == self.D
         S_perm = int(my_suff_stat["S_perm"])
@@ -291,6 +309,7 @@ class Model:
             self._y_token = (Y,)
             new_masks = True
         if new_masks:
+            reuploaded = True
             if self._incomplete:
                 eng.upload_masks(xi, my_data.get("x"))
                 self._yrec_token = None
@@ -302,8 +321,12 @@ class Model:
         if self._incomplete and "y_reconstructed" in my_data:
             yr = my_data["y_reconstructed"]
             if not self._same_objects(self._yrec_token, yr):  # an older reconstruction the M-step should read (bsc.py:186)
-                eng.upload_yrec(np.where(np.isnan(yr), 0.0, yr))
-                self._yrec_token = (yr,)
+                current = (isinstance(yr, ResidentReconstruction) and yr.resident and yr.engine is eng
+                           and not reuploaded)  # (upload_masks re-allocates the device's y_reconstructed)
+                if not current:
+                    yr_rows = np.asarray(yr.T if getattr(yr, "transposed", False) else yr)
+                    eng.upload_yrec(np.where(np.isnan(yr_rows), 0.0, yr_rows))
+                self._yrec_token = (yr,)  # (a current handle: the device holds it already)
         if upload_states and (self.sync_host or not self._resident):
             eng.upload_states(my_suff_stat["ss"])
             self._resident = True
@@ -380,7 +403,16 @@ class Model:
     def _write_reconstruction(self, my_data):
         """my_data["y_reconstructed"] (_models.py:643-665, sssc.py:507,613-627; complete data): a copy of
         y whose entries with my_data["x"] False are the posterior-predictive estimate W E_q[s] (EBSC) /
-        W E_q[s o z] (ES3C) under the Theta and K^n of the statistics pass that just ran."""
+        W E_q[s o z] (ES3C) under the Theta and K^n of the statistics pass that just ran.
+        resident_reconstruction: the same selection on the device, and a handle in place of the array."""
+        if self.resident_reconstruction:
+            if self._rec_handle is not None:
+                self._rec_handle._outdate("a later reconstruction (step / E_step / reconstruct) of the same model")
+            serial = self.engine.reconstruct_resident(my_data["x"])
+            self._rec_handle = ResidentReconstruction(self.engine, serial, my_data["y"], my_data["x"],
+                                                      my_data["x_infr"] if self._incomplete else None)
+            my_data["y_reconstructed"] = self._rec_handle
+            return
         y_hat = self.engine.reconstruct()
         y_rec = my_data["y"].copy()
         miss = np.logical_not(my_data["x"])

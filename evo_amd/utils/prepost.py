@@ -5,7 +5,8 @@
 
 With evo_amd that import reads ``from evo_amd.utils.prepost import ...`` and the loops run unchanged.  Extraction and
 the two standard merges run as HIP kernels on the GPU (``Engine.patches_extract`` / ``Engine.patches_merge``); any other
-merge callable runs on the host over the stack of estimates.
+merge callable runs on the host over the stack of estimates.  A model built with ``resident_reconstruction=True`` stores a
+``ResidentReconstruction`` handle in my_data["y_reconstructed"]; ``set_and_merge(handle.T, ...)`` merges it on the device.
 
 Conventions (ours; tvutil is not a dependency and bit parity with it is not claimed):
 
@@ -23,6 +24,8 @@ Conventions (ours; tvutil is not a dependency and bit parity with it is not clai
 import warnings
 
 import numpy as np
+
+from ..resident import ResidentReconstruction
 
 MAX_PATCH_ELEMS = 1024
 
@@ -139,7 +142,14 @@ class OverlappingPatches:
         return self._patches().T
 
     def set(self, Y_T):
-        """Store new patches, (D, N) like get() returns them."""
+        """Store new patches, (D, N) like get() returns them, or a ResidentReconstruction handle (either face)."""
+        if isinstance(Y_T, ResidentReconstruction):
+            rows = Y_T.T if Y_T.transposed else Y_T
+            if rows.shape != (self.N, self.D):
+                raise ValueError("set: the resident reconstruction is (N, D) = %s, the patches are %s"
+                                 % (rows.shape, (self.N, self.D)))
+            self._Y = rows
+            return
         Y_T = np.asarray(Y_T)
         if Y_T.shape != (self.D, self.N):
             raise ValueError("set: expected patches of shape (D, N) = %s, got %s" % ((self.D, self.N), Y_T.shape))
@@ -147,9 +157,21 @@ class OverlappingPatches:
 
     def merge(self, merge_method=mean_merger):
         """Image of the input's shape from the current patches.  mean_merger / median_merger run on the GPU; any other
-        callable f is applied on the host as f(stack, axis=0) to the NaN-padded (K, H, W[, C]) estimate stack."""
+        callable f is applied on the host as f(stack, axis=0) to the NaN-padded (K, H, W[, C]) estimate stack.
+        After set() with a ResidentReconstruction handle, mean_merger / median_merger read the reconstruction on the
+        HANDLE's engine (the model's context, whichever engine this object was built with) and only the image comes
+        back; any other callable, or a handle whose array was read and whose device copy is gone, takes the host array.
+        That covers one rank holding all patches: with several ranks gather as before
+        (gather_from_processes(my_data["y_reconstructed"]) materialises the handle)."""
         Y = self._patches()
-        if merge_method is mean_merger or merge_method is median_merger:
+        gpu_merge = merge_method is mean_merger or merge_method is median_merger
+        if isinstance(Y, ResidentReconstruction):
+            if gpu_merge:
+                img = Y.merge(self.shape, self.ph, self.pw, self.shift, "mean" if merge_method is mean_merger else "median")
+                if img is not None:
+                    return img
+            Y = Y.rows()
+        if gpu_merge:
             method = "mean" if merge_method is mean_merger else "median"
             return self.engine.patches_merge(Y, self.shape, self.ph, self.pw, self.shift, method)
         stack = estimate_stack(Y, self.shape[0], self.shape[1], self.C, self.ph, self.pw, self.shift)

@@ -87,6 +87,8 @@ int evoamd_synchronize(evoamd_ctx *ctx);
  * 0 = up to n = 128 the whole elimination in ONE launch (one workgroup per matrix, the matrix in its registers), 32 from
  * n = 256 on (32 x 32 pivot block inverted in registers through its Schur complement), 16 in between; 16 / 32 force the
  * multi-launch forms.
+ * "merge_select_fused" (0/1, default 0): evoamd_patches_merge_resident writes y_rec as N x D rows first and merges those
+ *   (0, measured faster) or selects while it gathers (1); same image bit for bit, see there.
  * "prefetch_lpj" (0/1, default 1): evoamd_mstep_device enqueues the next iteration's evoamd_lpj_resident
  * pass behind its mailbox kernel (the GPU works while the host turns the iteration around); the next
  * evoamd_lpj_resident call returns at once unless Theta, K^n, the data or an option changed in between.
@@ -393,6 +395,33 @@ int evoamd_patches_extract(evoamd_ctx *ctx, const double *img, int H, int W, int
  * bit), 1 median (np.nanmedian of that stack, bit for bit: even counts give (lo + hi) / 2).  No valid estimate: NaN. */
 int evoamd_patches_merge(evoamd_ctx *ctx, const double *Y, int H, int W, int C, int ph, int pw, int shift, int method,
                          double *img_out);
+/* The reconstruction without the N x D round trip: what Model.reconstruct / step(do_reconstruction) write into
+ * my_data["y_reconstructed"] (_models.py:643-665) stays on the device and only the merged image comes back.
+ * evoamd_reconstruct_resident makes the SELECTED reconstruction of the last statistics pass resident and copies nothing to
+ * the host: y_rec[n, d] = keep(n, d) ? y[n, d] : y_hat[n, d], y_hat as evoamd_reconstruct forms it (same preconditions,
+ * not in the float32 mode).  Incomplete data (evoamd_upload_masks): keep = x[n, d], or datapoint n has no reliable entry;
+ * the masks on the device are used, the argument is not read, and the y_reconstructed that the statistics pass wrote for the
+ * M-step (option "reconstruct_in_stats") is reused, not formed again.  A kept entry that is not reliable reads as NaN in the
+ * merge (the device copy of Y holds a zero there, which the M-step keeps reading).  PRECONDITION for the merged image to
+ * equal the merge of the host array: the caller's y is NaN wherever x_infr is 0, as in the examples; a finite value the
+ * host keeps in such an entry is not on the device and cannot be merged from there.  Complete data:
+ * x (N x D bool bytes) is the keep-mask, copied to the device by this call; NULL = every entry is estimated;
+ * EVOAMD_KEEP_RESIDENT = the mask the previous call uploaded for this geometry (upload once per mask, not per epoch).
+ * The resident reconstruction belongs to one statistics pass: the next pass, evoamd_set_params_*, evoamd_upload_data /
+ * _masks / _yrec and evoamd_configure outdate it.
+ * evoamd_patches_merge_resident: evoamd_patches_merge over it.  The patch geometry must give (N, D) of the configured
+ * context; EVOAMD_E_INVALID when it does not or when no current resident reconstruction exists (never stale data).
+ * Same kernels, same bits as evoamd_patches_merge of the host array; leaves the EM state untouched like it.  Option
+ * "merge_select_fused" (default 0): a select kernel writes y_rec (NaN where a kept entry is not reliable) as N x D rows into
+ * the patch scratch and the kernels of evoamd_patches_merge read that; 1: the merge kernels select while they gather (y,
+ * y_hat and the masks read in place) -- one N x D write and read less, but measured slower.
+ * evoamd_download_reconstruction: y_hat (N x D, host) of the resident reconstruction, for a caller that wants the array
+ * after all; unlike evoamd_reconstruct it refuses (EVOAMD_E_INVALID) once the reconstruction is outdated. */
+#define EVOAMD_KEEP_RESIDENT ((const uint8_t *)(uintptr_t)1)
+int evoamd_reconstruct_resident(evoamd_ctx *ctx, const uint8_t *x_or_null);
+int evoamd_patches_merge_resident(evoamd_ctx *ctx, int H, int W, int C, int ph, int pw, int shift, int method,
+                                  double *img_out);
+int evoamd_download_reconstruction(evoamd_ctx *ctx, double *y_hat);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------------- */
 /* 128-byte opaque id made by rank 0 and distributed by the caller (file / socket / MPI). */
