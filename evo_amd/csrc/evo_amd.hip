@@ -174,17 +174,11 @@ struct evoamd_ctx {
   // the evolutionary operators leave it alone (eas.py:213-239) and the Theta update pins its prior to 1 - 1.1e-5
   // (bsc.py:259-260, sssc.py:718-719)
   int bg_unit = 0;
-  // the mailbox header written by the last kernel of the ES3C update (lazy Theta, mailbox on the main stream): request
-  // (evoamd_mstep_device) and the sequence number that kernel was given (0 = the mailbox kernel has to run)
   // option "fold_clear": evoamd_vary_kn's kernel zeroes the accumulators of the next statistics pass and checks + clears
   // the census counters on its way (was a memset and a one-workgroup kernel in front of the census)
   int fold_clear = 1;
   bool acc_clean = false, clist_clean = false;
-  bool wq_copy_valid = false;
-  double *gram_diag_out = nullptr;  // set around a launch_gemm_tn call whose Gram kernel should also write diag(G)
-  bool gram_diag_written = false;  // EBSC: tmpA holds a copy of Wq (written by the finish kernel of the last statistics pass)
-  bool mbox_fold_req = false;
-  unsigned long long mbox_folded_seq = 0;
+  bool wq_copy_valid = false;  // EBSC: tmpA holds a copy of Wq (written by the finish kernel of the last statistics pass)
   int stats_chunks = 1;  // option "stats_chunks": the statistics pass runs in this many blocks of datapoints, the MFMA
                          // contraction of block i on the second stream beside the scatter kernels of block i + 1.
                          // Measured at the north-star shape (N = 100k, H = 512): 1 block 5.47 ms per iteration, 2 blocks
@@ -212,10 +206,10 @@ struct evoamd_ctx {
   size_t gemm_ws_n = 0;
   int pair_bins = 1;
   int gemm_streamk = 1;  // option "gemm_streamk": long-K 128-tile contraction as one resident-sized stream-K grid
-  int fork_spare = 0;  // what "sk_spare" = -1 (automatic) resolves to for the product being forked (stats_compute)
   int sk_spare = -1;  // option "sk_spare": workgroups per XCD the FORKED stream-K contraction leaves unlaunched, so that the
                      // H x H elimination chain on the main stream finds free CU slots beside it (a persistent grid of
-                     // 2 workgroups per CU otherwise holds every slot until the product is done)
+                     // 2 workgroups per CU otherwise holds every slot until the product is done); -1 = automatic
+                     // (StatsPlan::gemm_spare)
   int sssc_prec32 = 0;  // option "sssc_precision" = 32: SSSC(precision=np.float32), see evoamd_set_option in the header
   int main_unstaged = 1;  // option "lpj_main_unstaged": candidate batches on the table-driven lpj kernel without staged B rows
   // option "lpj_singular_screen": exactly singular Psi_A above two latents the reference's way (kernels_sssc.hpp,
@@ -395,8 +389,9 @@ struct evoamd_ctx {
 struct SpanGuard {
   evoamd_ctx *c;
   int kid;
+  hipStream_t stream;  // where the span's work is enqueued: the main stream unless the caller names another
   hipEvent_t a = nullptr, b = nullptr;
-  SpanGuard(evoamd_ctx *ctx, int k) : c(ctx), kid(k) {
+  SpanGuard(evoamd_ctx *ctx, int k, hipStream_t s = nullptr) : c(ctx), kid(k), stream(s ? s : ctx->stream) {
     if (!c->timing || !((c->timing_mask >> k) & 1u)) return;
     auto get = [&]() {
       hipEvent_t e;
@@ -410,11 +405,11 @@ struct SpanGuard {
     };
     a = get();
     b = get();
-    (void)hipEventRecord(a, c->stream);
+    (void)hipEventRecord(a, stream);
   }
   ~SpanGuard() {
     if (!c->timing || !a) return;
-    (void)hipEventRecord(b, c->stream);
+    (void)hipEventRecord(b, stream);
     c->spans.push_back({a, b, kid});
   }
 };
@@ -1330,9 +1325,24 @@ static bool launch_gemm_nn_raw(evoamd_ctx *c, const double *A, int lda, const do
   return false;
 }
 
-// C (M x Nc) = A^T B, K rows; C is zeroed first when K is split.
-// accumulate: C += A^T B with the atomic epilogue whatever the split (C holds earlier blocks of the same product: the
-// chunked statistics pass); mirror = false leaves the lower tiles of a symmetric block for a later call.
+// How a C = A^T B product runs, beyond its operands (launch_gemm_tn; launch_gemm_tn_f32 reads stream and spare).
+struct GemmTnOpts {
+  bool deterministic = false;  // no split-K atomics: the same operands give the same bits every time
+  // sym_row0 >= 0: rows sym_row0 .. of C are X^T X (symmetric, Nc x Nc, sym_row0 a multiple of the
+  // tile size): only its upper tiles are computed, the rest is mirrored
+  int sym_row0 = -1;
+  bool c_is_zero = false;   // C needs no memset in front of a split product
+  bool accumulate = false;  // C += A^T B with the atomic epilogue whatever the split (C holds earlier blocks of the same
+                            // product: the chunked statistics pass)
+  bool mirror = true;       // false leaves the lower tiles of a symmetric block for a later call
+  hipStream_t stream = nullptr;  // nullptr = the main stream; the statistics contraction runs on stream2
+  int spare = 0;  // stream-K / grouped grid: workgroups per XCD left unlaunched (stats_contract_block: beside the Theta chain)
+  double *diag = nullptr;  // where gram_small_kernel runs (gram_is_small) it writes diag(C) here on its way
+};
+
+// G = W^T W small enough for the one-wave-per-16x16-block kernel, which can leave diag(G) as well
+static bool gram_is_small(int M, i64 K) { return M <= 512 && K <= 4096; }
+
 // Workspace of the stream-K contractions: `segmax` 128 x 128 slabs per workgroup (a run of U / wpx units touches at
 // most n_real / wpx + 2 tiles).  Returns nullptr (atomic epilogue) when it cannot be had.
 static double *streamk_workspace(evoamd_ctx *c, unsigned wpx, i64 n_real, int *segmax) {
@@ -1352,17 +1362,17 @@ static double *streamk_workspace(evoamd_ctx *c, unsigned wpx, i64 n_real, int *s
   return c->gemm_ws;
 }
 
+// C (M x Nc) = A^T B, K rows; C is zeroed first when K is split.
 static int launch_gemm_tn(evoamd_ctx *c, const double *A, int lda, const double *B, int ldb, double *C, int ldc,
-                          int M, int Nc, i64 K, bool deterministic = false, int sym_row0 = -1,
-                          bool c_is_zero = false, bool accumulate = false, bool mirror = true) {
-  // sym_row0 >= 0: rows sym_row0 .. of C are X^T X (symmetric, Nc x Nc, sym_row0 a multiple of the
-  // tile size): only its upper tiles are computed, the rest is mirrored
-  if (deterministic && A == B && lda == ldb && M == Nc && M <= 512 && K <= 4096 && sym_row0 < 0) {
+                          int M, int Nc, i64 K, const GemmTnOpts &o = GemmTnOpts()) {
+  const bool deterministic = o.deterministic, c_is_zero = o.c_is_zero, accumulate = o.accumulate, mirror = o.mirror;
+  int sym_row0 = o.sym_row0;
+  const hipStream_t stream = o.stream ? o.stream : c->stream;
+  if (deterministic && A == B && lda == ldb && M == Nc && sym_row0 < 0 && gram_is_small(M, K)) {
     // G = W^T W of the Theta update: one wave per 16 x 16 block (gram_small_kernel)
-    SpanGuard g(c, KID_GEMM);
+    SpanGuard g(c, KID_GEMM, stream);
     const int nb16 = (int)cdiv(M, 16);
-    gram_small_kernel<<<dim3(nb16, nb16), 256, 0, c->stream>>>(A, lda, (int)K, M, C, ldc, c->gram_diag_out);
-    c->gram_diag_written = c->gram_diag_out != nullptr;
+    gram_small_kernel<<<dim3(nb16, nb16), 256, 0, stream>>>(A, lda, (int)K, M, C, ldc, o.diag);
     HIP_TRY(hipGetLastError());
     return 0;
   }
@@ -1421,10 +1431,10 @@ static int launch_gemm_tn(evoamd_ctx *c, const double *A, int lda, const double 
   if (split) {
     kps = (K + splits - 1) / splits;
     kps = ((kps + GEMM_BK - 1) / GEMM_BK) * GEMM_BK;
-    if (!c_is_zero && !accumulate) HIP_TRY(hipMemsetAsync(C, 0, (size_t)M * ldc * sizeof(double), c->stream));
+    if (!c_is_zero && !accumulate) HIP_TRY(hipMemsetAsync(C, 0, (size_t)M * ldc * sizeof(double), stream));
   }
   const unsigned grid = (unsigned)(tiles * (split ? splits : 1));
-  SpanGuard g(c, KID_GEMM);
+  SpanGuard g(c, KID_GEMM, stream);
   if (big && split && c->gemm_streamk) {
     // stream-K: one resident-sized grid, every XCD owns an eighth of K (option "gemm_streamk")
     i64 real = tiles;
@@ -1434,8 +1444,7 @@ static int launch_gemm_tn(evoamd_ctx *c, const double *A, int lda, const double 
     }
     const i64 Kx = ((cdiv(K, 8) + GEMM_BK - 1) / GEMM_BK) * GEMM_BK;
     // forked beside the Theta-update chain (stats_compute): leave sk_spare slots per XCD to the chain's kernels
-    const int spare = (c->stream == c->stream2) ? (c->sk_spare >= 0 ? c->sk_spare : c->fork_spare) : 0;
-    const unsigned wpx = (unsigned)std::max(1, 2 * c->n_cu / 8 - spare);
+    const unsigned wpx = (unsigned)std::max(1, 2 * c->n_cu / 8 - o.spare);
     int segmax = 0;
     double *ws = c->gemm_ws_opt ? streamk_workspace(c, wpx, real, &segmax) : nullptr;
     // grouped split-K (gemm_f64.hpp): when whole chunks per tile fill the resident grid (>= 93 % of its slots) and a
@@ -1443,25 +1452,25 @@ static int launch_gemm_tn(evoamd_ctx *c, const double *A, int lda, const double 
     const i64 J = (i64)8 * wpx / real;
     if (ws && c->gemm_grouped && J >= 2 && real * J * 100 >= (i64)8 * wpx * 93 && K / J >= 256) {
       const i64 Kc = ((cdiv(K, J) + 2 * GEMM_BK - 1) / (2 * GEMM_BK)) * (2 * GEMM_BK);  // whole slab pairs: no padding slab, mask-free drain
-      gemm_tn128_gk<double><<<8 * wpx, 256, GEMM128_LDS_BYTES, c->stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, Kc, gx, gy,
+      gemm_tn128_gk<double><<<8 * wpx, 256, GEMM128_LDS_BYTES, stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, Kc, gx, gy,
                                                                             sym_row0, (int)real, (int)J, ws);
-      gemm_gk_reduce_kernel<<<dim3((unsigned)real, GEMM_T * GEMM_T / 256), 256, 0, c->stream>>>(ws, C, ldc, M, Nc, gx, gy,
+      gemm_gk_reduce_kernel<<<dim3((unsigned)real, GEMM_T * GEMM_T / 256), 256, 0, stream>>>(ws, C, ldc, M, Nc, gx, gy,
                                                                                                sym_row0, (int)real, (int)J);
     } else {
-    gemm_tn128_sk_f64<<<8 * wpx, 256, GEMM128_LDS_BYTES, c->stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, Kx, gx, gy, sym_row0,
+    gemm_tn128_sk_f64<<<8 * wpx, 256, GEMM128_LDS_BYTES, stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, Kx, gx, gy, sym_row0,
                                                                        (int)real, ws, segmax);
     if (ws)
-      gemm_sk_reduce_kernel<<<dim3((unsigned)real, GEMM_T * GEMM_T / 256), 256, 0, c->stream>>>(
+      gemm_sk_reduce_kernel<<<dim3((unsigned)real, GEMM_T * GEMM_T / 256), 256, 0, stream>>>(
           ws, segmax, C, ldc, M, Nc, K, Kx, gx, gy, sym_row0, (int)real, (int)wpx);
     }
   } else if (big)
-    gemm_tn128_f64<<<grid, 256, GEMM128_LDS_BYTES, c->stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, kps, gx, gy, split, sym_row0);
+    gemm_tn128_f64<<<grid, 256, GEMM128_LDS_BYTES, stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, kps, gx, gy, split, sym_row0);
   else if (vec)
-    gemm_tn_f64<true><<<grid, 256, 0, c->stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, kps, gx, gy, split, sym_row0);
+    gemm_tn_f64<true><<<grid, 256, 0, stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, kps, gx, gy, split, sym_row0);
   else
-    gemm_tn_f64<false><<<grid, 256, 0, c->stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, kps, gx, gy, split, sym_row0);
+    gemm_tn_f64<false><<<grid, 256, 0, stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, kps, gx, gy, split, sym_row0);
   if (sym_row0 >= 0 && mirror)
-    mirror_lower_kernel<<<cdiv((i64)Nc * Nc, 256), 256, 0, c->stream>>>(C + (size_t)sym_row0 * ldc, Nc, ldc, T);
+    mirror_lower_kernel<<<cdiv((i64)Nc * Nc, 256), 256, 0, stream>>>(C + (size_t)sym_row0 * ldc, Nc, ldc, T);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1491,6 +1500,47 @@ static int launch_B(evoamd_ctx *c) {
   return 0;
 }
 
+// Everything the next E-step reads that depends on Theta: G = W^T W and diag(G) (EBSC) or the state-term tables (ES3C,
+// one theta_gen stamp per build), W^T for ES3C on incomplete data, B = Y W where there is data; B_valid says whether B
+// was built.  All on the main stream.  `updated`: Theta was written by the device update (theta_update_*), not uploaded --
+// the ES3C update has formed G already (its trace term reads it), and the EBSC Gram kernel leaves diag(G) on its way
+// where the parameter-sized kernel runs (an upload always launches extract_diag_kernel).
+static int derive_from_theta(evoamd_ctx *c, bool updated) {
+  const int H = c->H, D = c->D;
+  int r = 0;
+  c->B_valid = false;
+  if (c->model == EVOAMD_MODEL_BSC && c->bsc_direct) return 0;  // the direct residual kernel reads W only
+  GemmTnOpts gram;
+  gram.deterministic = true;  // the same Theta gives the same G, tables and lpj bits every time
+  if (c->model == EVOAMD_MODEL_SSSC) {
+    if (!updated) {
+      r = launch_gemm_tn(c, c->W, H, c->W, H, c->G, H, H, H, D, gram);
+      if (r) return r;
+      DBG_SYNC(c, "derive_from_theta: G = W^T W");
+    }
+    if (c->mask_infr) {  // incomplete data: the wavefront kernel forms W_obs^T W_obs from W^T (sssc.py:276)
+      if (!c->Wt) ALLOC(c->Wt, (size_t)H * D);
+      transpose_kernel<<<cdiv((i64)H * D, 256), 256, 0, c->stream>>>(c->W, D, H, c->Wt);
+    }
+    sssc_tables_kernel<<<cdiv((i64)H * H, 256), 256, 0, c->stream>>>(c->G, c->Psi, c->mus, c->pilbar_v, c->dpar, H, c->D1,
+                                                                     c->PT, c->GP, c->DG, c->sing_gen, ++c->theta_gen);
+    DBG_SYNC(c, "derive_from_theta: tables");
+  } else {
+    const bool diag_rides = updated && gram_is_small(H, D);
+    if (diag_rides) gram.diag = c->diag;
+    r = launch_gemm_tn(c, c->W, H, c->W, H, c->G, H, H, H, D, gram);
+    if (r) return r;
+    if (!diag_rides) extract_diag_kernel<<<cdiv(H, 256), 256, 0, c->stream>>>(c->G, H, c->diag);
+  }
+  HIP_TRY(hipGetLastError());
+  if (c->have_data) {
+    r = launch_B(c);  // B = Y W
+    if (r) return r;
+    c->B_valid = true;
+  }
+  return 0;
+}
+
 extern "C" int evoamd_set_params_bsc(evoamd_ctx *c, const double *W, double pi, double sigma, double *ljc) {
   REQUIRE(c && c->configured && c->model == EVOAMD_MODEL_BSC, "context is not configured for BSC");
   REQUIRE(W, "W is NULL");
@@ -1516,17 +1566,8 @@ extern "C" int evoamd_set_params_bsc(evoamd_ctx *c, const double *W, double pi, 
   HIP_TRY(hipStreamSynchronize(c->stream));
   memcpy(wt, W, (size_t)c->D * c->H * sizeof(double));
   HIP_TRY(hipMemcpyAsync(c->W, wt, (size_t)c->D * c->H * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  c->B_valid = false;
-  if (!c->bsc_direct) {
-    int r = launch_gemm_tn(c, c->W, c->H, c->W, c->H, c->G, c->H, c->H, c->H, c->D, /*deterministic=*/true);  // G = W^T W (no split-K atomics: the same Theta gives the same G, tables and lpj bits every time)
-    if (r) return r;
-    extract_diag_kernel<<<cdiv(c->H, 256), 256, 0, c->stream>>>(c->G, c->H, c->diag);
-    if (c->have_data) {
-      r = launch_B(c);  // B = Y W
-      if (r) return r;
-      c->B_valid = true;
-    }
-  }
+  int r = derive_from_theta(c, /*updated=*/false);
+  if (r) return r;
   c->have_params = true;
   c->gen++;
   c->h_theta_fresh = false;
@@ -1589,23 +1630,8 @@ extern "C" int evoamd_set_params_sssc(evoamd_ctx *c, const double *W, const doub
     HIP_TRY(hipMemcpyAsync(c->mus, hmu, (size_t)H * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->pilbar_v, hpb, (size_t)H * sizeof(double), hipMemcpyHostToDevice, c->stream));
   }
-  int r = launch_gemm_tn(c, c->W, H, c->W, H, c->G, H, H, H, D, /*deterministic=*/true);  // G = W^T W (no split-K atomics: the same Theta gives the same G, tables and lpj bits every time)
+  int r = derive_from_theta(c, /*updated=*/false);
   if (r) return r;
-  DBG_SYNC(c, "set_params_sssc: G = W^T W");
-  sssc_tables_kernel<<<cdiv((i64)H * H, 256), 256, 0, c->stream>>>(c->G, c->Psi, c->mus, c->pilbar_v, c->dpar, H, c->D1,
-                                                                     c->PT, c->GP, c->DG, c->sing_gen, ++c->theta_gen);
-  DBG_SYNC(c, "set_params_sssc: tables");
-  if (c->mask_infr) {  // incomplete data: the per-datapoint Gram blocks read W^T
-    if (!c->Wt) ALLOC(c->Wt, (size_t)H * D);
-    transpose_kernel<<<cdiv((i64)H * D, 256), 256, 0, c->stream>>>(c->W, D, H, c->Wt);
-  }
-  HIP_TRY(hipGetLastError());
-  c->B_valid = false;
-  if (c->have_data) {
-    r = launch_B(c);  // B = Y W
-    if (r) return r;
-    c->B_valid = true;
-  }
   c->have_params = true;
   c->gen++;
   c->h_theta_fresh = false;
@@ -1616,31 +1642,31 @@ extern "C" int evoamd_set_params_sssc(evoamd_ctx *c, const double *W, const doub
 // float32 mode: C (M x Nc double, zeroed by the caller) += A^T B with float A (K x M), B (K x Nc): the stream-K grid on
 // v_mfma_f32_16x16x4_f32 with the f64 atomic epilogue; small outputs by the one-thread-per-element kernel.
 static int launch_gemm_tn_f32(evoamd_ctx *c, const float *A, int lda, const float *B, int ldb, double *C, int ldc, int M, int Nc,
-                              i64 K) {
-  SpanGuard g(c, KID_GEMM);
+                              i64 K, const GemmTnOpts &o = GemmTnOpts()) {
+  const hipStream_t stream = o.stream ? o.stream : c->stream;
+  SpanGuard g(c, KID_GEMM, stream);
   if (M >= 128 && Nc >= 128 && K >= 2048 && (M % 4) == 0 && (Nc % 4) == 0) {
     const int gx = (int)cdiv(Nc, GEMM_T), gy = (int)cdiv(M, GEMM_T);
     const i64 Kx = ((cdiv(K, 8) + GEMM_BK - 1) / GEMM_BK) * GEMM_BK;
-    const int spare = (c->stream == c->stream2) ? (c->sk_spare >= 0 ? c->sk_spare : c->fork_spare) : 0;  // see launch_gemm_tn
-    const unsigned wpx = (unsigned)std::max(1, 2 * c->n_cu / 8 - spare);
+    const unsigned wpx = (unsigned)std::max(1, 2 * c->n_cu / 8 - o.spare);
     int segmax = 0;
     double *ws = c->gemm_ws_opt ? streamk_workspace(c, wpx, (i64)gx * gy, &segmax) : nullptr;
     const i64 real = (i64)gx * gy, J = (i64)8 * wpx / real;
     if (ws && c->gemm_grouped && J >= 2 && real * J * 100 >= (i64)8 * wpx * 93 && K / J >= 256) {  // see launch_gemm_tn
       const i64 Kc = ((cdiv(K, J) + 2 * GEMM_BK - 1) / (2 * GEMM_BK)) * (2 * GEMM_BK);
-      gemm_tn128_gk<float><<<8 * wpx, 256, GEMM128_LDS_BYTES, c->stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, Kc, gx, gy, -1,
+      gemm_tn128_gk<float><<<8 * wpx, 256, GEMM128_LDS_BYTES, stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, Kc, gx, gy, -1,
                                                                            (int)real, (int)J, ws);
-      gemm_gk_reduce_kernel<<<dim3((unsigned)real, GEMM_T * GEMM_T / 256), 256, 0, c->stream>>>(ws, C, ldc, M, Nc, gx, gy, -1,
+      gemm_gk_reduce_kernel<<<dim3((unsigned)real, GEMM_T * GEMM_T / 256), 256, 0, stream>>>(ws, C, ldc, M, Nc, gx, gy, -1,
                                                                                                (int)real, (int)J);
     } else {
-      gemm_tn128_sk_f32<<<8 * wpx, 256, GEMM128_LDS_BYTES, c->stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, Kx, gx, gy, gx * gy,
+      gemm_tn128_sk_f32<<<8 * wpx, 256, GEMM128_LDS_BYTES, stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, Kx, gx, gy, gx * gy,
                                                                          ws, segmax);
       if (ws)
-        gemm_sk_reduce_kernel<<<dim3((unsigned)(gx * gy), GEMM_T * GEMM_T / 256), 256, 0, c->stream>>>(
+        gemm_sk_reduce_kernel<<<dim3((unsigned)(gx * gy), GEMM_T * GEMM_T / 256), 256, 0, stream>>>(
             ws, segmax, C, ldc, M, Nc, K, Kx, gx, gy, -1, gx * gy, (int)wpx);
     }
   } else {
-    gemm_tn_naive_f32<<<cdiv((i64)M * Nc, 256), 256, 0, c->stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K);
+    gemm_tn_naive_f32<<<cdiv((i64)M * Nc, 256), 256, 0, stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K);
   }
   HIP_TRY(hipGetLastError());
   return 0;
@@ -2924,7 +2950,6 @@ struct StatsPlan {
   AccLayout a;
   i64 N;
   int H, D;
-  hipStream_t main_stream;  // c->stream at entry (the contraction borrows c->stream for stream2 and gives it back)
   bool masked;              // incomplete data
   LevelHints lv;            // how much is known about the final K^n (resident states and accepted candidates)
   bool gemm_timed;          // a class on the main stream is being timed: no second stream
@@ -2937,7 +2962,7 @@ struct StatsPlan {
   int nchunks;     // blocks of datapoints, each followed by its part of the contraction
   i64 rows_per_chunk;
   bool second_stream;
-  int fork_spare;  // what c->fork_spare becomes for this pass
+  int gemm_spare;  // workgroups per XCD the forked contraction leaves to the Theta chain where "sk_spare" is automatic
   int waves;       // waves per workgroup of the ES3C wave-per-datapoint kernel
   bool census;     // ES3C: the levels read the census lists
   bool bsc_wave;   // EBSC: the wave-per-datapoint kernel (else the round-1 kernel + column-sum pass)
@@ -2999,7 +3024,7 @@ static int stats_per_cu(size_t lds_per_wg, int wave_lim) {
 // every kernel that writes the E_q rows of the (only) block has been enqueued: the contraction's stream branches off here
 static int rows_written(evoamd_ctx *c, const StatsPlan &p, StatsFlow &fl) {
   if (p.second_stream && p.nchunks == 1 && p.early && !p.masked) {
-    HIP_TRY(hipEventRecord(c->ev_chunk[0], p.main_stream));
+    HIP_TRY(hipEventRecord(c->ev_chunk[0], c->stream));
     fl.early_recorded = true;
   }
   return 0;
@@ -3026,7 +3051,6 @@ static int stats_plan(evoamd_ctx *c, bool fork_gemm, StatsPlan &p) {
   p.N = c->N;
   p.H = c->H;
   p.D = c->D;
-  p.main_stream = c->stream;
   p.masked = c->mask_infr != nullptr;
   p.lv.known_tag = c->cand_from_device ? 1 : 2;
   p.lv.one_bit = c->cand_from_device;
@@ -3094,7 +3118,7 @@ static int stats_plan(evoamd_ctx *c, bool fork_gemm, StatsPlan &p) {
   // 1.14 -> 1.09 with 4 and 1.065 with 8 (12 / 16: the same): 4 where the product is long against the chain, else 8.
   {
     const double chain_us = c->H >= 256 ? 15.0 * cdiv(c->H, 32) : 8.5 * cdiv(c->H, 16);
-    p.fork_spare = !(p.fork_gemm && nchunks == 1) ? 0 : ((gemm_flops / 65e6 >= 3.0 * chain_us && c->H <= 512) ? 4 : 8);
+    p.gemm_spare = !(p.fork_gemm && nchunks == 1) ? 0 : ((gemm_flops / 65e6 >= 3.0 * chain_us && c->H <= 512) ? 4 : 8);
   }
   // EBSC: wave-per-datapoint kernel with prefetch, pair bins and in-kernel column sums where it applies (digests, S <= 256,
   // one block); else the round-1 kernel + column-sum pass
@@ -3484,26 +3508,27 @@ static int stats_contract_block(evoamd_ctx *c, const StatsPlan &p, const Es3cPas
   const AccLayout &a = p.a;
   const i64 n0 = blk.n0, nc = blk.nc;
   const int H = p.H, D = p.D, ci = blk.ci;
-  int r;
+  GemmTnOpts o;
   if (p.second_stream) {
-    if (!fl.early_recorded) HIP_TRY(hipEventRecord(c->ev_chunk[ci], p.main_stream));
+    if (!fl.early_recorded) HIP_TRY(hipEventRecord(c->ev_chunk[ci], c->stream));
     HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_chunk[ci], 0));
-    c->stream = c->stream2;
+    // beside the Theta-update chain: leave slots per XCD to the chain's kernels (option "sk_spare", else the plan's)
+    o.stream = c->stream2;
+    o.spare = c->sk_spare >= 0 ? c->sk_spare : p.gemm_spare;
   }
-  const bool acc_mode = p.nchunks > 1, last = ci == p.nchunks - 1;
+  o.c_is_zero = true;  // acc was cleared at the top of stats_compute
+  o.accumulate = p.nchunks > 1;
+  o.mirror = ci == p.nchunks - 1;
   if (c->model == EVOAMD_MODEL_BSC && c->f32)
-    r = launch_gemm_tn_f32(c, c->Esf + (size_t)n0 * H, H, c->Yf + (size_t)n0 * D, D, c->acc + a.Wp, D, H, D, nc);
-  else if (c->model == EVOAMD_MODEL_BSC)  // Wp = Es^T Y  (H,D); acc was cleared at the top of stats_compute
-    r = launch_gemm_tn(c, c->Es + (size_t)n0 * H, H, Ywp + (size_t)n0 * ldwp, ldwp, c->acc + a.Wp, D, H, D, nc, false, -1,
-                       /*c_is_zero=*/true, acc_mode, last);
-  else
-    // [Y | Es | Ez]^T Ez  ->  Wp (D,H) | sum_n xpt_s (x) xpt_sz (H,H) | sum_n xpt_sz (x) xpt_sz (H,H)
-    // (the last block is Ez^T Ez: symmetric, upper tiles only when its first row is tile-aligned;
-    // launch_gemm_tn drops the hint if its tile does not divide it)
-    r = launch_gemm_tn(c, c->Y + (size_t)n0 * c->ldY, c->ldY, ep.Ez + (size_t)n0 * c->ldY, c->ldY, c->acc + a.sWp, H,
-                       D + 2 * H, H, nc, false, ((D + H) % GEMM_BM) == 0 ? D + H : -1, /*c_is_zero=*/true, acc_mode, last);
-  c->stream = p.main_stream;
-  return r;
+    return launch_gemm_tn_f32(c, c->Esf + (size_t)n0 * H, H, c->Yf + (size_t)n0 * D, D, c->acc + a.Wp, D, H, D, nc, o);
+  if (c->model == EVOAMD_MODEL_BSC)  // Wp = Es^T Y  (H,D)
+    return launch_gemm_tn(c, c->Es + (size_t)n0 * H, H, Ywp + (size_t)n0 * ldwp, ldwp, c->acc + a.Wp, D, H, D, nc, o);
+  // [Y | Es | Ez]^T Ez  ->  Wp (D,H) | sum_n xpt_s (x) xpt_sz (H,H) | sum_n xpt_sz (x) xpt_sz (H,H)
+  // (the last block is Ez^T Ez: symmetric, upper tiles only when its first row is tile-aligned;
+  // launch_gemm_tn drops the hint if its tile does not divide it)
+  o.sym_row0 = ((D + H) % GEMM_BM) == 0 ? D + H : -1;
+  return launch_gemm_tn(c, c->Y + (size_t)n0 * c->ldY, c->ldY, ep.Ez + (size_t)n0 * c->ldY, c->ldY, c->acc + a.sWp, H,
+                        D + 2 * H, H, nc, o);
 }
 
 // ---- ES3C on incomplete data: y_hat = Ez W^T with the Theta of this E-step: the reconstruction (sssc.py:613-627), the
@@ -3514,10 +3539,13 @@ static int stats_sssc_masked_products(evoamd_ctx *c, const StatsPlan &p, const E
   const int H = p.H, D = p.D;
   int r = reconstruct_rows(c, "ES3C on incomplete data needs do_reconstruction in every step (sssc.py:630-633)");
   if (r) return r;
-  r = launch_gemm_tn(c, ep.Es, c->ldY, ep.Ez, c->ldY, c->acc + a.sWp + (size_t)D * H, H, 2 * H, H, p.N, false,
-                     (H % GEMM_BM) == 0 ? H : -1, /*c_is_zero=*/true);
+  GemmTnOpts o;
+  o.c_is_zero = true;
+  o.sym_row0 = (H % GEMM_BM) == 0 ? H : -1;
+  r = launch_gemm_tn(c, ep.Es, c->ldY, ep.Ez, c->ldY, c->acc + a.sWp + (size_t)D * H, H, 2 * H, H, p.N, o);
   if (r) return r;
-  return launch_gemm_tn(c, c->Yrec, D, ep.Ez, c->ldY, c->acc + a.sWp, H, D, H, p.N, false, -1, /*c_is_zero=*/true);
+  o.sym_row0 = -1;
+  return launch_gemm_tn(c, c->Yrec, D, ep.Ez, c->ldY, c->acc + a.sWp, H, D, H, p.N, o);
 }
 
 // ---- the second stream joins (or the caller will), the fused E-step's reduction, the accumulator tail where it did not
@@ -3530,7 +3558,7 @@ static int stats_epilogue(evoamd_ctx *c, const StatsPlan &p, const StatsFlow &fl
     if (p.fork_gemm)
       c->gemm_forked = true;  // the caller joins (after the H x H inverses)
     else
-      HIP_TRY(hipStreamWaitEvent(p.main_stream, c->ev_join, 0));
+      HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join, 0));
   }
   {
     int rfr = flush_reduce(c);  // fused E-step: free-energy term and counters into the scalar block (beside the forked contraction)
@@ -3626,7 +3654,6 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
     r = row_lse(c, c->lpj, p.N, c->L, c->rowmax, c->rowsum, c->dpar + DP_FS);
     if (r) return r;
   }
-  c->fork_spare = p.fork_spare;
   StatsFlow fl;
   // the whole statistics pass (everything that reads K^n + lpj and leaves the M-step sums, the GEMM aside)
   std::unique_ptr<SpanGuard> pass(new SpanGuard(c, KID_STATS_PASS));
@@ -3803,123 +3830,181 @@ static int launch_inverse(evoamd_ctx *c, double *A, double *B, int n, bool force
   return launch_inverse_pivoted(c, A, B, n);
 }
 
-// Theta^new from the device accumulator (which evoamd_stats / stats_compute left behind), clamps,
-// precompute and the dense G / B refresh; all stream-ordered, no host arithmetic.
-// Second half of the device Theta update: what only the NEXT E-step reads (ES3C state-term tables, G for
-// EBSC, B = Y W).  evoamd_mstep_device enqueues it behind the mailbox kernel, so the host gets F and
-// Theta^new one GEMM earlier and is ahead of the stream again by the time these finish.
-static int refresh_after_update(evoamd_ctx *c) {
-  const int H = c->H, D = c->D;
-  int r = 0;
-  SpanGuard g(c, KID_MSTEP);
-  if (c->model == EVOAMD_MODEL_SSSC) {
-    if (c->mask_infr) {  // incomplete data: the wavefront kernel forms W_obs^T W_obs from W^T (sssc.py:276)
-      if (!c->Wt) ALLOC(c->Wt, (size_t)H * D);
-      transpose_kernel<<<cdiv((i64)H * D, 256), 256, 0, c->stream>>>(c->W, D, H, c->Wt);
-    }
-    sssc_tables_kernel<<<cdiv((i64)H * H, 256), 256, 0, c->stream>>>(c->G, c->Psi, c->mus, c->pilbar_v, c->dpar, H, c->D1,
-                                                                     c->PT, c->GP, c->DG, c->sing_gen, ++c->theta_gen);
-    HIP_TRY(hipGetLastError());
-    r = launch_B(c);
-    if (r) return r;
-    c->B_valid = true;
-  } else if (!c->bsc_direct) {
-    c->gram_diag_out = c->diag;  // the parameter-sized Gram kernel leaves diag(G) on its way
-    c->gram_diag_written = false;
-    r = launch_gemm_tn(c, c->W, H, c->W, H, c->G, H, H, H, D, true);
-    c->gram_diag_out = nullptr;
-    if (r) return r;
-    if (!c->gram_diag_written) extract_diag_kernel<<<cdiv(H, 256), 256, 0, c->stream>>>(c->G, H, c->diag);
-    r = launch_B(c);
-    if (r) return r;
-    c->B_valid = true;
+// ---- evoamd_mstep_device: what one call decides before it enqueues anything (mstep_plan); the stages only read it.
+// learn_mask as include/evo_amd.h documents it: the five learn bits (L_W ... L_PSI, kernels_mstep.hpp) and two requests
+enum : int {
+  MSTEP_LEARN_BITS = L_W | L_PIES | L_MUS | L_SIGMA2 | L_PSI,
+  MSTEP_WANT_REC = 32,    // also form the data estimate under the OLD Theta (evoamd_reconstruct)
+  MSTEP_THETA_HOME = 64,  // Theta^new stays on the device: the caller fetches it on demand (evoamd_get_params_*, lazy Theta)
+};
+
+// lazy Theta: the host has no copy of the parameters the E-step ran with, and the update overwrites them in place; a copy
+// is kept until the update is known to be well posed (evoamd_restore_theta_backup)
+enum BackupRoute {
+  BACKUP_NONE,
+  BACKUP_IN_UPDATE,    // the first kernel of the ES3C update writes the copy on its way (backup_rides_in_update)
+  BACKUP_SIDE_KERNEL,  // theta_backup_kernel on the side stream, beside the statistics pass; the update waits for ev_bak
+};
+
+// how the mailbox (sequence number, error words, accumulator tail, scalar block, Theta^new or not) reaches the host
+enum PublishRoute {
+  PUBLISH_FOLDED,       // the last kernel of the update writes the header: no mailbox kernel
+  PUBLISH_MAIN,         // mailbox kernel on the main stream
+  PUBLISH_SIDE,         // mailbox kernel on the side stream, beside derive_from_theta and the prefetched pass
+  PUBLISH_COPY_ENGINE,  // Theta^new through the copy engine, a header-only mailbox kernel on the main stream
+};
+
+struct MstepPlan {
+  int learn;         // the learn bits; 0 = statistics only
+  bool want_rec;
+  bool theta_home;
+  bool force_pivot;  // the SPD retry: the H x H systems by the partially pivoted elimination
+  BackupRoute backup;
+  PublishRoute publish;
+  bool theta_in_mailbox;  // the mailbox kernel carries W (| Psi | mus | pies) behind the header
+};
+
+// ES3C with D <= 8 H: the first kernel of the update (sssc_mstep_prepare_kernel, an H x H grid) writes the backup on its
+// way, no launch and no event of its own.
+static bool backup_rides_in_update(const evoamd_ctx *c) {
+  return c->model == EVOAMD_MODEL_SSSC && c->D <= 8 * c->H;
+}
+
+// Routes of one call (learn = learn bits set, home = MSTEP_THETA_HOME, flops = contraction_flops, side = option
+// "mailbox_side_stream", dma = option "theta_copy_engine"):
+//
+//   learn  home | backup                                   | Theta^new to the host     | header written by
+//   -----------------------------------------------------------------------------------------------------------------
+//   no     any  | none                                     | --                        | mailbox kernel (*)
+//   yes    yes  | in the update (ES3C, D <= 8 H), else own | -- (fetched on demand)    | side && flops >= 8e9: mailbox
+//               | kernel on the side stream                |                           | kernel, side stream; else the
+//               |                                          |                           | update's last kernel (folded)
+//   yes    no   | none                                     | dma: copy engine          | mailbox kernel, main stream
+//               |                                          | else: the mailbox kernel  | mailbox kernel (**)
+//
+//   (*)  side stream when side && flops >= 8e9, else main stream      (**) the same with 8e10
+//
+// The SPD retry (status 3 from the first attempt) is the same plan with force_pivot, no backup (the first attempt took
+// it, and Theta is half overwritten by now) and never folded.
+//
+// The mailbox kernel writes to pinned host memory and ends in a system-scope fence: 26 us of which nothing behind it in
+// the stream depends.  On the side stream it runs beside derive_from_theta / the prefetched pass; what it reads (tail,
+// scalar block, error words, Theta) is next written by the NEXT iteration's kernels, which the host enqueues only after
+// it has seen this mailbox.  Measured, ms per iteration lazy / eager Theta: c4 3.94 -> 3.88 / 4.43 -> 4.05, N / 8 shard
+// 1.13 -> 1.08 / 1.37 -> 1.60, c2 0.386 -> 0.404: the event pair costs ~10 us, and a 3 MB Theta copy beside the refresh
+// only delays the host -- so only the mailbox of a long iteration goes there, with Theta on board only at the north-star
+// size.  Folding needs the mailbox on the main stream and nothing but the header in it.
+// Enqueues nothing and changes nothing in the context.
+static MstepPlan mstep_plan(const evoamd_ctx *c, int learn_mask, bool spd_retry) {
+  MstepPlan p = {};
+  p.learn = learn_mask & MSTEP_LEARN_BITS;
+  p.want_rec = (learn_mask & MSTEP_WANT_REC) != 0;
+  p.theta_home = (learn_mask & MSTEP_THETA_HOME) != 0;
+  p.force_pivot = spd_retry;
+  p.backup = BACKUP_NONE;
+  if (p.learn && p.theta_home && !spd_retry) p.backup = backup_rides_in_update(c) ? BACKUP_IN_UPDATE : BACKUP_SIDE_KERNEL;
+  const bool theta_out = p.learn && !p.theta_home;  // Theta^new goes to the host with this call
+  if (theta_out && c->theta_copy_engine) {
+    p.publish = PUBLISH_COPY_ENGINE;
+    return p;
   }
+  p.theta_in_mailbox = theta_out;
+  if (c->mbox_side && contraction_flops(c) >= (theta_out ? 8e10 : 8e9))
+    p.publish = PUBLISH_SIDE;
+  else
+    p.publish = (p.learn && p.theta_home && !spd_retry) ? PUBLISH_FOLDED : PUBLISH_MAIN;
+  return p;
+}
+
+// Theta^new from the device accumulator (which stats_compute left behind) and the clamps; all stream-ordered, no host
+// arithmetic.  What only the NEXT E-step reads is derive_from_theta's, which evoamd_mstep_device enqueues behind the
+// mailbox: the host gets F and Theta^new one GEMM earlier and is ahead of the stream again by the time that finishes.
+// Both end in the one scalar kernel that writes the mailbox header on its way when fold_seq != 0 (PUBLISH_FOLDED).
+static int theta_update_sssc(evoamd_ctx *c, const MstepPlan &p, unsigned long long fold_seq) {
+  const AccLayout a = acc_layout(c);
+  const int H = c->H, D = c->D, learn = p.learn;
+  const i64 HH = (i64)H * H;
+  const double *Nptr = c->acc + a.tail + 3;
+  double *bak = p.backup == BACKUP_IN_UPDATE ? c->theta_bak : nullptr;
+  int r = 0;
+  if (c->sssc_prec32)  // precision = float32: the moment sums as float32 values (evoamd_stats does the same on the host)
+    round_f32_kernel<<<cdiv(a.sWp, 256), 256, 0, c->stream>>>(c->acc, a.sWp);
+  // mus / pies first (Psi needs the NEW mus, sssc.py:733), then both H x H inverses in one launch:
+  // tmpA <- xpt_szsz (for W, sssc.py:693), tmpB <- xpt_ss + eps I (for Psi, sssc.py:738)
+  sssc_mstep_prepare_kernel<<<cdiv(HH, 256), 256, 0, c->stream>>>(c->acc + a.xs, c->acc + a.xsz, c->acc + a.xss,
+                                                                  c->acc + a.xszsz, Nptr, H, learn,
+                                                                  c->pies, c->mus, c->tmpA, c->tmpC, c->tmpB, bak, c->W,
+                                                                  c->Psi, c->dpar, D, c->bg_unit);
+  if ((learn & L_W) && (learn & L_PSI))
+    r = launch_inverse(c, c->tmpA, c->tmpB, H, p.force_pivot);
+  else if (learn & L_W)
+    r = launch_inverse(c, c->tmpA, nullptr, H, p.force_pivot);
+  else if (learn & L_PSI)
+    r = launch_inverse(c, c->tmpB, nullptr, H, p.force_pivot);
+  if (r) return r;
+  r = join_fork(c);  // sWp / s_sz / sz_sz come from the contraction
+  if (r) return r;
+  if (c->sssc_prec32) round_f32_kernel<<<cdiv(a.y2 - a.s_sz, 256), 256, 0, c->stream>>>(c->acc + a.s_sz, a.y2 - a.s_sz);
+  if (learn & L_W)
+    launch_gemm_nn_raw(c, c->acc + a.sWp, H, c->tmpA, H, c->W, H, D, H, H);
+  const bool masked = c->mask_infr != nullptr;  // sssc.py:747-755: the trace term arrives in tail[7]
+  // (Psi's element-wise finish rides along with the trace partials below when both run)
+  const bool psi_with_trace = (learn & L_PSI) && (learn & L_SIGMA2) && !masked;
+  if ((learn & L_PSI) && !psi_with_trace)
+    sssc_psi_finish_kernel<<<cdiv(HH, 256), 256, 0, c->stream>>>(c->tmpC, c->tmpB, c->acc + a.s_sz, c->mus, H, c->Psi);
+  else if (!(learn & L_PSI))
+    psi_floor_kernel<<<cdiv(H, 256), 256, 0, c->stream>>>(c->Psi, H);
+  HIP_TRY(hipGetLastError());
+  GemmTnOpts gram;
+  gram.deterministic = true;
+  r = launch_gemm_tn(c, c->W, H, c->W, H, c->G, H, H, H, D, gram);  // G = W^T W (new W)
+  if (r) return r;
+  const int n_part = (int)std::min<i64>(1024, cdiv(HH, 1024));
+  r = ensure_colpart(c, (size_t)n_part);
+  if (r) return r;
+  if (psi_with_trace)
+    sssc_trace_partial_kernel<<<n_part, 256, 0, c->stream>>>(c->acc + a.sz_sz, c->G, H, cdiv(HH, n_part), c->colpart, c->tmpC,
+                                                             c->tmpB, c->acc + a.s_sz, c->mus, c->Psi);
+  else if ((learn & L_SIGMA2) && !masked)
+    sssc_trace_partial_kernel<<<n_part, 256, 0, c->stream>>>(c->acc + a.sz_sz, c->G, H, cdiv(HH, n_part), c->colpart);
+  sssc_sigma_precompute_kernel<<<1, MS_T, 0, c->stream>>>(c->acc + a.y2, D, c->colpart, masked ? 0 : n_part, H, Nptr, learn,
+                                                          c->pies, c->pilbar_v, c->dpar, masked ? c->rel_frac : -1.0,
+                                                          c->acc + a.tail + 7, c->sssc_prec32,
+                                                          fold_seq ? c->h_theta_dev : nullptr, c->acc + a.tail, c->err, fold_seq);
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
-static int update_params_device(evoamd_ctx *c, int learn, bool force_pivot = false, bool defer_refresh = false,
-                                double *bak = nullptr) {
+static int theta_update_bsc(evoamd_ctx *c, const MstepPlan &p, unsigned long long fold_seq) {
   const AccLayout a = acc_layout(c);
-  const int H = c->H, D = c->D;
-  const i64 HH = (i64)H * H;
-  const double *Nptr = c->acc + a.tail + 3;
+  const int H = c->H, D = c->D, learn = p.learn;
   int r = 0;
+  if (learn & L_W) {  // W^T = solve(Wq, Wp)  (bsc.py:237; lstsq == solve for a non-singular Wq)
+    if (!c->wq_copy_valid || p.force_pivot)  // (else the finish kernel of the statistics pass left the copy in tmpA)
+      HIP_TRY(hipMemcpyAsync(c->tmpA, c->acc + a.Wq, (size_t)H * H * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    c->wq_copy_valid = false;
+    r = launch_inverse(c, c->tmpA, nullptr, H, p.force_pivot);
+    if (r) return r;
+    r = join_fork(c);  // Wp comes from the contraction
+    if (r) return r;
+    if (!launch_gemm_nn_raw(c, c->tmpA, H, c->acc + a.Wp, D, c->Wt, D, H, D, H, c->W, H))  // W^T, and W on the way
+      transpose_kernel<<<cdiv((i64)H * D, 256), 256, 0, c->stream>>>(c->Wt, H, D, c->W);
+  }
+  bsc_scalars_kernel<<<1, MS_T, 0, c->stream>>>(c->acc + a.pies, c->acc + a.sigma, H, D, c->acc + a.tail + 3, learn, c->dpar,
+                                                c->mask_infr ? c->rel_frac : -1.0, fold_seq ? c->h_theta_dev : nullptr,
+                                                c->acc + a.tail, c->err, fold_seq, c->bg_unit);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// the update of the context's model; Theta on the device is Theta^new behind it and B = Y W is stale
+static int theta_update(evoamd_ctx *c, const MstepPlan &p, unsigned long long fold_seq) {
   c->gen++;
   SpanGuard g(c, KID_MSTEP);
-  if (c->model == EVOAMD_MODEL_SSSC) {
-    if (c->sssc_prec32)  // precision = float32: the moment sums as float32 values (evoamd_stats does the same on the host)
-      round_f32_kernel<<<cdiv(a.sWp, 256), 256, 0, c->stream>>>(c->acc, a.sWp);
-    // mus / pies first (Psi needs the NEW mus, sssc.py:733), then both H x H inverses in one launch:
-    // tmpA <- xpt_szsz (for W, sssc.py:693), tmpB <- xpt_ss + eps I (for Psi, sssc.py:738)
-    sssc_mstep_prepare_kernel<<<cdiv(HH, 256), 256, 0, c->stream>>>(c->acc + a.xs, c->acc + a.xsz, c->acc + a.xss,
-                                                                    c->acc + a.xszsz, Nptr, H, learn,
-                                                                    c->pies, c->mus, c->tmpA, c->tmpC, c->tmpB, bak, c->W,
-                                                                    c->Psi, c->dpar, D, c->bg_unit);
-    if ((learn & L_W) && (learn & L_PSI))
-      r = launch_inverse(c, c->tmpA, c->tmpB, H, force_pivot);
-    else if (learn & L_W)
-      r = launch_inverse(c, c->tmpA, nullptr, H, force_pivot);
-    else if (learn & L_PSI)
-      r = launch_inverse(c, c->tmpB, nullptr, H, force_pivot);
-    if (r) return r;
-    r = join_fork(c);  // sWp / s_sz / sz_sz come from the contraction
-    if (r) return r;
-    if (c->sssc_prec32) round_f32_kernel<<<cdiv(a.y2 - a.s_sz, 256), 256, 0, c->stream>>>(c->acc + a.s_sz, a.y2 - a.s_sz);
-    if (learn & L_W)
-      launch_gemm_nn_raw(c, c->acc + a.sWp, H, c->tmpA, H, c->W, H, D, H, H);
-    const bool masked = c->mask_infr != nullptr;  // sssc.py:747-755: the trace term arrives in tail[7]
-    // (Psi's element-wise finish rides along with the trace partials below when both run)
-    const bool psi_with_trace = (learn & L_PSI) && (learn & L_SIGMA2) && !masked;
-    if ((learn & L_PSI) && !psi_with_trace)
-      sssc_psi_finish_kernel<<<cdiv(HH, 256), 256, 0, c->stream>>>(c->tmpC, c->tmpB, c->acc + a.s_sz, c->mus, H, c->Psi);
-    else if (!(learn & L_PSI))
-      psi_floor_kernel<<<cdiv(H, 256), 256, 0, c->stream>>>(c->Psi, H);
-    HIP_TRY(hipGetLastError());
-    r = launch_gemm_tn(c, c->W, H, c->W, H, c->G, H, H, H, D, /*deterministic=*/true);  // G = W^T W (new W)
-    if (r) return r;
-    const int n_part = (int)std::min<i64>(1024, cdiv(HH, 1024));
-    r = ensure_colpart(c, (size_t)n_part);
-    if (r) return r;
-    if (psi_with_trace)
-      sssc_trace_partial_kernel<<<n_part, 256, 0, c->stream>>>(c->acc + a.sz_sz, c->G, H, cdiv(HH, n_part), c->colpart, c->tmpC,
-                                                               c->tmpB, c->acc + a.s_sz, c->mus, c->Psi);
-    else if ((learn & L_SIGMA2) && !masked)
-      sssc_trace_partial_kernel<<<n_part, 256, 0, c->stream>>>(c->acc + a.sz_sz, c->G, H, cdiv(HH, n_part), c->colpart);
-    unsigned long long fold_seq = 0;
-    if (c->mbox_fold_req) {
-      fold_seq = ++c->mbox_seq;
-      c->mbox_folded_seq = fold_seq;
-    }
-    sssc_sigma_precompute_kernel<<<1, MS_T, 0, c->stream>>>(c->acc + a.y2, D, c->colpart, masked ? 0 : n_part, H, Nptr, learn,
-                                                            c->pies, c->pilbar_v, c->dpar, masked ? c->rel_frac : -1.0,
-                                                            c->acc + a.tail + 7, c->sssc_prec32,
-                                                            fold_seq ? c->h_theta_dev : nullptr, c->acc + a.tail, c->err, fold_seq);
-    HIP_TRY(hipGetLastError());
-    c->B_valid = false;
-  } else {
-    if (learn & L_W) {  // W^T = solve(Wq, Wp)  (bsc.py:237; lstsq == solve for a non-singular Wq)
-      if (!c->wq_copy_valid || force_pivot)  // (else the finish kernel of the statistics pass left the copy in tmpA)
-        HIP_TRY(hipMemcpyAsync(c->tmpA, c->acc + a.Wq, HH * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      c->wq_copy_valid = false;
-      r = launch_inverse(c, c->tmpA, nullptr, H, force_pivot);
-      if (r) return r;
-      r = join_fork(c);  // Wp comes from the contraction
-      if (r) return r;
-      if (!launch_gemm_nn_raw(c, c->tmpA, H, c->acc + a.Wp, D, c->Wt, D, H, D, H, c->W, H))  // W^T, and W on the way
-        transpose_kernel<<<cdiv((i64)H * D, 256), 256, 0, c->stream>>>(c->Wt, H, D, c->W);
-    }
-    unsigned long long fold_seq = 0;
-    if (c->mbox_fold_req) {
-      fold_seq = ++c->mbox_seq;
-      c->mbox_folded_seq = fold_seq;
-    }
-    bsc_scalars_kernel<<<1, MS_T, 0, c->stream>>>(c->acc + a.pies, c->acc + a.sigma, H, D, Nptr, learn, c->dpar,
-                                                  c->mask_infr ? c->rel_frac : -1.0, fold_seq ? c->h_theta_dev : nullptr,
-                                                  c->acc + a.tail, c->err, fold_seq, c->bg_unit);
-    HIP_TRY(hipGetLastError());
-    c->B_valid = false;
-  }
-  return defer_refresh ? 0 : refresh_after_update(c);
+  int r = c->model == EVOAMD_MODEL_SSSC ? theta_update_sssc(c, p, fold_seq) : theta_update_bsc(c, p, fold_seq);
+  if (r) return r;
+  c->B_valid = false;
+  return 0;
 }
 
 // y_hat = E W^T with E = Es (EBSC) / Ez (ES3C) rows of the last statistics pass (see evoamd_reconstruct)
@@ -3960,31 +4045,40 @@ extern "C" int evoamd_reconstruct(evoamd_ctx *c, double *y_hat) {
   return 0;
 }
 
-// Everything an EM iteration returns to the host goes through the mailbox kernel; the host polls
-// the sequence number (falls back to a blocking synchronise after 20 ms of spinning).
-static int mailbox_roundtrip(evoamd_ctx *c, bool with_theta, bool prefetch = false, bool refresh = false) {
+// Everything an EM iteration returns to the host goes through the mailbox; the host polls the sequence number.
+struct MailboxTicket {
+  unsigned long long seq;  // what the header will carry
+  hipStream_t stream;      // the stream its writer is on: what the poll synchronises with when spinning takes too long
+};
+
+// Enqueues whatever p.publish asks for.  fold_seq: what the update's last kernel was given (PUBLISH_FOLDED).
+static int mailbox_publish(evoamd_ctx *c, const MstepPlan &p, unsigned long long fold_seq, MailboxTicket &t) {
+  t.stream = c->stream;
+  if (p.publish == PUBLISH_FOLDED) {
+    t.seq = fold_seq;
+    return 0;
+  }
   const AccLayout a = acc_layout(c);
   const size_t DH = (size_t)c->D * c->H, HH = (size_t)c->H * c->H, H = c->H;
-  MailboxSegs segs = {};
-  const bool dma = with_theta && c->theta_copy_engine;
-  if (dma) {
+  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
+  if (p.publish == PUBLISH_COPY_ENGINE) {
     // Theta^new is final on the main stream here: the copy engine takes it from there, beside whatever follows
     double *dst = c->h_theta + MAILBOX_HDR;
     HIP_TRY(hipEventRecord(c->ev_theta, c->stream));
     HIP_TRY(hipStreamWaitEvent(c->stream_copy, c->ev_theta, 0));
     HIP_TRY(hipMemcpyAsync(dst, c->W, DH * sizeof(double), hipMemcpyDeviceToHost, c->stream_copy));
-    if (c->model == EVOAMD_MODEL_SSSC) {
+    if (sssc) {
       HIP_TRY(hipMemcpyAsync(dst + DH, c->Psi, HH * sizeof(double), hipMemcpyDeviceToHost, c->stream_copy));
       HIP_TRY(hipMemcpyAsync(dst + DH + HH, c->mus, H * sizeof(double), hipMemcpyDeviceToHost, c->stream_copy));
       HIP_TRY(hipMemcpyAsync(dst + DH + HH + H, c->pies, H * sizeof(double), hipMemcpyDeviceToHost, c->stream_copy));
     }
     HIP_TRY(hipEventRecord(c->ev_theta_done, c->stream_copy));
-    with_theta = false;  // the mailbox kernel writes the header only
   }
-  if (with_theta) {
+  MailboxSegs segs = {};
+  if (p.theta_in_mailbox) {
     segs.src[0] = c->W;
     segs.n[0] = (long long)DH;
-    if (c->model == EVOAMD_MODEL_SSSC) {
+    if (sssc) {
       segs.src[1] = c->Psi;
       segs.n[1] = (long long)HH;
       segs.src[2] = c->mus;
@@ -3993,54 +4087,44 @@ static int mailbox_roundtrip(evoamd_ctx *c, bool with_theta, bool prefetch = fal
       segs.n[3] = (long long)H;
     }
   }
-  const bool folded = c->mbox_folded_seq != 0 && !with_theta && !dma;  // the update's last kernel wrote the header
-  const unsigned long long seq = folded ? c->mbox_folded_seq : ++c->mbox_seq;
-  c->mbox_folded_seq = 0;
-  const long long total = MAILBOX_HDR + (with_theta ? (long long)(DH + HH + 2 * H) : 0);
+  t.seq = ++c->mbox_seq;
+  const long long total = MAILBOX_HDR + (p.theta_in_mailbox ? (long long)(DH + HH + 2 * H) : 0);
   const int grid = (int)std::min<long long>(64, cdiv(total, 256 * 8));
-  // The mailbox kernel writes to pinned host memory and ends in a system-scope fence: 26 us of which nothing behind it
-  // in the stream depends.  On the side stream it runs beside the refresh / the prefetched pass; what it reads (tail,
-  // scalar block, error words, Theta) is next written by the NEXT iteration's kernels, which the host enqueues only after
-  // it has seen this mailbox.
-  hipStream_t mstream = c->stream;
-  // (measured, ms per iteration lazy / eager Theta: c4 3.94 -> 3.88 / 4.43 -> 4.05, N / 8 shard 1.13 -> 1.08 / 1.37 -> 1.60,
-  // c2 0.386 -> 0.404: the event pair costs ~10 us, and a 3 MB Theta copy beside the refresh only delays the host -- so
-  // only the mailbox of a long iteration goes there, with Theta on board only at the north-star size)
-  const double it_flops = contraction_flops(c);
-  if (!folded && c->mbox_side && !dma && it_flops >= (with_theta ? 8e10 : 8e9)) {
+  if (p.publish == PUBLISH_SIDE) {
     HIP_TRY(hipEventRecord(c->ev_mbox, c->stream));
     HIP_TRY(hipStreamWaitEvent(c->stream_copy, c->ev_mbox, 0));
-    mstream = c->stream_copy;
+    t.stream = c->stream_copy;
   }
-  if (!folded)
-    mailbox_kernel<<<grid < 1 ? 1 : grid, 256, 0, mstream>>>(c->h_theta_dev, c->acc + a.tail, c->err, segs,
-                                                             c->mbox_counter, seq);
+  mailbox_kernel<<<grid < 1 ? 1 : grid, 256, 0, t.stream>>>(c->h_theta_dev, c->acc + a.tail, c->err, segs, c->mbox_counter, t.seq);
   HIP_TRY(hipGetLastError());
-  if (refresh) {
-    int rr = refresh_after_update(c);
-    if (rr) return rr;
-  }
-  if (prefetch && c->prefetch_lpj && !c->mask_infr && !c->last_estep_fused) {  // (a fused E-step evaluates K^n itself)
-    // behind the mailbox kernel in stream order: the host is released as soon as that kernel is done
-    // the host has not read this iteration's overflow counts yet (they arrive with the mailbox being polled
-    // below), so res_need / res_cnt still describe the K^n of the PREVIOUS iteration: conservative levels
-    c->prefetch_gen = ~0ull;
-    const int rp = lpj_resident_launch(c, c->lpj_alt, batch_hints(c, 0, /*prefetched=*/true));
-    if (rp == 0) c->prefetch_gen = c->gen;
-  }
+  return 0;
+}
+
+// The next iteration's pass over K^n, behind the mailbox in stream order: the host is released before it runs.
+static void prefetch_next_pass(evoamd_ctx *c) {
+  if (!c->prefetch_lpj || c->mask_infr || c->last_estep_fused) return;  // (a fused E-step evaluates K^n itself)
+  // the host has not read this iteration's overflow counts yet (they arrive with the mailbox being polled next), so
+  // res_need / res_cnt still describe the K^n of the PREVIOUS iteration: conservative levels
+  c->prefetch_gen = ~0ull;
+  const int rp = lpj_resident_launch(c, c->lpj_alt, batch_hints(c, 0, /*prefetched=*/true));
+  if (rp == 0) c->prefetch_gen = c->gen;
+}
+
+// Spins on the sequence number (falls back to a blocking synchronise after 20 ms of spinning).
+static int mailbox_poll(evoamd_ctx *c, const MstepPlan &p, const MailboxTicket &t) {
   volatile unsigned long long *flag = (volatile unsigned long long *)c->h_theta;
   const auto t0 = std::chrono::steady_clock::now();
   unsigned spins = 0;
-  while (*flag != seq) {
+  while (*flag != t.seq) {
     __builtin_ia32_pause();
     if ((++spins & 0xFFFu) == 0 &&
         std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 0.02) {
-      HIP_TRY(hipStreamSynchronize(mstream));
-      if (*flag != seq) return fail(EVOAMD_E_HIP, "mailbox kernel finished without publishing its sequence number");
+      HIP_TRY(hipStreamSynchronize(t.stream));
+      if (*flag != t.seq) return fail(EVOAMD_E_HIP, "mailbox kernel finished without publishing its sequence number");
     }
   }
   __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  if (dma) HIP_TRY(hipEventSynchronize(c->ev_theta_done));
+  if (p.publish == PUBLISH_COPY_ENGINE) HIP_TRY(hipEventSynchronize(c->ev_theta_done));
   return 0;
 }
 
@@ -4075,15 +4159,11 @@ static CopySegs theta_segs(evoamd_ctx *c) {
   return s;
 }
 
-// lazy Theta: the host has no copy of the parameters the E-step ran with, and the update overwrites them in place.
-// One launch (3 MB at the north-star shape, ~3 us) keeps them until the update is known to be well posed.
-// ES3C with D <= 8 H: the first kernel of the update (sssc_mstep_prepare_kernel, an H x H grid) writes the copy on its way,
-// no launch and no event of its own.
-static bool backup_rides_in_update(const evoamd_ctx *c) {
-  return c->model == EVOAMD_MODEL_SSSC && c->D <= 8 * c->H;
-}
-
-static int backup_theta(evoamd_ctx *c, bool reserve_only) {
+// Room for the copy of Theta the plan asks for and, on the side-kernel route, the copy itself: on the side stream,
+// beside the statistics pass (nothing writes Theta between the E-step and the update, which waits for ev_bak) -- one launch
+// (3 MB at the north-star shape, ~3 us), 9 us that were in front of the update.  Before the statistics pass is enqueued.
+static int mstep_backup(evoamd_ctx *c, const MstepPlan &p) {
+  if (p.backup == BACKUP_NONE) return 0;
   const CopySegs s = theta_segs(c);
   size_t n = 0;
   for (int k = 0; k < 5; k++) n += (size_t)s.n[k];
@@ -4091,9 +4171,7 @@ static int backup_theta(evoamd_ctx *c, bool reserve_only) {
     ALLOC(c->theta_bak, n);
     c->theta_bak_n = n;
   }
-  if (reserve_only) return 0;
-  // on the side stream, beside the statistics pass (nothing writes Theta between the E-step and the update, which waits
-  // for ev_bak): 9 us at the north-star shape that were in front of the update
+  if (p.backup == BACKUP_IN_UPDATE) return 0;  // (valid once the update is enqueued: mstep_attempt)
   theta_backup_kernel<<<(unsigned)std::min<size_t>(256, cdiv((i64)n, 256 * 8)), 256, 0, c->stream_copy>>>(c->theta_bak, s, 0);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->ev_bak, c->stream_copy));
@@ -4120,87 +4198,87 @@ extern "C" int evoamd_restore_theta_backup(evoamd_ctx *c) {
   return 0;
 }
 
-extern "C" int evoamd_mstep_device(evoamd_ctx *c, int learn_mask, double *tail_out, double *dpar_out) {
-  REQUIRE(tail_out && dpar_out, "NULL output");
-  REQUIRE(!(c && c->mask_infr && c->rel_frac < 0.0), "incomplete data: evoamd_set_reliable_fraction first (bsc.py:113-118)");
-  const bool theta_home = (learn_mask & 64) != 0;  // the caller fetches Theta^new on demand (evoamd_get_params_*)
-  c->theta_bak_valid = false;
-  c->mbox_folded_seq = 0;  // (a header written by an update whose mailbox was never polled is not this call's)
-  c->mbox_fold_req = false;
-  bool bak_pending = false;
-  double *bak_inline = nullptr;
-  if ((learn_mask & 31) && theta_home) {  // before the statistics pass is enqueued: the copy runs beside it
-    const bool rides = backup_rides_in_update(c);
-    int rb = backup_theta(c, rides);
-    if (rb) return rb;
-    if (rides)
-      bak_inline = c->theta_bak;
-    else
-      bak_pending = true;
-  }
-  int r = stats_compute(c, /*fork_gemm=*/true);
-  if (r) return r;
-  c->h_theta_fresh = false;
-  const bool want_rec = (learn_mask & 32) != 0;
-  learn_mask &= 31;
-  if (want_rec && !c->yhat_valid) {  // under the Theta the E-step used, i.e. before the update
-    r = compute_reconstruction(c);   // (incomplete data: the statistics pass formed it already)
+// One attempt at Theta^new and its way to the host.  Enqueued in this order: update, publish, what the next E-step
+// derives from Theta^new, the prefetched pass; then the host polls.
+static int mstep_attempt(evoamd_ctx *c, const MstepPlan &p) {
+  unsigned long long fold_seq = 0;
+  int r;
+  if (p.learn) {
+    if (p.publish == PUBLISH_FOLDED) fold_seq = ++c->mbox_seq;
+    r = theta_update(c, p, fold_seq);
     if (r) return r;
-  }
-  if (bak_pending) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_bak, 0));
-  if (learn_mask) {
-    {
-      // lazy Theta with the mailbox on the main stream: the header rides in the update's last kernel
-      const double it_flops = contraction_flops(c);
-      c->mbox_fold_req = theta_home && !(c->mbox_side && it_flops >= 8e9);
-    }
-    r = update_params_device(c, learn_mask, false, /*defer_refresh=*/true, bak_inline);
-    c->mbox_fold_req = false;
-    if (r) return r;
-    if (bak_inline) c->theta_bak_valid = true;
+    if (p.backup == BACKUP_IN_UPDATE) c->theta_bak_valid = true;
     c->stats_rows_valid = false;  // the rows belong to the previous Theta now
   }
   r = join_fork(c);
   if (r) return r;
   // accumulator tail (8) and the scalar block (16) are adjacent in device memory and in the mailbox;
-  // the reference's step() hands Theta^new back, so it rides along
-  r = mailbox_roundtrip(c, learn_mask != 0 && !theta_home, /*prefetch=*/true, /*refresh=*/learn_mask != 0);
+  // the reference's step() hands Theta^new back, so it rides along unless it stays home
+  MailboxTicket t;
+  r = mailbox_publish(c, p, fold_seq, t);
   if (r) return r;
+  if (p.learn) {
+    SpanGuard g(c, KID_MSTEP);
+    r = derive_from_theta(c, /*updated=*/true);
+    if (r) return r;
+  }
+  prefetch_next_pass(c);
+  return mailbox_poll(c, p, t);
+}
+
+// The mailbox has arrived: tail and scalar block to the caller, error words, overflow levels; after status 1 / 2 the
+// clean-up that lets the caller finish the step on the host.
+static int mstep_deliver(evoamd_ctx *c, const MstepPlan &p, double *tail_out, double *dpar_out) {
   const double *h = c->h_theta + 8;
-  if (learn_mask && h[8 + DP_STATUS] == 3.0) {
+  memcpy(tail_out, h, 8 * sizeof(double));
+  memcpy(dpar_out, h + 8, DP_COUNT * sizeof(double));
+  memcpy(c->h_dpar, h + 8, DP_COUNT * sizeof(double));
+  int r = mailbox_errors(c);
+  if (r) return r;
+  note_levels(c, c->h_dpar);
+  c->h_theta_fresh = p.learn != 0 && !p.theta_home && c->h_dpar[DP_STATUS] == 0.0;
+  if (c->h_dpar[DP_STATUS] == 0.0) return 0;
+  dpar_out[DP_STATUS] = c->h_dpar[DP_STATUS];  // 1 singular, 2 non-finite: the caller may finish the step on the host
+  HIP_TRY(hipMemsetAsync(c->dpar + DP_STATUS, 0, sizeof(double), c->stream));
+  // derive_from_theta and the prefetched pass behind the mailbox ran with the failed update's Theta: drop the pass and
+  // the clamp flags it may have raised (the caller re-installs a Theta before anything else is evaluated)
+  c->prefetch_gen = ~0ull;
+  c->have_params = false;
+  HIP_TRY(hipMemsetAsync(c->flags, 0, (size_t)3 * c->N * sizeof(unsigned), c->stream));
+  HIP_TRY(hipMemsetAsync(c->err, 0, 2 * sizeof(int), c->stream));
+  return fail(EVOAMD_E_SINGULAR, "device Theta update: %s",
+              c->h_dpar[DP_STATUS] == 1.0 ? "singular H x H system (the reference falls back to pinv / lstsq here)"
+                                          : "non-finite sigma / pi");
+}
+
+extern "C" int evoamd_mstep_device(evoamd_ctx *c, int learn_mask, double *tail_out, double *dpar_out) {
+  REQUIRE(tail_out && dpar_out, "NULL output");
+  REQUIRE(!(c && c->mask_infr && c->rel_frac < 0.0), "incomplete data: evoamd_set_reliable_fraction first (bsc.py:113-118)");
+  const MstepPlan p = mstep_plan(c, learn_mask, /*spd_retry=*/false);
+  c->theta_bak_valid = false;
+  int r = mstep_backup(c, p);
+  if (r) return r;
+  r = stats_compute(c, /*fork_gemm=*/true);
+  if (r) return r;
+  c->h_theta_fresh = false;
+  if (p.want_rec && !c->yhat_valid) {  // under the Theta the E-step used, i.e. before the update
+    r = compute_reconstruction(c);     // (incomplete data: the statistics pass formed it already)
+    if (r) return r;
+  }
+  if (p.backup == BACKUP_SIDE_KERNEL) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_bak, 0));
+  r = mstep_attempt(c, p);
+  if (r) return r;
+  if (p.learn && c->h_theta[8 + 8 + DP_STATUS] == 3.0) {
     // the SPD block elimination met a non-positive pivot: repeat the Theta update with partial
     // pivoting.  The statistics are still in acc; ljc moves back so that the update kernels shift
     // it into ljc_prev again.
     c->spd_fallbacks++;
     HIP_TRY(hipMemsetAsync(c->dpar + DP_STATUS, 0, sizeof(double), c->stream));
     HIP_TRY(hipMemcpyAsync(c->dpar + DP_LJC, c->dpar + DP_LJC_PREV, sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    c->mbox_folded_seq = 0;
-    r = update_params_device(c, learn_mask, /*force_pivot=*/true, /*defer_refresh=*/true);
-    if (r) return r;
-    r = mailbox_roundtrip(c, !theta_home, /*prefetch=*/true, /*refresh=*/true);
+    r = mstep_attempt(c, mstep_plan(c, learn_mask, /*spd_retry=*/true));
     if (r) return r;
   }
-  memcpy(tail_out, h, 8 * sizeof(double));
-  memcpy(dpar_out, h + 8, DP_COUNT * sizeof(double));
-  memcpy(c->h_dpar, h + 8, DP_COUNT * sizeof(double));
-  r = mailbox_errors(c);
-  if (r) return r;
-  note_levels(c, c->h_dpar);
-  c->h_theta_fresh = learn_mask != 0 && !theta_home && c->h_dpar[DP_STATUS] == 0.0;
-  if (c->h_dpar[DP_STATUS] != 0.0) {
-    dpar_out[DP_STATUS] = c->h_dpar[DP_STATUS];  // 1 singular, 2 non-finite: the caller may finish the step on the host
-    HIP_TRY(hipMemsetAsync(c->dpar + DP_STATUS, 0, sizeof(double), c->stream));
-    // the refresh and the prefetched pass behind the mailbox ran with the failed update's Theta: drop the pass and
-    // the clamp flags it may have raised (the caller re-installs a Theta before anything else is evaluated)
-    c->prefetch_gen = ~0ull;
-    c->have_params = false;
-    HIP_TRY(hipMemsetAsync(c->flags, 0, (size_t)3 * c->N * sizeof(unsigned), c->stream));
-    HIP_TRY(hipMemsetAsync(c->err, 0, 2 * sizeof(int), c->stream));
-    return fail(EVOAMD_E_SINGULAR, "device Theta update: %s",
-                c->h_dpar[DP_STATUS] == 1.0 ? "singular H x H system (the reference falls back to pinv / lstsq here)"
-                                            : "non-finite sigma / pi");
-  }
-  return 0;
+  return mstep_deliver(c, p, tail_out, dpar_out);
 }
 
 extern "C" int evoamd_gemm_tn(evoamd_ctx *c, const double *A, const double *B, double *C, int64_t K, int M, int Nc,
@@ -4215,7 +4293,9 @@ extern "C" int evoamd_gemm_tn(evoamd_ctx *c, const double *A, const double *B, d
   int r = 0;
   if (e == hipSuccess) e = hipMemcpyAsync(dA, A, (size_t)K * M * sizeof(double), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(dB, B, (size_t)K * Nc * sizeof(double), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) r = launch_gemm_tn(c, dA, M, dB, Nc, dC, Nc, M, Nc, K, false, sym_row0);
+  GemmTnOpts o;
+  o.sym_row0 = sym_row0;
+  if (e == hipSuccess) r = launch_gemm_tn(c, dA, M, dB, Nc, dC, Nc, M, Nc, K, o);
   if (e == hipSuccess && !r) e = hipMemcpyAsync(C, dC, (size_t)M * Nc * sizeof(double), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   (void)hipFree(dA);
