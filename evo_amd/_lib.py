@@ -80,6 +80,8 @@ SIGNATURES = {
     "evoamd_reconstruct_resident": (_I, [_vp, _c_u8p]),
     "evoamd_patches_merge_resident": (_I, [_vp, _I, _I, _I, _I, _I, _I, _I, _c_dp]),
     "evoamd_download_reconstruction": (_I, [_vp, _c_dp]),
+    "evoamd_posterior_codes": (_I, [_vp, _I, _DBL, _c_i32p, _c_dp, _c_dp, _c_i32p, _c_i32p, _c_dp, _c_u8p]),
+    "evoamd_download_posterior": (_I, [_vp, _c_dp, _c_dp]),
     "evoamd_comm_unique_id": (_I, [_c_u8p]),
     "evoamd_comm_init": (_I, [_vp, _c_u8p, _I, _I]),
     "evoamd_comm_allreduce_host": (_I, [_vp, _c_dp, _I64, _I]),

@@ -25,6 +25,7 @@
 #include "kernels_sssc_quad.hpp"
 #include "kernels_fused.hpp"
 #include "kernels_patches.hpp"
+#include "kernels_codes.hpp"
 
 // ---------------------------------------------------------------------------------------
 // error handling
@@ -374,6 +375,12 @@ struct evoamd_ctx {
   // evoamd_patches_*: image and patch rows on the device, grown on demand (never the EM state above)
   double *patch_img = nullptr, *patch_Y = nullptr;
   size_t patch_img_n = 0, patch_Y_n = 0;
+  // evoamd_posterior_codes: the compact outputs on the device (one allocation, grown on demand); rows_kn_gen = the K^n
+  // the rows of the last statistics pass were formed from; option "codes_path" (-1 automatic, else CODES_REG / _LDS / _GMEM)
+  uint8_t *codes_buf = nullptr;
+  size_t codes_bytes = 0;
+  unsigned long long rows_kn_gen = 0;
+  int codes_path = -1;
   // rccl
   void *comm = nullptr;
   int rank = 0, world = 1;
@@ -537,6 +544,8 @@ extern "C" int evoamd_ctx_create(int device, evoamd_ctx **out) {
                               136 * 1024));
   HIP_TRY(hipFuncSetAttribute((const void *)sssc_big_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               136 * 1024));
+  HIP_TRY(hipFuncSetAttribute((const void *)posterior_codes_kernel<CODES_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              CODES_WAVES * CODES_LDS_H * (int)sizeof(double)));
   HIP_TRY(hipFuncSetAttribute((const void *)gemm_tn128_f64, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)GEMM128_LDS_BYTES));
   HIP_TRY(hipFuncSetAttribute((const void *)gemm_tn128_rows_f64, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -579,7 +588,7 @@ static void free_all(evoamd_ctx *c) {
                   c->tmp_y,  c->tmp_lpj, c->tmp_states, c->dig, c->cand_dig, c->lpj_alt, c->cand_raw, c->dupold, c->gen_start,
                   c->pbins.ent, c->pbins.part, c->pbins.gcnt, c->gemm_ws, c->Yt, c->Yf, c->Ytf, c->Wf, c->Bf, c->Esf,
                   c->clist, c->clist_n, c->ovf_rec, c->theta_bak, c->rowF, c->rowcnt, c->defer, c->fpart, c->huge, c->huge_ctl,
-                  c->patch_img, c->patch_Y, c->keep_x, c->row_any};
+                  c->patch_img, c->patch_Y, c->keep_x, c->row_any, c->codes_buf};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (c->h_acc) (void)hipHostFree(c->h_acc);
@@ -634,6 +643,11 @@ extern "C" int evoamd_set_option(evoamd_ctx *c, const char *name, int value) {
   }
   if (strcmp(name, "reconstruct_in_stats") == 0) {  // one-shot: the next statistics pass forms y_reconstructed first
     c->rec_in_stats = value != 0;
+    return 0;
+  }
+  if (strcmp(name, "codes_path") == 0) {
+    if (value < -1 || value > CODES_GMEM) return fail(EVOAMD_E_INVALID, "codes_path: -1 (auto), 0 registers, 1 LDS, 2 global memory");
+    c->codes_path = value;
     return 0;
   }
   if (strcmp(name, "merge_select_fused") == 0) {
@@ -3695,6 +3709,7 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
   r = stats_epilogue(c, p, fl);
   if (r) return r;
   c->stats_rows_valid = true;
+  c->rows_kn_gen = c->kn_gen;
   return 0;
 }
 
@@ -4586,6 +4601,96 @@ extern "C" int evoamd_patches_merge_resident(evoamd_ctx *c, int H, int W, int C,
   }
   HIP_TRY(hipGetLastError());
   return launch_patches_merge(c, PatchRows{c->patch_Y}, g, method, img_out);
+}
+
+// ---- posterior code readout (kernels_codes.hpp) ----
+static const char *const CODES_NEED_STATS = ": call evoamd_stats first (and before setting new parameters or changing K^n)";
+
+static int codes_preamble(evoamd_ctx *c, const char *who) {
+  if (!(c && c->configured && c->have_data && c->have_params))
+    return fail(EVOAMD_E_INVALID, "%s: configure, upload data and set parameters first", who);
+  if (c->f32) return fail(EVOAMD_E_INVALID, "%s is not available in the float32 mode", who);
+  if (!(c->stats_rows_valid && c->rows_kn_gen == c->kn_gen)) return fail(EVOAMD_E_INVALID, "%s%s", who, CODES_NEED_STATS);
+  HIP_TRY(hipSetDevice(c->device));
+  return 0;
+}
+
+extern "C" int evoamd_posterior_codes(evoamd_ctx *c, int max_active, double p_min, int32_t *idx, double *p, double *m,
+                                      int32_t *nnz, int32_t *map_slot, double *map_q, uint8_t *map_state_packed) {
+  int r = codes_preamble(c, "evoamd_posterior_codes");
+  if (r) return r;
+  REQUIRE(max_active >= 1 && max_active <= CODES_MAX_A, "evoamd_posterior_codes: max_active must be in [1, 64]");
+  REQUIRE(p_min >= 0.0, "evoamd_posterior_codes: p_min must be >= 0 (and not NaN)");
+  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
+  REQUIRE(sssc || !m, "evoamd_posterior_codes: EBSC has no E_q[s z] (m must be NULL)");
+  const size_t N = (size_t)c->N, A = (size_t)max_active, PB = (size_t)(c->H + 7) / 8;
+  // p | m | map_q | idx | nnz | map_slot | map_state: descending alignment
+  const size_t o_p = 0, o_m = o_p + N * A * 8, o_q = o_m + N * A * 8, o_idx = o_q + N * 8, o_nnz = o_idx + N * A * 4,
+               o_slot = o_nnz + N * 4, o_state = o_slot + N * 4, need = o_state + N * PB;
+  if (need > c->codes_bytes) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    ALLOC(c->codes_buf, need);
+    c->codes_bytes = need;
+  }
+  uint8_t *b = c->codes_buf;
+  CodesArgs a = {};
+  a.Es = sssc ? c->Y + c->D : c->Es;
+  a.Ez = sssc ? c->Y + c->D + c->H : nullptr;
+  a.ldE = sssc ? c->ldY : c->H;
+  a.lpj = c->lpj;
+  a.states = c->states;
+  a.N = c->N;
+  a.H = c->H, a.HW = c->HW, a.S = c->S, a.S_perm = c->S_perm, a.L = c->L, a.PB = (int)PB;
+  a.A = max_active;
+  a.p_min = p_min;
+  a.idx = idx ? (int *)(b + o_idx) : nullptr;
+  a.p = p ? (double *)(b + o_p) : nullptr;
+  a.m = m ? (double *)(b + o_m) : nullptr;
+  a.nnz = nnz ? (int *)(b + o_nnz) : nullptr;
+  a.map_slot = map_slot ? (int *)(b + o_slot) : nullptr;
+  a.map_q = map_q ? (double *)(b + o_q) : nullptr;
+  a.map_state = map_state_packed ? b + o_state : nullptr;
+  a.err = c->err;
+  int home = c->codes_path >= 0 ? c->codes_path : (c->H <= 64 * CODES_R ? CODES_REG : c->H <= CODES_LDS_H ? CODES_LDS : CODES_GMEM);
+  REQUIRE(home != CODES_REG || c->H <= 64 * CODES_R, "evoamd_posterior_codes: codes_path 0 (registers) needs H <= 512");
+  REQUIRE(home != CODES_LDS || c->H <= CODES_LDS_H, "evoamd_posterior_codes: codes_path 1 (LDS) needs H <= 4096");
+  {
+    SpanGuard g(c, KID_MISC);
+    const unsigned grid = cdiv(c->N, CODES_WAVES);
+    if (home == CODES_REG)
+      posterior_codes_kernel<CODES_REG><<<grid, 64 * CODES_WAVES, 0, c->stream>>>(a);
+    else if (home == CODES_LDS)
+      posterior_codes_kernel<CODES_LDS><<<grid, 64 * CODES_WAVES, (size_t)CODES_WAVES * c->H * sizeof(double), c->stream>>>(a);
+    else
+      posterior_codes_kernel<CODES_GMEM><<<grid, 64 * CODES_WAVES, 0, c->stream>>>(a);
+  }
+  HIP_TRY(hipGetLastError());
+  if (idx) HIP_TRY(hipMemcpyAsync(idx, a.idx, N * A * 4, hipMemcpyDeviceToHost, c->stream));
+  if (p) HIP_TRY(hipMemcpyAsync(p, a.p, N * A * 8, hipMemcpyDeviceToHost, c->stream));
+  if (m) HIP_TRY(hipMemcpyAsync(m, a.m, N * A * 8, hipMemcpyDeviceToHost, c->stream));
+  if (nnz) HIP_TRY(hipMemcpyAsync(nnz, a.nnz, N * 4, hipMemcpyDeviceToHost, c->stream));
+  if (map_slot) HIP_TRY(hipMemcpyAsync(map_slot, a.map_slot, N * 4, hipMemcpyDeviceToHost, c->stream));
+  if (map_q) HIP_TRY(hipMemcpyAsync(map_q, a.map_q, N * 8, hipMemcpyDeviceToHost, c->stream));
+  if (map_state_packed) HIP_TRY(hipMemcpyAsync(map_state_packed, a.map_state, N * PB, hipMemcpyDeviceToHost, c->stream));
+  return check_err(c);  // synchronises the stream
+}
+
+// The dense rows the codes are cut from: Es (N x H) and, ES3C, Ez (N x H) of the last statistics pass.
+extern "C" int evoamd_download_posterior(evoamd_ctx *c, double *Es, double *Ez) {
+  int r = codes_preamble(c, "evoamd_download_posterior");
+  if (r) return r;
+  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
+  REQUIRE(sssc || !Ez, "evoamd_download_posterior: EBSC has no E_q[s z] (Ez must be NULL)");
+  const size_t w = (size_t)c->H * sizeof(double);
+  if (!sssc) {
+    if (Es) HIP_TRY(hipMemcpyAsync(Es, c->Es, (size_t)c->N * w, hipMemcpyDeviceToHost, c->stream));
+  } else {
+    const size_t pitch = (size_t)c->ldY * sizeof(double);
+    if (Es) HIP_TRY(hipMemcpy2DAsync(Es, w, c->Y + c->D, pitch, w, (size_t)c->N, hipMemcpyDeviceToHost, c->stream));
+    if (Ez) HIP_TRY(hipMemcpy2DAsync(Ez, w, c->Y + c->D + c->H, pitch, w, (size_t)c->N, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------

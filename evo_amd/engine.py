@@ -430,6 +430,34 @@ class Engine:
         check(self.lib.evoamd_patches_merge_resident(self._h, H, W, C, int(ph), int(pw), int(shift), m, dptr(out)))
         return out
 
+    # ---- posterior code readout (evo_amd.codes) ---------------------------------------------
+    def posterior_codes(self, max_active=16, p_min=0.0):
+        """The codes of the last statistics pass, compacted on the device: a PosteriorCodes with the ``max_active``
+        (1 .. 64) most probable latents per datapoint among those with E_q[s_h] > ``p_min`` and the most probable
+        state of K^n.  Only the compact arrays cross to the host.  EvoAmdError unless stats() (or a statistics-only
+        mstep_device) ran since the last change of Theta, the data or K^n."""
+        from .codes import PosteriorCodes
+        N, A, sssc = self.N, int(max_active), self.model == MODEL_SSSC
+        # (arguments the library refuses get 1-element arrays: it checks them before it writes anything)
+        shape = (N, A) if 1 <= A <= 64 else (1, 1)
+        idx = np.empty(shape, dtype=np.int32)
+        p = np.empty(shape)
+        m = np.empty(shape) if sssc else None
+        nnz, map_slot = np.empty(N, dtype=np.int32), np.empty(N, dtype=np.int32)
+        map_q = np.empty(N)
+        map_state = np.empty((N, (self.H + 7) // 8), dtype=np.uint8)
+        check(self.lib.evoamd_posterior_codes(self._h, A, float(p_min), i32ptr(idx), dptr(p), dptr(m) if sssc else None,
+                                              i32ptr(nnz), i32ptr(map_slot), dptr(map_q), u8ptr(map_state)))
+        return PosteriorCodes(self.H, idx, p, m, nnz, map_slot, map_q, map_state, p_min=p_min)
+
+    def download_posterior(self):
+        """(Es, Ez): the dense (N, H) rows E_q[s_h] and, ES3C, E_q[s_h z_h] (else None) of the last statistics pass --
+        what posterior_codes compacts.  Same preconditions."""
+        Es = np.empty((self.N, self.H))
+        Ez = np.empty((self.N, self.H)) if self.model == MODEL_SSSC else None
+        check(self.lib.evoamd_download_posterior(self._h, dptr(Es), None if Ez is None else dptr(Ez)))
+        return Es, Ez
+
     # ---- timing --------------------------------------------------------------------------
     def timing(self, on=True):
         """on: True (all kernel classes), False, or an iterable of class names (_lib.KERNEL_IDS)."""

@@ -786,6 +786,31 @@ class Model:
         if self._incomplete:
             self._yrec_token = (my_data["y_reconstructed"],)
 
+    def encode(self, model_params, my_suff_stat, my_data, max_active=16, p_min=0.0, dense=False):
+        """The code of every datapoint of this rank under ``model_params`` and the caller's K^n / lpj: a
+        evo_amd.codes.PosteriorCodes with, per datapoint, the ``max_active`` (1 .. 64) most probable latents among those
+        with E_q[s_h] > ``p_min`` -- their posterior marginals E_q[s_h] and, ES3C, posterior means E_q[s_h z_h] -- and the
+        most probable state of K^n.  One statistics pass (as in reconstruct()), then the rows it leaves on the device are
+        compacted there and only the compact form crosses to the host; ``dense=True`` also brings the dense (N, H) rows
+        of the same pass (codes.Es / codes.Ez).  Works with sync_host=False (K^n and lpj are read on the device), does
+        no communication and writes nothing into the three dicts."""
+        uploads = self._kn_uploads  # (see reconstruct(): decide before _prepare() runs)
+        eng = self._prepare(my_suff_stat, my_data)
+        # (the precompute stores its derived keys and zeroes the reset counters: on shallow copies here)
+        self.E_step_precompute(dict(model_params), dict(my_suff_stat), my_data)
+        if model_params is not self._dev_theta:
+            self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
+        if self.sync_host or self._kn_uploads != uploads:
+            eng.upload_lpj(my_suff_stat["lpj"])
+        if self._incomplete:
+            eng.set_option("reconstruct_in_stats", 1)
+            self._yrec_token = None  # the pass overwrites the device's y_reconstructed: the next M-step uploads the caller's
+        eng.stats()
+        codes = eng.posterior_codes(max_active, p_min)
+        if dense:
+            codes.Es, codes.Ez = eng.download_posterior()
+        return codes
+
     def modelmean(self, model_params, this_data, this_suff_stat):
         """Per-datapoint operator of the reference's reconstruct loop: (D_miss, S) means of the entries to be
         reconstructed, one column per state of this_suff_stat["ss"] (bsc.py:279-287, sssc.py:368-405)."""

@@ -423,6 +423,29 @@ int evoamd_patches_merge_resident(evoamd_ctx *ctx, int H, int W, int C, int ph, 
                                   double *img_out);
 int evoamd_download_reconstruction(evoamd_ctx *ctx, double *y_hat);
 
+/* ---- posterior code readout (the other product of a sparse-coding run: the code of each datapoint) ---- */
+/* Both calls read the E_q rows the LAST statistics pass left on the device -- E_q[s_h] (both models) and E_q[s_h z_h]
+ * (ES3C) per datapoint -- together with the K^n and lpj rows that pass read; they never run a pass themselves, and they
+ * refuse (EVOAMD_E_INVALID, "call evoamd_stats first ...") once evoamd_set_params_*, a Theta update, an upload of data or
+ * of K^n, or a K^n update has outdated the rows.  Not in the float32 mode.
+ * evoamd_posterior_codes compacts the rows on the device (csrc/kernels_codes.hpp) and copies only the compact form:
+ *   idx (N x max_active int32), p (N x max_active), m (N x max_active, ES3C; must be NULL for EBSC): the latents with
+ *     E_q[s_h] > p_min by descending E_q[s_h], ties by ascending h, cut to max_active (1 .. 64); p = E_q[s_h],
+ *     m = E_q[s_h z_h], both copied from the rows bit for bit; unused slots idx = -1, p = m = 0.  p_min >= 0.
+ *   nnz (N int32): latents with E_q[s_h] > p_min BEFORE the cut (nnz > max_active: the code was truncated).
+ *   map_slot (N int32): index of the largest entry of the lpj row (first one on ties; slots < S_perm are the permanent
+ *     states), map_q (N): its posterior weight 1 / (sum_s exp(lpj_s - lpj_max) + tiny), map_state_packed
+ *     (N x ceil(H/8) bytes): that state in np.packbits layout (evoamd_download_states_packed), the permanent all-zero
+ *     state as zero bits.
+ * Any output pointer may be NULL: that part is not copied.  Option "codes_path" (-1 automatic (default), 0 / 1 / 2): the
+ * kernel keeps a datapoint's row in registers (H <= 512) / in LDS (H <= 4096) / re-reads it from memory (any H); same
+ * results, for tests and measurements.
+ * evoamd_download_posterior: the dense rows themselves, Es (N x H) and Ez (N x H, ES3C; NULL for EBSC), either may be
+ * NULL -- 8 N H bytes each over PCIe where the codes are a few per cent of that. */
+int evoamd_posterior_codes(evoamd_ctx *ctx, int max_active, double p_min, int32_t *idx, double *p, double *m,
+                           int32_t *nnz, int32_t *map_slot, double *map_q, uint8_t *map_state_packed);
+int evoamd_download_posterior(evoamd_ctx *ctx, double *Es, double *Ez);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------------- */
 /* 128-byte opaque id made by rank 0 and distributed by the caller (file / socket / MPI). */
 int evoamd_comm_unique_id(uint8_t id_out[128]);
