@@ -21,7 +21,7 @@ KERNEL_IDS = {
     "stats": 5, "stats_overflow": 6, "gemm_f64": 7, "evolve": 8, "misc": 9, "mstep_device": 10,
     "lpj_pass": 11, "stats_pass": 12, "lpj_k3_4": 13, "lpj_k5_8": 14, "lpj_k9plus": 15,
     "stats_k3_4": 16, "stats_k5_8": 17, "stats_k9plus": 18, "allreduce": 19, "estep_fused": 20,
-    "patches": 21,
+    "patches": 21, "init_states": 22,
 }
 
 _c_dp = ctypes.POINTER(ctypes.c_double)
@@ -45,6 +45,7 @@ SIGNATURES = {
     "evoamd_download_states": (_I, [_vp, _c_u8p]),
     "evoamd_upload_states_packed": (_I, [_vp, _c_u8p, _I64, _I64]),
     "evoamd_download_states_packed": (_I, [_vp, _c_u8p, _I64, _I64]),
+    "evoamd_init_states": (_I, [_vp, _DBL, _U64, _I, _c_u8p]),
     "evoamd_upload_lpj": (_I, [_vp, _c_dp]),
     "evoamd_download_lpj": (_I, [_vp, _c_dp]),
     "evoamd_set_params_bsc": (_I, [_vp, _c_dp, _DBL, _DBL, _c_dp]),

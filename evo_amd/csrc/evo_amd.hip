@@ -26,6 +26,7 @@
 #include "kernels_fused.hpp"
 #include "kernels_patches.hpp"
 #include "kernels_codes.hpp"
+#include "kernels_init.hpp"
 
 // ---------------------------------------------------------------------------------------
 // error handling
@@ -66,6 +67,13 @@ static const bool g_dbg_sync = getenv("EVOAMD_DEBUG_SYNC") != nullptr;
   do {                                                       \
     if (!(cond)) return fail(EVOAMD_E_INVALID, "%s", msg);   \
   } while (0)
+// After a failed evoamd_init_states (kn_lost) K^n is partly written.  Guarded directly: the downloads of K^n, lpj_resident,
+// vary_kn, evolve_randflip, estep, evolve_states and the statistics pass (hence mstep_device and the pass it prefetches);
+// posterior_codes refuses through kn_gen (the failed call bumps it, so the rows of the last pass are outdated).  Nothing
+// else reads c->states / c->dig: lpj_candidates, set_candidates, lpj_shared, lpj_single and the reconstruction calls work on
+// the candidate batch, on states the caller passes or on the rows of the last statistics pass.
+#define REQUIRE_KN(c) \
+  REQUIRE(!(c)->kn_lost, "K^n is not on the device: evoamd_init_states stopped at its round cap (upload or initialise K^n first)")
 
 // ---------------------------------------------------------------------------------------
 // RCCL through dlopen (so the library loads on hosts without librccl)
@@ -137,6 +145,7 @@ enum {  // internal kernel ids (see evoamd_kernel_name)
   KID_ALLREDUCE,    // the RCCL all-reduce(s) of the packed accumulator: local statistics done -> sum delivered
   KID_ESTEP_FUSED,  // the fused per-datapoint E-step kernel (lpj of K^n -> candidates -> their lpj -> vary_Kn -> census)
   KID_PATCHES,      // overlapping image patches: extract / mean merge / median merge kernels
+  KID_INIT_STATES,  // evoamd_init_states: the K^n(0) sampler (or the table copy of the exact mode)
   KID_COUNT
 };
 
@@ -381,6 +390,14 @@ struct evoamd_ctx {
   size_t codes_bytes = 0;
   unsigned long long rows_kn_gen = 0;
   int codes_path = -1;
+  // evoamd_init_states (kernels_init.hpp): option "init_states_home" (-1 automatic, 0 LDS, 1 global memory), the slots of
+  // the global home (grown on demand), and kn_lost: the call stopped at its round cap, K^n is partly written -- every pass
+  // that reads K^n refuses until an upload or a successful evoamd_init_states
+  int init_home = -1;
+  u64 *init_scratch = nullptr;
+  size_t init_scratch_words = 0;
+  bool kn_lost = false;
+  i64 kn_refill = 0;  // while kn_lost: rows [0, kn_refill) have been uploaded again by evoamd_upload_states_packed
   // rccl
   void *comm = nullptr;
   int rank = 0, world = 1;
@@ -588,7 +605,7 @@ static void free_all(evoamd_ctx *c) {
                   c->tmp_y,  c->tmp_lpj, c->tmp_states, c->dig, c->cand_dig, c->lpj_alt, c->cand_raw, c->dupold, c->gen_start,
                   c->pbins.ent, c->pbins.part, c->pbins.gcnt, c->gemm_ws, c->Yt, c->Yf, c->Ytf, c->Wf, c->Bf, c->Esf,
                   c->clist, c->clist_n, c->ovf_rec, c->theta_bak, c->rowF, c->rowcnt, c->defer, c->fpart, c->huge, c->huge_ctl,
-                  c->patch_img, c->patch_Y, c->keep_x, c->row_any, c->codes_buf};
+                  c->patch_img, c->patch_Y, c->keep_x, c->row_any, c->codes_buf, c->init_scratch};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (c->h_acc) (void)hipHostFree(c->h_acc);
@@ -733,6 +750,11 @@ extern "C" int evoamd_set_option(evoamd_ctx *c, const char *name, int value) {
   }
   if (strcmp(name, "gemm_per_xcd") == 0) {
     c->gemm_per_xcd = value;
+    return 0;
+  }
+  if (strcmp(name, "init_states_home") == 0) {
+    if (value < -1 || value > 1) return fail(EVOAMD_E_INVALID, "init_states_home: -1 (auto), 0 LDS, 1 global memory");
+    c->init_home = value;
     return 0;
   }
   if (strcmp(name, "background_unit") == 0) {
@@ -1127,6 +1149,10 @@ extern "C" int evoamd_configure(evoamd_ctx *c, int model, int64_t N, int D, int 
   c->yhat_valid = c->stats_rows_valid = c->rec_resident = c->yrec_from_pass = false;
   c->theta_bak_valid = false;
   c->lists_clean = c->need_known = c->cand_from_device = false;  // fresh (uninitialised) overflow counters
+  c->kn_lost = false;
+  c->init_scratch_words = 0;
+  if (c->init_scratch) (void)hipFree(c->init_scratch);
+  c->init_scratch = nullptr;
   return 0;
 }
 
@@ -1237,12 +1263,14 @@ extern "C" int evoamd_upload_states(evoamd_ctx *c, const uint8_t *ss_bool) {
   if (r) return r;
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->need_known = false;
+  c->kn_lost = false;
   return 0;
 }
 
 extern "C" int evoamd_download_states(evoamd_ctx *c, uint8_t *ss_bool) {
   REQUIRE(c && c->configured, "configure first");
   REQUIRE(ss_bool, "ss is NULL");
+  REQUIRE_KN(c);
   HIP_TRY(hipSetDevice(c->device));
   const i64 ns = c->N * (i64)c->S;
   {
@@ -1277,12 +1305,111 @@ extern "C" int evoamd_upload_states_packed(evoamd_ctx *c, const uint8_t *packed,
   c->gen++;
   c->kn_gen++;
   c->need_known = false;
+  if (c->kn_lost && n0 <= c->kn_refill && n0 + n > c->kn_refill) {  // chunks in ascending order rebuild a lost K^n
+    c->kn_refill = n0 + n;
+    if (c->kn_refill >= c->N) c->kn_lost = false;
+  }
+  return 0;
+}
+
+// K^n(0) drawn on the device (kernels_init.hpp; variational/utils.py:100-138 with a counter-based stream), or -- exact
+// E-steps -- the caller's state table copied to every datapoint.
+extern "C" int evoamd_init_states(evoamd_ctx *c, double p_init, uint64_t seed, int max_rounds, const uint8_t *table_packed) {
+  REQUIRE(c && c->configured, "configure first");
+  REQUIRE(max_rounds >= 1 && max_rounds <= 65536, "evoamd_init_states: max_rounds must be in [1, 65536]");
+  REQUIRE(!(c->bg_unit && c->S_perm), "evoamd_init_states: no permanent all-zero state with the background unit (variational/utils.py:42-47)");
+  REQUIRE(c->H - c->bg_unit >= 1, "evoamd_init_states: no latent varies");
+  HIP_TRY(hipSetDevice(c->device));
+  const int S = c->S, HW = c->HW;
+  if (table_packed) {
+    const int Hv = c->H - c->bg_unit;
+    REQUIRE(Hv < 12 && S + c->S_perm == (1 << Hv),
+            "evoamd_init_states: a state table means exact E-steps, S + S_perm == 2^Hv with Hv < 12 (variational/utils.py:55)");
+  }
+  if (table_packed) {  // exact mode: (S, ceil(H/8)) packbits rows -> words behind them in the staging area -> every datapoint
+    const int PB = (c->H + 7) / 8;
+    const size_t off = (((size_t)S * PB + 7) / 8) * 8;
+    {
+      int rs = ensure_stage(c, off + (size_t)S * HW * sizeof(u64));
+      if (rs) return rs;
+    }
+    u64 *table = (u64 *)(c->stage + off);
+    HIP_TRY(hipMemcpyAsync(c->stage, table_packed, (size_t)S * PB, hipMemcpyHostToDevice, c->stream));
+    SpanGuard g(c, KID_INIT_STATES);
+    words_from_packbits_kernel<<<cdiv((i64)S * HW, 256), 256, 0, c->stream>>>(c->stage, table, S, PB, HW, c->H);
+    init_states_tile_kernel<<<cdiv(c->N * (i64)S, 256), 256, 0, c->stream>>>(table, c->states, c->dig, c->N, S, HW);
+  } else {
+    InitArgs a;
+    a.states = c->states;
+    a.dig = c->dig;
+    a.scratch = nullptr;
+    a.err = c->err + INIT_ERR_WORD;
+    a.N = c->N;
+    a.S = S;
+    a.S_perm = c->S_perm;
+    a.H = c->H;
+    a.Hv = c->H - c->bg_unit;
+    a.HW = HW;
+    a.max_rounds = max_rounds;
+    a.seed = seed;
+    a.p0 = p_init > 0.0 ? p_init : 1.0 / (double)c->H;
+    const size_t wave_words = 2 * (size_t)(HW + 1) * S;  // candidates and held set, each HW word rows + the hash row
+    int W = 4;
+    while (W > 1 && W * wave_words * sizeof(u64) > 150 * 1024) W >>= 1;
+    const bool lds_fits = W * wave_words * sizeof(u64) <= 150 * 1024;
+    REQUIRE(c->init_home != 0 || lds_fits, "init_states_home 0 (LDS): the round state of one wavefront does not fit");
+    const bool lds_home = c->init_home < 0 ? lds_fits : c->init_home == 0;
+    c->kn_lost = true;  // until the kernel has completed every datapoint
+    c->kn_refill = 0;
+    c->gen++;
+    c->kn_gen++;
+    c->need_known = false;
+    HIP_TRY(hipMemsetAsync(a.err, 0, sizeof(int), c->stream));
+    if (lds_home) {
+      const unsigned grid = (unsigned)std::min<i64>(cdiv(c->N, W), (i64)c->n_cu * 64);
+      SpanGuard g(c, KID_INIT_STATES);
+      init_states_kernel<true><<<grid, 64 * W, (size_t)W * wave_words * sizeof(u64), c->stream>>>(a);
+    } else {  // slots of global memory, one per wave of a resident-sized grid (at most 256 MB)
+      W = 4;
+      i64 grid = std::min<i64>(cdiv(c->N, W), (i64)c->n_cu * 2);
+      while (grid > 1 && (size_t)grid * W * wave_words * sizeof(u64) > ((size_t)256 << 20)) grid >>= 1;
+      const size_t need = (size_t)grid * W * wave_words;
+      if (need > c->init_scratch_words) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        ALLOC(c->init_scratch, need);
+        c->init_scratch_words = need;
+      }
+      a.scratch = c->init_scratch;
+      SpanGuard g(c, KID_INIT_STATES);
+      init_states_kernel<false><<<(unsigned)grid, 64 * W, 0, c->stream>>>(a);
+    }
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "init_states");
+    HIP_TRY(hipMemcpyAsync(c->h_err, a.err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->h_err[0] & INIT_ERR_CAP) {
+      HIP_TRY(hipMemsetAsync(a.err, 0, sizeof(int), c->stream));
+      return fail(EVOAMD_E_INVALID,
+                  "evoamd_init_states: a datapoint holds fewer than S = %d distinct states after max_rounds = %d rounds (the "
+                  "round cap); K^n is not initialised -- shapes with S close to 2^H belong to the host function",
+                  S, max_rounds);
+    }
+    c->kn_lost = false;
+    return 0;
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->gen++;
+  c->kn_gen++;
+  c->need_known = false;
+  c->kn_lost = false;
   return 0;
 }
 
 extern "C" int evoamd_download_states_packed(evoamd_ctx *c, uint8_t *packed, int64_t n0, int64_t n) {
   REQUIRE(c && c->configured, "configure first");
   REQUIRE(packed && n0 >= 0 && n > 0 && n0 + n <= c->N, "bad row range");
+  REQUIRE_KN(c);
   HIP_TRY(hipSetDevice(c->device));
   const int PB = (c->H + 7) / 8;
   const i64 ns = n * (i64)c->S;
@@ -2345,6 +2472,7 @@ static int lpj_resident_launch(evoamd_ctx *c, double *out, const LevelHints &lv)
 
 extern "C" int evoamd_lpj_resident(evoamd_ctx *c) {
   REQUIRE(c && c->configured && c->have_data && c->have_params, "configure, upload_data and set_params first");
+  REQUIRE_KN(c);
   HIP_TRY(hipSetDevice(c->device));
   if (c->prefetch_gen == c->gen) {  // evoamd_mstep_device already enqueued exactly this pass
     c->prefetch_gen = ~0ull;
@@ -2543,6 +2671,7 @@ extern "C" int evoamd_lpj_single_masked(evoamd_ctx *c, const double *y, const ui
 extern "C" int evoamd_vary_kn(evoamd_ctx *c, int Mprime, double *sums_out) {
   REQUIRE(c && c->configured && c->have_cand, "no resident candidate batch (call lpj_candidates / evolve first)");
   REQUIRE(Mprime >= 1 && Mprime <= c->S, "Mprime must be in [1, S]");
+  REQUIRE_KN(c);
   HIP_TRY(hipSetDevice(c->device));
   c->gen++;
   c->kn_gen++;
@@ -2599,6 +2728,7 @@ extern "C" int evoamd_evolve_randflip(evoamd_ctx *c, int n_parents, int n_childr
   REQUIRE(n_parents >= 1 && n_parents <= c->S && n_parents <= 64, "n_parents must be in [1, min(S, 64)]");
   REQUIRE(n_children >= 1 && n_children <= EV_MAX_CHILDREN && n_children <= c->H, "n_children must be in [1, min(8, H)]");
   REQUIRE(n_parents * n_children <= c->Cmax, "n_parents * n_children exceeds the configured Cmax");
+  REQUIRE_KN(c);
   HIP_TRY(hipSetDevice(c->device));
   {
     SpanGuard g(c, KID_EVOLVE);
@@ -2773,6 +2903,7 @@ extern "C" int evoamd_estep(evoamd_ctx *c, int n_parents, int n_children, uint64
   REQUIRE(n_children >= 1 && n_children <= EV_MAX_CHILDREN && n_children <= c->H, "n_children must be in [1, min(8, H)]");
   REQUIRE(n_parents * n_children <= c->Cmax, "n_parents * n_children exceeds the configured Cmax");
   REQUIRE(Mprime >= 1 && Mprime <= c->S, "Mprime must be in [1, S]");
+  REQUIRE_KN(c);
   HIP_TRY(hipSetDevice(c->device));
   // Sparse enough: FAST leaves every datapoint that meets a state above four latents to the low-occupancy FULL launches
   // -- the census of the last statistics pass says how many states there are above four
@@ -2822,6 +2953,7 @@ extern "C" int evoamd_evolve_states(evoamd_ctx *c, int mutation, int fit_parents
                                     int n_generations, uint64_t seed, double sparseness, double bitflip_prob) {
   REQUIRE(c && c->configured && c->have_data && c->have_params, "configure, upload_data and set_params first");
   REQUIRE(mutation >= EV_RANDFLIP && mutation <= EV_CROSS_SPARSEFLIP, "unknown mutation operator");
+  REQUIRE_KN(c);
   REQUIRE(n_parents >= 1 && n_parents <= c->S && n_parents <= 64, "n_parents must be in [1, min(S, 64)]");
   REQUIRE(n_generations >= 1, "n_generations must be positive");
   const bool crossing = mutation >= EV_CROSS;
@@ -3643,6 +3775,7 @@ static int stats_sssc_pass(evoamd_ctx *c, const StatsPlan &p, Es3cPass &ep) {
 // timed on the main stream.
 static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
   REQUIRE(c && c->configured && c->have_data && c->have_params, "configure, upload_data and set_params first");
+  REQUIRE_KN(c);
   StatsPlan p;
   int r = stats_plan(c, fork_gemm, p);
   if (r) return r;
@@ -4789,6 +4922,6 @@ extern "C" const char *evoamd_kernel_name(int kid) {
                                          "stats",        "stats_overflow", "gemm_f64",     "evolve",   "misc", "mstep_device",
                                          "lpj_pass",     "stats_pass",     "lpj_k3_4",     "lpj_k5_8", "lpj_k9plus",
                                          "stats_k3_4",   "stats_k5_8",     "stats_k9plus", "allreduce",    "estep_fused",
-                                         "patches"};
+                                         "patches",      "init_states"};
   return (kid >= 0 && kid < KID_COUNT) ? names[kid] : "?";
 }

@@ -108,6 +108,20 @@ class Engine:
         check(self.lib.evoamd_download_states_packed(self._h, u8ptr(out), int(n0), n))
         return out
 
+    def init_states(self, p_init, seed, max_rounds=256, table=None):
+        """K^n(0) drawn on the device with the law of evo_amd.variational.init_states and the counter-based stream of
+        evo_amd.variational.init_states_counter (its NumPy mirror, bit for bit); reads S_perm and the "background_unit"
+        option of the context.  ``table``: bool (S, H) state table of the exact mode (S == 2 ** Hv), copied to every
+        datapoint instead.  EvoAmdError naming the cap when a datapoint is not complete after ``max_rounds`` rounds: K^n
+        then counts as not uploaded."""
+        tp = None
+        if table is not None:
+            t = np.ascontiguousarray(table, dtype=np.bool_)
+            assert t.shape == (self.S, self.H), (t.shape, (self.S, self.H))
+            packed = np.packbits(t, axis=-1)
+            tp = u8ptr(packed)
+        check(self.lib.evoamd_init_states(self._h, float(p_init), int(seed) & (2 ** 64 - 1), int(max_rounds), tp))
+
     def upload_lpj(self, lpj):
         lpj = as_f64(lpj)
         assert lpj.shape == (self.N, self.L)

@@ -27,6 +27,7 @@ from ..resident import ResidentReconstruction
 from ..utils import parallel
 from ..variational import eas
 from ..variational.utils import vary_Kn  # noqa: F401  (re-exported like the reference module does)
+from ..variational.utils import init_states as _host_init_states
 
 F64_MIN = np.finfo(np.float64).min
 
@@ -272,6 +273,47 @@ class Model:
             eng.upload_states_packed(chunk, n0)
         self._resident = True
 
+    def init_resident_states(self, my_data, parent_selection, mutation_algorithm, no_parents, no_children, no_generations,
+                             bitflip_prob=None, Mprime=None, p_init_Kn=None, permanent=None, seed=None, max_rounds=256):
+        """``init_states`` for this rank's ``my_data`` with K^n(0) drawn on the device (Engine.init_states): the same law,
+        a counter-based stream instead of NumPy's (evo_amd.variational.init_states_counter reproduces it bit for bit for
+        ``self.last_init_seed``).  Returns my_suff_stat with init_states' keys, dtypes, assertions and the ``cross`` rule;
+        S is the model's.  sync_host=False: K^n stays on the device, "ss" and "lpj" are None (sync_to_host allocates them);
+        sync_host=True: "ss" is downloaded once.  ``seed`` None: drawn from np.random (np.random.seed makes runs
+        reproducible); rank and world size enter it, so ranks get different streams.  RuntimeError naming the cap when
+        a datapoint is not complete after ``max_rounds`` rounds -- shapes with S close to 2 ** H belong to init_states.
+        Exact E-steps: S == 2 ** Hv, or S == 2 ** Hv - 1 with the permanent all-zero state (what init_states lays out
+        when it is asked for 2 ** Hv states, so the mirror of that case is init_states_counter(N, S + 1, ...), not
+        (N, S, ...), which samples); the state table is built on the host and copied to every datapoint."""
+        N, H = my_data["y"].shape[0], self.H
+        permanent = permanent or {"background": False, "allzero": False, "singletons": False}
+        background = bool(permanent["background"])
+        Hv = H - 1 if background else H
+        S_perm = 0 if background else (1 if (permanent["allzero"] == 1 and permanent["singletons"] == 0) else 0)
+        S_arg = self.S + 1 if (S_perm and Hv < 12 and self.S == 2 ** Hv - 1) else self.S
+        if Mprime is None:
+            Mprime = self.S
+        # every key but the two arrays, from the host function itself (no datapoint: no random number is drawn)
+        suff = _host_init_states(0, S_arg, H, parent_selection, mutation_algorithm, no_parents, no_children, no_generations,
+                                 bitflip_prob, Mprime, p_init_Kn, permanent)
+        suff["ss"] = suff["lpj"] = None
+        table = None
+        if S_arg == 2 ** Hv:
+            sm = suff["sm"]
+            table = (np.concatenate((sm, np.ones((sm.shape[0], 1), dtype=bool)), axis=1) if background
+                     else (sm[1:] if S_perm else sm))
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+        self.last_init_seed = (int(seed) * max(1, self.comm.size) + self.comm.rank) & (2 ** 64 - 1)
+        eng = self._prepare(suff, my_data, upload_states=False)
+        self._resident = False
+        eng.init_states(1.0 / H if p_init_Kn is None else p_init_Kn, self.last_init_seed, max_rounds, table)
+        self._resident = True
+        if self.sync_host:
+            suff["ss"] = eng.download_states()
+            suff["lpj"] = np.empty((N, self.S + S_perm))
+        return suff
+
     def _prepare(self, my_suff_stat, my_data, upload_states=True):
         """Configure the engine for this rank's shard and make Y / K^n resident."""
         Y = my_data["y"]
@@ -341,8 +383,8 @@ class Model:
 
     def sync_to_host(self, my_suff_stat):
         """Copy the device-resident K^n and lpj into the caller's arrays (in place)."""
-        self.engine.download_states(my_suff_stat["ss"])
-        self.engine.download_lpj(my_suff_stat["lpj"])
+        my_suff_stat["ss"] = self.engine.download_states(my_suff_stat["ss"])  # (None: allocated -- init_resident_states)
+        my_suff_stat["lpj"] = self.engine.download_lpj(my_suff_stat["lpj"])
 
     # ---- hooks the concrete models provide ---------------------------------------------------
     def _push_params(self, model_params):

@@ -199,6 +199,26 @@ int evoamd_download_states(evoamd_ctx *ctx, uint8_t *ss_bool);
  * any row range, so a large K^n can be handed over in chunks. */
 int evoamd_upload_states_packed(evoamd_ctx *ctx, const uint8_t *packed, int64_t n0, int64_t n);
 int evoamd_download_states_packed(evoamd_ctx *ctx, uint8_t *packed, int64_t n0, int64_t n);
+/* K^n(0) drawn where it lives: the law of init_states (variational/utils.py:100-138) -- per datapoint rounds of S
+ * candidate states with independent bits Bernoulli(p_init) over the varying latents (p_init <= 0: 1 / H), candidates equal
+ * to the permanent all-zero state (S_perm = 1) dropped, first occurrences appended in ascending lexicographic row order
+ * (np.unique's) behind what is held, until S states are held; with option "background_unit" the last latent is on in every
+ * state and is not drawn.  The stream is counter-based, not NumPy's: the bit of (datapoint n, round r, candidate s,
+ * latent h) is rng_u01(seed, n, INIT_PURPOSE + r, s * Hv + h) < p_init (csrc/kernels_init.hpp has the definition;
+ * evo_amd.variational.init_states_counter is its NumPy mirror, bit for bit).  The reference loops without bound; here a
+ * datapoint that is not complete after max_rounds (1 .. 65536; 256 is ample unless S approaches 2^Hv, and such shapes
+ * belong to the host function) makes the call return EVOAMD_E_INVALID naming the cap: K^n then counts as not uploaded --
+ * every call that reads it refuses until evoamd_upload_states, evoamd_upload_states_packed calls that cover rows 0 .. N-1 in
+ * ascending order, a successful evoamd_init_states or a new evoamd_configure.
+ * Exact E-steps (S == 2^Hv): table_packed holds the (S, ceil(H/8)) np.packbits rows of the state table as the host function
+ * builds it (without the all-zero row when S_perm = 1, with the background unit's bit set); every datapoint gets it and
+ * no random number is drawn (refused unless S + S_perm == 2^Hv, Hv < 12; the rows themselves are the caller's).
+ * table_packed == NULL: the sampler.
+ * Needs evoamd_configure; reads S_perm and "background_unit" from the context.  Like evoamd_upload_states_packed it writes the
+ * digests too, and the lpj rows on the device no longer belong to K^n afterwards.  Option "init_states_home" (-1 automatic
+ * (default), 0, 1): a wavefront keeps the round's candidates and the held set in LDS / in a slot of global memory
+ * (automatic: LDS whenever 16 S (ceil(H/64) + 1) bytes fit one wavefront's share); same results, for tests. */
+int evoamd_init_states(evoamd_ctx *ctx, double p_init, uint64_t seed, int max_rounds, const uint8_t *table_packed);
 /* my_suff_stat["lpj"] (N,S_perm+S) float64. */
 int evoamd_upload_lpj(evoamd_ctx *ctx, const double *lpj);
 int evoamd_download_lpj(evoamd_ctx *ctx, double *lpj);
