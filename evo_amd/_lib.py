@@ -15,6 +15,10 @@ LIB_PATH = os.path.join(_HERE, "libevo_amd.so")
 
 MODEL_BSC, MODEL_SSSC = 0, 1
 
+# evoamd_generate: keep bits (EVOAMD_GEN_KEEP_*) and the output ids of evoamd_download_generated (EVOAMD_GEN_*)
+GEN_KEEP = {"s": 1, "z": 2, "y_mean": 4}
+GEN_WHAT = {"y": 0, "s": 1, "z": 2, "y_mean": 3}
+
 # kernel-class ids of evoamd_kernel_time_ms (evo_amd.hip: KID_*)
 KERNEL_IDS = {
     "lpj_resident": 0, "lpj_candidates": 1, "lpj_overflow": 2, "row_lse": 3, "vary_kn": 4,
@@ -27,6 +31,7 @@ KERNEL_IDS = {
 _c_dp = ctypes.POINTER(ctypes.c_double)
 _c_u8p = ctypes.POINTER(ctypes.c_uint8)
 _c_i32p = ctypes.POINTER(ctypes.c_int32)
+_c_u64p = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p
 _I, _I64, _U64, _DBL = ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double
 
@@ -83,6 +88,8 @@ SIGNATURES = {
     "evoamd_download_reconstruction": (_I, [_vp, _c_dp]),
     "evoamd_posterior_codes": (_I, [_vp, _I, _DBL, _c_i32p, _c_dp, _c_dp, _c_i32p, _c_i32p, _c_dp, _c_u8p]),
     "evoamd_download_posterior": (_I, [_vp, _c_dp, _c_dp]),
+    "evoamd_generate": (_I, [_vp, _I, _I64, _I, _I, _U64, _U64, _c_dp, _c_dp, _c_dp, _c_dp, _DBL, _c_u64p, _I]),
+    "evoamd_download_generated": (_I, [_vp, _I, _vp]),
     "evoamd_comm_unique_id": (_I, [_c_u8p]),
     "evoamd_comm_init": (_I, [_vp, _c_u8p, _I, _I]),
     "evoamd_comm_allreduce_host": (_I, [_vp, _c_dp, _I64, _I]),

@@ -27,6 +27,7 @@
 #include "kernels_patches.hpp"
 #include "kernels_codes.hpp"
 #include "kernels_init.hpp"
+#include "kernels_generate.hpp"
 
 // ---------------------------------------------------------------------------------------
 // error handling
@@ -398,6 +399,13 @@ struct evoamd_ctx {
   size_t init_scratch_words = 0;
   bool kn_lost = false;
   i64 kn_refill = 0;  // while kn_lost: rows [0, kn_refill) have been uploaded again by evoamd_upload_states_packed
+  // evoamd_generate (kernels_generate.hpp): Theta^gen, the given states and the outputs of the last call, grown on demand
+  // (never the EM state above); gen_keep < 0: no call has completed
+  double *gen_par = nullptr, *gen_y = nullptr, *gen_z = nullptr, *gen_ymean = nullptr;
+  u64 *gen_sin = nullptr, *gen_s = nullptr;
+  size_t gen_par_n = 0, gen_y_n = 0, gen_z_n = 0, gen_ymean_n = 0, gen_sin_n = 0, gen_s_n = 0;
+  i64 gen_N = 0;
+  int gen_D = 0, gen_H = 0, gen_keep = -1;
   // rccl
   void *comm = nullptr;
   int rank = 0, world = 1;
@@ -605,7 +613,8 @@ static void free_all(evoamd_ctx *c) {
                   c->tmp_y,  c->tmp_lpj, c->tmp_states, c->dig, c->cand_dig, c->lpj_alt, c->cand_raw, c->dupold, c->gen_start,
                   c->pbins.ent, c->pbins.part, c->pbins.gcnt, c->gemm_ws, c->Yt, c->Yf, c->Ytf, c->Wf, c->Bf, c->Esf,
                   c->clist, c->clist_n, c->ovf_rec, c->theta_bak, c->rowF, c->rowcnt, c->defer, c->fpart, c->huge, c->huge_ctl,
-                  c->patch_img, c->patch_Y, c->keep_x, c->row_any, c->codes_buf, c->init_scratch};
+                  c->patch_img, c->patch_Y, c->keep_x, c->row_any, c->codes_buf, c->init_scratch,
+                  c->gen_par, c->gen_y, c->gen_z, c->gen_ymean, c->gen_sin, c->gen_s};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (c->h_acc) (void)hipHostFree(c->h_acc);
@@ -4822,6 +4831,117 @@ extern "C" int evoamd_download_posterior(evoamd_ctx *c, double *Es, double *Ez) 
     if (Es) HIP_TRY(hipMemcpy2DAsync(Es, w, c->Y + c->D, pitch, w, (size_t)c->N, hipMemcpyDeviceToHost, c->stream));
     if (Ez) HIP_TRY(hipMemcpy2DAsync(Ez, w, c->Y + c->D + c->H, pitch, w, (size_t)c->N, hipMemcpyDeviceToHost, c->stream));
   }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// samples from the model (kernels_generate.hpp): own buffers, no EM state touched
+// ---------------------------------------------------------------------------------------
+template <typename T>
+static int gen_ensure(evoamd_ctx *c, T **p, size_t *have, size_t need) {
+  if (need <= *have) return 0;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  *have = 0;
+  int r = dev_alloc(p, need);
+  if (r) return r;
+  *have = need;
+  return 0;
+}
+
+extern "C" int evoamd_generate(evoamd_ctx *c, int model, int64_t N, int D, int H, uint64_t seed, uint64_t first_index,
+                               const double *Wt, const double *pies, const double *mus, const double *F, double sigma,
+                               const uint64_t *s_packed, int keep) {
+  REQUIRE(c && Wt && pies, "evoamd_generate: NULL argument");
+  REQUIRE(model == EVOAMD_MODEL_BSC || model == EVOAMD_MODEL_SSSC, "evoamd_generate: model must be EVOAMD_MODEL_BSC or EVOAMD_MODEL_SSSC");
+  REQUIRE(N >= 1 && D >= 1 && H >= 1, "evoamd_generate: N, D and H must be positive");
+  REQUIRE(sigma >= 0.0 && sigma <= 1.7976931348623157e308, "evoamd_generate: sigma must be finite and not negative");
+  REQUIRE((keep & ~(EVOAMD_GEN_KEEP_S | EVOAMD_GEN_KEEP_Z | EVOAMD_GEN_KEEP_YMEAN)) == 0, "evoamd_generate: unknown bit in keep");
+  const bool sssc = model == EVOAMD_MODEL_SSSC;
+  REQUIRE(!sssc || (mus && F), "evoamd_generate: ES3C needs mus and F (F F^T = Psi)");
+  if (!sssc) keep &= ~EVOAMD_GEN_KEEP_Z;  // EBSC: z = s
+  const size_t slice = sssc ? (size_t)H * sizeof(double) : 0;
+  if (slice > 64 * 1024)
+    return fail(EVOAMD_E_INVALID, "evoamd_generate: the eps values of one datapoint (H = %d doubles) exceed the 64 KB of LDS a wavefront may hold", H);
+  HIP_TRY(hipSetDevice(c->device));
+  const int HW = (H + 63) / 64;
+  const size_t nd = (size_t)N * D, nh = (size_t)N * H, nw = (size_t)N * HW;
+  const size_t par_n = (size_t)H * D + H + (sssc ? (size_t)H + (size_t)H * H : 0);
+  c->gen_keep = -1;  // until this call has completed
+  int r = gen_ensure(c, &c->gen_par, &c->gen_par_n, par_n);
+  if (!r) r = gen_ensure(c, &c->gen_y, &c->gen_y_n, nd);
+  if (!r && (keep & EVOAMD_GEN_KEEP_S)) r = gen_ensure(c, &c->gen_s, &c->gen_s_n, nw);
+  if (!r && (keep & EVOAMD_GEN_KEEP_Z)) r = gen_ensure(c, &c->gen_z, &c->gen_z_n, nh);
+  if (!r && (keep & EVOAMD_GEN_KEEP_YMEAN)) r = gen_ensure(c, &c->gen_ymean, &c->gen_ymean_n, nd);
+  if (!r && s_packed) r = gen_ensure(c, &c->gen_sin, &c->gen_sin_n, nw);
+  if (r) return r;
+  double *dWt = c->gen_par, *dpies = dWt + (size_t)H * D, *dmus = dpies + H, *dF = dmus + H;
+  HIP_TRY(hipMemcpyAsync(dWt, Wt, (size_t)H * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dpies, pies, (size_t)H * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (sssc) {
+    HIP_TRY(hipMemcpyAsync(dmus, mus, (size_t)H * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dF, F, (size_t)H * H * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  if (s_packed) HIP_TRY(hipMemcpyAsync(c->gen_sin, s_packed, nw * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+  GenArgs a;
+  a.Wt = dWt;
+  a.pies = dpies;
+  a.mus = sssc ? dmus : nullptr;
+  a.F = sssc ? dF : nullptr;
+  a.s_in = s_packed ? c->gen_sin : nullptr;
+  a.y = c->gen_y;
+  a.s_out = (keep & EVOAMD_GEN_KEEP_S) ? c->gen_s : nullptr;
+  a.z = (keep & EVOAMD_GEN_KEEP_Z) ? c->gen_z : nullptr;
+  a.y_mean = (keep & EVOAMD_GEN_KEEP_YMEAN) ? c->gen_ymean : nullptr;
+  a.N = N;
+  a.D = D;
+  a.H = H;
+  a.HW = HW;
+  a.sssc = sssc ? 1 : 0;
+  a.seed = seed;
+  a.first_index = first_index;
+  a.sigma = sigma;
+  int W = 4;  // waves per workgroup: their eps slices share 64 KB
+  while (W > 1 && W * slice > 64 * 1024) W >>= 1;
+  const unsigned grid = (unsigned)std::min<i64>(cdiv(N, W), (i64)c->n_cu * 64);
+  {
+    SpanGuard g(c, KID_MISC);
+    generate_kernel<<<grid, 64 * W, W * slice, c->stream>>>(a);
+  }
+  HIP_TRY(hipGetLastError());
+  DBG_SYNC(c, "generate");
+  HIP_TRY(hipStreamSynchronize(c->stream));  // the host arrays are borrowed for the call only
+  c->gen_N = N;
+  c->gen_D = D;
+  c->gen_H = H;
+  c->gen_keep = keep;
+  return 0;
+}
+
+extern "C" int evoamd_download_generated(evoamd_ctx *c, int what, void *out) {
+  REQUIRE(c && out, "evoamd_download_generated: NULL argument");
+  REQUIRE(c->gen_keep >= 0, "evoamd_download_generated: no evoamd_generate call has completed");
+  const size_t nd = (size_t)c->gen_N * c->gen_D * sizeof(double);
+  const void *src = nullptr;
+  size_t bytes = 0;
+  switch (what) {
+    case EVOAMD_GEN_Y: src = c->gen_y, bytes = nd; break;
+    case EVOAMD_GEN_S:
+      REQUIRE(c->gen_keep & EVOAMD_GEN_KEEP_S, "evoamd_download_generated: s was not kept by the last evoamd_generate (keep bit 1)");
+      src = c->gen_s, bytes = (size_t)c->gen_N * ((c->gen_H + 63) / 64) * sizeof(u64);
+      break;
+    case EVOAMD_GEN_Z:
+      REQUIRE(c->gen_keep & EVOAMD_GEN_KEEP_Z, "evoamd_download_generated: z was not kept by the last evoamd_generate (keep bit 2, ES3C only)");
+      src = c->gen_z, bytes = (size_t)c->gen_N * c->gen_H * sizeof(double);
+      break;
+    case EVOAMD_GEN_YMEAN:
+      REQUIRE(c->gen_keep & EVOAMD_GEN_KEEP_YMEAN, "evoamd_download_generated: y_mean was not kept by the last evoamd_generate (keep bit 4)");
+      src = c->gen_ymean, bytes = nd;
+      break;
+    default: return fail(EVOAMD_E_INVALID, "evoamd_download_generated: what must be EVOAMD_GEN_Y, _S, _Z or _YMEAN");
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }

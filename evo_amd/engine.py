@@ -122,6 +122,47 @@ class Engine:
             tp = u8ptr(packed)
         check(self.lib.evoamd_init_states(self._h, float(p_init), int(seed) & (2 ** 64 - 1), int(max_rounds), tp))
 
+    # ---- samples from the model ------------------------------------------------------------
+    def generate(self, model, N, seed, Wt, pies, mus=None, F=None, sigma=1.0, first_index=0, s=None,
+                 keep=("s", "z", "y_mean")):
+        """N samples drawn on the device (evoamd_generate; evo_amd.models.generate_counter is the NumPy mirror): ``Wt``
+        (H, D) = W^T, ``pies`` (H), ES3C ``mus`` (H) and ``F`` (H, H) with F F^T = Psi, ``sigma`` the noise's standard
+        deviation.  ``s`` bool (N, H): taken, not drawn.  ``keep``: which outputs besides y stay on the device for
+        download_generated.  Needs no configure() and leaves a configured EM state untouched."""
+        from .models.generate import pack_words
+        sssc = model not in (MODEL_BSC, "bsc", "BSC")
+        Wt, pies = as_f64(Wt), as_f64(pies)
+        H, D = Wt.shape
+        assert pies.shape == (H,), pies.shape
+        if sssc:
+            mus, F = as_f64(mus), as_f64(F)
+            assert mus.shape == (H,) and F.shape == (H, H), (mus.shape, F.shape)
+        words = None
+        if s is not None:
+            assert np.shape(s) == (int(N), H), (np.shape(s), (int(N), H))
+            words = pack_words(s)
+        bits = 0
+        for name in keep:
+            if name != "y":
+                bits |= _lib.GEN_KEEP[name]
+        check(self.lib.evoamd_generate(
+            self._h, MODEL_SSSC if sssc else MODEL_BSC, int(N), D, H, int(seed) & (2 ** 64 - 1),
+            int(first_index) & (2 ** 64 - 1), dptr(Wt), dptr(pies), dptr(mus) if sssc else None, dptr(F) if sssc else None,
+            float(sigma), None if words is None else words.ctypes.data_as(_lib._c_u64p), bits))
+        self._gen_shape = (int(N), D, H)
+
+    def download_generated(self, what):
+        """One output of the last generate(): "y" / "y_mean" (N, D), "z" (N, H; ES3C), "s" bool (N, H).  EvoAmdError for an
+        output that call did not keep."""
+        from .models.generate import unpack_words
+        N, D, H = getattr(self, "_gen_shape", (1, 1, 1))
+        if what == "s":
+            out = np.empty((N, (H + 63) // 64), dtype=np.uint64)
+        else:
+            out = np.empty((N, H if what == "z" else D), dtype=np.float64)
+        check(self.lib.evoamd_download_generated(self._h, _lib.GEN_WHAT[what], out.ctypes.data_as(ctypes.c_void_p)))
+        return unpack_words(out, H) if what == "s" else out
+
     def upload_lpj(self, lpj):
         lpj = as_f64(lpj)
         assert lpj.shape == (self.N, self.L)

@@ -599,6 +599,34 @@ class Model:
         s = np.random.random(size=(my_N, H_gen)) <= pies
         return self.generate_from_hidden(model_params, {"s": s})
 
+    def generate_data_device(self, model_params, my_N, seed=None, first_index=0, my_hdata=None,
+                             keep=("y", "s", "z", "y_mean")):
+        """``generate_data`` on the device (Engine.generate): the same law, a counter-based stream instead of NumPy's
+        (evo_amd.models.generate_counter reproduces it for ``self.last_generate_seed``: "s" bit for bit, the real-valued
+        outputs to ~1e-13), no loop over the datapoints.  Returns generate_data's dict -- "y", "s" (bool), "y_mean" and, ES3C,
+        "z" -- without the keys that ``keep`` does not name.  ``my_hdata={"s": ...}``: the generate_from_hidden form, s is
+        taken, not drawn.  Datapoint n is index ``first_index + n`` of the data set, so shards of one seed concatenate to
+        the set of a single call.  ``seed`` None: drawn from np.random; rank and world size enter it as in
+        init_resident_states.  BSC reads "pi" and "sigma", ES3C "pies", "mus", "Psi" and "sigma2"; ES3C's z is
+        s o (mus + F eps) with F F^T = Psi from one eigh per call, which has the reference's law N(mus_A, Psi_AA) on every
+        active set and also serves a singular Psi.  Needs no configured engine and leaves a resident run untouched."""
+        from .generate import generate_params
+        keep = tuple(keep)
+        known = ("y", "s", "y_mean") + (("z",) if self.model_name == "sssc" else ())
+        for name in keep:
+            if name not in ("y", "s", "z", "y_mean"):
+                raise ValueError("keep: unknown output %r" % (name,))
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+        self.last_generate_seed = (int(seed) * max(1, self.comm.size) + self.comm.rank) & (2 ** 64 - 1)
+        par = generate_params(self.model_name, model_params)
+        s = None if my_hdata is None else np.asarray(my_hdata["s"], dtype=np.bool_)
+        wanted = [name for name in known if name in keep]
+        eng = self.engine
+        eng.generate(self.model_name, my_N, self.last_generate_seed, par["Wt"], par["pies"], par["mus"], par["F"],
+                     par["sigma"], first_index=first_index, s=s, keep=wanted)
+        return {name: eng.download_generated(name) for name in wanted}
+
     def lpj_reset_check(self, lpj, my_suff_stat):
         """Host mirror of the clamp the kernels apply (_models.py:567-596); used for the permanent
         all-zero column evaluated on the host in free_energy(full=True)."""

@@ -466,6 +466,33 @@ int evoamd_posterior_codes(evoamd_ctx *ctx, int max_active, double p_min, int32_
                            int32_t *nnz, int32_t *map_slot, double *map_q, uint8_t *map_state_packed);
 int evoamd_download_posterior(evoamd_ctx *ctx, double *Es, double *Ez);
 
+/* ---- samples from the model (generate_data / generate_from_hidden: _models.py:73-99, bsc.py:27-57, sssc.py:66-102) ---- */
+/* N datapoints drawn on the device, one wavefront each (csrc/kernels_generate.hpp):
+ *   s_h ~ Bernoulli(pies[h]) (u <= pies[h]; EBSC: the caller fills pies with pi), or s given: s_packed (N x ceil(H/64)
+ *     64-bit words, latent h in word h/64 at bit 63-(h%64), the device layout of K^n) is taken, not drawn;
+ *   ES3C  z = s o (mus + F eps), eps ~ N(0, I_H), with F (H x H row-major) any matrix with F F^T = Psi -- the marginal on the
+ *     active set A is N(mus_A, Psi_AA), the reference's law, without a factorisation per datapoint (evo_amd.models forms
+ *     F = V sqrt(max(lambda, 0)) from eigh(Psi), which also serves a singular Psi);   EBSC  z = s, mus = F = NULL;
+ *   y_mean = W z (Wt is W^T, H x D row-major),   y = y_mean + sigma g, g ~ N(0, I_D)   (ES3C: sigma = sqrt(sigma2)).
+ * The stream is counter-based: datapoint n of the call is index first_index + n of the data set, so a set generated in
+ * shards is the same set; s_h = rng_u01(seed, index, GEN_PURPOSE + 0, h) <= pies[h], eps_j / g_d = Box-Muller normal number
+ * j / d of purpose GEN_PURPOSE + 1 / + 2 (kernels_generate.hpp has the definition; evo_amd.models.generate_counter is the
+ * NumPy mirror: s bit for bit, the real-valued outputs to the last places of log / sincos).  Every sum has a fixed order:
+ * a call repeats bit for bit.
+ * keep: bits EVOAMD_GEN_KEEP_S | _Z | _YMEAN -- which outputs besides y are stored (z: ES3C only, the bit is ignored for
+ * EBSC).  The outputs stay in device buffers of the context (grown on demand, freed by evoamd_ctx_destroy) until the next
+ * evoamd_generate; evoamd_download_generated copies one to the host: what = EVOAMD_GEN_Y (N x D double), _S (N x ceil(H/64)
+ * uint64), _Z (N x H double), _YMEAN (N x D double); EVOAMD_E_INVALID for an output the last call did not keep.
+ * Needs no evoamd_configure and leaves the EM state of a configured context (Y, K^n, Theta, masks, lpj, statistics)
+ * untouched.  H above 8192 (ES3C: the eps values of a datapoint no longer fit 64 KB of LDS) returns EVOAMD_E_INVALID.
+ * Both calls have completed on return. */
+enum { EVOAMD_GEN_KEEP_S = 1, EVOAMD_GEN_KEEP_Z = 2, EVOAMD_GEN_KEEP_YMEAN = 4 };
+enum { EVOAMD_GEN_Y = 0, EVOAMD_GEN_S = 1, EVOAMD_GEN_Z = 2, EVOAMD_GEN_YMEAN = 3 };
+int evoamd_generate(evoamd_ctx *ctx, int model, int64_t N, int D, int H, uint64_t seed, uint64_t first_index,
+                    const double *Wt, const double *pies, const double *mus_or_null, const double *F_or_null, double sigma,
+                    const uint64_t *s_packed_or_null, int keep);
+int evoamd_download_generated(evoamd_ctx *ctx, int what, void *out);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------------- */
 /* 128-byte opaque id made by rank 0 and distributed by the caller (file / socket / MPI). */
 int evoamd_comm_unique_id(uint8_t id_out[128]);
