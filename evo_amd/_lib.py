@@ -80,6 +80,7 @@ SIGNATURES = {
     "evoamd_get_params_sssc": (_I, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "evoamd_restore_theta_backup": (_I, [_vp]),
     "evoamd_free_energy": (_I, [_vp, _c_dp, _I64, _I, _c_dp]),
+    "evoamd_loglik_exact": (_I, [_vp, _I, _I, _c_dp, _c_dp, _c_dp]),
     "evoamd_set_estep_counts": (_I, [_vp, _DBL, _DBL]),
     "evoamd_patches_extract": (_I, [_vp, _c_dp, _I, _I, _I, _I, _I, _I, _c_dp]),
     "evoamd_patches_merge": (_I, [_vp, _c_dp, _I, _I, _I, _I, _I, _I, _I, _c_dp]),

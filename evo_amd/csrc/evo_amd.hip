@@ -28,6 +28,7 @@
 #include "kernels_codes.hpp"
 #include "kernels_init.hpp"
 #include "kernels_generate.hpp"
+#include "kernels_exact.hpp"
 
 // ---------------------------------------------------------------------------------------
 // error handling
@@ -382,6 +383,9 @@ struct evoamd_ctx {
   double *tmp_y = nullptr, *tmp_lpj = nullptr;
   u64 *tmp_states = nullptr;
   size_t tmp_states_words = 0, tmp_lpj_n = 0;
+  // evoamd_loglik_exact: running maximum / sum / marginal sums per datapoint and the outputs (one allocation, grown on demand)
+  double *exact_buf = nullptr;
+  size_t exact_n = 0;
   // evoamd_patches_*: image and patch rows on the device, grown on demand (never the EM state above)
   double *patch_img = nullptr, *patch_Y = nullptr;
   size_t patch_img_n = 0, patch_Y_n = 0;
@@ -614,7 +618,7 @@ static void free_all(evoamd_ctx *c) {
                   c->pbins.ent, c->pbins.part, c->pbins.gcnt, c->gemm_ws, c->Yt, c->Yf, c->Ytf, c->Wf, c->Bf, c->Esf,
                   c->clist, c->clist_n, c->ovf_rec, c->theta_bak, c->rowF, c->rowcnt, c->defer, c->fpart, c->huge, c->huge_ctl,
                   c->patch_img, c->patch_Y, c->keep_x, c->row_any, c->codes_buf, c->init_scratch,
-                  c->gen_par, c->gen_y, c->gen_z, c->gen_ymean, c->gen_sin, c->gen_s};
+                  c->gen_par, c->gen_y, c->gen_z, c->gen_ymean, c->gen_sin, c->gen_s, c->exact_buf};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (c->h_acc) (void)hipHostFree(c->h_acc);
@@ -4571,6 +4575,95 @@ extern "C" int evoamd_free_energy(evoamd_ctx *c, const double *lpj, int64_t N, i
   }
   (void)hipFree(d);
   return r;
+}
+
+// ---------------------------------------------------------------------------------------
+// exact log-likelihood over all 2^Hv states (kernels_exact.hpp): own scratch + the shared-batch scratch, no EM state touched
+// ---------------------------------------------------------------------------------------
+extern "C" int evoamd_loglik_exact(evoamd_ctx *c, int background, int chunk_states, double *ll_out, double *marg_out,
+                                   double *Fs_out) {
+  REQUIRE(c && c->configured && c->have_data && c->have_params, "configure, upload_data and set_params first");
+  REQUIRE(Fs_out, "evoamd_loglik_exact: Fs_out is NULL");
+  REQUIRE(background == 0 || background == 1, "evoamd_loglik_exact: background must be 0 or 1");
+  const int H = c->H, Hv = H - background;
+  if (Hv < 1 || Hv > EXACT_MAX_HV)
+    return fail(EVOAMD_E_INVALID, "evoamd_loglik_exact: %d latents vary (H = %d, background = %d); 1 .. %d can be enumerated",
+                Hv, H, background, EXACT_MAX_HV);
+  const i64 N = c->N;
+  const u64 total = 1ull << Hv;  // indices 0 .. 2^Hv - 1 (without background, index 0 is the permanent all-zero state)
+  i64 C = chunk_states;
+  if (chunk_states != 0) {
+    REQUIRE(chunk_states >= 64 && (chunk_states & (chunk_states - 1)) == 0,
+            "evoamd_loglik_exact: chunk_states must be 0 (automatic) or a power of two >= 64");
+    REQUIRE(N * C < 2147483647LL, "evoamd_loglik_exact: N * chunk_states must fit in int32");
+  } else {
+    C = 65536;
+    while (C > 64 && (N * C * (i64)sizeof(double) > (512ll << 20) || N * C >= 2147483647LL)) C >>= 1;
+    REQUIRE(N * C < 2147483647LL, "evoamd_loglik_exact: N * 64 must fit in int32");
+    while (C > 64 && (u64)(C >> 1) >= total) C >>= 1;  // no larger than the index space needs
+  }
+  int logC = 0;
+  while ((1ll << logC) < C) logC++;
+  const int cmax = (u64)C < total ? (int)C : (int)total;  // states of the largest chunk (Hv < 6: one partial chunk)
+  HIP_TRY(hipSetDevice(c->device));
+  int r = ensure_tmp(c, (size_t)cmax * c->HW, (size_t)N * cmax);
+  if (r) return r;
+  r = ensure_B(c);
+  if (r) return r;
+  if (c->model == EVOAMD_MODEL_SSSC) {
+    r = ensure_lists(c, N * cmax);
+    if (r) return r;
+  }
+  // m (N) | z (N) | ll (N) | Fs (1) | partial (ceil(N / 4)) | a (N x Hv) | marg (N x H)
+  const unsigned nb = cdiv(N, 4);
+  const size_t need = (size_t)3 * N + 1 + nb + (size_t)N * Hv + (size_t)N * H;
+  if (need > c->exact_n) {
+    ALLOC(c->exact_buf, need);
+    c->exact_n = need;
+  }
+  double *run_m = c->exact_buf, *run_z = run_m + N, *d_ll = run_z + N, *d_Fs = d_ll + N, *d_part = d_Fs + 1;
+  double *run_a = marg_out ? d_part + nb : nullptr, *d_marg = marg_out ? d_part + nb + (size_t)N * Hv : nullptr;
+  unsigned *flags = c->flags + c->N;  // the clamp flag words evoamd_lpj_shared borrows
+  {
+    SpanGuard g(c, KID_MISC);
+    if (!background)
+      allzero_lpj_kernel<<<cdiv(N, 256), 256, 0, c->stream>>>(c->yy, N, c->dpar, c->model == EVOAMD_MODEL_SSSC, run_m, 1,
+                                                              flags, c->err);
+    exact_seed_kernel<<<cdiv(N, 256), 256, 0, c->stream>>>(run_m, run_z, run_a, N, Hv, background);
+    HIP_TRY(hipGetLastError());
+  }
+  const LevelHints lv = batch_hints(c, 2);
+  for (u64 g0 = 0; g0 < total; g0 += (u64)C) {
+    const int cnt = total - g0 < (u64)C ? (int)(total - g0) : (int)C;
+    {
+      SpanGuard g(c, KID_MISC);
+      exact_enumerate_kernel<<<cdiv(cnt, 256), 256, 0, c->stream>>>(c->tmp_states, g0, cnt, Hv, c->HW, background);
+      HIP_TRY(hipGetLastError());
+    }
+    Batch b = {c->tmp_states, nullptr, c->Y, c->Bm, c->yy, N, cnt, 1, c->tmp_lpj, cnt, 0, flags, KID_MISC, 2};
+    b.mask = c->mask_infr;
+    r = launch_lpj(c, b, lv);
+    if (r) return r;
+    SpanGuard g(c, KID_MISC);
+    if (marg_out)
+      exact_fold_kernel<true><<<nb, 256, 0, c->stream>>>(c->tmp_lpj, cnt, N, g0, cnt, logC, Hv, !background, run_m, run_z, run_a);
+    else
+      exact_fold_kernel<false><<<nb, 256, 0, c->stream>>>(c->tmp_lpj, cnt, N, g0, cnt, logC, Hv, !background, run_m, run_z, run_a);
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "exact log-likelihood chunk");
+  }
+  {
+    SpanGuard g(c, KID_MISC);
+    exact_finish_kernel<<<nb, 256, 0, c->stream>>>(run_m, run_z, run_a, N, Hv, H, d_ll, d_marg, d_part);
+    reduce_partials_kernel<<<1, 256, 0, c->stream>>>(d_part, nb, d_Fs, 0);
+    HIP_TRY(hipGetLastError());
+  }
+  if (ll_out) HIP_TRY(hipMemcpyAsync(ll_out, d_ll, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (marg_out) HIP_TRY(hipMemcpyAsync(marg_out, d_marg, (size_t)N * H * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(Fs_out, d_Fs, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (c->model == EVOAMD_MODEL_SSSC) return check_err(c);  // synchronises the stream
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------

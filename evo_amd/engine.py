@@ -382,6 +382,20 @@ class Engine:
         check(self.lib.evoamd_free_energy(self._h, dptr(lpj), lpj.shape[0], lpj.shape[1], ctypes.byref(out)))
         return out.value
 
+    def loglik_exact(self, background=False, chunk_states=0, per_datapoint=True, marginals=False):
+        """Exact log-likelihood terms over all states of the H - background latents that vary (evoamd_loglik_exact; at
+        most 32), enumerated on the device in chunks of ``chunk_states`` (0 = automatic) and folded into a running
+        log-sum-exp per datapoint.  Returns (Fs, ll, marg): Fs = sum_n ll_n, ll (N) = logsumexp_s lpj_ns when
+        ``per_datapoint``, marg (N, H) = E_p[s_h | y_n] when ``marginals``, else None.  Needs data and Theta on the
+        device; K^n and everything else of the EM state stay as they are."""
+        ll = np.empty(self.N) if per_datapoint else None
+        marg = np.empty((self.N, self.H)) if marginals else None
+        Fs = ctypes.c_double()
+        check(self.lib.evoamd_loglik_exact(self._h, 1 if background else 0, int(chunk_states),
+                                           None if ll is None else dptr(ll), None if marg is None else dptr(marg),
+                                           ctypes.byref(Fs)))
+        return Fs.value, ll, marg
+
     def acc_views(self, acc):
         return acc_views(acc, self.model, self.D, self.H)
 

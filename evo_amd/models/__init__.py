@@ -2,3 +2,4 @@ from ._models import Model  # noqa: F401
 from .bsc import BSC  # noqa: F401
 from .sssc import SSSC  # noqa: F401
 from .generate import generate_counter  # noqa: F401
+from .exact import enumerate_chunk, fold_exact  # noqa: F401

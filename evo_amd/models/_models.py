@@ -837,6 +837,38 @@ class Model:
         Fs = self.engine.free_energy_sum(lpj)
         return model_params["ljc"] + self.comm.allreduce(Fs) / N
 
+    def exact_log_likelihood(self, my_data, model_params, my_suff_stat, per_datapoint=False, marginals=False,
+                             max_H=24, chunk_states=0):
+        """The exact log-likelihood over all states, the quantity ``free_energy(full=True)`` returns, without its
+        H < 12 cap: no state table is built (``my_suff_stat["sm"]`` is ignored).  The device enumerates the states of
+        the Hv = H - background latents that vary in chunks of ``chunk_states`` (0 = automatic), evaluates each chunk
+        against every datapoint and folds it into a running log-sum-exp per datapoint (Engine.loglik_exact).  The
+        work grows with 2^Hv: more than ``max_H`` (itself at most 32) varying latents raise ValueError before anything
+        runs.  Returns L = ljc + allreduce(sum_n ll_n) / N; with ``per_datapoint`` / ``marginals`` set, (L, ll, marg)
+        with this rank's ll (N_loc,) = log p(y_n | Theta) - ljc and the exact posterior marginals marg (N_loc, H) =
+        E_p[s_h | y_n] -- the ground truth of ``encode(...).p`` -- for the flags set, None otherwise.  Writes nothing
+        into the three dicts and leaves K^n and the rest of the EM state on the device as they are."""
+        from .exact import MAX_HV
+        background = bool(my_suff_stat["permanent"]["background"])
+        Hv = self.H - (1 if background else 0)
+        if max_H > MAX_HV:
+            raise ValueError("exact_log_likelihood: max_H = %d, at most %d latents can be enumerated" % (max_H, MAX_HV))
+        if Hv < 1 or Hv > max_H:
+            raise ValueError("exact_log_likelihood: %d latents vary, that is 2^%d = %d states per datapoint; "
+                             "max_H = %d allows 2^%d (raise max_H to run it anyway)" % (Hv, Hv, 2 ** Hv, max_H, max_H))
+        N_loc = my_data["y"].shape[0]
+        N = self.comm.allreduce(N_loc)
+        eng = self._prepare(my_suff_stat, my_data, upload_states=False)
+        theta = dict(model_params)  # (the precompute stores its derived keys and zeroes the reset counters: on copies)
+        self.E_step_precompute(theta, dict(my_suff_stat), my_data)
+        if model_params is not self._dev_theta:
+            self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
+        Fs, ll, marg = eng.loglik_exact(background, chunk_states, per_datapoint=per_datapoint, marginals=marginals)
+        L = theta["ljc"] + self.comm.allreduce(Fs) / N
+        if per_datapoint or marginals:
+            return L, ll, marg
+        return L
+
     def reconstruct(self, my_data, my_suff_stat, model_params):
         """(Re-)estimate the entries with my_data["x"] False from the posterior predictive distribution under
         ``model_params`` and the caller's K^n / lpj; adds my_data["y_reconstructed"] (_models.py:614-665).

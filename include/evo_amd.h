@@ -396,6 +396,19 @@ int evoamd_estep(evoamd_ctx *ctx, int n_parents, int n_children, uint64_t seed, 
 int evoamd_estep_counters(evoamd_ctx *ctx, int64_t out[4]);
 /* Fs only (sum_n logsumexp) of an arbitrary host lpj matrix (N,C) -- exact-likelihood path. */
 int evoamd_free_energy(evoamd_ctx *ctx, const double *lpj, int64_t N, int C, double *Fs_out);
+/* Exact log-likelihood terms over ALL states of the Hv = H - background latents that vary (1 <= Hv <= 32), without a
+ * state table and without an N x 2^Hv array: the states are produced on the device in chunks of `chunk_states` (a power
+ * of two >= 64; 0 = automatic: N x chunk doubles <= 512 MB, chunk <= 65536), each chunk is evaluated like an
+ * evoamd_lpj_shared batch (same preconditions: configure, upload_data, set_params_*; incomplete data included) and
+ * folded into a running log-sum-exp per datapoint.  background = 0: all 2^Hv states, the all-zero state's term as the
+ * permanent state's (the reference's forced S_perm = 1, _models.py:366-373); background = 1: every state of the first
+ * H - 1 latents with latent H - 1 on, no all-zero term (_models.py:389-390).  State index g has latent h on iff bit h of g.
+ * ll_out (N, may be NULL): ll_n = logsumexp_s lpj_ns;  marg_out (N x H, may be NULL): the exact posterior marginals
+ * E_p[s_h | y_n] (the background unit's column is 1);  *Fs_out = sum_n ll_n, summed in a fixed order.  Two calls with
+ * the same inputs and chunk size give the same bits.  K^n, lpj, candidates, statistics rows, a prefetched pass and the
+ * resident reconstruction stay as they are.  EVOAMD_E_SINGULAR / EVOAMD_E_KLIMIT as for evoamd_lpj_shared. */
+int evoamd_loglik_exact(evoamd_ctx *ctx, int background, int chunk_states, double *ll_out, double *marg_out,
+                        double *Fs_out);
 /* Adds the E-step scalars produced outside evoamd_stats (e.g. host-side vary_Kn counts)
  * into the accumulator tail before the all-reduce. */
 int evoamd_set_estep_counts(evoamd_ctx *ctx, double sum_nunique, double sum_sub);
