@@ -84,11 +84,14 @@ SIGNATURES = {
     "evoamd_set_estep_counts": (_I, [_vp, _DBL, _DBL]),
     "evoamd_patches_extract": (_I, [_vp, _c_dp, _I, _I, _I, _I, _I, _I, _c_dp]),
     "evoamd_patches_merge": (_I, [_vp, _c_dp, _I, _I, _I, _I, _I, _I, _I, _c_dp]),
+    "evoamd_patches_merge_weighted": (_I, [_vp, _c_dp, _c_dp, _I, _I, _I, _I, _I, _I, _c_dp]),
     "evoamd_reconstruct_resident": (_I, [_vp, _c_u8p]),
     "evoamd_patches_merge_resident": (_I, [_vp, _I, _I, _I, _I, _I, _I, _I, _c_dp]),
     "evoamd_download_reconstruction": (_I, [_vp, _c_dp]),
     "evoamd_posterior_codes": (_I, [_vp, _I, _DBL, _c_i32p, _c_dp, _c_dp, _c_i32p, _c_i32p, _c_dp, _c_u8p]),
     "evoamd_download_posterior": (_I, [_vp, _c_dp, _c_dp]),
+    "evoamd_predictive_moments": (_I, [_vp, _I, ctypes.POINTER(_I64)]),
+    "evoamd_download_predictive": (_I, [_vp, _c_dp, _c_dp]),
     "evoamd_generate": (_I, [_vp, _I, _I64, _I, _I, _U64, _U64, _c_dp, _c_dp, _c_dp, _c_dp, _DBL, _c_u64p, _I]),
     "evoamd_download_generated": (_I, [_vp, _I, _vp]),
     "evoamd_comm_unique_id": (_I, [_c_u8p]),

@@ -29,6 +29,7 @@
 #include "kernels_init.hpp"
 #include "kernels_generate.hpp"
 #include "kernels_exact.hpp"
+#include "kernels_predictive.hpp"
 
 // ---------------------------------------------------------------------------------------
 // error handling
@@ -389,6 +390,15 @@ struct evoamd_ctx {
   // evoamd_patches_*: image and patch rows on the device, grown on demand (never the EM state above)
   double *patch_img = nullptr, *patch_Y = nullptr;
   size_t patch_img_n = 0, patch_Y_n = 0;
+  double *patch_V = nullptr;  // evoamd_patches_merge_weighted: the variances of the patch rows
+  size_t patch_V_n = 0;
+  // evoamd_predictive_moments (kernels_predictive.hpp): mean | var (N x D each), the status word per datapoint and W^T
+  // (H x D, transposed from W by every call), grown on demand (never the EM state above); pred_N = 0: nothing to download
+  double *pred_buf = nullptr, *pred_Wt = nullptr;
+  int *pred_status = nullptr;
+  size_t pred_buf_n = 0, pred_Wt_n = 0, pred_status_n = 0;
+  i64 pred_N = 0;
+  int pred_D = 0;
   // evoamd_posterior_codes: the compact outputs on the device (one allocation, grown on demand); rows_kn_gen = the K^n
   // the rows of the last statistics pass were formed from; option "codes_path" (-1 automatic, else CODES_REG / _LDS / _GMEM)
   uint8_t *codes_buf = nullptr;
@@ -586,6 +596,12 @@ extern "C" int evoamd_ctx_create(int device, evoamd_ctx **out) {
   HIP_TRY(hipFuncSetAttribute((const void *)gemm_tn128_store_f32, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)GEMM128_LDS_BYTES));
   {
+    const int lds = (int)(PRED_WAVES * pred_lds_doubles(PRED_MAX_K, true) * sizeof(double));
+    const void *pk[] = {(const void *)predictive_kernel<1, true>, (const void *)predictive_kernel<2, true>,
+                        (const void *)predictive_kernel<4, true>, (const void *)predictive_kernel<8, true>};
+    for (const void *f : pk) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  }
+  {
     const void *wk[] = {(const void *)sssc_stats_wave_kernel<0, 4>,  (const void *)sssc_stats_wave_kernel<1, 4>,
                         (const void *)sssc_stats_wave_kernel<2, 4>,  (const void *)sssc_stats_wave_kernel<4, 4>,
                         (const void *)sssc_stats_wave_kernel<8, 4>,  (const void *)sssc_stats_wave_kernel<16, 4>,
@@ -618,7 +634,8 @@ static void free_all(evoamd_ctx *c) {
                   c->pbins.ent, c->pbins.part, c->pbins.gcnt, c->gemm_ws, c->Yt, c->Yf, c->Ytf, c->Wf, c->Bf, c->Esf,
                   c->clist, c->clist_n, c->ovf_rec, c->theta_bak, c->rowF, c->rowcnt, c->defer, c->fpart, c->huge, c->huge_ctl,
                   c->patch_img, c->patch_Y, c->keep_x, c->row_any, c->codes_buf, c->init_scratch,
-                  c->gen_par, c->gen_y, c->gen_z, c->gen_ymean, c->gen_sin, c->gen_s, c->exact_buf};
+                  c->gen_par, c->gen_y, c->gen_z, c->gen_ymean, c->gen_sin, c->gen_s, c->exact_buf,
+                  c->patch_V, c->pred_buf, c->pred_Wt, c->pred_status};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (c->h_acc) (void)hipHostFree(c->h_acc);
@@ -1070,6 +1087,10 @@ extern "C" int evoamd_configure(evoamd_ctx *c, int model, int64_t N, int D, int 
       HIP_TRY(hipMemsetAsync(c->Ytf, 0, (size_t)D * c->ldYt * sizeof(float), c->stream));
     }
   } else {
+    // W^T (incomplete data) is sized by (H, D) of the geometry it was built for: rebuilt on demand (evoamd_upload_masks,
+    // derive_from_theta), never reused across a configure -- a larger D would write past its end
+    if (c->Wt) (void)hipFree(c->Wt);
+    c->Wt = nullptr;
     ALLOC(c->G, (size_t)H * H);
     ALLOC(c->Psi, (size_t)H * H);
     ALLOC(c->GP, (size_t)H * H);
@@ -1163,6 +1184,7 @@ extern "C" int evoamd_configure(evoamd_ctx *c, int model, int64_t N, int D, int 
   c->theta_bak_valid = false;
   c->lists_clean = c->need_known = c->cand_from_device = false;  // fresh (uninitialised) overflow counters
   c->kn_lost = false;
+  c->pred_N = 0;
   c->init_scratch_words = 0;
   if (c->init_scratch) (void)hipFree(c->init_scratch);
   c->init_scratch = nullptr;
@@ -4749,6 +4771,31 @@ extern "C" int evoamd_patches_merge(evoamd_ctx *c, const double *Y, int H, int W
   return launch_patches_merge(c, PatchRows{c->patch_Y}, g, method, img_out);
 }
 
+extern "C" int evoamd_patches_merge_weighted(evoamd_ctx *c, const double *Y, const double *V, int H, int W, int C, int ph, int pw,
+                                             int shift, double *img_out) {
+  REQUIRE(c && Y && V && img_out, "evoamd_patches_merge_weighted: NULL argument");
+  PatchGeom g;
+  if (const char *msg = patch_geom_make(H, W, C, ph, pw, shift, &g)) return fail(EVOAMD_E_INVALID, "evoamd_patches_merge_weighted: %s", msg);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t img_n = (size_t)H * W * C, y_n = (size_t)g.N * g.D;
+  int r = ensure_patch_scratch(c, img_n, y_n);
+  if (r) return r;
+  if (y_n > c->patch_V_n) {
+    ALLOC(c->patch_V, y_n);
+    c->patch_V_n = y_n;
+  }
+  HIP_TRY(hipMemcpyAsync(c->patch_Y, Y, y_n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->patch_V, V, y_n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  {
+    SpanGuard sg(c, KID_PATCHES);
+    patches_wmean_kernel<<<cdiv((i64)img_n, 256), 256, 0, c->stream>>>(PatchRows{c->patch_Y}, PatchRows{c->patch_V}, g, c->patch_img);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(img_out, c->patch_img, img_n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 // ---- the selected reconstruction, resident (evoamd_reconstruct_resident / evoamd_patches_merge_resident) ----
 static const char *const REC_OUTDATED =
     "no current resident reconstruction: call evoamd_reconstruct_resident after the statistics pass (a later statistics "
@@ -4924,6 +4971,121 @@ extern "C" int evoamd_download_posterior(evoamd_ctx *c, double *Es, double *Ez) 
     if (Es) HIP_TRY(hipMemcpy2DAsync(Es, w, c->Y + c->D, pitch, w, (size_t)c->N, hipMemcpyDeviceToHost, c->stream));
     if (Ez) HIP_TRY(hipMemcpy2DAsync(Ez, w, c->Y + c->D + c->H, pitch, w, (size_t)c->N, hipMemcpyDeviceToHost, c->stream));
   }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// predictive moments (kernels_predictive.hpp): own buffers; of the EM state only B = Y W is (re)formed, like every lpj pass
+// ---------------------------------------------------------------------------------------
+template <bool SSSC>
+static void launch_predictive(evoamd_ctx *c, const PredArgs &a, int R, size_t lds) {
+  const unsigned grid = cdiv(a.N, PRED_WAVES);
+  switch (R) {
+    case 1: predictive_kernel<1, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(a); break;
+    case 2: predictive_kernel<2, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(a); break;
+    case 4: predictive_kernel<4, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(a); break;
+    default: predictive_kernel<8, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(a); break;
+  }
+}
+
+extern "C" int evoamd_predictive_moments(evoamd_ctx *c, int add_noise, int64_t counters[2]) {
+  REQUIRE(c && c->configured && c->have_data && c->have_params,
+          "evoamd_predictive_moments: configure, upload data and set parameters first");
+  REQUIRE(!c->f32, "evoamd_predictive_moments is not available in the float32 mode");
+  REQUIRE_KN(c);
+  REQUIRE(counters, "evoamd_predictive_moments: counters is NULL");
+  if (c->D > 64 * PRED_R_MAX)
+    return fail(EVOAMD_E_INVALID, "evoamd_predictive_moments: D = %d, at most %d observables are supported (64 lanes x %d registers)",
+                c->D, 64 * PRED_R_MAX, PRED_R_MAX);
+  HIP_TRY(hipSetDevice(c->device));
+  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
+  const i64 N = c->N;
+  const int D = c->D, H = c->H;
+  c->pred_N = 0;
+  if (sssc) {
+    int r = ensure_B(c);
+    if (r) return r;
+  }
+  const size_t nd = (size_t)N * D;
+  if (2 * nd > c->pred_buf_n || (size_t)H * D > c->pred_Wt_n || (size_t)N > c->pred_status_n)
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  if (2 * nd > c->pred_buf_n) {
+    c->pred_buf_n = 0;
+    ALLOC(c->pred_buf, 2 * nd);
+    c->pred_buf_n = 2 * nd;
+  }
+  if ((size_t)H * D > c->pred_Wt_n) {
+    c->pred_Wt_n = 0;
+    ALLOC(c->pred_Wt, (size_t)H * D);
+    c->pred_Wt_n = (size_t)H * D;
+  }
+  if ((size_t)N > c->pred_status_n) {
+    c->pred_status_n = 0;
+    ALLOC(c->pred_status, (size_t)N);
+    c->pred_status_n = (size_t)N;
+  }
+  // the scalars of the current Theta (a device update leaves them in the scalar block only)
+  double dpar[DP_COUNT];
+  HIP_TRY(hipMemcpyAsync(dpar, c->dpar, DP_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  PredArgs a = {};
+  a.mask = c->mask_infr;
+  a.row_any = c->mask_infr ? c->row_any : nullptr;
+  a.lpj = c->lpj;
+  a.states = c->states;
+  a.Wt = c->pred_Wt;
+  a.G = c->G;
+  a.Psi = c->Psi;
+  a.mus = c->mus;
+  a.Bm = c->Bm;
+  a.N = N;
+  a.D = D, a.H = H, a.HW = c->HW, a.S = c->S, a.S_perm = c->S_perm, a.L = c->L;
+  a.kcap = H < PRED_MAX_K ? H : PRED_MAX_K;
+  a.bg = c->bg_unit;
+  a.sigma2 = sssc ? dpar[DP_SIGMA2] : dpar[DP_SIGMA] * dpar[DP_SIGMA];
+  a.add_noise = add_noise ? 1 : 0;
+  a.mean = c->pred_buf;
+  a.var = c->pred_buf + nd;
+  a.status = c->pred_status;
+  int R = 1;
+  while (64 * R < D) R <<= 1;
+  const size_t lds = PRED_WAVES * pred_lds_doubles(a.kcap, sssc) * sizeof(double);
+  {
+    SpanGuard g(c, KID_MISC);
+    transpose_kernel<<<cdiv((i64)H * D, 256), 256, 0, c->stream>>>(c->W, D, H, c->pred_Wt);
+    if (sssc)
+      launch_predictive<true>(c, a, R, lds);
+    else
+      launch_predictive<false>(c, a, R, lds);
+  }
+  HIP_TRY(hipGetLastError());
+  std::vector<int> status((size_t)N);
+  HIP_TRY(hipMemcpyAsync(status.data(), c->pred_status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  counters[0] = counters[1] = 0;
+  for (i64 n = 0; n < N; n++) {
+    const int st = status[(size_t)n];
+    if ((st & 0xFF) == PRED_OVER_K)
+      return fail(EVOAMD_E_INVALID, "evoamd_predictive_moments: datapoint n = %lld holds a state with k = %d active latents, "
+                  "at most %d are supported (PRED_MAX_K)", (long long)n, st >> 8, PRED_MAX_K);
+    counters[0] += st == PRED_SINGULAR;
+    counters[1] += st == PRED_SKIPPED;
+  }
+  c->pred_N = N;
+  c->pred_D = D;
+  return 0;
+}
+
+extern "C" int evoamd_download_predictive(evoamd_ctx *c, double *mean, double *var) {
+  REQUIRE(c, "evoamd_download_predictive: ctx is NULL");
+  REQUIRE(c->configured && c->pred_N > 0 && c->pred_N == c->N && c->pred_D == c->D,
+          "evoamd_download_predictive: no results on the device (call evoamd_predictive_moments first; a failed call and "
+          "evoamd_configure drop them)");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t nd = (size_t)c->pred_N * c->pred_D;
+  if (mean) HIP_TRY(hipMemcpyAsync(mean, c->pred_buf, nd * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (var) HIP_TRY(hipMemcpyAsync(var, c->pred_buf + nd, nd * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -168,6 +168,37 @@ __global__ void __launch_bounds__(256) patches_mean_kernel(Src src, PatchGeom g,
   out[e] = cnt ? sum / (double)cnt : __builtin_nan("");
 }
 
+// Precision-weighted mean merge: out = (sum_k e_k w_k) / (sum_k w_k), w_k = 1 / v_k, over the covering patches in
+// increasing n; multiply and add are separate IEEE operations (no contraction), both sums start from 0.0.  An estimate
+// that is NaN, or whose variance is NaN or <= 0, is skipped; no valid estimate gives NaN.  One thread per output element,
+// like the mean merge; bit-identical to evo_amd.utils.prepost.PrecisionMerger.
+__global__ void __launch_bounds__(256) patches_wmean_kernel(PatchRows est, PatchRows var, PatchGeom g, double *__restrict__ out) {
+#pragma clang fp contract(off)
+  const i64 total = (i64)g.H * g.W * g.C;
+  const i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const int c = (int)(e % g.C);
+  const i64 px = e / g.C;
+  const int y = (int)(px / g.W), x = (int)(px - (i64)y * g.W);
+  int r0, r1, c0, c1;
+  patch_cover(y, g.H, g.ph, g.s, g.nr, r0, r1);
+  patch_cover(x, g.W, g.pw, g.s, g.nc, c0, c1);
+  double num = 0.0, den = 0.0;
+  int cnt = 0;
+  for (int ir = r0; ir <= r1; ir++)
+    for (int ic = c0; ic <= c1; ic++) {
+      const double v = patch_estimate(est, g, ir, ic, y, x, c);
+      const double s = patch_estimate(var, g, ir, ic, y, x, c);
+      if (v == v && s > 0.0) {  // (s > 0 is false for NaN)
+        const double w = 1.0 / s;
+        num += v * w;
+        den += w;
+        cnt++;
+      }
+    }
+  out[e] = cnt ? num / den : __builtin_nan("");
+}
+
 // Median merge: a bitonic sort of every output element's estimates across the lanes of a wave (and, for more than 64
 // estimates, across R registers per lane: element index = r * 64 + lane).  R = 1: segments of P lanes (P = the power of
 // two >= the largest estimate count, <= 64), 64 / P output elements per wave; R > 1: P = 64 R, one element per wave.

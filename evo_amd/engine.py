@@ -433,15 +433,28 @@ class Engine:
         check(self.lib.evoamd_patches_extract(self._h, dptr(img), H, W, C, int(ph), int(pw), int(shift), dptr(Y)))
         return Y
 
-    def patches_merge(self, Y, shape, ph, pw, shift=1, method="mean"):
+    def patches_merge(self, Y, shape, ph, pw, shift=1, method="mean", weights=None):
         """Y (N, D) -> image of ``shape`` ((H, W) or (H, W, C)), every element the NaN-skipping mean / median of its
-        estimates.  A C-contiguous float64 Y (e.g. the transpose of an F-ordered (D, N) array) is passed without a copy."""
+        estimates.  A C-contiguous float64 Y (e.g. the transpose of an F-ordered (D, N) array) is passed without a copy.
+        method="precision" with ``weights`` = the (N, D) variances V of the estimates: the precision-weighted mean
+        (sum e / v) / (sum 1 / v), estimates that are NaN or whose variance is NaN or <= 0 skipped
+        (evo_amd.utils.prepost.PrecisionMerger is the host mirror, bit for bit)."""
         from .utils.prepost import patch_geometry
         H, W, C = _image_hwc(shape)
         N, D = patch_geometry(H, W, C, ph, pw, shift)
         Y = as_f64(Y)
         if Y.shape != (N, D):
             raise ValueError("patches_merge: Y has shape %s, the geometry needs (%d, %d)" % (Y.shape, N, D))
+        if (method == "precision") != (weights is not None):
+            raise ValueError("patches_merge: method='precision' and weights (the variances) go together")
+        if method == "precision":
+            V = as_f64(weights)
+            if V.shape != (N, D):
+                raise ValueError("patches_merge: weights have shape %s, the geometry needs (%d, %d)" % (V.shape, N, D))
+            out = np.empty(tuple(shape), dtype=np.float64)
+            check(self.lib.evoamd_patches_merge_weighted(self._h, dptr(Y), dptr(V), H, W, C, int(ph), int(pw), int(shift),
+                                                         dptr(out)))
+            return out
         m = {"mean": 0, "median": 1}[method]
         out = np.empty(tuple(shape), dtype=np.float64)
         check(self.lib.evoamd_patches_merge(self._h, dptr(Y), H, W, C, int(ph), int(pw), int(shift), m, dptr(out)))
@@ -526,6 +539,21 @@ class Engine:
         Ez = np.empty((self.N, self.H)) if self.model == MODEL_SSSC else None
         check(self.lib.evoamd_download_posterior(self._h, dptr(Es), None if Ez is None else dptr(Ez)))
         return Es, Ez
+
+    # ---- predictive uncertainty (evo_amd.models.predictive is the NumPy mirror) -----------------
+    def predictive_moments(self, noise=True, want_mean=True, want_var=True):
+        """Posterior-predictive mean and variance of every entry under the Theta, K^n and lpj rows on the device
+        (evoamd_predictive_moments; no statistics pass runs and the EM state stays as it is).  Returns (mean, var, info):
+        float64 (N, D) arrays (None where not wanted) and info = {"n_singular", "n_skipped"}, the datapoints whose rows are
+        NaN because a k x k system is singular / because they have no reliable entry.  EvoAmdError naming n and k for a
+        state with more than 32 active latents, and for D > 512; nothing is downloaded then."""
+        counters = (ctypes.c_int64 * 2)()
+        check(self.lib.evoamd_predictive_moments(self._h, 1 if noise else 0, counters))
+        mean = np.empty((self.N, self.D)) if want_mean else None
+        var = np.empty((self.N, self.D)) if want_var else None
+        check(self.lib.evoamd_download_predictive(self._h, None if mean is None else dptr(mean),
+                                                  None if var is None else dptr(var)))
+        return mean, var, {"n_singular": int(counters[0]), "n_skipped": int(counters[1])}
 
     # ---- timing --------------------------------------------------------------------------
     def timing(self, on=True):

@@ -913,6 +913,33 @@ class Model:
             codes.Es, codes.Ez = eng.download_posterior()
         return codes
 
+    def predictive_moments(self, model_params, my_suff_stat, my_data, noise=True):
+        """The posterior-predictive mean and variance of EVERY entry (n, d) of this rank's data, observed or missing, under
+        ``model_params`` and the caller's K^n / lpj: (mean, var, info) with float64 (N_loc, D) arrays.  mean = W E_q[s]
+        (EBSC) / W E_q[s o z] (ES3C), what reconstruct() writes at the missing entries; var = the variance of the
+        mixture over K^n -- between the states' means plus, ES3C, each state's own w_d^T Lam_s w_d -- plus the noise
+        variance (EBSC sigma**2, ES3C sigma2) when ``noise``.  Formed in a centred form on the device
+        (Engine.predictive_moments; evo_amd.models.predictive_moments_host is the NumPy mirror): without the noise term
+        it is never negative.  A datapoint without a reliable entry (the rows reconstruct() skips) has NaN rows and is
+        counted in info["n_skipped"]; one with a singular k x k system has NaN rows and is counted in
+        info["n_singular"]; a state with more than 32 active latents raises EvoAmdError naming n and k.  Runs no
+        statistics pass, does no communication (per rank), writes nothing into the three dicts, works with
+        sync_host=False and leaves K^n, lpj, Theta, y_reconstructed and the statistics rows on the device as they are."""
+        if self.dtype == np.float32:
+            raise NotImplementedError("predictive_moments is not available in the float32 mode")
+        yr = my_data.get("y_reconstructed")
+        if isinstance(yr, ResidentReconstruction) and yr.resident and not yr.materialised:
+            yr.rows()  # setting the parameters below drops the device copy of an unread reconstruction: fetch it first
+        uploads = self._kn_uploads  # (see reconstruct(): decide before _prepare() runs)
+        eng = self._prepare(my_suff_stat, my_data)
+        # (the precompute stores its derived keys and zeroes the reset counters: on shallow copies here)
+        self.E_step_precompute(dict(model_params), dict(my_suff_stat), my_data)
+        if model_params is not self._dev_theta:
+            self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
+        if self.sync_host or self._kn_uploads != uploads:
+            eng.upload_lpj(my_suff_stat["lpj"])
+        return eng.predictive_moments(noise=noise)
+
     def modelmean(self, model_params, this_data, this_suff_stat):
         """Per-datapoint operator of the reference's reconstruct loop: (D_miss, S) means of the entries to be
         reconstructed, one column per state of this_suff_stat["ss"] (bsc.py:279-287, sssc.py:368-405)."""

@@ -5,7 +5,8 @@
 
 With evo_amd that import reads ``from evo_amd.utils.prepost import ...`` and the loops run unchanged.  Extraction and
 the two standard merges run as HIP kernels on the GPU (``Engine.patches_extract`` / ``Engine.patches_merge``); any other
-merge callable runs on the host over the stack of estimates.  A model built with ``resident_reconstruction=True`` stores a
+merge callable runs on the host over the stack of estimates; ``precision_merger(var.T)`` weights every estimate with the
+inverse of its posterior-predictive variance (Model.predictive_moments) and runs on the GPU too.  A model built with ``resident_reconstruction=True`` stores a
 ``ResidentReconstruction`` handle in my_data["y_reconstructed"]; ``set_and_merge(handle.T, ...)`` merges it on the device.
 
 Conventions (ours; tvutil is not a dependency and bit parity with it is not claimed):
@@ -42,6 +43,61 @@ def median_merger(stack, axis=0):
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", RuntimeWarning)
         return np.nanmedian(stack, axis=axis)
+
+
+class PrecisionMerger:
+    """Precision-weighted mean of every element's estimates: out = (sum_k e_k w_k) / (sum_k w_k) with w_k = 1 / v_k, v the
+    posterior-predictive variances of the patch entries (Model.predictive_moments), held as ``var_T`` (D, N) like the
+    patches.  The sums run over the covering patches in increasing n, multiply and add as separate operations, both from
+    0.0; an estimate that is NaN, or whose variance is NaN or <= 0, is skipped; no valid estimate gives NaN.
+    ``set_and_merge(mean.T, merge_method=precision_merger(var.T))`` merges on the GPU (Engine.patches_merge with
+    method="precision"); calling the object on the (K, H, W[, C]) estimate stack is the host mirror, bit for bit -- it
+    builds the stack of the variances with estimate_stack, for which it needs the geometry: ``bind`` (merge() calls it).
+    Merging ``var.T`` itself with mean_merger gives the per-pixel uncertainty map (the mean variance of a pixel's
+    estimates); the variance of the MERGED image is not that, nor 1 / sum_k w_k: patch estimates are not independent."""
+
+    def __init__(self, var_T):
+        self.var_T = np.asarray(var_T, dtype=np.float64)
+        if self.var_T.ndim != 2:
+            raise ValueError("precision_merger: var_T must be (D, N) like the patches, got shape %s" % (self.var_T.shape,))
+        self._geom = None
+
+    def bind(self, H, W, C, ph, pw, shift):
+        """The patch geometry the variances belong to (ValueError when (D, N) does not fit it)."""
+        N, D = patch_geometry(H, W, C, ph, pw, shift)
+        if self.var_T.shape != (D, N):
+            raise ValueError("precision_merger: variances of shape (D, N) = %s, the patches are %s"
+                             % (self.var_T.shape, (D, N)))
+        self._geom = (int(H), int(W), int(C), int(ph), int(pw), int(shift))
+        return self
+
+    def __call__(self, stack, axis=0):
+        if self._geom is None:
+            raise ValueError("precision_merger: bind(H, W, C, ph, pw, shift) first (OverlappingPatches.merge does)")
+        if axis != 0:
+            raise ValueError("precision_merger merges along axis 0 of the estimate stack")
+        H, W, C = self._geom[:3]
+        stack = np.asarray(stack, dtype=np.float64)
+        shape = stack.shape[1:]
+        est = stack.reshape(stack.shape[0], H, W, C)
+        vst = estimate_stack(self.var_T.T, *self._geom)
+        num, den = np.zeros((H, W, C)), np.zeros((H, W, C))
+        cnt = np.zeros((H, W, C), dtype=np.int64)
+        with np.errstate(all="ignore"):
+            for k in range(est.shape[0]):  # increasing n: the order of the stack
+                ok = ~np.isnan(est[k]) & (vst[k] > 0.0)
+                w = 1.0 / np.where(ok, vst[k], 1.0)
+                num = np.where(ok, num + np.where(ok, est[k], 0.0) * w, num)
+                den = np.where(ok, den + w, den)
+                cnt += ok
+            out = np.where(cnt > 0, num / den, np.nan)
+        return out.reshape(shape)
+
+
+def precision_merger(var_T):
+    """The merge_method of a precision-weighted merge: ``ovp.set_and_merge(mean.T, merge_method=precision_merger(var.T))``
+    with (mean, var, _) = model.predictive_moments(...).  See PrecisionMerger."""
+    return PrecisionMerger(var_T)
 
 
 def patch_tops(L, p, s):
@@ -164,6 +220,12 @@ class OverlappingPatches:
         That covers one rank holding all patches: with several ranks gather as before
         (gather_from_processes(my_data["y_reconstructed"]) materialises the handle)."""
         Y = self._patches()
+        if isinstance(merge_method, PrecisionMerger):
+            merge_method.bind(self.shape[0], self.shape[1], self.C, self.ph, self.pw, self.shift)
+            if isinstance(Y, ResidentReconstruction):
+                Y = Y.rows()
+            return self.engine.patches_merge(Y, self.shape, self.ph, self.pw, self.shift, "precision",
+                                             weights=merge_method.var_T.T)
         gpu_merge = merge_method is mean_merger or merge_method is median_merger
         if isinstance(Y, ResidentReconstruction):
             if gpu_merge:

@@ -428,6 +428,13 @@ int evoamd_patches_extract(evoamd_ctx *ctx, const double *img, int H, int W, int
  * bit), 1 median (np.nanmedian of that stack, bit for bit: even counts give (lo + hi) / 2).  No valid estimate: NaN. */
 int evoamd_patches_merge(evoamd_ctx *ctx, const double *Y, int H, int W, int C, int ph, int pw, int shift, int method,
                          double *img_out);
+/* precision-weighted merge: Y and V are (N, D) host arrays, the estimates and their variances;
+ * img_out = (sum_k e_k w_k) / (sum_k w_k) with w_k = 1 / v_k over the covering patches in increasing n -- multiply and
+ * add as separate IEEE operations (no contraction), both sums started from 0.0.  An estimate that is NaN, or whose v is
+ * NaN or <= 0, is skipped; no valid estimate gives NaN.  evo_amd.utils.prepost.PrecisionMerger is the host mirror, bit
+ * for bit.  Scratch and untouched state as for evoamd_patches_merge. */
+int evoamd_patches_merge_weighted(evoamd_ctx *ctx, const double *Y, const double *V, int H, int W, int C, int ph, int pw,
+                                  int shift, double *img_out);
 /* The reconstruction without the N x D round trip: what Model.reconstruct / step(do_reconstruction) write into
  * my_data["y_reconstructed"] (_models.py:643-665) stays on the device and only the merged image comes back.
  * evoamd_reconstruct_resident makes the SELECTED reconstruction of the last statistics pass resident and copies nothing to
@@ -478,6 +485,31 @@ int evoamd_download_reconstruction(evoamd_ctx *ctx, double *y_hat);
 int evoamd_posterior_codes(evoamd_ctx *ctx, int max_active, double p_min, int32_t *idx, double *p, double *m,
                            int32_t *nnz, int32_t *map_slot, double *map_q, uint8_t *map_state_packed);
 int evoamd_download_posterior(evoamd_ctx *ctx, double *Es, double *Ez);
+
+/* ---- predictive uncertainty (posterior-predictive mean and variance of every entry) ---- */
+/* evoamd_predictive_moments: for every datapoint n and observable d, reliable or missing, over the states s of K^n (and
+ * the permanent all-zero state) with the weights q_ns = exp(lpj_ns - max) / (sum + tiny) of the statistics pass, read
+ * from the lpj rows on the device:
+ *   mean[n, d] = sum_s q_ns m_ns,d,   var[n, d] = sum_s q_ns ((m_ns,d - mean[n, d])^2 + v_ns,d) + (add_noise ? sigma^2 : 0)
+ *   EBSC  m_ns = W s, v_ns = 0;   ES3C  m_ns = W_A kappa_ns, v_ns,d = w_dA^T Lam_ns w_dA with Lam_ns = (Psi_AA^-1 +
+ *   W_oA^T W_oA / sigma2)^-1 and kappa_ns = mu_A + Lam_ns W_oA^T (y_o - W_oA mu_A) / sigma2 over the datapoint's reliable
+ *   entries o (evoamd_upload_masks; all entries for complete data) -- `lam` and `lam_Wt` of sssc.py:289-303.
+ * One wavefront per datapoint (csrc/kernels_predictive.hpp); the variance is accumulated in centred form (weighted
+ * Welford), never as sum q m^2 - mean^2, and without the noise term it is never negative.  Every sum has a fixed order: a
+ * call repeats bit for bit.  Runs no statistics pass and leaves K^n, lpj, Theta, y_reconstructed and the statistics rows
+ * as they are (B = Y W is formed if it is not current, as by every lpj pass).  Needs data, K^n, lpj and Theta on the
+ * device; not in the float32 mode.
+ *   A datapoint without a reliable entry gets NaN rows and is counted in counters[1] (n_skipped).
+ *   A datapoint with a singular k x k system -- an exactly zero or non-finite pivot of the partially pivoted elimination
+ *   of Psi_AA or of I + Psi_AA G_A / sigma2, the criterion of the ES3C lpj levels -- among its states of non-zero weight
+ *   gets NaN rows and is counted in counters[0] (n_singular).
+ *   A state with more than 32 active latents (PRED_MAX_K): EVOAMD_E_INVALID naming the datapoint and k; nothing can be
+ *   downloaded then.  D above 512 (64 lanes x 8 registers per lane): EVOAMD_E_INVALID before anything runs.
+ * The results stay in device buffers of the context (grown on demand, freed by evoamd_ctx_destroy) until the next call;
+ * evoamd_download_predictive copies mean and / or var (N x D double each; either may be NULL) to the host and refuses
+ * (EVOAMD_E_INVALID) when the last call failed or the geometry has changed.  Both calls have completed on return. */
+int evoamd_predictive_moments(evoamd_ctx *ctx, int add_noise, int64_t counters[2]);
+int evoamd_download_predictive(evoamd_ctx *ctx, double *mean, double *var);
 
 /* ---- samples from the model (generate_data / generate_from_hidden: _models.py:73-99, bsc.py:27-57, sssc.py:66-102) ---- */
 /* N datapoints drawn on the device, one wavefront each (csrc/kernels_generate.hpp):
