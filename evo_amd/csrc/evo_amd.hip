@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <chrono>
 #include <memory>
 #include <string>
@@ -157,7 +158,133 @@ struct TimedSpan {
   int kid;
 };
 
+// ---------------------------------------------------------------------------------------
+// owning buffers (DESIGN: buffer ownership).  The only hipMalloc / hipHostMalloc / hipFree / hipHostFree of the library.
+// ---------------------------------------------------------------------------------------
+static int sync_streams(evoamd_ctx *c);
+static std::atomic<int64_t> g_live_dev{0}, g_live_pinned{0};  // evoamd_debug_live_buffers
+
+// Device memory of n elements of T.  Converts to T* so that launches and copies read as before; a kernel template that
+// deduces its element type from the argument takes get().
+template <typename T>
+class DevBuf {
+  T *p_ = nullptr;
+  size_t n_ = 0;
+
+  hipError_t alloc_raw(size_t n) {
+    reset();
+    if (n == 0) n = 1;
+    hipError_t e = hipMalloc((void **)&p_, n * sizeof(T));
+    if (e != hipSuccess) {
+      p_ = nullptr;
+      return e;
+    }
+    n_ = n;
+    g_live_dev++;
+    return hipSuccess;
+  }
+
+ public:
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) {
+      reset();
+      p_ = o.p_, n_ = o.n_;
+      o.p_ = nullptr, o.n_ = 0;
+    }
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  operator T *() const { return p_; }
+  T *get() const { return p_; }
+  size_t size() const { return n_; }  // elements; 0 = empty
+  void reset() {
+    if (p_) {
+      (void)hipFree(p_);
+      g_live_dev--;
+    }
+    p_ = nullptr;
+    n_ = 0;
+  }
+  // exactly n elements (0 becomes 1), whatever was there before is freed first; on failure the buffer is empty
+  int alloc(size_t n) {
+    hipError_t e = alloc_raw(n);
+    if (e != hipSuccess) return fail(EVOAMD_E_HIP, "hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
+    return 0;
+  }
+  // the optional buffers: false (and no sticky HIP error) when the memory cannot be had
+  bool try_alloc(size_t n) {
+    if (alloc_raw(n) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+  }
+  // grow-only: nothing but a compare while n fits; else wait for whatever may still read the old buffer and re-cut
+  int ensure(evoamd_ctx *c, size_t n) {
+    if (n <= n_) return 0;
+    int r = sync_streams(c);
+    return r ? r : alloc(n);
+  }
+};
+
+// hipHostMalloc memory of n elements of T.
+template <typename T>
+class PinnedBuf {
+  T *p_ = nullptr;
+  size_t n_ = 0;
+
+ public:
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf &) = delete;
+  PinnedBuf &operator=(const PinnedBuf &) = delete;
+  PinnedBuf(PinnedBuf &&o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }
+  PinnedBuf &operator=(PinnedBuf &&o) noexcept {
+    if (this != &o) {
+      reset();
+      p_ = o.p_, n_ = o.n_;
+      o.p_ = nullptr, o.n_ = 0;
+    }
+    return *this;
+  }
+  ~PinnedBuf() { reset(); }
+  operator T *() const { return p_; }
+  T *get() const { return p_; }
+  size_t size() const { return n_; }
+  void reset() {
+    if (p_) {
+      (void)hipHostFree(p_);
+      g_live_pinned--;
+    }
+    p_ = nullptr;
+    n_ = 0;
+  }
+  int alloc(size_t n, unsigned flags = hipHostMallocDefault) {
+    reset();
+    if (n == 0) n = 1;
+    hipError_t e = hipHostMalloc((void **)&p_, n * sizeof(T), flags);
+    if (e != hipSuccess) {
+      p_ = nullptr;
+      return fail(EVOAMD_E_HIP, "hipHostMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
+    }
+    n_ = n;
+    g_live_pinned++;
+    return 0;
+  }
+};
+
+#define TRY(expr)        \
+  do {                   \
+    int _r = (expr);     \
+    if (_r) return _r;   \
+  } while (0)
+
 struct evoamd_ctx {
+  evoamd_ctx() = default;
+  evoamd_ctx(const evoamd_ctx &) = delete;
+  evoamd_ctx &operator=(const evoamd_ctx &) = delete;
+  ~evoamd_ctx();  // releases the streams, the events and the communicator; the buffers release themselves
   int device = 0;
   hipStream_t stream = nullptr;
   // second stream: the K = N statistics contraction runs beside the H x H elimination chain of the
@@ -203,7 +330,10 @@ struct evoamd_ctx {
   int n_cu = 256;  // compute units of the device (persistent grids)
   int stats_stage = 1;  // option "stats_stage" (measurement): 0 = no LDS staging of B rows / singleton table
   int stats_waves = 0;  // option "stats_waves" (measurement): waves per workgroup of the ES3C statistics kernel, 0 = 4
-  PairBins pbins = {};
+  PairBins pbins = {};  // views into the three buffers below (alloc_pair_bins), all null when the bins do not fit
+  DevBuf<double4> pb_ent;
+  DevBuf<double> pb_part;
+  DevBuf<int> pb_gcnt;
   int bins_min = 256;  // option "pair_bins_min": pair bins from this many resident states (x 1024) on
  int bins_scale = 3;  // option "pair_bins_scale" (read by evoamd_configure): entry capacity of the pair bins in units of N x S
                        // (3: every resident state a pair, with a margin of three -- a sparse K^n; a K^n of 5..8 latents per
@@ -215,8 +345,7 @@ struct evoamd_ctx {
   int bins_nwg = 2048;  // option "pair_bins_nwg" (read by evoamd_configure): producer workgroups = private regions per bin
   int bsc_wave_opt = 1;  // option "bsc_stats_wave": EBSC statistics on the wave-per-datapoint kernel (0: round-1 kernel)
   int gemm_ws_opt = 1;  // option "gemm_workspace": stream-K partial tiles through a workspace + reduce kernel (0: f64 atomics)
-  double *gemm_ws = nullptr;  // partial tiles of the stream-K contractions (gemm_sk_reduce_kernel adds them to C)
-  size_t gemm_ws_n = 0;
+  DevBuf<double> gemm_ws;  // partial tiles of the stream-K contractions (gemm_sk_reduce_kernel adds them to C)
   int pair_bins = 1;
   int gemm_streamk = 1;  // option "gemm_streamk": long-K 128-tile contraction as one resident-sized stream-K grid
   int sk_spare = -1;  // option "sk_spare": workgroups per XCD the FORKED stream-K contraction leaves unlaunched, so that the
@@ -229,14 +358,14 @@ struct evoamd_ctx {
   // sssc_exact_mode) -- 0 never, 1 when the tables kernel has stamped this Theta (default), 2 always
   int sing_screen = 1;
   // states above SSSC_KCAP active latents (H > SSSC_KCAP only): slots of global memory for the wavefront kernel's matrices
-  double *huge = nullptr;
-  int *huge_ctl = nullptr;
+  DevBuf<double> huge;
+  DevBuf<int> huge_ctl;
   int huge_slots = 0, huge_kc = 0;
-  int *sing_gen = nullptr;  // = err + 4: generation of the last Theta whose Psi held an exactly singular 1x1 / 2x2 block
+  int *sing_gen = nullptr;  // view, = err + 4: generation of the last Theta whose Psi held an exactly singular 1x1 / 2x2 block
   int theta_gen = 0;        // stamp of the current Theta (one per sssc_tables_kernel launch)
   int gemm_grouped = 1;  // option "gemm_grouped": grouped split-K instead of stream-K where whole chunks fill the grid
   int gemm_per_xcd = 0;  // option "gemm_per_xcd" (experiments): K chunks per XCD of the 128-tile contraction, 0 = automatic
-  double *census = nullptr;  // 4 doubles at the head of acc_base: overflow census of the earlier blocks of a chunked statistics pass
+  double *census = nullptr;  // view: 4 doubles at the head of acc_base, overflow census of the earlier blocks of a chunked statistics pass
   i64 pre_n = 4;
   hipEvent_t ev_chunk[16] = {};
   bool configured = false, have_data = false, have_params = false, have_cand = false, B_valid = false;
@@ -257,25 +386,24 @@ struct evoamd_ctx {
   // float and the two K- / N-long contractions run on v_mfma_f32_16x16x4_f32; lpj arithmetic, Theta and every
   // accumulator stay double.  Yf (N,D), Ytf = Y^T (D, ldYt), Wf (D,H), Bf (N,H), Esf (N,H)
   bool f32_opt = false, f32 = false;
-  float *Yf = nullptr, *Ytf = nullptr, *Wf = nullptr, *Bf = nullptr, *Esf = nullptr;
+  DevBuf<float> Yf, Ytf, Wf, Bf, Esf;
   i64 ldYt = 0;
   // double precision: Y^T (D, ldYt) for B = Y W on the 128-tile kernel (large N; option "b_transposed", default 1)
-  double *Yt = nullptr;
+  DevBuf<double> Yt;
   int b_tn_opt = 1;
-  uint8_t *mask_infr = nullptr, *mask_x = nullptr;  // EBSC incomplete data: reliable entries / entries that keep their value
-  double *Yrec = nullptr;       // y_reconstructed (N x D): what the M-step's Wp contraction reads then
+  DevBuf<uint8_t> mask_infr, mask_x;  // EBSC incomplete data: reliable entries / entries that keep their value
+  DevBuf<double> Yrec;  // y_reconstructed (N x D): what the M-step's Wp contraction reads then
   bool yrec_valid = false, rec_in_stats = false;
-  double *yhat = nullptr, *tmpWt = nullptr;  // reconstruction (N x D) and W^T scratch (ES3C)
-  size_t yhat_n = 0;
+  DevBuf<double> yhat, tmpWt;  // reconstruction (N x D) and W^T scratch (ES3C)
   bool yhat_valid = false;
   bool stats_rows_valid = false;  // Es / Ez rows describe the current K^n and Theta
   // evoamd_reconstruct_resident: the selected reconstruction stays on the device for evoamd_patches_merge_resident.
   // rec_resident: y_hat (complete data) / Yrec (incomplete) + the masks below describe it; dropped with yhat_valid and by
   // every upload of data, masks or y_reconstructed.  yrec_from_pass: Yrec was written by the statistics pass y_hat is from.
   bool rec_resident = false, yrec_from_pass = false;
-  uint8_t *keep_x = nullptr;   // complete data: the caller's keep-mask (N x D), uploaded by evoamd_reconstruct_resident
+  DevBuf<uint8_t> keep_x;  // complete data: the caller's keep-mask (N x D), uploaded by evoamd_reconstruct_resident
   bool keep_x_valid = false, rec_uses_keep = false;
-  uint8_t *row_any = nullptr;  // incomplete data: datapoint has a reliable entry (N), written by evoamd_upload_masks
+  DevBuf<uint8_t> row_any;  // incomplete data: datapoint has a reliable entry (N), written by evoamd_upload_masks
   int merge_select_fused = 0;  // option "merge_select_fused" (0: select kernel, then the merge kernels over dense rows -- measured faster)
   // software pipelining across the API boundary: evoamd_mstep_device enqueues the NEXT iteration's pass
   // over the resident K^n behind the mailbox kernel, so the GPU works through the ~40 us the host needs
@@ -292,70 +420,64 @@ struct evoamd_ctx {
   i64 N = 0;
   int D = 0, H = 0, S = 0, S_perm = 0, Cmax = 0, HW = 0, L = 0;
   // data
-  double *Y = nullptr, *yy = nullptr, *y2sum = nullptr;  // SSSC: Y is the left block of [Y | Es | Ez], row stride ldY
+  DevBuf<double> Y, yy, y2sum;  // SSSC: Y is the left block of [Y | Es | Ez], row stride ldY
   int ldY = 0;
-  double *h_acc = nullptr, *h_par = nullptr;  // pinned host staging (accumulator D2H, Theta H2D)
-  size_t h_par_n = 0;
-  double *h_theta = nullptr;  // host mailbox (kernels_mstep.hpp: mailbox_kernel): seq | err | tail | dpar | Theta
-  double *h_theta_dev = nullptr;  // the same memory as the device sees it
+  PinnedBuf<double> h_acc, h_par;  // pinned host staging (accumulator D2H, Theta H2D)
+  PinnedBuf<double> h_theta;  // host mailbox (kernels_mstep.hpp: mailbox_kernel): seq | err | tail | dpar | Theta
+  double *h_theta_dev = nullptr;  // view: the same memory as the device sees it
   bool h_theta_fresh = false;
   // lazy Theta (evoamd_mstep_device with bit 64): the parameters the E-step ran with, saved on the device before the
   // update overwrites them -- what evoamd_restore_theta_backup re-installs when the update turns out singular
-  double *theta_bak = nullptr;
-  size_t theta_bak_n = 0;
+  DevBuf<double> theta_bak;
   bool theta_bak_valid = false;
   unsigned long long mbox_seq = 0;
-  unsigned *mbox_counter = nullptr;
-  int *h_err = nullptr;
+  DevBuf<unsigned> mbox_counter;
+  PinnedBuf<int> h_err;
   // variational state
-  u64 *states = nullptr, *cand = nullptr;
-  u64 *dig = nullptr, *cand_dig = nullptr;  // state digests (common.hpp), nullptr when H > DIG_MAX_H
-  double *lpj = nullptr, *cand_lpj = nullptr;
-  double *lpj_alt = nullptr;  // target of the prefetched pass; swapped with lpj when it is consumed (the rows of the
+  DevBuf<u64> states, cand;
+  DevBuf<u64> dig, cand_dig;  // state digests (common.hpp), empty when H > DIG_MAX_H
+  DevBuf<double> lpj, cand_lpj;
+  DevBuf<double> lpj_alt;  // target of the prefetched pass; swapped with lpj when it is consumed (the rows of the
                               // E-step that just ended stay readable until then: sync_to_host, download_lpj)
-  int *cand_counts = nullptr;
+  DevBuf<int> cand_counts;
   // general device EA (evolve_general_kernel): raw children of a generation, first slot of the last generation,
   // "this known state was duplicated by a child" bits; allocated on first use
-  u64 *cand_raw = nullptr, *dupold = nullptr;
-  int *gen_start = nullptr;
-  unsigned *flags = nullptr;  // 3 x N: resident | candidates | permanent
-  double *rowmax = nullptr, *rowsum = nullptr, *partial = nullptr, *partial2 = nullptr, *diag = nullptr;
-  i64 n_partial = 0;
-  uint8_t *stage = nullptr;  // bool staging for (N, max(S,Cmax), H)
-  size_t stage_bytes = 0;
+  DevBuf<u64> cand_raw, dupold;
+  DevBuf<int> gen_start;
+  DevBuf<unsigned> flags;  // 3 x N: resident | candidates | permanent
+  DevBuf<double> rowmax, rowsum, partial, partial2, diag;  // partial = 3 x partial2.size()
+  DevBuf<uint8_t> stage;  // bool staging for (N, max(S,Cmax), H), grown on demand
   // parameters
-  double *W = nullptr, *Wt = nullptr, *G = nullptr, *Psi = nullptr, *Bm = nullptr, *mus = nullptr,
-         *pilbar_v = nullptr;
-  double2 *GP = nullptr;
-  double4 *DG = nullptr;             // SSSC (H) {mu, pil_bar, G_hh, Psi_hh}
-  double4 *D1 = nullptr;             // SSSC (H) singleton state terms (sssc_tables_kernel)
-  PairEntry *PT = nullptr;           // SSSC (H,H) pair state terms
-  double *pies = nullptr;            // SSSC (H)
-  double *dpar = nullptr;            // device scalar block (DP_*), kernels read their scalars here
-  double *h_dpar = nullptr;          // pinned mirror
-  double *colpart = nullptr;  // per-workgroup partial column sums
-  size_t colpart_n = 0;
-  double *gjwork = nullptr;  // colp | rowp | perm of the multi-launch Gauss-Jordan inverse
-  double *tmpA = nullptr, *tmpB = nullptr, *tmpC = nullptr;  // (H,H) scratch of the device Theta update
+  DevBuf<double> W, Wt, G, Psi, Bm, mus, pilbar_v;
+  DevBuf<double2> GP;
+  DevBuf<double4> DG;                // SSSC (H) {mu, pil_bar, G_hh, Psi_hh}
+  DevBuf<double4> D1;                // SSSC (H) singleton state terms (sssc_tables_kernel)
+  DevBuf<PairEntry> PT;              // SSSC (H,H) pair state terms
+  DevBuf<double> pies;               // SSSC (H)
+  double *dpar = nullptr;            // view into acc_base: device scalar block (DP_*), kernels read their scalars here
+  PinnedBuf<double> h_dpar;          // pinned mirror
+  DevBuf<double> colpart;  // per-workgroup partial column sums, grown on demand
+  DevBuf<double> gjwork;  // colp | rowp | perm of the multi-launch Gauss-Jordan inverse
+  DevBuf<double> tmpA, tmpB, tmpC;  // (H,H) scratch of the device Theta update
   double ljc = 0;
   // statistics
-  double *acc = nullptr;
+  double *acc = nullptr;  // view into acc_base
   i64 acc_n = 0;
   // ES3C: second-moment contributions of the overflow kernels (states with > 2 active latents), kept
   // apart from the k = 2 sums so that sssc_finish_kernel can rebuild the lower triangle (2 H^2 doubles
   // in front of acc in the same allocation: one memset clears both)
-  double *acc_base = nullptr;
+  DevBuf<double> acc_base;
   i64 ovf_n = 0;
-  double *Es = nullptr;  // BSC: (N,H); SSSC: columns D..D+H of c->Y (Ez follows)
-  int *list1 = nullptr, *list2 = nullptr, *list3 = nullptr, *list_n = nullptr, *err = nullptr;
+  DevBuf<double> Es_own;  // BSC: (N,H)
+  double *Es = nullptr;   // view: Es_own (BSC) / columns D..D+H of c->Y (SSSC, Ez follows)
+  DevBuf<int> list1, list2, list3, list_n, err;  // list1..3: one size (ensure_lists)
   // ES3C census lists (kernels_sssc_quad.hpp): the resident states with 3..4 / 5..8 / > 8 active latents, built by ONE
   // pass over the digests whenever K^n has changed (kn_gen) and shared by the statistics pass and the next pass over
   // K^n; clist = 3 lists of LIST_SHARDS x list_cap(N S) entries, clist_n = their shard counters (4 x LIST_SHARDS, like
   // list_n); ovf_rec = one record per resident state (only the listed ones are ever touched)
-  int *clist = nullptr, *clist_n = nullptr;
-  size_t clist_words = 0;
-  OvfRec *ovf_rec = nullptr;
-  size_t ovf_rec_n = 0;
+  DevBuf<int> clist, clist_n;
+  size_t clist_words() const { return clist.size() / 3; }
+  DevBuf<OvfRec> ovf_rec;
   unsigned long long kn_gen = 1, census_gen = 0;
   int census_opt = 1;   // option "census_lists": 0 = round-2 level chains everywhere
   // option "merge_small_levels": with few states above four active latents (census of the last statistics pass) the
@@ -368,10 +490,10 @@ struct evoamd_ctx {
   // passes at every BASELINE shape) / 1 when K^n is sparse enough / 2 whenever the shape allows it; rowF / rowcnt = per-datapoint free-energy term and counters, defer = datapoints the
   // FAST instantiation left to the FULL one (N items + the counter behind them)
   int fused_opt = 0;
-  double *rowF = nullptr;
-  int *rowcnt = nullptr, *defer = nullptr;
-  double *fpart = nullptr;  // 3 x 1024 chain sums of fused_reduce3_kernel
-  unsigned long long *fprof = nullptr;  // -DFUSED_PROFILE builds
+  DevBuf<double> rowF;
+  DevBuf<int> rowcnt, defer;
+  DevBuf<double> fpart;  // 3 x 1024 chain sums of fused_reduce3_kernel
+  DevBuf<unsigned long long> fprof;  // -DFUSED_PROFILE builds
   bool last_estep_fused = false;
   bool reduce_pending = false;  // fused E-step: rowF / rowcnt not yet summed into the scalar block (fused_reduce3_kernel)
   long fused_calls = 0, unfused_calls = 0;
@@ -379,45 +501,36 @@ struct evoamd_ctx {
   int debug_fail_stats = 0;   // option "debug_fail_stats" (tests): the next statistics pass (ES3C, complete data) returns
                               // after its main kernel; any other pass disarms it
   int census_skip = 0;  // levels that passes over the CURRENT census did not launch (checked when it is rebuilt)
-  size_t list_words = 0;  // capacity of each overflow list (ints)
   // scratch for single / shared evaluations
-  double *tmp_y = nullptr, *tmp_lpj = nullptr;
-  u64 *tmp_states = nullptr;
-  size_t tmp_states_words = 0, tmp_lpj_n = 0;
+  DevBuf<double> tmp_y, tmp_lpj;
+  DevBuf<u64> tmp_states;
   // evoamd_loglik_exact: running maximum / sum / marginal sums per datapoint and the outputs (one allocation, grown on demand)
-  double *exact_buf = nullptr;
-  size_t exact_n = 0;
+  DevBuf<double> exact_buf;
   // evoamd_patches_*: image and patch rows on the device, grown on demand (never the EM state above)
-  double *patch_img = nullptr, *patch_Y = nullptr;
-  size_t patch_img_n = 0, patch_Y_n = 0;
-  double *patch_V = nullptr;  // evoamd_patches_merge_weighted: the variances of the patch rows
-  size_t patch_V_n = 0;
+  DevBuf<double> patch_img, patch_Y;
+  DevBuf<double> patch_V;  // evoamd_patches_merge_weighted: the variances of the patch rows
   // evoamd_predictive_moments (kernels_predictive.hpp): mean | var (N x D each), the status word per datapoint and W^T
   // (H x D, transposed from W by every call), grown on demand (never the EM state above); pred_N = 0: nothing to download
-  double *pred_buf = nullptr, *pred_Wt = nullptr;
-  int *pred_status = nullptr;
-  size_t pred_buf_n = 0, pred_Wt_n = 0, pred_status_n = 0;
+  DevBuf<double> pred_buf, pred_Wt;
+  DevBuf<int> pred_status;
   i64 pred_N = 0;
   int pred_D = 0;
   // evoamd_posterior_codes: the compact outputs on the device (one allocation, grown on demand); rows_kn_gen = the K^n
   // the rows of the last statistics pass were formed from; option "codes_path" (-1 automatic, else CODES_REG / _LDS / _GMEM)
-  uint8_t *codes_buf = nullptr;
-  size_t codes_bytes = 0;
+  DevBuf<uint8_t> codes_buf;
   unsigned long long rows_kn_gen = 0;
   int codes_path = -1;
   // evoamd_init_states (kernels_init.hpp): option "init_states_home" (-1 automatic, 0 LDS, 1 global memory), the slots of
   // the global home (grown on demand), and kn_lost: the call stopped at its round cap, K^n is partly written -- every pass
   // that reads K^n refuses until an upload or a successful evoamd_init_states
   int init_home = -1;
-  u64 *init_scratch = nullptr;
-  size_t init_scratch_words = 0;
+  DevBuf<u64> init_scratch;
   bool kn_lost = false;
   i64 kn_refill = 0;  // while kn_lost: rows [0, kn_refill) have been uploaded again by evoamd_upload_states_packed
   // evoamd_generate (kernels_generate.hpp): Theta^gen, the given states and the outputs of the last call, grown on demand
   // (never the EM state above); gen_keep < 0: no call has completed
-  double *gen_par = nullptr, *gen_y = nullptr, *gen_z = nullptr, *gen_ymean = nullptr;
-  u64 *gen_sin = nullptr, *gen_s = nullptr;
-  size_t gen_par_n = 0, gen_y_n = 0, gen_z_n = 0, gen_ymean_n = 0, gen_sin_n = 0, gen_s_n = 0;
+  DevBuf<double> gen_par, gen_y, gen_z, gen_ymean;
+  DevBuf<u64> gen_sin, gen_s;
   i64 gen_N = 0;
   int gen_D = 0, gen_H = 0, gen_keep = -1;
   // rccl
@@ -474,22 +587,6 @@ static int resolve_spans(evoamd_ctx *c) {
   return 0;
 }
 
-template <typename T>
-static int dev_alloc(T **p, size_t n) {
-  if (*p) {
-    (void)hipFree(*p);
-    *p = nullptr;
-  }
-  if (n == 0) n = 1;
-  HIP_TRY(hipMalloc((void **)p, n * sizeof(T)));
-  return 0;
-}
-#define ALLOC(p, n)                 \
-  do {                              \
-    int _r = dev_alloc(&(p), (n));  \
-    if (_r) return _r;              \
-  } while (0)
-
 static inline unsigned cdiv(i64 a, i64 b) { return (unsigned)((a + b - 1) / b); }
 // entries one shard of an overflow list can receive from `total` pairs (workgroup batches of 256..1024
 // pairs are dealt round-robin to the shards)
@@ -504,24 +601,12 @@ static void launch_colsum(evoamd_ctx *c, const double *X, int ldx, i64 R, int Cn
 }
 
 
-static int ensure_colpart(evoamd_ctx *c, size_t n) {
-  if (n <= c->colpart_n) return 0;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  ALLOC(c->colpart, n);
-  c->colpart_n = n;
-  return 0;
-}
-
 // overflow lists big enough for a batch of `total` (datapoint, state) pairs
 static int ensure_lists(evoamd_ctx *c, i64 total) {
   const size_t need = list_cap(total) * LIST_SHARDS;
-  if (need <= c->list_words) return 0;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  ALLOC(c->list1, need);
-  ALLOC(c->list2, need);
-  ALLOC(c->list3, need);
-  c->list_words = need;
-  return 0;
+  TRY(c->list1.ensure(c, need));
+  TRY(c->list2.ensure(c, need));
+  return c->list3.ensure(c, need);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -542,38 +627,8 @@ extern "C" int evoamd_device_count(int *count) {
   return 0;
 }
 
-extern "C" int evoamd_ctx_create(int device, evoamd_ctx **out) {
-  REQUIRE(out, "out is NULL");
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-    return fail(EVOAMD_E_NODEVICE, "no HIP device visible (libevo_amd needs an MI355X / gfx950 GPU)");
-  REQUIRE(device >= 0 && device < n, "device index out of range");
-  HIP_TRY(hipSetDevice(device));
-  hipDeviceProp_t prop;
-  HIP_TRY(hipGetDeviceProperties(&prop, device));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(EVOAMD_E_NODEVICE, "device %d is %s; libevo_amd is built for gfx950 only", device,
-                prop.gcnArchName);
-  evoamd_ctx *c = new evoamd_ctx();
-  c->device = device;
-  c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  {
-    // the main stream carries the latency-bound chains (Theta update, small launches), stream2 the forked MFMA
-    // contraction: the dispatcher serves the higher priority first whenever a CU slot is free
-    int prio_lo = 0, prio_hi = 0;
-    HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-    HIP_TRY(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_hi));
-    HIP_TRY(hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, prio_lo));
-  }
-  HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-  HIP_TRY(hipStreamCreateWithFlags(&c->stream_copy, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreateWithFlags(&c->ev_theta, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&c->ev_theta_done, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&c->ev_mbox, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&c->ev_bak, hipEventDisableTiming));
-  for (int i = 0; i < 16; i++) HIP_TRY(hipEventCreateWithFlags(&c->ev_chunk[i], hipEventDisableTiming));
-
+// kernels whose dynamic LDS exceeds the 64 KiB a launch may ask for by default
+static int set_kernel_lds_limits() {
   HIP_TRY(hipFuncSetAttribute((const void *)sssc_stats_flat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   HIP_TRY(hipFuncSetAttribute((const void *)sssc_big_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               136 * 1024));
@@ -620,234 +675,156 @@ extern "C" int evoamd_ctx_create(int device, evoamd_ctx **out) {
                         (const void *)sssc_estep_fused_kernel<16, false>, (const void *)sssc_estep_fused_kernel<16, true>};
     for (const void *fp : fk) HIP_TRY(hipFuncSetAttribute(fp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   }
-  *out = c;
   return 0;
 }
 
-static void free_all(evoamd_ctx *c) {
-  void *ptrs[] = {c->Y,      c->yy,     c->y2sum,   c->states,  c->cand,     c->lpj,       c->cand_lpj,
-                  c->cand_counts, c->flags, c->rowmax, c->rowsum, c->partial, c->partial2, c->diag, c->stage,    c->W,
-                  c->Wt,     c->G,      c->Psi,     c->Bm,      c->mus,      c->pilbar_v,  c->GP,      c->DG,    c->D1,    c->PT,   c->yhat,  c->tmpWt,  c->mask_infr,  c->mask_x,  c->Yrec,
-                  c->pies,   c->tmpA,    c->tmpB,    c->tmpC,    c->gjwork,  c->colpart,
-                  c->acc_base, c->Es,     c->list1,   c->list2,    c->list3,    c->list_n,    c->err,
-                  c->tmp_y,  c->tmp_lpj, c->tmp_states, c->dig, c->cand_dig, c->lpj_alt, c->cand_raw, c->dupold, c->gen_start,
-                  c->pbins.ent, c->pbins.part, c->pbins.gcnt, c->gemm_ws, c->Yt, c->Yf, c->Ytf, c->Wf, c->Bf, c->Esf,
-                  c->clist, c->clist_n, c->ovf_rec, c->theta_bak, c->rowF, c->rowcnt, c->defer, c->fpart, c->huge, c->huge_ctl,
-                  c->patch_img, c->patch_Y, c->keep_x, c->row_any, c->codes_buf, c->init_scratch,
-                  c->gen_par, c->gen_y, c->gen_z, c->gen_ymean, c->gen_sin, c->gen_s, c->exact_buf,
-                  c->patch_V, c->pred_buf, c->pred_Wt, c->pred_status};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
-  if (c->h_acc) (void)hipHostFree(c->h_acc);
-  if (c->h_par) (void)hipHostFree(c->h_par);
-  if (c->h_theta) (void)hipHostFree(c->h_theta);
-  c->h_theta = nullptr;
-  if (c->h_err) (void)hipHostFree(c->h_err);
-  if (c->h_dpar) (void)hipHostFree(c->h_dpar);
+extern "C" int evoamd_ctx_create(int device, evoamd_ctx **out) {
+  REQUIRE(out, "out is NULL");
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
+    return fail(EVOAMD_E_NODEVICE, "no HIP device visible (libevo_amd needs an MI355X / gfx950 GPU)");
+  REQUIRE(device >= 0 && device < n, "device index out of range");
+  HIP_TRY(hipSetDevice(device));
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, device));
+  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(EVOAMD_E_NODEVICE, "device %d is %s; libevo_amd is built for gfx950 only", device,
+                prop.gcnArchName);
+  std::unique_ptr<evoamd_ctx> guard(new evoamd_ctx());  // every early return destroys what was created so far
+  evoamd_ctx *c = guard.get();
+  c->device = device;
+  c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  {
+    // the main stream carries the latency-bound chains (Theta update, small launches), stream2 the forked MFMA
+    // contraction: the dispatcher serves the higher priority first whenever a CU slot is free
+    int prio_lo = 0, prio_hi = 0;
+    HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+    HIP_TRY(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_hi));
+    HIP_TRY(hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, prio_lo));
+  }
+  HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+  HIP_TRY(hipStreamCreateWithFlags(&c->stream_copy, hipStreamNonBlocking));
+  HIP_TRY(hipEventCreateWithFlags(&c->ev_theta, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&c->ev_theta_done, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&c->ev_mbox, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&c->ev_bak, hipEventDisableTiming));
+  for (int i = 0; i < 16; i++) HIP_TRY(hipEventCreateWithFlags(&c->ev_chunk[i], hipEventDisableTiming));
+  TRY(set_kernel_lds_limits());
+  *out = guard.release();
+  return 0;
+}
+
+static int sync_streams(evoamd_ctx *c) {
+  for (hipStream_t s : {c->stream, c->stream2, c->stream_copy})
+    if (s) HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+evoamd_ctx::~evoamd_ctx() {
+  (void)hipSetDevice(device);
+  (void)sync_streams(this);  // nothing in flight reads a buffer or records an event once the members go
+  if (comm && g_rccl.CommDestroy) g_rccl.CommDestroy(comm);
+  for (auto &s : spans) {
+    (void)hipEventDestroy(s.a);
+    (void)hipEventDestroy(s.b);
+  }
+  for (hipEvent_t e : pool) (void)hipEventDestroy(e);
+  for (hipStream_t s : {stream, stream2, stream_copy})
+    if (s) (void)hipStreamDestroy(s);
+  for (hipEvent_t e : {ev_fork, ev_join, ev_theta, ev_theta_done, ev_mbox, ev_bak})
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ev_chunk)
+    if (e) (void)hipEventDestroy(e);
 }
 
 extern "C" void evoamd_ctx_destroy(evoamd_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
-  for (auto &s : c->spans) {
-    (void)hipEventDestroy(s.a);
-    (void)hipEventDestroy(s.b);
-  }
-  for (auto e : c->pool) (void)hipEventDestroy(e);
-  free_all(c);
-  (void)hipStreamDestroy(c->stream);
-  if (c->stream2) (void)hipStreamDestroy(c->stream2);
-  if (c->stream_copy) (void)hipStreamDestroy(c->stream_copy);
-  if (c->ev_theta) (void)hipEventDestroy(c->ev_theta);
-  if (c->ev_theta_done) (void)hipEventDestroy(c->ev_theta_done);
-  if (c->ev_mbox) (void)hipEventDestroy(c->ev_mbox);
-  if (c->ev_bak) (void)hipEventDestroy(c->ev_bak);
-  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-  if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-  for (int i = 0; i < 16; i++)
-    if (c->ev_chunk[i]) (void)hipEventDestroy(c->ev_chunk[i]);
-
   delete c;
 }
+
+extern "C" int evoamd_debug_live_buffers(int64_t out[2]) {
+  REQUIRE(out, "out is NULL");
+  out[0] = g_live_dev;
+  out[1] = g_live_pinned;
+  return 0;
+}
+
+// One row per option of evoamd_set_option (what each one means: the comments at the fields of evoamd_ctx).
+struct OptionRow {
+  const char *name;
+  int evoamd_ctx::*ifield;   // where the value goes: an int field ...
+  bool evoamd_ctx::*bfield;  // ... or a bool field
+  int (*norm)(int) = nullptr;  // how the value is stored (nullptr: as it is)
+  int lo = 0, hi = 0;             // with `err`: the accepted range ...
+  bool (*accepts)(int) = nullptr;  // ... or set
+  const char *err = nullptr;     // the refusal (nullptr: every value is accepted)
+  void (*after)(evoamd_ctx *) = nullptr;  // side effect of a successful set
+};
+#define OPT_INT(f) &evoamd_ctx::f, nullptr
+#define OPT_BOOL(f) nullptr, &evoamd_ctx::f
+static int opt_flag(int v) { return v != 0; }
+static const OptionRow OPTIONS[] = {
+    {"sssc_k8", OPT_INT(k8_mode), [](int v) { return v < 0 ? -1 : (int)(v != 0); }},
+    {"ebsc_f32", OPT_BOOL(f32_opt), opt_flag},  // takes effect at the next evoamd_configure
+    {"bsc_direct", OPT_BOOL(bsc_direct), opt_flag, 0, 0, nullptr, nullptr,
+     [](evoamd_ctx *c) { c->have_params = false; }},  // G / B are (not) needed: set_params again
+    {"reconstruct_in_stats", OPT_BOOL(rec_in_stats), opt_flag},  // one-shot: the next statistics pass forms y_reconstructed first
+    {"codes_path", OPT_INT(codes_path), nullptr, -1, CODES_GMEM, nullptr, "codes_path: -1 (auto), 0 registers, 1 LDS, 2 global memory"},
+    {"merge_select_fused", OPT_INT(merge_select_fused), opt_flag},
+    {"prefetch_lpj", OPT_BOOL(prefetch_lpj), opt_flag},
+    {"inverse_block", OPT_INT(spd_block), nullptr, 0, 0, [](int v) { return v == 0 || v == 16 || v == 32; },
+     "inverse_block: 0 (auto), 16 or 32"},
+    {"overlap_gemm", OPT_INT(overlap_gemm)},
+    {"stats_stage", OPT_INT(stats_stage)},
+    {"stats_waves", OPT_INT(stats_waves)},
+    {"pair_bins", OPT_INT(pair_bins)},
+    {"gemm_streamk", OPT_INT(gemm_streamk)},
+    {"b_transposed", OPT_INT(b_tn_opt)},  // takes effect at the next evoamd_configure
+    {"pair_bins_scale", OPT_INT(bins_scale), nullptr, 1, 64, nullptr, "pair_bins_scale: 1 .. 64"},
+    {"pair_bins_nwg", OPT_INT(bins_nwg), nullptr, 0, 0, [](int v) { return v >= 256 && v <= 2048 && (v % 256) == 0; },
+     "pair_bins_nwg: 256 .. 2048, multiple of 256"},
+    {"pair_bins_auto", OPT_INT(bins_auto), opt_flag},
+    {"pair_bins_min", OPT_INT(bins_min)},
+    {"bsc_stats_wave", OPT_INT(bsc_wave_opt)},
+    {"gemm_workspace", OPT_INT(gemm_ws_opt)},
+    {"sssc_precision", OPT_INT(sssc_prec32), [](int v) { return (int)(v == 32); }, 0, 0, [](int v) { return v == 64 || v == 32; },
+     "sssc_precision: 64 or 32"},
+    {"lpj_main_unstaged", OPT_INT(main_unstaged), opt_flag},
+    {"lpj_singular_screen", OPT_INT(sing_screen), nullptr, 0, 2, nullptr, "lpj_singular_screen: 0 (never), 1 (automatic) or 2 (always)"},
+    {"gemm_grouped", OPT_INT(gemm_grouped), opt_flag},
+    {"gemm_per_xcd", OPT_INT(gemm_per_xcd)},
+    {"init_states_home", OPT_INT(init_home), nullptr, -1, 1, nullptr, "init_states_home: -1 (auto), 0 LDS, 1 global memory"},
+    {"background_unit", OPT_INT(bg_unit), opt_flag},
+    {"fold_clear", OPT_INT(fold_clear), opt_flag},
+    {"early_fork", OPT_INT(early_fork)},
+    {"merge_small_levels", OPT_INT(merge_small), opt_flag},
+    {"stats_flat", OPT_INT(stats_flat), opt_flag},
+    {"theta_copy_engine", OPT_INT(theta_copy_engine), opt_flag},
+    {"census_lists", OPT_INT(census_opt), opt_flag},  // takes effect at the next evoamd_configure
+    {"sk_spare", OPT_INT(sk_spare), nullptr, -1, 32, nullptr, "sk_spare: -1 (automatic) or 0 .. 32 workgroups per XCD"},
+    {"stats_chunks", OPT_INT(stats_chunks), nullptr, 1, 16, nullptr, "stats_chunks: 1 .. 16"},
+    {"mailbox_side_stream", OPT_INT(mbox_side), opt_flag},
+    {"fused_estep", OPT_INT(fused_opt), nullptr, 0, 2, nullptr, "fused_estep: 0 (never), 1 (automatic) or 2 (whenever the shape allows it)"},
+    {"debug_poison_list", OPT_INT(debug_poison_list), opt_flag},
+    {"debug_fail_stats", OPT_INT(debug_fail_stats), opt_flag},
+    {"state_digest", OPT_BOOL(use_digest), opt_flag},
+    {"inverse_spd", OPT_BOOL(spd_inverse), opt_flag},
+};
+#undef OPT_INT
+#undef OPT_BOOL
 
 extern "C" int evoamd_set_option(evoamd_ctx *c, const char *name, int value) {
   REQUIRE(c && name, "bad arguments");
   c->gen++;  // an option can change which kernel form evaluates K^n: drop a prefetched pass
-  if (strcmp(name, "sssc_k8") == 0) {
-    c->k8_mode = value < 0 ? -1 : (value != 0);
-    return 0;
-  }
-  if (strcmp(name, "ebsc_f32") == 0) {
-    c->f32_opt = value != 0;  // takes effect at the next evoamd_configure
-    return 0;
-  }
-  if (strcmp(name, "bsc_direct") == 0) {
-    c->bsc_direct = value != 0;
-    c->have_params = false;  // G / B are (not) needed: set_params again
-    return 0;
-  }
-  if (strcmp(name, "reconstruct_in_stats") == 0) {  // one-shot: the next statistics pass forms y_reconstructed first
-    c->rec_in_stats = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "codes_path") == 0) {
-    if (value < -1 || value > CODES_GMEM) return fail(EVOAMD_E_INVALID, "codes_path: -1 (auto), 0 registers, 1 LDS, 2 global memory");
-    c->codes_path = value;
-    return 0;
-  }
-  if (strcmp(name, "merge_select_fused") == 0) {
-    c->merge_select_fused = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "prefetch_lpj") == 0) {
-    c->prefetch_lpj = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "inverse_block") == 0) {
-    if (value != 0 && value != 16 && value != 32) return fail(EVOAMD_E_INVALID, "inverse_block: 0 (auto), 16 or 32");
-    c->spd_block = value;
-    return 0;
-  }
-  if (strcmp(name, "overlap_gemm") == 0) {
-    c->overlap_gemm = value;
-    return 0;
-  }
-  if (strcmp(name, "stats_stage") == 0) {
-    c->stats_stage = value;
-    return 0;
-  }
-  if (strcmp(name, "stats_waves") == 0) {
-    c->stats_waves = value;
-    return 0;
-  }
-  if (strcmp(name, "pair_bins") == 0) {
-    c->pair_bins = value;
-    return 0;
-  }
-  if (strcmp(name, "gemm_streamk") == 0) {
-    c->gemm_streamk = value;
-    return 0;
-  }
-  if (strcmp(name, "b_transposed") == 0) {  // takes effect at the next evoamd_configure
-    c->b_tn_opt = value;
-    return 0;
-  }
-  if (strcmp(name, "pair_bins_scale") == 0) {
-    if (value < 1 || value > 64) return fail(EVOAMD_E_INVALID, "pair_bins_scale: 1 .. 64");
-    c->bins_scale = value;
-    return 0;
-  }
-  if (strcmp(name, "pair_bins_nwg") == 0) {
-    if (value < 256 || value > 2048 || (value % 256) != 0) return fail(EVOAMD_E_INVALID, "pair_bins_nwg: 256 .. 2048, multiple of 256");
-    c->bins_nwg = value;
-    return 0;
-  }
-  if (strcmp(name, "pair_bins_auto") == 0) {
-    c->bins_auto = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "pair_bins_min") == 0) {
-    c->bins_min = value;
-    return 0;
-  }
-  if (strcmp(name, "bsc_stats_wave") == 0) {
-    c->bsc_wave_opt = value;
-    return 0;
-  }
-  if (strcmp(name, "gemm_workspace") == 0) {
-    c->gemm_ws_opt = value;
-    return 0;
-  }
-  if (strcmp(name, "sssc_precision") == 0) {
-    if (value != 64 && value != 32) return fail(EVOAMD_E_INVALID, "sssc_precision: 64 or 32");
-    c->sssc_prec32 = value == 32;
-    return 0;
-  }
-  if (strcmp(name, "lpj_main_unstaged") == 0) {
-    c->main_unstaged = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "lpj_singular_screen") == 0) {
-    if (value < 0 || value > 2) return fail(EVOAMD_E_INVALID, "lpj_singular_screen: 0 (never), 1 (automatic) or 2 (always)");
-    c->sing_screen = (int)value;
-    return 0;
-  }
-  if (strcmp(name, "gemm_grouped") == 0) {
-    c->gemm_grouped = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "gemm_per_xcd") == 0) {
-    c->gemm_per_xcd = value;
-    return 0;
-  }
-  if (strcmp(name, "init_states_home") == 0) {
-    if (value < -1 || value > 1) return fail(EVOAMD_E_INVALID, "init_states_home: -1 (auto), 0 LDS, 1 global memory");
-    c->init_home = value;
-    return 0;
-  }
-  if (strcmp(name, "background_unit") == 0) {
-    c->bg_unit = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "fold_clear") == 0) {
-    c->fold_clear = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "early_fork") == 0) {
-    c->early_fork = value;
-    return 0;
-  }
-  if (strcmp(name, "merge_small_levels") == 0) {
-    c->merge_small = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "stats_flat") == 0) {
-    c->stats_flat = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "theta_copy_engine") == 0) {
-    c->theta_copy_engine = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "census_lists") == 0) {  // takes effect at the next evoamd_configure
-    c->census_opt = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "sk_spare") == 0) {
-    if (value < -1 || value > 32) return fail(EVOAMD_E_INVALID, "sk_spare: -1 (automatic) or 0 .. 32 workgroups per XCD");
-    c->sk_spare = value;
-    return 0;
-  }
-  if (strcmp(name, "stats_chunks") == 0) {
-    if (value < 1 || value > 16) return fail(EVOAMD_E_INVALID, "stats_chunks: 1 .. 16");
-    c->stats_chunks = value;
-    return 0;
-  }
-  if (strcmp(name, "mailbox_side_stream") == 0) {
-    c->mbox_side = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "fused_estep") == 0) {
-    if (value < 0 || value > 2) return fail(EVOAMD_E_INVALID, "fused_estep: 0 (never), 1 (automatic) or 2 (whenever the shape allows it)");
-    c->fused_opt = value;
-    return 0;
-  }
-  if (strcmp(name, "debug_poison_list") == 0) {
-    c->debug_poison_list = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "debug_fail_stats") == 0) {
-    c->debug_fail_stats = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "state_digest") == 0) {
-    c->use_digest = value != 0;
-    return 0;
-  }
-  if (strcmp(name, "inverse_spd") == 0) {
-    c->spd_inverse = value != 0;
+  for (const OptionRow &o : OPTIONS) {
+    if (strcmp(name, o.name) != 0) continue;
+    if (o.err && !(o.accepts ? o.accepts(value) : (value >= o.lo && value <= o.hi))) return fail(EVOAMD_E_INVALID, "%s", o.err);
+    const int v = o.norm ? o.norm(value) : value;
+    if (o.ifield) c->*o.ifield = v;
+    else c->*o.bfield = v != 0;
+    if (o.after) o.after(c);
     return 0;
   }
   return fail(EVOAMD_E_INVALID, "unknown option '%s'", name);
@@ -905,9 +882,9 @@ static AccLayout acc_layout(const evoamd_ctx *c) {
 static int alloc_pair_bins(evoamd_ctx *c, int scale) {
   const i64 N = c->N;
   const int H = c->H, S = c->S;
-  if (c->pbins.ent) (void)hipFree(c->pbins.ent);
-  if (c->pbins.gcnt) (void)hipFree(c->pbins.gcnt);
-  if (c->pbins.part) (void)hipFree(c->pbins.part);
+  c->pb_ent.reset();
+  c->pb_gcnt.reset();
+  c->pb_part.reset();
   c->pbins = PairBins{};
   c->bins_scale_cur = 0;
   if (H >= 2 && H <= 1024) {
@@ -923,19 +900,19 @@ static int alloc_pair_bins(evoamd_ctx *c, int scale) {
     pb.nsh = std::max((i64)N * S >= (i64)8 << 20 ? 8 : 4, std::min(PB_NSH_MAX, 256 / std::max(1, pb.nb)));
     pb.cap = (int)std::max<i64>(64, (i64)scale * cdiv((i64)N * S, (i64)pb.nb * pb.nwg));
     const size_t ne = (size_t)pb.nb * pb.nwg * pb.cap;
-    const bool got = hipMalloc((void **)&pb.ent, ne * sizeof(double4)) == hipSuccess &&
-                     hipMalloc((void **)&pb.part, (size_t)pb.nb * pb.nsh * 3 * 2 * pb.rf * H * sizeof(double)) == hipSuccess &&
-                     hipMalloc((void **)&pb.gcnt, (size_t)pb.nb * pb.nwg * sizeof(int)) == hipSuccess;
-    if (got) {
-      HIP_TRY(hipMemsetAsync(pb.gcnt, 0, (size_t)pb.nb * pb.nwg * sizeof(int), c->stream));
+    if (c->pb_ent.try_alloc(ne) && c->pb_part.try_alloc((size_t)pb.nb * pb.nsh * 3 * 2 * pb.rf * H) &&
+        c->pb_gcnt.try_alloc((size_t)pb.nb * pb.nwg)) {
+      pb.ent = c->pb_ent;
+      pb.part = c->pb_part;
+      pb.gcnt = c->pb_gcnt;
+      HIP_TRY(hipMemsetAsync(pb.gcnt, 0, c->pb_gcnt.size() * sizeof(int), c->stream));
       c->pbins = pb;
       c->bins_scale_cur = scale;
       c->bins_dirty = false;
     } else {
-      (void)hipGetLastError();
-      if (pb.ent) (void)hipFree(pb.ent);
-      if (pb.part) (void)hipFree(pb.part);
-      if (pb.gcnt) (void)hipFree(pb.gcnt);
+      c->pb_ent.reset();
+      c->pb_part.reset();
+      c->pb_gcnt.reset();
     }
   }
   return 0;
@@ -967,16 +944,20 @@ static int ensure_bins_capacity(evoamd_ctx *c) {
   return 0;
 }
 
-extern "C" int evoamd_configure(evoamd_ctx *c, int model, int64_t N, int D, int H, int S, int S_perm,
-                                int Cmax) {
-  REQUIRE(c, "ctx is NULL");
+// ---- evoamd_configure: unconfigured -> validate -> geometry -> drop -> allocate by group -> clear -> flags -> configured ----
+static int configure_validate(const evoamd_ctx *c, int model, i64 N, int D, int H, int S, int S_perm, int Cmax) {
   REQUIRE(model == EVOAMD_MODEL_BSC || model == EVOAMD_MODEL_SSSC, "unknown model");
   REQUIRE(N > 0 && D > 0 && H > 0 && S > 0, "N, D, H, S must be positive");
   REQUIRE(S_perm == 0 || S_perm == 1, "S_perm must be 0 or 1");
   REQUIRE(Cmax >= 1 && Cmax <= 64 * VK_MAX_C_PER_LANE, "Cmax must be in [1, 256]");
   REQUIRE(S <= 64 * VK_MAX_S_PER_LANE, "S must be <= 1024");
   REQUIRE((i64)N * (S > Cmax ? S : Cmax) < 2147483647LL, "N * max(S, Cmax) must fit in int32");
-  HIP_TRY(hipSetDevice(c->device));
+  if (model == EVOAMD_MODEL_BSC && c->f32_opt)
+    REQUIRE((H % 4) == 0 && (D % 4) == 0, "float32 mode needs H and D to be multiples of 4 (16-byte rows)");
+  return 0;
+}
+
+static void configure_geometry(evoamd_ctx *c, int model, i64 N, int D, int H, int S, int S_perm, int Cmax) {
   c->model = model;
   c->N = N;
   c->D = D;
@@ -986,191 +967,193 @@ extern "C" int evoamd_configure(evoamd_ctx *c, int model, int64_t N, int D, int 
   c->Cmax = Cmax;
   c->HW = (H + 63) / 64;
   c->L = S + S_perm;
-  const i64 HW = c->HW;
   c->ldY = (model == EVOAMD_MODEL_SSSC) ? D + 3 * H : D;  // ES3C: [Y | Es | Ez | Ed]
-  ALLOC(c->Y, (size_t)N * c->ldY);
-  ALLOC(c->yy, (size_t)N);
-  ALLOC(c->y2sum, (size_t)D);
-  ALLOC(c->states, (size_t)N * S * HW);
-  ALLOC(c->cand, (size_t)N * Cmax * HW);
-  if (H <= DIG_MAX_H) {
-    ALLOC(c->dig, (size_t)N * S);
-    ALLOC(c->cand_dig, (size_t)N * Cmax);
-  } else {  // latent indices do not fit the digest's 14-bit slots: every kernel takes its word path
-    if (c->dig) (void)hipFree(c->dig);
-    if (c->cand_dig) (void)hipFree(c->cand_dig);
-    c->dig = c->cand_dig = nullptr;
-  }
-  ALLOC(c->lpj, (size_t)N * c->L);
-  ALLOC(c->lpj_alt, (size_t)N * c->L);
-  ALLOC(c->cand_lpj, (size_t)N * Cmax);
-  ALLOC(c->cand_counts, (size_t)N);
-  ALLOC(c->flags, (size_t)3 * N);
-  ALLOC(c->rowmax, (size_t)N);
-  ALLOC(c->rowsum, (size_t)N);
-  c->n_partial = cdiv(N, 4);
-  ALLOC(c->partial, (size_t)3 * c->n_partial);
-  ALLOC(c->partial2, (size_t)c->n_partial);
-  ALLOC(c->diag, (size_t)H);
-  const int SC = S > Cmax ? S : Cmax;  // the bool staging area (N x SC x H bytes at most) grows on demand: ensure_stage
-  ALLOC(c->W, (size_t)D * H);
-  ALLOC(c->tmpA, (size_t)H * H);
-  ALLOC(c->tmpB, (size_t)H * H);
-  ALLOC(c->tmpC, (size_t)H * H);
-  // two ping-pong H x H partners | pivoted path: D, Pn (2 x H x 32 each), ipiv, perm (unblocked,
-  // H > 1024: colp | rowp | perm in the same place) | SPD path: Pinv (2 x 2 x 256), diag (2 x H)
-  ALLOC(c->gjwork, (size_t)2 * H * H + (size_t)132 * H + 1040 + 4 * GJS32 * GJS32);  // + pivot inverses of the 32-column path
-  if (model == EVOAMD_MODEL_BSC) {
-    ALLOC(c->Es, (model == EVOAMD_MODEL_BSC && c->f32_opt) ? 1 : (size_t)N * H);
-  } else {
-    if (c->Es) { (void)hipFree(c->Es); }
-    c->Es = nullptr;  // lives inside c->Y for SSSC
-  }
+  c->f32 = model == EVOAMD_MODEL_BSC && c->f32_opt;
   c->acc_n = acc_len(c);
   // in front of the packed accumulator, cleared by the same memset: [overflow census (4) | CS_SLICES column-sum
   // slices of 3 H | overflow H x H pair] (ES3C)
   c->pre_n = (model == EVOAMD_MODEL_SSSC) ? 4 + (i64)CS_SLICES * 3 * H : 4 + (i64)BSC_CS_SLICES * H;
   c->ovf_n = c->pre_n + ((model == EVOAMD_MODEL_SSSC) ? 2 * (i64)H * H : 0);
-  ALLOC(c->acc_base, (size_t)c->ovf_n + c->acc_n + DP_COUNT);  // [... |] packed accumulator, then the scalar block (one D2H)
+}
+
+// What belongs to the previous geometry and is rebuilt on demand (or by the groups below where this one needs it).
+static void configure_drop(evoamd_ctx *c) {
+  // masks / reconstructions: their buffers are N x D of THAT shard
+  for (DevBuf<uint8_t> *b : {&c->mask_infr, &c->mask_x, &c->keep_x, &c->row_any}) b->reset();
+  c->Yrec.reset();
+  // the general device EA, sized by the geometry (evoamd_evolve_states)
+  c->cand_raw.reset();
+  c->dupold.reset();
+  c->gen_start.reset();
+  // W^T is sized by (H, D) of the geometry it was built for (ES3C: evoamd_upload_masks, derive_from_theta,
+  // compute_reconstruction; EBSC allocates it below) -- never reused across a configure: a larger D would write past its end
+  c->tmpWt.reset();
+  c->Wt.reset();
+  c->init_scratch.reset();
+  c->huge.reset();
+  c->huge_ctl.reset();
+  c->huge_slots = c->huge_kc = 0;
+  for (DevBuf<float> *b : {&c->Yf, &c->Ytf, &c->Wf, &c->Bf, &c->Esf}) b->reset();
+  c->Yt.reset();
+}
+
+static int configure_alloc_common(evoamd_ctx *c) {
+  const size_t N = (size_t)c->N, D = (size_t)c->D, H = (size_t)c->H, S = (size_t)c->S, Cmax = (size_t)c->Cmax, HW = (size_t)c->HW;
+  TRY(c->Y.alloc(N * c->ldY));
+  TRY(c->yy.alloc(N));
+  TRY(c->y2sum.alloc(D));
+  TRY(c->states.alloc(N * S * HW));
+  TRY(c->cand.alloc(N * Cmax * HW));
+  if (H <= DIG_MAX_H) {
+    TRY(c->dig.alloc(N * S));
+    TRY(c->cand_dig.alloc(N * Cmax));
+  } else {  // latent indices do not fit the digest's 14-bit slots: every kernel takes its word path
+    c->dig.reset();
+    c->cand_dig.reset();
+  }
+  TRY(c->lpj.alloc(N * c->L));
+  TRY(c->lpj_alt.alloc(N * c->L));
+  TRY(c->cand_lpj.alloc(N * Cmax));
+  TRY(c->cand_counts.alloc(N));
+  TRY(c->flags.alloc(3 * N));
+  TRY(c->rowmax.alloc(N));
+  TRY(c->rowsum.alloc(N));
+  TRY(c->partial.alloc((size_t)3 * cdiv(c->N, 4)));
+  TRY(c->partial2.alloc(cdiv(c->N, 4)));
+  TRY(c->diag.alloc(H));
+  // (the bool staging area, N x max(S, Cmax) x H bytes at most, grows on demand)
+  TRY(c->W.alloc(D * H));
+  TRY(c->tmpA.alloc(H * H));
+  TRY(c->tmpB.alloc(H * H));
+  TRY(c->tmpC.alloc(H * H));
+  // two ping-pong H x H partners | pivoted path: D, Pn (2 x H x 32 each), ipiv, perm (unblocked,
+  // H > 1024: colp | rowp | perm in the same place) | SPD path: Pinv (2 x 2 x 256), diag (2 x H)
+  TRY(c->gjwork.alloc(2 * H * H + 132 * H + 1040 + 4 * GJS32 * GJS32));  // + pivot inverses of the 32-column path
+  TRY(c->G.alloc(H * H));
+  TRY(c->acc_base.alloc((size_t)c->ovf_n + c->acc_n + DP_COUNT));  // [... |] packed accumulator, then the scalar block (one D2H)
   c->census = c->acc_base;
   c->acc = c->acc_base + c->ovf_n;
   c->dpar = c->acc + c->acc_n;
-  ALLOC(c->err, 8);
+  TRY(c->err.alloc(8));
   c->sing_gen = c->err + 4;
-  c->acc_clean = c->clist_clean = false;
-  c->huge_slots = c->huge_kc = 0;
-  if (c->huge) (void)hipFree(c->huge);
-  if (c->huge_ctl) (void)hipFree(c->huge_ctl);
-  c->huge = nullptr;
-  c->huge_ctl = nullptr;
-  if (model == EVOAMD_MODEL_SSSC && H > SSSC_KCAP) {
+  // Y^T for B = Y W on the 128-tile kernel (measured: pays at H = 1024, D = 256 -- c5 2.07 -> 1.90 ms --, equal at H = 512,
+  // slower at H = 256 / D = 64 where a tile has four K slabs; option value 2 forces it from H = 128 on for the tests).
+  // Optional: the row-major product serves.
+  if (!c->f32 && c->b_tn_opt && c->N >= 8192 && (c->H % 2) == 0 &&
+      ((c->H >= 768 && c->D >= 128) || (c->b_tn_opt == 2 && c->H >= 128 && c->D >= 32))) {
+    c->ldYt = ((c->N + 3) / 4) * 4;
+    (void)c->Yt.try_alloc(D * c->ldYt);
+  }
+  return 0;
+}
+
+static int configure_alloc_ebsc(evoamd_ctx *c) {
+  const size_t N = (size_t)c->N, D = (size_t)c->D, H = (size_t)c->H;
+  TRY(c->Es_own.alloc(c->f32 ? 1 : N * H));
+  c->Es = c->Es_own;
+  TRY(c->Wt.alloc(H * D));
+  TRY(c->Bm.alloc(c->f32 ? 1 : N * H));
+  if (c->f32) {
+    c->ldYt = ((c->N + 3) / 4) * 4;
+    TRY(c->Yf.alloc(N * D));
+    TRY(c->Ytf.alloc(D * c->ldYt));
+    TRY(c->Wf.alloc(D * H));
+    TRY(c->Bf.alloc(N * H));
+    TRY(c->Esf.alloc(N * H));
+  }
+  return 0;
+}
+
+static int configure_alloc_es3c(evoamd_ctx *c) {
+  const size_t N = (size_t)c->N, H = (size_t)c->H;
+  c->Es_own.reset();
+  c->Es = c->Y + c->D;  // lives inside c->Y
+  TRY(c->Psi.alloc(H * H));
+  TRY(c->GP.alloc(H * H));
+  TRY(c->DG.alloc(H));
+  TRY(c->D1.alloc(H));
+  TRY(c->PT.alloc(H * H));
+  TRY(c->Bm.alloc(N * H));
+  TRY(c->mus.alloc(H));
+  TRY(c->pilbar_v.alloc(H));
+  TRY(c->pies.alloc(H));
+  TRY(c->rowF.alloc(N));
+  TRY(c->rowcnt.alloc(N));
+  TRY(c->defer.alloc(2 * (N + 1) + 2));  // two lists of N datapoints, each with its counter behind it; + the reduce kernel's arrival counter
+  TRY(c->fpart.alloc((size_t)3 * R3_THREADS));
+  if (c->H > SSSC_KCAP) {
     // the reference evaluates a state with any number of active latents (sssc.py:261-324); above SSSC_KCAP the k x k
     // system does not fit a CU's LDS and the wavefront kernel works in one of these slots (at most 16, at most 256 MB)
-    const size_t slot = big_slot_doubles(H);
-    c->huge_kc = H;
+    const size_t slot = big_slot_doubles(c->H);
+    c->huge_kc = c->H;
     c->huge_slots = (int)std::max<size_t>(1, std::min<size_t>(16, ((size_t)256 << 20) / (slot * sizeof(double))));
-    ALLOC(c->huge, slot * (size_t)c->huge_slots);
-    ALLOC(c->huge_ctl, (size_t)c->huge_slots);
-    HIP_TRY(hipMemsetAsync(c->huge_ctl, 0, (size_t)c->huge_slots * sizeof(int), c->stream));
+    TRY(c->huge.alloc(slot * (size_t)c->huge_slots));
+    TRY(c->huge_ctl.alloc((size_t)c->huge_slots));
   }
-  for (float **fp : {&c->Yf, &c->Ytf, &c->Wf, &c->Bf, &c->Esf}) {
-    if (*fp) (void)hipFree(*fp);
-    *fp = nullptr;
+  return 0;
+}
+
+// ES3C: the overflow lists of a batch of N x max(S, Cmax) pairs and the census lists of the N x S resident states
+static int configure_alloc_lists(evoamd_ctx *c) {
+  const size_t words = list_cap(c->N * (i64)std::max(c->S, c->Cmax)) * LIST_SHARDS;
+  TRY(c->list1.alloc(words));
+  TRY(c->list2.alloc(words));
+  TRY(c->list3.alloc(words));
+  TRY(c->list_n.alloc(4 * LIST_SHARDS));
+  c->clist.reset();
+  c->clist_n.reset();
+  c->ovf_rec.reset();
+  if (c->census_opt) {
+    TRY(c->clist.alloc(3 * list_cap(c->N * (i64)c->S) * LIST_SHARDS));
+    TRY(c->clist_n.alloc(4 * LIST_SHARDS));
+    TRY(c->ovf_rec.alloc((size_t)c->N * c->S));
   }
-  if (c->Yt) (void)hipFree(c->Yt);
-  c->Yt = nullptr;
-  c->f32 = model == EVOAMD_MODEL_BSC && c->f32_opt;
-  // (measured: pays at H = 1024, D = 256 -- c5 2.07 -> 1.90 ms --, equal at H = 512, slower at H = 256 / D = 64 where a
-  // tile has four K slabs; option value 2 forces it from H = 128 on for the tests)
-  if (!c->f32 && c->b_tn_opt && N >= 8192 && (H % 2) == 0 &&
-      ((H >= 768 && D >= 128) || (c->b_tn_opt == 2 && H >= 128 && D >= 32))) {
-    c->ldYt = ((N + 3) / 4) * 4;
-    if (hipMalloc((void **)&c->Yt, (size_t)D * c->ldYt * sizeof(double)) == hipSuccess) {
-      HIP_TRY(hipMemsetAsync(c->Yt, 0, (size_t)D * c->ldYt * sizeof(double), c->stream));
-    } else {  // optional: the row-major product serves
-      (void)hipGetLastError();
-      c->Yt = nullptr;
-    }
-  }
-  if (c->f32) REQUIRE((H % 4) == 0 && (D % 4) == 0, "float32 mode needs H and D to be multiples of 4 (16-byte rows)");
-  if (model == EVOAMD_MODEL_BSC) {
-    ALLOC(c->Wt, (size_t)H * D);
-    ALLOC(c->G, (size_t)H * H);
-    ALLOC(c->Bm, c->f32 ? 1 : (size_t)N * H);
-    if (c->f32) {
-      c->ldYt = ((N + 3) / 4) * 4;
-      ALLOC(c->Yf, (size_t)N * D);
-      ALLOC(c->Ytf, (size_t)D * c->ldYt);
-      ALLOC(c->Wf, (size_t)D * H);
-      ALLOC(c->Bf, (size_t)N * H);
-      ALLOC(c->Esf, (size_t)N * H);
-      HIP_TRY(hipMemsetAsync(c->Ytf, 0, (size_t)D * c->ldYt * sizeof(float), c->stream));
-    }
-  } else {
-    // W^T (incomplete data) is sized by (H, D) of the geometry it was built for: rebuilt on demand (evoamd_upload_masks,
-    // derive_from_theta), never reused across a configure -- a larger D would write past its end
-    if (c->Wt) (void)hipFree(c->Wt);
-    c->Wt = nullptr;
-    ALLOC(c->G, (size_t)H * H);
-    ALLOC(c->Psi, (size_t)H * H);
-    ALLOC(c->GP, (size_t)H * H);
-    ALLOC(c->DG, (size_t)H);
-    ALLOC(c->D1, (size_t)H);
-    ALLOC(c->PT, (size_t)H * H);
-    ALLOC(c->Bm, (size_t)N * H);
-    ALLOC(c->mus, (size_t)H);
-    ALLOC(c->pilbar_v, (size_t)H);
-    ALLOC(c->pies, (size_t)H);
-    ALLOC(c->rowF, (size_t)N);
-    ALLOC(c->rowcnt, (size_t)N);
-    ALLOC(c->defer, 2 * ((size_t)N + 1) + 2);  // two lists of N datapoints, each with its counter behind it; + the reduce kernel's arrival counter
-    HIP_TRY(hipMemsetAsync(c->defer, 0, (2 * ((size_t)N + 1) + 2) * sizeof(int), c->stream));
-    ALLOC(c->fpart, (size_t)3 * R3_THREADS);
-    c->last_estep_fused = false;
-    c->list_words = 0;
-    int rl = ensure_lists(c, (i64)N * SC);
-    if (rl) return rl;
-    ALLOC(c->list_n, 4 * LIST_SHARDS);
-    if (c->clist) (void)hipFree(c->clist);
-    if (c->clist_n) (void)hipFree(c->clist_n);
-    if (c->ovf_rec) (void)hipFree(c->ovf_rec);
-    c->clist = c->clist_n = nullptr;
-    c->ovf_rec = nullptr;
-    c->clist_words = c->ovf_rec_n = 0;
-    if (c->census_opt && N * (i64)S > 0) {
-      c->clist_words = list_cap((i64)N * S) * LIST_SHARDS;
-      ALLOC(c->clist, 3 * c->clist_words);
-      ALLOC(c->clist_n, 4 * LIST_SHARDS);
-      HIP_TRY(hipMemsetAsync(c->clist_n, 0, 4 * LIST_SHARDS * sizeof(int), c->stream));
-      c->ovf_rec_n = (size_t)N * S;
-      ALLOC(c->ovf_rec, c->ovf_rec_n);
-    }
-  }
-  {
-    int rb = alloc_pair_bins(c, c->bins_scale);
-    if (rb) return rb;
-  }
-  if (c->h_acc) (void)hipHostFree(c->h_acc);
-  if (c->h_par) (void)hipHostFree(c->h_par);
-  if (!c->h_err) HIP_TRY(hipHostMalloc((void **)&c->h_err, 4 * sizeof(int), hipHostMallocDefault));
-  if (!c->h_dpar) HIP_TRY(hipHostMalloc((void **)&c->h_dpar, (DP_COUNT + 8) * sizeof(double), hipHostMallocDefault));
-  c->h_par_n = (size_t)D * H + (size_t)H * H + 3 * (size_t)H;
-  HIP_TRY(hipHostMalloc((void **)&c->h_acc, ((size_t)c->acc_n + DP_COUNT) * sizeof(double), hipHostMallocDefault));
-  HIP_TRY(hipHostMalloc((void **)&c->h_par, c->h_par_n * sizeof(double), hipHostMallocDefault));
-  if (c->h_theta) (void)hipHostFree(c->h_theta);
-  HIP_TRY(hipHostMalloc((void **)&c->h_theta, (c->h_par_n + MAILBOX_HDR) * sizeof(double),
-                        hipHostMallocCoherent | hipHostMallocMapped));
+  return 0;
+}
+
+static int configure_alloc_host(evoamd_ctx *c) {
+  const size_t par_n = (size_t)c->D * c->H + (size_t)c->H * c->H + 3 * (size_t)c->H;
+  if (!c->h_err) TRY(c->h_err.alloc(4));
+  if (!c->h_dpar) TRY(c->h_dpar.alloc(DP_COUNT + 8));
+  TRY(c->h_acc.alloc((size_t)c->acc_n + DP_COUNT));
+  TRY(c->h_par.alloc(par_n));
+  c->h_theta_dev = nullptr;
+  TRY(c->h_theta.alloc(par_n + MAILBOX_HDR, hipHostMallocCoherent | hipHostMallocMapped));
   memset(c->h_theta, 0, MAILBOX_HDR * sizeof(double));
   HIP_TRY(hipHostGetDevicePointer((void **)&c->h_theta_dev, c->h_theta, 0));
   if (!c->mbox_counter) {
-    HIP_TRY(hipMalloc((void **)&c->mbox_counter, sizeof(unsigned)));
+    TRY(c->mbox_counter.alloc(1));
     HIP_TRY(hipMemset(c->mbox_counter, 0, sizeof(unsigned)));
   }
-  c->h_theta_fresh = false;
-  HIP_TRY(hipMemsetAsync(c->Y, 0, (size_t)N * c->ldY * sizeof(double), c->stream));
-  HIP_TRY(hipMemsetAsync(c->flags, 0, (size_t)3 * N * sizeof(unsigned), c->stream));
-  HIP_TRY(hipMemsetAsync(c->cand_counts, 0, (size_t)N * sizeof(int), c->stream));
-  HIP_TRY(hipMemsetAsync(c->acc_base, 0, ((size_t)c->ovf_n + c->acc_n + DP_COUNT) * sizeof(double), c->stream));
-  HIP_TRY(hipMemsetAsync(c->err, 0, 8 * sizeof(int), c->stream));
+  return 0;
+}
+
+static int configure_clear(evoamd_ctx *c) {
+  auto zero = [&](auto &b) { return hipMemsetAsync(b.get(), 0, b.size() * sizeof(*b.get()), c->stream); };
+  if (c->huge_ctl) HIP_TRY(zero(c->huge_ctl));
+  if (c->Yt) HIP_TRY(zero(c->Yt));
+  if (c->f32) HIP_TRY(zero(c->Ytf));
+  if (c->model == EVOAMD_MODEL_SSSC) {
+    HIP_TRY(zero(c->defer));
+    if (c->clist_n) HIP_TRY(zero(c->clist_n));
+  }
+  HIP_TRY(zero(c->Y));
+  HIP_TRY(zero(c->flags));
+  HIP_TRY(zero(c->cand_counts));
+  HIP_TRY(zero(c->acc_base));
+  HIP_TRY(zero(c->err));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  // masks / reconstructions belong to the previous geometry (their buffers are N x D of THAT shard)
-  if (c->mask_infr) (void)hipFree(c->mask_infr);
-  if (c->mask_x) (void)hipFree(c->mask_x);
-  if (c->Yrec) (void)hipFree(c->Yrec);
-  c->mask_infr = c->mask_x = nullptr;
-  c->Yrec = nullptr;
+  return 0;
+}
+
+// Nothing the previous configuration left is valid; every generation counter moves on.
+static void configure_reset_flags(evoamd_ctx *c) {
+  c->acc_clean = c->clist_clean = false;
+  if (c->model == EVOAMD_MODEL_SSSC) c->last_estep_fused = false;
+  c->h_theta_fresh = false;
   c->yrec_valid = c->rec_in_stats = false;
-  if (c->keep_x) (void)hipFree(c->keep_x);
-  if (c->row_any) (void)hipFree(c->row_any);
-  c->keep_x = c->row_any = nullptr;
   c->keep_x_valid = false;
   c->rel_frac = -1.0;
-  if (c->cand_raw) (void)hipFree(c->cand_raw);  // sized by the geometry: rebuilt on demand (evoamd_evolve_states)
-  if (c->dupold) (void)hipFree(c->dupold);
-  if (c->gen_start) (void)hipFree(c->gen_start);
-  c->cand_raw = c->dupold = nullptr;
-  c->gen_start = nullptr;
-  c->configured = true;
   c->pays_agreed = -1;
   c->pending_skip = 0;
   c->gen++;
@@ -1178,16 +1161,33 @@ extern "C" int evoamd_configure(evoamd_ctx *c, int model, int64_t N, int D, int 
   c->census_gen = 0;
   c->census_skip = 0;
   c->have_data = c->have_params = c->have_cand = c->rows_fresh = false;
-  if (c->tmpWt) (void)hipFree(c->tmpWt);  // sized by (H, D): rebuilt on demand
-  c->tmpWt = nullptr;
   c->yhat_valid = c->stats_rows_valid = c->rec_resident = c->yrec_from_pass = false;
   c->theta_bak_valid = false;
   c->lists_clean = c->need_known = c->cand_from_device = false;  // fresh (uninitialised) overflow counters
   c->kn_lost = false;
   c->pred_N = 0;
-  c->init_scratch_words = 0;
-  if (c->init_scratch) (void)hipFree(c->init_scratch);
-  c->init_scratch = nullptr;
+}
+
+extern "C" int evoamd_configure(evoamd_ctx *c, int model, int64_t N, int D, int H, int S, int S_perm,
+                                int Cmax) {
+  REQUIRE(c, "ctx is NULL");
+  c->configured = false;  // until the last line: a configure that fails, at whichever stage, leaves a context that answers "configure first"
+  TRY(configure_validate(c, model, N, D, H, S, S_perm, Cmax));
+  HIP_TRY(hipSetDevice(c->device));
+  configure_geometry(c, model, N, D, H, S, S_perm, Cmax);
+  configure_drop(c);
+  TRY(configure_alloc_common(c));
+  if (model == EVOAMD_MODEL_BSC) {
+    TRY(configure_alloc_ebsc(c));
+  } else {
+    TRY(configure_alloc_es3c(c));
+    TRY(configure_alloc_lists(c));
+  }
+  TRY(alloc_pair_bins(c, c->bins_scale));
+  TRY(configure_alloc_host(c));
+  TRY(configure_clear(c));
+  configure_reset_flags(c);
+  c->configured = true;
   return 0;
 }
 
@@ -1223,17 +1223,16 @@ extern "C" int evoamd_upload_masks(evoamd_ctx *c, const uint8_t *x_infr, const u
   REQUIRE(!(c->f32 && x_infr), "incomplete data is not available in the float32 mode");
   HIP_TRY(hipSetDevice(c->device));
   if (!x_infr) {  // back to complete data (upload_data again restores entries that were zeroed)
-    if (c->mask_infr) (void)hipFree(c->mask_infr);
-    if (c->mask_x) (void)hipFree(c->mask_x);
-    c->mask_infr = c->mask_x = nullptr;
+    c->mask_infr.reset();
+    c->mask_x.reset();
     c->yrec_valid = c->rec_resident = c->yrec_from_pass = false;
     return 0;
   }
   const size_t nd = (size_t)c->N * c->D;
-  ALLOC(c->mask_infr, nd);
-  ALLOC(c->mask_x, nd);
-  ALLOC(c->Yrec, nd);
-  ALLOC(c->row_any, (size_t)c->N);
+  TRY(c->mask_infr.alloc(nd));
+  TRY(c->mask_x.alloc(nd));
+  TRY(c->Yrec.alloc(nd));
+  TRY(c->row_any.alloc((size_t)c->N));
   HIP_TRY(hipMemcpyAsync(c->mask_infr, x_infr, nd, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->mask_x, x ? x : x_infr, nd, hipMemcpyHostToDevice, c->stream));
   // missing entries (NaN in the reference's data) become zeros: they then drop out of ||y_obs||^2
@@ -1243,7 +1242,7 @@ extern "C" int evoamd_upload_masks(evoamd_ctx *c, const uint8_t *x_infr, const u
   HIP_TRY(hipMemsetAsync(c->y2sum, 0, (size_t)c->D * sizeof(double), c->stream));
   launch_colsum<true>(c, c->Y, c->ldY, c->N, c->D, c->y2sum);
   if (c->model == EVOAMD_MODEL_SSSC) {  // W^T (H, D) for the per-datapoint Gram blocks
-    if (!c->Wt) ALLOC(c->Wt, (size_t)c->H * c->D);
+    if (!c->Wt) TRY(c->Wt.alloc((size_t)c->H * c->D));
     if (c->have_params)
       transpose_kernel<<<cdiv((i64)c->H * c->D, 256), 256, 0, c->stream>>>(c->W, c->D, c->H, c->Wt);
   }
@@ -1270,12 +1269,10 @@ extern "C" int evoamd_upload_yrec(evoamd_ctx *c, const double *y_rec) {
   return 0;
 }
 
-static int ensure_stage(evoamd_ctx *c, size_t bytes);
-
 static int pack_to_device(evoamd_ctx *c, const uint8_t *host_bool, i64 nstates, u64 *dst) {
   const size_t bytes = (size_t)nstates * c->H;
   {
-    int rs = ensure_stage(c, bytes);
+    int rs = c->stage.ensure(c, bytes);
     if (rs) return rs;
   }
   HIP_TRY(hipMemcpyAsync(c->stage, host_bool, bytes, hipMemcpyHostToDevice, c->stream));
@@ -1309,7 +1306,7 @@ extern "C" int evoamd_download_states(evoamd_ctx *c, uint8_t *ss_bool) {
   HIP_TRY(hipSetDevice(c->device));
   const i64 ns = c->N * (i64)c->S;
   {
-    int rs = ensure_stage(c, (size_t)ns * c->H);
+    int rs = c->stage.ensure(c, (size_t)ns * c->H);
     if (rs) return rs;
   }
   unpack_states_kernel<<<cdiv(ns * c->H, 256), 256, 0, c->stream>>>(c->states, c->stage, ns, c->H, c->HW);
@@ -1328,7 +1325,7 @@ extern "C" int evoamd_upload_states_packed(evoamd_ctx *c, const uint8_t *packed,
   const i64 ns = n * (i64)c->S;
   const size_t bytes = (size_t)ns * PB;
   {
-    int rs = ensure_stage(c, bytes);
+    int rs = c->stage.ensure(c, bytes);
     if (rs) return rs;
   }
   HIP_TRY(hipMemcpyAsync(c->stage, packed, bytes, hipMemcpyHostToDevice, c->stream));
@@ -1365,7 +1362,7 @@ extern "C" int evoamd_init_states(evoamd_ctx *c, double p_init, uint64_t seed, i
     const int PB = (c->H + 7) / 8;
     const size_t off = (((size_t)S * PB + 7) / 8) * 8;
     {
-      int rs = ensure_stage(c, off + (size_t)S * HW * sizeof(u64));
+      int rs = c->stage.ensure(c, off + (size_t)S * HW * sizeof(u64));
       if (rs) return rs;
     }
     u64 *table = (u64 *)(c->stage + off);
@@ -1409,11 +1406,7 @@ extern "C" int evoamd_init_states(evoamd_ctx *c, double p_init, uint64_t seed, i
       i64 grid = std::min<i64>(cdiv(c->N, W), (i64)c->n_cu * 2);
       while (grid > 1 && (size_t)grid * W * wave_words * sizeof(u64) > ((size_t)256 << 20)) grid >>= 1;
       const size_t need = (size_t)grid * W * wave_words;
-      if (need > c->init_scratch_words) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        ALLOC(c->init_scratch, need);
-        c->init_scratch_words = need;
-      }
+      TRY(c->init_scratch.ensure(c, need));
       a.scratch = c->init_scratch;
       SpanGuard g(c, KID_INIT_STATES);
       init_states_kernel<false><<<(unsigned)grid, 64 * W, 0, c->stream>>>(a);
@@ -1450,7 +1443,7 @@ extern "C" int evoamd_download_states_packed(evoamd_ctx *c, uint8_t *packed, int
   const i64 ns = n * (i64)c->S;
   const size_t bytes = (size_t)ns * PB;
   {
-    int rs = ensure_stage(c, bytes);
+    int rs = c->stage.ensure(c, bytes);
     if (rs) return rs;
   }
   packbits_from_words_kernel<<<cdiv(ns * PB, 256), 256, 0, c->stream>>>(c->states + (size_t)n0 * c->S * c->HW, c->stage, ns,
@@ -1524,17 +1517,7 @@ static bool gram_is_small(int M, i64 K) { return M <= 512 && K <= 4096; }
 static double *streamk_workspace(evoamd_ctx *c, unsigned wpx, i64 n_real, int *segmax) {
   *segmax = (int)(n_real / wpx) + 2;
   const size_t need = (size_t)8 * wpx * (size_t)*segmax * GEMM_T * GEMM_T;
-  if (need > c->gemm_ws_n) {
-    if (c->gemm_ws) (void)hipFree(c->gemm_ws);
-    c->gemm_ws = nullptr;
-    c->gemm_ws_n = 0;
-    if (hipMalloc((void **)&c->gemm_ws, need * sizeof(double)) != hipSuccess) {
-      (void)hipGetLastError();
-      c->gemm_ws = nullptr;
-      return nullptr;
-    }
-    c->gemm_ws_n = need;
-  }
+  if (need > c->gemm_ws.size() && !c->gemm_ws.try_alloc(need)) return nullptr;
   return c->gemm_ws;
 }
 
@@ -1695,7 +1678,7 @@ static int derive_from_theta(evoamd_ctx *c, bool updated) {
       DBG_SYNC(c, "derive_from_theta: G = W^T W");
     }
     if (c->mask_infr) {  // incomplete data: the wavefront kernel forms W_obs^T W_obs from W^T (sssc.py:276)
-      if (!c->Wt) ALLOC(c->Wt, (size_t)H * D);
+      if (!c->Wt) TRY(c->Wt.alloc((size_t)H * D));
       transpose_kernel<<<cdiv((i64)H * D, 256), 256, 0, c->stream>>>(c->W, D, H, c->Wt);
     }
     sssc_tables_kernel<<<cdiv((i64)H * H, 256), 256, 0, c->stream>>>(c->G, c->Psi, c->mus, c->pilbar_v, c->dpar, H, c->D1,
@@ -2128,7 +2111,7 @@ static int ensure_census(evoamd_ctx *c) {
   unsigned grid = cdiv(total, CENSUS_T * CENSUS_PPT);
   if (grid > (unsigned)(8 * c->n_cu)) grid = (unsigned)(8 * c->n_cu);
   SpanGuard g(c, KID_MISC);
-  census_kernel<<<grid, CENSUS_T, 0, c->stream>>>(c->dig, total, c->clist, (i64)c->clist_words, c->clist_n, (int)list_cap(total), c->err);
+  census_kernel<<<grid, CENSUS_T, 0, c->stream>>>(c->dig, total, c->clist, (i64)c->clist_words(), c->clist_n, (int)list_cap(total), c->err);
   HIP_TRY(hipGetLastError());
   DBG_SYNC(c, "census");
   if (c->debug_poison_list) {  // test hook: entry 0 of shard 0 of the 3..4 list becomes an out-of-range (n, state) pair
@@ -2193,8 +2176,8 @@ static Es3cLists es3c_lists(const evoamd_ctx *c, int cap) {
   ls.i3 = {ls.o3.items, ls.o3.counts, cap};
   if (c->clist && c->clist_n) {
     ls.cA = {c->clist, c->clist_n, cap};
-    ls.cB = {c->clist + c->clist_words, c->clist_n + LIST_SHARDS, cap};
-    ls.cC = {c->clist + 2 * c->clist_words, c->clist_n + 2 * LIST_SHARDS, cap};
+    ls.cB = {c->clist + c->clist_words(), c->clist_n + LIST_SHARDS, cap};
+    ls.cC = {c->clist + 2 * c->clist_words(), c->clist_n + 2 * LIST_SHARDS, cap};
     ls.empty = {c->clist, c->clist_n + 3 * LIST_SHARDS, 0};
   }
   return ls;
@@ -2582,47 +2565,24 @@ extern "C" int evoamd_set_candidates(evoamd_ctx *c, const uint8_t *cand_bool, co
   return 0;
 }
 
-static int ensure_stage(evoamd_ctx *c, size_t bytes) {
-  if (bytes > c->stage_bytes) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    ALLOC(c->stage, bytes);
-    c->stage_bytes = bytes;
-  }
-  return 0;
-}
-
-static int ensure_tmp(evoamd_ctx *c, size_t state_words, size_t lpj_n) {
-  if (state_words > c->tmp_states_words) {
-    ALLOC(c->tmp_states, state_words);
-    c->tmp_states_words = state_words;
-  }
-  if (lpj_n > c->tmp_lpj_n) {
-    ALLOC(c->tmp_lpj, lpj_n);
-    c->tmp_lpj_n = lpj_n;
-  }
-  return 0;
-}
-
 extern "C" int evoamd_lpj_shared(evoamd_ctx *c, const uint8_t *states_bool, int C, double *lpj_out) {
   REQUIRE(c && c->configured && c->have_data && c->have_params, "configure, upload_data and set_params first");
   REQUIRE(states_bool && lpj_out && C > 0, "bad arguments");
   REQUIRE((i64)c->N * C < 2147483647LL, "N * C must fit in int32");
   HIP_TRY(hipSetDevice(c->device));
-  int r = ensure_tmp(c, (size_t)C * c->HW, (size_t)c->N * C);
+  TRY(c->tmp_states.ensure(c, (size_t)C * c->HW));
+  int r = c->tmp_lpj.ensure(c, (size_t)c->N * C);
   if (r) return r;
   r = ensure_B(c);
   if (r) return r;
   // stage through a private buffer (C*H may exceed the configured staging area)
-  uint8_t *st = nullptr;
-  HIP_TRY(hipMalloc((void **)&st, (size_t)C * c->H));
+  DevBuf<uint8_t> st;
+  TRY(st.alloc((size_t)C * c->H));
   HIP_TRY(hipMemcpyAsync(st, states_bool, (size_t)C * c->H, hipMemcpyHostToDevice, c->stream));
   pack_states_kernel<<<cdiv((i64)C * c->HW, 256), 256, 0, c->stream>>>(st, c->tmp_states, C, c->H, c->HW);
   if (c->model == EVOAMD_MODEL_SSSC) {
     r = ensure_lists(c, (i64)c->N * C);
-    if (r) {
-      (void)hipFree(st);
-      return r;
-    }
+    if (r) return r;
   }
   Batch b = {c->tmp_states, nullptr, c->Y, c->Bm, c->yy, c->N, C, 1, c->tmp_lpj, C, 0, c->flags + c->N, KID_MISC, 2};
   b.mask = c->mask_infr;
@@ -2633,7 +2593,6 @@ extern "C" int evoamd_lpj_shared(evoamd_ctx *c, const uint8_t *states_bool, int 
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) r = fail(EVOAMD_E_HIP, "lpj_shared copy back: %s", hipGetErrorString(e));
   }
-  (void)hipFree(st);
   if (r) return r;
   if (c->model == EVOAMD_MODEL_SSSC) return check_err(c);
   return 0;
@@ -2644,10 +2603,11 @@ static int lpj_single_impl(evoamd_ctx *c, const double *y, const uint8_t *x_infr
   REQUIRE(c && c->configured && c->have_params, "configure and set_params first");
   REQUIRE(y && states_bool && lpj_out && C > 0, "bad arguments");
   HIP_TRY(hipSetDevice(c->device));
-  int r = ensure_tmp(c, (size_t)C * c->HW, (size_t)C + 2);
+  TRY(c->tmp_states.ensure(c, (size_t)C * c->HW));
+  int r = c->tmp_lpj.ensure(c, (size_t)C + 2);
   if (r) return r;
-  if (!c->tmp_y) ALLOC(c->tmp_y, (size_t)c->D + c->H + 2);
-  r = ensure_stage(c, (size_t)C * c->H);
+  TRY(c->tmp_y.ensure(c, (size_t)c->D + c->H + 2));
+  r = c->stage.ensure(c, (size_t)C * c->H);
   if (r) return r;
   if (c->model == EVOAMD_MODEL_SSSC) {
     r = ensure_lists(c, C);
@@ -2658,7 +2618,7 @@ static int lpj_single_impl(evoamd_ctx *c, const double *y, const uint8_t *x_infr
   HIP_TRY(hipMemcpyAsync(dy, y, (size_t)c->D * sizeof(double), hipMemcpyHostToDevice, c->stream));
   uint8_t *dmask = nullptr;
   if (x_infr) {  // one row of x_infr behind the packed states' staging area
-    r = ensure_stage(c, (size_t)C * c->H + c->D);
+    r = c->stage.ensure(c, (size_t)C * c->H + c->D);
     if (r) return r;
     dmask = c->stage + (size_t)C * c->H;
     HIP_TRY(hipMemcpyAsync(dmask, x_infr, (size_t)c->D, hipMemcpyHostToDevice, c->stream));
@@ -2833,7 +2793,7 @@ static int launch_estep_fused(evoamd_ctx *c, int n_parents, int n_children, uint
   f.list_cap = (int)c->N;
 #ifdef FUSED_PROFILE
   if (!c->fprof) {
-    HIP_TRY(hipMalloc((void **)&c->fprof, 8 * sizeof(unsigned long long)));
+    TRY(c->fprof.alloc(8));
     HIP_TRY(hipMemset(c->fprof, 0, 8 * sizeof(unsigned long long)));
   }
   f.prof = c->fprof;
@@ -2861,7 +2821,7 @@ static int launch_estep_fused(evoamd_ctx *c, int n_parents, int n_children, uint
     c->clist_clean = false;  // the fused kernel appends to them
     f.cen_items = c->clist;
     f.cen_n = c->clist_n;
-    f.cen_stride = (i64)c->clist_words;
+    f.cen_stride = (i64)c->clist_words();
     f.cen_cap = (int)list_cap(c->N * (i64)c->S);
   }
   SpanGuard g(c, KID_ESTEP_FUSED);
@@ -3002,9 +2962,9 @@ extern "C" int evoamd_evolve_states(evoamd_ctx *c, int mutation, int fit_parents
   REQUIRE(!crossing || c->H >= 2, "crossover needs H >= 2");
   HIP_TRY(hipSetDevice(c->device));
   if (!c->cand_raw) {
-    ALLOC(c->cand_raw, (size_t)c->N * c->Cmax * c->HW);
-    ALLOC(c->dupold, (size_t)c->N * EVG_FLAGW);
-    ALLOC(c->gen_start, (size_t)c->N);
+    TRY(c->cand_raw.alloc((size_t)c->N * c->Cmax * c->HW));
+    TRY(c->dupold.alloc((size_t)c->N * EVG_FLAGW));
+    TRY(c->gen_start.alloc((size_t)c->N));
   }
   EvolveArgs a = {};
   a.states = c->states;
@@ -3052,7 +3012,7 @@ extern "C" int evoamd_download_candidates(evoamd_ctx *c, uint8_t *cand_bool, int
   REQUIRE(cand_bool && counts && lpj, "NULL output");
   HIP_TRY(hipSetDevice(c->device));
   const i64 ns = c->N * (i64)c->Cmax;
-  int r = ensure_stage(c, (size_t)ns * c->H);
+  int r = c->stage.ensure(c, (size_t)ns * c->H);
   if (r) return r;
   unpack_states_kernel<<<cdiv(ns * c->H, 256), 256, 0, c->stream>>>(c->cand, c->stage, ns, c->H, c->HW);
   HIP_TRY(hipGetLastError());
@@ -3071,11 +3031,8 @@ extern "C" int64_t evoamd_acc_size(evoamd_ctx *c) { return (c && c->configured) 
 
 static int row_lse(evoamd_ctx *c, const double *lpj, i64 N, int L, double *rowmax, double *rowsum, double *out_slot) {
   const unsigned nb = cdiv(N, 4);
-  if ((i64)nb > c->n_partial) {
-    ALLOC(c->partial, (size_t)3 * nb);
-    ALLOC(c->partial2, (size_t)nb);
-    c->n_partial = nb;
-  }
+  TRY(c->partial.ensure(c, (size_t)3 * nb));
+  TRY(c->partial2.ensure(c, nb));
   if (lpj != c->lpj) c->rows_fresh = false;  // the partial buffer now belongs to another matrix
   SpanGuard g(c, KID_ROW_LSE);
   row_lse_kernel<<<nb, 256, 0, c->stream>>>(lpj, N, L, rowmax, rowsum, c->partial);
@@ -3839,7 +3796,7 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
   StatsFlow fl;
   // the whole statistics pass (everything that reads K^n + lpj and leaves the M-step sums, the GEMM aside)
   std::unique_ptr<SpanGuard> pass(new SpanGuard(c, KID_STATS_PASS));
-  r = ensure_colpart(c, (size_t)p.nblk * (c->model == EVOAMD_MODEL_BSC ? p.H : 3 * p.H));
+  r = c->colpart.ensure(c, (size_t)p.nblk * (c->model == EVOAMD_MODEL_BSC ? p.H : 3 * p.H));
   if (r) return r;
   Es3cPass ep;
   r = stats_sssc_pass(c, p, ep);
@@ -4143,7 +4100,7 @@ static int theta_update_sssc(evoamd_ctx *c, const MstepPlan &p, unsigned long lo
   r = launch_gemm_tn(c, c->W, H, c->W, H, c->G, H, H, H, D, gram);  // G = W^T W (new W)
   if (r) return r;
   const int n_part = (int)std::min<i64>(1024, cdiv(HH, 1024));
-  r = ensure_colpart(c, (size_t)n_part);
+  r = c->colpart.ensure(c, (size_t)n_part);
   if (r) return r;
   if (psi_with_trace)
     sssc_trace_partial_kernel<<<n_part, 256, 0, c->stream>>>(c->acc + a.sz_sz, c->G, H, cdiv(HH, n_part), c->colpart, c->tmpC,
@@ -4194,15 +4151,12 @@ static int theta_update(evoamd_ctx *c, const MstepPlan &p, unsigned long long fo
 static int compute_reconstruction(evoamd_ctx *c) {
   REQUIRE(!c->f32, "reconstruction is not available in the float32 mode");
   const size_t need = (size_t)c->N * c->D;
-  if (need > c->yhat_n) {
-    ALLOC(c->yhat, need);
-    c->yhat_n = need;
-  }
+  TRY(c->yhat.ensure(c, need));
   const double *Wt = c->Wt;
   const double *E = c->Es;
   int lde = c->H;
   if (c->model == EVOAMD_MODEL_SSSC) {
-    if (!c->tmpWt) ALLOC(c->tmpWt, (size_t)c->H * c->D);
+    if (!c->tmpWt) TRY(c->tmpWt.alloc((size_t)c->H * c->D));
     transpose_kernel<<<cdiv((i64)c->H * c->D, 256), 256, 0, c->stream>>>(c->W, c->D, c->H, c->tmpWt);  // (D,H) -> (H,D)
     Wt = c->tmpWt;
     E = c->Y + c->D + c->H;  // Ez block of [Y | Es | Ez | Ed]
@@ -4295,7 +4249,7 @@ static void prefetch_next_pass(evoamd_ctx *c) {
 
 // Spins on the sequence number (falls back to a blocking synchronise after 20 ms of spinning).
 static int mailbox_poll(evoamd_ctx *c, const MstepPlan &p, const MailboxTicket &t) {
-  volatile unsigned long long *flag = (volatile unsigned long long *)c->h_theta;
+  volatile unsigned long long *flag = (volatile unsigned long long *)c->h_theta.get();
   const auto t0 = std::chrono::steady_clock::now();
   unsigned spins = 0;
   while (*flag != t.seq) {
@@ -4350,10 +4304,7 @@ static int mstep_backup(evoamd_ctx *c, const MstepPlan &p) {
   const CopySegs s = theta_segs(c);
   size_t n = 0;
   for (int k = 0; k < 5; k++) n += (size_t)s.n[k];
-  if (n > c->theta_bak_n) {
-    ALLOC(c->theta_bak, n);
-    c->theta_bak_n = n;
-  }
+  TRY(c->theta_bak.ensure(c, n));
   if (p.backup == BACKUP_IN_UPDATE) return 0;  // (valid once the update is enqueued: mstep_attempt)
   theta_backup_kernel<<<(unsigned)std::min<size_t>(256, cdiv((i64)n, 256 * 8)), 256, 0, c->stream_copy>>>(c->theta_bak, s, 0);
   HIP_TRY(hipGetLastError());
@@ -4469,21 +4420,18 @@ extern "C" int evoamd_gemm_tn(evoamd_ctx *c, const double *A, const double *B, d
   REQUIRE(c && A && B && C && K > 0 && M > 0 && Nc > 0, "bad arguments");
   REQUIRE(sym_row0 < 0 || (sym_row0 + Nc == M), "sym_row0: the symmetric block must be the last Nc rows of C");
   HIP_TRY(hipSetDevice(c->device));
-  double *dA = nullptr, *dB = nullptr, *dC = nullptr;
-  hipError_t e = hipMalloc((void **)&dA, (size_t)K * M * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void **)&dB, (size_t)K * Nc * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void **)&dC, (size_t)M * Nc * sizeof(double));
+  DevBuf<double> dA, dB, dC;
+  TRY(dA.alloc((size_t)K * M));
+  TRY(dB.alloc((size_t)K * Nc));
+  TRY(dC.alloc((size_t)M * Nc));
   int r = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(dA, A, (size_t)K * M * sizeof(double), hipMemcpyHostToDevice, c->stream);
+  hipError_t e = hipMemcpyAsync(dA, A, (size_t)K * M * sizeof(double), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(dB, B, (size_t)K * Nc * sizeof(double), hipMemcpyHostToDevice, c->stream);
   GemmTnOpts o;
   o.sym_row0 = sym_row0;
   if (e == hipSuccess) r = launch_gemm_tn(c, dA, M, dB, Nc, dC, Nc, M, Nc, K, o);
   if (e == hipSuccess && !r) e = hipMemcpyAsync(C, dC, (size_t)M * Nc * sizeof(double), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(dA);
-  (void)hipFree(dB);
-  (void)hipFree(dC);
   if (e != hipSuccess) return fail(EVOAMD_E_HIP, "evoamd_gemm_tn: %s", hipGetErrorString(e));
   return r;
 }
@@ -4584,8 +4532,8 @@ extern "C" int evoamd_get_params_sssc(evoamd_ctx *c, double *W, double *pies, do
 extern "C" int evoamd_free_energy(evoamd_ctx *c, const double *lpj, int64_t N, int C, double *Fs_out) {
   REQUIRE(c && lpj && Fs_out && N > 0 && C > 0, "bad arguments");
   HIP_TRY(hipSetDevice(c->device));
-  double *d = nullptr;
-  HIP_TRY(hipMalloc((void **)&d, ((size_t)N * C + 1) * sizeof(double)));
+  DevBuf<double> d;
+  TRY(d.alloc((size_t)N * C + 1));
   hipError_t e = hipMemcpyAsync(d, lpj, (size_t)N * C * sizeof(double), hipMemcpyHostToDevice, c->stream);
   int r = 0;
   if (e != hipSuccess) r = fail(EVOAMD_E_HIP, "free_energy upload: %s", hipGetErrorString(e));
@@ -4595,7 +4543,6 @@ extern "C" int evoamd_free_energy(evoamd_ctx *c, const double *lpj, int64_t N, i
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) r = fail(EVOAMD_E_HIP, "free_energy copy back: %s", hipGetErrorString(e));
   }
-  (void)hipFree(d);
   return r;
 }
 
@@ -4628,7 +4575,8 @@ extern "C" int evoamd_loglik_exact(evoamd_ctx *c, int background, int chunk_stat
   while ((1ll << logC) < C) logC++;
   const int cmax = (u64)C < total ? (int)C : (int)total;  // states of the largest chunk (Hv < 6: one partial chunk)
   HIP_TRY(hipSetDevice(c->device));
-  int r = ensure_tmp(c, (size_t)cmax * c->HW, (size_t)N * cmax);
+  TRY(c->tmp_states.ensure(c, (size_t)cmax * c->HW));
+  int r = c->tmp_lpj.ensure(c, (size_t)N * cmax);
   if (r) return r;
   r = ensure_B(c);
   if (r) return r;
@@ -4639,10 +4587,7 @@ extern "C" int evoamd_loglik_exact(evoamd_ctx *c, int background, int chunk_stat
   // m (N) | z (N) | ll (N) | Fs (1) | partial (ceil(N / 4)) | a (N x Hv) | marg (N x H)
   const unsigned nb = cdiv(N, 4);
   const size_t need = (size_t)3 * N + 1 + nb + (size_t)N * Hv + (size_t)N * H;
-  if (need > c->exact_n) {
-    ALLOC(c->exact_buf, need);
-    c->exact_n = need;
-  }
+  TRY(c->exact_buf.ensure(c, need));
   double *run_m = c->exact_buf, *run_z = run_m + N, *d_ll = run_z + N, *d_Fs = d_ll + N, *d_part = d_Fs + 1;
   double *run_a = marg_out ? d_part + nb : nullptr, *d_marg = marg_out ? d_part + nb + (size_t)N * Hv : nullptr;
   unsigned *flags = c->flags + c->N;  // the clamp flag words evoamd_lpj_shared borrows
@@ -4691,18 +4636,6 @@ extern "C" int evoamd_loglik_exact(evoamd_ctx *c, int background, int chunk_stat
 // ---------------------------------------------------------------------------------------
 // overlapping image patches (kernels_patches.hpp): own scratch, no EM state touched
 // ---------------------------------------------------------------------------------------
-static int ensure_patch_scratch(evoamd_ctx *c, size_t img_n, size_t y_n) {
-  if (img_n > c->patch_img_n) {
-    ALLOC(c->patch_img, img_n);
-    c->patch_img_n = img_n;
-  }
-  if (y_n > c->patch_Y_n) {
-    ALLOC(c->patch_Y, y_n);
-    c->patch_Y_n = y_n;
-  }
-  return 0;
-}
-
 extern "C" int evoamd_patches_extract(evoamd_ctx *c, const double *img, int H, int W, int C, int ph, int pw, int shift,
                                       double *Y_out) {
   REQUIRE(c && img && Y_out, "evoamd_patches_extract: NULL argument");
@@ -4710,7 +4643,8 @@ extern "C" int evoamd_patches_extract(evoamd_ctx *c, const double *img, int H, i
   if (const char *msg = patch_geom_make(H, W, C, ph, pw, shift, &g)) return fail(EVOAMD_E_INVALID, "evoamd_patches_extract: %s", msg);
   HIP_TRY(hipSetDevice(c->device));
   const size_t img_n = (size_t)H * W * C, y_n = (size_t)g.N * g.D;
-  int r = ensure_patch_scratch(c, img_n, y_n);
+  TRY(c->patch_img.ensure(c, img_n));
+  int r = c->patch_Y.ensure(c, y_n);
   if (r) return r;
   HIP_TRY(hipMemcpyAsync(c->patch_img, img, img_n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   {
@@ -4765,7 +4699,8 @@ extern "C" int evoamd_patches_merge(evoamd_ctx *c, const double *Y, int H, int W
   REQUIRE(method == 0 || method == 1, "evoamd_patches_merge: method must be 0 (mean) or 1 (median)");
   HIP_TRY(hipSetDevice(c->device));
   const size_t img_n = (size_t)H * W * C, y_n = (size_t)g.N * g.D;
-  int r = ensure_patch_scratch(c, img_n, y_n);
+  TRY(c->patch_img.ensure(c, img_n));
+  int r = c->patch_Y.ensure(c, y_n);
   if (r) return r;
   HIP_TRY(hipMemcpyAsync(c->patch_Y, Y, y_n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   return launch_patches_merge(c, PatchRows{c->patch_Y}, g, method, img_out);
@@ -4778,12 +4713,10 @@ extern "C" int evoamd_patches_merge_weighted(evoamd_ctx *c, const double *Y, con
   if (const char *msg = patch_geom_make(H, W, C, ph, pw, shift, &g)) return fail(EVOAMD_E_INVALID, "evoamd_patches_merge_weighted: %s", msg);
   HIP_TRY(hipSetDevice(c->device));
   const size_t img_n = (size_t)H * W * C, y_n = (size_t)g.N * g.D;
-  int r = ensure_patch_scratch(c, img_n, y_n);
+  TRY(c->patch_img.ensure(c, img_n));
+  int r = c->patch_Y.ensure(c, y_n);
   if (r) return r;
-  if (y_n > c->patch_V_n) {
-    ALLOC(c->patch_V, y_n);
-    c->patch_V_n = y_n;
-  }
+  TRY(c->patch_V.ensure(c, y_n));
   HIP_TRY(hipMemcpyAsync(c->patch_Y, Y, y_n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->patch_V, V, y_n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   {
@@ -4823,7 +4756,7 @@ extern "C" int evoamd_reconstruct_resident(evoamd_ctx *c, const uint8_t *x) {
     c->rec_uses_keep = true;
   } else if (x) {
     const size_t nd = (size_t)c->N * c->D;
-    if (!c->keep_x) ALLOC(c->keep_x, nd);
+    if (!c->keep_x) TRY(c->keep_x.alloc(nd));
     c->keep_x_valid = false;
     HIP_TRY(hipMemcpyAsync(c->keep_x, x, nd, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));  // x is pageable host memory of the caller
@@ -4870,11 +4803,12 @@ extern "C" int evoamd_patches_merge_resident(evoamd_ctx *c, int H, int W, int C,
   const size_t img_n = (size_t)H * W * C, y_n = (size_t)g.N * g.D;
   const PatchSelect sel = resident_select(c);
   if (c->merge_select_fused) {
-    int r = ensure_patch_scratch(c, img_n, 0);
+    int r = c->patch_img.ensure(c, img_n);
     if (r) return r;
     return launch_patches_merge(c, sel, g, method, img_out);
   }
-  int r = ensure_patch_scratch(c, img_n, y_n);  // select-then-merge (default): y_rec as dense rows, then the kernels of evoamd_patches_merge
+  TRY(c->patch_img.ensure(c, img_n));
+  int r = c->patch_Y.ensure(c, y_n);  // select-then-merge (default): y_rec as dense rows, then the kernels of evoamd_patches_merge
   if (r) return r;
   {
     SpanGuard sg(c, KID_PATCHES);
@@ -4909,11 +4843,7 @@ extern "C" int evoamd_posterior_codes(evoamd_ctx *c, int max_active, double p_mi
   // p | m | map_q | idx | nnz | map_slot | map_state: descending alignment
   const size_t o_p = 0, o_m = o_p + N * A * 8, o_q = o_m + N * A * 8, o_idx = o_q + N * 8, o_nnz = o_idx + N * A * 4,
                o_slot = o_nnz + N * 4, o_state = o_slot + N * 4, need = o_state + N * PB;
-  if (need > c->codes_bytes) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    ALLOC(c->codes_buf, need);
-    c->codes_bytes = need;
-  }
+  TRY(c->codes_buf.ensure(c, need));
   uint8_t *b = c->codes_buf;
   CodesArgs a = {};
   a.Es = sssc ? c->Y + c->D : c->Es;
@@ -5008,23 +4938,9 @@ extern "C" int evoamd_predictive_moments(evoamd_ctx *c, int add_noise, int64_t c
     if (r) return r;
   }
   const size_t nd = (size_t)N * D;
-  if (2 * nd > c->pred_buf_n || (size_t)H * D > c->pred_Wt_n || (size_t)N > c->pred_status_n)
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  if (2 * nd > c->pred_buf_n) {
-    c->pred_buf_n = 0;
-    ALLOC(c->pred_buf, 2 * nd);
-    c->pred_buf_n = 2 * nd;
-  }
-  if ((size_t)H * D > c->pred_Wt_n) {
-    c->pred_Wt_n = 0;
-    ALLOC(c->pred_Wt, (size_t)H * D);
-    c->pred_Wt_n = (size_t)H * D;
-  }
-  if ((size_t)N > c->pred_status_n) {
-    c->pred_status_n = 0;
-    ALLOC(c->pred_status, (size_t)N);
-    c->pred_status_n = (size_t)N;
-  }
+  TRY(c->pred_buf.ensure(c, 2 * nd));
+  TRY(c->pred_Wt.ensure(c, (size_t)H * D));
+  TRY(c->pred_status.ensure(c, (size_t)N));
   // the scalars of the current Theta (a device update leaves them in the scalar block only)
   double dpar[DP_COUNT];
   HIP_TRY(hipMemcpyAsync(dpar, c->dpar, DP_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -5093,17 +5009,6 @@ extern "C" int evoamd_download_predictive(evoamd_ctx *c, double *mean, double *v
 // ---------------------------------------------------------------------------------------
 // samples from the model (kernels_generate.hpp): own buffers, no EM state touched
 // ---------------------------------------------------------------------------------------
-template <typename T>
-static int gen_ensure(evoamd_ctx *c, T **p, size_t *have, size_t need) {
-  if (need <= *have) return 0;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  *have = 0;
-  int r = dev_alloc(p, need);
-  if (r) return r;
-  *have = need;
-  return 0;
-}
-
 extern "C" int evoamd_generate(evoamd_ctx *c, int model, int64_t N, int D, int H, uint64_t seed, uint64_t first_index,
                                const double *Wt, const double *pies, const double *mus, const double *F, double sigma,
                                const uint64_t *s_packed, int keep) {
@@ -5123,13 +5028,12 @@ extern "C" int evoamd_generate(evoamd_ctx *c, int model, int64_t N, int D, int H
   const size_t nd = (size_t)N * D, nh = (size_t)N * H, nw = (size_t)N * HW;
   const size_t par_n = (size_t)H * D + H + (sssc ? (size_t)H + (size_t)H * H : 0);
   c->gen_keep = -1;  // until this call has completed
-  int r = gen_ensure(c, &c->gen_par, &c->gen_par_n, par_n);
-  if (!r) r = gen_ensure(c, &c->gen_y, &c->gen_y_n, nd);
-  if (!r && (keep & EVOAMD_GEN_KEEP_S)) r = gen_ensure(c, &c->gen_s, &c->gen_s_n, nw);
-  if (!r && (keep & EVOAMD_GEN_KEEP_Z)) r = gen_ensure(c, &c->gen_z, &c->gen_z_n, nh);
-  if (!r && (keep & EVOAMD_GEN_KEEP_YMEAN)) r = gen_ensure(c, &c->gen_ymean, &c->gen_ymean_n, nd);
-  if (!r && s_packed) r = gen_ensure(c, &c->gen_sin, &c->gen_sin_n, nw);
-  if (r) return r;
+  TRY(c->gen_par.ensure(c, par_n));
+  TRY(c->gen_y.ensure(c, nd));
+  if (keep & EVOAMD_GEN_KEEP_S) TRY(c->gen_s.ensure(c, nw));
+  if (keep & EVOAMD_GEN_KEEP_Z) TRY(c->gen_z.ensure(c, nh));
+  if (keep & EVOAMD_GEN_KEEP_YMEAN) TRY(c->gen_ymean.ensure(c, nd));
+  if (s_packed) TRY(c->gen_sin.ensure(c, nw));
   double *dWt = c->gen_par, *dpies = dWt + (size_t)H * D, *dmus = dpies + H, *dF = dmus + H;
   HIP_TRY(hipMemcpyAsync(dWt, Wt, (size_t)H * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(dpies, pies, (size_t)H * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -5232,17 +5136,13 @@ extern "C" int evoamd_comm_allreduce_host(evoamd_ctx *c, double *buf, int64_t n,
   REQUIRE(c && buf && n > 0, "bad arguments");
   if (!c->comm) return 0;  // single rank: identity
   HIP_TRY(hipSetDevice(c->device));
-  double *d = nullptr;
-  HIP_TRY(hipMalloc((void **)&d, (size_t)n * sizeof(double)));
+  DevBuf<double> d;
+  TRY(d.alloc((size_t)n));
   HIP_TRY(hipMemcpyAsync(d, buf, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   int rc = g_rccl.AllReduce(d, d, (size_t)n, 8, op == 1 ? 2 : 0, c->comm, c->stream);
-  if (rc != 0) {
-    (void)hipFree(d);
-    return fail(EVOAMD_E_RCCL, "ncclAllReduce failed: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "?");
-  }
+  if (rc != 0) return fail(EVOAMD_E_RCCL, "ncclAllReduce failed: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "?");
   HIP_TRY(hipMemcpyAsync(buf, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  (void)hipFree(d);
   return 0;
 }
 

@@ -67,8 +67,9 @@ class Engine:
 
     # ---- geometry / uploads --------------------------------------------------------------
     def configure(self, model, N, D, H, S, S_perm=0, Cmax=16):
-        self.model = MODEL_BSC if model in (MODEL_BSC, "bsc", "BSC") else MODEL_SSSC
-        check(self.lib.evoamd_configure(self._h, self.model, int(N), int(D), int(H), int(S), int(S_perm), int(Cmax)))
+        m = MODEL_BSC if model in (MODEL_BSC, "bsc", "BSC") else MODEL_SSSC
+        check(self.lib.evoamd_configure(self._h, m, int(N), int(D), int(H), int(S), int(S_perm), int(Cmax)))
+        self.model = m
         self.N, self.D, self.H, self.S, self.S_perm, self.Cmax = int(N), int(D), int(H), int(S), int(S_perm), int(Cmax)
         self.L = self.S + self.S_perm
         self.has_masks = False  # evoamd_configure drops the masks of the previous geometry

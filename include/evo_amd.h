@@ -63,6 +63,9 @@ int evoamd_device_count(int *count);
 int evoamd_ctx_create(int device, evoamd_ctx **out);
 void evoamd_ctx_destroy(evoamd_ctx *ctx);
 int evoamd_synchronize(evoamd_ctx *ctx);
+/* Debug aid: process-wide counts of live device (out[0]) and pinned host (out[1]) allocations of the library.  Equal
+ * before a context is created and after it is destroyed: no buffer outlives its context. */
+int evoamd_debug_live_buffers(int64_t out[2]);
 /* Options: "ebsc_f32" (0/1, default 0; read by the next evoamd_configure of an EBSC geometry): float32 mode -- the data,
  * B = Y W and the per-datapoint E_q[s] rows are stored in float and the two long contractions (B = Y W, Wp = Es^T Y) run
  * on v_mfma_f32_16x16x4_f32; lpj arithmetic, selection, every accumulator and Theta stay float64 (the reference has no
@@ -183,7 +186,8 @@ int evoamd_set_option(evoamd_ctx *ctx, const char *name, int value);
 /* Allocates device storage for N datapoints on this rank: Y (N,D), K^n (N,S,HW) packed,
  * lpj (N,S_perm+S), candidate batch (N,Cmax,HW) + lpj, parameters and accumulators.
  * S_perm is 0 or 1 (permanent all-zero state; evo/variational/utils.py:39-54).
- * Replaces the array allocation of _init_lpj_and_state_arrays (variational/utils.py:94-95). */
+ * Replaces the array allocation of _init_lpj_and_state_arrays (variational/utils.py:94-95).
+ * A call that fails leaves the context unconfigured: every later call answers "configure first" until one succeeds. */
 int evoamd_configure(evoamd_ctx *ctx, int model, int64_t N, int D, int H, int S, int S_perm,
                      int Cmax);
 

@@ -219,10 +219,21 @@ def test_every_option_is_documented():
     """Each name evoamd_set_option accepts (csrc/evo_amd.hip) is described in include/evo_amd.h and listed in
     INTEGRATION.md -- the options are part of the boundary a maintainer binds."""
     src = open(os.path.join(ROOT, "evo_amd", "csrc", "evo_amd.hip")).read()
-    body = src[src.index('extern "C" int evoamd_set_option'):]
-    body = body[:body.index("unknown option")]
-    names = set(re.findall(r'strcmp\(name, "([a-z0-9_]+)"\)', body))
+    body = src[src.index("static const OptionRow OPTIONS[] = {"):]
+    body = body[:body.index("\n};")]
+    rows = re.findall(r'^    \{"([a-z0-9_]+)", OPT_', body, re.M)  # one row of the option table per name
+    names = set(rows)
+    assert len(rows) == len(names), "an option has two rows"
     assert {"bsc_direct", "state_digest", "prefetch_lpj", "overlap_gemm", "inverse_block"} <= names
+    # the 41 options of the library, written out: a row dropped from the table (or an invented one) fails here
+    assert names == {
+        "b_transposed", "background_unit", "bsc_direct", "bsc_stats_wave", "census_lists", "codes_path",
+        "debug_fail_stats", "debug_poison_list", "early_fork", "ebsc_f32", "fold_clear", "fused_estep", "gemm_grouped",
+        "gemm_per_xcd", "gemm_streamk", "gemm_workspace", "init_states_home", "inverse_block", "inverse_spd",
+        "lpj_main_unstaged", "lpj_singular_screen", "mailbox_side_stream", "merge_select_fused", "merge_small_levels",
+        "overlap_gemm", "pair_bins", "pair_bins_auto", "pair_bins_min", "pair_bins_nwg", "pair_bins_scale",
+        "prefetch_lpj", "reconstruct_in_stats", "sk_spare", "sssc_k8", "sssc_precision", "state_digest", "stats_chunks",
+        "stats_flat", "stats_stage", "stats_waves", "theta_copy_engine"}, sorted(names)
     header = open(os.path.join(ROOT, "include", "evo_amd.h")).read()
     integ = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     for n in sorted(names):

@@ -107,7 +107,7 @@ def test_pair_bin_geometry_restates_alloc_pair_bins():
 
 def test_options_of_the_cases_exist():
     hip = _src("evo_amd.hip")
-    names = set(re.findall(r'strcmp\(name, "(\w+)"\) == 0', hip))
+    names = set(re.findall(r'^    \{"(\w+)", OPT_', hip, re.M))  # the rows of the option table
     used = {k for c in sp.CASES for k in c[2]} | set(sp.DEFAULTS) | {"debug_fail_stats", "debug_poison_list"}
     assert used <= names, used - names
     assert set(sp.CONFIGURE_OPTIONS) <= names
