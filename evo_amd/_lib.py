@@ -19,6 +19,16 @@ MODEL_BSC, MODEL_SSSC = 0, 1
 GEN_KEEP = {"s": 1, "z": 2, "y_mean": 4}
 GEN_WHAT = {"y": 0, "s": 1, "z": 2, "y_mean": 3}
 
+# evoamd_debug_validity: names of the bits of out[0] (EVOAMD_VB_*, in bit order) and of out[1..7]
+VALIDITY_BITS = (
+    "have_data", "have_params", "have_cand", "B_valid", "rows_fresh", "stats_rows_valid", "yhat_valid", "rec_resident",
+    "yrec_valid", "yrec_from_pass", "rec_in_stats", "keep_x_valid", "rec_uses_keep", "need_known", "res_need0",
+    "res_need1", "res_need2", "cand_from_device", "lists_clean", "clist_clean", "acc_clean", "wq_copy_valid",
+    "h_theta_fresh", "theta_bak_valid", "kn_lost", "last_estep_fused", "reduce_pending", "bins_dirty", "gen_kept",
+    "prefetch_current", "census_current", "rows_kn_current",
+)
+VALIDITY_WORDS = ("gen", "kn_gen", "theta_gen", "pending_skip", "census_skip", "kn_refill", "pred_N")
+
 # kernel-class ids of evoamd_kernel_time_ms (evo_amd.hip: KID_*)
 KERNEL_IDS = {
     "lpj_resident": 0, "lpj_candidates": 1, "lpj_overflow": 2, "row_lse": 3, "vary_kn": 4,
@@ -44,6 +54,7 @@ SIGNATURES = {
     "evoamd_ctx_destroy": (None, [_vp]),
     "evoamd_synchronize": (_I, [_vp]),
     "evoamd_debug_live_buffers": (_I, [ctypes.POINTER(_I64)]),
+    "evoamd_debug_validity": (_I, [_vp, ctypes.POINTER(_I64)]),
     "evoamd_set_option": (_I, [_vp, ctypes.c_char_p, _I]),
     "evoamd_configure": (_I, [_vp, _I, _I64, _I, _I, _I, _I, _I]),
     "evoamd_upload_data": (_I, [_vp, _c_dp]),

@@ -545,6 +545,191 @@ struct evoamd_ctx {
   i64 t_n[KID_COUNT] = {0};
 };
 
+// ---- validity: begin
+// What is still valid (DESIGN: what a change invalidates).  The flags and generation counters written below are written
+// here and nowhere else: a call site says what happened, the function says what that invalidates.  on_*: an input
+// changed; made_* / drop_*: a product exists / is gone.  Readers read the fields directly.  (rec_in_stats is also armed
+// through the option table, like every option.)
+// what hangs on the last statistics pass: y_hat, the [Es | Ez] rows, the resident reconstruction, Yrec as that pass wrote it
+static void drop_stats_products(evoamd_ctx *c) { c->yhat_valid = c->stats_rows_valid = c->rec_resident = c->yrec_from_pass = false; }
+static void drop_prefetch(evoamd_ctx *c) { c->prefetch_gen = ~0ull; }  // consumed, or no longer what the next pass computes
+static void made_prefetch(evoamd_ctx *c) { c->prefetch_gen = c->gen; }
+static void drop_B(evoamd_ctx *c) { c->B_valid = false; }  // B = Y W: Theta-derived values are being rebuilt
+static void made_B(evoamd_ctx *c) { c->B_valid = true; }
+static int next_theta_stamp(evoamd_ctx *c) { return ++c->theta_gen; }  // one per build of the state-term tables
+
+// Nothing the previous configuration left is valid; every generation counter moves on.
+static void on_configure(evoamd_ctx *c) {
+  c->gen++;
+  c->kn_gen++;
+  c->census_gen = 0;
+  c->pending_skip = c->census_skip = 0;
+  c->have_data = c->have_params = c->have_cand = c->rows_fresh = c->acc_clean = c->clist_clean = false;
+  c->h_theta_fresh = c->theta_bak_valid = c->yrec_valid = c->rec_in_stats = c->keep_x_valid = c->kn_lost = false;
+  c->lists_clean = c->need_known = c->cand_from_device = false;  // fresh (uninitialised) overflow counters
+  // gap: a context that goes from ES3C to EBSC keeps last_estep_fused; if it was set, EBSC never prefetches (only slower)
+  if (c->model == EVOAMD_MODEL_SSSC) c->last_estep_fused = false;
+  drop_stats_products(c);
+  c->pred_N = 0;
+  c->rel_frac = -1.0;
+  c->pays_agreed = -1;
+}
+// an option can change which kernel form evaluates K^n: a prefetched pass is dropped
+static void on_option(evoamd_ctx *c) { c->gen++; }
+static void on_option_changes_derived(evoamd_ctx *c) { c->have_params = false; }  // bsc_direct: G / B are (not) needed, set_params again
+// ---- the data
+static void on_data_uploaded(evoamd_ctx *c) {
+  c->have_data = true;
+  c->gen++;
+  c->B_valid = false;
+  c->rec_resident = false;
+  // gap: stats_rows_valid and yhat_valid stand -- evoamd_reconstruct / evoamd_posterior_codes still serve the old data's rows
+}
+// `present`: masks arrived (Y, yy and hence B changed); else they were removed, which leaves Y as it is
+static void on_masks_changed(evoamd_ctx *c, bool present) {
+  c->yrec_valid = c->rec_resident = c->yrec_from_pass = false;
+  if (present) c->B_valid = false;
+  // gap: gen stands -- a pass prefetched on complete data is still consumed by the next evoamd_lpj_resident
+}
+static void on_yrec_uploaded(evoamd_ctx *c) { c->yrec_valid = true, c->rec_resident = c->yrec_from_pass = false; }
+// ---- Theta
+static void on_theta_installed(evoamd_ctx *c) {  // by the caller (evoamd_set_params_*), derived values rebuilt
+  c->have_params = true;
+  c->gen++;
+  c->h_theta_fresh = false;
+  drop_stats_products(c);
+}
+static void on_theta_update_begun(evoamd_ctx *c) { c->gen++; }
+// Updated on the device.  Unlike an install this keeps y_hat and the resident reconstruction: they were formed under the
+// Theta of the E-step on purpose (evoamd_mstep_device bit 32) and are fetched after the update.
+static void on_theta_updated(evoamd_ctx *c, bool backup_rode_along) {
+  c->B_valid = false;
+  if (backup_rode_along) c->theta_bak_valid = true;
+  c->stats_rows_valid = false;  // the rows belong to the previous Theta now
+}
+// The raw parameters of the last E-step are back (the Theta y_hat was formed under: the statistics products stay).
+static void on_theta_restored(evoamd_ctx *c) {
+  c->gen++;
+  c->h_theta_fresh = false;
+  c->B_valid = false;
+  // gap: G and the state-term tables still belong to the failed update until the next set_params, yet a pass may run
+  c->have_params = true;  // evoamd_get_params_* may read them
+  drop_prefetch(c);
+}
+// status 1 / 2: what was derived and prefetched behind the mailbox ran with the failed update's Theta
+static void on_theta_update_failed(evoamd_ctx *c) { c->prefetch_gen = ~0ull, c->have_params = false; }
+static void made_theta_backup(evoamd_ctx *c) { c->theta_bak_valid = true; }
+static void drop_theta_backup(evoamd_ctx *c) { c->theta_bak_valid = false; }
+static void made_theta_mailbox(evoamd_ctx *c, bool holds_theta) { c->h_theta_fresh = holds_theta; }
+// ---- K^n
+// K^n changed: the prefetched pass, the census and the rows of the last statistics pass describe the old one.  Selection
+// keeps the level hints (the counts of the last statistics pass remain the best estimate); a K^n from the caller drops them.
+enum KnBy { KN_BY_CALLER, KN_BY_SELECTION };
+static void on_kn_changed(evoamd_ctx *c, KnBy by) {
+  c->gen++;
+  c->kn_gen++;
+  if (by == KN_BY_CALLER) c->need_known = false;
+}
+static void on_kn_complete(evoamd_ctx *c) { c->kn_lost = false; }  // a whole K^n arrived: upload, or evoamd_init_states to its end
+// evoamd_init_states begun: K^n counts as lost until the kernel has completed every datapoint (stopped at its round cap:
+// no event, it stays lost)
+static void on_kn_init_begun(evoamd_ctx *c) {
+  c->kn_lost = true, c->kn_refill = 0;
+  on_kn_changed(c, KN_BY_CALLER);
+}
+// rows [n0, n0 + n) replaced: not a whole K^n, but chunks in ascending order rebuild a lost one
+static void on_kn_rows_uploaded(evoamd_ctx *c, i64 n0, i64 n) {
+  on_kn_changed(c, KN_BY_CALLER);
+  if (c->kn_lost && n0 <= c->kn_refill && n0 + n > c->kn_refill) {
+    c->kn_refill = n0 + n;
+    if (c->kn_refill >= c->N) c->kn_lost = false;
+  }
+}
+static void on_estep_route(evoamd_ctx *c, bool fused) { c->last_estep_fused = fused; }  // (a fused E-step evaluates K^n itself: no prefetch)
+// ---- lpj rows, row statistics, counters a kernel clears on its way
+static void on_lpj_overwritten(evoamd_ctx *c) { c->rows_fresh = false; }  // rowmax / rowsum / Fs partials describe other rows
+static void made_row_stats(evoamd_ctx *c) { c->rows_fresh = true; }
+// a chain is about to append to the on-the-fly lists; the caller has checked + cleared them unless they were clean
+static void on_lists_claimed(evoamd_ctx *c) {
+  if (!c->lists_clean) c->pending_skip = 0;
+  c->lists_clean = false;
+}
+// a kernel zeroed the overflow counters and checked the skipped levels of the chain before it (ES3C has such lists)
+static void made_clean_lists(evoamd_ctx *c) {
+  c->lists_clean = c->model == EVOAMD_MODEL_SSSC;
+  if (c->lists_clean) c->pending_skip = 0;
+}
+// the levels a pass did not launch (launch_sssc_lpj has the table): whoever clears the counters next checks them
+static void on_levels_skipped(evoamd_ctx *c, bool census_route, int skipped, int served, bool any) {
+  if (census_route) {
+    c->census_skip |= skipped;
+    if (any && !(served & 2)) c->pending_skip |= 2;
+  } else {
+    c->pending_skip = (c->pending_skip | skipped) & ~served;
+  }
+}
+// the selection kernel: row statistics of the new lpj rows, and on its way the old census checked + cleared, the
+// accumulators of the next statistics pass zeroed, the on-the-fly lists cleared
+static void made_selection(evoamd_ctx *c, bool census_cleared, bool acc_zeroed) {
+  made_row_stats(c);
+  if (census_cleared) {
+    c->clist_clean = true;
+    c->census_skip = 0;
+  }
+  c->acc_clean = acc_zeroed;
+  made_clean_lists(c);
+}
+// ---- census
+// its counters were checked; a kernel is about to append to the lists
+static void on_census_claimed(evoamd_ctx *c) { c->clist_clean = false, c->census_skip = 0; }
+static void made_census(evoamd_ctx *c) { c->census_gen = c->kn_gen; }
+static void on_census_poisoned(evoamd_ctx *c) { c->kn_gen++; }  // test hook: rebuilt before anything else reads it
+// ---- candidates
+// `near_parents`: children of evolve_randflip (k <= k_parent + 1: the overflow levels take a shortcut); a batch from the
+// host or from the general operators may differ from every resident state in many bits
+static void on_cand_installed(evoamd_ctx *c, bool near_parents) { c->cand_from_device = near_parents; }
+static void made_cand_lpj(evoamd_ctx *c) { c->have_cand = true; }
+// fused E-step: K^n advanced, its rows and (small shards) its census came with it, the children never left the kernel
+static void made_fused_estep(evoamd_ctx *c, bool inkernel_census) {
+  on_kn_changed(c, KN_BY_SELECTION);
+  if (inkernel_census) made_census(c);
+  made_row_stats(c);
+  c->have_cand = false, c->cand_from_device = true;
+  on_estep_route(c, true);
+}
+static void made_fused_rows(evoamd_ctx *c, bool reduced) { c->reduce_pending = !reduced; }  // rowF / rowcnt written / summed into the scalar block
+// ---- statistics pass and what is made of it
+static void on_bins_append(evoamd_ctx *c) { c->bins_dirty = true; }  // until the reduce kernel that zeroes the region counters
+static void made_bins_clean(evoamd_ctx *c) { c->bins_dirty = false; }
+static void on_stats_pass_begun(evoamd_ctx *c) {  // accumulators zeroed, region counters clean; the last pass's products go
+  c->bins_dirty = false;
+  c->acc_clean = false;
+  drop_stats_products(c);
+}
+static void made_stats_rows(evoamd_ctx *c) { c->stats_rows_valid = true, c->rows_kn_gen = c->kn_gen; }
+// After the accumulator + scalar block reached the host: remember which overflow levels K^n needs.
+static void made_level_hints(evoamd_ctx *c, const double *dpar_host) {
+  if (c->model != EVOAMD_MODEL_SSSC) return;
+  for (int j = 0; j < 3; j++) {
+    c->res_cnt[j] = dpar_host[DP_NGT2 + j];
+    c->res_need[j] = c->res_cnt[j] > 0.0;
+  }
+  c->need_known = true;
+}
+static void made_wq_copy(evoamd_ctx *c, bool present) { c->wq_copy_valid = present; }  // EBSC: tmpA holds Wq (false: inverted in place)
+static void made_yhat(evoamd_ctx *c) { c->yhat_valid = true; }
+// Yrec selected from the y_hat of this pass; `in_stats`: by the pass itself, which serves the one-shot option
+static void made_yrec_from_pass(evoamd_ctx *c, bool in_stats) {
+  c->yrec_valid = c->yrec_from_pass = true;
+  if (in_stats) c->rec_in_stats = false;
+}
+static void drop_resident_rec(evoamd_ctx *c) { c->rec_resident = false; }
+static void on_keep_mask(evoamd_ctx *c, bool uploaded) { c->keep_x_valid = uploaded; }
+static void made_resident_rec(evoamd_ctx *c, bool uses_keep) { c->rec_uses_keep = uses_keep, c->rec_resident = true; }
+static void made_predictive(evoamd_ctx *c, i64 N) { c->pred_N = N; }  // 0: nothing to download
+static void made_generated(evoamd_ctx *c, int keep) { c->gen_keep = keep; }  // -1: no call has completed
+// ---- validity: end
+
 struct SpanGuard {
   evoamd_ctx *c;
   int kid;
@@ -751,6 +936,28 @@ extern "C" int evoamd_debug_live_buffers(int64_t out[2]) {
   return 0;
 }
 
+extern "C" int evoamd_debug_validity(evoamd_ctx *c, int64_t out[8]) {
+  REQUIRE(c && out, "ctx / out is NULL");
+  const bool bits[32] = {c->have_data,      c->have_params,       c->have_cand,      c->B_valid,
+                         c->rows_fresh,     c->stats_rows_valid,  c->yhat_valid,     c->rec_resident,
+                         c->yrec_valid,     c->yrec_from_pass,    c->rec_in_stats,   c->keep_x_valid,
+                         c->rec_uses_keep,  c->need_known,        c->res_need[0],    c->res_need[1],
+                         c->res_need[2],    c->cand_from_device,  c->lists_clean,    c->clist_clean,
+                         c->acc_clean,      c->wq_copy_valid,     c->h_theta_fresh,  c->theta_bak_valid,
+                         c->kn_lost,        c->last_estep_fused,  c->reduce_pending, c->bins_dirty,
+                         c->gen_keep >= 0,  c->prefetch_gen == c->gen, c->census_gen == c->kn_gen, c->rows_kn_gen == c->kn_gen};
+  out[0] = 0;
+  for (int i = 0; i < 32; i++) out[0] |= (int64_t)bits[i] << i;
+  out[1] = (int64_t)c->gen;
+  out[2] = (int64_t)c->kn_gen;
+  out[3] = c->theta_gen;
+  out[4] = c->pending_skip;
+  out[5] = c->census_skip;
+  out[6] = c->kn_refill;
+  out[7] = c->pred_N;
+  return 0;
+}
+
 // One row per option of evoamd_set_option (what each one means: the comments at the fields of evoamd_ctx).
 struct OptionRow {
   const char *name;
@@ -769,7 +976,7 @@ static const OptionRow OPTIONS[] = {
     {"sssc_k8", OPT_INT(k8_mode), [](int v) { return v < 0 ? -1 : (int)(v != 0); }},
     {"ebsc_f32", OPT_BOOL(f32_opt), opt_flag},  // takes effect at the next evoamd_configure
     {"bsc_direct", OPT_BOOL(bsc_direct), opt_flag, 0, 0, nullptr, nullptr,
-     [](evoamd_ctx *c) { c->have_params = false; }},  // G / B are (not) needed: set_params again
+     on_option_changes_derived},
     {"reconstruct_in_stats", OPT_BOOL(rec_in_stats), opt_flag},  // one-shot: the next statistics pass forms y_reconstructed first
     {"codes_path", OPT_INT(codes_path), nullptr, -1, CODES_GMEM, nullptr, "codes_path: -1 (auto), 0 registers, 1 LDS, 2 global memory"},
     {"merge_select_fused", OPT_INT(merge_select_fused), opt_flag},
@@ -817,7 +1024,7 @@ static const OptionRow OPTIONS[] = {
 
 extern "C" int evoamd_set_option(evoamd_ctx *c, const char *name, int value) {
   REQUIRE(c && name, "bad arguments");
-  c->gen++;  // an option can change which kernel form evaluates K^n: drop a prefetched pass
+  on_option(c);
   for (const OptionRow &o : OPTIONS) {
     if (strcmp(name, o.name) != 0) continue;
     if (o.err && !(o.accepts ? o.accepts(value) : (value >= o.lo && value <= o.hi))) return fail(EVOAMD_E_INVALID, "%s", o.err);
@@ -834,8 +1041,7 @@ static int join_fork(evoamd_ctx *c);
 
 extern "C" int evoamd_synchronize(evoamd_ctx *c) {
   REQUIRE(c, "ctx is NULL");
-  int rj = join_fork(c);
-  if (rj) return rj;
+  TRY(join_fork(c));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -908,7 +1114,7 @@ static int alloc_pair_bins(evoamd_ctx *c, int scale) {
       HIP_TRY(hipMemsetAsync(pb.gcnt, 0, c->pb_gcnt.size() * sizeof(int), c->stream));
       c->pbins = pb;
       c->bins_scale_cur = scale;
-      c->bins_dirty = false;
+      made_bins_clean(c);
     } else {
       c->pb_ent.reset();
       c->pb_part.reset();
@@ -934,11 +1140,9 @@ static int ensure_bins_capacity(evoamd_ctx *c) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (c->stream2) HIP_TRY(hipStreamSynchronize(c->stream2));
   const int before = c->bins_scale_cur;
-  int r = alloc_pair_bins(c, want);
-  if (r) return r;
+  TRY(alloc_pair_bins(c, want));
   if (!c->pbins.ent) {  // does not fit: back to what there was (or the atomics if even that is gone now)
-    r = alloc_pair_bins(c, before);
-    if (r) return r;
+    TRY(alloc_pair_bins(c, before));
     c->bins_auto = 0;
   }
   return 0;
@@ -1146,28 +1350,6 @@ static int configure_clear(evoamd_ctx *c) {
   return 0;
 }
 
-// Nothing the previous configuration left is valid; every generation counter moves on.
-static void configure_reset_flags(evoamd_ctx *c) {
-  c->acc_clean = c->clist_clean = false;
-  if (c->model == EVOAMD_MODEL_SSSC) c->last_estep_fused = false;
-  c->h_theta_fresh = false;
-  c->yrec_valid = c->rec_in_stats = false;
-  c->keep_x_valid = false;
-  c->rel_frac = -1.0;
-  c->pays_agreed = -1;
-  c->pending_skip = 0;
-  c->gen++;
-  c->kn_gen++;
-  c->census_gen = 0;
-  c->census_skip = 0;
-  c->have_data = c->have_params = c->have_cand = c->rows_fresh = false;
-  c->yhat_valid = c->stats_rows_valid = c->rec_resident = c->yrec_from_pass = false;
-  c->theta_bak_valid = false;
-  c->lists_clean = c->need_known = c->cand_from_device = false;  // fresh (uninitialised) overflow counters
-  c->kn_lost = false;
-  c->pred_N = 0;
-}
-
 extern "C" int evoamd_configure(evoamd_ctx *c, int model, int64_t N, int D, int H, int S, int S_perm,
                                 int Cmax) {
   REQUIRE(c, "ctx is NULL");
@@ -1186,7 +1368,7 @@ extern "C" int evoamd_configure(evoamd_ctx *c, int model, int64_t N, int D, int 
   TRY(alloc_pair_bins(c, c->bins_scale));
   TRY(configure_alloc_host(c));
   TRY(configure_clear(c));
-  configure_reset_flags(c);
+  on_configure(c);
   c->configured = true;
   return 0;
 }
@@ -1211,10 +1393,7 @@ extern "C" int evoamd_upload_data(evoamd_ctx *c, const double *Y) {
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->have_data = true;
-  c->gen++;
-  c->B_valid = false;
-  c->rec_resident = false;
+  on_data_uploaded(c);
   return 0;
 }
 
@@ -1225,7 +1404,7 @@ extern "C" int evoamd_upload_masks(evoamd_ctx *c, const uint8_t *x_infr, const u
   if (!x_infr) {  // back to complete data (upload_data again restores entries that were zeroed)
     c->mask_infr.reset();
     c->mask_x.reset();
-    c->yrec_valid = c->rec_resident = c->yrec_from_pass = false;
+    on_masks_changed(c, /*present=*/false);
     return 0;
   }
   const size_t nd = (size_t)c->N * c->D;
@@ -1248,8 +1427,7 @@ extern "C" int evoamd_upload_masks(evoamd_ctx *c, const uint8_t *x_infr, const u
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->yrec_valid = c->rec_resident = c->yrec_from_pass = false;
-  c->B_valid = false;
+  on_masks_changed(c, /*present=*/true);
   return 0;
 }
 
@@ -1264,23 +1442,16 @@ extern "C" int evoamd_upload_yrec(evoamd_ctx *c, const double *y_rec) {
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipMemcpyAsync(c->Yrec, y_rec, (size_t)c->N * c->D * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->yrec_valid = true;
-  c->rec_resident = c->yrec_from_pass = false;
+  on_yrec_uploaded(c);
   return 0;
 }
 
 static int pack_to_device(evoamd_ctx *c, const uint8_t *host_bool, i64 nstates, u64 *dst) {
   const size_t bytes = (size_t)nstates * c->H;
-  {
-    int rs = c->stage.ensure(c, bytes);
-    if (rs) return rs;
-  }
+  TRY(c->stage.ensure(c, bytes));
   HIP_TRY(hipMemcpyAsync(c->stage, host_bool, bytes, hipMemcpyHostToDevice, c->stream));
   pack_states_kernel<<<cdiv(nstates * c->HW, 256), 256, 0, c->stream>>>(c->stage, dst, nstates, c->H, c->HW);
-  if (dst == c->states) {
-    c->gen++;
-    c->kn_gen++;
-  }
+  if (dst == c->states) on_kn_changed(c, KN_BY_CALLER);
   u64 *dg = dst == c->states ? c->dig : dst == c->cand ? c->cand_dig : nullptr;
   if (dg) digest_kernel<<<cdiv(nstates, 256), 256, 0, c->stream>>>(dst, dg, nstates, c->HW);
   HIP_TRY(hipGetLastError());
@@ -1291,11 +1462,9 @@ extern "C" int evoamd_upload_states(evoamd_ctx *c, const uint8_t *ss_bool) {
   REQUIRE(c && c->configured, "configure first");
   REQUIRE(ss_bool, "ss is NULL");
   HIP_TRY(hipSetDevice(c->device));
-  int r = pack_to_device(c, ss_bool, c->N * (i64)c->S, c->states);
-  if (r) return r;
+  TRY(pack_to_device(c, ss_bool, c->N * (i64)c->S, c->states));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->need_known = false;
-  c->kn_lost = false;
+  on_kn_complete(c);
   return 0;
 }
 
@@ -1305,10 +1474,7 @@ extern "C" int evoamd_download_states(evoamd_ctx *c, uint8_t *ss_bool) {
   REQUIRE_KN(c);
   HIP_TRY(hipSetDevice(c->device));
   const i64 ns = c->N * (i64)c->S;
-  {
-    int rs = c->stage.ensure(c, (size_t)ns * c->H);
-    if (rs) return rs;
-  }
+  TRY(c->stage.ensure(c, (size_t)ns * c->H));
   unpack_states_kernel<<<cdiv(ns * c->H, 256), 256, 0, c->stream>>>(c->states, c->stage, ns, c->H, c->HW);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(ss_bool, c->stage, (size_t)ns * c->H, hipMemcpyDeviceToHost, c->stream));
@@ -1324,23 +1490,14 @@ extern "C" int evoamd_upload_states_packed(evoamd_ctx *c, const uint8_t *packed,
   const int PB = (c->H + 7) / 8;
   const i64 ns = n * (i64)c->S;
   const size_t bytes = (size_t)ns * PB;
-  {
-    int rs = c->stage.ensure(c, bytes);
-    if (rs) return rs;
-  }
+  TRY(c->stage.ensure(c, bytes));
   HIP_TRY(hipMemcpyAsync(c->stage, packed, bytes, hipMemcpyHostToDevice, c->stream));
   u64 *dst = c->states + (size_t)n0 * c->S * c->HW;
   words_from_packbits_kernel<<<cdiv(ns * c->HW, 256), 256, 0, c->stream>>>(c->stage, dst, ns, PB, c->HW, c->H);
   if (c->dig) digest_kernel<<<cdiv(ns, 256), 256, 0, c->stream>>>(dst, c->dig + (size_t)n0 * c->S, ns, c->HW);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->gen++;
-  c->kn_gen++;
-  c->need_known = false;
-  if (c->kn_lost && n0 <= c->kn_refill && n0 + n > c->kn_refill) {  // chunks in ascending order rebuild a lost K^n
-    c->kn_refill = n0 + n;
-    if (c->kn_refill >= c->N) c->kn_lost = false;
-  }
+  on_kn_rows_uploaded(c, n0, n);
   return 0;
 }
 
@@ -1361,10 +1518,7 @@ extern "C" int evoamd_init_states(evoamd_ctx *c, double p_init, uint64_t seed, i
   if (table_packed) {  // exact mode: (S, ceil(H/8)) packbits rows -> words behind them in the staging area -> every datapoint
     const int PB = (c->H + 7) / 8;
     const size_t off = (((size_t)S * PB + 7) / 8) * 8;
-    {
-      int rs = c->stage.ensure(c, off + (size_t)S * HW * sizeof(u64));
-      if (rs) return rs;
-    }
+    TRY(c->stage.ensure(c, off + (size_t)S * HW * sizeof(u64)));
     u64 *table = (u64 *)(c->stage + off);
     HIP_TRY(hipMemcpyAsync(c->stage, table_packed, (size_t)S * PB, hipMemcpyHostToDevice, c->stream));
     SpanGuard g(c, KID_INIT_STATES);
@@ -1391,11 +1545,7 @@ extern "C" int evoamd_init_states(evoamd_ctx *c, double p_init, uint64_t seed, i
     const bool lds_fits = W * wave_words * sizeof(u64) <= 150 * 1024;
     REQUIRE(c->init_home != 0 || lds_fits, "init_states_home 0 (LDS): the round state of one wavefront does not fit");
     const bool lds_home = c->init_home < 0 ? lds_fits : c->init_home == 0;
-    c->kn_lost = true;  // until the kernel has completed every datapoint
-    c->kn_refill = 0;
-    c->gen++;
-    c->kn_gen++;
-    c->need_known = false;
+    on_kn_init_begun(c);
     HIP_TRY(hipMemsetAsync(a.err, 0, sizeof(int), c->stream));
     if (lds_home) {
       const unsigned grid = (unsigned)std::min<i64>(cdiv(c->N, W), (i64)c->n_cu * 64);
@@ -1422,15 +1572,13 @@ extern "C" int evoamd_init_states(evoamd_ctx *c, double p_init, uint64_t seed, i
                   "round cap); K^n is not initialised -- shapes with S close to 2^H belong to the host function",
                   S, max_rounds);
     }
-    c->kn_lost = false;
+    on_kn_complete(c);
     return 0;
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->gen++;
-  c->kn_gen++;
-  c->need_known = false;
-  c->kn_lost = false;
+  on_kn_changed(c, KN_BY_CALLER);
+  on_kn_complete(c);
   return 0;
 }
 
@@ -1442,10 +1590,7 @@ extern "C" int evoamd_download_states_packed(evoamd_ctx *c, uint8_t *packed, int
   const int PB = (c->H + 7) / 8;
   const i64 ns = n * (i64)c->S;
   const size_t bytes = (size_t)ns * PB;
-  {
-    int rs = c->stage.ensure(c, bytes);
-    if (rs) return rs;
-  }
+  TRY(c->stage.ensure(c, bytes));
   packbits_from_words_kernel<<<cdiv(ns * PB, 256), 256, 0, c->stream>>>(c->states + (size_t)n0 * c->S * c->HW, c->stage, ns,
                                                                          PB, c->HW);
   HIP_TRY(hipGetLastError());
@@ -1459,7 +1604,7 @@ extern "C" int evoamd_upload_lpj(evoamd_ctx *c, const double *lpj) {
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipMemcpyAsync(c->lpj, lpj, (size_t)c->N * c->L * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->rows_fresh = false;
+  on_lpj_overwritten(c);
   return 0;
 }
 
@@ -1666,15 +1811,13 @@ static int launch_B(evoamd_ctx *c) {
 // where the parameter-sized kernel runs (an upload always launches extract_diag_kernel).
 static int derive_from_theta(evoamd_ctx *c, bool updated) {
   const int H = c->H, D = c->D;
-  int r = 0;
-  c->B_valid = false;
+  drop_B(c);
   if (c->model == EVOAMD_MODEL_BSC && c->bsc_direct) return 0;  // the direct residual kernel reads W only
   GemmTnOpts gram;
   gram.deterministic = true;  // the same Theta gives the same G, tables and lpj bits every time
   if (c->model == EVOAMD_MODEL_SSSC) {
     if (!updated) {
-      r = launch_gemm_tn(c, c->W, H, c->W, H, c->G, H, H, H, D, gram);
-      if (r) return r;
+      TRY(launch_gemm_tn(c, c->W, H, c->W, H, c->G, H, H, H, D, gram));
       DBG_SYNC(c, "derive_from_theta: G = W^T W");
     }
     if (c->mask_infr) {  // incomplete data: the wavefront kernel forms W_obs^T W_obs from W^T (sssc.py:276)
@@ -1682,20 +1825,18 @@ static int derive_from_theta(evoamd_ctx *c, bool updated) {
       transpose_kernel<<<cdiv((i64)H * D, 256), 256, 0, c->stream>>>(c->W, D, H, c->Wt);
     }
     sssc_tables_kernel<<<cdiv((i64)H * H, 256), 256, 0, c->stream>>>(c->G, c->Psi, c->mus, c->pilbar_v, c->dpar, H, c->D1,
-                                                                     c->PT, c->GP, c->DG, c->sing_gen, ++c->theta_gen);
+                                                                     c->PT, c->GP, c->DG, c->sing_gen, next_theta_stamp(c));
     DBG_SYNC(c, "derive_from_theta: tables");
   } else {
     const bool diag_rides = updated && gram_is_small(H, D);
     if (diag_rides) gram.diag = c->diag;
-    r = launch_gemm_tn(c, c->W, H, c->W, H, c->G, H, H, H, D, gram);
-    if (r) return r;
+    TRY(launch_gemm_tn(c, c->W, H, c->W, H, c->G, H, H, H, D, gram));
     if (!diag_rides) extract_diag_kernel<<<cdiv(H, 256), 256, 0, c->stream>>>(c->G, H, c->diag);
   }
   HIP_TRY(hipGetLastError());
   if (c->have_data) {
-    r = launch_B(c);  // B = Y W
-    if (r) return r;
-    c->B_valid = true;
+    TRY(launch_B(c));  // B = Y W
+    made_B(c);
   }
   return 0;
 }
@@ -1725,12 +1866,8 @@ extern "C" int evoamd_set_params_bsc(evoamd_ctx *c, const double *W, double pi, 
   HIP_TRY(hipStreamSynchronize(c->stream));
   memcpy(wt, W, (size_t)c->D * c->H * sizeof(double));
   HIP_TRY(hipMemcpyAsync(c->W, wt, (size_t)c->D * c->H * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  int r = derive_from_theta(c, /*updated=*/false);
-  if (r) return r;
-  c->have_params = true;
-  c->gen++;
-  c->h_theta_fresh = false;
-  c->yhat_valid = c->stats_rows_valid = c->rec_resident = c->yrec_from_pass = false;
+  TRY(derive_from_theta(c, /*updated=*/false));
+  on_theta_installed(c);
   return 0;
 }
 
@@ -1789,12 +1926,8 @@ extern "C" int evoamd_set_params_sssc(evoamd_ctx *c, const double *W, const doub
     HIP_TRY(hipMemcpyAsync(c->mus, hmu, (size_t)H * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->pilbar_v, hpb, (size_t)H * sizeof(double), hipMemcpyHostToDevice, c->stream));
   }
-  int r = derive_from_theta(c, /*updated=*/false);
-  if (r) return r;
-  c->have_params = true;
-  c->gen++;
-  c->h_theta_fresh = false;
-  c->yhat_valid = c->stats_rows_valid = c->rec_resident = c->yrec_from_pass = false;
+  TRY(derive_from_theta(c, /*updated=*/false));
+  on_theta_installed(c);
   return 0;
 }
 
@@ -1850,10 +1983,9 @@ static int launch_B_f32(evoamd_ctx *c) {
 // B = Y W depends on both the data and Theta; recompute it if either arrived later.
 static int ensure_B(evoamd_ctx *c) {
   if (c->B_valid || (c->model == EVOAMD_MODEL_BSC && c->bsc_direct)) return 0;
-  int r = launch_B(c);
-  if (r) return r;
+  TRY(launch_B(c));
   DBG_SYNC(c, "B = Y W");
-  c->B_valid = true;
+  made_B(c);
   return 0;
 }
 
@@ -2086,9 +2218,8 @@ static int zero_lists(evoamd_ctx *c) {
       check_lists_kernel<<<1, 256, 0, c->stream>>>(c->list_n, 4 * LIST_SHARDS, c->pending_skip, c->err);
     else
       HIP_TRY(hipMemsetAsync(c->list_n, 0, 4 * LIST_SHARDS * sizeof(int), c->stream));
-    c->pending_skip = 0;
   }
-  c->lists_clean = false;  // the chain about to be launched appends to them
+  on_lists_claimed(c);  // the chain about to be launched appends to them
   return 0;
 }
 
@@ -2106,8 +2237,7 @@ static int ensure_census(evoamd_ctx *c) {
   // a level that no pass over the OLD census launched must have had an empty list; then fresh counters
   // (evoamd_vary_kn's kernel has done both on its way when it is what changed K^n)
   if (!c->clist_clean) check_lists_kernel<<<1, 256, 0, c->stream>>>(c->clist_n, 4 * LIST_SHARDS, c->census_skip, c->err);
-  c->clist_clean = false;
-  c->census_skip = 0;
+  on_census_claimed(c);
   unsigned grid = cdiv(total, CENSUS_T * CENSUS_PPT);
   if (grid > (unsigned)(8 * c->n_cu)) grid = (unsigned)(8 * c->n_cu);
   SpanGuard g(c, KID_MISC);
@@ -2120,10 +2250,10 @@ static int ensure_census(evoamd_ctx *c) {
     HIP_TRY(hipMemcpyAsync(c->clist, bad, sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->clist_n, one, sizeof(int), hipMemcpyHostToDevice, c->stream));  // (at least that one entry)
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->kn_gen++;  // the poisoned census is rebuilt before anything else reads it
+    on_census_poisoned(c);
     return 0;
   }
-  c->census_gen = c->kn_gen;
+  made_census(c);
   return 0;
 }
 
@@ -2152,6 +2282,22 @@ static void with_hw(int hw, F &&f) {
     case 16: f(std::integral_constant<int, 16>{}); break;
     default: f(std::integral_constant<int, 0>{}); break;
   }
+}
+
+// The one S -> states-per-lane map (S <= 64 x VK_MAX_S_PER_LANE) of the selection, randflip and fused kernels, and the
+// Cmax -> candidates-per-lane map of the selection kernel: f gets the value as a compile-time constant.
+template <typename F>
+static void with_spl(int S, F &&f) {
+  if (S <= 64) f(std::integral_constant<int, 1>{});
+  else if (S <= 128) f(std::integral_constant<int, 2>{});
+  else if (S <= 256) f(std::integral_constant<int, 4>{});
+  else if (S <= 512) f(std::integral_constant<int, 8>{});
+  else f(std::integral_constant<int, 16>{});
+}
+template <typename F>
+static void with_cpl(int Cmax, F &&f) {
+  if (Cmax <= 64) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 4>{});
 }
 
 // The on-the-fly lists 1..3 of a pass as the kernels append to them (o) and read them (i), the census lists of the resident
@@ -2436,30 +2582,18 @@ static int lpj_sssc_round2_levels(evoamd_ctx *c, const SsscArgs &a, const LpjPla
 // (zero_lists has checked and cleared what the chain before left, so pending_skip is 0 when the table is applied.)
 template <int TAG>
 static int launch_sssc_lpj(evoamd_ctx *c, const SsscArgs &a, int kid_main, const LevelHints &lv) {
-  int r = zero_lists(c);
-  if (r) return r;
+  TRY(zero_lists(c));
   LpjPlan p;
   lpj_plan(c, a, TAG, lv, kid_main, p);
   if (p.route == LPJ_MASKED) return lpj_sssc_masked(c, a, p);
-  if (p.route == LPJ_CENSUS) {
-    r = ensure_census(c);
-    if (r) return r;
-  }
-  r = lpj_sssc_main<TAG>(c, a, p);
-  if (r) return r;
+  if (p.route == LPJ_CENSUS) TRY(ensure_census(c));
+  TRY(lpj_sssc_main<TAG>(c, a, p));
   int served = 0;  // on-the-fly lists the levels read to the end (bit k - 1 = list k)
-  if (p.any) {
-    r = p.route == LPJ_CENSUS   ? lpj_sssc_census_levels<TAG>(c, a, p, served)
+  if (p.any)
+    TRY(p.route == LPJ_CENSUS   ? lpj_sssc_census_levels<TAG>(c, a, p, served)
         : p.route == LPJ_CHAINS ? lpj_sssc_chain_levels<TAG>(c, a, p, served)
-                                : lpj_sssc_round2_levels<TAG>(c, a, p, served);
-    if (r) return r;
-  }
-  if (p.route == LPJ_CENSUS) {
-    c->census_skip |= skip_mask(p.need);
-    if (p.any && !(served & 2)) c->pending_skip |= 2;
-  } else {
-    c->pending_skip = (c->pending_skip | skip_mask(p.need)) & ~served;
-  }
+                                : lpj_sssc_round2_levels<TAG>(c, a, p, served));
+  on_levels_skipped(c, p.route == LPJ_CENSUS, skip_mask(p.need), served, p.any);
   return 0;
 }
 
@@ -2486,26 +2620,9 @@ static int check_err(evoamd_ctx *c) {
   return 0;
 }
 
-static int lpj_resident_launch(evoamd_ctx *c, double *out, const LevelHints &lv);
-
-extern "C" int evoamd_lpj_resident(evoamd_ctx *c) {
-  REQUIRE(c && c->configured && c->have_data && c->have_params, "configure, upload_data and set_params first");
-  REQUIRE_KN(c);
-  HIP_TRY(hipSetDevice(c->device));
-  if (c->prefetch_gen == c->gen) {  // evoamd_mstep_device already enqueued exactly this pass
-    c->prefetch_gen = ~0ull;
-    std::swap(c->lpj, c->lpj_alt);
-    return 0;
-  }
-  return lpj_resident_launch(c, c->lpj, batch_hints(c, 0));
-}
-
 static int lpj_resident_launch(evoamd_ctx *c, double *out, const LevelHints &lv) {
-  {
-    int rb = ensure_B(c);
-    if (rb) return rb;
-  }
-  c->rows_fresh = false;
+  TRY(ensure_B(c));
+  on_lpj_overwritten(c);
   if (c->S_perm) {
     allzero_lpj_kernel<<<cdiv(c->N, 256), 256, 0, c->stream>>>(c->yy, c->N, c->dpar, c->model == EVOAMD_MODEL_SSSC,
                                                                out, c->L, c->flags + 2 * c->N, c->err);
@@ -2517,11 +2634,46 @@ static int lpj_resident_launch(evoamd_ctx *c, double *out, const LevelHints &lv)
   return launch_lpj(c, b, lv);  // stream-ordered; device-side errors surface at the next host-returning call
 }
 
-static int eval_candidates(evoamd_ctx *c) {
-  {
-    int rb = ensure_B(c);
-    if (rb) return rb;
+// ---- E-step stage: lpj of the resident K^n
+static int estep_resident_pass(evoamd_ctx *c) {
+  if (c->prefetch_gen == c->gen) {  // evoamd_mstep_device already enqueued exactly this pass
+    drop_prefetch(c);
+    std::swap(c->lpj, c->lpj_alt);
+    return 0;
   }
+  return lpj_resident_launch(c, c->lpj, batch_hints(c, 0));
+}
+
+// the argument checks the E-step entry points share (evoamd_evolve_states has wider rules of its own for the rest)
+static int estep_check_ready(const evoamd_ctx *c) {
+  REQUIRE(c && c->configured && c->have_data && c->have_params, "configure, upload_data and set_params first");
+  return 0;
+}
+static int estep_check_parents(const evoamd_ctx *c, int n_parents) {
+  REQUIRE(n_parents >= 1 && n_parents <= c->S && n_parents <= 64, "n_parents must be in [1, min(S, 64)]");
+  return 0;
+}
+static int estep_check_randflip(const evoamd_ctx *c, int n_parents, int n_children) {
+  TRY(estep_check_ready(c));
+  TRY(estep_check_parents(c, n_parents));
+  REQUIRE(n_children >= 1 && n_children <= EV_MAX_CHILDREN && n_children <= c->H, "n_children must be in [1, min(8, H)]");
+  REQUIRE(n_parents * n_children <= c->Cmax, "n_parents * n_children exceeds the configured Cmax");
+  return 0;
+}
+static int estep_check_mprime(const evoamd_ctx *c, int Mprime) {
+  REQUIRE(Mprime >= 1 && Mprime <= c->S, "Mprime must be in [1, S]");
+  return 0;
+}
+
+extern "C" int evoamd_lpj_resident(evoamd_ctx *c) {
+  TRY(estep_check_ready(c));
+  REQUIRE_KN(c);
+  HIP_TRY(hipSetDevice(c->device));
+  return estep_resident_pass(c);
+}
+
+static int eval_candidates(evoamd_ctx *c) {
+  TRY(ensure_B(c));
   Batch b = {c->cand, c->cand_counts, c->Y, c->Bm, c->yy, c->N, c->Cmax, 0, c->cand_lpj, c->Cmax, 0,
              c->flags + c->N, KID_LPJ_CAND, 1};
   b.mask = c->mask_infr;
@@ -2534,16 +2686,14 @@ extern "C" int evoamd_lpj_candidates(evoamd_ctx *c, const uint8_t *cand_bool, co
   REQUIRE(cand_bool && counts, "NULL candidate batch");
   REQUIRE(Cmax == c->Cmax, "Cmax differs from the configured value");
   HIP_TRY(hipSetDevice(c->device));
-  int r = pack_to_device(c, cand_bool, c->N * (i64)Cmax, c->cand);
-  if (r) return r;
+  TRY(pack_to_device(c, cand_bool, c->N * (i64)Cmax, c->cand));
   HIP_TRY(hipMemcpyAsync(c->cand_counts, counts, (size_t)c->N * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  c->cand_from_device = false;
-  r = eval_candidates(c);
-  if (r) return r;
+  on_cand_installed(c, /*near_parents=*/false);
+  TRY(eval_candidates(c));
   if (lpj_out)
     HIP_TRY(hipMemcpyAsync(lpj_out, c->cand_lpj, (size_t)c->N * Cmax * sizeof(double), hipMemcpyDeviceToHost,
                            c->stream));
-  c->have_cand = true;
+  made_cand_lpj(c);
   if (c->model == EVOAMD_MODEL_SSSC) return check_err(c);
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
@@ -2555,13 +2705,12 @@ extern "C" int evoamd_set_candidates(evoamd_ctx *c, const uint8_t *cand_bool, co
   REQUIRE(cand_bool && counts && lpj, "NULL argument");
   REQUIRE(Cmax == c->Cmax, "Cmax differs from the configured value");
   HIP_TRY(hipSetDevice(c->device));
-  int r = pack_to_device(c, cand_bool, c->N * (i64)Cmax, c->cand);
-  if (r) return r;
+  TRY(pack_to_device(c, cand_bool, c->N * (i64)Cmax, c->cand));
   HIP_TRY(hipMemcpyAsync(c->cand_counts, counts, (size_t)c->N * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->cand_lpj, lpj, (size_t)c->N * Cmax * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->cand_from_device = false;
-  c->have_cand = true;
+  on_cand_installed(c, /*near_parents=*/false);
+  made_cand_lpj(c);
   return 0;
 }
 
@@ -2571,22 +2720,17 @@ extern "C" int evoamd_lpj_shared(evoamd_ctx *c, const uint8_t *states_bool, int 
   REQUIRE((i64)c->N * C < 2147483647LL, "N * C must fit in int32");
   HIP_TRY(hipSetDevice(c->device));
   TRY(c->tmp_states.ensure(c, (size_t)C * c->HW));
-  int r = c->tmp_lpj.ensure(c, (size_t)c->N * C);
-  if (r) return r;
-  r = ensure_B(c);
-  if (r) return r;
+  TRY(c->tmp_lpj.ensure(c, (size_t)c->N * C));
+  TRY(ensure_B(c));
   // stage through a private buffer (C*H may exceed the configured staging area)
   DevBuf<uint8_t> st;
   TRY(st.alloc((size_t)C * c->H));
   HIP_TRY(hipMemcpyAsync(st, states_bool, (size_t)C * c->H, hipMemcpyHostToDevice, c->stream));
   pack_states_kernel<<<cdiv((i64)C * c->HW, 256), 256, 0, c->stream>>>(st, c->tmp_states, C, c->H, c->HW);
-  if (c->model == EVOAMD_MODEL_SSSC) {
-    r = ensure_lists(c, (i64)c->N * C);
-    if (r) return r;
-  }
+  if (c->model == EVOAMD_MODEL_SSSC) TRY(ensure_lists(c, (i64)c->N * C));
   Batch b = {c->tmp_states, nullptr, c->Y, c->Bm, c->yy, c->N, C, 1, c->tmp_lpj, C, 0, c->flags + c->N, KID_MISC, 2};
   b.mask = c->mask_infr;
-  r = launch_lpj(c, b, batch_hints(c, b.tag));
+  int r = launch_lpj(c, b, batch_hints(c, b.tag));
   if (!r) {
     hipError_t e = hipMemcpyAsync(lpj_out, c->tmp_lpj, (size_t)c->N * C * sizeof(double), hipMemcpyDeviceToHost,
                                   c->stream);
@@ -2604,22 +2748,16 @@ static int lpj_single_impl(evoamd_ctx *c, const double *y, const uint8_t *x_infr
   REQUIRE(y && states_bool && lpj_out && C > 0, "bad arguments");
   HIP_TRY(hipSetDevice(c->device));
   TRY(c->tmp_states.ensure(c, (size_t)C * c->HW));
-  int r = c->tmp_lpj.ensure(c, (size_t)C + 2);
-  if (r) return r;
+  TRY(c->tmp_lpj.ensure(c, (size_t)C + 2));
   TRY(c->tmp_y.ensure(c, (size_t)c->D + c->H + 2));
-  r = c->stage.ensure(c, (size_t)C * c->H);
-  if (r) return r;
-  if (c->model == EVOAMD_MODEL_SSSC) {
-    r = ensure_lists(c, C);
-    if (r) return r;
-  }
+  TRY(c->stage.ensure(c, (size_t)C * c->H));
+  if (c->model == EVOAMD_MODEL_SSSC) TRY(ensure_lists(c, C));
   double *dy = c->tmp_y, *db = c->tmp_y + c->D, *dyy = c->tmp_y + c->D + c->H;
   unsigned *dfl = (unsigned *)(c->tmp_lpj + C);
   HIP_TRY(hipMemcpyAsync(dy, y, (size_t)c->D * sizeof(double), hipMemcpyHostToDevice, c->stream));
   uint8_t *dmask = nullptr;
   if (x_infr) {  // one row of x_infr behind the packed states' staging area
-    r = c->stage.ensure(c, (size_t)C * c->H + c->D);
-    if (r) return r;
+    TRY(c->stage.ensure(c, (size_t)C * c->H + c->D));
     dmask = c->stage + (size_t)C * c->H;
     HIP_TRY(hipMemcpyAsync(dmask, x_infr, (size_t)c->D, hipMemcpyHostToDevice, c->stream));
     mask_apply_kernel<<<cdiv(c->D, 256), 256, 0, c->stream>>>(dy, c->D, dmask, 1, c->D);
@@ -2628,14 +2766,10 @@ static int lpj_single_impl(evoamd_ctx *c, const double *y, const uint8_t *x_infr
   HIP_TRY(hipMemsetAsync(dfl, 0, sizeof(unsigned), c->stream));
   pack_states_kernel<<<cdiv((i64)C * c->HW, 256), 256, 0, c->stream>>>(c->stage, c->tmp_states, C, c->H, c->HW);
   row_sqnorm_kernel<<<1, 256, 0, c->stream>>>(dy, c->D, 1, c->D, dyy);
-  if (c->model == EVOAMD_MODEL_SSSC) {
-    r = launch_gemm_nn(c, dy, c->D, c->W, c->H, db, c->H, 1, c->H, c->D);
-    if (r) return r;
-  }
+  if (c->model == EVOAMD_MODEL_SSSC) TRY(launch_gemm_nn(c, dy, c->D, c->W, c->H, db, c->H, 1, c->H, c->D));
   Batch b = {c->tmp_states, nullptr, dy, db, dyy, 1, C, 1, c->tmp_lpj, C, 0, dfl, KID_MISC, 2};
   b.mask = dmask;
-  r = launch_lpj(c, b, batch_hints(c, b.tag));
-  if (r) return r;
+  TRY(launch_lpj(c, b, batch_hints(c, b.tag)));
   unsigned fl = 0;
   HIP_TRY(hipMemcpyAsync(lpj_out, c->tmp_lpj, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(&fl, dfl, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
@@ -2663,50 +2797,40 @@ extern "C" int evoamd_lpj_single_masked(evoamd_ctx *c, const double *y, const ui
 // ---------------------------------------------------------------------------------------
 // selection
 // ---------------------------------------------------------------------------------------
-extern "C" int evoamd_vary_kn(evoamd_ctx *c, int Mprime, double *sums_out) {
-  REQUIRE(c && c->configured && c->have_cand, "no resident candidate batch (call lpj_candidates / evolve first)");
-  REQUIRE(Mprime >= 1 && Mprime <= c->S, "Mprime must be in [1, S]");
-  REQUIRE_KN(c);
-  HIP_TRY(hipSetDevice(c->device));
-  c->gen++;
-  c->kn_gen++;
+// ---- E-step stage: selection (vary_Kn) over the resident candidate batch
+static int estep_select(evoamd_ctx *c, int Mprime, double *sums_out) {
+  on_kn_changed(c, KN_BY_SELECTION);
   {
     SpanGuard g(c, KID_VARY_KN);
-#define VK_LAUNCH(SPL, CPL)                                                                                   \
-  vary_kn_kernel<SPL, CPL><<<cdiv(c->N, 4), 256, 0, c->stream>>>(c->states, c->lpj, c->cand, c->cand_lpj,        \
-                                                                 c->cand_counts, c->N, c->S, c->S_perm, c->HW,   \
-                                                                 c->Cmax, Mprime, c->rowmax,                      \
-                                                                 c->rowsum, c->partial, c->list_n, 4 * LIST_SHARDS, \
-                                                                 c->dig, c->cand_dig, (c->use_digest && c->dig) ? 1 : 0, \
-                                                                 c->pending_skip, c->err, cl_n, 4 * LIST_SHARDS,      \
-                                                                 c->census_skip, c->acc_base, zero_n)
-    const bool c1 = c->Cmax <= 64;
     int *cl_n = census_mode(c) ? c->clist_n : nullptr;  // the old census dies with the old K^n: checked + cleared on the way
     const i64 zero_n = c->fold_clear ? (i64)(c->ovf_n + c->acc_n) : 0;  // ... and the next statistics pass finds its accumulators zeroed
     if (!c->fold_clear) cl_n = nullptr;
-    if (c->S <= 64) { if (c1) VK_LAUNCH(1, 1); else VK_LAUNCH(1, 4); }
-    else if (c->S <= 128) { if (c1) VK_LAUNCH(2, 1); else VK_LAUNCH(2, 4); }
-    else if (c->S <= 256) { if (c1) VK_LAUNCH(4, 1); else VK_LAUNCH(4, 4); }
-    else if (c->S <= 512) { if (c1) VK_LAUNCH(8, 1); else VK_LAUNCH(8, 4); }
-    else { if (c1) VK_LAUNCH(16, 1); else VK_LAUNCH(16, 4); }
-#undef VK_LAUNCH
+    with_spl(c->S, [&](auto spl) {
+      with_cpl(c->Cmax, [&](auto cpl) {
+        vary_kn_kernel<decltype(spl)::value, decltype(cpl)::value><<<cdiv(c->N, 4), 256, 0, c->stream>>>(
+            c->states, c->lpj, c->cand, c->cand_lpj, c->cand_counts, c->N, c->S, c->S_perm, c->HW, c->Cmax, Mprime, c->rowmax,
+            c->rowsum, c->partial, c->list_n, 4 * LIST_SHARDS, c->dig, c->cand_dig, (c->use_digest && c->dig) ? 1 : 0,
+            c->pending_skip, c->err, cl_n, 4 * LIST_SHARDS, c->census_skip, c->acc_base, zero_n);
+      });
+    });
     reduce3_partials_kernel<<<1, R3_THREADS, 0, c->stream>>>(c->partial, cdiv(c->N, 4), c->dpar);
     HIP_TRY(hipGetLastError());
     DBG_SYNC(c, "vary_kn");
-    c->rows_fresh = true;
-    if (cl_n) {
-      c->clist_clean = true;
-      c->census_skip = 0;
-    }
-    c->acc_clean = zero_n > 0;
-    c->lists_clean = c->model == EVOAMD_MODEL_SSSC;  // vary_kn zeroed the overflow counters
-    if (c->lists_clean) c->pending_skip = 0;          // ... and checked the skipped levels of the chain before it
+    made_selection(c, cl_n != nullptr, zero_n > 0);
   }
   if (sums_out) {
     HIP_TRY(hipMemcpyAsync(sums_out, c->dpar + DP_ECNT0, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
   return 0;
+}
+
+extern "C" int evoamd_vary_kn(evoamd_ctx *c, int Mprime, double *sums_out) {
+  REQUIRE(c && c->configured && c->have_cand, "no resident candidate batch (call lpj_candidates / evolve first)");
+  TRY(estep_check_mprime(c, Mprime));
+  REQUIRE_KN(c);
+  HIP_TRY(hipSetDevice(c->device));
+  return estep_select(c, Mprime, sums_out);
 }
 
 extern "C" int evoamd_set_estep_counts(evoamd_ctx *c, double sum_nunique, double sum_sub) {
@@ -2718,37 +2842,31 @@ extern "C" int evoamd_set_estep_counts(evoamd_ctx *c, double sum_nunique, double
   return 0;
 }
 
-extern "C" int evoamd_evolve_randflip(evoamd_ctx *c, int n_parents, int n_children, uint64_t seed, int fit_parents) {
-  REQUIRE(c && c->configured && c->have_data && c->have_params, "configure, upload_data and set_params first");
-  REQUIRE(n_parents >= 1 && n_parents <= c->S && n_parents <= 64, "n_parents must be in [1, min(S, 64)]");
-  REQUIRE(n_children >= 1 && n_children <= EV_MAX_CHILDREN && n_children <= c->H, "n_children must be in [1, min(8, H)]");
-  REQUIRE(n_parents * n_children <= c->Cmax, "n_parents * n_children exceeds the configured Cmax");
-  REQUIRE_KN(c);
-  HIP_TRY(hipSetDevice(c->device));
+// ---- E-step stage: randflip children of the selected parents and their lpj
+static int estep_children(evoamd_ctx *c, int n_parents, int n_children, uint64_t seed, int fit_parents) {
   {
     SpanGuard g(c, KID_EVOLVE);
-#define EV_LAUNCH(SPL)                                                                                         \
-  evolve_randflip_kernel<SPL><<<cdiv(c->N, 4), 256, 0, c->stream>>>(c->states, c->lpj, c->N, c->S, c->S_perm, c->H - c->bg_unit, \
-                                                                    c->HW, n_parents, n_children, c->Cmax, seed,  \
-                                                                    fit_parents, c->cand, c->cand_counts, c->list_n,   \
-                                                                    c->model == EVOAMD_MODEL_SSSC ? 4 * LIST_SHARDS : 0, \
-                                                                    c->cand_dig, c->pending_skip, c->err)
-    if (c->S <= 64) EV_LAUNCH(1);
-    else if (c->S <= 128) EV_LAUNCH(2);
-    else if (c->S <= 256) EV_LAUNCH(4);
-    else if (c->S <= 512) EV_LAUNCH(8);
-    else EV_LAUNCH(16);
-#undef EV_LAUNCH
+    with_spl(c->S, [&](auto spl) {
+      evolve_randflip_kernel<decltype(spl)::value><<<cdiv(c->N, 4), 256, 0, c->stream>>>(
+          c->states, c->lpj, c->N, c->S, c->S_perm, c->H - c->bg_unit, c->HW, n_parents, n_children, c->Cmax, seed, fit_parents,
+          c->cand, c->cand_counts, c->list_n, c->model == EVOAMD_MODEL_SSSC ? 4 * LIST_SHARDS : 0, c->cand_dig, c->pending_skip,
+          c->err);
+    });
     HIP_TRY(hipGetLastError());
     DBG_SYNC(c, "evolve");
-    c->lists_clean = c->model == EVOAMD_MODEL_SSSC;
-    if (c->lists_clean) c->pending_skip = 0;
-    c->cand_from_device = true;
+    made_clean_lists(c);
+    on_cand_installed(c, /*near_parents=*/true);
   }
-  int r = eval_candidates(c);
-  if (r) return r;
-  c->have_cand = true;
+  TRY(eval_candidates(c));
+  made_cand_lpj(c);
   return 0;
+}
+
+extern "C" int evoamd_evolve_randflip(evoamd_ctx *c, int n_parents, int n_children, uint64_t seed, int fit_parents) {
+  TRY(estep_check_randflip(c, n_parents, n_children));
+  REQUIRE_KN(c);
+  HIP_TRY(hipSetDevice(c->device));
+  return estep_children(c, n_parents, n_children, seed, fit_parents);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2765,126 +2883,138 @@ static bool fused_shape_ok(const evoamd_ctx *c, int n_parents, int n_children) {
          ((size_t)(1024 / c->S + 2) * c->H + (c->H <= 512 ? (size_t)4 * c->H : 0)) * sizeof(double) <= MAIN_LPJ_LDS_MAX;
 }
 
+#define FUSED_LDS_MAX (150 * 1024)  // dynamic LDS of one workgroup of the fused kernel
+// Shards below this many resident states: the fused kernel lists the census of the NEW K^n itself (a launch saved); on
+// larger ones census_kernel does (its 35-47 us at the north-star shape are less than the ~70 the ballots and reservations
+// cost inside the fused kernel).  Read by the launch and by the census "made" event.
+static const i64 INKERNEL_CENSUS_BELOW = (i64)4 << 20;
+
+// One launch of the fused kernel.  Two launches of one body: every datapoint with LDS for 16 latents per pivoted child,
+// then -- from a list on the device, empty in practice -- the datapoints that met a denser child, one wave per workgroup
+// with LDS for SSSC_KCAP latents.
+struct FusedStage {
+  int W, kc_big, lds_wave_bytes;
+  size_t lds;
+  unsigned grid;
+};
+// Every host decision of evoamd_estep.  Filled by estep_plan from the context as it is at entry; enqueues nothing.
+struct EstepPlan {
+  bool fused = false;            // one fused kernel per datapoint, else the separate passes
+  int spl = 1;                   // states per lane (with_spl)
+  bool inkernel_census = false;  // fused route: the kernel lists the new K^n
+  FusedStage st[2] = {};
+};
+
+static int estep_plan(const evoamd_ctx *c, int n_parents, int n_children, EstepPlan &p) {
+  p = EstepPlan{};
+  with_spl(c->S, [&](auto spl) { p.spl = decltype(spl)::value; });
+  // Sparse enough: FAST leaves every datapoint that meets a state above four latents to the low-occupancy FULL launches
+  // -- the census of the last statistics pass says how many states there are above four
+  p.fused = c->fused_opt != 0 && fused_shape_ok(c, n_parents, n_children);
+  if (p.fused && c->fused_opt == 1) p.fused = c->need_known && c->res_cnt[1] <= 0.25 * (double)c->N;
+  if (!p.fused) return 0;
+  p.inkernel_census = c->N * (i64)c->S < INKERNEL_CENSUS_BELOW;
+  const size_t tab = (size_t)4 * c->H * sizeof(double);
+  for (int stage = 0; stage < 2; stage++) {
+    FusedStage &st = p.st[stage];
+    st.W = stage == 0 ? 4 : 1;
+    st.kc_big = stage == 0 ? 16 : SSSC_KCAP;
+    st.lds_wave_bytes = fused_lds_wave_bytes(p.spl, st.kc_big);
+    auto lds_of = [&](int w) { return (stage == 0 ? tab : 0) + (size_t)w * st.lds_wave_bytes; };
+    while (stage == 1 && lds_of(1) > FUSED_LDS_MAX && st.kc_big > 16) {  // (S = 1024: the rows leave room for fewer latents)
+      st.kc_big -= 4;
+      st.lds_wave_bytes = fused_lds_wave_bytes(p.spl, st.kc_big);
+    }
+    while (st.W > 1 && lds_of(st.W) > FUSED_LDS_MAX) st.W >>= 1;
+    st.lds = lds_of(st.W);
+    REQUIRE(st.lds <= FUSED_LDS_MAX, "fused E-step: S too large for the LDS rows");
+    int per_cu = (int)((160 * 1024) / (st.lds + 256));
+    per_cu = std::max(1, std::min(per_cu, 8 / st.W));  // two waves per SIMD (256 registers; four waves with scratch traffic ran the same)
+    st.grid = (unsigned)std::min<i64>(cdiv(c->N, st.W), (i64)c->n_cu * per_cu);
+  }
+  return 0;
+}
+
 static int flush_reduce(evoamd_ctx *c);
 
-static int launch_estep_fused(evoamd_ctx *c, int n_parents, int n_children, uint64_t seed, int fit_parents, int Mprime) {
-  int r = flush_reduce(c);  // (a previous fused E-step whose counters nobody has read yet)
-  if (r) return r;
-  r = ensure_B(c);
-  if (r) return r;
+// ---- fused stage: resident states above two latents -- the list kernels over the census of THIS K^n (built by the last
+// fused call or by census_kernel), sixteen states per wave pass; their values land in the lpj row the fused kernel reads
+static int estep_fused_levels(evoamd_ctx *c) {
+  LevelHints lv = batch_hints(c, 0);
+  lv.levels_only = true;
+  return lpj_resident_launch(c, c->lpj, lv);
+}
+
+// ---- fused stage: the argument block both launches share (the per-launch fields: estep_fused_launch)
+static FusedArgs estep_fused_args(evoamd_ctx *c, const EstepPlan &p, int n_parents, int n_children, uint64_t seed, int fit_parents,
+                                  int Mprime) {
   Batch b = {c->states, nullptr, c->Y, c->Bm, c->yy, c->N, c->S, 0, c->lpj, c->L, 0, c->flags, KID_LPJ_RES, 0};
   FusedArgs f = {};
   f.a = sssc_args(c, b);
-  f.states = c->states;
-  f.dig = c->dig;
-  f.lpj = c->lpj;
-  f.S = c->S;
-  f.n_parents = n_parents;
-  f.n_children = n_children;
-  f.fit_parents = fit_parents;
-  f.Mprime = Mprime;
-  f.seed = seed;
-  f.rowmax = c->rowmax;
-  f.rowsum = c->rowsum;
-  f.rowF = c->rowF;
-  f.rowcnt = c->rowcnt;
-  f.flags_res = c->flags;
-  f.flags_cand = c->flags + c->N;
+  f.states = c->states, f.dig = c->dig, f.lpj = c->lpj, f.S = c->S;
+  f.n_parents = n_parents, f.n_children = n_children, f.fit_parents = fit_parents, f.Mprime = Mprime, f.seed = seed;
+  f.rowmax = c->rowmax, f.rowsum = c->rowsum, f.rowF = c->rowF, f.rowcnt = c->rowcnt;
+  f.flags_res = c->flags, f.flags_cand = c->flags + c->N;
   f.list_cap = (int)c->N;
-#ifdef FUSED_PROFILE
-  if (!c->fprof) {
-    TRY(c->fprof.alloc(8));
-    HIP_TRY(hipMemset(c->fprof, 0, 8 * sizeof(unsigned long long)));
-  }
-  f.prof = c->fprof;
-#endif
-  f.cand = c->cand;
-  f.Cmax = c->Cmax;
-  int *list1 = c->defer, *cnt1 = c->defer + c->N;
-  const int SPL = c->S <= 64 ? 1 : (c->S <= 128 ? 2 : (c->S <= 256 ? 4 : (c->S <= 512 ? 8 : 16)));
-  const size_t tab = (size_t)4 * c->H * sizeof(double);
-  // resident states above two latents: the list kernels over the census of THIS K^n (built by the last fused call or by
-  // census_kernel), sixteen states per wave pass; their values land in the lpj row the fused kernel reads
-  {
-    LevelHints lv = batch_hints(c, 0);
-    lv.levels_only = true;
-    const int rl = lpj_resident_launch(c, c->lpj, lv);
-    if (rl) return rl;
-  }
-  HIP_TRY(hipMemsetAsync(cnt1, 0, sizeof(int), c->stream));
-  // the census of the NEW K^n: by the kernel itself on small shards (a launch saved), by census_kernel on large ones (its
-  // 35-47 us at the north-star shape are less than the ~70 the ballots and reservations cost inside the fused kernel)
-  const bool inkernel_census = c->N * (i64)c->S < ((i64)4 << 20);
-  if (inkernel_census) {
-    check_lists_kernel<<<1, 256, 0, c->stream>>>(c->clist_n, 4 * LIST_SHARDS, c->census_skip, c->err);
-    c->census_skip = 0;
-    c->clist_clean = false;  // the fused kernel appends to them
+  f.cand = c->cand, f.Cmax = c->Cmax;
+  if (p.inkernel_census) {
     f.cen_items = c->clist;
     f.cen_n = c->clist_n;
     f.cen_stride = (i64)c->clist_words();
     f.cen_cap = (int)list_cap(c->N * (i64)c->S);
   }
+  return f;
+}
+
+#ifdef FUSED_PROFILE
+static int estep_fused_profile(evoamd_ctx *c) {
+  unsigned long long h[8];
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpy(h, c->fprof, sizeof(h), hipMemcpyDeviceToHost));
+  if ((c->fused_calls % 50) == 49) {
+    fprintf(stderr, "[fused profile] wave cycles per datapoint:");
+    for (int i = 0; i < 8; i++) fprintf(stderr, " p%d %.0f", i, (double)h[i] / (double)c->N / (double)(c->fused_calls + 1));
+    fprintf(stderr, "\n");
+  }
+  return 0;
+}
+#endif
+
+// ---- fused stage: the deferral counter, the old census's check where the kernel lists the new one, the two launches
+static int estep_fused_launch(evoamd_ctx *c, const EstepPlan &p, FusedArgs &f) {
+  int *list1 = c->defer, *cnt1 = c->defer + c->N;
+  HIP_TRY(hipMemsetAsync(cnt1, 0, sizeof(int), c->stream));
+  if (p.inkernel_census) {
+    check_lists_kernel<<<1, 256, 0, c->stream>>>(c->clist_n, 4 * LIST_SHARDS, c->census_skip, c->err);
+    on_census_claimed(c);  // the fused kernel appends to them
+  }
   SpanGuard g(c, KID_ESTEP_FUSED);
-  // two launches of one body: every datapoint with LDS for 16 latents per pivoted child, then -- from a list on the device,
-  // empty in practice -- the datapoints that met a denser child, one wave per workgroup with LDS for SSSC_KCAP latents
   for (int stage = 0; stage < 2; stage++) {
+    const FusedStage &st = p.st[stage];
     f.in_items = stage == 0 ? nullptr : list1;
     f.in_count = stage == 0 ? nullptr : cnt1;
     f.out_items = stage == 0 ? list1 : nullptr;
     f.out_count = stage == 0 ? cnt1 : nullptr;
-    int W = stage == 0 ? 4 : 1;
-    f.kc_big = stage == 0 ? 16 : SSSC_KCAP;
+    f.kc_big = st.kc_big;
     f.stage_d1 = stage == 0;
-    f.lds_wave_bytes = fused_lds_wave_bytes(SPL, f.kc_big);
-    auto lds_of = [&](int w) { return (f.stage_d1 ? tab : 0) + (size_t)w * f.lds_wave_bytes; };
-    while (stage == 1 && lds_of(1) > 150 * 1024 && f.kc_big > 16) {  // (S = 1024: the rows leave room for fewer latents)
-      f.kc_big -= 4;
-      f.lds_wave_bytes = fused_lds_wave_bytes(SPL, f.kc_big);
-    }
-    while (W > 1 && lds_of(W) > 150 * 1024) W >>= 1;
-    const size_t lds = lds_of(W);
-    REQUIRE(lds <= 150 * 1024, "fused E-step: S too large for the LDS rows");
-    int per_cu = (int)((160 * 1024) / (lds + 256));
-    per_cu = std::max(1, std::min(per_cu, 8 / W));  // two waves per SIMD (256 registers; four waves with scratch traffic ran the same)
-    const unsigned grid = (unsigned)std::min<i64>(cdiv(c->N, W), (i64)c->n_cu * per_cu);
-#define FUSED_LAUNCH(SPLV)                                                               \
-  do {                                                                                   \
-    if (stage)                                                                           \
-      sssc_estep_fused_kernel<SPLV, true><<<grid, 64 * W, lds, c->stream>>>(f);          \
-    else                                                                                 \
-      sssc_estep_fused_kernel<SPLV, false><<<grid, 64 * W, lds, c->stream>>>(f);         \
-  } while (0)
-    switch (SPL) {
-      case 1: FUSED_LAUNCH(1); break;
-      case 2: FUSED_LAUNCH(2); break;
-      case 4: FUSED_LAUNCH(4); break;
-      case 8: FUSED_LAUNCH(8); break;
-      default: FUSED_LAUNCH(16); break;
-    }
-#undef FUSED_LAUNCH
+    f.lds_wave_bytes = st.lds_wave_bytes;
+    with_spl(c->S, [&](auto spl) {
+      if (stage)
+        sssc_estep_fused_kernel<decltype(spl)::value, true><<<st.grid, 64 * st.W, st.lds, c->stream>>>(f);
+      else
+        sssc_estep_fused_kernel<decltype(spl)::value, false><<<st.grid, 64 * st.W, st.lds, c->stream>>>(f);
+    });
     HIP_TRY(hipGetLastError());
     DBG_SYNC(c, stage == 0 ? "fused E-step" : "fused E-step (listed datapoints, KCAP latents)");
   }
-  c->reduce_pending = true;  // summed in front of the first reader (statistics pass: beside the forked contraction)
-#ifdef FUSED_PROFILE
-  {
-    unsigned long long h[8];
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(h, c->fprof, sizeof(h), hipMemcpyDeviceToHost));
-    if ((c->fused_calls % 50) == 49) {
-      fprintf(stderr, "[fused profile] wave cycles per datapoint:");
-      for (int i = 0; i < 8; i++) fprintf(stderr, " p%d %.0f", i, (double)h[i] / (double)c->N / (double)(c->fused_calls + 1));
-      fprintf(stderr, "\n");
-    }
-  }
-#endif
+  made_fused_rows(c, /*reduced=*/false);  // summed in front of the first reader (statistics pass: beside the forked contraction)
   return 0;
 }
 
 // rowF / rowcnt of the fused E-step -> dpar[DP_FS], dpar[DP_ECNT0 / 1]
 static int flush_reduce(evoamd_ctx *c) {
   if (!c->reduce_pending) return 0;
-  c->reduce_pending = false;
+  made_fused_rows(c, /*reduced=*/true);
   fused_reduce3_kernel<<<FR3_BLOCKS, R3_THREADS / FR3_BLOCKS, 0, c->stream>>>(c->rowF, c->rowcnt, c->N, c->dpar, c->fpart,
                                                                               (unsigned *)(c->defer + 2 * (c->N + 1)));
   HIP_TRY(hipGetLastError());
@@ -2893,39 +3023,39 @@ static int flush_reduce(evoamd_ctx *c) {
 }
 
 extern "C" int evoamd_estep(evoamd_ctx *c, int n_parents, int n_children, uint64_t seed, int fit_parents, int Mprime, int *fused_out) {
-  REQUIRE(c && c->configured && c->have_data && c->have_params, "configure, upload_data and set_params first");
-  REQUIRE(n_parents >= 1 && n_parents <= c->S && n_parents <= 64, "n_parents must be in [1, min(S, 64)]");
-  REQUIRE(n_children >= 1 && n_children <= EV_MAX_CHILDREN && n_children <= c->H, "n_children must be in [1, min(8, H)]");
-  REQUIRE(n_parents * n_children <= c->Cmax, "n_parents * n_children exceeds the configured Cmax");
-  REQUIRE(Mprime >= 1 && Mprime <= c->S, "Mprime must be in [1, S]");
+  TRY(estep_check_randflip(c, n_parents, n_children));
+  TRY(estep_check_mprime(c, Mprime));
   REQUIRE_KN(c);
   HIP_TRY(hipSetDevice(c->device));
-  // Sparse enough: FAST leaves every datapoint that meets a state above four latents to the low-occupancy FULL launches
-  // -- the census of the last statistics pass says how many states there are above four
-  bool fused = c->fused_opt != 0 && fused_shape_ok(c, n_parents, n_children);
-  if (fused && c->fused_opt == 1) fused = c->need_known && c->res_cnt[1] <= 0.25 * (double)c->N;
-  if (fused_out) *fused_out = fused ? 1 : 0;
-  if (!fused) {
+  EstepPlan p;
+  TRY(estep_plan(c, n_parents, n_children, p));
+  if (fused_out) *fused_out = p.fused ? 1 : 0;
+  if (!p.fused) {
     c->unfused_calls++;
-    c->last_estep_fused = false;
-    int r = evoamd_lpj_resident(c);
-    if (r) return r;
-    r = evoamd_evolve_randflip(c, n_parents, n_children, seed, fit_parents);
-    if (r) return r;
-    return evoamd_vary_kn(c, Mprime, nullptr);
+    on_estep_route(c, /*fused=*/false);
+    TRY(estep_resident_pass(c));
+    TRY(estep_children(c, n_parents, n_children, seed, fit_parents));
+    return estep_select(c, Mprime, nullptr);
   }
   c->fused_calls++;
-  c->prefetch_gen = ~0ull;  // a prefetched pass over K^n (if any) is not needed
-  c->rows_fresh = false;
-  int r = launch_estep_fused(c, n_parents, n_children, seed, fit_parents, Mprime);
-  if (r) return r;
-  c->gen++;
-  c->kn_gen++;
-  if (c->N * (i64)c->S < ((i64)4 << 20)) c->census_gen = c->kn_gen;  // the fused kernel listed the new K^n on the way
-  c->rows_fresh = true;
-  c->have_cand = false;  // the children never left the kernel
-  c->cand_from_device = true;
-  c->last_estep_fused = true;
+  drop_prefetch(c);  // a prefetched pass over K^n (if any) is not needed
+  on_lpj_overwritten(c);
+  TRY(flush_reduce(c));  // (a previous fused E-step whose counters nobody has read yet)
+  TRY(ensure_B(c));
+  FusedArgs f = estep_fused_args(c, p, n_parents, n_children, seed, fit_parents, Mprime);
+#ifdef FUSED_PROFILE
+  if (!c->fprof) {
+    TRY(c->fprof.alloc(8));
+    HIP_TRY(hipMemset(c->fprof, 0, 8 * sizeof(unsigned long long)));
+  }
+  f.prof = c->fprof;
+#endif
+  TRY(estep_fused_levels(c));
+  TRY(estep_fused_launch(c, p, f));
+#ifdef FUSED_PROFILE
+  TRY(estep_fused_profile(c));
+#endif
+  made_fused_estep(c, p.inkernel_census);
   return 0;
 }
 
@@ -2946,10 +3076,10 @@ extern "C" int evoamd_estep_counters(evoamd_ctx *c, int64_t out[4]) {
 
 extern "C" int evoamd_evolve_states(evoamd_ctx *c, int mutation, int fit_parents, int n_parents, int n_children,
                                     int n_generations, uint64_t seed, double sparseness, double bitflip_prob) {
-  REQUIRE(c && c->configured && c->have_data && c->have_params, "configure, upload_data and set_params first");
+  TRY(estep_check_ready(c));
   REQUIRE(mutation >= EV_RANDFLIP && mutation <= EV_CROSS_SPARSEFLIP, "unknown mutation operator");
   REQUIRE_KN(c);
-  REQUIRE(n_parents >= 1 && n_parents <= c->S && n_parents <= 64, "n_parents must be in [1, min(S, 64)]");
+  TRY(estep_check_parents(c, n_parents));
   REQUIRE(n_generations >= 1, "n_generations must be positive");
   const bool crossing = mutation >= EV_CROSS;
   const int per_gen = crossing ? n_parents * (n_parents - 1) : n_parents * n_children;
@@ -2998,12 +3128,10 @@ extern "C" int evoamd_evolve_states(evoamd_ctx *c, int mutation, int fit_parents
       HIP_TRY(hipGetLastError());
       DBG_SYNC(c, "evolve (general)");
     }
-    // children may differ from every resident state in many bits: no shortcut for the overflow levels
-    c->cand_from_device = false;
-    int r = eval_candidates(c);  // the next generation's pool needs these lpj (eas.py:264)
-    if (r) return r;
+    on_cand_installed(c, /*near_parents=*/false);  // children may differ from every resident state in many bits
+    TRY(eval_candidates(c));  // the next generation's pool needs these lpj (eas.py:264)
   }
-  c->have_cand = true;
+  made_cand_lpj(c);
   return 0;
 }
 
@@ -3012,8 +3140,7 @@ extern "C" int evoamd_download_candidates(evoamd_ctx *c, uint8_t *cand_bool, int
   REQUIRE(cand_bool && counts && lpj, "NULL output");
   HIP_TRY(hipSetDevice(c->device));
   const i64 ns = c->N * (i64)c->Cmax;
-  int r = c->stage.ensure(c, (size_t)ns * c->H);
-  if (r) return r;
+  TRY(c->stage.ensure(c, (size_t)ns * c->H));
   unpack_states_kernel<<<cdiv(ns * c->H, 256), 256, 0, c->stream>>>(c->cand, c->stage, ns, c->H, c->HW);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(cand_bool, c->stage, (size_t)ns * c->H, hipMemcpyDeviceToHost, c->stream));
@@ -3033,7 +3160,7 @@ static int row_lse(evoamd_ctx *c, const double *lpj, i64 N, int L, double *rowma
   const unsigned nb = cdiv(N, 4);
   TRY(c->partial.ensure(c, (size_t)3 * nb));
   TRY(c->partial2.ensure(c, nb));
-  if (lpj != c->lpj) c->rows_fresh = false;  // the partial buffer now belongs to another matrix
+  if (lpj != c->lpj) on_lpj_overwritten(c);  // the partial buffer now belongs to another matrix
   SpanGuard g(c, KID_ROW_LSE);
   row_lse_kernel<<<nb, 256, 0, c->stream>>>(lpj, N, L, rowmax, rowsum, c->partial);
   reduce_partials_kernel<<<1, 256, 0, c->stream>>>(c->partial, nb, out_slot, 0);
@@ -3171,13 +3298,11 @@ static int rows_written(evoamd_ctx *c, const StatsPlan &p, StatsFlow &fl) {
 // incomplete data: y_hat = E W^T under the Theta of this E-step, and y_reconstructed from it -- the rows the Wp
 // contraction reads.  `asked_msg`: ES3C requires rec_in_stats, and says so between the two launches.
 static int reconstruct_rows(evoamd_ctx *c, const char *asked_msg = nullptr) {
-  int r = compute_reconstruction(c);
-  if (r) return r;
+  TRY(compute_reconstruction(c));
   if (asked_msg) REQUIRE(c->rec_in_stats, asked_msg);
   select_rec_kernel<<<cdiv(c->N, 4), 256, 0, c->stream>>>(c->Y, c->ldY, c->mask_x, c->mask_infr, c->yhat, c->N, c->D, c->Yrec);
   HIP_TRY(hipGetLastError());
-  c->yrec_valid = c->yrec_from_pass = true;
-  c->rec_in_stats = false;
+  made_yrec_from_pass(c, /*in_stats=*/true);
   return 0;
 }
 
@@ -3216,8 +3341,7 @@ static int stats_plan(evoamd_ctx *c, bool fork_gemm, StatsPlan &p) {
     // issue three all-reduces and others one: agree once per geometry (max over ranks), same call on every rank
     if (c->pays_agreed < 0) {
       double v = pays ? 1.0 : 0.0;
-      int ra = evoamd_comm_allreduce_host(c, &v, 1, 1);
-      if (ra) return ra;
+      TRY(evoamd_comm_allreduce_host(c, &v, 1, 1));
       c->pays_agreed = v > 0.0 ? 1 : 0;
     }
     pays = c->pays_agreed == 1;
@@ -3283,7 +3407,7 @@ static int stats_bsc_wave(evoamd_ctx *c, const StatsPlan &p, const StatsBlock &b
   if (sgrid > 2048) sgrid = 2048;  // the size of the sigma partials
   if (bsc_pb.ent && sgrid > bsc_pb.nwg) sgrid = bsc_pb.nwg;  // one private region per producer workgroup and bin
   PB_GRID_CHECK(bsc_pb, sgrid);
-  if (bsc_pb.ent) c->bins_dirty = true;
+  if (bsc_pb.ent) on_bins_append(c);
   fl.bsc_grid = sgrid;
   void *EsP = c->f32 ? (void *)c->Esf : (void *)c->Es;
   double *csb = c->acc_base + 4;
@@ -3297,13 +3421,12 @@ static int stats_bsc_wave(evoamd_ctx *c, const StatsPlan &p, const StatsBlock &b
 #undef BSC_WAVE
   HIP_TRY(hipGetLastError());
   DBG_SYNC(c, "bsc stats (wave)");
-  int r = rows_written(c, p, fl);  // the E_q[s] rows are written: the product may start
-  if (r) return r;
+  TRY(rows_written(c, p, fl));  // the E_q[s] rows are written: the product may start
   if (bsc_pb.ent) {
     pair_bins_reduce_kernel<<<bsc_pb.nb * bsc_pb.nsh, PB_RTHREADS, (size_t)3 * 2 * bsc_pb.rf * H * sizeof(double), c->stream>>>(
         bsc_pb, H, 0);
     HIP_TRY(hipGetLastError());
-    c->bins_dirty = false;
+    made_bins_clean(c);
   }
   return 0;
 }
@@ -3340,12 +3463,10 @@ static int stats_bsc_classic(evoamd_ctx *c, const StatsPlan &p, const StatsBlock
 
 // ---- EBSC producers of one block, then (incomplete data) the rows the Wp contraction reads instead of Y
 static int stats_bsc_block(evoamd_ctx *c, const StatsPlan &p, const StatsBlock &blk, StatsFlow &fl, const double *&Ywp, int &ldwp) {
-  int r = p.bsc_wave ? stats_bsc_wave(c, p, blk, fl) : stats_bsc_classic(c, p, blk);
-  if (r) return r;
+  TRY(p.bsc_wave ? stats_bsc_wave(c, p, blk, fl) : stats_bsc_classic(c, p, blk));
   if (p.masked) {  // incomplete data: the Wp contraction reads y_reconstructed (bsc.py:184-189,211); one block only
     if (c->rec_in_stats) {
-      r = reconstruct_rows(c);  // y_hat = Es W^T under the Theta of this E-step (_models.py:193-194)
-      if (r) return r;
+      TRY(reconstruct_rows(c));  // y_hat = Es W^T under the Theta of this E-step (_models.py:193-194)
     }
     REQUIRE(c->yrec_valid, "incomplete data: the M-step needs y_reconstructed (bsc.py:186); reconstruct or upload it");
     Ywp = c->Yrec;
@@ -3413,8 +3534,7 @@ static Es3cBlock sssc_block_setup(evoamd_ctx *c, const StatsPlan &p, const Es3cP
 static int stats_sssc_census_quads(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep, const Es3cBlock &eb, StatsFlow &fl) {
   const bool *need = ep.need;
   const PairBins &pb = fl.pb;
-  int r = ensure_census(c);
-  if (r) return r;
+  TRY(ensure_census(c));
   if (need[0] || need[1]) {
     SpanGuard g(c, KID_STATS_OVF);
     const unsigned gcap = pb.ent ? (unsigned)std::min(2048, pb.nwg) : 2048u;
@@ -3505,7 +3625,7 @@ static int stats_sssc_census_levels(evoamd_ctx *c, const Es3cPass &ep, const Es3
     SpanGuard g(c, KID_STATS_OVF);
     SpanGuard gl(c, KID_STATS_K9P);
     const int served = census_wavefront_levels<1, 2>(c, eb.sc, ep.ls, need, eb.few4, eb.lv, eb.total);
-    if (!(served & 2)) c->pending_skip |= 2;  // (as in launch_sssc_lpj: nobody serves the on-the-fly list 2)
+    on_levels_skipped(c, /*census_route=*/true, 0, served, true);  // (as in launch_sssc_lpj: nobody serves the on-the-fly list 2)
     HIP_TRY(hipGetLastError());
     DBG_SYNC(c, "sssc stats wavefront level (census)");
   }
@@ -3561,8 +3681,7 @@ static int stats_sssc_block(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &e
                             bool debug_fail) {
   PairBins &pb = fl.pb;
   const Es3cBlock eb = sssc_block_setup(c, p, ep, blk);
-  int r;
-  if (pb.ent) c->bins_dirty = true;  // this block's producers append; until its reduce (which zeroes the counters)
+  if (pb.ent) on_bins_append(c);  // this block's producers append; until its reduce (which zeroes the counters)
   if (blk.ci > 0) {  // the previous block's overflow census joins the running sum; fresh lists for this block
     census_lists_kernel<<<1, 256, 0, c->stream>>>(c->list_n, LIST_SHARDS, skip_mask(ep.need), c->err, c->census);
     HIP_TRY(hipGetLastError());
@@ -3573,23 +3692,17 @@ static int stats_sssc_block(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &e
     pb.nwg = std::min(pb.nwg, c->n_cu);
     pb.cap = (int)std::min<i64>(per_bin / pb.nwg, 1 << 30);
   }
-  if (p.census) {
-    r = stats_sssc_census_quads(c, p, ep, eb, fl);
-    if (r) return r;
-  }
-  r = stats_sssc_main(c, p, ep, eb, blk, fl);
-  if (r) return r;
+  if (p.census) TRY(stats_sssc_census_quads(c, p, ep, eb, fl));
+  TRY(stats_sssc_main(c, p, ep, eb, blk, fl));
   if (debug_fail)  // test hook: a pass that returns between its producers and the pair-bin reduce
     return fail(EVOAMD_E_INVALID, "debug_fail_stats: statistics pass stopped after its main kernel");
-  r = p.census ? stats_sssc_census_levels(c, ep, eb) : stats_sssc_chain_levels(c, p, ep, eb, fl);
-  if (r) return r;
-  r = rows_written(c, p, fl);
-  if (r) return r;
+  TRY(p.census ? stats_sssc_census_levels(c, ep, eb) : stats_sssc_chain_levels(c, p, ep, eb, fl));
+  TRY(rows_written(c, p, fl));
   if (pb.ent) {  // the entries of the main kernel and of the register-kernel levels: one tile pass per block
     SpanGuard g(c, KID_STATS);
     pair_bins_reduce_kernel<<<pb.nb * pb.nsh, PB_RTHREADS, (size_t)3 * 2 * pb.rf * p.H * sizeof(double), c->stream>>>(pb, p.H, blk.ci > 0);
     HIP_TRY(hipGetLastError());
-    c->bins_dirty = false;
+    made_bins_clean(c);
     DBG_SYNC(c, "pair bins reduce");
   }
   // a skipped level must have found its input list empty (census_lists_kernel / tail_kernel check)
@@ -3612,7 +3725,7 @@ static int stats_finish(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep, S
       fl.tail_done = true;
     }
     double *wq_copy = (!c->comm && !masked && c->tmpA) ? c->tmpA : nullptr;
-    c->wq_copy_valid = wq_copy != nullptr;
+    made_wq_copy(c, wq_copy != nullptr);
     const unsigned fgrid = cdiv((i64)H * H, 256) + (fl.tail_done ? 1 : 0);
     if (p.bsc_wave)
       bsc_finish_kernel<<<fgrid, 256, 0, c->stream>>>(c->acc + a.Wq, c->acc + a.pies, c->acc_base + 4, BSC_CS_SLICES, H,
@@ -3675,13 +3788,11 @@ static int stats_contract_block(evoamd_ctx *c, const StatsPlan &p, const Es3cPas
 static int stats_sssc_masked_products(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep) {
   const AccLayout &a = p.a;
   const int H = p.H, D = p.D;
-  int r = reconstruct_rows(c, "ES3C on incomplete data needs do_reconstruction in every step (sssc.py:630-633)");
-  if (r) return r;
+  TRY(reconstruct_rows(c, "ES3C on incomplete data needs do_reconstruction in every step (sssc.py:630-633)"));
   GemmTnOpts o;
   o.c_is_zero = true;
   o.sym_row0 = (H % GEMM_BM) == 0 ? H : -1;
-  r = launch_gemm_tn(c, ep.Es, c->ldY, ep.Ez, c->ldY, c->acc + a.sWp + (size_t)D * H, H, 2 * H, H, p.N, o);
-  if (r) return r;
+  TRY(launch_gemm_tn(c, ep.Es, c->ldY, ep.Ez, c->ldY, c->acc + a.sWp + (size_t)D * H, H, 2 * H, H, p.N, o));
   o.sym_row0 = -1;
   return launch_gemm_tn(c, c->Yrec, D, ep.Ez, c->ldY, c->acc + a.sWp, H, D, H, p.N, o);
 }
@@ -3698,17 +3809,13 @@ static int stats_epilogue(evoamd_ctx *c, const StatsPlan &p, const StatsFlow &fl
     else
       HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join, 0));
   }
-  {
-    int rfr = flush_reduce(c);  // fused E-step: free-energy term and counters into the scalar block (beside the forked contraction)
-    if (rfr) return rfr;
-  }
+  TRY(flush_reduce(c));  // fused E-step: free-energy term and counters into the scalar block (beside the forked contraction)
   {
     SpanGuard g(c, KID_MISC);
     if (!fl.tail_done) tail_kernel<<<1, 256, 0, c->stream>>>(make_tail_args(c, a, N, p.census, fl.skipped));
     HIP_TRY(hipGetLastError());
     DBG_SYNC(c, "stats contraction + tail");
-    c->lists_clean = c->model == EVOAMD_MODEL_SSSC;
-    if (c->lists_clean) c->pending_skip = 0;
+    made_clean_lists(c);
     if (c->model == EVOAMD_MODEL_SSSC && c->mask_infr) {  // tail[7] = sum over reliable entries of y_hat^2
       masked_sqsum_kernel<<<256, 256, 0, c->stream>>>(c->yhat, c->mask_infr, N * (i64)p.D, c->acc + a.tail + 7);
       HIP_TRY(hipGetLastError());
@@ -3769,38 +3876,29 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
   REQUIRE(c && c->configured && c->have_data && c->have_params, "configure, upload_data and set_params first");
   REQUIRE_KN(c);
   StatsPlan p;
-  int r = stats_plan(c, fork_gemm, p);
-  if (r) return r;
+  TRY(stats_plan(c, fork_gemm, p));
   // ---- preamble
-  r = join_fork(c);  // a previous call that failed between fork and join must not race with the memset below
-  if (r) return r;
+  TRY(join_fork(c));  // a previous call that failed between fork and join must not race with the memset below
   HIP_TRY(hipSetDevice(c->device));
-  r = ensure_bins_capacity(c);
-  if (r) return r;
+  TRY(ensure_bins_capacity(c));
   if (c->bins_dirty && c->pbins.gcnt)  // an earlier pass returned between its producers and the reduce: stale region counts
     HIP_TRY(hipMemsetAsync(c->pbins.gcnt, 0, (size_t)c->pbins.nb * c->pbins.nwg * sizeof(int), c->stream));
-  c->bins_dirty = false;
   // test hook: consumed by every pass (it stops only an ES3C pass on complete data, after its main kernel)
   const bool debug_fail = c->debug_fail_stats != 0;
   c->debug_fail_stats = 0;
   if (!c->acc_clean)  // (else: zeroed by the selection kernel on its way)
     HIP_TRY(hipMemsetAsync(c->acc_base, 0, (size_t)(c->ovf_n + c->acc_n) * sizeof(double), c->stream));
-  c->acc_clean = false;
-  c->yhat_valid = c->stats_rows_valid = c->rec_resident = c->yrec_from_pass = false;
-  r = ensure_B(c);
-  if (r) return r;
+  on_stats_pass_begun(c);
+  TRY(ensure_B(c));
   if (!c->rows_fresh) {  // otherwise vary_kn left rowmax / rowsum / dpar[DP_FS] behind
-    r = row_lse(c, c->lpj, p.N, c->L, c->rowmax, c->rowsum, c->dpar + DP_FS);
-    if (r) return r;
+    TRY(row_lse(c, c->lpj, p.N, c->L, c->rowmax, c->rowsum, c->dpar + DP_FS));
   }
   StatsFlow fl;
   // the whole statistics pass (everything that reads K^n + lpj and leaves the M-step sums, the GEMM aside)
   std::unique_ptr<SpanGuard> pass(new SpanGuard(c, KID_STATS_PASS));
-  r = c->colpart.ensure(c, (size_t)p.nblk * (c->model == EVOAMD_MODEL_BSC ? p.H : 3 * p.H));
-  if (r) return r;
+  TRY(c->colpart.ensure(c, (size_t)p.nblk * (c->model == EVOAMD_MODEL_BSC ? p.H : 3 * p.H)));
   Es3cPass ep;
-  r = stats_sssc_pass(c, p, ep);
-  if (r) return r;
+  TRY(stats_sssc_pass(c, p, ep));
   const double *Ywp = c->Y;  // EBSC: what the Wp contraction reads
   int ldwp = c->ldY;
   if (c->model == EVOAMD_MODEL_SSSC && !p.masked && stats_bins_pay(c)) fl.pb = c->pbins;
@@ -3809,52 +3907,30 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
     const i64 n0 = (i64)ci * p.rows_per_chunk;
     const i64 nc = std::min<i64>(p.rows_per_chunk, p.N - n0);
     const StatsBlock blk = {ci, n0, nc, (int)(n0 / p.rpb), (int)cdiv(nc, p.rpb)};
-    if (c->model == EVOAMD_MODEL_BSC)
-      r = stats_bsc_block(c, p, blk, fl, Ywp, ldwp);
-    else if (p.masked)
-      r = stats_sssc_masked_block(c, p, ep);
-    else
-      r = stats_sssc_block(c, p, ep, blk, fl, debug_fail);
-    if (r) return r;
+    TRY(c->model == EVOAMD_MODEL_BSC ? stats_bsc_block(c, p, blk, fl, Ywp, ldwp)
+        : p.masked                   ? stats_sssc_masked_block(c, p, ep)
+                                     : stats_sssc_block(c, p, ep, blk, fl, debug_fail));
     if (ci == p.nchunks - 1) {
       // (before this block's contraction is enqueued: on one stream the span of the statistics pass must not cover it)
-      r = stats_finish(c, p, ep, fl);
-      if (r) return r;
+      TRY(stats_finish(c, p, ep, fl));
       pass.reset();
     }
     if (c->model == EVOAMD_MODEL_SSSC && p.masked) continue;  // two products from the reconstructed rows, below
-    r = stats_contract_block(c, p, ep, blk, fl, Ywp, ldwp);
-    if (r) return r;
+    TRY(stats_contract_block(c, p, ep, blk, fl, Ywp, ldwp));
   }
   // ---- epilogue
-  if (c->model == EVOAMD_MODEL_SSSC && p.masked) {
-    r = stats_sssc_masked_products(c, p, ep);
-    if (r) return r;
-  }
-  r = stats_epilogue(c, p, fl);
-  if (r) return r;
-  c->stats_rows_valid = true;
-  c->rows_kn_gen = c->kn_gen;
+  if (c->model == EVOAMD_MODEL_SSSC && p.masked) TRY(stats_sssc_masked_products(c, p, ep));
+  TRY(stats_epilogue(c, p, fl));
+  made_stats_rows(c);
   return 0;
-}
-
-// After the accumulator + scalar block reached the host: remember which overflow levels K^n needs.
-static void note_levels(evoamd_ctx *c, const double *dpar_host) {
-  if (c->model != EVOAMD_MODEL_SSSC) return;
-  for (int j = 0; j < 3; j++) {
-    c->res_cnt[j] = dpar_host[DP_NGT2 + j];
-    c->res_need[j] = c->res_cnt[j] > 0.0;
-  }
-  c->need_known = true;
 }
 
 extern "C" int evoamd_stats(evoamd_ctx *c, double *acc_out) {
   REQUIRE(acc_out, "acc_out is NULL");
-  int r = stats_compute(c);
-  if (r) return r;
+  TRY(stats_compute(c));
   HIP_TRY(hipMemcpyAsync(c->h_acc, c->acc, ((size_t)c->acc_n + DP_COUNT) * sizeof(double), hipMemcpyDeviceToHost,
                          c->stream));
-  r = check_err(c);  // synchronises the stream
+  const int r = check_err(c);  // synchronises the stream
   if (c->sssc_prec32 && c->model == EVOAMD_MODEL_SSSC) {
     // precision = float32: the reference keeps these sums in float32 arrays (sssc.py:484-498); here they are summed in
     // double and rounded once -- closer to the exact sums than the reference's own float32 running sums
@@ -3863,7 +3939,7 @@ extern "C" int evoamd_stats(evoamd_ctx *c, double *acc_out) {
     for (i64 i = a.s_sz; i < a.y2; i++) c->h_acc[i] = (double)(float)c->h_acc[i];
   }
   memcpy(acc_out, c->h_acc, (size_t)c->acc_n * sizeof(double));
-  if (!r) note_levels(c, c->h_acc + c->acc_n);
+  if (!r) made_level_hints(c, c->h_acc + c->acc_n);
   return r;
 }
 
@@ -4082,8 +4158,7 @@ static int theta_update_sssc(evoamd_ctx *c, const MstepPlan &p, unsigned long lo
   else if (learn & L_PSI)
     r = launch_inverse(c, c->tmpB, nullptr, H, p.force_pivot);
   if (r) return r;
-  r = join_fork(c);  // sWp / s_sz / sz_sz come from the contraction
-  if (r) return r;
+  TRY(join_fork(c));  // sWp / s_sz / sz_sz come from the contraction
   if (c->sssc_prec32) round_f32_kernel<<<cdiv(a.y2 - a.s_sz, 256), 256, 0, c->stream>>>(c->acc + a.s_sz, a.y2 - a.s_sz);
   if (learn & L_W)
     launch_gemm_nn_raw(c, c->acc + a.sWp, H, c->tmpA, H, c->W, H, D, H, H);
@@ -4097,11 +4172,9 @@ static int theta_update_sssc(evoamd_ctx *c, const MstepPlan &p, unsigned long lo
   HIP_TRY(hipGetLastError());
   GemmTnOpts gram;
   gram.deterministic = true;
-  r = launch_gemm_tn(c, c->W, H, c->W, H, c->G, H, H, H, D, gram);  // G = W^T W (new W)
-  if (r) return r;
+  TRY(launch_gemm_tn(c, c->W, H, c->W, H, c->G, H, H, H, D, gram));  // G = W^T W (new W)
   const int n_part = (int)std::min<i64>(1024, cdiv(HH, 1024));
-  r = c->colpart.ensure(c, (size_t)n_part);
-  if (r) return r;
+  TRY(c->colpart.ensure(c, (size_t)n_part));
   if (psi_with_trace)
     sssc_trace_partial_kernel<<<n_part, 256, 0, c->stream>>>(c->acc + a.sz_sz, c->G, H, cdiv(HH, n_part), c->colpart, c->tmpC,
                                                              c->tmpB, c->acc + a.s_sz, c->mus, c->Psi);
@@ -4118,15 +4191,12 @@ static int theta_update_sssc(evoamd_ctx *c, const MstepPlan &p, unsigned long lo
 static int theta_update_bsc(evoamd_ctx *c, const MstepPlan &p, unsigned long long fold_seq) {
   const AccLayout a = acc_layout(c);
   const int H = c->H, D = c->D, learn = p.learn;
-  int r = 0;
   if (learn & L_W) {  // W^T = solve(Wq, Wp)  (bsc.py:237; lstsq == solve for a non-singular Wq)
     if (!c->wq_copy_valid || p.force_pivot)  // (else the finish kernel of the statistics pass left the copy in tmpA)
       HIP_TRY(hipMemcpyAsync(c->tmpA, c->acc + a.Wq, (size_t)H * H * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    c->wq_copy_valid = false;
-    r = launch_inverse(c, c->tmpA, nullptr, H, p.force_pivot);
-    if (r) return r;
-    r = join_fork(c);  // Wp comes from the contraction
-    if (r) return r;
+    made_wq_copy(c, false);
+    TRY(launch_inverse(c, c->tmpA, nullptr, H, p.force_pivot));
+    TRY(join_fork(c));  // Wp comes from the contraction
     if (!launch_gemm_nn_raw(c, c->tmpA, H, c->acc + a.Wp, D, c->Wt, D, H, D, H, c->W, H))  // W^T, and W on the way
       transpose_kernel<<<cdiv((i64)H * D, 256), 256, 0, c->stream>>>(c->Wt, H, D, c->W);
   }
@@ -4137,14 +4207,11 @@ static int theta_update_bsc(evoamd_ctx *c, const MstepPlan &p, unsigned long lon
   return 0;
 }
 
-// the update of the context's model; Theta on the device is Theta^new behind it and B = Y W is stale
+// the update of the context's model; Theta on the device is Theta^new behind it (on_theta_updated: B = Y W is stale)
 static int theta_update(evoamd_ctx *c, const MstepPlan &p, unsigned long long fold_seq) {
-  c->gen++;
+  on_theta_update_begun(c);
   SpanGuard g(c, KID_MSTEP);
-  int r = c->model == EVOAMD_MODEL_SSSC ? theta_update_sssc(c, p, fold_seq) : theta_update_bsc(c, p, fold_seq);
-  if (r) return r;
-  c->B_valid = false;
-  return 0;
+  return c->model == EVOAMD_MODEL_SSSC ? theta_update_sssc(c, p, fold_seq) : theta_update_bsc(c, p, fold_seq);
 }
 
 // y_hat = E W^T with E = Es (EBSC) / Ez (ES3C) rows of the last statistics pass (see evoamd_reconstruct)
@@ -4165,7 +4232,7 @@ static int compute_reconstruction(evoamd_ctx *c) {
   SpanGuard g(c, KID_GEMM);
   launch_gemm_nn_raw(c, E, lde, Wt, c->D, c->yhat, c->D, c->N, c->D, c->H);
   HIP_TRY(hipGetLastError());
-  c->yhat_valid = true;
+  made_yhat(c);
   return 0;
 }
 
@@ -4174,8 +4241,7 @@ extern "C" int evoamd_reconstruct(evoamd_ctx *c, double *y_hat) {
   HIP_TRY(hipSetDevice(c->device));
   if (!c->yhat_valid) {
     REQUIRE(c->stats_rows_valid, "evoamd_reconstruct: call evoamd_stats first (and before setting new parameters)");
-    int r = compute_reconstruction(c);
-    if (r) return r;
+    TRY(compute_reconstruction(c));
   }
   HIP_TRY(hipMemcpyAsync(y_hat, c->yhat, (size_t)c->N * c->D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -4242,9 +4308,8 @@ static void prefetch_next_pass(evoamd_ctx *c) {
   if (!c->prefetch_lpj || c->mask_infr || c->last_estep_fused) return;  // (a fused E-step evaluates K^n itself)
   // the host has not read this iteration's overflow counts yet (they arrive with the mailbox being polled next), so
   // res_need / res_cnt still describe the K^n of the PREVIOUS iteration: conservative levels
-  c->prefetch_gen = ~0ull;
-  const int rp = lpj_resident_launch(c, c->lpj_alt, batch_hints(c, 0, /*prefetched=*/true));
-  if (rp == 0) c->prefetch_gen = c->gen;
+  drop_prefetch(c);
+  if (lpj_resident_launch(c, c->lpj_alt, batch_hints(c, 0, /*prefetched=*/true)) == 0) made_prefetch(c);
 }
 
 // Spins on the sequence number (falls back to a blocking synchronise after 20 ms of spinning).
@@ -4309,7 +4374,7 @@ static int mstep_backup(evoamd_ctx *c, const MstepPlan &p) {
   theta_backup_kernel<<<(unsigned)std::min<size_t>(256, cdiv((i64)n, 256 * 8)), 256, 0, c->stream_copy>>>(c->theta_bak, s, 0);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->ev_bak, c->stream_copy));
-  c->theta_bak_valid = true;
+  made_theta_backup(c);
   return 0;
 }
 
@@ -4317,18 +4382,13 @@ extern "C" int evoamd_restore_theta_backup(evoamd_ctx *c) {
   REQUIRE(c && c->configured, "configure first");
   REQUIRE(c->theta_bak && c->theta_bak_valid, "no parameter backup (evoamd_mstep_device keeps one when Theta stays on the device)");
   HIP_TRY(hipSetDevice(c->device));
-  int r = join_fork(c);
-  if (r) return r;
+  TRY(join_fork(c));
   HIP_TRY(hipStreamSynchronize(c->stream_copy));
   theta_backup_kernel<<<256, 256, 0, c->stream>>>(c->theta_bak, theta_segs(c), 1);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
   // the raw parameters are back; everything derived from them (G, tables, B = Y W) is rebuilt by the next set_params
-  c->gen++;
-  c->h_theta_fresh = false;
-  c->B_valid = false;
-  c->have_params = true;  // evoamd_get_params_* may read them
-  c->prefetch_gen = ~0ull;
+  on_theta_restored(c);
   return 0;
 }
 
@@ -4336,25 +4396,19 @@ extern "C" int evoamd_restore_theta_backup(evoamd_ctx *c) {
 // derives from Theta^new, the prefetched pass; then the host polls.
 static int mstep_attempt(evoamd_ctx *c, const MstepPlan &p) {
   unsigned long long fold_seq = 0;
-  int r;
   if (p.learn) {
     if (p.publish == PUBLISH_FOLDED) fold_seq = ++c->mbox_seq;
-    r = theta_update(c, p, fold_seq);
-    if (r) return r;
-    if (p.backup == BACKUP_IN_UPDATE) c->theta_bak_valid = true;
-    c->stats_rows_valid = false;  // the rows belong to the previous Theta now
+    TRY(theta_update(c, p, fold_seq));
+    on_theta_updated(c, p.backup == BACKUP_IN_UPDATE);
   }
-  r = join_fork(c);
-  if (r) return r;
+  TRY(join_fork(c));
   // accumulator tail (8) and the scalar block (16) are adjacent in device memory and in the mailbox;
   // the reference's step() hands Theta^new back, so it rides along unless it stays home
   MailboxTicket t;
-  r = mailbox_publish(c, p, fold_seq, t);
-  if (r) return r;
+  TRY(mailbox_publish(c, p, fold_seq, t));
   if (p.learn) {
     SpanGuard g(c, KID_MSTEP);
-    r = derive_from_theta(c, /*updated=*/true);
-    if (r) return r;
+    TRY(derive_from_theta(c, /*updated=*/true));
   }
   prefetch_next_pass(c);
   return mailbox_poll(c, p, t);
@@ -4367,17 +4421,15 @@ static int mstep_deliver(evoamd_ctx *c, const MstepPlan &p, double *tail_out, do
   memcpy(tail_out, h, 8 * sizeof(double));
   memcpy(dpar_out, h + 8, DP_COUNT * sizeof(double));
   memcpy(c->h_dpar, h + 8, DP_COUNT * sizeof(double));
-  int r = mailbox_errors(c);
-  if (r) return r;
-  note_levels(c, c->h_dpar);
-  c->h_theta_fresh = p.learn != 0 && !p.theta_home && c->h_dpar[DP_STATUS] == 0.0;
+  TRY(mailbox_errors(c));
+  made_level_hints(c, c->h_dpar);
+  made_theta_mailbox(c, p.learn != 0 && !p.theta_home && c->h_dpar[DP_STATUS] == 0.0);
   if (c->h_dpar[DP_STATUS] == 0.0) return 0;
   dpar_out[DP_STATUS] = c->h_dpar[DP_STATUS];  // 1 singular, 2 non-finite: the caller may finish the step on the host
   HIP_TRY(hipMemsetAsync(c->dpar + DP_STATUS, 0, sizeof(double), c->stream));
   // derive_from_theta and the prefetched pass behind the mailbox ran with the failed update's Theta: drop the pass and
   // the clamp flags it may have raised (the caller re-installs a Theta before anything else is evaluated)
-  c->prefetch_gen = ~0ull;
-  c->have_params = false;
+  on_theta_update_failed(c);
   HIP_TRY(hipMemsetAsync(c->flags, 0, (size_t)3 * c->N * sizeof(unsigned), c->stream));
   HIP_TRY(hipMemsetAsync(c->err, 0, 2 * sizeof(int), c->stream));
   return fail(EVOAMD_E_SINGULAR, "device Theta update: %s",
@@ -4389,19 +4441,15 @@ extern "C" int evoamd_mstep_device(evoamd_ctx *c, int learn_mask, double *tail_o
   REQUIRE(tail_out && dpar_out, "NULL output");
   REQUIRE(!(c && c->mask_infr && c->rel_frac < 0.0), "incomplete data: evoamd_set_reliable_fraction first (bsc.py:113-118)");
   const MstepPlan p = mstep_plan(c, learn_mask, /*spd_retry=*/false);
-  c->theta_bak_valid = false;
-  int r = mstep_backup(c, p);
-  if (r) return r;
-  r = stats_compute(c, /*fork_gemm=*/true);
-  if (r) return r;
-  c->h_theta_fresh = false;
+  drop_theta_backup(c);
+  TRY(mstep_backup(c, p));
+  TRY(stats_compute(c, /*fork_gemm=*/true));
+  made_theta_mailbox(c, false);
   if (p.want_rec && !c->yhat_valid) {  // under the Theta the E-step used, i.e. before the update
-    r = compute_reconstruction(c);     // (incomplete data: the statistics pass formed it already)
-    if (r) return r;
+    TRY(compute_reconstruction(c));     // (incomplete data: the statistics pass formed it already)
   }
   if (p.backup == BACKUP_SIDE_KERNEL) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_bak, 0));
-  r = mstep_attempt(c, p);
-  if (r) return r;
+  TRY(mstep_attempt(c, p));
   if (p.learn && c->h_theta[8 + 8 + DP_STATUS] == 3.0) {
     // the SPD block elimination met a non-positive pivot: repeat the Theta update with partial
     // pivoting.  The statistics are still in acc; ljc moves back so that the update kernels shift
@@ -4409,8 +4457,7 @@ extern "C" int evoamd_mstep_device(evoamd_ctx *c, int learn_mask, double *tail_o
     c->spd_fallbacks++;
     HIP_TRY(hipMemsetAsync(c->dpar + DP_STATUS, 0, sizeof(double), c->stream));
     HIP_TRY(hipMemcpyAsync(c->dpar + DP_LJC, c->dpar + DP_LJC_PREV, sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    r = mstep_attempt(c, mstep_plan(c, learn_mask, /*spd_retry=*/true));
-    if (r) return r;
+    TRY(mstep_attempt(c, mstep_plan(c, learn_mask, /*spd_retry=*/true)));
   }
   return mstep_deliver(c, p, tail_out, dpar_out);
 }
@@ -4576,14 +4623,9 @@ extern "C" int evoamd_loglik_exact(evoamd_ctx *c, int background, int chunk_stat
   const int cmax = (u64)C < total ? (int)C : (int)total;  // states of the largest chunk (Hv < 6: one partial chunk)
   HIP_TRY(hipSetDevice(c->device));
   TRY(c->tmp_states.ensure(c, (size_t)cmax * c->HW));
-  int r = c->tmp_lpj.ensure(c, (size_t)N * cmax);
-  if (r) return r;
-  r = ensure_B(c);
-  if (r) return r;
-  if (c->model == EVOAMD_MODEL_SSSC) {
-    r = ensure_lists(c, N * cmax);
-    if (r) return r;
-  }
+  TRY(c->tmp_lpj.ensure(c, (size_t)N * cmax));
+  TRY(ensure_B(c));
+  if (c->model == EVOAMD_MODEL_SSSC) TRY(ensure_lists(c, N * cmax));
   // m (N) | z (N) | ll (N) | Fs (1) | partial (ceil(N / 4)) | a (N x Hv) | marg (N x H)
   const unsigned nb = cdiv(N, 4);
   const size_t need = (size_t)3 * N + 1 + nb + (size_t)N * Hv + (size_t)N * H;
@@ -4609,8 +4651,7 @@ extern "C" int evoamd_loglik_exact(evoamd_ctx *c, int background, int chunk_stat
     }
     Batch b = {c->tmp_states, nullptr, c->Y, c->Bm, c->yy, N, cnt, 1, c->tmp_lpj, cnt, 0, flags, KID_MISC, 2};
     b.mask = c->mask_infr;
-    r = launch_lpj(c, b, lv);
-    if (r) return r;
+    TRY(launch_lpj(c, b, lv));
     SpanGuard g(c, KID_MISC);
     if (marg_out)
       exact_fold_kernel<true><<<nb, 256, 0, c->stream>>>(c->tmp_lpj, cnt, N, g0, cnt, logC, Hv, !background, run_m, run_z, run_a);
@@ -4644,8 +4685,7 @@ extern "C" int evoamd_patches_extract(evoamd_ctx *c, const double *img, int H, i
   HIP_TRY(hipSetDevice(c->device));
   const size_t img_n = (size_t)H * W * C, y_n = (size_t)g.N * g.D;
   TRY(c->patch_img.ensure(c, img_n));
-  int r = c->patch_Y.ensure(c, y_n);
-  if (r) return r;
+  TRY(c->patch_Y.ensure(c, y_n));
   HIP_TRY(hipMemcpyAsync(c->patch_img, img, img_n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   {
     SpanGuard sg(c, KID_PATCHES);
@@ -4700,8 +4740,7 @@ extern "C" int evoamd_patches_merge(evoamd_ctx *c, const double *Y, int H, int W
   HIP_TRY(hipSetDevice(c->device));
   const size_t img_n = (size_t)H * W * C, y_n = (size_t)g.N * g.D;
   TRY(c->patch_img.ensure(c, img_n));
-  int r = c->patch_Y.ensure(c, y_n);
-  if (r) return r;
+  TRY(c->patch_Y.ensure(c, y_n));
   HIP_TRY(hipMemcpyAsync(c->patch_Y, Y, y_n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   return launch_patches_merge(c, PatchRows{c->patch_Y}, g, method, img_out);
 }
@@ -4714,8 +4753,7 @@ extern "C" int evoamd_patches_merge_weighted(evoamd_ctx *c, const double *Y, con
   HIP_TRY(hipSetDevice(c->device));
   const size_t img_n = (size_t)H * W * C, y_n = (size_t)g.N * g.D;
   TRY(c->patch_img.ensure(c, img_n));
-  int r = c->patch_Y.ensure(c, y_n);
-  if (r) return r;
+  TRY(c->patch_Y.ensure(c, y_n));
   TRY(c->patch_V.ensure(c, y_n));
   HIP_TRY(hipMemcpyAsync(c->patch_Y, Y, y_n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->patch_V, V, y_n * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -4738,33 +4776,31 @@ extern "C" int evoamd_reconstruct_resident(evoamd_ctx *c, const uint8_t *x) {
   REQUIRE(c && c->configured && c->have_data && c->have_params, "evoamd_reconstruct_resident: configure, upload data and set parameters first");
   REQUIRE(!c->f32, "reconstruction is not available in the float32 mode");
   HIP_TRY(hipSetDevice(c->device));
-  c->rec_resident = false;
+  drop_resident_rec(c);
+  bool uses_keep = false;
   if (!c->yhat_valid) {
     REQUIRE(c->stats_rows_valid, "evoamd_reconstruct_resident: call evoamd_stats first (and before setting new parameters)");
-    int r = compute_reconstruction(c);
-    if (r) return r;
+    TRY(compute_reconstruction(c));
   }
   if (c->mask_infr) {  // incomplete data: the masks are resident, x is not read
     if (!c->yrec_from_pass) {  // the pass ran without reconstruct_in_stats (its M-step read an older y_reconstructed)
       select_rec_kernel<<<cdiv(c->N, 4), 256, 0, c->stream>>>(c->Y, c->ldY, c->mask_x, c->mask_infr, c->yhat, c->N, c->D, c->Yrec);
       HIP_TRY(hipGetLastError());
-      c->yrec_valid = c->yrec_from_pass = true;
+      made_yrec_from_pass(c, /*in_stats=*/false);
     }
-    c->rec_uses_keep = false;
   } else if (x == EVOAMD_KEEP_RESIDENT) {
     REQUIRE(c->keep_x_valid, "evoamd_reconstruct_resident: EVOAMD_KEEP_RESIDENT, but no keep-mask was uploaded for this geometry");
-    c->rec_uses_keep = true;
+    uses_keep = true;
   } else if (x) {
     const size_t nd = (size_t)c->N * c->D;
     if (!c->keep_x) TRY(c->keep_x.alloc(nd));
-    c->keep_x_valid = false;
+    on_keep_mask(c, /*uploaded=*/false);
     HIP_TRY(hipMemcpyAsync(c->keep_x, x, nd, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));  // x is pageable host memory of the caller
-    c->keep_x_valid = c->rec_uses_keep = true;
-  } else {
-    c->rec_uses_keep = false;
+    on_keep_mask(c, /*uploaded=*/true);
+    uses_keep = true;
   }
-  c->rec_resident = true;
+  made_resident_rec(c, uses_keep);
   return 0;
 }
 
@@ -4803,13 +4839,11 @@ extern "C" int evoamd_patches_merge_resident(evoamd_ctx *c, int H, int W, int C,
   const size_t img_n = (size_t)H * W * C, y_n = (size_t)g.N * g.D;
   const PatchSelect sel = resident_select(c);
   if (c->merge_select_fused) {
-    int r = c->patch_img.ensure(c, img_n);
-    if (r) return r;
+    TRY(c->patch_img.ensure(c, img_n));
     return launch_patches_merge(c, sel, g, method, img_out);
   }
   TRY(c->patch_img.ensure(c, img_n));
-  int r = c->patch_Y.ensure(c, y_n);  // select-then-merge (default): y_rec as dense rows, then the kernels of evoamd_patches_merge
-  if (r) return r;
+  TRY(c->patch_Y.ensure(c, y_n));  // select-then-merge (default): y_rec as dense rows, then the kernels of evoamd_patches_merge
   {
     SpanGuard sg(c, KID_PATCHES);
     const i64 blocks = (i64)((y_n + 255) / 256);
@@ -4833,8 +4867,7 @@ static int codes_preamble(evoamd_ctx *c, const char *who) {
 
 extern "C" int evoamd_posterior_codes(evoamd_ctx *c, int max_active, double p_min, int32_t *idx, double *p, double *m,
                                       int32_t *nnz, int32_t *map_slot, double *map_q, uint8_t *map_state_packed) {
-  int r = codes_preamble(c, "evoamd_posterior_codes");
-  if (r) return r;
+  TRY(codes_preamble(c, "evoamd_posterior_codes"));
   REQUIRE(max_active >= 1 && max_active <= CODES_MAX_A, "evoamd_posterior_codes: max_active must be in [1, 64]");
   REQUIRE(p_min >= 0.0, "evoamd_posterior_codes: p_min must be >= 0 (and not NaN)");
   const bool sssc = c->model == EVOAMD_MODEL_SSSC;
@@ -4889,8 +4922,7 @@ extern "C" int evoamd_posterior_codes(evoamd_ctx *c, int max_active, double p_mi
 
 // The dense rows the codes are cut from: Es (N x H) and, ES3C, Ez (N x H) of the last statistics pass.
 extern "C" int evoamd_download_posterior(evoamd_ctx *c, double *Es, double *Ez) {
-  int r = codes_preamble(c, "evoamd_download_posterior");
-  if (r) return r;
+  TRY(codes_preamble(c, "evoamd_download_posterior"));
   const bool sssc = c->model == EVOAMD_MODEL_SSSC;
   REQUIRE(sssc || !Ez, "evoamd_download_posterior: EBSC has no E_q[s z] (Ez must be NULL)");
   const size_t w = (size_t)c->H * sizeof(double);
@@ -4932,11 +4964,8 @@ extern "C" int evoamd_predictive_moments(evoamd_ctx *c, int add_noise, int64_t c
   const bool sssc = c->model == EVOAMD_MODEL_SSSC;
   const i64 N = c->N;
   const int D = c->D, H = c->H;
-  c->pred_N = 0;
-  if (sssc) {
-    int r = ensure_B(c);
-    if (r) return r;
-  }
+  made_predictive(c, 0);
+  if (sssc) TRY(ensure_B(c));
   const size_t nd = (size_t)N * D;
   TRY(c->pred_buf.ensure(c, 2 * nd));
   TRY(c->pred_Wt.ensure(c, (size_t)H * D));
@@ -4988,7 +5017,7 @@ extern "C" int evoamd_predictive_moments(evoamd_ctx *c, int add_noise, int64_t c
     counters[0] += st == PRED_SINGULAR;
     counters[1] += st == PRED_SKIPPED;
   }
-  c->pred_N = N;
+  made_predictive(c, N);
   c->pred_D = D;
   return 0;
 }
@@ -5027,7 +5056,7 @@ extern "C" int evoamd_generate(evoamd_ctx *c, int model, int64_t N, int D, int H
   const int HW = (H + 63) / 64;
   const size_t nd = (size_t)N * D, nh = (size_t)N * H, nw = (size_t)N * HW;
   const size_t par_n = (size_t)H * D + H + (sssc ? (size_t)H + (size_t)H * H : 0);
-  c->gen_keep = -1;  // until this call has completed
+  made_generated(c, -1);  // until this call has completed
   TRY(c->gen_par.ensure(c, par_n));
   TRY(c->gen_y.ensure(c, nd));
   if (keep & EVOAMD_GEN_KEEP_S) TRY(c->gen_s.ensure(c, nw));
@@ -5073,7 +5102,7 @@ extern "C" int evoamd_generate(evoamd_ctx *c, int model, int64_t N, int D, int H
   c->gen_N = N;
   c->gen_D = D;
   c->gen_H = H;
-  c->gen_keep = keep;
+  made_generated(c, keep);
   return 0;
 }
 
@@ -5109,8 +5138,7 @@ extern "C" int evoamd_download_generated(evoamd_ctx *c, int what, void *out) {
 // RCCL
 // ---------------------------------------------------------------------------------------
 extern "C" int evoamd_comm_unique_id(uint8_t id_out[128]) {
-  int r = rccl_load();
-  if (r) return r;
+  TRY(rccl_load());
   RcclId id;
   RCCL_TRY(g_rccl.GetUniqueId(&id));
   memcpy(id_out, id.internal, 128);
@@ -5120,8 +5148,7 @@ extern "C" int evoamd_comm_unique_id(uint8_t id_out[128]) {
 extern "C" int evoamd_comm_init(evoamd_ctx *c, const uint8_t id_in[128], int rank, int world) {
   REQUIRE(c, "ctx is NULL");
   REQUIRE(world >= 1 && rank >= 0 && rank < world, "bad rank / world");
-  int r = rccl_load();
-  if (r) return r;
+  TRY(rccl_load());
   HIP_TRY(hipSetDevice(c->device));
   RcclId id;
   memcpy(id.internal, id_in, 128);
@@ -5163,10 +5190,7 @@ extern "C" int evoamd_comm_destroy(evoamd_ctx *c) {
 // ---------------------------------------------------------------------------------------
 extern "C" int evoamd_timing_enable(evoamd_ctx *c, int on) {
   REQUIRE(c, "ctx is NULL");
-  if (!on && c->timing) {
-    int r = resolve_spans(c);
-    if (r) return r;
-  }
+  if (!on && c->timing) TRY(resolve_spans(c));
   c->timing = on != 0;
   c->timing_mask = (unsigned)on;  // bit k = kernel class k; 1-bits beyond EVOAMD_K_COUNT are harmless
   return 0;
@@ -5174,8 +5198,7 @@ extern "C" int evoamd_timing_enable(evoamd_ctx *c, int on) {
 
 extern "C" int evoamd_timing_reset(evoamd_ctx *c) {
   REQUIRE(c, "ctx is NULL");
-  int r = resolve_spans(c);
-  if (r) return r;
+  TRY(resolve_spans(c));
   for (int i = 0; i < KID_COUNT; i++) {
     c->t_ms[i] = 0;
     c->t_n[i] = 0;
@@ -5185,8 +5208,7 @@ extern "C" int evoamd_timing_reset(evoamd_ctx *c) {
 
 extern "C" int evoamd_kernel_time_ms(evoamd_ctx *c, int kid, double *avg_ms, int64_t *launches) {
   REQUIRE(c && kid >= 0 && kid < KID_COUNT, "bad kernel id");
-  int r = resolve_spans(c);
-  if (r) return r;
+  TRY(resolve_spans(c));
   if (avg_ms) *avg_ms = c->t_n[kid] ? c->t_ms[kid] / (double)c->t_n[kid] : 0.0;
   if (launches) *launches = c->t_n[kid];
   return 0;

@@ -62,6 +62,15 @@ class Engine:
     def synchronize(self):
         check(self.lib.evoamd_synchronize(self._h))
 
+    def debug_validity(self):
+        """The host-side validity state of the context (evoamd_debug_validity): {flag name: bool} for the bits of
+        _lib.VALIDITY_BITS and {name: int} for _lib.VALIDITY_WORDS.  No device work."""
+        out = (ctypes.c_int64 * 8)()
+        check(self.lib.evoamd_debug_validity(self._h, out))
+        d = {name: bool((out[0] >> i) & 1) for i, name in enumerate(_lib.VALIDITY_BITS)}
+        d.update(zip(_lib.VALIDITY_WORDS, (int(v) for v in out[1:])))
+        return d
+
     def set_option(self, name, value):
         check(self.lib.evoamd_set_option(self._h, name.encode(), int(value)))
 

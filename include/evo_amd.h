@@ -66,6 +66,23 @@ int evoamd_synchronize(evoamd_ctx *ctx);
 /* Debug aid: process-wide counts of live device (out[0]) and pinned host (out[1]) allocations of the library.  Equal
  * before a context is created and after it is destroyed: no buffer outlives its context. */
 int evoamd_debug_live_buffers(int64_t out[2]);
+/* Debug aid: the host-side validity state of a context (DESIGN: what a change invalidates).  out[0] = the boolean fields
+ * at the bit positions below, then gen, kn_gen, theta_gen, pending_skip, census_skip, kn_refill, pred_N.  Reads host
+ * fields only: no HIP call, no synchronisation. */
+enum {
+  EVOAMD_VB_HAVE_DATA = 0, EVOAMD_VB_HAVE_PARAMS = 1, EVOAMD_VB_HAVE_CAND = 2, EVOAMD_VB_B_VALID = 3,
+  EVOAMD_VB_ROWS_FRESH = 4, EVOAMD_VB_STATS_ROWS_VALID = 5, EVOAMD_VB_YHAT_VALID = 6, EVOAMD_VB_REC_RESIDENT = 7,
+  EVOAMD_VB_YREC_VALID = 8, EVOAMD_VB_YREC_FROM_PASS = 9, EVOAMD_VB_REC_IN_STATS = 10, EVOAMD_VB_KEEP_X_VALID = 11,
+  EVOAMD_VB_REC_USES_KEEP = 12, EVOAMD_VB_NEED_KNOWN = 13, EVOAMD_VB_RES_NEED0 = 14, EVOAMD_VB_RES_NEED1 = 15,
+  EVOAMD_VB_RES_NEED2 = 16, EVOAMD_VB_CAND_FROM_DEVICE = 17, EVOAMD_VB_LISTS_CLEAN = 18, EVOAMD_VB_CLIST_CLEAN = 19,
+  EVOAMD_VB_ACC_CLEAN = 20, EVOAMD_VB_WQ_COPY_VALID = 21, EVOAMD_VB_H_THETA_FRESH = 22, EVOAMD_VB_THETA_BAK_VALID = 23,
+  EVOAMD_VB_KN_LOST = 24, EVOAMD_VB_LAST_ESTEP_FUSED = 25, EVOAMD_VB_REDUCE_PENDING = 26, EVOAMD_VB_BINS_DIRTY = 27,
+  EVOAMD_VB_GEN_KEPT = 28,          /* gen_keep >= 0: an evoamd_generate call has completed */
+  EVOAMD_VB_PREFETCH_CURRENT = 29,  /* prefetch_gen == gen */
+  EVOAMD_VB_CENSUS_CURRENT = 30,    /* census_gen == kn_gen */
+  EVOAMD_VB_ROWS_KN_CURRENT = 31    /* rows_kn_gen == kn_gen */
+};
+int evoamd_debug_validity(evoamd_ctx *ctx, int64_t out[8]);
 /* Options: "ebsc_f32" (0/1, default 0; read by the next evoamd_configure of an EBSC geometry): float32 mode -- the data,
  * B = Y W and the per-datapoint E_q[s] rows are stored in float and the two long contractions (B = Y W, Wp = Es^T Y) run
  * on v_mfma_f32_16x16x4_f32; lpj arithmetic, selection, every accumulator and Theta stay float64 (the reference has no

@@ -6,7 +6,7 @@ cand_lpj), with the awkward inputs of vary_kn_kernel planted on purpose (duplica
 "with data" also carry Y and a well-conditioned Theta; their lpj values come from the float64 oracle in the GPU module.
 
 Restated from the source, so that a test can say which kernel instantiation or route a case reaches: the SPL / CPL ladder
-of evoamd_vary_kn, the eligibility rule of bsc_lpj_gram2_kernel, the digest layout of common.hpp, the LDS plan of the
+of with_spl / with_cpl, the eligibility rule of bsc_lpj_gram2_kernel, the digest layout of common.hpp, the LDS plan of the
 fused E-step, and the documented selection rule of vary_kn_kernel (ties included)."""
 import os
 
@@ -22,7 +22,7 @@ DIG_SLOTS = 4
 # kernels_common.hpp
 VK_MAX_S_PER_LANE = 16
 VK_MAX_C_PER_LANE = 4
-# evo_amd.hip (launch_bsc_lpj): LDS of the gram2 kernel's B rows; (launch_estep_fused): LDS limit of one workgroup
+# evo_amd.hip (launch_bsc_lpj): LDS of the gram2 kernel's B rows; (FUSED_LDS_MAX): LDS limit of one workgroup of the fused kernel
 GRAM2_LDS_MAX = 40 * 1024
 FUSED_LDS_MAX = 150 * 1024
 SSSC_KCAP = 64
@@ -30,7 +30,7 @@ SSSC_KCAP = 64
 
 # ---- restatements --------------------------------------------------------------------------------------------------
 def vk_instantiation(S, Cmax):
-    """evoamd_vary_kn: the <SPL, CPL> of vary_kn_kernel that a geometry launches."""
+    """with_spl / with_cpl: the <SPL, CPL> of vary_kn_kernel that a geometry launches."""
     spl = 1 if S <= 64 else 2 if S <= 128 else 4 if S <= 256 else 8 if S <= 512 else 16
     return spl, (1 if Cmax <= 64 else 4)
 
@@ -70,7 +70,7 @@ def fused_lds_wave_bytes(SPL, kc_big):
 
 
 def fused_launch_plan(S, H):
-    """launch_estep_fused: per stage (waves per workgroup, kc_big, LDS bytes, halvings of W, kc_big shrinks)."""
+    """estep_plan: per stage (waves per workgroup, kc_big, LDS bytes, halvings of W, kc_big shrinks)."""
     SPL = vk_instantiation(S, 1)[0]
     tab = 4 * H * 8
     out = []
@@ -488,6 +488,16 @@ FUSED = {
     "fused_s513": (7, 12, 64, 513, 8, 8, 513, False, 504),
     "fused_s1024": (7, 12, 64, 1024, 16, 4, 64, False, 505),
     "fused_s1024_dense": (7, 12, 64, 1024, 64, 1, 64, True, 506),
+}
+# every S class of with_spl (S <= 64, 65-128, 129-256, 257-512, 513-1024) through the randflip kernel, the selection and
+# the fused kernel (ES3C, at most 64 children): (N, D, H, S, parents, children, Mprime, seed).  H = 12 gives enough
+# distinct states for S = 520; a wrong template argument in the dispatch shows at these sizes, larger ones add nothing
+SPL_FLOW = {
+    "spl_s4": (8, 6, 12, 4, 2, 2, 4, 601),
+    "spl_s72": (8, 6, 12, 72, 4, 4, 24, 602),
+    "spl_s136": (8, 6, 12, 136, 8, 4, 136, 603),
+    "spl_s264": (8, 6, 12, 264, 8, 8, 88, 604),
+    "spl_s520": (8, 6, 12, 520, 8, 8, 173, 605),
 }
 
 

@@ -152,24 +152,36 @@ def test_tie_cases_tell_the_rule_from_its_wrong_variants(problems):
 
 
 def test_vary_kn_ladder_matches_the_source():
+    """with_spl / with_cpl are the one place that maps S and Cmax to the <SPL, CPL> of vary_kn_kernel; the selection,
+    the randflip and the fused launch and the fused plan all go through them."""
     hip = _src("evo_amd.hip")
-    body = hip[hip.index('extern "C" int evoamd_vary_kn('):]
-    body = body[:body.index("\n}\n")]
-    assert "const bool c1 = c->Cmax <= 64;" in body
-    rows = re.findall(r"if \(c->S <= (\d+)\) \{ if \(c1\) VK_LAUNCH\((\d+), (\d+)\); else VK_LAUNCH\((\d+), (\d+)\); \}",
-                      body)
-    last = re.search(r"else \{ if \(c1\) VK_LAUNCH\((\d+), (\d+)\); else VK_LAUNCH\((\d+), (\d+)\); \}", body)
-    assert len(rows) == 4 and last, rows
-    for lim, s1, c1, s4, c4 in rows:
-        lim = int(lim)
-        assert ep.vk_instantiation(lim, 64) == (int(s1), int(c1)) and ep.vk_instantiation(lim, 65) == (int(s4), int(c4))
-        assert ep.vk_instantiation(lim + 1, 1)[0] > int(s1)
-    assert ep.vk_instantiation(1024, 64) == (int(last.group(1)), int(last.group(2)))
-    assert ep.vk_instantiation(513, 256) == (int(last.group(3)), int(last.group(4)))
+
+    def ladder(name, arg):
+        body = hip[hip.index("static void %s(int %s, F &&f) {" % (name, arg)):]
+        body = body[:body.index("\n}\n")]
+        rows = re.findall(r"if \(%s <= (\d+)\) f\(std::integral_constant<int, (\d+)>\{\}\);" % arg, body)
+        last = re.search(r"\n  else f\(std::integral_constant<int, (\d+)>\{\}\);", body)
+        assert last and body.count("integral_constant") == len(rows) + 1, body
+        return [(int(lim), int(v)) for lim, v in rows], int(last.group(1))
+
+    s_rows, s_last = ladder("with_spl", "S")
+    c_rows, c_last = ladder("with_cpl", "Cmax")
+    assert len(s_rows) == 4 and c_rows == [(64, 1)], (s_rows, c_rows)
+    for lim, spl in s_rows:
+        assert ep.vk_instantiation(lim, 64) == (spl, 1) and ep.vk_instantiation(lim, 65) == (spl, c_last)
+        assert ep.vk_instantiation(lim + 1, 1)[0] > spl
+    assert ep.vk_instantiation(1024, 64) == (s_last, 1)
+    assert ep.vk_instantiation(513, 256) == (s_last, c_last)
     kc = _src("kernels_common.hpp")
     assert _define(kc, "VK_MAX_S_PER_LANE") == ep.VK_MAX_S_PER_LANE and _define(kc, "VK_MAX_C_PER_LANE") == ep.VK_MAX_C_PER_LANE
+    # nobody maps S or Cmax on the side: every launch of the three kernels takes its template arguments from them
+    assert "vary_kn_kernel<decltype(spl)::value, decltype(cpl)::value><<<" in hip
+    assert "evolve_randflip_kernel<decltype(spl)::value><<<" in hip
+    assert hip.count("sssc_estep_fused_kernel<decltype(spl)::value, ") == 2 == len(re.findall(r"sssc_estep_fused_kernel<[^>]*><<<", hip))
+    assert hip.count("vary_kn_kernel<") == 1 == hip.count("evolve_randflip_kernel<")
     # the fused E-step sizes its rows with the same ladder
-    assert "const int SPL = c->S <= 64 ? 1 : (c->S <= 128 ? 2 : (c->S <= 256 ? 4 : (c->S <= 512 ? 8 : 16)));" in hip
+    assert "with_spl(c->S, [&](auto spl) { p.spl = decltype(spl)::value; });" in hip
+    assert "st.lds_wave_bytes = fused_lds_wave_bytes(p.spl, st.kc_big);" in hip
 
 
 def test_gram2_rule_matches_the_source():
@@ -203,18 +215,20 @@ def test_digest_layout_matches_the_source():
 
 
 def test_fused_plan_matches_the_source_and_never_halves():
-    """launch_estep_fused restated: at every S <= 1024 and every H the fused E-step admits, neither the halving of W nor
+    """estep_plan restated: at every S <= 1024 and every H the fused E-step admits, neither the halving of W nor
     the kc_big shrink of the second launch fires and the REQUIRE on the LDS cannot refuse.  At S = 1024 the second
     launch (kc_big = 64) sits 64 bytes under the limit -- the case test_gpu_estep_paths runs."""
     hip = _src("evo_amd.hip")
     for line in ("const size_t tab = (size_t)4 * c->H * sizeof(double);",
-                 "int W = stage == 0 ? 4 : 1;",
-                 "f.kc_big = stage == 0 ? 16 : SSSC_KCAP;",
-                 "auto lds_of = [&](int w) { return (f.stage_d1 ? tab : 0) + (size_t)w * f.lds_wave_bytes; };",
-                 "while (stage == 1 && lds_of(1) > 150 * 1024 && f.kc_big > 16) {",
-                 "while (W > 1 && lds_of(W) > 150 * 1024) W >>= 1;",
-                 'REQUIRE(lds <= 150 * 1024, "fused E-step: S too large for the LDS rows");'):
+                 "st.W = stage == 0 ? 4 : 1;",
+                 "st.kc_big = stage == 0 ? 16 : SSSC_KCAP;",
+                 "auto lds_of = [&](int w) { return (stage == 0 ? tab : 0) + (size_t)w * st.lds_wave_bytes; };",
+                 "while (stage == 1 && lds_of(1) > FUSED_LDS_MAX && st.kc_big > 16) {",
+                 "while (st.W > 1 && lds_of(st.W) > FUSED_LDS_MAX) st.W >>= 1;",
+                 'REQUIRE(st.lds <= FUSED_LDS_MAX, "fused E-step: S too large for the LDS rows");',
+                 "f.stage_d1 = stage == 0;"):
         assert line in hip, line
+    assert "#define FUSED_LDS_MAX (150 * 1024)" in hip and ep.FUSED_LDS_MAX == 150 * 1024
     kf = _src("kernels_fused.hpp")
     body = kf[kf.index("inline int fused_lds_wave_bytes("):]
     body = body[:body.index("\n}\n")]
@@ -273,6 +287,10 @@ def test_device_flow_and_fused_cases_fit_the_operators():
         assert ((1024 // S + 2) * H + (4 * H if H <= 512 else 0)) * 8 <= 48 * 1024, name
     assert {v[3] for v in ep.FUSED.values()} >= {65, 257, 513, 1024}
     assert any(v[7] for v in ep.FUSED.values())
+    for name, (N, D, H, S, npar, nch, Mp, seed) in ep.SPL_FLOW.items():
+        assert H % 2 == 0 and npar * nch <= 64 and npar <= min(S, 64) and nch <= 8 and 1 <= Mp <= S, name
+        assert ((1024 // S + 2) * H + 4 * H) * 8 <= 48 * 1024, name
+    assert sorted(ep.vk_instantiation(v[3], v[4] * v[5]) for v in ep.SPL_FLOW.values()) == [(s, 1) for s in (1, 2, 4, 8, 16)]
     hip = _src("evo_amd.hip")
     assert "#define MAIN_LPJ_LDS_MAX (48 * 1024)" in hip
     assert "((size_t)(1024 / c->S + 2) * c->H + (c->H <= 512 ? (size_t)4 * c->H : 0)) * sizeof(double) <= MAIN_LPJ_LDS_MAX;" in hip

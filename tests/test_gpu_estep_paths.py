@@ -2,7 +2,8 @@
 instantiations with digest and word de-duplication and S_perm 0 / 1 (bit for bit against oracle.vary_Kn), its tie rule,
 the row statistics it leaves for the next statistics pass, the candidate lpj kernels (EBSC Gram / gram2 / direct, the
 ES3C chain levels), the device flow (evolve_randflip -> vary_kn with more than 64 children) and the fused E-step against
-the separate passes at S up to 1024.  Problems are synthetic (_estep_problems.py)."""
+the separate passes at S up to 1024, and every S class of the launch dispatch (with_spl) through the randflip kernel, the
+selection and the fused kernel.  Problems are synthetic (_estep_problems.py)."""
 import functools
 
 import numpy as np
@@ -289,3 +290,50 @@ def test_fused_estep_matches_separate_passes(engine, name):
         assert float(va[k]) == float(vb[k]), (name, k, float(va[k]), float(vb[k]))
     scale = max(1.0, float(np.abs(off[5]).max()))
     assert np.abs(on[5] - off[5]).max() <= 1e-12 * scale, name
+
+
+@pytest.mark.parametrize("name", list(ep.SPL_FLOW))
+def test_every_s_class_through_randflip_selection_and_fused(engine, name):
+    """with_spl, one case per S class (ES3C, at most 64 children): evolve_randflip -> vary_kn against oracle.vary_Kn run on
+    the device's own lpj values, K^n, lpj and the counters bit for bit; then the fused E-step from the same K^n and seed
+    must give that K^n and lpj row bit for bit as well."""
+    from oracle import evo_oracle as orc
+    N, D, H, S, npar, nch, Mp, seed = ep.SPL_FLOW[name]
+    rng = np.random.RandomState(seed)
+    p = {"name": name, "model": "sssc", "N": N, "D": D, "H": H, "S": S, "S_perm": 0, "Cmax": npar * nch,
+         "Y": rng.normal(size=(N, D)), "theta": ep.es3c_theta(rng, D, H), "ss": ep.make_kn(rng, N, S, H)}
+    _configure(engine, p, 1)
+    engine.set_option("merge_small_levels", 0)  # (one arithmetic per state in both runs, as in the test above)
+    try:
+        engine.upload_states(p["ss"])
+        engine.lpj_resident()
+        engine.stats()  # (the same prefix as _fused_run)
+        lpj0 = engine.download_lpj()
+        engine.evolve_randflip(npar, nch, seed)
+        cand, counts, cl = engine.download_candidates()
+        p.update(cand=cand, counts=counts)
+        _assert_tie_free(p, lpj0, cl, name)
+        want_ss, want_lpj = p["ss"].copy(), lpj0.copy()
+        nu = ns = 0
+        for n in range(N):
+            c = int(counts[n])
+            a, b = orc.vary_Kn(lpj0[n].copy(), cl[n, :c].copy(), want_lpj[n], want_ss[n], cand[n, :c], H, S, 0,
+                               np.zeros((0, H), dtype=bool), Mp)
+            nu += a
+            ns += b
+        engine.set_estep_counts(0.0, 0.0)
+        sums = engine.vary_kn(Mp)
+        got_ss, got_lpj = engine.download_states(), engine.download_lpj()
+        on = _fused_run(engine, p, 2, npar, nch, Mp, seed, True)
+    finally:
+        engine.set_option("fused_estep", 0)
+        engine.set_option("merge_small_levels", 1)
+    assert ns > 0, name
+    assert np.array_equal(got_ss, want_ss), "%s: K^n differs in datapoints %s" % (
+        name, np.flatnonzero((got_ss != want_ss).any(axis=(1, 2))))
+    assert np.array_equal(got_lpj, want_lpj), name
+    assert tuple(sums) == (float(nu), float(ns)), (name, sums, nu, ns)
+    assert on[0] is True, name + ": the fused kernel did not run"
+    assert np.array_equal(on[3], want_ss), "%s (fused): K^n differs in datapoints %s" % (
+        name, np.flatnonzero((on[3] != want_ss).any(axis=(1, 2))))
+    assert np.array_equal(on[4], want_lpj), name + " (fused)"

@@ -241,6 +241,39 @@ def test_every_option_is_documented():
         assert '"%s"' % n in integ, "INTEGRATION.md does not list option " + n
 
 
+def test_validity_fields_are_written_in_one_section():
+    """The flags and generation counters that say what is still valid (what a change invalidates) are
+    assigned, incremented or swapped only between the two markers of csrc/evo_amd.hip, where every change is a named
+    event; a flag added to a call site by hand fails here.  The E-step launches go through with_spl (no launch macro),
+    and the threshold of the in-kernel census is written once."""
+    src = open(os.path.join(ROOT, "evo_amd", "csrc", "evo_amd.hip")).read()
+    begin, end = "// ---- validity: begin\n", "// ---- validity: end\n"
+    assert src.count(begin) == 1 and src.count(end) == 1 and src.index(begin) < src.index(end)
+    outside = src[:src.index(begin)] + src[src.index(end):]
+    fields = (
+        "gen", "prefetch_gen", "kn_gen", "census_gen", "rows_kn_gen", "theta_gen",
+        "have_data", "have_params", "have_cand",
+        "B_valid", "rows_fresh", "stats_rows_valid", "yhat_valid",
+        "rec_resident", "yrec_valid", "yrec_from_pass", "rec_in_stats", "keep_x_valid", "rec_uses_keep",
+        "need_known", "res_need", "res_cnt",
+        "cand_from_device", "lists_clean", "pending_skip", "clist_clean", "census_skip", "acc_clean",
+        "wq_copy_valid", "h_theta_fresh", "theta_bak_valid",
+        "kn_lost", "kn_refill",
+        "last_estep_fused", "reduce_pending", "bins_dirty", "pred_N", "gen_keep")
+    name = r"\b(?:c|ctx)->(?:%s)\b(?:\[[^\]]*\])?" % "|".join(fields)  # (the fields stayed members of the context)
+    # (the issue's c->FIELD\s*(=[^=]|\+\+|--), and with it compound assignments, prefix forms and std::swap)
+    writes = re.compile(r"%s\s*(?:[-+*/|&^]?=[^=]|\+\+|--)|(?:\+\+|--)\s*%s|swap\([^)]*%s" % (name, name, name))
+    wrong = [line.strip() for line in outside.splitlines() if writes.search(line)]
+    assert not wrong, "\n".join(wrong)
+    inside = src[src.index(begin):src.index(end)]
+    for f in fields:  # ... and every one of them is written there: the list names real fields
+        assert re.search(r"c->%s\b" % f, inside), f
+    for gone in ("VK_LAUNCH", "EV_LAUNCH", "FUSED_LAUNCH"):
+        assert gone not in src, gone
+    assert src.count("4 << 20") == 1
+    assert "c->N * (i64)c->S < INKERNEL_CENSUS_BELOW" in src and src.count("INKERNEL_CENSUS_BELOW") == 2
+
+
 def test_product_path_has_no_cpu_fallback():
     """evo_amd must not import the oracle, and creating an engine without a GPU must raise."""
     import evo_amd
