@@ -19,6 +19,10 @@ MODEL_BSC, MODEL_SSSC = 0, 1
 GEN_KEEP = {"s": 1, "z": 2, "y_mean": 4}
 GEN_WHAT = {"y": 0, "s": 1, "z": 2, "y_mean": 3}
 
+# evoamd_posterior_sample: keep bits (EVOAMD_PSAMP_KEEP_*) and the output ids of evoamd_download_posterior_samples
+PSAMP_KEEP = {"slot": 1, "s": 2, "z": 4, "y": 8}
+PSAMP_WHAT = {"slot": 0, "s": 1, "z": 2, "y": 3}
+
 # evoamd_debug_validity: names of the bits of out[0] (EVOAMD_VB_*, in bit order) and of out[1..7]
 VALIDITY_BITS = (
     "have_data", "have_params", "have_cand", "B_valid", "rows_fresh", "stats_rows_valid", "yhat_valid", "rec_resident",
@@ -37,6 +41,13 @@ KERNEL_IDS = {
     "stats_k3_4": 16, "stats_k5_8": 17, "stats_k9plus": 18, "allreduce": 19, "estep_fused": 20,
     "patches": 21, "init_states": 22,
 }
+# classes outside the EM path, added after tests/test_gpu_validity.py recorded its launch census over KERNEL_IDS (which
+# therefore stays as it is); Engine.timing / Engine.kernel_time_ms take names of either table
+KERNEL_IDS_EXTRA = {"posterior_sample": 23}
+
+
+def kernel_id(name):
+    return KERNEL_IDS[name] if name in KERNEL_IDS else KERNEL_IDS_EXTRA[name]
 
 _c_dp = ctypes.POINTER(ctypes.c_double)
 _c_u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -104,6 +115,8 @@ SIGNATURES = {
     "evoamd_download_posterior": (_I, [_vp, _c_dp, _c_dp]),
     "evoamd_predictive_moments": (_I, [_vp, _I, ctypes.POINTER(_I64)]),
     "evoamd_download_predictive": (_I, [_vp, _c_dp, _c_dp]),
+    "evoamd_posterior_sample": (_I, [_vp, _I, _U64, _U64, _I, _I, _I, ctypes.POINTER(_I64)]),
+    "evoamd_download_posterior_samples": (_I, [_vp, _I, _vp]),
     "evoamd_generate": (_I, [_vp, _I, _I64, _I, _I, _U64, _U64, _c_dp, _c_dp, _c_dp, _c_dp, _DBL, _c_u64p, _I]),
     "evoamd_download_generated": (_I, [_vp, _I, _vp]),
     "evoamd_comm_unique_id": (_I, [_c_u8p]),

@@ -31,6 +31,7 @@
 #include "kernels_generate.hpp"
 #include "kernels_exact.hpp"
 #include "kernels_predictive.hpp"
+#include "kernels_posterior_sample.hpp"
 
 // ---------------------------------------------------------------------------------------
 // error handling
@@ -150,6 +151,7 @@ enum {  // internal kernel ids (see evoamd_kernel_name)
   KID_ESTEP_FUSED,  // the fused per-datapoint E-step kernel (lpj of K^n -> candidates -> their lpj -> vary_Kn -> census)
   KID_PATCHES,      // overlapping image patches: extract / mean merge / median merge kernels
   KID_INIT_STATES,  // evoamd_init_states: the K^n(0) sampler (or the table copy of the exact mode)
+  KID_POSTERIOR_SAMPLE,  // evoamd_posterior_sample: W^T and the sampling kernel (transfers excluded)
   KID_COUNT
 };
 
@@ -515,6 +517,14 @@ struct evoamd_ctx {
   DevBuf<int> pred_status;
   i64 pred_N = 0;
   int pred_D = 0;
+  // evoamd_posterior_sample (kernels_posterior_sample.hpp): the outputs of the last call and the status word per datapoint,
+  // grown on demand and released by evoamd_configure (never the EM state above; W^T goes through pred_Wt, rewritten by
+  // every call); ps_keep < 0: nothing to download
+  DevBuf<int> ps_slot, ps_status;
+  DevBuf<u64> ps_s;
+  DevBuf<double> ps_z, ps_y;
+  i64 ps_N = 0, ps_T = 0;
+  int ps_D = 0, ps_H = 0, ps_keep = -1;
   // evoamd_posterior_codes: the compact outputs on the device (one allocation, grown on demand); rows_kn_gen = the K^n
   // the rows of the last statistics pass were formed from; option "codes_path" (-1 automatic, else CODES_REG / _LDS / _GMEM)
   DevBuf<uint8_t> codes_buf;
@@ -728,6 +738,7 @@ static void on_keep_mask(evoamd_ctx *c, bool uploaded) { c->keep_x_valid = uploa
 static void made_resident_rec(evoamd_ctx *c, bool uses_keep) { c->rec_uses_keep = uses_keep, c->rec_resident = true; }
 static void made_predictive(evoamd_ctx *c, i64 N) { c->pred_N = N; }  // 0: nothing to download
 static void made_generated(evoamd_ctx *c, int keep) { c->gen_keep = keep; }  // -1: no call has completed
+static void made_posterior_samples(evoamd_ctx *c, int keep) { c->ps_keep = keep; }  // -1: nothing to download (no EM state reads it)
 // ---- validity: end
 
 struct SpanGuard {
@@ -840,6 +851,9 @@ static int set_kernel_lds_limits() {
     const void *pk[] = {(const void *)predictive_kernel<1, true>, (const void *)predictive_kernel<2, true>,
                         (const void *)predictive_kernel<4, true>, (const void *)predictive_kernel<8, true>};
     for (const void *f : pk) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    const void *sk[] = {(const void *)posterior_sample_kernel<1, true>, (const void *)posterior_sample_kernel<2, true>,
+                        (const void *)posterior_sample_kernel<4, true>, (const void *)posterior_sample_kernel<8, true>};
+    for (const void *f : sk) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   }
   {
     const void *wk[] = {(const void *)sssc_stats_wave_kernel<0, 4>,  (const void *)sssc_stats_wave_kernel<1, 4>,
@@ -1194,6 +1208,13 @@ static void configure_drop(evoamd_ctx *c) {
   c->tmpWt.reset();
   c->Wt.reset();
   c->init_scratch.reset();
+  // the posterior samples of the previous geometry
+  c->ps_slot.reset();
+  c->ps_status.reset();
+  c->ps_s.reset();
+  c->ps_z.reset();
+  c->ps_y.reset();
+  made_posterior_samples(c, -1);
   c->huge.reset();
   c->huge_ctl.reset();
   c->huge_slots = c->huge_kc = 0;
@@ -5036,6 +5057,153 @@ extern "C" int evoamd_download_predictive(evoamd_ctx *c, double *mean, double *v
 }
 
 // ---------------------------------------------------------------------------------------
+// posterior samples (kernels_posterior_sample.hpp): own buffers; of the EM state only B = Y W is (re)formed, like every lpj pass
+// ---------------------------------------------------------------------------------------
+template <bool SSSC>
+static void launch_posterior_sample(evoamd_ctx *c, const PsampArgs &q, int R, size_t lds) {
+  const unsigned grid = cdiv(q.p.N, PRED_WAVES);
+  switch (R) {
+    case 1: posterior_sample_kernel<1, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(q); break;
+    case 2: posterior_sample_kernel<2, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(q); break;
+    case 4: posterior_sample_kernel<4, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(q); break;
+    default: posterior_sample_kernel<8, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(q); break;
+  }
+}
+
+extern "C" int evoamd_posterior_sample(evoamd_ctx *c, int n_samples, uint64_t seed, uint64_t first_index, int keep_mask,
+                                       int fill_all, int add_noise, int64_t counters[4]) {
+  REQUIRE(c && c->configured && c->have_data && c->have_params,
+          "evoamd_posterior_sample: configure, upload data and set parameters first");
+  REQUIRE(!c->f32, "evoamd_posterior_sample is not available in the float32 mode");
+  REQUIRE_KN(c);
+  REQUIRE(counters, "evoamd_posterior_sample: counters is NULL");
+  REQUIRE(n_samples >= 1, "evoamd_posterior_sample: n_samples must be positive");
+  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
+  const int all = PSAMP_KEEP_SLOT | PSAMP_KEEP_S | PSAMP_KEEP_Z | PSAMP_KEEP_Y;
+  REQUIRE(keep_mask != 0 && (keep_mask & ~all) == 0, "evoamd_posterior_sample: keep_mask must name at least one of the outputs (bits 1, 2, 4, 8)");
+  REQUIRE(sssc || !(keep_mask & PSAMP_KEEP_Z), "evoamd_posterior_sample: z is an ES3C output (EBSC: z = s)");
+  if (c->D > 64 * PRED_R_MAX)
+    return fail(EVOAMD_E_INVALID, "evoamd_posterior_sample: D = %d, at most %d observables are supported (64 lanes x %d registers)",
+                c->D, 64 * PRED_R_MAX, PRED_R_MAX);
+  HIP_TRY(hipSetDevice(c->device));
+  const i64 N = c->N, T = n_samples;
+  const int D = c->D, H = c->H, HW = c->HW;
+  made_posterior_samples(c, -1);
+  // ---- do the outputs fit?  Decided before anything is released, allocated or launched.
+  const size_t nt = (size_t)N * (size_t)T;
+  {
+    size_t grow = 0, released = 0;
+    auto plan = [&](bool wanted, size_t have, size_t want, size_t elem) {
+      if (wanted && want > have) grow += want * elem, released += have * elem;
+    };
+    plan(keep_mask & PSAMP_KEEP_SLOT, c->ps_slot.size(), nt, sizeof(int));
+    plan(keep_mask & PSAMP_KEEP_S, c->ps_s.size(), nt * HW, sizeof(u64));
+    plan(keep_mask & PSAMP_KEEP_Z, c->ps_z.size(), nt * H, sizeof(double));
+    plan(keep_mask & PSAMP_KEEP_Y, c->ps_y.size(), nt * D, sizeof(double));
+    plan(true, c->ps_status.size(), (size_t)N, sizeof(int));
+    plan(true, c->pred_Wt.size(), (size_t)H * D, sizeof(double));
+    if (grow) {
+      size_t free_b = 0, total_b = 0;
+      HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+      if (grow > free_b + released)
+        return fail(EVOAMD_E_INVALID, "evoamd_posterior_sample: the outputs asked for need %zu bytes of device memory, %zu are free "
+                    "(fewer draws per call, or fewer arrays in keep)", grow, free_b + released);
+    }
+  }
+  if (sssc) TRY(ensure_B(c));
+  if (keep_mask & PSAMP_KEEP_SLOT) TRY(c->ps_slot.ensure(c, nt));
+  if (keep_mask & PSAMP_KEEP_S) TRY(c->ps_s.ensure(c, nt * HW));
+  if (keep_mask & PSAMP_KEEP_Z) TRY(c->ps_z.ensure(c, nt * H));
+  if (keep_mask & PSAMP_KEEP_Y) TRY(c->ps_y.ensure(c, nt * D));
+  TRY(c->ps_status.ensure(c, (size_t)N));
+  TRY(c->pred_Wt.ensure(c, (size_t)H * D));
+  // the scalars of the current Theta (a device update leaves them in the scalar block only)
+  double dpar[DP_COUNT];
+  HIP_TRY(hipMemcpyAsync(dpar, c->dpar, DP_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  PsampArgs q = {};
+  PredArgs &a = q.p;
+  a.mask = c->mask_infr;
+  a.row_any = c->mask_infr ? c->row_any : nullptr;
+  a.lpj = c->lpj;
+  a.states = c->states;
+  a.Wt = c->pred_Wt;
+  a.G = c->G;
+  a.Psi = c->Psi;
+  a.mus = c->mus;
+  a.Bm = c->Bm;
+  a.N = N;
+  a.D = D, a.H = H, a.HW = HW, a.S = c->S, a.S_perm = c->S_perm, a.L = c->L;
+  a.kcap = H < PRED_MAX_K ? H : PRED_MAX_K;
+  a.bg = c->bg_unit;
+  a.sigma2 = sssc ? dpar[DP_SIGMA2] : dpar[DP_SIGMA] * dpar[DP_SIGMA];
+  a.status = c->ps_status;
+  q.Y = c->Y;
+  q.ldY = c->ldY;
+  q.T = T;
+  q.seed = seed, q.first_index = first_index;
+  q.fill_all = fill_all ? 1 : 0, q.add_noise = add_noise ? 1 : 0;
+  q.sigma = sssc ? sqrt(dpar[DP_SIGMA2]) : dpar[DP_SIGMA];
+  q.slot = (keep_mask & PSAMP_KEEP_SLOT) ? c->ps_slot.get() : nullptr;
+  q.s = (keep_mask & PSAMP_KEEP_S) ? c->ps_s.get() : nullptr;
+  q.z = (keep_mask & PSAMP_KEEP_Z) ? c->ps_z.get() : nullptr;
+  q.y = (keep_mask & PSAMP_KEEP_Y) ? c->ps_y.get() : nullptr;
+  int R = 1;
+  while (64 * R < D) R <<= 1;
+  const size_t lds = PRED_WAVES * pred_lds_doubles(a.kcap, sssc) * sizeof(double);
+  {
+    SpanGuard g(c, KID_POSTERIOR_SAMPLE);
+    transpose_kernel<<<cdiv((i64)H * D, 256), 256, 0, c->stream>>>(c->W, D, H, c->pred_Wt);
+    if (sssc)
+      launch_posterior_sample<true>(c, q, R, lds);
+    else
+      launch_posterior_sample<false>(c, q, R, lds);
+  }
+  HIP_TRY(hipGetLastError());
+  DBG_SYNC(c, "posterior_sample");
+  std::vector<int> status((size_t)N);
+  HIP_TRY(hipMemcpyAsync(status.data(), c->ps_status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  counters[0] = counters[1] = counters[2] = counters[3] = 0;
+  for (i64 n = 0; n < N; n++) {
+    const int st = status[(size_t)n];
+    if ((st & 0xFF) == PRED_OVER_K)
+      return fail(EVOAMD_E_INVALID, "evoamd_posterior_sample: datapoint n = %lld holds a state with k = %d active latents, "
+                  "at most %d are supported (PRED_MAX_K)", (long long)n, st >> 8, PRED_MAX_K);
+    counters[0] += st == PRED_SINGULAR;
+    counters[1] += st == PRED_SKIPPED;
+    counters[2] += st == PSAMP_NOT_PD;
+    counters[3] += st == PSAMP_BAD_WEIGHTS;
+  }
+  c->ps_N = N, c->ps_T = T, c->ps_D = D, c->ps_H = H;
+  made_posterior_samples(c, keep_mask);
+  return 0;
+}
+
+extern "C" int evoamd_download_posterior_samples(evoamd_ctx *c, int what, void *out) {
+  REQUIRE(c && out, "evoamd_download_posterior_samples: NULL argument");
+  REQUIRE(c->configured && c->ps_keep >= 0 && c->ps_N == c->N && c->ps_D == c->D && c->ps_H == c->H,
+          "evoamd_download_posterior_samples: no results on the device (call evoamd_posterior_sample first; a failed call and "
+          "evoamd_configure drop them)");
+  const size_t nt = (size_t)c->ps_N * (size_t)c->ps_T;
+  const void *src = nullptr;
+  size_t bytes = 0;
+  int bit = 0;
+  switch (what) {
+    case EVOAMD_PSAMP_SLOT: src = c->ps_slot, bytes = nt * sizeof(int), bit = PSAMP_KEEP_SLOT; break;
+    case EVOAMD_PSAMP_S: src = c->ps_s, bytes = nt * c->HW * sizeof(u64), bit = PSAMP_KEEP_S; break;
+    case EVOAMD_PSAMP_Z: src = c->ps_z, bytes = nt * c->ps_H * sizeof(double), bit = PSAMP_KEEP_Z; break;
+    case EVOAMD_PSAMP_Y: src = c->ps_y, bytes = nt * c->ps_D * sizeof(double), bit = PSAMP_KEEP_Y; break;
+    default: return fail(EVOAMD_E_INVALID, "evoamd_download_posterior_samples: what must be EVOAMD_PSAMP_SLOT, _S, _Z or _Y");
+  }
+  REQUIRE(c->ps_keep & bit, "evoamd_download_posterior_samples: the last evoamd_posterior_sample did not keep this output");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
 // samples from the model (kernels_generate.hpp): own buffers, no EM state touched
 // ---------------------------------------------------------------------------------------
 extern "C" int evoamd_generate(evoamd_ctx *c, int model, int64_t N, int D, int H, uint64_t seed, uint64_t first_index,
@@ -5219,6 +5387,6 @@ extern "C" const char *evoamd_kernel_name(int kid) {
                                          "stats",        "stats_overflow", "gemm_f64",     "evolve",   "misc", "mstep_device",
                                          "lpj_pass",     "stats_pass",     "lpj_k3_4",     "lpj_k5_8", "lpj_k9plus",
                                          "stats_k3_4",   "stats_k5_8",     "stats_k9plus", "allreduce",    "estep_fused",
-                                         "patches",      "init_states"};
+                                         "patches",      "init_states",    "posterior_sample"};
   return (kid >= 0 && kid < KID_COUNT) ? names[kid] : "?";
 }

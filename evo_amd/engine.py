@@ -565,9 +565,43 @@ class Engine:
                                                   None if var is None else dptr(var)))
         return mean, var, {"n_singular": int(counters[0]), "n_skipped": int(counters[1])}
 
+    # ---- posterior samples (evo_amd.models.posterior_sample is the NumPy mirror) -----------------
+    def sample_posterior(self, n_samples=1, seed=0, first_index=0, keep=("slot", "s", "z", "y"), fill="missing", noise=True):
+        """``n_samples`` draws per datapoint from the variational posterior under the Theta, K^n and lpj rows on the device
+        (evoamd_posterior_sample; no statistics pass runs and the EM state stays as it is).  Returns a dict with the arrays
+        ``keep`` names -- "slot" int32 (N, T), "s" bool (N, T, H), "z" float64 (N, T, H; ES3C only), "y" float64 (N, T, D)
+        -- and "info" = {"n_singular", "n_skipped", "n_not_pd", "n_bad_weights"}: the datapoints without draws (slot -1,
+        s zero, z and y NaN).  Only the arrays named are allocated, written and downloaded.  EvoAmdError naming n and k
+        for a state with more than 32 active latents, for D > 512, for "z" with EBSC, and -- naming the bytes -- for
+        outputs that do not fit into the free device memory; nothing is downloaded then."""
+        from .models.generate import unpack_words
+        if fill not in ("missing", "all"):
+            raise ValueError("fill must be 'missing' or 'all'")
+        keep = tuple(keep)
+        bits = 0
+        for name in keep:
+            if name not in _lib.PSAMP_KEEP:
+                raise ValueError("keep: unknown output %r" % (name,))
+            bits |= _lib.PSAMP_KEEP[name]
+        T = int(n_samples)
+        counters = (ctypes.c_int64 * 4)()
+        check(self.lib.evoamd_posterior_sample(self._h, T, int(seed) & (2 ** 64 - 1), int(first_index) & (2 ** 64 - 1), bits,
+                                               1 if fill == "all" else 0, 1 if noise else 0, counters))
+        N, D, H = self.N, self.D, self.H
+        shapes = {"slot": ((N, T), np.int32), "s": ((N * T, (H + 63) // 64), np.uint64), "z": ((N, T, H), np.float64),
+                  "y": ((N, T, D), np.float64)}
+        out = {}
+        for name in ("slot", "s", "z", "y"):
+            if name in keep:
+                a = np.empty(*shapes[name])
+                check(self.lib.evoamd_download_posterior_samples(self._h, _lib.PSAMP_WHAT[name], a.ctypes.data_as(ctypes.c_void_p)))
+                out[name] = unpack_words(a, H).reshape(N, T, H) if name == "s" else a
+        out["info"] = dict(zip(("n_singular", "n_skipped", "n_not_pd", "n_bad_weights"), (int(v) for v in counters)))
+        return out
+
     # ---- timing --------------------------------------------------------------------------
     def timing(self, on=True):
-        """on: True (all kernel classes), False, or an iterable of class names (_lib.KERNEL_IDS)."""
+        """on: True (all kernel classes), False, or an iterable of class names (_lib.KERNEL_IDS, _lib.KERNEL_IDS_EXTRA)."""
         if on is True:
             mask = -1
         elif not on:
@@ -575,7 +609,7 @@ class Engine:
         else:
             mask = 0
             for name in on:
-                mask |= 1 << _lib.KERNEL_IDS[name]
+                mask |= 1 << _lib.kernel_id(name)
         check(self.lib.evoamd_timing_enable(self._h, mask))
 
     def timing_reset(self):
@@ -584,7 +618,7 @@ class Engine:
     def kernel_time_ms(self, name):
         avg = ctypes.c_double()
         n = ctypes.c_int64()
-        check(self.lib.evoamd_kernel_time_ms(self._h, _lib.KERNEL_IDS[name], ctypes.byref(avg), ctypes.byref(n)))
+        check(self.lib.evoamd_kernel_time_ms(self._h, _lib.kernel_id(name), ctypes.byref(avg), ctypes.byref(n)))
         return avg.value, n.value
 
 

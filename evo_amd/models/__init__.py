@@ -4,3 +4,4 @@ from .sssc import SSSC  # noqa: F401
 from .generate import generate_counter  # noqa: F401
 from .exact import enumerate_chunk, fold_exact  # noqa: F401
 from .predictive import predictive_moments_host  # noqa: F401
+from .posterior_sample import sample_posterior_counter  # noqa: F401

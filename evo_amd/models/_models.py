@@ -23,6 +23,7 @@ N datapoints of this rank (see evo_amd/engine.py and csrc/).  Two candidate-gene
 import numpy as np
 
 from .. import engine as _engine
+from .._lib import EvoAmdError
 from ..resident import ResidentReconstruction
 from ..utils import parallel
 from ..variational import eas
@@ -939,6 +940,57 @@ class Model:
         if self.sync_host or self._kn_uploads != uploads:
             eng.upload_lpj(my_suff_stat["lpj"])
         return eng.predictive_moments(noise=noise)
+
+    _KEEP_ALL = ("slot", "s", "z", "y")  # the default of sample_posterior, told from the same names given by the caller
+
+    def sample_posterior(self, model_params, my_suff_stat, my_data, n_samples=1, seed=None, first_index=0,
+                         keep=_KEEP_ALL, fill="missing", noise=True):
+        """``n_samples`` draws per datapoint of this rank from the variational posterior under ``model_params`` and the
+        caller's K^n / lpj: a dict with, for datapoint n and draw t, "slot" (int32 (N, T): the column of lpj drawn with
+        probability q_ns), "s" (bool (N, T, H): the drawn state), ES3C "z" (float64 (N, T, H): z_A ~ N(kappa_s, Lam_s) on
+        the active set, the Lam and kappa of predictive_moments) and "y" (float64 (N, T, D): W z -- EBSC W s -- plus the
+        noise sigma g when ``noise``).  ``fill="missing"``: the reliable entries (x_infr) carry the datapoint's own y and
+        only the others the draw (multiple imputation); ``fill="all"``: every entry carries the draw (a posterior-
+        predictive replicate).  ``keep`` names the arrays to form: only those are allocated, written and downloaded; the
+        default drops "z" for EBSC, which refuses it when asked for by name.  "info" counts the datapoints without draws
+        (slot -1, s zero, z and y NaN): "n_skipped" (no reliable entry), "n_bad_weights" (an lpj row with a NaN or +inf,
+        or all -inf), "n_singular" / "n_not_pd" (a DRAWN state whose k x k system is singular / whose Lam is not positive
+        definite: an indefinite Psi).  The stream is counter-based (evo_amd.models.sample_posterior_counter reproduces it
+        for ``self.last_sample_seed``: slot and s bit for bit): datapoint n is index ``first_index + n`` of the data set,
+        so shards concatenate to the single call, and draw t does not depend on ``n_samples``.  ``seed`` None: drawn from
+        np.random; rank and world size enter it as in generate_data_device.  The float32 mode, D > 512 and a state with
+        more than 32 active latents raise (EvoAmdError naming n and k), as do outputs that do not fit into the free device
+        memory (naming the bytes).  Runs no statistics pass, does no communication, writes nothing into the three dicts,
+        works with sync_host=False and leaves K^n, lpj, Theta, y_reconstructed and the statistics rows on the device as
+        they are."""
+        default_keep = keep is Model._KEEP_ALL
+        keep = tuple(keep)
+        for name in keep:
+            if name not in ("slot", "s", "z", "y"):
+                raise ValueError("keep: unknown output %r" % (name,))
+        if self.model_name != "sssc" and "z" in keep:
+            if not default_keep:
+                raise EvoAmdError("sample_posterior: \"z\" is an ES3C output (EBSC: z = s)")
+            keep = tuple(name for name in keep if name != "z")
+        if fill not in ("missing", "all"):
+            raise ValueError("fill must be 'missing' or 'all'")
+        if self.dtype == np.float32:
+            raise EvoAmdError("sample_posterior is not available in the float32 mode")
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+        self.last_sample_seed = (int(seed) * max(1, self.comm.size) + self.comm.rank) & (2 ** 64 - 1)
+        yr = my_data.get("y_reconstructed")
+        if isinstance(yr, ResidentReconstruction) and yr.resident and not yr.materialised:
+            yr.rows()  # setting the parameters below drops the device copy of an unread reconstruction: fetch it first
+        uploads = self._kn_uploads  # (see reconstruct(): decide before _prepare() runs)
+        eng = self._prepare(my_suff_stat, my_data)
+        # (the precompute stores its derived keys and zeroes the reset counters: on shallow copies here)
+        self.E_step_precompute(dict(model_params), dict(my_suff_stat), my_data)
+        if model_params is not self._dev_theta:
+            self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
+        if self.sync_host or self._kn_uploads != uploads:
+            eng.upload_lpj(my_suff_stat["lpj"])
+        return eng.sample_posterior(n_samples, self.last_sample_seed, first_index, keep, fill, noise)
 
     def modelmean(self, model_params, this_data, this_suff_stat):
         """Per-datapoint operator of the reference's reconstruct loop: (D_miss, S) means of the entries to be

@@ -21,9 +21,9 @@ PRED_MAX_K = 32
 F64_TINY = np.finfo(np.float64).tiny
 
 
-def state_terms_es3c(W, mus, Psi, sigma2, idx, y, obs=None):
-    """(m, v) of one ES3C state with the active latents ``idx`` (k >= 1 of them) for the datapoint ``y`` whose reliable
-    entries are ``obs`` (bool (D,), None: all): m (D,) = W_A kappa and v (D,) = diag(W_A Lam W_A^T), clamped at 0.
+def state_posterior_es3c(W, mus, Psi, sigma2, idx, y, obs=None):
+    """(Lam, kappa) of one ES3C state with the active latents ``idx`` (k >= 1 of them) for the datapoint ``y`` whose
+    reliable entries are ``obs`` (bool (D,), None: all): the Gaussian posterior N(kappa, Lam) of z_A.
     Lam = (I + Psi_AA G_A / sigma2)^-1 Psi_AA, the form that needs no inverse of Psi_AA.  None for a singular system:
     np.linalg raises LinAlgError (an exactly zero pivot) on Psi_AA or on I + Psi_AA G_A / sigma2, or a non-finite result."""
     WA = W[:, idx]
@@ -41,7 +41,17 @@ def state_terms_es3c(W, mus, Psi, sigma2, idx, y, obs=None):
         return None
     if not np.isfinite(X).all():
         return None
-    Lam, kappa = X[:, :k], mus[idx] + X[:, k] / sigma2
+    return X[:, :k], mus[idx] + X[:, k] / sigma2
+
+
+def state_terms_es3c(W, mus, Psi, sigma2, idx, y, obs=None):
+    """(m, v) of one ES3C state (the arguments of state_posterior_es3c): m (D,) = W_A kappa and v (D,) =
+    diag(W_A Lam W_A^T), clamped at 0.  None for a singular system."""
+    post = state_posterior_es3c(W, mus, Psi, sigma2, idx, y, obs)
+    if post is None:
+        return None
+    Lam, kappa = post
+    WA = W[:, idx]
     return WA @ kappa, np.maximum(np.einsum("di,ij,dj->d", WA, Lam, WA), 0.0)
 
 

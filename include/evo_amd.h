@@ -559,6 +559,39 @@ int evoamd_generate(evoamd_ctx *ctx, int model, int64_t N, int D, int H, uint64_
                     const uint64_t *s_packed_or_null, int keep);
 int evoamd_download_generated(evoamd_ctx *ctx, int what, void *out);
 
+/* ---- posterior samples (draws from q: states of K^n, ES3C latents, data rows) ---- */
+/* evoamd_posterior_sample: for every datapoint n of the context and every draw t < n_samples, from the Theta, K^n and
+ * lpj rows on the device (csrc/kernels_posterior_sample.hpp has the law; evo_amd.models.sample_posterior_counter is its
+ * NumPy mirror: slot and s bit for bit, z and y to the rounding of the k x k arithmetic):
+ *   slot  the column of lpj drawn with probability q_ns (0 .. S_perm + S - 1; the weights are those of
+ *         evoamd_posterior_codes' map_q: a bit-reproducible exp, summed in slot order; a slot of weight 0 is never drawn);
+ *   s     the drawn state: ceil(H/64) 64-bit words, latent h in word h/64 at bit 63-(h%64), all zero for the permanent
+ *         all-zero state, the background unit set where that option is on;
+ *   z     ES3C: z_A ~ N(kappa_s, Lam_s) on the active set with the Lam and kappa of evoamd_predictive_moments (Cholesky
+ *         factor of the symmetrised Lam), 0 elsewhere;
+ *   y     W z (EBSC: W s) + sigma g when add_noise; fill_all = 0: the reliable entries (evoamd_upload_masks; all of them
+ *         for complete data) carry the datapoint's own y and only the others the draw; fill_all = 1: every entry the draw.
+ * The stream is counter-based like evoamd_generate's, under a purpose of its own: datapoint n is index first_index + n of
+ * the data set (shards concatenate to the single call) and draw t does not depend on n_samples (fewer draws are a prefix).
+ * keep_mask: EVOAMD_PSAMP_KEEP_SLOT | _S | _Z | _Y -- only these outputs are allocated and written (z: ES3C only).
+ * counters[4] = datapoints without draws (slot -1, s zero, z and y NaN in every row) because: [0] a drawn state has a
+ * singular k x k system, [1] they have no reliable entry, [2] the Lam of a drawn state is not positive definite (an
+ * indefinite Psi), [3] their lpj row holds a NaN or +inf or only -inf ("bad weights").  One wavefront per datapoint; every
+ * sum has a fixed order and there are no atomics: a call repeats bit for bit.  Runs no statistics pass and leaves K^n, lpj,
+ * Theta, y_reconstructed, the statistics rows and every validity flag of the EM state as they are (B = Y W is formed if
+ * it is not current, as by every lpj pass).  Refusals (EVOAMD_E_INVALID): the float32 mode; D above 512; a state of K^n
+ * with more than 32 active latents (the message names n and k; nothing can be downloaded then); outputs that do not fit
+ * into the free device memory (the message names the bytes needed; decided before anything is launched).
+ * The outputs stay in device buffers of the context (grown on demand, released by evoamd_configure and
+ * evoamd_ctx_destroy) until the next call; evoamd_download_posterior_samples copies one to the host: what =
+ * EVOAMD_PSAMP_SLOT (N x T int32), _S (N x T x ceil(H/64) uint64), _Z (N x T x H double), _Y (N x T x D double);
+ * EVOAMD_E_INVALID for an output the last call did not keep.  Both calls have completed on return. */
+enum { EVOAMD_PSAMP_KEEP_SLOT = 1, EVOAMD_PSAMP_KEEP_S = 2, EVOAMD_PSAMP_KEEP_Z = 4, EVOAMD_PSAMP_KEEP_Y = 8 };
+enum { EVOAMD_PSAMP_SLOT = 0, EVOAMD_PSAMP_S = 1, EVOAMD_PSAMP_Z = 2, EVOAMD_PSAMP_Y = 3 };
+int evoamd_posterior_sample(evoamd_ctx *ctx, int n_samples, uint64_t seed, uint64_t first_index, int keep_mask,
+                            int fill_all, int add_noise, int64_t counters[4]);
+int evoamd_download_posterior_samples(evoamd_ctx *ctx, int what, void *out);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------------- */
 /* 128-byte opaque id made by rank 0 and distributed by the caller (file / socket / MPI). */
 int evoamd_comm_unique_id(uint8_t id_out[128]);
@@ -595,7 +628,9 @@ enum {
                                   this rank's statistics being done to the sum being delivered, i.e. wait for the slowest rank + transfer */
   EVOAMD_K_ESTEP_FUSED = 20,   /* fused per-datapoint E-step kernel (option "fused_estep") */
   EVOAMD_K_PATCHES = 21,       /* evoamd_patches_extract / evoamd_patches_merge kernels (transfers excluded) */
-  EVOAMD_K_COUNT = 22
+  EVOAMD_K_INIT_STATES = 22,   /* evoamd_init_states: the K^n(0) sampler */
+  EVOAMD_K_POSTERIOR_SAMPLE = 23, /* evoamd_posterior_sample: W^T and the sampling kernel (transfers excluded) */
+  EVOAMD_K_COUNT = 24
 };
 /* on = bit mask of kernel classes to time (bit k = class k; -1 = all, 0 = off).  Each timed span
  * records two HIP events on the compute stream, which costs about 10 us of stream time per span:
