@@ -43,7 +43,7 @@ KERNEL_IDS = {
 }
 # classes outside the EM path, added after tests/test_gpu_validity.py recorded its launch census over KERNEL_IDS (which
 # therefore stays as it is); Engine.timing / Engine.kernel_time_ms take names of either table
-KERNEL_IDS_EXTRA = {"posterior_sample": 23}
+KERNEL_IDS_EXTRA = {"posterior_sample": 23, "seed_states": 24}
 
 
 def kernel_id(name):
@@ -74,6 +74,7 @@ SIGNATURES = {
     "evoamd_upload_states_packed": (_I, [_vp, _c_u8p, _I64, _I64]),
     "evoamd_download_states_packed": (_I, [_vp, _c_u8p, _I64, _I64]),
     "evoamd_init_states": (_I, [_vp, _DBL, _U64, _I, _c_u8p]),
+    "evoamd_seed_states": (_I, [_vp, _I, _c_i32p, _c_dp]),
     "evoamd_upload_lpj": (_I, [_vp, _c_dp]),
     "evoamd_download_lpj": (_I, [_vp, _c_dp]),
     "evoamd_set_params_bsc": (_I, [_vp, _c_dp, _DBL, _DBL, _c_dp]),

@@ -32,6 +32,7 @@
 #include "kernels_exact.hpp"
 #include "kernels_predictive.hpp"
 #include "kernels_posterior_sample.hpp"
+#include "kernels_seed.hpp"
 
 // ---------------------------------------------------------------------------------------
 // error handling
@@ -152,6 +153,7 @@ enum {  // internal kernel ids (see evoamd_kernel_name)
   KID_PATCHES,      // overlapping image patches: extract / mean merge / median merge kernels
   KID_INIT_STATES,  // evoamd_init_states: the K^n(0) sampler (or the table copy of the exact mode)
   KID_POSTERIOR_SAMPLE,  // evoamd_posterior_sample: W^T and the sampling kernel (transfers excluded)
+  KID_SEED_STATES,  // evoamd_seed_states: the greedy seeding kernel
   KID_COUNT
 };
 
@@ -535,6 +537,7 @@ struct evoamd_ctx {
   // that reads K^n refuses until an upload or a successful evoamd_init_states
   int init_home = -1;
   DevBuf<u64> init_scratch;
+  DevBuf<double2> seed_gpt;  // evoamd_seed_states, ES3C: the transpose of GP (H x H), grown on demand, rewritten by every call
   bool kn_lost = false;
   i64 kn_refill = 0;  // while kn_lost: rows [0, kn_refill) have been uploaded again by evoamd_upload_states_packed
   // evoamd_generate (kernels_generate.hpp): Theta^gen, the given states and the outputs of the last call, grown on demand
@@ -855,6 +858,8 @@ static int set_kernel_lds_limits() {
                         (const void *)posterior_sample_kernel<4, true>, (const void *)posterior_sample_kernel<8, true>};
     for (const void *f : sk) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   }
+  HIP_TRY(hipFuncSetAttribute((const void *)seed_states_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  HIP_TRY(hipFuncSetAttribute((const void *)seed_states_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   {
     const void *wk[] = {(const void *)sssc_stats_wave_kernel<0, 4>,  (const void *)sssc_stats_wave_kernel<1, 4>,
                         (const void *)sssc_stats_wave_kernel<2, 4>,  (const void *)sssc_stats_wave_kernel<4, 4>,
@@ -1208,6 +1213,7 @@ static void configure_drop(evoamd_ctx *c) {
   c->tmpWt.reset();
   c->Wt.reset();
   c->init_scratch.reset();
+  c->seed_gpt.reset();
   // the posterior samples of the previous geometry
   c->ps_slot.reset();
   c->ps_status.reset();
@@ -5057,6 +5063,75 @@ extern "C" int evoamd_download_predictive(evoamd_ctx *c, double *mean, double *v
 }
 
 // ---------------------------------------------------------------------------------------
+// K^n seeded by greedy forward selection on the model's lpj (kernels_seed.hpp).  Every refusal comes before the first write.
+extern "C" int evoamd_seed_states(evoamd_ctx *c, int max_active, int32_t *path_out, double *lpj_out) {
+  REQUIRE(c && c->configured, "configure first");
+  REQUIRE(c->have_params, "evoamd_seed_states: no Theta installed (set parameters first)");
+  REQUIRE(c->have_data, "evoamd_seed_states: no data (upload data first)");
+  REQUIRE(!c->mask_infr, "evoamd_seed_states: incomplete data (masks present) is not supported");
+  REQUIRE(!c->bg_unit, "evoamd_seed_states: option background_unit is not supported");
+  REQUIRE(!c->f32, "evoamd_seed_states is not available in the float32 mode (ebsc_f32)");
+  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
+  REQUIRE(sssc || !c->bsc_direct, "evoamd_seed_states: bsc_direct keeps no G = W^T W, which the scores need");
+  const int S = c->S, H = c->H, HW = c->HW, A = max_active;
+  const int cap = sssc ? SEED_MAX_A_SSSC : SEED_MAX_A_BSC;
+  if (A < 1 || A > S || A > H || A > cap)
+    return fail(EVOAMD_E_INVALID, "evoamd_seed_states: max_active = %d must be in [1, min(S = %d, H = %d, %d)] (%s)", A, S, H,
+                cap, sssc ? "ES3C: at most 8" : "EBSC: at most 64");
+  const int q_lo = S / A, q_rem = S % A;
+  for (int t = 1; t <= A; t++) {
+    const int q = q_lo + (t <= q_rem ? 1 : 0);
+    if (q > H - (t - 1))
+      return fail(EVOAMD_E_INVALID, "evoamd_seed_states: the quota q_%d = %d exceeds the H - (t - 1) = %d latents left at step %d "
+                  "(S = %d, max_active = %d)", t, q, H - (t - 1), t, S, A);
+  }
+  const int Hp = (int)cdiv(H, 64) * 64, Q = q_lo + (q_rem ? 1 : 0);
+  const size_t wave_bytes = seed_wave_bytes(Hp, HW, Q, A);
+  REQUIRE(wave_bytes <= 150 * 1024, "evoamd_seed_states: the scores of one datapoint (16 H bytes) do not fit one wavefront's share of LDS");
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(ensure_B(c));
+  const size_t n_out = (size_t)c->N * A;
+  const size_t out_bytes = ((n_out * sizeof(int) + 7) / 8) * 8;
+  if (path_out || lpj_out) TRY(c->stage.ensure(c, out_bytes + n_out * sizeof(double)));
+  if (sssc) TRY(c->seed_gpt.ensure(c, (size_t)H * H));
+  SeedArgs a;
+  a.states = c->states;
+  a.dig = c->dig;
+  a.Bm = c->Bm;
+  a.yy = c->yy;
+  a.G = c->G;
+  a.Gd = c->diag;
+  a.GP = c->GP;
+  a.mus = c->mus;
+  a.pil_bar = c->pilbar_v;
+  a.GPt = c->seed_gpt;
+  a.dpar = c->dpar;
+  a.path = path_out ? (int *)c->stage.get() : nullptr;
+  a.lpj_path = lpj_out ? (double *)(c->stage.get() + out_bytes) : nullptr;
+  a.err = c->err;
+  a.N = c->N;
+  a.S = S, a.H = H, a.HW = HW, a.A = A, a.Hp = Hp, a.Q = Q;
+  int W = 4;
+  while (W > 1 && W * wave_bytes > 150 * 1024) W >>= 1;
+  const unsigned grid = (unsigned)std::min<i64>(cdiv(c->N, W), (i64)c->n_cu * 64);
+  on_kn_changed(c, KN_BY_CALLER);
+  {
+    SpanGuard g(c, KID_SEED_STATES);
+    if (sssc) seed_transpose_gp_kernel<<<cdiv((i64)H * H, 256), 256, 0, c->stream>>>(c->GP, H, c->seed_gpt);
+    if (sssc)
+      seed_states_kernel<true><<<grid, 64 * W, W * wave_bytes, c->stream>>>(a);
+    else
+      seed_states_kernel<false><<<grid, 64 * W, W * wave_bytes, c->stream>>>(a);
+  }
+  HIP_TRY(hipGetLastError());
+  DBG_SYNC(c, "seed_states");
+  if (path_out) HIP_TRY(hipMemcpyAsync(path_out, a.path, n_out * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (lpj_out) HIP_TRY(hipMemcpyAsync(lpj_out, a.lpj_path, n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  on_kn_complete(c);
+  return 0;
+}
+
 // posterior samples (kernels_posterior_sample.hpp): own buffers; of the EM state only B = Y W is (re)formed, like every lpj pass
 // ---------------------------------------------------------------------------------------
 template <bool SSSC>
@@ -5387,6 +5462,6 @@ extern "C" const char *evoamd_kernel_name(int kid) {
                                          "stats",        "stats_overflow", "gemm_f64",     "evolve",   "misc", "mstep_device",
                                          "lpj_pass",     "stats_pass",     "lpj_k3_4",     "lpj_k5_8", "lpj_k9plus",
                                          "stats_k3_4",   "stats_k5_8",     "stats_k9plus", "allreduce",    "estep_fused",
-                                         "patches",      "init_states",    "posterior_sample"};
+                                         "patches",      "init_states",    "posterior_sample", "seed_states"};
   return (kid >= 0 && kid < KID_COUNT) ? names[kid] : "?";
 }

@@ -1,0 +1,434 @@
+// K^n seeded from Theta and the data: greedy forward selection (matching pursuit) on the model's own lpj, one wavefront
+// per datapoint.  Deterministic, no random numbers.  evo_amd/variational/utils.py: seed_states_host is the NumPy mirror
+// -- keep the two and the tests in step.
+//
+// THE LAW, per datapoint n (A = max_active steps, Hv = H varying latents, A_0 = {}):
+//   quotas   q_t = S / A + (t <= S mod A), t = 1..A, so sum q_t = S
+//   step t   every j not in A_{t-1} is scored with score_j = lpj(A_{t-1} + {j}) -- the model's lpj without ljc and without
+//            the lpj_reset_check clamp; a score that is not finite, or (ES3C) whose det T is not positive, is -inf;
+//            latents are ranked by descending score, ties (and the -inf ones) by ascending j; the q_t best states
+//            A_{t-1} + {j} go to the next q_t slots in rank order; the best one becomes A_t
+//   slots    step-major: the state of step t and rank r sits at slot sum_{u<t} q_u + r.  Sizes are t and the states of a
+//            step differ in j, so all S states are distinct and none is the all-zero state (S_perm keeps its own column).
+// THE SCORES, in the Gram form of the lpj kernels (B = Y W, G = W^T W, yy = |y|^2):
+//   EBSC  score_j = lpj(A_{t-1}) + pil_bar + pre1 (G_jj - 2 c_j), c_j = B_nj - sum_{i in A_{t-1}} G_ij; e_j = G_jj - 2 c_j is
+//         kept in LDS across the steps (one row of G per step), lpj({}) = pre1 yy
+//   ES3C  the k x k system of kernels_sssc.hpp's header, k = t, eliminated from scratch per candidate in registers
+//         (template on k, so every loop unrolls): v = b - G_A mu, rr = yy - sum mu_i (b_i + v_i), T = I + Psi_A G_A / sigma2,
+//         LU of [T | Psi_A v] with partial pivoting (first max |pivot|), det T with its sign from the pivots,
+//         lpj = sum pil_bar - (log det T + rr / sigma2 - v^T T^-1 Psi_A v / sigma2^2) / 2.  The candidates of a step share
+//         A_{t-1}: its blocks G_A, Psi_A, T_A, mu_A, b_A, v_A are formed once per step in LDS (SeedShared) and a candidate
+//         adds its own row and column, 4 (t - 1)^2 multiply-adds, in front of the t^3 / 3 of the elimination: about
+//         H sum_t (t^3 / 3 + 4 t^2) = 6e5 multiply-adds per datapoint at H = 512, A = 8.
+// Mapping: lane l owns latents l, l + 64, ...; its scores go to LDS as 64-bit keys whose unsigned order is the order of
+// the doubles (key 0 = latent already in A_{t-1}, below the key of -inf).  The q_t best by a THRESHOLD SEARCH over the
+// keys: the q_t-th largest key T is built bit by bit (64 counting passes of ballots over the lane's own keys, which stay
+// in registers while H <= 1024 and are re-read sixteen chunks per LDS round trip above that), the
+// members are the keys above T and the first keys equal to T in ascending j; they are compacted into a list in ascending
+// j, ranked by counting within the list (q_t^2 / 64 broadcast reads) and laid out by rank.  Then q_t HW words and q_t
+// digests (the digest digest_kernel would compute: the first DIG_SLOTS of the ascending active latents, k = t) leave the
+// wave with lane-strided stores.  Every latent index that crossed LDS passes guard_index before it becomes an address.
+// LDS per wave: keys and e (Hp = Hv rounded up to 64 doubles each), the HW words of A_{t-1}, the shared blocks (168 doubles),
+// the members' keys and two lists of their latents (max q_t each), the path and the ascending active set (A ints each).
+#pragma once
+#include "common.hpp"
+#include "kernels_mstep.hpp"
+
+#define SEED_MAX_A_SSSC 8
+#define SEED_MAX_A_BSC 64
+#define SEED_KREG 16  // chunks of keys a lane holds in registers during the threshold search
+#define SEED_M (SEED_MAX_A_SSSC - 1)  // the active set in front of a step's candidates: at most 7 latents
+#define SEED_SHARED_DOUBLES (3 * SEED_M * SEED_M + 3 * SEED_M)
+
+struct SeedArgs {
+  u64 *states;          // (N, S, HW) K^n
+  u64 *dig;             // (N, S) or nullptr
+  const double *Bm;     // (N, H) B = Y W
+  const double *yy;     // (N)
+  const double *G;      // EBSC (H, H)
+  const double *Gd;     // EBSC (H) diag(G)
+  const double2 *GP;    // ES3C (H, H) {G_ij, Psi_ij}
+  const double2 *GPt;   // ES3C (H, H) its transpose {G_ji, Psi_ji} (seed_transpose_gp_kernel): the row of j, coalesced over j
+  const double *mus;    // ES3C (H)
+  const double *pil_bar;  // ES3C (H)
+  const double *dpar;
+  int *path;            // (N, A) or nullptr
+  double *lpj_path;     // (N, A) or nullptr
+  int *err;             // err[0] of the context's block (EVO_ERR_BAD_ENTRY)
+  i64 N;
+  int S, H, HW, A, Hp, Q;  // Hp: Hv rounded up to 64; Q: largest quota
+};
+
+__host__ __device__ inline size_t seed_wave_bytes(int Hp, int HW, int Q, int A) {
+  size_t b = (size_t)2 * Hp * 8 + (size_t)HW * 8 + (size_t)SEED_SHARED_DOUBLES * 8 + (size_t)Q * 8 + (size_t)2 * Q * 4 + (size_t)2 * A * 4;
+  return (b + 15) & ~(size_t)15;
+}
+
+__device__ __forceinline__ void seed_wave_sync() {
+  __threadfence_block();
+  __builtin_amdgcn_wave_barrier();
+}
+// the order of the doubles as an unsigned order; never 0 (the key of -inf is 0x000F..F)
+__device__ __forceinline__ u64 seed_key(double v) {
+  if (!(fabs(v) <= 1.7976931348623157e308)) v = -__builtin_inf();  // NaN, +inf, -inf
+  v += 0.0;  // -0 -> +0: equal scores, equal keys
+  const u64 b = (u64)__double_as_longlong(v);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double seed_unkey(u64 k) {
+  const u64 b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
+  return __longlong_as_double((long long)b);
+}
+__device__ __forceinline__ u64 seed_uniform(u64 v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+  return ((u64)hi << 32) | lo;
+}
+
+// What the candidates of one step share (ES3C): the blocks of the active set A_{t-1}, m = t - 1 <= 7 latents, formed once
+// per step by the wave and read back as LDS broadcasts.  Row stride SEED_M.
+struct SeedShared {
+  double *GA, *PA, *TA;    // G_A, Psi_A, T_A = I + Psi_A G_A / sigma2
+  double *muA, *bA, *vA;   // mu_A, B_nA, v_A = B_nA - G_A mu_A
+};
+
+// ES3C lpj of the state act[0..K-2] + {j} for one datapoint (file header).  act is wave-uniform, j the lane's latent.  The
+// bordered system: only the row and the column of j are the lane's own -- 2 (K - 1) coalesced loads of {G, Psi} (the row
+// from the transposed table: gathered from GP it would fetch a 128-byte line per 16 bytes used), the diagonal entry and
+// 4 (K - 1)^2 multiply-adds in front of the elimination.
+template <int K>
+__device__ __forceinline__ double seed_score_sssc(const SeedArgs &a, const SeedShared &sh, const int *act, double pbA, int j,
+                                                  const double *__restrict__ Bn, double yy, double s2inv) {
+  constexpr int M = K - 1, MM = M > 0 ? M : 1;
+  double gc[MM], pc[MM], gr[MM], pr[MM];  // G_ij, Psi_ij, G_ji, Psi_ji, i in A
+#pragma unroll
+  for (int i = 0; i < M; i++) {
+    const double2 c = a.GP[(size_t)act[i] * a.H + j], r = a.GPt[(size_t)act[i] * a.H + j];
+    gc[i] = c.x, pc[i] = c.y, gr[i] = r.x, pr[i] = r.y;
+  }
+  const double2 djj = a.GP[(size_t)j * a.H + j];
+  const double gjj = djj.x, pjj = djj.y, muj = a.mus[j], bj = Bn[j];
+  const double pb = pbA + a.pil_bar[j];
+  double v[K], rr = yy;
+  {
+    double s = bj - gjj * muj;
+#pragma unroll
+    for (int i = 0; i < M; i++) {
+      s -= gr[i] * sh.muA[i];
+      v[i] = sh.vA[i] - gc[i] * muj;
+      rr -= sh.muA[i] * (sh.bA[i] + v[i]);
+    }
+    v[M] = s;
+    rr -= muj * (bj + s);
+  }
+  double t[K][K + 1];  // [T | Psi v] of the bordered system
+  {
+    double corner = pjj * gjj, rhs_m = pjj * v[M];
+#pragma unroll
+    for (int i = 0; i < M; i++) {
+      double col = pc[i] * gjj, row = pjj * gr[i], rhs = pc[i] * v[M];
+#pragma unroll
+      for (int l = 0; l < M; l++) {
+        col += sh.PA[i * SEED_M + l] * gc[l];  // (Psi_A G_Aj)_i
+        row += pr[l] * sh.GA[l * SEED_M + i];  // (Psi_jA G_A)_i
+        rhs += sh.PA[i * SEED_M + l] * v[l];
+        t[i][l] = sh.TA[i * SEED_M + l] + s2inv * (pc[i] * gr[l]);
+      }
+      t[i][M] = s2inv * col;
+      t[M][i] = s2inv * row;
+      t[i][K] = rhs;
+      corner += pr[i] * gc[i];
+      rhs_m += pr[i] * v[i];
+    }
+    t[M][M] = 1.0 + s2inv * corner;
+    t[M][K] = rhs_m;
+  }
+  // LU with partial pivoting (first max |pivot|); rows swap by selects, so nothing is indexed at run time
+  LogDetAcc ld;
+  bool neg = false, zero = false;
+  double rpiv[K];
+#pragma unroll
+  for (int c = 0; c < K; c++) {
+    int r = c;
+    double best = fabs(t[c][c]);
+#pragma unroll
+    for (int i = c + 1; i < K; i++) {
+      const double x = fabs(t[i][c]);
+      if (x > best) best = x, r = i;
+    }
+#pragma unroll
+    for (int i = c + 1; i < K; i++) {
+      const bool sw = r == i;
+#pragma unroll
+      for (int m = c; m <= K; m++) {
+        const double x = t[c][m], y = t[i][m];
+        t[c][m] = sw ? y : x;
+        t[i][m] = sw ? x : y;
+      }
+    }
+    neg = neg != (r != c);
+    const double piv = t[c][c];
+    neg = neg != (piv < 0.0);
+    zero = zero || !(fabs(piv) > 0.0);  // 0 or NaN
+    ld.mul(piv);
+    const double rp = fast_rcp(piv);
+    rpiv[c] = rp;
+#pragma unroll
+    for (int i = c + 1; i < K; i++) {
+      const double f = t[i][c] * rp;
+#pragma unroll
+      for (int m = c + 1; m <= K; m++) t[i][m] -= f * t[c][m];
+    }
+  }
+  // back substitution: x = T^-1 Psi_A v, quad = v^T x (v in the pivoted order of the columns = the original order)
+  double x[K], quad = 0.0;
+#pragma unroll
+  for (int i = K - 1; i >= 0; i--) {
+    double s = t[i][K];
+#pragma unroll
+    for (int m = i + 1; m < K; m++) s -= t[i][m] * x[m];
+    x[i] = s * rpiv[i];
+    quad += v[i] * x[i];
+  }
+  if (neg || zero) return -__builtin_inf();
+  return pb - 0.5 * (ld.value() + rr * s2inv - quad * s2inv * s2inv);
+}
+
+// Psi is not symmetric (kernels_sssc.hpp), so the rows {G_ja, Psi_ja} of the candidates come from a transposed copy of GP,
+// rebuilt by every call (H x H entries: 4 MB at H = 512).
+__global__ __launch_bounds__(256) void seed_transpose_gp_kernel(const double2 *__restrict__ GP, int H, double2 *__restrict__ GPt) {
+  const i64 idx = (i64)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (i64)H * H) return;
+  const int r = (int)(idx / H), c = (int)(idx - (i64)r * H);
+  GPt[idx] = GP[(size_t)c * H + r];
+}
+
+template <bool SSSC>
+__global__ __launch_bounds__(256) void seed_states_kernel(SeedArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char seed_lds[];
+  const int lane = lane_id(), wave = wave_id_uniform();
+  const int W = (int)(blockDim.x >> 6);
+  const int S = a.S, H = a.H, HW = a.HW, A = a.A, Hp = a.Hp, Q = a.Q;
+  const int NC = Hp >> 6, NG = (NC + SEED_KREG - 1) / SEED_KREG;  // chunks of 64 latents, register loads of SEED_KREG chunks
+  unsigned char *home = seed_lds + (size_t)wave * seed_wave_bytes(Hp, HW, Q, A);
+  u64 *keys = (u64 *)home;
+  double *cc = (double *)(keys + Hp);
+  u64 *base = (u64 *)(cc + Hp);
+  double *shd = (double *)(base + HW);
+  const SeedShared sh = {shd, shd + SEED_M * SEED_M, shd + 2 * SEED_M * SEED_M, shd + 3 * SEED_M * SEED_M,
+                         shd + 3 * SEED_M * SEED_M + SEED_M, shd + 3 * SEED_M * SEED_M + 2 * SEED_M};
+  u64 *selk = (u64 *)(shd + SEED_SHARED_DOUBLES);
+  int *sel = (int *)(selk + Q);
+  int *byrank = sel + Q;
+  int *path = byrank + Q;
+  int *sorted = path + A;
+  const double pre1 = SSSC ? 0.0 : a.dpar[DP_PRE1];
+  const double pilb = SSSC ? 0.0 : a.dpar[DP_PILBAR];
+  const double s2inv = SSSC ? a.dpar[DP_S2INV] : 0.0;
+  const int q_lo = S / A, q_rem = S - q_lo * A;
+  for (i64 n = (i64)blockIdx.x * W + wave; n < a.N; n += (i64)gridDim.x * W) {
+    const double *Bn = a.Bm + (size_t)n * H;
+    const double yy = a.yy[n];
+    u64 *dst = a.states + (size_t)n * S * HW;
+    for (int w = lane; w < HW; w += 64) base[w] = 0ull;
+    if (!SSSC)  // e_j = G_jj - 2 B_nj; eight chunks of loads in flight
+      for (int c0 = 0; c0 < NC; c0 += 8) {
+        double gd[8], bn[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+          const int j = 64 * (c0 + u) + lane;
+          const bool in = c0 + u < NC && j < H;
+          gd[u] = in ? a.Gd[j] : 0.0;
+          bn[u] = in ? Bn[j] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; u++)
+          if (c0 + u < NC) cc[64 * (c0 + u) + lane] = gd[u] - 2.0 * bn[u];
+      }
+    seed_wave_sync();
+    double lpj_base = pre1 * yy;  // EBSC: lpj(A_{t-1})
+    int slot0 = 0;
+    for (int t = 1; t <= A; t++) {
+      const int q = q_lo + (t <= q_rem ? 1 : 0);
+      // ---- scores -> keys
+      int act[SEED_MAX_A_SSSC];
+      double pbA = 0.0;
+      if (SSSC) {
+        const int m = t - 1;
+#pragma unroll
+        for (int i = 0; i < SEED_MAX_A_SSSC; i++)
+          act[i] = i < m ? guard_index(__builtin_amdgcn_readfirstlane(path[i]), H, a.err) : 0;
+        // the blocks of A_{t-1}: lane i m + c holds entry (i, c)
+        const int bi = lane / (m > 0 ? m : 1), bc = lane - bi * (m > 0 ? m : 1);
+        const bool in_block = m > 0 && lane < m * m;
+        if (in_block) {
+          const double2 e = a.GP[(size_t)guard_index(path[bi], H, a.err) * H + guard_index(path[bc], H, a.err)];
+          sh.GA[bi * SEED_M + bc] = e.x;
+          sh.PA[bi * SEED_M + bc] = e.y;
+        }
+        if (lane < m) {
+          const int h = guard_index(path[lane], H, a.err);
+          sh.muA[lane] = a.mus[h];
+          sh.bA[lane] = Bn[h];
+        }
+        seed_wave_sync();
+        if (in_block) {
+          double s = 0.0;
+          for (int l = 0; l < m; l++) s += sh.PA[bi * SEED_M + l] * sh.GA[l * SEED_M + bc];
+          sh.TA[bi * SEED_M + bc] = (bi == bc ? 1.0 : 0.0) + s2inv * s;
+        }
+        if (lane < m) {
+          double s = sh.bA[lane];
+          for (int l = 0; l < m; l++) s -= sh.GA[lane * SEED_M + l] * sh.muA[l];
+          sh.vA[lane] = s;
+        }
+        for (int i = 0; i < m; i++) pbA += a.pil_bar[guard_index(path[i], H, a.err)];
+        seed_wave_sync();
+      }
+      for (int c = 0; c < NC; c++) {
+        const int j = 64 * c + lane;
+        u64 key = 0ull;
+        const bool live = j < H && !((base[j < H ? j >> 6 : 0] >> (63 - (j & 63))) & 1ull);
+        if (live) {
+          double sc;
+          if (SSSC) {
+            switch (t) {
+              case 1: sc = seed_score_sssc<1>(a, sh, act, pbA, j, Bn, yy, s2inv); break;
+              case 2: sc = seed_score_sssc<2>(a, sh, act, pbA, j, Bn, yy, s2inv); break;
+              case 3: sc = seed_score_sssc<3>(a, sh, act, pbA, j, Bn, yy, s2inv); break;
+              case 4: sc = seed_score_sssc<4>(a, sh, act, pbA, j, Bn, yy, s2inv); break;
+              case 5: sc = seed_score_sssc<5>(a, sh, act, pbA, j, Bn, yy, s2inv); break;
+              case 6: sc = seed_score_sssc<6>(a, sh, act, pbA, j, Bn, yy, s2inv); break;
+              case 7: sc = seed_score_sssc<7>(a, sh, act, pbA, j, Bn, yy, s2inv); break;
+              default: sc = seed_score_sssc<8>(a, sh, act, pbA, j, Bn, yy, s2inv); break;
+            }
+          } else {
+            sc = lpj_base + pilb + pre1 * cc[j];
+          }
+          key = seed_key(sc);
+        }
+        keys[j] = key;
+      }
+      seed_wave_sync();
+      // ---- T = the q-th largest key: the largest T with #{key >= T} >= q (q <= live latents: T > 0).  SEED_KREG chunks
+      // of keys at a time in registers, so that one LDS round trip serves that many ballots; H <= 1024: they stay there
+      u64 kreg[SEED_KREG];
+      if (NG == 1) {
+#pragma unroll
+        for (int u = 0; u < SEED_KREG; u++) kreg[u] = u < NC ? keys[64 * u + lane] : 0ull;
+      }
+      u64 T = 0ull;
+      for (int bit = 63; bit >= 0; bit--) {
+        const u64 cand = T | (1ull << bit);
+        int cnt = 0;
+        for (int g = 0; g < NG; g++) {
+          if (NG > 1) {
+#pragma unroll
+            for (int u = 0; u < SEED_KREG; u++) kreg[u] = SEED_KREG * g + u < NC ? keys[64 * (SEED_KREG * g + u) + lane] : 0ull;
+          }
+#pragma unroll
+          for (int u = 0; u < SEED_KREG; u++) cnt += __popcll(__ballot(kreg[u] >= cand));  // (absent chunks: key 0)
+        }
+        if (cnt >= q) T = cand;
+      }
+      // ---- members in ascending j: every key above T, then keys equal to T while there is room
+      int n_gt = 0;
+      for (int g = 0; g < NG; g++) {
+        if (NG > 1) {
+#pragma unroll
+          for (int u = 0; u < SEED_KREG; u++) kreg[u] = SEED_KREG * g + u < NC ? keys[64 * (SEED_KREG * g + u) + lane] : 0ull;
+        }
+#pragma unroll
+        for (int u = 0; u < SEED_KREG; u++) n_gt += __popcll(__ballot(kreg[u] > T));
+      }
+      int room = q - n_gt, pos = 0;  // wave-uniform
+      for (int c = 0; c < NC; c++) {
+        const int j = 64 * c + lane;
+        const u64 k = keys[j];
+        const u64 eqm = __ballot(k == T);
+        const int before = __popcll(eqm & ((1ull << lane) - 1ull));
+        const bool mem = k > T || (k == T && before < room);
+        const u64 mm = __ballot(mem);
+        const int at = pos + __popcll(mm & ((1ull << lane) - 1ull));
+        if (mem && at < Q) sel[at] = j, selk[at] = k;
+        const int took = __popcll(eqm);
+        room -= took < room ? took : room;
+        pos += __popcll(mm);
+      }
+      seed_wave_sync();
+      // ---- rank within the list (it is in ascending j): keys above mine, equal keys in front of me
+      for (int m0 = 0; m0 < q; m0 += 64) {
+        const int m = m0 + lane;
+        const bool mine = m < q;
+        const int jm = sel[mine ? m : 0];
+        const u64 km = selk[mine ? m : 0];
+        int rank = 0;
+#pragma unroll 8
+        for (int i = 0; i < q; i++) {
+          const u64 ki = selk[i];
+          rank += (ki > km || (ki == km && i < m)) ? 1 : 0;
+        }
+        if (mine && rank < Q) byrank[rank] = jm;
+      }
+      seed_wave_sync();
+      // ---- the q states and their digests
+      for (int idx = lane; idx < q * HW; idx += 64) {
+        const int r = idx / HW, w = idx - r * HW;
+        const int j = guard_index(byrank[r], H, a.err);
+        dst[(size_t)(slot0 + r) * HW + w] = base[w] | ((j >> 6) == w ? (0x8000000000000000ull >> (j & 63)) : 0ull);
+      }
+      if (a.dig)
+        for (int r = lane; r < q; r += 64) {
+          const int j = guard_index(byrank[r], H, a.err);
+          u64 d = 0;
+          int k = 0;
+          bool ins = false;
+          for (int i = 0; i < t - 1 && k < DIG_SLOTS; i++) {
+            const int h = sorted[i];
+            if (!ins && j < h) {
+              digest_add(d, k, j);
+              ins = true;
+            }
+            digest_add(d, k, h);
+          }
+          if (!ins) digest_add(d, k, j);
+          a.dig[(size_t)n * S + slot0 + r] = digest_close(d, t);
+        }
+      // ---- the winner joins the active set
+      const int jw = guard_index(__builtin_amdgcn_readfirstlane(byrank[0]), H, a.err);
+      const double sw = seed_unkey(seed_uniform(keys[jw]));
+      if (lane == 0) {
+        if (a.path) a.path[(size_t)n * A + t - 1] = jw;
+        if (a.lpj_path) a.lpj_path[(size_t)n * A + t - 1] = sw;
+      }
+      lpj_base = sw;
+      seed_wave_sync();  // everybody has read sorted / base / keys
+      if (lane == 0) {
+        path[t - 1] = jw;
+        int i = t - 1;  // insertion into the ascending list
+        while (i > 0 && sorted[i - 1] > jw) {
+          sorted[i] = sorted[i - 1];
+          i--;
+        }
+        sorted[i] = jw;
+        base[jw >> 6] |= 0x8000000000000000ull >> (jw & 63);
+      }
+      if (!SSSC && t < A) {
+        const double *Gw = a.G + (size_t)jw * H;  // c_j -= G_wj: e_j += 2 G_wj
+        for (int c0 = 0; c0 < NC; c0 += 8) {
+          double gw[8];
+#pragma unroll
+          for (int u = 0; u < 8; u++) {
+            const int j = 64 * (c0 + u) + lane;
+            gw[u] = (c0 + u < NC && j < H) ? Gw[j] : 0.0;
+          }
+#pragma unroll
+          for (int u = 0; u < 8; u++)
+            if (c0 + u < NC) cc[64 * (c0 + u) + lane] += 2.0 * gw[u];
+        }
+      }
+      seed_wave_sync();
+      slot0 += q;
+    }
+  }
+}

@@ -132,6 +132,21 @@ class Engine:
             tp = u8ptr(packed)
         check(self.lib.evoamd_init_states(self._h, float(p_init), int(seed) & (2 ** 64 - 1), int(max_rounds), tp))
 
+    def seed_states(self, max_active, want_path=False):
+        """K^n seeded on the device from Theta and the data by greedy forward selection on the model's own lpj
+        (evoamd_seed_states; evo_amd.variational.seed_states_host is its NumPy mirror): deterministic, ``max_active``
+        steps per datapoint, S distinct states of 1 .. max_active latents in step-major slots.  ``want_path``: returns
+        (path int32 (N, max_active), lpj_path (N, max_active)) -- the latent added at each step and its state's lpj --
+        else None.  EvoAmdError naming the rule, with K^n left as it was, for a missing Theta, incomplete data, the
+        background unit, the float32 mode, bsc_direct or a ``max_active`` the law refuses."""
+        A = int(max_active)
+        path = lpj = None
+        if want_path:
+            path = np.empty((self.N, max(A, 1)), dtype=np.int32)
+            lpj = np.empty((self.N, max(A, 1)), dtype=np.float64)
+        check(self.lib.evoamd_seed_states(self._h, A, i32ptr(path) if want_path else None, dptr(lpj) if want_path else None))
+        return (path, lpj) if want_path else None
+
     # ---- samples from the model ------------------------------------------------------------
     def generate(self, model, N, seed, Wt, pies, mus=None, F=None, sigma=1.0, first_index=0, s=None,
                  keep=("s", "z", "y_mean")):

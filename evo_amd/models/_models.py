@@ -315,6 +315,51 @@ class Model:
             suff["lpj"] = np.empty((N, self.S + S_perm))
         return suff
 
+    def seed_resident_states(self, model_params, my_data, parent_selection, mutation_algorithm, no_parents, no_children,
+                             no_generations, max_active=None, bitflip_prob=None, Mprime=None, permanent=None,
+                             want_path=False):
+        """``init_states`` for this rank's ``my_data`` with K^n SEEDED on the device from ``model_params`` and the data
+        (Engine.seed_states; evo_amd.variational.seed_states_host is the NumPy mirror): greedy forward selection on the
+        model's own lpj, deterministic -- the start for codes, reconstructions, predictive moments or samples from a
+        trained Theta, where Bernoulli(1 / H) states would need dozens of E-steps first.  Theta is pushed first.
+        ``max_active`` None: min(8, S, H).  Returns my_suff_stat with init_states' keys, dtypes and ``cross`` rule and
+        init_resident_states' sync_host behaviour ("ss" / "lpj" None with sync_host=False; with sync_host=True "ss" is
+        downloaded once); the lpj rows of the seeded K^n are computed on the device right away (sync_host=True: "lpj"
+        holds them), so encode(), predictive_moments() and sample_posterior() can follow without an E-step.
+        ``want_path``: self.last_seed_path = (path, lpj_path), else None.  ValueError for incomplete data, the
+        background unit and a ``max_active`` the law refuses; NotImplementedError in the float32 mode."""
+        from ..variational.utils import seed_quotas
+        N, H = my_data["y"].shape[0], self.H
+        permanent = permanent or {"background": False, "allzero": False, "singletons": False}
+        if permanent["background"]:
+            raise ValueError("seed_resident_states: the background unit is not supported")
+        if self.dtype == np.float32:
+            raise NotImplementedError("seed_resident_states is not available in the float32 mode")
+        if not self._complete(my_data):
+            raise ValueError("seed_resident_states: incomplete data (x_infr with False entries) is not supported")
+        if max_active is None:
+            max_active = min(8, self.S, H)
+        seed_quotas(self.S, H, max_active, self.model_name != "bsc")
+        S_perm = 1 if (permanent["allzero"] == 1 and permanent["singletons"] == 0) else 0
+        if Mprime is None:
+            Mprime = self.S
+        # every key but the two arrays, from the host function itself (no datapoint: no random number is drawn)
+        suff = _host_init_states(0, self.S, H, parent_selection, mutation_algorithm, no_parents, no_children,
+                                 no_generations, bitflip_prob, Mprime, None, permanent)
+        suff["ss"] = suff["lpj"] = None
+        eng = self._prepare(suff, my_data, upload_states=False)
+        # (the precompute stores its derived keys and zeroes the reset counters: on shallow copies here)
+        self.E_step_precompute(dict(model_params), dict(suff), my_data)
+        if model_params is not self._dev_theta:
+            self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
+        self.last_seed_path = eng.seed_states(max_active, want_path=want_path)
+        self._resident = True
+        eng.lpj_resident()
+        if self.sync_host:
+            suff["ss"] = eng.download_states()
+            suff["lpj"] = eng.download_lpj()
+        return suff
+
     def _prepare(self, my_suff_stat, my_data, upload_states=True):
         """Configure the engine for this rank's shard and make Y / K^n resident."""
         Y = my_data["y"]

@@ -219,3 +219,118 @@ def init_states_counter(N, S, H, seed, p_init_Kn=None, permanent=None, max_round
     Hv = H - 1 if background else H
     p0 = 1.0 / H if p_init_Kn is None else p_init_Kn
     return assemble_states(N, S, H, counter_draw(seed, S, Hv, p0), permanent, max_rounds)
+
+
+# ---- K^n seeded from Theta and the data: the NumPy mirror of evoamd_seed_states (csrc/kernels_seed.hpp) ------------------
+#
+# Greedy forward selection on the model's own lpj (without ljc, without the lpj_reset_check clamp).  Per datapoint, with
+# A = max_active steps, A_0 = {} and quotas q_t = S // A + (t <= S % A): step t scores every latent j outside A_{t-1} with
+# lpj(A_{t-1} + {j}), ranks by descending score (ties: ascending j; a score that is not finite, or an ES3C det T that is not
+# positive, is -inf), writes the q_t best states to the next q_t slots in rank order and keeps the best as A_t.
+SEED_MAX_ACTIVE = {"bsc": 64, "sssc": 8}
+
+
+def seed_quotas(S, Hv, max_active, sssc):
+    """The quotas q_1 .. q_A of the seeding law; ValueError naming the rule for a ``max_active`` the law refuses."""
+    A, cap = int(max_active), SEED_MAX_ACTIVE["sssc" if sssc else "bsc"]
+    if A < 1 or A > S or A > Hv or A > cap:
+        raise ValueError("seed_states: max_active = %d must be in [1, min(S = %d, Hv = %d, %d)] (%s)"
+                         % (A, S, Hv, cap, "ES3C: at most 8" if sssc else "EBSC: at most 64"))
+    q = [S // A + (1 if t <= S % A else 0) for t in range(1, A + 1)]
+    for t, qt in enumerate(q, start=1):
+        if qt > Hv - (t - 1):
+            raise ValueError("seed_states: the quota q_%d = %d exceeds the Hv - (t - 1) = %d latents left at step %d "
+                             "(S = %d, max_active = %d)" % (t, qt, Hv - (t - 1), t, S, A))
+    return q
+
+
+def _seed_scores_sssc(G, Psi, mus, pil_bar, s2inv, b_n, yy_n, active, cand):
+    """ES3C lpj of active + [j] for every j of ``cand`` (the quantities of models/predictive.py: state_posterior_es3c)."""
+    k = len(active) + 1
+    idx = np.empty((len(cand), k), dtype=np.intp)
+    idx[:, :k - 1] = active
+    idx[:, k - 1] = cand
+    Gb = G[idx[:, :, None], idx[:, None, :]]
+    Pb = Psi[idx[:, :, None], idx[:, None, :]]
+    mu, b = mus[idx], b_n[idx]
+    v = b - np.einsum("cij,cj->ci", Gb, mu)
+    rr = yy_n - (mu * (b + v)).sum(axis=1)
+    T = np.eye(k)[None] + Pb @ Gb * s2inv
+    rhs = np.einsum("cij,cj->ci", Pb, v)
+    sign, logdet = np.linalg.slogdet(T)
+    try:
+        x = np.linalg.solve(T, rhs[:, :, None])[:, :, 0]
+    except np.linalg.LinAlgError:  # an exactly singular system among them: one by one
+        x = np.full_like(rhs, np.nan)
+        for c in range(len(cand)):
+            try:
+                x[c] = np.linalg.solve(T[c], rhs[c])
+            except np.linalg.LinAlgError:
+                pass
+    with np.errstate(invalid="ignore", over="ignore"):
+        lpj = pil_bar[idx].sum(axis=1) - 0.5 * (logdet + rr * s2inv - (v * x).sum(axis=1) * s2inv * s2inv)
+    return np.where((sign > 0) & np.isfinite(lpj), lpj, -np.inf)
+
+
+def _seed_gap(a, b):
+    if not (np.isfinite(a) and np.isfinite(b)):
+        return np.inf  # -inf ranks last and among themselves by j: nothing a rounding error decides
+    return (a - b) / max(1.0, abs(a))
+
+
+def seed_states_host(model, theta, Y, S, max_active, S_perm=0):
+    """K^n as evoamd_seed_states / Model.seed_resident_states lay it out.  ``model``: "bsc" or "sssc"; ``theta``: W, pi,
+    sigma (EBSC) or W, pies, mus, Psi, sigma2 (ES3C); ``Y`` (N, D) complete data; ``S`` varying states per datapoint (the
+    permanent all-zero state of ``S_perm`` = 1 is not among them and is never produced).  Returns (states, path,
+    lpj_path, margin): states bool (N, S, H); path int32 (N, A), the latent added at each step; lpj_path (N, A), the
+    winner's score; margin (N,), the smallest relative gap (a - b) / max(1, |a|) over the steps of a datapoint between
+    the winner and the runner-up and between rank q_t - 1 and rank q_t -- a datapoint whose margin is far above the
+    rounding error of the scores is decided the same way by any correct implementation."""
+    sssc = model not in ("bsc", "BSC", "ebsc")
+    assert S_perm in (0, 1)
+    W = np.asarray(theta["W"], dtype=np.float64)
+    Y = np.asarray(Y, dtype=np.float64)
+    (D, H), N = W.shape, Y.shape[0]
+    assert Y.shape == (N, D)
+    A = int(max_active)
+    quotas = seed_quotas(int(S), H, A, sssc)
+    G, B, yy = W.T @ W, Y @ W, (Y * Y).sum(axis=1)
+    if sssc:
+        mus, Psi = np.asarray(theta["mus"], dtype=np.float64), np.asarray(theta["Psi"], dtype=np.float64)
+        pies = np.asarray(theta["pies"], dtype=np.float64)
+        pil_bar, s2inv = np.log(pies / (1.0 - pies)), 1.0 / float(theta["sigma2"])
+    else:
+        pi, sigma = float(theta["pi"]), float(theta["sigma"])
+        pre1, pil_bar, Gd = -1.0 / 2.0 / sigma / sigma, np.log(pi / (1.0 - pi)), np.diag(G).copy()
+    states = np.zeros((N, S, H), dtype=bool)
+    path = np.zeros((N, A), dtype=np.int32)
+    lpj_path = np.zeros((N, A))
+    margin = np.full(N, np.inf)
+    for n in range(N):
+        active, free = [], np.ones(H, dtype=bool)
+        c, base, slot = B[n].copy(), (0.0 if sssc else pre1 * yy[n]), 0
+        for t, q in enumerate(quotas, start=1):
+            cand = np.flatnonzero(free)
+            if sssc:
+                score = _seed_scores_sssc(G, Psi, mus, pil_bar, s2inv, B[n], yy[n], active, cand)
+            else:
+                with np.errstate(invalid="ignore", over="ignore"):
+                    score = base + pil_bar + pre1 * (Gd[cand] - 2.0 * c[cand])
+                score = np.where(np.isfinite(score), score, -np.inf)
+            order = np.lexsort((cand, -score))  # descending score, ties (and the -inf ones) by ascending j
+            ranked, sc = cand[order], score[order]
+            if len(sc) > 1:
+                margin[n] = min(margin[n], _seed_gap(sc[0], sc[1]))
+            if q < len(sc):
+                margin[n] = min(margin[n], _seed_gap(sc[q - 1], sc[q]))
+            for r in range(q):
+                states[n, slot + r, active] = True
+                states[n, slot + r, ranked[r]] = True
+            jw = int(ranked[0])
+            path[n, t - 1], lpj_path[n, t - 1] = jw, sc[0]
+            active.append(jw)
+            free[jw] = False
+            c -= G[jw]
+            base = sc[0]
+            slot += q
+    return states, path, lpj_path, margin

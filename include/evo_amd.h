@@ -240,6 +240,21 @@ int evoamd_download_states_packed(evoamd_ctx *ctx, uint8_t *packed, int64_t n0, 
  * (default), 0, 1): a wavefront keeps the round's candidates and the held set in LDS / in a slot of global memory
  * (automatic: LDS whenever 16 S (ceil(H/64) + 1) bytes fit one wavefront's share); same results, for tests. */
 int evoamd_init_states(evoamd_ctx *ctx, double p_init, uint64_t seed, int max_rounds, const uint8_t *table_packed);
+/* K^n seeded from Theta and the data: greedy forward selection on the model's own lpj (csrc/kernels_seed.hpp has the
+ * law; evo_amd.variational.seed_states_host is its NumPy mirror).  Deterministic, no random numbers.  Per datapoint,
+ * max_active = A steps with quotas q_t = S / A + (t <= S mod A): step t scores every latent j outside the active set
+ * A_{t-1} with lpj(A_{t-1} + {j}) -- what evoamd_lpj_resident computes before its clamp, without ljc; not finite, or an
+ * ES3C determinant that is not positive: -inf -- ranks them by descending score (ties and -inf: ascending j), writes the
+ * q_t best states to the next q_t slots in rank order and keeps the best as A_t.  The S varying slots are filled
+ * step-major with S distinct states of sizes 1 .. A; the permanent all-zero state of S_perm = 1 keeps its own column.
+ * path_out (N, A): the latent added at each step; lpj_out (N, A): the winner's score; either may be NULL.
+ * Refused with EVOAMD_E_INVALID before anything is written (K^n and its validity stay as they were): no Theta installed
+ * or no data, incomplete data (masks present), option "background_unit", "ebsc_f32", "bsc_direct" (there is no G),
+ * max_active < 1, > S, > H, > 8 (ES3C) or > 64 (EBSC), a quota q_t > H - (t - 1), or an H whose scores do not fit one
+ * wavefront's share of LDS (16 H bytes; about H = 9000).  Incomplete data and the background unit are out of scope.
+ * Like evoamd_init_states it writes the digests too; a prefetched pass, the census and the statistics rows are dropped
+ * and the lpj rows on the device no longer belong to K^n afterwards. */
+int evoamd_seed_states(evoamd_ctx *ctx, int max_active, int32_t *path_out, double *lpj_out);
 /* my_suff_stat["lpj"] (N,S_perm+S) float64. */
 int evoamd_upload_lpj(evoamd_ctx *ctx, const double *lpj);
 int evoamd_download_lpj(evoamd_ctx *ctx, double *lpj);
@@ -630,7 +645,8 @@ enum {
   EVOAMD_K_PATCHES = 21,       /* evoamd_patches_extract / evoamd_patches_merge kernels (transfers excluded) */
   EVOAMD_K_INIT_STATES = 22,   /* evoamd_init_states: the K^n(0) sampler */
   EVOAMD_K_POSTERIOR_SAMPLE = 23, /* evoamd_posterior_sample: W^T and the sampling kernel (transfers excluded) */
-  EVOAMD_K_COUNT = 24
+  EVOAMD_K_SEED_STATES = 24,   /* evoamd_seed_states: the greedy K^n seeding kernel (B = Y W and transfers excluded) */
+  EVOAMD_K_COUNT = 25
 };
 /* on = bit mask of kernel classes to time (bit k = class k; -1 = all, 0 = off).  Each timed span
  * records two HIP events on the compute stream, which costs about 10 us of stream time per span:
