@@ -118,6 +118,8 @@ SIGNATURES = {
     "evoamd_download_predictive": (_I, [_vp, _c_dp, _c_dp]),
     "evoamd_posterior_sample": (_I, [_vp, _I, _U64, _U64, _I, _I, _I, ctypes.POINTER(_I64)]),
     "evoamd_download_posterior_samples": (_I, [_vp, _I, _vp]),
+    "evoamd_patches_merge_samples": (_I, [_vp, _I, _I, _I, _I, _I, _I, _I, _I, _I, _c_dp, _c_dp, _c_dp]),
+    "evoamd_patches_merge_predictive": (_I, [_vp, _I, _I, _I, _I, _I, _I, _I, _c_dp]),
     "evoamd_generate": (_I, [_vp, _I, _I64, _I, _I, _U64, _U64, _c_dp, _c_dp, _c_dp, _c_dp, _DBL, _c_u64p, _I]),
     "evoamd_download_generated": (_I, [_vp, _I, _vp]),
     "evoamd_comm_unique_id": (_I, [_c_u8p]),

@@ -4726,32 +4726,38 @@ extern "C" int evoamd_patches_extract(evoamd_ctx *c, const double *img, int H, i
 }
 
 // The merge kernels over the estimates `src` serves (PatchRows: dense device rows; PatchSelect: the resident selected
-// reconstruction), into c->patch_img, then the image to the host.  c->patch_img holds img_n doubles.
+// reconstruction; PatchDrawRows: the resident posterior draws, one per grid row) into `out` on the device: n_img images of
+// img_n doubles, image i from grid row i.  Enqueues only.
 template <class Src>
-static int launch_patches_merge(evoamd_ctx *c, const Src &src, const PatchGeom &g, int method, double *img_out) {
+static void enqueue_patches_merge(evoamd_ctx *c, const Src &src, const PatchGeom &g, int method, double *out, unsigned n_img) {
   const size_t img_n = (size_t)g.H * g.W * g.C;
-  {
-    SpanGuard sg(c, KID_PATCHES);
-    if (method == 0) {
-      patches_mean_kernel<<<cdiv((i64)img_n, 256), 256, 0, c->stream>>>(src, g, c->patch_img);
+  SpanGuard sg(c, KID_PATCHES);
+  if (method == 0) {
+    patches_mean_kernel<<<dim3(cdiv((i64)img_n, 256), n_img), 256, 0, c->stream>>>(src, g, out);
+  } else {
+    const int K = patch_max_cover(g);  // <= ph * pw <= 1024
+    int P = 1;
+    while (P < K) P <<= 1;
+    if (P <= 64) {
+      const i64 waves = ((i64)img_n + 64 / P - 1) / (64 / P);
+      patches_median_kernel<1><<<dim3(cdiv(waves, 4), n_img), 256, 0, c->stream>>>(src, g, P, out);
     } else {
-      const int K = patch_max_cover(g);  // <= ph * pw <= 1024
-      int P = 1;
-      while (P < K) P <<= 1;
-      if (P <= 64) {
-        const i64 waves = ((i64)img_n + 64 / P - 1) / (64 / P);
-        patches_median_kernel<1><<<cdiv(waves, 4), 256, 0, c->stream>>>(src, g, P, c->patch_img);
-      } else {
-        const unsigned blocks = cdiv((i64)img_n, 4);  // one wave per output element
-        switch (P) {
-          case 128: patches_median_kernel<2><<<blocks, 256, 0, c->stream>>>(src, g, P, c->patch_img); break;
-          case 256: patches_median_kernel<4><<<blocks, 256, 0, c->stream>>>(src, g, P, c->patch_img); break;
-          case 512: patches_median_kernel<8><<<blocks, 256, 0, c->stream>>>(src, g, P, c->patch_img); break;
-          default: patches_median_kernel<16><<<blocks, 256, 0, c->stream>>>(src, g, P, c->patch_img); break;
-        }
+      const dim3 blocks(cdiv((i64)img_n, 4), n_img);  // one wave per output element
+      switch (P) {
+        case 128: patches_median_kernel<2><<<blocks, 256, 0, c->stream>>>(src, g, P, out); break;
+        case 256: patches_median_kernel<4><<<blocks, 256, 0, c->stream>>>(src, g, P, out); break;
+        case 512: patches_median_kernel<8><<<blocks, 256, 0, c->stream>>>(src, g, P, out); break;
+        default: patches_median_kernel<16><<<blocks, 256, 0, c->stream>>>(src, g, P, out); break;
       }
     }
   }
+}
+
+// One image into c->patch_img (which holds img_n doubles), then to the host.
+template <class Src>
+static int launch_patches_merge(evoamd_ctx *c, const Src &src, const PatchGeom &g, int method, double *img_out) {
+  const size_t img_n = (size_t)g.H * g.W * g.C;
+  enqueue_patches_merge(c, src, g, method, c->patch_img.get(), 1);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(img_out, c->patch_img, img_n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -4878,6 +4884,82 @@ extern "C" int evoamd_patches_merge_resident(evoamd_ctx *c, int H, int W, int C,
   }
   HIP_TRY(hipGetLastError());
   return launch_patches_merge(c, PatchRows{c->patch_Y}, g, method, img_out);
+}
+
+// ---- merges of what evoamd_posterior_sample / evoamd_predictive_moments left on the device ----
+// Nothing of the EM state or its validity flags is touched; the images go through the patch scratch.
+extern "C" int evoamd_patches_merge_samples(evoamd_ctx *c, int H, int W, int C, int ph, int pw, int shift, int method, int t0,
+                                            int n_draws, double *imgs_out, double *mean_out, double *std_out) {
+  REQUIRE(c, "evoamd_patches_merge_samples: ctx is NULL");
+  REQUIRE(imgs_out || mean_out || std_out, "evoamd_patches_merge_samples: imgs_out, mean_out and std_out are all NULL");
+  PatchGeom g;
+  if (const char *msg = patch_geom_make(H, W, C, ph, pw, shift, &g)) return fail(EVOAMD_E_INVALID, "evoamd_patches_merge_samples: %s", msg);
+  REQUIRE(method == 0 || method == 1, "evoamd_patches_merge_samples: method must be 0 (mean) or 1 (median)");
+  REQUIRE(c->configured && c->ps_keep >= 0 && c->ps_N == c->N && c->ps_D == c->D,
+          "evoamd_patches_merge_samples: no draws on the device (call evoamd_posterior_sample first; a failed call and "
+          "evoamd_configure leave none)");
+  REQUIRE(c->ps_keep & PSAMP_KEEP_Y, "evoamd_patches_merge_samples: the last evoamd_posterior_sample did not keep y");
+  if (g.N != c->ps_N || g.D != c->ps_D)
+    return fail(EVOAMD_E_INVALID, "evoamd_patches_merge_samples: the patch geometry is (N, D) = (%lld, %d), the draws are (%lld, %d)",
+                (long long)g.N, g.D, (long long)c->ps_N, c->ps_D);
+  if (t0 < 0 || n_draws < 1 || (i64)t0 + n_draws > c->ps_T)
+    return fail(EVOAMD_E_INVALID, "evoamd_patches_merge_samples: draws %d .. %lld asked for, the last call made T = %lld",
+                t0, (long long)t0 + n_draws - 1, (long long)c->ps_T);
+  REQUIRE(n_draws <= 65535, "evoamd_patches_merge_samples: at most 65535 draws per call");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t img_n = (size_t)H * W * C;
+  const bool moments = mean_out || std_out;
+  // scratch: [the n images, where they are stored | mean | std]; the mean merger forms the moments without storing images
+  const bool store = imgs_out || method == 1;
+  const size_t n_store = store ? (size_t)n_draws * img_n : 0;
+  TRY(c->patch_img.ensure(c, n_store + 2 * img_n));
+  double *imgs = store ? c->patch_img.get() : nullptr;
+  double *d_mean = c->patch_img.get() + n_store, *d_std = d_mean + img_n;
+  if (method == 0) {
+    SpanGuard sg(c, KID_PATCHES);
+    patches_mean_draws_kernel<<<cdiv((i64)img_n, 256), 256, 0, c->stream>>>(c->ps_y, c->ps_T, t0, n_draws, g, imgs,
+                                                                            mean_out ? d_mean : nullptr, std_out ? d_std : nullptr);
+  } else {
+    enqueue_patches_merge(c, PatchDrawRows{c->ps_y, c->ps_T, t0}, g, 1, imgs, (unsigned)n_draws);
+    if (moments) {
+      SpanGuard sg(c, KID_PATCHES);
+      patches_moments_kernel<<<cdiv((i64)img_n, 256), 256, 0, c->stream>>>(imgs, n_draws, (i64)img_n, mean_out ? d_mean : nullptr,
+                                                                           std_out ? d_std : nullptr);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  if (imgs_out) HIP_TRY(hipMemcpyAsync(imgs_out, imgs, n_store * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (mean_out) HIP_TRY(hipMemcpyAsync(mean_out, d_mean, img_n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (std_out) HIP_TRY(hipMemcpyAsync(std_out, d_std, img_n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+extern "C" int evoamd_patches_merge_predictive(evoamd_ctx *c, int H, int W, int C, int ph, int pw, int shift, int what,
+                                               double *img_out) {
+  REQUIRE(c && img_out, "evoamd_patches_merge_predictive: NULL argument");
+  PatchGeom g;
+  if (const char *msg = patch_geom_make(H, W, C, ph, pw, shift, &g)) return fail(EVOAMD_E_INVALID, "evoamd_patches_merge_predictive: %s", msg);
+  REQUIRE(what >= 0 && what <= 3, "evoamd_patches_merge_predictive: what must be 0 (mean of mean), 1 (median of mean), 2 (precision) or 3 (mean of var)");
+  REQUIRE(c->configured && c->pred_N > 0 && c->pred_N == c->N && c->pred_D == c->D,
+          "evoamd_patches_merge_predictive: no moments on the device (call evoamd_predictive_moments first; a failed call and "
+          "evoamd_configure leave none)");
+  if (g.N != c->pred_N || g.D != c->pred_D)
+    return fail(EVOAMD_E_INVALID, "evoamd_patches_merge_predictive: the patch geometry is (N, D) = (%lld, %d), the moments are (%lld, %d)",
+                (long long)g.N, g.D, (long long)c->pred_N, c->pred_D);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t img_n = (size_t)H * W * C, nd = (size_t)c->pred_N * c->pred_D;
+  TRY(c->patch_img.ensure(c, img_n));
+  const PatchRows mean{c->pred_buf.get()}, var{c->pred_buf.get() + nd};
+  if (what != 2) return launch_patches_merge(c, what == 3 ? var : mean, g, what == 1 ? 1 : 0, img_out);
+  {
+    SpanGuard sg(c, KID_PATCHES);
+    patches_wmean_kernel<<<cdiv((i64)img_n, 256), 256, 0, c->stream>>>(mean, var, g, c->patch_img);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(img_out, c->patch_img, img_n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 // ---- posterior code readout (kernels_codes.hpp) ----

@@ -89,6 +89,17 @@ __global__ void __launch_bounds__(256) patches_extract_kernel(const double *__re
 struct PatchRows {
   const double *__restrict__ Y;
   __device__ __forceinline__ double load(i64 n, int d, int D) const { return Y[n * D + d]; }
+  __device__ __forceinline__ i64 image() const { return 0; }  // which image of `out` this launch row (blockIdx.y) writes
+};
+// PatchDrawRows: the draws the last evoamd_posterior_sample kept, y (N, T, D), read where they lie: grid row blockIdx.y
+// of a launch merges draw t0 + blockIdx.y into image blockIdx.y (one row: one draw).  The arithmetic of a merge of the
+// dense (N, D) slice y[:, t, :], hence its bits; only the address differs.
+struct PatchDrawRows {
+  const double *__restrict__ y;
+  i64 T;
+  int t0;
+  __device__ __forceinline__ double load(i64 n, int d, int D) const { return y[(n * T + t0 + blockIdx.y) * D + d]; }
+  __device__ __forceinline__ i64 image() const { return blockIdx.y; }
 };
 // PatchSelect: the selected reconstruction of a configured context, formed while it is gathered (evoamd_reconstruct_resident):
 //   complete data    x[n, d] ? Y[n, d] : y_hat[n, d]   (x == NULL: y_hat everywhere); rec = y_hat, infr == NULL
@@ -111,6 +122,7 @@ struct PatchSelect {
     }
     return (x && x[e]) ? Y[n * ldY + d] : rec[e];
   }
+  __device__ __forceinline__ i64 image() const { return 0; }
 };
 
 // The estimate of pixel (y, x, c) held by patch (ir, ic).
@@ -165,7 +177,72 @@ __global__ void __launch_bounds__(256) patches_mean_kernel(Src src, PatchGeom g,
         cnt++;
       }
     }
-  out[e] = cnt ? sum / (double)cnt : __builtin_nan("");
+  out[src.image() * total + e] = cnt ? sum / (double)cnt : __builtin_nan("");
+}
+
+// Mean merge of draws t0 .. t0 + n - 1 of y (N, T, D) in one launch, and the pixelwise moments over the merged images.
+// One thread per output element, as in patches_mean_kernel: the cover of the pixel is computed once for all draws, and the
+// draws run one after the other in an inner loop, so that at any moment the whole grid gathers from ONE draw -- a slice
+// of N D doubles, which the caches hold, as in a merge of dense rows.  Draws side by side (in grid rows, or several per
+// thread in registers) were measured slower per draw, up to 3 times.  Every element of y is read once.
+//   image t   sum over the covering patches in increasing n, NaN skipped, divided by the count; none valid: NaN -- the
+//             operations of patches_mean_kernel in its order.  Stored when imgs != NULL: imgs (n, H, W, C).
+//   moments   Welford over the images in draw order from mean = 0, M2 = 0: delta = x_t - mean, mean += delta / t,
+//             M2 += delta (x_t - mean); mean_out = mean, std_out = sqrt(M2 / n) (ddof 0).  A NaN image makes both NaN;
+//             identical images give their value and exactly 0 (evo_amd.utils.prepost.image_moments_host is the mirror).
+//             Either may be NULL.
+__global__ void __launch_bounds__(256) patches_mean_draws_kernel(const double *__restrict__ y, i64 T, int t0, int n, PatchGeom g,
+                                                                 double *__restrict__ imgs, double *__restrict__ mean_out,
+                                                                 double *__restrict__ std_out) {
+#pragma clang fp contract(off)
+  const i64 total = (i64)g.H * g.W * g.C;
+  const i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const int c = (int)(e % g.C);
+  const i64 px = e / g.C;
+  const int py = (int)(px / g.W), x = (int)(px - (i64)py * g.W);
+  int r0, r1, c0, c1;
+  patch_cover(py, g.H, g.ph, g.s, g.nr, r0, r1);
+  patch_cover(x, g.W, g.pw, g.s, g.nc, c0, c1);
+  double mean = 0.0, M2 = 0.0;
+  for (int t = 0; t < n; t++) {
+    const PatchDrawRows src{y, T, t0 + t};
+    double sum = 0.0;
+    int cnt = 0;
+    for (int ir = r0; ir <= r1; ir++)
+      for (int ic = c0; ic <= c1; ic++) {
+        const double v = patch_estimate(src, g, ir, ic, py, x, c);
+        if (v == v) {
+          sum += v;
+          cnt++;
+        }
+      }
+    const double v = cnt ? sum / (double)cnt : __builtin_nan("");
+    if (imgs) imgs[(i64)t * total + e] = v;
+    const double delta = v - mean;
+    mean += delta / (double)(t + 1);
+    M2 += delta * (v - mean);
+  }
+  if (mean_out) mean_out[e] = mean;
+  if (std_out) std_out[e] = sqrt(M2 / (double)n);
+}
+
+// The same moments over n images (n, total) already on the device (the median merge of draws leaves them there): one
+// thread per output element, Welford in draw order as above.
+__global__ void __launch_bounds__(256) patches_moments_kernel(const double *__restrict__ imgs, int n, i64 total,
+                                                              double *__restrict__ mean_out, double *__restrict__ std_out) {
+#pragma clang fp contract(off)
+  const i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  double mean = 0.0, M2 = 0.0;
+  for (int t = 0; t < n; t++) {
+    const double v = imgs[(i64)t * total + e];
+    const double delta = v - mean;
+    mean += delta / (double)(t + 1);
+    M2 += delta * (v - mean);
+  }
+  if (mean_out) mean_out[e] = mean;
+  if (std_out) std_out[e] = sqrt(M2 / (double)n);
 }
 
 // Precision-weighted mean merge: out = (sum_k e_k w_k) / (sum_k w_k), w_k = 1 / v_k, over the covering patches in
@@ -292,6 +369,6 @@ __global__ void __launch_bounds__(256) patches_median_kernel(Src src, PatchGeom 
       m = lo;
     else
       m = (lo + hi) / 2.0;
-    out[e] = m;
+    out[src.image() * total + e] = m;
   }
 }

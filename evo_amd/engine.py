@@ -46,6 +46,8 @@ class Engine:
         self._configures = 0  # evoamd_configure calls: a keep-mask uploaded for an earlier geometry is gone
         self._keep_token = None  # (x object, geometry, _configures, any(x)) of the keep-mask on the device
         self._rec_serial = 0     # counts reconstruct_resident calls: names the reconstruction the device holds
+        self._ps_serial = 0      # counts sample_posterior calls (and configures): names the draws the device holds
+        self._pred_serial = 0    # the same for predictive_moments
 
     # ---- lifetime ------------------------------------------------------------------------
     def close(self):
@@ -83,6 +85,8 @@ class Engine:
         self.L = self.S + self.S_perm
         self.has_masks = False  # evoamd_configure drops the masks of the previous geometry
         self._configures += 1
+        self._ps_serial += 1    # ... and releases the draws and moments of the previous geometry
+        self._pred_serial += 1
 
     def same_geometry(self, model, N, D, H, S, S_perm, Cmax):
         m = MODEL_BSC if model in (MODEL_BSC, "bsc", "BSC") else MODEL_SSSC
@@ -566,29 +570,69 @@ class Engine:
         return Es, Ez
 
     # ---- predictive uncertainty (evo_amd.models.predictive is the NumPy mirror) -----------------
-    def predictive_moments(self, noise=True, want_mean=True, want_var=True):
+    def predictive_moments(self, noise=True, want_mean=True, want_var=True, resident=False):
         """Posterior-predictive mean and variance of every entry under the Theta, K^n and lpj rows on the device
         (evoamd_predictive_moments; no statistics pass runs and the EM state stays as it is).  Returns (mean, var, info):
         float64 (N, D) arrays (None where not wanted) and info = {"n_singular", "n_skipped"}, the datapoints whose rows are
         NaN because a k x k system is singular / because they have no reliable entry.  EvoAmdError naming n and k for a
-        state with more than 32 active latents, and for D > 512; nothing is downloaded then."""
+        state with more than 32 active latents, and for D > 512; nothing is downloaded then.  ``resident=True``: nothing
+        is downloaded at all; mean and var are ResidentMoments handles of the buffers on the device
+        (patches_merge_predictive merges them there) until the next call."""
         counters = (ctypes.c_int64 * 2)()
+        self._pred_serial += 1  # (before the call: a failed one leaves nothing either)
         check(self.lib.evoamd_predictive_moments(self._h, 1 if noise else 0, counters))
+        info = {"n_singular": int(counters[0]), "n_skipped": int(counters[1])}
+        if resident:
+            from .resident import ResidentMoments
+            mean = ResidentMoments(self, self._pred_serial, (self.N, self.D), "mean")
+            return (mean if want_mean else None), (mean.sibling("var") if want_var else None), info
         mean = np.empty((self.N, self.D)) if want_mean else None
         var = np.empty((self.N, self.D)) if want_var else None
         check(self.lib.evoamd_download_predictive(self._h, None if mean is None else dptr(mean),
                                                   None if var is None else dptr(var)))
-        return mean, var, {"n_singular": int(counters[0]), "n_skipped": int(counters[1])}
+        return mean, var, info
+
+    def _check_result_serial(self, kind, serial, what):
+        if serial is not None and serial != getattr(self, kind):
+            raise EvoAmdError("the %s on the device are newer ones (a later call or a configure)" % what)
+
+    def download_predictive(self, which, shape=None, serial=None):
+        """The (N, D) "mean" or "var" the last predictive_moments left on the device; EvoAmdError once they are gone."""
+        self._check_result_serial("_pred_serial", serial, "predictive moments")
+        out = np.empty((self.N, self.D) if shape is None else tuple(shape))
+        if out.shape != (self.N, self.D):
+            raise EvoAmdError("the predictive moments on the device belong to another geometry")
+        check(self.lib.evoamd_download_predictive(self._h, dptr(out) if which == "mean" else None,
+                                                  dptr(out) if which == "var" else None))
+        return out
+
+    def patches_merge_predictive(self, shape, ph, pw, shift=1, what=2, serial=None):
+        """The image merged from the moments the last predictive_moments left on the device (evoamd_patches_merge_predictive):
+        ``what`` 0 mean-merge of mean, 1 median-merge of mean, 2 precision-weighted merge of mean by var, 3 mean-merge of
+        var.  Only the image crosses to the host.  The geometry must give (N, D) of the moments (ValueError)."""
+        from .utils.prepost import patch_geometry
+        H, W, C = _image_hwc(shape)
+        N, D = patch_geometry(H, W, C, ph, pw, shift)
+        if (N, D) != (self.N, self.D):
+            raise ValueError("patches_merge_predictive: the geometry needs (%d, %d), the moments are (%d, %d)"
+                             % (N, D, self.N, self.D))
+        self._check_result_serial("_pred_serial", serial, "predictive moments")
+        out = np.empty(tuple(shape), dtype=np.float64)
+        check(self.lib.evoamd_patches_merge_predictive(self._h, H, W, C, int(ph), int(pw), int(shift), int(what), dptr(out)))
+        return out
 
     # ---- posterior samples (evo_amd.models.posterior_sample is the NumPy mirror) -----------------
-    def sample_posterior(self, n_samples=1, seed=0, first_index=0, keep=("slot", "s", "z", "y"), fill="missing", noise=True):
+    def sample_posterior(self, n_samples=1, seed=0, first_index=0, keep=("slot", "s", "z", "y"), fill="missing", noise=True,
+                         resident=False):
         """``n_samples`` draws per datapoint from the variational posterior under the Theta, K^n and lpj rows on the device
         (evoamd_posterior_sample; no statistics pass runs and the EM state stays as it is).  Returns a dict with the arrays
         ``keep`` names -- "slot" int32 (N, T), "s" bool (N, T, H), "z" float64 (N, T, H; ES3C only), "y" float64 (N, T, D)
         -- and "info" = {"n_singular", "n_skipped", "n_not_pd", "n_bad_weights"}: the datapoints without draws (slot -1,
         s zero, z and y NaN).  Only the arrays named are allocated, written and downloaded.  EvoAmdError naming n and k
         for a state with more than 32 active latents, for D > 512, for "z" with EBSC, and -- naming the bytes -- for
-        outputs that do not fit into the free device memory; nothing is downloaded then."""
+        outputs that do not fit into the free device memory; nothing is downloaded then.  ``resident=True`` (``keep`` must
+        name "y"): "y" is not downloaded; the entry is a ResidentDraws handle of the buffer on the device
+        (patches_merge_samples merges the draws there) until the next call."""
         from .models.generate import unpack_words
         if fill not in ("missing", "all"):
             raise ValueError("fill must be 'missing' or 'all'")
@@ -598,8 +642,11 @@ class Engine:
             if name not in _lib.PSAMP_KEEP:
                 raise ValueError("keep: unknown output %r" % (name,))
             bits |= _lib.PSAMP_KEEP[name]
+        if resident and "y" not in keep:
+            raise ValueError("resident=True keeps the draws \"y\" on the device: keep must name \"y\"")
         T = int(n_samples)
         counters = (ctypes.c_int64 * 4)()
+        self._ps_serial += 1  # (before the call: a failed one leaves nothing either)
         check(self.lib.evoamd_posterior_sample(self._h, T, int(seed) & (2 ** 64 - 1), int(first_index) & (2 ** 64 - 1), bits,
                                                1 if fill == "all" else 0, 1 if noise else 0, counters))
         N, D, H = self.N, self.D, self.H
@@ -607,12 +654,47 @@ class Engine:
                   "y": ((N, T, D), np.float64)}
         out = {}
         for name in ("slot", "s", "z", "y"):
-            if name in keep:
+            if name == "y" and resident and name in keep:
+                from .resident import ResidentDraws
+                out[name] = ResidentDraws(self, self._ps_serial, (N, T, D))
+            elif name in keep:
                 a = np.empty(*shapes[name])
                 check(self.lib.evoamd_download_posterior_samples(self._h, _lib.PSAMP_WHAT[name], a.ctypes.data_as(ctypes.c_void_p)))
                 out[name] = unpack_words(a, H).reshape(N, T, H) if name == "s" else a
         out["info"] = dict(zip(("n_singular", "n_skipped", "n_not_pd", "n_bad_weights"), (int(v) for v in counters)))
         return out
+
+    def download_posterior_draws(self, T, serial=None):
+        """The (N, T, D) draws "y" the last sample_posterior left on the device; EvoAmdError once they are gone."""
+        self._check_result_serial("_ps_serial", serial, "posterior draws")
+        a = np.empty((self.N, int(T), self.D))
+        check(self.lib.evoamd_download_posterior_samples(self._h, _lib.PSAMP_WHAT["y"], a.ctypes.data_as(ctypes.c_void_p)))
+        return a
+
+    def patches_merge_samples(self, shape, ph, pw, shift=1, method="mean", t0=0, n_draws=1, images=True, moments=False,
+                              serial=None):
+        """Merge draws t0 .. t0 + n_draws - 1 of the "y" the last sample_posterior left on the device into images
+        (evoamd_patches_merge_samples: one launch for all of them).  Returns (imgs, mean, std): imgs (n_draws, *shape)
+        when ``images``, mean / std of ``shape`` -- the pixelwise Welford moments over the merged images, ddof 0 -- when
+        ``moments``; None for what was not asked for.  Only these arrays cross to the host.  The geometry must give
+        (N, D) of the draws (ValueError)."""
+        from .utils.prepost import patch_geometry
+        H, W, C = _image_hwc(shape)
+        N, D = patch_geometry(H, W, C, ph, pw, shift)
+        if (N, D) != (self.N, self.D):
+            raise ValueError("patches_merge_samples: the geometry needs (%d, %d), the draws are (%d, %d) per draw"
+                             % (N, D, self.N, self.D))
+        if not (images or moments):
+            raise ValueError("patches_merge_samples: ask for the images, the moments or both")
+        self._check_result_serial("_ps_serial", serial, "posterior draws")
+        m = {"mean": 0, "median": 1}[method]
+        imgs = np.empty((int(n_draws),) + tuple(shape)) if images and int(n_draws) >= 1 else None
+        mean = np.empty(tuple(shape)) if moments else None
+        std = np.empty(tuple(shape)) if moments else None
+        check(self.lib.evoamd_patches_merge_samples(self._h, H, W, C, int(ph), int(pw), int(shift), m, int(t0), int(n_draws),
+                                                    None if imgs is None else dptr(imgs),
+                                                    None if mean is None else dptr(mean), None if std is None else dptr(std)))
+        return imgs, mean, std
 
     # ---- timing --------------------------------------------------------------------------
     def timing(self, on=True):

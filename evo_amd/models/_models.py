@@ -189,6 +189,7 @@ class Model:
         # there and only the image crosses to the host; np.asarray(handle) downloads what the default path stores.
         # Off by default: the reference's loop reads an ndarray every epoch.
         self.resident_reconstruction = bool(resident_reconstruction)
+        self._draws_handle = self._moments_handle = None  # the handles of the last resident=True sample_posterior / predictive_moments
         self._rec_handle = None
         # dtype=np.float32 (EBSC only): the data, B = Y W and the E_q[s] rows are kept in float and the two long
         # contractions run on the f32 matrix cores; lpj arithmetic, selection, sums and Theta stay float64.  The reference
@@ -959,7 +960,7 @@ class Model:
             codes.Es, codes.Ez = eng.download_posterior()
         return codes
 
-    def predictive_moments(self, model_params, my_suff_stat, my_data, noise=True):
+    def predictive_moments(self, model_params, my_suff_stat, my_data, noise=True, resident=False):
         """The posterior-predictive mean and variance of EVERY entry (n, d) of this rank's data, observed or missing, under
         ``model_params`` and the caller's K^n / lpj: (mean, var, info) with float64 (N_loc, D) arrays.  mean = W E_q[s]
         (EBSC) / W E_q[s o z] (ES3C), what reconstruct() writes at the missing entries; var = the variance of the
@@ -970,9 +971,16 @@ class Model:
         counted in info["n_skipped"]; one with a singular k x k system has NaN rows and is counted in
         info["n_singular"]; a state with more than 32 active latents raises EvoAmdError naming n and k.  Runs no
         statistics pass, does no communication (per rank), writes nothing into the three dicts, works with
-        sync_host=False and leaves K^n, lpj, Theta, y_reconstructed and the statistics rows on the device as they are."""
+        sync_host=False and leaves K^n, lpj, Theta, y_reconstructed and the statistics rows on the device as they are.
+        ``resident=True``: mean and var stay on the device and come back as ResidentMoments handles (array-like; np.asarray
+        downloads once): ``ovp.set_and_merge(mean.T, merge_method=precision_merger(var.T))`` and
+        ``ovp.set_and_merge(var.T, merge_method=mean_merger)`` merge them there and only the image crosses to the host.
+        The handles belong to this call: the next predictive_moments outdates what was not read (RuntimeError)."""
         if self.dtype == np.float32:
             raise NotImplementedError("predictive_moments is not available in the float32 mode")
+        if self._moments_handle is not None:
+            self._moments_handle._outdate("a later predictive_moments of the same model")
+            self._moments_handle = None
         yr = my_data.get("y_reconstructed")
         if isinstance(yr, ResidentReconstruction) and yr.resident and not yr.materialised:
             yr.rows()  # setting the parameters below drops the device copy of an unread reconstruction: fetch it first
@@ -984,12 +992,15 @@ class Model:
             self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
         if self.sync_host or self._kn_uploads != uploads:
             eng.upload_lpj(my_suff_stat["lpj"])
-        return eng.predictive_moments(noise=noise)
+        mean, var, info = eng.predictive_moments(noise=noise, resident=resident)
+        if resident:
+            self._moments_handle = mean
+        return mean, var, info
 
     _KEEP_ALL = ("slot", "s", "z", "y")  # the default of sample_posterior, told from the same names given by the caller
 
     def sample_posterior(self, model_params, my_suff_stat, my_data, n_samples=1, seed=None, first_index=0,
-                         keep=_KEEP_ALL, fill="missing", noise=True):
+                         keep=_KEEP_ALL, fill="missing", noise=True, resident=False):
         """``n_samples`` draws per datapoint of this rank from the variational posterior under ``model_params`` and the
         caller's K^n / lpj: a dict with, for datapoint n and draw t, "slot" (int32 (N, T): the column of lpj drawn with
         probability q_ns), "s" (bool (N, T, H): the drawn state), ES3C "z" (float64 (N, T, H): z_A ~ N(kappa_s, Lam_s) on
@@ -1007,7 +1018,10 @@ class Model:
         more than 32 active latents raise (EvoAmdError naming n and k), as do outputs that do not fit into the free device
         memory (naming the bytes).  Runs no statistics pass, does no communication, writes nothing into the three dicts,
         works with sync_host=False and leaves K^n, lpj, Theta, y_reconstructed and the statistics rows on the device as
-        they are."""
+        they are.  ``resident=True`` (``keep`` must name "y", else ValueError): "y" is not downloaded; the entry is a
+        ResidentDraws handle -- ``handle.merge(ovp)`` gives the T merged images, ``handle.merge_moments(ovp)`` their
+        pixelwise mean and standard deviation, both formed on the device; np.asarray(handle) is the array of the default
+        path.  The handle belongs to this call: the next sample_posterior outdates an unread one (RuntimeError)."""
         default_keep = keep is Model._KEEP_ALL
         keep = tuple(keep)
         for name in keep:
@@ -1019,8 +1033,13 @@ class Model:
             keep = tuple(name for name in keep if name != "z")
         if fill not in ("missing", "all"):
             raise ValueError("fill must be 'missing' or 'all'")
+        if resident and "y" not in keep:
+            raise ValueError("sample_posterior: resident=True keeps the draws \"y\" on the device: keep must name \"y\"")
         if self.dtype == np.float32:
             raise EvoAmdError("sample_posterior is not available in the float32 mode")
+        if self._draws_handle is not None:
+            self._draws_handle._outdate("a later sample_posterior of the same model")
+            self._draws_handle = None
         if seed is None:
             seed = int(np.random.randint(0, 2 ** 31 - 1))
         self.last_sample_seed = (int(seed) * max(1, self.comm.size) + self.comm.rank) & (2 ** 64 - 1)
@@ -1035,7 +1054,10 @@ class Model:
             self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
         if self.sync_host or self._kn_uploads != uploads:
             eng.upload_lpj(my_suff_stat["lpj"])
-        return eng.sample_posterior(n_samples, self.last_sample_seed, first_index, keep, fill, noise)
+        out = eng.sample_posterior(n_samples, self.last_sample_seed, first_index, keep, fill, noise, resident=resident)
+        if resident:
+            self._draws_handle = out["y"]
+        return out
 
     def modelmean(self, model_params, this_data, this_suff_stat):
         """Per-datapoint operator of the reference's reconstruct loop: (D_miss, S) means of the entries to be

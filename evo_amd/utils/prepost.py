@@ -8,6 +8,10 @@ the two standard merges run as HIP kernels on the GPU (``Engine.patches_extract`
 merge callable runs on the host over the stack of estimates; ``precision_merger(var.T)`` weights every estimate with the
 inverse of its posterior-predictive variance (Model.predictive_moments) and runs on the GPU too.  A model built with ``resident_reconstruction=True`` stores a
 ``ResidentReconstruction`` handle in my_data["y_reconstructed"]; ``set_and_merge(handle.T, ...)`` merges it on the device.
+``sample_posterior(..., resident=True)`` and ``predictive_moments(..., resident=True)`` leave their draws and moments on
+the device in the same way (``ResidentDraws`` / ``ResidentMoments``): one draw (``handle.draw(t).T``), the predictive mean
+with ``precision_merger(var.T)`` and the uncertainty map ``var.T`` merge where they lie; ``image_moments_host`` is the
+NumPy mirror of the pixelwise moments ``ResidentDraws.merge_moments`` forms on the device.
 
 Conventions (ours; tvutil is not a dependency and bit parity with it is not claimed):
 
@@ -26,7 +30,9 @@ import warnings
 
 import numpy as np
 
-from ..resident import ResidentReconstruction
+from ..resident import DrawFace, ResidentMoments, ResidentReconstruction
+
+_RESIDENT_ROWS = (ResidentReconstruction, DrawFace, ResidentMoments)  # (N, D) rows on the device, either face
 
 MAX_PATCH_ELEMS = 1024
 
@@ -57,17 +63,34 @@ class PrecisionMerger:
     estimates); the variance of the MERGED image is not that, nor 1 / sum_k w_k: patch estimates are not independent."""
 
     def __init__(self, var_T):
-        self.var_T = np.asarray(var_T, dtype=np.float64)
-        if self.var_T.ndim != 2:
-            raise ValueError("precision_merger: var_T must be (D, N) like the patches, got shape %s" % (self.var_T.shape,))
+        # a ResidentMoments handle stays on the device: merge() runs the precision merge there when the estimates are the
+        # mean of the same predictive_moments call, and var_T downloads it only for the host paths
+        self._src = var_T if isinstance(var_T, ResidentMoments) else np.asarray(var_T, dtype=np.float64)
+        if self._src.ndim != 2:
+            raise ValueError("precision_merger: var_T must be (D, N) like the patches, got shape %s" % (self._src.shape,))
         self._geom = None
+
+    @property
+    def var_T(self):
+        """The variances as a (D, N) ndarray (a handle is downloaded on first use)."""
+        if isinstance(self._src, ResidentMoments):
+            a = self._src.rows()
+            return a.T if self._src.transposed else a
+        return self._src
+
+    @property
+    def resident_var(self):
+        """The (N, D) face of the ResidentMoments handle the merger was built from, or None."""
+        if not isinstance(self._src, ResidentMoments):
+            return None
+        return self._src.T if self._src.transposed else self._src
 
     def bind(self, H, W, C, ph, pw, shift):
         """The patch geometry the variances belong to (ValueError when (D, N) does not fit it)."""
         N, D = patch_geometry(H, W, C, ph, pw, shift)
-        if self.var_T.shape != (D, N):
+        if tuple(self._src.shape) != (D, N):
             raise ValueError("precision_merger: variances of shape (D, N) = %s, the patches are %s"
-                             % (self.var_T.shape, (D, N)))
+                             % (tuple(self._src.shape), (D, N)))
         self._geom = (int(H), int(W), int(C), int(ph), int(pw), int(shift))
         return self
 
@@ -98,6 +121,25 @@ def precision_merger(var_T):
     """The merge_method of a precision-weighted merge: ``ovp.set_and_merge(mean.T, merge_method=precision_merger(var.T))``
     with (mean, var, _) = model.predictive_moments(...).  See PrecisionMerger."""
     return PrecisionMerger(var_T)
+
+
+def image_moments_host(images):
+    """(mean, std) over axis 0 of a (T, ...) stack of images by Welford's recurrence in draw order, from mean = 0 and
+    M2 = 0: delta = x_t - mean, mean += delta / t, M2 += delta (x_t - mean); std = sqrt(M2 / T) (ddof 0, the np.std of T
+    merged images).  Sequential over axis 0, multiply and add as separate operations: the NumPy mirror, bit for bit, of
+    the moments ResidentDraws.merge_moments forms on the device.  A NaN in any image makes both outputs NaN at that pixel;
+    identical images give their own value and exactly 0."""
+    images = np.asarray(images, dtype=np.float64)
+    if images.ndim < 1 or images.shape[0] < 1:
+        raise ValueError("image_moments_host: a stack of at least one image, got shape %s" % (images.shape,))
+    mean = np.zeros(images.shape[1:])
+    M2 = np.zeros(images.shape[1:])
+    with np.errstate(invalid="ignore"):
+        for t in range(images.shape[0]):
+            delta = images[t] - mean
+            mean = mean + delta / float(t + 1)
+            M2 = M2 + delta * (images[t] - mean)
+        return mean, np.sqrt(M2 / float(images.shape[0]))
 
 
 def patch_tops(L, p, s):
@@ -198,11 +240,12 @@ class OverlappingPatches:
         return self._patches().T
 
     def set(self, Y_T):
-        """Store new patches, (D, N) like get() returns them, or a ResidentReconstruction handle (either face)."""
-        if isinstance(Y_T, ResidentReconstruction):
+        """Store new patches, (D, N) like get() returns them, or rows that lie on the device, either face: a
+        ResidentReconstruction handle, a draw of a ResidentDraws handle (``handle.draw(t)``), a ResidentMoments handle."""
+        if isinstance(Y_T, _RESIDENT_ROWS):
             rows = Y_T.T if Y_T.transposed else Y_T
             if rows.shape != (self.N, self.D):
-                raise ValueError("set: the resident reconstruction is (N, D) = %s, the patches are %s"
+                raise ValueError("set: the resident rows are (N, D) = %s, the patches are %s"
                                  % (rows.shape, (self.N, self.D)))
             self._Y = rows
             return
@@ -218,16 +261,23 @@ class OverlappingPatches:
         HANDLE's engine (the model's context, whichever engine this object was built with) and only the image comes
         back; any other callable, or a handle whose array was read and whose device copy is gone, takes the host array.
         That covers one rank holding all patches: with several ranks gather as before
-        (gather_from_processes(my_data["y_reconstructed"]) materialises the handle)."""
+        (gather_from_processes(my_data["y_reconstructed"]) materialises the handle).
+        A draw of a ResidentDraws handle and a ResidentMoments handle merge in the same way on their engine;
+        precision_merger(var.T) over mean.T runs there when both are the handles of one predictive_moments call, else
+        both are downloaded."""
         Y = self._patches()
         if isinstance(merge_method, PrecisionMerger):
             merge_method.bind(self.shape[0], self.shape[1], self.C, self.ph, self.pw, self.shift)
-            if isinstance(Y, ResidentReconstruction):
+            if isinstance(Y, ResidentMoments) and merge_method.resident_var is not None:
+                img = Y.merge_precision(merge_method.resident_var, self.shape, self.ph, self.pw, self.shift)
+                if img is not None:
+                    return img
+            if isinstance(Y, _RESIDENT_ROWS):
                 Y = Y.rows()
             return self.engine.patches_merge(Y, self.shape, self.ph, self.pw, self.shift, "precision",
                                              weights=merge_method.var_T.T)
         gpu_merge = merge_method is mean_merger or merge_method is median_merger
-        if isinstance(Y, ResidentReconstruction):
+        if isinstance(Y, _RESIDENT_ROWS):
             if gpu_merge:
                 img = Y.merge(self.shape, self.ph, self.pw, self.shift, "mean" if merge_method is mean_merger else "median")
                 if img is not None:
@@ -242,6 +292,18 @@ class OverlappingPatches:
     def set_and_merge(self, Y_T, merge_method=mean_merger):
         self.set(Y_T)
         return self.merge(merge_method)
+
+
+def merge_rows(ovp, Y, merge_method=mean_merger):
+    """The image ``ovp.set_and_merge(Y.T, merge_method)`` gives for host rows Y (N, D), without replacing ovp's patches."""
+    if merge_method is mean_merger or merge_method is median_merger:
+        return ovp.engine.patches_merge(Y, ovp.shape, ovp.ph, ovp.pw, ovp.shift,
+                                        "mean" if merge_method is mean_merger else "median")
+    if isinstance(merge_method, PrecisionMerger):
+        merge_method.bind(ovp.shape[0], ovp.shape[1], ovp.C, ovp.ph, ovp.pw, ovp.shift)
+        return ovp.engine.patches_merge(Y, ovp.shape, ovp.ph, ovp.pw, ovp.shift, "precision", weights=merge_method.var_T.T)
+    stack = estimate_stack(Y, ovp.shape[0], ovp.shape[1], ovp.C, ovp.ph, ovp.pw, ovp.shift)
+    return np.asarray(merge_method(stack, axis=0)).reshape(ovp.shape)
 
 
 class MultiDimOverlappingPatches(OverlappingPatches):

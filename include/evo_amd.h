@@ -607,6 +607,31 @@ int evoamd_posterior_sample(evoamd_ctx *ctx, int n_samples, uint64_t seed, uint6
                             int fill_all, int add_noise, int64_t counters[4]);
 int evoamd_download_posterior_samples(evoamd_ctx *ctx, int what, void *out);
 
+/* ---- merges of the resident draws and predictive moments (nothing of N x T x D or N x D crosses to the host) ---- */
+/* The patch geometry (H, W, C, ph, pw, shift: the conventions of evoamd_patches_merge) must give (N, D) of the buffers.
+ * evoamd_patches_merge_samples merges draws t0 .. t0+n_draws-1 of the y draws the last evoamd_posterior_sample kept, each
+ * draw t read where it lies (element ((n T + t) D + d)), in one launch per method:
+ *   imgs_out  (n_draws, H, W, C) or NULL: image t is, bit for bit, evoamd_patches_merge of the dense slice y[:, t, :]
+ *             (method 0 mean, 1 median; estimates in increasing n, NaN skipped, no valid estimate gives NaN);
+ *   mean_out / std_out  (H, W, C) or NULL: the pixelwise moments over those merged images, in draw order, by Welford from
+ *             mean = 0, M2 = 0: delta = x_t - mean, mean += delta / t, M2 += delta (x_t - mean), as separate IEEE
+ *             operations; mean_out = mean, std_out = sqrt(M2 / n_draws) (ddof 0).  A NaN in any image makes both NaN at
+ *             that pixel; identical images give their value and exactly 0.  evo_amd.utils.prepost.image_moments_host is
+ *             the NumPy mirror, bit for bit.  With method 0 the images are not stored when imgs_out is NULL.
+ * evoamd_patches_merge_predictive merges the mean / var buffers of the last evoamd_predictive_moments: what = 0 mean-merge
+ * of mean, 1 median-merge of mean, 2 precision-weighted merge of mean by var (evoamd_patches_merge_weighted), 3 mean-merge
+ * of var (the per-pixel uncertainty map) -- the kernels of evoamd_patches_merge / _weighted reading the context's buffers,
+ * hence their bits.
+ * Both refuse with EVOAMD_E_INVALID before anything is launched: a geometry that does not give (N, D) of the buffers; t0 or
+ * n_draws outside the T of the last call (n_draws 1 .. 65535); y not kept; no current results (the last sample / predictive
+ * call failed, or evoamd_configure released them: never stale data); for samples, imgs_out, mean_out and std_out all NULL.
+ * Both leave the EM state and every validity flag as they are, put the images into the context's patch scratch (grown on
+ * demand: n_draws + 2 images at most), allocate nothing of the size of the draws, and have completed on return. */
+int evoamd_patches_merge_samples(evoamd_ctx *ctx, int H, int W, int C, int ph, int pw, int shift, int method,
+                                 int t0, int n_draws, double *imgs_out, double *mean_out, double *std_out);
+int evoamd_patches_merge_predictive(evoamd_ctx *ctx, int H, int W, int C, int ph, int pw, int shift, int what,
+                                    double *img_out);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------------- */
 /* 128-byte opaque id made by rank 0 and distributed by the caller (file / socket / MPI). */
 int evoamd_comm_unique_id(uint8_t id_out[128]);

@@ -12,6 +12,20 @@ shape (ES3C D = 256, H = 512, S = 200, N = 100k) and at c5 (EBSC D = 256, H = 10
 K^n is drawn on the device (Engine.init_states, p = ``--pih`` / H) and its lpj rows come from one pass over it.
 
     python tools/time_posterior_samples.py [--shapes c4,c5] [--scale 1.0] [--pih 2] [--reps 3] [--draws 1,8,64] [--host-n 30]
+
+``--merge``: the whole user-visible operation, from the call to the T merged images and to their pixelwise (mean, std), on
+the image-shaped problems of tools/merge_timing.py (``--geometries g16,g8``), both ways:
+
+  default   sample_posterior downloads y (N, T, D); every draw is merged by Engine.patches_merge (an upload of its (N, D)
+            slice each); np.mean / np.std over the images;
+  resident  sample_posterior(resident=True); ResidentDraws.merge / merge_moments: one launch, only the images (or only the
+            two moment images) come back.
+
+Wall times around calls that end synchronised, one warm-up and five repeats each (median, min, max: the spread), and the
+device time of the batched merge per draw next to one patches_merge_resident at the same geometry.  The images of the two
+paths are compared bit for bit.
+
+    python tools/time_posterior_samples.py --merge [--geometries g16,g8] [--draws 1,8,64]
 """
 import argparse
 import ctypes
@@ -27,6 +41,7 @@ from evo_amd._lib import PSAMP_KEEP, PSAMP_WHAT, EvoAmdError, check  # noqa: E40
 from evo_amd.engine import Engine  # noqa: E402
 from evo_amd.models import sample_posterior_counter  # noqa: E402
 from evo_amd.models.generate import unpack_words  # noqa: E402
+from evo_amd.utils.prepost import median_merger  # noqa: E402
 
 SHAPES = {"c4": ("es3c", 100000, 256, 512, 200), "c5": ("ebsc", 200000, 256, 1024, 256)}
 KEEP = ("slot", "s", "y")
@@ -46,6 +61,59 @@ def stat(what, v, unit="ms"):
     print("%s: median %.3f %s, min %.3f, max %.3f (%d calls)" % (what, np.median(v), unit, v.min(), v.max(), v.size), flush=True)
 
 
+def merge_mode(args):
+    import merge_timing as mt
+    eng = Engine(0)
+    for name in args.geometries.split(","):
+        ovp, tag = mt.setup(eng, name, args.pih)
+        geom = (ovp.shape, ovp.ph, ovp.pw, ovp.shift)
+        # one resident merge of the reconstruction at this geometry, for scale (select kernel + mean merge)
+        eng.stats()
+        eng.reconstruct_resident()
+        mt.stat(tag + " patches_merge_resident (mean), device", mt.kernel_ms(eng, lambda: eng.patches_merge_resident(*geom)))
+        mt.stat(tag + " patches_merge_resident (mean), call", mt.timed(lambda: eng.patches_merge_resident(*geom))[0])
+        eng.lpj_resident()
+        for T in (int(t) for t in args.draws.split(",")):
+            tt = "%s T=%d" % (tag, T)
+
+            def default_images():
+                y = eng.sample_posterior(T, seed=5, keep=("y",), fill="all")["y"]
+                return np.stack([eng.patches_merge(y[:, t], *geom) for t in range(T)])
+
+            def default_moments():
+                imgs = default_images()
+                return np.mean(imgs, axis=0), np.std(imgs, axis=0)
+
+            def resident_images():
+                return eng.sample_posterior(T, seed=5, keep=("y",), fill="all", resident=True)["y"].merge(ovp)
+
+            def resident_moments():
+                return eng.sample_posterior(T, seed=5, keep=("y",), fill="all", resident=True)["y"].merge_moments(ovp)
+
+            try:
+                t_di, imgs_d = mt.timed(default_images)
+            except (EvoAmdError, MemoryError) as e:
+                print("%s refused: %s" % (tt, e), flush=True)
+                continue
+            t_ri, imgs_r = mt.timed(resident_images)
+            t_dm, mom_d = mt.timed(default_moments)
+            t_rm, mom_r = mt.timed(resident_moments)
+            mt.stat(tt + " to the T images, default path", t_di)
+            mt.stat(tt + " to the T images, resident path", t_ri)
+            mt.stat(tt + " to (mean, std), default path", t_dm)
+            mt.stat(tt + " to (mean, std), resident path", t_rm)
+            print("%s images of the two paths equal bit for bit: %s; max |mean| diff %.3g, max |std| diff %.3g"
+                  % (tt, np.array_equal(imgs_d, imgs_r, equal_nan=True), np.abs(mom_d[0] - mom_r[0]).max(),
+                     np.abs(mom_d[1] - mom_r[1]).max()), flush=True)
+            h = eng.sample_posterior(T, seed=5, keep=("y",), fill="all", resident=True)["y"]
+            mt.stat(tt + " batched mean merge to images, device, per draw", mt.kernel_ms(eng, lambda: h.merge(ovp)) / T)
+            mt.stat(tt + " batched mean merge to moments, device, per draw", mt.kernel_ms(eng, lambda: h.merge_moments(ovp)) / T)
+            mt.stat(tt + " batched median merge to images, device, per draw",
+                    mt.kernel_ms(eng, lambda: h.merge(ovp, median_merger)) / T)
+            del imgs_d, imgs_r, h
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="c4,c5")
@@ -54,7 +122,11 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--draws", default="1,8,64")
     ap.add_argument("--host-n", type=int, default=30)
+    ap.add_argument("--merge", action="store_true", help="time sample -> merged images / moments, default against resident")
+    ap.add_argument("--geometries", default="g16,g8")
     args = ap.parse_args()
+    if args.merge:
+        return merge_mode(args)
     eng = Engine(0)
     for name in args.shapes.split(","):
         algo, N, D, H, S = SHAPES[name]

@@ -11,6 +11,14 @@ shape (ES3C D = 256, H = 512, S = 200, N = 100k) and at c5 (EBSC D = 256, H = 10
 K^n is drawn on the device (Engine.init_states, p = ``--pih`` / H) and its lpj rows come from one pass over it.
 
     python tools/time_predictive.py [--shapes c4,c5] [--scale 1.0] [--pih 2] [--reps 3] [--host-n 40]
+
+``--merge``: the whole user-visible operation, from the call to the precision-merged image and to the uncertainty map, on
+the image-shaped problems of tools/merge_timing.py (``--geometries g16,g8``), both ways: the default path downloads mean
+and var (N, D) and ``set_and_merge(mean.T, precision_merger(var.T))`` uploads both again; with ``resident=True`` the two
+stay on the device and only the image comes back.  Wall times around calls that end synchronised, one warm-up and five
+repeats each (median, min, max: the spread); the images of the two paths are compared bit for bit.
+
+    python tools/time_predictive.py --merge [--geometries g16,g8]
 """
 import argparse
 import ctypes
@@ -43,6 +51,38 @@ def stat(what, v, unit="ms"):
     print("%s: median %.3f %s, min %.3f, max %.3f (%d calls)" % (what, np.median(v), unit, v.min(), v.max(), v.size), flush=True)
 
 
+def merge_mode(args):
+    import merge_timing as mt
+    from evo_amd.utils.prepost import mean_merger, precision_merger
+    eng = Engine(0)
+    for name in args.geometries.split(","):
+        ovp, tag = mt.setup(eng, name, args.pih)
+
+        def precision(resident):
+            mean, var, _ = eng.predictive_moments(resident=resident)
+            return ovp.set_and_merge(mean.T, merge_method=precision_merger(var.T))
+
+        def both(resident):
+            mean, var, _ = eng.predictive_moments(resident=resident)
+            return (ovp.set_and_merge(mean.T, merge_method=precision_merger(var.T)),
+                    ovp.set_and_merge(var.T, merge_method=mean_merger))
+
+        t_d, img_d = mt.timed(lambda: precision(False))
+        t_r, img_r = mt.timed(lambda: precision(True))
+        t_db, both_d = mt.timed(lambda: both(False))
+        t_rb, both_r = mt.timed(lambda: both(True))
+        mt.stat(tag + " to the precision-merged image, default path", t_d)
+        mt.stat(tag + " to the precision-merged image, resident path", t_r)
+        mt.stat(tag + " to the image and the uncertainty map, default path", t_db)
+        mt.stat(tag + " to the image and the uncertainty map, resident path", t_rb)
+        print("%s images of the two paths equal bit for bit: %s, uncertainty maps: %s"
+              % (tag, np.array_equal(img_d, img_r, equal_nan=True), np.array_equal(both_d[1], both_r[1], equal_nan=True)), flush=True)
+        mean, var, _ = eng.predictive_moments(resident=True)
+        mt.stat(tag + " precision merge of the resident moments, device",
+                mt.kernel_ms(eng, lambda: ovp.set_and_merge(mean.T, merge_method=precision_merger(var.T))))
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="c4,c5")
@@ -50,7 +90,11 @@ def main():
     ap.add_argument("--pih", type=float, default=2.0)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--host-n", type=int, default=40)
+    ap.add_argument("--merge", action="store_true", help="time moments -> merged image, default against resident")
+    ap.add_argument("--geometries", default="g16,g8")
     args = ap.parse_args()
+    if args.merge:
+        return merge_mode(args)
     eng = Engine(0)
     for name in args.shapes.split(","):
         algo, N, D, H, S = SHAPES[name]
