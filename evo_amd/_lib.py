@@ -19,6 +19,9 @@ MODEL_BSC, MODEL_SSSC = 0, 1
 GEN_KEEP = {"s": 1, "z": 2, "y_mean": 4}
 GEN_WHAT = {"y": 0, "s": 1, "z": 2, "y_mean": 3}
 
+# evoamd_seed_states_ex: flags (EVOAMD_SEED_*)
+SEED_INCOMPLETE = 1
+
 # evoamd_posterior_sample: keep bits (EVOAMD_PSAMP_KEEP_*) and the output ids of evoamd_download_posterior_samples
 PSAMP_KEEP = {"slot": 1, "s": 2, "z": 4, "y": 8}
 PSAMP_WHAT = {"slot": 0, "s": 1, "z": 2, "y": 3}
@@ -75,6 +78,7 @@ SIGNATURES = {
     "evoamd_download_states_packed": (_I, [_vp, _c_u8p, _I64, _I64]),
     "evoamd_init_states": (_I, [_vp, _DBL, _U64, _I, _c_u8p]),
     "evoamd_seed_states": (_I, [_vp, _I, _c_i32p, _c_dp]),
+    "evoamd_seed_states_ex": (_I, [_vp, _I, ctypes.c_uint, _c_i32p, _c_dp]),
     "evoamd_upload_lpj": (_I, [_vp, _c_dp]),
     "evoamd_download_lpj": (_I, [_vp, _c_dp]),
     "evoamd_set_params_bsc": (_I, [_vp, _c_dp, _DBL, _DBL, _c_dp]),

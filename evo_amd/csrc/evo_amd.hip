@@ -538,6 +538,7 @@ struct evoamd_ctx {
   int init_home = -1;
   DevBuf<u64> init_scratch;
   DevBuf<double2> seed_gpt;  // evoamd_seed_states, ES3C: the transpose of GP (H x H), grown on demand, rewritten by every call
+  DevBuf<double> seed_rows;  // evoamd_seed_states_ex, ES3C on incomplete data: the rows of G(n) that do not fit LDS, grown on demand
   bool kn_lost = false;
   i64 kn_refill = 0;  // while kn_lost: rows [0, kn_refill) have been uploaded again by evoamd_upload_states_packed
   // evoamd_generate (kernels_generate.hpp): Theta^gen, the given states and the outputs of the last call, grown on demand
@@ -860,6 +861,8 @@ static int set_kernel_lds_limits() {
   }
   HIP_TRY(hipFuncSetAttribute((const void *)seed_states_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   HIP_TRY(hipFuncSetAttribute((const void *)seed_states_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  HIP_TRY(hipFuncSetAttribute((const void *)seed_states_masked_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  HIP_TRY(hipFuncSetAttribute((const void *)seed_states_masked_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   {
     const void *wk[] = {(const void *)sssc_stats_wave_kernel<0, 4>,  (const void *)sssc_stats_wave_kernel<1, 4>,
                         (const void *)sssc_stats_wave_kernel<2, 4>,  (const void *)sssc_stats_wave_kernel<4, 4>,
@@ -1214,6 +1217,7 @@ static void configure_drop(evoamd_ctx *c) {
   c->Wt.reset();
   c->init_scratch.reset();
   c->seed_gpt.reset();
+  c->seed_rows.reset();
   // the posterior samples of the previous geometry
   c->ps_slot.reset();
   c->ps_status.reset();
@@ -1443,6 +1447,8 @@ extern "C" int evoamd_upload_masks(evoamd_ctx *c, const uint8_t *x_infr, const u
   HIP_TRY(hipMemcpyAsync(c->mask_x, x ? x : x_infr, nd, hipMemcpyHostToDevice, c->stream));
   // missing entries (NaN in the reference's data) become zeros: they then drop out of ||y_obs||^2
   mask_apply_kernel<<<cdiv((i64)nd, 256), 256, 0, c->stream>>>(c->Y, c->ldY, c->mask_infr, c->N, c->D);
+  if (c->Yt)  // B = Y W is formed from Y^T where it exists: it must hold the zeros too (evoamd_seed_states_ex reads that B)
+    transpose_to_f64_kernel<<<dim3(cdiv(c->N, 32), cdiv(c->D, 32)), 256, 0, c->stream>>>(c->Y, c->ldY, c->N, c->D, c->Yt, c->ldYt);
   row_sqnorm_kernel<<<cdiv(c->N, 4), 256, 0, c->stream>>>(c->Y, c->ldY, c->N, c->D, c->yy);
   patches_row_any_kernel<<<cdiv(c->N, 4), 256, 0, c->stream>>>(c->mask_infr, c->N, c->D, c->row_any);
   HIP_TRY(hipMemsetAsync(c->y2sum, 0, (size_t)c->D * sizeof(double), c->stream));
@@ -5146,11 +5152,15 @@ extern "C" int evoamd_download_predictive(evoamd_ctx *c, double *mean, double *v
 
 // ---------------------------------------------------------------------------------------
 // K^n seeded by greedy forward selection on the model's lpj (kernels_seed.hpp).  Every refusal comes before the first write.
-extern "C" int evoamd_seed_states(evoamd_ctx *c, int max_active, int32_t *path_out, double *lpj_out) {
+// EVOAMD_SEED_INCOMPLETE is a permission: with masks resident the masked kernel runs (the datapoint's own Gram rows from W
+// and the mask), without masks the complete kernel, whatever the flag says.
+extern "C" int evoamd_seed_states_ex(evoamd_ctx *c, int max_active, unsigned flags, int32_t *path_out, double *lpj_out) {
   REQUIRE(c && c->configured, "configure first");
   REQUIRE(c->have_params, "evoamd_seed_states: no Theta installed (set parameters first)");
   REQUIRE(c->have_data, "evoamd_seed_states: no data (upload data first)");
-  REQUIRE(!c->mask_infr, "evoamd_seed_states: incomplete data (masks present) is not supported");
+  REQUIRE(!(flags & ~(unsigned)EVOAMD_SEED_INCOMPLETE), "evoamd_seed_states_ex: unknown flag");
+  REQUIRE(!c->mask_infr || (flags & EVOAMD_SEED_INCOMPLETE),
+          "evoamd_seed_states: incomplete data (masks present) is not supported (evoamd_seed_states_ex with EVOAMD_SEED_INCOMPLETE)");
   REQUIRE(!c->bg_unit, "evoamd_seed_states: option background_unit is not supported");
   REQUIRE(!c->f32, "evoamd_seed_states is not available in the float32 mode (ebsc_f32)");
   const bool sssc = c->model == EVOAMD_MODEL_SSSC;
@@ -5168,14 +5178,25 @@ extern "C" int evoamd_seed_states(evoamd_ctx *c, int max_active, int32_t *path_o
                   "(S = %d, max_active = %d)", t, q, H - (t - 1), t, S, A);
   }
   const int Hp = (int)cdiv(H, 64) * 64, Q = q_lo + (q_rem ? 1 : 0);
-  const size_t wave_bytes = seed_wave_bytes(Hp, HW, Q, A);
-  REQUIRE(wave_bytes <= 150 * 1024, "evoamd_seed_states: the scores of one datapoint (16 H bytes) do not fit one wavefront's share of LDS");
+  const bool masked = c->mask_infr != nullptr;
+  const int D = c->D, R = masked && sssc ? A : 0;  // ES3C, masked: the winners' rows of G(n) and its diagonal
+  // their home: LDS while one wavefront's share fits, else a buffer of the context
+  const bool rows_lds = R && seed_masked_wave_bytes(Hp, HW, Q, A, D, R) <= 150 * 1024;
+  const size_t wave_bytes = masked ? seed_masked_wave_bytes(Hp, HW, Q, A, D, rows_lds ? R : 0) : seed_wave_bytes(Hp, HW, Q, A);
+  REQUIRE(wave_bytes <= 150 * 1024, masked ? "evoamd_seed_states: the scores of one datapoint (16 H bytes) and the column of W (12 D "
+                                             "bytes) do not fit one wavefront's share of LDS"
+                                           : "evoamd_seed_states: the scores of one datapoint (16 H bytes) do not fit one wavefront's share of LDS");
   HIP_TRY(hipSetDevice(c->device));
   TRY(ensure_B(c));
   const size_t n_out = (size_t)c->N * A;
   const size_t out_bytes = ((n_out * sizeof(int) + 7) / 8) * 8;
   if (path_out || lpj_out) TRY(c->stage.ensure(c, out_bytes + n_out * sizeof(double)));
   if (sssc) TRY(c->seed_gpt.ensure(c, (size_t)H * H));
+  int W = 4;
+  while (W > 1 && W * wave_bytes > 150 * 1024) W >>= 1;
+  // (rows in global memory: fewer workgroups, each wavefront of the grid owns R Hp doubles)
+  const unsigned grid = (unsigned)std::min<i64>(cdiv(c->N, W), (i64)c->n_cu * (R && !rows_lds ? 4 : 64));
+  if (R && !rows_lds) TRY(c->seed_rows.ensure(c, (size_t)grid * W * R * Hp));
   SeedArgs a;
   a.states = c->states;
   a.dig = c->dig;
@@ -5193,14 +5214,19 @@ extern "C" int evoamd_seed_states(evoamd_ctx *c, int max_active, int32_t *path_o
   a.err = c->err;
   a.N = c->N;
   a.S = S, a.H = H, a.HW = HW, a.A = A, a.Hp = Hp, a.Q = Q;
-  int W = 4;
-  while (W > 1 && W * wave_bytes > 150 * 1024) W >>= 1;
-  const unsigned grid = (unsigned)std::min<i64>(cdiv(c->N, W), (i64)c->n_cu * 64);
+  a.W = c->W;
+  a.mask = c->mask_infr;
+  a.rows = R && !rows_lds ? c->seed_rows.get() : nullptr;
+  a.D = D, a.R = R;
   on_kn_changed(c, KN_BY_CALLER);
   {
     SpanGuard g(c, KID_SEED_STATES);
     if (sssc) seed_transpose_gp_kernel<<<cdiv((i64)H * H, 256), 256, 0, c->stream>>>(c->GP, H, c->seed_gpt);
-    if (sssc)
+    if (masked && sssc)
+      seed_states_masked_kernel<true><<<grid, 64 * W, W * wave_bytes, c->stream>>>(a);
+    else if (masked)
+      seed_states_masked_kernel<false><<<grid, 64 * W, W * wave_bytes, c->stream>>>(a);
+    else if (sssc)
       seed_states_kernel<true><<<grid, 64 * W, W * wave_bytes, c->stream>>>(a);
     else
       seed_states_kernel<false><<<grid, 64 * W, W * wave_bytes, c->stream>>>(a);
@@ -5212,6 +5238,10 @@ extern "C" int evoamd_seed_states(evoamd_ctx *c, int max_active, int32_t *path_o
   HIP_TRY(hipStreamSynchronize(c->stream));
   on_kn_complete(c);
   return 0;
+}
+
+extern "C" int evoamd_seed_states(evoamd_ctx *c, int max_active, int32_t *path_out, double *lpj_out) {
+  return evoamd_seed_states_ex(c, max_active, 0u, path_out, lpj_out);
 }
 
 // posterior samples (kernels_posterior_sample.hpp): own buffers; of the EM state only B = Y W is (re)formed, like every lpj pass

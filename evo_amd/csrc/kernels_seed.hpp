@@ -30,6 +30,8 @@
 // wave with lane-strided stores.  Every latent index that crossed LDS passes guard_index before it becomes an address.
 // LDS per wave: keys and e (Hp = Hv rounded up to 64 doubles each), the HW words of A_{t-1}, the shared blocks (168 doubles),
 // the members' keys and two lists of their latents (max q_t each), the path and the ascending active set (A ints each).
+// INCOMPLETE DATA (seed_states_masked_kernel, at the end of this file): the same law with G, B, yy over the datapoint's
+// reliable entries; G(n) is the datapoint's own, so its diagonal and the winners' rows are formed from W and the mask.
 #pragma once
 #include "common.hpp"
 #include "kernels_mstep.hpp"
@@ -57,10 +59,22 @@ struct SeedArgs {
   int *err;             // err[0] of the context's block (EVO_ERR_BAD_ENTRY)
   i64 N;
   int S, H, HW, A, Hp, Q;  // Hp: Hv rounded up to 64; Q: largest quota
+  // incomplete data (seed_states_masked_kernel) only
+  const double *W;      // (D, H)
+  const uint8_t *mask;  // (N, D) x_infr
+  double *rows;         // ES3C: R rows of Hp doubles per wavefront of the grid when they do not fit LDS, else nullptr
+  int D, R;             // R: rows of G(n) a wavefront keeps (ES3C: A - 1 winners' rows and the diagonal; EBSC: 0)
 };
 
 __host__ __device__ inline size_t seed_wave_bytes(int Hp, int HW, int Q, int A) {
   size_t b = (size_t)2 * Hp * 8 + (size_t)HW * 8 + (size_t)SEED_SHARED_DOUBLES * 8 + (size_t)Q * 8 + (size_t)2 * Q * 4 + (size_t)2 * A * 4;
+  return (b + 15) & ~(size_t)15;
+}
+
+// masked kernel: behind the complete kernel's share the staged column m o W_.w (D doubles), the R rows of G(n) when LDS is
+// their home (rows_lds = R, else 0) and the list of the reliable d (D ints)
+__host__ __device__ inline size_t seed_masked_wave_bytes(int Hp, int HW, int Q, int A, int D, int rows_lds) {
+  size_t b = seed_wave_bytes(Hp, HW, Q, A) + (size_t)D * 8 + (size_t)rows_lds * Hp * 8 + (size_t)D * 4;
   return (b + 15) & ~(size_t)15;
 }
 
@@ -96,18 +110,32 @@ struct SeedShared {
 // bordered system: only the row and the column of j are the lane's own -- 2 (K - 1) coalesced loads of {G, Psi} (the row
 // from the transposed table: gathered from GP it would fetch a 128-byte line per 16 bytes used), the diagonal entry and
 // 4 (K - 1)^2 multiply-adds in front of the elimination.
-template <int K>
+// MASKED (incomplete data): G is the datapoint's own -- rows[i * Hp + j] = G(n)_{act[i], j} (symmetric: row and column at once)
+// and rows[(R - 1) * Hp + j] its diagonal, formed by seed_states_masked_kernel; only Psi comes from the tables.
+template <int K, bool MASKED>
 __device__ __forceinline__ double seed_score_sssc(const SeedArgs &a, const SeedShared &sh, const int *act, double pbA, int j,
-                                                  const double *__restrict__ Bn, double yy, double s2inv) {
+                                                  const double *__restrict__ Bn, double yy, double s2inv,
+                                                  const double *rows = nullptr) {
   constexpr int M = K - 1, MM = M > 0 ? M : 1;
   double gc[MM], pc[MM], gr[MM], pr[MM];  // G_ij, Psi_ij, G_ji, Psi_ji, i in A
+  double gjj, pjj;
+  if constexpr (MASKED) {
 #pragma unroll
-  for (int i = 0; i < M; i++) {
-    const double2 c = a.GP[(size_t)act[i] * a.H + j], r = a.GPt[(size_t)act[i] * a.H + j];
-    gc[i] = c.x, pc[i] = c.y, gr[i] = r.x, pr[i] = r.y;
+    for (int i = 0; i < M; i++) {
+      gc[i] = gr[i] = rows[(size_t)i * a.Hp + j];
+      pc[i] = a.GP[(size_t)act[i] * a.H + j].y, pr[i] = a.GPt[(size_t)act[i] * a.H + j].y;
+    }
+    gjj = rows[(size_t)(a.R - 1) * a.Hp + j], pjj = a.GP[(size_t)j * a.H + j].y;
+  } else {
+#pragma unroll
+    for (int i = 0; i < M; i++) {
+      const double2 c = a.GP[(size_t)act[i] * a.H + j], r = a.GPt[(size_t)act[i] * a.H + j];
+      gc[i] = c.x, pc[i] = c.y, gr[i] = r.x, pr[i] = r.y;
+    }
+    const double2 djj = a.GP[(size_t)j * a.H + j];
+    gjj = djj.x, pjj = djj.y;
   }
-  const double2 djj = a.GP[(size_t)j * a.H + j];
-  const double gjj = djj.x, pjj = djj.y, muj = a.mus[j], bj = Bn[j];
+  const double muj = a.mus[j], bj = Bn[j];
   const double pb = pbA + a.pil_bar[j];
   double v[K], rr = yy;
   {
@@ -203,25 +231,213 @@ __global__ __launch_bounds__(256) void seed_transpose_gp_kernel(const double2 *_
   GPt[idx] = GP[(size_t)c * H + r];
 }
 
+// One wavefront's share of LDS (file header)
+struct SeedLds {
+  u64 *keys;
+  double *cc;
+  u64 *base;
+  SeedShared sh;
+  u64 *selk;
+  int *sel, *byrank, *path, *sorted;
+};
+__device__ __forceinline__ SeedLds seed_carve(unsigned char *home, int Hp, int HW, int Q, int A) {
+  SeedLds L;
+  L.keys = (u64 *)home;
+  L.cc = (double *)(L.keys + Hp);
+  L.base = (u64 *)(L.cc + Hp);
+  double *shd = (double *)(L.base + HW);
+  L.sh = {shd, shd + SEED_M * SEED_M, shd + 2 * SEED_M * SEED_M, shd + 3 * SEED_M * SEED_M,
+          shd + 3 * SEED_M * SEED_M + SEED_M, shd + 3 * SEED_M * SEED_M + 2 * SEED_M};
+  L.selk = (u64 *)(shd + SEED_SHARED_DOUBLES);
+  L.sel = (int *)(L.selk + Q);
+  L.byrank = L.sel + Q;
+  L.path = L.byrank + Q;
+  L.sorted = L.path + A;
+  return L;
+}
+
+// ES3C, once per step: act[] = A_{t-1} as wave-uniform values and its blocks in LDS (SeedShared); returns sum pil_bar over
+// A_{t-1}.  rows: nullptr = G from the tables, else the datapoint's own rows (seed_score_sssc).
+__device__ __forceinline__ double seed_form_blocks(const SeedArgs &a, const SeedLds &L, int t, int lane, const double *__restrict__ Bn,
+                                                   double s2inv, int *act, const double *rows) {
+  const SeedShared &sh = L.sh;
+  const int *path = L.path;
+  const int H = a.H;
+  const int m = t - 1;
+  double pbA = 0.0;
+#pragma unroll
+  for (int i = 0; i < SEED_MAX_A_SSSC; i++)
+    act[i] = i < m ? guard_index(__builtin_amdgcn_readfirstlane(path[i]), H, a.err) : 0;
+  // the blocks of A_{t-1}: lane i m + c holds entry (i, c)
+  const int bi = lane / (m > 0 ? m : 1), bc = lane - bi * (m > 0 ? m : 1);
+  const bool in_block = m > 0 && lane < m * m;
+  if (in_block) {
+    const int hc = guard_index(path[bc], H, a.err);
+    const double2 e = a.GP[(size_t)guard_index(path[bi], H, a.err) * H + hc];
+    sh.GA[bi * SEED_M + bc] = rows ? rows[(size_t)bi * a.Hp + hc] : e.x;
+    sh.PA[bi * SEED_M + bc] = e.y;
+  }
+  if (lane < m) {
+    const int h = guard_index(path[lane], H, a.err);
+    sh.muA[lane] = a.mus[h];
+    sh.bA[lane] = Bn[h];
+  }
+  seed_wave_sync();
+  if (in_block) {
+    double s = 0.0;
+    for (int l = 0; l < m; l++) s += sh.PA[bi * SEED_M + l] * sh.GA[l * SEED_M + bc];
+    sh.TA[bi * SEED_M + bc] = (bi == bc ? 1.0 : 0.0) + s2inv * s;
+  }
+  if (lane < m) {
+    double s = sh.bA[lane];
+    for (int l = 0; l < m; l++) s -= sh.GA[lane * SEED_M + l] * sh.muA[l];
+    sh.vA[lane] = s;
+  }
+  for (int i = 0; i < m; i++) pbA += a.pil_bar[guard_index(path[i], H, a.err)];
+  seed_wave_sync();
+  return pbA;
+}
+
+template <bool MASKED>
+__device__ __forceinline__ double seed_score_sssc_step(int t, const SeedArgs &a, const SeedShared &sh, const int *act, double pbA, int j,
+                                                       const double *__restrict__ Bn, double yy, double s2inv, const double *rows) {
+  switch (t) {
+    case 1: return seed_score_sssc<1, MASKED>(a, sh, act, pbA, j, Bn, yy, s2inv, rows);
+    case 2: return seed_score_sssc<2, MASKED>(a, sh, act, pbA, j, Bn, yy, s2inv, rows);
+    case 3: return seed_score_sssc<3, MASKED>(a, sh, act, pbA, j, Bn, yy, s2inv, rows);
+    case 4: return seed_score_sssc<4, MASKED>(a, sh, act, pbA, j, Bn, yy, s2inv, rows);
+    case 5: return seed_score_sssc<5, MASKED>(a, sh, act, pbA, j, Bn, yy, s2inv, rows);
+    case 6: return seed_score_sssc<6, MASKED>(a, sh, act, pbA, j, Bn, yy, s2inv, rows);
+    case 7: return seed_score_sssc<7, MASKED>(a, sh, act, pbA, j, Bn, yy, s2inv, rows);
+    default: return seed_score_sssc<8, MASKED>(a, sh, act, pbA, j, Bn, yy, s2inv, rows);
+  }
+}
+
+// From the keys of step t in LDS (the caller has synchronised) to the q states and digests of datapoint n in slots
+// slot0 .. slot0 + q - 1, the path entry and the winner in A_t (path, sorted, base): file header.  Returns the winner's
+// latent (wave-uniform) and its score in sw; the caller synchronises before the next step reads path / sorted / base.
+__device__ __forceinline__ int seed_select_step(const SeedArgs &a, const SeedLds &L, i64 n, int t, int q, int slot0, int lane, double &sw_out) {
+  const int S = a.S, H = a.H, HW = a.HW, A = a.A, Hp = a.Hp, Q = a.Q;
+  const int NC = Hp >> 6, NG = (NC + SEED_KREG - 1) / SEED_KREG;  // chunks of 64 latents, register loads of SEED_KREG chunks
+  u64 *keys = L.keys, *base = L.base, *selk = L.selk;
+  int *sel = L.sel, *byrank = L.byrank, *path = L.path, *sorted = L.sorted;
+  u64 *dst = a.states + (size_t)n * S * HW;
+  // ---- T = the q-th largest key: the largest T with #{key >= T} >= q (q <= live latents: T > 0).  SEED_KREG chunks
+  // of keys at a time in registers, so that one LDS round trip serves that many ballots; H <= 1024: they stay there
+  u64 kreg[SEED_KREG];
+  if (NG == 1) {
+#pragma unroll
+    for (int u = 0; u < SEED_KREG; u++) kreg[u] = u < NC ? keys[64 * u + lane] : 0ull;
+  }
+  u64 T = 0ull;
+  for (int bit = 63; bit >= 0; bit--) {
+    const u64 cand = T | (1ull << bit);
+    int cnt = 0;
+    for (int g = 0; g < NG; g++) {
+      if (NG > 1) {
+#pragma unroll
+        for (int u = 0; u < SEED_KREG; u++) kreg[u] = SEED_KREG * g + u < NC ? keys[64 * (SEED_KREG * g + u) + lane] : 0ull;
+      }
+#pragma unroll
+      for (int u = 0; u < SEED_KREG; u++) cnt += __popcll(__ballot(kreg[u] >= cand));  // (absent chunks: key 0)
+    }
+    if (cnt >= q) T = cand;
+  }
+  // ---- members in ascending j: every key above T, then keys equal to T while there is room
+  int n_gt = 0;
+  for (int g = 0; g < NG; g++) {
+    if (NG > 1) {
+#pragma unroll
+      for (int u = 0; u < SEED_KREG; u++) kreg[u] = SEED_KREG * g + u < NC ? keys[64 * (SEED_KREG * g + u) + lane] : 0ull;
+    }
+#pragma unroll
+    for (int u = 0; u < SEED_KREG; u++) n_gt += __popcll(__ballot(kreg[u] > T));
+  }
+  int room = q - n_gt, pos = 0;  // wave-uniform
+  for (int c = 0; c < NC; c++) {
+    const int j = 64 * c + lane;
+    const u64 k = keys[j];
+    const u64 eqm = __ballot(k == T);
+    const int before = __popcll(eqm & ((1ull << lane) - 1ull));
+    const bool mem = k > T || (k == T && before < room);
+    const u64 mm = __ballot(mem);
+    const int at = pos + __popcll(mm & ((1ull << lane) - 1ull));
+    if (mem && at < Q) sel[at] = j, selk[at] = k;
+    const int took = __popcll(eqm);
+    room -= took < room ? took : room;
+    pos += __popcll(mm);
+  }
+  seed_wave_sync();
+  // ---- rank within the list (it is in ascending j): keys above mine, equal keys in front of me
+  for (int m0 = 0; m0 < q; m0 += 64) {
+    const int m = m0 + lane;
+    const bool mine = m < q;
+    const int jm = sel[mine ? m : 0];
+    const u64 km = selk[mine ? m : 0];
+    int rank = 0;
+#pragma unroll 8
+    for (int i = 0; i < q; i++) {
+      const u64 ki = selk[i];
+      rank += (ki > km || (ki == km && i < m)) ? 1 : 0;
+    }
+    if (mine && rank < Q) byrank[rank] = jm;
+  }
+  seed_wave_sync();
+  // ---- the q states and their digests
+  for (int idx = lane; idx < q * HW; idx += 64) {
+    const int r = idx / HW, w = idx - r * HW;
+    const int j = guard_index(byrank[r], H, a.err);
+    dst[(size_t)(slot0 + r) * HW + w] = base[w] | ((j >> 6) == w ? (0x8000000000000000ull >> (j & 63)) : 0ull);
+  }
+  if (a.dig)
+    for (int r = lane; r < q; r += 64) {
+      const int j = guard_index(byrank[r], H, a.err);
+      u64 d = 0;
+      int k = 0;
+      bool ins = false;
+      for (int i = 0; i < t - 1 && k < DIG_SLOTS; i++) {
+        const int h = sorted[i];
+        if (!ins && j < h) {
+          digest_add(d, k, j);
+          ins = true;
+        }
+        digest_add(d, k, h);
+      }
+      if (!ins) digest_add(d, k, j);
+      a.dig[(size_t)n * S + slot0 + r] = digest_close(d, t);
+    }
+  // ---- the winner joins the active set
+  const int jw = guard_index(__builtin_amdgcn_readfirstlane(byrank[0]), H, a.err);
+  const double sw = seed_unkey(seed_uniform(keys[jw]));
+  if (lane == 0) {
+    if (a.path) a.path[(size_t)n * A + t - 1] = jw;
+    if (a.lpj_path) a.lpj_path[(size_t)n * A + t - 1] = sw;
+  }
+  sw_out = sw;
+  seed_wave_sync();  // everybody has read sorted / base / keys
+  if (lane == 0) {
+    path[t - 1] = jw;
+    int i = t - 1;  // insertion into the ascending list
+    while (i > 0 && sorted[i - 1] > jw) {
+      sorted[i] = sorted[i - 1];
+      i--;
+    }
+    sorted[i] = jw;
+    base[jw >> 6] |= 0x8000000000000000ull >> (jw & 63);
+  }
+  return jw;
+}
+
 template <bool SSSC>
 __global__ __launch_bounds__(256) void seed_states_kernel(SeedArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char seed_lds[];
   const int lane = lane_id(), wave = wave_id_uniform();
   const int W = (int)(blockDim.x >> 6);
   const int S = a.S, H = a.H, HW = a.HW, A = a.A, Hp = a.Hp, Q = a.Q;
-  const int NC = Hp >> 6, NG = (NC + SEED_KREG - 1) / SEED_KREG;  // chunks of 64 latents, register loads of SEED_KREG chunks
-  unsigned char *home = seed_lds + (size_t)wave * seed_wave_bytes(Hp, HW, Q, A);
-  u64 *keys = (u64 *)home;
-  double *cc = (double *)(keys + Hp);
-  u64 *base = (u64 *)(cc + Hp);
-  double *shd = (double *)(base + HW);
-  const SeedShared sh = {shd, shd + SEED_M * SEED_M, shd + 2 * SEED_M * SEED_M, shd + 3 * SEED_M * SEED_M,
-                         shd + 3 * SEED_M * SEED_M + SEED_M, shd + 3 * SEED_M * SEED_M + 2 * SEED_M};
-  u64 *selk = (u64 *)(shd + SEED_SHARED_DOUBLES);
-  int *sel = (int *)(selk + Q);
-  int *byrank = sel + Q;
-  int *path = byrank + Q;
-  int *sorted = path + A;
+  const int NC = Hp >> 6;  // chunks of 64 latents
+  const SeedLds L = seed_carve(seed_lds + (size_t)wave * seed_wave_bytes(Hp, HW, Q, A), Hp, HW, Q, A);
+  u64 *keys = L.keys, *base = L.base;
+  double *cc = L.cc;
   const double pre1 = SSSC ? 0.0 : a.dpar[DP_PRE1];
   const double pilb = SSSC ? 0.0 : a.dpar[DP_PILBAR];
   const double s2inv = SSSC ? a.dpar[DP_S2INV] : 0.0;
@@ -229,7 +445,6 @@ __global__ __launch_bounds__(256) void seed_states_kernel(SeedArgs a) {
   for (i64 n = (i64)blockIdx.x * W + wave; n < a.N; n += (i64)gridDim.x * W) {
     const double *Bn = a.Bm + (size_t)n * H;
     const double yy = a.yy[n];
-    u64 *dst = a.states + (size_t)n * S * HW;
     for (int w = lane; w < HW; w += 64) base[w] = 0ull;
     if (!SSSC)  // e_j = G_jj - 2 B_nj; eight chunks of loads in flight
       for (int c0 = 0; c0 < NC; c0 += 8) {
@@ -253,166 +468,25 @@ __global__ __launch_bounds__(256) void seed_states_kernel(SeedArgs a) {
       // ---- scores -> keys
       int act[SEED_MAX_A_SSSC];
       double pbA = 0.0;
-      if (SSSC) {
-        const int m = t - 1;
-#pragma unroll
-        for (int i = 0; i < SEED_MAX_A_SSSC; i++)
-          act[i] = i < m ? guard_index(__builtin_amdgcn_readfirstlane(path[i]), H, a.err) : 0;
-        // the blocks of A_{t-1}: lane i m + c holds entry (i, c)
-        const int bi = lane / (m > 0 ? m : 1), bc = lane - bi * (m > 0 ? m : 1);
-        const bool in_block = m > 0 && lane < m * m;
-        if (in_block) {
-          const double2 e = a.GP[(size_t)guard_index(path[bi], H, a.err) * H + guard_index(path[bc], H, a.err)];
-          sh.GA[bi * SEED_M + bc] = e.x;
-          sh.PA[bi * SEED_M + bc] = e.y;
-        }
-        if (lane < m) {
-          const int h = guard_index(path[lane], H, a.err);
-          sh.muA[lane] = a.mus[h];
-          sh.bA[lane] = Bn[h];
-        }
-        seed_wave_sync();
-        if (in_block) {
-          double s = 0.0;
-          for (int l = 0; l < m; l++) s += sh.PA[bi * SEED_M + l] * sh.GA[l * SEED_M + bc];
-          sh.TA[bi * SEED_M + bc] = (bi == bc ? 1.0 : 0.0) + s2inv * s;
-        }
-        if (lane < m) {
-          double s = sh.bA[lane];
-          for (int l = 0; l < m; l++) s -= sh.GA[lane * SEED_M + l] * sh.muA[l];
-          sh.vA[lane] = s;
-        }
-        for (int i = 0; i < m; i++) pbA += a.pil_bar[guard_index(path[i], H, a.err)];
-        seed_wave_sync();
-      }
+      if (SSSC) pbA = seed_form_blocks(a, L, t, lane, Bn, s2inv, act, nullptr);
       for (int c = 0; c < NC; c++) {
         const int j = 64 * c + lane;
         u64 key = 0ull;
         const bool live = j < H && !((base[j < H ? j >> 6 : 0] >> (63 - (j & 63))) & 1ull);
         if (live) {
           double sc;
-          if (SSSC) {
-            switch (t) {
-              case 1: sc = seed_score_sssc<1>(a, sh, act, pbA, j, Bn, yy, s2inv); break;
-              case 2: sc = seed_score_sssc<2>(a, sh, act, pbA, j, Bn, yy, s2inv); break;
-              case 3: sc = seed_score_sssc<3>(a, sh, act, pbA, j, Bn, yy, s2inv); break;
-              case 4: sc = seed_score_sssc<4>(a, sh, act, pbA, j, Bn, yy, s2inv); break;
-              case 5: sc = seed_score_sssc<5>(a, sh, act, pbA, j, Bn, yy, s2inv); break;
-              case 6: sc = seed_score_sssc<6>(a, sh, act, pbA, j, Bn, yy, s2inv); break;
-              case 7: sc = seed_score_sssc<7>(a, sh, act, pbA, j, Bn, yy, s2inv); break;
-              default: sc = seed_score_sssc<8>(a, sh, act, pbA, j, Bn, yy, s2inv); break;
-            }
-          } else {
+          if (SSSC)
+            sc = seed_score_sssc_step<false>(t, a, L.sh, act, pbA, j, Bn, yy, s2inv, nullptr);
+          else
             sc = lpj_base + pilb + pre1 * cc[j];
-          }
           key = seed_key(sc);
         }
         keys[j] = key;
       }
       seed_wave_sync();
-      // ---- T = the q-th largest key: the largest T with #{key >= T} >= q (q <= live latents: T > 0).  SEED_KREG chunks
-      // of keys at a time in registers, so that one LDS round trip serves that many ballots; H <= 1024: they stay there
-      u64 kreg[SEED_KREG];
-      if (NG == 1) {
-#pragma unroll
-        for (int u = 0; u < SEED_KREG; u++) kreg[u] = u < NC ? keys[64 * u + lane] : 0ull;
-      }
-      u64 T = 0ull;
-      for (int bit = 63; bit >= 0; bit--) {
-        const u64 cand = T | (1ull << bit);
-        int cnt = 0;
-        for (int g = 0; g < NG; g++) {
-          if (NG > 1) {
-#pragma unroll
-            for (int u = 0; u < SEED_KREG; u++) kreg[u] = SEED_KREG * g + u < NC ? keys[64 * (SEED_KREG * g + u) + lane] : 0ull;
-          }
-#pragma unroll
-          for (int u = 0; u < SEED_KREG; u++) cnt += __popcll(__ballot(kreg[u] >= cand));  // (absent chunks: key 0)
-        }
-        if (cnt >= q) T = cand;
-      }
-      // ---- members in ascending j: every key above T, then keys equal to T while there is room
-      int n_gt = 0;
-      for (int g = 0; g < NG; g++) {
-        if (NG > 1) {
-#pragma unroll
-          for (int u = 0; u < SEED_KREG; u++) kreg[u] = SEED_KREG * g + u < NC ? keys[64 * (SEED_KREG * g + u) + lane] : 0ull;
-        }
-#pragma unroll
-        for (int u = 0; u < SEED_KREG; u++) n_gt += __popcll(__ballot(kreg[u] > T));
-      }
-      int room = q - n_gt, pos = 0;  // wave-uniform
-      for (int c = 0; c < NC; c++) {
-        const int j = 64 * c + lane;
-        const u64 k = keys[j];
-        const u64 eqm = __ballot(k == T);
-        const int before = __popcll(eqm & ((1ull << lane) - 1ull));
-        const bool mem = k > T || (k == T && before < room);
-        const u64 mm = __ballot(mem);
-        const int at = pos + __popcll(mm & ((1ull << lane) - 1ull));
-        if (mem && at < Q) sel[at] = j, selk[at] = k;
-        const int took = __popcll(eqm);
-        room -= took < room ? took : room;
-        pos += __popcll(mm);
-      }
-      seed_wave_sync();
-      // ---- rank within the list (it is in ascending j): keys above mine, equal keys in front of me
-      for (int m0 = 0; m0 < q; m0 += 64) {
-        const int m = m0 + lane;
-        const bool mine = m < q;
-        const int jm = sel[mine ? m : 0];
-        const u64 km = selk[mine ? m : 0];
-        int rank = 0;
-#pragma unroll 8
-        for (int i = 0; i < q; i++) {
-          const u64 ki = selk[i];
-          rank += (ki > km || (ki == km && i < m)) ? 1 : 0;
-        }
-        if (mine && rank < Q) byrank[rank] = jm;
-      }
-      seed_wave_sync();
-      // ---- the q states and their digests
-      for (int idx = lane; idx < q * HW; idx += 64) {
-        const int r = idx / HW, w = idx - r * HW;
-        const int j = guard_index(byrank[r], H, a.err);
-        dst[(size_t)(slot0 + r) * HW + w] = base[w] | ((j >> 6) == w ? (0x8000000000000000ull >> (j & 63)) : 0ull);
-      }
-      if (a.dig)
-        for (int r = lane; r < q; r += 64) {
-          const int j = guard_index(byrank[r], H, a.err);
-          u64 d = 0;
-          int k = 0;
-          bool ins = false;
-          for (int i = 0; i < t - 1 && k < DIG_SLOTS; i++) {
-            const int h = sorted[i];
-            if (!ins && j < h) {
-              digest_add(d, k, j);
-              ins = true;
-            }
-            digest_add(d, k, h);
-          }
-          if (!ins) digest_add(d, k, j);
-          a.dig[(size_t)n * S + slot0 + r] = digest_close(d, t);
-        }
-      // ---- the winner joins the active set
-      const int jw = guard_index(__builtin_amdgcn_readfirstlane(byrank[0]), H, a.err);
-      const double sw = seed_unkey(seed_uniform(keys[jw]));
-      if (lane == 0) {
-        if (a.path) a.path[(size_t)n * A + t - 1] = jw;
-        if (a.lpj_path) a.lpj_path[(size_t)n * A + t - 1] = sw;
-      }
+      double sw;
+      const int jw = seed_select_step(a, L, n, t, q, slot0, lane, sw);
       lpj_base = sw;
-      seed_wave_sync();  // everybody has read sorted / base / keys
-      if (lane == 0) {
-        path[t - 1] = jw;
-        int i = t - 1;  // insertion into the ascending list
-        while (i > 0 && sorted[i - 1] > jw) {
-          sorted[i] = sorted[i - 1];
-          i--;
-        }
-        sorted[i] = jw;
-        base[jw >> 6] |= 0x8000000000000000ull >> (jw & 63);
-      }
       if (!SSSC && t < A) {
         const double *Gw = a.G + (size_t)jw * H;  // c_j -= G_wj: e_j += 2 G_wj
         for (int c0 = 0; c0 < NC; c0 += 8) {
@@ -426,6 +500,124 @@ __global__ __launch_bounds__(256) void seed_states_kernel(SeedArgs a) {
           for (int u = 0; u < 8; u++)
             if (c0 + u < NC) cc[64 * (c0 + u) + lane] += 2.0 * gw[u];
         }
+      }
+      seed_wave_sync();
+      slot0 += q;
+    }
+  }
+}
+
+// Incomplete data: the same law with the datapoint's own Gram rows G(n) = sum over its reliable d of W_d. W_d.^T, formed
+// from W and the resident mask (B and yy are masked already: evoamd_upload_masks zeroes the missing entries of Y).  The
+// reliable d go to a list in LDS in ascending d (ballots); a sweep runs down that list -- every lane reads W_dj coalesced
+// over j for four chunks of latents at a time and sums in the list's order, so the bits do not depend on the launch.  The
+// diagonal g_jj = sum W_dj^2 once per datapoint, the winner's row g_wj = sum (W_dw) W_dj after each step but the last
+// with the column W_dw staged in LDS.  EBSC folds both into e_j as the complete kernel does; ES3C keeps the rows of the
+// winners and the diagonal (R = A rows of Hp doubles: in LDS, or in a.rows when they do not fit).  A lane reads back only
+// the row entries it wrote itself, except for the blocks of A_{t-1}, which come after a seed_wave_sync.
+template <bool DIAG>
+__device__ __forceinline__ void seed_gram_sweep(const SeedArgs &a, int lane, const int *dl, const double *col, int nd, double *out) {
+  const int H = a.H, NC = a.Hp >> 6;
+  for (int c0 = 0; c0 < NC; c0 += 4) {
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    int jj[4];
+    bool in[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int j = 64 * (c0 + u) + lane;
+      in[u] = c0 + u < NC && j < H;
+      jj[u] = in[u] ? j : 0;
+    }
+#pragma unroll 2
+    for (int i = 0; i < nd; i++) {
+      const double *Wd = a.W + (size_t)guard_index(dl[i], a.D, a.err) * H;
+      const double cw = DIAG ? 0.0 : col[i];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const double w = in[u] ? Wd[jj[u]] : 0.0;
+        acc[u] = fma(DIAG ? w : cw, w, acc[u]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+      if (c0 + u < NC) out[64 * (c0 + u) + lane] = acc[u];
+  }
+}
+
+template <bool SSSC>
+__global__ __launch_bounds__(256) void seed_states_masked_kernel(SeedArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char seed_lds[];
+  const int lane = lane_id(), wave = wave_id_uniform();
+  const int W = (int)(blockDim.x >> 6);
+  const int S = a.S, H = a.H, HW = a.HW, A = a.A, Hp = a.Hp, Q = a.Q, D = a.D, R = a.R;
+  const int NC = Hp >> 6;
+  const int rows_lds = a.rows ? 0 : R;
+  unsigned char *home = seed_lds + (size_t)wave * seed_masked_wave_bytes(Hp, HW, Q, A, D, rows_lds);
+  const SeedLds L = seed_carve(home, Hp, HW, Q, A);
+  u64 *keys = L.keys, *base = L.base;
+  double *cc = L.cc;
+  double *col = (double *)(home + seed_wave_bytes(Hp, HW, Q, A));
+  double *rows = a.rows ? a.rows + ((size_t)blockIdx.x * W + wave) * R * Hp : col + D;
+  int *dl = (int *)(col + D + (size_t)rows_lds * Hp);
+  double *tmp = (double *)keys;  // EBSC: a row on its way into e (the keys of a step are dead by then)
+  const double pre1 = SSSC ? 0.0 : a.dpar[DP_PRE1];
+  const double pilb = SSSC ? 0.0 : a.dpar[DP_PILBAR];
+  const double s2inv = SSSC ? a.dpar[DP_S2INV] : 0.0;
+  const int q_lo = S / A, q_rem = S - q_lo * A;
+  for (i64 n = (i64)blockIdx.x * W + wave; n < a.N; n += (i64)gridDim.x * W) {
+    const double *Bn = a.Bm + (size_t)n * H;
+    const uint8_t *mn = a.mask + (size_t)n * D;
+    const double yy = a.yy[n];
+    for (int w = lane; w < HW; w += 64) base[w] = 0ull;
+    int nd = 0;  // the reliable d in ascending order
+    for (int d0 = 0; d0 < D; d0 += 64) {
+      const int d = d0 + lane;
+      const bool on = d < D && mn[d < D ? d : 0] != 0;
+      const u64 b = __ballot(on);
+      if (on) dl[nd + __popcll(b & ((1ull << lane) - 1ull))] = d;
+      nd += __popcll(b);
+    }
+    seed_wave_sync();
+    double *gd = SSSC ? rows + (size_t)(R - 1) * Hp : tmp;
+    seed_gram_sweep<true>(a, lane, dl, col, nd, gd);
+    if (!SSSC)  // e_j = g_jj - 2 B_nj
+      for (int c = 0; c < NC; c++) {
+        const int j = 64 * c + lane;
+        cc[j] = gd[j] - 2.0 * (j < H ? Bn[j] : 0.0);
+      }
+    seed_wave_sync();
+    double lpj_base = pre1 * yy;  // EBSC: lpj(A_{t-1})
+    int slot0 = 0;
+    for (int t = 1; t <= A; t++) {
+      const int q = q_lo + (t <= q_rem ? 1 : 0);
+      int act[SEED_MAX_A_SSSC];
+      double pbA = 0.0;
+      if (SSSC) pbA = seed_form_blocks(a, L, t, lane, Bn, s2inv, act, rows);
+      for (int c = 0; c < NC; c++) {
+        const int j = 64 * c + lane;
+        u64 key = 0ull;
+        const bool live = j < H && !((base[j < H ? j >> 6 : 0] >> (63 - (j & 63))) & 1ull);
+        if (live) {
+          double sc;
+          if (SSSC)
+            sc = seed_score_sssc_step<true>(t, a, L.sh, act, pbA, j, Bn, yy, s2inv, rows);
+          else
+            sc = lpj_base + pilb + pre1 * cc[j];
+          key = seed_key(sc);
+        }
+        keys[j] = key;
+      }
+      seed_wave_sync();
+      double sw;
+      const int jw = seed_select_step(a, L, n, t, q, slot0, lane, sw);
+      lpj_base = sw;
+      if (t < A) {  // the winner's row of G(n)
+        for (int i = lane; i < nd; i += 64) col[i] = a.W[(size_t)guard_index(dl[i], D, a.err) * H + jw];
+        seed_wave_sync();
+        double *gw = SSSC ? rows + (size_t)(t - 1) * Hp : tmp;
+        seed_gram_sweep<false>(a, lane, dl, col, nd, gw);
+        if (!SSSC)  // c_j -= g_wj: e_j += 2 g_wj
+          for (int c = 0; c < NC; c++) cc[64 * c + lane] += 2.0 * gw[64 * c + lane];
       }
       seed_wave_sync();
       slot0 += q;

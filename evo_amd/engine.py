@@ -136,19 +136,26 @@ class Engine:
             tp = u8ptr(packed)
         check(self.lib.evoamd_init_states(self._h, float(p_init), int(seed) & (2 ** 64 - 1), int(max_rounds), tp))
 
-    def seed_states(self, max_active, want_path=False):
+    def seed_states(self, max_active, want_path=False, incomplete=False):
         """K^n seeded on the device from Theta and the data by greedy forward selection on the model's own lpj
         (evoamd_seed_states; evo_amd.variational.seed_states_host is its NumPy mirror): deterministic, ``max_active``
         steps per datapoint, S distinct states of 1 .. max_active latents in step-major slots.  ``want_path``: returns
         (path int32 (N, max_active), lpj_path (N, max_active)) -- the latent added at each step and its state's lpj --
-        else None.  EvoAmdError naming the rule, with K^n left as it was, for a missing Theta, incomplete data, the
-        background unit, the float32 mode, bsc_direct or a ``max_active`` the law refuses."""
+        else None.  ``incomplete`` permits incomplete data (evoamd_seed_states_ex, EVOAMD_SEED_INCOMPLETE): with masks
+        resident (upload_masks) the law runs on each datapoint's reliable entries, its Gram rows formed from W and the
+        mask; without masks the flag changes nothing.  EvoAmdError naming the rule, with K^n left as it was, for a
+        missing Theta, masks present without ``incomplete``, the background unit, the float32 mode, bsc_direct or a
+        ``max_active`` the law refuses."""
         A = int(max_active)
         path = lpj = None
         if want_path:
             path = np.empty((self.N, max(A, 1)), dtype=np.int32)
             lpj = np.empty((self.N, max(A, 1)), dtype=np.float64)
-        check(self.lib.evoamd_seed_states(self._h, A, i32ptr(path) if want_path else None, dptr(lpj) if want_path else None))
+        pp, lp = (i32ptr(path), dptr(lpj)) if want_path else (None, None)
+        if incomplete:
+            check(self.lib.evoamd_seed_states_ex(self._h, A, _lib.SEED_INCOMPLETE, pp, lp))
+        else:
+            check(self.lib.evoamd_seed_states(self._h, A, pp, lp))
         return (path, lpj) if want_path else None
 
     # ---- samples from the model ------------------------------------------------------------

@@ -318,7 +318,7 @@ class Model:
 
     def seed_resident_states(self, model_params, my_data, parent_selection, mutation_algorithm, no_parents, no_children,
                              no_generations, max_active=None, bitflip_prob=None, Mprime=None, permanent=None,
-                             want_path=False):
+                             want_path=False, incomplete=False):
         """``init_states`` for this rank's ``my_data`` with K^n SEEDED on the device from ``model_params`` and the data
         (Engine.seed_states; evo_amd.variational.seed_states_host is the NumPy mirror): greedy forward selection on the
         model's own lpj, deterministic -- the start for codes, reconstructions, predictive moments or samples from a
@@ -327,8 +327,11 @@ class Model:
         init_resident_states' sync_host behaviour ("ss" / "lpj" None with sync_host=False; with sync_host=True "ss" is
         downloaded once); the lpj rows of the seeded K^n are computed on the device right away (sync_host=True: "lpj"
         holds them), so encode(), predictive_moments() and sample_posterior() can follow without an E-step.
-        ``want_path``: self.last_seed_path = (path, lpj_path), else None.  ValueError for incomplete data, the
-        background unit and a ``max_active`` the law refuses; NotImplementedError in the float32 mode."""
+        ``want_path``: self.last_seed_path = (path, lpj_path), else None.  ``incomplete=True`` admits my_data["x_infr"]
+        with False entries (inpainting, imputation): the masks go up as for any E-step and every datapoint is seeded on
+        its reliable entries alone -- values of y under False, NaN included, never enter.  ValueError for incomplete
+        data without ``incomplete=True``, the background unit and a ``max_active`` the law refuses; NotImplementedError
+        in the float32 mode."""
         from ..variational.utils import seed_quotas
         N, H = my_data["y"].shape[0], self.H
         permanent = permanent or {"background": False, "allzero": False, "singletons": False}
@@ -336,8 +339,9 @@ class Model:
             raise ValueError("seed_resident_states: the background unit is not supported")
         if self.dtype == np.float32:
             raise NotImplementedError("seed_resident_states is not available in the float32 mode")
-        if not self._complete(my_data):
-            raise ValueError("seed_resident_states: incomplete data (x_infr with False entries) is not supported")
+        if not incomplete and not self._complete(my_data):
+            raise ValueError("seed_resident_states: incomplete data (x_infr with False entries) is not supported "
+                             "by default: pass incomplete=True")
         if max_active is None:
             max_active = min(8, self.S, H)
         seed_quotas(self.S, H, max_active, self.model_name != "bsc")
@@ -353,7 +357,7 @@ class Model:
         self.E_step_precompute(dict(model_params), dict(suff), my_data)
         if model_params is not self._dev_theta:
             self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
-        self.last_seed_path = eng.seed_states(max_active, want_path=want_path)
+        self.last_seed_path = eng.seed_states(max_active, want_path=want_path, incomplete=bool(incomplete))
         self._resident = True
         eng.lpj_resident()
         if self.sync_host:

@@ -278,14 +278,18 @@ def _seed_gap(a, b):
     return (a - b) / max(1.0, abs(a))
 
 
-def seed_states_host(model, theta, Y, S, max_active, S_perm=0):
+def seed_states_host(model, theta, Y, S, max_active, S_perm=0, x_infr=None):
     """K^n as evoamd_seed_states / Model.seed_resident_states lay it out.  ``model``: "bsc" or "sssc"; ``theta``: W, pi,
     sigma (EBSC) or W, pies, mus, Psi, sigma2 (ES3C); ``Y`` (N, D) complete data; ``S`` varying states per datapoint (the
     permanent all-zero state of ``S_perm`` = 1 is not among them and is never produced).  Returns (states, path,
     lpj_path, margin): states bool (N, S, H); path int32 (N, A), the latent added at each step; lpj_path (N, A), the
     winner's score; margin (N,), the smallest relative gap (a - b) / max(1, |a|) over the steps of a datapoint between
     the winner and the runner-up and between rank q_t - 1 and rank q_t -- a datapoint whose margin is far above the
-    rounding error of the scores is decided the same way by any correct implementation."""
+    rounding error of the scores is decided the same way by any correct implementation.
+    ``x_infr`` bool (N, D), incomplete data: datapoint n is scored on its reliable entries o = x_infr[n] alone --
+    G(n) = W_o^T W_o, B_n = y_o^T W_o, yy_n = |y_o|^2 (the lpj of the reference's W[this_x_infr, :] branches); entries of Y
+    under False are never read as numbers (NaN included); a datapoint without a reliable entry is scored by the prior
+    alone.  None: complete data."""
     sssc = model not in ("bsc", "BSC", "ebsc")
     assert S_perm in (0, 1)
     W = np.asarray(theta["W"], dtype=np.float64)
@@ -294,19 +298,31 @@ def seed_states_host(model, theta, Y, S, max_active, S_perm=0):
     assert Y.shape == (N, D)
     A = int(max_active)
     quotas = seed_quotas(int(S), H, A, sssc)
-    G, B, yy = W.T @ W, Y @ W, (Y * Y).sum(axis=1)
+    if x_infr is None:
+        G, B, yy = W.T @ W, Y @ W, (Y * Y).sum(axis=1)
+    else:
+        x_infr = np.asarray(x_infr, dtype=bool)
+        assert x_infr.shape == (N, D)
+        Y = np.where(x_infr, Y, 0.0)
+        G, B, yy = None, Y @ W, (Y * Y).sum(axis=1)
     if sssc:
         mus, Psi = np.asarray(theta["mus"], dtype=np.float64), np.asarray(theta["Psi"], dtype=np.float64)
         pies = np.asarray(theta["pies"], dtype=np.float64)
         pil_bar, s2inv = np.log(pies / (1.0 - pies)), 1.0 / float(theta["sigma2"])
     else:
         pi, sigma = float(theta["pi"]), float(theta["sigma"])
-        pre1, pil_bar, Gd = -1.0 / 2.0 / sigma / sigma, np.log(pi / (1.0 - pi)), np.diag(G).copy()
+        pre1, pil_bar = -1.0 / 2.0 / sigma / sigma, np.log(pi / (1.0 - pi))
+        Gd = None if G is None else np.diag(G).copy()
     states = np.zeros((N, S, H), dtype=bool)
     path = np.zeros((N, A), dtype=np.int32)
     lpj_path = np.zeros((N, A))
     margin = np.full(N, np.inf)
+    masked = x_infr is not None
     for n in range(N):
+        if masked:  # the datapoint's own Gram matrix, from the reliable rows of W
+            Wo = W[x_infr[n]]
+            G = Wo.T @ Wo
+            Gd = np.diag(G).copy()
         active, free = [], np.ones(H, dtype=bool)
         c, base, slot = B[n].copy(), (0.0 if sssc else pre1 * yy[n]), 0
         for t, q in enumerate(quotas, start=1):

@@ -251,10 +251,24 @@ int evoamd_init_states(evoamd_ctx *ctx, double p_init, uint64_t seed, int max_ro
  * Refused with EVOAMD_E_INVALID before anything is written (K^n and its validity stay as they were): no Theta installed
  * or no data, incomplete data (masks present), option "background_unit", "ebsc_f32", "bsc_direct" (there is no G),
  * max_active < 1, > S, > H, > 8 (ES3C) or > 64 (EBSC), a quota q_t > H - (t - 1), or an H whose scores do not fit one
- * wavefront's share of LDS (16 H bytes; about H = 9000).  Incomplete data and the background unit are out of scope.
+ * wavefront's share of LDS (16 H bytes; about H = 9000).  Incomplete data needs evoamd_seed_states_ex; the background unit
+ * is out of scope.
  * Like evoamd_init_states it writes the digests too; a prefetched pass, the census and the statistics rows are dropped
  * and the lpj rows on the device no longer belong to K^n afterwards. */
 int evoamd_seed_states(evoamd_ctx *ctx, int max_active, int32_t *path_out, double *lpj_out);
+/* evoamd_seed_states with flags (0: exactly evoamd_seed_states, every refusal and its text included).
+ * EVOAMD_SEED_INCOMPLETE permits incomplete data; it is a permission, not a mode: with masks resident
+ * (evoamd_upload_masks) the same law runs with the Gram quantities of the datapoint's reliable entries o = x_infr[n] --
+ * G(n) = W_o^T W_o formed per datapoint from W and the resident mask, B_n = y_o^T W_o and |y_o|^2 as evoamd_upload_masks
+ * left them (it zeroes the missing entries of Y); Psi, mu, pil_bar, sigma2 and pre1 are not masked -- the lpj that
+ * evoamd_lpj_resident computes on masked data.  A datapoint without a reliable entry is scored by the prior alone (EBSC:
+ * all equal, so the slots fill in ascending j).  Without masks the complete kernel runs, unchanged.  Refused as above with
+ * the flag too: "background_unit", "ebsc_f32", "bsc_direct", a bad max_active or quota, an unknown flag, and scores plus the
+ * staged column of W (16 H + 12 D bytes) that do not fit one wavefront's share of LDS.  ES3C keeps max_active rows of
+ * G(n) per wavefront: in LDS while 8 max_active ceil64(H) more bytes fit, else in a buffer of the context grown on demand.
+ * No atomics, a fixed summation order: two calls give the same bits. */
+#define EVOAMD_SEED_INCOMPLETE 1u
+int evoamd_seed_states_ex(evoamd_ctx *ctx, int max_active, unsigned flags, int32_t *path_out, double *lpj_out);
 /* my_suff_stat["lpj"] (N,S_perm+S) float64. */
 int evoamd_upload_lpj(evoamd_ctx *ctx, const double *lpj);
 int evoamd_download_lpj(evoamd_ctx *ctx, double *lpj);

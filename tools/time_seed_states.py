@@ -9,7 +9,11 @@ generate_data_device from a sparse Theta (pi H = 3, Gaussian W * 0.8, noise 0.3;
   start   the first free energy of an E-step (rng="device") from the seeded K^n, and the number of E-steps a start from
           init_resident_states needs on the same data and Theta before its free energy passes it (at most ``--esteps``).
 
-    python tools/time_seed_states.py [--config c4|c5|both] [--n N] [--reps 5] [--host-n 30] [--esteps 60]
+``--missing FRACTION`` (default 0: all of the above on complete data, nothing else): an i.i.d. mask hides that fraction of
+the entries (NaN in the data); the masked call (evoamd_seed_states_ex, EVOAMD_SEED_INCOMPLETE) is timed beside the
+complete call in the same run, and ``mirror`` and ``start`` run on the masked data.
+
+    python tools/time_seed_states.py [--config c4|c5|both] [--n N] [--reps 5] [--host-n 30] [--esteps 60] [--missing 0.5]
 """
 import argparse
 import os
@@ -47,30 +51,48 @@ def run(name, args):
     Y = model.generate_data_device(theta, N, seed=7, keep=("y",))["y"]
     my_data = {"y": Y, "x_infr": np.ones_like(Y, dtype=bool)}
     tag = "%s %s D=%d H=%d S=%d N=%d A=%d" % (name, algo, D, H, S, N, A)
+    masked = args.missing > 0
+    x_infr = None
+
+    def time_device(what, incomplete):
+        eng.timing(["seed_states"])
+        t = []
+        for _ in range(args.reps):
+            eng.timing_reset()
+            eng.seed_states(A, incomplete=incomplete)
+            t.append(eng.kernel_time_ms("seed_states")[0])
+        eng.timing(False)
+        t = np.array(t)
+        print("device seed_states %s %s: mean %.3f ms, median %.3f, min %.3f, max %.3f (%d launches)"
+              % (what, tag, t.mean(), np.median(t), t.min(), t.max(), t.size), flush=True)
+        return np.median(t)
+
     # ---- device
     suff = model.seed_resident_states(dict(theta), my_data, *EA, max_active=A)  # warm-up
     eng = model.engine
-    eng.timing(["seed_states"])
-    t = []
-    for _ in range(args.reps):
-        eng.timing_reset()
-        eng.seed_states(A)
-        t.append(eng.kernel_time_ms("seed_states")[0])
-    eng.timing(False)
-    t = np.array(t)
-    print("device seed_states %s: mean %.3f ms, median %.3f, min %.3f, max %.3f (%d launches)"
-          % (tag, t.mean(), np.median(t), t.min(), t.max(), t.size), flush=True)
+    t_complete = time_device("complete", False)
+    if masked:  # the same run, the same engine: the masked call beside the complete one
+        x_infr = np.random.RandomState(11).random_sample(Y.shape) >= args.missing
+        my_data = {"y": np.where(x_infr, Y, np.nan), "x_infr": x_infr, "x": x_infr.copy()}
+        tag += " missing=%.2f" % args.missing
+        model = cls(D, H, S, rng="device", sync_host=False, seed=1, engine=eng)
+        suff = model.seed_resident_states(dict(theta), my_data, *EA, max_active=A, incomplete=True)  # warm-up
+        t_masked = time_device("masked", True)
+        print("device seed_states %s: masked / complete = %.2f (medians)" % (tag, t_masked / t_complete), flush=True)
     # ---- the start it gives
     if args.esteps > 0:
         eng.lpj_resident()
         th = dict(theta)
-        F_seed = model.E_step(th, suff, my_data)[0]
+        # (incomplete data: the statistics pass of an E-step reads y_reconstructed, which _reconstruct forms first, as
+        # step(do_reconstruction=True) does; each model gets its own dict to write it into)
+        F_seed = model.E_step(th, suff, my_data, _reconstruct=masked)[0]
+        my_data = dict(my_data)
         other = cls(D, H, S, rng="device", sync_host=False, seed=1, engine=eng)
         noise = other.init_resident_states(my_data, *EA, seed=3)
         th2, n_steps, F = dict(theta), 0, -np.inf
         F_first = None
         while n_steps < args.esteps and not F > F_seed:
-            F = other.E_step(th2, noise, my_data)[0]
+            F = other.E_step(th2, noise, my_data, _reconstruct=masked)[0]
             n_steps += 1
             if F_first is None:
                 F_first = F
@@ -82,7 +104,7 @@ def run(name, args):
     if args.host_n > 0:
         n = min(args.host_n, N)
         t0 = time.perf_counter()
-        seed_states_host("bsc" if algo == "ebsc" else "sssc", theta, Y[:n], S, A)
+        seed_states_host("bsc" if algo == "ebsc" else "sssc", theta, Y[:n], S, A, x_infr=x_infr[:n] if masked else None)
         dt = time.perf_counter() - t0
         print("mirror seed_states_host %s on one core: %.2f s for %d datapoints; extrapolated to N=%d: %.0f s"
               % (tag, dt, n, N, dt * N / n), flush=True)
@@ -96,6 +118,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-n", type=int, default=30)
     ap.add_argument("--esteps", type=int, default=60)
+    ap.add_argument("--missing", type=float, default=0.0, help="fraction of entries hidden by an i.i.d. mask (0: complete data)")
     args = ap.parse_args()
     for name in (["c4", "c5"] if args.config == "both" else [args.config]):
         run(name, args)
