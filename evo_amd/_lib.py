@@ -94,6 +94,9 @@ SIGNATURES = {
     "evoamd_estep_counters": (_I, [_vp, ctypes.POINTER(_I64)]),
     "evoamd_evolve_states": (_I, [_vp, _I, _I, _I, _I, _I, _U64, _DBL, _DBL]),
     "evoamd_download_candidates": (_I, [_vp, _c_u8p, _c_i32p, _c_dp]),
+    "evoamd_refine_states": (_I, [_vp, _I, _I, _I, _I, _I, _I, _U64, _U64, _DBL, _DBL, _I, _I, _I, _DBL, _c_dp,
+                                  ctypes.POINTER(_I)]),
+    "evoamd_posterior_scores": (_I, [_vp, _c_dp, _c_dp, _c_i32p, _c_i32p, _c_dp]),
     "evoamd_acc_size": (_I64, [_vp]),
     "evoamd_stats": (_I, [_vp, _c_dp]),
     "evoamd_mstep_device": (_I, [_vp, _I, _c_dp, _c_dp]),

@@ -33,6 +33,7 @@
 #include "kernels_predictive.hpp"
 #include "kernels_posterior_sample.hpp"
 #include "kernels_seed.hpp"
+#include "kernels_refine.hpp"
 
 // ---------------------------------------------------------------------------------------
 // error handling
@@ -539,6 +540,9 @@ struct evoamd_ctx {
   DevBuf<u64> init_scratch;
   DevBuf<double2> seed_gpt;  // evoamd_seed_states, ES3C: the transpose of GP (H x H), grown on demand, rewritten by every call
   DevBuf<double> seed_rows;  // evoamd_seed_states_ex, ES3C on incomplete data: the rows of G(n) that do not fit LDS, grown on demand
+  // evoamd_refine_states: one row {Fs, new unique, swapped} per iteration; evoamd_posterior_scores: its (N) outputs.  Grown on
+  // demand, rewritten by every call, read by nothing else
+  DevBuf<double> refine_trace, score_buf;
   bool kn_lost = false;
   i64 kn_refill = 0;  // while kn_lost: rows [0, kn_refill) have been uploaded again by evoamd_upload_states_packed
   // evoamd_generate (kernels_generate.hpp): Theta^gen, the given states and the outputs of the last call, grown on demand
@@ -3107,8 +3111,9 @@ extern "C" int evoamd_estep_counters(evoamd_ctx *c, int64_t out[4]) {
   return 0;
 }
 
-extern "C" int evoamd_evolve_states(evoamd_ctx *c, int mutation, int fit_parents, int n_parents, int n_children,
-                                    int n_generations, uint64_t seed, double sparseness, double bitflip_prob) {
+// the argument checks of the general operators (evoamd_evolve_states, and evoamd_refine_states where it uses them)
+static int estep_check_evolve(const evoamd_ctx *c, int mutation, int n_parents, int n_children, int n_generations,
+                              double bitflip_prob) {
   TRY(estep_check_ready(c));
   REQUIRE(mutation >= EV_RANDFLIP && mutation <= EV_CROSS_SPARSEFLIP, "unknown mutation operator");
   REQUIRE_KN(c);
@@ -3123,7 +3128,12 @@ extern "C" int evoamd_evolve_states(evoamd_ctx *c, int mutation, int fit_parents
   const bool sparse = mutation == EV_SPARSEFLIP || mutation == EV_CROSS_SPARSEFLIP;
   REQUIRE(!sparse || bitflip_prob == bitflip_prob, "sparseflip needs bitflip_prob (eas.py:69)");
   REQUIRE(!crossing || c->H >= 2, "crossover needs H >= 2");
-  HIP_TRY(hipSetDevice(c->device));
+  return 0;
+}
+
+// ---- E-step stage: children of any operator over any number of generations, and their lpj
+static int estep_children_general(evoamd_ctx *c, int mutation, int fit_parents, int n_parents, int n_children,
+                                  int n_generations, uint64_t seed, double sparseness, double bitflip_prob) {
   if (!c->cand_raw) {
     TRY(c->cand_raw.alloc((size_t)c->N * c->Cmax * c->HW));
     TRY(c->dupold.alloc((size_t)c->N * EVG_FLAGW));
@@ -3168,6 +3178,14 @@ extern "C" int evoamd_evolve_states(evoamd_ctx *c, int mutation, int fit_parents
   return 0;
 }
 
+extern "C" int evoamd_evolve_states(evoamd_ctx *c, int mutation, int fit_parents, int n_parents, int n_children,
+                                    int n_generations, uint64_t seed, double sparseness, double bitflip_prob) {
+  TRY(estep_check_evolve(c, mutation, n_parents, n_children, n_generations, bitflip_prob));
+  HIP_TRY(hipSetDevice(c->device));
+  return estep_children_general(c, mutation, fit_parents, n_parents, n_children, n_generations, seed, sparseness,
+                                bitflip_prob);
+}
+
 extern "C" int evoamd_download_candidates(evoamd_ctx *c, uint8_t *cand_bool, int32_t *counts, double *lpj) {
   REQUIRE(c && c->configured && c->have_cand, "no resident candidate batch");
   REQUIRE(cand_bool && counts && lpj, "NULL output");
@@ -3179,6 +3197,98 @@ extern "C" int evoamd_download_candidates(evoamd_ctx *c, uint8_t *cand_bool, int
   HIP_TRY(hipMemcpyAsync(cand_bool, c->stage, (size_t)ns * c->H, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(counts, c->cand_counts, (size_t)c->N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(lpj, c->cand_lpj, (size_t)ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (c->model == EVOAMD_MODEL_SSSC) return check_err(c);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// K^n refined at fixed Theta: the E-step stages in a loop (kernels_refine.hpp).  One pass over the resident K^n at
+// entry; after that the selection kernel keeps the lpj rows current (it writes the lpj of every state it swaps in), so an
+// iteration is children, their lpj, selection and one trace row.  Never the fused kernel: it evaluates K^n itself.
+// ---------------------------------------------------------------------------------------
+static int refine_trace(evoamd_ctx *c, i64 row, int mode) {
+  SpanGuard g(c, KID_MISC);
+  refine_trace_kernel<<<1, 64, 0, c->stream>>>(c->dpar, row < 0 ? nullptr : c->refine_trace + 3 * row, mode);
+  HIP_TRY(hipGetLastError());
+  DBG_SYNC(c, "refine trace");
+  return 0;
+}
+
+extern "C" int evoamd_refine_states(evoamd_ctx *c, int n_iterations, int mutation, int fit_parents, int n_parents,
+                                    int n_children, int n_generations, uint64_t seed0, uint64_t seed_stride,
+                                    double sparseness, double bitflip_prob, int Mprime, int check_every, int patience,
+                                    double min_sub, double *trace_out, int *n_done_out) {
+  const bool fast = mutation == EV_RANDFLIP && n_generations == 1 && n_children <= EV_MAX_CHILDREN;
+  if (fast)
+    TRY(estep_check_randflip(c, n_parents, n_children));
+  else
+    TRY(estep_check_evolve(c, mutation, n_parents, n_children, n_generations, bitflip_prob));
+  TRY(estep_check_mprime(c, Mprime));
+  REQUIRE_KN(c);
+  REQUIRE(n_iterations >= 1, "evoamd_refine_states: n_iterations must be positive");
+  REQUIRE(patience <= 0 || check_every >= 1, "evoamd_refine_states: check_every must be positive when patience is");
+  REQUIRE(trace_out && n_done_out, "evoamd_refine_states: trace_out / n_done_out is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(c->refine_trace.ensure(c, (size_t)3 * n_iterations));
+  on_estep_route(c, /*fused=*/false);
+  TRY(estep_resident_pass(c));
+  TRY(refine_trace(c, -1, REFINE_TRACE_ZERO));  // (counts nobody has read yet would end up in row 0)
+  int done = 0, copied = 0;
+  while (done < n_iterations) {
+    const uint64_t seed = seed0 + (uint64_t)done * seed_stride;
+    if (fast)
+      TRY(estep_children(c, n_parents, n_children, seed, fit_parents));
+    else
+      TRY(estep_children_general(c, mutation, fit_parents, n_parents, n_children, n_generations, seed, sparseness,
+                                 bitflip_prob));
+    TRY(estep_select(c, Mprime, nullptr));
+    TRY(refine_trace(c, done, REFINE_TRACE_ROW));
+    done++;
+    if (patience > 0 && (done % check_every == 0 || done == n_iterations)) {  // the chunk's rows: the one wait of the loop
+      HIP_TRY(hipMemcpyAsync(trace_out + 3 * copied, c->refine_trace + 3 * copied, (size_t)3 * (done - copied) * sizeof(double),
+                             hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      copied = done;
+      bool quiet = done >= patience;
+      for (int t = done - patience; quiet && t < done; t++) quiet = trace_out[3 * t + 2] / (double)c->N <= min_sub;
+      if (quiet) break;
+    }
+  }
+  TRY(refine_trace(c, done - 1, REFINE_TRACE_RESTORE));
+  if (copied < done)
+    HIP_TRY(hipMemcpyAsync(trace_out + 3 * copied, c->refine_trace + 3 * copied, (size_t)3 * (done - copied) * sizeof(double),
+                           hipMemcpyDeviceToHost, c->stream));
+  *n_done_out = done;
+  if (c->model == EVOAMD_MODEL_SSSC) return check_err(c);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// F_n, the entropy of q_n, the best column and the latent counts of the resident lpj rows and K^n (kernels_refine.hpp).
+// Reads rows and states only: valid after a seed, an upload or a pass alike; nothing of the EM state changes.
+extern "C" int evoamd_posterior_scores(evoamd_ctx *c, double *F_out, double *entropy_out, int32_t *best_out,
+                                       int32_t *k_best_out, double *k_mean_out) {
+  REQUIRE(c && c->configured, "configure first");
+  REQUIRE_KN(c);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t N = (size_t)c->N;
+  TRY(c->score_buf.ensure(c, 4 * N));  // F | entropy | k_mean | best, k_best (int32)
+  double *dF = c->score_buf, *dE = dF + N, *dK = dF + 2 * N;
+  int *dbest = (int *)(dF + 3 * N), *dkbest = dbest + N;
+  {
+    SpanGuard g(c, KID_MISC);
+    posterior_score_kernel<<<cdiv(c->N, SCORE_WAVES), 64 * SCORE_WAVES, 0, c->stream>>>(
+        c->lpj, c->states, c->N, c->L, c->S, c->S_perm, c->HW, F_out ? dF : nullptr, entropy_out ? dE : nullptr,
+        best_out ? dbest : nullptr, k_best_out ? dkbest : nullptr, k_mean_out ? dK : nullptr);
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "posterior scores");
+  }
+  if (F_out) HIP_TRY(hipMemcpyAsync(F_out, dF, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (entropy_out) HIP_TRY(hipMemcpyAsync(entropy_out, dE, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (k_mean_out) HIP_TRY(hipMemcpyAsync(k_mean_out, dK, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (best_out) HIP_TRY(hipMemcpyAsync(best_out, dbest, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (k_best_out) HIP_TRY(hipMemcpyAsync(k_best_out, dkbest, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   if (c->model == EVOAMD_MODEL_SSSC) return check_err(c);
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;

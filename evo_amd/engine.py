@@ -327,6 +327,44 @@ class Engine:
                                             int(n_children), int(n_generations), int(seed) & (2 ** 64 - 1),
                                             float(sparseness), float("nan") if bitflip_prob is None else float(bitflip_prob)))
 
+    def refine_states(self, n_iterations, mutation, n_parents, n_children, n_generations, seed0, seed_stride=1,
+                      fit_parents=True, sparseness=0.0, bitflip_prob=None, Mprime=None, check_every=8, patience=0,
+                      min_sub=0.0):
+        """K^n refined at fixed Theta (evoamd_refine_states): one pass over the resident K^n, then ``n_iterations`` x
+        (children with seed ``seed0 + t * seed_stride``, their lpj, selection with ``Mprime``, default S) -- what
+        lpj_resident() followed by that many evolve_randflip / evolve_states + vary_kn calls compute, bit for bit,
+        without a host wait in between and without a statistics pass.  ``patience`` > 0: after every ``check_every``
+        iterations the loop ends once the last ``patience`` iterations all swapped at most ``min_sub`` states per
+        datapoint.  Returns (trace (n_done, 3), n_done): row t = (Fs, new unique states, swapped states) of iteration t."""
+        T = int(n_iterations)
+        trace = np.zeros((max(T, 1), 3), dtype=np.float64)
+        n_done = ctypes.c_int(0)
+        mask = 2 ** 64 - 1
+        check(self.lib.evoamd_refine_states(
+            self._h, T, self.MUTATIONS[mutation], 1 if fit_parents else 0, int(n_parents), int(n_children),
+            int(n_generations), int(seed0) & mask, int(seed_stride) & mask, float(sparseness),
+            float("nan") if bitflip_prob is None else float(bitflip_prob), self.S if Mprime is None else int(Mprime),
+            int(check_every), int(patience), float(min_sub), dptr(trace), ctypes.byref(n_done)))
+        return trace[:n_done.value], n_done.value
+
+    SCORES = ("F", "entropy", "best", "k_best", "k_mean")
+
+    def posterior_scores(self, what=SCORES):
+        """Per-datapoint scores of the lpj rows and K^n on the device (evoamd_posterior_scores;
+        evo_amd.variational.posterior_scores_host is the NumPy mirror): a dict with the (N) arrays ``what`` names --
+        "F" = logsumexp_s lpj_ns (the bound per datapoint without ljc), "entropy" of q_n, "best" (int32: the first
+        column of lpj with the row's maximum), "k_best" (int32: active latents of that state) and "k_mean" =
+        sum_s q_ns |s_s|.  No pass runs; the EM state stays as it is."""
+        what = tuple(what)
+        for name in what:
+            if name not in self.SCORES:
+                raise ValueError("posterior_scores: unknown score %r" % (name,))
+        out = {name: np.empty(self.N, dtype=np.int32 if name in ("best", "k_best") else np.float64) for name in what}
+        ptr = {name: (i32ptr(a) if a.dtype == np.int32 else dptr(a)) for name, a in out.items()}
+        check(self.lib.evoamd_posterior_scores(self._h, ptr.get("F"), ptr.get("entropy"), ptr.get("best"),
+                                               ptr.get("k_best"), ptr.get("k_mean")))
+        return out
+
     def download_candidates(self):
         """(cand bool (N,Cmax,H), counts (N,), lpj (N,Cmax)) of the resident candidate batch."""
         cand = np.empty((self.N, self.Cmax, self.H), dtype=np.bool_)

@@ -157,6 +157,20 @@ class LazyTheta(dict):
         return dict.setdefault(self, key, default)
 
 
+class RefineResult:
+    """What Model.refine_resident_states returns: ``F``, ``S_nunique``, ``S_sub`` (n_done,) per iteration, ``n_done`` (the
+    longest rank's), ``n_done_local`` (this rank's) and ``stopped_early`` (n_done < the iterations asked for)."""
+    __slots__ = ("F", "S_nunique", "S_sub", "n_done", "n_done_local", "stopped_early")
+
+    def __init__(self, F, S_nunique, S_sub, n_done, n_done_local, stopped_early):
+        self.F, self.S_nunique, self.S_sub = F, S_nunique, S_sub
+        self.n_done, self.n_done_local, self.stopped_early = int(n_done), int(n_done_local), bool(stopped_early)
+
+    def __repr__(self):
+        return "RefineResult(n_done=%d, stopped_early=%s, F=%s)" % (
+            self.n_done, self.stopped_early, self.F[-1] if self.n_done else None)
+
+
 class Model:
     model_name = None  # "bsc" | "sssc"
 
@@ -833,6 +847,75 @@ class Model:
         N = float(v["N"])
         F = model_params["ljc"] + float(v["Fs"]) / N
         return F, float(v["sum_nunique"]) / N, float(v["sum_sub"]) / N
+
+    def refine_resident_states(self, model_params, my_suff_stat, my_data, n_iterations, patience=None, min_sub=0.0,
+                               check_every=8):
+        """``n_iterations`` E-steps on K^n while ``model_params`` stays fixed -- the step between seed_resident_states (or a
+        trained model meeting new data) and encode / predictive_moments / sample_posterior / posterior_scores -- in ONE
+        library call (Engine.refine_states): K^n is evaluated once, then every iteration is children, their lpj and
+        selection; no statistics pass, no host wait in between.  The EA is my_suff_stat's, the seeds are those of
+        ``n_iterations`` successive E_step calls (same K^n as those, bit for bit), and ``self._n_steps`` advances by
+        ``n_iterations`` on every rank whatever was run.  ``patience`` (None: run them all): after every ``check_every``
+        iterations the loop ends once the last ``patience`` iterations all swapped at most ``min_sub`` states per
+        datapoint of this rank.  Returns a RefineResult: ``F`` (n_done,) = ljc + allreduce(Fs_t) / N after iteration t,
+        ``S_nunique`` and ``S_sub`` (n_done,) normalised like E_step's, ``n_done`` and ``stopped_early``.  The loop involves
+        no collective: with several ranks each stops on its own (``n_done_local``), and a rank that stopped before the
+        longest one enters the sums with its last Fs and zero counts.  sync_host=True: "ss" and "lpj" are downloaded
+        once at the end, in place; sync_host=False: only the trace crosses to the host.  The reset counters of
+        my_suff_stat stay as they are.  ValueError with rng="reference" (candidates come from the host there);
+        NotImplementedError as in E_step for an EA the device does not know."""
+        if self.rng == "reference":
+            raise ValueError("refine_resident_states needs rng='device': with rng='reference' candidates come from the host")
+        T = int(n_iterations)
+        if T < 1:
+            raise ValueError("refine_resident_states: n_iterations must be positive")
+        mut = my_suff_stat["mutation_algorithm"]
+        if mut not in self._MUTATION_NAMES:
+            raise NotImplementedError("rng='device' knows the reference's five mutation operators; got %r" % (mut,))
+        fit = my_suff_stat["parent_selection"] is eas.fitparents
+        if not fit and my_suff_stat["parent_selection"] is not eas.randparents:
+            raise NotImplementedError("rng='device' knows fitparents and randparents")
+        eng = self._prepare(my_suff_stat, my_data)
+        theta = dict(model_params)  # (the precompute stores its derived keys and zeroes the reset counters: on copies)
+        self.E_step_precompute(theta, dict(my_suff_stat), my_data)
+        if model_params is not self._dev_theta:
+            self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
+        seed0, stride = self._device_seed(), max(1, self.comm.size)
+        self._n_steps += T
+        trace, n_local = eng.refine_states(
+            T, self._MUTATION_NAMES[mut], min(my_suff_stat["n_parents"], self.S), my_suff_stat["n_children"],
+            my_suff_stat["n_generations"], seed0, stride, fit, float(theta["piH"]), my_suff_stat["bitflip_prob"],
+            my_suff_stat["Mprime"], check_every=check_every, patience=0 if patience is None else int(patience),
+            min_sub=min_sub)
+        # rows of all T iterations: {Fs, new unique, swapped, this rank still ran}; past this rank's end its last Fs
+        rows = np.zeros((T, 4))
+        rows[:n_local, :3] = trace
+        rows[:n_local, 3] = 1.0
+        rows[n_local:, 0] = trace[-1, 0]
+        rows = _reduce_array(self.comm, rows)
+        N = float(self.comm.allreduce(my_data["y"].shape[0]))
+        n_done = int(np.count_nonzero(rows[:, 3] > 0.0))
+        if self.sync_host:
+            self.sync_to_host(my_suff_stat)
+        return RefineResult(theta["ljc"] + rows[:n_done, 0] / N, rows[:n_done, 1] / N, rows[:n_done, 2] / N, n_done,
+                            n_local, n_done < T)
+
+    def posterior_scores(self, model_params, my_suff_stat, my_data):
+        """Per-datapoint scores of this rank's data under ``model_params`` and the caller's K^n / lpj: a dict with the
+        (N_loc,) arrays "F" = logsumexp_s lpj_ns (``model_params["ljc"] + F.mean()`` is the rank's free energy; the
+        counterpart over K^n of exact_log_likelihood's ll), "entropy" of q_n, "n_eff" = exp(entropy) (the effective
+        number of states), "best" (the column of lpj with the row's maximum, the first of equal ones), "k_best" (active
+        latents of that state) and "k_mean" = E_q[|s|].  For held-out data and outlier search: a low F_n is a datapoint
+        the model explains badly.  One small kernel over the rows on the device (Engine.posterior_scores;
+        evo_amd.variational.posterior_scores_host is the NumPy mirror): no pass, no communication, nothing written into
+        the three dicts, works with sync_host=False."""
+        uploads = self._kn_uploads  # (see reconstruct(): decide before _prepare() runs)
+        eng = self._prepare(my_suff_stat, my_data)
+        if self.sync_host or self._kn_uploads != uploads:
+            eng.upload_lpj(my_suff_stat["lpj"])
+        out = eng.posterior_scores()
+        out["n_eff"] = np.exp(out["entropy"])
+        return out
 
     def _stats_for_mstep(self, model_params, my_suff_stat, my_data, _from_step):
         """Accumulators for the M-step: reuse the ones E_step just produced inside step(), else

@@ -350,3 +350,29 @@ def seed_states_host(model, theta, Y, S, max_active, S_perm=0, x_infr=None):
             base = sc[0]
             slot += q
     return states, path, lpj_path, margin
+
+
+def posterior_scores_host(lpj, ss=None, S_perm=0):
+    """NumPy mirror of Engine.posterior_scores (csrc/kernels_refine.hpp): ``lpj`` (N, L) with L = S_perm + S columns,
+    ``ss`` bool (N, S, H) the states of columns S_perm .. L - 1 (columns below S_perm are the permanent all-zero
+    state).  With m = max_s lpj_ns, d_s = lpj_ns - m, w_s = exp(d_s), z = sum_s w_s it returns a dict with "F" = m +
+    log z, "entropy" = log z - sum_s w_s d_s / z (a weight that underflowed to 0 contributes 0), "best" (int32: the
+    first column with lpj_ns == m) and, when ``ss`` is given, "k_best" (int32: active latents of that state) and
+    "k_mean" = sum_s q_ns |s_s|."""
+    lpj = np.asarray(lpj, dtype=np.float64)
+    N, L = lpj.shape
+    m = lpj.max(axis=1)
+    d = lpj - m[:, None]
+    w = np.exp(d)
+    z = w.sum(axis=1)
+    wd = np.zeros_like(w)
+    np.multiply(w, d, out=wd, where=w > 0.0)
+    out = {"F": m + np.log(z), "entropy": np.log(z) - wd.sum(axis=1) / z,
+           "best": np.argmax(lpj == m[:, None], axis=1).astype(np.int32)}
+    if ss is not None:
+        ss = np.asarray(ss, dtype=bool)
+        assert ss.shape[:2] == (N, L - S_perm), (ss.shape, (N, L - S_perm))
+        k = np.concatenate((np.zeros((N, S_perm), dtype=np.int64), ss.sum(axis=2)), axis=1)
+        out["k_best"] = k[np.arange(N), out["best"]].astype(np.int32)
+        out["k_mean"] = (w * k).sum(axis=1) / z
+    return out

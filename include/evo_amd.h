@@ -346,6 +346,34 @@ int evoamd_evolve_states(evoamd_ctx *ctx, int mutation, int fit_parents, int n_p
  * (eas.py:313), for callers that keep the reference's two-call structure, and for the distribution tests. */
 int evoamd_download_candidates(evoamd_ctx *ctx, uint8_t *cand_bool, int32_t *counts, double *lpj);
 
+/* K^n refined while Theta stays fixed: one pass over the resident K^n at entry, then n_iterations x (children, their
+ * lpj, selection).  The selection kernel writes the lpj of every state it swaps in, so the rows stay current and no
+ * iteration evaluates K^n again; no statistics pass runs and the fused E-step kernel is never used.  Iteration t draws
+ * its children with seed0 + t * seed_stride (mod 2^64): evoamd_evolve_randflip's kernel for mutation 0 with one
+ * generation and at most 8 children, evoamd_evolve_states' otherwise -- arguments and checks as for those two calls
+ * and evoamd_vary_kn, results bit for bit those of the separate calls.  trace_out (n_iterations, 3): row t =
+ * {Fs = sum_n logsumexp_s lpj_ns after iteration t, new unique states, swapped states} of this rank, per iteration
+ * (not running sums).  patience <= 0: nothing waits for the device until the end.  patience > 0: after every
+ * check_every iterations that chunk's rows are fetched and the loop ends there once the last `patience` rows all have
+ * swapped / N <= min_sub; *n_done_out = iterations run (rows beyond are not written), and the result is what
+ * n_iterations = *n_done_out without patience gives.  On return the lpj rows belong to the resident K^n, the
+ * products of the last statistics pass are gone as after any selection, and the scalar block is as one evoamd_estep
+ * with the last iteration's arguments leaves it: a following evoamd_stats reports that iteration's counts and Fs. */
+int evoamd_refine_states(evoamd_ctx *ctx, int n_iterations, int mutation, int fit_parents, int n_parents,
+                         int n_children, int n_generations, uint64_t seed0, uint64_t seed_stride, double sparseness,
+                         double bitflip_prob, int Mprime, int check_every, int patience, double min_sub,
+                         double *trace_out, int *n_done_out);
+
+/* Per-datapoint scores of the lpj rows and K^n resident on the device (after a seed, an upload or any pass), each output
+ * (N) or NULL.  With m = max_s lpj_ns, w_s = exp(lpj_ns - m), z = sum_s w_s over the S_perm + S columns:
+ * F_out = m + log z (the bound per datapoint without ljc, the counterpart of ll_out of evoamd_loglik_exact);
+ * entropy_out = log z - sum_s w_s (lpj_ns - m) / z, the entropy of q_n (weights that underflow to 0 contribute 0);
+ * best_out = the first column of the row that holds m; k_best_out = active latents of that state (0 for the permanent
+ * all-zero column); k_mean_out = sum_s q_ns |s_s|.  Counts come from the packed words.  Fixed reduction order: two
+ * calls give the same bits.  Nothing of the EM state changes. */
+int evoamd_posterior_scores(evoamd_ctx *ctx, double *F_out, double *entropy_out, int32_t *best_out,
+                            int32_t *k_best_out, double *k_mean_out);
+
 /* ---- M-step sufficient statistics + free energy ------------------------------------- */
 /* Number of doubles in the packed accumulator for the configured model:
  *   BSC : Wp (H,D) | Wq (H,H) | pies (H) | sigma | tail[8]
