@@ -26,6 +26,9 @@ SEED_INCOMPLETE = 1
 PSAMP_KEEP = {"slot": 1, "s": 2, "z": 4, "y": 8}
 PSAMP_WHAT = {"slot": 0, "s": 1, "z": 2, "y": 3}
 
+# evoamd_download_loglik_draws: the output ids (EVOAMD_LLE_*)
+LLE_WHAT = {"s": 0, "inside": 1, "log_r": 2, "lpj": 3}
+
 # evoamd_debug_validity: names of the bits of out[0] (EVOAMD_VB_*, in bit order) and of out[1..7]
 VALIDITY_BITS = (
     "have_data", "have_params", "have_cand", "B_valid", "rows_fresh", "stats_rows_valid", "yhat_valid", "rec_resident",
@@ -46,7 +49,7 @@ KERNEL_IDS = {
 }
 # classes outside the EM path, added after tests/test_gpu_validity.py recorded its launch census over KERNEL_IDS (which
 # therefore stays as it is); Engine.timing / Engine.kernel_time_ms take names of either table
-KERNEL_IDS_EXTRA = {"posterior_sample": 23, "seed_states": 24}
+KERNEL_IDS_EXTRA = {"posterior_sample": 23, "seed_states": 24, "loglik_proposal": 25, "loglik_lpj": 26, "loglik_fold": 27}
 
 
 def kernel_id(name):
@@ -125,6 +128,9 @@ SIGNATURES = {
     "evoamd_download_predictive": (_I, [_vp, _c_dp, _c_dp]),
     "evoamd_posterior_sample": (_I, [_vp, _I, _U64, _U64, _I, _I, _I, ctypes.POINTER(_I64)]),
     "evoamd_download_posterior_samples": (_I, [_vp, _I, _vp]),
+    "evoamd_loglik_estimate": (_I, [_vp, _I, _U64, _U64, _DBL, _I, _c_dp, _c_dp, _c_dp, _c_dp, _c_i32p,
+                                    ctypes.POINTER(_I64), _c_dp]),
+    "evoamd_download_loglik_draws": (_I, [_vp, _I, _vp]),
     "evoamd_patches_merge_samples": (_I, [_vp, _I, _I, _I, _I, _I, _I, _I, _I, _I, _c_dp, _c_dp, _c_dp]),
     "evoamd_patches_merge_predictive": (_I, [_vp, _I, _I, _I, _I, _I, _I, _I, _c_dp]),
     "evoamd_generate": (_I, [_vp, _I, _I64, _I, _I, _U64, _U64, _c_dp, _c_dp, _c_dp, _c_dp, _DBL, _c_u64p, _I]),

@@ -34,6 +34,7 @@
 #include "kernels_posterior_sample.hpp"
 #include "kernels_seed.hpp"
 #include "kernels_refine.hpp"
+#include "kernels_loglik_estimate.hpp"
 
 // ---------------------------------------------------------------------------------------
 // error handling
@@ -155,6 +156,9 @@ enum {  // internal kernel ids (see evoamd_kernel_name)
   KID_INIT_STATES,  // evoamd_init_states: the K^n(0) sampler (or the table copy of the exact mode)
   KID_POSTERIOR_SAMPLE,  // evoamd_posterior_sample: W^T and the sampling kernel (transfers excluded)
   KID_SEED_STATES,  // evoamd_seed_states: the greedy seeding kernel
+  KID_LLE_PROPOSAL,  // evoamd_loglik_estimate: the proposal kernel (marginals, draws, membership), all passes
+  KID_LLE_LPJ,       // ... the lpj launches over the outside draws, all passes
+  KID_LLE_FOLD,      // ... the fold kernel of every pass and the finish
   KID_COUNT
 };
 
@@ -528,6 +532,16 @@ struct evoamd_ctx {
   DevBuf<double> ps_z, ps_y;
   i64 ps_N = 0, ps_T = 0;
   int ps_D = 0, ps_H = 0, ps_keep = -1;
+  // evoamd_loglik_estimate (kernels_loglik_estimate.hpp): the running values and outputs per datapoint, log r and t of a
+  // pass's outside draws, the clamp flag words of its lpj launches (never those of the EM state) and, with keep_draws, the
+  // draws of the last call; grown on demand and released by evoamd_configure; lle_keep < 0: nothing to download
+  DevBuf<double> lle_d, lle_keep_d, lle_rho;  // lle_rho: the proposal of every datapoint, kept between the passes of a call
+  DevBuf<int> lle_i;
+  DevBuf<unsigned> lle_flags;
+  DevBuf<u64> lle_keep_s, lle_hash;  // lle_hash: the hashes of K^n's states, kept between the passes of a call
+  DevBuf<uint8_t> lle_keep_in;
+  i64 lle_N = 0, lle_T = 0;
+  int lle_H = 0, lle_keep = -1;
   // evoamd_posterior_codes: the compact outputs on the device (one allocation, grown on demand); rows_kn_gen = the K^n
   // the rows of the last statistics pass were formed from; option "codes_path" (-1 automatic, else CODES_REG / _LDS / _GMEM)
   DevBuf<uint8_t> codes_buf;
@@ -707,6 +721,9 @@ static void on_census_poisoned(evoamd_ctx *c) { c->kn_gen++; }  // test hook: re
 // host or from the general operators may differ from every resident state in many bits
 static void on_cand_installed(evoamd_ctx *c, bool near_parents) { c->cand_from_device = near_parents; }
 static void made_cand_lpj(evoamd_ctx *c) { c->have_cand = true; }
+// the candidate buffers were borrowed for states that are no children of K^n (the importance draws of
+// evoamd_loglik_estimate): no batch counts as installed, evoamd_vary_kn refuses until the next one
+static void drop_cand_batch(evoamd_ctx *c) { c->have_cand = false, c->cand_from_device = false; }
 // fused E-step: K^n advanced, its rows and (small shards) its census came with it, the children never left the kernel
 static void made_fused_estep(evoamd_ctx *c, bool inkernel_census) {
   on_kn_changed(c, KN_BY_SELECTION);
@@ -747,6 +764,7 @@ static void made_resident_rec(evoamd_ctx *c, bool uses_keep) { c->rec_uses_keep 
 static void made_predictive(evoamd_ctx *c, i64 N) { c->pred_N = N; }  // 0: nothing to download
 static void made_generated(evoamd_ctx *c, int keep) { c->gen_keep = keep; }  // -1: no call has completed
 static void made_posterior_samples(evoamd_ctx *c, int keep) { c->ps_keep = keep; }  // -1: nothing to download (no EM state reads it)
+static void made_loglik_draws(evoamd_ctx *c, int keep) { c->lle_keep = keep; }  // -1: nothing to download (no EM state reads it)
 // ---- validity: end
 
 struct SpanGuard {
@@ -1229,6 +1247,16 @@ static void configure_drop(evoamd_ctx *c) {
   c->ps_z.reset();
   c->ps_y.reset();
   made_posterior_samples(c, -1);
+  // ... and the importance draws of evoamd_loglik_estimate
+  c->lle_d.reset();
+  c->lle_keep_d.reset();
+  c->lle_rho.reset();
+  c->lle_hash.reset();
+  c->lle_i.reset();
+  c->lle_flags.reset();
+  c->lle_keep_s.reset();
+  c->lle_keep_in.reset();
+  made_loglik_draws(c, -1);
   c->huge.reset();
   c->huge_ctl.reset();
   c->huge_slots = c->huge_kc = 0;
@@ -5501,6 +5529,197 @@ extern "C" int evoamd_download_posterior_samples(evoamd_ctx *c, int what, void *
 }
 
 // ---------------------------------------------------------------------------------------
+// log-likelihood beyond K^n by importance draws (kernels_loglik_estimate.hpp).  The outside draws of a pass go through
+// the RESIDENT CANDIDATE BATCH (c->cand, cand_dig, cand_counts, cand_lpj) and eval_candidates' launches under tag 1, not
+// through a private batch under tag 2: the candidate instantiations are the ones built for ragged per-datapoint states at
+// the large shapes (EBSC: the Gram form over B = Y W instead of the direct residual; ES3C: the table-driven main kernel
+// over digests, which dig_for only grants the two resident arrays), a pass is then at most Cmax draws by construction and
+// no second N x Cmax x HW array exists.  The price: the batch a previous E-step left is gone (drop_cand_batch), and the
+// hints say "nothing known" (known_tag 2: every level, worst-case grids), because draws are no children of K^n.  The clamp
+// flags go to words of the call's own, so the reset counters of the next evoamd_stats do not see the draws.
+// ---------------------------------------------------------------------------------------
+static int lle_kh(int HW) { return HW <= 1 ? 1 : HW <= 2 ? 2 : HW <= 4 ? 4 : HW <= 8 ? 8 : LLE_MAX_KH; }  // latents per lane
+
+static void launch_lle_proposal(evoamd_ctx *c, const LleArgs &a, size_t lds) {
+  const unsigned grid = cdiv(a.N, LLE_WAVES);
+  switch (lle_kh(a.HW)) {  // (a.rho holds N x 64 lle_kh(HW) doubles)
+    case 1: lle_proposal_kernel<1><<<grid, 64 * LLE_WAVES, lds, c->stream>>>(a); break;
+    case 2: lle_proposal_kernel<2><<<grid, 64 * LLE_WAVES, lds, c->stream>>>(a); break;
+    case 4: lle_proposal_kernel<4><<<grid, 64 * LLE_WAVES, lds, c->stream>>>(a); break;
+    case 8: lle_proposal_kernel<8><<<grid, 64 * LLE_WAVES, lds, c->stream>>>(a); break;
+    default: lle_proposal_kernel<LLE_MAX_KH><<<grid, 64 * LLE_WAVES, lds, c->stream>>>(a); break;
+  }
+}
+
+extern "C" int evoamd_loglik_estimate(evoamd_ctx *c, int n_samples, uint64_t seed, uint64_t first_index, double prior_mix,
+                                      int keep_draws, double *ll_out, double *F_out, double *mass_out, double *ess_out,
+                                      int32_t *n_outside_out, int64_t counters[2], double *sum_out) {
+  REQUIRE(c && c->configured && c->have_data && c->have_params,
+          "evoamd_loglik_estimate: configure, upload data and set parameters first");
+  REQUIRE(!c->f32, "evoamd_loglik_estimate is not available in the float32 mode");
+  REQUIRE_KN(c);
+  REQUIRE(counters && sum_out, "evoamd_loglik_estimate: counters or sum_out is NULL");
+  REQUIRE(n_samples >= 1, "evoamd_loglik_estimate: n_samples must be positive");
+  REQUIRE(prior_mix > 0.0 && prior_mix <= 1.0, "evoamd_loglik_estimate: prior_mix must be in (0, 1]");
+  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
+  const i64 N = c->N, T = n_samples;
+  const int H = c->H, HW = c->HW, Cmax = c->Cmax, Hv = H - (c->bg_unit ? 1 : 0);
+  if (HW > LLE_MAX_KH)
+    return fail(EVOAMD_E_INVALID, "evoamd_loglik_estimate: H = %d, at most %d latents are supported (64 lanes x %d registers)", H,
+                64 * LLE_MAX_KH, LLE_MAX_KH);
+  REQUIRE(Hv >= 1, "evoamd_loglik_estimate: no latent varies");
+  const size_t lds = (size_t)LLE_WAVES * (size_t)(c->L + c->S) * sizeof(double);
+  if (lds > LLE_LDS_MAX)
+    return fail(EVOAMD_E_INVALID, "evoamd_loglik_estimate: S_perm + 2 S = %d, at most %d weights and hashes fit the LDS slice of a "
+                "datapoint", c->L + c->S, (int)(LLE_LDS_MAX / (LLE_WAVES * sizeof(double))));
+  HIP_TRY(hipSetDevice(c->device));
+  made_loglik_draws(c, -1);
+  const size_t nt = (size_t)N * (size_t)T, nc = (size_t)N * (size_t)Cmax;
+  const unsigned nb = cdiv(N, 4);
+  // F | m | z | q | ll | mass | ess | all-zero lpj (N each) | sum (1) | partial (nb) | log r (N x Cmax)
+  const size_t need_d = 8 * (size_t)N + 1 + nb + nc;
+  const size_t need_i = 2 * (size_t)N + nc;  // status | n_outside | t (N x Cmax)
+  const size_t need_rho = (size_t)N * 64 * (size_t)lle_kh(HW);
+  // ---- do the buffers fit?  Decided before anything is released, allocated or launched.
+  {
+    size_t grow = 0, released = 0;
+    auto plan = [&](bool wanted, size_t have, size_t want, size_t elem) {
+      if (wanted && want > have) grow += want * elem, released += have * elem;
+    };
+    plan(keep_draws, c->lle_keep_s.size(), nt * HW, sizeof(u64));
+    plan(keep_draws, c->lle_keep_in.size(), nt, sizeof(uint8_t));
+    plan(keep_draws, c->lle_keep_d.size(), 2 * nt, sizeof(double));
+    plan(true, c->lle_d.size(), need_d, sizeof(double));
+    plan(true, c->lle_i.size(), need_i, sizeof(int));
+    plan(true, c->lle_flags.size(), (size_t)N, sizeof(unsigned));
+    plan(true, c->lle_rho.size(), need_rho, sizeof(double));
+    plan(true, c->lle_hash.size(), (size_t)N * c->S, sizeof(u64));
+    if (grow) {
+      size_t free_b = 0, total_b = 0;
+      HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+      if (grow > free_b + released)
+        return fail(EVOAMD_E_INVALID, "evoamd_loglik_estimate: the buffers asked for need %zu bytes of device memory, %zu are free "
+                    "(fewer draws per call, or keep_draws = 0)", grow, free_b + released);
+    }
+  }
+  TRY(ensure_B(c));
+  if (sssc) TRY(ensure_lists(c, N * (i64)Cmax));
+  TRY(c->lle_d.ensure(c, need_d));
+  TRY(c->lle_i.ensure(c, need_i));
+  TRY(c->lle_flags.ensure(c, (size_t)N));
+  TRY(c->lle_rho.ensure(c, need_rho));
+  TRY(c->lle_hash.ensure(c, (size_t)N * c->S));
+  if (keep_draws) {
+    TRY(c->lle_keep_s.ensure(c, nt * HW));
+    TRY(c->lle_keep_in.ensure(c, nt));
+    TRY(c->lle_keep_d.ensure(c, 2 * nt));
+    // a datapoint without an estimate keeps these: s zero, inside 0, log r and lpj NaN (all bits set); so does the lpj
+    // of an inside draw
+    HIP_TRY(hipMemsetAsync(c->lle_keep_s, 0, nt * HW * sizeof(u64), c->stream));
+    HIP_TRY(hipMemsetAsync(c->lle_keep_in, 0, nt, c->stream));
+    HIP_TRY(hipMemsetAsync(c->lle_keep_d, 0xFF, 2 * nt * sizeof(double), c->stream));
+  }
+  HIP_TRY(hipMemsetAsync(c->lle_flags, 0, (size_t)N * sizeof(unsigned), c->stream));
+  double *dF = c->lle_d, *run_m = dF + N, *run_z = run_m + N, *run_q = run_z + N, *d_ll = run_q + N, *d_mass = d_ll + N;
+  double *d_ess = d_mass + N, *d_az = d_ess + N, *d_sum = d_az + N, *d_part = d_sum + 1, *d_logr = d_part + nb;
+  int *d_status = c->lle_i, *d_nout = d_status + N, *d_tix = d_nout + N;
+  double *keep_logr = keep_draws ? c->lle_keep_d.get() : nullptr, *keep_lpj = keep_draws ? keep_logr + nt : nullptr;
+  drop_cand_batch(c);  // from here on the candidate buffers hold importance draws
+  {
+    SpanGuard g(c, KID_LLE_FOLD);
+    posterior_score_kernel<<<cdiv(N, SCORE_WAVES), 64 * SCORE_WAVES, 0, c->stream>>>(c->lpj, c->states, N, c->L, c->S, c->S_perm, HW,
+                                                                                     dF, nullptr, nullptr, nullptr, nullptr);
+    allzero_lpj_kernel<<<cdiv(N, 256), 256, 0, c->stream>>>(c->yy, N, c->dpar, sssc, d_az, 1, c->lle_flags, c->err);
+    HIP_TRY(hipGetLastError());
+  }
+  LleArgs a = {};
+  a.lpj = c->lpj, a.states = c->states;
+  a.pies = sssc ? c->pies.get() : nullptr;
+  a.dpar = c->dpar;
+  a.row_any = c->mask_infr ? c->row_any.get() : nullptr;
+  a.N = N, a.T = T;
+  a.H = H, a.Hv = Hv, a.HW = HW, a.S = c->S, a.S_perm = c->S_perm, a.L = c->L, a.bg = c->bg_unit ? 1 : 0, a.Cmax = Cmax;
+  a.lam = prior_mix, a.oml = 1.0 - prior_mix;
+  a.seed = seed, a.first_index = first_index;
+  a.cand = c->cand, a.cand_dig = (c->use_digest && c->cand_dig) ? c->cand_dig.get() : nullptr, a.counts = c->cand_counts;
+  a.logr = d_logr, a.tix = d_tix, a.status = d_status, a.rho = c->lle_rho, a.hash = c->lle_hash;
+  a.keep_s = keep_draws ? c->lle_keep_s.get() : nullptr;
+  a.keep_inside = keep_draws ? c->lle_keep_in.get() : nullptr;
+  a.keep_logr = keep_logr;
+  const LevelHints lv;  // known_tag 2: nothing is known about the draws
+  for (i64 t0 = 0; t0 < T; t0 += Cmax) {
+    a.t0 = t0;
+    a.P = (int)std::min<i64>(Cmax, T - t0);
+    {
+      SpanGuard g(c, KID_LLE_PROPOSAL);
+      launch_lle_proposal(c, a, lds);
+      HIP_TRY(hipGetLastError());
+      DBG_SYNC(c, "loglik_estimate proposal");
+    }
+    on_cand_installed(c, /*near_parents=*/false);
+    {
+      SpanGuard g(c, KID_LLE_LPJ);
+      Batch b = {c->cand, c->cand_counts, c->Y, c->Bm, c->yy, N, Cmax, 0, c->cand_lpj, Cmax, 0, c->lle_flags, KID_LPJ_CAND, 1};
+      b.mask = c->mask_infr;
+      TRY(launch_lpj(c, b, lv));
+    }
+    SpanGuard g(c, KID_LLE_FOLD);
+    lle_fold_kernel<<<nb, 256, 0, c->stream>>>(c->cand_lpj, Cmax, c->cand_counts, d_logr, d_tix, d_az, N, T, t0 == 0, run_m, run_z,
+                                               run_q, d_nout, keep_lpj);
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "loglik_estimate fold");
+  }
+  {
+    SpanGuard g(c, KID_LLE_FOLD);
+    lle_finish_kernel<<<nb, 256, 0, c->stream>>>(dF, run_m, run_z, run_q, d_nout, d_status, N, log((double)T), d_ll, d_mass, d_ess,
+                                                 d_part);
+    reduce_partials_kernel<<<1, 256, 0, c->stream>>>(d_part, nb, d_sum, 0);
+    HIP_TRY(hipGetLastError());
+  }
+  std::vector<int> status((size_t)N);
+  HIP_TRY(hipMemcpyAsync(status.data(), d_status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (ll_out) HIP_TRY(hipMemcpyAsync(ll_out, d_ll, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (F_out) HIP_TRY(hipMemcpyAsync(F_out, dF, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (mass_out) HIP_TRY(hipMemcpyAsync(mass_out, d_mass, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (ess_out) HIP_TRY(hipMemcpyAsync(ess_out, d_ess, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (n_outside_out) HIP_TRY(hipMemcpyAsync(n_outside_out, d_nout, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(sum_out, d_sum, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (sssc)
+    TRY(check_err(c));  // synchronises the stream; a draw the levels refuse surfaces here
+  else
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  counters[0] = counters[1] = 0;
+  for (i64 n = 0; n < N; n++) {
+    counters[0] += status[(size_t)n] == LLE_BAD_WEIGHTS;
+    counters[1] += status[(size_t)n] == LLE_SKIPPED;
+  }
+  c->lle_N = N, c->lle_T = T, c->lle_H = H;
+  made_loglik_draws(c, keep_draws ? 1 : 0);
+  return 0;
+}
+
+extern "C" int evoamd_download_loglik_draws(evoamd_ctx *c, int what, void *out) {
+  REQUIRE(c && out, "evoamd_download_loglik_draws: NULL argument");
+  REQUIRE(c->configured && c->lle_keep == 1 && c->lle_N == c->N && c->lle_H == c->H,
+          "evoamd_download_loglik_draws: no draws on the device (call evoamd_loglik_estimate with keep_draws first; a failed "
+          "call and evoamd_configure drop them)");
+  const size_t nt = (size_t)c->lle_N * (size_t)c->lle_T;
+  const void *src = nullptr;
+  size_t bytes = 0;
+  switch (what) {
+    case EVOAMD_LLE_S: src = c->lle_keep_s, bytes = nt * c->HW * sizeof(u64); break;
+    case EVOAMD_LLE_INSIDE: src = c->lle_keep_in, bytes = nt; break;
+    case EVOAMD_LLE_LOG_R: src = c->lle_keep_d, bytes = nt * sizeof(double); break;
+    case EVOAMD_LLE_LPJ: src = c->lle_keep_d + nt, bytes = nt * sizeof(double); break;
+    default: return fail(EVOAMD_E_INVALID, "evoamd_download_loglik_draws: what must be EVOAMD_LLE_S, _INSIDE, _LOG_R or _LPJ");
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
 // samples from the model (kernels_generate.hpp): own buffers, no EM state touched
 // ---------------------------------------------------------------------------------------
 extern "C" int evoamd_generate(evoamd_ctx *c, int model, int64_t N, int D, int H, uint64_t seed, uint64_t first_index,
@@ -5684,6 +5903,7 @@ extern "C" const char *evoamd_kernel_name(int kid) {
                                          "stats",        "stats_overflow", "gemm_f64",     "evolve",   "misc", "mstep_device",
                                          "lpj_pass",     "stats_pass",     "lpj_k3_4",     "lpj_k5_8", "lpj_k9plus",
                                          "stats_k3_4",   "stats_k5_8",     "stats_k9plus", "allreduce",    "estep_fused",
-                                         "patches",      "init_states",    "posterior_sample", "seed_states"};
+                                         "patches",      "init_states",    "posterior_sample", "seed_states",
+                                         "loglik_proposal", "loglik_lpj",  "loglik_fold"};
   return (kid >= 0 && kid < KID_COUNT) ? names[kid] : "?";
 }

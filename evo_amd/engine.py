@@ -741,6 +741,46 @@ class Engine:
                                                     None if mean is None else dptr(mean), None if std is None else dptr(std)))
         return imgs, mean, std
 
+    # ---- log-likelihood beyond K^n (evo_amd.models.loglik_estimate is the NumPy mirror) -------
+    def loglik_estimate(self, n_samples=256, seed=0, first_index=0, prior_mix=0.25, keep_draws=False):
+        """The importance-draw estimate of log p(y_n) - ljc per datapoint under the Theta, K^n and lpj rows on the device
+        (evoamd_loglik_estimate; csrc/kernels_loglik_estimate.hpp has the law).  Returns (total, n_ok, info): total = the
+        sum of ll over the n_ok datapoints that have an estimate, info = the (N,) arrays "ll", "F", "gap",
+        "mass_outside", "ess", "n_outside" (int32; NaN / 0 rows for a datapoint without an estimate), the counters
+        "n_bad_weights" and "n_skipped" and, with ``keep_draws``, "s" bool (N, T, H), "inside" bool (N, T), "log_r" and
+        "lpj" (N, T; lpj NaN where the draw is inside K^n).  K^n, lpj, Theta and the statistics rows stay as they are;
+        the resident candidate batch is used up (vary_kn refuses until the next one).  EvoAmdError for the float32 mode,
+        H > 1024, S_perm + 2 S > 2048 and, naming the bytes, buffers that do not fit the free device memory."""
+        from .models.generate import unpack_words
+        T = int(n_samples)
+        if T < 1:
+            raise ValueError("n_samples must be positive")
+        if not 0.0 < float(prior_mix) <= 1.0:
+            raise ValueError("prior_mix must be in (0, 1]")
+        N, H = self.N, self.H
+        info = {name: np.empty(N) for name in ("ll", "F", "mass_outside", "ess")}
+        info["n_outside"] = np.empty(N, dtype=np.int32)
+        counters = (ctypes.c_int64 * 2)()
+        total = ctypes.c_double()
+        check(self.lib.evoamd_loglik_estimate(
+            self._h, T, int(seed) & (2 ** 64 - 1), int(first_index) & (2 ** 64 - 1), float(prior_mix), 1 if keep_draws else 0,
+            dptr(info["ll"]), dptr(info["F"]), dptr(info["mass_outside"]), dptr(info["ess"]), i32ptr(info["n_outside"]),
+            counters, ctypes.byref(total)))
+        none = np.isnan(info["ll"])
+        info["F"][none] = np.nan
+        info["n_outside"][none] = 0
+        info["gap"] = info["ll"] - info["F"]
+        info["n_bad_weights"], info["n_skipped"] = int(counters[0]), int(counters[1])
+        if keep_draws:
+            shapes = {"s": ((N * T, (H + 63) // 64), np.uint64), "inside": ((N, T), np.uint8),
+                      "log_r": ((N, T), np.float64), "lpj": ((N, T), np.float64)}
+            for name in ("s", "inside", "log_r", "lpj"):
+                a = np.empty(*shapes[name])
+                check(self.lib.evoamd_download_loglik_draws(self._h, _lib.LLE_WHAT[name], a.ctypes.data_as(ctypes.c_void_p)))
+                info[name] = (unpack_words(a, H).reshape(N, T, H) if name == "s" else
+                              a.astype(np.bool_) if name == "inside" else a)
+        return total.value, N - int(none.sum()), info
+
     # ---- timing --------------------------------------------------------------------------
     def timing(self, on=True):
         """on: True (all kernel classes), False, or an iterable of class names (_lib.KERNEL_IDS, _lib.KERNEL_IDS_EXTRA)."""

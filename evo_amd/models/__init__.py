@@ -5,3 +5,4 @@ from .generate import generate_counter  # noqa: F401
 from .exact import enumerate_chunk, fold_exact  # noqa: F401
 from .predictive import predictive_moments_host  # noqa: F401
 from .posterior_sample import sample_posterior_counter  # noqa: F401
+from .loglik_estimate import estimate_log_likelihood_counter, proposal_of  # noqa: F401

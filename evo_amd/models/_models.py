@@ -1003,6 +1003,57 @@ class Model:
             return L, ll, marg
         return L
 
+    def estimate_log_likelihood(self, model_params, my_suff_stat, my_data, n_samples=256, seed=None, first_index=0,
+                                prior_mix=0.25, per_datapoint=False, keep_draws=False):
+        """An estimate of the log-likelihood where the 2^H states of exact_log_likelihood cannot be enumerated, and with
+        it of the tightness of the bound, log p(y_n) - F_n = KL(q_n || p(s | y_n)).  For every datapoint of this rank
+        ``n_samples`` states are drawn on the device from a product of Bernoullis whose means are q_n's own marginals over
+        K^n mixed with the prior (``prior_mix`` in (0, 1]: rho_h = (1 - prior_mix) p_h + prior_mix pi_h); a draw that K^n
+        holds counts as zero, the others are evaluated by the model's lpj kernels and weighted by 1 / r_n:
+        Z^_n = sum_{s in K^n} e^{lpj_ns} + (1 / T) sum_t 1[s_t not in K^n] e^{lpj(s_t)} / r_n(s_t).  The estimate is
+        unbiased in the likelihood, ll^_n = log Z^_n >= F_n for every datapoint and seed, and E[ll^_n] <= log p(y_n) - ljc:
+        it lies at or above the bound and, in expectation, at or below the truth.  Returns L^ = ljc + allreduce(sum_n
+        ll^_n) / N, the convention of exact_log_likelihood; with ``per_datapoint``, (L^, info) with the (N_loc,) arrays
+        "ll" (ll^_n without ljc), "F" (the bound: posterior_scores()["F"]), "gap" = ll - F >= 0, "mass_outside" (the share
+        of Z^_n from outside K^n), "ess" (the effective number of outside draws, (sum w)^2 / sum w^2: a value near 1 says
+        one draw carries the estimate), "n_outside" (int32) and the counters "n_bad_weights" / "n_skipped" of
+        sample_posterior: those datapoints have NaN rows and are left out of the sum -- L^ is then over the remaining
+        datapoints and divided by their count.  ``keep_draws``: info also carries "s" (bool (N, T, H)), "inside" (bool
+        (N, T)), "log_r" and "lpj" ((N, T), lpj NaN where the draw is inside K^n).  The stream is counter-based
+        (evo_amd.models.estimate_log_likelihood_counter reproduces it for ``self.last_estimate_seed``: the draws, inside
+        and n_outside bit for bit): datapoint n is index ``first_index + n`` of the data set, so shards concatenate to
+        the single call, and draw t does not depend on ``n_samples``.  ``seed`` None: drawn from np.random; rank and world
+        size enter it as in sample_posterior.  ValueError for n_samples < 1 and prior_mix outside (0, 1]; EvoAmdError for
+        the float32 mode, H > 1024, and draws that do not fit the free device memory.  Works with sync_host=False and on
+        incomplete data, writes nothing into the three dicts, does no communication besides the final all-reduce and
+        leaves K^n, lpj, Theta, y_reconstructed and the statistics rows on the device as they are."""
+        if int(n_samples) < 1:
+            raise ValueError("estimate_log_likelihood: n_samples must be positive")
+        if not 0.0 < float(prior_mix) <= 1.0:
+            raise ValueError("estimate_log_likelihood: prior_mix must be in (0, 1]")
+        if self.dtype == np.float32:
+            raise EvoAmdError("estimate_log_likelihood is not available in the float32 mode")
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+        self.last_estimate_seed = (int(seed) * max(1, self.comm.size) + self.comm.rank) & (2 ** 64 - 1)
+        yr = my_data.get("y_reconstructed")
+        if isinstance(yr, ResidentReconstruction) and yr.resident and not yr.materialised:
+            yr.rows()  # setting the parameters below drops the device copy of an unread reconstruction: fetch it first
+        uploads = self._kn_uploads  # (see reconstruct(): decide before _prepare() runs)
+        eng = self._prepare(my_suff_stat, my_data)
+        theta = dict(model_params)  # (the precompute stores its derived keys and zeroes the reset counters: on copies)
+        self.E_step_precompute(theta, dict(my_suff_stat), my_data)
+        if model_params is not self._dev_theta:
+            self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
+        if self.sync_host or self._kn_uploads != uploads:
+            eng.upload_lpj(my_suff_stat["lpj"])
+        total, n_ok, info = eng.loglik_estimate(n_samples, self.last_estimate_seed, first_index, prior_mix, keep_draws)
+        total, n_all = _reduce_array(self.comm, np.array([total, float(n_ok)]))  # (the one all-reduce of the call)
+        L = theta["ljc"] + total / n_all if n_all else float("nan")
+        if per_datapoint or keep_draws:
+            return L, info
+        return L
+
     def reconstruct(self, my_data, my_suff_stat, model_params):
         """(Re-)estimate the entries with my_data["x"] False from the posterior predictive distribution under
         ``model_params`` and the caller's K^n / lpj; adds my_data["y_reconstructed"] (_models.py:614-665).

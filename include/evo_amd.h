@@ -649,6 +649,41 @@ int evoamd_posterior_sample(evoamd_ctx *ctx, int n_samples, uint64_t seed, uint6
                             int fill_all, int add_noise, int64_t counters[4]);
 int evoamd_download_posterior_samples(evoamd_ctx *ctx, int what, void *out);
 
+/* ---- log-likelihood beyond K^n (importance draws from a proposal centred on q) ---- */
+/* evoamd_loglik_estimate: for every datapoint n of the context, n_samples states drawn from a product of Bernoullis r_n
+ * whose means are q_n's own marginals over K^n mixed with the prior (rho_h = (1 - prior_mix) p_h + prior_mix pi_h);
+ * the draws K^n does not hold are evaluated by the model's lpj launches and folded onto the bound in the log domain:
+ *   ll^_n = log( sum_{s in K^n} e^{lpj_ns} + (1 / T) sum_t 1[s_t not in K^n] e^{lpj(s_t)} / r_n(s_t) ).
+ * Unbiased in the likelihood, ll^_n >= F_n for every datapoint and seed, E[ll^_n] <= log p(y_n) - ljc.
+ * csrc/kernels_loglik_estimate.hpp has the law; evo_amd.models.estimate_log_likelihood_counter is its NumPy mirror (the
+ * draws, inside / outside and n_outside bit for bit, the real values to rounding).  The stream is counter-based under a
+ * purpose of its own: datapoint n is index first_index + n of the data set (shards concatenate to the single call) and
+ * draw t depends neither on n_samples nor on the passes (fewer draws are a prefix).
+ * Outputs (host, N each, any may be NULL): ll_out = ll^_n without ljc; F_out = the bound, evoamd_posterior_scores' F;
+ * mass_out = the share of Z^_n from outside K^n; ess_out = (sum w)^2 / sum w^2 over the outside draws; n_outside_out
+ * (int32).  sum_out (required) = sum of ll^_n over the datapoints that have an estimate.  counters[2] = datapoints without
+ * one (NaN outputs, left out of the sum) because [0] their lpj row holds a NaN or +inf or only -inf ("bad weights"), [1]
+ * they have no reliable entry.
+ * The draws run in passes of Cmax (the configured candidate capacity) through the resident candidate buffers and the
+ * candidate lpj launches: on return NO candidate batch counts as installed (evoamd_vary_kn refuses until the next
+ * evoamd_lpj_candidates / evolve call).  K^n, lpj, Theta, the statistics rows, y_reconstructed, a prefetched pass and the
+ * reset counters the next evoamd_stats reports stay as they are (the draws' clamp flags go to words of the call's own).
+ * The first pass leaves the proposal (N x 64 KH doubles, KH = the power of two >= ceil(H/64)) and one hash per state of
+ * K^n (N x S words) in buffers of the context for the later passes (grown on demand, released by evoamd_configure).
+ * keep_draws != 0: the draws stay in device buffers of the context (grown on demand, released by evoamd_configure and
+ * evoamd_ctx_destroy) for evoamd_download_loglik_draws: what = EVOAMD_LLE_S (N x T x ceil(H/64) uint64, the layout of
+ * K^n), _INSIDE (N x T uint8), _LOG_R (N x T double), _LPJ (N x T double, NaN where the draw is inside K^n).
+ * Refusals (EVOAMD_E_INVALID) before anything is launched: n_samples < 1; prior_mix outside (0, 1]; the float32 mode;
+ * H above 1024 (64 lanes x 16 latents per lane); S_perm + 2 S above 2048 (the weights and state hashes of a datapoint
+ * live in LDS); buffers that do not fit into the free device memory (the message names the bytes).  ES3C: a draw the lpj
+ * levels refuse surfaces as EVOAMD_E_KLIMIT / EVOAMD_E_SINGULAR, as for evoamd_lpj_candidates.  Both calls have completed
+ * on return. */
+enum { EVOAMD_LLE_S = 0, EVOAMD_LLE_INSIDE = 1, EVOAMD_LLE_LOG_R = 2, EVOAMD_LLE_LPJ = 3 };
+int evoamd_loglik_estimate(evoamd_ctx *ctx, int n_samples, uint64_t seed, uint64_t first_index, double prior_mix,
+                           int keep_draws, double *ll_out, double *F_out, double *mass_out, double *ess_out,
+                           int32_t *n_outside_out, int64_t counters[2], double *sum_out);
+int evoamd_download_loglik_draws(evoamd_ctx *ctx, int what, void *out);
+
 /* ---- merges of the resident draws and predictive moments (nothing of N x T x D or N x D crosses to the host) ---- */
 /* The patch geometry (H, W, C, ph, pw, shift: the conventions of evoamd_patches_merge) must give (N, D) of the buffers.
  * evoamd_patches_merge_samples merges draws t0 .. t0+n_draws-1 of the y draws the last evoamd_posterior_sample kept, each
@@ -713,7 +748,10 @@ enum {
   EVOAMD_K_INIT_STATES = 22,   /* evoamd_init_states: the K^n(0) sampler */
   EVOAMD_K_POSTERIOR_SAMPLE = 23, /* evoamd_posterior_sample: W^T and the sampling kernel (transfers excluded) */
   EVOAMD_K_SEED_STATES = 24,   /* evoamd_seed_states: the greedy K^n seeding kernel (B = Y W and transfers excluded) */
-  EVOAMD_K_COUNT = 25
+  EVOAMD_K_LOGLIK_PROPOSAL = 25, /* evoamd_loglik_estimate: the proposal kernel (marginals, draws, membership), per pass */
+  EVOAMD_K_LOGLIK_LPJ = 26,    /* ... the lpj launches over a pass's outside draws (every level)                          */
+  EVOAMD_K_LOGLIK_FOLD = 27,   /* ... the fold kernel of a pass; the bound + all-zero terms and the finish (one span each) */
+  EVOAMD_K_COUNT = 28
 };
 /* on = bit mask of kernel classes to time (bit k = class k; -1 = all, 0 = off).  Each timed span
  * records two HIP events on the compute stream, which costs about 10 us of stream time per span:
