@@ -35,6 +35,7 @@
 #include "kernels_seed.hpp"
 #include "kernels_refine.hpp"
 #include "kernels_loglik_estimate.hpp"
+#include "kernels_remap.hpp"
 
 // ---------------------------------------------------------------------------------------
 // error handling
@@ -159,6 +160,7 @@ enum {  // internal kernel ids (see evoamd_kernel_name)
   KID_LLE_PROPOSAL,  // evoamd_loglik_estimate: the proposal kernel (marginals, draws, membership), all passes
   KID_LLE_LPJ,       // ... the lpj launches over the outside draws, all passes
   KID_LLE_FOLD,      // ... the fold kernel of every pass and the finish
+  KID_REMAP,         // evoamd_remap_latents: the remap kernel (index upload and downloads excluded)
   KID_COUNT
 };
 
@@ -557,6 +559,15 @@ struct evoamd_ctx {
   // evoamd_refine_states: one row {Fs, new unique, swapped} per iteration; evoamd_posterior_scores: its (N) outputs.  Grown on
   // demand, rewritten by every call, read by nothing else
   DevBuf<double> refine_trace, score_buf;
+  // evoamd_remap_latents: K^n in the new latent numbering and its digests, [index (H_new) | n_replaced (N)] and the sum;
+  // grown on demand, NOT sized by the geometry: they survive the configure between the remap and
+  // evoamd_adopt_remapped_states, which swaps them in and releases them.  remap_H = 0: nothing to adopt.
+  // evoamd_latent_map_counts: its (64 HW) counters
+  DevBuf<u64> remap_states, remap_dig;
+  DevBuf<int> remap_i;
+  DevBuf<unsigned long long> remap_sum, map_counts;
+  i64 remap_N = 0;
+  int remap_S = 0, remap_H = 0;
   bool kn_lost = false;
   i64 kn_refill = 0;  // while kn_lost: rows [0, kn_refill) have been uploaded again by evoamd_upload_states_packed
   // evoamd_generate (kernels_generate.hpp): Theta^gen, the given states and the outputs of the last call, grown on demand
@@ -764,6 +775,7 @@ static void made_resident_rec(evoamd_ctx *c, bool uses_keep) { c->rec_uses_keep 
 static void made_predictive(evoamd_ctx *c, i64 N) { c->pred_N = N; }  // 0: nothing to download
 static void made_generated(evoamd_ctx *c, int keep) { c->gen_keep = keep; }  // -1: no call has completed
 static void made_posterior_samples(evoamd_ctx *c, int keep) { c->ps_keep = keep; }  // -1: nothing to download (no EM state reads it)
+static void made_remap(evoamd_ctx *c, i64 N, int S, int H_new) { c->remap_N = N, c->remap_S = S, c->remap_H = H_new; }  // 0: nothing to adopt
 static void made_loglik_draws(evoamd_ctx *c, int keep) { c->lle_keep = keep; }  // -1: nothing to download (no EM state reads it)
 // ---- validity: end
 
@@ -881,6 +893,7 @@ static int set_kernel_lds_limits() {
                         (const void *)posterior_sample_kernel<4, true>, (const void *)posterior_sample_kernel<8, true>};
     for (const void *f : sk) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   }
+  HIP_TRY(hipFuncSetAttribute((const void *)remap_latents_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, REMAP_LDS_BYTES));
   HIP_TRY(hipFuncSetAttribute((const void *)seed_states_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   HIP_TRY(hipFuncSetAttribute((const void *)seed_states_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   HIP_TRY(hipFuncSetAttribute((const void *)seed_states_masked_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
@@ -3318,6 +3331,131 @@ extern "C" int evoamd_posterior_scores(evoamd_ctx *c, double *F_out, double *ent
   if (best_out) HIP_TRY(hipMemcpyAsync(best_out, dbest, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   if (k_best_out) HIP_TRY(hipMemcpyAsync(k_best_out, dkbest, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   if (c->model == EVOAMD_MODEL_SSSC) return check_err(c);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// the dictionary resized: K^n in a new latent numbering (kernels_remap.hpp has the law)
+// ---------------------------------------------------------------------------------------
+// Writes into context-owned scratch and remembers (N, S, H_new) with it; the resident K^n, the lpj rows and every flag
+// stay as they are.  Every refusal comes before anything is launched or allocated.
+extern "C" int evoamd_remap_latents(evoamd_ctx *c, const int32_t *index, int H_new, int32_t *n_replaced_out, int64_t *sum_out) {
+  REQUIRE(c && c->configured, "evoamd_remap_latents: nothing is resident (configure and upload, initialise or seed K^n first)");
+  REQUIRE_KN(c);
+  REQUIRE(index, "evoamd_remap_latents: index is NULL");
+  REQUIRE(H_new >= 1 && H_new <= DIG_MAX_H, "evoamd_remap_latents: H_new must be in [1, 16384] (the digests' latent indices)");
+  const int H = c->H, S = c->S, bg = c->bg_unit ? 1 : 0;
+  {
+    std::vector<uint8_t> seen((size_t)H, 0);
+    for (int h = 0; h < H_new; h++) {
+      const int v = index[h];
+      if (v == -1) continue;
+      if (v < 0 || v >= H)
+        return fail(EVOAMD_E_INVALID, "evoamd_remap_latents: index[%d] = %d is out of range (-1 or a source latent in [0, %d))", h, v, H);
+      if (seen[v]) return fail(EVOAMD_E_INVALID, "evoamd_remap_latents: duplicate source latent %d (index[%d])", v, h);
+      seen[v] = 1;
+    }
+  }
+  if (bg) {
+    if (index[H_new - 1] != H - 1)
+      return fail(EVOAMD_E_INVALID, "evoamd_remap_latents: with the background unit the last index must be H - 1 = %d (it is %d)",
+                  H - 1, index[H_new - 1]);
+  }
+  const i64 Hv2 = H_new - bg;
+  if (Hv2 * (Hv2 + 1) / 2 < S)
+    return fail(EVOAMD_E_INVALID,
+                "evoamd_remap_latents: Hv' (Hv' + 1) / 2 = %lld fill candidates are fewer than S = %d states (Hv' = %lld): such "
+                "shapes belong to init_states", (long long)(Hv2 * (Hv2 + 1) / 2), S, (long long)Hv2);
+  const int HW = c->HW, HW2 = (H_new + 63) / 64;
+  int W = REMAP_WAVES;
+  while (W > 1 && remap_lds_words(W, S, HW, HW2) * sizeof(u64) > REMAP_LDS_BYTES) W >>= 1;
+  if (remap_lds_words(W, S, HW, HW2) * sizeof(u64) > REMAP_LDS_BYTES)
+    return fail(EVOAMD_E_INVALID,
+                "evoamd_remap_latents: S = %d states of %d + %d words and their digests do not fit one wavefront's LDS slice "
+                "(the cap at these H, H_new is S = %d)", S, HW, HW2, (int)((REMAP_LDS_BYTES / 8 - 32 * HW2) / (HW + HW2 + 1)));
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t N = (size_t)c->N;
+  made_remap(c, 0, 0, 0);  // whatever an earlier remap left is overwritten from here on
+  TRY(c->remap_states.ensure(c, N * S * HW2));
+  TRY(c->remap_dig.ensure(c, N * S));
+  TRY(c->remap_i.ensure(c, (size_t)H_new + N));
+  TRY(c->remap_sum.ensure(c, 1));
+  HIP_TRY(hipMemcpyAsync(c->remap_i, index, (size_t)H_new * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(c->remap_sum, 0, sizeof(unsigned long long), c->stream));
+  RemapArgs a;
+  a.src = c->states;
+  a.index = c->remap_i;
+  a.dst = c->remap_states;
+  a.dig = c->remap_dig;
+  a.n_replaced = c->remap_i + H_new;
+  a.sum = c->remap_sum;
+  a.N = c->N;
+  a.S = S;
+  a.S_perm = c->S_perm;
+  a.H = H;
+  a.HW = HW;
+  a.H2 = H_new;
+  a.HW2 = HW2;
+  a.Hv2 = (int)Hv2;
+  a.bg = bg;
+  {
+    const unsigned grid = (unsigned)std::min<i64>(cdiv(c->N, W), (i64)c->n_cu * 16);
+    SpanGuard g(c, KID_REMAP);
+    remap_latents_kernel<<<grid, 64 * W, remap_lds_words(W, S, HW, HW2) * sizeof(u64), c->stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "remap latents");
+  }
+  unsigned long long sum = 0;
+  if (n_replaced_out) HIP_TRY(hipMemcpyAsync(n_replaced_out, a.n_replaced, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(&sum, c->remap_sum, sizeof(sum), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (sum_out) *sum_out = (int64_t)sum;
+  made_remap(c, c->N, S, H_new);
+  return 0;
+}
+
+// After the caller has configured the context for H_new: the scratch becomes the resident K^n (a swap of the buffers), as
+// if the caller had uploaded it; the scratch is released, so a second adopt without a new remap is refused.
+extern "C" int evoamd_adopt_remapped_states(evoamd_ctx *c) {
+  REQUIRE(c && c->configured, "configure first");
+  REQUIRE(c->remap_H > 0, "evoamd_adopt_remapped_states: no remapped states to adopt (evoamd_remap_latents first; an adopt uses them up)");
+  if (c->N != c->remap_N || c->S != c->remap_S || c->H != c->remap_H)
+    return fail(EVOAMD_E_INVALID,
+                "evoamd_adopt_remapped_states: the context is configured for (N, S, H) = (%lld, %d, %d), the remapped states are "
+                "(%lld, %d, %d)", (long long)c->N, c->S, c->H, (long long)c->remap_N, c->remap_S, c->remap_H);
+  REQUIRE(c->dig && c->remap_states.size() >= c->states.size() && c->remap_dig.size() >= c->dig.size(),
+          "evoamd_adopt_remapped_states: the scratch does not cover the geometry");
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(sync_streams(c));  // a prefetched pass may still read the old buffers
+  std::swap(c->states, c->remap_states);
+  std::swap(c->dig, c->remap_dig);
+  c->remap_states.reset();
+  c->remap_dig.reset();
+  made_remap(c, 0, 0, 0);
+  on_kn_changed(c, KN_BY_CALLER);
+  on_kn_complete(c);
+  return 0;
+}
+
+// counts_out[h] = datapoints whose MAP state (first column of maximal lpj) has latent h on.  Reads rows and states only,
+// like evoamd_posterior_scores.
+extern "C" int evoamd_latent_map_counts(evoamd_ctx *c, int64_t *counts_out) {
+  REQUIRE(c && c->configured, "configure first");
+  REQUIRE(counts_out, "counts_out is NULL");
+  REQUIRE_KN(c);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = (size_t)64 * c->HW;
+  TRY(c->map_counts.ensure(c, n));
+  HIP_TRY(hipMemsetAsync(c->map_counts, 0, n * sizeof(unsigned long long), c->stream));
+  {
+    SpanGuard g(c, KID_MISC);
+    latent_map_count_kernel<<<cdiv(c->N, MAPCOUNT_WAVES), 64 * MAPCOUNT_WAVES, 0, c->stream>>>(
+        c->lpj, c->states, c->N, c->L, c->S, c->S_perm, c->HW, c->map_counts);
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "latent map counts");
+  }
+  HIP_TRY(hipMemcpyAsync(counts_out, c->map_counts, (size_t)c->H * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -5904,6 +6042,6 @@ extern "C" const char *evoamd_kernel_name(int kid) {
                                          "lpj_pass",     "stats_pass",     "lpj_k3_4",     "lpj_k5_8", "lpj_k9plus",
                                          "stats_k3_4",   "stats_k5_8",     "stats_k9plus", "allreduce",    "estep_fused",
                                          "patches",      "init_states",    "posterior_sample", "seed_states",
-                                         "loglik_proposal", "loglik_lpj",  "loglik_fold"};
+                                         "loglik_proposal", "loglik_lpj",  "loglik_fold",     "remap_latents"};
   return (kid >= 0 && kid < KID_COUNT) ? names[kid] : "?";
 }

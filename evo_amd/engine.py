@@ -365,6 +365,34 @@ class Engine:
                                                ptr.get("k_best"), ptr.get("k_mean")))
         return out
 
+    # ---- the dictionary resized (evo_amd.variational.remap_states_host is the NumPy mirror) -------
+    def remap_latents(self, index):
+        """K^n moved to the latent numbering ``index`` (int (H_new,): source latent or -1 for a new one) on the device
+        (evoamd_remap_latents; csrc/kernels_remap.hpp has the law): gathered bits, first occurrences kept in place,
+        collapsed slots filled from the enumeration of singletons and pairs.  The result waits in scratch of the context
+        for adopt_remapped_states(); the resident K^n, lpj and every flag stay as they are.  Returns (n_replaced int32
+        (N,), their sum).  EvoAmdError naming the rule, with the context as it was, for a bad index, a source named twice,
+        the background unit not kept last, H_new (H_new + 1) / 2 < S (without the background unit) and an S above the
+        LDS cap of the shape."""
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        assert idx.ndim == 1 and idx.size >= 1, idx.shape
+        n_rep = np.empty(self.N, dtype=np.int32)
+        total = ctypes.c_int64(0)
+        check(self.lib.evoamd_remap_latents(self._h, i32ptr(idx), idx.size, i32ptr(n_rep), ctypes.byref(total)))
+        return n_rep, int(total.value)
+
+    def adopt_remapped_states(self):
+        """After configure() for H_new (same N and S): the states remap_latents() left become the resident K^n, as an upload
+        of the same rows would make them.  EvoAmdError, with K^n as it was, when the geometry differs from the remap's or
+        nothing waits (an adopt uses the states up)."""
+        check(self.lib.evoamd_adopt_remapped_states(self._h))
+
+    def latent_map_counts(self):
+        """int64 (H,): the datapoints whose most probable state of K^n (first column of maximal lpj) has latent h on."""
+        out = np.empty(self.H, dtype=np.int64)
+        check(self.lib.evoamd_latent_map_counts(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return out
+
     def download_candidates(self):
         """(cand bool (N,Cmax,H), counts (N,), lpj (N,Cmax)) of the resident candidate batch."""
         cand = np.empty((self.N, self.Cmax, self.H), dtype=np.bool_)

@@ -917,6 +917,86 @@ class Model:
         out["n_eff"] = np.exp(out["entropy"])
         return out
 
+    def _clone_kwargs(self):
+        """The constructor arguments, beside (D, H, S), of a model like this one on the same engine."""
+        return dict(to_learn=list(self.to_learn), comm=self.comm, rng=self.rng, sync_host=self.sync_host,
+                    engine=self.engine, seed=self.seed, device_mstep=self.device_mstep, dtype=self.dtype,
+                    lazy_theta=self.lazy_theta, resident_reconstruction=self.resident_reconstruction)
+
+    def remap_latents(self, model_params, my_suff_stat, my_data, index, **new_columns):
+        """Resize the dictionary: prune, reorder or grow the latents of a trained model and carry K^n along on the device.
+        ``index`` int (H',): entry h' names the source latent that becomes latent h', or -1 for a NEW latent, off in every
+        state (evo_amd.variational.prune_index builds one from latent_usage()); with permanent["background"] the last
+        entry must be H - 1.  K^n is gathered to the new numbering there (Engine.remap_latents;
+        evo_amd.variational.remap_states_host is the NumPy mirror, bit for bit): states that differed only in dropped
+        latents collapse, the first stays in its slot and the others are replaced by unused singletons and pairs, so every
+        datapoint keeps S distinct states.  Requires Hv' (Hv' + 1) / 2 >= S.  Theta goes through
+        evo_amd.models.remap_theta(model_name, model_params, index, **new_columns) (W_new, pies_new, mus_new,
+        Psi_diag_new, rng).  Returns (new_model, new_theta, new_suff, info): ``new_model`` is type(self)(D, H', S, ...) with
+        this model's settings ON THE SAME ENGINE, prepared (configure, data, masks) with the remapped K^n resident and its
+        lpj rows under ``new_theta`` computed, so encode, posterior_scores, refine_resident_states or step can follow at
+        once; ``new_suff`` has my_suff_stat's keys re-derived for H' ("ss" / "lpj" None with sync_host=False, downloaded
+        once with sync_host=True); ``info`` = {"n_replaced" (N,), "sum_replaced", "index"}.  This model is invalidated
+        (its K^n is gone from the device; it uploads again when used).  sync_host=True (or a K^n that is not resident)
+        uploads my_suff_stat["ss"] first.  ValueError before the device is touched for an index the law refuses; in the
+        float32 mode configure's own H % 4 rule applies to H'.  Several ranks: each remaps its shard, no collective."""
+        from ..variational.utils import check_remap_index
+        from .remap import remap_theta
+        permanent = my_suff_stat["permanent"]
+        background = bool(permanent["background"])
+        idx = check_remap_index(index, self.H, self.S, background)
+        H2 = int(idx.size)
+        new_theta = remap_theta(self.model_name, model_params, idx, **new_columns)
+        if not self.sync_host and not self._resident and my_suff_stat.get("ss") is None:
+            raise ValueError("remap_latents: K^n is neither resident on the device nor in my_suff_stat['ss']")
+        eng = self._prepare(my_suff_stat, my_data)
+        n_replaced, total = eng.remap_latents(idx)
+        new_model = type(self)(self.D, H2, self.S, **self._clone_kwargs())
+        new_suff = dict(my_suff_stat)
+        derived = _host_init_states(0, self.S, H2, "fit", "randflip", 1, 1, 1, None, None, None, permanent)
+        for key in ("incl", "sm", "S_perm"):
+            new_suff[key] = derived[key]
+        new_suff["ss"] = new_suff["lpj"] = None
+        self.invalidate()  # from here on the engine belongs to the new geometry
+        neng = new_model._prepare(new_suff, my_data, upload_states=False)
+        neng.adopt_remapped_states()
+        new_model._resident = True
+        new_theta = new_model.check_params(new_theta)
+        new_model.E_step_precompute(new_theta, new_suff, my_data)
+        neng.lpj_resident()
+        if self.sync_host:
+            new_suff["ss"] = neng.download_states()
+            new_suff["lpj"] = neng.download_lpj()
+        return new_model, new_theta, new_suff, {"n_replaced": n_replaced, "sum_replaced": total, "index": idx}
+
+    def latent_usage(self, model_params, my_suff_stat, my_data):
+        """Which latents the data use, over all ranks: {"usage": (H,) = sum_n E_q[s_h] / N -- the column sums one
+        statistics pass leaves in its accumulator, all-reduced like it --, "map_count": int64 (H,) = datapoints whose most
+        probable state of K^n (the first column of maximal lpj) has latent h on (Engine.latent_map_counts), "N"}.
+        evo_amd.variational.latent_usage_host is the NumPy mirror; prune_index turns "usage" into an index for
+        remap_latents.  Works with sync_host=False; writes nothing into the three dicts."""
+        uploads = self._kn_uploads  # (see reconstruct(): decide before _prepare() runs)
+        eng = self._prepare(my_suff_stat, my_data)
+        # (the precompute stores its derived keys and zeroes the reset counters: on shallow copies here)
+        self.E_step_precompute(dict(model_params), dict(my_suff_stat), my_data)
+        if model_params is not self._dev_theta:
+            self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
+        if self.sync_host or self._kn_uploads != uploads:
+            eng.upload_lpj(my_suff_stat["lpj"])
+        if self._incomplete:
+            eng.set_option("reconstruct_in_stats", 1)
+            self._yrec_token = None  # the pass overwrites the device's y_reconstructed: the next M-step uploads the caller's
+        acc = eng.stats()
+        if not getattr(self.comm, "device_reduces", False):
+            acc = _reduce_array(self.comm, acc)
+        v = eng.acc_views(acc)
+        N = float(v["N"])
+        counts = eng.latent_map_counts()
+        if self.comm.size > 1:
+            counts = np.rint(_reduce_array(self.comm, counts.astype(np.float64))).astype(np.int64)
+        sums = v["pies"] if self.model_name == "bsc" else v["xpt_s"]
+        return {"usage": np.array(sums, dtype=np.float64) / N, "map_count": counts, "N": int(N)}
+
     def _stats_for_mstep(self, model_params, my_suff_stat, my_data, _from_step):
         """Accumulators for the M-step: reuse the ones E_step just produced inside step(), else
         recompute them from the caller's K^n / lpj arrays."""

@@ -38,6 +38,11 @@ class SSSC(Model):
             "sigma2": (tol, +np.inf, False, None),
         }
 
+    def _clone_kwargs(self):
+        kw = Model._clone_kwargs(self)
+        kw.update(use_storage=self.use_storage, precision=self.dtype_precision)
+        return kw
+
     # ---- generative model (host, off the hot path) -------------------------------------------
     def generate_from_hidden(self, model_params, my_hdata):
         """z_A ~ N(mus_A, Psi_AA), y = W_A z_A + N(0, sigma2) (sssc.py:65-102); RNG per datapoint:

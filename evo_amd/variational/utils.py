@@ -376,3 +376,134 @@ def posterior_scores_host(lpj, ss=None, S_perm=0):
         out["k_best"] = k[np.arange(N), out["best"]].astype(np.int32)
         out["k_mean"] = (w * k).sum(axis=1) / z
     return out
+
+
+# ---- the dictionary resized: the NumPy mirror of evoamd_remap_latents (csrc/kernels_remap.hpp) -----------------------------
+#
+# index: int (H',); an entry >= 0 names a source latent in [0, H), each at most once; -1 marks a NEW latent, off in every
+# state.  Hv' = H' - 1 with the background unit (the last entry is then H - 1), else H'.  Per datapoint: gather t_j[h'] =
+# s_j[index[h']] (0 for -1); slot j is KEPT iff t_j differs from every t_i with i < j and, with S_perm = 1, is not all-zero;
+# the other slots, in ascending order, each take the next state of the enumeration {0}, {1}, .. {Hv' - 1}, {0,1}, {0,2}, ..
+# {0,Hv'-1}, {1,2}, .. (each with the background bit) that equals no kept state of the datapoint.  Hv' (Hv' + 1) / 2 >= S
+# guarantees that the enumeration does not run out.
+REMAP_MAX_H = 1 << 14  # DIG_MAX_H of csrc/common.hpp
+
+
+def check_remap_index(index, H, S, background=False):
+    """``index`` as a validated int32 array; ValueError naming the rule otherwise."""
+    idx = np.asarray(index)
+    if idx.ndim != 1 or idx.size < 1 or not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError("remap: index must be a one-dimensional integer array with at least one entry")
+    idx = idx.astype(np.int32)
+    H2 = idx.size
+    if H2 > REMAP_MAX_H:
+        raise ValueError("remap: H' = %d exceeds %d" % (H2, REMAP_MAX_H))
+    bad = np.flatnonzero((idx < -1) | (idx >= H))
+    if bad.size:
+        raise ValueError("remap: index[%d] = %d is out of range (-1 or a source latent in [0, %d))"
+                         % (bad[0], idx[bad[0]], H))
+    src = idx[idx >= 0]
+    uniq, cnt = np.unique(src, return_counts=True)
+    if (cnt > 1).any():
+        raise ValueError("remap: duplicate source latent %d" % uniq[cnt > 1][0])
+    if background:
+        if idx[-1] == -1:
+            raise ValueError("remap: a new latent (-1) cannot take the background unit's place: the last index must be "
+                             "H - 1 = %d" % (H - 1))
+        if idx[-1] != H - 1:
+            raise ValueError("remap: the background unit is not last: the last index must be H - 1 = %d (it is %d)"
+                             % (H - 1, idx[-1]))
+    Hv2 = H2 - (1 if background else 0)
+    if Hv2 * (Hv2 + 1) // 2 < S:
+        raise ValueError("remap: Hv' (Hv' + 1) / 2 = %d fill candidates are fewer than S = %d states (Hv' = %d): such "
+                         "shapes belong to init_states" % (Hv2 * (Hv2 + 1) // 2, S, Hv2))
+    return idx
+
+
+def _remap_enumeration(Hv2, H2, background):
+    for a in range(Hv2):
+        row = np.zeros(H2, dtype=bool)
+        row[a] = True
+        if background:
+            row[-1] = True
+        yield row
+    for a in range(Hv2):
+        for b in range(a + 1, Hv2):
+            row = np.zeros(H2, dtype=bool)
+            row[a] = row[b] = True
+            if background:
+                row[-1] = True
+            yield row
+
+
+def remap_states_host(ss, index, S_perm=0, background=False):
+    """K^n in the latent numbering ``index`` as evoamd_remap_latents / Model.remap_latents lay it out: ``ss`` bool
+    (N, S, H) -> (ss_new bool (N, S, H'), n_replaced int32 (N,)).  Host only; ValueError for an index the law refuses."""
+    ss = np.asarray(ss, dtype=bool)
+    N, S, H = ss.shape
+    idx = check_remap_index(index, H, S, background)
+    H2 = idx.size
+    Hv2 = H2 - (1 if background else 0)
+    out = np.zeros((N, S, H2), dtype=bool)
+    src = idx >= 0
+    out[:, :, src] = ss[:, :, idx[src]]
+    n_replaced = np.zeros(N, dtype=np.int32)
+    for n in range(N):
+        kept, dup = set(), []
+        for j in range(S):
+            key = out[n, j].tobytes()
+            if key in kept or (S_perm and not out[n, j].any()):
+                dup.append(j)
+            else:
+                kept.add(key)
+        if dup:
+            fills = _remap_enumeration(Hv2, H2, background)
+            for j in dup:
+                row = next(fills)
+                while row.tobytes() in kept:
+                    row = next(fills)
+                out[n, j] = row
+            n_replaced[n] = len(dup)
+    return out, n_replaced
+
+
+def latent_usage_host(ss, lpj, S_perm=0):
+    """NumPy mirror of Model.latent_usage on one rank: {"usage": (H,) = sum_n E_q[s_h] / N with q_ns = exp(lpj_ns - max) /
+    (sum_s exp(lpj_ns - max) + tiny) as the statistics pass forms it, "map_count": int64 (H,) = datapoints whose first
+    column of maximal lpj is a state with latent h on, "N"}.  ``lpj`` (N, S_perm + S); columns below S_perm are the
+    permanent all-zero state."""
+    ss = np.asarray(ss, dtype=bool)
+    lpj = np.asarray(lpj, dtype=np.float64)
+    N, S, H = ss.shape
+    assert lpj.shape == (N, S + S_perm), (lpj.shape, (N, S + S_perm))
+    m = lpj.max(axis=1)
+    w = np.exp(lpj - m[:, None])
+    q = w[:, S_perm:] / (w.sum(axis=1) + np.finfo(np.float64).tiny)[:, None]
+    Es = np.einsum("ns,nsh->nh", q, ss)
+    best = np.argmax(lpj == m[:, None], axis=1)
+    in_kn = best >= S_perm
+    rows = np.flatnonzero(in_kn)
+    counts = ss[rows, best[rows] - S_perm].sum(axis=0).astype(np.int64) if rows.size else np.zeros(H, dtype=np.int64)
+    return {"usage": Es.sum(axis=0) / N, "map_count": counts, "N": N}
+
+
+def prune_index(usage, keep_min=None, n_keep=None, n_new=0, background=False):
+    """An ``index`` for remap_latents from a per-latent usage (Model.latent_usage()["usage"]): the latents with usage >=
+    ``keep_min`` or, with ``n_keep``, the n_keep most used ones (ties: the lower latent), in ascending order; then
+    ``n_new`` entries -1; with ``background`` the last latent is kept whatever its usage and stays last, behind the new
+    ones.  Exactly one of ``keep_min`` / ``n_keep``."""
+    usage = np.asarray(usage, dtype=np.float64)
+    if usage.ndim != 1 or (keep_min is None) == (n_keep is None):
+        raise ValueError("prune_index: a one-dimensional usage and exactly one of keep_min / n_keep")
+    H = usage.size
+    Hv = H - 1 if background else H
+    if keep_min is not None:
+        kept = np.flatnonzero(usage[:Hv] >= keep_min)
+    else:
+        if not 0 <= int(n_keep) <= Hv:
+            raise ValueError("prune_index: n_keep = %d must be in [0, %d]" % (n_keep, Hv))
+        kept = np.sort(np.argsort(-usage[:Hv], kind="stable")[:int(n_keep)])
+    parts = [kept.astype(np.int32), np.full(int(n_new), -1, dtype=np.int32)]
+    if background:
+        parts.append(np.array([H - 1], dtype=np.int32))
+    return np.concatenate(parts)

@@ -709,6 +709,36 @@ int evoamd_patches_merge_samples(evoamd_ctx *ctx, int H, int W, int C, int ph, i
 int evoamd_patches_merge_predictive(evoamd_ctx *ctx, int H, int W, int C, int ph, int pw, int shift, int what,
                                     double *img_out);
 
+/* ---- the dictionary resized: prune, reorder, grow ------------------------------------ */
+/* K^n moved to a new latent numbering on the device (csrc/kernels_remap.hpp has the law;
+ * evo_amd.variational.remap_states_host is its NumPy mirror, bit for bit).  index: int32 (H_new); an entry >= 0 names a
+ * source latent in [0, H), each at most once; -1 marks a NEW latent, off in every state.  Hv' = H_new - 1 with the
+ * "background_unit" option (the last entry must then be H - 1: the unit stays last and on), else H_new.  Per datapoint:
+ *   gather  t_j[h'] = s_j[index[h']] where index[h'] >= 0, else 0, for the S slots of K^n (the permanent all-zero column of
+ *           S_perm = 1 is not a slot);
+ *   keep    slot j is kept iff t_j differs from every t_i with i < j and, where S_perm = 1, is not the all-zero state;
+ *   fill    the other slots, in ascending order, each take the next state of the enumeration {0}, {1}, .. {Hv' - 1}, {0,1},
+ *           {0,2}, .. {0,Hv'-1}, {1,2}, .. (each ORed with the background bit) that equals no kept state of the datapoint;
+ *   bound   Hv' (Hv' + 1) / 2 >= S, so that the enumeration cannot run out.
+ * The result -- packed states (N, S, ceil(H_new/64)), their digests, n_replaced (N) -- goes to scratch the context owns and
+ * that survives evoamd_configure; the resident K^n, the lpj rows and every validity flag stay as they are.
+ * n_replaced_out (N) and sum_out may be NULL.  Deterministic: two calls give the same bits.
+ * EVOAMD_E_INVALID, before anything is launched and with the context as it was, for: no configured context or a K^n lost
+ * to a failed evoamd_init_states; an index entry outside {-1} + [0, H); a source named twice; with the background unit a
+ * last entry other than H - 1; H_new outside [1, 16384]; the bound; and an S whose LDS slice -- 8 S (ceil(H/64) +
+ * ceil(H_new/64) + 1) bytes beside 256 ceil(H_new/64) bytes of index -- exceeds 150 KiB (S <= 1024 fits up to
+ * H + H_new = 1088; the message names the cap of the shape).
+ * Then: evoamd_configure for H_new (same N and S), data and Theta as usual, and evoamd_adopt_remapped_states, which makes
+ * the scratch the resident K^n and digests -- what evoamd_upload_states of the same rows leaves, with the same
+ * invalidations (census, row statistics, prefetched pass) -- and releases it.  EVOAMD_E_INVALID with K^n as it was when
+ * (N, S, H) of the context differ from the scratch's, and for an adopt without a remap before it (a second adopt). */
+int evoamd_remap_latents(evoamd_ctx *ctx, const int32_t *index, int H_new, int32_t *n_replaced_out, int64_t *sum_out);
+int evoamd_adopt_remapped_states(evoamd_ctx *ctx);
+/* counts_out (H): the number of datapoints whose most probable state of K^n -- the first column of maximal lpj, the rule of
+ * evoamd_posterior_scores' best -- has latent h on.  Integer atomics: independent of the order.  Needs valid lpj rows;
+ * nothing of the EM state changes. */
+int evoamd_latent_map_counts(evoamd_ctx *ctx, int64_t *counts_out);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------------- */
 /* 128-byte opaque id made by rank 0 and distributed by the caller (file / socket / MPI). */
 int evoamd_comm_unique_id(uint8_t id_out[128]);
@@ -751,7 +781,8 @@ enum {
   EVOAMD_K_LOGLIK_PROPOSAL = 25, /* evoamd_loglik_estimate: the proposal kernel (marginals, draws, membership), per pass */
   EVOAMD_K_LOGLIK_LPJ = 26,    /* ... the lpj launches over a pass's outside draws (every level)                          */
   EVOAMD_K_LOGLIK_FOLD = 27,   /* ... the fold kernel of a pass; the bound + all-zero terms and the finish (one span each) */
-  EVOAMD_K_COUNT = 28
+  EVOAMD_K_REMAP = 28,         /* evoamd_remap_latents: the remap kernel (index upload and downloads excluded) */
+  EVOAMD_K_COUNT = 29
 };
 /* on = bit mask of kernel classes to time (bit k = class k; -1 = all, 0 = off).  Each timed span
  * records two HIP events on the compute stream, which costs about 10 us of stream time per span:
