@@ -50,7 +50,7 @@ KERNEL_IDS = {
 # classes outside the EM path, added after tests/test_gpu_validity.py recorded its launch census over KERNEL_IDS (which
 # therefore stays as it is); Engine.timing / Engine.kernel_time_ms take names of either table
 KERNEL_IDS_EXTRA = {"posterior_sample": 23, "seed_states": 24, "loglik_proposal": 25, "loglik_lpj": 26, "loglik_fold": 27,
-                    "remap_latents": 28}
+                    "remap_latents": 28, "stats_kappa": 29}
 
 
 def kernel_id(name):

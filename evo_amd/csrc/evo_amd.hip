@@ -161,6 +161,8 @@ enum {  // internal kernel ids (see evoamd_kernel_name)
   KID_LLE_LPJ,       // ... the lpj launches over the outside draws, all passes
   KID_LLE_FOLD,      // ... the fold kernel of every pass and the finish
   KID_REMAP,         // evoamd_remap_latents: the remap kernel (index upload and downloads excluded)
+  KID_STATS_KAPPA,   // the ES3C statistics kernel on the kappa route (option "stats_kappa"), nested in KID_STATS: its launch count
+                     // says which route a pass took
   KID_COUNT
 };
 
@@ -494,6 +496,19 @@ struct evoamd_ctx {
   // option "merge_small_levels": with few states above four active latents (census of the last statistics pass) the
   // pivoting wavefront kernel serves the 5..8 list too, instead of a quad launch of its own (3 passes x ~10-20 us)
   int merge_small = 1;
+  // ES3C kappa records (kernels_sssc.hpp: sssc_stats_wave_kernel<.., KAP>): {kappa_0, kappa_1} per resident state (N x S) and
+  // per candidate (N x Cmax), written by the table-driven lpj kernels beside the lpj, carried by the selection kernel, read by
+  // the statistics pass instead of the B rows and the state-term tables.  Allocated by evoamd_configure where the route
+  // can run (kappa_shape_ok).  kap_gen / cand_kap_gen: the `gen` they were written (or carried into) -- valid while equal
+  // to c->gen; kap_carry: the selection that is being enqueued moves the records with the states.
+  DevBuf<double2> kap, cand_kap;
+  unsigned long long kap_gen = ~0ull, cand_kap_gen = ~0ull;
+  bool kap_carry = false;
+  int stats_kappa = 1;  // option "stats_kappa": 0 never / 1 from kappa_min resident states on / 2 wherever the shape allows it
+  int kappa_min = 16384;  // option "stats_kappa_min": the automatic setting takes the route from this many resident states
+                          // (x 1024) on -- measured: N S = 20 M gains 0.07 ms of 3.9, 10 M is even (0.01 of 2.23, inside
+                          // the noise), 2.5 M and 0.64 M lose 0.005-0.01 ms (the record stores, the second finish launch
+                          // and the fourth plane cost more than the gathers saved)
   int stats_flat = 0;   // option "stats_flat": census mode, states with <= 2 latents on the thread-per-state kernel instead of
                         // the wave-per-datapoint one.  Measured (c4, steady state): 504-539 vs 584 us for the kernel, but the
                         // quad levels then share 256 bin regions instead of 2048 (107 vs 69 us) and N / 8 shards lose: off
@@ -610,6 +625,7 @@ static void on_configure(evoamd_ctx *c) {
   c->have_data = c->have_params = c->have_cand = c->rows_fresh = c->acc_clean = c->clist_clean = false;
   c->h_theta_fresh = c->theta_bak_valid = c->yrec_valid = c->rec_in_stats = c->keep_x_valid = c->kn_lost = false;
   c->lists_clean = c->need_known = c->cand_from_device = false;  // fresh (uninitialised) overflow counters
+  c->kap_gen = c->cand_kap_gen = ~0ull, c->kap_carry = false;
   // gap: a context that goes from ES3C to EBSC keeps last_estep_fused; if it was set, EBSC never prefetches (only slower)
   if (c->model == EVOAMD_MODEL_SSSC) c->last_estep_fused = false;
   drop_stats_products(c);
@@ -669,10 +685,16 @@ static void made_theta_mailbox(evoamd_ctx *c, bool holds_theta) { c->h_theta_fre
 // keeps the level hints (the counts of the last statistics pass remain the best estimate); a K^n from the caller drops them.
 enum KnBy { KN_BY_CALLER, KN_BY_SELECTION };
 static void on_kn_changed(evoamd_ctx *c, KnBy by) {
+  // the kappa records follow K^n through a selection only, and only when both sides hold current ones (made_selection
+  // stamps them again); every other event -- and every other gen++ above and below -- leaves them behind
+  c->kap_carry = by == KN_BY_SELECTION && c->kap_gen == c->gen && c->cand_kap_gen == c->gen;
   c->gen++;
   c->kn_gen++;
   if (by == KN_BY_CALLER) c->need_known = false;
 }
+// kappa records (ES3C, option "stats_kappa"): the pass over K^n / over the candidate batch wrote them under this gen (or not)
+static void made_kappa(evoamd_ctx *c, bool written) { c->kap_gen = written ? c->gen : ~0ull; }
+static void made_cand_kappa(evoamd_ctx *c, bool written) { c->cand_kap_gen = written ? c->gen : ~0ull; }
 static void on_kn_complete(evoamd_ctx *c) { c->kn_lost = false; }  // a whole K^n arrived: upload, or evoamd_init_states to its end
 // evoamd_init_states begun: K^n counts as lost until the kernel has completed every datapoint (stopped at its round cap:
 // no event, it stays lost)
@@ -713,8 +735,10 @@ static void on_levels_skipped(evoamd_ctx *c, bool census_route, int skipped, int
 }
 // the selection kernel: row statistics of the new lpj rows, and on its way the old census checked + cleared, the
 // accumulators of the next statistics pass zeroed, the on-the-fly lists cleared
-static void made_selection(evoamd_ctx *c, bool census_cleared, bool acc_zeroed) {
+static void made_selection(evoamd_ctx *c, bool census_cleared, bool acc_zeroed, bool kappa_carried) {
   made_row_stats(c);
+  if (kappa_carried && c->kap_carry) c->kap_gen = c->gen;
+  c->kap_carry = false;
   if (census_cleared) {
     c->clist_clean = true;
     c->census_skip = 0;
@@ -730,16 +754,17 @@ static void on_census_poisoned(evoamd_ctx *c) { c->kn_gen++; }  // test hook: re
 // ---- candidates
 // `near_parents`: children of evolve_randflip (k <= k_parent + 1: the overflow levels take a shortcut); a batch from the
 // host or from the general operators may differ from every resident state in many bits
-static void on_cand_installed(evoamd_ctx *c, bool near_parents) { c->cand_from_device = near_parents; }
+static void on_cand_installed(evoamd_ctx *c, bool near_parents) { c->cand_from_device = near_parents, c->cand_kap_gen = ~0ull; }
 static void made_cand_lpj(evoamd_ctx *c) { c->have_cand = true; }
 // the candidate buffers were borrowed for states that are no children of K^n (the importance draws of
 // evoamd_loglik_estimate): no batch counts as installed, evoamd_vary_kn refuses until the next one
-static void drop_cand_batch(evoamd_ctx *c) { c->have_cand = false, c->cand_from_device = false; }
+static void drop_cand_batch(evoamd_ctx *c) { c->have_cand = false, c->cand_from_device = false, c->cand_kap_gen = ~0ull; }
 // fused E-step: K^n advanced, its rows and (small shards) its census came with it, the children never left the kernel
 static void made_fused_estep(evoamd_ctx *c, bool inkernel_census) {
   on_kn_changed(c, KN_BY_SELECTION);
   if (inkernel_census) made_census(c);
   made_row_stats(c);
+  c->kap_carry = false;  // the fused kernel carries no kappa records
   c->have_cand = false, c->cand_from_device = true;
   on_estep_route(c, true);
 }
@@ -903,9 +928,10 @@ static int set_kernel_lds_limits() {
                         (const void *)sssc_stats_wave_kernel<2, 4>,  (const void *)sssc_stats_wave_kernel<4, 4>,
                         (const void *)sssc_stats_wave_kernel<8, 4>,  (const void *)sssc_stats_wave_kernel<16, 4>,
                         (const void *)sssc_stats_wave_kernel<0, 1>,  (const void *)sssc_stats_wave_kernel<0, 8>,
-                        (const void *)sssc_stats_wave_kernel<0, 16>};
+                        (const void *)sssc_stats_wave_kernel<0, 16>, (const void *)sssc_stats_wave_kernel<1, 4, true, true>};
     for (const void *f : wk) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));  // + <= 9.2 KiB static
-    HIP_TRY(hipFuncSetAttribute((const void *)pair_bins_reduce_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * PB_TILE * 8));
+    HIP_TRY(hipFuncSetAttribute((const void *)pair_bins_reduce_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * PB_TILE * 8));
+    HIP_TRY(hipFuncSetAttribute((const void *)pair_bins_reduce_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * PB_TILE * 8));
     HIP_TRY(hipFuncSetAttribute((const void *)sssc_small_kernel<4, 1, 2, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
     HIP_TRY(hipFuncSetAttribute((const void *)sssc_small_kernel<8, 1, 2, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
   }
@@ -1076,13 +1102,24 @@ static const OptionRow OPTIONS[] = {
     {"state_digest", OPT_BOOL(use_digest), opt_flag},
     {"inverse_spd", OPT_BOOL(spd_inverse), opt_flag},
 };
+// Options added after tests/test_host_logic.py wrote out the names of the table above (which therefore stays as it is,
+// like _lib.KERNEL_IDS); tests/test_stats_kappa_algebra.py holds these to the same rule: documented in include/evo_amd.h
+// and listed in INTEGRATION.md.
+static const OptionRow OPTIONS_LATER[] = {
+  {"stats_kappa", OPT_INT(stats_kappa), nullptr, 0, 2, nullptr, "stats_kappa: 0 (never), 1 (automatic) or 2 (wherever the shape allows it)"},
+  {"stats_kappa_min", OPT_INT(kappa_min), nullptr, 0, 1 << 20, nullptr, "stats_kappa_min: 0 .. 1048576 (x 1024 resident states)"},
+};
 #undef OPT_INT
 #undef OPT_BOOL
 
 extern "C" int evoamd_set_option(evoamd_ctx *c, const char *name, int value) {
   REQUIRE(c && name, "bad arguments");
   on_option(c);
-  for (const OptionRow &o : OPTIONS) {
+  std::vector<const OptionRow *> rows;
+  for (const OptionRow &o : OPTIONS) rows.push_back(&o);
+  for (const OptionRow &o : OPTIONS_LATER) rows.push_back(&o);
+  for (const OptionRow *row : rows) {
+    const OptionRow &o = *row;
     if (strcmp(name, o.name) != 0) continue;
     if (o.err && !(o.accepts ? o.accepts(value) : (value >= o.lo && value <= o.hi))) return fail(EVOAMD_E_INVALID, "%s", o.err);
     const int v = o.norm ? o.norm(value) : value;
@@ -1162,8 +1199,9 @@ static int alloc_pair_bins(evoamd_ctx *c, int scale) {
     // the chip -- H = 128 has 4 bins, H = 256 has 16: with 4 workgroups each the reduce ran on 16 / 64 of 256 CUs
     pb.nsh = std::max((i64)N * S >= (i64)8 << 20 ? 8 : 4, std::min(PB_NSH_MAX, 256 / std::max(1, pb.nb)));
     pb.cap = (int)std::max<i64>(64, (i64)scale * cdiv((i64)N * S, (i64)pb.nb * pb.nwg));
+    pb.planes = 3;  // (room for four: the ES3C kappa route reduces its passes into four, stats_sssc_block)
     const size_t ne = (size_t)pb.nb * pb.nwg * pb.cap;
-    if (c->pb_ent.try_alloc(ne) && c->pb_part.try_alloc((size_t)pb.nb * pb.nsh * 3 * 2 * pb.rf * H) &&
+    if (c->pb_ent.try_alloc(ne) && c->pb_part.try_alloc((size_t)pb.nb * pb.nsh * (c->model == EVOAMD_MODEL_SSSC ? 4 : 3) * 2 * pb.rf * H) &&
         c->pb_gcnt.try_alloc((size_t)pb.nb * pb.nwg)) {
       pb.ent = c->pb_ent;
       pb.part = c->pb_part;
@@ -1205,6 +1243,12 @@ static int ensure_bins_capacity(evoamd_ctx *c) {
   return 0;
 }
 
+// ES3C kappa route: does the option ask for it at this size?  (Read by evoamd_configure for the record buffers and by
+// kappa_shape_ok for every pass.)
+static bool kappa_wanted(const evoamd_ctx *c) {
+  return c->stats_kappa == 2 || (c->stats_kappa == 1 && c->N * (i64)c->S >= (i64)c->kappa_min * 1024);
+}
+
 // ---- evoamd_configure: unconfigured -> validate -> geometry -> drop -> allocate by group -> clear -> flags -> configured ----
 static int configure_validate(const evoamd_ctx *c, int model, i64 N, int D, int H, int S, int S_perm, int Cmax) {
   REQUIRE(model == EVOAMD_MODEL_BSC || model == EVOAMD_MODEL_SSSC, "unknown model");
@@ -1233,7 +1277,8 @@ static void configure_geometry(evoamd_ctx *c, int model, i64 N, int D, int H, in
   c->acc_n = acc_len(c);
   // in front of the packed accumulator, cleared by the same memset: [overflow census (4) | CS_SLICES column-sum
   // slices of 3 H | overflow H x H pair] (ES3C)
-  c->pre_n = (model == EVOAMD_MODEL_SSSC) ? 4 + (i64)CS_SLICES * 3 * H : 4 + (i64)BSC_CS_SLICES * H;
+  // (ES3C: + CS_SLICES slices of H, the singleton states' sums of q of the kappa route)
+  c->pre_n = (model == EVOAMD_MODEL_SSSC) ? 4 + (i64)CS_SLICES * 4 * H : 4 + (i64)BSC_CS_SLICES * H;
   c->ovf_n = c->pre_n + ((model == EVOAMD_MODEL_SSSC) ? 2 * (i64)H * H : 0);
 }
 
@@ -1387,6 +1432,16 @@ static int configure_alloc_lists(evoamd_ctx *c) {
     TRY(c->clist.alloc(3 * list_cap(c->N * (i64)c->S) * LIST_SHARDS));
     TRY(c->clist_n.alloc(4 * LIST_SHARDS));
     TRY(c->ovf_rec.alloc((size_t)c->N * c->S));
+  }
+  // the kappa records, where the route can run at all (optional: without them the passes take the table route)
+  c->kap.reset();
+  c->cand_kap.reset();
+  if (c->census_opt && kappa_wanted(c) && c->dig && (c->H % 2) == 0 && !c->sssc_prec32 &&
+      (size_t)(4 * 2 + 4) * c->H * sizeof(double) <= 150 * 1024) {
+    if (!c->kap.try_alloc((size_t)c->N * c->S) || !c->cand_kap.try_alloc((size_t)c->N * c->Cmax)) {
+      c->kap.reset();
+      c->cand_kap.reset();
+    }
   }
   return 0;
 }
@@ -2438,6 +2493,12 @@ static size_t main_lpj_lds(int C, int H) {
   return ((size_t)(1024 / C + 2) * H + (H <= 512 ? (size_t)4 * H : 0)) * sizeof(double);
 }
 
+// ES3C kappa route (option "stats_kappa"): what the lpj passes and the statistics pass both need -- the record buffers
+// (allocated by evoamd_configure where H and the options allowed it), census lists, digests, complete data, f64, even H
+static bool kappa_shape_ok(const evoamd_ctx *c) {
+  return kappa_wanted(c) && c->kap && c->cand_kap && census_mode(c) && (c->H % 2) == 0 && !c->sssc_prec32;
+}
+
 enum LpjRoute {
   LPJ_MASKED,  // incomplete data: the wavefront kernel for every pair
   LPJ_CENSUS,  // pass over the resident K^n with census lists: the main kernel appends nothing, the levels read the lists
@@ -2469,6 +2530,7 @@ struct LpjPlan {
   bool few4;       // census / chains: the wavefront launch serves the 5..8 list too (few_above4)
   bool k8;         // round 2: K = 8 register kernel (use_k8_kernel)
   bool few_dense;  // round 2: one wavefront launch for lists 2 and 3 (few_dense_states)
+  bool kappa;      // the table-driven main kernel leaves the kappa records of its states (K^n: c->kap, candidates: c->cand_kap)
 };
 
 // Fills the plan from the context as it is at entry.  Enqueues nothing.  `tag` (Batch::tag) names the kernel
@@ -2508,6 +2570,11 @@ static void lpj_plan(const evoamd_ctx *c, const SsscArgs &a, int tag, const Leve
     p.main = LPJ_MAIN_SMALL;
     p.grid = cdiv(p.total, 512);
   }
+  // kappa records for the statistics pass (option "stats_kappa"): the pass over K^n and the resident candidate batch,
+  // on any form of the table-driven main kernel (it evaluates every state with at most two latents in all of them)
+  p.kappa = kappa_shape_ok(c) && !lv.levels_only &&
+            (p.main == LPJ_MAIN_CENSUS || p.main == LPJ_MAIN_STAGED || p.main == LPJ_MAIN_UNSTAGED) &&
+            ((tag == 0 && a.states == c->states && a.C == c->S) || (tag == 1 && a.states == c->cand && a.C == c->Cmax));
   p.few4 = p.route != LPJ_ROUND2 && few_above4(c, lv);
   p.k8 = p.route == LPJ_ROUND2 && use_k8_kernel(c, lv);
   p.few_dense = p.route == LPJ_ROUND2 && few_dense_states(c, lv);
@@ -2659,10 +2726,14 @@ static int lpj_sssc_round2_levels(evoamd_ctx *c, const SsscArgs &a, const LpjPla
 //
 // (zero_lists has checked and cleared what the chain before left, so pending_skip is 0 when the table is applied.)
 template <int TAG>
-static int launch_sssc_lpj(evoamd_ctx *c, const SsscArgs &a, int kid_main, const LevelHints &lv) {
+static int launch_sssc_lpj(evoamd_ctx *c, const SsscArgs &a_in, int kid_main, const LevelHints &lv) {
   TRY(zero_lists(c));
   LpjPlan p;
-  lpj_plan(c, a, TAG, lv, kid_main, p);
+  lpj_plan(c, a_in, TAG, lv, kid_main, p);
+  SsscArgs a = a_in;
+  if (p.kappa) a.kap_out = TAG == 0 ? c->kap.get() : c->cand_kap.get();
+  if (TAG == 0 && a.states == c->states) made_kappa(c, p.kappa);
+  if (TAG == 1 && a.states == c->cand) made_cand_kappa(c, p.kappa);
   if (p.route == LPJ_MASKED) return lpj_sssc_masked(c, a, p);
   if (p.route == LPJ_CENSUS) TRY(ensure_census(c));
   TRY(lpj_sssc_main<TAG>(c, a, p));
@@ -2883,18 +2954,20 @@ static int estep_select(evoamd_ctx *c, int Mprime, double *sums_out) {
     int *cl_n = census_mode(c) ? c->clist_n : nullptr;  // the old census dies with the old K^n: checked + cleared on the way
     const i64 zero_n = c->fold_clear ? (i64)(c->ovf_n + c->acc_n) : 0;  // ... and the next statistics pass finds its accumulators zeroed
     if (!c->fold_clear) cl_n = nullptr;
+    const bool kap_carry = c->kap_carry && c->kap && c->cand_kap;  // both sides hold current kappa records: they move along
     with_spl(c->S, [&](auto spl) {
       with_cpl(c->Cmax, [&](auto cpl) {
         vary_kn_kernel<decltype(spl)::value, decltype(cpl)::value><<<cdiv(c->N, 4), 256, 0, c->stream>>>(
             c->states, c->lpj, c->cand, c->cand_lpj, c->cand_counts, c->N, c->S, c->S_perm, c->HW, c->Cmax, Mprime, c->rowmax,
             c->rowsum, c->partial, c->list_n, 4 * LIST_SHARDS, c->dig, c->cand_dig, (c->use_digest && c->dig) ? 1 : 0,
-            c->pending_skip, c->err, cl_n, 4 * LIST_SHARDS, c->census_skip, c->acc_base, zero_n);
+            c->pending_skip, c->err, cl_n, 4 * LIST_SHARDS, c->census_skip, c->acc_base, zero_n,
+            kap_carry ? c->kap.get() : nullptr, kap_carry ? c->cand_kap.get() : nullptr);
       });
     });
     reduce3_partials_kernel<<<1, R3_THREADS, 0, c->stream>>>(c->partial, cdiv(c->N, 4), c->dpar);
     HIP_TRY(hipGetLastError());
     DBG_SYNC(c, "vary_kn");
-    made_selection(c, cl_n != nullptr, zero_n > 0);
+    made_selection(c, cl_n != nullptr, zero_n > 0, kap_carry);
   }
   if (sums_out) {
     HIP_TRY(hipMemcpyAsync(sums_out, c->dpar + DP_ECNT0, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -3540,6 +3613,7 @@ struct StatsPlan {
   int waves;       // waves per workgroup of the ES3C wave-per-datapoint kernel
   bool census;     // ES3C: the levels read the census lists
   bool bsc_wave;   // EBSC: the wave-per-datapoint kernel (else the round-1 kernel + column-sum pass)
+  bool kappa;      // ES3C: the kappa route -- the main kernel reads the lpj pass's kappa records instead of B rows and tables
 };
 
 // One block of datapoints: rows [n0, n0 + nc) = column-sum partials [blk0, blk0 + nblk_c)
@@ -3678,6 +3752,10 @@ static int stats_plan(evoamd_ctx *c, bool fork_gemm, StatsPlan &p) {
                 : ((size_t)(4 * 2 + 3) * p.H * sizeof(double) <= 150 * 1024 ? 4 : 1);
   p.census = census_mode(c) && !p.masked && p.waves == 4;
   if (p.census) nchunks = 1;  // the census lists cover the whole shard
+  // kappa route (option "stats_kappa"): census lists + the four-wave kernel with staging on (not a measurement form of
+  // it), and records written under this gen for this K^n (or carried into it by the selection)
+  p.kappa = p.census && kappa_shape_ok(c) && c->kap_gen == c->gen && !c->stats_flat && c->stats_stage != 0 &&
+            (c->stats_waves == 0 || c->stats_waves == 4);
   p.rows_per_chunk = (i64)cdiv(p.nblk, nchunks) * p.rpb;
   p.nchunks = nchunks = (int)cdiv(p.N, p.rows_per_chunk);
   p.second_stream = p.fork_gemm || nchunks > 1;
@@ -3732,7 +3810,7 @@ static int stats_bsc_wave(evoamd_ctx *c, const StatsPlan &p, const StatsBlock &b
   DBG_SYNC(c, "bsc stats (wave)");
   TRY(rows_written(c, p, fl));  // the E_q[s] rows are written: the product may start
   if (bsc_pb.ent) {
-    pair_bins_reduce_kernel<<<bsc_pb.nb * bsc_pb.nsh, PB_RTHREADS, (size_t)3 * 2 * bsc_pb.rf * H * sizeof(double), c->stream>>>(
+    pair_bins_reduce_kernel<3><<<bsc_pb.nb * bsc_pb.nsh, PB_RTHREADS, (size_t)3 * 2 * bsc_pb.rf * H * sizeof(double), c->stream>>>(
         bsc_pb, H, 0);
     HIP_TRY(hipGetLastError());
     made_bins_clean(c);
@@ -3897,6 +3975,19 @@ static int stats_sssc_main(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep
   if (stage) lds = lds_staged;
   const int per_cu = stats_per_cu(lds + lds_static, 32 / Wv);  // 32 waves per CU
   SpanGuard g(c, KID_STATS);
+  if (p.kappa) {
+    // kappa route: rows + four accumulator columns, no B rows and no tables in LDS
+    SpanGuard gk(c, KID_STATS_KAPPA);
+    const size_t ldk = (size_t)(4 * 2 + 4) * H * sizeof(double);
+    const int per_cu_k = stats_per_cu(ldk + lds_static, 32 / 4);
+    int kgrid = (int)std::min<i64>(cdiv(nc, 4), (i64)c->n_cu * per_cu_k * 4);
+    if (pb.ent && kgrid > pb.nwg) kgrid = pb.nwg;
+    PB_GRID_CHECK(pb, kgrid);
+    sssc_stats_wave_kernel<1, 4, true, true><<<kgrid, 256, ldk, c->stream>>>(sc, o1, pb, 1, c->ovf_rec, eb.few4 ? 4 : 8);
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "sssc stats main (kappa)");
+    return 0;
+  }
   // a wave per datapoint while that is at most a few rounds of resident workgroups (a second datapoint per wave
   // doubles the kernel's critical path at small N), a persistent grid-stride loop beyond
   int sgrid = (int)std::min<i64>(cdiv(nc, Wv), (i64)c->n_cu * per_cu * 4);
@@ -4009,7 +4100,10 @@ static int stats_sssc_block(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &e
   TRY(rows_written(c, p, fl));
   if (pb.ent) {  // the entries of the main kernel and of the register-kernel levels: one tile pass per block
     SpanGuard g(c, KID_STATS);
-    pair_bins_reduce_kernel<<<pb.nb * pb.nsh, PB_RTHREADS, (size_t)3 * 2 * pb.rf * p.H * sizeof(double), c->stream>>>(pb, p.H, blk.ci > 0);
+    if (pb.planes == 4)
+      pair_bins_reduce_kernel<4><<<pb.nb * pb.nsh, PB_RTHREADS, (size_t)4 * 2 * pb.rf * p.H * sizeof(double), c->stream>>>(pb, p.H, blk.ci > 0);
+    else
+      pair_bins_reduce_kernel<3><<<pb.nb * pb.nsh, PB_RTHREADS, (size_t)3 * 2 * pb.rf * p.H * sizeof(double), c->stream>>>(pb, p.H, blk.ci > 0);
     HIP_TRY(hipGetLastError());
     made_bins_clean(c);
     DBG_SYNC(c, "pair bins reduce");
@@ -4053,9 +4147,14 @@ static int stats_finish(evoamd_ctx *c, const StatsPlan &p, const Es3cPass &ep, S
       fl.tail_done = true;
     }
     // complete data: the kernels left the column sums in CS_SLICES slices; else per-block partials of the rows
+    if (p.kappa)  // the Lam terms of the diagonal second moments, into slice 0 of the column sums the launch below adds up
+      sssc_finish_kernel<<<H, 256, 0, c->stream>>>(c->acc + a.xss, c->acc + a.xszsz, c->acc + a.xs, c->acc + a.xsz, sa.cs, CS_SLICES,
+                                                   H, c->y2sum, c->acc + a.y2, D, sa.xss_o, sa.xszsz_o, c->PT, fl.pb, TailArgs{}, 2,
+                                                   c->err, c->D1, sa.cs, sa.cs1);
     sssc_finish_kernel<<<cdiv(nthr, 256) + (fl.tail_done ? 1 : 0), 256, 0, c->stream>>>(
         c->acc + a.xss, c->acc + a.xszsz, c->acc + a.xs, c->acc + a.xsz, masked ? c->colpart : sa.cs,
-        masked ? p.nblk : CS_SLICES, H, c->y2sum, c->acc + a.y2, D, sa.xss_o, sa.xszsz_o, masked ? nullptr : c->PT, fl.pb, ta);
+        masked ? p.nblk : CS_SLICES, H, c->y2sum, c->acc + a.y2, D, sa.xss_o, sa.xszsz_o, masked ? nullptr : c->PT, fl.pb, ta,
+        p.kappa ? 1 : 0, c->err);
   }
   HIP_TRY(hipGetLastError());
   DBG_SYNC(c, "colsum + finish");
@@ -4168,6 +4267,8 @@ static int stats_sssc_pass(evoamd_ctx *c, const StatsPlan &p, Es3cPass &ep) {
   sa.xss_o = c->acc_base + c->pre_n;
   sa.xszsz_o = c->acc_base + c->pre_n + (size_t)H * H;
   if (!p.masked) sa.cs = c->acc_base + 4;  // the kernels sum the columns of [Es | Ez] and the diagonal second moments themselves
+  sa.cs1 = c->acc_base + 4 + (size_t)CS_SLICES * 3 * H;
+  if (p.kappa) sa.kap_in = c->kap;
   ep.ls = es3c_lists(c, (int)list_cap(N * (i64)c->S));
   // the final K^n is made of resident states and accepted candidates: same levels as the candidates
   levels_for(c, p.lv, ep.need);
@@ -4211,6 +4312,7 @@ static int stats_compute(evoamd_ctx *c, bool fork_gemm = false) {
   const double *Ywp = c->Y;  // EBSC: what the Wp contraction reads
   int ldwp = c->ldY;
   if (c->model == EVOAMD_MODEL_SSSC && !p.masked && stats_bins_pay(c)) fl.pb = c->pbins;
+  if (p.kappa) fl.pb.planes = 4;  // the pair states' q apart from the Lam-complete entries of the quad levels
   // ---- the blocks of datapoints
   for (int ci = 0; ci < p.nchunks; ci++) {
     const i64 n0 = (i64)ci * p.rows_per_chunk;
@@ -6042,6 +6144,7 @@ extern "C" const char *evoamd_kernel_name(int kid) {
                                          "lpj_pass",     "stats_pass",     "lpj_k3_4",     "lpj_k5_8", "lpj_k9plus",
                                          "stats_k3_4",   "stats_k5_8",     "stats_k9plus", "allreduce",    "estep_fused",
                                          "patches",      "init_states",    "posterior_sample", "seed_states",
-                                         "loglik_proposal", "loglik_lpj",  "loglik_fold",     "remap_latents"};
+                                         "loglik_proposal", "loglik_lpj",  "loglik_fold",     "remap_latents",
+                                         "stats_kappa"};
   return (kid >= 0 && kid < KID_COUNT) ? names[kid] : "?";
 }

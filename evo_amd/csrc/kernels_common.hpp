@@ -503,7 +503,11 @@ __global__ __launch_bounds__(256) void vary_kn_kernel(u64 *__restrict__ states, 
                                                       u64 *__restrict__ dig, const u64 *__restrict__ cand_dig,
                                                       int dig_dedup, int skipped_mask, int *__restrict__ err,
                                                       int *__restrict__ clist_n = nullptr, int n_clist = 0, int census_skip = 0,
-                                                      double *__restrict__ zero_ptr = nullptr, i64 zero_n = 0) {
+                                                      double *__restrict__ zero_ptr = nullptr, i64 zero_n = 0,
+                                                      double2 *__restrict__ kap = nullptr,
+                                                      const double2 *__restrict__ cand_kap = nullptr) {
+  // kap / cand_kap (ES3C, option "stats_kappa"): the kappa records the lpj passes left beside the lpj values, element
+  // n S + s / n Cmax + c like the digests; an accepted candidate's record moves with its words, lpj and digest
   __shared__ int blk_uniq[4], blk_sub[4];
   if (blockIdx.x == 0 && list_n)  // the statistics pass that follows appends to fresh overflow lists
     clear_lists_checked(list_n, n_list, skipped_mask, err);
@@ -704,6 +708,7 @@ __global__ __launch_bounds__(256) void vary_kn_kernel(u64 *__restrict__ states, 
           }
           lpj_n[wi] = new_v[wave][j];
           if (dig) dig[n * (i64)S + wi] = cand_dig[n * (i64)Cmax + bi];
+          if (kap) kap[n * (i64)S + wi] = cand_kap[n * (i64)Cmax + bi];
         }
       }
       for (int j = 0; j < g; j++) {  // the register copy of the row follows the swaps

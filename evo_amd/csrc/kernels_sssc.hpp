@@ -71,6 +71,10 @@ struct SsscArgs {
   double *lpj_out;  // element (n, col0 + c), row stride ldo
   int ldo, col0;
   unsigned *flags;  // (N)
+  // kappa records (option "stats_kappa"): {kappa_0, kappa_1} of every state with at most two active latents the table-driven
+  // main kernel evaluates, element n C + c like the digests; nullptr: not written.  STATS mode reads them (kap_in).
+  double2 *kap_out;
+  const double2 *kap_in;
   // STATS mode
   const double *lpj_in;  // (N, ldo) rows incl. permanent column
   const double *rowmax, *rowsum;
@@ -81,6 +85,7 @@ struct SsscArgs {
   // blockIdx % CS_SLICES (3 H atomics per workgroup, contention spread over the slices) and sssc_finish_kernel adds
   // the slices.  nullptr: the Ed rows + a separate column-sum pass (incomplete data).
   double *cs;
+  double *cs1;            // kappa route: CS_SLICES slices of H doubles, sum of q over the SINGLETON states of each latent
   double *xss, *xszsz;    // (H,H) zero-initialised: strict UPPER triangle sums of the states with 2 active latents
   double *xss_o, *xszsz_o;  // (H,H) zero-initialised: what the overflow kernels (> 2 active latents) add, xszsz_o both triangles
   int *err;               // [0] |= 1: k > KCAP, |= 2: singular system
@@ -754,8 +759,11 @@ __device__ __forceinline__ void append_end(const ListOut &lo, int shard, const i
 // B = Y W (LDS or global).  Identity padding makes the k = 2 expressions exact for k < 2.  ONE function for every kernel
 // that evaluates such states -- the pass over K^n, the candidate batches and the fused per-datapoint E-step
 // (kernels_fused.hpp) -- so that a state has the same lpj bits wherever it is evaluated.
-__device__ __forceinline__ double sssc_k2_value(const int k, const int idx0, const int idx1, const double4 *D1t, const double *Bn,
-                                                const PairEntry &pe, const double yyn, const double s, int *err) {
+// kap0 / kap1: kappa = Lam v / sigma2 + mu of the state (sssc.py:574-575) from the same t0 / t1 the quadratic form uses; the
+// identity padding gives kap1 = 0 for k = 1 and both zero for k = 0.  The lpj bits do not depend on whether they are used.
+__device__ __forceinline__ double sssc_k2_value_kappa(const int k, const int idx0, const int idx1, const double4 *D1t,
+                                                      const double *Bn, const PairEntry &pe, const double yyn, const double s,
+                                                      int *err, double &kap0, double &kap1) {
 #pragma clang fp contract(off)
   double4 d0 = make_double4(0.0, 0.0, 0.0, 0.0), d1 = make_double4(0.0, 0.0, 0.0, 0.0);  // mu, L1, G_hh, Lam
   double b0 = 0.0, b1 = 0.0, g01 = 0.0, L = 0.0, l00 = 0.0, l01 = 0.0, l10 = 0.0, l11 = 0.0;
@@ -785,7 +793,14 @@ __device__ __forceinline__ double sssc_k2_value(const int k, const int idx0, con
   const double rr = fma(-d1.x, b1 + v1, fma(-d0.x, b0 + v0, yyn));
   const double t0 = fma(l01, v1, l00 * v0), t1 = fma(l11, v1, l10 * v0);
   const double quad = fma(v1, t1, v0 * t0);
+  kap0 = fma(s, t0, d0.x);
+  kap1 = fma(s, t1, d1.x);
   return fma(-0.5 * s, fma(-s, quad, rr), L);
+}
+__device__ __forceinline__ double sssc_k2_value(const int k, const int idx0, const int idx1, const double4 *D1t, const double *Bn,
+                                                const PairEntry &pe, const double yyn, const double s, int *err) {
+  double kap0, kap1;
+  return sssc_k2_value_kappa(k, idx0, idx1, D1t, Bn, pe, yyn, s, err, kap0, kap1);
 }
 
 // Main lpj pass in natural order.  A workgroup owns BS consecutive (n, state) pairs, i.e. at most
@@ -902,10 +917,18 @@ __global__ __launch_bounds__(BS) void sssc_main_lpj_kernel(SsscArgs a, ListOut l
       const int k = ktot[p];
       const double *Bn = STAGEB ? Bs + (size_t)nloc[p] * a.H              // LDS
                                 : a.Bm + (n_first + nloc[p]) * (i64)a.H;  // global
-      const double val = sssc_k2_value(k, idx0[p], idx1[p], D1t, Bn, pe[p], yyn[p], s, a.err);
+      double kap0, kap1;
+      const double val = sssc_k2_value_kappa(k, idx0[p], idx1[p], D1t, Bn, pe[p], yyn[p], s, a.err, kap0, kap1);
       unsigned fl = 0;
       const i64 n = n_first + nloc[p];
       a.lpj_out[n * a.ldo + a.col0 + c[p]] = clamp_lpj(val, fl);
+      if (a.kap_out) {  // 16 coalesced bytes per state, streamed: nobody reads them before the statistics pass
+        typedef double kap_v2 __attribute__((ext_vector_type(2)));
+        kap_v2 kv;
+        kv.x = kap0;
+        kv.y = kap1;
+        __builtin_nontemporal_store(kv, (kap_v2 *)&a.kap_out[n * a.C + c[p]]);
+      }
       if (fl) {
         atomicOr(&a.flags[n], fl);
         atomicOr(&a.err[1], 1);
@@ -939,7 +962,17 @@ __global__ __launch_bounds__(BS) void sssc_main_lpj_kernel(SsscArgs a, ListOut l
 // owns such a state adds the record to its wave's LDS rows, so no kernel adds to the [Es | Ez] rows with global atomics.
 // rec_kmax = 4: the few states with 5..8 latents have no record -- the wavefront kernel adds them afterwards (atomics),
 // like the states above eight.
-template <int HWT, int W, bool CEN = false>
+// KAP (kappa route, option "stats_kappa"; census mode, four waves, digests, HWT = 1 whatever H): the lpj pass over this K^n
+// left kappa of every state with at most two active latents (a.kap_in, sssc_k2_value_kappa; the selection kernel carried
+// the records of the accepted candidates), so a state costs 32 coalesced bytes (digest, lpj, record) and NO B row, D1 or
+// pair-table gather.  The Lam terms of the second moments depend on the active set only and factor out of the sum over
+// the datapoints: the kernel leaves sum q kappa^2 (accD), sum q of the singleton states per latent (accS1 -> a.cs1) and
+// per pair state one flagged bin entry {q, q kappa_0 kappa_1}; sssc_kappa_diag_body / sssc_finish_kernel put Lam back.
+// A full bin region falls back to atomics on a.xss / a.xszsz (the pair states' upper-triangle sums, idle on the binned
+// route).  Dynamic LDS: W x 2 H doubles of rows + 4 H of accumulators.
+// (Two resident workgroups per CU like the table form: its LDS would leave room for three, but compiled for three -- 168
+// registers instead of its 222 -- the kernel spilled and took 0.64 ms instead of 0.28 at the north-star shape.)
+template <int HWT, int W, bool CEN = false, bool KAP = false>
 __global__ __launch_bounds__(64 * W, W == 4 ? 2 : 1) void sssc_stats_wave_kernel(SsscArgs a, ListOut lo, PairBins pb, int stage,
                                                                                 const OvfRec *__restrict__ rec = nullptr,
                                                                                 const int rec_kmax = 8) {
@@ -951,11 +984,12 @@ __global__ __launch_bounds__(64 * W, W == 4 ? 2 : 1) void sssc_stats_wave_kernel
   const int H = a.H, lane = lane_id(), wave = wave_id_uniform();
   double *rowS = wrows + (size_t)wave * 2 * H, *rowZ = rowS + H;
   double *accS = wrows + (size_t)W * 2 * H, *accZ = accS + H, *accD = accZ + H;
+  double *accS1 = accD + H;                                   // KAP only
   double *rowB = accD + H + (size_t)wave * H;                 // stage only
   double4 *d1s = (double4 *)(accD + H + (size_t)W * H);       // stage only (32-byte aligned: all offsets are multiples of H doubles, H even)
   const bool binned = pb.ent != nullptr;
-  for (int i = threadIdx.x; i < 3 * H; i += 64 * W) accS[i] = 0.0;
-  if (HWT > 0 || stage)
+  for (int i = threadIdx.x; i < (KAP ? 4 : 3) * H; i += 64 * W) accS[i] = 0.0;
+  if (!KAP && (HWT > 0 || stage))
     for (int i = threadIdx.x; i < H; i += 64 * W) d1s[i] = a.D1[i];
   if (binned)
     for (int i = threadIdx.x; i < pb.nb; i += 64 * W) bcnt[i] = CEN ? pb.gcnt[(size_t)i * pb.nwg + blockIdx.x] : 0;
@@ -986,19 +1020,22 @@ __global__ __launch_bounds__(64 * W, W == 4 ? 2 : 1) void sssc_stats_wave_kernel
   // unconditional (clamped addresses, the last datapoint prefetches itself again): a load under a branch makes the
   // compiler wait for vmcnt(0) at the next use of anything loaded earlier.
   constexpr bool PF = HWT > 0;
-  constexpr int HB = PF ? HWT : 1;
+  constexpr int HB = (PF && !KAP) ? HWT : 1;
   struct Pre {
     double rmax, rsum, B[HB], l[4];
     u64 d[4];
+    double2 kp[KAP ? 4 : 1];
   };
   auto issue = [&](i64 nn, Pre &p) {
     p.rmax = a.rowmax[nn];
     p.rsum = a.rowsum[nn];
-    const double *Bnn = a.Bm + nn * H;
+    if (!KAP) {
+      const double *Bnn = a.Bm + nn * H;
 #pragma unroll
-    for (int i = 0; i < HB; i++) {
-      const int h = lane + 64 * i;
-      p.B[i] = Bnn[h < H ? h : H - 1];
+      for (int i = 0; i < HB; i++) {
+        const int h = lane + 64 * i;
+        p.B[i] = Bnn[h < H ? h : H - 1];
+      }
     }
     const double *lpn = a.lpj_in + nn * a.ldo + a.col0;
     const u64 *dgn = a.dig + nn * (i64)a.C;
@@ -1007,6 +1044,7 @@ __global__ __launch_bounds__(64 * W, W == 4 ? 2 : 1) void sssc_stats_wave_kernel
       const int c = 64 * u + lane, cc = c < a.C ? c : 0;
       p.d[u] = dgn[cc];
       p.l[u] = lpn[cc];
+      if (KAP) p.kp[u] = a.kap_in[nn * (i64)a.C + cc];
     }
   };
   const i64 n_first = (i64)blockIdx.x * W + wave, n_stride = (i64)gridDim.x * W;
@@ -1020,12 +1058,14 @@ __global__ __launch_bounds__(64 * W, W == 4 ? 2 : 1) void sssc_stats_wave_kernel
     if (PF) {
       rmax = cur.rmax;
       rsum = cur.rsum + EVO_F64_TINY;
+      if (!KAP) {
 #pragma unroll
-      for (int i = 0; i < HB; i++) {
-        const int h = lane + 64 * i;
-        if (h < H) rowB[h] = cur.B[i];
+        for (int i = 0; i < HB; i++) {
+          const int h = lane + 64 * i;
+          if (h < H) rowB[h] = cur.B[i];
+        }
+        Bn = rowB;
       }
-      Bn = rowB;
     } else {
       rmax = a.rowmax[n];
       rsum = a.rowsum[n] + EVO_F64_TINY;
@@ -1049,18 +1089,21 @@ __global__ __launch_bounds__(64 * W, W == 4 ? 2 : 1) void sssc_stats_wave_kernel
       bool live[RG];
       int k[RG], idx0[RG], idx1[RG];
       double l[RG];
+      double2 kp[RG];
 #pragma unroll
       for (int u = 0; u < RG; u++) {  // phase A: the states and their lpj
         const int c = c0 + 64 * u + lane;
         live[u] = c < a.C;
         k[u] = idx0[u] = idx1[u] = 0;
         l[u] = 0.0;
+        kp[u] = make_double2(0.0, 0.0);
         if (first) {
           const u64 d = cur.d[u];
           k[u] = live[u] ? dig_k(d) : 0;
           idx0[u] = dig_idx(d, 0);
           idx1[u] = dig_idx(d, 1);
           l[u] = cur.l[u];
+          if (KAP) kp[u] = cur.kp[u];
         } else {
           if (a.dig) {
             const u64 d = a.dig[n * (i64)a.C + (live[u] ? c : 0)];
@@ -1071,6 +1114,7 @@ __global__ __launch_bounds__(64 * W, W == 4 ? 2 : 1) void sssc_stats_wave_kernel
             load_state_k2<0>(a.states + (n * (i64)a.C + c) * a.HW, a.HW, k[u], idx0[u], idx1[u]);
           }
           l[u] = lp[live[u] ? c : 0];
+          if (KAP) kp[u] = a.kap_in[n * (i64)a.C + (live[u] ? c : 0)];
         }
       }
       // states with more than two active latents: to the overflow list.  A few of them (the usual case) wait in
@@ -1113,7 +1157,7 @@ __global__ __launch_bounds__(64 * W, W == 4 ? 2 : 1) void sssc_stats_wave_kernel
       for (int u = 0; u < RG; u++) {
         act[u] = live[u] && !over[u] && k[u] > 0;
         pair[u] = act[u] && k[u] == 2;
-        pe[u] = a.PT[pair[u] ? (i64)idx0[u] * H + idx1[u] : 0];
+        if (!KAP) pe[u] = a.PT[pair[u] ? (i64)idx0[u] * H + idx1[u] : 0];
       }
       if (CEN) {
         const OvfRec *rp = rec + (size_t)(n * a.C) + (ofirst >= 0 ? c0 + 64 * ofirst + lane : 0);
@@ -1139,7 +1183,29 @@ __global__ __launch_bounds__(64 * W, W == 4 ? 2 : 1) void sssc_stats_wave_kernel
 #pragma unroll
       for (int u = 0; u < RG; u++) {
         const double q = act[u] ? exp(l[u] + (0.0 - rmax)) : 0.0;
-        if (q != 0.0) {
+        if (KAP) {
+          // no table, no B row: kappa came with the state; the Lam terms are added per active set by the finish kernels
+          if (q != 0.0) {
+            const double qn = q / rsum;
+            const double k0 = kp[u].x, k1 = kp[u].y;
+            unsafeAtomicAdd(&rowS[idx0[u]], qn);
+            unsafeAtomicAdd(&rowZ[idx0[u]], qn * k0);
+            unsafeAtomicAdd(&accD[idx0[u]], qn * (k0 * k0));
+            if (pair[u]) {
+              unsafeAtomicAdd(&rowS[idx1[u]], qn);
+              unsafeAtomicAdd(&rowZ[idx1[u]], qn * k1);
+              unsafeAtomicAdd(&accD[idx1[u]], qn * (k1 * k1));
+              const double pv = qn * (k0 * k1);
+              if (!binned || !pb_append(pb, bcnt, blockIdx.x, H, idx0[u], idx1[u], qn, pv, 0.0, true)) {
+                const i64 o01 = (i64)idx0[u] * H + idx1[u];
+                unsafeAtomicAdd(&a.xss[o01], qn);
+                unsafeAtomicAdd(&a.xszsz[o01], pv);
+              }
+            } else {
+              unsafeAtomicAdd(&accS1[idx0[u]], qn);
+            }
+          }
+        } else if (q != 0.0) {
           const double qn = q / rsum;
           const double4 d0 = D1t[idx0[u]];  // mu, L1, G_hh, Lam
           const double b0 = Bn[idx0[u]];
@@ -1268,6 +1334,7 @@ __global__ __launch_bounds__(64 * W, W == 4 ? 2 : 1) void sssc_stats_wave_kernel
       unsafeAtomicAdd(&sl[H + h], accZ[h]);
     }
     if (accD[h] != 0.0) unsafeAtomicAdd(&sl[2 * H + h], accD[h]);
+    if (KAP && accS1[h] != 0.0) unsafeAtomicAdd(&a.cs1[(size_t)(blockIdx.x % CS_SLICES) * H + h], accS1[h]);
   }
   if (binned)
     for (int i = threadIdx.x; i < pb.nb; i += 64 * W) {
@@ -1896,6 +1963,43 @@ __global__ __launch_bounds__(64) void sssc_big_kernel(SsscArgs a, ListIn li, Lis
   }
 }
 
+// Kappa route, first of the two launches of sssc_finish_kernel (kappa = 2): the Lam terms of the DIAGONAL second moments.  With P(i,j) the sum of q over
+// the pair states {i, j} (fourth plane of the pair bins + the fallback atomics in xss) and P1(i) the sum of q over the
+// singleton states {i} (cs1):   xpt_szsz[i][i] += Lam_1(i) P1(i) + sum_{j > i} Lam_00(i,j) P(i,j) + sum_{j < i} Lam_11(j,i) P(j,i)
+// -- added to slice 0 of the diagonal column sums, which the second launch adds up.  One workgroup per latent.
+__device__ __forceinline__ void sssc_kappa_diag_body(const double *__restrict__ xss, double *__restrict__ cs,
+                                                     const double *__restrict__ cs1, int H,
+                                                     const double4 *__restrict__ D1,
+                                                     const PairEntry *__restrict__ PT, const PairBins &pb) {
+  __shared__ double red[256];
+  const int i = blockIdx.x;
+  double acc = 0.0;
+  for (int j = threadIdx.x; j < H; j += 256) {
+    if (j == i) continue;
+    const int lo = i < j ? i : j, hi = i < j ? j : i;
+    const i64 t = (i64)lo * H + hi;
+    double P = xss[t];
+    if (pb.part && pb.planes == 4) P += pb_collect_pair_q(pb, H, lo, hi);
+    if (P != 0.0) {
+      const PairEntry pe = PT[t];
+      acc += (i < j ? pe.l00 : pe.l11) * P;
+    }
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    double p1 = 0.0;
+    for (int sl = 0; sl < CS_SLICES; sl++) p1 += cs1[(size_t)sl * H + i];
+    double add = red[0];
+    if (p1 != 0.0) add += D1[i].w * p1;
+    cs[2 * H + i] += add;
+  }
+}
+
 // Finishes the ES3C accumulator after the scatter kernels, one launch (was 7): thread (i,j) of the
 // H x H grid mirrors xpt_ss; the diagonal threads add the per-workgroup partial column sums of
 // [Es | Ez | Ed] (colsum_partial_kernel, nblk partials of 3H columns, fixed order) and write
@@ -1907,7 +2011,15 @@ __global__ __launch_bounds__(256) void sssc_finish_kernel(double *__restrict__ x
                                                           int D, const double *__restrict__ xss_o,
                                                           const double *__restrict__ xszsz_o,
                                                           const PairEntry *__restrict__ PT, PairBins pb,
-                                                          TailArgs ta = TailArgs{}) {
+                                                          TailArgs ta = TailArgs{}, int kappa = 0,
+                                                          int *__restrict__ err = nullptr,
+                                                          const double4 *__restrict__ D1 = nullptr,
+                                                          double *__restrict__ cs = nullptr,
+                                                          const double *__restrict__ cs1 = nullptr) {
+  if (kappa == 2) {  // kappa route, the launch in front (H workgroups): the Lam terms of the diagonal, nothing else
+    sssc_kappa_diag_body(xss, cs, cs1, H, D1, PT, pb);
+    return;
+  }
   if (ta.tail && blockIdx.x == gridDim.x - 1) {  // the accumulator tail rides along as one extra workgroup (was a launch)
     tail_body(ta);
     return;
@@ -1937,12 +2049,25 @@ __global__ __launch_bounds__(256) void sssc_finish_kernel(double *__restrict__ x
       const PairEntry pe = PT[t];
       lower = u + (pe.l10 - pe.l01) * uss;
     }
-    double bq = 0.0, bu = 0.0, bl = 0.0;
-    if (pb.part) pb_collect(pb, H, i, j, bq, bu, bl);  // what went through the pair bins in this pass
-    const double ss = uss + xss_o[t] + bq;
+    double bq = 0.0, bu = 0.0, bl = 0.0, bp = 0.0;
+    if (pb.part) pb_collect(pb, H, i, j, bq, bu, bl, bp);  // what went through the pair bins in this pass
+    double upper = u;
+    if (kappa) {
+      // kappa route: the pair states left q (bp, uss) and q kappa_0 kappa_1 (in bu = bl, u): Lam_01 / Lam_10 of the pair
+      // times the sum of q goes back in here (the diagonal terms: sssc_kappa_diag_body)
+      const double P = uss + bp;
+      lower = u;
+      if (P != 0.0) {
+        const PairEntry pe = PT[t];
+        if (pair_singular_lam(pe.l00)) atomicOr(err, 2);
+        upper = u + pe.l01 * P;
+        lower = u + pe.l10 * P;
+      }
+    }
+    const double ss = uss + xss_o[t] + bq + bp;
     xss[t] = ss;
     xss[tl] = ss;
-    xszsz[t] = u + xszsz_o[t] + bu;
+    xszsz[t] = upper + xszsz_o[t] + bu;
     xszsz[tl] = lower + xszsz_o[tl] + bl;
   }
 }

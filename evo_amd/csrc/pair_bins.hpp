@@ -13,7 +13,7 @@
 // bin in an LDS tile and adds the tile to the matrices once.  Rows are folded (i with H-2-i: H partners per folded row) so that the
 // bins of the upper triangle fill evenly.  A bin region that is full falls back to the direct atomics.
 // ---------------------------------------------------------------------------------------
-#define PB_TILE 4096  // pair slots per LDS tile (x 3 values x 8 bytes = 96 KiB)
+#define PB_TILE 4096  // pair slots per LDS tile (x 3 values x 8 bytes = 96 KiB; four planes on the ES3C kappa route: 128 KiB)
 #define PB_MAX_BINS 256
 #define PB_NSH_MAX 16  // reduce workgroups per bin: pb.nsh <= this.  8 at large H (bins fill unevenly -- a few popular
                        // latents --: more, smaller workgroups per bin let the scheduler even it out: 146 -> 116 us at c4; 16:
@@ -25,23 +25,28 @@ struct PairBins {
   // key = (tile row << 16) | j in the low bits of the fourth double
   double4 *ent;
   int *gcnt;       // nb x nwg: entries each producer workgroup left in each bin (the reduce kernel zeroes them)
-  double *part;    // nb x nsh reduced tiles of 3 planes x (2 rf H) slots, summed by sssc_finish_kernel
+  double *part;    // nb x nsh reduced tiles of `planes` planes x (2 rf H) slots, summed by sssc_finish_kernel
   int cap, nb, rf, nwg;  // rf folded rows per bin: the tile holds 2 rf rows x H columns; nwg producer workgroups
   int nsh;               // reduce workgroups per bin (4: small shards, 8: from 8 M resident states on; up to 256 / nb)
+  int planes;            // planes of a reduced tile: 3 {q, upper, lower}; 4 (ES3C kappa route): + q of the pair-state entries
 };
 __device__ __forceinline__ int pb_fold(int i, int H) { return i < H - 2 - i ? i : H - 2 - i; }
 
 // One entry for element (i, j), i < j, into the private region of workgroup `wg`; false: the region is full (the
 // caller adds the three values with global atomics instead).  `bcnt`: the workgroup's LDS counters, one per bin.
+// `pair_state`: the entry of a state with exactly two active latents on the kappa route (ES3C, option "stats_kappa"):
+// {q, q kappa_0 kappa_1, unused}, WITHOUT the Lam terms -- bit 32 of the key marks it, the reduce kernel keeps its q in a
+// plane of its own and sssc_finish_kernel multiplies the pair's Lam back in.
 __device__ __forceinline__ bool pb_append(const PairBins &pb, int *bcnt, int wg, int H, int i, int j, double q,
-                                          double vu, double vl) {
+                                          double vu, double vl, bool pair_state = false) {
   const int f = pb_fold(i, H);
   const int bin = f / pb.rf;
   const int pos = atomicAdd(&bcnt[bin], 1);  // LDS: the workgroup's running count for this bin
   if (pos >= pb.cap) return false;
   const int r = 2 * (f - bin * pb.rf) + (i != f ? 1 : 0);
   const size_t at = ((size_t)bin * pb.nwg + wg) * pb.cap + pos;
-  pb.ent[at] = make_double4(q, vu, vl, __longlong_as_double((long long)(((unsigned)r << 16) | (unsigned)j)));
+  const unsigned long long key = (pair_state ? 1ull << 32 : 0ull) | (((unsigned)r << 16) | (unsigned)j);
+  pb.ent[at] = make_double4(q, vu, vl, __longlong_as_double((long long)key));
   return true;
 }
 
@@ -49,6 +54,9 @@ __device__ __forceinline__ bool pb_append(const PairBins &pb, int *bcnt, int wg,
 // <- their entries (ds_add_f64), then the whole tile with plain stores to its own slab of pb.part (accumulate != 0:
 // added to what an earlier block of datapoints left there).  sssc_finish_kernel adds the nsh slabs of a bin in a
 // fixed order: no global atomic anywhere on this route.  One wave per region at a time.  2 rf H <= PB_TILE.
+// NP = 4 (pb.planes, ES3C kappa route): a pair-state entry {q, k, -} adds q to the fourth plane P and k to BOTH the upper
+// and the lower plane; every other entry {q, u, l} goes to the first three as with NP = 3.
+template <int NP>
 __global__ __launch_bounds__(PB_RTHREADS) void pair_bins_reduce_kernel(PairBins pb, int H, int accumulate) {
   extern __shared__ double pb_tile[];
   constexpr int NW = PB_RTHREADS / 64;
@@ -56,8 +64,8 @@ __global__ __launch_bounds__(PB_RTHREADS) void pair_bins_reduce_kernel(PairBins 
   const int NSH = pb.nsh;
   const int bin = blockIdx.x / NSH, sh = blockIdx.x - bin * NSH;
   const int slots = 2 * pb.rf * H;
-  double *tq = pb_tile, *tu = pb_tile + slots, *tl = pb_tile + 2 * slots;
-  for (int i = threadIdx.x; i < 3 * slots; i += PB_RTHREADS) pb_tile[i] = 0.0;
+  double *tq = pb_tile, *tu = pb_tile + slots, *tl = pb_tile + 2 * slots, *tp = pb_tile + (NP - 1) * slots;
+  for (int i = threadIdx.x; i < NP * slots; i += PB_RTHREADS) pb_tile[i] = 0.0;
   lds_barrier();
   const int lane = lane_id(), wave = wave_id_uniform();
   // A wave serves the regions w = sh + NSH (wave + NW j), j = 0, 1, ...: 64 of them at a time.  Their counts are
@@ -106,32 +114,57 @@ __global__ __launch_bounds__(PB_RTHREADS) void pair_bins_reduce_kernel(PairBins 
 #pragma unroll
       for (int u = 0; u < 4; u++)
         if (on[u]) {
-          const unsigned k = (unsigned)__double_as_longlong(v[u].w);
+          const unsigned long long key = (unsigned long long)__double_as_longlong(v[u].w);
+          const unsigned k = (unsigned)key;
           const int t = (int)(k >> 16) * H + (int)(k & 0xFFFFu);
-          unsafeAtomicAdd(&tq[t], v[u].x);
-          unsafeAtomicAdd(&tu[t], v[u].y);
-          unsafeAtomicAdd(&tl[t], v[u].z);
+          if (NP == 4 && (key >> 32) != 0ull) {  // pair-state entry
+            unsafeAtomicAdd(&tp[t], v[u].x);
+            unsafeAtomicAdd(&tu[t], v[u].y);
+            unsafeAtomicAdd(&tl[t], v[u].y);
+          } else {
+            unsafeAtomicAdd(&tq[t], v[u].x);
+            unsafeAtomicAdd(&tu[t], v[u].y);
+            unsafeAtomicAdd(&tl[t], v[u].z);
+          }
         }
     }
     lds_wave_fence();
   }
   lds_barrier();
-  double *out = pb.part + (size_t)blockIdx.x * 3 * slots;
-  for (int i = threadIdx.x; i < 3 * slots; i += PB_RTHREADS) out[i] = accumulate ? out[i] + pb_tile[i] : pb_tile[i];
+  double *out = pb.part + (size_t)blockIdx.x * NP * slots;
+  for (int i = threadIdx.x; i < NP * slots; i += PB_RTHREADS) out[i] = accumulate ? out[i] + pb_tile[i] : pb_tile[i];
 }
 
-// What the pair bins hold for element t = (i, j), i < j: {sum q, sum for (i, j), sum for (j, i)}.
-__device__ __forceinline__ void pb_collect(const PairBins &pb, int H, int i, int j, double &bq, double &bu, double &bl) {
+// What the pair bins hold for element t = (i, j), i < j: {sum q, sum for (i, j), sum for (j, i)} and, where the tiles have
+// a fourth plane, the sum of q over the pair-state entries (bp; else 0).
+__device__ __forceinline__ void pb_collect(const PairBins &pb, int H, int i, int j, double &bq, double &bu, double &bl,
+                                           double &bp) {
   const int f = pb_fold(i, H), bin = f / pb.rf;
   const int slots = 2 * pb.rf * H;
   const int slot = (2 * (f - bin * pb.rf) + (i != f ? 1 : 0)) * H + j;
-  const double *p = pb.part + (size_t)bin * pb.nsh * 3 * slots + slot;
-  bq = bu = bl = 0.0;
-  for (int sh = 0; sh < pb.nsh; sh++, p += 3 * slots) {
+  const int np = pb.planes == 4 ? 4 : 3;
+  const double *p = pb.part + (size_t)bin * pb.nsh * np * slots + slot;
+  bq = bu = bl = bp = 0.0;
+  for (int sh = 0; sh < pb.nsh; sh++, p += (size_t)np * slots) {
     bq += p[0];
     bu += p[slots];
     bl += p[2 * slots];
+    if (np == 4) bp += p[3 * slots];
   }
+}
+__device__ __forceinline__ void pb_collect(const PairBins &pb, int H, int i, int j, double &bq, double &bu, double &bl) {
+  double bp;
+  pb_collect(pb, H, i, j, bq, bu, bl, bp);
+}
+// ... the fourth plane alone (pb.planes == 4)
+__device__ __forceinline__ double pb_collect_pair_q(const PairBins &pb, int H, int i, int j) {
+  const int f = pb_fold(i, H), bin = f / pb.rf;
+  const int slots = 2 * pb.rf * H;
+  const int slot = (2 * (f - bin * pb.rf) + (i != f ? 1 : 0)) * H + j;
+  const double *p = pb.part + (size_t)bin * pb.nsh * 4 * slots + 3 * (size_t)slots + slot;
+  double bp = 0.0;
+  for (int sh = 0; sh < pb.nsh; sh++, p += (size_t)4 * slots) bp += p[0];
+  return bp;
 }
 
 

@@ -175,6 +175,16 @@ int evoamd_debug_validity(evoamd_ctx *ctx, int64_t out[8]);
  * "stats_flat" (0/1, default 0: measured a few per cent at N = 100k, a loss at N / 8): with census lists, the ES3C statistics of the states with at most two active latents run
  * on the thread-per-state kernel (1024-thread workgroups owning floor(1024 / S) datapoints per round, 16 waves per CU);
  * 0: the wave-per-datapoint kernel.
+ * "stats_kappa" (0/1/2, default 1 = from "stats_kappa_min" x 1024 resident states on, 2 = wherever the shape allows it; the
+ * record buffers are allocated by evoamd_configure where the setting asks for the route): ES3C with census lists,
+ * digests, complete data, f64 and even H -- the table-driven lpj kernels leave {kappa_0, kappa_1} of every state with at
+ * most two active latents beside its lpj (16 bytes per state), evoamd_vary_kn moves an accepted candidate's record with
+ * it, and the statistics pass reads the records instead of the B rows and the state-term tables; the Lam terms of the
+ * second moments are added once per active set by the finish kernels.  The records count only while they were written
+ * under the current Theta for the current K^n (any other change of either drops them and the pass takes the table route
+ * unchanged); 0: never written, never read.  EVOAMD_K_STATS_KAPPA counts the passes that took the route.
+ * "stats_kappa_min" (default 16384): the automatic setting of "stats_kappa" takes the route from this many x 1024 resident
+ * states (N x S) on -- measured on MI355X: 20 M states gain 0.07 ms per EM iteration, 10 M are even, 2.5 M and 0.64 M lose ~0.01.
  * "theta_copy_engine" (0/1, default 0; measured without gain): evoamd_mstep_device downloads Theta^new with asynchronous copies on a third
  * stream (copy engine) beside the kernels queued behind the update; 0: the mailbox kernel writes Theta into the pinned
  * host buffer itself, in front of them.
@@ -782,7 +792,8 @@ enum {
   EVOAMD_K_LOGLIK_LPJ = 26,    /* ... the lpj launches over a pass's outside draws (every level)                          */
   EVOAMD_K_LOGLIK_FOLD = 27,   /* ... the fold kernel of a pass; the bound + all-zero terms and the finish (one span each) */
   EVOAMD_K_REMAP = 28,         /* evoamd_remap_latents: the remap kernel (index upload and downloads excluded) */
-  EVOAMD_K_COUNT = 29
+  EVOAMD_K_STATS_KAPPA = 29,   /* the ES3C statistics kernel on the kappa route (option "stats_kappa"), nested in EVOAMD_K_STATS */
+  EVOAMD_K_COUNT = 30
 };
 /* on = bit mask of kernel classes to time (bit k = class k; -1 = all, 0 = off).  Each timed span
  * records two HIP events on the compute stream, which costs about 10 us of stream time per span:
