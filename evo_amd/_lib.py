@@ -50,7 +50,7 @@ KERNEL_IDS = {
 # classes outside the EM path, added after tests/test_gpu_validity.py recorded its launch census over KERNEL_IDS (which
 # therefore stays as it is); Engine.timing / Engine.kernel_time_ms take names of either table
 KERNEL_IDS_EXTRA = {"posterior_sample": 23, "seed_states": 24, "loglik_proposal": 25, "loglik_lpj": 26, "loglik_fold": 27,
-                    "remap_latents": 28, "stats_kappa": 29}
+                    "remap_latents": 28, "stats_kappa": 29, "sweep": 30}
 
 
 def kernel_id(name):
@@ -100,6 +100,8 @@ SIGNATURES = {
     "evoamd_download_candidates": (_I, [_vp, _c_u8p, _c_i32p, _c_dp]),
     "evoamd_refine_states": (_I, [_vp, _I, _I, _I, _I, _I, _I, _U64, _U64, _DBL, _DBL, _I, _I, _I, _DBL, _c_dp,
                                   ctypes.POINTER(_I)]),
+    "evoamd_sweep_propose": (_I, [_vp, _I, _I, _c_dp, _c_i32p, _c_dp, _c_i32p]),
+    "evoamd_sweep_states": (_I, [_vp, _I, _I, _I, _I, _I, _c_dp, ctypes.POINTER(_I), _c_i32p, _c_dp, _c_i32p]),
     "evoamd_posterior_scores": (_I, [_vp, _c_dp, _c_dp, _c_i32p, _c_i32p, _c_dp]),
     "evoamd_remap_latents": (_I, [_vp, _c_i32p, _I, _c_i32p, ctypes.POINTER(_I64)]),
     "evoamd_adopt_remapped_states": (_I, [_vp]),

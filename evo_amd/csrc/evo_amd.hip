@@ -36,6 +36,7 @@
 #include "kernels_refine.hpp"
 #include "kernels_loglik_estimate.hpp"
 #include "kernels_remap.hpp"
+#include "kernels_sweep.hpp"
 
 // ---------------------------------------------------------------------------------------
 // error handling
@@ -163,6 +164,7 @@ enum {  // internal kernel ids (see evoamd_kernel_name)
   KID_REMAP,         // evoamd_remap_latents: the remap kernel (index upload and downloads excluded)
   KID_STATS_KAPPA,   // the ES3C statistics kernel on the kappa route (option "stats_kappa"), nested in KID_STATS: its launch count
                      // says which route a pass took
+  KID_SWEEP,         // evoamd_sweep_propose / evoamd_sweep_states: the proposal kernel (ES3C: with the transpose of GP)
   KID_COUNT
 };
 
@@ -574,6 +576,10 @@ struct evoamd_ctx {
   // evoamd_refine_states: one row {Fs, new unique, swapped} per iteration; evoamd_posterior_scores: its (N) outputs.  Grown on
   // demand, rewritten by every call, read by nothing else
   DevBuf<double> refine_trace, score_buf;
+  // evoamd_sweep_propose / evoamd_sweep_states: the scores of the emitted rows (N, Cmax) and the gains (N); best_flip and
+  // n_capped (N each).  Grown on demand.
+  DevBuf<double> sweep_d;
+  DevBuf<int> sweep_i;
   // evoamd_remap_latents: K^n in the new latent numbering and its digests, [index (H_new) | n_replaced (N)] and the sum;
   // grown on demand, NOT sized by the geometry: they survive the configure between the remap and
   // evoamd_adopt_remapped_states, which swaps them in and releases them.  remap_H = 0: nothing to adopt.
@@ -923,6 +929,8 @@ static int set_kernel_lds_limits() {
   HIP_TRY(hipFuncSetAttribute((const void *)seed_states_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   HIP_TRY(hipFuncSetAttribute((const void *)seed_states_masked_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   HIP_TRY(hipFuncSetAttribute((const void *)seed_states_masked_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  HIP_TRY(hipFuncSetAttribute((const void *)sweep_neighbours_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  HIP_TRY(hipFuncSetAttribute((const void *)sweep_neighbours_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   {
     const void *wk[] = {(const void *)sssc_stats_wave_kernel<0, 4>,  (const void *)sssc_stats_wave_kernel<1, 4>,
                         (const void *)sssc_stats_wave_kernel<2, 4>,  (const void *)sssc_stats_wave_kernel<4, 4>,
@@ -5622,6 +5630,152 @@ extern "C" int evoamd_seed_states(evoamd_ctx *c, int max_active, int32_t *path_o
   return evoamd_seed_states_ex(c, max_active, 0u, path_out, lpj_out);
 }
 
+// ---------------------------------------------------------------------------------------
+// Local search on K^n: the one-flip neighbours of its best states (kernels_sweep.hpp has the law).  A sweep is the proposal
+// kernel into the resident candidate batch, the model's own lpj of the emitted rows and the selection; the lpj rows of K^n
+// stay what a pass over it would give.  Complete data only.  Every refusal comes before the first write.
+// ---------------------------------------------------------------------------------------
+struct SweepPlan {
+  int W = 4;
+  size_t wave_bytes = 0;
+  unsigned grid = 1;
+};
+
+static int sweep_check(const evoamd_ctx *c, int n_parents, int n_keep, SweepPlan &p) {
+  REQUIRE(c && c->configured, "configure first");
+  REQUIRE(c->have_params, "sweep: no Theta installed (set parameters first)");
+  REQUIRE(c->have_data, "sweep: no data (upload data first)");
+  REQUIRE_KN(c);
+  REQUIRE(!c->mask_infr, "sweep: incomplete data (masks present) is not supported");
+  REQUIRE(!c->bg_unit, "sweep: option background_unit is not supported");
+  REQUIRE(!c->f32, "sweep is not available in the float32 mode (ebsc_f32)");
+  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
+  REQUIRE(sssc || !c->bsc_direct, "sweep: bsc_direct keeps no G = W^T W, which the scores need");
+  if (n_parents < 1 || n_parents > c->S || n_parents > SWEEP_MAX_P)
+    return fail(EVOAMD_E_INVALID, "sweep: n_parents = %d must be in [1, min(S = %d, %d)]", n_parents, c->S, SWEEP_MAX_P);
+  REQUIRE(n_keep >= 1, "sweep: n_keep must be positive");
+  if ((i64)n_parents * n_keep > c->Cmax)
+    return fail(EVOAMD_E_INVALID, "sweep: n_parents * n_keep = %lld exceeds the configured Cmax = %d", (long long)n_parents * n_keep,
+                c->Cmax);
+  const int Hp = (int)cdiv(c->H, 64) * 64;
+  p.wave_bytes = sweep_wave_bytes(sssc, Hp, c->HW, n_keep);
+  REQUIRE(p.wave_bytes <= 150 * 1024, "sweep: the keys of one datapoint (8 or 16 H bytes) do not fit one wavefront's share of LDS");
+  p.W = 4;
+  while (p.W > 1 && p.W * p.wave_bytes > 150 * 1024) p.W >>= 1;
+  p.grid = (unsigned)std::min<i64>(cdiv(c->N, p.W), (i64)c->n_cu * 64);
+  return 0;
+}
+
+// the buffers a sweep needs, B = Y W, (ES3C) the transpose of GP: once per call, Theta stays fixed
+static int sweep_prepare(evoamd_ctx *c) {
+  const size_t N = (size_t)c->N;
+  TRY(ensure_B(c));
+  TRY(c->sweep_d.ensure(c, N * c->Cmax + N));
+  TRY(c->sweep_i.ensure(c, 2 * N));
+  if (c->model == EVOAMD_MODEL_SSSC) {
+    TRY(ensure_lists(c, c->N * (i64)c->Cmax));
+    TRY(c->seed_gpt.ensure(c, (size_t)c->H * c->H));
+    SpanGuard g(c, KID_SWEEP);
+    seed_transpose_gp_kernel<<<cdiv((i64)c->H * c->H, 256), 256, 0, c->stream>>>(c->GP, c->H, c->seed_gpt);
+    HIP_TRY(hipGetLastError());
+  }
+  return 0;
+}
+
+// ---- one sweep's proposals: the kernel, then the lpj of the emitted rows ("nothing known" level hints)
+static int sweep_propose_stage(evoamd_ctx *c, const SweepPlan &p, int n_parents, int n_keep, bool want_score) {
+  const size_t N = (size_t)c->N;
+  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
+  SweepArgs a = {};
+  a.sd.states = c->states;
+  a.sd.Bm = c->Bm, a.sd.yy = c->yy;
+  a.sd.G = c->G, a.sd.Gd = c->diag;
+  a.sd.GP = c->GP, a.sd.GPt = c->seed_gpt;
+  a.sd.mus = c->mus, a.sd.pil_bar = c->pilbar_v;
+  a.sd.dpar = c->dpar, a.sd.err = c->err;
+  a.sd.N = c->N;
+  a.sd.S = c->S, a.sd.H = c->H, a.sd.HW = c->HW, a.sd.Hp = (int)cdiv(c->H, 64) * 64, a.sd.Q = n_keep;
+  a.lpj = c->lpj;
+  a.cand = c->cand, a.cand_dig = (c->use_digest && c->cand_dig) ? c->cand_dig.get() : nullptr, a.counts = c->cand_counts;
+  a.score = want_score ? c->sweep_d.get() : nullptr;
+  a.gain = c->sweep_d + N * c->Cmax;
+  a.best_flip = c->sweep_i, a.n_capped = c->sweep_i + N;
+  a.L = c->L, a.S_perm = c->S_perm, a.P = n_parents, a.q = n_keep, a.Cmax = c->Cmax;
+  {
+    SpanGuard g(c, KID_SWEEP);
+    if (want_score) HIP_TRY(hipMemsetAsync(c->sweep_d, 0xFF, N * c->Cmax * sizeof(double), c->stream));  // rows not emitted: NaN
+    if (sssc)
+      sweep_neighbours_kernel<true><<<p.grid, 64 * p.W, p.W * p.wave_bytes, c->stream>>>(a);
+    else
+      sweep_neighbours_kernel<false><<<p.grid, 64 * p.W, p.W * p.wave_bytes, c->stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "sweep proposals");
+  }
+  on_cand_installed(c, /*near_parents=*/false);
+  TRY(eval_candidates(c));
+  made_cand_lpj(c);
+  return 0;
+}
+
+static int sweep_fetch(evoamd_ctx *c, double *score_out, int32_t *best_flip_out, double *gain_out, int32_t *n_capped_out) {
+  const size_t N = (size_t)c->N;
+  if (score_out) HIP_TRY(hipMemcpyAsync(score_out, c->sweep_d, N * c->Cmax * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (gain_out) HIP_TRY(hipMemcpyAsync(gain_out, c->sweep_d + N * c->Cmax, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (best_flip_out) HIP_TRY(hipMemcpyAsync(best_flip_out, c->sweep_i, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (n_capped_out) HIP_TRY(hipMemcpyAsync(n_capped_out, c->sweep_i + N, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (c->model == EVOAMD_MODEL_SSSC) return check_err(c);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+extern "C" int evoamd_sweep_propose(evoamd_ctx *c, int n_parents, int n_keep, double *score_out, int32_t *best_flip_out,
+                                    double *gain_out, int32_t *n_capped_out) {
+  SweepPlan p;
+  TRY(sweep_check(c, n_parents, n_keep, p));
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(sweep_prepare(c));
+  on_estep_route(c, /*fused=*/false);
+  TRY(estep_resident_pass(c));
+  TRY(sweep_propose_stage(c, p, n_parents, n_keep, score_out != nullptr));
+  return sweep_fetch(c, score_out, best_flip_out, gain_out, n_capped_out);
+}
+
+extern "C" int evoamd_sweep_states(evoamd_ctx *c, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
+                                   double *trace_out, int *n_done_out, int32_t *best_flip_out, double *gain_out,
+                                   int32_t *n_capped_out) {
+  SweepPlan p;
+  TRY(sweep_check(c, n_parents, n_keep, p));
+  TRY(estep_check_mprime(c, Mprime));
+  REQUIRE(n_sweeps >= 1, "evoamd_sweep_states: n_sweeps must be positive");
+  REQUIRE(trace_out && n_done_out, "evoamd_sweep_states: trace_out / n_done_out is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(sweep_prepare(c));
+  TRY(c->refine_trace.ensure(c, (size_t)3 * n_sweeps));
+  on_estep_route(c, /*fused=*/false);
+  TRY(estep_resident_pass(c));  // after it the selection kernel keeps the rows current (evoamd_refine_states)
+  TRY(refine_trace(c, -1, REFINE_TRACE_ZERO));
+  int done = 0, copied = 0;
+  while (done < n_sweeps) {
+    TRY(sweep_propose_stage(c, p, n_parents, n_keep, false));
+    TRY(estep_select(c, Mprime, nullptr));
+    TRY(refine_trace(c, done, REFINE_TRACE_ROW));
+    done++;
+    if (stop_when_quiet) {  // the row of this sweep: the one wait of the loop
+      HIP_TRY(hipMemcpyAsync(trace_out + 3 * copied, c->refine_trace + 3 * copied, 3 * sizeof(double), hipMemcpyDeviceToHost,
+                             c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      copied = done;
+      if (trace_out[3 * (done - 1) + 2] <= 0.0) break;
+    }
+  }
+  TRY(refine_trace(c, done - 1, REFINE_TRACE_RESTORE));
+  if (copied < done)
+    HIP_TRY(hipMemcpyAsync(trace_out + 3 * copied, c->refine_trace + 3 * copied, (size_t)3 * (done - copied) * sizeof(double),
+                           hipMemcpyDeviceToHost, c->stream));
+  *n_done_out = done;
+  return sweep_fetch(c, nullptr, best_flip_out, gain_out, n_capped_out);
+}
+
 // posterior samples (kernels_posterior_sample.hpp): own buffers; of the EM state only B = Y W is (re)formed, like every lpj pass
 // ---------------------------------------------------------------------------------------
 template <bool SSSC>
@@ -6145,6 +6299,6 @@ extern "C" const char *evoamd_kernel_name(int kid) {
                                          "stats_k3_4",   "stats_k5_8",     "stats_k9plus", "allreduce",    "estep_fused",
                                          "patches",      "init_states",    "posterior_sample", "seed_states",
                                          "loglik_proposal", "loglik_lpj",  "loglik_fold",     "remap_latents",
-                                         "stats_kappa"};
+                                         "stats_kappa",  "sweep"};
   return (kid >= 0 && kid < KID_COUNT) ? names[kid] : "?";
 }

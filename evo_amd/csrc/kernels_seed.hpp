@@ -106,6 +106,61 @@ struct SeedShared {
   double *muA, *bA, *vA;   // mu_A, B_nA, v_A = B_nA - G_A mu_A
 };
 
+// The elimination every ES3C score ends in (seed_score_sssc; kernels_sweep.hpp): t = [T | Psi_A v] of a K x K system, v, the
+// state's sum of pil_bar and rr; returns its lpj, -inf when det T is not positive.
+template <int K>
+__device__ __forceinline__ double seed_eliminate(double (&t)[K][K + 1], const double (&v)[K], double pb, double rr, double s2inv) {
+  // LU with partial pivoting (first max |pivot|); rows swap by selects, so nothing is indexed at run time
+  LogDetAcc ld;
+  bool neg = false, zero = false;
+  double rpiv[K];
+#pragma unroll
+  for (int c = 0; c < K; c++) {
+    int r = c;
+    double best = fabs(t[c][c]);
+#pragma unroll
+    for (int i = c + 1; i < K; i++) {
+      const double x = fabs(t[i][c]);
+      if (x > best) best = x, r = i;
+    }
+#pragma unroll
+    for (int i = c + 1; i < K; i++) {
+      const bool sw = r == i;
+#pragma unroll
+      for (int m = c; m <= K; m++) {
+        const double x = t[c][m], y = t[i][m];
+        t[c][m] = sw ? y : x;
+        t[i][m] = sw ? x : y;
+      }
+    }
+    neg = neg != (r != c);
+    const double piv = t[c][c];
+    neg = neg != (piv < 0.0);
+    zero = zero || !(fabs(piv) > 0.0);  // 0 or NaN
+    ld.mul(piv);
+    const double rp = fast_rcp(piv);
+    rpiv[c] = rp;
+#pragma unroll
+    for (int i = c + 1; i < K; i++) {
+      const double f = t[i][c] * rp;
+#pragma unroll
+      for (int m = c + 1; m <= K; m++) t[i][m] -= f * t[c][m];
+    }
+  }
+  // back substitution: x = T^-1 Psi_A v, quad = v^T x (v in the pivoted order of the columns = the original order)
+  double x[K], quad = 0.0;
+#pragma unroll
+  for (int i = K - 1; i >= 0; i--) {
+    double s = t[i][K];
+#pragma unroll
+    for (int m = i + 1; m < K; m++) s -= t[i][m] * x[m];
+    x[i] = s * rpiv[i];
+    quad += v[i] * x[i];
+  }
+  if (neg || zero) return -__builtin_inf();
+  return pb - 0.5 * (ld.value() + rr * s2inv - quad * s2inv * s2inv);
+}
+
 // ES3C lpj of the state act[0..K-2] + {j} for one datapoint (file header).  act is wave-uniform, j the lane's latent.  The
 // bordered system: only the row and the column of j are the lane's own -- 2 (K - 1) coalesced loads of {G, Psi} (the row
 // from the transposed table: gathered from GP it would fetch a 128-byte line per 16 bytes used), the diagonal entry and
@@ -171,55 +226,7 @@ __device__ __forceinline__ double seed_score_sssc(const SeedArgs &a, const SeedS
     t[M][M] = 1.0 + s2inv * corner;
     t[M][K] = rhs_m;
   }
-  // LU with partial pivoting (first max |pivot|); rows swap by selects, so nothing is indexed at run time
-  LogDetAcc ld;
-  bool neg = false, zero = false;
-  double rpiv[K];
-#pragma unroll
-  for (int c = 0; c < K; c++) {
-    int r = c;
-    double best = fabs(t[c][c]);
-#pragma unroll
-    for (int i = c + 1; i < K; i++) {
-      const double x = fabs(t[i][c]);
-      if (x > best) best = x, r = i;
-    }
-#pragma unroll
-    for (int i = c + 1; i < K; i++) {
-      const bool sw = r == i;
-#pragma unroll
-      for (int m = c; m <= K; m++) {
-        const double x = t[c][m], y = t[i][m];
-        t[c][m] = sw ? y : x;
-        t[i][m] = sw ? x : y;
-      }
-    }
-    neg = neg != (r != c);
-    const double piv = t[c][c];
-    neg = neg != (piv < 0.0);
-    zero = zero || !(fabs(piv) > 0.0);  // 0 or NaN
-    ld.mul(piv);
-    const double rp = fast_rcp(piv);
-    rpiv[c] = rp;
-#pragma unroll
-    for (int i = c + 1; i < K; i++) {
-      const double f = t[i][c] * rp;
-#pragma unroll
-      for (int m = c + 1; m <= K; m++) t[i][m] -= f * t[c][m];
-    }
-  }
-  // back substitution: x = T^-1 Psi_A v, quad = v^T x (v in the pivoted order of the columns = the original order)
-  double x[K], quad = 0.0;
-#pragma unroll
-  for (int i = K - 1; i >= 0; i--) {
-    double s = t[i][K];
-#pragma unroll
-    for (int m = i + 1; m < K; m++) s -= t[i][m] * x[m];
-    x[i] = s * rpiv[i];
-    quad += v[i] * x[i];
-  }
-  if (neg || zero) return -__builtin_inf();
-  return pb - 0.5 * (ld.value() + rr * s2inv - quad * s2inv * s2inv);
+  return seed_eliminate<K>(t, v, pb, rr, s2inv);
 }
 
 // Psi is not symmetric (kernels_sssc.hpp), so the rows {G_ja, Psi_ja} of the candidates come from a transposed copy of GP,
@@ -313,15 +320,12 @@ __device__ __forceinline__ double seed_score_sssc_step(int t, const SeedArgs &a,
   }
 }
 
-// From the keys of step t in LDS (the caller has synchronised) to the q states and digests of datapoint n in slots
-// slot0 .. slot0 + q - 1, the path entry and the winner in A_t (path, sorted, base): file header.  Returns the winner's
-// latent (wave-uniform) and its score in sw; the caller synchronises before the next step reads path / sorted / base.
-__device__ __forceinline__ int seed_select_step(const SeedArgs &a, const SeedLds &L, i64 n, int t, int q, int slot0, int lane, double &sw_out) {
-  const int S = a.S, H = a.H, HW = a.HW, A = a.A, Hp = a.Hp, Q = a.Q;
+// The q largest keys of L.keys (q <= keys above 0) -> their latents in L.byrank[0..q-1], descending key, ties by ascending
+// j (file header: threshold search, members in ascending j, rank by counting).  Ends synchronised.
+__device__ __forceinline__ void seed_rank_keys(const SeedLds &L, int Hp, int q, int Q, int lane) {
   const int NC = Hp >> 6, NG = (NC + SEED_KREG - 1) / SEED_KREG;  // chunks of 64 latents, register loads of SEED_KREG chunks
-  u64 *keys = L.keys, *base = L.base, *selk = L.selk;
-  int *sel = L.sel, *byrank = L.byrank, *path = L.path, *sorted = L.sorted;
-  u64 *dst = a.states + (size_t)n * S * HW;
+  u64 *keys = L.keys, *selk = L.selk;
+  int *sel = L.sel, *byrank = L.byrank;
   // ---- T = the q-th largest key: the largest T with #{key >= T} >= q (q <= live latents: T > 0).  SEED_KREG chunks
   // of keys at a time in registers, so that one LDS round trip serves that many ballots; H <= 1024: they stay there
   u64 kreg[SEED_KREG];
@@ -383,6 +387,17 @@ __device__ __forceinline__ int seed_select_step(const SeedArgs &a, const SeedLds
     if (mine && rank < Q) byrank[rank] = jm;
   }
   seed_wave_sync();
+}
+
+// From the keys of step t in LDS (the caller has synchronised) to the q states and digests of datapoint n in slots
+// slot0 .. slot0 + q - 1, the path entry and the winner in A_t (path, sorted, base): file header.  Returns the winner's
+// latent (wave-uniform) and its score in sw; the caller synchronises before the next step reads path / sorted / base.
+__device__ __forceinline__ int seed_select_step(const SeedArgs &a, const SeedLds &L, i64 n, int t, int q, int slot0, int lane, double &sw_out) {
+  const int S = a.S, H = a.H, HW = a.HW, A = a.A, Hp = a.Hp, Q = a.Q;
+  u64 *keys = L.keys, *base = L.base;
+  int *byrank = L.byrank, *path = L.path, *sorted = L.sorted;
+  u64 *dst = a.states + (size_t)n * S * HW;
+  seed_rank_keys(L, Hp, q, Q, lane);
   // ---- the q states and their digests
   for (int idx = lane; idx < q * HW; idx += 64) {
     const int r = idx / HW, w = idx - r * HW;

@@ -171,6 +171,22 @@ class RefineResult:
             self.n_done, self.stopped_early, self.F[-1] if self.n_done else None)
 
 
+class SweepResult:
+    """What Model.sweep_resident_states returns: ``F``, ``S_nunique``, ``S_sub`` (n_done,) per sweep, ``n_done`` (the
+    longest rank's), ``n_done_local`` (this rank's), ``stopped_early`` (n_done < the sweeps asked for) and, per datapoint of
+    this rank for the last sweep it ran, ``gain`` (N,), ``best_flip`` int32 (N,) and ``n_capped`` int32 (N,)."""
+    __slots__ = ("F", "S_nunique", "S_sub", "n_done", "n_done_local", "stopped_early", "gain", "best_flip", "n_capped")
+
+    def __init__(self, F, S_nunique, S_sub, n_done, n_done_local, stopped_early, gain, best_flip, n_capped):
+        self.F, self.S_nunique, self.S_sub = F, S_nunique, S_sub
+        self.n_done, self.n_done_local, self.stopped_early = int(n_done), int(n_done_local), bool(stopped_early)
+        self.gain, self.best_flip, self.n_capped = gain, best_flip, n_capped
+
+    def __repr__(self):
+        return "SweepResult(n_done=%d, stopped_early=%s, F=%s)" % (
+            self.n_done, self.stopped_early, self.F[-1] if self.n_done else None)
+
+
 class Model:
     model_name = None  # "bsc" | "sssc"
 
@@ -899,6 +915,50 @@ class Model:
             self.sync_to_host(my_suff_stat)
         return RefineResult(theta["ljc"] + rows[:n_done, 0] / N, rows[:n_done, 1] / N, rows[:n_done, 2] / N, n_done,
                             n_local, n_done < T)
+
+    def sweep_resident_states(self, model_params, my_suff_stat, my_data, n_sweeps=4, n_parents=1, n_keep=None,
+                              stop_when_quiet=True):
+        """Local search on K^n while ``model_params`` stays fixed (Engine.sweep_states; csrc/kernels_sweep.hpp has the law,
+        evo_amd.variational.sweep_states_host is the NumPy mirror): per sweep every one-flip neighbour of the
+        ``n_parents`` best states of each datapoint is scored in the Gram form of the seeding kernel, the ``n_keep`` best
+        per parent that K^n does not hold (None: Cmax // n_parents) are evaluated by the model's lpj kernels and go through
+        the usual selection.  Deterministic: nothing is drawn, so neither rng="device" nor a known EA is needed and
+        ``self._n_steps`` stays.  ``stop_when_quiet``: a rank's loop ends after a sweep that swapped nothing; then
+        ``gain`` <= 0 certifies per datapoint that the best state of K^n has no better one-flip neighbour outside K^n.
+        Returns a SweepResult: ``F`` (n_done,) = ljc + allreduce(Fs_t) / N after sweep t, ``S_nunique`` and ``S_sub``
+        normalised like E_step's, ``n_done``, ``stopped_early`` and this rank's ``gain``, ``best_flip``, ``n_capped`` of its
+        last sweep.  The loop involves no collective: ranks stop on their own and enter the sums as in
+        refine_resident_states.  sync_host as there.  ValueError for the background unit and incomplete data (both out
+        of scope of the sweep); NotImplementedError in the float32 mode."""
+        T = int(n_sweeps)
+        if T < 1:
+            raise ValueError("sweep_resident_states: n_sweeps must be positive")
+        if my_suff_stat["permanent"]["background"]:
+            raise ValueError("sweep_resident_states: the background unit is not supported")
+        if self.dtype == np.float32:
+            raise NotImplementedError("sweep_resident_states is not available in the float32 mode")
+        if not self._complete(my_data):
+            raise ValueError("sweep_resident_states: incomplete data (x_infr with False entries) is not supported")
+        eng = self._prepare(my_suff_stat, my_data)
+        theta = dict(model_params)  # (the precompute stores its derived keys and zeroes the reset counters: on copies)
+        self.E_step_precompute(theta, dict(my_suff_stat), my_data)
+        if model_params is not self._dev_theta:
+            self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
+        P = int(n_parents)
+        trace, n_local, cert = eng.sweep_states(T, P, eng.Cmax // max(P, 1) if n_keep is None else int(n_keep),
+                                                my_suff_stat["Mprime"], stop_when_quiet=stop_when_quiet)
+        # rows of all T sweeps: {Fs, new unique, swapped, this rank still ran}; past this rank's end its last Fs
+        rows = np.zeros((T, 4))
+        rows[:n_local, :3] = trace
+        rows[:n_local, 3] = 1.0
+        rows[n_local:, 0] = trace[-1, 0]
+        rows = _reduce_array(self.comm, rows)
+        N = float(self.comm.allreduce(my_data["y"].shape[0]))
+        n_done = int(np.count_nonzero(rows[:, 3] > 0.0))
+        if self.sync_host:
+            self.sync_to_host(my_suff_stat)
+        return SweepResult(theta["ljc"] + rows[:n_done, 0] / N, rows[:n_done, 1] / N, rows[:n_done, 2] / N, n_done,
+                           n_local, n_done < T, cert["gain"], cert["best_flip"], cert["n_capped"])
 
     def posterior_scores(self, model_params, my_suff_stat, my_data):
         """Per-datapoint scores of this rank's data under ``model_params`` and the caller's K^n / lpj: a dict with the

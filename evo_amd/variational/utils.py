@@ -352,6 +352,98 @@ def seed_states_host(model, theta, Y, S, max_active, S_perm=0, x_infr=None):
     return states, path, lpj_path, margin
 
 
+# ---- local search on K^n: the NumPy mirror of one sweep's proposals (csrc/kernels_sweep.hpp has the law) -----------------
+def sweep_states_host(model, theta, Y, ss, lpj, S_perm, n_parents, n_keep):
+    """One sweep's proposals as evoamd_sweep_propose emits them.  ``ss`` bool (N, S, H) and ``lpj`` (N, S_perm + S) are
+    taken as given, so the choice of the parents (the ``n_parents`` = P varying states with the largest lpj, ties by
+    ascending slot) is exact.  Every one-flip neighbour of a parent is scored with the model's lpj (no ljc, no clamp) unless
+    it is the all-zero state, K^n holds it, or it has more than SEED_MAX_ACTIVE latents; per parent the ``n_keep`` = q best
+    (descending score, ties by ascending latent; scores that are not finite are never proposed) are emitted parent-major,
+    then by rank.  Returns (cand bool (N, P q, H), counts int32 (N,), scores (N, P q) -- NaN beyond counts --, best_flip
+    int32 (N,), gain (N,), n_capped int32 (N,), margin (N,)): best_flip / gain describe the best scored neighbour of parent
+    0 (-1 / -inf without one; gain NaN when an ES3C parent 0 above 8 latents has no score of its own), n_capped counts the
+    parents that lost a neighbour to the cap, margin is the smallest relative gap (a - b) / max(1, |a|) between
+    consecutive chosen ranks and between rank q - 1 and rank q over the datapoint's parents."""
+    sssc = model not in ("bsc", "BSC", "ebsc")
+    assert S_perm in (0, 1)
+    W = np.asarray(theta["W"], dtype=np.float64)
+    Y = np.asarray(Y, dtype=np.float64)
+    ss = np.asarray(ss, dtype=bool)
+    lpj = np.asarray(lpj, dtype=np.float64)
+    (D, H), (N, S) = W.shape, ss.shape[:2]
+    assert Y.shape == (N, D) and ss.shape == (N, S, H) and lpj.shape == (N, S_perm + S)
+    P, q = int(n_parents), int(n_keep)
+    if not (1 <= P <= min(S, 64)) or q < 1:
+        raise ValueError("sweep_states: n_parents = %d must be in [1, min(S = %d, 64)] and n_keep = %d positive" % (P, S, q))
+    cap = SEED_MAX_ACTIVE["sssc" if sssc else "bsc"]
+    G, B, yy = W.T @ W, Y @ W, (Y * Y).sum(axis=1)
+    if sssc:
+        mus, Psi = np.asarray(theta["mus"], dtype=np.float64), np.asarray(theta["Psi"], dtype=np.float64)
+        pies = np.asarray(theta["pies"], dtype=np.float64)
+        pil_bar, s2inv = np.log(pies / (1.0 - pies)), 1.0 / float(theta["sigma2"])
+
+        def state_lpj(n, act):
+            if len(act) == 0:
+                return -0.5 * yy[n] * s2inv
+            return float(_seed_scores_sssc(G, Psi, mus, pil_bar, s2inv, B[n], yy[n], list(act[:-1]), np.array(act[-1:]))[0])
+    else:
+        pi, sigma = float(theta["pi"]), float(theta["sigma"])
+        pre1, pil_bar = -1.0 / 2.0 / sigma / sigma, np.log(pi / (1.0 - pi))
+        Gd = np.diag(G).copy()
+    cand = np.zeros((N, P * q, H), dtype=bool)
+    counts = np.zeros(N, dtype=np.int32)
+    scores = np.full((N, P * q), np.nan)
+    best_flip = np.full(N, -1, dtype=np.int32)
+    gain = np.full(N, -np.inf)
+    n_capped = np.zeros(N, dtype=np.int32)
+    margin = np.full(N, np.inf)
+    for n in range(N):
+        row = np.where(np.isfinite(lpj[n, S_perm:]), lpj[n, S_perm:], -np.inf) + 0.0
+        parents = np.lexsort((np.arange(S), -row))[:P]
+        for r, slot in enumerate(parents):
+            p = ss[n, slot]
+            act = np.flatnonzero(p)
+            m = len(act)
+            diff = ss[n] ^ p
+            one = diff.sum(axis=1) == 1
+            held = np.zeros(H, dtype=bool)
+            held[np.argmax(diff[one], axis=1)] = True
+            size = np.where(p, m - 1, m + 1)
+            live = (size > 0) & ~held
+            lost = live & (size > cap)
+            live &= ~lost
+            n_capped[n] += bool(lost.any())
+            sc = np.full(H, -np.inf)
+            if sssc:
+                base = state_lpj(n, act) if m <= cap else np.nan
+                add = np.flatnonzero(live & ~p)
+                if len(add):
+                    sc[add] = _seed_scores_sssc(G, Psi, mus, pil_bar, s2inv, B[n], yy[n], list(act), add)
+                for j in np.flatnonzero(live & p):
+                    sc[j] = state_lpj(n, act[act != j])
+            else:
+                c = B[n] - G[act].sum(axis=0)
+                base = pre1 * (yy[n] - (B[n, act] + c[act]).sum()) + m * pil_bar
+                with np.errstate(invalid="ignore", over="ignore"):
+                    both = np.where(p, base - pil_bar + pre1 * (Gd + 2.0 * c), base + pil_bar + pre1 * (Gd - 2.0 * c))
+                sc[live] = both[live]
+            js = np.flatnonzero(np.isfinite(sc))
+            order = np.lexsort((js, -sc[js]))
+            ranked, rs = js[order], sc[js][order]
+            k = min(q, len(ranked))
+            for i in range(k):
+                if i + 1 < len(rs):
+                    margin[n] = min(margin[n], _seed_gap(rs[i], rs[i + 1]))
+                at = counts[n] + i
+                cand[n, at] = p
+                cand[n, at, ranked[i]] = ~p[ranked[i]]
+                scores[n, at] = rs[i]
+            counts[n] += k
+            if r == 0 and k:
+                best_flip[n], gain[n] = ranked[0], rs[0] - base
+    return cand, counts, scores, best_flip, gain, n_capped, margin
+
+
 def posterior_scores_host(lpj, ss=None, S_perm=0):
     """NumPy mirror of Engine.posterior_scores (csrc/kernels_refine.hpp): ``lpj`` (N, L) with L = S_perm + S columns,
     ``ss`` bool (N, S, H) the states of columns S_perm .. L - 1 (columns below S_perm are the permanent all-zero

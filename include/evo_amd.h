@@ -374,6 +374,37 @@ int evoamd_refine_states(evoamd_ctx *ctx, int n_iterations, int mutation, int fi
                          double bitflip_prob, int Mprime, int check_every, int patience, double min_sub,
                          double *trace_out, int *n_done_out);
 
+/* Local search on K^n at fixed Theta: a deterministic sweep of the one-flip neighbourhood of its best states
+ * (csrc/kernels_sweep.hpp has the law; evo_amd.variational.sweep_states_host is the NumPy mirror).  Per datapoint the
+ * n_parents varying states with the largest lpj (descending, ties by ascending slot) are the parents; every state that
+ * differs from a parent in one latent is scored with the model's lpj in the Gram form of evoamd_seed_states, unless it is
+ * the all-zero state, K^n holds it already (an exact test on the packed words) or it exceeds the seeding cap (ES3C 8,
+ * EBSC 64 active latents); per parent the n_keep best scored neighbours (descending score, ties by ascending latent; a
+ * score that is not finite is never proposed) go to the resident candidate batch, parent-major, then by rank.
+ * evoamd_sweep_propose evaluates the resident rows (as evoamd_refine_states does at entry), runs the proposal kernel and
+ * the model's own lpj kernels on the emitted rows -- clamp and reset counters as for E-step children -- and leaves the
+ * batch for evoamd_vary_kn and evoamd_download_candidates; the sweep's scores only rank.  Outputs, each may be NULL:
+ * score_out (N, Cmax) the score of every emitted row (NaN beyond counts[n]); from the best parent, best_flip_out (N) the
+ * latent of its best scored neighbour or -1 and gain_out (N) that score minus the parent's own, -inf without a scored
+ * neighbour (NaN: an ES3C parent above 8 latents has no score of its own) -- gain <= 0 certifies that the best state of
+ * K^n has no better one-flip neighbour outside K^n; n_capped_out (N) the parents that lost a neighbour to the cap.
+ * EVOAMD_E_INVALID before anything is written -- K^n, the rows and the candidate batch stay as they were -- without Theta,
+ * data or K^n, with masks present (incomplete data is not supported), with background_unit, ebsc_f32 or bsc_direct, for
+ * n_parents outside [1, min(S, 64)], n_keep < 1, n_parents * n_keep > Cmax, and when the keys of one datapoint do not
+ * fit a wavefront's share of LDS at this H.  No atomics, fixed summation order: two calls give the same bits. */
+int evoamd_sweep_propose(evoamd_ctx *ctx, int n_parents, int n_keep, double *score_out, int32_t *best_flip_out,
+                         double *gain_out, int32_t *n_capped_out);
+/* n_sweeps x (the proposals above, selection with Mprime as evoamd_vary_kn): one pass over K^n at entry, after that the
+ * selection kernel keeps the rows current, so on return they are bit for bit what evoamd_lpj_resident would give and the
+ * result is that of the separate calls.  trace_out (n_sweeps, 3): row t = {Fs, new unique states, swapped states} of
+ * sweep t, as for evoamd_refine_states, with the scalar block left as that call leaves it.  stop_when_quiet: the row is
+ * fetched after each sweep and the loop ends after a sweep that swapped nothing; *n_done_out = sweeps run.  The
+ * certificate outputs describe the last sweep run: after a quiet one, the final K^n.  Refusals as above, and for an
+ * Mprime outside [1, S], n_sweeps < 1 or a NULL trace_out / n_done_out. */
+int evoamd_sweep_states(evoamd_ctx *ctx, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
+                        double *trace_out, int *n_done_out, int32_t *best_flip_out, double *gain_out,
+                        int32_t *n_capped_out);
+
 /* Per-datapoint scores of the lpj rows and K^n resident on the device (after a seed, an upload or any pass), each output
  * (N) or NULL.  With m = max_s lpj_ns, w_s = exp(lpj_ns - m), z = sum_s w_s over the S_perm + S columns:
  * F_out = m + log z (the bound per datapoint without ljc, the counterpart of ll_out of evoamd_loglik_exact);
@@ -793,7 +824,8 @@ enum {
   EVOAMD_K_LOGLIK_FOLD = 27,   /* ... the fold kernel of a pass; the bound + all-zero terms and the finish (one span each) */
   EVOAMD_K_REMAP = 28,         /* evoamd_remap_latents: the remap kernel (index upload and downloads excluded) */
   EVOAMD_K_STATS_KAPPA = 29,   /* the ES3C statistics kernel on the kappa route (option "stats_kappa"), nested in EVOAMD_K_STATS */
-  EVOAMD_K_COUNT = 30
+  EVOAMD_K_SWEEP = 30,         /* evoamd_sweep_propose / evoamd_sweep_states: the proposal kernel (ES3C: with the transpose of GP) */
+  EVOAMD_K_COUNT = 31
 };
 /* on = bit mask of kernel classes to time (bit k = class k; -1 = all, 0 = off).  Each timed span
  * records two HIP events on the compute stream, which costs about 10 us of stream time per span:

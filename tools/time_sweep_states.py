@@ -1,0 +1,121 @@
+"""Time the local search on K^n (Model.sweep_resident_states, evoamd_sweep_states) from the seeded start beside
+Model.refine_resident_states over the same wall time, at the north-star shape (ES3C D = 256, H = 512, S = 200, N = 100k) and
+at c5 (EBSC D = 256, H = 1024, S = 256, N = 200k) on one MI355X.  Data and Theta as tools/time_refine.py; the start is the
+seeded K^n (seed_resident_states is deterministic: every route re-seeds and so starts from the same states).
+
+  wall    host clock around one sweep_resident_states call of ``--sweeps`` sweeps (stop_when_quiet off, one warm-up call
+          first), ms per sweep, median (min - max) of ``--repeats`` calls from the same start; the proposal kernel's own
+          time from a further run with Engine.timing on the class "sweep";
+  F       the free energy before and after each sweep;
+  refine  refine_resident_states is run with growing iteration counts until one call takes at least the sweeps' wall
+          time: its iterations, wall time and F -- the yardstick, untouched by the sweep;
+  L^ - F  estimate_log_likelihood's L^ - F and mean ess at the seeded start and after the sweeps (same seed).
+
+    python tools/time_sweep_states.py [--config c4|c5|both] [--n N] [--sweeps 4] [--parents 1] [--repeats 5]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from evo_amd.models import BSC, SSSC  # noqa: E402
+from time_refine import CONFIGS, EA, sparse_theta  # noqa: E402
+
+
+def run(name, args):
+    algo, D, H, S, N = CONFIGS[name]
+    N = args.n or N
+    T, P = args.sweeps, args.parents
+    rng = np.random.RandomState(0)
+    theta = sparse_theta(rng, algo, D, H)
+    cls = BSC if algo == "ebsc" else SSSC
+    first = cls(D, H, S, rng="device", sync_host=False, seed=1)
+    Y = first.generate_data_device(theta, N, seed=7, keep=("y",))["y"]
+    my_data = {"y": Y, "x_infr": np.ones_like(Y, dtype=bool)}
+    eng = first.engine
+    tag = "%s %s D=%d H=%d S=%d N=%d" % (name, algo, D, H, S, N)
+
+    def seeded():
+        model = cls(D, H, S, rng="device", sync_host=False, seed=1, engine=eng)
+        return model, model.seed_resident_states(dict(theta), my_data, *EA)
+
+    def bound(model, suff):
+        th = dict(theta)
+        model.E_step_precompute(th, dict(suff), my_data)
+        return th["ljc"] + model.posterior_scores(theta, suff, my_data)["F"].mean()
+
+    def tightness(model, suff):
+        L, info = model.estimate_log_likelihood(dict(theta), suff, my_data, n_samples=256, seed=11, per_datapoint=True)
+        return L - bound(model, suff), float(np.nanmean(info["ess"]))
+
+    def sweep_route(sweeps, timed_class=False):
+        model, suff = seeded()
+        before = bound(model, suff)
+        if timed_class:
+            eng.timing(("sweep",))
+            eng.timing_reset()
+        eng.synchronize()
+        t0 = time.perf_counter()
+        res = model.sweep_resident_states(dict(theta), suff, my_data, n_sweeps=sweeps, n_parents=P, stop_when_quiet=False)
+        ms = (time.perf_counter() - t0) * 1e3
+        kernel = eng.kernel_time_ms("sweep") if timed_class else None
+        if timed_class:
+            eng.timing(False)
+        return ms, before, res, model, suff, kernel
+
+    def refine_route(iters):
+        model, suff = seeded()
+        eng.synchronize()
+        t0 = time.perf_counter()
+        res = model.refine_resident_states(dict(theta), suff, my_data, iters)
+        return (time.perf_counter() - t0) * 1e3, res.F
+
+    sweep_route(1)  # warm-up: code objects, buffers
+    refine_route(2)
+    model, suff = seeded()
+    gap0, ess0 = tightness(model, suff)
+    walls = []
+    for _ in range(args.repeats):
+        ms, before, res, model, suff, _ = sweep_route(T)
+        walls.append(ms)
+    gap1, ess1 = tightness(model, suff)
+    ms = float(np.median(walls))
+    _, _, _, _, _, (k_ms, k_n) = sweep_route(T, timed_class=True)
+    print("wall %s: sweep_resident_states %.3f ms per sweep (%d sweeps, n_parents %d, one call; median of %d calls, %.3f - "
+          "%.3f); proposal kernel class %.3f ms per span (%d spans, events on%s)"
+          % (tag, ms / T, T, P, len(walls), min(walls) / T, max(walls) / T, k_ms, k_n,
+             "; one of them the transpose of GP" if algo == "es3c" else ""), flush=True)
+    print("F %s: seeded %.4f; after each sweep %s; swapped per datapoint %s; gain > 0 at the end: %d of %d datapoints"
+          % (tag, before, " ".join("%.4f" % f for f in res.F), " ".join("%.3f" % s for s in res.S_sub),
+             int((res.gain > 0).sum()), N), flush=True)
+    iters, ms_r, F_r = 1, 0.0, None
+    while True:
+        ms_r, F_r = refine_route(iters)
+        if ms_r >= ms or iters >= 4096:
+            break
+        iters = max(iters + 1, int(iters * min(4.0, 1.2 * ms / max(ms_r, 1e-3))))
+    print("refine %s: refine_resident_states needs %d iterations for the sweeps' wall time (%.3f ms against %.3f ms): "
+          "F %.4f against the sweeps' %.4f" % (tag, iters, ms_r, ms, F_r[-1], res.F[-1]), flush=True)
+    print("L^ - F %s (256 draws): seeded %.4f nats (mean ess %.2f); after %d sweeps %.4f nats (mean ess %.2f)"
+          % (tag, gap0, ess0, T, gap1, ess1), flush=True)
+    eng.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="both", choices=["c4", "c5", "both"])
+    ap.add_argument("--n", type=int, default=0, help="datapoints (0: the configuration's)")
+    ap.add_argument("--sweeps", type=int, default=4)
+    ap.add_argument("--parents", type=int, default=1)
+    ap.add_argument("--repeats", type=int, default=5, help="timed calls of the sweep route (the median is reported)")
+    args = ap.parse_args()
+    for name in (["c4", "c5"] if args.config == "both" else [args.config]):
+        run(name, args)
+
+
+if __name__ == "__main__":
+    main()
