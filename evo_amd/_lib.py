@@ -21,6 +21,8 @@ GEN_WHAT = {"y": 0, "s": 1, "z": 2, "y_mean": 3}
 
 # evoamd_seed_states_ex: flags (EVOAMD_SEED_*)
 SEED_INCOMPLETE = 1
+# evoamd_sweep_propose_ex / evoamd_sweep_states_ex: flags (EVOAMD_SWEEP_*)
+SWEEP_INCOMPLETE = 1
 
 # evoamd_posterior_sample: keep bits (EVOAMD_PSAMP_KEEP_*) and the output ids of evoamd_download_posterior_samples
 PSAMP_KEEP = {"slot": 1, "s": 2, "z": 4, "y": 8}
@@ -102,6 +104,9 @@ SIGNATURES = {
                                   ctypes.POINTER(_I)]),
     "evoamd_sweep_propose": (_I, [_vp, _I, _I, _c_dp, _c_i32p, _c_dp, _c_i32p]),
     "evoamd_sweep_states": (_I, [_vp, _I, _I, _I, _I, _I, _c_dp, ctypes.POINTER(_I), _c_i32p, _c_dp, _c_i32p]),
+    "evoamd_sweep_propose_ex": (_I, [_vp, _I, _I, ctypes.c_uint, _c_dp, _c_i32p, _c_dp, _c_i32p]),
+    "evoamd_sweep_states_ex": (_I, [_vp, _I, _I, _I, _I, _I, ctypes.c_uint, _c_dp, ctypes.POINTER(_I), _c_i32p, _c_dp,
+                                    _c_i32p]),
     "evoamd_posterior_scores": (_I, [_vp, _c_dp, _c_dp, _c_i32p, _c_i32p, _c_dp]),
     "evoamd_remap_latents": (_I, [_vp, _c_i32p, _I, _c_i32p, ctypes.POINTER(_I64)]),
     "evoamd_adopt_remapped_states": (_I, [_vp]),

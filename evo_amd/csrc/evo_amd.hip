@@ -572,7 +572,7 @@ struct evoamd_ctx {
   int init_home = -1;
   DevBuf<u64> init_scratch;
   DevBuf<double2> seed_gpt;  // evoamd_seed_states, ES3C: the transpose of GP (H x H), grown on demand, rewritten by every call
-  DevBuf<double> seed_rows;  // evoamd_seed_states_ex, ES3C on incomplete data: the rows of G(n) that do not fit LDS, grown on demand
+  DevBuf<double> seed_rows;  // evoamd_seed_states_ex / evoamd_sweep_*_ex, ES3C on incomplete data: the rows of G(n) that do not fit LDS, grown on demand
   // evoamd_refine_states: one row {Fs, new unique, swapped} per iteration; evoamd_posterior_scores: its (N) outputs.  Grown on
   // demand, rewritten by every call, read by nothing else
   DevBuf<double> refine_trace, score_buf;
@@ -931,6 +931,8 @@ static int set_kernel_lds_limits() {
   HIP_TRY(hipFuncSetAttribute((const void *)seed_states_masked_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   HIP_TRY(hipFuncSetAttribute((const void *)sweep_neighbours_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   HIP_TRY(hipFuncSetAttribute((const void *)sweep_neighbours_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  HIP_TRY(hipFuncSetAttribute((const void *)sweep_neighbours_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  HIP_TRY(hipFuncSetAttribute((const void *)sweep_neighbours_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   {
     const void *wk[] = {(const void *)sssc_stats_wave_kernel<0, 4>,  (const void *)sssc_stats_wave_kernel<1, 4>,
                         (const void *)sssc_stats_wave_kernel<2, 4>,  (const void *)sssc_stats_wave_kernel<4, 4>,
@@ -5633,20 +5635,26 @@ extern "C" int evoamd_seed_states(evoamd_ctx *c, int max_active, int32_t *path_o
 // ---------------------------------------------------------------------------------------
 // Local search on K^n: the one-flip neighbours of its best states (kernels_sweep.hpp has the law).  A sweep is the proposal
 // kernel into the resident candidate batch, the model's own lpj of the emitted rows and the selection; the lpj rows of K^n
-// stay what a pass over it would give.  Complete data only.  Every refusal comes before the first write.
+// stay what a pass over it would give.  Every refusal comes before the first write.
+// EVOAMD_SWEEP_INCOMPLETE is a permission, like EVOAMD_SEED_INCOMPLETE: with masks resident the masked instantiation runs (the
+// datapoint's own Gram quantities from W and the mask), without masks the complete one, whatever the flag says.
 // ---------------------------------------------------------------------------------------
 struct SweepPlan {
   int W = 4;
   size_t wave_bytes = 0;
   unsigned grid = 1;
+  bool masked = false;
+  int R = 0;              // masked ES3C: rows of G(n) per wavefront (SWEEP_ROWS)
+  bool rows_lds = false;  // ... their home: LDS while one wavefront's share fits, else a buffer of the context
 };
 
-static int sweep_check(const evoamd_ctx *c, int n_parents, int n_keep, SweepPlan &p) {
+static int sweep_check(const evoamd_ctx *c, int n_parents, int n_keep, unsigned flags, SweepPlan &p) {
   REQUIRE(c && c->configured, "configure first");
+  REQUIRE(!(flags & ~(unsigned)EVOAMD_SWEEP_INCOMPLETE), "sweep: unknown flag");
   REQUIRE(c->have_params, "sweep: no Theta installed (set parameters first)");
   REQUIRE(c->have_data, "sweep: no data (upload data first)");
   REQUIRE_KN(c);
-  REQUIRE(!c->mask_infr, "sweep: incomplete data (masks present) is not supported");
+  REQUIRE(!c->mask_infr || (flags & EVOAMD_SWEEP_INCOMPLETE), "sweep: incomplete data (masks present) is not supported");
   REQUIRE(!c->bg_unit, "sweep: option background_unit is not supported");
   REQUIRE(!c->f32, "sweep is not available in the float32 mode (ebsc_f32)");
   const bool sssc = c->model == EVOAMD_MODEL_SSSC;
@@ -5658,18 +5666,32 @@ static int sweep_check(const evoamd_ctx *c, int n_parents, int n_keep, SweepPlan
     return fail(EVOAMD_E_INVALID, "sweep: n_parents * n_keep = %lld exceeds the configured Cmax = %d", (long long)n_parents * n_keep,
                 c->Cmax);
   const int Hp = (int)cdiv(c->H, 64) * 64;
-  p.wave_bytes = sweep_wave_bytes(sssc, Hp, c->HW, n_keep);
-  REQUIRE(p.wave_bytes <= 150 * 1024, "sweep: the keys of one datapoint (8 or 16 H bytes) do not fit one wavefront's share of LDS");
+  p.masked = c->mask_infr != nullptr;
+  if (!p.masked) {
+    p.wave_bytes = sweep_wave_bytes(sssc, Hp, c->HW, n_keep);
+    REQUIRE(p.wave_bytes <= 150 * 1024, "sweep: the keys of one datapoint (8 or 16 H bytes) do not fit one wavefront's share of LDS");
+    p.W = 4;
+    while (p.W > 1 && p.W * p.wave_bytes > 150 * 1024) p.W >>= 1;
+    p.grid = (unsigned)std::min<i64>(cdiv(c->N, p.W), (i64)c->n_cu * 64);
+    return 0;
+  }
+  p.R = sssc ? SWEEP_ROWS : 0;
+  p.rows_lds = p.R && sweep_masked_wave_bytes(sssc, Hp, c->HW, n_keep, c->D, p.R) <= 150 * 1024;
+  p.wave_bytes = sweep_masked_wave_bytes(sssc, Hp, c->HW, n_keep, c->D, p.rows_lds ? p.R : 0);
+  REQUIRE(p.wave_bytes <= 150 * 1024, "sweep: the keys of one datapoint (8 or 24 H bytes), the staged column of W (8 D bytes) and the "
+                                      "list of the reliable entries (4 D bytes) do not fit one wavefront's share of LDS");
   p.W = 4;
-  while (p.W > 1 && p.W * p.wave_bytes > 150 * 1024) p.W >>= 1;
-  p.grid = (unsigned)std::min<i64>(cdiv(c->N, p.W), (i64)c->n_cu * 64);
+  while (p.W > 1 && p.W * p.wave_bytes > 150 * 1024) p.W--;
+  // (rows in global memory: fewer workgroups, each wavefront of the grid owns R Hp doubles)
+  p.grid = (unsigned)std::min<i64>(cdiv(c->N, p.W), (i64)c->n_cu * (p.R && !p.rows_lds ? 4 : 64));
   return 0;
 }
 
 // the buffers a sweep needs, B = Y W, (ES3C) the transpose of GP: once per call, Theta stays fixed
-static int sweep_prepare(evoamd_ctx *c) {
+static int sweep_prepare(evoamd_ctx *c, const SweepPlan &p) {
   const size_t N = (size_t)c->N;
   TRY(ensure_B(c));
+  if (p.R && !p.rows_lds) TRY(c->seed_rows.ensure(c, (size_t)p.grid * p.W * p.R * ((size_t)cdiv(c->H, 64) * 64)));
   TRY(c->sweep_d.ensure(c, N * c->Cmax + N));
   TRY(c->sweep_i.ensure(c, 2 * N));
   if (c->model == EVOAMD_MODEL_SSSC) {
@@ -5701,10 +5723,18 @@ static int sweep_propose_stage(evoamd_ctx *c, const SweepPlan &p, int n_parents,
   a.gain = c->sweep_d + N * c->Cmax;
   a.best_flip = c->sweep_i, a.n_capped = c->sweep_i + N;
   a.L = c->L, a.S_perm = c->S_perm, a.P = n_parents, a.q = n_keep, a.Cmax = c->Cmax;
+  if (p.masked) {
+    a.sd.W = c->W, a.sd.mask = c->mask_infr, a.sd.D = c->D, a.sd.R = p.R;
+    a.sd.rows = p.R && !p.rows_lds ? c->seed_rows.get() : nullptr;
+  }
   {
     SpanGuard g(c, KID_SWEEP);
     if (want_score) HIP_TRY(hipMemsetAsync(c->sweep_d, 0xFF, N * c->Cmax * sizeof(double), c->stream));  // rows not emitted: NaN
-    if (sssc)
+    if (p.masked && sssc)
+      sweep_neighbours_kernel<true, true><<<p.grid, 64 * p.W, p.W * p.wave_bytes, c->stream>>>(a);
+    else if (p.masked)
+      sweep_neighbours_kernel<false, true><<<p.grid, 64 * p.W, p.W * p.wave_bytes, c->stream>>>(a);
+    else if (sssc)
       sweep_neighbours_kernel<true><<<p.grid, 64 * p.W, p.W * p.wave_bytes, c->stream>>>(a);
     else
       sweep_neighbours_kernel<false><<<p.grid, 64 * p.W, p.W * p.wave_bytes, c->stream>>>(a);
@@ -5728,28 +5758,33 @@ static int sweep_fetch(evoamd_ctx *c, double *score_out, int32_t *best_flip_out,
   return 0;
 }
 
-extern "C" int evoamd_sweep_propose(evoamd_ctx *c, int n_parents, int n_keep, double *score_out, int32_t *best_flip_out,
-                                    double *gain_out, int32_t *n_capped_out) {
+extern "C" int evoamd_sweep_propose_ex(evoamd_ctx *c, int n_parents, int n_keep, unsigned flags, double *score_out,
+                                       int32_t *best_flip_out, double *gain_out, int32_t *n_capped_out) {
   SweepPlan p;
-  TRY(sweep_check(c, n_parents, n_keep, p));
+  TRY(sweep_check(c, n_parents, n_keep, flags, p));
   HIP_TRY(hipSetDevice(c->device));
-  TRY(sweep_prepare(c));
+  TRY(sweep_prepare(c, p));
   on_estep_route(c, /*fused=*/false);
   TRY(estep_resident_pass(c));
   TRY(sweep_propose_stage(c, p, n_parents, n_keep, score_out != nullptr));
   return sweep_fetch(c, score_out, best_flip_out, gain_out, n_capped_out);
 }
 
-extern "C" int evoamd_sweep_states(evoamd_ctx *c, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
-                                   double *trace_out, int *n_done_out, int32_t *best_flip_out, double *gain_out,
-                                   int32_t *n_capped_out) {
+extern "C" int evoamd_sweep_propose(evoamd_ctx *c, int n_parents, int n_keep, double *score_out, int32_t *best_flip_out,
+                                    double *gain_out, int32_t *n_capped_out) {
+  return evoamd_sweep_propose_ex(c, n_parents, n_keep, 0u, score_out, best_flip_out, gain_out, n_capped_out);
+}
+
+extern "C" int evoamd_sweep_states_ex(evoamd_ctx *c, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
+                                      unsigned flags, double *trace_out, int *n_done_out, int32_t *best_flip_out,
+                                      double *gain_out, int32_t *n_capped_out) {
   SweepPlan p;
-  TRY(sweep_check(c, n_parents, n_keep, p));
+  TRY(sweep_check(c, n_parents, n_keep, flags, p));
   TRY(estep_check_mprime(c, Mprime));
   REQUIRE(n_sweeps >= 1, "evoamd_sweep_states: n_sweeps must be positive");
   REQUIRE(trace_out && n_done_out, "evoamd_sweep_states: trace_out / n_done_out is NULL");
   HIP_TRY(hipSetDevice(c->device));
-  TRY(sweep_prepare(c));
+  TRY(sweep_prepare(c, p));
   TRY(c->refine_trace.ensure(c, (size_t)3 * n_sweeps));
   on_estep_route(c, /*fused=*/false);
   TRY(estep_resident_pass(c));  // after it the selection kernel keeps the rows current (evoamd_refine_states)
@@ -5774,6 +5809,13 @@ extern "C" int evoamd_sweep_states(evoamd_ctx *c, int n_sweeps, int n_parents, i
                            hipMemcpyDeviceToHost, c->stream));
   *n_done_out = done;
   return sweep_fetch(c, nullptr, best_flip_out, gain_out, n_capped_out);
+}
+
+extern "C" int evoamd_sweep_states(evoamd_ctx *c, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
+                                   double *trace_out, int *n_done_out, int32_t *best_flip_out, double *gain_out,
+                                   int32_t *n_capped_out) {
+  return evoamd_sweep_states_ex(c, n_sweeps, n_parents, n_keep, Mprime, stop_when_quiet, 0u, trace_out, n_done_out, best_flip_out,
+                                gain_out, n_capped_out);
 }
 
 // posterior samples (kernels_posterior_sample.hpp): own buffers; of the EM state only B = Y W is (re)formed, like every lpj pass

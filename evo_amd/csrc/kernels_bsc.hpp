@@ -77,11 +77,13 @@ __global__ __launch_bounds__(256) void bsc_lpj_kernel(
               if (d0 + lane + 64 * r < D) acc[r] += wr[64 * r];
           }
         }
+        // (explicit fma here and at the end: left to the compiler, the contraction differed between the unrolled slots of a
+        // chunk, and the lpj of a state depended in its last bit on the slot it sat in)
         double p = 0.0;
 #pragma unroll
         for (int r = 0; r < R; r++) {
           double t = mv[r] ? acc[r] - yv[r] : 0.0;  // select, not multiply: missing entries may hold NaN
-          p += t * t;
+          p = fma(t, t, p);
         }
         part[i] += p;
         kk[i] = k;
@@ -94,7 +96,7 @@ __global__ __launch_bounds__(256) void bsc_lpj_kernel(
     if (c < c1) {
       double tot = wave_sum(part[i]);
       if (lane == 0) {
-        double v = pre1 * tot + pil_bar * (double)kk[i];
+        double v = fma(pil_bar, (double)kk[i], pre1 * tot);
         lpj_out[n * ldo + col0 + c] = clamp_lpj(v, fl);
       }
     }

@@ -2,7 +2,7 @@
 // (evoamd_sweep_propose / evoamd_sweep_states).  Deterministic, no random numbers, no atomics.
 // evo_amd/variational/utils.py: sweep_states_host is the NumPy mirror -- keep the two and the tests in step.
 //
-// THE LAW, per datapoint n and per sweep (P = n_parents, q = n_keep, Hv = H varying latents; complete data only):
+// THE LAW, per datapoint n and per sweep (P = n_parents, q = n_keep, Hv = H varying latents):
 //   parents     the P varying states of K^n with the largest lpj of the row, descending lpj, ties by ascending slot (the
 //               permanent all-zero column of S_perm = 1 is no parent); parent r has the active set p_r, m = |p_r|
 //   neighbours  p_r with bit j flipped, for every j < Hv.  Not scored (key 0, "absent"), tested in this order: (a) the
@@ -26,11 +26,36 @@
 //               -inf (NaN: scored, but parent 0 has no base).  gain <= 0: the best state of K^n has no better one-flip
 //               neighbour outside K^n (a held one cannot be better, or it would be the best state).
 // The scores only rank: the lpj of the emitted rows comes from the model's own lpj kernels afterwards.
+// INCOMPLETE DATA (the MASKED instantiations; evoamd_sweep_*_ex with EVOAMD_SWEEP_INCOMPLETE and masks resident): the same
+// law -- parents, neighbours and the tests (a), (b), (c), choice, emission, certificate, n_capped, the caps 8 / 64 -- with
+// the Gram quantities of the datapoint's reliable entries o = x_infr[n], as in the masked seeding law of kernels_seed.hpp:
+// G(n) = sum_{d in o} W_d. W_d.^T replaces G; B_n and yy_n are what evoamd_upload_masks leaves (it zeroes the missing entries
+// of Y, so NaN there is never read as a number); Psi, mu, pil_bar, sigma2 and pre1 are not masked.  This is the lpj of the
+// reference's W[this_x_infr, :] branches, which evoamd_lpj_resident and the candidate lpj kernels compute on masked data.  A
+// datapoint without a reliable entry needs no special case: G(n) = 0, B_n = 0, yy_n = 0, it is scored by the prior alone
+// and ties go to ascending j.  The summation orders are fixed, so two launches give the same bits:
+//   reliable d  an ascending list in LDS (ballots), as in seed_states_masked_kernel; every sum over d runs down that list
+//               (seed_gram_sweep: fma, four chunks of latents at a time)
+//   EBSC        g_jj = sum_{d in o} W_dj^2 once per datapoint, shared by all P parents.  Per parent ONE sweep with a combined
+//               column in place of the m rows of G: r_d = sum_{i in p, ascending i} W_di for the reliable d, staged in LDS;
+//               c_j = B_nj - sum_{d in o, ascending d} r_d W_dj.  base and the add / remove scores are the expressions above
+//               with g_jj for G_jj.  Cost per datapoint: the diagonal sweep and P sweeps of |o| H multiply-adds (plus
+//               P |o| m gathers for r), independent of m in the sweeps.
+//   ES3C        per datapoint the diagonal, per parent the rows G(n)_{a,.} of its first min(m, 9) active latents in the order
+//               of its list (none when m > 9: nothing of that parent is scored) -- row i: the column W_.a staged in LDS, then
+//               g_aj = sum_d W_da W_dj.  Additions border the parent's blocks through seed_form_blocks(.., rows) and
+//               seed_score_sssc_step<true>; removals and the base are the from-scratch elimination sweep_lpj_scratch<K, true>,
+//               which takes G entries from the rows (entry (i, l) from the row of i) and Psi from GP[..].y.  The SWEEP_ROWS
+//               = 10 rows live in LDS while one wavefront's share fits the 150 KB the launch attributes allow, else in a
+//               per-wavefront buffer of the context with a smaller grid, as the seeding kernel's rows.  A row is formed
+//               anew for every parent (no reuse between the parents of a datapoint).
 // Mapping: lane l owns latents l, l + 64, ...; parents by P rounds of a wave-wide lexicographic maximum below the last
 // pick; the membership test marks held flips in the key array (S HW words per parent, lane s takes states s, s + 64, ..).
 // LDS per wave: keys (Hp u64), EBSC c_j (Hp doubles), the parent's words (HW), ES3C the shared blocks (SeedShared), the
 // members' keys and two lists of their latents (q each), the parent's active latents (SWEEP_PATH ints) and the parents'
-// slots (64 ints).  Every latent index and slot that crossed LDS passes guard_index before it becomes an address.
+// slots (64 ints); incomplete data adds EBSC g_jj (Hp doubles), the staged column (D doubles), ES3C the rows (10 Hp doubles,
+// when LDS is their home) and the list of the reliable d (D ints).  Every latent index, entry index d and slot that crossed
+// LDS passes guard_index before it becomes an address.
 // Cost: EBSC P m rows of G per datapoint (L2-resident at H <= 1024) and P S HW words for the membership; ES3C about
 // P H (k^3 / 3 + 4 k^2) multiply-adds: bound by vector issue, not by HBM.
 #pragma once
@@ -39,6 +64,7 @@
 
 #define SWEEP_PATH 16  // active latents of a parent kept as a list (ES3C reads at most 9)
 #define SWEEP_MAX_P 64
+#define SWEEP_ROWS (SEED_MAX_A_SSSC + 2)  // incomplete data, ES3C: the rows of G(n) of a parent's first 9 active latents and its diagonal
 
 struct SweepArgs {
   SeedArgs sd;          // states (K^n, read only), Bm, yy, G, Gd, GP, GPt, mus, pil_bar, dpar, err, N, S, H, HW, Hp; Q = q
@@ -59,12 +85,27 @@ __host__ __device__ inline size_t sweep_wave_bytes(bool sssc, int Hp, int HW, in
   return (b + 15) & ~(size_t)15;
 }
 
+// incomplete data: behind the complete kernel's share EBSC the diagonal g_jj (Hp doubles), the staged column (D doubles), ES3C
+// the SWEEP_ROWS rows of G(n) when LDS is their home (rows_lds = SWEEP_ROWS, else 0) and the list of the reliable d (D ints)
+__host__ __device__ inline size_t sweep_masked_wave_bytes(bool sssc, int Hp, int HW, int q, int D, int rows_lds) {
+  size_t b = sweep_wave_bytes(sssc, Hp, HW, q) + (size_t)(sssc ? 0 : Hp) * 8 + (size_t)D * 8 + (size_t)rows_lds * Hp * 8 + (size_t)D * 4;
+  return (b + 15) & ~(size_t)15;
+}
+
 // ES3C lpj of the state idx[0..K-1] for one datapoint, eliminated from scratch by the calling lane.  The K x K blocks of
 // {G, Psi} are read where they are used (the few entries stay in the cache): held in registers beside the system they
 // would not fit the register file at K = 8.
-template <int K>
+// MASKED (incomplete data): G is the datapoint's own -- G(n)_{idx[i], idx[l]} = rows[pos[i] * Hp + idx[l]], pos[i] the place of
+// idx[i] in the parent's list of active latents (the kernel forms one row per place); only Psi comes from the table.
+template <int K, bool MASKED = false>
 __device__ __forceinline__ double sweep_lpj_scratch(const SeedArgs &a, const int *idx, const double *__restrict__ Bn, double yy,
-                                                    double s2inv) {
+                                                    double s2inv, const double *rows = nullptr, const int *pos = nullptr) {
+  auto gram = [&](int i, int l) -> double {
+    if constexpr (MASKED)
+      return rows[(size_t)pos[i] * a.Hp + idx[l]];
+    else
+      return a.GP[(size_t)idx[i] * a.H + idx[l]].x;
+  };
   double mu[K], b[K], v[K];
   double pb = 0.0, rr = yy;
 #pragma unroll
@@ -76,7 +117,7 @@ __device__ __forceinline__ double sweep_lpj_scratch(const SeedArgs &a, const int
   for (int i = 0; i < K; i++) {
     double s = b[i];
 #pragma unroll
-    for (int l = 0; l < K; l++) s -= a.GP[(size_t)idx[i] * a.H + idx[l]].x * mu[l];
+    for (int l = 0; l < K; l++) s -= gram(i, l) * mu[l];
     v[i] = s;
     rr -= mu[i] * (b[i] + s);
   }
@@ -93,7 +134,7 @@ __device__ __forceinline__ double sweep_lpj_scratch(const SeedArgs &a, const int
     for (int l = 0; l < K; l++) {
       double s = 0.0;
 #pragma unroll
-      for (int u = 0; u < K; u++) s += pi[u] * a.GP[(size_t)idx[u] * a.H + idx[l]].x;
+      for (int u = 0; u < K; u++) s += pi[u] * gram(u, l);
       t[i][l] = (i == l ? 1.0 : 0.0) + s2inv * s;
     }
     t[i][K] = rhs;
@@ -102,23 +143,25 @@ __device__ __forceinline__ double sweep_lpj_scratch(const SeedArgs &a, const int
 }
 
 // path[0..m-1] without entry `skip` (skip < 0: all of them), k = the length of that list, 1 <= k <= 8
+template <bool MASKED = false>
 __device__ __forceinline__ double sweep_lpj_scratch_k(int k, const SeedArgs &a, const int *path, int skip, const double *__restrict__ Bn,
-                                                      double yy, double s2inv) {
-  int idx[SEED_MAX_A_SSSC];
+                                                      double yy, double s2inv, const double *rows = nullptr) {
+  int idx[SEED_MAX_A_SSSC], pos[SEED_MAX_A_SSSC];
 #pragma unroll
   for (int i = 0; i < SEED_MAX_A_SSSC; i++) {
     const int src = (skip >= 0 && i >= skip) ? i + 1 : i;
     idx[i] = i < k ? guard_index(path[src], a.H, a.err) : 0;
+    pos[i] = i < k ? src : 0;
   }
   switch (k) {
-    case 1: return sweep_lpj_scratch<1>(a, idx, Bn, yy, s2inv);
-    case 2: return sweep_lpj_scratch<2>(a, idx, Bn, yy, s2inv);
-    case 3: return sweep_lpj_scratch<3>(a, idx, Bn, yy, s2inv);
-    case 4: return sweep_lpj_scratch<4>(a, idx, Bn, yy, s2inv);
-    case 5: return sweep_lpj_scratch<5>(a, idx, Bn, yy, s2inv);
-    case 6: return sweep_lpj_scratch<6>(a, idx, Bn, yy, s2inv);
-    case 7: return sweep_lpj_scratch<7>(a, idx, Bn, yy, s2inv);
-    default: return sweep_lpj_scratch<8>(a, idx, Bn, yy, s2inv);
+    case 1: return sweep_lpj_scratch<1, MASKED>(a, idx, Bn, yy, s2inv, rows, pos);
+    case 2: return sweep_lpj_scratch<2, MASKED>(a, idx, Bn, yy, s2inv, rows, pos);
+    case 3: return sweep_lpj_scratch<3, MASKED>(a, idx, Bn, yy, s2inv, rows, pos);
+    case 4: return sweep_lpj_scratch<4, MASKED>(a, idx, Bn, yy, s2inv, rows, pos);
+    case 5: return sweep_lpj_scratch<5, MASKED>(a, idx, Bn, yy, s2inv, rows, pos);
+    case 6: return sweep_lpj_scratch<6, MASKED>(a, idx, Bn, yy, s2inv, rows, pos);
+    case 7: return sweep_lpj_scratch<7, MASKED>(a, idx, Bn, yy, s2inv, rows, pos);
+    default: return sweep_lpj_scratch<8, MASKED>(a, idx, Bn, yy, s2inv, rows, pos);
   }
 }
 
@@ -131,7 +174,8 @@ __device__ __forceinline__ u64 sweep_wave_max_u64(u64 v) {
   return ((u64)hi << 32) | lo;
 }
 
-template <bool SSSC>
+// MASKED: the law on incomplete data (file header); the complete instantiations compile to what they were without it.
+template <bool SSSC, bool MASKED = false>
 __global__ __launch_bounds__(256) void sweep_neighbours_kernel(SweepArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sweep_lds[];
   const SeedArgs &sd = a.sd;
@@ -143,8 +187,20 @@ __global__ __launch_bounds__(256) void sweep_neighbours_kernel(SweepArgs a) {
   // one wavefront's share of LDS (file header)
   SeedLds L;
   int *parents;
+  // incomplete data: the diagonal of G(n), the staged column, ES3C the rows of G(n) (row SWEEP_ROWS - 1: the diagonal), the reliable d
+  double *gd = nullptr, *col = nullptr, *rows = nullptr;
+  int *dl = nullptr;
   {
-    unsigned char *home = sweep_lds + (size_t)wave * sweep_wave_bytes(SSSC, Hp, HW, q);
+    unsigned char *home = sweep_lds + (size_t)wave * (MASKED ? sweep_masked_wave_bytes(SSSC, Hp, HW, q, sd.D, sd.rows ? 0 : sd.R)
+                                                             : sweep_wave_bytes(SSSC, Hp, HW, q));
+    if constexpr (MASKED) {
+      double *x = (double *)(home + sweep_wave_bytes(SSSC, Hp, HW, q));
+      gd = x, x += SSSC ? 0 : Hp;
+      col = x, x += sd.D;
+      rows = sd.rows ? sd.rows + ((size_t)blockIdx.x * W + wave) * sd.R * Hp : x;
+      dl = (int *)(x + (sd.rows ? (size_t)0 : (size_t)sd.R * Hp));
+      if (SSSC) gd = rows + (size_t)(sd.R - 1) * Hp;
+    }
     L.keys = (u64 *)home;
     L.cc = (double *)(L.keys + Hp);
     L.base = (u64 *)(L.cc + (SSSC ? 0 : Hp));
@@ -169,6 +225,19 @@ __global__ __launch_bounds__(256) void sweep_neighbours_kernel(SweepArgs a) {
     const double yy = sd.yy[n];
     const double *row = a.lpj + (size_t)n * a.L + a.S_perm;
     const u64 *kn = sd.states + (size_t)n * S * HW;
+    int nd = 0;  // incomplete data: the reliable d in ascending order, then g_jj = sum over them of W_dj^2
+    if constexpr (MASKED) {
+      const uint8_t *mn = sd.mask + (size_t)n * sd.D;
+      for (int d0 = 0; d0 < sd.D; d0 += 64) {
+        const int d = d0 + lane;
+        const bool on = d < sd.D && mn[d < sd.D ? d : 0] != 0;
+        const u64 b = __ballot(on);
+        if (on) dl[nd + __popcll(b & ((1ull << lane) - 1ull))] = d;
+        nd += __popcll(b);
+      }
+      seed_wave_sync();
+      seed_gram_sweep<true>(sd, lane, dl, col, nd, gd);
+    }
     // ---- parents: round r takes the largest (lpj, -slot) below the pick of round r - 1
     {
       u64 pk = 0ull;
@@ -233,12 +302,24 @@ __global__ __launch_bounds__(256) void sweep_neighbours_kernel(SweepArgs a) {
       bool lost = false;   // a neighbour neither all-zero nor held, above the cap
       double base;
       if (SSSC) {
+        if constexpr (MASKED) {
+          // row i of G(n) for the parent's i-th active latent, m <= 9 (above that nothing of this parent is scored): the
+          // column W_.a staged in LDS, then the sweep over the reliable d
+          const int nr = m <= CAP + 1 ? m : 0;
+          for (int i = 0; i < nr; i++) {
+            const int ja = guard_index(__builtin_amdgcn_readfirstlane(path[i]), H, sd.err);
+            for (int t = lane; t < nd; t += 64) col[t] = sd.W[(size_t)guard_index(dl[t], sd.D, sd.err) * H + ja];
+            seed_wave_sync();
+            seed_gram_sweep<false>(sd, lane, dl, col, nd, rows + (size_t)i * Hp);
+            seed_wave_sync();  // the column is staged again; the rows are read by other lanes
+          }
+        }
         // removals: lane i takes the i-th active latent out, base: every lane the same system
         if (m >= 2 && m <= CAP + 1) {
           if (lane < m) {
             const int ja = guard_index(path[lane], H, sd.err);
             u64 key = 0ull;
-            if (keys[ja] != 1ull) key = sweep_key(sweep_lpj_scratch_k(m - 1, sd, path, lane, Bn, yy, s2inv));
+            if (keys[ja] != 1ull) key = sweep_key(sweep_lpj_scratch_k<MASKED>(m - 1, sd, path, lane, Bn, yy, s2inv, rows));
             keys[ja] = key;
           }
         } else if (m == 1) {
@@ -254,11 +335,11 @@ __global__ __launch_bounds__(256) void sweep_neighbours_kernel(SweepArgs a) {
           }
         }
         base = m == 0 ? -0.5 * yy * s2inv
-                      : (m <= CAP ? sweep_lpj_scratch_k(m, sd, path, -1, Bn, yy, s2inv) : __builtin_nan(""));
+                      : (m <= CAP ? sweep_lpj_scratch_k<MASKED>(m, sd, path, -1, Bn, yy, s2inv, rows) : __builtin_nan(""));
         // additions, bordered on the parent's blocks
         int act[SEED_MAX_A_SSSC];
         double pbA = 0.0;
-        if (add_ok) pbA = seed_form_blocks(sd, L, m + 1, lane, Bn, s2inv, act, nullptr);
+        if (add_ok) pbA = seed_form_blocks(sd, L, m + 1, lane, Bn, s2inv, act, MASKED ? rows : nullptr);
         for (int c = 0; c < NC; c++) {
           const int j = 64 * c + lane;
           if (j >= H) continue;
@@ -266,10 +347,30 @@ __global__ __launch_bounds__(256) void sweep_neighbours_kernel(SweepArgs a) {
           const bool held = keys[j] == 1ull;
           lost = lost || (!held && !add_ok);
           u64 key = 0ull;
-          if (!held && add_ok) key = sweep_key(seed_score_sssc_step<false>(m + 1, sd, L.sh, act, pbA, j, Bn, yy, s2inv, nullptr));
+          if (!held && add_ok)
+            key = sweep_key(seed_score_sssc_step<MASKED>(m + 1, sd, L.sh, act, pbA, j, Bn, yy, s2inv, MASKED ? rows : nullptr));
           keys[j] = key;
         }
       } else {
+        if constexpr (MASKED) {
+          // the combined column r_d = sum_{i in p} W_di (ascending i) for the reliable d, then ONE sweep:
+          // c_j = B_nj - sum_d r_d W_dj (ascending d)
+          for (int t = lane; t < nd; t += 64) {
+            const double *Wd = sd.W + (size_t)guard_index(dl[t], sd.D, sd.err) * H;
+            double s = 0.0;
+            for (int w = 0; w < HW; w++) {
+              u64 v = par[w];
+              while (v) s += Wd[guard_index(64 * w + pop_msb(v), H, sd.err)];
+            }
+            col[t] = s;
+          }
+          seed_wave_sync();
+          seed_gram_sweep<false>(sd, lane, dl, col, nd, cc);
+          for (int c = 0; c < NC; c++) {
+            const int j = 64 * c + lane;
+            cc[j] = (j < H ? Bn[j] : 0.0) - cc[j];
+          }
+        } else
         // c_j = B_nj - sum_{i in p} G_ij, the rows in ascending i, four chunks of latents at a time
         for (int c0 = 0; c0 < NC; c0 += 4) {
           double acc[4];
@@ -317,7 +418,7 @@ __global__ __launch_bounds__(256) void sweep_neighbours_kernel(SweepArgs a) {
           lost = lost || (!zero && !held && !ok);
           u64 key = 0ull;
           if (!zero && !held && ok) {
-            const double gjj = sd.Gd[j], cj = cc[j];
+            const double gjj = MASKED ? gd[j] : sd.Gd[j], cj = cc[j];
             key = sweep_key(on ? base - pilb + pre1 * (gjj + 2.0 * cj) : base + pilb + pre1 * (gjj - 2.0 * cj));
           }
           keys[j] = key;

@@ -347,7 +347,7 @@ class Engine:
             int(check_every), int(patience), float(min_sub), dptr(trace), ctypes.byref(n_done)))
         return trace[:n_done.value], n_done.value
 
-    def sweep_propose(self, n_parents, n_keep, want_scores=True):
+    def sweep_propose(self, n_parents, n_keep, want_scores=True, incomplete=False):
         """One sweep's proposals of the local search on K^n (evoamd_sweep_propose; csrc/kernels_sweep.hpp has the law,
         evo_amd.variational.sweep_states_host is the NumPy mirror): the resident rows are evaluated, every one-flip
         neighbour of the ``n_parents`` best states of each datapoint is scored, the ``n_keep`` best per parent that K^n
@@ -355,22 +355,30 @@ class Engine:
         download_candidates() can follow.  Returns a dict: "score" (N, Cmax) the score of every emitted row, NaN elsewhere
         (None without ``want_scores``), "best_flip" int32 (N,) and "gain" (N,) of the best state's best scored neighbour
         (-1 / -inf without one; gain <= 0: no better one-flip neighbour outside K^n), "n_capped" int32 (N,).  EvoAmdError
-        naming the rule, with the context as it was, without Theta, data or K^n, for incomplete data, the background
-        unit, the float32 mode, bsc_direct, n_parents outside [1, min(S, 64)], n_keep < 1 or n_parents * n_keep > Cmax."""
+        naming the rule, with the context as it was, without Theta, data or K^n, for incomplete data without
+        ``incomplete``, the background unit, the float32 mode, bsc_direct, n_parents outside [1, min(S, 64)], n_keep < 1
+        or n_parents * n_keep > Cmax.  ``incomplete`` permits incomplete data (evoamd_sweep_propose_ex,
+        EVOAMD_SWEEP_INCOMPLETE): with masks resident (upload_masks) every datapoint's neighbours are scored on its
+        reliable entries, its Gram quantities formed from W and the mask (sweep_states_host with ``x_infr``); without masks
+        the flag changes nothing."""
         score = np.empty((self.N, self.Cmax), dtype=np.float64) if want_scores else None
         best = np.empty(self.N, dtype=np.int32)
         gain = np.empty(self.N, dtype=np.float64)
         capped = np.empty(self.N, dtype=np.int32)
-        check(self.lib.evoamd_sweep_propose(self._h, int(n_parents), int(n_keep), dptr(score) if want_scores else None,
-                                            i32ptr(best), dptr(gain), i32ptr(capped)))
+        out = (dptr(score) if want_scores else None, i32ptr(best), dptr(gain), i32ptr(capped))
+        if incomplete:
+            check(self.lib.evoamd_sweep_propose_ex(self._h, int(n_parents), int(n_keep), _lib.SWEEP_INCOMPLETE, *out))
+        else:
+            check(self.lib.evoamd_sweep_propose(self._h, int(n_parents), int(n_keep), *out))
         return {"score": score, "best_flip": best, "gain": gain, "n_capped": capped}
 
-    def sweep_states(self, n_sweeps, n_parents=1, n_keep=None, Mprime=None, stop_when_quiet=True):
+    def sweep_states(self, n_sweeps, n_parents=1, n_keep=None, Mprime=None, stop_when_quiet=True, incomplete=False):
         """``n_sweeps`` x (sweep_propose, selection with ``Mprime``, default S) in one library call (evoamd_sweep_states):
         bit for bit what the separate calls give, the lpj rows stay those of the resident K^n.  ``n_keep`` None: Cmax //
         n_parents.  ``stop_when_quiet``: the loop ends after a sweep that swapped nothing.  Returns (trace (n_done, 3),
         n_done, certificate): row t = (Fs, new unique states, swapped states) of sweep t; the certificate is the dict of
-        sweep_propose without "score", for the last sweep run (after a quiet one: the final K^n)."""
+        sweep_propose without "score", for the last sweep run (after a quiet one: the final K^n).  ``incomplete`` as for
+        sweep_propose (evoamd_sweep_states_ex)."""
         T = int(n_sweeps)
         P = int(n_parents)
         q = self.Cmax // max(P, 1) if n_keep is None else int(n_keep)
@@ -379,9 +387,12 @@ class Engine:
         best = np.empty(self.N, dtype=np.int32)
         gain = np.empty(self.N, dtype=np.float64)
         capped = np.empty(self.N, dtype=np.int32)
-        check(self.lib.evoamd_sweep_states(self._h, T, P, q, self.S if Mprime is None else int(Mprime),
-                                           1 if stop_when_quiet else 0, dptr(trace), ctypes.byref(n_done), i32ptr(best),
-                                           dptr(gain), i32ptr(capped)))
+        head = (self._h, T, P, q, self.S if Mprime is None else int(Mprime), 1 if stop_when_quiet else 0)
+        out = (dptr(trace), ctypes.byref(n_done), i32ptr(best), dptr(gain), i32ptr(capped))
+        if incomplete:
+            check(self.lib.evoamd_sweep_states_ex(*head, _lib.SWEEP_INCOMPLETE, *out))
+        else:
+            check(self.lib.evoamd_sweep_states(*head, *out))
         return trace[:n_done.value], n_done.value, {"best_flip": best, "gain": gain, "n_capped": capped}
 
     SCORES = ("F", "entropy", "best", "k_best", "k_mean")

@@ -917,7 +917,7 @@ class Model:
                             n_local, n_done < T)
 
     def sweep_resident_states(self, model_params, my_suff_stat, my_data, n_sweeps=4, n_parents=1, n_keep=None,
-                              stop_when_quiet=True):
+                              stop_when_quiet=True, incomplete=False):
         """Local search on K^n while ``model_params`` stays fixed (Engine.sweep_states; csrc/kernels_sweep.hpp has the law,
         evo_amd.variational.sweep_states_host is the NumPy mirror): per sweep every one-flip neighbour of the
         ``n_parents`` best states of each datapoint is scored in the Gram form of the seeding kernel, the ``n_keep`` best
@@ -928,8 +928,10 @@ class Model:
         Returns a SweepResult: ``F`` (n_done,) = ljc + allreduce(Fs_t) / N after sweep t, ``S_nunique`` and ``S_sub``
         normalised like E_step's, ``n_done``, ``stopped_early`` and this rank's ``gain``, ``best_flip``, ``n_capped`` of its
         last sweep.  The loop involves no collective: ranks stop on their own and enter the sums as in
-        refine_resident_states.  sync_host as there.  ValueError for the background unit and incomplete data (both out
-        of scope of the sweep); NotImplementedError in the float32 mode."""
+        refine_resident_states.  sync_host as there.  ``incomplete=True`` admits my_data["x_infr"] with False entries
+        (inpainting, imputation): the masks go up as for any E-step and every neighbour is scored on the datapoint's
+        reliable entries alone -- values of y under False, NaN included, never enter.  ValueError for the background
+        unit and for incomplete data without ``incomplete=True``; NotImplementedError in the float32 mode."""
         T = int(n_sweeps)
         if T < 1:
             raise ValueError("sweep_resident_states: n_sweeps must be positive")
@@ -937,8 +939,9 @@ class Model:
             raise ValueError("sweep_resident_states: the background unit is not supported")
         if self.dtype == np.float32:
             raise NotImplementedError("sweep_resident_states is not available in the float32 mode")
-        if not self._complete(my_data):
-            raise ValueError("sweep_resident_states: incomplete data (x_infr with False entries) is not supported")
+        if not incomplete and not self._complete(my_data):
+            raise ValueError("sweep_resident_states: incomplete data (x_infr with False entries) is not supported "
+                             "by default: pass incomplete=True")
         eng = self._prepare(my_suff_stat, my_data)
         theta = dict(model_params)  # (the precompute stores its derived keys and zeroes the reset counters: on copies)
         self.E_step_precompute(theta, dict(my_suff_stat), my_data)
@@ -946,7 +949,8 @@ class Model:
             self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
         P = int(n_parents)
         trace, n_local, cert = eng.sweep_states(T, P, eng.Cmax // max(P, 1) if n_keep is None else int(n_keep),
-                                                my_suff_stat["Mprime"], stop_when_quiet=stop_when_quiet)
+                                                my_suff_stat["Mprime"], stop_when_quiet=stop_when_quiet,
+                                                incomplete=bool(incomplete))
         # rows of all T sweeps: {Fs, new unique, swapped, this rank still ran}; past this rank's end its last Fs
         rows = np.zeros((T, 4))
         rows[:n_local, :3] = trace

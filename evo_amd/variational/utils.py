@@ -353,7 +353,7 @@ def seed_states_host(model, theta, Y, S, max_active, S_perm=0, x_infr=None):
 
 
 # ---- local search on K^n: the NumPy mirror of one sweep's proposals (csrc/kernels_sweep.hpp has the law) -----------------
-def sweep_states_host(model, theta, Y, ss, lpj, S_perm, n_parents, n_keep):
+def sweep_states_host(model, theta, Y, ss, lpj, S_perm, n_parents, n_keep, x_infr=None):
     """One sweep's proposals as evoamd_sweep_propose emits them.  ``ss`` bool (N, S, H) and ``lpj`` (N, S_perm + S) are
     taken as given, so the choice of the parents (the ``n_parents`` = P varying states with the largest lpj, ties by
     ascending slot) is exact.  Every one-flip neighbour of a parent is scored with the model's lpj (no ljc, no clamp) unless
@@ -363,11 +363,20 @@ def sweep_states_host(model, theta, Y, ss, lpj, S_perm, n_parents, n_keep):
     int32 (N,), gain (N,), n_capped int32 (N,), margin (N,)): best_flip / gain describe the best scored neighbour of parent
     0 (-1 / -inf without one; gain NaN when an ES3C parent 0 above 8 latents has no score of its own), n_capped counts the
     parents that lost a neighbour to the cap, margin is the smallest relative gap (a - b) / max(1, |a|) between
-    consecutive chosen ranks and between rank q - 1 and rank q over the datapoint's parents."""
+    consecutive chosen ranks and between rank q - 1 and rank q over the datapoint's parents.
+    ``x_infr`` bool (N, D), incomplete data: datapoint n is scored on its reliable entries o = x_infr[n] alone, as in
+    seed_states_host -- G(n) = W_o^T W_o, B_n = y_o^T W_o, yy_n = |y_o|^2; entries of Y under False are never read as
+    numbers (NaN included) and a datapoint without a reliable entry is scored by the prior alone.  ``lpj`` is then the
+    masked lpj of ``ss``.  None: complete data."""
     sssc = model not in ("bsc", "BSC", "ebsc")
     assert S_perm in (0, 1)
     W = np.asarray(theta["W"], dtype=np.float64)
     Y = np.asarray(Y, dtype=np.float64)
+    masked = x_infr is not None
+    if masked:
+        x_infr = np.asarray(x_infr, dtype=bool)
+        assert x_infr.shape == Y.shape
+        Y = np.where(x_infr, Y, 0.0)
     ss = np.asarray(ss, dtype=bool)
     lpj = np.asarray(lpj, dtype=np.float64)
     (D, H), (N, S) = W.shape, ss.shape[:2]
@@ -398,6 +407,10 @@ def sweep_states_host(model, theta, Y, ss, lpj, S_perm, n_parents, n_keep):
     n_capped = np.zeros(N, dtype=np.int32)
     margin = np.full(N, np.inf)
     for n in range(N):
+        if masked:  # the datapoint's own Gram matrix, from the reliable rows of W (state_lpj reads G where it is called)
+            Wo = W[x_infr[n]]
+            G = Wo.T @ Wo
+            Gd = np.diag(G).copy()
         row = np.where(np.isfinite(lpj[n, S_perm:]), lpj[n, S_perm:], -np.inf) + 0.0
         parents = np.lexsort((np.arange(S), -row))[:P]
         for r, slot in enumerate(parents):

@@ -389,7 +389,7 @@ int evoamd_refine_states(evoamd_ctx *ctx, int n_iterations, int mutation, int fi
  * neighbour (NaN: an ES3C parent above 8 latents has no score of its own) -- gain <= 0 certifies that the best state of
  * K^n has no better one-flip neighbour outside K^n; n_capped_out (N) the parents that lost a neighbour to the cap.
  * EVOAMD_E_INVALID before anything is written -- K^n, the rows and the candidate batch stay as they were -- without Theta,
- * data or K^n, with masks present (incomplete data is not supported), with background_unit, ebsc_f32 or bsc_direct, for
+ * data or K^n, with masks present (incomplete data needs the _ex calls below), with background_unit, ebsc_f32 or bsc_direct, for
  * n_parents outside [1, min(S, 64)], n_keep < 1, n_parents * n_keep > Cmax, and when the keys of one datapoint do not
  * fit a wavefront's share of LDS at this H.  No atomics, fixed summation order: two calls give the same bits. */
 int evoamd_sweep_propose(evoamd_ctx *ctx, int n_parents, int n_keep, double *score_out, int32_t *best_flip_out,
@@ -404,6 +404,25 @@ int evoamd_sweep_propose(evoamd_ctx *ctx, int n_parents, int n_keep, double *sco
 int evoamd_sweep_states(evoamd_ctx *ctx, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
                         double *trace_out, int *n_done_out, int32_t *best_flip_out, double *gain_out,
                         int32_t *n_capped_out);
+/* The two calls above with flags (0: exactly those calls, every refusal and its text included).  EVOAMD_SWEEP_INCOMPLETE
+ * permits incomplete data; it is a permission, not a mode, like EVOAMD_SEED_INCOMPLETE: with masks resident
+ * (evoamd_upload_masks) the same law runs with the Gram quantities of the datapoint's reliable entries o = x_infr[n] --
+ * G(n) = W_o^T W_o formed per datapoint from W and the resident mask, B_n = y_o^T W_o and |y_o|^2 as evoamd_upload_masks
+ * left them (it zeroes the missing entries of Y, so NaN there is never read); Psi, mu, pil_bar, sigma2 and pre1 are not
+ * masked -- the lpj that evoamd_lpj_resident and the candidate lpj kernels compute on masked data, which evaluate the
+ * emitted rows.  A datapoint without a reliable entry is scored by the prior alone.  Without masks the complete kernel
+ * runs, bit for bit as without the flag.  EBSC: the diagonal of G(n) once per datapoint and ONE sweep over W per parent
+ * with the combined column r_d = sum_{i in p} W_di; ES3C: the rows of G(n) of a parent's first 9 active latents and the
+ * diagonal, 10 rows of ceil64(H) doubles per wavefront, in LDS while they fit one wavefront's share, else in a buffer of
+ * the context grown on demand.  Refusals as above, and for an unknown flag bit and for keys (8 H bytes, EBSC 24 H), a
+ * staged column (8 D bytes) and a list of the reliable entries (4 D bytes) that do not fit one wavefront's share of LDS.
+ * No atomics, a fixed summation order (ascending d, ascending i): two calls give the same bits. */
+#define EVOAMD_SWEEP_INCOMPLETE 1u
+int evoamd_sweep_propose_ex(evoamd_ctx *ctx, int n_parents, int n_keep, unsigned flags, double *score_out,
+                            int32_t *best_flip_out, double *gain_out, int32_t *n_capped_out);
+int evoamd_sweep_states_ex(evoamd_ctx *ctx, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
+                           unsigned flags, double *trace_out, int *n_done_out, int32_t *best_flip_out, double *gain_out,
+                           int32_t *n_capped_out);
 
 /* Per-datapoint scores of the lpj rows and K^n resident on the device (after a seed, an upload or any pass), each output
  * (N) or NULL.  With m = max_s lpj_ns, w_s = exp(lpj_ns - m), z = sum_s w_s over the S_perm + S columns:

@@ -11,7 +11,12 @@ seeded K^n (seed_resident_states is deterministic: every route re-seeds and so s
           time: its iterations, wall time and F -- the yardstick, untouched by the sweep;
   L^ - F  estimate_log_likelihood's L^ - F and mean ess at the seeded start and after the sweeps (same seed).
 
-    python tools/time_sweep_states.py [--config c4|c5|both] [--n N] [--sweeps 4] [--parents 1] [--repeats 5]
+``--missing FRACTION`` (default 0: all of the above on complete data, nothing else): an i.i.d. mask hides that fraction of
+the entries (NaN in the data); after the complete measurement the same lines are printed for the masked data
+(seed_resident_states and sweep_resident_states with incomplete=True: evoamd_sweep_states_ex, EVOAMD_SWEEP_INCOMPLETE), in
+the same run on the same engine, with refine_resident_states on the masked data as the yardstick.
+
+    python tools/time_sweep_states.py [--config c4|c5|both] [--n N] [--sweeps 4] [--parents 1] [--repeats 5] [--missing 0.5]
 """
 import argparse
 import os
@@ -29,19 +34,29 @@ from time_refine import CONFIGS, EA, sparse_theta  # noqa: E402
 def run(name, args):
     algo, D, H, S, N = CONFIGS[name]
     N = args.n or N
-    T, P = args.sweeps, args.parents
     rng = np.random.RandomState(0)
     theta = sparse_theta(rng, algo, D, H)
     cls = BSC if algo == "ebsc" else SSSC
     first = cls(D, H, S, rng="device", sync_host=False, seed=1)
     Y = first.generate_data_device(theta, N, seed=7, keep=("y",))["y"]
-    my_data = {"y": Y, "x_infr": np.ones_like(Y, dtype=bool)}
     eng = first.engine
-    tag = "%s %s D=%d H=%d S=%d N=%d" % (name, algo, D, H, S, N)
+    measure(args, cls, eng, S, theta, {"y": Y, "x_infr": np.ones_like(Y, dtype=bool)}, False,
+            "%s %s D=%d H=%d S=%d N=%d" % (name, algo, D, H, S, N), algo)
+    if args.missing > 0:  # the same run, the same engine: the masked calls beside the complete ones
+        x_infr = np.random.RandomState(11).random_sample(Y.shape) >= args.missing
+        measure(args, cls, eng, S, theta, {"y": np.where(x_infr, Y, np.nan), "x_infr": x_infr, "x": x_infr.copy()},
+                True,
+                "%s %s D=%d H=%d S=%d N=%d missing=%.2f" % (name, algo, D, H, S, N, args.missing), algo)
+    eng.close()
+
+
+def measure(args, cls, eng, S, theta, my_data, incomplete, tag, algo):
+    (N, D), H = my_data["y"].shape, theta["W"].shape[1]
+    T, P = args.sweeps, args.parents
 
     def seeded():
         model = cls(D, H, S, rng="device", sync_host=False, seed=1, engine=eng)
-        return model, model.seed_resident_states(dict(theta), my_data, *EA)
+        return model, model.seed_resident_states(dict(theta), my_data, *EA, incomplete=incomplete)
 
     def bound(model, suff):
         th = dict(theta)
@@ -60,7 +75,8 @@ def run(name, args):
             eng.timing_reset()
         eng.synchronize()
         t0 = time.perf_counter()
-        res = model.sweep_resident_states(dict(theta), suff, my_data, n_sweeps=sweeps, n_parents=P, stop_when_quiet=False)
+        res = model.sweep_resident_states(dict(theta), suff, my_data, n_sweeps=sweeps, n_parents=P, stop_when_quiet=False,
+                                          incomplete=incomplete)
         ms = (time.perf_counter() - t0) * 1e3
         kernel = eng.kernel_time_ms("sweep") if timed_class else None
         if timed_class:
@@ -89,9 +105,9 @@ def run(name, args):
           "%.3f); proposal kernel class %.3f ms per span (%d spans, events on%s)"
           % (tag, ms / T, T, P, len(walls), min(walls) / T, max(walls) / T, k_ms, k_n,
              "; one of them the transpose of GP" if algo == "es3c" else ""), flush=True)
-    print("F %s: seeded %.4f; after each sweep %s; swapped per datapoint %s; gain > 0 at the end: %d of %d datapoints"
-          % (tag, before, " ".join("%.4f" % f for f in res.F), " ".join("%.3f" % s for s in res.S_sub),
-             int((res.gain > 0).sum()), N), flush=True)
+    print("F %s: seeded %.4f; after each sweep %s; swapped per datapoint %s; gain > 0 at the end: %d, gain <= 0: %d of %d "
+          "datapoints" % (tag, before, " ".join("%.4f" % f for f in res.F), " ".join("%.3f" % s for s in res.S_sub),
+                          int((res.gain > 0).sum()), int((res.gain <= 0).sum()), N), flush=True)
     iters, ms_r, F_r = 1, 0.0, None
     while True:
         ms_r, F_r = refine_route(iters)
@@ -102,7 +118,6 @@ def run(name, args):
           "F %.4f against the sweeps' %.4f" % (tag, iters, ms_r, ms, F_r[-1], res.F[-1]), flush=True)
     print("L^ - F %s (256 draws): seeded %.4f nats (mean ess %.2f); after %d sweeps %.4f nats (mean ess %.2f)"
           % (tag, gap0, ess0, T, gap1, ess1), flush=True)
-    eng.close()
 
 
 def main():
@@ -112,6 +127,7 @@ def main():
     ap.add_argument("--sweeps", type=int, default=4)
     ap.add_argument("--parents", type=int, default=1)
     ap.add_argument("--repeats", type=int, default=5, help="timed calls of the sweep route (the median is reported)")
+    ap.add_argument("--missing", type=float, default=0.0, help="fraction of entries hidden by an i.i.d. mask (0: complete data)")
     args = ap.parse_args()
     for name in (["c4", "c5"] if args.config == "both" else [args.config]):
         run(name, args)
