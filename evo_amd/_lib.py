@@ -23,6 +23,9 @@ GEN_WHAT = {"y": 0, "s": 1, "z": 2, "y_mean": 3}
 SEED_INCOMPLETE = 1
 # evoamd_sweep_propose_ex / evoamd_sweep_states_ex: flags (EVOAMD_SWEEP_*)
 SWEEP_INCOMPLETE = 1
+# evoamd_sweep_propose_nb / evoamd_sweep_states_nb: the neighbourhood bits beside it
+SWEEP_SWAP, SWEEP_NO_FLIP = 2, 4
+SWEEP_NEIGHBOURHOODS = {"flip": 0, "swap": SWEEP_SWAP | SWEEP_NO_FLIP, "both": SWEEP_SWAP}
 
 # evoamd_posterior_sample: keep bits (EVOAMD_PSAMP_KEEP_*) and the output ids of evoamd_download_posterior_samples
 PSAMP_KEEP = {"slot": 1, "s": 2, "z": 4, "y": 8}
@@ -52,7 +55,7 @@ KERNEL_IDS = {
 # classes outside the EM path, added after tests/test_gpu_validity.py recorded its launch census over KERNEL_IDS (which
 # therefore stays as it is); Engine.timing / Engine.kernel_time_ms take names of either table
 KERNEL_IDS_EXTRA = {"posterior_sample": 23, "seed_states": 24, "loglik_proposal": 25, "loglik_lpj": 26, "loglik_fold": 27,
-                    "remap_latents": 28, "stats_kappa": 29, "sweep": 30}
+                    "remap_latents": 28, "stats_kappa": 29, "sweep": 30, "sweep_swap": 31}
 
 
 def kernel_id(name):
@@ -64,6 +67,14 @@ _c_i32p = ctypes.POINTER(ctypes.c_int32)
 _c_u64p = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p
 _I, _I64, _U64, _DBL = ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double
+
+
+
+class SweepOut(ctypes.Structure):
+    """evoamd_sweep_out: the outputs of the _nb sweep calls, each pointer may be NULL."""
+    _fields_ = [("score", _c_dp), ("best_flip", _c_i32p), ("gain", _c_dp), ("n_capped", _c_i32p),
+                ("best_swap", _c_i32p), ("swap_gain", _c_dp), ("n_capped_swap", _c_i32p)]
+
 
 # name -> (restype, argtypes); one entry per prototype in include/evo_amd.h
 SIGNATURES = {
@@ -107,6 +118,9 @@ SIGNATURES = {
     "evoamd_sweep_propose_ex": (_I, [_vp, _I, _I, ctypes.c_uint, _c_dp, _c_i32p, _c_dp, _c_i32p]),
     "evoamd_sweep_states_ex": (_I, [_vp, _I, _I, _I, _I, _I, ctypes.c_uint, _c_dp, ctypes.POINTER(_I), _c_i32p, _c_dp,
                                     _c_i32p]),
+    "evoamd_sweep_propose_nb": (_I, [_vp, _I, _I, ctypes.c_uint, ctypes.POINTER(SweepOut)]),
+    "evoamd_sweep_states_nb": (_I, [_vp, _I, _I, _I, _I, _I, ctypes.c_uint, _c_dp, ctypes.POINTER(_I),
+                                    ctypes.POINTER(SweepOut)]),
     "evoamd_posterior_scores": (_I, [_vp, _c_dp, _c_dp, _c_i32p, _c_i32p, _c_dp]),
     "evoamd_remap_latents": (_I, [_vp, _c_i32p, _I, _c_i32p, ctypes.POINTER(_I64)]),
     "evoamd_adopt_remapped_states": (_I, [_vp]),

@@ -37,6 +37,7 @@
 #include "kernels_loglik_estimate.hpp"
 #include "kernels_remap.hpp"
 #include "kernels_sweep.hpp"
+#include "kernels_sweep_swap.hpp"
 
 // ---------------------------------------------------------------------------------------
 // error handling
@@ -165,6 +166,7 @@ enum {  // internal kernel ids (see evoamd_kernel_name)
   KID_STATS_KAPPA,   // the ES3C statistics kernel on the kappa route (option "stats_kappa"), nested in KID_STATS: its launch count
                      // says which route a pass took
   KID_SWEEP,         // evoamd_sweep_propose / evoamd_sweep_states: the proposal kernel (ES3C: with the transpose of GP)
+  KID_SWEEP_SWAP,    // evoamd_sweep_*_nb with EVOAMD_SWEEP_SWAP: the swap proposal kernel
   KID_COUNT
 };
 
@@ -580,6 +582,9 @@ struct evoamd_ctx {
   // n_capped (N each).  Grown on demand.
   DevBuf<double> sweep_d;
   DevBuf<int> sweep_i;
+  // evoamd_sweep_*_nb with EVOAMD_SWEEP_SWAP: swap_gain (N); best_swap (N, 2) and n_capped_swap (N).  Grown on demand.
+  DevBuf<double> swap_d;
+  DevBuf<int> swap_i;
   // evoamd_remap_latents: K^n in the new latent numbering and its digests, [index (H_new) | n_replaced (N)] and the sum;
   // grown on demand, NOT sized by the geometry: they survive the configure between the remap and
   // evoamd_adopt_remapped_states, which swaps them in and releases them.  remap_H = 0: nothing to adopt.
@@ -933,6 +938,8 @@ static int set_kernel_lds_limits() {
   HIP_TRY(hipFuncSetAttribute((const void *)sweep_neighbours_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   HIP_TRY(hipFuncSetAttribute((const void *)sweep_neighbours_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   HIP_TRY(hipFuncSetAttribute((const void *)sweep_neighbours_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  HIP_TRY(hipFuncSetAttribute((const void *)sweep_swap_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  HIP_TRY(hipFuncSetAttribute((const void *)sweep_swap_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   {
     const void *wk[] = {(const void *)sssc_stats_wave_kernel<0, 4>,  (const void *)sssc_stats_wave_kernel<1, 4>,
                         (const void *)sssc_stats_wave_kernel<2, 4>,  (const void *)sssc_stats_wave_kernel<4, 4>,
@@ -5646,6 +5653,11 @@ struct SweepPlan {
   bool masked = false;
   int R = 0;              // masked ES3C: rows of G(n) per wavefront (SWEEP_ROWS)
   bool rows_lds = false;  // ... their home: LDS while one wavefront's share fits, else a buffer of the context
+  // the swap stage (evoamd_sweep_*_nb; kernels_sweep_swap.hpp): nb = the EVOAMD_SWEEP_SWAP / EVOAMD_SWEEP_NO_FLIP bits, 0 = flips only
+  unsigned nb = 0;
+  int swap_W = 4;
+  size_t swap_wave_bytes = 0;
+  unsigned swap_grid = 1;
 };
 
 static int sweep_check(const evoamd_ctx *c, int n_parents, int n_keep, unsigned flags, SweepPlan &p) {
@@ -5687,10 +5699,39 @@ static int sweep_check(const evoamd_ctx *c, int n_parents, int n_keep, unsigned 
   return 0;
 }
 
+// The checks of the _nb calls with a swap bit set: the flag rules, everything sweep_check refuses for complete data, the
+// quota of two stages and the swap kernel's share of LDS.
+static int sweep_check_nb(const evoamd_ctx *c, int n_parents, int n_keep, unsigned flags, SweepPlan &p) {
+  REQUIRE(c && c->configured, "configure first");
+  REQUIRE(!(flags & ~(unsigned)(EVOAMD_SWEEP_INCOMPLETE | EVOAMD_SWEEP_SWAP | EVOAMD_SWEEP_NO_FLIP)), "sweep: unknown flag");
+  REQUIRE((flags & EVOAMD_SWEEP_SWAP) || !(flags & EVOAMD_SWEEP_NO_FLIP),
+          "sweep: EVOAMD_SWEEP_NO_FLIP is valid only together with EVOAMD_SWEEP_SWAP");
+  REQUIRE(!(flags & EVOAMD_SWEEP_INCOMPLETE),
+          "sweep: EVOAMD_SWEEP_SWAP together with EVOAMD_SWEEP_INCOMPLETE: swaps on incomplete data are not supported");
+  TRY(sweep_check(c, n_parents, n_keep, 0u, p));
+  const bool both = !(flags & EVOAMD_SWEEP_NO_FLIP);
+  if (both && (i64)2 * n_parents * n_keep > c->Cmax)
+    return fail(EVOAMD_E_INVALID, "sweep: 2 * n_parents * n_keep = %lld (flips and swaps, n_keep rows per parent each) exceeds the "
+                                  "configured Cmax = %d", (long long)2 * n_parents * n_keep, c->Cmax);
+  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
+  p.swap_wave_bytes = sweep_swap_wave_bytes(sssc, (int)cdiv(c->H, 64) * 64, c->HW, n_keep, c->S);
+  REQUIRE(p.swap_wave_bytes <= 150 * 1024, "sweep: the keys of one datapoint (8 or 16 H bytes), the running lists of the swap stage "
+                                           "(32 n_keep bytes) and the held pairs (4 S bytes) do not fit one wavefront's share of LDS");
+  p.swap_W = 4;
+  while (p.swap_W > 1 && p.swap_W * p.swap_wave_bytes > 150 * 1024) p.swap_W >>= 1;
+  p.swap_grid = (unsigned)std::min<i64>(cdiv(c->N, p.swap_W), (i64)c->n_cu * 64);
+  p.nb = flags & (EVOAMD_SWEEP_SWAP | EVOAMD_SWEEP_NO_FLIP);
+  return 0;
+}
+
 // the buffers a sweep needs, B = Y W, (ES3C) the transpose of GP: once per call, Theta stays fixed
 static int sweep_prepare(evoamd_ctx *c, const SweepPlan &p) {
   const size_t N = (size_t)c->N;
   TRY(ensure_B(c));
+  if (p.nb) {
+    TRY(c->swap_d.ensure(c, N));
+    TRY(c->swap_i.ensure(c, 3 * N));
+  }
   if (p.R && !p.rows_lds) TRY(c->seed_rows.ensure(c, (size_t)p.grid * p.W * p.R * ((size_t)cdiv(c->H, 64) * 64)));
   TRY(c->sweep_d.ensure(c, N * c->Cmax + N));
   TRY(c->sweep_i.ensure(c, 2 * N));
@@ -5727,7 +5768,9 @@ static int sweep_propose_stage(evoamd_ctx *c, const SweepPlan &p, int n_parents,
     a.sd.W = c->W, a.sd.mask = c->mask_infr, a.sd.D = c->D, a.sd.R = p.R;
     a.sd.rows = p.R && !p.rows_lds ? c->seed_rows.get() : nullptr;
   }
-  {
+  if (want_score && (p.nb & EVOAMD_SWEEP_NO_FLIP))
+    HIP_TRY(hipMemsetAsync(c->sweep_d, 0xFF, N * c->Cmax * sizeof(double), c->stream));  // rows not emitted: NaN
+  if (!(p.nb & EVOAMD_SWEEP_NO_FLIP)) {
     SpanGuard g(c, KID_SWEEP);
     if (want_score) HIP_TRY(hipMemsetAsync(c->sweep_d, 0xFF, N * c->Cmax * sizeof(double), c->stream));  // rows not emitted: NaN
     if (p.masked && sssc)
@@ -5741,14 +5784,33 @@ static int sweep_propose_stage(evoamd_ctx *c, const SweepPlan &p, int n_parents,
     HIP_TRY(hipGetLastError());
     DBG_SYNC(c, "sweep proposals");
   }
+  if (p.nb & EVOAMD_SWEEP_SWAP) {  // the swap stage: its rows go behind the flip stage's
+    SweepSwapArgs b = {};
+    b.sw = a;
+    b.swap_gain = c->swap_d;
+    b.best_swap = c->swap_i, b.n_capped_swap = c->swap_i + 2 * N;
+    b.append = (p.nb & EVOAMD_SWEEP_NO_FLIP) ? 0 : 1;
+    SpanGuard g(c, KID_SWEEP_SWAP);
+    if (sssc)
+      sweep_swap_kernel<true><<<p.swap_grid, 64 * p.swap_W, p.swap_W * p.swap_wave_bytes, c->stream>>>(b);
+    else
+      sweep_swap_kernel<false><<<p.swap_grid, 64 * p.swap_W, p.swap_W * p.swap_wave_bytes, c->stream>>>(b);
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "sweep swap proposals");
+  }
   on_cand_installed(c, /*near_parents=*/false);
   TRY(eval_candidates(c));
   made_cand_lpj(c);
   return 0;
 }
 
-static int sweep_fetch(evoamd_ctx *c, double *score_out, int32_t *best_flip_out, double *gain_out, int32_t *n_capped_out) {
+static int sweep_fetch(evoamd_ctx *c, double *score_out, int32_t *best_flip_out, double *gain_out, int32_t *n_capped_out,
+                       int32_t *best_swap_out = nullptr, double *swap_gain_out = nullptr, int32_t *n_capped_swap_out = nullptr) {
   const size_t N = (size_t)c->N;
+  if (best_swap_out) HIP_TRY(hipMemcpyAsync(best_swap_out, c->swap_i, 2 * N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (swap_gain_out) HIP_TRY(hipMemcpyAsync(swap_gain_out, c->swap_d, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (n_capped_swap_out)
+    HIP_TRY(hipMemcpyAsync(n_capped_swap_out, c->swap_i + 2 * N, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   if (score_out) HIP_TRY(hipMemcpyAsync(score_out, c->sweep_d, N * c->Cmax * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (gain_out) HIP_TRY(hipMemcpyAsync(gain_out, c->sweep_d + N * c->Cmax, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (best_flip_out) HIP_TRY(hipMemcpyAsync(best_flip_out, c->sweep_i, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -5775,11 +5837,9 @@ extern "C" int evoamd_sweep_propose(evoamd_ctx *c, int n_parents, int n_keep, do
   return evoamd_sweep_propose_ex(c, n_parents, n_keep, 0u, score_out, best_flip_out, gain_out, n_capped_out);
 }
 
-extern "C" int evoamd_sweep_states_ex(evoamd_ctx *c, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
-                                      unsigned flags, double *trace_out, int *n_done_out, int32_t *best_flip_out,
-                                      double *gain_out, int32_t *n_capped_out) {
-  SweepPlan p;
-  TRY(sweep_check(c, n_parents, n_keep, flags, p));
+// the loop of evoamd_sweep_states_ex / evoamd_sweep_states_nb behind the plan's checks
+static int sweep_states_run(evoamd_ctx *c, const SweepPlan &p, int n_sweeps, int n_parents, int n_keep, int Mprime,
+                            int stop_when_quiet, double *trace_out, int *n_done_out, const evoamd_sweep_out &o) {
   TRY(estep_check_mprime(c, Mprime));
   REQUIRE(n_sweeps >= 1, "evoamd_sweep_states: n_sweeps must be positive");
   REQUIRE(trace_out && n_done_out, "evoamd_sweep_states: trace_out / n_done_out is NULL");
@@ -5808,7 +5868,49 @@ extern "C" int evoamd_sweep_states_ex(evoamd_ctx *c, int n_sweeps, int n_parents
     HIP_TRY(hipMemcpyAsync(trace_out + 3 * copied, c->refine_trace + 3 * copied, (size_t)3 * (done - copied) * sizeof(double),
                            hipMemcpyDeviceToHost, c->stream));
   *n_done_out = done;
-  return sweep_fetch(c, nullptr, best_flip_out, gain_out, n_capped_out);
+  const bool flips = !(p.nb & EVOAMD_SWEEP_NO_FLIP), swaps = (p.nb & EVOAMD_SWEEP_SWAP) != 0;
+  return sweep_fetch(c, nullptr, flips ? o.best_flip : nullptr, flips ? o.gain : nullptr, flips ? o.n_capped : nullptr,
+                     swaps ? o.best_swap : nullptr, swaps ? o.swap_gain : nullptr, swaps ? o.n_capped_swap : nullptr);
+}
+
+extern "C" int evoamd_sweep_states_ex(evoamd_ctx *c, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
+                                      unsigned flags, double *trace_out, int *n_done_out, int32_t *best_flip_out,
+                                      double *gain_out, int32_t *n_capped_out) {
+  SweepPlan p;
+  TRY(sweep_check(c, n_parents, n_keep, flags, p));
+  evoamd_sweep_out o = {};
+  o.best_flip = best_flip_out, o.gain = gain_out, o.n_capped = n_capped_out;
+  return sweep_states_run(c, p, n_sweeps, n_parents, n_keep, Mprime, stop_when_quiet, trace_out, n_done_out, o);
+}
+
+// The _nb calls: without a swap bit exactly the _ex calls; with one, the swap stage beside (or instead of) the flip stage.
+extern "C" int evoamd_sweep_propose_nb(evoamd_ctx *c, int n_parents, int n_keep, unsigned flags, const evoamd_sweep_out *out) {
+  const evoamd_sweep_out none = {};
+  const evoamd_sweep_out &o = out ? *out : none;
+  if (!(flags & (EVOAMD_SWEEP_SWAP | EVOAMD_SWEEP_NO_FLIP)))
+    return evoamd_sweep_propose_ex(c, n_parents, n_keep, flags, o.score, o.best_flip, o.gain, o.n_capped);
+  SweepPlan p;
+  TRY(sweep_check_nb(c, n_parents, n_keep, flags, p));
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(sweep_prepare(c, p));
+  on_estep_route(c, /*fused=*/false);
+  TRY(estep_resident_pass(c));
+  TRY(sweep_propose_stage(c, p, n_parents, n_keep, o.score != nullptr));
+  const bool flips = !(flags & EVOAMD_SWEEP_NO_FLIP);
+  return sweep_fetch(c, o.score, flips ? o.best_flip : nullptr, flips ? o.gain : nullptr, flips ? o.n_capped : nullptr, o.best_swap,
+                     o.swap_gain, o.n_capped_swap);
+}
+
+extern "C" int evoamd_sweep_states_nb(evoamd_ctx *c, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
+                                      unsigned flags, double *trace_out, int *n_done_out, const evoamd_sweep_out *out) {
+  const evoamd_sweep_out none = {};
+  const evoamd_sweep_out &o = out ? *out : none;
+  if (!(flags & (EVOAMD_SWEEP_SWAP | EVOAMD_SWEEP_NO_FLIP)))
+    return evoamd_sweep_states_ex(c, n_sweeps, n_parents, n_keep, Mprime, stop_when_quiet, flags, trace_out, n_done_out, o.best_flip,
+                                  o.gain, o.n_capped);
+  SweepPlan p;
+  TRY(sweep_check_nb(c, n_parents, n_keep, flags, p));
+  return sweep_states_run(c, p, n_sweeps, n_parents, n_keep, Mprime, stop_when_quiet, trace_out, n_done_out, o);
 }
 
 extern "C" int evoamd_sweep_states(evoamd_ctx *c, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
@@ -6341,6 +6443,6 @@ extern "C" const char *evoamd_kernel_name(int kid) {
                                          "stats_k3_4",   "stats_k5_8",     "stats_k9plus", "allreduce",    "estep_fused",
                                          "patches",      "init_states",    "posterior_sample", "seed_states",
                                          "loglik_proposal", "loglik_lpj",  "loglik_fold",     "remap_latents",
-                                         "stats_kappa",  "sweep"};
+                                         "stats_kappa",  "sweep",       "sweep_swap"};
   return (kid >= 0 && kid < KID_COUNT) ? names[kid] : "?";
 }

@@ -347,7 +347,28 @@ class Engine:
             int(check_every), int(patience), float(min_sub), dptr(trace), ctypes.byref(n_done)))
         return trace[:n_done.value], n_done.value
 
-    def sweep_propose(self, n_parents, n_keep, want_scores=True, incomplete=False):
+    def _sweep_nb_flags(self, neighbourhood, incomplete):
+        if neighbourhood not in _lib.SWEEP_NEIGHBOURHOODS:
+            raise ValueError("sweep: neighbourhood = %r must be one of 'flip', 'swap', 'both'" % (neighbourhood,))
+        return _lib.SWEEP_NEIGHBOURHOODS[neighbourhood] | (_lib.SWEEP_INCOMPLETE if incomplete else 0)
+
+    def _sweep_nb_out(self, neighbourhood, want_scores):
+        """The output arrays of an _nb sweep call and the evoamd_sweep_out that points at them."""
+        N, flips = self.N, neighbourhood != "swap"
+        res = {"score": np.empty((N, self.Cmax), dtype=np.float64) if want_scores else None,
+               "best_flip": np.empty(N, dtype=np.int32) if flips else None,
+               "gain": np.empty(N, dtype=np.float64) if flips else None,
+               "n_capped": np.empty(N, dtype=np.int32) if flips else None,
+               "best_swap": np.empty((N, 2), dtype=np.int32),
+               "swap_gain": np.empty(N, dtype=np.float64),
+               "n_capped_swap": np.empty(N, dtype=np.int32)}
+        out = _lib.SweepOut()
+        for name, a in res.items():
+            if a is not None:
+                setattr(out, name, dptr(a) if a.dtype == np.float64 else i32ptr(a))
+        return res, out
+
+    def sweep_propose(self, n_parents, n_keep, want_scores=True, incomplete=False, neighbourhood="flip"):
         """One sweep's proposals of the local search on K^n (evoamd_sweep_propose; csrc/kernels_sweep.hpp has the law,
         evo_amd.variational.sweep_states_host is the NumPy mirror): the resident rows are evaluated, every one-flip
         neighbour of the ``n_parents`` best states of each datapoint is scored, the ``n_keep`` best per parent that K^n
@@ -360,7 +381,19 @@ class Engine:
         or n_parents * n_keep > Cmax.  ``incomplete`` permits incomplete data (evoamd_sweep_propose_ex,
         EVOAMD_SWEEP_INCOMPLETE): with masks resident (upload_masks) every datapoint's neighbours are scored on its
         reliable entries, its Gram quantities formed from W and the mask (sweep_states_host with ``x_infr``); without masks
-        the flag changes nothing."""
+        the flag changes nothing.
+        ``neighbourhood``: "flip" (the call above), "swap" or "both" (evoamd_sweep_propose_nb; csrc/kernels_sweep_swap.hpp
+        has the law, evo_amd.variational.swap_states_host is the mirror): every swap of a parent -- one active latent a off,
+        one inactive latent j on -- that K^n does not hold is scored and the ``n_keep`` best per parent are appended behind
+        the flip rows ("both": 2 * n_parents * n_keep <= Cmax).  The dict gains "best_swap" int32 (N, 2) = (a, j) of the best
+        state's best scored swap or (-1, -1), "swap_gain" (N,) (-inf without one) and "n_capped_swap" int32 (N,), the
+        parents above the seeding cap, none of whose swaps is scored; with "swap" the three flip keys are None.  Swaps on
+        incomplete data (``incomplete`` or masks resident) are refused."""
+        if neighbourhood != "flip":
+            res, out = self._sweep_nb_out(neighbourhood, want_scores)
+            check(self.lib.evoamd_sweep_propose_nb(self._h, int(n_parents), int(n_keep),
+                                                   self._sweep_nb_flags(neighbourhood, incomplete), ctypes.byref(out)))
+            return res
         score = np.empty((self.N, self.Cmax), dtype=np.float64) if want_scores else None
         best = np.empty(self.N, dtype=np.int32)
         gain = np.empty(self.N, dtype=np.float64)
@@ -372,18 +405,28 @@ class Engine:
             check(self.lib.evoamd_sweep_propose(self._h, int(n_parents), int(n_keep), *out))
         return {"score": score, "best_flip": best, "gain": gain, "n_capped": capped}
 
-    def sweep_states(self, n_sweeps, n_parents=1, n_keep=None, Mprime=None, stop_when_quiet=True, incomplete=False):
+    def sweep_states(self, n_sweeps, n_parents=1, n_keep=None, Mprime=None, stop_when_quiet=True, incomplete=False,
+                     neighbourhood="flip"):
         """``n_sweeps`` x (sweep_propose, selection with ``Mprime``, default S) in one library call (evoamd_sweep_states):
         bit for bit what the separate calls give, the lpj rows stay those of the resident K^n.  ``n_keep`` None: Cmax //
         n_parents.  ``stop_when_quiet``: the loop ends after a sweep that swapped nothing.  Returns (trace (n_done, 3),
         n_done, certificate): row t = (Fs, new unique states, swapped states) of sweep t; the certificate is the dict of
         sweep_propose without "score", for the last sweep run (after a quiet one: the final K^n).  ``incomplete`` as for
-        sweep_propose (evoamd_sweep_states_ex)."""
+        sweep_propose (evoamd_sweep_states_ex).  ``neighbourhood`` as for sweep_propose (evoamd_sweep_states_nb): with
+        "both" ``n_keep`` None is Cmax // (2 n_parents), "quiet" means that neither stage's rows swapped anything in, and
+        the certificate gains the swap keys."""
         T = int(n_sweeps)
         P = int(n_parents)
-        q = self.Cmax // max(P, 1) if n_keep is None else int(n_keep)
+        q = self.Cmax // max(P * (2 if neighbourhood == "both" else 1), 1) if n_keep is None else int(n_keep)
         trace = np.zeros((max(T, 1), 3), dtype=np.float64)
         n_done = ctypes.c_int(0)
+        if neighbourhood != "flip":
+            res, out = self._sweep_nb_out(neighbourhood, False)
+            check(self.lib.evoamd_sweep_states_nb(
+                self._h, T, P, q, self.S if Mprime is None else int(Mprime), 1 if stop_when_quiet else 0,
+                self._sweep_nb_flags(neighbourhood, incomplete), dptr(trace), ctypes.byref(n_done), ctypes.byref(out)))
+            del res["score"]
+            return trace[:n_done.value], n_done.value, res
         best = np.empty(self.N, dtype=np.int32)
         gain = np.empty(self.N, dtype=np.float64)
         capped = np.empty(self.N, dtype=np.int32)

@@ -174,13 +174,18 @@ class RefineResult:
 class SweepResult:
     """What Model.sweep_resident_states returns: ``F``, ``S_nunique``, ``S_sub`` (n_done,) per sweep, ``n_done`` (the
     longest rank's), ``n_done_local`` (this rank's), ``stopped_early`` (n_done < the sweeps asked for) and, per datapoint of
-    this rank for the last sweep it ran, ``gain`` (N,), ``best_flip`` int32 (N,) and ``n_capped`` int32 (N,)."""
-    __slots__ = ("F", "S_nunique", "S_sub", "n_done", "n_done_local", "stopped_early", "gain", "best_flip", "n_capped")
+    this rank for the last sweep it ran, ``gain`` (N,), ``best_flip`` int32 (N,) and ``n_capped`` int32 (N,) of the flip
+    stage (None with neighbourhood="swap") and ``swap_gain`` (N,), ``best_swap`` int32 (N, 2) and ``n_capped_swap`` int32
+    (N,) of the swap stage (None with neighbourhood="flip")."""
+    __slots__ = ("F", "S_nunique", "S_sub", "n_done", "n_done_local", "stopped_early", "gain", "best_flip", "n_capped",
+                 "swap_gain", "best_swap", "n_capped_swap")
 
-    def __init__(self, F, S_nunique, S_sub, n_done, n_done_local, stopped_early, gain, best_flip, n_capped):
+    def __init__(self, F, S_nunique, S_sub, n_done, n_done_local, stopped_early, gain, best_flip, n_capped,
+                 swap_gain=None, best_swap=None, n_capped_swap=None):
         self.F, self.S_nunique, self.S_sub = F, S_nunique, S_sub
         self.n_done, self.n_done_local, self.stopped_early = int(n_done), int(n_done_local), bool(stopped_early)
         self.gain, self.best_flip, self.n_capped = gain, best_flip, n_capped
+        self.swap_gain, self.best_swap, self.n_capped_swap = swap_gain, best_swap, n_capped_swap
 
     def __repr__(self):
         return "SweepResult(n_done=%d, stopped_early=%s, F=%s)" % (
@@ -917,7 +922,7 @@ class Model:
                             n_local, n_done < T)
 
     def sweep_resident_states(self, model_params, my_suff_stat, my_data, n_sweeps=4, n_parents=1, n_keep=None,
-                              stop_when_quiet=True, incomplete=False):
+                              stop_when_quiet=True, incomplete=False, neighbourhood="flip"):
         """Local search on K^n while ``model_params`` stays fixed (Engine.sweep_states; csrc/kernels_sweep.hpp has the law,
         evo_amd.variational.sweep_states_host is the NumPy mirror): per sweep every one-flip neighbour of the
         ``n_parents`` best states of each datapoint is scored in the Gram form of the seeding kernel, the ``n_keep`` best
@@ -931,8 +936,21 @@ class Model:
         refine_resident_states.  sync_host as there.  ``incomplete=True`` admits my_data["x_infr"] with False entries
         (inpainting, imputation): the masks go up as for any E-step and every neighbour is scored on the datapoint's
         reliable entries alone -- values of y under False, NaN included, never enter.  ValueError for the background
-        unit and for incomplete data without ``incomplete=True``; NotImplementedError in the float32 mode."""
+        unit and for incomplete data without ``incomplete=True``; NotImplementedError in the float32 mode.
+        ``neighbourhood``: "flip" (the above), "swap" or "both" (csrc/kernels_sweep_swap.hpp has the law,
+        evo_amd.variational.swap_states_host is the mirror): the swaps of a parent -- one active latent off, one inactive
+        latent on, the move that one-flip search cannot make without a loss in between -- are scored too and the
+        ``n_keep`` best per parent that K^n does not hold follow the flip rows (``n_keep`` None with "both": Cmax //
+        (2 n_parents)).  The result gains ``swap_gain``, ``best_swap`` and ``n_capped_swap``; after a quiet sweep with
+        "both", ``gain`` <= 0 and ``swap_gain`` <= 0 certify that the best state has no better one-flip or swap neighbour
+        outside K^n.  Swaps on incomplete data are not supported: ValueError for ``incomplete=True`` with a swap
+        ``neighbourhood``."""
         T = int(n_sweeps)
+        if neighbourhood not in ("flip", "swap", "both"):
+            raise ValueError("sweep_resident_states: neighbourhood = %r must be one of 'flip', 'swap', 'both'" % (neighbourhood,))
+        if incomplete and neighbourhood != "flip":
+            raise ValueError("sweep_resident_states: incomplete=True with neighbourhood=%r: swaps on incomplete data are not "
+                             "supported" % (neighbourhood,))
         if T < 1:
             raise ValueError("sweep_resident_states: n_sweeps must be positive")
         if my_suff_stat["permanent"]["background"]:
@@ -948,9 +966,13 @@ class Model:
         if model_params is not self._dev_theta:
             self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
         P = int(n_parents)
-        trace, n_local, cert = eng.sweep_states(T, P, eng.Cmax // max(P, 1) if n_keep is None else int(n_keep),
-                                                my_suff_stat["Mprime"], stop_when_quiet=stop_when_quiet,
-                                                incomplete=bool(incomplete))
+        if neighbourhood == "flip":
+            trace, n_local, cert = eng.sweep_states(T, P, eng.Cmax // max(P, 1) if n_keep is None else int(n_keep),
+                                                    my_suff_stat["Mprime"], stop_when_quiet=stop_when_quiet,
+                                                    incomplete=bool(incomplete))
+        else:
+            trace, n_local, cert = eng.sweep_states(T, P, None if n_keep is None else int(n_keep), my_suff_stat["Mprime"],
+                                                    stop_when_quiet=stop_when_quiet, neighbourhood=neighbourhood)
         # rows of all T sweeps: {Fs, new unique, swapped, this rank still ran}; past this rank's end its last Fs
         rows = np.zeros((T, 4))
         rows[:n_local, :3] = trace
@@ -962,7 +984,8 @@ class Model:
         if self.sync_host:
             self.sync_to_host(my_suff_stat)
         return SweepResult(theta["ljc"] + rows[:n_done, 0] / N, rows[:n_done, 1] / N, rows[:n_done, 2] / N, n_done,
-                           n_local, n_done < T, cert["gain"], cert["best_flip"], cert["n_capped"])
+                           n_local, n_done < T, cert["gain"], cert["best_flip"], cert["n_capped"], cert.get("swap_gain"),
+                           cert.get("best_swap"), cert.get("n_capped_swap"))
 
     def posterior_scores(self, model_params, my_suff_stat, my_data):
         """Per-datapoint scores of this rank's data under ``model_params`` and the caller's K^n / lpj: a dict with the

@@ -457,6 +457,104 @@ def sweep_states_host(model, theta, Y, ss, lpj, S_perm, n_parents, n_keep, x_inf
     return cand, counts, scores, best_flip, gain, n_capped, margin
 
 
+# ---- local search on K^n, the swap neighbourhood: the NumPy mirror of the swap stage (csrc/kernels_sweep_swap.hpp has the law)
+def swap_states_host(model, theta, Y, ss, lpj, S_perm, n_parents, n_keep):
+    """One sweep's swap proposals as evoamd_sweep_propose_nb emits them with EVOAMD_SWEEP_SWAP | EVOAMD_SWEEP_NO_FLIP (with
+    both stages on they follow the rows of sweep_states_host).  ``ss`` bool (N, S, H) and ``lpj`` (N, S_perm + S) are taken
+    as given; the parents are those of sweep_states_host.  Every swap of a parent p -- a in p switched off, j not in p
+    switched on -- is scored with the model's lpj (no ljc, no clamp) unless K^n holds that state; a parent above
+    SEED_MAX_ACTIVE latents has none of its swaps scored and counts in n_capped_swap, an empty parent has no swaps.  Per
+    parent the ``n_keep`` = q best (descending score, ties by ascending a, then ascending j; scores that are not finite are
+    never proposed) are emitted parent-major, then by rank.  Complete data only.  Returns (cand bool (N, P q, H), counts
+    int32 (N,), scores (N, P q) -- NaN beyond counts --, best_swap int32 (N, 2), swap_gain (N,), n_capped_swap int32 (N,),
+    margin (N,)): best_swap / swap_gain describe the best scored swap of parent 0 ((-1, -1) / -inf without one), margin is
+    the smallest relative gap (a - b) / max(1, |a|) between consecutive chosen ranks and between rank q - 1 and rank q
+    over the datapoint's parents, as in sweep_states_host."""
+    sssc = model not in ("bsc", "BSC", "ebsc")
+    assert S_perm in (0, 1)
+    W = np.asarray(theta["W"], dtype=np.float64)
+    Y = np.asarray(Y, dtype=np.float64)
+    ss = np.asarray(ss, dtype=bool)
+    lpj = np.asarray(lpj, dtype=np.float64)
+    (D, H), (N, S) = W.shape, ss.shape[:2]
+    assert Y.shape == (N, D) and ss.shape == (N, S, H) and lpj.shape == (N, S_perm + S)
+    P, q = int(n_parents), int(n_keep)
+    if not (1 <= P <= min(S, 64)) or q < 1:
+        raise ValueError("swap_states: n_parents = %d must be in [1, min(S = %d, 64)] and n_keep = %d positive" % (P, S, q))
+    cap = SEED_MAX_ACTIVE["sssc" if sssc else "bsc"]
+    G, B, yy = W.T @ W, Y @ W, (Y * Y).sum(axis=1)
+    if sssc:
+        mus, Psi = np.asarray(theta["mus"], dtype=np.float64), np.asarray(theta["Psi"], dtype=np.float64)
+        pies = np.asarray(theta["pies"], dtype=np.float64)
+        pil_bar, s2inv = np.log(pies / (1.0 - pies)), 1.0 / float(theta["sigma2"])
+    else:
+        pi, sigma = float(theta["pi"]), float(theta["sigma"])
+        pre1, pil_bar = -1.0 / 2.0 / sigma / sigma, np.log(pi / (1.0 - pi))
+        Gd = np.diag(G).copy()
+    cand = np.zeros((N, P * q, H), dtype=bool)
+    counts = np.zeros(N, dtype=np.int32)
+    scores = np.full((N, P * q), np.nan)
+    best_swap = np.full((N, 2), -1, dtype=np.int32)
+    swap_gain = np.full(N, -np.inf)
+    n_capped_swap = np.zeros(N, dtype=np.int32)
+    margin = np.full(N, np.inf)
+    for n in range(N):
+        row = np.where(np.isfinite(lpj[n, S_perm:]), lpj[n, S_perm:], -np.inf) + 0.0
+        parents = np.lexsort((np.arange(S), -row))[:P]
+        for r, slot in enumerate(parents):
+            p = ss[n, slot]
+            act = np.flatnonzero(p)
+            m = len(act)
+            if m > cap:
+                n_capped_swap[n] += 1
+                continue
+            if m == 0:
+                continue
+            # (b) the swaps K^n holds: two differing bits, one in p and one outside
+            diff = ss[n] ^ p
+            two = (diff.sum(axis=1) == 2) & ((diff & p).sum(axis=1) == 1)
+            held = np.zeros((H, H), dtype=bool)
+            held[np.argmax(diff[two] & p, axis=1), np.argmax(diff[two] & ~p, axis=1)] = True
+            free = np.flatnonzero(~p)
+            if sssc:
+                base = float(_seed_scores_sssc(G, Psi, mus, pil_bar, s2inv, B[n], yy[n], list(act[:-1]), act[-1:])[0])
+            else:
+                c = B[n] - G[act].sum(axis=0)
+                base = pre1 * (yy[n] - (B[n, act] + c[act]).sum()) + m * pil_bar
+            sa, sj, sc = [], [], []
+            for a in act:  # ascending a, then ascending j
+                js = free[~held[a, free]]
+                if len(js) == 0:
+                    continue
+                if sssc:
+                    s = _seed_scores_sssc(G, Psi, mus, pil_bar, s2inv, B[n], yy[n], list(act[act != a]), js)
+                else:
+                    with np.errstate(invalid="ignore", over="ignore"):
+                        base_a = base - pil_bar + pre1 * (Gd[a] + 2.0 * c[a])
+                        caj = c[js] + G[a, js]
+                        s = base_a + pil_bar + pre1 * (Gd[js] - 2.0 * caj)
+                ok = np.isfinite(s)
+                sa.append(np.full(ok.sum(), a)), sj.append(js[ok]), sc.append(s[ok])
+            if not sc:
+                continue
+            sa, sj, sc = np.concatenate(sa), np.concatenate(sj), np.concatenate(sc)
+            order = np.lexsort((sj, sa, -sc))
+            sa, sj, rs = sa[order], sj[order], sc[order]
+            k = min(q, len(rs))
+            for i in range(k):
+                if i + 1 < len(rs):
+                    margin[n] = min(margin[n], _seed_gap(rs[i], rs[i + 1]))
+                at = counts[n] + i
+                cand[n, at] = p
+                cand[n, at, sa[i]] = False
+                cand[n, at, sj[i]] = True
+                scores[n, at] = rs[i]
+            counts[n] += k
+            if r == 0 and k:
+                best_swap[n], swap_gain[n] = (sa[0], sj[0]), rs[0] - base
+    return cand, counts, scores, best_swap, swap_gain, n_capped_swap, margin
+
+
 def posterior_scores_host(lpj, ss=None, S_perm=0):
     """NumPy mirror of Engine.posterior_scores (csrc/kernels_refine.hpp): ``lpj`` (N, L) with L = S_perm + S columns,
     ``ss`` bool (N, S, H) the states of columns S_perm .. L - 1 (columns below S_perm are the permanent all-zero

@@ -423,6 +423,37 @@ int evoamd_sweep_propose_ex(evoamd_ctx *ctx, int n_parents, int n_keep, unsigned
 int evoamd_sweep_states_ex(evoamd_ctx *ctx, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
                            unsigned flags, double *trace_out, int *n_done_out, int32_t *best_flip_out, double *gain_out,
                            int32_t *n_capped_out);
+/* The swap neighbourhood beside the one-flip one (csrc/kernels_sweep_swap.hpp has the law;
+ * evo_amd.variational.swap_states_host is the NumPy mirror): one active latent a of a parent switched off and one inactive
+ * latent j switched on, every pair (a, j) scored with the model's lpj unless K^n holds that state (an exact test on the
+ * packed words) or the parent exceeds the seeding cap (ES3C 8, EBSC 64 active latents: none of its swaps is scored); per
+ * parent the n_keep best (descending score, ties by ascending a, then ascending j) are appended behind the rows of the
+ * flip stage, parent-major, then by rank.  Flags: EVOAMD_SWEEP_SWAP scores swaps too, EVOAMD_SWEEP_NO_FLIP (valid only
+ * together with it) leaves the flip stage out; with neither bit the _nb calls are exactly the _ex calls.  With both
+ * stages on each gets up to n_keep rows per parent and 2 * n_parents * n_keep <= Cmax is required, with one stage
+ * n_parents * n_keep <= Cmax.  Outputs, each (and out itself) may be NULL: score, best_flip, gain, n_capped as above
+ * (the three of the flip stage are not written with EVOAMD_SWEEP_NO_FLIP); from the best parent best_swap (N, 2) = (a, j) of
+ * its best scored swap or (-1, -1) and swap_gain (N) that score minus the parent's own, -inf without a scored swap;
+ * n_capped_swap (N) the parents above the cap.  After a quiet sweep with both stages on, gain <= 0 and swap_gain <= 0
+ * certify that the best state of K^n has no better one-flip or swap neighbour outside K^n.  In the loop call "quiet" means
+ * that the sweep swapped nothing into K^n.  Refusals, before anything is written: everything the calls above refuse,
+ * EVOAMD_SWEEP_SWAP together with EVOAMD_SWEEP_INCOMPLETE or with masks resident (swaps on incomplete data are not
+ * supported), EVOAMD_SWEEP_NO_FLIP without EVOAMD_SWEEP_SWAP, the quota rule, and an LDS share that does not fit.  No atomics,
+ * fixed summation order: two calls give the same bits. */
+#define EVOAMD_SWEEP_SWAP 2u
+#define EVOAMD_SWEEP_NO_FLIP 4u
+typedef struct evoamd_sweep_out {
+  double *score;          /* (N, Cmax) */
+  int32_t *best_flip;     /* (N) */
+  double *gain;           /* (N) */
+  int32_t *n_capped;      /* (N) */
+  int32_t *best_swap;     /* (N, 2) */
+  double *swap_gain;      /* (N) */
+  int32_t *n_capped_swap; /* (N) */
+} evoamd_sweep_out;
+int evoamd_sweep_propose_nb(evoamd_ctx *ctx, int n_parents, int n_keep, unsigned flags, const evoamd_sweep_out *out);
+int evoamd_sweep_states_nb(evoamd_ctx *ctx, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
+                           unsigned flags, double *trace_out, int *n_done_out, const evoamd_sweep_out *out);
 
 /* Per-datapoint scores of the lpj rows and K^n resident on the device (after a seed, an upload or any pass), each output
  * (N) or NULL.  With m = max_s lpj_ns, w_s = exp(lpj_ns - m), z = sum_s w_s over the S_perm + S columns:
@@ -844,7 +875,8 @@ enum {
   EVOAMD_K_REMAP = 28,         /* evoamd_remap_latents: the remap kernel (index upload and downloads excluded) */
   EVOAMD_K_STATS_KAPPA = 29,   /* the ES3C statistics kernel on the kappa route (option "stats_kappa"), nested in EVOAMD_K_STATS */
   EVOAMD_K_SWEEP = 30,         /* evoamd_sweep_propose / evoamd_sweep_states: the proposal kernel (ES3C: with the transpose of GP) */
-  EVOAMD_K_COUNT = 31
+  EVOAMD_K_SWEEP_SWAP = 31,    /* evoamd_sweep_*_nb with EVOAMD_SWEEP_SWAP: the swap proposal kernel */
+  EVOAMD_K_COUNT = 32
 };
 /* on = bit mask of kernel classes to time (bit k = class k; -1 = all, 0 = off).  Each timed span
  * records two HIP events on the compute stream, which costs about 10 us of stream time per span:
