@@ -76,6 +76,29 @@ class SweepOut(ctypes.Structure):
                 ("best_swap", _c_i32p), ("swap_gain", _c_dp), ("n_capped_swap", _c_i32p)]
 
 
+_I32 = ctypes.c_int32
+
+
+class DenseDesc(ctypes.Structure):
+    """evoamd_dense_desc: one call of the test-only evoamd_dense_probe."""
+    _fields_ = [("op", _I32), ("M", _I32), ("Nc", _I32), ("K", _I64), ("lda", _I32), ("ldb", _I32), ("ldc", _I32),
+                ("lda2", _I32), ("ldct", _I32), ("off_a", _I32), ("off_b", _I32), ("off_c", _I32), ("same_operand", _I32),
+                ("deterministic", _I32), ("sym_row0", _I32), ("c_is_zero", _I32), ("accumulate", _I32), ("mirror", _I32),
+                ("spare", _I32), ("diag", _I32), ("guard", _I32)]
+
+
+class DenseRoute(ctypes.Structure):
+    """evoamd_dense_route: what the dense launcher chose."""
+    _fields_ = [("route", _I32), ("tile", _I32), ("splits", _I32), ("J", _I32), ("wpx", _I32), ("segmax", _I32),
+                ("ws", _I32), ("n_cu", _I32)]
+
+
+DENSE_OPS = ("tn", "tn_f32", "nn", "rows", "rows_f32", "colsum", "colsum_sq")  # EVOAMD_DENSE_*
+DENSE_ROUTES = ("none", "gram_small", "tn64_scalar", "tn64_vec", "tn128_split", "tn128_streamk", "tn128_grouped",
+                "f32_streamk", "f32_grouped", "f32_naive", "nn_small", "nn_vec", "nn_scalar", "rows", "rows_f32_store",
+                "rows_f32_naive", "colsum")  # EVOAMD_ROUTE_*
+
+
 # name -> (restype, argtypes); one entry per prototype in include/evo_amd.h
 SIGNATURES = {
     "evoamd_abi_version": (_I, []),
@@ -135,6 +158,7 @@ SIGNATURES = {
     "evoamd_lpj_single_masked": (_I, [_vp, _c_dp, _c_u8p, _c_u8p, _I, _c_dp, _c_i32p]),
     "evoamd_inverse": (_I, [_vp, _c_dp, _c_dp, _I, _c_dp]),
     "evoamd_gemm_tn": (_I, [_vp, _c_dp, _c_dp, _c_dp, _I64, _I, _I, _I]),
+    "evoamd_dense_probe": (_I, [_vp, ctypes.POINTER(DenseDesc), _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(DenseRoute)]),
     "evoamd_get_params_bsc": (_I, [_vp, _c_dp, _c_dp, _c_dp]),
     "evoamd_get_params_sssc": (_I, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "evoamd_restore_theta_backup": (_I, [_vp]),

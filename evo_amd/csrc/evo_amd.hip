@@ -382,6 +382,7 @@ struct evoamd_ctx {
   int theta_gen = 0;        // stamp of the current Theta (one per sssc_tables_kernel launch)
   int gemm_grouped = 1;  // option "gemm_grouped": grouped split-K instead of stream-K where whole chunks fill the grid
   int gemm_per_xcd = 0;  // option "gemm_per_xcd" (experiments): K chunks per XCD of the 128-tile contraction, 0 = automatic
+  evoamd_dense_route route = {};  // what the last dense launcher chose (one host store per call; evoamd_dense_probe returns it)
   double *census = nullptr;  // view: 4 doubles at the head of acc_base, overflow census of the earlier blocks of a chunked statistics pass
   i64 pre_n = 4;
   hipEvent_t ev_chunk[16] = {};
@@ -866,6 +867,7 @@ static inline size_t list_cap(i64 total) { return (size_t)(256 * (((total + 255)
 template <bool SQUARE>
 static void launch_colsum(evoamd_ctx *c, const double *X, int ldx, i64 R, int Cn, double *out) {
   const i64 rpb = 256;
+  c->route = {EVOAMD_ROUTE_COLSUM, 64, (int)cdiv(R, rpb), 0, 0, 0, 0, 0};
   dim3 grid(cdiv(Cn, 64), cdiv(R, rpb));
   colsum_f64<SQUARE><<<grid, 256, 0, c->stream>>>(X, ldx, R, Cn, rpb, out);
 }
@@ -1771,18 +1773,22 @@ extern "C" int evoamd_download_lpj(evoamd_ctx *c, double *lpj) {
 // ---------------------------------------------------------------------------------------
 // 16-byte row pieces need an even leading dimension and a 16-byte aligned base
 static bool gemm_vec_ok(const double *p, int ld) { return (ld % 2) == 0 && ((uintptr_t)p % 16) == 0; }
+static bool gemm_vec_ok_f32(const float *p, int ld) { return (ld % 4) == 0 && ((uintptr_t)p % 16) == 0; }
 
 // Ct / ldct: C^T as well where the parameter-sized kernel runs; returns whether it was written
 static bool launch_gemm_nn_raw(evoamd_ctx *c, const double *A, int lda, const double *B, int ldb, double *C, int ldc,
                                i64 M, int Nc, int K, double *Ct = nullptr, int ldct = 0) {
   if (M <= 1024 && Nc <= 1024 && K <= 1024) {  // parameter-sized: one wave per 16 x 16 block
+    c->route = {EVOAMD_ROUTE_NN_SMALL, 16, 1, 0, 0, 0, 0, 0};
     gemm_nn_small_kernel<<<dim3(cdiv(Nc, 16), cdiv(M, 16)), 256, 0, c->stream>>>(A, lda, B, ldb, C, ldc, (int)M, Nc, K, Ct, ldct);
     return Ct != nullptr;
   }
   const int gx = (int)cdiv(Nc, GEMM_BN), gy = (int)cdiv(M, GEMM_BM);
   const int rows_per_xcd = (gy + 7) / 8;
   const unsigned grid = (unsigned)(8 * rows_per_xcd * gx);
-  if (gemm_vec_ok(A, lda) && gemm_vec_ok(B, ldb) && (K % 2) == 0 && (Nc % 2) == 0 && K >= 2 && Nc >= 2 && M >= 1)
+  const bool vec = gemm_vec_ok(A, lda) && gemm_vec_ok(B, ldb) && (K % 2) == 0 && (Nc % 2) == 0 && K >= 2 && Nc >= 2 && M >= 1;
+  c->route = {vec ? EVOAMD_ROUTE_NN_VEC : EVOAMD_ROUTE_NN_SCALAR, GEMM_BM, 1, 0, 0, 0, 0, 0};
+  if (vec)
     gemm_nn_f64<true><<<grid, 256, 0, c->stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, gx, gy, rows_per_xcd);
   else
     gemm_nn_f64<false><<<grid, 256, 0, c->stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, gx, gy, rows_per_xcd);
@@ -1826,6 +1832,7 @@ static int launch_gemm_tn(evoamd_ctx *c, const double *A, int lda, const double 
     // G = W^T W of the Theta update: one wave per 16 x 16 block (gram_small_kernel)
     SpanGuard g(c, KID_GEMM, stream);
     const int nb16 = (int)cdiv(M, 16);
+    c->route = {EVOAMD_ROUTE_GRAM_SMALL, 16, 1, 0, 0, 0, 0, 0};
     gram_small_kernel<<<dim3(nb16, nb16), 256, 0, stream>>>(A, lda, (int)K, M, C, ldc, o.diag);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1885,10 +1892,17 @@ static int launch_gemm_tn(evoamd_ctx *c, const double *A, int lda, const double 
   if (split) {
     kps = (K + splits - 1) / splits;
     kps = ((kps + GEMM_BK - 1) / GEMM_BK) * GEMM_BK;
-    if (!c_is_zero && !accumulate) HIP_TRY(hipMemsetAsync(C, 0, (size_t)M * ldc * sizeof(double), stream));
+    if (!c_is_zero && !accumulate) {
+      // the product's own M x Nc region only: the columns Nc .. ldc of a wider C belong to the caller
+      if (ldc == Nc)
+        HIP_TRY(hipMemsetAsync(C, 0, (size_t)M * ldc * sizeof(double), stream));
+      else
+        HIP_TRY(hipMemset2DAsync(C, (size_t)ldc * sizeof(double), 0, (size_t)Nc * sizeof(double), (size_t)M, stream));
+    }
   }
   const unsigned grid = (unsigned)(tiles * (split ? splits : 1));
   SpanGuard g(c, KID_GEMM, stream);
+  if (!big) c->route = {vec ? EVOAMD_ROUTE_TN64_VEC : EVOAMD_ROUTE_TN64_SCALAR, T, (int)splits, 0, 0, 0, 0, 0};
   if (big && split && c->gemm_streamk) {
     // stream-K: one resident-sized grid, every XCD owns an eighth of K (option "gemm_streamk")
     i64 real = tiles;
@@ -1904,7 +1918,9 @@ static int launch_gemm_tn(evoamd_ctx *c, const double *A, int lda, const double 
     // grouped split-K (gemm_f64.hpp): when whole chunks per tile fill the resident grid (>= 93 % of its slots) and a
     // chunk is long enough for the pipeline ramp
     const i64 J = (i64)8 * wpx / real;
-    if (ws && c->gemm_grouped && J >= 2 && real * J * 100 >= (i64)8 * wpx * 93 && K / J >= 256) {
+    const bool grouped = ws && c->gemm_grouped && J >= 2 && real * J * 100 >= (i64)8 * wpx * 93 && K / J >= 256;
+    c->route = {grouped ? EVOAMD_ROUTE_TN128_GROUPED : EVOAMD_ROUTE_TN128_STREAMK, T, (int)splits, (int)J, (int)wpx, segmax, ws != nullptr, 0};
+    if (grouped) {
       const i64 Kc = ((cdiv(K, J) + 2 * GEMM_BK - 1) / (2 * GEMM_BK)) * (2 * GEMM_BK);  // whole slab pairs: no padding slab, mask-free drain
       gemm_tn128_gk<double><<<8 * wpx, 256, GEMM128_LDS_BYTES, stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, Kc, gx, gy,
                                                                             sym_row0, (int)real, (int)J, ws);
@@ -1917,9 +1933,10 @@ static int launch_gemm_tn(evoamd_ctx *c, const double *A, int lda, const double 
       gemm_sk_reduce_kernel<<<dim3((unsigned)real, GEMM_T * GEMM_T / 256), 256, 0, stream>>>(
           ws, segmax, C, ldc, M, Nc, K, Kx, gx, gy, sym_row0, (int)real, (int)wpx);
     }
-  } else if (big)
+  } else if (big) {
+    c->route = {EVOAMD_ROUTE_TN128_SPLIT, T, (int)splits, 0, 0, 0, 0, 0};
     gemm_tn128_f64<<<grid, 256, GEMM128_LDS_BYTES, stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, kps, gx, gy, split, sym_row0);
-  else if (vec)
+  } else if (vec)
     gemm_tn_f64<true><<<grid, 256, 0, stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, kps, gx, gy, split, sym_row0);
   else
     gemm_tn_f64<false><<<grid, 256, 0, stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, kps, gx, gy, split, sym_row0);
@@ -1942,14 +1959,23 @@ static int launch_gemm_nn(evoamd_ctx *c, const double *A, int lda, const double 
 // ---------------------------------------------------------------------------------------
 static int launch_B_f32(evoamd_ctx *c);
 
+// C (M x Nc) = At^T B with the whole K per 128 x 128 tile: At (K x M) and B (K x Nc) are read in 16-byte pieces, so both
+// need an even leading dimension, a 16-byte aligned base and (B) an even Nc; M may be odd when lda is rounded up past it
+// (the piece across column M - 1 stays inside the row, the row it feeds is never stored).
+static void launch_rows_f64(evoamd_ctx *c, const double *At, int lda, const double *B, int ldb, double *C, int ldc, int M,
+                            int Nc, i64 K) {
+  const int gx = (int)cdiv(Nc, GEMM_T), gy = (int)cdiv(M, GEMM_T);
+  c->route = {EVOAMD_ROUTE_ROWS, GEMM_T, 1, 0, 0, 0, 0, 0};
+  gemm_tn128_rows_f64<<<(unsigned)(8 * cdiv(gy, 8) * gx), 256, GEMM128_LDS_BYTES, c->stream>>>(At, lda, B, ldb, C, ldc, M, Nc,
+                                                                                                K, gx, gy);
+}
+
 // B = Y W (N x H): float32 mode, or from Y^T on the 128-tile kernel (large N), or the 64-tile row-major product
 static int launch_B(evoamd_ctx *c) {
   if (c->f32) return launch_B_f32(c);
   if (!c->Yt) return launch_gemm_nn(c, c->Y, c->ldY, c->W, c->H, c->Bm, c->H, c->N, c->H, c->D);
   SpanGuard g(c, KID_GEMM);
-  const int gx = (int)cdiv(c->H, GEMM_T), gy = (int)cdiv(c->N, GEMM_T);
-  gemm_tn128_rows_f64<<<(unsigned)(8 * cdiv(gy, 8) * gx), 256, GEMM128_LDS_BYTES, c->stream>>>(
-      c->Yt, (int)c->ldYt, c->W, c->H, c->Bm, c->H, (int)c->N, c->H, c->D, gx, gy);
+  launch_rows_f64(c, c->Yt, (int)c->ldYt, c->W, c->H, c->Bm, c->H, (int)c->N, c->H, c->D);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -2087,14 +2113,16 @@ static int launch_gemm_tn_f32(evoamd_ctx *c, const float *A, int lda, const floa
                               i64 K, const GemmTnOpts &o = GemmTnOpts()) {
   const hipStream_t stream = o.stream ? o.stream : c->stream;
   SpanGuard g(c, KID_GEMM, stream);
-  if (M >= 128 && Nc >= 128 && K >= 2048 && (M % 4) == 0 && (Nc % 4) == 0) {
+  if (M >= 128 && Nc >= 128 && K >= 2048 && (M % 4) == 0 && (Nc % 4) == 0 && gemm_vec_ok_f32(A, lda) && gemm_vec_ok_f32(B, ldb)) {
     const int gx = (int)cdiv(Nc, GEMM_T), gy = (int)cdiv(M, GEMM_T);
     const i64 Kx = ((cdiv(K, 8) + GEMM_BK - 1) / GEMM_BK) * GEMM_BK;
     const unsigned wpx = (unsigned)std::max(1, 2 * c->n_cu / 8 - o.spare);
     int segmax = 0;
     double *ws = c->gemm_ws_opt ? streamk_workspace(c, wpx, (i64)gx * gy, &segmax) : nullptr;
     const i64 real = (i64)gx * gy, J = (i64)8 * wpx / real;
-    if (ws && c->gemm_grouped && J >= 2 && real * J * 100 >= (i64)8 * wpx * 93 && K / J >= 256) {  // see launch_gemm_tn
+    const bool grouped = ws && c->gemm_grouped && J >= 2 && real * J * 100 >= (i64)8 * wpx * 93 && K / J >= 256;  // see launch_gemm_tn
+    c->route = {grouped ? EVOAMD_ROUTE_F32_GROUPED : EVOAMD_ROUTE_F32_STREAMK, GEMM_T, 8, (int)J, (int)wpx, segmax, ws != nullptr, 0};
+    if (grouped) {
       const i64 Kc = ((cdiv(K, J) + 2 * GEMM_BK - 1) / (2 * GEMM_BK)) * (2 * GEMM_BK);
       gemm_tn128_gk<float><<<8 * wpx, 256, GEMM128_LDS_BYTES, stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K, Kc, gx, gy, -1,
                                                                            (int)real, (int)J, ws);
@@ -2108,24 +2136,34 @@ static int launch_gemm_tn_f32(evoamd_ctx *c, const float *A, int lda, const floa
             ws, segmax, C, ldc, M, Nc, K, Kx, gx, gy, -1, gx * gy, (int)wpx);
     }
   } else {
+    c->route = {EVOAMD_ROUTE_F32_NAIVE, 0, 1, 0, 0, 0, 0, 0};
     gemm_tn_naive_f32<<<cdiv((i64)M * Nc, 256), 256, 0, stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K);
   }
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
+// C (M x Nc float) = A B from the transposed copy At (K x M) on the f32 matrix cores where the 128-tile store kernel can
+// read 16-byte pieces (leading dimensions multiples of 4, 16-byte aligned bases, Nc a multiple of 4: a piece of B that
+// straddles column Nc - 1 would run into the next row, behind the last row out of the buffer), else one thread per
+// element from the row-major A (M x K).
+static void launch_rows_f32(evoamd_ctx *c, const float *At, int ldat, const float *A, int lda, const float *B, int ldb,
+                            float *C, int ldc, i64 M, int Nc, int K) {
+  if (Nc >= 128 && M >= 128 && (Nc % 4) == 0 && gemm_vec_ok_f32(At, ldat) && gemm_vec_ok_f32(B, ldb)) {
+    const int gx = (int)cdiv(Nc, GEMM_T), gy = (int)cdiv(M, GEMM_T);
+    c->route = {EVOAMD_ROUTE_ROWS_F32_STORE, GEMM_T, 1, 0, 0, 0, 0, 0};
+    gemm_tn128_store_f32<<<(unsigned)gx * gy, 256, GEMM128_LDS_BYTES, c->stream>>>(At, ldat, B, ldb, C, ldc, (int)M, Nc, K, gx);
+  } else {
+    c->route = {EVOAMD_ROUTE_ROWS_F32_NAIVE, 0, 1, 0, 0, 0, 0, 0};
+    gemm_nn_naive_f32<<<cdiv(M * (i64)Nc, 256), 256, 0, c->stream>>>(A, lda, B, ldb, C, ldc, M, Nc, K);
+  }
+}
+
 // float32 mode: Wf <- W, then Bf = Y W as (Y^T)^T Wf on the f32 matrix cores (whole K = D per 128 x 128 tile)
 static int launch_B_f32(evoamd_ctx *c) {
   SpanGuard g(c, KID_GEMM);
   to_f32_kernel<<<cdiv((i64)c->D * c->H, 256), 256, 0, c->stream>>>(c->W, c->H, c->D, c->H, c->Wf, c->H);
-  if (c->H >= 128 && c->N >= 128) {
-    const int gx = (int)cdiv(c->H, GEMM_T), gy = (int)cdiv(c->N, GEMM_T);
-    gemm_tn128_store_f32<<<(unsigned)gx * gy, 256, GEMM128_LDS_BYTES, c->stream>>>(c->Ytf, (int)c->ldYt, c->Wf, c->H, c->Bf,
-                                                                                  c->H, (int)c->N, c->H, c->D, gx);
-  } else {
-    gemm_nn_naive_f32<<<cdiv(c->N * (i64)c->H, 256), 256, 0, c->stream>>>(c->Yf, c->D, c->Wf, c->H, c->Bf, c->H, c->N, c->H,
-                                                                           c->D);
-  }
+  launch_rows_f32(c, c->Ytf, (int)c->ldYt, c->Yf, c->D, c->Wf, c->H, c->Bf, c->H, c->N, c->H, c->D);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -4909,6 +4947,105 @@ extern "C" int evoamd_gemm_tn(evoamd_ctx *c, const double *A, const double *B, d
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return fail(EVOAMD_E_HIP, "evoamd_gemm_tn: %s", hipGetErrorString(e));
   return r;
+}
+
+// One padded operand of evoamd_dense_probe on the device: `off` elements, guard rows, the logical rows, guard rows.
+struct ProbeBuf {
+  DevBuf<double> d;  // (16-byte aligned; holds floats as well)
+  size_t bytes = 0;
+  int up(const void *h, size_t off, size_t rows, size_t ld, int guard, size_t elem, hipStream_t s) {
+    bytes = (off + (rows + 2 * (size_t)guard) * ld) * elem;
+    TRY(d.alloc((bytes + 7) / 8));
+    HIP_TRY(hipMemcpyAsync(d.get(), h, bytes, hipMemcpyHostToDevice, s));
+    return 0;
+  }
+  int down(void *h, hipStream_t s) const {
+    HIP_TRY(hipMemcpyAsync(h, d.get(), bytes, hipMemcpyDeviceToHost, s));
+    return 0;
+  }
+  template <typename T>
+  T *base(size_t off, size_t ld, int guard) const {
+    return (T *)d.get() + off + (size_t)guard * ld;
+  }
+};
+
+extern "C" int evoamd_dense_probe(evoamd_ctx *c, const evoamd_dense_desc *d, const void *A, const void *B, const void *A2,
+                                  void *C, void *side, evoamd_dense_route *route) {
+  REQUIRE(c && d && A && C, "evoamd_dense_probe: bad arguments");
+  const int op = d->op, M = d->M, Nc = d->Nc, g = d->guard;
+  const i64 K = d->K;
+  REQUIRE(op >= EVOAMD_DENSE_TN && op <= EVOAMD_DENSE_COLSUM_SQ, "evoamd_dense_probe: unknown op");
+  REQUIRE(M > 0 && Nc > 0 && K > 0 && g >= 0 && d->off_a >= 0 && d->off_b >= 0 && d->off_c >= 0, "evoamd_dense_probe: bad shape");
+  const bool colsum = op == EVOAMD_DENSE_COLSUM || op == EVOAMD_DENSE_COLSUM_SQ;
+  const bool nn = op == EVOAMD_DENSE_NN;
+  const bool f32 = op == EVOAMD_DENSE_TN_F32 || op == EVOAMD_DENSE_ROWS_F32;
+  const bool same = d->same_operand != 0;
+  const size_t ea = f32 ? sizeof(float) : sizeof(double);
+  const size_t ec = op == EVOAMD_DENSE_ROWS_F32 ? sizeof(float) : sizeof(double);
+  const i64 rowsA = nn ? M : K, colsA = nn ? K : M, rowsC = colsum ? 1 : M, colsC = colsum ? M : Nc;
+  REQUIRE(d->lda >= colsA && d->ldc >= colsC && K <= INT32_MAX, "evoamd_dense_probe: a leading dimension is shorter than its row");
+  REQUIRE(colsum || same || (B && d->ldb >= Nc), "evoamd_dense_probe: B");
+  REQUIRE(!same || (op == EVOAMD_DENSE_TN && M == Nc), "evoamd_dense_probe: same_operand is the Gram route of op TN");
+  REQUIRE(d->sym_row0 < 0 || (d->sym_row0 + Nc == M), "sym_row0: the symmetric block must be the last Nc rows of C");
+  REQUIRE(op != EVOAMD_DENSE_ROWS_F32 || (A2 && d->lda2 >= K), "evoamd_dense_probe: ROWS_F32 needs the row-major A2");
+  REQUIRE(!(nn && d->ldct > 0) || (side && d->ldct >= M), "evoamd_dense_probe: Ct");
+  REQUIRE(!d->diag || (op == EVOAMD_DENSE_TN && side), "evoamd_dense_probe: diag");
+  HIP_TRY(hipSetDevice(c->device));
+  const hipStream_t s = c->stream;
+  ProbeBuf bA, bB, bA2, bC, bS;
+  TRY(bA.up(A, d->off_a, rowsA, d->lda, g, ea, s));
+  if (!colsum && !same) TRY(bB.up(B, d->off_b, K, d->ldb, g, ea, s));
+  if (op == EVOAMD_DENSE_ROWS_F32) TRY(bA2.up(A2, 0, M, d->lda2, g, ea, s));
+  TRY(bC.up(C, d->off_c, rowsC, d->ldc, g, ec, s));
+  const bool want_ct = nn && d->ldct > 0;
+  if (want_ct) TRY(bS.up(side, 0, Nc, d->ldct, g, sizeof(double), s));
+  if (d->diag) TRY(bS.up(side, 0, M, 1, g, sizeof(double), s));
+  c->route = {};
+  int r = 0;
+  if (op == EVOAMD_DENSE_TN) {
+    GemmTnOpts o;
+    o.deterministic = d->deterministic != 0;
+    o.sym_row0 = d->sym_row0;
+    o.c_is_zero = d->c_is_zero != 0;
+    o.accumulate = d->accumulate != 0;
+    o.mirror = d->mirror != 0;
+    o.spare = d->spare;
+    o.diag = d->diag ? bS.base<double>(0, 1, g) : nullptr;
+    const double *pa = bA.base<double>(d->off_a, d->lda, g);
+    const double *pb = same ? pa : bB.base<double>(d->off_b, d->ldb, g);
+    r = launch_gemm_tn(c, pa, d->lda, pb, same ? d->lda : d->ldb, bC.base<double>(d->off_c, d->ldc, g), d->ldc, M, Nc, K, o);
+  } else if (op == EVOAMD_DENSE_TN_F32) {
+    GemmTnOpts o;
+    o.spare = d->spare;
+    r = launch_gemm_tn_f32(c, bA.base<float>(d->off_a, d->lda, g), d->lda, bB.base<float>(d->off_b, d->ldb, g), d->ldb,
+                           bC.base<double>(d->off_c, d->ldc, g), d->ldc, M, Nc, K, o);
+  } else if (nn) {
+    launch_gemm_nn_raw(c, bA.base<double>(d->off_a, d->lda, g), d->lda, bB.base<double>(d->off_b, d->ldb, g), d->ldb,
+                       bC.base<double>(d->off_c, d->ldc, g), d->ldc, M, Nc, (int)K, want_ct ? bS.base<double>(0, d->ldct, g) : nullptr,
+                       d->ldct);
+  } else if (op == EVOAMD_DENSE_ROWS) {
+    const double *pa = bA.base<double>(d->off_a, d->lda, g), *pb = bB.base<double>(d->off_b, d->ldb, g);
+    REQUIRE(gemm_vec_ok(pa, d->lda) && gemm_vec_ok(pb, d->ldb) && (Nc % 2) == 0,
+            "evoamd_dense_probe: ROWS reads 16-byte pieces (even ld, aligned bases, even Nc: what evoamd_configure grants)");
+    launch_rows_f64(c, pa, d->lda, pb, d->ldb, bC.base<double>(d->off_c, d->ldc, g), d->ldc, M, Nc, K);
+  } else if (op == EVOAMD_DENSE_ROWS_F32) {
+    launch_rows_f32(c, bA.base<float>(d->off_a, d->lda, g), d->lda, bA2.base<float>(0, d->lda2, g), d->lda2,
+                    bB.base<float>(d->off_b, d->ldb, g), d->ldb, bC.base<float>(d->off_c, d->ldc, g), d->ldc, M, Nc, (int)K);
+  } else if (op == EVOAMD_DENSE_COLSUM) {
+    launch_colsum<false>(c, bA.base<double>(d->off_a, d->lda, g), d->lda, K, M, bC.base<double>(d->off_c, d->ldc, g));
+  } else {
+    launch_colsum<true>(c, bA.base<double>(d->off_a, d->lda, g), d->lda, K, M, bC.base<double>(d->off_c, d->ldc, g));
+  }
+  if (r) return r;
+  HIP_TRY(hipGetLastError());
+  TRY(bC.down(C, s));
+  if (want_ct || d->diag) TRY(bS.down(side, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (route) {
+    *route = c->route;
+    route->n_cu = c->n_cu;
+  }
+  return 0;
 }
 
 extern "C" int evoamd_inverse(evoamd_ctx *c, double *A, double *B, int n, double *timing_ms) {

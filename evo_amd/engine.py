@@ -552,6 +552,44 @@ class Engine:
                                       int(sym_row0)))
         return C
 
+    def dense_probe(self, op, A, B, C, M, Nc, K, lda, ldb=0, ldc=0, A2=None, lda2=0, side=None, ldct=0, off_a=0, off_b=0,
+                    off_c=0, same_operand=False, deterministic=False, sym_row0=-1, c_is_zero=False, accumulate=False,
+                    mirror=True, spare=0, diag=False, guard=0):
+        """TEST-ONLY (evoamd_dense_probe): one launch of a dense kernel through the launcher the hot path calls.  ``op`` is
+        a name of _lib.DENSE_OPS; A, B, A2, C and side are whole padded 1-D buffers (``off`` elements, ``guard`` rows, the
+        logical rows, ``guard`` rows, each ``ld`` long; float32 for the operands of the f32 ops and the C of rows_f32).
+        Returns (C, side, route): copies of the two output buffers after the call and the launcher's route record as a
+        dict (``route`` by its name in _lib.DENSE_ROUTES)."""
+        o = _lib.DENSE_OPS.index(op)
+        f32 = op in ("tn_f32", "rows_f32")
+        ta, tc = (np.float32 if f32 else np.float64), (np.float32 if op == "rows_f32" else np.float64)
+        colsum, nn = op.startswith("colsum"), op == "nn"
+
+        def buf(x, dtype, off, rows, ld):
+            x = np.ascontiguousarray(x, dtype=dtype)
+            assert x.ndim == 1 and x.size == off + (rows + 2 * guard) * ld, (op, x.shape, off, rows, ld, guard)
+            return x
+
+        A = buf(A, ta, off_a, M if nn else K, lda)
+        B = None if colsum or same_operand else buf(B, ta, off_b, K, ldb)
+        A2 = buf(A2, ta, 0, M, lda2) if op == "rows_f32" else None
+        C = buf(C, tc, off_c, 1 if colsum else M, ldc).copy()
+        if nn and ldct > 0:
+            side = buf(side, np.float64, 0, Nc, ldct).copy()
+        elif diag:
+            side = buf(side, np.float64, 0, M, 1).copy()
+        else:
+            side = None
+        d = _lib.DenseDesc(o, M, Nc, K, lda, ldb, ldc, lda2, ldct, off_a, off_b, off_c, int(same_operand),
+                           int(deterministic), int(sym_row0), int(c_is_zero), int(accumulate), int(mirror), int(spare),
+                           int(diag), guard)
+        r = _lib.DenseRoute()
+        vp = lambda x: None if x is None else x.ctypes.data_as(ctypes.c_void_p)
+        check(self.lib.evoamd_dense_probe(self._h, ctypes.byref(d), vp(A), vp(B), vp(A2), vp(C), vp(side), ctypes.byref(r)))
+        route = {name: int(getattr(r, name)) for name, _ in _lib.DenseRoute._fields_}
+        route["route"] = _lib.DENSE_ROUTES[route["route"]]
+        return C, side, route
+
     def get_params_bsc(self):
         W = np.empty((self.D, self.H))
         pi, sigma = ctypes.c_double(), ctypes.c_double()

@@ -540,6 +540,60 @@ int evoamd_inverse(evoamd_ctx *ctx, double *A, double *B, int n, double *timing_
  * parity tests (the long-K tile variants only run at sizes no oracle fixture reaches). */
 int evoamd_gemm_tn(evoamd_ctx *ctx, const double *A, const double *B, double *C, int64_t K, int M, int Nc,
                    int sym_row0);
+/* TEST-ONLY: one dense kernel launch through the launcher the hot path calls, with the strides, base alignments and
+ * options the real callers use (tests/test_gpu_dense.py; DESIGN "Dense probe").  Every operand is a whole padded host
+ * buffer: `off` elements, then `guard` rows, the logical rows, `guard` rows, each row `ld` elements long; the probe
+ * uploads all of it, passes base = buffer + off + guard * ld, and downloads all of C (and of `side`), so the caller
+ * sees every element the kernel could have touched near its operands.
+ *   op TN        C (M x Nc) = A^T B, A (K x M), B (K x Nc) double           -- launch_gemm_tn, every GemmTnOpts field;
+ *                same_operand: B is A (the Gram route); diag != 0: `side` is diag(C), guard + M + guard doubles
+ *      TN_F32    the same with float A, B and double C                      -- launch_gemm_tn_f32 (reads spare)
+ *      NN        C (M x Nc) = A B, A (M x K)                                -- launch_gemm_nn_raw; ldct > 0: `side` is
+ *                C^T, (guard + Nc + guard) x ldct (written by the parameter-sized kernel only)
+ *      ROWS      C (M x Nc) = A^T B, whole K per 128-tile, plain stores     -- the B = Y W launch from Y^T
+ *      ROWS_F32  the same in float; A2 (M x K, lda2) is the row-major copy the one-thread-per-element form reads
+ *      COLSUM / COLSUM_SQ  C (1 x M) += column sums (of squares) of A (K x M) -- launch_colsum
+ * route (may be NULL) receives what the launcher recorded: which kernel, tile, K splits, grouped chunks J, workgroups
+ * per XCD, workspace slabs per workgroup, whether the workspace was used, and the device's compute units. */
+#define EVOAMD_DENSE_TN 0
+#define EVOAMD_DENSE_TN_F32 1
+#define EVOAMD_DENSE_NN 2
+#define EVOAMD_DENSE_ROWS 3
+#define EVOAMD_DENSE_ROWS_F32 4
+#define EVOAMD_DENSE_COLSUM 5
+#define EVOAMD_DENSE_COLSUM_SQ 6
+#define EVOAMD_ROUTE_NONE 0
+#define EVOAMD_ROUTE_GRAM_SMALL 1
+#define EVOAMD_ROUTE_TN64_SCALAR 2
+#define EVOAMD_ROUTE_TN64_VEC 3
+#define EVOAMD_ROUTE_TN128_SPLIT 4
+#define EVOAMD_ROUTE_TN128_STREAMK 5
+#define EVOAMD_ROUTE_TN128_GROUPED 6
+#define EVOAMD_ROUTE_F32_STREAMK 7
+#define EVOAMD_ROUTE_F32_GROUPED 8
+#define EVOAMD_ROUTE_F32_NAIVE 9
+#define EVOAMD_ROUTE_NN_SMALL 10
+#define EVOAMD_ROUTE_NN_VEC 11
+#define EVOAMD_ROUTE_NN_SCALAR 12
+#define EVOAMD_ROUTE_ROWS 13
+#define EVOAMD_ROUTE_ROWS_F32_STORE 14
+#define EVOAMD_ROUTE_ROWS_F32_NAIVE 15
+#define EVOAMD_ROUTE_COLSUM 16
+typedef struct evoamd_dense_desc {
+  int32_t op;
+  int32_t M, Nc;
+  int64_t K;
+  int32_t lda, ldb, ldc, lda2, ldct;
+  int32_t off_a, off_b, off_c; /* elements in front of each padded buffer: an odd one takes the base off 16 bytes */
+  int32_t same_operand;
+  int32_t deterministic, sym_row0, c_is_zero, accumulate, mirror, spare, diag;
+  int32_t guard;
+} evoamd_dense_desc;
+typedef struct evoamd_dense_route {
+  int32_t route, tile, splits, J, wpx, segmax, ws, n_cu;
+} evoamd_dense_route;
+int evoamd_dense_probe(evoamd_ctx *ctx, const evoamd_dense_desc *d, const void *A, const void *B, const void *A2,
+                       void *C, void *side, evoamd_dense_route *route);
 /* Current parameters of the context back to the host (after evoamd_mstep_device). */
 int evoamd_get_params_bsc(evoamd_ctx *ctx, double *W, double *pi, double *sigma);
 int evoamd_get_params_sssc(evoamd_ctx *ctx, double *W, double *pies, double *mus, double *Psi,
