@@ -119,6 +119,7 @@ SIGNATURES = {
     "evoamd_init_states": (_I, [_vp, _DBL, _U64, _I, _c_u8p]),
     "evoamd_seed_states": (_I, [_vp, _I, _c_i32p, _c_dp]),
     "evoamd_seed_states_ex": (_I, [_vp, _I, ctypes.c_uint, _c_i32p, _c_dp]),
+    "evoamd_seed_states_beam": (_I, [_vp, _I, _I, _c_i32p, _c_dp]),
     "evoamd_upload_lpj": (_I, [_vp, _c_dp]),
     "evoamd_download_lpj": (_I, [_vp, _c_dp]),
     "evoamd_set_params_bsc": (_I, [_vp, _c_dp, _DBL, _DBL, _c_dp]),

@@ -33,6 +33,7 @@
 #include "kernels_predictive.hpp"
 #include "kernels_posterior_sample.hpp"
 #include "kernels_seed.hpp"
+#include "kernels_seed_beam.hpp"
 #include "kernels_refine.hpp"
 #include "kernels_loglik_estimate.hpp"
 #include "kernels_remap.hpp"
@@ -934,6 +935,8 @@ static int set_kernel_lds_limits() {
   HIP_TRY(hipFuncSetAttribute((const void *)remap_latents_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, REMAP_LDS_BYTES));
   HIP_TRY(hipFuncSetAttribute((const void *)seed_states_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   HIP_TRY(hipFuncSetAttribute((const void *)seed_states_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  HIP_TRY(hipFuncSetAttribute((const void *)seed_states_beam_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  HIP_TRY(hipFuncSetAttribute((const void *)seed_states_beam_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   HIP_TRY(hipFuncSetAttribute((const void *)seed_states_masked_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   HIP_TRY(hipFuncSetAttribute((const void *)seed_states_masked_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
   HIP_TRY(hipFuncSetAttribute((const void *)sweep_neighbours_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
@@ -5686,18 +5689,17 @@ extern "C" int evoamd_download_predictive(evoamd_ctx *c, double *mean, double *v
 // K^n seeded by greedy forward selection on the model's lpj (kernels_seed.hpp).  Every refusal comes before the first write.
 // EVOAMD_SEED_INCOMPLETE is a permission: with masks resident the masked kernel runs (the datapoint's own Gram rows from W
 // and the mask), without masks the complete kernel, whatever the flag says.
-extern "C" int evoamd_seed_states_ex(evoamd_ctx *c, int max_active, unsigned flags, int32_t *path_out, double *lpj_out) {
-  REQUIRE(c && c->configured, "configure first");
+// seed_admit: what the greedy call and the beam call (evoamd_seed_states_beam) refuse alike, with one text each;
+// masks_refusal: the caller's text for resident masks, nullptr when it admits them.
+static int seed_admit(evoamd_ctx *c, int max_active, const char *masks_refusal) {
   REQUIRE(c->have_params, "evoamd_seed_states: no Theta installed (set parameters first)");
   REQUIRE(c->have_data, "evoamd_seed_states: no data (upload data first)");
-  REQUIRE(!(flags & ~(unsigned)EVOAMD_SEED_INCOMPLETE), "evoamd_seed_states_ex: unknown flag");
-  REQUIRE(!c->mask_infr || (flags & EVOAMD_SEED_INCOMPLETE),
-          "evoamd_seed_states: incomplete data (masks present) is not supported (evoamd_seed_states_ex with EVOAMD_SEED_INCOMPLETE)");
+  REQUIRE(!c->mask_infr || !masks_refusal, masks_refusal);
   REQUIRE(!c->bg_unit, "evoamd_seed_states: option background_unit is not supported");
   REQUIRE(!c->f32, "evoamd_seed_states is not available in the float32 mode (ebsc_f32)");
   const bool sssc = c->model == EVOAMD_MODEL_SSSC;
   REQUIRE(sssc || !c->bsc_direct, "evoamd_seed_states: bsc_direct keeps no G = W^T W, which the scores need");
-  const int S = c->S, H = c->H, HW = c->HW, A = max_active;
+  const int S = c->S, H = c->H, A = max_active;
   const int cap = sssc ? SEED_MAX_A_SSSC : SEED_MAX_A_BSC;
   if (A < 1 || A > S || A > H || A > cap)
     return fail(EVOAMD_E_INVALID, "evoamd_seed_states: max_active = %d must be in [1, min(S = %d, H = %d, %d)] (%s)", A, S, H,
@@ -5709,6 +5711,18 @@ extern "C" int evoamd_seed_states_ex(evoamd_ctx *c, int max_active, unsigned fla
       return fail(EVOAMD_E_INVALID, "evoamd_seed_states: the quota q_%d = %d exceeds the H - (t - 1) = %d latents left at step %d "
                   "(S = %d, max_active = %d)", t, q, H - (t - 1), t, S, A);
   }
+  return 0;
+}
+
+extern "C" int evoamd_seed_states_ex(evoamd_ctx *c, int max_active, unsigned flags, int32_t *path_out, double *lpj_out) {
+  REQUIRE(c && c->configured, "configure first");
+  // (a missing Theta or missing data is named before an unknown flag)
+  REQUIRE(!(flags & ~(unsigned)EVOAMD_SEED_INCOMPLETE) || !c->have_params || !c->have_data, "evoamd_seed_states_ex: unknown flag");
+  TRY(seed_admit(c, max_active, (flags & EVOAMD_SEED_INCOMPLETE) ? nullptr : "evoamd_seed_states: incomplete data (masks present) "
+                 "is not supported (evoamd_seed_states_ex with EVOAMD_SEED_INCOMPLETE)"));
+  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
+  const int S = c->S, H = c->H, HW = c->HW, A = max_active;
+  const int q_lo = S / A, q_rem = S % A;
   const int Hp = (int)cdiv(H, 64) * 64, Q = q_lo + (q_rem ? 1 : 0);
   const bool masked = c->mask_infr != nullptr;
   const int D = c->D, R = masked && sssc ? A : 0;  // ES3C, masked: the winners' rows of G(n) and its diagonal
@@ -5774,6 +5788,74 @@ extern "C" int evoamd_seed_states_ex(evoamd_ctx *c, int max_active, unsigned fla
 
 extern "C" int evoamd_seed_states(evoamd_ctx *c, int max_active, int32_t *path_out, double *lpj_out) {
   return evoamd_seed_states_ex(c, max_active, 0u, path_out, lpj_out);
+}
+
+// K^n seeded by a beam of partial states (kernels_seed_beam.hpp has the law).  Complete data only; every refusal comes before
+// the first write.
+extern "C" int evoamd_seed_states_beam(evoamd_ctx *c, int max_active, int beam, int32_t *path_out, double *lpj_out) {
+  REQUIRE(c && c->configured, "configure first");
+  TRY(seed_admit(c, max_active, "evoamd_seed_states_beam: incomplete data (masks present) is not supported: beam seeding is "
+                 "for complete data"));
+  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
+  const int S = c->S, H = c->H, HW = c->HW, A = max_active, B = beam;
+  if (B < 1 || B > S / A || B > SEED_BEAM_MAX)
+    return fail(EVOAMD_E_INVALID, "evoamd_seed_states_beam: beam = %d must be in [1, min(S / max_active = %d, %d)] (every beam "
+                "member is a stored state; SEED_BEAM_MAX = %d)", B, S / A, SEED_BEAM_MAX, SEED_BEAM_MAX);
+  const int q_lo = S / A, q_rem = S % A;
+  const int Hp = (int)cdiv(H, 64) * 64, Q = q_lo + (q_rem ? 1 : 0);
+  const size_t wave_bytes = seed_beam_wave_bytes(Hp, HW, Q, A, B);
+  if (wave_bytes > 150 * 1024)
+    return fail(EVOAMD_E_INVALID, "evoamd_seed_states_beam: the keys of one datapoint and the two beams (H = %d, beam = %d: %zu "
+                "bytes) do not fit one wavefront's share of LDS", H, B, wave_bytes);
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(ensure_B(c));
+  const size_t n_out = (size_t)c->N * A;
+  const size_t out_bytes = ((n_out * sizeof(int) + 7) / 8) * 8;
+  if (path_out || lpj_out) TRY(c->stage.ensure(c, out_bytes + n_out * sizeof(double)));
+  if (sssc) TRY(c->seed_gpt.ensure(c, (size_t)H * H));
+  int W = 4;
+  while (W > 1 && W * wave_bytes > 150 * 1024) W >>= 1;
+  const unsigned grid = (unsigned)std::min<i64>(cdiv(c->N, W), (i64)c->n_cu * 64);
+  SeedBeamArgs b;
+  SeedArgs &a = b.sd;
+  a.states = c->states;
+  a.dig = c->dig;
+  a.Bm = c->Bm;
+  a.yy = c->yy;
+  a.G = c->G;
+  a.Gd = c->diag;
+  a.GP = c->GP;
+  a.mus = c->mus;
+  a.pil_bar = c->pilbar_v;
+  a.GPt = c->seed_gpt;
+  a.dpar = c->dpar;
+  a.path = path_out ? (int *)c->stage.get() : nullptr;
+  a.lpj_path = lpj_out ? (double *)(c->stage.get() + out_bytes) : nullptr;
+  a.err = c->err;
+  a.N = c->N;
+  a.S = S, a.H = H, a.HW = HW, a.A = A, a.Hp = Hp, a.Q = Q;
+  a.W = nullptr;
+  a.mask = nullptr;
+  a.rows = nullptr;
+  a.D = c->D, a.R = 0;
+  b.B = B;
+  on_kn_changed(c, KN_BY_CALLER);
+  {
+    SpanGuard g(c, KID_SEED_STATES);
+    if (sssc) {
+      seed_transpose_gp_kernel<<<cdiv((i64)H * H, 256), 256, 0, c->stream>>>(c->GP, H, c->seed_gpt);
+      seed_states_beam_kernel<true><<<grid, 64 * W, W * wave_bytes, c->stream>>>(b);
+    } else {
+      seed_states_beam_kernel<false><<<grid, 64 * W, W * wave_bytes, c->stream>>>(b);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  DBG_SYNC(c, "seed_states_beam");
+  if (path_out) HIP_TRY(hipMemcpyAsync(path_out, a.path, n_out * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (lpj_out) HIP_TRY(hipMemcpyAsync(lpj_out, a.lpj_path, n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  on_kn_complete(c);
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -158,6 +158,22 @@ class Engine:
             check(self.lib.evoamd_seed_states(self._h, A, pp, lp))
         return (path, lpj) if want_path else None
 
+    def seed_states_beam(self, max_active, beam, want_path=False):
+        """K^n seeded on the device by a beam of partial states (evoamd_seed_states_beam;
+        evo_amd.variational.seed_states_beam_host is its NumPy mirror): the law of seed_states with the ``beam`` best
+        partial states kept per step and all of them expanded; ``beam`` = 1 is seed_states bit for bit.  Complete data
+        only.  ``want_path``: returns (path int32 (N, max_active), the path of the rank-0 state of the last step, and
+        lpj_path (N, max_active), the rank-0 score of each step), else None.  EvoAmdError naming the rule, with K^n left
+        as it was, for everything seed_states refuses, resident masks, ``beam`` < 1, > S // max_active or > 16."""
+        A = int(max_active)
+        path = lpj = None
+        if want_path:
+            path = np.empty((self.N, max(A, 1)), dtype=np.int32)
+            lpj = np.empty((self.N, max(A, 1)), dtype=np.float64)
+        pp, lp = (i32ptr(path), dptr(lpj)) if want_path else (None, None)
+        check(self.lib.evoamd_seed_states_beam(self._h, A, int(beam), pp, lp))
+        return (path, lpj) if want_path else None
+
     # ---- samples from the model ------------------------------------------------------------
     def generate(self, model, N, seed, Wt, pies, mus=None, F=None, sigma=1.0, first_index=0, s=None,
                  keep=("s", "z", "y_mean")):

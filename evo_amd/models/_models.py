@@ -353,7 +353,7 @@ class Model:
 
     def seed_resident_states(self, model_params, my_data, parent_selection, mutation_algorithm, no_parents, no_children,
                              no_generations, max_active=None, bitflip_prob=None, Mprime=None, permanent=None,
-                             want_path=False, incomplete=False):
+                             want_path=False, incomplete=False, beam=None):
         """``init_states`` for this rank's ``my_data`` with K^n SEEDED on the device from ``model_params`` and the data
         (Engine.seed_states; evo_amd.variational.seed_states_host is the NumPy mirror): greedy forward selection on the
         model's own lpj, deterministic -- the start for codes, reconstructions, predictive moments or samples from a
@@ -366,20 +366,31 @@ class Model:
         with False entries (inpainting, imputation): the masks go up as for any E-step and every datapoint is seeded on
         its reliable entries alone -- values of y under False, NaN included, never enter.  ValueError for incomplete
         data without ``incomplete=True``, the background unit and a ``max_active`` the law refuses; NotImplementedError
-        in the float32 mode."""
-        from ..variational.utils import seed_quotas
+        in the float32 mode.
+        ``beam`` None: the greedy law above.  An integer B >= 1: the beam law (Engine.seed_states_beam;
+        evo_amd.variational.seed_states_beam_host is its mirror) -- the B best partial states are kept per step and all
+        of them expanded, which on correlated dictionaries finds states a single greedy path misses; B = 1 is the greedy
+        law bit for bit; self.last_seed_path then holds the path of the last step's best state and the best score of each
+        step.  Complete data only: ValueError naming ``beam`` with ``incomplete=True`` or incomplete data, and for a B
+        outside [1, min(S // max_active, 16)]."""
+        from ..variational.utils import seed_beam_check, seed_quotas
         N, H = my_data["y"].shape[0], self.H
         permanent = permanent or {"background": False, "allzero": False, "singletons": False}
         if permanent["background"]:
             raise ValueError("seed_resident_states: the background unit is not supported")
         if self.dtype == np.float32:
             raise NotImplementedError("seed_resident_states is not available in the float32 mode")
+        if beam is not None and (incomplete or not self._complete(my_data)):
+            raise ValueError("seed_resident_states: beam is for complete data only (no incomplete=True, no x_infr with "
+                             "False entries)")
         if not incomplete and not self._complete(my_data):
             raise ValueError("seed_resident_states: incomplete data (x_infr with False entries) is not supported "
                              "by default: pass incomplete=True")
         if max_active is None:
             max_active = min(8, self.S, H)
         seed_quotas(self.S, H, max_active, self.model_name != "bsc")
+        if beam is not None:
+            seed_beam_check(self.S, max_active, beam)
         S_perm = 1 if (permanent["allzero"] == 1 and permanent["singletons"] == 0) else 0
         if Mprime is None:
             Mprime = self.S
@@ -392,7 +403,10 @@ class Model:
         self.E_step_precompute(dict(model_params), dict(suff), my_data)
         if model_params is not self._dev_theta:
             self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
-        self.last_seed_path = eng.seed_states(max_active, want_path=want_path, incomplete=bool(incomplete))
+        if beam is None:
+            self.last_seed_path = eng.seed_states(max_active, want_path=want_path, incomplete=bool(incomplete))
+        else:
+            self.last_seed_path = eng.seed_states_beam(max_active, beam, want_path=want_path)
         self._resident = True
         eng.lpj_resident()
         if self.sync_host:

@@ -352,6 +352,96 @@ def seed_states_host(model, theta, Y, S, max_active, S_perm=0, x_infr=None):
     return states, path, lpj_path, margin
 
 
+# ---- beam seeding: the NumPy mirror of evoamd_seed_states_beam (csrc/kernels_seed_beam.hpp has the law) --------------------
+SEED_BEAM_MAX = 16
+
+
+def seed_beam_check(S, max_active, beam):
+    """ValueError naming ``beam`` unless 1 <= beam <= min(S // max_active, SEED_BEAM_MAX) (every beam member is a stored
+    state)."""
+    B, top = int(beam), int(S) // int(max_active)
+    if B < 1 or B > top or B > SEED_BEAM_MAX:
+        raise ValueError("seed_states: beam = %d must be in [1, min(S // max_active = %d, %d)]" % (B, top, SEED_BEAM_MAX))
+    return B
+
+
+def seed_states_beam_host(model, theta, Y, S, max_active, beam, S_perm=0):
+    """K^n as evoamd_seed_states_beam / Model.seed_resident_states(beam=B) lay it out: the law of seed_states_host with the
+    ``beam`` = B best partial states kept per step (rank order) and all of them expanded.  A member carries its path, and
+    its candidates P_r + {j} are scored in the arithmetic of that path (EBSC: c = B_n - G_{w_1} - ... in path order and
+    score = lpj(P_r) + pil_bar + pre1 (G_jj - 2 c_j) with lpj(P_r) the score the member was ranked with; ES3C: the system in
+    path order).  A candidate whose set an earlier parent reaches as well is absent (a test on the sets, never on scores);
+    all candidates of a step are ranked by descending score, ties by ascending parent rank, then ascending j; the q_t best
+    fill the step's slots in rank order and the first B of them are the next beam.  B = 1 is seed_states_host exactly.
+    Complete data only.  Returns (states bool (N, S, H), lpj (N, S) the score every slot was ranked with, path int32 (N, A)
+    the path of the rank-0 state of the last step, lpj_path (N, A) the rank-0 score of each step, margin (N,)): margin is
+    the smallest relative gap (_seed_gap) between any two adjacent ranks among the first max(q_t, B) + 1 ranked candidates,
+    over the steps -- everything that decides the output."""
+    sssc = model not in ("bsc", "BSC", "ebsc")
+    assert S_perm in (0, 1)
+    W = np.asarray(theta["W"], dtype=np.float64)
+    Y = np.asarray(Y, dtype=np.float64)
+    (D, H), N = W.shape, Y.shape[0]
+    assert Y.shape == (N, D)
+    A = int(max_active)
+    quotas = seed_quotas(int(S), H, A, sssc)
+    nB = seed_beam_check(S, A, beam)
+    G, Bm, yy = W.T @ W, Y @ W, (Y * Y).sum(axis=1)
+    if sssc:
+        mus, Psi = np.asarray(theta["mus"], dtype=np.float64), np.asarray(theta["Psi"], dtype=np.float64)
+        pies = np.asarray(theta["pies"], dtype=np.float64)
+        pil_bar, s2inv = np.log(pies / (1.0 - pies)), 1.0 / float(theta["sigma2"])
+    else:
+        pi, sigma = float(theta["pi"]), float(theta["sigma"])
+        pre1, pil_bar = -1.0 / 2.0 / sigma / sigma, np.log(pi / (1.0 - pi))
+        Gd = np.diag(G).copy()
+    states = np.zeros((N, S, H), dtype=bool)
+    lpj = np.zeros((N, S))
+    path = np.zeros((N, A), dtype=np.int32)
+    lpj_path = np.zeros((N, A))
+    margin = np.full(N, np.inf)
+    for n in range(N):
+        # a member: (path, score, c) with c = B_n minus the rows of G of its path, in path order (EBSC)
+        members = [([], 0.0 if sssc else pre1 * yy[n], None if sssc else Bm[n].copy())]
+        slot = 0
+        for t, q in enumerate(quotas, start=1):
+            sc_all, par_all, j_all = [], [], []
+            sets = [frozenset(m[0]) for m in members]
+            for r, (pth, base, c) in enumerate(members):
+                free = np.ones(H, dtype=bool)
+                free[pth] = False
+                for r2 in range(r):  # the sets an earlier parent reaches
+                    extra = sets[r2] - sets[r]
+                    if len(extra) == 1:
+                        free[next(iter(extra))] = False
+                cand = np.flatnonzero(free)
+                if sssc:
+                    score = _seed_scores_sssc(G, Psi, mus, pil_bar, s2inv, Bm[n], yy[n], pth, cand)
+                else:
+                    with np.errstate(invalid="ignore", over="ignore"):
+                        score = base + pil_bar + pre1 * (Gd[cand] - 2.0 * c[cand])
+                    score = np.where(np.isfinite(score), score, -np.inf)
+                sc_all.append(score)
+                par_all.append(np.full(len(cand), r))
+                j_all.append(cand)
+            sc_all, par_all, j_all = np.concatenate(sc_all), np.concatenate(par_all), np.concatenate(j_all)
+            order = np.lexsort((j_all, par_all, -sc_all))  # descending score, then parent rank, then j
+            sc, par, jj = sc_all[order], par_all[order], j_all[order]
+            for i in range(min(max(q, nB), len(sc) - 1)):
+                margin[n] = min(margin[n], _seed_gap(sc[i], sc[i + 1]))
+            for r in range(q):
+                states[n, slot + r, members[par[r]][0]] = True
+                states[n, slot + r, jj[r]] = True
+                lpj[n, slot + r] = sc[r]
+            lpj_path[n, t - 1] = sc[0]
+            if t == A:
+                path[n] = members[par[0]][0] + [int(jj[0])]
+            members = [(members[par[i]][0] + [int(jj[i])], sc[i], None if sssc else members[par[i]][2] - G[jj[i]])
+                       for i in range(min(nB, q))]
+            slot += q
+    return states, lpj, path, lpj_path, margin
+
+
 # ---- local search on K^n: the NumPy mirror of one sweep's proposals (csrc/kernels_sweep.hpp has the law) -----------------
 def sweep_states_host(model, theta, Y, ss, lpj, S_perm, n_parents, n_keep, x_infr=None):
     """One sweep's proposals as evoamd_sweep_propose emits them.  ``ss`` bool (N, S, H) and ``lpj`` (N, S_perm + S) are

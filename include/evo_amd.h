@@ -279,6 +279,19 @@ int evoamd_seed_states(evoamd_ctx *ctx, int max_active, int32_t *path_out, doubl
  * No atomics, a fixed summation order: two calls give the same bits. */
 #define EVOAMD_SEED_INCOMPLETE 1u
 int evoamd_seed_states_ex(evoamd_ctx *ctx, int max_active, unsigned flags, int32_t *path_out, double *lpj_out);
+/* K^n seeded by a BEAM of partial states (csrc/kernels_seed_beam.hpp has the law; evo_amd.variational.seed_states_beam_host
+ * is its NumPy mirror): the law of evoamd_seed_states with the `beam` = B best partial states kept per step and all of them
+ * expanded.  Step t scores P_r + {j} for every beam member P_r (rank order) and every j outside it, in the Gram form of
+ * evoamd_seed_states and the arithmetic of the member's own path; a set that an earlier member reaches as well is absent (an
+ * exact test on the packed words); all candidates are ranked by descending score (ties: ascending parent rank, then ascending
+ * j; -inf last), the q_t best go to the next q_t slots in rank order and the first B of them are the next beam.  beam = 1 is
+ * evoamd_seed_states bit for bit.  The S states are distinct, step t's have t latents, none is all-zero.
+ * path_out (N, A): the path of the rank-0 state of the last step; lpj_out (N, A): the rank-0 score of each step; either may
+ * be NULL.  Complete data only.  Refused with EVOAMD_E_INVALID before anything is written, K^n and its validity left as they
+ * were: everything evoamd_seed_states refuses (same texts), masks resident, beam < 1, beam > S / max_active (every beam
+ * member is a stored state), beam > 16 (SEED_BEAM_MAX), and an (H, beam) whose keys and beams do not fit one wavefront's
+ * share of LDS.  No atomics, a fixed summation order: two calls give the same bits.  Timed under EVOAMD_K_SEED_STATES. */
+int evoamd_seed_states_beam(evoamd_ctx *ctx, int max_active, int beam, int32_t *path_out, double *lpj_out);
 /* my_suff_stat["lpj"] (N,S_perm+S) float64. */
 int evoamd_upload_lpj(evoamd_ctx *ctx, const double *lpj);
 int evoamd_download_lpj(evoamd_ctx *ctx, double *lpj);

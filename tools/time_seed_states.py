@@ -13,7 +13,14 @@ generate_data_device from a sparse Theta (pi H = 3, Gaussian W * 0.8, noise 0.3;
 the entries (NaN in the data); the masked call (evoamd_seed_states_ex, EVOAMD_SEED_INCOMPLETE) is timed beside the
 complete call in the same run, and ``mirror`` and ``start`` run on the masked data.
 
+``--beam B [B ...]`` (complete data only): the beam kernel (evoamd_seed_states_beam) is timed for every B beside the greedy
+kernel of the same run, same engine, same data; per B the free energy of the seeded K^n (ljc + mean posterior_scores F), for
+the first and the last B the estimate L^ of the log-likelihood (estimate_log_likelihood, ``--samples`` draws), L^ - F and the
+mean effective sample size; then the greedy start is followed by neighbourhood="both" sweeps (one call each, wall time
+with the host wait) until they have used at least the slowest beam kernel's time, F after each.
+
     python tools/time_seed_states.py [--config c4|c5|both] [--n N] [--reps 5] [--host-n 30] [--esteps 60] [--missing 0.5]
+                                     [--beam 1 2 4 8] [--samples 256]
 """
 import argparse
 import os
@@ -54,12 +61,15 @@ def run(name, args):
     masked = args.missing > 0
     x_infr = None
 
-    def time_device(what, incomplete):
+    def time_device(what, incomplete, beam=None):
         eng.timing(["seed_states"])
         t = []
         for _ in range(args.reps):
             eng.timing_reset()
-            eng.seed_states(A, incomplete=incomplete)
+            if beam is None:
+                eng.seed_states(A, incomplete=incomplete)
+            else:
+                eng.seed_states_beam(A, beam)
             t.append(eng.kernel_time_ms("seed_states")[0])
         eng.timing(False)
         t = np.array(t)
@@ -79,6 +89,42 @@ def run(name, args):
         suff = model.seed_resident_states(dict(theta), my_data, *EA, max_active=A, incomplete=True)  # warm-up
         t_masked = time_device("masked", True)
         print("device seed_states %s: masked / complete = %.2f (medians)" % (tag, t_masked / t_complete), flush=True)
+    # ---- the beam beside the greedy kernel: time, the bound of the start, its tightness, and sweeps for the same time
+    if args.beam and not masked:
+        def bound(m, sf):
+            return eng.ljc + m.posterior_scores(dict(theta), sf, my_data)["F"].mean()
+
+        eng.lpj_resident()  # (the timed launches wrote K^n again: its rows are due)
+        F_greedy = bound(model, suff)
+        print("beam %s: greedy kernel median %.3f ms, F of its K^n %.4f" % (tag, t_complete, F_greedy), flush=True)
+        t_slowest = 0.0
+        for B in args.beam:
+            bm = cls(D, H, S, rng="device", sync_host=False, seed=1, engine=eng)
+            sf = bm.seed_resident_states(dict(theta), my_data, *EA, max_active=A, beam=B)  # warm-up
+            t_b = time_device("beam %d" % B, False, beam=B)
+            eng.lpj_resident()
+            F_b = bound(bm, sf)
+            t_slowest = max(t_slowest, t_b)
+            print("beam %s B=%d: kernel / greedy kernel = %.2f (medians), F of its K^n %.4f (greedy %+.4f)"
+                  % (tag, B, t_b / t_complete, F_b, F_b - F_greedy), flush=True)
+            if B in (args.beam[0], args.beam[-1]):
+                L_hat, info = bm.estimate_log_likelihood(dict(theta), sf, my_data, n_samples=args.samples, seed=5,
+                                                         per_datapoint=True)
+                print("beam %s B=%d: L^ %.4f at T=%d, L^ - F %.4f, mean ess %.2f"
+                      % (tag, B, L_hat, args.samples, L_hat - F_b, info["ess"].mean()), flush=True)
+        gm = cls(D, H, S, rng="device", sync_host=False, seed=1, engine=eng)
+        sf = gm.seed_resident_states(dict(theta), my_data, *EA, max_active=A)
+        gm.sweep_resident_states(dict(theta), sf, my_data, n_sweeps=1, neighbourhood="both", stop_when_quiet=False)  # warm-up
+        sf = gm.seed_resident_states(dict(theta), my_data, *EA, max_active=A)
+        used, n_sw = 0.0, 0
+        while used < t_slowest and n_sw < 64:
+            t0 = time.perf_counter()
+            res = gm.sweep_resident_states(dict(theta), sf, my_data, n_sweeps=1, neighbourhood="both", stop_when_quiet=False)
+            used += 1e3 * (time.perf_counter() - t0)
+            n_sw += 1
+            print("beam %s: greedy start + %d \"both\" sweep(s), %.1f ms wall so far (slowest beam kernel %.1f ms): F %.4f "
+                  "(greedy %+.4f)" % (tag, n_sw, used, t_slowest, res.F[-1], res.F[-1] - F_greedy), flush=True)
+        suff = model.seed_resident_states(dict(theta), my_data, *EA, max_active=A)
     # ---- the start it gives
     if args.esteps > 0:
         eng.lpj_resident()
@@ -119,6 +165,8 @@ def main():
     ap.add_argument("--host-n", type=int, default=30)
     ap.add_argument("--esteps", type=int, default=60)
     ap.add_argument("--missing", type=float, default=0.0, help="fraction of entries hidden by an i.i.d. mask (0: complete data)")
+    ap.add_argument("--beam", type=int, nargs="*", default=[], help="beam widths to time beside the greedy kernel (complete data)")
+    ap.add_argument("--samples", type=int, default=256, help="draws of estimate_log_likelihood for the first and last --beam")
     args = ap.parse_args()
     for name in (["c4", "c5"] if args.config == "both" else [args.config]):
         run(name, args)
