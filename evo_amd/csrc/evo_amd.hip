@@ -415,6 +415,7 @@ struct evoamd_ctx {
   bool yrec_valid = false, rec_in_stats = false;
   DevBuf<double> yhat, tmpWt;  // reconstruction (N x D) and W^T scratch (ES3C)
   bool yhat_valid = false;
+  bool keep_differs = false;  // incomplete data: the keep-mask x of evoamd_upload_masks is not x_infr (EBSC sigma, stats_epilogue)
   bool stats_rows_valid = false;  // Es / Ez rows describe the current K^n and Theta
   // evoamd_reconstruct_resident: the selected reconstruction stays on the device for evoamd_patches_merge_resident.
   // rec_resident: y_hat (complete data) / Yrec (incomplete) + the masks below describe it; dropped with yhat_valid and by
@@ -1554,6 +1555,7 @@ extern "C" int evoamd_upload_masks(evoamd_ctx *c, const uint8_t *x_infr, const u
   REQUIRE(c && c->configured && c->have_data, "configure and upload_data first");
   REQUIRE(!(c->f32 && x_infr), "incomplete data is not available in the float32 mode");
   HIP_TRY(hipSetDevice(c->device));
+  c->keep_differs = x_infr && x && memcmp(x, x_infr, (size_t)c->N * c->D) != 0;
   if (!x_infr) {  // back to complete data (upload_data again restores entries that were zeroed)
     c->mask_infr.reset();
     c->mask_x.reset();
@@ -2968,6 +2970,12 @@ static int lpj_single_impl(evoamd_ctx *c, const double *y, const uint8_t *x_infr
     dmask = c->stage + (size_t)C * c->H;
     HIP_TRY(hipMemcpyAsync(dmask, x_infr, (size_t)c->D, hipMemcpyHostToDevice, c->stream));
     mask_apply_kernel<<<cdiv(c->D, 256), 256, 0, c->stream>>>(dy, c->D, dmask, 1, c->D);
+    if (c->model == EVOAMD_MODEL_SSSC && !c->mask_infr) {
+      // no resident masks: nobody has allocated W^T or kept it current (derive_from_theta transposes only with masks
+      // resident), and the wavefront kernel forms W_obs^T W_obs from it
+      if (!c->Wt) TRY(c->Wt.alloc((size_t)c->H * c->D));
+      transpose_kernel<<<cdiv((i64)c->H * c->D, 256), 256, 0, c->stream>>>(c->W, c->D, c->H, c->Wt);
+    }
   }
   HIP_TRY(hipMemcpyAsync(c->stage, states_bool, (size_t)C * c->H, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(dfl, 0, sizeof(unsigned), c->stream));
@@ -3741,7 +3749,8 @@ static int rows_written(evoamd_ctx *c, const StatsPlan &p, StatsFlow &fl) {
 static int reconstruct_rows(evoamd_ctx *c, const char *asked_msg = nullptr) {
   TRY(compute_reconstruction(c));
   if (asked_msg) REQUIRE(c->rec_in_stats, asked_msg);
-  select_rec_kernel<<<cdiv(c->N, 4), 256, 0, c->stream>>>(c->Y, c->ldY, c->mask_x, c->mask_infr, c->yhat, c->N, c->D, c->Yrec);
+  select_rec_kernel<<<cdiv(c->N, 4), 256, 0, c->stream>>>(c->Y, c->ldY, c->mask_x, c->mask_infr, c->yhat, c->N, c->D, c->Yrec,
+                                                          c->model == EVOAMD_MODEL_BSC);
   HIP_TRY(hipGetLastError());
   made_yrec_from_pass(c, /*in_stats=*/true);
   return 0;
@@ -4284,6 +4293,13 @@ static int stats_epilogue(evoamd_ctx *c, const StatsPlan &p, const StatsFlow &fl
     made_clean_lists(c);
     if (c->model == EVOAMD_MODEL_SSSC && c->mask_infr) {  // tail[7] = sum over reliable entries of y_hat^2
       masked_sqsum_kernel<<<256, 256, 0, c->stream>>>(c->yhat, c->mask_infr, N * (i64)p.D, c->acc + a.tail + 7);
+      HIP_TRY(hipGetLastError());
+    }
+    if (c->model == EVOAMD_MODEL_BSC && c->mask_infr && c->keep_differs) {
+      // the keep-mask drops reliable entries: the reference's sigma reads y_reconstructed there (bsc.py:187,214-216), the
+      // kernels' sum came from the lpj, i.e. from the data (with x == x_infr the two agree and nothing is launched)
+      if (!c->yhat_valid) TRY(compute_reconstruction(c));
+      bsc_sigma_rec_kernel<<<256, 256, 0, c->stream>>>(c->Y, c->ldY, c->Yrec, c->yhat, c->mask_infr, N, p.D, c->acc + a.sigma);
       HIP_TRY(hipGetLastError());
     }
   }
@@ -5358,7 +5374,8 @@ extern "C" int evoamd_reconstruct_resident(evoamd_ctx *c, const uint8_t *x) {
   }
   if (c->mask_infr) {  // incomplete data: the masks are resident, x is not read
     if (!c->yrec_from_pass) {  // the pass ran without reconstruct_in_stats (its M-step read an older y_reconstructed)
-      select_rec_kernel<<<cdiv(c->N, 4), 256, 0, c->stream>>>(c->Y, c->ldY, c->mask_x, c->mask_infr, c->yhat, c->N, c->D, c->Yrec);
+      select_rec_kernel<<<cdiv(c->N, 4), 256, 0, c->stream>>>(c->Y, c->ldY, c->mask_x, c->mask_infr, c->yhat, c->N, c->D, c->Yrec,
+                                                          c->model == EVOAMD_MODEL_BSC);
       HIP_TRY(hipGetLastError());
       made_yrec_from_pass(c, /*in_stats=*/false);
     }

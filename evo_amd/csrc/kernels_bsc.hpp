@@ -347,16 +347,17 @@ __global__ __launch_bounds__(256) void mask_apply_kernel(double *__restrict__ Y,
   if (!mask[t]) Y[n * ld + d] = 0.0;
 }
 
-// y_reconstructed on the device (_models.py:643-665): keep y where x is set, the posterior-predictive
-// estimate elsewhere; datapoints without a single reliable entry are skipped (:648-649).
+// y_reconstructed on the device, the rows the M-step's Wp reads: keep y where x is set, the posterior-predictive estimate
+// elsewhere.  skip_empty (EBSC): datapoints without a single reliable entry are skipped (Model.reconstruct,
+// _models.py:648-649); ES3C's own loop reconstructs them too (sssc.py:613-627,632: the prior's estimate).
 __global__ __launch_bounds__(256) void select_rec_kernel(const double *__restrict__ Y, int ld,
                                                          const uint8_t *__restrict__ x, const uint8_t *__restrict__ infr,
                                                          const double *__restrict__ yhat, i64 N, int D,
-                                                         double *__restrict__ Yrec) {
+                                                         double *__restrict__ Yrec, bool skip_empty) {
   const int lane = lane_id(), wave = wave_id_uniform();
   const i64 n = (i64)blockIdx.x * 4 + wave;
   if (n >= N) return;
-  bool any = false;
+  bool any = !skip_empty;
   for (int d = lane; d < D; d += 64) any = any || infr[n * D + d] != 0;
   any = __any(any);
   for (int d = lane; d < D; d += 64) {
@@ -380,6 +381,32 @@ __global__ __launch_bounds__(256) void masked_sqsum_kernel(const double *__restr
     __syncthreads();
   }
   if (threadIdx.x == 0) unsafeAtomicAdd(out, sh[0]);
+}
+
+// EBSC sigma on incomplete data: the reference's residual reads y_reconstructed at the reliable entries (bsc.py:187,207,
+// 214-216: this_y = y_reconstructed[n], indexed with x_infr).  The statistics kernels sum q_s ||y_obs - W_obs s||^2 from
+// the lpj, i.e. from the data; where the keep-mask x drops a reliable entry, yrec is the estimate there and the two sums
+// differ by
+//   sum over reliable (n, d) of (yrec^2 - y^2) - 2 (yrec - y) y_hat,   y_hat = W E_q[s]
+// (the weights of a datapoint sum to one; an entry with yrec == y adds exactly zero).  One atomic per workgroup.
+__global__ __launch_bounds__(256) void bsc_sigma_rec_kernel(const double *__restrict__ Y, int ld, const double *__restrict__ Yrec,
+                                                            const double *__restrict__ yhat, const uint8_t *__restrict__ infr,
+                                                            i64 N, int D, double *__restrict__ sigma) {
+  __shared__ double sh[256];
+  double s = 0.0;
+  for (i64 e = (i64)blockIdx.x * 256 + threadIdx.x; e < N * D; e += (i64)gridDim.x * 256) {
+    if (!infr[e]) continue;
+    const i64 n = e / D;
+    const double y = Y[n * ld + (e - n * D)], yr = Yrec[e];
+    s += (yr - y) * ((yr + y) - 2.0 * yhat[e]);
+  }
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) unsafeAtomicAdd(sigma, sh[0]);
 }
 
 // Permanent all-zero state: lpj = pre * ||y_n||^2 (bsc.py:72 with pre = pre1; sssc.py:237 with

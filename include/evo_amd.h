@@ -518,8 +518,13 @@ int evoamd_mstep_device(evoamd_ctx *ctx, int learn_mask, double *tail_out, doubl
  * datapoint).  The M-step's Wp contraction reads y_reconstructed (bsc.py:184-189): either
  * evoamd_set_option(ctx, "reconstruct_in_stats", 1) before evoamd_stats (it then forms
  * y_hat = Es W^T and y_rec = x ? y : y_hat first; fetch y_hat with evoamd_reconstruct), or hand over an
- * older one with evoamd_upload_yrec.  x_infr == NULL returns to complete data (upload Y again); evoamd_configure
- * drops the masks too.  evoamd_mstep_device handles incomplete data once evoamd_set_reliable_fraction was called. */
+ * older one with evoamd_upload_yrec.  The rows the Wp contraction reads skip a datapoint without a reliable entry for
+ * EBSC (_models.py:648-649) and reconstruct it for ES3C, whose own loop has no such test (sssc.py:613-627,632).  EBSC's
+ * sigma sum reads y_reconstructed at the reliable entries too (bsc.py:187,214-216): where x drops a reliable entry the
+ * estimate enters, not the datum -- a correction launched only when x differs from x_infr; with x == x_infr an uploaded
+ * y_reconstructed is taken to hold y at the reliable entries.  x_infr == NULL returns to complete data (upload Y again);
+ * evoamd_configure drops the masks too.  evoamd_mstep_device handles incomplete data once evoamd_set_reliable_fraction
+ * was called. */
 int evoamd_upload_masks(evoamd_ctx *ctx, const uint8_t *x_infr, const uint8_t *x);
 int evoamd_upload_yrec(evoamd_ctx *ctx, const double *y_reconstructed);
 /* Incomplete data with the device Theta update (evoamd_mstep_device): the mean number of reliable
@@ -529,7 +534,8 @@ int evoamd_upload_yrec(evoamd_ctx *ctx, const double *y_reconstructed);
  * Negative: complete data (default).  Call before evoamd_set_params_bsc / _sssc. */
 int evoamd_set_reliable_fraction(evoamd_ctx *ctx, double reliable_per_datapoint);
 /* evoamd_lpj_single with this datapoint's x_infr row (D bool bytes): log_pseudo_joint reading
- * my_data["this_x_infr"] (bsc.py:80-95). */
+ * my_data["this_x_infr"] (bsc.py:80-95).  Needs no resident masks (ES3C: it then forms the W^T of the current Theta
+ * itself). */
 int evoamd_lpj_single_masked(evoamd_ctx *ctx, const double *y, const uint8_t *x_infr, const uint8_t *states, int C,
                              double *lpj_out, int32_t *flags_out);
 /* Posterior-predictive data estimate (complete data): y_hat (N x D, host) with
