@@ -901,6 +901,7 @@ extern "C" int evoamd_device_count(int *count) {
   return 0;
 }
 
+static int kn_set_lds_limits();  // the seeding and sweep kernels: one table, beside their launch plan
 // kernels whose dynamic LDS exceeds the 64 KiB a launch may ask for by default
 static int set_kernel_lds_limits() {
   HIP_TRY(hipFuncSetAttribute((const void *)sssc_stats_flat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
@@ -934,18 +935,7 @@ static int set_kernel_lds_limits() {
     for (const void *f : sk) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   }
   HIP_TRY(hipFuncSetAttribute((const void *)remap_latents_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, REMAP_LDS_BYTES));
-  HIP_TRY(hipFuncSetAttribute((const void *)seed_states_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-  HIP_TRY(hipFuncSetAttribute((const void *)seed_states_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-  HIP_TRY(hipFuncSetAttribute((const void *)seed_states_beam_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-  HIP_TRY(hipFuncSetAttribute((const void *)seed_states_beam_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-  HIP_TRY(hipFuncSetAttribute((const void *)seed_states_masked_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-  HIP_TRY(hipFuncSetAttribute((const void *)seed_states_masked_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-  HIP_TRY(hipFuncSetAttribute((const void *)sweep_neighbours_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-  HIP_TRY(hipFuncSetAttribute((const void *)sweep_neighbours_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-  HIP_TRY(hipFuncSetAttribute((const void *)sweep_neighbours_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-  HIP_TRY(hipFuncSetAttribute((const void *)sweep_neighbours_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-  HIP_TRY(hipFuncSetAttribute((const void *)sweep_swap_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-  HIP_TRY(hipFuncSetAttribute((const void *)sweep_swap_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  TRY(kn_set_lds_limits());
   {
     const void *wk[] = {(const void *)sssc_stats_wave_kernel<0, 4>,  (const void *)sssc_stats_wave_kernel<1, 4>,
                         (const void *)sssc_stats_wave_kernel<2, 4>,  (const void *)sssc_stats_wave_kernel<4, 4>,
@@ -5703,19 +5693,117 @@ extern "C" int evoamd_download_predictive(evoamd_ctx *c, double *mean, double *v
 }
 
 // ---------------------------------------------------------------------------------------
-// K^n seeded by greedy forward selection on the model's lpj (kernels_seed.hpp).  Every refusal comes before the first write.
+// Proposals for K^n: seeding (kernels_seed.hpp, kernels_seed_beam.hpp) and local search (kernels_sweep.hpp,
+// kernels_sweep_swap.hpp).  One table of the family's kernels, indexed like their LDS layouts; one admission for what all
+// of them refuse; one launch plan (how many wavefronts of a workgroup fit the LDS limit, how large the grid is); one rule
+// for the home of the rows of G(n) on masked ES3C; one builder of the SeedArgs fields that come from the context.
+// Every refusal comes before the first write.
+// ---------------------------------------------------------------------------------------
+#define KN_LDS_MAX (150 * 1024)  // dynamic LDS a workgroup of these kernels may ask for
+static const void *const kn_kernels[SEED_LDS_KINDS][2] = {  // [SeedLdsKind][ES3C]
+    {(const void *)seed_states_kernel<false>, (const void *)seed_states_kernel<true>},
+    {(const void *)seed_states_masked_kernel<false>, (const void *)seed_states_masked_kernel<true>},
+    {(const void *)seed_states_beam_kernel<false>, (const void *)seed_states_beam_kernel<true>},
+    {(const void *)sweep_neighbours_kernel<false>, (const void *)sweep_neighbours_kernel<true>},
+    {(const void *)sweep_neighbours_kernel<false, true>, (const void *)sweep_neighbours_kernel<true, true>},
+    {(const void *)sweep_swap_kernel<false>, (const void *)sweep_swap_kernel<true>}};
+
+static int kn_set_lds_limits() {
+  for (const auto &pair : kn_kernels)
+    for (const void *f : pair) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, KN_LDS_MAX));
+  return 0;
+}
+
+// What seeding and sweeping refuse alike, in this order.  who: the caller's name in the texts; masks_refusal: the caller's
+// text for resident masks, nullptr when it admits them; need_kn: the call reads K^n.
+static int kn_admit(const evoamd_ctx *c, const char *who, const char *masks_refusal, bool need_kn) {
+  if (!c->have_params) return fail(EVOAMD_E_INVALID, "%s: no Theta installed (set parameters first)", who);
+  if (!c->have_data) return fail(EVOAMD_E_INVALID, "%s: no data (upload data first)", who);
+  if (need_kn) REQUIRE_KN(c);
+  REQUIRE(!c->mask_infr || !masks_refusal, masks_refusal);
+  if (c->bg_unit) return fail(EVOAMD_E_INVALID, "%s: option background_unit is not supported", who);
+  if (c->f32) return fail(EVOAMD_E_INVALID, "%s is not available in the float32 mode (ebsc_f32)", who);
+  if (c->model != EVOAMD_MODEL_SSSC && c->bsc_direct)
+    return fail(EVOAMD_E_INVALID, "%s: bsc_direct keeps no G = W^T W, which the scores need", who);
+  return 0;
+}
+
+// From one wavefront's share of LDS to the wavefronts of a workgroup and the grid.  W starts at 4 and shrinks until W shares
+// fit: by halving everywhere but in the masked flip sweep, which steps down by one.  The difference is inherited and
+// unmeasured; it stays, because either rule changed would change a launch shape.
+enum KnStep { KN_STEP_HALVE, KN_STEP_DECREMENT };
+struct KnLaunch {
+  int W = 4;
+  size_t wave_bytes = 0;
+  unsigned grid = 1;
+};
+// refusal: the text when one share does not fit; cu_mult: workgroups per CU the grid is capped at
+static int kn_plan_launch(const evoamd_ctx *c, size_t wave_bytes, const char *refusal, int cu_mult, KnStep step, KnLaunch &l) {
+  REQUIRE(wave_bytes <= KN_LDS_MAX, refusal);
+  l.wave_bytes = wave_bytes;
+  l.W = 4;
+  while (l.W > 1 && l.W * wave_bytes > KN_LDS_MAX) l.W = step == KN_STEP_HALVE ? l.W >> 1 : l.W - 1;
+  l.grid = (unsigned)std::min<i64>(cdiv(c->N, l.W), (i64)c->n_cu * cu_mult);
+  return 0;
+}
+
+// Masked ES3C: the R rows of G(n) a wavefront keeps.  Their home is LDS while one wavefront's share with them fits, else a
+// buffer of the context (seed_rows) with fewer workgroups, each wavefront of the grid owning R Hp doubles.
+struct KnRows {
+  int R = 0, lds = 0;  // lds: the rows whose home is LDS (R or 0)
+  int cu_mult = 64;
+  size_t doubles(const KnLaunch &l, int Hp) const { return R && !lds ? (size_t)l.grid * l.W * R * Hp : 0; }
+};
+static KnRows kn_plan_rows(SeedLdsKind kind, SeedLdsShape shape, int R) {
+  KnRows r;
+  shape.rows_lds = r.R = R;
+  r.lds = R && seed_lds_bytes(kind, shape) <= KN_LDS_MAX ? R : 0;
+  r.cu_mult = R && !r.lds ? 4 : 64;
+  return r;
+}
+
+// the SeedArgs fields that come straight from the context; the callers set A / Q / path / lpj_path and rows / R.  Every
+// kernel of the family is handed dig, W, mask and D, also those that never read them: the sweeps read no dig, and W, mask
+// and D are read by the masked instantiations alone.
+static void fill_seed_args(const evoamd_ctx *c, SeedArgs &a) {
+  a = SeedArgs{};
+  a.states = c->states, a.dig = c->dig;
+  a.Bm = c->Bm, a.yy = c->yy;
+  a.G = c->G, a.Gd = c->diag;
+  a.GP = c->GP, a.GPt = c->seed_gpt;
+  a.mus = c->mus, a.pil_bar = c->pilbar_v;
+  a.dpar = c->dpar, a.err = c->err;
+  a.N = c->N;
+  a.S = c->S, a.H = c->H, a.HW = c->HW, a.Hp = (int)cdiv(c->H, 64) * 64;
+  a.W = c->W, a.mask = c->mask_infr, a.D = c->D;
+}
+
+// which kernel kinds take which argument struct: another pairing is refused, not launched
+static bool kn_takes(SeedLdsKind k, const SeedArgs &) { return k == SEED_LDS_GREEDY || k == SEED_LDS_GREEDY_MASKED; }
+static bool kn_takes(SeedLdsKind k, const SeedBeamArgs &) { return k == SEED_LDS_BEAM; }
+static bool kn_takes(SeedLdsKind k, const SweepArgs &) { return k == SEED_LDS_FLIP || k == SEED_LDS_FLIP_MASKED; }
+static bool kn_takes(SeedLdsKind k, const SweepSwapArgs &) { return k == SEED_LDS_SWAP; }
+template <class Args>
+static int kn_launch(evoamd_ctx *c, SeedLdsKind kind, const KnLaunch &l, const Args &args) {
+  REQUIRE(kn_takes(kind, args), "kn_launch: these are not the arguments of this kind of kernel");
+  void *argv[] = {const_cast<Args *>(&args)};
+  HIP_TRY(hipLaunchKernel(kn_kernels[kind][c->model == EVOAMD_MODEL_SSSC], dim3(l.grid), dim3(64 * l.W), argv,
+                          l.W * l.wave_bytes, c->stream));
+  return 0;
+}
+
+static int kn_transpose_gp(evoamd_ctx *c) {
+  seed_transpose_gp_kernel<<<cdiv((i64)c->H * c->H, 256), 256, 0, c->stream>>>(c->GP, c->H, c->seed_gpt);
+  return 0;
+}
+
+// ---- seeding: greedy forward selection on the model's lpj, or a beam of partial states (beam > 0; complete data only).
 // EVOAMD_SEED_INCOMPLETE is a permission: with masks resident the masked kernel runs (the datapoint's own Gram rows from W
 // and the mask), without masks the complete kernel, whatever the flag says.
-// seed_admit: what the greedy call and the beam call (evoamd_seed_states_beam) refuse alike, with one text each;
-// masks_refusal: the caller's text for resident masks, nullptr when it admits them.
+// seed_admit: what the greedy call and the beam call refuse alike, with one text each; masks_refusal as in kn_admit.
 static int seed_admit(evoamd_ctx *c, int max_active, const char *masks_refusal) {
-  REQUIRE(c->have_params, "evoamd_seed_states: no Theta installed (set parameters first)");
-  REQUIRE(c->have_data, "evoamd_seed_states: no data (upload data first)");
-  REQUIRE(!c->mask_infr || !masks_refusal, masks_refusal);
-  REQUIRE(!c->bg_unit, "evoamd_seed_states: option background_unit is not supported");
-  REQUIRE(!c->f32, "evoamd_seed_states is not available in the float32 mode (ebsc_f32)");
+  TRY(kn_admit(c, "evoamd_seed_states", masks_refusal, /*need_kn=*/false));
   const bool sssc = c->model == EVOAMD_MODEL_SSSC;
-  REQUIRE(sssc || !c->bsc_direct, "evoamd_seed_states: bsc_direct keeps no G = W^T W, which the scores need");
   const int S = c->S, H = c->H, A = max_active;
   const int cap = sssc ? SEED_MAX_A_SSSC : SEED_MAX_A_BSC;
   if (A < 1 || A > S || A > H || A > cap)
@@ -5731,233 +5819,130 @@ static int seed_admit(evoamd_ctx *c, int max_active, const char *masks_refusal) 
   return 0;
 }
 
+// the body of evoamd_seed_states_ex (beam = 0) and evoamd_seed_states_beam (beam = B, after its range check)
+static int seed_states_run(evoamd_ctx *c, int max_active, int beam, int32_t *path_out, double *lpj_out) {
+  const bool sssc = c->model == EVOAMD_MODEL_SSSC, masked = c->mask_infr != nullptr;
+  const int S = c->S, H = c->H, A = max_active;
+  const int Hp = (int)cdiv(H, 64) * 64, Q = S / A + (S % A ? 1 : 0);
+  const SeedLdsKind kind = beam ? SEED_LDS_BEAM : (masked ? SEED_LDS_GREEDY_MASKED : SEED_LDS_GREEDY);
+  SeedLdsShape shape = {sssc, Hp, c->HW, Q, A, beam, masked ? c->D : 0, 0, 0};
+  // ES3C, masked: the winners' rows of G(n) and its diagonal
+  const KnRows rows = kn_plan_rows(kind, shape, masked && sssc ? A : 0);
+  shape.rows_lds = rows.lds;
+  const size_t wave_bytes = seed_lds_bytes(kind, shape);
+  if (beam && wave_bytes > KN_LDS_MAX)
+    return fail(EVOAMD_E_INVALID, "evoamd_seed_states_beam: the keys of one datapoint and the two beams (H = %d, beam = %d: %zu "
+                "bytes) do not fit one wavefront's share of LDS", H, beam, wave_bytes);
+  KnLaunch l;
+  TRY(kn_plan_launch(c, wave_bytes,
+                     masked ? "evoamd_seed_states: the scores of one datapoint (16 H bytes) and the column of W (12 D "
+                              "bytes) do not fit one wavefront's share of LDS"
+                            : "evoamd_seed_states: the scores of one datapoint (16 H bytes) do not fit one wavefront's share of LDS",
+                     rows.cu_mult, KN_STEP_HALVE, l));
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(ensure_B(c));
+  const size_t n_out = (size_t)c->N * A;
+  const size_t out_bytes = ((n_out * sizeof(int) + 7) / 8) * 8;
+  if (path_out || lpj_out) TRY(c->stage.ensure(c, out_bytes + n_out * sizeof(double)));
+  if (sssc) TRY(c->seed_gpt.ensure(c, (size_t)H * H));
+  if (rows.doubles(l, Hp)) TRY(c->seed_rows.ensure(c, rows.doubles(l, Hp)));
+  SeedBeamArgs b;
+  SeedArgs &a = b.sd;  // (the greedy kernels take the SeedArgs alone)
+  fill_seed_args(c, a);
+  a.A = A, a.Q = Q;
+  a.path = path_out ? (int *)c->stage.get() : nullptr;
+  a.lpj_path = lpj_out ? (double *)(c->stage.get() + out_bytes) : nullptr;
+  a.rows = rows.doubles(l, Hp) ? c->seed_rows.get() : nullptr;
+  a.R = rows.R;
+  b.B = beam;
+  on_kn_changed(c, KN_BY_CALLER);
+  {
+    SpanGuard g(c, KID_SEED_STATES);
+    if (sssc) TRY(kn_transpose_gp(c));
+    TRY(beam ? kn_launch(c, kind, l, b) : kn_launch(c, kind, l, a));
+  }
+  HIP_TRY(hipGetLastError());
+  DBG_SYNC(c, beam ? "seed_states_beam" : "seed_states");
+  if (path_out) HIP_TRY(hipMemcpyAsync(path_out, a.path, n_out * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (lpj_out) HIP_TRY(hipMemcpyAsync(lpj_out, a.lpj_path, n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  on_kn_complete(c);
+  return 0;
+}
+
 extern "C" int evoamd_seed_states_ex(evoamd_ctx *c, int max_active, unsigned flags, int32_t *path_out, double *lpj_out) {
   REQUIRE(c && c->configured, "configure first");
   // (a missing Theta or missing data is named before an unknown flag)
   REQUIRE(!(flags & ~(unsigned)EVOAMD_SEED_INCOMPLETE) || !c->have_params || !c->have_data, "evoamd_seed_states_ex: unknown flag");
   TRY(seed_admit(c, max_active, (flags & EVOAMD_SEED_INCOMPLETE) ? nullptr : "evoamd_seed_states: incomplete data (masks present) "
                  "is not supported (evoamd_seed_states_ex with EVOAMD_SEED_INCOMPLETE)"));
-  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
-  const int S = c->S, H = c->H, HW = c->HW, A = max_active;
-  const int q_lo = S / A, q_rem = S % A;
-  const int Hp = (int)cdiv(H, 64) * 64, Q = q_lo + (q_rem ? 1 : 0);
-  const bool masked = c->mask_infr != nullptr;
-  const int D = c->D, R = masked && sssc ? A : 0;  // ES3C, masked: the winners' rows of G(n) and its diagonal
-  // their home: LDS while one wavefront's share fits, else a buffer of the context
-  const bool rows_lds = R && seed_masked_wave_bytes(Hp, HW, Q, A, D, R) <= 150 * 1024;
-  const size_t wave_bytes = masked ? seed_masked_wave_bytes(Hp, HW, Q, A, D, rows_lds ? R : 0) : seed_wave_bytes(Hp, HW, Q, A);
-  REQUIRE(wave_bytes <= 150 * 1024, masked ? "evoamd_seed_states: the scores of one datapoint (16 H bytes) and the column of W (12 D "
-                                             "bytes) do not fit one wavefront's share of LDS"
-                                           : "evoamd_seed_states: the scores of one datapoint (16 H bytes) do not fit one wavefront's share of LDS");
-  HIP_TRY(hipSetDevice(c->device));
-  TRY(ensure_B(c));
-  const size_t n_out = (size_t)c->N * A;
-  const size_t out_bytes = ((n_out * sizeof(int) + 7) / 8) * 8;
-  if (path_out || lpj_out) TRY(c->stage.ensure(c, out_bytes + n_out * sizeof(double)));
-  if (sssc) TRY(c->seed_gpt.ensure(c, (size_t)H * H));
-  int W = 4;
-  while (W > 1 && W * wave_bytes > 150 * 1024) W >>= 1;
-  // (rows in global memory: fewer workgroups, each wavefront of the grid owns R Hp doubles)
-  const unsigned grid = (unsigned)std::min<i64>(cdiv(c->N, W), (i64)c->n_cu * (R && !rows_lds ? 4 : 64));
-  if (R && !rows_lds) TRY(c->seed_rows.ensure(c, (size_t)grid * W * R * Hp));
-  SeedArgs a;
-  a.states = c->states;
-  a.dig = c->dig;
-  a.Bm = c->Bm;
-  a.yy = c->yy;
-  a.G = c->G;
-  a.Gd = c->diag;
-  a.GP = c->GP;
-  a.mus = c->mus;
-  a.pil_bar = c->pilbar_v;
-  a.GPt = c->seed_gpt;
-  a.dpar = c->dpar;
-  a.path = path_out ? (int *)c->stage.get() : nullptr;
-  a.lpj_path = lpj_out ? (double *)(c->stage.get() + out_bytes) : nullptr;
-  a.err = c->err;
-  a.N = c->N;
-  a.S = S, a.H = H, a.HW = HW, a.A = A, a.Hp = Hp, a.Q = Q;
-  a.W = c->W;
-  a.mask = c->mask_infr;
-  a.rows = R && !rows_lds ? c->seed_rows.get() : nullptr;
-  a.D = D, a.R = R;
-  on_kn_changed(c, KN_BY_CALLER);
-  {
-    SpanGuard g(c, KID_SEED_STATES);
-    if (sssc) seed_transpose_gp_kernel<<<cdiv((i64)H * H, 256), 256, 0, c->stream>>>(c->GP, H, c->seed_gpt);
-    if (masked && sssc)
-      seed_states_masked_kernel<true><<<grid, 64 * W, W * wave_bytes, c->stream>>>(a);
-    else if (masked)
-      seed_states_masked_kernel<false><<<grid, 64 * W, W * wave_bytes, c->stream>>>(a);
-    else if (sssc)
-      seed_states_kernel<true><<<grid, 64 * W, W * wave_bytes, c->stream>>>(a);
-    else
-      seed_states_kernel<false><<<grid, 64 * W, W * wave_bytes, c->stream>>>(a);
-  }
-  HIP_TRY(hipGetLastError());
-  DBG_SYNC(c, "seed_states");
-  if (path_out) HIP_TRY(hipMemcpyAsync(path_out, a.path, n_out * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (lpj_out) HIP_TRY(hipMemcpyAsync(lpj_out, a.lpj_path, n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  on_kn_complete(c);
-  return 0;
+  return seed_states_run(c, max_active, 0, path_out, lpj_out);
 }
 
 extern "C" int evoamd_seed_states(evoamd_ctx *c, int max_active, int32_t *path_out, double *lpj_out) {
   return evoamd_seed_states_ex(c, max_active, 0u, path_out, lpj_out);
 }
 
-// K^n seeded by a beam of partial states (kernels_seed_beam.hpp has the law).  Complete data only; every refusal comes before
-// the first write.
+// K^n seeded by a beam of partial states (kernels_seed_beam.hpp has the law).  Complete data only.
 extern "C" int evoamd_seed_states_beam(evoamd_ctx *c, int max_active, int beam, int32_t *path_out, double *lpj_out) {
   REQUIRE(c && c->configured, "configure first");
   TRY(seed_admit(c, max_active, "evoamd_seed_states_beam: incomplete data (masks present) is not supported: beam seeding is "
                  "for complete data"));
-  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
-  const int S = c->S, H = c->H, HW = c->HW, A = max_active, B = beam;
-  if (B < 1 || B > S / A || B > SEED_BEAM_MAX)
+  if (beam < 1 || beam > c->S / max_active || beam > SEED_BEAM_MAX)
     return fail(EVOAMD_E_INVALID, "evoamd_seed_states_beam: beam = %d must be in [1, min(S / max_active = %d, %d)] (every beam "
-                "member is a stored state; SEED_BEAM_MAX = %d)", B, S / A, SEED_BEAM_MAX, SEED_BEAM_MAX);
-  const int q_lo = S / A, q_rem = S % A;
-  const int Hp = (int)cdiv(H, 64) * 64, Q = q_lo + (q_rem ? 1 : 0);
-  const size_t wave_bytes = seed_beam_wave_bytes(Hp, HW, Q, A, B);
-  if (wave_bytes > 150 * 1024)
-    return fail(EVOAMD_E_INVALID, "evoamd_seed_states_beam: the keys of one datapoint and the two beams (H = %d, beam = %d: %zu "
-                "bytes) do not fit one wavefront's share of LDS", H, B, wave_bytes);
-  HIP_TRY(hipSetDevice(c->device));
-  TRY(ensure_B(c));
-  const size_t n_out = (size_t)c->N * A;
-  const size_t out_bytes = ((n_out * sizeof(int) + 7) / 8) * 8;
-  if (path_out || lpj_out) TRY(c->stage.ensure(c, out_bytes + n_out * sizeof(double)));
-  if (sssc) TRY(c->seed_gpt.ensure(c, (size_t)H * H));
-  int W = 4;
-  while (W > 1 && W * wave_bytes > 150 * 1024) W >>= 1;
-  const unsigned grid = (unsigned)std::min<i64>(cdiv(c->N, W), (i64)c->n_cu * 64);
-  SeedBeamArgs b;
-  SeedArgs &a = b.sd;
-  a.states = c->states;
-  a.dig = c->dig;
-  a.Bm = c->Bm;
-  a.yy = c->yy;
-  a.G = c->G;
-  a.Gd = c->diag;
-  a.GP = c->GP;
-  a.mus = c->mus;
-  a.pil_bar = c->pilbar_v;
-  a.GPt = c->seed_gpt;
-  a.dpar = c->dpar;
-  a.path = path_out ? (int *)c->stage.get() : nullptr;
-  a.lpj_path = lpj_out ? (double *)(c->stage.get() + out_bytes) : nullptr;
-  a.err = c->err;
-  a.N = c->N;
-  a.S = S, a.H = H, a.HW = HW, a.A = A, a.Hp = Hp, a.Q = Q;
-  a.W = nullptr;
-  a.mask = nullptr;
-  a.rows = nullptr;
-  a.D = c->D, a.R = 0;
-  b.B = B;
-  on_kn_changed(c, KN_BY_CALLER);
-  {
-    SpanGuard g(c, KID_SEED_STATES);
-    if (sssc) {
-      seed_transpose_gp_kernel<<<cdiv((i64)H * H, 256), 256, 0, c->stream>>>(c->GP, H, c->seed_gpt);
-      seed_states_beam_kernel<true><<<grid, 64 * W, W * wave_bytes, c->stream>>>(b);
-    } else {
-      seed_states_beam_kernel<false><<<grid, 64 * W, W * wave_bytes, c->stream>>>(b);
-    }
-  }
-  HIP_TRY(hipGetLastError());
-  DBG_SYNC(c, "seed_states_beam");
-  if (path_out) HIP_TRY(hipMemcpyAsync(path_out, a.path, n_out * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (lpj_out) HIP_TRY(hipMemcpyAsync(lpj_out, a.lpj_path, n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  on_kn_complete(c);
-  return 0;
+                "member is a stored state; SEED_BEAM_MAX = %d)", beam, c->S / max_active, SEED_BEAM_MAX, SEED_BEAM_MAX);
+  return seed_states_run(c, max_active, beam, path_out, lpj_out);
 }
 
-// ---------------------------------------------------------------------------------------
-// Local search on K^n: the one-flip neighbours of its best states (kernels_sweep.hpp has the law).  A sweep is the proposal
-// kernel into the resident candidate batch, the model's own lpj of the emitted rows and the selection; the lpj rows of K^n
-// stay what a pass over it would give.  Every refusal comes before the first write.
+// ---- local search on K^n: the one-flip and the swap neighbours of its best states (kernels_sweep.hpp and
+// kernels_sweep_swap.hpp have the laws).  A sweep is the proposal kernels into the resident candidate batch, the model's own
+// lpj of the emitted rows and the selection; the lpj rows of K^n stay what a pass over it would give.
 // EVOAMD_SWEEP_INCOMPLETE is a permission, like EVOAMD_SEED_INCOMPLETE: with masks resident the masked instantiation runs (the
 // datapoint's own Gram quantities from W and the mask), without masks the complete one, whatever the flag says.
-// ---------------------------------------------------------------------------------------
 struct SweepPlan {
-  int W = 4;
-  size_t wave_bytes = 0;
-  unsigned grid = 1;
+  KnLaunch flip, swap;  // the flip stage; the swap stage (EVOAMD_SWEEP_SWAP)
   bool masked = false;
-  int R = 0;              // masked ES3C: rows of G(n) per wavefront (SWEEP_ROWS)
-  bool rows_lds = false;  // ... their home: LDS while one wavefront's share fits, else a buffer of the context
-  // the swap stage (evoamd_sweep_*_nb; kernels_sweep_swap.hpp): nb = the EVOAMD_SWEEP_SWAP / EVOAMD_SWEEP_NO_FLIP bits, 0 = flips only
-  unsigned nb = 0;
-  int swap_W = 4;
-  size_t swap_wave_bytes = 0;
-  unsigned swap_grid = 1;
+  KnRows rows;          // masked ES3C: the SWEEP_ROWS rows of G(n) per wavefront
+  unsigned nb = 0;      // the EVOAMD_SWEEP_SWAP / EVOAMD_SWEEP_NO_FLIP bits, 0 = flips only
 };
 
-static int sweep_check(const evoamd_ctx *c, int n_parents, int n_keep, unsigned flags, SweepPlan &p) {
+// admits: the flag bits the entry point knows -- 0 (the plain calls), EVOAMD_SWEEP_INCOMPLETE (_ex) or all three (_nb)
+static int sweep_plan(const evoamd_ctx *c, int n_parents, int n_keep, unsigned flags, unsigned admits, SweepPlan &p) {
   REQUIRE(c && c->configured, "configure first");
-  REQUIRE(!(flags & ~(unsigned)EVOAMD_SWEEP_INCOMPLETE), "sweep: unknown flag");
-  REQUIRE(c->have_params, "sweep: no Theta installed (set parameters first)");
-  REQUIRE(c->have_data, "sweep: no data (upload data first)");
-  REQUIRE_KN(c);
-  REQUIRE(!c->mask_infr || (flags & EVOAMD_SWEEP_INCOMPLETE), "sweep: incomplete data (masks present) is not supported");
-  REQUIRE(!c->bg_unit, "sweep: option background_unit is not supported");
-  REQUIRE(!c->f32, "sweep is not available in the float32 mode (ebsc_f32)");
-  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
-  REQUIRE(sssc || !c->bsc_direct, "sweep: bsc_direct keeps no G = W^T W, which the scores need");
+  REQUIRE(!(flags & ~admits), "sweep: unknown flag");
+  REQUIRE((flags & EVOAMD_SWEEP_SWAP) || !(flags & EVOAMD_SWEEP_NO_FLIP),
+          "sweep: EVOAMD_SWEEP_NO_FLIP is valid only together with EVOAMD_SWEEP_SWAP");
+  REQUIRE(!(flags & EVOAMD_SWEEP_SWAP) || !(flags & EVOAMD_SWEEP_INCOMPLETE),
+          "sweep: EVOAMD_SWEEP_SWAP together with EVOAMD_SWEEP_INCOMPLETE: swaps on incomplete data are not supported");
+  TRY(kn_admit(c, "sweep", (flags & EVOAMD_SWEEP_INCOMPLETE) ? nullptr : "sweep: incomplete data (masks present) is not supported",
+               /*need_kn=*/true));
   if (n_parents < 1 || n_parents > c->S || n_parents > SWEEP_MAX_P)
     return fail(EVOAMD_E_INVALID, "sweep: n_parents = %d must be in [1, min(S = %d, %d)]", n_parents, c->S, SWEEP_MAX_P);
   REQUIRE(n_keep >= 1, "sweep: n_keep must be positive");
   if ((i64)n_parents * n_keep > c->Cmax)
     return fail(EVOAMD_E_INVALID, "sweep: n_parents * n_keep = %lld exceeds the configured Cmax = %d", (long long)n_parents * n_keep,
                 c->Cmax);
-  const int Hp = (int)cdiv(c->H, 64) * 64;
+  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
   p.masked = c->mask_infr != nullptr;
-  if (!p.masked) {
-    p.wave_bytes = sweep_wave_bytes(sssc, Hp, c->HW, n_keep);
-    REQUIRE(p.wave_bytes <= 150 * 1024, "sweep: the keys of one datapoint (8 or 16 H bytes) do not fit one wavefront's share of LDS");
-    p.W = 4;
-    while (p.W > 1 && p.W * p.wave_bytes > 150 * 1024) p.W >>= 1;
-    p.grid = (unsigned)std::min<i64>(cdiv(c->N, p.W), (i64)c->n_cu * 64);
-    return 0;
-  }
-  p.R = sssc ? SWEEP_ROWS : 0;
-  p.rows_lds = p.R && sweep_masked_wave_bytes(sssc, Hp, c->HW, n_keep, c->D, p.R) <= 150 * 1024;
-  p.wave_bytes = sweep_masked_wave_bytes(sssc, Hp, c->HW, n_keep, c->D, p.rows_lds ? p.R : 0);
-  REQUIRE(p.wave_bytes <= 150 * 1024, "sweep: the keys of one datapoint (8 or 24 H bytes), the staged column of W (8 D bytes) and the "
-                                      "list of the reliable entries (4 D bytes) do not fit one wavefront's share of LDS");
-  p.W = 4;
-  while (p.W > 1 && p.W * p.wave_bytes > 150 * 1024) p.W--;
-  // (rows in global memory: fewer workgroups, each wavefront of the grid owns R Hp doubles)
-  p.grid = (unsigned)std::min<i64>(cdiv(c->N, p.W), (i64)c->n_cu * (p.R && !p.rows_lds ? 4 : 64));
-  return 0;
-}
-
-// The checks of the _nb calls with a swap bit set: the flag rules, everything sweep_check refuses for complete data, the
-// quota of two stages and the swap kernel's share of LDS.
-static int sweep_check_nb(const evoamd_ctx *c, int n_parents, int n_keep, unsigned flags, SweepPlan &p) {
-  REQUIRE(c && c->configured, "configure first");
-  REQUIRE(!(flags & ~(unsigned)(EVOAMD_SWEEP_INCOMPLETE | EVOAMD_SWEEP_SWAP | EVOAMD_SWEEP_NO_FLIP)), "sweep: unknown flag");
-  REQUIRE((flags & EVOAMD_SWEEP_SWAP) || !(flags & EVOAMD_SWEEP_NO_FLIP),
-          "sweep: EVOAMD_SWEEP_NO_FLIP is valid only together with EVOAMD_SWEEP_SWAP");
-  REQUIRE(!(flags & EVOAMD_SWEEP_INCOMPLETE),
-          "sweep: EVOAMD_SWEEP_SWAP together with EVOAMD_SWEEP_INCOMPLETE: swaps on incomplete data are not supported");
-  TRY(sweep_check(c, n_parents, n_keep, 0u, p));
-  const bool both = !(flags & EVOAMD_SWEEP_NO_FLIP);
-  if (both && (i64)2 * n_parents * n_keep > c->Cmax)
+  const SeedLdsKind kind = p.masked ? SEED_LDS_FLIP_MASKED : SEED_LDS_FLIP;
+  SeedLdsShape shape = {sssc, (int)cdiv(c->H, 64) * 64, c->HW, n_keep, 0, 0, p.masked ? c->D : 0, 0, c->S};
+  p.rows = kn_plan_rows(kind, shape, p.masked && sssc ? SWEEP_ROWS : 0);
+  shape.rows_lds = p.rows.lds;
+  TRY(kn_plan_launch(c, seed_lds_bytes(kind, shape),
+                     p.masked ? "sweep: the keys of one datapoint (8 or 24 H bytes), the staged column of W (8 D bytes) and the "
+                                "list of the reliable entries (4 D bytes) do not fit one wavefront's share of LDS"
+                              : "sweep: the keys of one datapoint (8 or 16 H bytes) do not fit one wavefront's share of LDS",
+                     p.rows.cu_mult, p.masked ? KN_STEP_DECREMENT : KN_STEP_HALVE, p.flip));
+  p.nb = flags & (EVOAMD_SWEEP_SWAP | EVOAMD_SWEEP_NO_FLIP);
+  if (!p.nb) return 0;
+  // the swap stage: the quota of two stages and the swap kernel's share of LDS
+  if (!(flags & EVOAMD_SWEEP_NO_FLIP) && (i64)2 * n_parents * n_keep > c->Cmax)
     return fail(EVOAMD_E_INVALID, "sweep: 2 * n_parents * n_keep = %lld (flips and swaps, n_keep rows per parent each) exceeds the "
                                   "configured Cmax = %d", (long long)2 * n_parents * n_keep, c->Cmax);
-  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
-  p.swap_wave_bytes = sweep_swap_wave_bytes(sssc, (int)cdiv(c->H, 64) * 64, c->HW, n_keep, c->S);
-  REQUIRE(p.swap_wave_bytes <= 150 * 1024, "sweep: the keys of one datapoint (8 or 16 H bytes), the running lists of the swap stage "
-                                           "(32 n_keep bytes) and the held pairs (4 S bytes) do not fit one wavefront's share of LDS");
-  p.swap_W = 4;
-  while (p.swap_W > 1 && p.swap_W * p.swap_wave_bytes > 150 * 1024) p.swap_W >>= 1;
-  p.swap_grid = (unsigned)std::min<i64>(cdiv(c->N, p.swap_W), (i64)c->n_cu * 64);
-  p.nb = flags & (EVOAMD_SWEEP_SWAP | EVOAMD_SWEEP_NO_FLIP);
-  return 0;
+  return kn_plan_launch(c, seed_lds_bytes(SEED_LDS_SWAP, shape),
+                        "sweep: the keys of one datapoint (8 or 16 H bytes), the running lists of the swap stage "
+                        "(32 n_keep bytes) and the held pairs (4 S bytes) do not fit one wavefront's share of LDS",
+                        64, KN_STEP_HALVE, p.swap);
 }
 
 // the buffers a sweep needs, B = Y W, (ES3C) the transpose of GP: once per call, Theta stays fixed
@@ -5968,69 +5953,52 @@ static int sweep_prepare(evoamd_ctx *c, const SweepPlan &p) {
     TRY(c->swap_d.ensure(c, N));
     TRY(c->swap_i.ensure(c, 3 * N));
   }
-  if (p.R && !p.rows_lds) TRY(c->seed_rows.ensure(c, (size_t)p.grid * p.W * p.R * ((size_t)cdiv(c->H, 64) * 64)));
+  const size_t rows = p.rows.doubles(p.flip, (int)cdiv(c->H, 64) * 64);
+  if (rows) TRY(c->seed_rows.ensure(c, rows));
   TRY(c->sweep_d.ensure(c, N * c->Cmax + N));
   TRY(c->sweep_i.ensure(c, 2 * N));
   if (c->model == EVOAMD_MODEL_SSSC) {
     TRY(ensure_lists(c, c->N * (i64)c->Cmax));
     TRY(c->seed_gpt.ensure(c, (size_t)c->H * c->H));
     SpanGuard g(c, KID_SWEEP);
-    seed_transpose_gp_kernel<<<cdiv((i64)c->H * c->H, 256), 256, 0, c->stream>>>(c->GP, c->H, c->seed_gpt);
+    TRY(kn_transpose_gp(c));
     HIP_TRY(hipGetLastError());
   }
   return 0;
 }
 
-// ---- one sweep's proposals: the kernel, then the lpj of the emitted rows ("nothing known" level hints)
+// ---- one sweep's proposals: the kernels, then the lpj of the emitted rows ("nothing known" level hints)
 static int sweep_propose_stage(evoamd_ctx *c, const SweepPlan &p, int n_parents, int n_keep, bool want_score) {
   const size_t N = (size_t)c->N;
-  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
-  SweepArgs a = {};
-  a.sd.states = c->states;
-  a.sd.Bm = c->Bm, a.sd.yy = c->yy;
-  a.sd.G = c->G, a.sd.Gd = c->diag;
-  a.sd.GP = c->GP, a.sd.GPt = c->seed_gpt;
-  a.sd.mus = c->mus, a.sd.pil_bar = c->pilbar_v;
-  a.sd.dpar = c->dpar, a.sd.err = c->err;
-  a.sd.N = c->N;
-  a.sd.S = c->S, a.sd.H = c->H, a.sd.HW = c->HW, a.sd.Hp = (int)cdiv(c->H, 64) * 64, a.sd.Q = n_keep;
+  SweepSwapArgs b = {};
+  SweepArgs &a = b.sw;  // (the flip kernels take the SweepArgs alone)
+  fill_seed_args(c, a.sd);
+  a.sd.Q = n_keep;
+  if (p.masked) {
+    a.sd.R = p.rows.R;
+    a.sd.rows = p.rows.R && !p.rows.lds ? c->seed_rows.get() : nullptr;
+  }
   a.lpj = c->lpj;
   a.cand = c->cand, a.cand_dig = (c->use_digest && c->cand_dig) ? c->cand_dig.get() : nullptr, a.counts = c->cand_counts;
   a.score = want_score ? c->sweep_d.get() : nullptr;
   a.gain = c->sweep_d + N * c->Cmax;
   a.best_flip = c->sweep_i, a.n_capped = c->sweep_i + N;
   a.L = c->L, a.S_perm = c->S_perm, a.P = n_parents, a.q = n_keep, a.Cmax = c->Cmax;
-  if (p.masked) {
-    a.sd.W = c->W, a.sd.mask = c->mask_infr, a.sd.D = c->D, a.sd.R = p.R;
-    a.sd.rows = p.R && !p.rows_lds ? c->seed_rows.get() : nullptr;
-  }
   if (want_score && (p.nb & EVOAMD_SWEEP_NO_FLIP))
     HIP_TRY(hipMemsetAsync(c->sweep_d, 0xFF, N * c->Cmax * sizeof(double), c->stream));  // rows not emitted: NaN
   if (!(p.nb & EVOAMD_SWEEP_NO_FLIP)) {
     SpanGuard g(c, KID_SWEEP);
     if (want_score) HIP_TRY(hipMemsetAsync(c->sweep_d, 0xFF, N * c->Cmax * sizeof(double), c->stream));  // rows not emitted: NaN
-    if (p.masked && sssc)
-      sweep_neighbours_kernel<true, true><<<p.grid, 64 * p.W, p.W * p.wave_bytes, c->stream>>>(a);
-    else if (p.masked)
-      sweep_neighbours_kernel<false, true><<<p.grid, 64 * p.W, p.W * p.wave_bytes, c->stream>>>(a);
-    else if (sssc)
-      sweep_neighbours_kernel<true><<<p.grid, 64 * p.W, p.W * p.wave_bytes, c->stream>>>(a);
-    else
-      sweep_neighbours_kernel<false><<<p.grid, 64 * p.W, p.W * p.wave_bytes, c->stream>>>(a);
+    TRY(kn_launch(c, p.masked ? SEED_LDS_FLIP_MASKED : SEED_LDS_FLIP, p.flip, a));
     HIP_TRY(hipGetLastError());
     DBG_SYNC(c, "sweep proposals");
   }
   if (p.nb & EVOAMD_SWEEP_SWAP) {  // the swap stage: its rows go behind the flip stage's
-    SweepSwapArgs b = {};
-    b.sw = a;
     b.swap_gain = c->swap_d;
     b.best_swap = c->swap_i, b.n_capped_swap = c->swap_i + 2 * N;
     b.append = (p.nb & EVOAMD_SWEEP_NO_FLIP) ? 0 : 1;
     SpanGuard g(c, KID_SWEEP_SWAP);
-    if (sssc)
-      sweep_swap_kernel<true><<<p.swap_grid, 64 * p.swap_W, p.swap_W * p.swap_wave_bytes, c->stream>>>(b);
-    else
-      sweep_swap_kernel<false><<<p.swap_grid, 64 * p.swap_W, p.swap_W * p.swap_wave_bytes, c->stream>>>(b);
+    TRY(kn_launch(c, SEED_LDS_SWAP, p.swap, b));
     HIP_TRY(hipGetLastError());
     DBG_SYNC(c, "sweep swap proposals");
   }
@@ -6040,42 +6008,40 @@ static int sweep_propose_stage(evoamd_ctx *c, const SweepPlan &p, int n_parents,
   return 0;
 }
 
-static int sweep_fetch(evoamd_ctx *c, double *score_out, int32_t *best_flip_out, double *gain_out, int32_t *n_capped_out,
-                       int32_t *best_swap_out = nullptr, double *swap_gain_out = nullptr, int32_t *n_capped_swap_out = nullptr) {
+// the outputs of the stages that ran, each where the caller gave a buffer; score: only evoamd_sweep_propose_* return it
+static int sweep_fetch(evoamd_ctx *c, const SweepPlan &p, const evoamd_sweep_out &o, bool score) {
   const size_t N = (size_t)c->N;
-  if (best_swap_out) HIP_TRY(hipMemcpyAsync(best_swap_out, c->swap_i, 2 * N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (swap_gain_out) HIP_TRY(hipMemcpyAsync(swap_gain_out, c->swap_d, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (n_capped_swap_out)
-    HIP_TRY(hipMemcpyAsync(n_capped_swap_out, c->swap_i + 2 * N, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (score_out) HIP_TRY(hipMemcpyAsync(score_out, c->sweep_d, N * c->Cmax * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (gain_out) HIP_TRY(hipMemcpyAsync(gain_out, c->sweep_d + N * c->Cmax, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (best_flip_out) HIP_TRY(hipMemcpyAsync(best_flip_out, c->sweep_i, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (n_capped_out) HIP_TRY(hipMemcpyAsync(n_capped_out, c->sweep_i + N, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  const bool flips = !(p.nb & EVOAMD_SWEEP_NO_FLIP), swaps = (p.nb & EVOAMD_SWEEP_SWAP) != 0;
+  if (swaps && o.best_swap) HIP_TRY(hipMemcpyAsync(o.best_swap, c->swap_i, 2 * N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (swaps && o.swap_gain) HIP_TRY(hipMemcpyAsync(o.swap_gain, c->swap_d, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (swaps && o.n_capped_swap)
+    HIP_TRY(hipMemcpyAsync(o.n_capped_swap, c->swap_i + 2 * N, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (score && o.score) HIP_TRY(hipMemcpyAsync(o.score, c->sweep_d, N * c->Cmax * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (flips && o.gain) HIP_TRY(hipMemcpyAsync(o.gain, c->sweep_d + N * c->Cmax, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (flips && o.best_flip) HIP_TRY(hipMemcpyAsync(o.best_flip, c->sweep_i, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (flips && o.n_capped) HIP_TRY(hipMemcpyAsync(o.n_capped, c->sweep_i + N, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   if (c->model == EVOAMD_MODEL_SSSC) return check_err(c);
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
 
-extern "C" int evoamd_sweep_propose_ex(evoamd_ctx *c, int n_parents, int n_keep, unsigned flags, double *score_out,
-                                       int32_t *best_flip_out, double *gain_out, int32_t *n_capped_out) {
+// the body of evoamd_sweep_propose / _ex / _nb
+static int sweep_propose_run(evoamd_ctx *c, int n_parents, int n_keep, unsigned flags, unsigned admits, const evoamd_sweep_out &o) {
   SweepPlan p;
-  TRY(sweep_check(c, n_parents, n_keep, flags, p));
+  TRY(sweep_plan(c, n_parents, n_keep, flags, admits, p));
   HIP_TRY(hipSetDevice(c->device));
   TRY(sweep_prepare(c, p));
   on_estep_route(c, /*fused=*/false);
   TRY(estep_resident_pass(c));
-  TRY(sweep_propose_stage(c, p, n_parents, n_keep, score_out != nullptr));
-  return sweep_fetch(c, score_out, best_flip_out, gain_out, n_capped_out);
+  TRY(sweep_propose_stage(c, p, n_parents, n_keep, o.score != nullptr));
+  return sweep_fetch(c, p, o, /*score=*/true);
 }
 
-extern "C" int evoamd_sweep_propose(evoamd_ctx *c, int n_parents, int n_keep, double *score_out, int32_t *best_flip_out,
-                                    double *gain_out, int32_t *n_capped_out) {
-  return evoamd_sweep_propose_ex(c, n_parents, n_keep, 0u, score_out, best_flip_out, gain_out, n_capped_out);
-}
-
-// the loop of evoamd_sweep_states_ex / evoamd_sweep_states_nb behind the plan's checks
-static int sweep_states_run(evoamd_ctx *c, const SweepPlan &p, int n_sweeps, int n_parents, int n_keep, int Mprime,
-                            int stop_when_quiet, double *trace_out, int *n_done_out, const evoamd_sweep_out &o) {
+// the body of evoamd_sweep_states / _ex / _nb
+static int sweep_states_run(evoamd_ctx *c, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet, unsigned flags,
+                            unsigned admits, double *trace_out, int *n_done_out, const evoamd_sweep_out &o) {
+  SweepPlan p;
+  TRY(sweep_plan(c, n_parents, n_keep, flags, admits, p));
   TRY(estep_check_mprime(c, Mprime));
   REQUIRE(n_sweeps >= 1, "evoamd_sweep_states: n_sweeps must be positive");
   REQUIRE(trace_out && n_done_out, "evoamd_sweep_states: trace_out / n_done_out is NULL");
@@ -6104,56 +6070,51 @@ static int sweep_states_run(evoamd_ctx *c, const SweepPlan &p, int n_sweeps, int
     HIP_TRY(hipMemcpyAsync(trace_out + 3 * copied, c->refine_trace + 3 * copied, (size_t)3 * (done - copied) * sizeof(double),
                            hipMemcpyDeviceToHost, c->stream));
   *n_done_out = done;
-  const bool flips = !(p.nb & EVOAMD_SWEEP_NO_FLIP), swaps = (p.nb & EVOAMD_SWEEP_SWAP) != 0;
-  return sweep_fetch(c, nullptr, flips ? o.best_flip : nullptr, flips ? o.gain : nullptr, flips ? o.n_capped : nullptr,
-                     swaps ? o.best_swap : nullptr, swaps ? o.swap_gain : nullptr, swaps ? o.n_capped_swap : nullptr);
+  return sweep_fetch(c, p, o, /*score=*/false);
 }
 
-extern "C" int evoamd_sweep_states_ex(evoamd_ctx *c, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
-                                      unsigned flags, double *trace_out, int *n_done_out, int32_t *best_flip_out,
-                                      double *gain_out, int32_t *n_capped_out) {
-  SweepPlan p;
-  TRY(sweep_check(c, n_parents, n_keep, flags, p));
+// The three generations of the sweep ABI forward to the two bodies: the plain calls admit no flag, the _ex calls
+// EVOAMD_SWEEP_INCOMPLETE (the swap bits are unknown flags to them), the _nb calls all three.
+static evoamd_sweep_out sweep_flip_out(double *score, int32_t *best_flip, double *gain, int32_t *n_capped) {
   evoamd_sweep_out o = {};
-  o.best_flip = best_flip_out, o.gain = gain_out, o.n_capped = n_capped_out;
-  return sweep_states_run(c, p, n_sweeps, n_parents, n_keep, Mprime, stop_when_quiet, trace_out, n_done_out, o);
+  o.score = score, o.best_flip = best_flip, o.gain = gain, o.n_capped = n_capped;
+  return o;
+}
+static const unsigned SWEEP_NB_FLAGS = EVOAMD_SWEEP_INCOMPLETE | EVOAMD_SWEEP_SWAP | EVOAMD_SWEEP_NO_FLIP;
+
+extern "C" int evoamd_sweep_propose(evoamd_ctx *c, int n_parents, int n_keep, double *score_out, int32_t *best_flip_out,
+                                    double *gain_out, int32_t *n_capped_out) {
+  return sweep_propose_run(c, n_parents, n_keep, 0u, 0u, sweep_flip_out(score_out, best_flip_out, gain_out, n_capped_out));
 }
 
-// The _nb calls: without a swap bit exactly the _ex calls; with one, the swap stage beside (or instead of) the flip stage.
+extern "C" int evoamd_sweep_propose_ex(evoamd_ctx *c, int n_parents, int n_keep, unsigned flags, double *score_out,
+                                       int32_t *best_flip_out, double *gain_out, int32_t *n_capped_out) {
+  return sweep_propose_run(c, n_parents, n_keep, flags, EVOAMD_SWEEP_INCOMPLETE,
+                           sweep_flip_out(score_out, best_flip_out, gain_out, n_capped_out));
+}
+
 extern "C" int evoamd_sweep_propose_nb(evoamd_ctx *c, int n_parents, int n_keep, unsigned flags, const evoamd_sweep_out *out) {
-  const evoamd_sweep_out none = {};
-  const evoamd_sweep_out &o = out ? *out : none;
-  if (!(flags & (EVOAMD_SWEEP_SWAP | EVOAMD_SWEEP_NO_FLIP)))
-    return evoamd_sweep_propose_ex(c, n_parents, n_keep, flags, o.score, o.best_flip, o.gain, o.n_capped);
-  SweepPlan p;
-  TRY(sweep_check_nb(c, n_parents, n_keep, flags, p));
-  HIP_TRY(hipSetDevice(c->device));
-  TRY(sweep_prepare(c, p));
-  on_estep_route(c, /*fused=*/false);
-  TRY(estep_resident_pass(c));
-  TRY(sweep_propose_stage(c, p, n_parents, n_keep, o.score != nullptr));
-  const bool flips = !(flags & EVOAMD_SWEEP_NO_FLIP);
-  return sweep_fetch(c, o.score, flips ? o.best_flip : nullptr, flips ? o.gain : nullptr, flips ? o.n_capped : nullptr, o.best_swap,
-                     o.swap_gain, o.n_capped_swap);
-}
-
-extern "C" int evoamd_sweep_states_nb(evoamd_ctx *c, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
-                                      unsigned flags, double *trace_out, int *n_done_out, const evoamd_sweep_out *out) {
-  const evoamd_sweep_out none = {};
-  const evoamd_sweep_out &o = out ? *out : none;
-  if (!(flags & (EVOAMD_SWEEP_SWAP | EVOAMD_SWEEP_NO_FLIP)))
-    return evoamd_sweep_states_ex(c, n_sweeps, n_parents, n_keep, Mprime, stop_when_quiet, flags, trace_out, n_done_out, o.best_flip,
-                                  o.gain, o.n_capped);
-  SweepPlan p;
-  TRY(sweep_check_nb(c, n_parents, n_keep, flags, p));
-  return sweep_states_run(c, p, n_sweeps, n_parents, n_keep, Mprime, stop_when_quiet, trace_out, n_done_out, o);
+  return sweep_propose_run(c, n_parents, n_keep, flags, SWEEP_NB_FLAGS, out ? *out : evoamd_sweep_out{});
 }
 
 extern "C" int evoamd_sweep_states(evoamd_ctx *c, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
                                    double *trace_out, int *n_done_out, int32_t *best_flip_out, double *gain_out,
                                    int32_t *n_capped_out) {
-  return evoamd_sweep_states_ex(c, n_sweeps, n_parents, n_keep, Mprime, stop_when_quiet, 0u, trace_out, n_done_out, best_flip_out,
-                                gain_out, n_capped_out);
+  return sweep_states_run(c, n_sweeps, n_parents, n_keep, Mprime, stop_when_quiet, 0u, 0u, trace_out, n_done_out,
+                          sweep_flip_out(nullptr, best_flip_out, gain_out, n_capped_out));
+}
+
+extern "C" int evoamd_sweep_states_ex(evoamd_ctx *c, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
+                                      unsigned flags, double *trace_out, int *n_done_out, int32_t *best_flip_out,
+                                      double *gain_out, int32_t *n_capped_out) {
+  return sweep_states_run(c, n_sweeps, n_parents, n_keep, Mprime, stop_when_quiet, flags, EVOAMD_SWEEP_INCOMPLETE, trace_out,
+                          n_done_out, sweep_flip_out(nullptr, best_flip_out, gain_out, n_capped_out));
+}
+
+extern "C" int evoamd_sweep_states_nb(evoamd_ctx *c, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
+                                      unsigned flags, double *trace_out, int *n_done_out, const evoamd_sweep_out *out) {
+  return sweep_states_run(c, n_sweeps, n_parents, n_keep, Mprime, stop_when_quiet, flags, SWEEP_NB_FLAGS, trace_out, n_done_out,
+                          out ? *out : evoamd_sweep_out{});
 }
 
 // posterior samples (kernels_posterior_sample.hpp): own buffers; of the EM state only B = Y W is (re)formed, like every lpj pass

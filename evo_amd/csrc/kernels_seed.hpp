@@ -66,17 +66,169 @@ struct SeedArgs {
   int D, R;             // R: rows of G(n) a wavefront keeps (ES3C: A - 1 winners' rows and the diagonal; EBSC: 0)
 };
 
-__host__ __device__ inline size_t seed_wave_bytes(int Hp, int HW, int Q, int A) {
-  size_t b = (size_t)2 * Hp * 8 + (size_t)HW * 8 + (size_t)SEED_SHARED_DOUBLES * 8 + (size_t)Q * 8 + (size_t)2 * Q * 4 + (size_t)2 * A * 4;
-  return (b + 15) & ~(size_t)15;
+// ONE WAVEFRONT'S SHARE OF LDS, described once for the host (which takes the total) and the kernels (which take their
+// pointers from the same walk).  One description per kernel of the family; nothing else carves LDS in kernels_seed.hpp,
+// kernels_seed_beam.hpp, kernels_sweep.hpp and kernels_sweep_swap.hpp.  8-byte regions first, then the ints; a masked or
+// swap kernel's extras start behind the complete kernel's share rounded to 16 bytes.
+#define SWEEP_PATH 16                 // sweeps: active latents of a parent kept as a list (ES3C reads at most 9)
+#define SWEEP_MAX_P 64                // sweeps: parents per datapoint
+#define SWAP_LIST SEED_MAX_A_BSC      // swap sweep: the parent's active latents as a list, every a of a scored parent
+enum SeedLdsKind { SEED_LDS_GREEDY, SEED_LDS_GREEDY_MASKED, SEED_LDS_BEAM, SEED_LDS_FLIP, SEED_LDS_FLIP_MASKED, SEED_LDS_SWAP,
+                   SEED_LDS_KINDS };
+struct SeedLdsShape {
+  bool sssc;
+  int Hp, HW, Q;      // Q: the largest quota (sweeps: n_keep)
+  int A, B;           // seeding: max_active; the beam
+  int D, rows_lds;    // masked: entries per datapoint; the rows of G(n) whose home is LDS (0: a.rows holds them)
+  int S;              // swap sweep: states per datapoint
+};
+// Two cursors walk the one description: SeedLdsOffsets yields byte offsets and the total (host, and the kernels for their
+// share's size), SeedLdsPointers the typed pointers from a wavefront's home (kernels).  A region the kernel kind does not
+// have stays 0 / nullptr.
+struct SeedLdsOffsets {
+  template <class T>
+  using at = size_t;
+  size_t pos = 0;
+  template <class T>
+  __host__ __device__ constexpr size_t take(size_t n) {
+    const size_t o = pos;
+    pos += n * sizeof(T);
+    return o;
+  }
+  __host__ __device__ constexpr void align16() { pos = (pos + 15) & ~(size_t)15; }
+  __host__ __device__ constexpr void seek(size_t to) { pos = to; }
+  __host__ __device__ constexpr size_t used() const { return pos; }
+};
+struct SeedLdsPointers {
+  template <class T>
+  using at = T *;
+  unsigned char *home, *p;
+  template <class T>
+  __host__ __device__ T *take(size_t n) {
+    T *r = (T *)p;
+    p = (unsigned char *)(r + n);
+    return r;
+  }
+  __host__ __device__ void align16() { p = home + (((size_t)(p - home) + 15) & ~(size_t)15); }
+  __host__ __device__ void seek(size_t to) { p = home + to; }
+  __host__ __device__ size_t used() const { return (size_t)(p - home); }
+};
+template <class C>
+struct SeedLdsRegions {
+  template <class T>
+  using at = typename C::template at<T>;
+  at<u64> keys = {};
+  at<double> cc = {};
+  at<u64> base = {};
+  at<double> sh = {};
+  at<u64> selk = {};
+  at<int> sel = {}, byrank = {}, path = {}, sorted = {};
+  at<int> parents = {};                                   // sweeps: the parents' slots
+  at<double> gd = {}, col = {}, rows = {};                // incomplete data
+  at<int> dl = {};
+  at<u64> rk[2] = {};                                     // beam, swap: the running lists (key, parent | a, j)
+  at<int> rp[2] = {}, rj[2] = {};
+  at<double> msc = {};                                    // the two beams
+  at<u64> mwords = {};
+  at<int> mpath = {}, msorted = {};
+  at<int> full = {};                                      // swap sweep
+  at<unsigned> held = {};
+  size_t total = 0;  // rounded up to 16 bytes
+};
+__host__ __device__ constexpr size_t seed_lds_bytes(SeedLdsKind kind, const SeedLdsShape &s);
+template <class C>
+__host__ __device__ constexpr SeedLdsRegions<C> seed_lds_walk(SeedLdsKind kind, const SeedLdsShape &s, C c) {
+  const bool beam = kind == SEED_LDS_BEAM, sweep = kind == SEED_LDS_FLIP || kind == SEED_LDS_FLIP_MASKED || kind == SEED_LDS_SWAP;
+  const size_t Hp = (size_t)s.Hp, Q = (size_t)s.Q;
+  SeedLdsRegions<C> l;
+  l.keys = c.template take<u64>(Hp);  // (masked EBSC seeding: also tmp, a row on its way into e)
+  if (!beam) {
+    l.cc = c.template take<double>(sweep && s.sssc ? 0 : Hp);  // EBSC e_j / c_j (the seeding kernels keep the region for ES3C too)
+    l.base = c.template take<u64>((size_t)s.HW);              // the words of A_{t-1} / of the parent
+  }
+  l.sh = c.template take<double>(sweep && !s.sssc ? 0 : SEED_SHARED_DOUBLES);
+  l.selk = c.template take<u64>(Q);
+  if (beam) {
+    l.rk[0] = c.template take<u64>(Q), l.rk[1] = c.template take<u64>(Q);
+    l.msc = c.template take<double>((size_t)2 * s.B);
+    l.mwords = c.template take<u64>((size_t)2 * s.B * s.HW);
+  }
+  l.sel = c.template take<int>(Q), l.byrank = c.template take<int>(Q);
+  if (beam) {
+    l.rp[0] = c.template take<int>(Q), l.rj[0] = c.template take<int>(Q);
+    l.rp[1] = c.template take<int>(Q), l.rj[1] = c.template take<int>(Q);
+    l.mpath = c.template take<int>((size_t)2 * s.B * s.A);
+    l.msorted = c.template take<int>((size_t)2 * s.B * s.A);
+  } else if (sweep) {
+    l.path = c.template take<int>(SWEEP_PATH);
+    l.parents = c.template take<int>(SWEEP_MAX_P);
+  } else {
+    l.path = c.template take<int>((size_t)s.A);
+    l.sorted = c.template take<int>((size_t)s.A);
+  }
+  c.align16();
+  // The extras of the sweeps start behind the flip kernel's share.  The cursor is set there from that kind's own total, not
+  // left where the walk arrived: the same place, but measured -- the masked ES3C flip sweep, which fills the register file,
+  // runs 3.6 % slower with its addresses formed from where the walk arrived, and masked EBSC seeding 1 % slower with them
+  // formed from the total, so seeding keeps the walk's position
+  if (kind == SEED_LDS_FLIP_MASKED || kind == SEED_LDS_SWAP) c.seek(seed_lds_bytes(SEED_LDS_FLIP, s));
+  if (kind == SEED_LDS_GREEDY_MASKED || kind == SEED_LDS_FLIP_MASKED) {
+    // EBSC sweep: the diagonal g_jj; the staged column of W; ES3C the rows of G(n) when LDS is their home; the reliable d
+    if (kind == SEED_LDS_FLIP_MASKED) l.gd = c.template take<double>(s.sssc ? 0 : Hp);
+    l.col = c.template take<double>((size_t)s.D);
+    l.rows = c.template take<double>((size_t)s.rows_lds * Hp);
+    l.dl = c.template take<int>((size_t)s.D);
+    c.align16();
+  }
+  if (kind == SEED_LDS_SWAP) {  // the running lists, the parent's active latents, the held pairs
+    l.rk[0] = c.template take<u64>(Q), l.rk[1] = c.template take<u64>(Q);
+    l.rp[0] = c.template take<int>(Q), l.rj[0] = c.template take<int>(Q);
+    l.rp[1] = c.template take<int>(Q), l.rj[1] = c.template take<int>(Q);
+    l.full = c.template take<int>(SWAP_LIST);
+    l.held = c.template take<unsigned>((size_t)s.S);
+    c.align16();
+  }
+  l.total = c.used();
+  return l;
 }
-
-// masked kernel: behind the complete kernel's share the staged column m o W_.w (D doubles), the R rows of G(n) when LDS is
-// their home (rows_lds = R, else 0) and the list of the reliable d (D ints)
-__host__ __device__ inline size_t seed_masked_wave_bytes(int Hp, int HW, int Q, int A, int D, int rows_lds) {
-  size_t b = seed_wave_bytes(Hp, HW, Q, A) + (size_t)D * 8 + (size_t)rows_lds * Hp * 8 + (size_t)D * 4;
-  return (b + 15) & ~(size_t)15;
+__host__ __device__ constexpr size_t seed_lds_bytes(SeedLdsKind kind, const SeedLdsShape &s) {
+  return seed_lds_walk(kind, s, SeedLdsOffsets{}).total;
 }
+using SeedLdsView = SeedLdsRegions<SeedLdsPointers>;
+// wave's share of the workgroup's dynamic LDS as pointers
+__device__ __forceinline__ SeedLdsView seed_lds_view(unsigned char *lds, int wave, SeedLdsKind kind, const SeedLdsShape &s) {
+  unsigned char *home = lds + (size_t)wave * seed_lds_bytes(kind, s);
+  return seed_lds_walk(kind, s, SeedLdsPointers{home, home});
+}
+// The totals of the closed formulas this description replaced, evaluated on the host before they went: H = 100 (Hp = 128),
+// 512, 1100 (Hp = 1152, HW = 18) and 1800 (Hp = 1856, HW = 29); masked ES3C with the rows in LDS and without.  The shape
+// is {sssc, Hp, HW, Q, A, B, D, rows_lds, S}.
+static_assert(seed_lds_bytes(SEED_LDS_GREEDY, SeedLdsShape{false, 128, 2, 3, 4, 0, 0, 0, 0}) == 3488, "greedy seeding");
+static_assert(seed_lds_bytes(SEED_LDS_GREEDY, SeedLdsShape{true, 512, 8, 13, 5, 0, 0, 0, 0}) == 9856, "greedy seeding");
+static_assert(seed_lds_bytes(SEED_LDS_GREEDY, SeedLdsShape{false, 1152, 18, 8, 8, 0, 0, 0, 0}) == 20112, "greedy seeding");
+static_assert(seed_lds_bytes(SEED_LDS_GREEDY, SeedLdsShape{true, 1856, 29, 4, 3, 0, 0, 0, 0}) == 31360, "greedy seeding");
+static_assert(seed_lds_bytes(SEED_LDS_GREEDY_MASKED, SeedLdsShape{false, 128, 2, 3, 4, 0, 24, 0, 0}) == 3776, "masked seeding");
+static_assert(seed_lds_bytes(SEED_LDS_GREEDY_MASKED, SeedLdsShape{true, 128, 2, 3, 4, 0, 24, 4, 0}) == 7872, "masked seeding");
+static_assert(seed_lds_bytes(SEED_LDS_GREEDY_MASKED, SeedLdsShape{true, 512, 8, 13, 5, 0, 300, 0, 0}) == 13456, "masked seeding");
+static_assert(seed_lds_bytes(SEED_LDS_GREEDY_MASKED, SeedLdsShape{true, 1152, 18, 8, 8, 0, 37, 8, 0}) == 94288, "masked seeding");
+static_assert(seed_lds_bytes(SEED_LDS_GREEDY_MASKED, SeedLdsShape{false, 1856, 29, 4, 3, 0, 4, 0, 0}) == 31408, "masked seeding");
+static_assert(seed_lds_bytes(SEED_LDS_BEAM, SeedLdsShape{false, 128, 2, 3, 4, 1, 0, 0, 0}) == 2624, "beam seeding");
+static_assert(seed_lds_bytes(SEED_LDS_BEAM, SeedLdsShape{true, 512, 8, 13, 5, 4, 0, 0, 0}) == 6960, "beam seeding");
+static_assert(seed_lds_bytes(SEED_LDS_BEAM, SeedLdsShape{false, 1152, 18, 8, 8, 16, 0, 0, 0}) == 17856, "beam seeding");
+static_assert(seed_lds_bytes(SEED_LDS_BEAM, SeedLdsShape{true, 1856, 29, 4, 3, 2, 0, 0, 0}) == 17440, "beam seeding");
+static_assert(seed_lds_bytes(SEED_LDS_FLIP, SeedLdsShape{false, 128, 2, 3, 0, 0, 0, 0, 0}) == 2432, "flip sweep");
+static_assert(seed_lds_bytes(SEED_LDS_FLIP, SeedLdsShape{true, 128, 2, 3, 0, 0, 0, 0, 0}) == 2752, "flip sweep");
+static_assert(seed_lds_bytes(SEED_LDS_FLIP, SeedLdsShape{false, 1152, 18, 8, 0, 0, 0, 0, 0}) == 19024, "flip sweep");
+static_assert(seed_lds_bytes(SEED_LDS_FLIP, SeedLdsShape{true, 1856, 29, 4, 0, 0, 0, 0, 0}) == 16816, "flip sweep");
+static_assert(seed_lds_bytes(SEED_LDS_FLIP_MASKED, SeedLdsShape{true, 128, 2, 3, 0, 0, 24, 10, 0}) == 13280, "masked flip sweep");
+static_assert(seed_lds_bytes(SEED_LDS_FLIP_MASKED, SeedLdsShape{false, 512, 8, 13, 0, 0, 300, 0, 0}) == 16480, "masked flip sweep");
+static_assert(seed_lds_bytes(SEED_LDS_FLIP_MASKED, SeedLdsShape{true, 512, 8, 13, 0, 0, 300, 10, 0}) == 50592, "masked flip sweep");
+static_assert(seed_lds_bytes(SEED_LDS_FLIP_MASKED, SeedLdsShape{true, 1152, 18, 8, 0, 0, 37, 0, 0}) == 11600, "masked flip sweep");
+static_assert(seed_lds_bytes(SEED_LDS_FLIP_MASKED, SeedLdsShape{false, 1856, 29, 4, 0, 0, 4, 0, 0}) == 45216, "masked flip sweep");
+static_assert(seed_lds_bytes(SEED_LDS_SWAP, SeedLdsShape{false, 128, 2, 3, 0, 0, 0, 0, 30}) == 2912, "swap sweep");
+static_assert(seed_lds_bytes(SEED_LDS_SWAP, SeedLdsShape{true, 512, 8, 13, 0, 0, 0, 0, 64}) == 6960, "swap sweep");
+static_assert(seed_lds_bytes(SEED_LDS_SWAP, SeedLdsShape{false, 1152, 18, 8, 0, 0, 0, 0, 200}) == 20336, "swap sweep");
+static_assert(seed_lds_bytes(SEED_LDS_SWAP, SeedLdsShape{true, 1856, 29, 4, 0, 0, 0, 0, 6}) == 17232, "swap sweep");
 
 __device__ __forceinline__ void seed_wave_sync() {
   __threadfence_block();
@@ -238,7 +390,7 @@ __global__ __launch_bounds__(256) void seed_transpose_gp_kernel(const double2 *_
   GPt[idx] = GP[(size_t)c * H + r];
 }
 
-// One wavefront's share of LDS (file header)
+// One wavefront's share of LDS as pointers: the regions every kernel of the family hands to the shared device functions
 struct SeedLds {
   u64 *keys;
   double *cc;
@@ -247,20 +399,37 @@ struct SeedLds {
   u64 *selk;
   int *sel, *byrank, *path, *sorted;
 };
-__device__ __forceinline__ SeedLds seed_carve(unsigned char *home, int Hp, int HW, int Q, int A) {
+__device__ __forceinline__ SeedLds seed_carve(const SeedLdsView &v) {
   SeedLds L;
-  L.keys = (u64 *)home;
-  L.cc = (double *)(L.keys + Hp);
-  L.base = (u64 *)(L.cc + Hp);
-  double *shd = (double *)(L.base + HW);
+  L.keys = v.keys, L.cc = v.cc, L.base = v.base;
+  double *shd = v.sh;
   L.sh = {shd, shd + SEED_M * SEED_M, shd + 2 * SEED_M * SEED_M, shd + 3 * SEED_M * SEED_M,
           shd + 3 * SEED_M * SEED_M + SEED_M, shd + 3 * SEED_M * SEED_M + 2 * SEED_M};
-  L.selk = (u64 *)(shd + SEED_SHARED_DOUBLES);
-  L.sel = (int *)(L.selk + Q);
-  L.byrank = L.sel + Q;
-  L.path = L.byrank + Q;
-  L.sorted = L.path + A;
+  L.selk = v.selk, L.sel = v.sel, L.byrank = v.byrank, L.path = v.path, L.sorted = v.sorted;
   return L;
+}
+
+// The three scalars of dpar the scores need: EBSC pre1 and pil_bar, ES3C 1 / sigma2 (the others 0)
+struct SeedScalars {
+  double pre1, pilb, s2inv;
+};
+template <bool SSSC>
+__device__ __forceinline__ SeedScalars seed_scalars(const double *dpar) {
+  return {SSSC ? 0.0 : dpar[DP_PRE1], SSSC ? 0.0 : dpar[DP_PILBAR], SSSC ? dpar[DP_S2INV] : 0.0};
+}
+
+// Incomplete data: the reliable d of the mask row mn into dl in ascending order (ballots); returns how many.  The caller
+// synchronises before dl is read.
+__device__ __forceinline__ int seed_list_reliable(const uint8_t *mn, int D, int lane, int *dl) {
+  int nd = 0;
+  for (int d0 = 0; d0 < D; d0 += 64) {
+    const int d = d0 + lane;
+    const bool on = d < D && mn[d < D ? d : 0] != 0;
+    const u64 b = __ballot(on);
+    if (on) dl[nd + __popcll(b & ((1ull << lane) - 1ull))] = d;
+    nd += __popcll(b);
+  }
+  return nd;
 }
 
 // ES3C, once per step: act[] = A_{t-1} as wave-uniform values and its blocks in LDS (SeedShared); returns sum pil_bar over
@@ -450,12 +619,10 @@ __global__ __launch_bounds__(256) void seed_states_kernel(SeedArgs a) {
   const int W = (int)(blockDim.x >> 6);
   const int S = a.S, H = a.H, HW = a.HW, A = a.A, Hp = a.Hp, Q = a.Q;
   const int NC = Hp >> 6;  // chunks of 64 latents
-  const SeedLds L = seed_carve(seed_lds + (size_t)wave * seed_wave_bytes(Hp, HW, Q, A), Hp, HW, Q, A);
+  const SeedLds L = seed_carve(seed_lds_view(seed_lds, wave, SEED_LDS_GREEDY, SeedLdsShape{SSSC, Hp, HW, Q, A, 0, 0, 0, 0}));
   u64 *keys = L.keys, *base = L.base;
   double *cc = L.cc;
-  const double pre1 = SSSC ? 0.0 : a.dpar[DP_PRE1];
-  const double pilb = SSSC ? 0.0 : a.dpar[DP_PILBAR];
-  const double s2inv = SSSC ? a.dpar[DP_S2INV] : 0.0;
+  const auto [pre1, pilb, s2inv] = seed_scalars<SSSC>(a.dpar);
   const int q_lo = S / A, q_rem = S - q_lo * A;
   for (i64 n = (i64)blockIdx.x * W + wave; n < a.N; n += (i64)gridDim.x * W) {
     const double *Bn = a.Bm + (size_t)n * H;
@@ -566,32 +733,22 @@ __global__ __launch_bounds__(256) void seed_states_masked_kernel(SeedArgs a) {
   const int W = (int)(blockDim.x >> 6);
   const int S = a.S, H = a.H, HW = a.HW, A = a.A, Hp = a.Hp, Q = a.Q, D = a.D, R = a.R;
   const int NC = Hp >> 6;
-  const int rows_lds = a.rows ? 0 : R;
-  unsigned char *home = seed_lds + (size_t)wave * seed_masked_wave_bytes(Hp, HW, Q, A, D, rows_lds);
-  const SeedLds L = seed_carve(home, Hp, HW, Q, A);
+  const SeedLdsView V = seed_lds_view(seed_lds, wave, SEED_LDS_GREEDY_MASKED, SeedLdsShape{SSSC, Hp, HW, Q, A, 0, D, a.rows ? 0 : R, 0});
+  const SeedLds L = seed_carve(V);
   u64 *keys = L.keys, *base = L.base;
   double *cc = L.cc;
-  double *col = (double *)(home + seed_wave_bytes(Hp, HW, Q, A));
-  double *rows = a.rows ? a.rows + ((size_t)blockIdx.x * W + wave) * R * Hp : col + D;
-  int *dl = (int *)(col + D + (size_t)rows_lds * Hp);
+  double *col = V.col;
+  double *rows = a.rows ? a.rows + ((size_t)blockIdx.x * W + wave) * R * Hp : V.rows;
+  int *dl = V.dl;
   double *tmp = (double *)keys;  // EBSC: a row on its way into e (the keys of a step are dead by then)
-  const double pre1 = SSSC ? 0.0 : a.dpar[DP_PRE1];
-  const double pilb = SSSC ? 0.0 : a.dpar[DP_PILBAR];
-  const double s2inv = SSSC ? a.dpar[DP_S2INV] : 0.0;
+  const auto [pre1, pilb, s2inv] = seed_scalars<SSSC>(a.dpar);
   const int q_lo = S / A, q_rem = S - q_lo * A;
   for (i64 n = (i64)blockIdx.x * W + wave; n < a.N; n += (i64)gridDim.x * W) {
     const double *Bn = a.Bm + (size_t)n * H;
     const uint8_t *mn = a.mask + (size_t)n * D;
     const double yy = a.yy[n];
     for (int w = lane; w < HW; w += 64) base[w] = 0ull;
-    int nd = 0;  // the reliable d in ascending order
-    for (int d0 = 0; d0 < D; d0 += 64) {
-      const int d = d0 + lane;
-      const bool on = d < D && mn[d < D ? d : 0] != 0;
-      const u64 b = __ballot(on);
-      if (on) dl[nd + __popcll(b & ((1ull << lane) - 1ull))] = d;
-      nd += __popcll(b);
-    }
+    const int nd = seed_list_reliable(mn, D, lane, dl);
     seed_wave_sync();
     double *gd = SSSC ? rows + (size_t)(R - 1) * Hp : tmp;
     seed_gram_sweep<true>(a, lane, dl, col, nd, gd);

@@ -34,8 +34,8 @@
 // Infinity Cache).  Double-buffered in LDS they would take 2 B Hp 8 bytes (128 KB at B = 8, H = 1024: one wave per
 // workgroup), and a per-wavefront buffer in global memory moves three rows per parent and step (old e, the row of G, new e)
 // against (A - 1) / 2 = 3.5 here, for a buffer of 2 B Hp doubles per resident wave.  The bits are those of the definition.
-// LDS per wave (seed_beam_wave_bytes): the keys (Hp), the shared ES3C blocks (168 doubles), the pass's members (Q keys, 2 Q
-// ints), the running lists (2 Q keys, 4 Q ints) and the two beams (2 B (HW + 1) words, 4 B A ints).
+// LDS per wave (SEED_LDS_BEAM of seed_lds_walk): the keys (Hp), the shared ES3C blocks (168 doubles), the pass's members
+// (Q keys, 2 Q ints), the running lists (2 Q keys, 4 Q ints) and the two beams (2 B (HW + 1) words, 4 B A ints).
 #pragma once
 #include "common.hpp"
 #include "kernels_seed.hpp"
@@ -47,12 +47,6 @@ struct SeedBeamArgs {
   int B;        // beam
 };
 
-__host__ __device__ inline size_t seed_beam_wave_bytes(int Hp, int HW, int Q, int A, int B) {
-  size_t b = (size_t)8 * ((size_t)Hp + SEED_SHARED_DOUBLES + 3 * (size_t)Q + 2 * (size_t)B * (HW + 1)) +
-             (size_t)4 * (6 * (size_t)Q + 4 * (size_t)B * A);
-  return (b + 15) & ~(size_t)15;
-}
-
 template <bool SSSC>
 __global__ __launch_bounds__(256) void seed_states_beam_kernel(SeedBeamArgs ba) {
   extern __shared__ __attribute__((aligned(16))) unsigned char seed_beam_lds[];
@@ -61,36 +55,14 @@ __global__ __launch_bounds__(256) void seed_states_beam_kernel(SeedBeamArgs ba) 
   const int W = (int)(blockDim.x >> 6);
   const int S = a.S, H = a.H, HW = a.HW, A = a.A, Hp = a.Hp, Q = a.Q, B = ba.B;
   const int NC = Hp >> 6;
-  // one wavefront's share of LDS (file header): 8-byte entries first
-  SeedLds L;
-  u64 *rk0, *rk1, *mwords;
-  double *msc;
-  int *rp0, *rj0, *rp1, *rj1, *mpath, *msorted;
-  {
-    unsigned char *home = seed_beam_lds + (size_t)wave * seed_beam_wave_bytes(Hp, HW, Q, A, B);
-    L.keys = (u64 *)home;
-    L.cc = nullptr;
-    L.base = nullptr;
-    double *shd = (double *)(L.keys + Hp);
-    L.sh = {shd, shd + SEED_M * SEED_M, shd + 2 * SEED_M * SEED_M, shd + 3 * SEED_M * SEED_M,
-            shd + 3 * SEED_M * SEED_M + SEED_M, shd + 3 * SEED_M * SEED_M + 2 * SEED_M};
-    L.selk = (u64 *)(shd + SEED_SHARED_DOUBLES);
-    rk0 = L.selk + Q;
-    rk1 = rk0 + Q;
-    msc = (double *)(rk1 + Q);
-    mwords = (u64 *)(msc + 2 * B);
-    L.sel = (int *)(mwords + (size_t)2 * B * HW);
-    L.byrank = L.sel + Q;
-    rp0 = L.byrank + Q, rj0 = rp0 + Q, rp1 = rj0 + Q, rj1 = rp1 + Q;
-    mpath = rj1 + Q;
-    msorted = mpath + 2 * B * A;
-    L.path = nullptr;
-    L.sorted = nullptr;
-  }
+  // one wavefront's share of LDS (seed_lds_walk); cc / base / path / sorted are absent: a beam member carries its own
+  const SeedLdsView V = seed_lds_view(seed_beam_lds, wave, SEED_LDS_BEAM, SeedLdsShape{SSSC, Hp, HW, Q, A, B, 0, 0, 0});
+  const SeedLds L = seed_carve(V);
+  u64 *rk0 = V.rk[0], *rk1 = V.rk[1], *mwords = V.mwords;
+  double *msc = V.msc;
+  int *rp0 = V.rp[0], *rj0 = V.rj[0], *rp1 = V.rp[1], *rj1 = V.rj[1], *mpath = V.mpath, *msorted = V.msorted;
   u64 *keys = L.keys;
-  const double pre1 = SSSC ? 0.0 : a.dpar[DP_PRE1];
-  const double pilb = SSSC ? 0.0 : a.dpar[DP_PILBAR];
-  const double s2inv = SSSC ? a.dpar[DP_S2INV] : 0.0;
+  const auto [pre1, pilb, s2inv] = seed_scalars<SSSC>(a.dpar);
   const int q_lo = S / A, q_rem = S - q_lo * A;
   for (i64 n = (i64)blockIdx.x * W + wave; n < a.N; n += (i64)gridDim.x * W) {
     const double *Bn = a.Bm + (size_t)n * H;

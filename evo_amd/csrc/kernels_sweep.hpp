@@ -62,8 +62,6 @@
 #include "common.hpp"
 #include "kernels_seed.hpp"
 
-#define SWEEP_PATH 16  // active latents of a parent kept as a list (ES3C reads at most 9)
-#define SWEEP_MAX_P 64
 #define SWEEP_ROWS (SEED_MAX_A_SSSC + 2)  // incomplete data, ES3C: the rows of G(n) of a parent's first 9 active latents and its diagonal
 
 struct SweepArgs {
@@ -78,19 +76,6 @@ struct SweepArgs {
   int *n_capped;        // (N)
   int L, S_perm, P, q, Cmax;
 };
-
-__host__ __device__ inline size_t sweep_wave_bytes(bool sssc, int Hp, int HW, int q) {
-  size_t b = (size_t)(sssc ? 1 : 2) * Hp * 8 + (size_t)HW * 8 + (size_t)(sssc ? SEED_SHARED_DOUBLES : 0) * 8 + (size_t)q * 8 +
-             (size_t)2 * q * 4 + (size_t)SWEEP_PATH * 4 + (size_t)SWEEP_MAX_P * 4;
-  return (b + 15) & ~(size_t)15;
-}
-
-// incomplete data: behind the complete kernel's share EBSC the diagonal g_jj (Hp doubles), the staged column (D doubles), ES3C
-// the SWEEP_ROWS rows of G(n) when LDS is their home (rows_lds = SWEEP_ROWS, else 0) and the list of the reliable d (D ints)
-__host__ __device__ inline size_t sweep_masked_wave_bytes(bool sssc, int Hp, int HW, int q, int D, int rows_lds) {
-  size_t b = sweep_wave_bytes(sssc, Hp, HW, q) + (size_t)(sssc ? 0 : Hp) * 8 + (size_t)D * 8 + (size_t)rows_lds * Hp * 8 + (size_t)D * 4;
-  return (b + 15) & ~(size_t)15;
-}
 
 // ES3C lpj of the state idx[0..K-1] for one datapoint, eliminated from scratch by the calling lane.  The K x K blocks of
 // {G, Psi} are read where they are used (the few entries stay in the cache): held in registers beside the system they
@@ -174,6 +159,50 @@ __device__ __forceinline__ u64 sweep_wave_max_u64(u64 v) {
   return ((u64)hi << 32) | lo;
 }
 
+// The parents of a datapoint (file header): round r takes the largest (lpj, -slot) of the row below the pick of round
+// r - 1; their slots go to parents[0..P-1].  The caller synchronises before it reads them.
+__device__ __forceinline__ void sweep_pick_parents(const double *row, int S, int P, int lane, int *parents) {
+  u64 pk = 0ull;
+  int ps = -1;
+  for (int r = 0; r < P; r++) {
+    u64 bk = 0ull;
+    int bs = 0x7fffffff;
+    for (int s = lane; s < S; s += 64) {
+      const u64 k = seed_key(row[s]);
+      const bool elig = r == 0 || k < pk || (k == pk && s > ps);
+      if (elig && k > bk) bk = k, bs = s;  // (ascending s: an equal key later in the lane's list never wins)
+    }
+    const u64 gk = sweep_wave_max_u64(bk);
+    const int gs = (int)wave_min_u32(bk == gk ? (unsigned)bs : 0x7fffffffu);
+    if (lane == 0) parents[r] = gs;
+    pk = gk, ps = gs;
+  }
+}
+
+// The words pw of a parent into par[]; returns its size (wave-uniform).  The caller synchronises before par is read.
+__device__ __forceinline__ int sweep_load_parent(const u64 *pw, int HW, int lane, u64 *par) {
+  int m = 0;
+  for (int w = lane; w < HW; w += 64) {
+    const u64 v = pw[w];
+    par[w] = v;
+    m += __popcll(v);
+  }
+  return wave_sum_i(m);
+}
+
+// The active latents of the words par[] in ascending order into list[] (the first cap of them; ballots)
+__device__ __forceinline__ void sweep_list_active(const u64 *par, int H, int NC, int lane, int *list, int cap) {
+  int pos = 0;
+  for (int c = 0; c < NC && pos < cap; c++) {
+    const int j = 64 * c + lane;
+    const bool on = j < H && ((par[j < H ? j >> 6 : 0] >> (63 - (j & 63))) & 1ull);
+    const u64 b = __ballot(on);
+    const int at = pos + __popcll(b & ((1ull << lane) - 1ull));
+    if (on && at < cap) list[at] = j;
+    pos += __popcll(b);
+  }
+}
+
 // MASKED: the law on incomplete data (file header); the complete instantiations compile to what they were without it.
 template <bool SSSC, bool MASKED = false>
 __global__ __launch_bounds__(256) void sweep_neighbours_kernel(SweepArgs a) {
@@ -184,42 +213,23 @@ __global__ __launch_bounds__(256) void sweep_neighbours_kernel(SweepArgs a) {
   const int S = sd.S, H = sd.H, HW = sd.HW, Hp = sd.Hp, P = a.P, q = a.q, Cmax = a.Cmax;
   const int NC = Hp >> 6;
   constexpr int CAP = SSSC ? SEED_MAX_A_SSSC : SEED_MAX_A_BSC;
-  // one wavefront's share of LDS (file header)
-  SeedLds L;
-  int *parents;
+  // one wavefront's share of LDS (seed_lds_walk)
+  const SeedLdsView V = MASKED ? seed_lds_view(sweep_lds, wave, SEED_LDS_FLIP_MASKED, SeedLdsShape{SSSC, Hp, HW, q, 0, 0, sd.D, sd.rows ? 0 : sd.R, 0})
+                               : seed_lds_view(sweep_lds, wave, SEED_LDS_FLIP, SeedLdsShape{SSSC, Hp, HW, q, 0, 0, 0, 0, 0});
+  const SeedLds L = seed_carve(V);
+  int *parents = V.parents;
   // incomplete data: the diagonal of G(n), the staged column, ES3C the rows of G(n) (row SWEEP_ROWS - 1: the diagonal), the reliable d
   double *gd = nullptr, *col = nullptr, *rows = nullptr;
   int *dl = nullptr;
-  {
-    unsigned char *home = sweep_lds + (size_t)wave * (MASKED ? sweep_masked_wave_bytes(SSSC, Hp, HW, q, sd.D, sd.rows ? 0 : sd.R)
-                                                             : sweep_wave_bytes(SSSC, Hp, HW, q));
-    if constexpr (MASKED) {
-      double *x = (double *)(home + sweep_wave_bytes(SSSC, Hp, HW, q));
-      gd = x, x += SSSC ? 0 : Hp;
-      col = x, x += sd.D;
-      rows = sd.rows ? sd.rows + ((size_t)blockIdx.x * W + wave) * sd.R * Hp : x;
-      dl = (int *)(x + (sd.rows ? (size_t)0 : (size_t)sd.R * Hp));
-      if (SSSC) gd = rows + (size_t)(sd.R - 1) * Hp;
-    }
-    L.keys = (u64 *)home;
-    L.cc = (double *)(L.keys + Hp);
-    L.base = (u64 *)(L.cc + (SSSC ? 0 : Hp));
-    double *shd = (double *)(L.base + HW);
-    L.sh = {shd, shd + SEED_M * SEED_M, shd + 2 * SEED_M * SEED_M, shd + 3 * SEED_M * SEED_M,
-            shd + 3 * SEED_M * SEED_M + SEED_M, shd + 3 * SEED_M * SEED_M + 2 * SEED_M};
-    L.selk = (u64 *)(shd + (SSSC ? SEED_SHARED_DOUBLES : 0));
-    L.sel = (int *)(L.selk + q);
-    L.byrank = L.sel + q;
-    L.path = L.byrank + q;
-    L.sorted = nullptr;
-    parents = L.path + SWEEP_PATH;
+  if constexpr (MASKED) {
+    col = V.col, dl = V.dl;
+    rows = sd.rows ? sd.rows + ((size_t)blockIdx.x * W + wave) * sd.R * Hp : V.rows;
+    gd = SSSC ? rows + (size_t)(sd.R - 1) * Hp : V.gd;
   }
   u64 *keys = L.keys, *par = L.base;
   double *cc = L.cc;
   int *path = L.path;
-  const double pre1 = SSSC ? 0.0 : sd.dpar[DP_PRE1];
-  const double pilb = SSSC ? 0.0 : sd.dpar[DP_PILBAR];
-  const double s2inv = SSSC ? sd.dpar[DP_S2INV] : 0.0;
+  const auto [pre1, pilb, s2inv] = seed_scalars<SSSC>(sd.dpar);
   for (i64 n = (i64)blockIdx.x * W + wave; n < sd.N; n += (i64)gridDim.x * W) {
     const double *Bn = sd.Bm + (size_t)n * H;
     const double yy = sd.yy[n];
@@ -227,18 +237,12 @@ __global__ __launch_bounds__(256) void sweep_neighbours_kernel(SweepArgs a) {
     const u64 *kn = sd.states + (size_t)n * S * HW;
     int nd = 0;  // incomplete data: the reliable d in ascending order, then g_jj = sum over them of W_dj^2
     if constexpr (MASKED) {
-      const uint8_t *mn = sd.mask + (size_t)n * sd.D;
-      for (int d0 = 0; d0 < sd.D; d0 += 64) {
-        const int d = d0 + lane;
-        const bool on = d < sd.D && mn[d < sd.D ? d : 0] != 0;
-        const u64 b = __ballot(on);
-        if (on) dl[nd + __popcll(b & ((1ull << lane) - 1ull))] = d;
-        nd += __popcll(b);
-      }
+      nd = seed_list_reliable(sd.mask + (size_t)n * sd.D, sd.D, lane, dl);
       seed_wave_sync();
       seed_gram_sweep<true>(sd, lane, dl, col, nd, gd);
     }
-    // ---- parents: round r takes the largest (lpj, -slot) below the pick of round r - 1
+    // ---- parents: the rounds of sweep_pick_parents, kept in line here: through the call the masked ES3C instantiation,
+    // which fills the register file, spills 12 bytes per lane
     {
       u64 pk = 0ull;
       int ps = -1;
@@ -262,13 +266,7 @@ __global__ __launch_bounds__(256) void sweep_neighbours_kernel(SweepArgs a) {
       const int slot = guard_index(__builtin_amdgcn_readfirstlane(parents[r]), S, sd.err);
       const u64 *pw = kn + (size_t)slot * HW;
       // ---- the parent's words, its size, the keys cleared
-      int m = 0;
-      for (int w = lane; w < HW; w += 64) {
-        const u64 v = pw[w];
-        par[w] = v;
-        m += __popcll(v);
-      }
-      m = wave_sum_i(m);
+      const int m = sweep_load_parent(pw, HW, lane, par);
       for (int c = 0; c < NC; c++) keys[64 * c + lane] = 0ull;
       seed_wave_sync();
       // ---- (b) flips that K^n holds: key 1 marks them (no score has that key)
@@ -286,17 +284,7 @@ __global__ __launch_bounds__(256) void sweep_neighbours_kernel(SweepArgs a) {
         }
       }
       // ---- the parent's active latents in ascending order (the first SWEEP_PATH of them)
-      {
-        int pos = 0;
-        for (int c = 0; c < NC && pos < SWEEP_PATH; c++) {
-          const int j = 64 * c + lane;
-          const bool on = j < H && ((par[j < H ? j >> 6 : 0] >> (63 - (j & 63))) & 1ull);
-          const u64 b = __ballot(on);
-          const int at = pos + __popcll(b & ((1ull << lane) - 1ull));
-          if (on && at < SWEEP_PATH) path[at] = j;
-          pos += __popcll(b);
-        }
-      }
+      sweep_list_active(par, H, NC, lane, path, SWEEP_PATH);
       seed_wave_sync();
       const bool add_ok = m + 1 <= CAP, rem_ok = m - 1 >= 1 && m - 1 <= CAP;
       bool lost = false;   // a neighbour neither all-zero nor held, above the cap

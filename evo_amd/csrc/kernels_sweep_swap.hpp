@@ -39,7 +39,6 @@
 #include "common.hpp"
 #include "kernels_sweep.hpp"
 
-#define SWAP_LIST SEED_MAX_A_BSC  // the parent's active latents as a list: every a of a scored parent
 #define SWAP_NONE 0xFFFFFFFFu     // a resident state that is no swap neighbour of the parent
 
 struct SweepSwapArgs {
@@ -49,11 +48,6 @@ struct SweepSwapArgs {
   int *n_capped_swap;   // (N)
   int append;           // 1: the rows go behind counts[n] (the flip stage ran), 0: from row 0
 };
-
-__host__ __device__ inline size_t sweep_swap_wave_bytes(bool sssc, int Hp, int HW, int q, int S) {
-  size_t b = sweep_wave_bytes(sssc, Hp, HW, q) + (size_t)2 * q * 8 + (size_t)4 * q * 4 + (size_t)SWAP_LIST * 4 + (size_t)S * 4;
-  return (b + 15) & ~(size_t)15;
-}
 
 template <bool SSSC>
 __global__ __launch_bounds__(256) void sweep_swap_kernel(SweepSwapArgs A) {
@@ -66,60 +60,22 @@ __global__ __launch_bounds__(256) void sweep_swap_kernel(SweepSwapArgs A) {
   const int NC = Hp >> 6;
   constexpr int CAP = SSSC ? SEED_MAX_A_SSSC : SEED_MAX_A_BSC;
   // one wavefront's share of LDS: the flip kernel's layout, then the running lists, the active latents, the held pairs
-  SeedLds L;
-  int *parents, *full;
-  unsigned *held;
-  u64 *rk0, *rk1;
-  int *ra0, *rj0, *ra1, *rj1;
-  {
-    unsigned char *home = sweep_swap_lds + (size_t)wave * sweep_swap_wave_bytes(SSSC, Hp, HW, q, S);
-    L.keys = (u64 *)home;
-    L.cc = (double *)(L.keys + Hp);
-    L.base = (u64 *)(L.cc + (SSSC ? 0 : Hp));
-    double *shd = (double *)(L.base + HW);
-    L.sh = {shd, shd + SEED_M * SEED_M, shd + 2 * SEED_M * SEED_M, shd + 3 * SEED_M * SEED_M,
-            shd + 3 * SEED_M * SEED_M + SEED_M, shd + 3 * SEED_M * SEED_M + 2 * SEED_M};
-    L.selk = (u64 *)(shd + (SSSC ? SEED_SHARED_DOUBLES : 0));
-    L.sel = (int *)(L.selk + q);
-    L.byrank = L.sel + q;
-    L.path = L.byrank + q;
-    L.sorted = nullptr;
-    parents = L.path + SWEEP_PATH;
-    rk0 = (u64 *)(home + sweep_wave_bytes(SSSC, Hp, HW, q));
-    rk1 = rk0 + q;
-    ra0 = (int *)(rk1 + q), rj0 = ra0 + q, ra1 = rj0 + q, rj1 = ra1 + q;
-    full = rj1 + q;
-    held = (unsigned *)(full + SWAP_LIST);
-  }
+  const SeedLdsView V = seed_lds_view(sweep_swap_lds, wave, SEED_LDS_SWAP, SeedLdsShape{SSSC, Hp, HW, q, 0, 0, 0, 0, S});
+  const SeedLds L = seed_carve(V);
+  int *parents = V.parents, *full = V.full;
+  unsigned *held = V.held;
+  u64 *rk0 = V.rk[0], *rk1 = V.rk[1];
+  int *ra0 = V.rp[0], *rj0 = V.rj[0], *ra1 = V.rp[1], *rj1 = V.rj[1];
   u64 *keys = L.keys, *par = L.base;
   double *cc = L.cc;
   int *path = L.path;
-  const double pre1 = SSSC ? 0.0 : sd.dpar[DP_PRE1];
-  const double pilb = SSSC ? 0.0 : sd.dpar[DP_PILBAR];
-  const double s2inv = SSSC ? sd.dpar[DP_S2INV] : 0.0;
+  const auto [pre1, pilb, s2inv] = seed_scalars<SSSC>(sd.dpar);
   for (i64 n = (i64)blockIdx.x * W + wave; n < sd.N; n += (i64)gridDim.x * W) {
     const double *Bn = sd.Bm + (size_t)n * H;
     const double yy = sd.yy[n];
     const double *row = a.lpj + (size_t)n * a.L + a.S_perm;
     const u64 *kn = sd.states + (size_t)n * S * HW;
-    // ---- parents: round r takes the largest (lpj, -slot) below the pick of round r - 1 (the flip kernel's rounds)
-    {
-      u64 pk = 0ull;
-      int ps = -1;
-      for (int r = 0; r < P; r++) {
-        u64 bk = 0ull;
-        int bs = 0x7fffffff;
-        for (int s = lane; s < S; s += 64) {
-          const u64 k = seed_key(row[s]);
-          const bool elig = r == 0 || k < pk || (k == pk && s > ps);
-          if (elig && k > bk) bk = k, bs = s;
-        }
-        const u64 gk = sweep_wave_max_u64(bk);
-        const int gs = (int)wave_min_u32(bk == gk ? (unsigned)bs : 0x7fffffffu);
-        if (lane == 0) parents[r] = gs;
-        pk = gk, ps = gs;
-      }
-    }
+    sweep_pick_parents(row, S, P, lane, parents);
     seed_wave_sync();
     int row0 = A.append ? __builtin_amdgcn_readfirstlane(a.counts[n]) : 0;
     row0 = row0 < 0 ? 0 : (row0 > Cmax ? Cmax : row0);
@@ -128,13 +84,7 @@ __global__ __launch_bounds__(256) void sweep_swap_kernel(SweepSwapArgs A) {
       const int slot = guard_index(__builtin_amdgcn_readfirstlane(parents[r]), S, sd.err);
       const u64 *pw = kn + (size_t)slot * HW;
       // ---- the parent's words and its size
-      int m = 0;
-      for (int w = lane; w < HW; w += 64) {
-        const u64 v = pw[w];
-        par[w] = v;
-        m += __popcll(v);
-      }
-      m = wave_sum_i(m);
+      const int m = sweep_load_parent(pw, HW, lane, par);
       seed_wave_sync();
       if (m > CAP) capped_parents++;  // (c)
       int nrun = 0;                   // the running list: entries 0 .. nrun - 1 of (ok, oa, oj), by rank
@@ -142,18 +92,8 @@ __global__ __launch_bounds__(256) void sweep_swap_kernel(SweepSwapArgs A) {
       int *oa = ra0, *oj = rj0, *na = ra1, *nj = rj1;
       double base = 0.0;
       if (m >= 1 && m <= CAP) {
-        // ---- the parent's active latents in ascending order
-        {
-          int pos = 0;
-          for (int c = 0; c < NC; c++) {
-            const int j = 64 * c + lane;
-            const bool on = j < H && ((par[j < H ? j >> 6 : 0] >> (63 - (j & 63))) & 1ull);
-            const u64 b = __ballot(on);
-            const int at = pos + __popcll(b & ((1ull << lane) - 1ull));
-            if (on && at < SWAP_LIST) full[at] = j;
-            pos += __popcll(b);
-          }
-        }
+        // ---- the parent's active latents in ascending order (m <= CAP <= SWAP_LIST: all of them)
+        sweep_list_active(par, H, NC, lane, full, SWAP_LIST);
         // ---- (b) the swap that a resident state holds: (a << 16) | j (H < 2^16: the keys of one datapoint fit LDS)
         for (int s = lane; s < S; s += 64) {
           const u64 *sw = kn + (size_t)s * HW;

@@ -136,6 +136,15 @@ class Engine:
             tp = u8ptr(packed)
         check(self.lib.evoamd_init_states(self._h, float(p_init), int(seed) & (2 ** 64 - 1), int(max_rounds), tp))
 
+    def _seed_out(self, max_active, want_path):
+        """max_active as an int, what a seeding call returns -- (path, lpj_path) or None -- and the two pointers."""
+        A = int(max_active)
+        if not want_path:
+            return A, None, (None, None)
+        path = np.empty((self.N, max(A, 1)), dtype=np.int32)
+        lpj = np.empty((self.N, max(A, 1)), dtype=np.float64)
+        return A, (path, lpj), (i32ptr(path), dptr(lpj))
+
     def seed_states(self, max_active, want_path=False, incomplete=False):
         """K^n seeded on the device from Theta and the data by greedy forward selection on the model's own lpj
         (evoamd_seed_states; evo_amd.variational.seed_states_host is its NumPy mirror): deterministic, ``max_active``
@@ -146,17 +155,12 @@ class Engine:
         mask; without masks the flag changes nothing.  EvoAmdError naming the rule, with K^n left as it was, for a
         missing Theta, masks present without ``incomplete``, the background unit, the float32 mode, bsc_direct or a
         ``max_active`` the law refuses."""
-        A = int(max_active)
-        path = lpj = None
-        if want_path:
-            path = np.empty((self.N, max(A, 1)), dtype=np.int32)
-            lpj = np.empty((self.N, max(A, 1)), dtype=np.float64)
-        pp, lp = (i32ptr(path), dptr(lpj)) if want_path else (None, None)
+        A, out, ptrs = self._seed_out(max_active, want_path)
         if incomplete:
-            check(self.lib.evoamd_seed_states_ex(self._h, A, _lib.SEED_INCOMPLETE, pp, lp))
+            check(self.lib.evoamd_seed_states_ex(self._h, A, _lib.SEED_INCOMPLETE, *ptrs))
         else:
-            check(self.lib.evoamd_seed_states(self._h, A, pp, lp))
-        return (path, lpj) if want_path else None
+            check(self.lib.evoamd_seed_states(self._h, A, *ptrs))
+        return out
 
     def seed_states_beam(self, max_active, beam, want_path=False):
         """K^n seeded on the device by a beam of partial states (evoamd_seed_states_beam;
@@ -165,14 +169,9 @@ class Engine:
         only.  ``want_path``: returns (path int32 (N, max_active), the path of the rank-0 state of the last step, and
         lpj_path (N, max_active), the rank-0 score of each step), else None.  EvoAmdError naming the rule, with K^n left
         as it was, for everything seed_states refuses, resident masks, ``beam`` < 1, > S // max_active or > 16."""
-        A = int(max_active)
-        path = lpj = None
-        if want_path:
-            path = np.empty((self.N, max(A, 1)), dtype=np.int32)
-            lpj = np.empty((self.N, max(A, 1)), dtype=np.float64)
-        pp, lp = (i32ptr(path), dptr(lpj)) if want_path else (None, None)
-        check(self.lib.evoamd_seed_states_beam(self._h, A, int(beam), pp, lp))
-        return (path, lpj) if want_path else None
+        A, out, ptrs = self._seed_out(max_active, want_path)
+        check(self.lib.evoamd_seed_states_beam(self._h, A, int(beam), *ptrs))
+        return out
 
     # ---- samples from the model ------------------------------------------------------------
     def generate(self, model, N, seed, Wt, pies, mus=None, F=None, sigma=1.0, first_index=0, s=None,
@@ -363,26 +362,28 @@ class Engine:
             int(check_every), int(patience), float(min_sub), dptr(trace), ctypes.byref(n_done)))
         return trace[:n_done.value], n_done.value
 
-    def _sweep_nb_flags(self, neighbourhood, incomplete):
+    def _sweep_nb(self, neighbourhood, incomplete, score_key, want_scores=False):
+        """The flags of an _nb sweep call, the dict it returns -- an array per key of the neighbourhood, the three flip
+        keys None with "swap", no swap key with "flip", a "score" key only with ``score_key`` (an array with
+        ``want_scores``, else None) -- and the evoamd_sweep_out that points at the arrays."""
         if neighbourhood not in _lib.SWEEP_NEIGHBOURHOODS:
             raise ValueError("sweep: neighbourhood = %r must be one of 'flip', 'swap', 'both'" % (neighbourhood,))
-        return _lib.SWEEP_NEIGHBOURHOODS[neighbourhood] | (_lib.SWEEP_INCOMPLETE if incomplete else 0)
-
-    def _sweep_nb_out(self, neighbourhood, want_scores):
-        """The output arrays of an _nb sweep call and the evoamd_sweep_out that points at them."""
+        flags = _lib.SWEEP_NEIGHBOURHOODS[neighbourhood] | (_lib.SWEEP_INCOMPLETE if incomplete else 0)
         N, flips = self.N, neighbourhood != "swap"
-        res = {"score": np.empty((N, self.Cmax), dtype=np.float64) if want_scores else None,
-               "best_flip": np.empty(N, dtype=np.int32) if flips else None,
-               "gain": np.empty(N, dtype=np.float64) if flips else None,
-               "n_capped": np.empty(N, dtype=np.int32) if flips else None,
-               "best_swap": np.empty((N, 2), dtype=np.int32),
-               "swap_gain": np.empty(N, dtype=np.float64),
-               "n_capped_swap": np.empty(N, dtype=np.int32)}
+        res = {}
+        if score_key:
+            res["score"] = np.empty((N, self.Cmax), dtype=np.float64) if want_scores else None
+        res.update(best_flip=np.empty(N, dtype=np.int32) if flips else None,
+                   gain=np.empty(N, dtype=np.float64) if flips else None,
+                   n_capped=np.empty(N, dtype=np.int32) if flips else None)
+        if neighbourhood != "flip":
+            res.update(best_swap=np.empty((N, 2), dtype=np.int32), swap_gain=np.empty(N, dtype=np.float64),
+                       n_capped_swap=np.empty(N, dtype=np.int32))
         out = _lib.SweepOut()
         for name, a in res.items():
             if a is not None:
                 setattr(out, name, dptr(a) if a.dtype == np.float64 else i32ptr(a))
-        return res, out
+        return flags, res, out
 
     def sweep_propose(self, n_parents, n_keep, want_scores=True, incomplete=False, neighbourhood="flip"):
         """One sweep's proposals of the local search on K^n (evoamd_sweep_propose; csrc/kernels_sweep.hpp has the law,
@@ -404,22 +405,11 @@ class Engine:
         the flip rows ("both": 2 * n_parents * n_keep <= Cmax).  The dict gains "best_swap" int32 (N, 2) = (a, j) of the best
         state's best scored swap or (-1, -1), "swap_gain" (N,) (-inf without one) and "n_capped_swap" int32 (N,), the
         parents above the seeding cap, none of whose swaps is scored; with "swap" the three flip keys are None.  Swaps on
-        incomplete data (``incomplete`` or masks resident) are refused."""
-        if neighbourhood != "flip":
-            res, out = self._sweep_nb_out(neighbourhood, want_scores)
-            check(self.lib.evoamd_sweep_propose_nb(self._h, int(n_parents), int(n_keep),
-                                                   self._sweep_nb_flags(neighbourhood, incomplete), ctypes.byref(out)))
-            return res
-        score = np.empty((self.N, self.Cmax), dtype=np.float64) if want_scores else None
-        best = np.empty(self.N, dtype=np.int32)
-        gain = np.empty(self.N, dtype=np.float64)
-        capped = np.empty(self.N, dtype=np.int32)
-        out = (dptr(score) if want_scores else None, i32ptr(best), dptr(gain), i32ptr(capped))
-        if incomplete:
-            check(self.lib.evoamd_sweep_propose_ex(self._h, int(n_parents), int(n_keep), _lib.SWEEP_INCOMPLETE, *out))
-        else:
-            check(self.lib.evoamd_sweep_propose(self._h, int(n_parents), int(n_keep), *out))
-        return {"score": score, "best_flip": best, "gain": gain, "n_capped": capped}
+        incomplete data (``incomplete`` or masks resident) are refused.  Every neighbourhood goes through
+        evoamd_sweep_propose_nb, which without a swap bit is exactly evoamd_sweep_propose_ex."""
+        flags, res, out = self._sweep_nb(neighbourhood, incomplete, True, want_scores)
+        check(self.lib.evoamd_sweep_propose_nb(self._h, int(n_parents), int(n_keep), flags, ctypes.byref(out)))
+        return res
 
     def sweep_states(self, n_sweeps, n_parents=1, n_keep=None, Mprime=None, stop_when_quiet=True, incomplete=False,
                      neighbourhood="flip"):
@@ -436,23 +426,11 @@ class Engine:
         q = self.Cmax // max(P * (2 if neighbourhood == "both" else 1), 1) if n_keep is None else int(n_keep)
         trace = np.zeros((max(T, 1), 3), dtype=np.float64)
         n_done = ctypes.c_int(0)
-        if neighbourhood != "flip":
-            res, out = self._sweep_nb_out(neighbourhood, False)
-            check(self.lib.evoamd_sweep_states_nb(
-                self._h, T, P, q, self.S if Mprime is None else int(Mprime), 1 if stop_when_quiet else 0,
-                self._sweep_nb_flags(neighbourhood, incomplete), dptr(trace), ctypes.byref(n_done), ctypes.byref(out)))
-            del res["score"]
-            return trace[:n_done.value], n_done.value, res
-        best = np.empty(self.N, dtype=np.int32)
-        gain = np.empty(self.N, dtype=np.float64)
-        capped = np.empty(self.N, dtype=np.int32)
-        head = (self._h, T, P, q, self.S if Mprime is None else int(Mprime), 1 if stop_when_quiet else 0)
-        out = (dptr(trace), ctypes.byref(n_done), i32ptr(best), dptr(gain), i32ptr(capped))
-        if incomplete:
-            check(self.lib.evoamd_sweep_states_ex(*head, _lib.SWEEP_INCOMPLETE, *out))
-        else:
-            check(self.lib.evoamd_sweep_states(*head, *out))
-        return trace[:n_done.value], n_done.value, {"best_flip": best, "gain": gain, "n_capped": capped}
+        flags, res, out = self._sweep_nb(neighbourhood, incomplete, False)
+        check(self.lib.evoamd_sweep_states_nb(
+            self._h, T, P, q, self.S if Mprime is None else int(Mprime), 1 if stop_when_quiet else 0, flags, dptr(trace),
+            ctypes.byref(n_done), ctypes.byref(out)))
+        return trace[:n_done.value], n_done.value, res
 
     SCORES = ("F", "entropy", "best", "k_best", "k_mean")
 

@@ -14,6 +14,7 @@ CASES = {
     "s200": (9, 16, 130, 200, 8, 0),     # 25 states per step, more than 64 states per wave, HW = 3
     "tight": (33, 4, 8, 20, 3, 0),       # quotas 7, 7, 6 close to Hv - t + 1
     "large_h": (5, 8, 1100, 6, 6, 0),    # HW = 18, q_t = 1: the path only
+    "wpw2": (5, 4, 2500, 6, 3, 0),       # Hp = 2560: four wavefronts' shares of LDS (41 KB each) exceed 150 KiB, two fit
 }
 ALGOS = ("ebsc", "es3c")
 SEEDS = {name: 100 + i for i, name in enumerate(sorted(CASES))}

@@ -25,13 +25,18 @@ CASES = {
     "rows_gmem": (3, 4, 1990, 8, 0, 1, 4, 8, 3),    # ES3C: ten rows of 2048 doubles do not fit LDS
     # a row without any reliable entry (datapoint 0) and a row with exactly one (datapoint 1)
     "empty_row": (7, 8, 70, 12, 0, 2, 4, 4, 3),
+    # EBSC: one wavefront's share of LDS is 45 216 bytes, three fit 150 KiB and four do not (the workgroup steps down by one)
+    "wpw3": (7, 4, 1800, 6, 0, 1, 4, 3, 3),
 }
 FRACTIONS = (0.3, 0.6)
 ALGOS = ("ebsc", "es3c")
-ONLY = {"rows_gmem": ("es3c",)}
+ONLY = {"rows_gmem": ("es3c",), "wpw3": ("ebsc",)}
 # picked so that every problem's smallest margin exceeds 1e-6 (tests/test_sweep_states_masked_host.py holds them to it)
 SEEDS = {name: 700 + i for i, name in enumerate(sorted(CASES))}
 SEEDS["d130"] = 720  # (700 leaves ES3C at 0.3 a margin of 8e-7)
+# (1800 latents rank closely and D = 4 leaves rows without a reliable entry: the first seed from 709 on with margins above
+# 2e-6 -- 2.5e-5 and 1.1e-5 -- and a reliable entry in every row at both fractions)
+SEEDS["wpw3"] = 816
 
 
 def all_problems():

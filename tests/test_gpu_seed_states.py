@@ -8,13 +8,14 @@
 3. the digests the kernel writes against digest_kernel's (same lpj bits before and after a re-upload of the same rows);
 4. no stale rows or prefetched pass after a seed call; two seed calls give the same K^n;
 5. every refusal leaves K^n as it was;
-6. Model.seed_resident_states for both models, device-resident and host-synchronised.
+6. Model.seed_resident_states for both models, device-resident and host-synchronised;
+7. evoamd_seed_states and evoamd_seed_states_ex without a flag give the same bits.
 """
 import numpy as np
 import pytest
 
 from _seed_problems import ALGOS, CASES, make_data, make_theta, problem, quotas
-from evo_amd._lib import EvoAmdError
+from evo_amd._lib import EvoAmdError, check, dptr, i32ptr
 from evo_amd.engine import Engine
 from evo_amd.models import BSC, SSSC
 
@@ -288,3 +289,20 @@ def test_model_seed_resident_states(model_eng, algo, permanent, sync_host):
     print("%s sync_host=%s: first free energy seeded %.4f, init_resident_states %.4f" % (algo, sync_host, F_seed, F_noise))
     assert np.isfinite(F_seed) and np.isfinite(F_noise)
     assert F_seed > F_noise
+
+
+def test_plain_and_ex_calls_agree(eng):
+    """evoamd_seed_states against evoamd_seed_states_ex with no flag, on the smallest problem: K^n, path and lpj bit for bit."""
+    p = problem("ebsc", "tight")
+    _install(eng, p)
+    got = []
+    for call in ("plain", "ex"):
+        eng.upload_states(np.zeros((p.N, p.S, p.H), dtype=bool))
+        path, lpj = np.full((p.N, p.A), -7, dtype=np.int32), np.full((p.N, p.A), -7.0)
+        if call == "plain":
+            check(eng.lib.evoamd_seed_states(eng._h, p.A, i32ptr(path), dptr(lpj)))
+        else:
+            check(eng.lib.evoamd_seed_states_ex(eng._h, p.A, 0, i32ptr(path), dptr(lpj)))
+        got.append((eng.download_states_packed(), path, lpj))
+    assert np.array_equal(got[0][1], p.path) and got[0][0].any()
+    assert all(np.array_equal(x, y) for x, y in zip(got[0], got[1]))

@@ -3,8 +3,9 @@ csrc/kernels_sweep.hpp) against its NumPy mirror (evo_amd.variational.sweep_stat
 
 1. proposals against the mirror; 2. the loop against the separate calls, bit for bit; 3. the rows it leaves equal a fresh
 pass; 4. monotone and closed, by brute force at H = 10; 5. an under-seeded K^n improves; 6. refusals leave everything as
-it was; 7. the Model level.
+it was; 7. the Model level; 8. the plain, _ex and _nb entry points of the library give the same bits.
 """
+import ctypes
 import functools
 
 import numpy as np
@@ -12,6 +13,8 @@ import pytest
 
 import _sweep_problems as sp
 from _seed_problems import make_data, make_theta
+from evo_amd import _lib
+from evo_amd._lib import check, dptr, i32ptr
 from evo_amd.engine import Engine, EvoAmdError
 from evo_amd.models import BSC, SSSC
 from evo_amd.variational import seed_states_host, sweep_states_host
@@ -362,3 +365,68 @@ def test_float32_model_refuses(model_eng):
 def test_kernel_class_is_named(eng):
     from evo_amd import _lib
     assert eng.lib.evoamd_kernel_name(_lib.KERNEL_IDS_EXTRA["sweep"]) == b"sweep"
+
+
+# ---- 8. the three generations of the ABI: Engine goes through the _nb calls alone, so the plain and the _ex calls are made here
+def _sweep_buffers(eng, with_score):
+    N = eng.N
+    out = {"score": np.full((N, eng.Cmax), -7.0) if with_score else None, "best_flip": np.full(N, -7, dtype=np.int32),
+           "gain": np.full(N, -7.0), "n_capped": np.full(N, -7, dtype=np.int32)}
+    ptr = [None if a is None else (dptr(a) if a.dtype == np.float64 else i32ptr(a)) for a in out.values()]
+    return out, ptr
+
+
+def _same(a, b):
+    return a.keys() == b.keys() and all(np.array_equal(a[k], b[k], equal_nan=True) for k in a if a[k] is not None)
+
+
+@pytest.mark.parametrize("algo", sp.ALGOS)
+def test_plain_ex_and_nb_propose_calls_agree(eng, algo):
+    p = sp.problem(algo, "tight")
+    _install(eng, p)
+    got = []
+    for call in ("plain", "ex", "nb"):
+        eng.upload_states(p.ss)
+        out, ptr = _sweep_buffers(eng, True)
+        if call == "plain":
+            check(eng.lib.evoamd_sweep_propose(eng._h, p.P, p.q, *ptr))
+        elif call == "ex":
+            check(eng.lib.evoamd_sweep_propose_ex(eng._h, p.P, p.q, 0, *ptr))
+        else:
+            so = _lib.SweepOut()
+            so.score, so.best_flip, so.gain, so.n_capped = ptr
+            check(eng.lib.evoamd_sweep_propose_nb(eng._h, p.P, p.q, 0, ctypes.byref(so)))
+        assert not (out["best_flip"] == -7).any() and not (out["n_capped"] == -7).any()
+        got.append((out, eng.download_candidates()))
+    for out, cands in got[1:]:
+        assert _same(out, got[0][0])
+        (cand, counts, lpjc), (cand0, counts0, lpjc0) = cands, got[0][1]
+        assert np.array_equal(counts, counts0) and counts.sum() > 0
+        for n in range(p.N):  # the emitted rows (the batch behind them is not the call's)
+            assert np.array_equal(cand[n, :counts[n]], cand0[n, :counts[n]])
+            assert np.array_equal(lpjc[n, :counts[n]], lpjc0[n, :counts[n]])
+
+
+@pytest.mark.parametrize("algo", sp.ALGOS)
+def test_plain_ex_and_nb_states_calls_agree(eng, algo):
+    p = sp.problem(algo, "tight")
+    _install(eng, p)
+    got = []
+    for call in ("plain", "ex", "nb"):
+        eng.upload_states(p.ss)
+        out, ptr = _sweep_buffers(eng, False)
+        trace, n_done = np.zeros((1, 3)), ctypes.c_int(0)
+        head = (eng._h, 1, p.P, p.q, p.S, 0)
+        if call == "plain":
+            check(eng.lib.evoamd_sweep_states(*head, dptr(trace), ctypes.byref(n_done), *ptr[1:]))
+        elif call == "ex":
+            check(eng.lib.evoamd_sweep_states_ex(*head, 0, dptr(trace), ctypes.byref(n_done), *ptr[1:]))
+        else:
+            so = _lib.SweepOut()
+            so.best_flip, so.gain, so.n_capped = ptr[1:]
+            check(eng.lib.evoamd_sweep_states_nb(*head, 0, dptr(trace), ctypes.byref(n_done), ctypes.byref(so)))
+        assert n_done.value == 1 and not (out["best_flip"] == -7).any()
+        got.append((out, trace, _state(eng)))
+    for out, trace, state in got[1:]:
+        assert _same(out, got[0][0]) and np.array_equal(trace, got[0][1])
+        assert all(np.array_equal(x, y) for x, y in zip(state, got[0][2]))
