@@ -55,7 +55,7 @@ KERNEL_IDS = {
 # classes outside the EM path, added after tests/test_gpu_validity.py recorded its launch census over KERNEL_IDS (which
 # therefore stays as it is); Engine.timing / Engine.kernel_time_ms take names of either table
 KERNEL_IDS_EXTRA = {"posterior_sample": 23, "seed_states": 24, "loglik_proposal": 25, "loglik_lpj": 26, "loglik_fold": 27,
-                    "remap_latents": 28, "stats_kappa": 29, "sweep": 30, "sweep_swap": 31}
+                    "remap_latents": 28, "stats_kappa": 29, "sweep": 30, "sweep_swap": 31, "resize": 32}
 
 
 def kernel_id(name):
@@ -148,6 +148,8 @@ SIGNATURES = {
     "evoamd_posterior_scores": (_I, [_vp, _c_dp, _c_dp, _c_i32p, _c_i32p, _c_dp]),
     "evoamd_remap_latents": (_I, [_vp, _c_i32p, _I, _c_i32p, ctypes.POINTER(_I64)]),
     "evoamd_adopt_remapped_states": (_I, [_vp]),
+    "evoamd_resize_states": (_I, [_vp, _I, _c_i32p]),
+    "evoamd_adopt_resized_states": (_I, [_vp]),
     "evoamd_latent_map_counts": (_I, [_vp, ctypes.POINTER(_I64)]),
     "evoamd_acc_size": (_I64, [_vp]),
     "evoamd_stats": (_I, [_vp, _c_dp]),
@@ -190,6 +192,7 @@ SIGNATURES = {
     "evoamd_comm_allreduce_host": (_I, [_vp, _c_dp, _I64, _I]),
     "evoamd_comm_destroy": (_I, [_vp]),
     "evoamd_timing_enable": (_I, [_vp, _I]),
+    "evoamd_timing_enable64": (_I, [_vp, _U64]),
     "evoamd_timing_reset": (_I, [_vp]),
     "evoamd_kernel_time_ms": (_I, [_vp, _I, _c_dp, ctypes.POINTER(_I64)]),
     "evoamd_kernel_name": (ctypes.c_char_p, [_I]),

@@ -37,6 +37,7 @@
 #include "kernels_refine.hpp"
 #include "kernels_loglik_estimate.hpp"
 #include "kernels_remap.hpp"
+#include "kernels_resize.hpp"
 #include "kernels_sweep.hpp"
 #include "kernels_sweep_swap.hpp"
 
@@ -168,6 +169,7 @@ enum {  // internal kernel ids (see evoamd_kernel_name)
                      // says which route a pass took
   KID_SWEEP,         // evoamd_sweep_propose / evoamd_sweep_states: the proposal kernel (ES3C: with the transpose of GP)
   KID_SWEEP_SWAP,    // evoamd_sweep_*_nb with EVOAMD_SWEEP_SWAP: the swap proposal kernel
+  KID_RESIZE,        // evoamd_resize_states: the resize kernel (downloads excluded)
   KID_COUNT
 };
 
@@ -597,6 +599,15 @@ struct evoamd_ctx {
   DevBuf<unsigned long long> remap_sum, map_counts;
   i64 remap_N = 0;
   int remap_S = 0, remap_H = 0;
+  // evoamd_resize_states: K^n at the new S, its digests and src_slot (N, S_new); grown on demand and kept through the
+  // configure between the resize and evoamd_adopt_resized_states, like the remap scratch.  resize_S = 0: nothing to adopt.
+  DevBuf<u64> resize_states, resize_dig;
+  DevBuf<int> resize_src;
+  i64 resize_N = 0;
+  int resize_S = 0, resize_H = 0;
+  // the K^n (kn_gen) the rows in lpj were computed for or uploaded beside; selection carries it along (it writes the lpj of
+  // every state it swaps in)
+  unsigned long long lpj_kn_gen = 0;
   bool kn_lost = false;
   i64 kn_refill = 0;  // while kn_lost: rows [0, kn_refill) have been uploaded again by evoamd_upload_states_packed
   // evoamd_generate (kernels_generate.hpp): Theta^gen, the given states and the outputs of the last call, grown on demand
@@ -610,7 +621,7 @@ struct evoamd_ctx {
   int rank = 0, world = 1;
   // timing
   bool timing = false;
-  unsigned timing_mask = 0xFFFFFFFFu;  // which kernel classes record events (each record costs ~5 us of stream time)
+  u64 timing_mask = ~0ull;  // which kernel classes record events (each record costs ~5 us of stream time)
   std::vector<TimedSpan> spans;
   std::vector<hipEvent_t> pool;
   double t_ms[KID_COUNT] = {0};
@@ -702,8 +713,10 @@ static void on_kn_changed(evoamd_ctx *c, KnBy by) {
   // the kappa records follow K^n through a selection only, and only when both sides hold current ones (made_selection
   // stamps them again); every other event -- and every other gen++ above and below -- leaves them behind
   c->kap_carry = by == KN_BY_SELECTION && c->kap_gen == c->gen && c->cand_kap_gen == c->gen;
+  const bool rows_follow = by == KN_BY_SELECTION && c->lpj_kn_gen == c->kn_gen;
   c->gen++;
   c->kn_gen++;
+  if (rows_follow) c->lpj_kn_gen = c->kn_gen;
   if (by == KN_BY_CALLER) c->need_known = false;
 }
 // kappa records (ES3C, option "stats_kappa"): the pass over K^n / over the candidate batch wrote them under this gen (or not)
@@ -728,6 +741,7 @@ static void on_estep_route(evoamd_ctx *c, bool fused) { c->last_estep_fused = fu
 // ---- lpj rows, row statistics, counters a kernel clears on its way
 static void on_lpj_overwritten(evoamd_ctx *c) { c->rows_fresh = false; }  // rowmax / rowsum / Fs partials describe other rows
 static void made_row_stats(evoamd_ctx *c) { c->rows_fresh = true; }
+static void made_lpj_rows(evoamd_ctx *c) { c->lpj_kn_gen = c->kn_gen; }  // the rows in lpj are those of the resident K^n
 // a chain is about to append to the on-the-fly lists; the caller has checked + cleared them unless they were clean
 static void on_lists_claimed(evoamd_ctx *c) {
   if (!c->lists_clean) c->pending_skip = 0;
@@ -778,6 +792,7 @@ static void made_fused_estep(evoamd_ctx *c, bool inkernel_census) {
   on_kn_changed(c, KN_BY_SELECTION);
   if (inkernel_census) made_census(c);
   made_row_stats(c);
+  made_lpj_rows(c);  // (the fused kernel evaluates K^n itself and keeps the rows of what it swaps in)
   c->kap_carry = false;  // the fused kernel carries no kappa records
   c->have_cand = false, c->cand_from_device = true;
   on_estep_route(c, true);
@@ -815,6 +830,7 @@ static void made_predictive(evoamd_ctx *c, i64 N) { c->pred_N = N; }  // 0: noth
 static void made_generated(evoamd_ctx *c, int keep) { c->gen_keep = keep; }  // -1: no call has completed
 static void made_posterior_samples(evoamd_ctx *c, int keep) { c->ps_keep = keep; }  // -1: nothing to download (no EM state reads it)
 static void made_remap(evoamd_ctx *c, i64 N, int S, int H_new) { c->remap_N = N, c->remap_S = S, c->remap_H = H_new; }  // 0: nothing to adopt
+static void made_resize(evoamd_ctx *c, i64 N, int S_new, int H) { c->resize_N = N, c->resize_S = S_new, c->resize_H = H; }  // 0: nothing to adopt
 static void made_loglik_draws(evoamd_ctx *c, int keep) { c->lle_keep = keep; }  // -1: nothing to download (no EM state reads it)
 // ---- validity: end
 
@@ -824,7 +840,7 @@ struct SpanGuard {
   hipStream_t stream;  // where the span's work is enqueued: the main stream unless the caller names another
   hipEvent_t a = nullptr, b = nullptr;
   SpanGuard(evoamd_ctx *ctx, int k, hipStream_t s = nullptr) : c(ctx), kid(k), stream(s ? s : ctx->stream) {
-    if (!c->timing || !((c->timing_mask >> k) & 1u)) return;
+    if (!c->timing || !((c->timing_mask >> k) & 1ull)) return;
     auto get = [&]() {
       hipEvent_t e;
       if (!c->pool.empty()) {
@@ -935,6 +951,7 @@ static int set_kernel_lds_limits() {
     for (const void *f : sk) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   }
   HIP_TRY(hipFuncSetAttribute((const void *)remap_latents_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, REMAP_LDS_BYTES));
+  HIP_TRY(hipFuncSetAttribute((const void *)resize_states_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RESIZE_LDS_BYTES));
   TRY(kn_set_lds_limits());
   {
     const void *wk[] = {(const void *)sssc_stats_wave_kernel<0, 4>,  (const void *)sssc_stats_wave_kernel<1, 4>,
@@ -1752,6 +1769,7 @@ extern "C" int evoamd_upload_lpj(evoamd_ctx *c, const double *lpj) {
   HIP_TRY(hipMemcpyAsync(c->lpj, lpj, (size_t)c->N * c->L * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   on_lpj_overwritten(c);
+  made_lpj_rows(c);  // the caller's word for it, as for the states it uploads
   return 0;
 }
 
@@ -2838,9 +2856,12 @@ static int estep_resident_pass(evoamd_ctx *c) {
   if (c->prefetch_gen == c->gen) {  // evoamd_mstep_device already enqueued exactly this pass
     drop_prefetch(c);
     std::swap(c->lpj, c->lpj_alt);
+    made_lpj_rows(c);
     return 0;
   }
-  return lpj_resident_launch(c, c->lpj, batch_hints(c, 0));
+  TRY(lpj_resident_launch(c, c->lpj, batch_hints(c, 0)));
+  made_lpj_rows(c);
+  return 0;
 }
 
 // the argument checks the E-step entry points share (evoamd_evolve_states has wider rules of its own for the rest)
@@ -3562,6 +3583,103 @@ extern "C" int evoamd_adopt_remapped_states(evoamd_ctx *c) {
   c->remap_states.reset();
   c->remap_dig.reset();
   made_remap(c, 0, 0, 0);
+  on_kn_changed(c, KN_BY_CALLER);
+  on_kn_complete(c);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// K^n resized: S changes, the best states stay, new slots are filled near the best (kernels_resize.hpp has the law)
+// ---------------------------------------------------------------------------------------
+// Writes into context-owned scratch and remembers (N, S_new, H) with it; the resident K^n, the lpj rows and every flag
+// stay as they are.  Every refusal comes before anything is launched or allocated.
+extern "C" int evoamd_resize_states(evoamd_ctx *c, int S_new, int32_t *src_slot_out) {
+  REQUIRE(c && c->configured, "evoamd_resize_states: nothing is resident (configure and upload, initialise or seed K^n first)");
+  REQUIRE_KN(c);
+  REQUIRE(c->lpj_kn_gen == c->kn_gen,
+          "evoamd_resize_states: the lpj rows are not those of the resident K^n (evoamd_lpj_resident or evoamd_upload_lpj first)");
+  const int S = c->S, H = c->H, HW = c->HW, bg = c->bg_unit ? 1 : 0;
+  REQUIRE(S_new >= 1, "evoamd_resize_states: S_new must be positive");
+  REQUIRE(c->dig && H <= DIG_MAX_H, "evoamd_resize_states: H must be at most 16384 (the digests' latent indices)");
+  if (S_new == S) return fail(EVOAMD_E_INVALID, "evoamd_resize_states: S_new = %d is the resident S: nothing to resize", S_new);
+  if (S_new > RESIZE_MAX_S || S > RESIZE_MAX_S)
+    return fail(EVOAMD_E_INVALID, "evoamd_resize_states: S = %d -> S_new = %d: at most %d states per datapoint are supported",
+                S, S_new, RESIZE_MAX_S);
+  const i64 Hv = H - bg;
+  if (S_new > S && Hv * (Hv + 1) / 2 - 1 < S_new)
+    return fail(EVOAMD_E_INVALID,
+                "evoamd_resize_states: Hv (Hv + 1) / 2 - 1 = %lld neighbours of the best state are fewer than S_new = %d states "
+                "(Hv = %lld)", (long long)(Hv * (Hv + 1) / 2 - 1), S_new, (long long)Hv);
+  int W = RESIZE_WAVES;
+  const size_t share = resize_lds_words(S, S_new, HW) * sizeof(u64);
+  while (W > 1 && W * share > RESIZE_LDS_BYTES) W >>= 1;
+  if (share > RESIZE_LDS_BYTES)
+    return fail(EVOAMD_E_INVALID, "evoamd_resize_states: the keys of S = %d states, %d words of the best state and the list of "
+                "S_new = %d slots (%zu bytes) do not fit one wavefront's share of LDS", S, HW, S_new, share);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t N = (size_t)c->N;
+  {  // does the scratch fit?  Decided before anything is released, allocated or launched.
+    size_t grow = 0, released = 0;
+    auto plan = [&](size_t have, size_t want, size_t elem) {
+      if (want > have) grow += want * elem, released += have * elem;
+    };
+    plan(c->resize_states.size(), N * S_new * HW, sizeof(u64));
+    plan(c->resize_dig.size(), N * S_new, sizeof(u64));
+    plan(c->resize_src.size(), N * S_new, sizeof(int));
+    if (grow) {
+      size_t free_b = 0, total_b = 0;
+      HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+      if (grow > free_b + released)
+        return fail(EVOAMD_E_INVALID, "evoamd_resize_states: the resized K^n needs %zu bytes of device memory, %zu are free", grow,
+                    free_b + released);
+    }
+  }
+  made_resize(c, 0, 0, 0);  // whatever an earlier resize left is overwritten from here on
+  TRY(c->resize_states.ensure(c, N * S_new * HW));
+  TRY(c->resize_dig.ensure(c, N * S_new));
+  TRY(c->resize_src.ensure(c, N * S_new));
+  ResizeArgs a;
+  a.src = c->states;
+  a.lpj = c->lpj;
+  a.dst = c->resize_states;
+  a.dig = c->resize_dig;
+  a.src_slot = c->resize_src;
+  a.err = c->err;
+  a.N = c->N;
+  a.S = S, a.S2 = S_new, a.S_perm = c->S_perm, a.L = c->L;
+  a.H = H, a.HW = HW, a.Hv = (int)Hv, a.bg = bg;
+  {
+    const unsigned grid = (unsigned)std::min<i64>(cdiv(c->N, W), (i64)c->n_cu * 16);
+    SpanGuard g(c, KID_RESIZE);
+    resize_states_kernel<<<grid, 64 * W, W * share, c->stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "resize states");
+  }
+  if (src_slot_out) HIP_TRY(hipMemcpyAsync(src_slot_out, a.src_slot, N * S_new * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  TRY(check_err(c));  // (waits for the stream)
+  made_resize(c, c->N, S_new, H);
+  return 0;
+}
+
+// After the caller has configured the context for (N, H, S_new): the scratch becomes the resident K^n (a swap of the
+// buffers), as if the caller had uploaded it; the scratch is released, so a second adopt without a new resize is refused.
+extern "C" int evoamd_adopt_resized_states(evoamd_ctx *c) {
+  REQUIRE(c && c->configured, "configure first");
+  REQUIRE(c->resize_S > 0, "evoamd_adopt_resized_states: no resized states to adopt (evoamd_resize_states first; an adopt uses them up)");
+  if (c->N != c->resize_N || c->S != c->resize_S || c->H != c->resize_H)
+    return fail(EVOAMD_E_INVALID,
+                "evoamd_adopt_resized_states: the context is configured for (N, S, H) = (%lld, %d, %d), the resized states are "
+                "(%lld, %d, %d)", (long long)c->N, c->S, c->H, (long long)c->resize_N, c->resize_S, c->resize_H);
+  REQUIRE(c->dig && c->resize_states.size() >= c->states.size() && c->resize_dig.size() >= c->dig.size(),
+          "evoamd_adopt_resized_states: the scratch does not cover the geometry");
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(sync_streams(c));  // a prefetched pass may still read the old buffers
+  std::swap(c->states, c->resize_states);
+  std::swap(c->dig, c->resize_dig);
+  c->resize_states.reset();
+  c->resize_dig.reset();
+  c->resize_src.reset();
+  made_resize(c, 0, 0, 0);
   on_kn_changed(c, KN_BY_CALLER);
   on_kn_complete(c);
   return 0;
@@ -6611,7 +6729,15 @@ extern "C" int evoamd_timing_enable(evoamd_ctx *c, int on) {
   REQUIRE(c, "ctx is NULL");
   if (!on && c->timing) TRY(resolve_spans(c));
   c->timing = on != 0;
-  c->timing_mask = (unsigned)on;  // bit k = kernel class k; 1-bits beyond EVOAMD_K_COUNT are harmless
+  c->timing_mask = (u64)(i64)on;  // bit k = kernel class k; -1 reaches the classes from 32 on too
+  return 0;
+}
+
+extern "C" int evoamd_timing_enable64(evoamd_ctx *c, uint64_t on) {
+  REQUIRE(c, "ctx is NULL");
+  if (!on && c->timing) TRY(resolve_spans(c));
+  c->timing = on != 0;
+  c->timing_mask = on;  // bit k = kernel class k; 1-bits beyond EVOAMD_K_COUNT are harmless
   return 0;
 }
 
@@ -6640,6 +6766,6 @@ extern "C" const char *evoamd_kernel_name(int kid) {
                                          "stats_k3_4",   "stats_k5_8",     "stats_k9plus", "allreduce",    "estep_fused",
                                          "patches",      "init_states",    "posterior_sample", "seed_states",
                                          "loglik_proposal", "loglik_lpj",  "loglik_fold",     "remap_latents",
-                                         "stats_kappa",  "sweep",       "sweep_swap"};
+                                         "stats_kappa",  "sweep",       "sweep_swap",      "resize"};
   return (kid >= 0 && kid < KID_COUNT) ? names[kid] : "?";
 }

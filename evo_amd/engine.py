@@ -472,6 +472,27 @@ class Engine:
         nothing waits (an adopt uses the states up)."""
         check(self.lib.evoamd_adopt_remapped_states(self._h))
 
+    # ---- K^n resized (evo_amd.variational.resize_states_host is the NumPy mirror) ------------------
+    def resize_states(self, S_new):
+        """K^n at ``S_new`` states per datapoint, computed on the device from the resident K^n and its lpj rows
+        (evoamd_resize_states; csrc/kernels_resize.hpp has the law): a shrink keeps the S_new best states in ascending old
+        slot; a grow keeps every state in place and fills the new slots with the one-flip, then two-flip neighbours of the
+        best state that the datapoint does not hold.  The result waits in scratch of the context for
+        adopt_resized_states(); the resident K^n, lpj and every flag stay as they are.  Returns src_slot int32 (N, S_new):
+        the old slot of every new slot, -1 for a fill.  EvoAmdError, with everything as it was, for what the law refuses
+        (S_new < 1, S_new = S, above 1024, the bound Hv (Hv + 1) / 2 - 1 >= S_new on a grow, lpj rows that are not those of
+        the resident K^n)."""
+        S_new = int(S_new)
+        src = np.empty((self.N, max(S_new, 1)), dtype=np.int32)
+        check(self.lib.evoamd_resize_states(self._h, S_new, i32ptr(src)))
+        return src
+
+    def adopt_resized_states(self):
+        """After configure() for S_new (same N and H): the states resize_states() left become the resident K^n, as an upload
+        of the same rows would make them.  EvoAmdError, with K^n as it was, when the geometry differs from the resize's or
+        nothing waits (an adopt uses the states up)."""
+        check(self.lib.evoamd_adopt_resized_states(self._h))
+
     def latent_map_counts(self):
         """int64 (H,): the datapoints whose most probable state of K^n (first column of maximal lpj) has latent h on."""
         out = np.empty(self.H, dtype=np.int64)
@@ -936,14 +957,14 @@ class Engine:
     def timing(self, on=True):
         """on: True (all kernel classes), False, or an iterable of class names (_lib.KERNEL_IDS, _lib.KERNEL_IDS_EXTRA)."""
         if on is True:
-            mask = -1
+            mask = (1 << 64) - 1
         elif not on:
             mask = 0
         else:
             mask = 0
             for name in on:
                 mask |= 1 << _lib.kernel_id(name)
-        check(self.lib.evoamd_timing_enable(self._h, mask))
+        check(self.lib.evoamd_timing_enable64(self._h, mask))
 
     def timing_reset(self):
         check(self.lib.evoamd_timing_reset(self._h))

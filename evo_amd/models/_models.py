@@ -1070,6 +1070,66 @@ class Model:
             new_suff["lpj"] = neng.download_lpj()
         return new_model, new_theta, new_suff, {"n_replaced": n_replaced, "sum_replaced": total, "index": idx}
 
+    def resize_states(self, model_params, my_suff_stat, my_data, S_new):
+        """Change S, the number of states per datapoint, and carry K^n along on the device (Engine.resize_states;
+        csrc/kernels_resize.hpp has the law, evo_amd.variational.resize_states_host is the NumPy mirror, bit for bit).
+        Per datapoint, with the slots ranked by their lpj (descending, ties by ascending slot; NaN and +-inf as -inf): a
+        SHRINK keeps the ``S_new`` best states in ascending old slot; a GROW keeps every state in place and fills the new
+        slots with the one-flip neighbours of the best state in ascending latent, then its two-flip neighbours, skipping
+        the empty state and states the datapoint holds (requires Hv (Hv + 1) / 2 - 1 >= S_new).  The rows that rank are
+        the caller's: my_suff_stat["lpj"] where K^n is uploaded (sync_host=True, or a K^n that was not resident; None
+        there: computed under ``model_params``), else the resident rows of the last E-step, seed or refine.  Returns
+        (new_model, new_suff, info): ``new_model`` is type(self)(D, H, S_new, ...) with this model's settings ON THE SAME
+        ENGINE, prepared (configure, data, masks) with the resized K^n resident and its lpj rows recomputed under
+        ``model_params``, so encode, posterior_scores, sweep_resident_states, refine_resident_states or step can follow
+        at once; ``new_suff`` has my_suff_stat's keys re-derived for S_new ("ss" / "lpj" None with sync_host=False,
+        downloaded once with sync_host=True; an "Mprime" above S_new becomes S_new); ``info`` = {"src_slot" int32 (N,
+        S_new): the old slot of every new slot, -1 for a fill, "F_before", "F_after" (N,): posterior_scores' F per
+        datapoint on either side}.  This model is invalidated (its K^n is gone from the device; it uploads again when
+        used).  What remap_latents admits -- the background unit, incomplete data, S_perm 0 / 1 -- is admitted here;
+        the float32 mode is not: NotImplementedError (its rows rank in float32, where ties differ from the mirror's).
+        ValueError before the device is touched for a size the law refuses.  Several ranks: each resizes its shard, no
+        collective."""
+        from ..variational.utils import check_resize
+        permanent = my_suff_stat["permanent"]
+        S2 = check_resize(self.S, S_new, self.H, bool(permanent["background"]))
+        if self.dtype == np.float32:
+            raise NotImplementedError("resize_states is not available in the float32 mode")
+        if not self.sync_host and not self._resident and my_suff_stat.get("ss") is None:
+            raise ValueError("resize_states: K^n is neither resident on the device nor in my_suff_stat['ss']")
+        uploads = self._kn_uploads  # (see reconstruct(): decide before _prepare() runs)
+        eng = self._prepare(my_suff_stat, my_data)
+        theta = dict(model_params)  # (the precompute stores its derived keys and zeroes the reset counters: on copies)
+        self.E_step_precompute(theta, dict(my_suff_stat), my_data)
+        if model_params is not self._dev_theta:
+            self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
+        if self.sync_host or self._kn_uploads != uploads:
+            if my_suff_stat.get("lpj") is None:
+                eng.lpj_resident()
+            else:
+                eng.upload_lpj(my_suff_stat["lpj"])
+        F_before = eng.posterior_scores()["F"]
+        src_slot = eng.resize_states(S2)
+        new_model = type(self)(self.D, self.H, S2, **self._clone_kwargs())
+        new_suff = dict(my_suff_stat)
+        derived = _host_init_states(0, S2, self.H, "fit", "randflip", 1, 1, 1, None, None, None, permanent)
+        for key in ("incl", "sm", "S_perm"):
+            new_suff[key] = derived[key]
+        if new_suff.get("Mprime") is not None:
+            new_suff["Mprime"] = min(int(new_suff["Mprime"]), S2)
+        new_suff["ss"] = new_suff["lpj"] = None
+        self.invalidate()  # from here on the engine belongs to the new geometry
+        neng = new_model._prepare(new_suff, my_data, upload_states=False)
+        neng.adopt_resized_states()
+        new_model._resident = True
+        new_model.E_step_precompute(dict(model_params), dict(new_suff), my_data)
+        neng.lpj_resident()
+        F_after = neng.posterior_scores()["F"]
+        if self.sync_host:
+            new_suff["ss"] = neng.download_states()
+            new_suff["lpj"] = neng.download_lpj()
+        return new_model, new_suff, {"src_slot": src_slot, "F_before": F_before, "F_after": F_after}
+
     def latent_usage(self, model_params, my_suff_stat, my_data):
         """Which latents the data use, over all ranks: {"usage": (H,) = sum_n E_q[s_h] / N -- the column sums one
         statistics pass leaves in its accumulator, all-reduced like it --, "map_count": int64 (H,) = datapoints whose most

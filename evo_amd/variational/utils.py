@@ -760,6 +760,80 @@ def remap_states_host(ss, index, S_perm=0, background=False):
     return out, n_replaced
 
 
+# ---- K^n resized: the NumPy mirror of evoamd_resize_states (csrc/kernels_resize.hpp) ------------------------------------------
+#
+# Per datapoint, from the S varying slots of K^n and the lpj row (the permanent all-zero column of S_perm = 1 is not a slot);
+# Hv = H - background.  Slot j has key seed_key(lpj[n, S_perm + j]): NaN and +-inf rank as -inf, -0 equals +0; rank order is
+# descending key, then ascending slot.  Shrink (S' < S): the kept slots are the first S' in rank order, written in ascending
+# old slot; src_slot[n, j'] is the old slot of new slot j'.  Grow (S' > S): slots 0 .. S - 1 in place, src_slot[n, j] = j; b =
+# the best varying state (rank 0), e_c = candidate c of the enumeration {0}, .. {Hv - 1}, {0,1}, {0,2}, .. {Hv-2, Hv-1}; the
+# candidate fill f_c = b XOR e_c is skipped when it has no varying latent on or equals a state the datapoint holds; slots S,
+# S + 1, .. take the unskipped f_c in ascending c, src_slot -1.  Bound: Hv (Hv + 1) / 2 - 1 >= S'.
+RESIZE_MAX_S = 1024  # RESIZE_MAX_S of csrc/kernels_resize.hpp
+
+
+def check_resize(S, S_new, H, background=False):
+    """``S_new`` as an int the law admits for a K^n of S states of H latents; ValueError naming the rule otherwise."""
+    S_new = int(S_new)
+    if S_new < 1:
+        raise ValueError("resize: S_new = %d must be positive" % S_new)
+    if S_new == S:
+        raise ValueError("resize: S_new = %d is the S of K^n: nothing to resize" % S_new)
+    if S_new > RESIZE_MAX_S or S > RESIZE_MAX_S:
+        raise ValueError("resize: S = %d -> S_new = %d: at most %d states per datapoint are supported" % (S, S_new, RESIZE_MAX_S))
+    if H > REMAP_MAX_H:
+        raise ValueError("resize: H = %d exceeds %d" % (H, REMAP_MAX_H))
+    Hv = H - (1 if background else 0)
+    if S_new > S and Hv * (Hv + 1) // 2 - 1 < S_new:
+        raise ValueError("resize: Hv (Hv + 1) / 2 - 1 = %d neighbours of the best state are fewer than S_new = %d states "
+                         "(Hv = %d)" % (Hv * (Hv + 1) // 2 - 1, S_new, Hv))
+    return S_new
+
+
+def _resize_enumeration(Hv):
+    for a in range(Hv):
+        yield (a,)
+    for a in range(Hv):
+        for b in range(a + 1, Hv):
+            yield (a, b)
+
+
+def resize_states_host(ss, lpj, S_perm, S_new, background=False):
+    """K^n at ``S_new`` states per datapoint as evoamd_resize_states / Model.resize_states lay it out: ``ss`` bool (N, S, H),
+    ``lpj`` (N, S_perm + S) -> (states bool (N, S_new, H), src_slot int32 (N, S_new)).  Host only; ValueError for a size the
+    law refuses."""
+    ss = np.asarray(ss, dtype=bool)
+    lpj = np.asarray(lpj, dtype=np.float64)
+    N, S, H = ss.shape
+    assert S_perm in (0, 1) and lpj.shape == (N, S_perm + S), (lpj.shape, (N, S_perm + S))
+    S2 = check_resize(S, S_new, H, background)
+    Hv = H - (1 if background else 0)
+    out = np.zeros((N, S2, H), dtype=bool)
+    src = np.full((N, S2), -1, dtype=np.int32)
+    for n in range(N):
+        row = np.where(np.isfinite(lpj[n, S_perm:]), lpj[n, S_perm:], -np.inf) + 0.0  # the order of seed_key
+        order = np.lexsort((np.arange(S), -row))
+        if S2 < S:
+            kept = np.sort(order[:S2])
+            out[n], src[n] = ss[n, kept], kept
+            continue
+        out[n, :S], src[n, :S] = ss[n], np.arange(S)
+        b = ss[n, order[0]]
+        held = {s.tobytes() for s in ss[n]}
+        at = S
+        for e in _resize_enumeration(Hv):
+            if at == S2:
+                break
+            f = b.copy()
+            f[list(e)] ^= True
+            if not f[:Hv].any() or f.tobytes() in held:
+                continue
+            out[n, at] = f
+            at += 1
+        assert at == S2  # (the bound)
+    return out, src
+
+
 def latent_usage_host(ss, lpj, S_perm=0):
     """NumPy mirror of Model.latent_usage on one rank: {"usage": (H,) = sum_n E_q[s_h] / N with q_ns = exp(lpj_ns - max) /
     (sum_s exp(lpj_ns - max) + tiny) as the statistics pass forms it, "map_count": int64 (H,) = datapoints whose first

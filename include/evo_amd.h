@@ -898,6 +898,34 @@ int evoamd_patches_merge_predictive(evoamd_ctx *ctx, int H, int W, int C, int ph
  * (N, S, H) of the context differ from the scratch's, and for an adopt without a remap before it (a second adopt). */
 int evoamd_remap_latents(evoamd_ctx *ctx, const int32_t *index, int H_new, int32_t *n_replaced_out, int64_t *sum_out);
 int evoamd_adopt_remapped_states(evoamd_ctx *ctx);
+/* ---- K^n resized: S changes, the best states stay, new slots are filled near the best -- */
+/* (csrc/kernels_resize.hpp has the law; evo_amd.variational.resize_states_host is its NumPy mirror, bit for bit.)  Per
+ * datapoint, independently, from the S varying slots of the resident K^n and the datapoint's lpj row (the permanent all-zero
+ * column of S_perm = 1 is not a slot and is carried over untouched); Hv = H - 1 with the "background_unit" option, else H:
+ *   keys    slot j has key seed_key(lpj[n, S_perm + j]): NaN and +-inf rank as -inf, -0 equals +0.  Rank order is
+ *           descending key, then ascending slot.
+ *   shrink  (S_new < S) the kept slots are the first S_new in rank order, written in ascending old slot (a stable
+ *           compaction); src_slot[n, j'] is the old slot of new slot j'.
+ *   grow    (S_new > S) slots 0 .. S - 1 are copied in place, src_slot[n, j] = j.  With b the best varying state (rank 0)
+ *           and e_c candidate c of the enumeration {0}, .. {Hv - 1}, {0,1}, {0,2}, .. {Hv-2, Hv-1}, the candidate fill is
+ *           f_c = b XOR e_c: the one-flip neighbours of the best state in ascending latent, then its two-flip neighbours.
+ *           f_c is skipped when it has no varying latent on or equals (on the full words) a state the datapoint holds.
+ *           Slots S, S + 1, .. take the unskipped f_c in ascending c; src_slot is -1 there.  The background bit stays on.
+ *   bound   Hv (Hv + 1) / 2 - 1 >= S_new on a grow, so that the enumeration cannot run out.
+ * The result -- packed states (N, S_new, ceil(H/64)), their digests, src_slot int32 (N, S_new) -- goes to scratch the context
+ * owns and that survives evoamd_configure; the resident K^n, the lpj rows and every validity flag stay as they are.
+ * src_slot_out (N * S_new) may be NULL.  No floating point beyond the key, no random numbers, no atomics: two calls give the
+ * same bits.  EVOAMD_E_INVALID, before anything is launched or allocated and with the context as it was, for: no configured
+ * context or a K^n lost to a failed evoamd_init_states; lpj rows that are not those of the resident K^n (evoamd_lpj_resident,
+ * an E-step or evoamd_upload_lpj after the last change of K^n by the caller makes them so); S_new < 1, S_new = S, S or
+ * S_new above 1024; H above 16384; the bound; a share of LDS -- 8 (S + ceil(H/64)) + 4 S_new bytes -- above 150 KiB (no
+ * admitted shape reaches it); scratch that does not fit the free device memory.
+ * Then: evoamd_configure for (N, H, S_new), data and Theta as usual, and evoamd_adopt_resized_states, which makes the scratch
+ * the resident K^n and digests -- what evoamd_upload_states of the same rows leaves, with the same invalidations -- and
+ * releases it.  EVOAMD_E_INVALID with K^n as it was when (N, S, H) of the context differ from the scratch's, and for an
+ * adopt without a resize before it (a second adopt). */
+int evoamd_resize_states(evoamd_ctx *ctx, int S_new, int32_t *src_slot_out);
+int evoamd_adopt_resized_states(evoamd_ctx *ctx);
 /* counts_out (H): the number of datapoints whose most probable state of K^n -- the first column of maximal lpj, the rule of
  * evoamd_posterior_scores' best -- has latent h on.  Integer atomics: independent of the order.  Needs valid lpj rows;
  * nothing of the EM state changes. */
@@ -949,12 +977,15 @@ enum {
   EVOAMD_K_STATS_KAPPA = 29,   /* the ES3C statistics kernel on the kappa route (option "stats_kappa"), nested in EVOAMD_K_STATS */
   EVOAMD_K_SWEEP = 30,         /* evoamd_sweep_propose / evoamd_sweep_states: the proposal kernel (ES3C: with the transpose of GP) */
   EVOAMD_K_SWEEP_SWAP = 31,    /* evoamd_sweep_*_nb with EVOAMD_SWEEP_SWAP: the swap proposal kernel */
-  EVOAMD_K_COUNT = 32
+  EVOAMD_K_RESIZE = 32,        /* evoamd_resize_states: the resize kernel (downloads excluded) */
+  EVOAMD_K_COUNT = 33
 };
 /* on = bit mask of kernel classes to time (bit k = class k; -1 = all, 0 = off).  Each timed span
  * records two HIP events on the compute stream, which costs about 10 us of stream time per span:
  * a throughput run times only the class it needs. */
 int evoamd_timing_enable(evoamd_ctx *ctx, int on);
+/* the same with a 64-bit mask: the classes from 32 on have no bit in the int (which reaches them with -1 only) */
+int evoamd_timing_enable64(evoamd_ctx *ctx, uint64_t on);
 int evoamd_timing_reset(evoamd_ctx *ctx);
 int evoamd_kernel_time_ms(evoamd_ctx *ctx, int kernel_class, double *avg_ms, int64_t *launches);
 const char *evoamd_kernel_name(int kernel_class);
