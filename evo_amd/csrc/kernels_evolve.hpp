@@ -8,11 +8,42 @@
 //                     distinct and uniform over H.
 // The reference consumes NumPy's global Mersenne-Twister stream datapoint by datapoint, which
 // a batched generator cannot reproduce; this kernel uses a counter-based generator keyed on
-// (seed, n, purpose, index), so results are reproducible for a given seed but only
-// *statistically* equivalent to the reference (SURVEY section 7 "RNG order").  Weighted sampling
-// without replacement uses exponential races (key_s = -log(u_s)/p_s, take the smallest
-// n_parents), which is exact successive sampling.  Duplicates are not removed here: the
-// selection kernel (vary_kn_kernel) applies the reference's de-duplication rules.
+// (seed, n, purpose, index), so against the reference the law is the same and the draws are not
+// (SURVEY section 7 "RNG order").  Weighted sampling without replacement uses exponential races
+// (key_s = -log(u_s)/p_s, take the smallest n_parents), which is exact successive sampling.
+// Duplicates are not removed here: the selection kernel (vary_kn_kernel) applies the reference's
+// de-duplication rules.
+//
+// THE STREAM (evo_amd/variational/eas_counter.py: evolve_randflip_counter and evolve_states_counter are the NumPy
+// mirrors of the two kernels below, bit for bit -- keep them, this block and tests/test_gpu_evolve_parity.py in step).
+// rng_u01(seed, n, purpose, index) below is integer hashing, one exact integer -> double conversion, one IEEE addition
+// and a multiplication by a power of two (kernels_init.hpp spells it out).  With Hd the operators' domain (H, or H - 1
+// with the permanent background unit, whose bit no operator touches and every child inherits):
+//   fast kernel     parent draw: the race uniform of state s is (purpose 1, index s).
+//                   flips: pick t of the p-th drawn parent is (purpose 2 + p, index t): r = int(u (Hd - t)), clamped to
+//                   Hd - t - 1, mapped to the r-th position the earlier picks left unused (they are kept sorted); child i
+//                   of the parent flips pick i and goes to slot p * n_children + i.
+//   general kernel  gsalt = (generation + 1) << 32.
+//                   parent draw: pool entry i is (gsalt + 1, i); P = min(|pool|, n_parents) parents.
+//                   randflip: the picks of parent p as above with (gsalt + 8 + 1024 + p, t).
+//                   crossing: pair t of combinations(range(P), 2) cuts at cp = 1 + int(u (Hd - 1)), clamped to Hd - 1,
+//                   u = (gsalt + 8 + 4096 + t, 0); children 2t and 2t + 1 are the two tail exchanges.
+//                   child kid has the purpose gsalt + 16 + kid: cross_randflip flips int(u Hd), clamped, u at index 0;
+//                   sparseflip judges every position against the (crossed) state before any flip, s_abs counted over
+//                   the domain after the crossing: a 1 at latent h flips iff the uniform at index 1 + h is < p1; the 0s
+//                   by geometric skipping from pos = -1, draw t at index 1 + Hd + t: pos += 1 + floor(log(u) /
+//                   log1p(-p0)) until pos >= Hd, each 0 landed on flips (p0 >= 1: every 0 flips, p0 <= 0: none).
+//   pools           generation 0: the K^n states in order.  Later: the previous generation's new unique states in slot
+//                   order, then the positions 1 <= u < S_perm + S + g0 of [incl; K^n; candidates] that one of its children
+//                   duplicated, ascending, each with lpj_unique[u - 1].  An empty pool ends the datapoint.
+//   de-duplication  a child is dropped if it equals a row of [incl; K^n; earlier candidates] -- incl is the all-zero state
+//                   with S_perm = 1 -- or an earlier child of its generation; the survivors are appended in np.unique's
+//                   row order (unsigned order of the MSB-first words).
+// The one step NumPy cannot repeat bit for bit is the race key, formed in float32: key = e / float(p) with e =
+// -__logf(max(float(u), FLT_MIN)), 1e30f where p <= 0, clamped at 3e38f; p = lpj - 2 min(min lpj, 0) in double (1 for
+// randparents); equal keys go to the lowest index.  The mirror forms the key in double from the same float32-rounded u
+// and p and reports the smallest relative gap among the first P + 1 sorted keys; a datapoint whose gap is below 2^-18
+// (six float32 steps of 2^-23 each, times four) counts as undecided and is left out of the comparison.
 #pragma once
 #include "common.hpp"
 #include "kernels_common.hpp"
@@ -61,8 +92,8 @@ __global__ __launch_bounds__(256) void evolve_randflip_kernel(
   lmin = wave_min(lmin);
   const double shift = 2.0 * fmin(lmin, 0.0);
   // Exponential race keys -log(u) / p in SINGLE precision, compared as unsigned integers (the bit pattern
-  // of a non-negative float is monotone): only the ORDER of the keys matters, this mode is statistically,
-  // not bit-wise, tied to the reference's sampler, and the kernel is VALU-issue bound -- one v_log_f32
+  // of a non-negative float is monotone): only the ORDER of the keys matters (THE STREAM above has the margin
+  // under which the NumPy mirror calls a draw undecided), and the kernel is VALU-issue bound -- one v_log_f32
   // and one v_rcp_f32 instead of the f64 routines, 32-bit DPP reductions instead of f64 ones.
   constexpr unsigned KEY_TAKEN = 0x7f800000u;  // +inf: slots that do not exist or were drawn already
   unsigned ukey[SPL];
@@ -165,8 +196,9 @@ __global__ __launch_bounds__(256) void evolve_randflip_kernel(
 //             the survivors are written in lexicographic order (np.unique's, eas.py:252-257) behind the
 //             candidates of the earlier generations, so the candidate batch IS new_states[new_and_unique].
 // The caller evaluates lpj of the batch between two generations (the next pool needs it).
-// Counter-based RNG keyed on (seed, n, generation, purpose, index): reproducible per seed, statistically --
-// not stream- -- equivalent to np.random.
+// Counter-based RNG keyed on (seed, n, generation, purpose, index): THE STREAM at the top of this file, which
+// evolve_states_counter (evo_amd/variational/eas_counter.py) repeats bit for bit; against np.random the law is the
+// same, the draws are not.
 // ---------------------------------------------------------------------------------------------------
 enum { EV_RANDFLIP = 0, EV_SPARSEFLIP = 1, EV_CROSS = 2, EV_CROSS_RANDFLIP = 3, EV_CROSS_SPARSEFLIP = 4 };
 
@@ -401,7 +433,9 @@ __global__ __launch_bounds__(64) void evolve_general_kernel(EvolveArgs a) {
             pos += 1;
           } else {
             const double u = rng_u01(a.seed, (u64)n, kp, 1 + (u64)H + t);
-            pos += 1 + (i64)floor(log(u) / l1p);
+            // (clamped before the conversion: at a pole of alpha p0 is ~1e-100 and the skip far beyond an i64)
+            const double skip = floor(log(u) / l1p);
+            pos += 1 + (skip < (double)H ? (i64)skip : (i64)H);
           }
           t++;
           if (pos >= H) break;

@@ -316,6 +316,10 @@ class Engine:
         return sums
 
     def evolve_randflip(self, n_parents, n_children, seed, fit_parents=True):
+        """fitparents / randparents + randflip for one generation on the device (evoamd_evolve_randflip); fills and
+        evaluates the candidate batch, slot p * n_children + i = child i of the p-th drawn parent, nothing de-duplicated.
+        Counter-based stream (csrc/kernels_evolve.hpp, "THE STREAM"): evo_amd.variational.evolve_randflip_counter is the
+        NumPy mirror, bit for bit wherever the float32 race keys of the parent draw are further apart than its margin."""
         check(self.lib.evoamd_evolve_randflip(self._h, int(n_parents), int(n_children), int(seed) & (2 ** 64 - 1),
                                               1 if fit_parents else 0))
 
@@ -337,7 +341,10 @@ class Engine:
 
     def evolve_states(self, mutation, n_parents, n_children, n_generations, seed, fit_parents=True, sparseness=0.0,
                       bitflip_prob=None):
-        """All EA operators / generations on the device (eas.py:153-313); fills and evaluates the candidate batch."""
+        """All EA operators / generations on the device (eas.py:153-313); fills and evaluates the candidate batch: the new
+        unique states of every generation, np.unique's row order within one.  Counter-based stream
+        (csrc/kernels_evolve.hpp, "THE STREAM"): evo_amd.variational.evolve_states_counter is the NumPy mirror, bit for
+        bit wherever the float32 race keys of the parent draws are further apart than its margin."""
         check(self.lib.evoamd_evolve_states(self._h, self.MUTATIONS[mutation], 1 if fit_parents else 0, int(n_parents),
                                             int(n_children), int(n_generations), int(seed) & (2 ** 64 - 1),
                                             float(sparseness), float("nan") if bitflip_prob is None else float(bitflip_prob)))

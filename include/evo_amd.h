@@ -346,9 +346,11 @@ int evoamd_lpj_single(evoamd_ctx *ctx, const double *y, const uint8_t *states_bo
 int evoamd_vary_kn(evoamd_ctx *ctx, int Mprime, double *sums_out);
 
 /* Device-side evolutionary candidate generation (fitness-proportional parents + random
- * bit flips, eas.py:10-43,138-146,153-313 for n_generations = 1), counter-based RNG:
- * statistically equivalent to, not stream-identical with, np.random.  Fills the resident
- * candidate batch (de-duplicated) and evaluates it. */
+ * bit flips, eas.py:10-43,138-146,153-313 for n_generations = 1), counter-based RNG: the
+ * law of the reference, not np.random's draws; the stream is documented in
+ * csrc/kernels_evolve.hpp and evo_amd.variational.evolve_randflip_counter repeats it bit for
+ * bit.  Fills the resident candidate batch (slot p * n_children + i: child i of the p-th
+ * drawn parent; vary_kn de-duplicates) and evaluates it. */
 int evoamd_evolve_randflip(evoamd_ctx *ctx, int n_parents, int n_children, uint64_t seed,
                            int fit_parents);
 
