@@ -26,6 +26,8 @@ SWEEP_INCOMPLETE = 1
 # evoamd_sweep_propose_nb / evoamd_sweep_states_nb: the neighbourhood bits beside it
 SWEEP_SWAP, SWEEP_NO_FLIP = 2, 4
 SWEEP_NEIGHBOURHOODS = {"flip": 0, "swap": SWEEP_SWAP | SWEEP_NO_FLIP, "both": SWEEP_SWAP}
+# evoamd_neighbour_bound: flags (EVOAMD_NBOUND_*)
+NBOUND_INCOMPLETE = 1
 
 # evoamd_posterior_sample: keep bits (EVOAMD_PSAMP_KEEP_*) and the output ids of evoamd_download_posterior_samples
 PSAMP_KEEP = {"slot": 1, "s": 2, "z": 4, "y": 8}
@@ -55,7 +57,8 @@ KERNEL_IDS = {
 # classes outside the EM path, added after tests/test_gpu_validity.py recorded its launch census over KERNEL_IDS (which
 # therefore stays as it is); Engine.timing / Engine.kernel_time_ms take names of either table
 KERNEL_IDS_EXTRA = {"posterior_sample": 23, "seed_states": 24, "loglik_proposal": 25, "loglik_lpj": 26, "loglik_fold": 27,
-                    "remap_latents": 28, "stats_kappa": 29, "sweep": 30, "sweep_swap": 31, "resize": 32}
+                    "remap_latents": 28, "stats_kappa": 29, "sweep": 30, "sweep_swap": 31, "resize": 32,
+                    "neighbour_bound": 33}
 
 
 def kernel_id(name):
@@ -74,6 +77,12 @@ class SweepOut(ctypes.Structure):
     """evoamd_sweep_out: the outputs of the _nb sweep calls, each pointer may be NULL."""
     _fields_ = [("score", _c_dp), ("best_flip", _c_i32p), ("gain", _c_dp), ("n_capped", _c_i32p),
                 ("best_swap", _c_i32p), ("swap_gain", _c_dp), ("n_capped_swap", _c_i32p)]
+
+
+class NboundOut(ctypes.Structure):
+    """evoamd_nbound_out: the outputs of evoamd_neighbour_bound, each pointer may be NULL."""
+    _fields_ = [("F", _c_dp), ("M", _c_dp), ("n_states", _c_i32p), ("n_capped", _c_i32p), ("best_score", _c_dp),
+                ("best_parent", _c_i32p), ("best_flip", _c_i32p), ("sum", _c_dp)]
 
 
 _I32 = ctypes.c_int32
@@ -145,6 +154,7 @@ SIGNATURES = {
     "evoamd_sweep_propose_nb": (_I, [_vp, _I, _I, ctypes.c_uint, ctypes.POINTER(SweepOut)]),
     "evoamd_sweep_states_nb": (_I, [_vp, _I, _I, _I, _I, _I, ctypes.c_uint, _c_dp, ctypes.POINTER(_I),
                                     ctypes.POINTER(SweepOut)]),
+    "evoamd_neighbour_bound": (_I, [_vp, _I, ctypes.c_uint, ctypes.POINTER(NboundOut)]),
     "evoamd_posterior_scores": (_I, [_vp, _c_dp, _c_dp, _c_i32p, _c_i32p, _c_dp]),
     "evoamd_remap_latents": (_I, [_vp, _c_i32p, _I, _c_i32p, ctypes.POINTER(_I64)]),
     "evoamd_adopt_remapped_states": (_I, [_vp]),

@@ -40,6 +40,7 @@
 #include "kernels_resize.hpp"
 #include "kernels_sweep.hpp"
 #include "kernels_sweep_swap.hpp"
+#include "kernels_nbound.hpp"
 
 // ---------------------------------------------------------------------------------------
 // error handling
@@ -170,6 +171,7 @@ enum {  // internal kernel ids (see evoamd_kernel_name)
   KID_SWEEP,         // evoamd_sweep_propose / evoamd_sweep_states: the proposal kernel (ES3C: with the transpose of GP)
   KID_SWEEP_SWAP,    // evoamd_sweep_*_nb with EVOAMD_SWEEP_SWAP: the swap proposal kernel
   KID_RESIZE,        // evoamd_resize_states: the resize kernel (downloads excluded)
+  KID_NBOUND,        // evoamd_neighbour_bound: the neighbourhood kernel (ES3C: with the transpose of GP) and the bound of the rows
   KID_COUNT
 };
 
@@ -590,6 +592,9 @@ struct evoamd_ctx {
   // evoamd_sweep_*_nb with EVOAMD_SWEEP_SWAP: swap_gain (N); best_swap (N, 2) and n_capped_swap (N).  Grown on demand.
   DevBuf<double> swap_d;
   DevBuf<int> swap_i;
+  // evoamd_neighbour_bound: F | M | F+ | best_score (N each); n_states | n_capped | best_parent | best_flip (N each).  Grown on demand.
+  DevBuf<double> nbound_d;
+  DevBuf<int> nbound_i;
   // evoamd_remap_latents: K^n in the new latent numbering and its digests, [index (H_new) | n_replaced (N)] and the sum;
   // grown on demand, NOT sized by the geometry: they survive the configure between the remap and
   // evoamd_adopt_remapped_states, which swaps them in and releases them.  remap_H = 0: nothing to adopt.
@@ -5811,8 +5816,9 @@ extern "C" int evoamd_download_predictive(evoamd_ctx *c, double *mean, double *v
 }
 
 // ---------------------------------------------------------------------------------------
-// Proposals for K^n: seeding (kernels_seed.hpp, kernels_seed_beam.hpp) and local search (kernels_sweep.hpp,
-// kernels_sweep_swap.hpp).  One table of the family's kernels, indexed like their LDS layouts; one admission for what all
+// Proposals for K^n: seeding (kernels_seed.hpp, kernels_seed_beam.hpp), local search (kernels_sweep.hpp,
+// kernels_sweep_swap.hpp) and the neighbourhood bound that sums what the flip sweep ranks (kernels_nbound.hpp).
+// One table of the family's kernels, indexed like their LDS layouts; one admission for what all
 // of them refuse; one launch plan (how many wavefronts of a workgroup fit the LDS limit, how large the grid is); one rule
 // for the home of the rows of G(n) on masked ES3C; one builder of the SeedArgs fields that come from the context.
 // Every refusal comes before the first write.
@@ -5824,7 +5830,9 @@ static const void *const kn_kernels[SEED_LDS_KINDS][2] = {  // [SeedLdsKind][ES3
     {(const void *)seed_states_beam_kernel<false>, (const void *)seed_states_beam_kernel<true>},
     {(const void *)sweep_neighbours_kernel<false>, (const void *)sweep_neighbours_kernel<true>},
     {(const void *)sweep_neighbours_kernel<false, true>, (const void *)sweep_neighbours_kernel<true, true>},
-    {(const void *)sweep_swap_kernel<false>, (const void *)sweep_swap_kernel<true>}};
+    {(const void *)sweep_swap_kernel<false>, (const void *)sweep_swap_kernel<true>},
+    {(const void *)nbound_kernel<false>, (const void *)nbound_kernel<true>},
+    {(const void *)nbound_kernel<false, true>, (const void *)nbound_kernel<true, true>}};
 
 static int kn_set_lds_limits() {
   for (const auto &pair : kn_kernels)
@@ -5901,6 +5909,7 @@ static bool kn_takes(SeedLdsKind k, const SeedArgs &) { return k == SEED_LDS_GRE
 static bool kn_takes(SeedLdsKind k, const SeedBeamArgs &) { return k == SEED_LDS_BEAM; }
 static bool kn_takes(SeedLdsKind k, const SweepArgs &) { return k == SEED_LDS_FLIP || k == SEED_LDS_FLIP_MASKED; }
 static bool kn_takes(SeedLdsKind k, const SweepSwapArgs &) { return k == SEED_LDS_SWAP; }
+static bool kn_takes(SeedLdsKind k, const NboundArgs &) { return k == SEED_LDS_NBOUND || k == SEED_LDS_NBOUND_MASKED; }
 template <class Args>
 static int kn_launch(evoamd_ctx *c, SeedLdsKind kind, const KnLaunch &l, const Args &args) {
   REQUIRE(kn_takes(kind, args), "kn_launch: these are not the arguments of this kind of kernel");
@@ -6233,6 +6242,83 @@ extern "C" int evoamd_sweep_states_nb(evoamd_ctx *c, int n_sweeps, int n_parents
                                       unsigned flags, double *trace_out, int *n_done_out, const evoamd_sweep_out *out) {
   return sweep_states_run(c, n_sweeps, n_parents, n_keep, Mprime, stop_when_quiet, flags, SWEEP_NB_FLAGS, trace_out, n_done_out,
                           out ? *out : evoamd_sweep_out{});
+}
+
+// ---- the neighbourhood bound (kernels_nbound.hpp has the law): the one-flip neighbours of the n_parents best states of K^n,
+// summed.  A reading of K^n at fixed Theta: the resident rows are evaluated as a sweep does at entry; K^n, the candidate
+// batch and the statistics rows are not written.  EVOAMD_NBOUND_INCOMPLETE is a permission, like EVOAMD_SWEEP_INCOMPLETE.
+extern "C" int evoamd_neighbour_bound(evoamd_ctx *c, int n_parents, unsigned flags, const evoamd_nbound_out *out) {
+  REQUIRE(c && c->configured, "configure first");
+  REQUIRE(!(flags & ~(unsigned)EVOAMD_NBOUND_INCOMPLETE), "evoamd_neighbour_bound: unknown flag");
+  TRY(kn_admit(c, "evoamd_neighbour_bound",
+               (flags & EVOAMD_NBOUND_INCOMPLETE) ? nullptr : "evoamd_neighbour_bound: incomplete data (masks present) is not "
+                                                              "supported without EVOAMD_NBOUND_INCOMPLETE",
+               /*need_kn=*/true));
+  if (n_parents < 1 || n_parents > c->S)
+    return fail(EVOAMD_E_INVALID, "evoamd_neighbour_bound: n_parents = %d must be in [1, S = %d]", n_parents, c->S);
+  const bool sssc = c->model == EVOAMD_MODEL_SSSC, masked = c->mask_infr != nullptr;
+  const int Hp = (int)cdiv(c->H, 64) * 64;
+  const SeedLdsKind kind = masked ? SEED_LDS_NBOUND_MASKED : SEED_LDS_NBOUND;
+  SeedLdsShape shape = {sssc, Hp, c->HW, 0, 0, 0, masked ? c->D : 0, 0, c->S};
+  const KnRows rows = kn_plan_rows(kind, shape, masked && sssc ? SWEEP_ROWS : 0);
+  shape.rows_lds = rows.lds;
+  KnLaunch l;
+  TRY(kn_plan_launch(c, seed_lds_bytes(kind, shape),
+                     masked ? "evoamd_neighbour_bound: the keys of one datapoint (8 or 24 H bytes), the parents and their ranks (8 S "
+                              "bytes), the staged column of W (8 D bytes) and the list of the reliable entries (4 D bytes) do not "
+                              "fit one wavefront's share of LDS"
+                            : "evoamd_neighbour_bound: the keys of one datapoint (8 or 16 H bytes) and the parents and their ranks "
+                              "(8 S bytes) do not fit one wavefront's share of LDS",
+                     rows.cu_mult, masked ? KN_STEP_DECREMENT : KN_STEP_HALVE, l));
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t N = (size_t)c->N;
+  TRY(ensure_B(c));
+  if (rows.doubles(l, Hp)) TRY(c->seed_rows.ensure(c, rows.doubles(l, Hp)));
+  TRY(c->nbound_d.ensure(c, 4 * N));
+  TRY(c->nbound_i.ensure(c, 4 * N));
+  if (sssc) TRY(c->seed_gpt.ensure(c, (size_t)c->H * c->H));
+  on_estep_route(c, /*fused=*/false);
+  TRY(estep_resident_pass(c));
+  NboundArgs a = {};
+  fill_seed_args(c, a.sd);
+  if (masked) {
+    a.sd.R = rows.R;
+    a.sd.rows = rows.R && !rows.lds ? c->seed_rows.get() : nullptr;
+  }
+  a.lpj = c->lpj;
+  a.F = c->nbound_d, a.M = a.F + N, a.F_plus = a.F + 2 * N, a.best_score = a.F + 3 * N;
+  a.n_states = c->nbound_i, a.n_capped = a.n_states + N, a.best_parent = a.n_states + 2 * N, a.best_flip = a.n_states + 3 * N;
+  a.L = c->L, a.S_perm = c->S_perm, a.P = n_parents;
+  {
+    SpanGuard g(c, KID_NBOUND);
+    if (sssc) TRY(kn_transpose_gp(c));
+    posterior_score_kernel<<<cdiv(c->N, SCORE_WAVES), 64 * SCORE_WAVES, 0, c->stream>>>(c->lpj, c->states, c->N, c->L, c->S, c->S_perm,
+                                                                                        c->HW, a.F, nullptr, nullptr, nullptr, nullptr);
+    TRY(kn_launch(c, kind, l, a));
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "neighbour bound");
+  }
+  std::vector<double> fp(N);
+  HIP_TRY(hipMemcpyAsync(fp.data(), a.F_plus, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  const evoamd_nbound_out o = out ? *out : evoamd_nbound_out{};
+  if (o.F) HIP_TRY(hipMemcpyAsync(o.F, a.F, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (o.M) HIP_TRY(hipMemcpyAsync(o.M, a.M, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (o.best_score) HIP_TRY(hipMemcpyAsync(o.best_score, a.best_score, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (o.n_states) HIP_TRY(hipMemcpyAsync(o.n_states, a.n_states, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (o.n_capped) HIP_TRY(hipMemcpyAsync(o.n_capped, a.n_capped, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (o.best_parent) HIP_TRY(hipMemcpyAsync(o.best_parent, a.best_parent, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (o.best_flip) HIP_TRY(hipMemcpyAsync(o.best_flip, a.best_flip, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (sssc)
+    TRY(check_err(c));  // synchronises the stream
+  else
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  if (o.sum) {  // over the rows with an estimate, in datapoint order
+    double sum = 0.0, count = 0.0;
+    for (size_t n = 0; n < N; n++)
+      if (fp[n] == fp[n]) sum += fp[n], count += 1.0;
+    o.sum[0] = sum, o.sum[1] = count;
+  }
+  return 0;
 }
 
 // posterior samples (kernels_posterior_sample.hpp): own buffers; of the EM state only B = Y W is (re)formed, like every lpj pass
@@ -6766,6 +6852,7 @@ extern "C" const char *evoamd_kernel_name(int kid) {
                                          "stats_k3_4",   "stats_k5_8",     "stats_k9plus", "allreduce",    "estep_fused",
                                          "patches",      "init_states",    "posterior_sample", "seed_states",
                                          "loglik_proposal", "loglik_lpj",  "loglik_fold",     "remap_latents",
-                                         "stats_kappa",  "sweep",       "sweep_swap",      "resize"};
+                                         "stats_kappa",  "sweep",       "sweep_swap",      "resize",
+                                         "neighbour_bound"};
   return (kid >= 0 && kid < KID_COUNT) ? names[kid] : "?";
 }

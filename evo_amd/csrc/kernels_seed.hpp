@@ -68,19 +68,19 @@ struct SeedArgs {
 
 // ONE WAVEFRONT'S SHARE OF LDS, described once for the host (which takes the total) and the kernels (which take their
 // pointers from the same walk).  One description per kernel of the family; nothing else carves LDS in kernels_seed.hpp,
-// kernels_seed_beam.hpp, kernels_sweep.hpp and kernels_sweep_swap.hpp.  8-byte regions first, then the ints; a masked or
-// swap kernel's extras start behind the complete kernel's share rounded to 16 bytes.
+// kernels_seed_beam.hpp, kernels_sweep.hpp, kernels_sweep_swap.hpp and kernels_nbound.hpp.  8-byte regions first, then the
+// ints; a masked, swap or neighbourhood-bound kernel's extras start behind the complete kernel's share rounded to 16 bytes.
 #define SWEEP_PATH 16                 // sweeps: active latents of a parent kept as a list (ES3C reads at most 9)
 #define SWEEP_MAX_P 64                // sweeps: parents per datapoint
 #define SWAP_LIST SEED_MAX_A_BSC      // swap sweep: the parent's active latents as a list, every a of a scored parent
 enum SeedLdsKind { SEED_LDS_GREEDY, SEED_LDS_GREEDY_MASKED, SEED_LDS_BEAM, SEED_LDS_FLIP, SEED_LDS_FLIP_MASKED, SEED_LDS_SWAP,
-                   SEED_LDS_KINDS };
+                   SEED_LDS_NBOUND, SEED_LDS_NBOUND_MASKED, SEED_LDS_KINDS };
 struct SeedLdsShape {
   bool sssc;
   int Hp, HW, Q;      // Q: the largest quota (sweeps: n_keep)
   int A, B;           // seeding: max_active; the beam
   int D, rows_lds;    // masked: entries per datapoint; the rows of G(n) whose home is LDS (0: a.rows holds them)
-  int S;              // swap sweep: states per datapoint
+  int S;              // swap sweep, neighbourhood bound: states per datapoint
 };
 // Two cursors walk the one description: SeedLdsOffsets yields byte offsets and the total (host, and the kernels for their
 // share's size), SeedLdsPointers the typed pointers from a wavefront's home (kernels).  A region the kernel kind does not
@@ -124,6 +124,7 @@ struct SeedLdsRegions {
   at<u64> selk = {};
   at<int> sel = {}, byrank = {}, path = {}, sorted = {};
   at<int> parents = {};                                   // sweeps: the parents' slots
+  at<int> rank = {};                                      // neighbourhood bound: slot -> parent rank
   at<double> gd = {}, col = {}, rows = {};                // incomplete data
   at<int> dl = {};
   at<u64> rk[2] = {};                                     // beam, swap: the running lists (key, parent | a, j)
@@ -138,7 +139,9 @@ struct SeedLdsRegions {
 __host__ __device__ constexpr size_t seed_lds_bytes(SeedLdsKind kind, const SeedLdsShape &s);
 template <class C>
 __host__ __device__ constexpr SeedLdsRegions<C> seed_lds_walk(SeedLdsKind kind, const SeedLdsShape &s, C c) {
-  const bool beam = kind == SEED_LDS_BEAM, sweep = kind == SEED_LDS_FLIP || kind == SEED_LDS_FLIP_MASKED || kind == SEED_LDS_SWAP;
+  const bool nbound = kind == SEED_LDS_NBOUND || kind == SEED_LDS_NBOUND_MASKED;
+  const bool flip_masked = kind == SEED_LDS_FLIP_MASKED || kind == SEED_LDS_NBOUND_MASKED;
+  const bool beam = kind == SEED_LDS_BEAM, sweep = kind == SEED_LDS_FLIP || flip_masked || kind == SEED_LDS_SWAP || nbound;
   const size_t Hp = (size_t)s.Hp, Q = (size_t)s.Q;
   SeedLdsRegions<C> l;
   l.keys = c.template take<u64>(Hp);  // (masked EBSC seeding: also tmp, a row on its way into e)
@@ -171,10 +174,10 @@ __host__ __device__ constexpr SeedLdsRegions<C> seed_lds_walk(SeedLdsKind kind, 
   // left where the walk arrived: the same place, but measured -- the masked ES3C flip sweep, which fills the register file,
   // runs 3.6 % slower with its addresses formed from where the walk arrived, and masked EBSC seeding 1 % slower with them
   // formed from the total, so seeding keeps the walk's position
-  if (kind == SEED_LDS_FLIP_MASKED || kind == SEED_LDS_SWAP) c.seek(seed_lds_bytes(SEED_LDS_FLIP, s));
-  if (kind == SEED_LDS_GREEDY_MASKED || kind == SEED_LDS_FLIP_MASKED) {
+  if (flip_masked || kind == SEED_LDS_SWAP) c.seek(seed_lds_bytes(SEED_LDS_FLIP, s));
+  if (kind == SEED_LDS_GREEDY_MASKED || flip_masked) {
     // EBSC sweep: the diagonal g_jj; the staged column of W; ES3C the rows of G(n) when LDS is their home; the reliable d
-    if (kind == SEED_LDS_FLIP_MASKED) l.gd = c.template take<double>(s.sssc ? 0 : Hp);
+    if (flip_masked) l.gd = c.template take<double>(s.sssc ? 0 : Hp);
     l.col = c.template take<double>((size_t)s.D);
     l.rows = c.template take<double>((size_t)s.rows_lds * Hp);
     l.dl = c.template take<int>((size_t)s.D);
@@ -186,6 +189,11 @@ __host__ __device__ constexpr SeedLdsRegions<C> seed_lds_walk(SeedLdsKind kind, 
     l.rp[1] = c.template take<int>(Q), l.rj[1] = c.template take<int>(Q);
     l.full = c.template take<int>(SWAP_LIST);
     l.held = c.template take<unsigned>((size_t)s.S);
+    c.align16();
+  }
+  if (nbound) {  // behind the flip / masked flip share: up to S parents (the 64 slots of the share stay unused) and the ranks
+    l.parents = c.template take<int>((size_t)s.S);
+    l.rank = c.template take<int>((size_t)s.S);
     c.align16();
   }
   l.total = c.used();
@@ -229,6 +237,15 @@ static_assert(seed_lds_bytes(SEED_LDS_SWAP, SeedLdsShape{false, 128, 2, 3, 0, 0,
 static_assert(seed_lds_bytes(SEED_LDS_SWAP, SeedLdsShape{true, 512, 8, 13, 0, 0, 0, 0, 64}) == 6960, "swap sweep");
 static_assert(seed_lds_bytes(SEED_LDS_SWAP, SeedLdsShape{false, 1152, 18, 8, 0, 0, 0, 0, 200}) == 20336, "swap sweep");
 static_assert(seed_lds_bytes(SEED_LDS_SWAP, SeedLdsShape{true, 1856, 29, 4, 0, 0, 0, 0, 6}) == 17232, "swap sweep");
+// The neighbourhood bound (kernels_nbound.hpp): the flip / masked flip share at Q = 0 plus 8 S bytes, worked out by hand
+static_assert(seed_lds_bytes(SEED_LDS_NBOUND, SeedLdsShape{false, 128, 2, 0, 0, 0, 0, 0, 30}) == 2624, "neighbourhood bound");
+static_assert(seed_lds_bytes(SEED_LDS_NBOUND, SeedLdsShape{true, 512, 8, 0, 0, 0, 0, 0, 200}) == 7424, "neighbourhood bound");
+static_assert(seed_lds_bytes(SEED_LDS_NBOUND, SeedLdsShape{false, 128, 2, 3, 0, 0, 0, 0, 30}) ==
+                  seed_lds_bytes(SEED_LDS_FLIP, SeedLdsShape{false, 128, 2, 3, 0, 0, 0, 0, 0}) + 240, "neighbourhood bound");
+static_assert(seed_lds_bytes(SEED_LDS_NBOUND_MASKED, SeedLdsShape{true, 128, 2, 0, 0, 0, 24, 10, 12}) == 13328, "masked neighbourhood bound");
+static_assert(seed_lds_bytes(SEED_LDS_NBOUND_MASKED, SeedLdsShape{false, 512, 8, 0, 0, 0, 300, 0, 256}) == 18320, "masked neighbourhood bound");
+static_assert(seed_lds_bytes(SEED_LDS_NBOUND_MASKED, SeedLdsShape{true, 512, 8, 13, 0, 0, 300, 10, 64}) ==
+                  seed_lds_bytes(SEED_LDS_FLIP_MASKED, SeedLdsShape{true, 512, 8, 13, 0, 0, 300, 10, 0}) + 512, "masked neighbourhood bound");
 
 __device__ __forceinline__ void seed_wave_sync() {
   __threadfence_block();

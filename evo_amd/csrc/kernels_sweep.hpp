@@ -203,6 +203,198 @@ __device__ __forceinline__ void sweep_list_active(const u64 *par, int H, int NC,
   }
 }
 
+// One parent scored (file header: neighbours, the tests (a), (b), (c), scores): the words of the state in `slot` go to
+// L.base, its first SWEEP_PATH active latents to L.path, and L.keys[j] becomes the key of the neighbour that flips j, 0 for an
+// absent one.  Returns the parent's size m; lost: this lane saw a neighbour lost to the cap; base: the parent's own score.
+// gd, col, rows, dl, nd: incomplete data, as the kernels set them up.  OWN (kernels_nbound.hpp, rule (d)): rank[s] is the
+// parent rank of slot s or INT_MAX, r this parent's rank; a neighbour that an earlier parent owns is absent, not lost.
+template <bool SSSC, bool MASKED, bool OWN>
+__device__ __forceinline__ int sweep_score_parent(const SeedArgs &sd, const SeedLds &L, const SeedScalars &sc, const u64 *kn, int slot,
+                                                  int lane, const double *__restrict__ Bn, double yy, double *gd, double *col,
+                                                  double *rows, const int *dl, int nd, int r, const int *rank, bool &lost_out,
+                                                  double &base_out) {
+  const int S = sd.S, H = sd.H, HW = sd.HW, Hp = sd.Hp;
+  const int NC = Hp >> 6;
+  constexpr int CAP = SSSC ? SEED_MAX_A_SSSC : SEED_MAX_A_BSC;
+  const double pre1 = sc.pre1, pilb = sc.pilb, s2inv = sc.s2inv;
+  u64 *keys = L.keys, *par = L.base;
+  double *cc = L.cc;
+  int *path = L.path;
+  const u64 *pw = kn + (size_t)slot * HW;
+  // ---- the parent's words, its size, the keys cleared
+  const int m = sweep_load_parent(pw, HW, lane, par);
+  for (int c = 0; c < NC; c++) keys[64 * c + lane] = 0ull;
+  seed_wave_sync();
+  // ---- (b) flips that K^n holds: key 1 marks them (no score has that key).  OWN, (d): an earlier parent two flips away
+  // sets bit 1 of both differing latents (LDS atomics: a latent may be held and owned; a held one keeps bit 0, which wins)
+  for (int s0 = 0; s0 < S; s0 += 64) {
+    const int s = s0 + lane;
+    if (s < S) {
+      const u64 *sw = kn + (size_t)s * HW;
+      int cnt = 0, at = 0, last = 0;
+      for (int w = 0; w < HW; w++) {
+        const u64 x = sw[w] ^ par[w];
+        if constexpr (OWN) {
+          if (x) {
+            if (cnt == 0) at = 64 * w + __clzll((long long)x);
+            last = 64 * w + 63 - __builtin_ctzll(x);
+          }
+        } else {
+          if (x) at = 64 * w + __clzll((long long)x);
+        }
+        cnt += __popcll(x);
+      }
+      if constexpr (OWN) {
+        if (cnt == 1 && at < H) atomicOr((unsigned long long *)&keys[at], 1ull);
+        if (cnt == 2 && last < H && rank[s] < r) {
+          atomicOr((unsigned long long *)&keys[at], 2ull);
+          atomicOr((unsigned long long *)&keys[last], 2ull);
+        }
+      } else {
+        if (cnt == 1 && at < H) keys[at] = 1ull;
+      }
+    }
+  }
+  // the mark of latent j before its key is written: held (b), owned (d; never without OWN)
+  auto is_held = [&](u64 mk) { return OWN ? (mk & 1ull) != 0 : mk == 1ull; };
+  auto is_owned = [&](u64 mk) { return OWN && mk == 2ull; };
+  // ---- the parent's active latents in ascending order (the first SWEEP_PATH of them)
+  sweep_list_active(par, H, NC, lane, path, SWEEP_PATH);
+  seed_wave_sync();
+  const bool add_ok = m + 1 <= CAP, rem_ok = m - 1 >= 1 && m - 1 <= CAP;
+  bool lost = false;   // a neighbour neither all-zero nor held, above the cap
+  double base;
+  if (SSSC) {
+    if constexpr (MASKED) {
+      // row i of G(n) for the parent's i-th active latent, m <= 9 (above that nothing of this parent is scored): the
+      // column W_.a staged in LDS, then the sweep over the reliable d
+      const int nr = m <= CAP + 1 ? m : 0;
+      for (int i = 0; i < nr; i++) {
+        const int ja = guard_index(__builtin_amdgcn_readfirstlane(path[i]), H, sd.err);
+        for (int t = lane; t < nd; t += 64) col[t] = sd.W[(size_t)guard_index(dl[t], sd.D, sd.err) * H + ja];
+        seed_wave_sync();
+        seed_gram_sweep<false>(sd, lane, dl, col, nd, rows + (size_t)i * Hp);
+        seed_wave_sync();  // the column is staged again; the rows are read by other lanes
+      }
+    }
+    // removals: lane i takes the i-th active latent out, base: every lane the same system
+    if (m >= 2 && m <= CAP + 1) {
+      if (lane < m) {
+        const int ja = guard_index(path[lane], H, sd.err);
+        u64 key = 0ull;
+        const u64 mk = keys[ja];
+        if (!is_held(mk) && !is_owned(mk)) key = sweep_key(sweep_lpj_scratch_k<MASKED>(m - 1, sd, path, lane, Bn, yy, s2inv, rows));
+        keys[ja] = key;
+      }
+    } else if (m == 1) {
+      if (lane == 0) keys[guard_index(path[0], H, sd.err)] = 0ull;  // (a)
+    } else if (m > CAP + 1) {  // every removal is above the cap
+      for (int c = 0; c < NC; c++) {
+        const int j = 64 * c + lane;
+        const bool on = j < H && ((par[j < H ? j >> 6 : 0] >> (63 - (j & 63))) & 1ull);
+        if (on) {
+          lost = lost || !is_held(keys[j]);
+          keys[j] = 0ull;
+        }
+      }
+    }
+    base = m == 0 ? -0.5 * yy * s2inv
+                  : (m <= CAP ? sweep_lpj_scratch_k<MASKED>(m, sd, path, -1, Bn, yy, s2inv, rows) : __builtin_nan(""));
+    // additions, bordered on the parent's blocks
+    int act[SEED_MAX_A_SSSC];
+    double pbA = 0.0;
+    if (add_ok) pbA = seed_form_blocks(sd, L, m + 1, lane, Bn, s2inv, act, MASKED ? rows : nullptr);
+    for (int c = 0; c < NC; c++) {
+      const int j = 64 * c + lane;
+      if (j >= H) continue;
+      if ((par[j >> 6] >> (63 - (j & 63))) & 1ull) continue;  // a removal: done above
+      const u64 mk = keys[j];
+      const bool held = is_held(mk);
+      lost = lost || (!held && !add_ok);
+      u64 key = 0ull;
+      if (!held && add_ok && !is_owned(mk))
+        key = sweep_key(seed_score_sssc_step<MASKED>(m + 1, sd, L.sh, act, pbA, j, Bn, yy, s2inv, MASKED ? rows : nullptr));
+      keys[j] = key;
+    }
+  } else {
+    if constexpr (MASKED) {
+      // the combined column r_d = sum_{i in p} W_di (ascending i) for the reliable d, then ONE sweep:
+      // c_j = B_nj - sum_d r_d W_dj (ascending d)
+      for (int t = lane; t < nd; t += 64) {
+        const double *Wd = sd.W + (size_t)guard_index(dl[t], sd.D, sd.err) * H;
+        double s = 0.0;
+        for (int w = 0; w < HW; w++) {
+          u64 v = par[w];
+          while (v) s += Wd[guard_index(64 * w + pop_msb(v), H, sd.err)];
+        }
+        col[t] = s;
+      }
+      seed_wave_sync();
+      seed_gram_sweep<false>(sd, lane, dl, col, nd, cc);
+      for (int c = 0; c < NC; c++) {
+        const int j = 64 * c + lane;
+        cc[j] = (j < H ? Bn[j] : 0.0) - cc[j];
+      }
+    } else
+    // c_j = B_nj - sum_{i in p} G_ij, the rows in ascending i, four chunks of latents at a time
+    for (int c0 = 0; c0 < NC; c0 += 4) {
+      double acc[4];
+      int jj[4];
+      bool in[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int j = 64 * (c0 + u) + lane;
+        in[u] = c0 + u < NC && j < H;
+        jj[u] = in[u] ? j : 0;
+        acc[u] = in[u] ? Bn[jj[u]] : 0.0;
+      }
+      for (int w = 0; w < HW; w++) {
+        u64 v = seed_uniform(par[w]);
+        while (v) {
+          const int i = guard_index(64 * w + pop_msb(v), H, sd.err);
+          const double *Gi = sd.G + (size_t)i * H;
+#pragma unroll
+          for (int u = 0; u < 4; u++) acc[u] -= in[u] ? Gi[jj[u]] : 0.0;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++)
+        if (c0 + u < NC) cc[64 * (c0 + u) + lane] = acc[u];
+    }
+    seed_wave_sync();
+    {
+      double s = yy;  // every lane the same sum, ascending a
+      for (int w = 0; w < HW; w++) {
+        u64 v = seed_uniform(par[w]);
+        while (v) {
+          const int i = guard_index(64 * w + pop_msb(v), H, sd.err);
+          s -= Bn[i] + cc[i];
+        }
+      }
+      base = pre1 * s + (double)m * pilb;
+    }
+    for (int c = 0; c < NC; c++) {
+      const int j = 64 * c + lane;
+      if (j >= H) continue;
+      const bool on = (par[j >> 6] >> (63 - (j & 63))) & 1ull;
+      const u64 mk = keys[j];
+      const bool held = is_held(mk);
+      const bool zero = on && m == 1;  // (a)
+      const bool ok = on ? rem_ok : add_ok;
+      lost = lost || (!zero && !held && !ok);
+      u64 key = 0ull;
+      if (!zero && !held && ok && !is_owned(mk)) {
+        const double gjj = MASKED ? gd[j] : sd.Gd[j], cj = cc[j];
+        key = sweep_key(on ? base - pilb + pre1 * (gjj + 2.0 * cj) : base + pilb + pre1 * (gjj - 2.0 * cj));
+      }
+      keys[j] = key;
+    }
+  }
+  lost_out = lost;
+  base_out = base;
+  return m;
+}
+
 // MASKED: the law on incomplete data (file header); the complete instantiations compile to what they were without it.
 template <bool SSSC, bool MASKED = false>
 __global__ __launch_bounds__(256) void sweep_neighbours_kernel(SweepArgs a) {
@@ -212,7 +404,6 @@ __global__ __launch_bounds__(256) void sweep_neighbours_kernel(SweepArgs a) {
   const int W = (int)(blockDim.x >> 6);
   const int S = sd.S, H = sd.H, HW = sd.HW, Hp = sd.Hp, P = a.P, q = a.q, Cmax = a.Cmax;
   const int NC = Hp >> 6;
-  constexpr int CAP = SSSC ? SEED_MAX_A_SSSC : SEED_MAX_A_BSC;
   // one wavefront's share of LDS (seed_lds_walk)
   const SeedLdsView V = MASKED ? seed_lds_view(sweep_lds, wave, SEED_LDS_FLIP_MASKED, SeedLdsShape{SSSC, Hp, HW, q, 0, 0, sd.D, sd.rows ? 0 : sd.R, 0})
                                : seed_lds_view(sweep_lds, wave, SEED_LDS_FLIP, SeedLdsShape{SSSC, Hp, HW, q, 0, 0, 0, 0, 0});
@@ -227,9 +418,7 @@ __global__ __launch_bounds__(256) void sweep_neighbours_kernel(SweepArgs a) {
     gd = SSSC ? rows + (size_t)(sd.R - 1) * Hp : V.gd;
   }
   u64 *keys = L.keys, *par = L.base;
-  double *cc = L.cc;
-  int *path = L.path;
-  const auto [pre1, pilb, s2inv] = seed_scalars<SSSC>(sd.dpar);
+  const SeedScalars sc = seed_scalars<SSSC>(sd.dpar);
   for (i64 n = (i64)blockIdx.x * W + wave; n < sd.N; n += (i64)gridDim.x * W) {
     const double *Bn = sd.Bm + (size_t)n * H;
     const double yy = sd.yy[n];
@@ -241,177 +430,15 @@ __global__ __launch_bounds__(256) void sweep_neighbours_kernel(SweepArgs a) {
       seed_wave_sync();
       seed_gram_sweep<true>(sd, lane, dl, col, nd, gd);
     }
-    // ---- parents: the rounds of sweep_pick_parents, kept in line here: through the call the masked ES3C instantiation,
-    // which fills the register file, spills 12 bytes per lane
-    {
-      u64 pk = 0ull;
-      int ps = -1;
-      for (int r = 0; r < P; r++) {
-        u64 bk = 0ull;
-        int bs = 0x7fffffff;
-        for (int s = lane; s < S; s += 64) {
-          const u64 k = seed_key(row[s]);
-          const bool elig = r == 0 || k < pk || (k == pk && s > ps);
-          if (elig && k > bk) bk = k, bs = s;  // (ascending s: an equal key later in the lane's list never wins)
-        }
-        const u64 gk = sweep_wave_max_u64(bk);
-        const int gs = (int)wave_min_u32(bk == gk ? (unsigned)bs : 0x7fffffffu);
-        if (lane == 0) parents[r] = gs;
-        pk = gk, ps = gs;
-      }
-    }
+    // ---- parents
+    sweep_pick_parents(row, S, P, lane, parents);
     seed_wave_sync();
     int row0 = 0, capped_parents = 0;
     for (int r = 0; r < P; r++) {
       const int slot = guard_index(__builtin_amdgcn_readfirstlane(parents[r]), S, sd.err);
-      const u64 *pw = kn + (size_t)slot * HW;
-      // ---- the parent's words, its size, the keys cleared
-      const int m = sweep_load_parent(pw, HW, lane, par);
-      for (int c = 0; c < NC; c++) keys[64 * c + lane] = 0ull;
-      seed_wave_sync();
-      // ---- (b) flips that K^n holds: key 1 marks them (no score has that key)
-      for (int s0 = 0; s0 < S; s0 += 64) {
-        const int s = s0 + lane;
-        if (s < S) {
-          const u64 *sw = kn + (size_t)s * HW;
-          int cnt = 0, at = 0;
-          for (int w = 0; w < HW; w++) {
-            const u64 x = sw[w] ^ par[w];
-            if (x) at = 64 * w + __clzll((long long)x);
-            cnt += __popcll(x);
-          }
-          if (cnt == 1 && at < H) keys[at] = 1ull;
-        }
-      }
-      // ---- the parent's active latents in ascending order (the first SWEEP_PATH of them)
-      sweep_list_active(par, H, NC, lane, path, SWEEP_PATH);
-      seed_wave_sync();
-      const bool add_ok = m + 1 <= CAP, rem_ok = m - 1 >= 1 && m - 1 <= CAP;
-      bool lost = false;   // a neighbour neither all-zero nor held, above the cap
+      bool lost;
       double base;
-      if (SSSC) {
-        if constexpr (MASKED) {
-          // row i of G(n) for the parent's i-th active latent, m <= 9 (above that nothing of this parent is scored): the
-          // column W_.a staged in LDS, then the sweep over the reliable d
-          const int nr = m <= CAP + 1 ? m : 0;
-          for (int i = 0; i < nr; i++) {
-            const int ja = guard_index(__builtin_amdgcn_readfirstlane(path[i]), H, sd.err);
-            for (int t = lane; t < nd; t += 64) col[t] = sd.W[(size_t)guard_index(dl[t], sd.D, sd.err) * H + ja];
-            seed_wave_sync();
-            seed_gram_sweep<false>(sd, lane, dl, col, nd, rows + (size_t)i * Hp);
-            seed_wave_sync();  // the column is staged again; the rows are read by other lanes
-          }
-        }
-        // removals: lane i takes the i-th active latent out, base: every lane the same system
-        if (m >= 2 && m <= CAP + 1) {
-          if (lane < m) {
-            const int ja = guard_index(path[lane], H, sd.err);
-            u64 key = 0ull;
-            if (keys[ja] != 1ull) key = sweep_key(sweep_lpj_scratch_k<MASKED>(m - 1, sd, path, lane, Bn, yy, s2inv, rows));
-            keys[ja] = key;
-          }
-        } else if (m == 1) {
-          if (lane == 0) keys[guard_index(path[0], H, sd.err)] = 0ull;  // (a)
-        } else if (m > CAP + 1) {  // every removal is above the cap
-          for (int c = 0; c < NC; c++) {
-            const int j = 64 * c + lane;
-            const bool on = j < H && ((par[j < H ? j >> 6 : 0] >> (63 - (j & 63))) & 1ull);
-            if (on) {
-              lost = lost || keys[j] != 1ull;
-              keys[j] = 0ull;
-            }
-          }
-        }
-        base = m == 0 ? -0.5 * yy * s2inv
-                      : (m <= CAP ? sweep_lpj_scratch_k<MASKED>(m, sd, path, -1, Bn, yy, s2inv, rows) : __builtin_nan(""));
-        // additions, bordered on the parent's blocks
-        int act[SEED_MAX_A_SSSC];
-        double pbA = 0.0;
-        if (add_ok) pbA = seed_form_blocks(sd, L, m + 1, lane, Bn, s2inv, act, MASKED ? rows : nullptr);
-        for (int c = 0; c < NC; c++) {
-          const int j = 64 * c + lane;
-          if (j >= H) continue;
-          if ((par[j >> 6] >> (63 - (j & 63))) & 1ull) continue;  // a removal: done above
-          const bool held = keys[j] == 1ull;
-          lost = lost || (!held && !add_ok);
-          u64 key = 0ull;
-          if (!held && add_ok)
-            key = sweep_key(seed_score_sssc_step<MASKED>(m + 1, sd, L.sh, act, pbA, j, Bn, yy, s2inv, MASKED ? rows : nullptr));
-          keys[j] = key;
-        }
-      } else {
-        if constexpr (MASKED) {
-          // the combined column r_d = sum_{i in p} W_di (ascending i) for the reliable d, then ONE sweep:
-          // c_j = B_nj - sum_d r_d W_dj (ascending d)
-          for (int t = lane; t < nd; t += 64) {
-            const double *Wd = sd.W + (size_t)guard_index(dl[t], sd.D, sd.err) * H;
-            double s = 0.0;
-            for (int w = 0; w < HW; w++) {
-              u64 v = par[w];
-              while (v) s += Wd[guard_index(64 * w + pop_msb(v), H, sd.err)];
-            }
-            col[t] = s;
-          }
-          seed_wave_sync();
-          seed_gram_sweep<false>(sd, lane, dl, col, nd, cc);
-          for (int c = 0; c < NC; c++) {
-            const int j = 64 * c + lane;
-            cc[j] = (j < H ? Bn[j] : 0.0) - cc[j];
-          }
-        } else
-        // c_j = B_nj - sum_{i in p} G_ij, the rows in ascending i, four chunks of latents at a time
-        for (int c0 = 0; c0 < NC; c0 += 4) {
-          double acc[4];
-          int jj[4];
-          bool in[4];
-#pragma unroll
-          for (int u = 0; u < 4; u++) {
-            const int j = 64 * (c0 + u) + lane;
-            in[u] = c0 + u < NC && j < H;
-            jj[u] = in[u] ? j : 0;
-            acc[u] = in[u] ? Bn[jj[u]] : 0.0;
-          }
-          for (int w = 0; w < HW; w++) {
-            u64 v = seed_uniform(par[w]);
-            while (v) {
-              const int i = guard_index(64 * w + pop_msb(v), H, sd.err);
-              const double *Gi = sd.G + (size_t)i * H;
-#pragma unroll
-              for (int u = 0; u < 4; u++) acc[u] -= in[u] ? Gi[jj[u]] : 0.0;
-            }
-          }
-#pragma unroll
-          for (int u = 0; u < 4; u++)
-            if (c0 + u < NC) cc[64 * (c0 + u) + lane] = acc[u];
-        }
-        seed_wave_sync();
-        {
-          double s = yy;  // every lane the same sum, ascending a
-          for (int w = 0; w < HW; w++) {
-            u64 v = seed_uniform(par[w]);
-            while (v) {
-              const int i = guard_index(64 * w + pop_msb(v), H, sd.err);
-              s -= Bn[i] + cc[i];
-            }
-          }
-          base = pre1 * s + (double)m * pilb;
-        }
-        for (int c = 0; c < NC; c++) {
-          const int j = 64 * c + lane;
-          if (j >= H) continue;
-          const bool on = (par[j >> 6] >> (63 - (j & 63))) & 1ull;
-          const bool held = keys[j] == 1ull;
-          const bool zero = on && m == 1;  // (a)
-          const bool ok = on ? rem_ok : add_ok;
-          lost = lost || (!zero && !held && !ok);
-          u64 key = 0ull;
-          if (!zero && !held && ok) {
-            const double gjj = MASKED ? gd[j] : sd.Gd[j], cj = cc[j];
-            key = sweep_key(on ? base - pilb + pre1 * (gjj + 2.0 * cj) : base + pilb + pre1 * (gjj - 2.0 * cj));
-          }
-          keys[j] = key;
-        }
-      }
+      const int m = sweep_score_parent<SSSC, MASKED, false>(sd, L, sc, kn, slot, lane, Bn, yy, gd, col, rows, dl, nd, 0, nullptr, lost, base);
       if (__any(lost)) capped_parents++;
       seed_wave_sync();
       // ---- the q best scored neighbours

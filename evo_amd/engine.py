@@ -439,6 +439,36 @@ class Engine:
             ctypes.byref(n_done), ctypes.byref(out)))
         return trace[:n_done.value], n_done.value, res
 
+    def neighbour_bound(self, n_parents, incomplete=False):
+        """The neighbourhood bound under the Theta, K^n and data on the device (evoamd_neighbour_bound;
+        csrc/kernels_nbound.hpp has the law, evo_amd.variational.neighbour_bound_host is the NumPy mirror): the resident
+        rows are evaluated, every one-flip neighbour of the ``n_parents`` best states of each datapoint that K^n does not
+        hold is scored as a flip sweep scores it, each state once, and the scores are summed.  Returns a dict of (N,)
+        arrays: "F" (the bound of K^n without ljc), "M" (log of the neighbours' summed mass, -inf without one), "F_plus" =
+        logaddexp(F, M), "gap" = F_plus - F >= 0, "mass_outside" = exp(M - F_plus), "n_states" and "n_capped" (int32),
+        "best_score", "best_parent" and "best_flip" (int32; -inf / -1 / -1 without a scored neighbour), and the scalars
+        "sum" (of F_plus over the datapoints with an estimate) and "count" (their number); a datapoint with "bad weights"
+        has NaN in the real-valued arrays.  Deterministic; K^n, the candidate batch and the statistics rows are not
+        written.  EvoAmdError naming the rule, with the context as it was, without Theta, data or K^n, for incomplete data
+        without ``incomplete`` (EVOAMD_NBOUND_INCOMPLETE, a permission as for sweep_propose), the background unit, the
+        float32 mode, bsc_direct and n_parents outside [1, S]."""
+        N = self.N
+        res = {name: np.empty(N, dtype=np.float64) for name in ("F", "M", "best_score")}
+        res.update({name: np.empty(N, dtype=np.int32) for name in ("n_states", "n_capped", "best_parent", "best_flip")})
+        total = np.zeros(2, dtype=np.float64)
+        out = _lib.NboundOut()
+        for name, a in res.items():
+            setattr(out, name, dptr(a) if a.dtype == np.float64 else i32ptr(a))
+        out.sum = dptr(total)
+        check(self.lib.evoamd_neighbour_bound(self._h, int(n_parents), _lib.NBOUND_INCOMPLETE if incomplete else 0,
+                                              ctypes.byref(out)))
+        with np.errstate(invalid="ignore"):
+            res["F_plus"] = np.logaddexp(res["F"], res["M"])
+            res["gap"] = res["F_plus"] - res["F"]
+            res["mass_outside"] = np.exp(res["M"] - res["F_plus"])
+        res["sum"], res["count"] = float(total[0]), int(total[1])
+        return res
+
     SCORES = ("F", "entropy", "best", "k_best", "k_mean")
 
     def posterior_scores(self, what=SCORES):

@@ -1295,6 +1295,56 @@ class Model:
             return L, info
         return L
 
+    def neighbourhood_bound(self, model_params, my_suff_stat, my_data, n_parents=None, per_datapoint=False,
+                            incomplete=False):
+        """A deterministic lower bound on the log-likelihood above the free energy: the exact mass of the one-flip
+        neighbours of K^n (Engine.neighbour_bound; csrc/kernels_nbound.hpp has the law,
+        evo_amd.variational.neighbour_bound_host is the NumPy mirror).  For every datapoint of this rank the ``n_parents``
+        best states of K^n (None: all S) are the parents; every state one flip away from a parent that K^n does not hold
+        is scored as a flip sweep scores it -- each state once, whichever parents reach it -- and the scores are summed,
+        not ranked: F+_n = log(sum_{s in K^n} e^{lpj_ns} + sum_{s in Nb_n} e^{lpj_n(s)}), F_n <= F+_n <= log p(y_n) - ljc.
+        No draws, so no variance: where estimate_log_likelihood rests on a single draw (``ess`` near 1), this says how much
+        of the mass K^n misses lies one flip away.  It sums one-flip neighbours only; ES3C neighbours above 8 active
+        latents (EBSC: 64) are left out and their parents counted in "n_capped".  Returns L+ = ljc + allreduce(sum_n
+        F+_n) / count, the convention of estimate_log_likelihood; with ``per_datapoint``, (L+, info) with the (N_loc,)
+        arrays "F" (the bound: posterior_scores()["F"]), "F_plus", "gap" = F_plus - F >= 0, "mass_outside" (the share of
+        the sum from outside K^n), "n_states" (the neighbours summed), "n_capped", "best_score", "best_parent" (rank) and
+        "best_flip" (latent) of the best neighbour (-inf / -1 / -1 without one) and the counter "n_bad_weights": those
+        datapoints have NaN rows and are left out of the sum and the count.  ``incomplete=True`` admits my_data["x_infr"]
+        with False entries: every neighbour is scored on the datapoint's reliable entries alone, as in
+        sweep_resident_states.  ValueError for the background unit, for incomplete data without ``incomplete=True`` and
+        for n_parents outside [1, S]; NotImplementedError in the float32 mode.  Works with sync_host=False, writes nothing
+        into the three dicts, does no communication besides the final all-reduce and leaves K^n, lpj, Theta,
+        y_reconstructed and the statistics rows on the device as they are (the call evaluates the resident rows itself,
+        as a sweep does, so the host's lpj is not uploaded)."""
+        S = self.S
+        P = int(S if n_parents is None else n_parents)
+        if my_suff_stat["permanent"]["background"]:
+            raise ValueError("neighbourhood_bound: the background unit is not supported")
+        if self.dtype == np.float32:
+            raise NotImplementedError("neighbourhood_bound is not available in the float32 mode")
+        if not 1 <= P <= S:
+            raise ValueError("neighbourhood_bound: n_parents = %d must be in [1, S = %d]" % (P, S))
+        if not incomplete and not self._complete(my_data):
+            raise ValueError("neighbourhood_bound: incomplete data (x_infr with False entries) is not supported by default: "
+                             "pass incomplete=True")
+        yr = my_data.get("y_reconstructed")
+        if isinstance(yr, ResidentReconstruction) and yr.resident and not yr.materialised:
+            yr.rows()  # setting the parameters below drops the device copy of an unread reconstruction: fetch it first
+        eng = self._prepare(my_suff_stat, my_data)
+        theta = dict(model_params)  # (the precompute stores its derived keys and zeroes the reset counters: on copies)
+        self.E_step_precompute(theta, dict(my_suff_stat), my_data)
+        if model_params is not self._dev_theta:
+            self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
+        info = eng.neighbour_bound(P, incomplete=bool(incomplete))
+        total, n_all = _reduce_array(self.comm, np.array([info.pop("sum"), float(info.pop("count"))]))  # (the one all-reduce)
+        L = theta["ljc"] + total / n_all if n_all else float("nan")
+        if not per_datapoint:
+            return L
+        info.pop("M")
+        info["n_bad_weights"] = int(np.isnan(info["F"]).sum())
+        return L, info
+
     def reconstruct(self, my_data, my_suff_stat, model_params):
         """(Re-)estimate the entries with my_data["x"] False from the posterior predictive distribution under
         ``model_params`` and the caller's K^n / lpj; adds my_data["y_reconstructed"] (_models.py:614-665).

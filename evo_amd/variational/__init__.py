@@ -5,3 +5,4 @@ from .utils import (init_states, init_states_counter, posterior_scores_host, see
 from .utils import check_remap_index, latent_usage_host, prune_index, remap_states_host  # noqa: F401
 from .utils import check_resize, resize_states_host  # noqa: F401
 from .eas_counter import evolve_randflip_counter, evolve_states_counter  # noqa: F401
+from .utils import neighbour_bound_host  # noqa: F401

@@ -458,37 +458,11 @@ def sweep_states_host(model, theta, Y, ss, lpj, S_perm, n_parents, n_keep, x_inf
     seed_states_host -- G(n) = W_o^T W_o, B_n = y_o^T W_o, yy_n = |y_o|^2; entries of Y under False are never read as
     numbers (NaN included) and a datapoint without a reliable entry is scored by the prior alone.  ``lpj`` is then the
     masked lpj of ``ss``.  None: complete data."""
-    sssc = model not in ("bsc", "BSC", "ebsc")
-    assert S_perm in (0, 1)
-    W = np.asarray(theta["W"], dtype=np.float64)
-    Y = np.asarray(Y, dtype=np.float64)
-    masked = x_infr is not None
-    if masked:
-        x_infr = np.asarray(x_infr, dtype=bool)
-        assert x_infr.shape == Y.shape
-        Y = np.where(x_infr, Y, 0.0)
-    ss = np.asarray(ss, dtype=bool)
-    lpj = np.asarray(lpj, dtype=np.float64)
-    (D, H), (N, S) = W.shape, ss.shape[:2]
-    assert Y.shape == (N, D) and ss.shape == (N, S, H) and lpj.shape == (N, S_perm + S)
+    fs = _FlipScores(model, theta, Y, ss, lpj, S_perm, x_infr)
+    N, S, H = fs.N, fs.S, fs.H
     P, q = int(n_parents), int(n_keep)
     if not (1 <= P <= min(S, 64)) or q < 1:
         raise ValueError("sweep_states: n_parents = %d must be in [1, min(S = %d, 64)] and n_keep = %d positive" % (P, S, q))
-    cap = SEED_MAX_ACTIVE["sssc" if sssc else "bsc"]
-    G, B, yy = W.T @ W, Y @ W, (Y * Y).sum(axis=1)
-    if sssc:
-        mus, Psi = np.asarray(theta["mus"], dtype=np.float64), np.asarray(theta["Psi"], dtype=np.float64)
-        pies = np.asarray(theta["pies"], dtype=np.float64)
-        pil_bar, s2inv = np.log(pies / (1.0 - pies)), 1.0 / float(theta["sigma2"])
-
-        def state_lpj(n, act):
-            if len(act) == 0:
-                return -0.5 * yy[n] * s2inv
-            return float(_seed_scores_sssc(G, Psi, mus, pil_bar, s2inv, B[n], yy[n], list(act[:-1]), np.array(act[-1:]))[0])
-    else:
-        pi, sigma = float(theta["pi"]), float(theta["sigma"])
-        pre1, pil_bar = -1.0 / 2.0 / sigma / sigma, np.log(pi / (1.0 - pi))
-        Gd = np.diag(G).copy()
     cand = np.zeros((N, P * q, H), dtype=bool)
     counts = np.zeros(N, dtype=np.int32)
     scores = np.full((N, P * q), np.nan)
@@ -497,39 +471,10 @@ def sweep_states_host(model, theta, Y, ss, lpj, S_perm, n_parents, n_keep, x_inf
     n_capped = np.zeros(N, dtype=np.int32)
     margin = np.full(N, np.inf)
     for n in range(N):
-        if masked:  # the datapoint's own Gram matrix, from the reliable rows of W (state_lpj reads G where it is called)
-            Wo = W[x_infr[n]]
-            G = Wo.T @ Wo
-            Gd = np.diag(G).copy()
-        row = np.where(np.isfinite(lpj[n, S_perm:]), lpj[n, S_perm:], -np.inf) + 0.0
-        parents = np.lexsort((np.arange(S), -row))[:P]
-        for r, slot in enumerate(parents):
-            p = ss[n, slot]
-            act = np.flatnonzero(p)
-            m = len(act)
-            diff = ss[n] ^ p
-            one = diff.sum(axis=1) == 1
-            held = np.zeros(H, dtype=bool)
-            held[np.argmax(diff[one], axis=1)] = True
-            size = np.where(p, m - 1, m + 1)
-            live = (size > 0) & ~held
-            lost = live & (size > cap)
-            live &= ~lost
-            n_capped[n] += bool(lost.any())
-            sc = np.full(H, -np.inf)
-            if sssc:
-                base = state_lpj(n, act) if m <= cap else np.nan
-                add = np.flatnonzero(live & ~p)
-                if len(add):
-                    sc[add] = _seed_scores_sssc(G, Psi, mus, pil_bar, s2inv, B[n], yy[n], list(act), add)
-                for j in np.flatnonzero(live & p):
-                    sc[j] = state_lpj(n, act[act != j])
-            else:
-                c = B[n] - G[act].sum(axis=0)
-                base = pre1 * (yy[n] - (B[n, act] + c[act]).sum()) + m * pil_bar
-                with np.errstate(invalid="ignore", over="ignore"):
-                    both = np.where(p, base - pil_bar + pre1 * (Gd + 2.0 * c), base + pil_bar + pre1 * (Gd - 2.0 * c))
-                sc[live] = both[live]
+        for r, slot in enumerate(fs.parents(n)[:P]):
+            p = fs.ss[n, slot]
+            sc, lost, base = fs.neighbours(n, p)
+            n_capped[n] += lost
             js = np.flatnonzero(np.isfinite(sc))
             order = np.lexsort((js, -sc[js]))
             ranked, rs = js[order], sc[js][order]
@@ -545,6 +490,151 @@ def sweep_states_host(model, theta, Y, ss, lpj, S_perm, n_parents, n_keep, x_inf
             if r == 0 and k:
                 best_flip[n], gain[n] = ranked[0], rs[0] - base
     return cand, counts, scores, best_flip, gain, n_capped, margin
+
+
+class _FlipScores:
+    """What sweep_states_host and neighbour_bound_host share (the flip law of csrc/kernels_sweep.hpp): the parents of a
+    datapoint and the score of every one-flip neighbour of a parent."""
+
+    def __init__(self, model, theta, Y, ss, lpj, S_perm, x_infr=None):
+        self.sssc = model not in ("bsc", "BSC", "ebsc")
+        assert S_perm in (0, 1)
+        self.S_perm = S_perm
+        W = self.W = np.asarray(theta["W"], dtype=np.float64)
+        Y = np.asarray(Y, dtype=np.float64)
+        self.masked = x_infr is not None
+        if self.masked:
+            self.x_infr = np.asarray(x_infr, dtype=bool)
+            assert self.x_infr.shape == Y.shape
+            Y = np.where(self.x_infr, Y, 0.0)
+        self.ss = np.asarray(ss, dtype=bool)
+        self.lpj = np.asarray(lpj, dtype=np.float64)
+        (D, self.H), (self.N, self.S) = W.shape, self.ss.shape[:2]
+        assert Y.shape == (self.N, D) and self.ss.shape == (self.N, self.S, self.H)
+        assert self.lpj.shape == (self.N, S_perm + self.S)
+        self.cap = SEED_MAX_ACTIVE["sssc" if self.sssc else "bsc"]
+        self.G, self.B, self.yy = W.T @ W, Y @ W, (Y * Y).sum(axis=1)
+        self.Gd = np.diag(self.G).copy()
+        self.n_G = None  # masked: the datapoint whose Gram matrix G is
+        if self.sssc:
+            self.mus, self.Psi = np.asarray(theta["mus"], dtype=np.float64), np.asarray(theta["Psi"], dtype=np.float64)
+            pies = np.asarray(theta["pies"], dtype=np.float64)
+            self.pil_bar, self.s2inv = np.log(pies / (1.0 - pies)), 1.0 / float(theta["sigma2"])
+        else:
+            pi, sigma = float(theta["pi"]), float(theta["sigma"])
+            self.pre1, self.pil_bar = -1.0 / 2.0 / sigma / sigma, np.log(pi / (1.0 - pi))
+
+    def _gram(self, n):
+        if self.masked and self.n_G != n:  # the datapoint's own Gram matrix, from the reliable rows of W
+            Wo = self.W[self.x_infr[n]]
+            self.G = Wo.T @ Wo
+            self.Gd = np.diag(self.G).copy()
+            self.n_G = n
+
+    def _state_lpj(self, n, act):
+        if len(act) == 0:
+            return -0.5 * self.yy[n] * self.s2inv
+        return float(_seed_scores_sssc(self.G, self.Psi, self.mus, self.pil_bar, self.s2inv, self.B[n], self.yy[n],
+                                       list(act[:-1]), np.array(act[-1:]))[0])
+
+    def parents(self, n):
+        """The S varying slots of datapoint n by descending lpj, ties by ascending slot."""
+        row = np.where(np.isfinite(self.lpj[n, self.S_perm:]), self.lpj[n, self.S_perm:], -np.inf) + 0.0
+        return np.lexsort((np.arange(self.S), -row))
+
+    def neighbours(self, n, p):
+        """(sc, lost, base) of the parent ``p`` (bool (H,)) of datapoint n: sc (H,) the score of p with bit j flipped, -inf
+        where that state is all-zero, held by K^n, above the cap or has no finite score; lost: a neighbour went to the
+        cap; base: the score of p itself (ES3C above the cap: NaN)."""
+        self._gram(n)
+        G, B, yy, cap, H = self.G, self.B, self.yy, self.cap, self.H
+        act = np.flatnonzero(p)
+        m = len(act)
+        diff = self.ss[n] ^ p
+        one = diff.sum(axis=1) == 1
+        held = np.zeros(H, dtype=bool)
+        held[np.argmax(diff[one], axis=1)] = True
+        size = np.where(p, m - 1, m + 1)
+        live = (size > 0) & ~held
+        lost = live & (size > cap)
+        live &= ~lost
+        sc = np.full(H, -np.inf)
+        if self.sssc:
+            base = self._state_lpj(n, act) if m <= cap else np.nan
+            add = np.flatnonzero(live & ~p)
+            if len(add):
+                sc[add] = _seed_scores_sssc(G, self.Psi, self.mus, self.pil_bar, self.s2inv, B[n], yy[n], list(act), add)
+            for j in np.flatnonzero(live & p):
+                sc[j] = self._state_lpj(n, act[act != j])
+        else:
+            pre1, pil_bar = self.pre1, self.pil_bar
+            c = B[n] - G[act].sum(axis=0)
+            base = pre1 * (yy[n] - (B[n, act] + c[act]).sum()) + m * pil_bar
+            with np.errstate(invalid="ignore", over="ignore"):
+                both = np.where(p, base - pil_bar + pre1 * (self.Gd + 2.0 * c), base + pil_bar + pre1 * (self.Gd - 2.0 * c))
+            sc[live] = both[live]
+        sc[~np.isfinite(sc)] = -np.inf
+        return sc, bool(lost.any()), base
+
+
+# ---- the neighbourhood bound: the NumPy mirror of evoamd_neighbour_bound (csrc/kernels_nbound.hpp has the law) --------------
+def neighbour_bound_host(model, theta, Y, ss, lpj, S_perm, n_parents, x_infr=None):
+    """The exact mass of the one-flip neighbours of K^n as evoamd_neighbour_bound sums it, written from the law on bool rows.
+    ``ss`` bool (N, S, H) and ``lpj`` (N, S_perm + S) are taken as given; the parents are the ``n_parents`` = P (1 <= P <= S)
+    varying states with the largest lpj, ties by ascending slot, and the scores are those of sweep_states_host.  A
+    neighbour -- parent r with bit j flipped -- is absent when it is (a) the all-zero state, (b) held by K^n, (c) above
+    SEED_MAX_ACTIVE latents (``n_capped`` counts the parents that lost one so), (d) owned by an earlier parent: some r' < r is
+    two flips from parent r and j is one of the two differing bits; or when its score is not finite.  Returns a dict of
+    (N,) arrays: "F" = logsumexp of the lpj row, "M" = log sum exp of the present scores (-inf without one), "F_plus" =
+    logaddexp(F, M), "gap", "mass_outside" = exp(M - F_plus), "n_states", "n_capped" (int32), "best_score", "best_parent"
+    (rank) and "best_flip" (int32) of the largest present score, ties by ascending rank, then latent (-inf / -1 / -1
+    without one), and "margin", the relative gap (a - b) / max(1, |a|) between the two largest present scores (inf with
+    fewer than two).  A row with a NaN or +inf, or all -inf ("bad weights"): NaN in the real-valued arrays, 0 / -1 in the
+    others.  ``x_infr`` as for sweep_states_host."""
+    fs = _FlipScores(model, theta, Y, ss, lpj, S_perm, x_infr)
+    N, S, H = fs.N, fs.S, fs.H
+    P = int(n_parents)
+    if not 1 <= P <= S:
+        raise ValueError("neighbour_bound: n_parents = %d must be in [1, S = %d]" % (P, S))
+    out = {name: np.full(N, np.nan) for name in ("F", "M", "F_plus", "gap", "mass_outside")}
+    out["best_score"] = np.full(N, -np.inf)
+    out["margin"] = np.full(N, np.inf)
+    for name in ("n_states", "n_capped"):
+        out[name] = np.zeros(N, dtype=np.int32)
+    for name in ("best_parent", "best_flip"):
+        out[name] = np.full(N, -1, dtype=np.int32)
+    for n in range(N):
+        row = fs.lpj[n]
+        if np.isnan(row).any() or (row == np.inf).any() or not (row > -np.inf).any():
+            continue  # bad weights
+        mx = row.max()
+        F = mx + np.log(np.exp(row - mx).sum())
+        parents = fs.parents(n)[:P]
+        present = []  # (score, r, j)
+        for r, slot in enumerate(parents):
+            p = fs.ss[n, slot]
+            sc, lost, _ = fs.neighbours(n, p)
+            out["n_capped"][n] += lost
+            for r2 in range(r):  # (d)
+                d = np.flatnonzero(fs.ss[n, parents[r2]] ^ p)
+                if len(d) == 2:
+                    sc[d] = -np.inf
+            present += [(sc[j], r, j) for j in np.flatnonzero(np.isfinite(sc))]
+        out["F"][n] = F
+        out["n_states"][n] = len(present)
+        M = -np.inf
+        if present:
+            v = np.array([t[0] for t in present])
+            M = v.max() + np.log(np.exp(v - v.max()).sum())
+            present.sort(key=lambda t: (-t[0], t[1], t[2]))
+            out["best_score"][n], out["best_parent"][n], out["best_flip"][n] = present[0]
+            if len(present) > 1:
+                out["margin"][n] = _seed_gap(present[0][0], present[1][0])
+        out["M"][n] = M
+        out["F_plus"][n] = np.logaddexp(F, M)
+        out["gap"][n] = out["F_plus"][n] - F
+        out["mass_outside"][n] = np.exp(M - out["F_plus"][n])
+    return out
 
 
 # ---- local search on K^n, the swap neighbourhood: the NumPy mirror of the swap stage (csrc/kernels_sweep_swap.hpp has the law)

@@ -470,6 +470,37 @@ int evoamd_sweep_propose_nb(evoamd_ctx *ctx, int n_parents, int n_keep, unsigned
 int evoamd_sweep_states_nb(evoamd_ctx *ctx, int n_sweeps, int n_parents, int n_keep, int Mprime, int stop_when_quiet,
                            unsigned flags, double *trace_out, int *n_done_out, const evoamd_sweep_out *out);
 
+/* The neighbourhood bound: the exact mass of the one-flip neighbours of the best states of K^n (csrc/kernels_nbound.hpp has
+ * the law; evo_amd.variational.neighbour_bound_host is the NumPy mirror).  Per datapoint the n_parents varying states with
+ * the largest lpj are the parents, as for evoamd_sweep_propose but up to S of them; every state one flip away from a parent
+ * is scored with the sweep's own scores unless it is the all-zero state, K^n holds it, it exceeds the seeding cap (ES3C 8,
+ * EBSC 64 active latents) or an earlier parent owns it -- exact tests on the packed words, so every state of the union of
+ * the neighbourhoods outside K^n is counted exactly once -- and the scores are summed, not ranked:
+ * M_n = log sum exp(score), F+_n = logaddexp(F_n, M_n) with F_n evoamd_posterior_scores' bound, F_n <= F+_n <= log p(y_n) - ljc.
+ * A deterministic lower bound: no random numbers, no atomics on global memory, a fixed summation order, two calls give the
+ * same bits.  The call evaluates the resident rows (as evoamd_sweep_propose does at entry) and writes nothing into K^n, the
+ * candidate batch or the statistics rows.  Outputs (host, N each, each pointer and out itself may be NULL): F; M (-inf
+ * without a scored neighbour); n_states, the neighbours summed; n_capped, the parents that lost a neighbour to the cap;
+ * best_score, best_parent (the parent's rank) and best_flip (the latent) of the largest score, ties by ascending rank, then
+ * latent (-inf / -1 / -1 without one); sum (2) = {the sum of F+_n over the datapoints with an estimate, their number}.  A
+ * row with a NaN or +inf, or all -inf ("bad weights", as evoamd_loglik_estimate): F and M NaN, the counts 0, no estimate.
+ * flags: EVOAMD_NBOUND_INCOMPLETE permits incomplete data, a permission like EVOAMD_SWEEP_INCOMPLETE: with masks resident the
+ * masked instantiation runs, without masks the complete one.  EVOAMD_E_INVALID before anything is written: an unknown flag;
+ * no Theta, data or K^n; masks resident without the flag; background_unit, ebsc_f32 or bsc_direct; n_parents outside [1, S];
+ * one wavefront's share of LDS (the flip sweep's with n_keep = 0 plus 8 S bytes) too large. */
+#define EVOAMD_NBOUND_INCOMPLETE 1u
+typedef struct evoamd_nbound_out {
+  double *F;            /* (N) */
+  double *M;            /* (N) */
+  int32_t *n_states;    /* (N) */
+  int32_t *n_capped;    /* (N) */
+  double *best_score;   /* (N) */
+  int32_t *best_parent; /* (N) */
+  int32_t *best_flip;   /* (N) */
+  double *sum;          /* (2) */
+} evoamd_nbound_out;
+int evoamd_neighbour_bound(evoamd_ctx *ctx, int n_parents, unsigned flags, const evoamd_nbound_out *out);
+
 /* Per-datapoint scores of the lpj rows and K^n resident on the device (after a seed, an upload or any pass), each output
  * (N) or NULL.  With m = max_s lpj_ns, w_s = exp(lpj_ns - m), z = sum_s w_s over the S_perm + S columns:
  * F_out = m + log z (the bound per datapoint without ljc, the counterpart of ll_out of evoamd_loglik_exact);
@@ -980,7 +1011,8 @@ enum {
   EVOAMD_K_SWEEP = 30,         /* evoamd_sweep_propose / evoamd_sweep_states: the proposal kernel (ES3C: with the transpose of GP) */
   EVOAMD_K_SWEEP_SWAP = 31,    /* evoamd_sweep_*_nb with EVOAMD_SWEEP_SWAP: the swap proposal kernel */
   EVOAMD_K_RESIZE = 32,        /* evoamd_resize_states: the resize kernel (downloads excluded) */
-  EVOAMD_K_COUNT = 33
+  EVOAMD_K_NBOUND = 33,        /* evoamd_neighbour_bound: the neighbourhood kernel (ES3C: with the transpose of GP) and the bound of the rows */
+  EVOAMD_K_COUNT = 34
 };
 /* on = bit mask of kernel classes to time (bit k = class k; -1 = all, 0 = off).  Each timed span
  * records two HIP events on the compute stream, which costs about 10 us of stream time per span:
