@@ -58,7 +58,7 @@ KERNEL_IDS = {
 # therefore stays as it is); Engine.timing / Engine.kernel_time_ms take names of either table
 KERNEL_IDS_EXTRA = {"posterior_sample": 23, "seed_states": 24, "loglik_proposal": 25, "loglik_lpj": 26, "loglik_fold": 27,
                     "remap_latents": 28, "stats_kappa": 29, "sweep": 30, "sweep_swap": 31, "resize": 32,
-                    "neighbour_bound": 33}
+                    "neighbour_bound": 33, "predictive_score": 34}
 
 
 def kernel_id(name):
@@ -83,6 +83,11 @@ class NboundOut(ctypes.Structure):
     """evoamd_nbound_out: the outputs of evoamd_neighbour_bound, each pointer may be NULL."""
     _fields_ = [("F", _c_dp), ("M", _c_dp), ("n_states", _c_i32p), ("n_capped", _c_i32p), ("best_score", _c_dp),
                 ("best_parent", _c_i32p), ("best_flip", _c_i32p), ("sum", _c_dp)]
+
+
+class PredScoreOut(ctypes.Structure):
+    """evoamd_pred_score_out: the outputs of evoamd_predictive_score, each pointer may be NULL (logp and pit together)."""
+    _fields_ = [("logp", _c_dp), ("pit", _c_dp), ("logp_n", _c_dp), ("count", _c_i32p)]
 
 
 _I32 = ctypes.c_int32
@@ -188,6 +193,7 @@ SIGNATURES = {
     "evoamd_download_posterior": (_I, [_vp, _c_dp, _c_dp]),
     "evoamd_predictive_moments": (_I, [_vp, _I, ctypes.POINTER(_I64)]),
     "evoamd_download_predictive": (_I, [_vp, _c_dp, _c_dp]),
+    "evoamd_predictive_score": (_I, [_vp, _c_dp, _c_u8p, _I, ctypes.POINTER(PredScoreOut), ctypes.POINTER(_I64), _c_dp]),
     "evoamd_posterior_sample": (_I, [_vp, _I, _U64, _U64, _I, _I, _I, ctypes.POINTER(_I64)]),
     "evoamd_download_posterior_samples": (_I, [_vp, _I, _vp]),
     "evoamd_loglik_estimate": (_I, [_vp, _I, _U64, _U64, _DBL, _I, _c_dp, _c_dp, _c_dp, _c_dp, _c_i32p,

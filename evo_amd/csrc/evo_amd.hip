@@ -31,6 +31,7 @@
 #include "kernels_generate.hpp"
 #include "kernels_exact.hpp"
 #include "kernels_predictive.hpp"
+#include "kernels_predictive_score.hpp"
 #include "kernels_posterior_sample.hpp"
 #include "kernels_seed.hpp"
 #include "kernels_seed_beam.hpp"
@@ -172,6 +173,7 @@ enum {  // internal kernel ids (see evoamd_kernel_name)
   KID_SWEEP_SWAP,    // evoamd_sweep_*_nb with EVOAMD_SWEEP_SWAP: the swap proposal kernel
   KID_RESIZE,        // evoamd_resize_states: the resize kernel (downloads excluded)
   KID_NBOUND,        // evoamd_neighbour_bound: the neighbourhood kernel (ES3C: with the transpose of GP) and the bound of the rows
+  KID_PRED_SCORE,    // evoamd_predictive_score: the transpose of W, the visit list, the score kernel, its partials and their two reductions
   KID_COUNT
 };
 
@@ -552,6 +554,13 @@ struct evoamd_ctx {
   DevBuf<int> pred_status;
   i64 pred_N = 0;
   int pred_D = 0;
+  // evoamd_predictive_score (kernels_predictive_score.hpp): y_true, then logp | pit (N x D each), logp_n (N), the
+  // partials (2 grid) and the total (2); the query bytes (N x D); count | nbad | status (N each); the list of the visited
+  // datapoints and their number (N + 1).  Grown on demand, rewritten by every call (W^T goes through pred_Wt)
+  DevBuf<double> pscore_y, pscore_d;
+  DevBuf<uint8_t> pscore_q;
+  DevBuf<int> pscore_i;
+  DevBuf<i64> pscore_list;
   // evoamd_posterior_sample (kernels_posterior_sample.hpp): the outputs of the last call and the status word per datapoint,
   // grown on demand and released by evoamd_configure (never the EM state above; W^T goes through pred_Wt, rewritten by
   // every call); ps_keep < 0: nothing to download
@@ -954,6 +963,9 @@ static int set_kernel_lds_limits() {
     const void *sk[] = {(const void *)posterior_sample_kernel<1, true>, (const void *)posterior_sample_kernel<2, true>,
                         (const void *)posterior_sample_kernel<4, true>, (const void *)posterior_sample_kernel<8, true>};
     for (const void *f : sk) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    const void *ck[] = {(const void *)predictive_score_kernel<1, true>, (const void *)predictive_score_kernel<2, true>,
+                        (const void *)predictive_score_kernel<4, true>, (const void *)predictive_score_kernel<8, true>};
+    for (const void *f : ck) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   }
   HIP_TRY(hipFuncSetAttribute((const void *)remap_latents_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, REMAP_LDS_BYTES));
   HIP_TRY(hipFuncSetAttribute((const void *)resize_states_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RESIZE_LDS_BYTES));
@@ -1340,6 +1352,12 @@ static void configure_drop(evoamd_ctx *c) {
   c->ps_z.reset();
   c->ps_y.reset();
   made_posterior_samples(c, -1);
+  // ... the inputs and outputs of evoamd_predictive_score (N x D of that geometry; nothing of them is handed out later)
+  c->pscore_y.reset();
+  c->pscore_q.reset();
+  c->pscore_d.reset();
+  c->pscore_i.reset();
+  c->pscore_list.reset();
   // ... and the importance draws of evoamd_loglik_estimate
   c->lle_d.reset();
   c->lle_keep_d.reset();
@@ -5816,6 +5834,125 @@ extern "C" int evoamd_download_predictive(evoamd_ctx *c, double *mean, double *v
 }
 
 // ---------------------------------------------------------------------------------------
+// log predictive density and PIT per entry (kernels_predictive_score.hpp has the law): the admission, the Theta scalars,
+// the PredArgs and the launch shape of evoamd_predictive_moments; own buffers, sized before anything is launched; the
+// moments evoamd_predictive_moments left on the device stay as they are
+// ---------------------------------------------------------------------------------------
+template <bool SSSC>
+static void launch_predictive_score(evoamd_ctx *c, const PredScoreArgs &q, int R, unsigned grid, size_t lds) {
+  switch (R) {
+    case 1: predictive_score_kernel<1, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(q); break;
+    case 2: predictive_score_kernel<2, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(q); break;
+    case 4: predictive_score_kernel<4, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(q); break;
+    default: predictive_score_kernel<8, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(q); break;
+  }
+}
+
+extern "C" int evoamd_predictive_score(evoamd_ctx *c, const double *y_true, const uint8_t *query, int add_noise,
+                                       const evoamd_pred_score_out *out, int64_t counters[4], double total[2]) {
+  REQUIRE(c && c->configured && c->have_data && c->have_params,
+          "evoamd_predictive_score: configure, upload data and set parameters first");
+  REQUIRE(!c->f32, "evoamd_predictive_score is not available in the float32 mode");
+  REQUIRE_KN(c);
+  REQUIRE(y_true && query && counters && total, "evoamd_predictive_score: y_true, query, counters or total is NULL");
+  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
+  REQUIRE(sssc || add_noise, "evoamd_predictive_score: EBSC without the noise term has variance 0 at every entry: nothing to score");
+  if (c->D > 64 * PRED_R_MAX)
+    return fail(EVOAMD_E_INVALID, "evoamd_predictive_score: D = %d, at most %d observables are supported (64 lanes x %d registers)",
+                c->D, 64 * PRED_R_MAX, PRED_R_MAX);
+  HIP_TRY(hipSetDevice(c->device));
+  const evoamd_pred_score_out o = out ? *out : evoamd_pred_score_out{};
+  REQUIRE(!o.logp == !o.pit, "evoamd_predictive_score: logp and pit come together (both or neither)");
+  const i64 N = c->N;
+  const int D = c->D, H = c->H;
+  const size_t nd = (size_t)N * D, n = (size_t)N;
+  const bool per_entry = o.logp != nullptr;
+  const unsigned grid = cdiv(N, PRED_WAVES);
+  // ---- every buffer, before anything is launched
+  TRY(c->pscore_y.ensure(c, nd));
+  TRY(c->pscore_q.ensure(c, nd));
+  TRY(c->pscore_d.ensure(c, (per_entry ? 2 * nd : 0) + n + 2 * (size_t)grid + 2));
+  TRY(c->pscore_i.ensure(c, 3 * n));
+  TRY(c->pscore_list.ensure(c, n + 1));
+  TRY(c->pred_Wt.ensure(c, (size_t)H * D));
+  if (sssc) TRY(ensure_B(c));
+  // the scalars of the current Theta (a device update leaves them in the scalar block only)
+  double dpar[DP_COUNT];
+  HIP_TRY(hipMemcpyAsync(dpar, c->dpar, DP_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->pscore_y, y_true, nd * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->pscore_q, query, nd, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  PredScoreArgs q = {};
+  PredArgs &a = q.p;
+  a.mask = c->mask_infr;
+  a.row_any = c->mask_infr ? c->row_any : nullptr;
+  a.lpj = c->lpj;
+  a.states = c->states;
+  a.Wt = c->pred_Wt;
+  a.G = c->G;
+  a.Psi = c->Psi;
+  a.mus = c->mus;
+  a.Bm = c->Bm;
+  a.N = N;
+  a.D = D, a.H = H, a.HW = c->HW, a.S = c->S, a.S_perm = c->S_perm, a.L = c->L;
+  a.kcap = H < PRED_MAX_K ? H : PRED_MAX_K;
+  a.bg = c->bg_unit;
+  a.sigma2 = sssc ? dpar[DP_SIGMA2] : dpar[DP_SIGMA] * dpar[DP_SIGMA];
+  a.add_noise = add_noise ? 1 : 0;
+  q.y_true = c->pscore_y;
+  q.query = c->pscore_q;
+  double *dd = c->pscore_d;
+  if (per_entry) q.logp = dd, q.pit = dd + nd, dd += 2 * nd;
+  q.logp_n = dd;
+  double *partial = dd + n, *d_total = partial + 2 * (size_t)grid;
+  q.count = c->pscore_i, q.nbad = q.count + n, a.status = q.count + 2 * n;
+  q.list = c->pscore_list;
+  int R = 1;
+  while (64 * R < D) R <<= 1;
+  const size_t lds = PRED_WAVES * pred_lds_doubles(a.kcap, sssc) * sizeof(double);
+  {
+    SpanGuard g(c, KID_PRED_SCORE);
+    transpose_kernel<<<cdiv((i64)H * D, 256), 256, 0, c->stream>>>(c->W, D, H, c->pred_Wt);
+    pred_score_visit_kernel<<<grid, 64 * PRED_WAVES, 0, c->stream>>>(q);
+    pred_score_compact_kernel<<<1, PRED_COMPACT_THREADS, 0, c->stream>>>(a.status, N, q.list);
+    if (sssc)
+      launch_predictive_score<true>(c, q, R, grid, lds);
+    else
+      launch_predictive_score<false>(c, q, R, grid, lds);
+    pred_score_partials_kernel<<<cdiv((i64)grid, 256), 256, 0, c->stream>>>(q.logp_n, q.count, N, (i64)grid, partial);
+    reduce_partials_kernel<<<1, 256, 0, c->stream>>>(partial, (i64)grid, d_total, 0);
+    reduce_partials_kernel<<<1, 256, 0, c->stream>>>(partial + grid, (i64)grid, d_total + 1, 0);
+  }
+  HIP_TRY(hipGetLastError());
+  DBG_SYNC(c, "predictive_score");
+  std::vector<int> ints(3 * n);
+  HIP_TRY(hipMemcpyAsync(ints.data(), c->pscore_i, 3 * n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const int *status = ints.data() + 2 * n, *nbad = ints.data() + n;
+  int64_t cnt[4] = {0, 0, 0, 0};
+  for (i64 i = 0; i < N; i++) {
+    const int st = status[(size_t)i];
+    if ((st & 0xFF) == PRED_OVER_K)
+      return fail(EVOAMD_E_INVALID, "evoamd_predictive_score: datapoint n = %lld holds a state with k = %d active latents, "
+                  "at most %d are supported (PRED_MAX_K)", (long long)i, st >> 8, PRED_MAX_K);
+    cnt[0] += st == PRED_SINGULAR;
+    cnt[1] += st == PRED_SKIPPED;
+    cnt[2] += st == PRED_NOT_QUERIED;
+    cnt[3] += nbad[(size_t)i];
+  }
+  if (per_entry) {
+    HIP_TRY(hipMemcpyAsync(o.logp, q.logp, nd * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(o.pit, q.pit, nd * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (o.logp_n) HIP_TRY(hipMemcpyAsync(o.logp_n, q.logp_n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(total, d_total, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (o.count) memcpy(o.count, ints.data(), n * sizeof(int));
+  for (int k = 0; k < 4; k++) counters[k] = cnt[k];
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
 // Proposals for K^n: seeding (kernels_seed.hpp, kernels_seed_beam.hpp), local search (kernels_sweep.hpp,
 // kernels_sweep_swap.hpp) and the neighbourhood bound that sums what the flip sweep ranks (kernels_nbound.hpp).
 // One table of the family's kernels, indexed like their LDS layouts; one admission for what all
@@ -6853,6 +6990,6 @@ extern "C" const char *evoamd_kernel_name(int kid) {
                                          "patches",      "init_states",    "posterior_sample", "seed_states",
                                          "loglik_proposal", "loglik_lpj",  "loglik_fold",     "remap_latents",
                                          "stats_kappa",  "sweep",       "sweep_swap",      "resize",
-                                         "neighbour_bound"};
+                                         "neighbour_bound", "predictive_score"};
   return (kid >= 0 && kid < KID_COUNT) ? names[kid] : "?";
 }

@@ -846,6 +846,37 @@ class Engine:
                                                   None if var is None else dptr(var)))
         return mean, var, info
 
+    def predictive_score(self, y_true, query, noise=True, per_entry=False):
+        """Log predictive density and PIT of the entries ``query`` (bool (N, D)) names, at the values ``y_true`` (float64
+        (N, D), read at the queried entries only), under the mixture over the Theta, K^n and lpj rows on the device
+        (evoamd_predictive_score; csrc/kernels_predictive_score.hpp has the law, evo_amd.models.predictive_log_score_host
+        is the NumPy mirror).  Returns a dict: "logp_n" (N,) the sum over the datapoint's scored entries, "count" (N,)
+        int32, the scalars "sum" and "total_count" (reduced on the device), the counters "n_singular", "n_skipped",
+        "n_not_queried" (datapoints without a scored entry: not visited) and "n_bad_values" (queried entries whose y_true
+        is not finite) and, with ``per_entry``, "logp" and "pit" (N, D), NaN outside the scored entries.  Deterministic;
+        no statistics pass runs and the EM state and the moments of predictive_moments stay as they are.  ValueError for
+        wrong shapes; EvoAmdError naming the rule for EBSC without noise, D > 512, the float32 mode, and -- naming n and k
+        -- a state with more than 32 active latents in a visited datapoint."""
+        y_true = np.ascontiguousarray(y_true, dtype=np.float64)
+        query = np.ascontiguousarray(np.asarray(query, dtype=bool).view(np.uint8))
+        if y_true.shape != (self.N, self.D) or query.shape != (self.N, self.D):
+            raise ValueError("predictive_score: y_true and query must be (N, D) = (%d, %d), got %r and %r"
+                             % (self.N, self.D, y_true.shape, query.shape))
+        res = {"logp_n": np.empty(self.N, dtype=np.float64), "count": np.empty(self.N, dtype=np.int32)}
+        out = _lib.PredScoreOut()
+        out.logp_n, out.count = dptr(res["logp_n"]), i32ptr(res["count"])
+        if per_entry:
+            res["logp"], res["pit"] = np.empty((self.N, self.D)), np.empty((self.N, self.D))
+            out.logp, out.pit = dptr(res["logp"]), dptr(res["pit"])
+        counters = (ctypes.c_int64 * 4)()
+        total = np.zeros(2, dtype=np.float64)
+        check(self.lib.evoamd_predictive_score(self._h, dptr(y_true), u8ptr(query), 1 if noise else 0, ctypes.byref(out),
+                                               counters, dptr(total)))
+        res["sum"], res["total_count"] = float(total[0]), int(total[1])
+        for i, name in enumerate(("n_singular", "n_skipped", "n_not_queried", "n_bad_values")):
+            res[name] = int(counters[i])
+        return res
+
     def _check_result_serial(self, kind, serial, what):
         if serial is not None and serial != getattr(self, kind):
             raise EvoAmdError("the %s on the device are newer ones (a later call or a configure)" % what)

@@ -1426,6 +1426,60 @@ class Model:
             self._moments_handle = mean
         return mean, var, info
 
+    def predictive_log_score(self, model_params, my_suff_stat, my_data, y_true, query=None, noise=True, per_entry=False):
+        """The log predictive density of held-out entries and its calibration counterpart, the PIT: (score, info).  Entry
+        (n, d) is scored when ``query[n, d]`` (bool (N_loc, D)) is set and ``y_true[n, d]`` (float64 (N_loc, D)) is finite;
+        ``query=None`` means ~my_data["x_infr"], the entries the model did not see (ValueError "nothing to score" on
+        complete data).  An explicit ``query`` may name reliable entries: that is an IN-SAMPLE score -- the model has
+        conditioned on the very value it is asked to predict -- and says nothing about held-out entries.  Values of
+        ``y_true`` outside ``query`` are never read (NaN there is fine).  The predictive distribution of an entry is the
+        MIXTURE over K^n (and the permanent all-zero state) with the weights q_ns, one Gaussian N(m_ns,d, tau_ns,d) per
+        state -- m and v of predictive_moments, tau = v + the noise variance with ``noise`` (score noisy observations) or
+        tau = v without (score the clean signal, the denoising case; EBSC has v = 0 everywhere then: ValueError) -- not
+        the single Gaussian of predictive_moments' mean and var, which differs from it wherever the states disagree.
+        logp = log sum_s q_ns N(y; m, tau), pit = sum_s q_ns Phi((y - m) / sqrt(tau)) (Engine.predictive_score;
+        csrc/kernels_predictive_score.hpp has the law, evo_amd.models.predictive_log_score_host is the NumPy mirror;
+        pit_summary reads the PIT).  ``score`` is the mean log density per scored entry over all ranks (one all-reduce of
+        [sum, count], as estimate_log_likelihood; NaN when nothing was scored).  info holds this rank's "logp_n" (N_loc,)
+        -- the sum over the datapoint's scored entries --, "count" (N_loc,) int32, the counters "n_singular", "n_skipped"
+        (datapoints with a singular system / without a reliable entry, as in predictive_moments: nothing of them is
+        scored), "n_not_queried" (datapoints without a scored entry: not visited at all) and "n_bad_values" (queried
+        entries whose y_true is not finite: NaN, left out) and, with ``per_entry``, "logp" and "pit" (N_loc, D), NaN
+        outside the scored entries.  It scores entries one by one, not the joint density of a datapoint's held-out
+        entries.  The float32 mode raises NotImplementedError; D > 512 and a state with more than 32 active latents in a
+        visited datapoint raise as in predictive_moments.  Deterministic (two calls give the same bits), works with
+        sync_host=False, writes nothing into the three dicts and leaves K^n, lpj, the candidate batch, Theta,
+        y_reconstructed, the statistics rows and the moments of predictive_moments on the device as they are."""
+        if self.dtype == np.float32:
+            raise NotImplementedError("predictive_log_score is not available in the float32 mode")
+        if self.model_name != "sssc" and not noise:
+            raise ValueError("predictive_log_score: EBSC without noise has variance 0 at every entry: nothing to score")
+        shape = np.shape(my_data["y"])
+        if query is None:
+            if self._complete(my_data):
+                raise ValueError("predictive_log_score: nothing to score (query=None on complete data)")
+            query = ~np.asarray(my_data["x_infr"], dtype=bool)
+        query = np.asarray(query)
+        if query.dtype != np.bool_ or query.shape != shape:
+            raise ValueError("predictive_log_score: query must be a bool array of shape %r" % (shape,))
+        y_true = np.asarray(y_true)
+        if y_true.shape != shape:
+            raise ValueError("predictive_log_score: y_true must have the shape %r of my_data[\"y\"], got %r" % (shape, y_true.shape))
+        yr = my_data.get("y_reconstructed")
+        if isinstance(yr, ResidentReconstruction) and yr.resident and not yr.materialised:
+            yr.rows()  # setting the parameters below drops the device copy of an unread reconstruction: fetch it first
+        uploads = self._kn_uploads  # (see reconstruct(): decide before _prepare() runs)
+        eng = self._prepare(my_suff_stat, my_data)
+        # (the precompute stores its derived keys and zeroes the reset counters: on shallow copies here)
+        self.E_step_precompute(dict(model_params), dict(my_suff_stat), my_data)
+        if model_params is not self._dev_theta:
+            self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
+        if self.sync_host or self._kn_uploads != uploads:
+            eng.upload_lpj(my_suff_stat["lpj"])
+        info = eng.predictive_score(y_true, query, noise=noise, per_entry=per_entry)
+        total, n_all = _reduce_array(self.comm, np.array([info.pop("sum"), float(info.pop("total_count"))]))  # (the one all-reduce)
+        return (total / n_all if n_all else float("nan")), info
+
     _KEEP_ALL = ("slot", "s", "z", "y")  # the default of sample_posterior, told from the same names given by the caller
 
     def sample_posterior(self, model_params, my_suff_stat, my_data, n_samples=1, seed=None, first_index=0,

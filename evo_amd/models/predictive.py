@@ -95,42 +95,52 @@ def predictive_moments_host(model, theta, states, lpj, Y, x_infr=None, S_perm=0,
             continue
         e = np.exp(lpj[n] - lpj[n].max())
         q = e / (e.sum() + F64_TINY)
-        m = np.zeros((S_perm + S, D))
-        v = np.zeros((S_perm + S, D))
-        singular = False
-        for s in range(S):
-            if q[S_perm + s] == 0.0:
-                continue
-            idx = np.flatnonzero(states[n, s])
-            if idx.size == 0:
-                continue
-            if not sssc:
-                m[S_perm + s] = W[:, idx].sum(axis=1)
-                continue
-            if obs is None:
-                key = idx.tobytes()
-                if key not in cache:
-                    cache[key] = _complete_terms(W, mus, Psi, sigma2, idx)
-                terms = cache[key]
-                if terms is None:
-                    singular = True
-                    break
-                WA, Lam, vdiag = terms
-                kappa = mus[idx] + Lam @ (WA.T @ (Y[n] - WA @ mus[idx])) / sigma2
-                m[S_perm + s], v[S_perm + s] = WA @ kappa, vdiag
-            else:
-                terms = state_terms_es3c(W, mus, Psi, sigma2, idx, Y[n], obs)
-                if terms is None:
-                    singular = True
-                    break
-                m[S_perm + s], v[S_perm + s] = terms
+        terms = _datapoint_terms(sssc, W, mus if sssc else None, Psi if sssc else None, sigma2, states[n], q == 0.0, Y[n], obs,
+                                 S_perm, cache)
+        singular = terms is None
         if singular:
             info["n_singular"] += 1
             continue
+        m, v = terms
         mu = q @ m
         mean[n] = mu
         var[n] = q @ ((m - mu) ** 2 + v) + (sigma2 if noise else 0.0)
     return mean, var, info
+
+
+def _datapoint_terms(sssc, W, mus, Psi, sigma2, states_n, skip, y, obs, S_perm, cache):
+    """(m, v), each (S_perm + S, D): the per-state terms of one datapoint -- zero rows for the permanent all-zero state,
+    for an empty state and for the slots ``skip`` (bool (S_perm + S,)) names -- or None when a state that is not skipped
+    has a singular system.  ``obs``: the datapoint's reliable entries, None for complete data, where ``cache`` keeps the
+    terms of an active set (they depend on the datapoint through y alone)."""
+    S, D = states_n.shape[0], W.shape[0]
+    m = np.zeros((S_perm + S, D))
+    v = np.zeros((S_perm + S, D))
+    for s in range(S):
+        if skip[S_perm + s]:
+            continue
+        idx = np.flatnonzero(states_n[s])
+        if idx.size == 0:
+            continue
+        if not sssc:
+            m[S_perm + s] = W[:, idx].sum(axis=1)
+            continue
+        if obs is None:
+            key = idx.tobytes()
+            if key not in cache:
+                cache[key] = _complete_terms(W, mus, Psi, sigma2, idx)
+            terms = cache[key]
+            if terms is None:
+                return None
+            WA, Lam, vdiag = terms
+            kappa = mus[idx] + Lam @ (WA.T @ (y - WA @ mus[idx])) / sigma2
+            m[S_perm + s], v[S_perm + s] = WA @ kappa, vdiag
+        else:
+            terms = state_terms_es3c(W, mus, Psi, sigma2, idx, y, obs)
+            if terms is None:
+                return None
+            m[S_perm + s], v[S_perm + s] = terms
+    return m, v
 
 
 def _complete_terms(W, mus, Psi, sigma2, idx):

@@ -786,6 +786,36 @@ int evoamd_download_posterior(evoamd_ctx *ctx, double *Es, double *Ez);
 int evoamd_predictive_moments(evoamd_ctx *ctx, int add_noise, int64_t counters[2]);
 int evoamd_download_predictive(evoamd_ctx *ctx, double *mean, double *var);
 
+/* evoamd_predictive_score: the log predictive density and the PIT (the predictive CDF at the true value) of single entries
+ * under the MIXTURE over K^n that evoamd_predictive_moments collapses to two moments (csrc/kernels_predictive_score.hpp has
+ * the law; evo_amd.models.predictive_log_score_host is the NumPy mirror).  y_true (N x D double) and query (N x D bytes)
+ * are host arrays; an entry is SCORED when its query byte is set and its y_true is finite; y_true is never read elsewhere.
+ *   Weights e_s = exp(lpj_s - max lpj) in slot order (the permanent all-zero state first), a state of weight exactly 0 is
+ *   skipped, Wsum = sum e_s; m_sd and v_sd per state exactly as evoamd_predictive_moments forms them (v clamped at 0).
+ *   Per state and scored entry: tau = v_sd + (add_noise ? sigma^2 : 0), u = y_true - m_sd, ld = -(log(2 pi tau) + u^2 / tau) / 2,
+ *   Phi = erfc(-u / sqrt(2 tau)) / 2; tau = 0 is a point mass: ld = -inf, Phi = [u >= 0].
+ *   logp[n, d] = logsumexp_s((lpj_s - max lpj) + ld_s) - log Wsum, folded in slot order with a running maximum (-inf when
+ *   no state has a density);  pit[n, d] = (sum_s e_s Phi_s) / Wsum.
+ *   A queried entry with a non-finite y_true: NaN in logp and pit, left out of every sum and count, counted in counters[3].
+ *   A datapoint without a scored entry is not visited (no decode, no solve): counters[2] (n_not_queried), logp_n 0, count 0.
+ *   A datapoint without a reliable entry (counters[1], n_skipped) or with a singular system (counters[0], n_singular), as
+ *   for evoamd_predictive_moments: NaN at every entry, logp_n 0, count 0.  Entries outside the query are NaN.
+ * Outputs (host; out and each pointer may be NULL, logp and pit come together): logp, pit (N x D), logp_n (N; the sum of
+ * the datapoint's scored entries), count (N; their number); total[2] = {the sum of logp_n, the sum of count}, reduced on
+ * the device in a fixed order.  No atomics: two calls give the same bits.  Runs no statistics pass and leaves K^n, lpj,
+ * Theta, the candidate batch, y_reconstructed, the statistics rows and the moments of evoamd_predictive_moments as they are
+ * (B = Y W is formed if it is not current).  EVOAMD_E_INVALID, before anything is written: no data, Theta or K^n; the float32
+ * mode; EBSC with add_noise = 0 (variance 0 everywhere); D above 512.  A state with more than 32 active latents in a VISITED
+ * datapoint: EVOAMD_E_INVALID naming the datapoint and k; no output is written.  The call has completed on return. */
+typedef struct evoamd_pred_score_out {
+  double *logp;    /* (N, D) */
+  double *pit;     /* (N, D) */
+  double *logp_n;  /* (N) */
+  int32_t *count;  /* (N) */
+} evoamd_pred_score_out;
+int evoamd_predictive_score(evoamd_ctx *ctx, const double *y_true, const uint8_t *query, int add_noise,
+                            const evoamd_pred_score_out *out, int64_t counters[4], double total[2]);
+
 /* ---- samples from the model (generate_data / generate_from_hidden: _models.py:73-99, bsc.py:27-57, sssc.py:66-102) ---- */
 /* N datapoints drawn on the device, one wavefront each (csrc/kernels_generate.hpp):
  *   s_h ~ Bernoulli(pies[h]) (u <= pies[h]; EBSC: the caller fills pies with pi), or s given: s_packed (N x ceil(H/64)
@@ -1012,7 +1042,8 @@ enum {
   EVOAMD_K_SWEEP_SWAP = 31,    /* evoamd_sweep_*_nb with EVOAMD_SWEEP_SWAP: the swap proposal kernel */
   EVOAMD_K_RESIZE = 32,        /* evoamd_resize_states: the resize kernel (downloads excluded) */
   EVOAMD_K_NBOUND = 33,        /* evoamd_neighbour_bound: the neighbourhood kernel (ES3C: with the transpose of GP) and the bound of the rows */
-  EVOAMD_K_COUNT = 34
+  EVOAMD_K_PRED_SCORE = 34,    /* evoamd_predictive_score: the transpose of W, the visit list, the score kernel, its partials and their reductions */
+  EVOAMD_K_COUNT = 35
 };
 /* on = bit mask of kernel classes to time (bit k = class k; -1 = all, 0 = off).  Each timed span
  * records two HIP events on the compute stream, which costs about 10 us of stream time per span:
