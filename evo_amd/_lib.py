@@ -28,6 +28,8 @@ SWEEP_SWAP, SWEEP_NO_FLIP = 2, 4
 SWEEP_NEIGHBOURHOODS = {"flip": 0, "swap": SWEEP_SWAP | SWEEP_NO_FLIP, "both": SWEEP_SWAP}
 # evoamd_neighbour_bound: flags (EVOAMD_NBOUND_*)
 NBOUND_INCOMPLETE = 1
+# evoamd_ais_loglik: flags (EVOAMD_AIS_*)
+AIS_REVERSE, AIS_ADMIT = 1, 2
 
 # evoamd_posterior_sample: keep bits (EVOAMD_PSAMP_KEEP_*) and the output ids of evoamd_download_posterior_samples
 PSAMP_KEEP = {"slot": 1, "s": 2, "z": 4, "y": 8}
@@ -58,7 +60,7 @@ KERNEL_IDS = {
 # therefore stays as it is); Engine.timing / Engine.kernel_time_ms take names of either table
 KERNEL_IDS_EXTRA = {"posterior_sample": 23, "seed_states": 24, "loglik_proposal": 25, "loglik_lpj": 26, "loglik_fold": 27,
                     "remap_latents": 28, "stats_kappa": 29, "sweep": 30, "sweep_swap": 31, "resize": 32,
-                    "neighbour_bound": 33, "predictive_score": 34}
+                    "neighbour_bound": 33, "predictive_score": 34, "ais": 35}
 
 
 def kernel_id(name):
@@ -83,6 +85,13 @@ class NboundOut(ctypes.Structure):
     """evoamd_nbound_out: the outputs of evoamd_neighbour_bound, each pointer may be NULL."""
     _fields_ = [("F", _c_dp), ("M", _c_dp), ("n_states", _c_i32p), ("n_capped", _c_i32p), ("best_score", _c_dp),
                 ("best_parent", _c_i32p), ("best_flip", _c_i32p), ("sum", _c_dp)]
+
+
+class AisOut(ctypes.Structure):
+    """evoamd_ais_out: the outputs of evoamd_ais_loglik, each pointer may be NULL."""
+    _fields_ = [("ll", _c_dp), ("ess", _c_dp), ("log_w_mean", _c_dp), ("log_w_min", _c_dp), ("log_w_max", _c_dp),
+                ("n_flips", ctypes.POINTER(ctypes.c_int64)), ("log_w", _c_dp), ("final_words", _c_u64p), ("chain_flips", _c_i32p),
+                ("F_before", _c_dp), ("F_after", _c_dp), ("admit_sums", _c_dp), ("sum", _c_dp)]
 
 
 class PredScoreOut(ctypes.Structure):
@@ -160,6 +169,7 @@ SIGNATURES = {
     "evoamd_sweep_states_nb": (_I, [_vp, _I, _I, _I, _I, _I, ctypes.c_uint, _c_dp, ctypes.POINTER(_I),
                                     ctypes.POINTER(SweepOut)]),
     "evoamd_neighbour_bound": (_I, [_vp, _I, ctypes.c_uint, ctypes.POINTER(NboundOut)]),
+    "evoamd_ais_loglik": (_I, [_vp, _I, _I, _c_dp, _U64, _U64, ctypes.c_uint, _c_u64p, _I, ctypes.POINTER(AisOut)]),
     "evoamd_posterior_scores": (_I, [_vp, _c_dp, _c_dp, _c_i32p, _c_i32p, _c_dp]),
     "evoamd_remap_latents": (_I, [_vp, _c_i32p, _I, _c_i32p, ctypes.POINTER(_I64)]),
     "evoamd_adopt_remapped_states": (_I, [_vp]),

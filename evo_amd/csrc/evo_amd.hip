@@ -42,6 +42,7 @@
 #include "kernels_sweep.hpp"
 #include "kernels_sweep_swap.hpp"
 #include "kernels_nbound.hpp"
+#include "kernels_ais.hpp"
 
 // ---------------------------------------------------------------------------------------
 // error handling
@@ -174,6 +175,7 @@ enum {  // internal kernel ids (see evoamd_kernel_name)
   KID_RESIZE,        // evoamd_resize_states: the resize kernel (downloads excluded)
   KID_NBOUND,        // evoamd_neighbour_bound: the neighbourhood kernel (ES3C: with the transpose of GP) and the bound of the rows
   KID_PRED_SCORE,    // evoamd_predictive_score: the transpose of W, the visit list, the score kernel, its partials and their two reductions
+  KID_AIS,           // evoamd_ais_loglik: the chain kernel and the fold over the chains (admit: the emission; its lpj and selection count in their own classes)
   KID_COUNT
 };
 
@@ -604,6 +606,13 @@ struct evoamd_ctx {
   // evoamd_neighbour_bound: F | M | F+ | best_score (N each); n_states | n_capped | best_parent | best_flip (N each).  Grown on demand.
   DevBuf<double> nbound_d;
   DevBuf<int> nbound_i;
+  // evoamd_ais_loglik (kernels_ais.hpp): betas (T + 1) | log w (N, C) | ll | ess | log_w_mean | log_w_min | log_w_max | F_before |
+  // F_after (N each); the chains' flips (N, C); the final states (N, C, HW) with the words of s_start (N, HW) behind them;
+  // n_flips (N).  Sized before anything is launched, released by evoamd_configure.
+  DevBuf<double> ais_d;
+  DevBuf<int> ais_i;
+  DevBuf<u64> ais_s;
+  DevBuf<i64> ais_nf;
   // evoamd_remap_latents: K^n in the new latent numbering and its digests, [index (H_new) | n_replaced (N)] and the sum;
   // grown on demand, NOT sized by the geometry: they survive the configure between the remap and
   // evoamd_adopt_remapped_states, which swaps them in and releases them.  remap_H = 0: nothing to adopt.
@@ -1368,6 +1377,11 @@ static void configure_drop(evoamd_ctx *c) {
   c->lle_keep_s.reset();
   c->lle_keep_in.reset();
   made_loglik_draws(c, -1);
+  // ... and the chains of evoamd_ais_loglik
+  c->ais_d.reset();
+  c->ais_i.reset();
+  c->ais_s.reset();
+  c->ais_nf.reset();
   c->huge.reset();
   c->huge_ctl.reset();
   c->huge_slots = c->huge_kc = 0;
@@ -6458,6 +6472,201 @@ extern "C" int evoamd_neighbour_bound(evoamd_ctx *c, int n_parents, unsigned fla
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------
+// annealed importance sampling (kernels_ais.hpp has the law): EBSC on complete data.  Plan (every refusal, the launch
+// shape, the sizes), then the named stages: buffers, chains, fold, (admit) emission + candidate lpj + selection, fetch.
+// Without EVOAMD_AIS_ADMIT nothing of the EM state is written: B = Y W is (re)formed like by every lpj pass, nothing else.
+// ---------------------------------------------------------------------------------------
+struct AisPlan {
+  bool reverse = false, admit = false;
+  int C = 0, T = 0, nc = 1;  // nc: the chunk count the kernel is instantiated for (1, 2, 4, 8, 16)
+  unsigned grid = 1;
+  size_t n_d = 0, n_i = 0, n_s = 0;  // elements of ais_d / ais_i / ais_s
+};
+
+static int ais_plan(const evoamd_ctx *c, int n_chains, int n_temps, const double *betas, unsigned flags, const uint64_t *s_start,
+                    int Mprime, AisPlan &p) {
+  REQUIRE(c && c->configured, "configure first");
+  REQUIRE(!(flags & ~(unsigned)(EVOAMD_AIS_REVERSE | EVOAMD_AIS_ADMIT)), "evoamd_ais_loglik: unknown flag");
+  if (!c->have_params) return fail(EVOAMD_E_INVALID, "evoamd_ais_loglik: no Theta installed (set parameters first)");
+  if (!c->have_data) return fail(EVOAMD_E_INVALID, "evoamd_ais_loglik: no data (upload data first)");
+  REQUIRE(c->model == EVOAMD_MODEL_BSC, "evoamd_ais_loglik: ES3C is not supported (a collapsed Gibbs step needs a bordered k x k "
+                                        "system per flip); the call is for EBSC");
+  REQUIRE(!c->f32, "evoamd_ais_loglik is not available in the float32 mode (ebsc_f32): the chains run on the double B = Y W");
+  REQUIRE(!c->bg_unit, "evoamd_ais_loglik: option background_unit is not supported (every latent is scanned)");
+  REQUIRE(!c->bsc_direct, "evoamd_ais_loglik: bsc_direct keeps no G = W^T W, whose rows the Gibbs scan reads");
+  REQUIRE(!c->mask_infr, "evoamd_ais_loglik: incomplete data (masks resident) is not supported: the chains need one G for all datapoints");
+  if (c->H > 64 * AIS_MAX_NC)
+    return fail(EVOAMD_E_INVALID, "evoamd_ais_loglik: H = %d, at most %d latents are supported (64 lanes x %d registers of c_j)", c->H,
+                64 * AIS_MAX_NC, AIS_MAX_NC);
+  if (n_chains < 1) return fail(EVOAMD_E_INVALID, "evoamd_ais_loglik: n_chains = %d must be positive", n_chains);
+  if (n_temps < 1) return fail(EVOAMD_E_INVALID, "evoamd_ais_loglik: n_temps = %d must be positive", n_temps);
+  REQUIRE(betas, "evoamd_ais_loglik: betas is NULL");
+  if (betas[0] != 0.0) return fail(EVOAMD_E_INVALID, "evoamd_ais_loglik: betas must start at 0 (betas[0] = %g)", betas[0]);
+  if (betas[n_temps] != 1.0)
+    return fail(EVOAMD_E_INVALID, "evoamd_ais_loglik: betas must end at 1 (betas[%d] = %g)", n_temps, betas[n_temps]);
+  for (int t = 1; t <= n_temps; t++)
+    if (!(betas[t] >= betas[t - 1]) || (t == 1 && !(betas[1] > 0.0)))
+      return fail(EVOAMD_E_INVALID, "evoamd_ais_loglik: betas must not descend and must leave 0 at once (betas[%d] = %g after %g)", t,
+                  betas[t], betas[t - 1]);
+  p.reverse = (flags & EVOAMD_AIS_REVERSE) != 0, p.admit = (flags & EVOAMD_AIS_ADMIT) != 0;
+  REQUIRE(!p.reverse || s_start, "evoamd_ais_loglik: EVOAMD_AIS_REVERSE needs s_start, the (N, HW) words of the starting states");
+  REQUIRE(!(p.reverse && p.admit), "evoamd_ais_loglik: EVOAMD_AIS_ADMIT with EVOAMD_AIS_REVERSE: a reverse chain ends at the prior, "
+                                   "its final states are no proposals for K^n");
+  if (p.admit) {
+    REQUIRE_KN(c);
+    TRY(estep_check_mprime(c, Mprime));
+  }
+  REQUIRE((i64)c->N * n_chains < 2147483647LL, "evoamd_ais_loglik: N * n_chains must fit in int32");
+  p.C = n_chains, p.T = n_temps;
+  while (p.nc < c->HW) p.nc <<= 1;
+  const size_t N = (size_t)c->N, NC = N * (size_t)n_chains;
+  p.grid = (unsigned)std::min<i64>(cdiv((i64)NC, AIS_WAVES), (i64)c->n_cu * 64);
+  p.n_d = (size_t)n_temps + 1 + NC + 7 * N;
+  p.n_i = NC;
+  p.n_s = NC * c->HW + N * c->HW;
+  return 0;
+}
+
+template <bool REV>
+static void ais_launch_chains(evoamd_ctx *c, const AisPlan &p, const AisArgs &a) {
+  const size_t lds = (size_t)(1 + AIS_WAVES) * 64 * c->HW * sizeof(double);  // G_jj, then B_n. per wavefront
+  switch (p.nc) {
+    case 1: ais_chain_kernel<1, REV><<<p.grid, 64 * AIS_WAVES, lds, c->stream>>>(a); break;
+    case 2: ais_chain_kernel<2, REV><<<p.grid, 64 * AIS_WAVES, lds, c->stream>>>(a); break;
+    case 4: ais_chain_kernel<4, REV><<<p.grid, 64 * AIS_WAVES, lds, c->stream>>>(a); break;
+    case 8: ais_chain_kernel<8, REV><<<p.grid, 64 * AIS_WAVES, lds, c->stream>>>(a); break;
+    default: ais_chain_kernel<AIS_MAX_NC, REV><<<p.grid, 64 * AIS_WAVES, lds, c->stream>>>(a); break;
+  }
+}
+
+// the views into the call's buffers
+struct AisBufs {
+  double *betas, *log_w, *ll, *ess, *lw_mean, *lw_min, *lw_max, *F_before, *F_after;
+  int *flips;
+  u64 *fin, *s_start;
+  i64 *n_flips;
+};
+static AisBufs ais_views(const evoamd_ctx *c, const AisPlan &p) {
+  const size_t N = (size_t)c->N, NC = N * (size_t)p.C;
+  AisBufs b;
+  b.betas = c->ais_d, b.log_w = b.betas + p.T + 1, b.ll = b.log_w + NC, b.ess = b.ll + N, b.lw_mean = b.ess + N;
+  b.lw_min = b.lw_mean + N, b.lw_max = b.lw_min + N, b.F_before = b.lw_max + N, b.F_after = b.F_before + N;
+  b.flips = c->ais_i;
+  b.fin = c->ais_s, b.s_start = b.fin + NC * c->HW;
+  b.n_flips = c->ais_nf;
+  return b;
+}
+
+// ---- stage: every buffer, before anything is launched
+static int ais_prepare(evoamd_ctx *c, const AisPlan &p) {
+  TRY(ensure_B(c));
+  TRY(c->ais_d.ensure(c, p.n_d));
+  TRY(c->ais_i.ensure(c, p.n_i));
+  TRY(c->ais_s.ensure(c, p.n_s));
+  TRY(c->ais_nf.ensure(c, (size_t)c->N));
+  return 0;
+}
+
+// ---- stage: the chains and the fold over them
+static int ais_chains_stage(evoamd_ctx *c, const AisPlan &p, const double *betas, uint64_t seed, uint64_t first_index,
+                            const uint64_t *s_start) {
+  const AisBufs b = ais_views(c, p);
+  HIP_TRY(hipMemcpyAsync(b.betas, betas, ((size_t)p.T + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (p.reverse)
+    HIP_TRY(hipMemcpyAsync(b.s_start, s_start, (size_t)c->N * c->HW * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+  AisArgs a = {};
+  a.Bm = c->Bm, a.yy = c->yy, a.G = c->G, a.Gd = c->diag, a.dpar = c->dpar;
+  a.betas = b.betas, a.s_start = p.reverse ? b.s_start : nullptr;
+  a.log_w = b.log_w, a.fin = b.fin, a.flips = b.flips, a.err = c->err;
+  a.N = c->N, a.C = p.C, a.T = p.T, a.H = c->H, a.HW = c->HW;
+  a.seed = seed, a.first_index = first_index;
+  SpanGuard g(c, KID_AIS);
+  if (p.reverse)
+    ais_launch_chains<true>(c, p, a);
+  else
+    ais_launch_chains<false>(c, p, a);
+  HIP_TRY(hipGetLastError());
+  DBG_SYNC(c, "ais chains");
+  ais_fold_kernel<<<cdiv(c->N, 256), 256, 0, c->stream>>>(b.log_w, b.flips, c->N, p.C, p.reverse ? 1 : 0, c->H, c->dpar, b.ll, b.ess,
+                                                          b.lw_mean, b.lw_min, b.lw_max, b.n_flips);
+  HIP_TRY(hipGetLastError());
+  DBG_SYNC(c, "ais fold");
+  return 0;
+}
+
+// ---- stage (admit): the final states as a candidate batch, their lpj from the model's own kernels, the selection --
+// the tail of a sweep; F before and after from posterior_score_kernel
+static int ais_admit_stage(evoamd_ctx *c, const AisPlan &p, int Mprime, double sums[2]) {
+  const AisBufs b = ais_views(c, p);
+  on_estep_route(c, /*fused=*/false);
+  TRY(estep_resident_pass(c));
+  posterior_score_kernel<<<cdiv(c->N, SCORE_WAVES), 64 * SCORE_WAVES, 0, c->stream>>>(c->lpj, c->states, c->N, c->L, c->S, c->S_perm,
+                                                                                      c->HW, b.F_before, nullptr, nullptr, nullptr, nullptr);
+  {
+    SpanGuard g(c, KID_AIS);
+    ais_admit_kernel<<<cdiv(c->N, 256), 256, 0, c->stream>>>(b.fin, c->N, p.C, c->HW, c->Cmax, c->cand,
+                                                             (c->use_digest && c->cand_dig) ? c->cand_dig.get() : nullptr, c->cand_counts);
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "ais admit");
+  }
+  on_cand_installed(c, /*near_parents=*/false);
+  TRY(eval_candidates(c));
+  made_cand_lpj(c);
+  TRY(estep_select(c, Mprime, sums));
+  posterior_score_kernel<<<cdiv(c->N, SCORE_WAVES), 64 * SCORE_WAVES, 0, c->stream>>>(c->lpj, c->states, c->N, c->L, c->S, c->S_perm,
+                                                                                      c->HW, b.F_after, nullptr, nullptr, nullptr, nullptr);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---- stage: the outputs, each where the caller gave a buffer; sum over the datapoints in their order
+static int ais_fetch(evoamd_ctx *c, const AisPlan &p, const evoamd_ais_out &o) {
+  const AisBufs b = ais_views(c, p);
+  const size_t N = (size_t)c->N, NC = N * (size_t)p.C;
+  std::vector<double> ll(N);
+  HIP_TRY(hipMemcpyAsync(ll.data(), b.ll, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (o.ess) HIP_TRY(hipMemcpyAsync(o.ess, b.ess, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (o.log_w_mean) HIP_TRY(hipMemcpyAsync(o.log_w_mean, b.lw_mean, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (o.log_w_min) HIP_TRY(hipMemcpyAsync(o.log_w_min, b.lw_min, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (o.log_w_max) HIP_TRY(hipMemcpyAsync(o.log_w_max, b.lw_max, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (o.n_flips) HIP_TRY(hipMemcpyAsync(o.n_flips, b.n_flips, N * sizeof(i64), hipMemcpyDeviceToHost, c->stream));
+  if (o.log_w) HIP_TRY(hipMemcpyAsync(o.log_w, b.log_w, NC * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (o.final_words) HIP_TRY(hipMemcpyAsync(o.final_words, b.fin, NC * c->HW * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  if (o.chain_flips) HIP_TRY(hipMemcpyAsync(o.chain_flips, b.flips, NC * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (p.admit && o.F_before) HIP_TRY(hipMemcpyAsync(o.F_before, b.F_before, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (p.admit && o.F_after) HIP_TRY(hipMemcpyAsync(o.F_after, b.F_after, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->h_err, c->err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->h_err[0] & EVO_ERR_BAD_ENTRY) {  // guard_index replaced a latent index that was out of range
+    HIP_TRY(hipMemsetAsync(c->err, 0, sizeof(int), c->stream));
+    return fail(EVOAMD_E_INVALID, "internal: evoamd_ais_loglik: a latent index of a chain was out of range");
+  }
+  if (o.ll) memcpy(o.ll, ll.data(), N * sizeof(double));
+  if (o.sum) {
+    double s = 0.0;
+    for (size_t n = 0; n < N; n++) s += ll[n];
+    o.sum[0] = s;
+  }
+  return 0;
+}
+
+extern "C" int evoamd_ais_loglik(evoamd_ctx *c, int n_chains, int n_temps, const double *betas, uint64_t seed, uint64_t first_index,
+                                 unsigned flags, const uint64_t *s_start, int Mprime, const evoamd_ais_out *out) {
+  AisPlan p;
+  TRY(ais_plan(c, n_chains, n_temps, betas, flags, s_start, Mprime, p));
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(ais_prepare(c, p));
+  TRY(ais_chains_stage(c, p, betas, seed, first_index, s_start));
+  const evoamd_ais_out o = out ? *out : evoamd_ais_out{};
+  double sums[2] = {0.0, 0.0};
+  if (p.admit) {
+    TRY(ais_admit_stage(c, p, Mprime, sums));
+    if (o.admit_sums) o.admit_sums[0] = sums[0], o.admit_sums[1] = sums[1];
+  }
+  return ais_fetch(c, p, o);
+}
+
 // posterior samples (kernels_posterior_sample.hpp): own buffers; of the EM state only B = Y W is (re)formed, like every lpj pass
 // ---------------------------------------------------------------------------------------
 template <bool SSSC>
@@ -6990,6 +7199,7 @@ extern "C" const char *evoamd_kernel_name(int kid) {
                                          "patches",      "init_states",    "posterior_sample", "seed_states",
                                          "loglik_proposal", "loglik_lpj",  "loglik_fold",     "remap_latents",
                                          "stats_kappa",  "sweep",       "sweep_swap",      "resize",
-                                         "neighbour_bound", "predictive_score"};
+                                         "neighbour_bound", "predictive_score",
+                                         "ais"};
   return (kid >= 0 && kid < KID_COUNT) ? names[kid] : "?";
 }

@@ -469,6 +469,62 @@ class Engine:
         res["sum"], res["count"] = float(total[0]), int(total[1])
         return res
 
+    def ais_loglik(self, betas, n_chains=16, seed=0, first_index=0, reverse=False, s_start=None, keep_states=False,
+                   admit=False, Mprime=1):
+        """Annealed importance sampling under the Theta and data on the device (evoamd_ais_loglik; csrc/kernels_ais.hpp
+        has the law, evo_amd.models.ais_log_likelihood_counter is the NumPy mirror).  ``betas``: the float64 schedule of
+        T + 1 values from 0 to 1.  Returns a dict of (N,) arrays "ll" (forward: a lower bound on log p(y_n) - ljc in
+        expectation; ``reverse``: an upper bound, provided row n of ``s_start`` (bool (N, H)) is an exact posterior
+        sample), "ess", "log_w_mean", "log_w_min", "log_w_max", "n_flips" (int64) and the scalar "sum" of ll;
+        ``keep_states`` adds "log_w" (N, C), "final" (uint8, N x C x ceil(H / 8), np.packbits layout) and "chain_flips"
+        (int32 (N, C)); ``admit`` (forward only) runs the final states of the first min(C, Cmax) chains through the
+        candidate lpj kernels and the selection with ``Mprime`` and adds "F_before", "F_after" (N,) and the scalars
+        "S_nunique" and "S_sub" (sums over the datapoints, as vary_kn).  Without ``admit`` K^n, lpj, the candidate batch
+        and the statistics rows are not written.  EvoAmdError naming the rule, before anything is written, for ES3C, the
+        float32 mode, the background unit, bsc_direct, masks resident, H > 1024, n_chains < 1, betas that do not start at
+        0, end at 1 or that descend, reverse without s_start and admit with reverse."""
+        from .models.generate import pack_words
+        betas = np.ascontiguousarray(betas, dtype=np.float64)
+        if betas.ndim != 1 or betas.size < 2:
+            raise ValueError("betas must be a 1-d array of T + 1 >= 2 values")
+        N, H, C, T = self.N, self.H, int(n_chains), betas.size - 1
+        HW = (H + 63) // 64
+        words = None
+        if s_start is not None:
+            s_start = np.asarray(s_start)
+            if s_start.shape != (N, H) or s_start.dtype != np.bool_:
+                raise ValueError("s_start must be a bool array of shape (N, H)")
+            words = pack_words(s_start)
+        res = {name: np.empty(N, dtype=np.float64) for name in ("ll", "ess", "log_w_mean", "log_w_min", "log_w_max")}
+        res["n_flips"] = np.empty(N, dtype=np.int64)
+        total, sums = np.zeros(1), np.zeros(2)
+        out = _lib.AisOut()
+        for name in ("ll", "ess", "log_w_mean", "log_w_min", "log_w_max"):
+            setattr(out, name, dptr(res[name]))
+        out.n_flips = res["n_flips"].ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        out.sum = dptr(total)
+        fin = None
+        if keep_states and C >= 1:
+            res["log_w"] = np.empty((N, C))
+            res["chain_flips"] = np.empty((N, C), dtype=np.int32)
+            fin = np.empty((N * C, HW), dtype=np.uint64)
+            out.log_w, out.chain_flips = dptr(res["log_w"]), i32ptr(res["chain_flips"])
+            out.final_words = fin.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        if admit:
+            res["F_before"], res["F_after"] = np.empty(N), np.empty(N)
+            out.F_before, out.F_after, out.admit_sums = dptr(res["F_before"]), dptr(res["F_after"]), dptr(sums)
+        flags = (_lib.AIS_REVERSE if reverse else 0) | (_lib.AIS_ADMIT if admit else 0)
+        check(self.lib.evoamd_ais_loglik(
+            self._h, C, T, dptr(betas), int(seed) & (2 ** 64 - 1), int(first_index) & (2 ** 64 - 1), flags,
+            None if words is None else words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), int(Mprime), ctypes.byref(out)))
+        if fin is not None:  # the MSB-first words as bytes are the np.packbits layout
+            nb = (H + 7) // 8
+            res["final"] = np.ascontiguousarray(fin.astype(">u8").view(np.uint8).reshape(N * C, HW * 8)[:, :nb]).reshape(-1)
+        if admit:
+            res["S_nunique"], res["S_sub"] = float(sums[0]), float(sums[1])
+        res["sum"] = float(total[0])
+        return res
+
     SCORES = ("F", "entropy", "best", "k_best", "k_mean")
 
     def posterior_scores(self, what=SCORES):

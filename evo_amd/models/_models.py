@@ -1345,6 +1345,85 @@ class Model:
         info["n_bad_weights"] = int(np.isnan(info["F"]).sum())
         return L, info
 
+    def ais_log_likelihood(self, model_params, my_suff_stat, my_data, n_chains=16, n_temps=128, betas=None, seed=None,
+                           first_index=0, direction="forward", s_start=None, per_datapoint=False, keep_states=False,
+                           admit=False):
+        """Annealed importance sampling (Neal 2001): bounds on the log-likelihood that do not depend on K^n, for EBSC on
+        complete data (Engine.ais_loglik; csrc/kernels_ais.hpp has the law, evo_amd.models.ais_log_likelihood_counter is
+        the NumPy mirror).  Per datapoint ``n_chains`` Gibbs chains walk through the temperatures ``betas`` (a float64
+        array of T + 1 values from 0 to 1 that never descends; None: the sigmoid schedule of ``n_temps`` steps,
+        evo_amd.models.sigmoid_schedule) between the prior and the posterior, one systematic scan over the latents per
+        temperature.  ``direction="forward"``: from a prior draw; the mean of the chains' weights is an unbiased estimate
+        of p(y_n), so ll_n is a stochastic LOWER bound (E[ll_n] <= log p(y_n) - ljc).  ``direction="reverse"``: from row n
+        of ``s_start`` (bool (N, H)) back to the prior; ll_n is a stochastic UPPER bound (bidirectional Monte Carlo) --
+        it is an exact posterior sample only when y_n was generated from this Theta with that s: for synthetic data, the
+        "s" that generate_data_device returns.  For any other start the reverse value bounds nothing.  Returns L = ljc +
+        allreduce(sum_n ll_n) / N, the convention of estimate_log_likelihood; with ``per_datapoint``, (L, info) with the
+        (N_loc,) arrays "ll", "ess" (of the averaged terms: w forward, 1 / w reverse), "log_w_mean", "log_w_min",
+        "log_w_max" and "n_flips" (int64, the accepted flips of all chains); ``keep_states`` adds "log_w" (N, C), "final"
+        (the chains' last states, uint8, N x C x ceil(H / 8) in np.packbits layout) and "chain_flips" (N, C).  The final
+        states of forward chains are approximate posterior samples: ``admit=True`` (forward only) puts those of the first
+        min(C, Cmax) chains into the candidate batch in chain order (the all-zero state skipped), evaluates them with
+        the model's own lpj kernels and runs the usual selection with my_suff_stat["Mprime"]; info gains "S_sub" (the
+        substitutions, normalised like E_step's), "F_before" and "F_after" (N_loc,), and with sync_host K^n and lpj are
+        copied back.  Without ``admit`` K^n, lpj, the candidate batch and the statistics rows stay as they are.  The
+        stream is counter-based (``self.last_ais_seed``): datapoint n is index ``first_index + n`` of the data set, so
+        shards concatenate to the single call, and chain c does not depend on ``n_chains``.  ``seed`` None: drawn from
+        np.random; rank and world size enter it as in sample_posterior.  NotImplementedError for ES3C; ValueError for the
+        float32 mode, the background unit, incomplete data, H > 1024, n_chains < 1, betas that do not start at 0, end at
+        1 or that descend, reverse without an ``s_start`` of shape (N, H) bool, and admit with reverse.  One all-reduce."""
+        from .ais import AIS_MAX_H, check_betas, sigmoid_schedule
+        if self.model_name != "bsc":
+            raise NotImplementedError("ais_log_likelihood is for EBSC: ES3C is out of scope (its importance estimate works, "
+                                      "and a collapsed Gibbs step would need a bordered k x k system per flip)")
+        if self.dtype == np.float32:
+            raise ValueError("ais_log_likelihood is not available in the float32 mode")
+        if my_suff_stat["permanent"]["background"]:
+            raise ValueError("ais_log_likelihood: the background unit is not supported")
+        if not self._complete(my_data):
+            raise ValueError("ais_log_likelihood: incomplete data (x_infr with False entries) is not supported")
+        if self.H > AIS_MAX_H:
+            raise ValueError("ais_log_likelihood: H = %d, at most %d latents are supported" % (self.H, AIS_MAX_H))
+        C = int(n_chains)
+        if C < 1:
+            raise ValueError("ais_log_likelihood: n_chains = %d must be positive" % C)
+        betas = sigmoid_schedule(n_temps) if betas is None else check_betas(betas)
+        if direction not in ("forward", "reverse"):
+            raise ValueError("ais_log_likelihood: direction = %r must be 'forward' or 'reverse'" % (direction,))
+        reverse = direction == "reverse"
+        N = my_data["y"].shape[0]
+        if reverse:
+            if s_start is None or np.shape(s_start) != (N, self.H) or np.asarray(s_start).dtype != np.bool_:
+                raise ValueError("ais_log_likelihood: direction='reverse' needs s_start, a bool array of shape (N, H) = (%d, %d)"
+                                 % (N, self.H))
+            if admit:
+                raise ValueError("ais_log_likelihood: admit=True with direction='reverse': a reverse chain ends at the prior, "
+                                 "its final states are no proposals for K^n")
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+        self.last_ais_seed = (int(seed) * max(1, self.comm.size) + self.comm.rank) & (2 ** 64 - 1)
+        yr = my_data.get("y_reconstructed")
+        if isinstance(yr, ResidentReconstruction) and yr.resident and not yr.materialised:
+            yr.rows()  # setting the parameters below drops the device copy of an unread reconstruction: fetch it first
+        eng = self._prepare(my_suff_stat, my_data, upload_states=bool(admit))  # (the chains read no K^n)
+        theta = dict(model_params)  # (the precompute stores its derived keys and zeroes the reset counters: on copies)
+        self.E_step_precompute(theta, dict(my_suff_stat), my_data)
+        if model_params is not self._dev_theta:
+            self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
+        info = eng.ais_loglik(betas, C, self.last_ais_seed, first_index, reverse=reverse, s_start=s_start if reverse else None,
+                              keep_states=bool(keep_states), admit=bool(admit),
+                              Mprime=my_suff_stat["Mprime"] if admit else 1)
+        red = _reduce_array(self.comm, np.array([info.pop("sum"), float(N), info.pop("S_sub", 0.0)]))  # (the one all-reduce)
+        L = theta["ljc"] + red[0] / red[1]
+        if admit:
+            info.pop("S_nunique")
+            info["S_sub"] = red[2] / red[1]
+            if self.sync_host:
+                self.sync_to_host(my_suff_stat)
+        if per_datapoint or keep_states or admit:
+            return L, info
+        return L
+
     def reconstruct(self, my_data, my_suff_stat, model_params):
         """(Re-)estimate the entries with my_data["x"] False from the posterior predictive distribution under
         ``model_params`` and the caller's K^n / lpj; adds my_data["y_reconstructed"] (_models.py:614-665).

@@ -1,0 +1,208 @@
+"""Annealed importance sampling for EBSC: the NumPy mirror of Model.ais_log_likelihood (csrc/kernels_ais.hpp, which states
+the law).  Host only: it never touches the engine.
+
+Per datapoint n (data set index i = first_index + n), chain c < C and temperatures 0 = beta_0 < beta_1 <= ... <= beta_T = 1,
+with f_beta(s) = exp(|s| pil_bar + beta l(s)), l(s) = pre1 (yy_n - sum_{a in s} (B_na + c_a)), c_j = B_nj - sum_{i in s} G_ij:
+
+    start     forward: x_0,h = [u01(x0, AIS_PURPOSE + c, h) < pi], an exact draw from f_0 / Z_0, Z_0 = (1 - pi)^-H;
+              reverse: x_{T-1} = row n of s_start, the same for every chain
+    K_t       one systematic Gibbs scan at beta_t over h ascending (forward) or descending (reverse): Delta = pil_bar +
+              (beta_t pre1) (G_hh - 2 c_h) with h off, pil_bar - (beta_t pre1) (G_hh + 2 c_h) with h on, p = 1 / (1 + exp(-Delta)),
+              new bit = [u01(x0, AIS_PURPOSE + c, (t + 1) H + h) < p]; on a change c_j -= G_hj (switched on) or += G_hj (off)
+    forward   for t = 1 .. T: log w += (beta_t - beta_{t-1}) l(x_{t-1}); for t < T: x_t = K_t(x_{t-1}); one more scan at
+              beta_T (uniform block T + 1) gives ``final``
+    reverse   for t = T - 1 .. 1: x_{t-1} = K~_t(x_t); log w = sum_t (beta_t - beta_{t-1}) l(x_{t-1}), t = T first; final = x_0
+    estimate  a_c = log w_c (forward) / -log w_c (reverse) folded in chain order; forward ll = logsumexp(a) - log C + H
+              log1p(exp(pil_bar)) (E[ll] <= log p(y_n) - ljc), reverse ll = -(logsumexp(a) - log C) + H log1p(exp(pil_bar)) (E[ll]
+              >= log p(y_n) - ljc IF s_start[n] is an exact posterior sample: y_n generated from this Theta with that s);
+              ess = (sum e^a)^2 / sum e^{2 a}
+
+The mirror scans h sequentially; the kernel settles a chunk of 64 latents by ballots, which gives the same decisions.  The
+operations are the kernel's in the kernel's order (separate NumPy operations, no fused forms).  ``final``, ``n_flips`` and
+the starting draw are bit-level wherever no decision is closer to its uniform than the rounding of B, G and exp (``margin``
+says how close the closest was); the real-valued outputs are formula-level.
+"""
+import numpy as np
+
+from ..variational.utils import _M64, _mix64
+from .generate import _first_hash
+
+AIS_PURPOSE = 0x4149530000000000  # "AIS"
+AIS_MAX_H = 1024
+
+
+def sigmoid_schedule(n_temps, delta=4.0):
+    """beta_t = (sigma(delta (2 t / T - 1)) - sigma(-delta)) / (sigma(delta) - sigma(-delta)), t = 0 .. T (Grosse et al.), the
+    ends set to exactly 0 and 1."""
+    T = int(n_temps)
+    if T < 1:
+        raise ValueError("n_temps must be positive")
+    sig = lambda x: 1.0 / (1.0 + np.exp(-x))  # noqa: E731
+    t = np.arange(T + 1, dtype=np.float64)
+    betas = (sig(delta * (2.0 * t / T - 1.0)) - sig(-delta)) / (sig(delta) - sig(-delta))
+    betas[0], betas[-1] = 0.0, 1.0
+    return betas
+
+
+def check_betas(betas):
+    """The schedule as a float64 array, or ValueError naming the rule it breaks."""
+    b = np.ascontiguousarray(betas, dtype=np.float64)
+    if b.ndim != 1 or b.size < 2:
+        raise ValueError("ais: betas must be a 1-d array of T + 1 >= 2 values")
+    if b[0] != 0.0:
+        raise ValueError("ais: betas must start at 0 (betas[0] = %g)" % b[0])
+    if b[-1] != 1.0:
+        raise ValueError("ais: betas must end at 1 (betas[-1] = %g)" % b[-1])
+    if not np.all(b[1:] >= b[:-1]) or not b[1] > 0.0:
+        raise ValueError("ais: betas must not descend and must leave 0 at once")
+    return b
+
+
+def ais_scalars(theta):
+    """(pre1, pil_bar, pi) of an EBSC Theta, as E_step_precompute forms them."""
+    pi, sigma = float(theta["pi"]), float(theta["sigma"])
+    return -1.0 / 2.0 / sigma / sigma, float(np.log(pi / (1.0 - pi))), pi
+
+
+def ais_conditional(pre1, pil_bar, c_h, G_hh, on, beta):
+    """p(s_h = 1 | the other latents) under f_beta, from c_h = B_nh - sum_{i in s} G_ih of the CURRENT state (h included
+    when it is on).  Scalars, or arrays over chains for c_h and on."""
+    bp = beta * pre1
+    two_c = 2.0 * np.asarray(c_h, dtype=np.float64)
+    t_on = bp * (G_hh + two_c)
+    t_off = bp * (G_hh - two_c)
+    delta = np.where(on, pil_bar - t_on, pil_bar + t_off)
+    with np.errstate(over="ignore"):
+        return 1.0 / (1.0 + np.exp(-delta))
+
+
+def _ell(pre1, yy, Bn, c, s):
+    """l(s) for every chain: s bool (C, H), c (C, H); the sum runs over the active a in ascending order."""
+    total = np.zeros(s.shape[0])
+    for a in np.flatnonzero(s.any(axis=0)):
+        total = np.where(s[:, a], total + (Bn[a] + c[:, a]), total)
+    return pre1 * (yy - total)
+
+
+def _u01_chains(x0, C, index):
+    """u01(x0, AIS_PURPOSE + c, index) for c < C: x0 (1, 1), index uint64 (k,) -> float64 (C, k)."""
+    salt = np.array([((AIS_PURPOSE + c) * 0xd1b54a32d192ed03 + 0x632be59bd9b4e019) & _M64 for c in range(C)], dtype=np.uint64)
+    x = _mix64(x0[0, 0] ^ (salt[:, None] + index[None, :]))
+    return ((x >> np.uint64(11)).astype(np.float64) + 0.5) * (1.0 / 9007199254740992.0)
+
+
+def _fold(a):
+    """(logsumexp, ess) of a_0, a_1, ... folded in order, the maximum rescaled when it grows."""
+    m, z, q = -np.inf, 0.0, 0.0
+    for t in a:
+        if t > m:
+            r = np.exp(m - t)
+            z = z * r + 1.0
+            q = q * (r * r) + 1.0
+            m = t
+        else:
+            e = np.exp(t - m)
+            z = z + e
+            q = q + e * e
+    return m + np.log(z), z * z / q
+
+
+def ais_log_likelihood_counter(theta, Y, n_chains=16, n_temps=128, betas=None, seed=0, first_index=0, direction="forward",
+                               s_start=None, B=None, G=None):
+    """What Model.ais_log_likelihood returns in ``info`` with per_datapoint=True and keep_states=True, for stream seed
+    ``seed`` (``model.last_ais_seed``): the (N,) arrays "ll", "ess", "log_w_mean", "log_w_min", "log_w_max", "n_flips"
+    (int64), "log_w" (N, C), "final" (uint8, N x C x ceil(H / 8), np.packbits layout), and beside them "final_bool" (N, C,
+    H), "start" (the starting states, bool (N, C, H)), "margin" (N, C) = the minimum over all decisions of the chain of
+    |u - p| (the starting draw: |u - pi|) and "sum" = the sum of ll.  ``theta``: an EBSC Theta with "W" (D, H), "pi",
+    "sigma"; ``Y`` (N, D) complete data; ``B`` / ``G``: Y W and W^T W when the caller has them (else formed here)."""
+    if direction not in ("forward", "reverse"):
+        raise ValueError("ais: direction must be 'forward' or 'reverse'")
+    rev = direction == "reverse"
+    C = int(n_chains)
+    if C < 1:
+        raise ValueError("ais: n_chains must be positive")
+    betas = sigmoid_schedule(n_temps) if betas is None else check_betas(betas)
+    T = betas.size - 1
+    W = np.asarray(theta["W"], dtype=np.float64)
+    Y = np.asarray(Y, dtype=np.float64)
+    N, H = Y.shape[0], W.shape[1]
+    if H > AIS_MAX_H:
+        raise ValueError("ais: H = %d, at most %d latents are supported" % (H, AIS_MAX_H))
+    if rev:
+        if s_start is None or np.shape(s_start) != (N, H) or np.asarray(s_start).dtype != np.bool_:
+            raise ValueError("ais: direction='reverse' needs s_start, a bool array of shape (N, H)")
+        s_start = np.asarray(s_start)
+    pre1, pilb, pi = ais_scalars(theta)
+    B = np.dot(Y, W) if B is None else np.asarray(B, dtype=np.float64)
+    G = np.dot(W.T, W) if G is None else np.asarray(G, dtype=np.float64)
+    yy = (Y * Y).sum(axis=1)
+    Gd = np.diag(G).copy()
+    seed, first_index = int(seed) & _M64, int(first_index) & _M64
+    hs = np.arange(H, dtype=np.uint64)
+    out = {"log_w": np.empty((N, C)), "final_bool": np.zeros((N, C, H), dtype=bool), "start": np.zeros((N, C, H), dtype=bool),
+           "margin": np.full((N, C), np.inf), "n_flips": np.zeros(N, dtype=np.int64)}
+    for name in ("ll", "ess", "log_w_mean", "log_w_min", "log_w_max"):
+        out[name] = np.empty(N)
+    chain_flips = np.zeros((N, C), dtype=np.int64)
+    lz0 = H * np.log1p(np.exp(pilb))
+
+    def scan(s, c, beta, u, order, flips, margin):
+        """One scan of all chains in place: s bool (C, H), c (C, H), u (C, H); flips and margin (C,) are updated."""
+        for h in order:
+            on = s[:, h].copy()
+            p = ais_conditional(pre1, pilb, c[:, h], Gd[h], on, beta)
+            np.minimum(margin, np.abs(u[:, h] - p), out=margin)
+            nb = u[:, h] < p
+            up, down = nb & ~on, on & ~nb
+            if up.any():
+                c[up] = c[up] - G[h]     # (one subtraction per j)
+            if down.any():
+                c[down] = c[down] + G[h]
+            s[:, h] = nb
+            flips += up | down
+
+    fwd, bwd = range(H), range(H - 1, -1, -1)
+    with np.errstate(over="ignore"):  # the hashes wrap mod 2^64
+        for n in range(N):
+            x0 = _first_hash(seed, np.array([(first_index + n) & _M64], dtype=np.uint64))
+            block = lambda b: _u01_chains(x0, C, np.uint64(b * H) + hs)  # noqa: E731  (uniform block b: indices b H .. b H + H - 1)
+            margin = np.full(C, np.inf)
+            flips = np.zeros(C, dtype=np.int64)
+            if rev:
+                s = np.repeat(s_start[n][None, :], C, axis=0)
+            else:
+                u = block(0)
+                s = u < pi
+                margin = np.abs(u - pi).min(axis=1)
+            out["start"][n] = s
+            c = np.repeat(B[n][None, :], C, axis=0)
+            for i in np.flatnonzero(s.any(axis=0)):
+                c[s[:, i]] = c[s[:, i]] - G[i]
+            if not rev:
+                lw = np.zeros(C)
+                for t in range(1, T + 1):  # (the scan of t = T gives ``final``)
+                    lw = lw + (betas[t] - betas[t - 1]) * _ell(pre1, yy[n], B[n], c, s)
+                    scan(s, c, betas[t], block(t + 1), fwd, flips, margin)
+            else:
+                lw = (betas[T] - betas[T - 1]) * _ell(pre1, yy[n], B[n], c, s)
+                for t in range(T - 1, 0, -1):
+                    scan(s, c, betas[t], block(t + 1), bwd, flips, margin)
+                    lw = lw + (betas[t] - betas[t - 1]) * _ell(pre1, yy[n], B[n], c, s)
+            out["log_w"][n] = lw
+            out["final_bool"][n] = s
+            out["margin"][n] = margin
+            chain_flips[n] = flips
+            lse, ess = _fold(-lw if rev else lw)
+            lse = lse - np.log(float(C))
+            out["ll"][n] = (-lse if rev else lse) + lz0
+            out["ess"][n] = ess
+            total = 0.0
+            for v in lw:
+                total = total + v
+            out["log_w_mean"][n] = total / float(C)
+            out["log_w_min"][n], out["log_w_max"][n] = lw.min(), lw.max()
+    out["n_flips"] = chain_flips.sum(axis=1)
+    out["chain_flips"] = chain_flips
+    out["final"] = np.packbits(out["final_bool"], axis=-1).reshape(-1)
+    out["sum"] = float(np.sum(out["ll"]))
+    return out

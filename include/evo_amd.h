@@ -501,6 +501,47 @@ typedef struct evoamd_nbound_out {
 } evoamd_nbound_out;
 int evoamd_neighbour_bound(evoamd_ctx *ctx, int n_parents, unsigned flags, const evoamd_nbound_out *out);
 
+/* Annealed importance sampling: stochastic lower and upper bounds on log p(y_n) - ljc that do not depend on K^n
+ * (csrc/kernels_ais.hpp has the law; evo_amd.models.ais_log_likelihood_counter is the NumPy mirror).  EBSC on complete data.
+ * Per datapoint n_chains Gibbs chains of n_temps temperatures, one wavefront per (datapoint, chain); betas: the float64
+ * schedule of n_temps + 1 values, 0 = betas[0] < betas[1] <= ... <= betas[n_temps] = 1 (host); seed / first_index: the
+ * counter stream of evoamd_generate (datapoint n is index first_index + n of the data set; chain c draws under purpose
+ * AIS_PURPOSE + c, one uniform per (c, t, h): chain c does not depend on n_chains, shards concatenate).
+ * flags: 0 = forward chains from the prior (ll: a lower bound in expectation); EVOAMD_AIS_REVERSE = chains from s_start
+ * back to the prior (ll: an upper bound in expectation, PROVIDED row n of s_start is an exact posterior sample, which it is
+ * only when y_n was generated from this Theta with that s); s_start: (N, ceil(H / 64)) words in the layout of K^n (host).
+ * EVOAMD_AIS_ADMIT (forward only): the final states of the first min(n_chains, Cmax) chains become the candidate batch in
+ * chain order, the all-zero state skipped, digests written where in use; the model's candidate lpj kernels evaluate them
+ * and the selection (vary_kn with Mprime) runs -- the tail of a sweep; the resident rows are evaluated first, as a sweep
+ * does at entry.  Without it K^n, lpj, the candidate batch and the statistics rows are not written (Mprime is not read).
+ * Outputs (host; each pointer and out itself may be NULL): ll, ess, log_w_mean, log_w_min, log_w_max (N doubles), n_flips
+ * (N int64, the accepted flips of all chains), log_w (N, n_chains), final_words (N, n_chains, ceil(H / 64)) in the layout
+ * of K^n, chain_flips (N, n_chains: the accepted flips of each chain), sum (1) = the sum of ll in datapoint order; with EVOAMD_AIS_ADMIT F_before / F_after (N, the bound of K^n without
+ * ljc around the selection) and admit_sums (2) = {sum of the new unique states, sum of the substitutions}, as evoamd_vary_kn.
+ * Deterministic: two calls give the same bits.  EVOAMD_E_INVALID before anything is written, each with its own text: an
+ * unknown flag; no Theta or data; ES3C; the float32 mode (ebsc_f32); background_unit; bsc_direct; masks resident; H > 1024;
+ * n_chains < 1; n_temps < 1; betas NULL, not starting at 0, not ending at 1, or descending; EVOAMD_AIS_REVERSE without
+ * s_start; EVOAMD_AIS_ADMIT with EVOAMD_AIS_REVERSE, without K^n or with Mprime outside [1, S]. */
+#define EVOAMD_AIS_REVERSE 1u
+#define EVOAMD_AIS_ADMIT 2u
+typedef struct evoamd_ais_out {
+  double *ll;            /* (N) */
+  double *ess;           /* (N) */
+  double *log_w_mean;    /* (N) */
+  double *log_w_min;     /* (N) */
+  double *log_w_max;     /* (N) */
+  int64_t *n_flips;      /* (N) */
+  double *log_w;         /* (N, n_chains) */
+  uint64_t *final_words; /* (N, n_chains, ceil(H / 64)) */
+  int32_t *chain_flips;  /* (N, n_chains) */
+  double *F_before;      /* (N), EVOAMD_AIS_ADMIT */
+  double *F_after;       /* (N), EVOAMD_AIS_ADMIT */
+  double *admit_sums;    /* (2), EVOAMD_AIS_ADMIT */
+  double *sum;           /* (1) */
+} evoamd_ais_out;
+int evoamd_ais_loglik(evoamd_ctx *ctx, int n_chains, int n_temps, const double *betas, uint64_t seed, uint64_t first_index,
+                      unsigned flags, const uint64_t *s_start, int Mprime, const evoamd_ais_out *out);
+
 /* Per-datapoint scores of the lpj rows and K^n resident on the device (after a seed, an upload or any pass), each output
  * (N) or NULL.  With m = max_s lpj_ns, w_s = exp(lpj_ns - m), z = sum_s w_s over the S_perm + S columns:
  * F_out = m + log z (the bound per datapoint without ljc, the counterpart of ll_out of evoamd_loglik_exact);
@@ -1043,7 +1084,8 @@ enum {
   EVOAMD_K_RESIZE = 32,        /* evoamd_resize_states: the resize kernel (downloads excluded) */
   EVOAMD_K_NBOUND = 33,        /* evoamd_neighbour_bound: the neighbourhood kernel (ES3C: with the transpose of GP) and the bound of the rows */
   EVOAMD_K_PRED_SCORE = 34,    /* evoamd_predictive_score: the transpose of W, the visit list, the score kernel, its partials and their reductions */
-  EVOAMD_K_COUNT = 35
+  EVOAMD_K_AIS = 35,           /* evoamd_ais_loglik: the chain kernel, the fold over the chains and (admit) the emission */
+  EVOAMD_K_COUNT = 36
 };
 /* on = bit mask of kernel classes to time (bit k = class k; -1 = all, 0 = off).  Each timed span
  * records two HIP events on the compute stream, which costs about 10 us of stream time per span:
