@@ -60,7 +60,7 @@ KERNEL_IDS = {
 # therefore stays as it is); Engine.timing / Engine.kernel_time_ms take names of either table
 KERNEL_IDS_EXTRA = {"posterior_sample": 23, "seed_states": 24, "loglik_proposal": 25, "loglik_lpj": 26, "loglik_fold": 27,
                     "remap_latents": 28, "stats_kappa": 29, "sweep": 30, "sweep_swap": 31, "resize": 32,
-                    "neighbour_bound": 33, "predictive_score": 34, "ais": 35}
+                    "neighbour_bound": 33, "predictive_score": 34, "ais": 35, "ais_post": 36}
 
 
 def kernel_id(name):
@@ -92,6 +92,14 @@ class AisOut(ctypes.Structure):
     _fields_ = [("ll", _c_dp), ("ess", _c_dp), ("log_w_mean", _c_dp), ("log_w_min", _c_dp), ("log_w_max", _c_dp),
                 ("n_flips", ctypes.POINTER(ctypes.c_int64)), ("log_w", _c_dp), ("final_words", _c_u64p), ("chain_flips", _c_i32p),
                 ("F_before", _c_dp), ("F_after", _c_dp), ("admit_sums", _c_dp), ("sum", _c_dp)]
+
+
+class AisPostOut(ctypes.Structure):
+    """evoamd_ais_post_out: the outputs of evoamd_ais_posterior, each pointer may be NULL."""
+    _fields_ = [("p", _c_dp), ("p_se", _c_dp), ("count", _c_dp), ("map_lpj", _c_dp), ("map_state", _c_u64p), ("ll", _c_dp),
+                ("ess", _c_dp), ("log_w_mean", _c_dp), ("log_w_min", _c_dp), ("log_w_max", _c_dp),
+                ("n_flips", ctypes.POINTER(ctypes.c_int64)), ("mean", _c_dp), ("log_w", _c_dp), ("rb", _c_dp),
+                ("chain_map_lpj", _c_dp), ("chain_map_state", _c_u64p), ("chain_flips", _c_i32p)]
 
 
 class PredScoreOut(ctypes.Structure):
@@ -170,6 +178,7 @@ SIGNATURES = {
                                     ctypes.POINTER(SweepOut)]),
     "evoamd_neighbour_bound": (_I, [_vp, _I, ctypes.c_uint, ctypes.POINTER(NboundOut)]),
     "evoamd_ais_loglik": (_I, [_vp, _I, _I, _c_dp, _U64, _U64, ctypes.c_uint, _c_u64p, _I, ctypes.POINTER(AisOut)]),
+    "evoamd_ais_posterior": (_I, [_vp, _I, _I, _I, _c_dp, _U64, _U64, _I64, ctypes.POINTER(AisPostOut)]),
     "evoamd_posterior_scores": (_I, [_vp, _c_dp, _c_dp, _c_i32p, _c_i32p, _c_dp]),
     "evoamd_remap_latents": (_I, [_vp, _c_i32p, _I, _c_i32p, ctypes.POINTER(_I64)]),
     "evoamd_adopt_remapped_states": (_I, [_vp]),

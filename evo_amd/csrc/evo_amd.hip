@@ -43,6 +43,7 @@
 #include "kernels_sweep_swap.hpp"
 #include "kernels_nbound.hpp"
 #include "kernels_ais.hpp"
+#include "kernels_ais_post.hpp"
 
 // ---------------------------------------------------------------------------------------
 // error handling
@@ -176,6 +177,7 @@ enum {  // internal kernel ids (see evoamd_kernel_name)
   KID_NBOUND,        // evoamd_neighbour_bound: the neighbourhood kernel (ES3C: with the transpose of GP) and the bound of the rows
   KID_PRED_SCORE,    // evoamd_predictive_score: the transpose of W, the visit list, the score kernel, its partials and their two reductions
   KID_AIS,           // evoamd_ais_loglik: the chain kernel and the fold over the chains (admit: the emission; its lpj and selection count in their own classes)
+  KID_AIS_POST,      // evoamd_ais_posterior: the chain kernel and the fold of every block of datapoints (the product for `mean` counts as gemm)
   KID_COUNT
 };
 
@@ -613,6 +615,16 @@ struct evoamd_ctx {
   DevBuf<int> ais_i;
   DevBuf<u64> ais_s;
   DevBuf<i64> ais_nf;
+  // evoamd_ais_posterior (kernels_ais_post.hpp): p | p_se (N, H each) | mean (N, D; only when asked for) | betas (T + 1) | log w |
+  // best lpj | weights (N, C each) | count | map_lpj | ll | ess | log_w_mean | log_w_min | log_w_max (N each); the rows r_c. of
+  // one block of datapoints (at most AIS_POST_ROWS_BYTES); the chains' flips (N, C); the chains' best states (N, C, HW) with
+  // map_state (N, HW) behind them; n_flips (N).  Sized before anything is launched, released by evoamd_configure.
+  // aisp_lds_set: bit log2(NC) = that instantiation has its dynamic LDS limit raised.
+  DevBuf<double> aisp_d, aisp_rows;
+  DevBuf<int> aisp_i;
+  DevBuf<u64> aisp_s;
+  DevBuf<i64> aisp_nf;
+  unsigned aisp_lds_set = 0;
   // evoamd_remap_latents: K^n in the new latent numbering and its digests, [index (H_new) | n_replaced (N)] and the sum;
   // grown on demand, NOT sized by the geometry: they survive the configure between the remap and
   // evoamd_adopt_remapped_states, which swaps them in and releases them.  remap_H = 0: nothing to adopt.
@@ -1382,6 +1394,12 @@ static void configure_drop(evoamd_ctx *c) {
   c->ais_i.reset();
   c->ais_s.reset();
   c->ais_nf.reset();
+  // ... and of evoamd_ais_posterior
+  c->aisp_d.reset();
+  c->aisp_rows.reset();
+  c->aisp_i.reset();
+  c->aisp_s.reset();
+  c->aisp_nf.reset();
   c->huge.reset();
   c->huge_ctl.reset();
   c->huge_slots = c->huge_kc = 0;
@@ -6667,6 +6685,207 @@ extern "C" int evoamd_ais_loglik(evoamd_ctx *c, int n_chains, int n_temps, const
   return ais_fetch(c, p, o);
 }
 
+// ---------------------------------------------------------------------------------------
+// posterior expectations from the AIS chains (kernels_ais_post.hpp has the law): EBSC on complete data.  Plan (every
+// refusal, the launch shape, the block of datapoints, the sizes), then the named stages: buffers, chains + fold block by
+// block, the product for `mean`, fetch.  Nothing of the EM state is written, y_hat and its validity included: B = Y W is
+// (re)formed like by every lpj pass, nothing else.
+// ---------------------------------------------------------------------------------------
+struct AisPostPlan {
+  int C = 0, T = 0, K = 0, nc = 1;  // nc: the chunk count the kernel is instantiated for (1, 2, 4, 8, 16)
+  i64 block = 1;                    // datapoints per block
+  bool mean = false;
+  size_t lds = 0;
+  size_t n_d = 0, n_rows = 0, n_i = 0, n_s = 0;  // elements of aisp_d / aisp_rows / aisp_i / aisp_s
+};
+
+static int ais_post_plan(const evoamd_ctx *c, int n_chains, int n_temps, int n_keep, const double *betas, int64_t block_datapoints,
+                         bool mean, AisPostPlan &p) {
+  REQUIRE(c && c->configured, "configure first");
+  if (!c->have_params) return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: no Theta installed (set parameters first)");
+  if (!c->have_data) return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: no data (upload data first)");
+  REQUIRE(c->model == EVOAMD_MODEL_BSC, "evoamd_ais_posterior: ES3C is not supported (a collapsed Gibbs step needs a bordered k x k "
+                                        "system per flip); the call is for EBSC");
+  REQUIRE(!c->f32, "evoamd_ais_posterior is not available in the float32 mode (ebsc_f32): the chains run on the double B = Y W");
+  REQUIRE(!c->bg_unit, "evoamd_ais_posterior: option background_unit is not supported (every latent is scanned)");
+  REQUIRE(!c->bsc_direct, "evoamd_ais_posterior: bsc_direct keeps no G = W^T W, whose rows the Gibbs scan reads");
+  REQUIRE(!c->mask_infr,
+          "evoamd_ais_posterior: incomplete data (masks resident) is not supported: the chains need one G for all datapoints");
+  if (c->H > 64 * AIS_MAX_NC)
+    return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: H = %d, at most %d latents are supported (64 lanes x %d registers of c_j)", c->H,
+                64 * AIS_MAX_NC, AIS_MAX_NC);
+  if (n_chains < 1) return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: n_chains = %d must be positive", n_chains);
+  if (n_temps < 1) return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: n_temps = %d must be positive", n_temps);
+  if (n_keep < 1) return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: n_keep = %d must be positive", n_keep);
+  REQUIRE((i64)n_temps + n_keep < 2147483647LL, "evoamd_ais_posterior: n_temps + n_keep must fit in int32");
+  REQUIRE(betas, "evoamd_ais_posterior: betas is NULL");
+  if (betas[0] != 0.0) return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: betas must start at 0 (betas[0] = %g)", betas[0]);
+  if (betas[n_temps] != 1.0)
+    return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: betas must end at 1 (betas[%d] = %g)", n_temps, betas[n_temps]);
+  for (int t = 1; t <= n_temps; t++)
+    if (!(betas[t] >= betas[t - 1]) || (t == 1 && !(betas[1] > 0.0)))
+      return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: betas must not descend and must leave 0 at once (betas[%d] = %g after %g)", t,
+                  betas[t], betas[t - 1]);
+  REQUIRE((i64)c->N * n_chains < 2147483647LL, "evoamd_ais_posterior: N * n_chains must fit in int32");
+  const size_t row = (size_t)n_chains * 64 * c->HW;  // doubles of one datapoint's rows
+  const i64 fit = (i64)(AIS_POST_ROWS_BYTES / (row * sizeof(double)));
+  if (block_datapoints < 0) return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: block_datapoints = %lld must not be negative", (long long)block_datapoints);
+  if (fit < 1 || block_datapoints > fit)
+    return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: the per-chain rows of one block (%lld datapoints x %d chains x %d doubles) exceed %llu MiB",
+                (long long)std::max<i64>(block_datapoints, 1), n_chains, 64 * c->HW, (unsigned long long)(AIS_POST_ROWS_BYTES >> 20));
+  p.C = n_chains, p.T = n_temps, p.K = n_keep, p.mean = mean;
+  while (p.nc < c->HW) p.nc <<= 1;
+  p.block = std::min<i64>(block_datapoints > 0 ? block_datapoints : fit, c->N);
+  p.lds = ais_post_lds_bytes(c->HW);
+  const size_t N = (size_t)c->N, NC = N * (size_t)n_chains;
+  p.n_d = (size_t)n_temps + 1 + 3 * NC + 2 * N * c->H + 7 * N + (mean ? N * c->D : 0);
+  p.n_rows = (size_t)p.block * row;
+  p.n_i = NC;
+  p.n_s = NC * c->HW + N * c->HW;
+  return 0;
+}
+
+// the views into the call's buffers
+struct AisPostBufs {
+  double *betas, *log_w, *best_lpj, *wts, *p, *p_se, *count, *map_lpj, *ll, *ess, *lw_mean, *lw_min, *lw_max, *mean;
+  int *flips;
+  u64 *best, *map_state;
+  i64 *n_flips;
+};
+static AisPostBufs ais_post_views(const evoamd_ctx *c, const AisPostPlan &p) {
+  const size_t N = (size_t)c->N, NC = N * (size_t)p.C, NH = N * (size_t)c->H;
+  AisPostBufs b;
+  // (p, p_se and mean first: the product for `mean` reads 16-byte vectors where the operands allow it)
+  b.p = c->aisp_d, b.p_se = b.p + NH, b.mean = b.p_se + NH, b.betas = b.mean + (p.mean ? N * (size_t)c->D : 0);
+  b.log_w = b.betas + p.T + 1, b.best_lpj = b.log_w + NC, b.wts = b.best_lpj + NC, b.count = b.wts + NC;
+  b.map_lpj = b.count + N, b.ll = b.map_lpj + N, b.ess = b.ll + N, b.lw_mean = b.ess + N, b.lw_min = b.lw_mean + N;
+  b.lw_max = b.lw_min + N;
+  b.flips = c->aisp_i;
+  b.best = c->aisp_s, b.map_state = b.best + NC * c->HW;
+  b.n_flips = c->aisp_nf;
+  return b;
+}
+
+template <int NC>
+static int ais_post_launch_one(evoamd_ctx *c, const AisPostPlan &p, const AisPostArgs &a, unsigned grid, unsigned bit) {
+  if (p.lds > (64u << 10) && !(c->aisp_lds_set & bit)) {  // once per instantiation
+    HIP_TRY(hipFuncSetAttribute((const void *)ais_post_chain_kernel<NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+    c->aisp_lds_set |= bit;
+  }
+  ais_post_chain_kernel<NC><<<grid, 64 * AIS_WAVES, p.lds, c->stream>>>(a);
+  return 0;
+}
+static int ais_post_launch_chains(evoamd_ctx *c, const AisPostPlan &p, const AisPostArgs &a) {
+  const unsigned grid = (unsigned)std::min<i64>(cdiv(a.nb * (i64)p.C, AIS_WAVES), (i64)c->n_cu * 64);
+  switch (p.nc) {
+    case 1: return ais_post_launch_one<1>(c, p, a, grid, 1u);
+    case 2: return ais_post_launch_one<2>(c, p, a, grid, 2u);
+    case 4: return ais_post_launch_one<4>(c, p, a, grid, 4u);
+    case 8: return ais_post_launch_one<8>(c, p, a, grid, 8u);
+    default: return ais_post_launch_one<AIS_MAX_NC>(c, p, a, grid, 16u);
+  }
+}
+
+// ---- stage: every buffer, before anything is launched
+static int ais_post_prepare(evoamd_ctx *c, const AisPostPlan &p) {
+  TRY(ensure_B(c));
+  TRY(c->aisp_d.ensure(c, p.n_d));
+  TRY(c->aisp_rows.ensure(c, p.n_rows));
+  TRY(c->aisp_i.ensure(c, p.n_i));
+  TRY(c->aisp_s.ensure(c, p.n_s));
+  TRY(c->aisp_nf.ensure(c, (size_t)c->N));
+  return 0;
+}
+
+// ---- stage: block by block, the chains and the fold over them
+// (rb_host: where the caller wants the rows r_c., (N, C, H) on the host -- each block's leave before the next one overwrites them)
+static int ais_post_chains_stage(evoamd_ctx *c, const AisPostPlan &p, const double *betas, uint64_t seed, uint64_t first_index,
+                                 double *rb_host) {
+  const AisPostBufs b = ais_post_views(c, p);
+  HIP_TRY(hipMemcpyAsync(b.betas, betas, ((size_t)p.T + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  AisPostArgs a = {};
+  a.G = c->G, a.Gd = c->diag, a.dpar = c->dpar, a.betas = b.betas, a.rb = c->aisp_rows, a.err = c->err;
+  a.C = p.C, a.T = p.T, a.K = p.K, a.H = c->H, a.HW = c->HW;
+  a.seed = seed;
+  AisPostFoldArgs f = {};
+  f.log_w = b.log_w, f.best_lpj = b.best_lpj, f.best = b.best, f.flips = b.flips, f.rb = c->aisp_rows, f.dpar = c->dpar;
+  f.wts = b.wts, f.p = b.p, f.p_se = b.p_se, f.count = b.count, f.map_lpj = b.map_lpj, f.ll = b.ll, f.ess = b.ess;
+  f.lw_mean = b.lw_mean, f.lw_min = b.lw_min, f.lw_max = b.lw_max, f.map_state = b.map_state, f.n_flips = b.n_flips;
+  f.C = p.C, f.H = c->H, f.HW = c->HW;
+  SpanGuard g(c, KID_AIS_POST);
+  for (i64 n0 = 0; n0 < c->N; n0 += p.block) {
+    a.nb = f.nb = std::min<i64>(p.block, c->N - n0);
+    f.n0 = n0;
+    const size_t i0 = (size_t)n0 * p.C;  // the chain kernel sees its block alone
+    a.Bm = c->Bm + (size_t)n0 * c->H, a.yy = c->yy + n0, a.first_index = first_index + (uint64_t)n0;
+    a.log_w = b.log_w + i0, a.best_lpj = b.best_lpj + i0, a.best = b.best + i0 * c->HW, a.flips = b.flips + i0;
+    TRY(ais_post_launch_chains(c, p, a));
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "ais_post chains");
+    ais_post_fold_kernel<<<cdiv(a.nb, AIS_WAVES), 64 * AIS_WAVES, 0, c->stream>>>(f);
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "ais_post fold");
+    if (rb_host)
+      HIP_TRY(hipMemcpy2DAsync(rb_host + (size_t)n0 * p.C * c->H, (size_t)c->H * sizeof(double), c->aisp_rows.get(),
+                               (size_t)64 * c->HW * sizeof(double), (size_t)c->H * sizeof(double), (size_t)a.nb * p.C,
+                               hipMemcpyDeviceToHost, c->stream));
+  }
+  return 0;
+}
+
+// ---- stage: mean = p W^T, the route of compute_reconstruction, into the call's own buffer (never c->yhat)
+static int ais_post_mean_stage(evoamd_ctx *c, const AisPostPlan &p) {
+  const AisPostBufs b = ais_post_views(c, p);
+  SpanGuard g(c, KID_GEMM);
+  launch_gemm_nn_raw(c, b.p, c->H, c->Wt, c->D, b.mean, c->D, c->N, c->D, c->H);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---- stage: the outputs, each where the caller gave a buffer
+static int ais_post_fetch(evoamd_ctx *c, const AisPostPlan &p, const evoamd_ais_post_out &o) {
+  const AisPostBufs b = ais_post_views(c, p);
+  const size_t N = (size_t)c->N, NC = N * (size_t)p.C, H = (size_t)c->H;
+  auto get = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
+    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+  };
+  HIP_TRY(get(o.p, b.p, N * H * sizeof(double)));
+  HIP_TRY(get(o.p_se, b.p_se, N * H * sizeof(double)));
+  HIP_TRY(get(o.count, b.count, N * sizeof(double)));
+  HIP_TRY(get(o.map_lpj, b.map_lpj, N * sizeof(double)));
+  HIP_TRY(get(o.map_state, b.map_state, N * c->HW * sizeof(u64)));
+  HIP_TRY(get(o.ll, b.ll, N * sizeof(double)));
+  HIP_TRY(get(o.ess, b.ess, N * sizeof(double)));
+  HIP_TRY(get(o.log_w_mean, b.lw_mean, N * sizeof(double)));
+  HIP_TRY(get(o.log_w_min, b.lw_min, N * sizeof(double)));
+  HIP_TRY(get(o.log_w_max, b.lw_max, N * sizeof(double)));
+  HIP_TRY(get(o.n_flips, b.n_flips, N * sizeof(i64)));
+  if (p.mean) HIP_TRY(get(o.mean, b.mean, N * c->D * sizeof(double)));
+  HIP_TRY(get(o.log_w, b.log_w, NC * sizeof(double)));
+  HIP_TRY(get(o.chain_map_lpj, b.best_lpj, NC * sizeof(double)));
+  HIP_TRY(get(o.chain_map_state, b.best, NC * c->HW * sizeof(u64)));
+  HIP_TRY(get(o.chain_flips, b.flips, NC * sizeof(int)));
+  HIP_TRY(hipMemcpyAsync(c->h_err, c->err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->h_err[0] & EVO_ERR_BAD_ENTRY) {  // guard_index replaced a latent index that was out of range
+    HIP_TRY(hipMemsetAsync(c->err, 0, sizeof(int), c->stream));
+    return fail(EVOAMD_E_INVALID, "internal: evoamd_ais_posterior: a latent index of a chain was out of range");
+  }
+  return 0;
+}
+
+extern "C" int evoamd_ais_posterior(evoamd_ctx *c, int n_chains, int n_temps, int n_keep, const double *betas, uint64_t seed,
+                                    uint64_t first_index, int64_t block_datapoints, const evoamd_ais_post_out *out) {
+  const evoamd_ais_post_out o = out ? *out : evoamd_ais_post_out{};
+  AisPostPlan p;
+  TRY(ais_post_plan(c, n_chains, n_temps, n_keep, betas, block_datapoints, o.mean != nullptr, p));
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(ais_post_prepare(c, p));
+  TRY(ais_post_chains_stage(c, p, betas, seed, first_index, o.rb));
+  if (p.mean) TRY(ais_post_mean_stage(c, p));
+  return ais_post_fetch(c, p, o);
+}
+
 // posterior samples (kernels_posterior_sample.hpp): own buffers; of the EM state only B = Y W is (re)formed, like every lpj pass
 // ---------------------------------------------------------------------------------------
 template <bool SSSC>
@@ -7200,6 +7419,6 @@ extern "C" const char *evoamd_kernel_name(int kid) {
                                          "loglik_proposal", "loglik_lpj",  "loglik_fold",     "remap_latents",
                                          "stats_kappa",  "sweep",       "sweep_swap",      "resize",
                                          "neighbour_bound", "predictive_score",
-                                         "ais"};
+                                         "ais",          "ais_post"};
   return (kid >= 0 && kid < KID_COUNT) ? names[kid] : "?";
 }

@@ -1,0 +1,307 @@
+// Posterior expectations from annealed importance sampling (evoamd_ais_posterior): the forward chains of kernels_ais.hpp,
+// continued at beta = 1, give weighted marginals E_p[s_h | y_n] that do not start from K^n.  A forward chain with its weight
+// is a properly weighted sample of the true posterior; the self-normalised sum over the chains is a consistent estimate of
+// a posterior expectation, and every further Gibbs scan at beta = 1 keeps it so.  EBSC on complete data.  One wavefront per
+// (datapoint, chain); no atomics on the outputs, every store a plain vector store, every sum in a fixed order: two launches
+// give the same bits.  evo_amd/models/ais.py: ais_posterior_counter is the NumPy mirror -- keep the two and the tests in step.
+//
+// THE LAW (names, stream, start, c_j, l(s), K_t and log w as in kernels_ais.hpp, forward direction), per datapoint n, chain
+// c < C, temperatures beta_0 .. beta_T and K = n_keep >= 1:
+//   chain      for t = 1 .. T: log w += (beta_t - beta_{t-1}) l(x_{t-1}); x_t = K_t(x_{t-1}) with the uniform block t + 1.  The
+//              scan at beta_T = 1 is the first KEPT scan; kept scans 2 .. K follow at beta = 1 with the uniform blocks T + 2,
+//              T + 3, ...; they do not enter w.  So log w, and with K = 1 the flips and the state, are those of
+//              evoamd_ais_loglik's forward chain c.
+//   R_c[h]     in every kept scan, when latent h is decided: R_c[h] += p with p = 1 / (1 + exp(-Delta)) from the current
+//              c_h -- a plain add in scan order, whether or not the bit changes.  r_ch = R_c[h] / K.  (Rao-Blackwell: the
+//              conditional, not the bit.  A latent that no chain switched on still gets its mass.)
+//   best       after every kept scan lpj(x) = |x| pil_bar + l(x) (one multiplication, one addition); the chain keeps its best
+//              visited state: a strictly greater value replaces it, the earliest scan wins ties.
+//   n_flips    the accepted flips of the chain, every kept scan included.
+//   fold       (ais_post_fold_kernel) per datapoint, chains in order: m, z, q as ais_fold_kernel forms them (running maximum
+//              rescaled), lse = m + log z, a_c = exp(log w_c - lse);
+//              p_nh = sum_c a_c r_ch; p_se_nh = sqrt(sum_c (a_c (r_ch - p_nh))^2), the delta-method error of a self-normalised
+//              estimate; count_n = sum_h p_nh, h ascending; map_lpj / map_state = the best over the chains, ties to the
+//              lowest chain; ll, ess, log_w_mean / _min / _max and n_flips as ais_fold_kernel.
+//
+// Mapping: as ais_chain_kernel<NC, false> -- lane l owns latents l, l + 64, ..., c_j in registers, the state one wave-uniform
+// word per chunk in ballot order.  The chunk scan is the exact one of kernels_ais.hpp; a lane adds the p of the round in which
+// it is SETTLED: the flipping lane and every open lane before it, or every open lane when no lane changes.  At that round c_h
+// holds exactly the flips of all earlier latents, which is what a sequential scan sees.  R_c[h] is touched by the lane that
+// owns h alone.
+// LDS: G_jj once per workgroup, B_n. and R_c per wavefront, (1 + 2 AIS_WAVES) Hp doubles, and behind them per wavefront the
+// best lpj in front of the best state's words (AIS_WAVES (HW + 1) words): 72.5 KiB at H = 1024, two workgroups per CU, which
+// is what the registers allow anyway.  Above 64 KiB the launch needs hipFuncAttributeMaxDynamicSharedMemorySize (set by the
+// host once per instantiation).  R_c, the best words and the best lpj are in LDS, not in registers: the two registers of
+// that lpj alone put NC = 1 and NC = 4 one occupancy step below ais_chain_kernel<NC, false>.
+// The rows r_c. of a block of datapoints go to a buffer of at most AIS_POST_ROWS_BYTES; the host walks the datapoints in
+// blocks, chains then fold.  Nothing depends on the block size: every index of the stream is the datapoint's own.
+#pragma once
+#include "kernels_ais.hpp"
+
+#define AIS_POST_ROWS_BYTES (256ull << 20)  // the per-chain rows of one block of datapoints: at most 256 MiB
+
+// One block of nb datapoints: the per-datapoint and per-chain pointers are those of the block's first datapoint, and
+// first_index is the data set index of that datapoint.
+struct AisPostArgs {
+  const double *Bm;     // (nb, H) B = Y W
+  const double *yy;     // (nb)
+  const double *G;      // (H, H)
+  const double *Gd;     // (H) diag(G)
+  const double *dpar;
+  const double *betas;  // (T + 1)
+  double *log_w;        // (nb, C)
+  double *best_lpj;     // (nb, C)
+  u64 *best;            // (nb, C, HW) MSB-first words
+  int *flips;           // (nb, C)
+  double *rb;           // (nb, C, Hp)
+  int *err;
+  i64 nb;
+  int C, T, K, H, HW;
+  u64 seed, first_index;
+};
+
+static inline size_t ais_post_lds_bytes(int HW) {
+  return (size_t)(1 + 2 * AIS_WAVES) * 64 * HW * sizeof(double) + (size_t)AIS_WAVES * (HW + 1) * sizeof(u64);
+}
+
+template <int NC>
+__global__ __launch_bounds__(64 * AIS_WAVES) void ais_post_chain_kernel(AisPostArgs a) {
+#pragma clang fp contract(off)
+  const int lane = lane_id(), wave = wave_id_uniform();
+  const int H = a.H, HW = a.HW, T = a.T, C = a.C, K = a.K;
+  const double pre1 = a.dpar[DP_PRE1], pilb = a.dpar[DP_PILBAR], pi = a.dpar[DP_PI];
+  // LDS: G_jj for the workgroup (Hp doubles), then B_n. and R_c of each wavefront (Hp doubles each), then per wavefront the
+  // best lpj and the best state's words (the two registers of that lpj are what separates NC = 1 and 4 from the next lower
+  // occupancy)
+  extern __shared__ double ais_post_lds[];
+  const int Hp = 64 * HW;
+  double *gd = ais_post_lds, *bn = ais_post_lds + (size_t)(1 + 2 * wave) * Hp, *R = bn + Hp;
+  double *bl = ais_post_lds + (size_t)(1 + 2 * AIS_WAVES) * Hp + (size_t)wave * (HW + 1);
+  u64 *bw = (u64 *)(bl + 1);
+  for (int h = (int)threadIdx.x; h < Hp; h += (int)blockDim.x) gd[h] = h < H ? a.Gd[h] : 0.0;
+  __syncthreads();
+  const i64 items = a.nb * (i64)C;
+  for (i64 it = (i64)blockIdx.x * AIS_WAVES + wave; it < items; it += (i64)gridDim.x * AIS_WAVES) {
+    const i64 n = it / C;
+    const int ch = (int)(it - n * C);
+    const u64 x0 = mix64(a.seed + 0x9e3779b97f4a7c15ull * (a.first_index + (u64)n + 1));
+    const u64 purpose = AIS_PURPOSE + (u64)ch;
+    const double yy = a.yy[n];
+    double c[NC];
+    u64 word[NC];  // wave-uniform, ballot order
+    seed_wave_sync();  // the previous item's reads of bn and bw are done
+#pragma unroll
+    for (int k = 0; k < NC; k++) {
+      const int h = 64 * k + lane;
+      c[k] = (k < HW && h < H) ? a.Bm[(size_t)n * H + h] : 0.0;
+      if (k < HW) bn[h] = c[k], R[h] = 0.0;
+      word[k] = 0ull;
+    }
+    seed_wave_sync();
+    // ---- the start: an exact draw from the prior
+#pragma unroll
+    for (int k = 0; k < NC; k++) {
+      if (k >= HW) continue;
+      const int h = 64 * k + lane;
+      word[k] = __ballot(h < H && gen_u01(x0, purpose, (u64)h) < pi);
+    }
+    // c_j = B_nj - sum over the active i, ascending
+#pragma unroll
+    for (int k = 0; k < NC; k++) {
+      if (k >= HW) continue;
+      u64 bits = word[k];
+      while (bits) {
+        const int b = __builtin_ctzll(bits);
+        bits &= bits - 1ull;
+        const int i = guard_index(64 * k + b, H, a.err);
+        const double *Gi = a.G + (size_t)i * H;
+#pragma unroll
+        for (int kk = 0; kk < NC; kk++) {
+          const int j = 64 * kk + lane;
+          if (kk < HW && j < H) c[kk] = c[kk] - Gi[j];
+        }
+      }
+    }
+    int flips = 0;
+    // l(s) of the current state
+    auto ell = [&]() -> double {
+#pragma clang fp contract(off)
+      double sum = 0.0;
+#pragma unroll
+      for (int k = 0; k < NC; k++) {
+        if (k >= HW) continue;
+        u64 bits = word[k];
+        while (bits) {
+          const int b = __builtin_ctzll(bits);
+          bits &= bits - 1ull;
+          sum = sum + (bn[64 * k + b] + ais_readlane(c[k], b));
+        }
+      }
+      return pre1 * (yy - sum);
+    };
+    // one flip of latent 64 k + b: the count, row h of G into every lane's c
+    auto apply = [&](int k_flip, int b, bool was_on) {
+#pragma clang fp contract(off)
+      const int h = guard_index(64 * k_flip + b, H, a.err);
+      const double *Gh = a.G + (size_t)h * H;
+#pragma unroll
+      for (int kk = 0; kk < NC; kk++) {
+        const int j = 64 * kk + lane;
+        if (kk < HW && j < H) {
+          const double g = Gh[j];
+          c[kk] = was_on ? c[kk] + g : c[kk] - g;
+        }
+      }
+      flips++;
+    };
+    // one systematic scan at beta, uniform block `block`; keep: a lane adds its p to R in the round that settles it
+    auto scan = [&](double beta, int block, bool keep) {
+#pragma clang fp contract(off)
+      const double bp = beta * pre1;
+      const u64 base = (u64)block * (u64)H;
+#pragma unroll
+      for (int k = 0; k < NC; k++) {
+        if (k >= HW) continue;
+        const int h = 64 * k + lane;
+        const bool valid = h < H;
+        const double u = gen_u01(x0, purpose, base + (u64)(valid ? h : 0));
+        const double g = gd[h];
+        u64 open = ~0ull;  // the lanes not yet settled
+        while (true) {
+          const bool on = (word[k] >> lane) & 1ull;
+          const double e = on ? g + 2.0 * c[k] : g - 2.0 * c[k];
+          const double t = bp * e;
+          const double delta = on ? pilb - t : pilb + t;
+          const double p = 1.0 / (1.0 + exp(-delta));
+          const bool nb = u < p;
+          const u64 m = __ballot(valid && nb != on) & open;
+          const int b = m ? __builtin_ctzll(m) : 63;  // (wave-uniform) the lane that flips, or none: all open lanes settle
+          if (keep && valid && ((open >> lane) & 1ull) && lane <= b) R[h] = R[h] + p;
+          if (m == 0ull) break;
+          const bool was_on = (word[k] >> b) & 1ull;
+          word[k] ^= 1ull << b;
+          apply(k, b, was_on);
+          open = b == 63 ? 0ull : ~0ull << (b + 1);
+          if (open == 0ull) break;
+        }
+      }
+    };
+    double lw = 0.0;
+    for (int t = 1; t <= T + K; t++) {  // the scans t = T .. T + K - 1 are the kept ones, all at beta_T = 1
+      const double e = ell();  // of x_{t-1}: enters w up to t = T, and lpj behind every kept scan
+      const double bt = a.betas[t < T ? t : T];
+      if (t <= T) lw = lw + (bt - a.betas[t - 1]) * e;
+      if (t > T) {
+        int cnt = 0;
+#pragma unroll
+        for (int k = 0; k < NC; k++)
+          if (k < HW) cnt += __popcll(word[k]);
+        const double lpj = (double)cnt * pilb + e;
+        seed_wave_sync();
+        const bool better = t == T + 1 || lpj > bl[0];  // (wave-uniform)
+        seed_wave_sync();
+        if (better) {
+          if (lane == 0) bl[0] = lpj;
+#pragma unroll
+          for (int k = 0; k < NC; k++)
+            if (k < HW && lane == k) bw[k] = __brevll(word[k]);
+        }
+      }
+      if (t < T + K) scan(bt, t + 1, t >= T);
+    }
+    seed_wave_sync();  // bw, written by lane k, is read by lane k again: the fence orders it behind the last write
+    if (lane == 0) {
+      a.log_w[it] = lw;
+      a.best_lpj[it] = bl[0];
+      a.flips[it] = flips;
+    }
+    if (lane < HW) a.best[(size_t)it * HW + lane] = bw[lane];
+    const double kd = (double)K;
+#pragma unroll
+    for (int k = 0; k < NC; k++)
+      if (k < HW) a.rb[(size_t)it * Hp + 64 * k + lane] = R[64 * k + lane] / kd;
+  }
+}
+
+struct AisPostFoldArgs {
+  const double *log_w;     // (N, C)
+  const double *best_lpj;  // (N, C)
+  const u64 *best;         // (N, C, HW)
+  const int *flips;        // (N, C)
+  const double *rb;        // (nb, C, Hp)
+  const double *dpar;
+  double *wts;             // (N, C): a_c, formed once
+  double *p, *p_se;        // (N, H)
+  double *count, *map_lpj, *ll, *ess, *lw_mean, *lw_min, *lw_max;  // (N)
+  u64 *map_state;          // (N, HW)
+  i64 *n_flips;            // (N)
+  i64 n0, nb;
+  int C, H, HW;
+};
+
+// Per datapoint of the block: one wavefront, lanes over h, chains in order.
+__global__ __launch_bounds__(64 * AIS_WAVES) void ais_post_fold_kernel(AisPostFoldArgs a) {
+#pragma clang fp contract(off)
+  const int lane = lane_id(), wave = wave_id_uniform();
+  const i64 nl = (i64)blockIdx.x * AIS_WAVES + wave;
+  if (nl >= a.nb) return;  // (wave-uniform)
+  const i64 n = a.n0 + nl;
+  const int C = a.C, H = a.H, HW = a.HW, Hp = 64 * HW;
+  const double *lw = a.log_w + (size_t)n * C;
+  // the weights' fold, the same in every lane
+  double m = -INFINITY, z = 0.0, q = 0.0, sum = 0.0, lo = INFINITY, hi = -INFINITY;
+  i64 nf = 0;
+  int top = 0;
+  double top_lpj = a.best_lpj[(size_t)n * C];
+  for (int c = 0; c < C; c++) {
+    const double v = lw[c];
+    if (v > m) {  // (the first one: 0 * exp(-inf) + 1)
+      const double r = exp(m - v);
+      z = z * r + 1.0;
+      q = q * (r * r) + 1.0;
+      m = v;
+    } else {
+      const double e = exp(v - m);
+      z = z + e;
+      q = q + e * e;
+    }
+    sum = sum + v;
+    lo = fmin(lo, v), hi = fmax(hi, v);
+    nf += a.flips[(size_t)n * C + c];
+    const double bl = a.best_lpj[(size_t)n * C + c];
+    if (bl > top_lpj) top = c, top_lpj = bl;  // strictly: ties go to the lowest chain
+  }
+  const double lse = m + log(z);
+  double *wts = a.wts + (size_t)n * C;
+  for (int c = lane; c < C; c += 64) wts[c] = exp(lw[c] - lse);
+  seed_wave_sync();
+  const double *rows = a.rb + (size_t)nl * C * Hp;
+  double cnt = 0.0;
+  for (int k = 0; k < HW; k++) {
+    const int h = 64 * k + lane;
+    const bool valid = h < H;
+    double p = 0.0, s2 = 0.0;
+    for (int c = 0; c < C; c++) p = p + wts[c] * rows[(size_t)c * Hp + h];
+    for (int c = 0; c < C; c++) {
+      const double d = wts[c] * (rows[(size_t)c * Hp + h] - p);
+      s2 = s2 + d * d;
+    }
+    if (valid) {
+      a.p[(size_t)n * H + h] = p;
+      a.p_se[(size_t)n * H + h] = sqrt(s2);
+    }
+    const double pv = valid ? p : 0.0;  // (the rows are 0 there anyway)
+#pragma unroll
+    for (int l = 0; l < 64; l++) cnt = cnt + ais_readlane(pv, l);  // h ascending
+  }
+  if (lane < HW) a.map_state[(size_t)n * HW + lane] = a.best[((size_t)n * C + top) * HW + lane];
+  if (lane == 0) {
+    a.count[n] = cnt;
+    a.map_lpj[n] = top_lpj;
+    a.ll[n] = (lse - log((double)C)) + (double)H * log1p(exp(a.dpar[DP_PILBAR]));
+    a.ess[n] = z * z / q;
+    a.lw_mean[n] = sum / (double)C;
+    a.lw_min[n] = lo, a.lw_max[n] = hi;
+    a.n_flips[n] = nf;
+  }
+}

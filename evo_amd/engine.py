@@ -525,6 +525,56 @@ class Engine:
         res["sum"] = float(total[0])
         return res
 
+    def ais_posterior(self, betas, n_chains=16, n_keep=4, seed=0, first_index=0, mean=False, keep_chains=False, block=0):
+        """Posterior expectations that do not start from K^n, under the Theta and data on the device (evoamd_ais_posterior;
+        csrc/kernels_ais_post.hpp has the law, evo_amd.models.ais_posterior_counter is the NumPy mirror): the forward
+        chains of ais_loglik, continued by ``n_keep`` - 1 further scans at beta = 1, each chain weighted by its w.
+        ``betas``: the float64 schedule of T + 1 values from 0 to 1.  Returns a dict with "p" and "p_se" (N, H: the weighted,
+        Rao-Blackwellised marginals E_p[s_h | y_n] and their delta-method standard errors), "count" (N: sum_h p_nh),
+        "map_lpj" (N) and "map_state" (uint8 (N, ceil(H / 8)), np.packbits layout: the best state any chain visited after
+        a kept scan), and "ll", "ess", "log_w_mean", "log_w_min", "log_w_max", "n_flips" (int64) as ais_loglik gives them
+        for forward chains (n_flips counts the kept scans too).  ``mean`` adds "mean" (N, D) = p W^T; ``keep_chains`` adds
+        "log_w", "chain_map_lpj" (N, C), "rb" (N, C, H: the chains' averaged conditionals), "chain_map_state" (uint8 (N, C,
+        ceil(H / 8))) and "chain_flips" (int32 (N, C)).  ``block``: datapoints per block of the per-chain rows (0: as many
+        as 256 MiB hold); the results do not depend on it.  K^n, lpj, the candidate batch, the statistics rows and y_hat
+        are not written.  EvoAmdError naming the rule, before anything is written, for ES3C, the float32 mode, the
+        background unit, bsc_direct, masks resident, H > 1024, n_chains < 1, n_keep < 1, betas that do not start at 0, end
+        at 1 or that descend, and a block above 256 MiB."""
+        betas = np.ascontiguousarray(betas, dtype=np.float64)
+        if betas.ndim != 1 or betas.size < 2:
+            raise ValueError("betas must be a 1-d array of T + 1 >= 2 values")
+        N, H, D, C, T = self.N, self.H, self.D, int(n_chains), betas.size - 1
+        HW, nb = (H + 63) // 64, (H + 7) // 8
+        u64p = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))  # noqa: E731
+        res = {"p": np.empty((N, H)), "p_se": np.empty((N, H))}
+        res.update({name: np.empty(N) for name in ("count", "map_lpj", "ll", "ess", "log_w_mean", "log_w_min", "log_w_max")})
+        res["n_flips"] = np.empty(N, dtype=np.int64)
+        out = _lib.AisPostOut()
+        for name, a in res.items():
+            if a.dtype == np.float64:
+                setattr(out, name, dptr(a))
+        out.n_flips = res["n_flips"].ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        map_words = np.empty((N, HW), dtype=np.uint64)
+        out.map_state = u64p(map_words)
+        if mean:
+            res["mean"] = np.empty((N, D))
+            out.mean = dptr(res["mean"])
+        chain_words = None
+        if keep_chains and C >= 1:
+            res["log_w"], res["chain_map_lpj"], res["rb"] = np.empty((N, C)), np.empty((N, C)), np.empty((N, C, H))
+            res["chain_flips"] = np.empty((N, C), dtype=np.int32)
+            chain_words = np.empty((N * C, HW), dtype=np.uint64)
+            out.log_w, out.chain_map_lpj, out.rb = dptr(res["log_w"]), dptr(res["chain_map_lpj"]), dptr(res["rb"])
+            out.chain_flips, out.chain_map_state = i32ptr(res["chain_flips"]), u64p(chain_words)
+        check(self.lib.evoamd_ais_posterior(self._h, C, T, int(n_keep), dptr(betas), int(seed) & (2 ** 64 - 1),
+                                            int(first_index) & (2 ** 64 - 1), int(block), ctypes.byref(out)))
+        # the MSB-first words as bytes are the np.packbits layout
+        as_bytes = lambda w: np.ascontiguousarray(w.astype(">u8").view(np.uint8).reshape(w.shape[0], HW * 8)[:, :nb])  # noqa: E731
+        res["map_state"] = as_bytes(map_words)
+        if chain_words is not None:
+            res["chain_map_state"] = as_bytes(chain_words).reshape(N, C, nb)
+        return res
+
     SCORES = ("F", "entropy", "best", "k_best", "k_mean")
 
     def posterior_scores(self, what=SCORES):

@@ -1424,6 +1424,60 @@ class Model:
             return L, info
         return L
 
+    def ais_posterior(self, model_params, my_suff_stat, my_data, n_chains=16, n_temps=128, n_keep=4, betas=None, seed=None,
+                      first_index=0, mean=False, keep_chains=False):
+        """Posterior expectations beyond K^n, for EBSC on complete data with H <= 1024 (Engine.ais_posterior;
+        csrc/kernels_ais_post.hpp has the law, evo_amd.models.ais_posterior_counter is the NumPy mirror).  encode(...).p,
+        reconstruct and predictive_moments are expectations under q_n, the posterior truncated to K^n; here the chains ARE
+        the forward chains of ais_log_likelihood (same stream, start and schedule), continued: a chain with its weight is a
+        properly weighted sample of the true posterior, the scan at beta_T = 1 is the first of ``n_keep`` >= 1 kept scans,
+        and in a kept scan the conditional p(s_h = 1 | the rest) is recorded when latent h is decided (Rao-Blackwell).
+        Returns a dict of per-datapoint arrays of this rank: "p" (N, H) = sum_c a_c r_ch with a_c the normalised weights --
+        a consistent estimate of E_p[s_h | y_n] -- and "p_se" (N, H), its delta-method standard error (it measures the
+        spread over the chains: a mode that no chain visited is not in it; read "ess" beside it); "count" (N) = sum_h
+        p_nh; "map_lpj" (N) and "map_state" (uint8 (N, ceil(H / 8)), np.packbits layout), the best state any chain
+        visited after a kept scan; "ll", "ess", "log_w_mean", "log_w_min", "log_w_max", "n_flips" as ais_log_likelihood
+        (direction="forward", per_datapoint=True) gives them, n_flips with the kept scans.  ``mean=True`` adds "mean" (N,
+        D) = p W^T, the posterior mean of W s: the reconstruction that does not go through K^n.  ``keep_chains=True`` adds
+        "log_w", "chain_map_lpj" (N, C), "rb" (N, C, H), "chain_map_state" (uint8 (N, C, ceil(H / 8))) and "chain_flips"
+        (N, C).  Chain c does not depend on ``n_chains``, shards by ``first_index`` concatenate, two calls give the same
+        bits; ``seed`` None: drawn from np.random and left in ``self.last_ais_seed`` (rank and world size enter it as in
+        ais_log_likelihood).  Nothing of the EM state is written -- not K^n, lpj, the candidate batch, the statistics rows
+        or y_hat -- and there is no collective.  Out of scope: reverse chains, admit, ES3C, incomplete data, resident
+        handles for p / mean, second moments, use of the marginals in the M-step.  NotImplementedError for ES3C;
+        ValueError for the float32 mode, the background unit, incomplete data, H > 1024, n_chains < 1, n_keep < 1 and
+        betas that do not start at 0, end at 1 or that descend."""
+        from .ais import AIS_MAX_H, check_betas, sigmoid_schedule
+        if self.model_name != "bsc":
+            raise NotImplementedError("ais_posterior is for EBSC: ES3C is out of scope (a collapsed Gibbs step would need a "
+                                      "bordered k x k system per flip)")
+        if self.dtype == np.float32:
+            raise ValueError("ais_posterior is not available in the float32 mode")
+        if my_suff_stat["permanent"]["background"]:
+            raise ValueError("ais_posterior: the background unit is not supported")
+        if not self._complete(my_data):
+            raise ValueError("ais_posterior: incomplete data (x_infr with False entries) is not supported")
+        if self.H > AIS_MAX_H:
+            raise ValueError("ais_posterior: H = %d, at most %d latents are supported" % (self.H, AIS_MAX_H))
+        C, K = int(n_chains), int(n_keep)
+        if C < 1:
+            raise ValueError("ais_posterior: n_chains = %d must be positive" % C)
+        if K < 1:
+            raise ValueError("ais_posterior: n_keep = %d must be positive" % K)
+        betas = sigmoid_schedule(n_temps) if betas is None else check_betas(betas)
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+        self.last_ais_seed = (int(seed) * max(1, self.comm.size) + self.comm.rank) & (2 ** 64 - 1)
+        yr = my_data.get("y_reconstructed")
+        if isinstance(yr, ResidentReconstruction) and yr.resident and not yr.materialised:
+            yr.rows()  # setting the parameters below drops the device copy of an unread reconstruction: fetch it first
+        eng = self._prepare(my_suff_stat, my_data, upload_states=False)  # (the chains read no K^n)
+        theta = dict(model_params)  # (the precompute stores its derived keys and zeroes the reset counters: on copies)
+        self.E_step_precompute(theta, dict(my_suff_stat), my_data)
+        if model_params is not self._dev_theta:
+            self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
+        return eng.ais_posterior(betas, C, K, self.last_ais_seed, first_index, mean=bool(mean), keep_chains=bool(keep_chains))
+
     def reconstruct(self, my_data, my_suff_stat, model_params):
         """(Re-)estimate the entries with my_data["x"] False from the posterior predictive distribution under
         ``model_params`` and the caller's K^n / lpj; adds my_data["y_reconstructed"] (_models.py:614-665).

@@ -206,3 +206,137 @@ def ais_log_likelihood_counter(theta, Y, n_chains=16, n_temps=128, betas=None, s
     out["final"] = np.packbits(out["final_bool"], axis=-1).reshape(-1)
     out["sum"] = float(np.sum(out["ll"]))
     return out
+
+
+def ais_posterior_counter(theta, Y, n_chains=16, n_temps=128, n_keep=4, betas=None, seed=0, first_index=0, mean=False, B=None,
+                          G=None):
+    """The NumPy mirror of Model.ais_posterior (csrc/kernels_ais_post.hpp states the law): the forward chains of
+    ais_log_likelihood_counter, continued.  The scan at beta_T = 1 (uniform block T + 1) is the first KEPT scan; kept scans
+    2 .. ``n_keep`` follow at beta = 1 with the uniform blocks T + 2, T + 3, ...; none of them enters w.  In every kept scan
+    the conditional p = 1 / (1 + exp(-Delta)) from the current c_h is added to R_c[h] at the moment latent h is decided,
+    whether or not the bit changes; r_ch = R_c[h] / n_keep.  After each kept scan lpj(x) = |x| pil_bar + l(x); a chain keeps
+    its best visited state, a strictly greater value replaces it.  Per datapoint, with lse = logsumexp(log w) folded in chain
+    order (``_fold``) and a_c = exp(log w_c - lse):
+
+        p[n, h]     = sum_c a_c r_ch                       (chain order)
+        p_se[n, h]  = sqrt(sum_c (a_c (r_ch - p_nh))^2)    the delta-method error of a self-normalised estimate
+        count[n]    = sum_h p_nh                           (h ascending)
+        map_lpj / map_state: the best over the chains, ties to the lowest chain; map_state in np.packbits layout
+
+    Returns these with "ll", "ess", "log_w_mean", "log_w_min", "log_w_max", "n_flips" (int64; the kept scans included) as
+    ais_log_likelihood_counter forms them, the per-chain "log_w" (N, C), "rb" (N, C, H), "chain_map_lpj" (N, C),
+    "chain_map_state" (uint8 (N, C, ceil(H / 8))), "chain_flips" (N, C), beside them "chain_map_bool" (N, C, H), "map_bool"
+    (N, H), "first_bool" and "first_flips" (the state and the flips after the first kept scan: ``final_bool`` and
+    ``chain_flips`` of ais_log_likelihood_counter), "margin" (N, C; every decision of the chain, the kept scans included)
+    and, with ``mean``, "mean" (N, D) = p W^T."""
+    C, K = int(n_chains), int(n_keep)
+    if C < 1:
+        raise ValueError("ais_posterior: n_chains must be positive")
+    if K < 1:
+        raise ValueError("ais_posterior: n_keep must be positive")
+    betas = sigmoid_schedule(n_temps) if betas is None else check_betas(betas)
+    T = betas.size - 1
+    W = np.asarray(theta["W"], dtype=np.float64)
+    Y = np.asarray(Y, dtype=np.float64)
+    N, H = Y.shape[0], W.shape[1]
+    if H > AIS_MAX_H:
+        raise ValueError("ais_posterior: H = %d, at most %d latents are supported" % (H, AIS_MAX_H))
+    pre1, pilb, pi = ais_scalars(theta)
+    B = np.dot(Y, W) if B is None else np.asarray(B, dtype=np.float64)
+    G = np.dot(W.T, W) if G is None else np.asarray(G, dtype=np.float64)
+    yy = (Y * Y).sum(axis=1)
+    Gd = np.diag(G).copy()
+    seed, first_index = int(seed) & _M64, int(first_index) & _M64
+    hs = np.arange(H, dtype=np.uint64)
+    out = {"log_w": np.empty((N, C)), "rb": np.empty((N, C, H)), "chain_map_lpj": np.empty((N, C)),
+           "chain_map_bool": np.zeros((N, C, H), dtype=bool), "first_bool": np.zeros((N, C, H), dtype=bool),
+           "margin": np.empty((N, C)), "p": np.empty((N, H)), "p_se": np.empty((N, H)), "count": np.empty(N),
+           "map_lpj": np.empty(N), "map_bool": np.zeros((N, H), dtype=bool)}
+    for name in ("ll", "ess", "log_w_mean", "log_w_min", "log_w_max"):
+        out[name] = np.empty(N)
+    chain_flips = np.zeros((N, C), dtype=np.int64)
+    first_flips = np.zeros((N, C), dtype=np.int64)
+    lz0 = H * np.log1p(np.exp(pilb))
+
+    def scan(s, c, beta, u, flips, margin, R):
+        """One ascending scan of all chains in place; R (C, H) or None: where the conditionals are added."""
+        for h in range(H):
+            on = s[:, h].copy()
+            p = ais_conditional(pre1, pilb, c[:, h], Gd[h], on, beta)
+            if R is not None:
+                R[:, h] = R[:, h] + p
+            np.minimum(margin, np.abs(u[:, h] - p), out=margin)
+            nb = u[:, h] < p
+            up, down = nb & ~on, on & ~nb
+            if up.any():
+                c[up] = c[up] - G[h]
+            if down.any():
+                c[down] = c[down] + G[h]
+            s[:, h] = nb
+            flips += up | down
+
+    with np.errstate(over="ignore"):  # the hashes wrap mod 2^64
+        for n in range(N):
+            x0 = _first_hash(seed, np.array([(first_index + n) & _M64], dtype=np.uint64))
+            block = lambda b: _u01_chains(x0, C, np.uint64(b * H) + hs)  # noqa: E731
+            flips = np.zeros(C, dtype=np.int64)
+            u = block(0)
+            s = u < pi
+            margin = np.abs(u - pi).min(axis=1)
+            c = np.repeat(B[n][None, :], C, axis=0)
+            for i in np.flatnonzero(s.any(axis=0)):
+                c[s[:, i]] = c[s[:, i]] - G[i]
+            lw = np.zeros(C)
+            R = np.zeros((C, H))
+            best = np.full(C, -np.inf)
+            best_s = np.zeros((C, H), dtype=bool)
+            for t in range(1, T + K):
+                if t <= T:
+                    lw = lw + (betas[t] - betas[t - 1]) * _ell(pre1, yy[n], B[n], c, s)
+                kept = t >= T
+                scan(s, c, betas[min(t, T)], block(t + 1), flips, margin, R if kept else None)
+                if kept:
+                    lpj = s.sum(axis=1).astype(np.float64) * pilb + _ell(pre1, yy[n], B[n], c, s)
+                    better = lpj > best  # (strictly: the earliest scan wins ties)
+                    best = np.where(better, lpj, best)
+                    best_s[better] = s[better]
+                if t == T:
+                    out["first_bool"][n] = s
+                    first_flips[n] = flips
+            r = R / float(K)
+            out["log_w"][n], out["rb"][n], out["margin"][n] = lw, r, margin
+            out["chain_map_lpj"][n], out["chain_map_bool"][n] = best, best_s
+            chain_flips[n] = flips
+            lse, ess = _fold(lw)
+            out["ll"][n] = (lse - np.log(float(C))) + lz0
+            out["ess"][n] = ess
+            total = 0.0
+            for v in lw:
+                total = total + v
+            out["log_w_mean"][n] = total / float(C)
+            out["log_w_min"][n], out["log_w_max"][n] = lw.min(), lw.max()
+            a = np.exp(lw - lse)
+            p = np.zeros(H)
+            for ch in range(C):
+                p = p + a[ch] * r[ch]
+            q = np.zeros(H)
+            for ch in range(C):
+                d = a[ch] * (r[ch] - p)
+                q = q + d * d
+            out["p"][n], out["p_se"][n] = p, np.sqrt(q)
+            cnt = 0.0
+            for v in p:
+                cnt = cnt + v
+            out["count"][n] = cnt
+            top = 0
+            for ch in range(1, C):
+                if best[ch] > best[top]:
+                    top = ch
+            out["map_lpj"][n], out["map_bool"][n] = best[top], best_s[top]
+    out["n_flips"] = chain_flips.sum(axis=1)
+    out["chain_flips"], out["first_flips"] = chain_flips, first_flips
+    out["chain_map_state"] = np.packbits(out["chain_map_bool"], axis=-1)
+    out["map_state"] = np.packbits(out["map_bool"], axis=-1)
+    if mean:
+        out["mean"] = np.dot(out["p"], W.T)
+    return out

@@ -542,6 +542,50 @@ typedef struct evoamd_ais_out {
 int evoamd_ais_loglik(evoamd_ctx *ctx, int n_chains, int n_temps, const double *betas, uint64_t seed, uint64_t first_index,
                       unsigned flags, const uint64_t *s_start, int Mprime, const evoamd_ais_out *out);
 
+/* Posterior expectations beyond K^n: weighted marginals E_p[s_h | y_n] and means from the forward chains of
+ * evoamd_ais_loglik, continued (csrc/kernels_ais_post.hpp has the law; evo_amd.models.ais_posterior_counter is the NumPy
+ * mirror).  evoamd_posterior_codes, evoamd_reconstruct and evoamd_predictive_moments are expectations under q_n, the posterior
+ * truncated to K^n, and evoamd_loglik_exact with marginals stops at H of about 30; this call goes beyond both: a forward chain
+ * with its weight is a properly weighted sample of the TRUE posterior.  EBSC on complete data, H <= 1024.
+ * The chains are those of evoamd_ais_loglik with flags = 0 (same stream, start and schedule): the scan at betas[n_temps] = 1
+ * is the first of n_keep >= 1 KEPT scans, the others follow at beta = 1 with the uniform blocks n_temps + 2, ...; in a kept
+ * scan the conditional p(s_h = 1 | the rest) is added to R_c[h] when latent h is decided (Rao-Blackwell), r_ch = R_c[h] /
+ * n_keep; after each kept scan the chain compares lpj of its state with the best it has seen.  Per datapoint, with a_c the
+ * normalised weights: p = sum_c a_c r_c., p_se = sqrt(sum_c (a_c (r_c. - p))^2), count = sum_h p_h, map_lpj / map_state =
+ * the best state over the chains (ties: the lowest chain), ll / ess / log_w_* / n_flips as evoamd_ais_loglik (n_flips counts
+ * the kept scans too).  mean (N, D) = p W^T, the posterior mean of W s, through the f64 GEMM into a buffer of its own.
+ * block_datapoints: 0 = the datapoints are walked in blocks whose per-chain rows (block x n_chains x 64 ceil(H / 64) doubles)
+ * stay within 256 MiB; > 0 = that many per block (for tests; the same limit holds).  Results do not depend on it.
+ * Outputs (host; each pointer and out itself may be NULL): p, p_se (N, H), count, map_lpj, ll, ess, log_w_mean, log_w_min,
+ * log_w_max (N), n_flips (N int64), map_state (N, ceil(H / 64)) words in the layout of K^n, mean (N, D), and per chain log_w,
+ * chain_map_lpj (N, n_chains), rb (N, n_chains, H), chain_map_state (N, n_chains, ceil(H / 64)), chain_flips (N, n_chains).
+ * Nothing of the EM state is written: not K^n, lpj, the candidate batch or the statistics rows, not y_hat or its validity
+ * (B = Y W is (re)formed like by every lpj pass).  Deterministic: two calls give the same bits.  No reverse chains, no admit.
+ * EVOAMD_E_INVALID before anything is written, each with its own text: no Theta or data; ES3C; the float32 mode (ebsc_f32);
+ * background_unit; bsc_direct; masks resident; H > 1024; n_chains < 1; n_temps < 1; n_keep < 1; betas NULL, not starting at
+ * 0, not ending at 1, or descending; block_datapoints < 0 or one block's rows above 256 MiB. */
+typedef struct evoamd_ais_post_out {
+  double *p;                 /* (N, H) */
+  double *p_se;              /* (N, H) */
+  double *count;             /* (N) */
+  double *map_lpj;           /* (N) */
+  uint64_t *map_state;       /* (N, ceil(H / 64)) */
+  double *ll;                /* (N) */
+  double *ess;               /* (N) */
+  double *log_w_mean;        /* (N) */
+  double *log_w_min;         /* (N) */
+  double *log_w_max;         /* (N) */
+  int64_t *n_flips;          /* (N) */
+  double *mean;              /* (N, D) */
+  double *log_w;             /* (N, n_chains) */
+  double *rb;                /* (N, n_chains, H) */
+  double *chain_map_lpj;     /* (N, n_chains) */
+  uint64_t *chain_map_state; /* (N, n_chains, ceil(H / 64)) */
+  int32_t *chain_flips;      /* (N, n_chains) */
+} evoamd_ais_post_out;
+int evoamd_ais_posterior(evoamd_ctx *ctx, int n_chains, int n_temps, int n_keep, const double *betas, uint64_t seed,
+                         uint64_t first_index, int64_t block_datapoints, const evoamd_ais_post_out *out);
+
 /* Per-datapoint scores of the lpj rows and K^n resident on the device (after a seed, an upload or any pass), each output
  * (N) or NULL.  With m = max_s lpj_ns, w_s = exp(lpj_ns - m), z = sum_s w_s over the S_perm + S columns:
  * F_out = m + log z (the bound per datapoint without ljc, the counterpart of ll_out of evoamd_loglik_exact);
@@ -1085,7 +1129,8 @@ enum {
   EVOAMD_K_NBOUND = 33,        /* evoamd_neighbour_bound: the neighbourhood kernel (ES3C: with the transpose of GP) and the bound of the rows */
   EVOAMD_K_PRED_SCORE = 34,    /* evoamd_predictive_score: the transpose of W, the visit list, the score kernel, its partials and their reductions */
   EVOAMD_K_AIS = 35,           /* evoamd_ais_loglik: the chain kernel, the fold over the chains and (admit) the emission */
-  EVOAMD_K_COUNT = 36
+  EVOAMD_K_AIS_POST = 36,      /* evoamd_ais_posterior: the chain kernel and the fold of every block of datapoints (the product for mean counts as gemm) */
+  EVOAMD_K_COUNT = 37
 };
 /* on = bit mask of kernel classes to time (bit k = class k; -1 = all, 0 = off).  Each timed span
  * records two HIP events on the compute stream, which costs about 10 us of stream time per span:
