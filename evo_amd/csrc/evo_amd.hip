@@ -11,6 +11,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <memory>
 #include <string>
 #include <type_traits>
@@ -307,6 +308,28 @@ class PinnedBuf {
     int _r = (expr);     \
     if (_r) return _r;   \
   } while (0)
+
+// The buffers a call is about to size, each named once.  Asked before anything is released, allocated or launched: they fit
+// unless grow > avail; the refusal and its hint are the caller's.  ensure_all() then grows them in the order listed.
+struct FitList {
+  size_t grow = 0, released = 0;  // bytes of the buffers that must grow; bytes those give back when they are re-cut
+  std::vector<std::function<int(evoamd_ctx *)>> ensures;
+  template <typename T>
+  void add(DevBuf<T> &b, size_t want) {
+    if (want > b.size()) grow += want * sizeof(T), released += b.size() * sizeof(T);
+    ensures.push_back([&b, want](evoamd_ctx *c) { return b.ensure(c, want); });
+  }
+  int measure(size_t &avail) const {  // avail: the free device memory plus `released` (no query while nothing grows)
+    size_t free_b = 0, total_b = 0;
+    if (grow) HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    avail = free_b + released;
+    return 0;
+  }
+  int ensure_all(evoamd_ctx *c) const {
+    for (const auto &e : ensures) TRY(e(c));
+    return 0;
+  }
+};
 
 struct evoamd_ctx {
   evoamd_ctx() = default;
@@ -3673,26 +3696,17 @@ extern "C" int evoamd_resize_states(evoamd_ctx *c, int S_new, int32_t *src_slot_
                 "S_new = %d slots (%zu bytes) do not fit one wavefront's share of LDS", S, HW, S_new, share);
   HIP_TRY(hipSetDevice(c->device));
   const size_t N = (size_t)c->N;
-  {  // does the scratch fit?  Decided before anything is released, allocated or launched.
-    size_t grow = 0, released = 0;
-    auto plan = [&](size_t have, size_t want, size_t elem) {
-      if (want > have) grow += want * elem, released += have * elem;
-    };
-    plan(c->resize_states.size(), N * S_new * HW, sizeof(u64));
-    plan(c->resize_dig.size(), N * S_new, sizeof(u64));
-    plan(c->resize_src.size(), N * S_new, sizeof(int));
-    if (grow) {
-      size_t free_b = 0, total_b = 0;
-      HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-      if (grow > free_b + released)
-        return fail(EVOAMD_E_INVALID, "evoamd_resize_states: the resized K^n needs %zu bytes of device memory, %zu are free", grow,
-                    free_b + released);
-    }
-  }
+  FitList scratch;  // does it fit?  Decided before anything is released, allocated or launched.
+  scratch.add(c->resize_states, N * S_new * HW);
+  scratch.add(c->resize_dig, N * S_new);
+  scratch.add(c->resize_src, N * S_new);
+  size_t avail;
+  TRY(scratch.measure(avail));
+  if (scratch.grow > avail)
+    return fail(EVOAMD_E_INVALID, "evoamd_resize_states: the resized K^n needs %zu bytes of device memory, %zu are free", scratch.grow,
+                avail);
   made_resize(c, 0, 0, 0);  // whatever an earlier resize left is overwritten from here on
-  TRY(c->resize_states.ensure(c, N * S_new * HW));
-  TRY(c->resize_dig.ensure(c, N * S_new));
-  TRY(c->resize_src.ensure(c, N * S_new));
+  TRY(scratch.ensure_all(c));
   ResizeArgs a;
   a.src = c->states;
   a.lpj = c->lpj;
@@ -5683,13 +5697,117 @@ extern "C" int evoamd_patches_merge_predictive(evoamd_ctx *c, int H, int W, int 
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------
+// Read-out calls: they read (K^n, lpj, Theta, data) and write only to buffers of their own -- the posterior codes, the
+// predictive moments and scores, the posterior samples, the log-likelihood estimate and, further down, the neighbourhood
+// bound and the two AIS calls.  What they share stands here once: one admission (readout_admit), one way to hand outputs
+// back (fetch_if, download_view) and, for the three calls whose kernels take PredArgs, one builder of the fields that come
+// from the context, one R x model dispatch and one tally of the status vector.  Outputs sized by what the caller asks for
+// are listed in a FitList.  A call supplies its own refusals, buffers and views, its kernels' own arguments, the validity
+// of its results (made_*) and the point at which it drops its earlier ones.
+// ---------------------------------------------------------------------------------------
+// who: the caller's name in the texts; need_kn: the call reads K^n itself (the codes refuse through kn_gen instead)
+static int readout_admit(const evoamd_ctx *c, const char *who, bool need_kn = true) {
+  if (!(c && c->configured && c->have_data && c->have_params))
+    return fail(EVOAMD_E_INVALID, "%s: configure, upload data and set parameters first", who);
+  if (c->f32) return fail(EVOAMD_E_INVALID, "%s is not available in the float32 mode", who);
+  if (need_kn) REQUIRE_KN(c);
+  return 0;
+}
+
+// the optional array of a call: copied where the caller gave a buffer
+static hipError_t fetch_if(evoamd_ctx *c, void *dst, const void *src, size_t bytes) {
+  return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+}
+
+// the tail of the evoamd_download_* calls: one array a call left on the device, to the host
+static int download_view(evoamd_ctx *c, void *out, const void *src, size_t bytes) {
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---- the calls on PredArgs (kernels_predictive.hpp): one lane holds R of the D observables
+static int pred_admit_D(const evoamd_ctx *c, const char *who) {
+  if (c->D > 64 * PRED_R_MAX)
+    return fail(EVOAMD_E_INVALID, "%s: D = %d, at most %d observables are supported (64 lanes x %d registers)", who, c->D,
+                64 * PRED_R_MAX, PRED_R_MAX);
+  return 0;
+}
+
+// the PredArgs fields that come straight from the context; the callers set status, add_noise and their outputs, and
+// sigma2 through pred_sigma once the scalars are on the host
+struct PredLaunch {
+  int R = 1;       // observables per lane: the kernels' first template argument
+  size_t lds = 0;  // dynamic LDS of a workgroup
+};
+static PredLaunch fill_pred_args(const evoamd_ctx *c, PredArgs &a) {
+  a.mask = c->mask_infr, a.row_any = c->mask_infr ? c->row_any.get() : nullptr;
+  a.lpj = c->lpj, a.states = c->states;
+  a.Wt = c->pred_Wt, a.G = c->G, a.Psi = c->Psi, a.mus = c->mus, a.Bm = c->Bm;
+  a.N = c->N;
+  a.D = c->D, a.H = c->H, a.HW = c->HW, a.S = c->S, a.S_perm = c->S_perm, a.L = c->L;
+  a.kcap = c->H < PRED_MAX_K ? c->H : PRED_MAX_K;
+  a.bg = c->bg_unit;
+  PredLaunch l;
+  while (64 * l.R < c->D) l.R <<= 1;
+  l.lds = PRED_WAVES * pred_lds_doubles(a.kcap, c->model == EVOAMD_MODEL_SSSC) * sizeof(double);
+  return l;
+}
+
+// dpar: the scalars of the current Theta, fetched by the caller (a device update leaves them in the scalar block only).
+// Sets sigma2 and returns sigma.
+static double pred_sigma(const evoamd_ctx *c, const double *dpar, PredArgs &a) {
+  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
+  a.sigma2 = sssc ? dpar[DP_SIGMA2] : dpar[DP_SIGMA] * dpar[DP_SIGMA];
+  return sssc ? sqrt(dpar[DP_SIGMA2]) : dpar[DP_SIGMA];
+}
+
+// W^T into pred_Wt; launched inside the caller's SpanGuard, so it counts in the caller's timing class
+static void pred_transpose_W(evoamd_ctx *c) {
+  transpose_kernel<<<cdiv((i64)c->H * c->D, 256), 256, 0, c->stream>>>(c->W, c->D, c->H, c->pred_Wt);
+}
+
+// (R, model) as compile-time constants: launch(r, s) with decltype(r)::value in {1, 2, 4, 8} and decltype(s)::value = ES3C
+template <typename Launch>
+static void pred_dispatch(int R, bool sssc, Launch launch) {
+  auto with_model = [&](auto s) {
+    switch (R) {
+      case 1: launch(std::integral_constant<int, 1>{}, s); break;
+      case 2: launch(std::integral_constant<int, 2>{}, s); break;
+      case 4: launch(std::integral_constant<int, 4>{}, s); break;
+      default: launch(std::integral_constant<int, 8>{}, s); break;
+    }
+  };
+  if (sssc)
+    with_model(std::true_type{});
+  else
+    with_model(std::false_type{});
+}
+
+// The status vector of such a kernel, on the host: the refusal of a state beyond PRED_MAX_K, else counts[0] = singular,
+// counts[1] = skipped, counts[2 + i] = the datapoints whose status is extra[i].  counts is written in place.
+static int pred_tally(const char *who, const int *status, i64 N, int64_t *counts, std::initializer_list<int> extra = {}) {
+  for (size_t k = 0; k < 2 + extra.size(); k++) counts[k] = 0;
+  for (i64 n = 0; n < N; n++) {
+    const int st = status[(size_t)n];
+    if ((st & 0xFF) == PRED_OVER_K)
+      return fail(EVOAMD_E_INVALID, "%s: datapoint n = %lld holds a state with k = %d active latents, "
+                  "at most %d are supported (PRED_MAX_K)", who, (long long)n, st >> 8, PRED_MAX_K);
+    counts[0] += st == PRED_SINGULAR;
+    counts[1] += st == PRED_SKIPPED;
+    int64_t *cnt = counts + 2;
+    for (int code : extra) *cnt++ += st == code;
+  }
+  return 0;
+}
+
 // ---- posterior code readout (kernels_codes.hpp) ----
 static const char *const CODES_NEED_STATS = ": call evoamd_stats first (and before setting new parameters or changing K^n)";
 
 static int codes_preamble(evoamd_ctx *c, const char *who) {
-  if (!(c && c->configured && c->have_data && c->have_params))
-    return fail(EVOAMD_E_INVALID, "%s: configure, upload data and set parameters first", who);
-  if (c->f32) return fail(EVOAMD_E_INVALID, "%s is not available in the float32 mode", who);
+  TRY(readout_admit(c, who, /*need_kn=*/false));
   if (!(c->stats_rows_valid && c->rows_kn_gen == c->kn_gen)) return fail(EVOAMD_E_INVALID, "%s%s", who, CODES_NEED_STATS);
   HIP_TRY(hipSetDevice(c->device));
   return 0;
@@ -5740,13 +5858,13 @@ extern "C" int evoamd_posterior_codes(evoamd_ctx *c, int max_active, double p_mi
       posterior_codes_kernel<CODES_GMEM><<<grid, 64 * CODES_WAVES, 0, c->stream>>>(a);
   }
   HIP_TRY(hipGetLastError());
-  if (idx) HIP_TRY(hipMemcpyAsync(idx, a.idx, N * A * 4, hipMemcpyDeviceToHost, c->stream));
-  if (p) HIP_TRY(hipMemcpyAsync(p, a.p, N * A * 8, hipMemcpyDeviceToHost, c->stream));
-  if (m) HIP_TRY(hipMemcpyAsync(m, a.m, N * A * 8, hipMemcpyDeviceToHost, c->stream));
-  if (nnz) HIP_TRY(hipMemcpyAsync(nnz, a.nnz, N * 4, hipMemcpyDeviceToHost, c->stream));
-  if (map_slot) HIP_TRY(hipMemcpyAsync(map_slot, a.map_slot, N * 4, hipMemcpyDeviceToHost, c->stream));
-  if (map_q) HIP_TRY(hipMemcpyAsync(map_q, a.map_q, N * 8, hipMemcpyDeviceToHost, c->stream));
-  if (map_state_packed) HIP_TRY(hipMemcpyAsync(map_state_packed, a.map_state, N * PB, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(fetch_if(c, idx, a.idx, N * A * 4));
+  HIP_TRY(fetch_if(c, p, a.p, N * A * 8));
+  HIP_TRY(fetch_if(c, m, a.m, N * A * 8));
+  HIP_TRY(fetch_if(c, nnz, a.nnz, N * 4));
+  HIP_TRY(fetch_if(c, map_slot, a.map_slot, N * 4));
+  HIP_TRY(fetch_if(c, map_q, a.map_q, N * 8));
+  HIP_TRY(fetch_if(c, map_state_packed, a.map_state, N * PB));
   return check_err(c);  // synchronises the stream
 }
 
@@ -5770,26 +5888,10 @@ extern "C" int evoamd_download_posterior(evoamd_ctx *c, double *Es, double *Ez) 
 // ---------------------------------------------------------------------------------------
 // predictive moments (kernels_predictive.hpp): own buffers; of the EM state only B = Y W is (re)formed, like every lpj pass
 // ---------------------------------------------------------------------------------------
-template <bool SSSC>
-static void launch_predictive(evoamd_ctx *c, const PredArgs &a, int R, size_t lds) {
-  const unsigned grid = cdiv(a.N, PRED_WAVES);
-  switch (R) {
-    case 1: predictive_kernel<1, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(a); break;
-    case 2: predictive_kernel<2, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(a); break;
-    case 4: predictive_kernel<4, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(a); break;
-    default: predictive_kernel<8, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(a); break;
-  }
-}
-
 extern "C" int evoamd_predictive_moments(evoamd_ctx *c, int add_noise, int64_t counters[2]) {
-  REQUIRE(c && c->configured && c->have_data && c->have_params,
-          "evoamd_predictive_moments: configure, upload data and set parameters first");
-  REQUIRE(!c->f32, "evoamd_predictive_moments is not available in the float32 mode");
-  REQUIRE_KN(c);
+  TRY(readout_admit(c, "evoamd_predictive_moments"));
   REQUIRE(counters, "evoamd_predictive_moments: counters is NULL");
-  if (c->D > 64 * PRED_R_MAX)
-    return fail(EVOAMD_E_INVALID, "evoamd_predictive_moments: D = %d, at most %d observables are supported (64 lanes x %d registers)",
-                c->D, 64 * PRED_R_MAX, PRED_R_MAX);
+  TRY(pred_admit_D(c, "evoamd_predictive_moments"));
   HIP_TRY(hipSetDevice(c->device));
   const bool sssc = c->model == EVOAMD_MODEL_SSSC;
   const i64 N = c->N;
@@ -5800,53 +5902,28 @@ extern "C" int evoamd_predictive_moments(evoamd_ctx *c, int add_noise, int64_t c
   TRY(c->pred_buf.ensure(c, 2 * nd));
   TRY(c->pred_Wt.ensure(c, (size_t)H * D));
   TRY(c->pred_status.ensure(c, (size_t)N));
-  // the scalars of the current Theta (a device update leaves them in the scalar block only)
   double dpar[DP_COUNT];
   HIP_TRY(hipMemcpyAsync(dpar, c->dpar, DP_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   PredArgs a = {};
-  a.mask = c->mask_infr;
-  a.row_any = c->mask_infr ? c->row_any : nullptr;
-  a.lpj = c->lpj;
-  a.states = c->states;
-  a.Wt = c->pred_Wt;
-  a.G = c->G;
-  a.Psi = c->Psi;
-  a.mus = c->mus;
-  a.Bm = c->Bm;
-  a.N = N;
-  a.D = D, a.H = H, a.HW = c->HW, a.S = c->S, a.S_perm = c->S_perm, a.L = c->L;
-  a.kcap = H < PRED_MAX_K ? H : PRED_MAX_K;
-  a.bg = c->bg_unit;
-  a.sigma2 = sssc ? dpar[DP_SIGMA2] : dpar[DP_SIGMA] * dpar[DP_SIGMA];
+  const PredLaunch l = fill_pred_args(c, a);
+  pred_sigma(c, dpar, a);
   a.add_noise = add_noise ? 1 : 0;
   a.mean = c->pred_buf;
   a.var = c->pred_buf + nd;
   a.status = c->pred_status;
-  int R = 1;
-  while (64 * R < D) R <<= 1;
-  const size_t lds = PRED_WAVES * pred_lds_doubles(a.kcap, sssc) * sizeof(double);
   {
     SpanGuard g(c, KID_MISC);
-    transpose_kernel<<<cdiv((i64)H * D, 256), 256, 0, c->stream>>>(c->W, D, H, c->pred_Wt);
-    if (sssc)
-      launch_predictive<true>(c, a, R, lds);
-    else
-      launch_predictive<false>(c, a, R, lds);
+    pred_transpose_W(c);
+    pred_dispatch(l.R, sssc, [&](auto r, auto s) {
+      predictive_kernel<decltype(r)::value, decltype(s)::value><<<cdiv(N, PRED_WAVES), 64 * PRED_WAVES, l.lds, c->stream>>>(a);
+    });
   }
   HIP_TRY(hipGetLastError());
   std::vector<int> status((size_t)N);
   HIP_TRY(hipMemcpyAsync(status.data(), c->pred_status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  counters[0] = counters[1] = 0;
-  for (i64 n = 0; n < N; n++) {
-    const int st = status[(size_t)n];
-    if ((st & 0xFF) == PRED_OVER_K)
-      return fail(EVOAMD_E_INVALID, "evoamd_predictive_moments: datapoint n = %lld holds a state with k = %d active latents, "
-                  "at most %d are supported (PRED_MAX_K)", (long long)n, st >> 8, PRED_MAX_K);
-    counters[0] += st == PRED_SINGULAR;
-    counters[1] += st == PRED_SKIPPED;
-  }
+  TRY(pred_tally("evoamd_predictive_moments", status.data(), N, counters));
   made_predictive(c, N);
   c->pred_D = D;
   return 0;
@@ -5870,28 +5947,13 @@ extern "C" int evoamd_download_predictive(evoamd_ctx *c, double *mean, double *v
 // the PredArgs and the launch shape of evoamd_predictive_moments; own buffers, sized before anything is launched; the
 // moments evoamd_predictive_moments left on the device stay as they are
 // ---------------------------------------------------------------------------------------
-template <bool SSSC>
-static void launch_predictive_score(evoamd_ctx *c, const PredScoreArgs &q, int R, unsigned grid, size_t lds) {
-  switch (R) {
-    case 1: predictive_score_kernel<1, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(q); break;
-    case 2: predictive_score_kernel<2, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(q); break;
-    case 4: predictive_score_kernel<4, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(q); break;
-    default: predictive_score_kernel<8, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(q); break;
-  }
-}
-
 extern "C" int evoamd_predictive_score(evoamd_ctx *c, const double *y_true, const uint8_t *query, int add_noise,
                                        const evoamd_pred_score_out *out, int64_t counters[4], double total[2]) {
-  REQUIRE(c && c->configured && c->have_data && c->have_params,
-          "evoamd_predictive_score: configure, upload data and set parameters first");
-  REQUIRE(!c->f32, "evoamd_predictive_score is not available in the float32 mode");
-  REQUIRE_KN(c);
+  TRY(readout_admit(c, "evoamd_predictive_score"));
   REQUIRE(y_true && query && counters && total, "evoamd_predictive_score: y_true, query, counters or total is NULL");
   const bool sssc = c->model == EVOAMD_MODEL_SSSC;
   REQUIRE(sssc || add_noise, "evoamd_predictive_score: EBSC without the noise term has variance 0 at every entry: nothing to score");
-  if (c->D > 64 * PRED_R_MAX)
-    return fail(EVOAMD_E_INVALID, "evoamd_predictive_score: D = %d, at most %d observables are supported (64 lanes x %d registers)",
-                c->D, 64 * PRED_R_MAX, PRED_R_MAX);
+  TRY(pred_admit_D(c, "evoamd_predictive_score"));
   HIP_TRY(hipSetDevice(c->device));
   const evoamd_pred_score_out o = out ? *out : evoamd_pred_score_out{};
   REQUIRE(!o.logp == !o.pit, "evoamd_predictive_score: logp and pit come together (both or neither)");
@@ -5908,28 +5970,15 @@ extern "C" int evoamd_predictive_score(evoamd_ctx *c, const double *y_true, cons
   TRY(c->pscore_list.ensure(c, n + 1));
   TRY(c->pred_Wt.ensure(c, (size_t)H * D));
   if (sssc) TRY(ensure_B(c));
-  // the scalars of the current Theta (a device update leaves them in the scalar block only)
-  double dpar[DP_COUNT];
+  double dpar[DP_COUNT];  // one synchronise for the scalars and the two uploads
   HIP_TRY(hipMemcpyAsync(dpar, c->dpar, DP_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(c->pscore_y, y_true, nd * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->pscore_q, query, nd, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   PredScoreArgs q = {};
   PredArgs &a = q.p;
-  a.mask = c->mask_infr;
-  a.row_any = c->mask_infr ? c->row_any : nullptr;
-  a.lpj = c->lpj;
-  a.states = c->states;
-  a.Wt = c->pred_Wt;
-  a.G = c->G;
-  a.Psi = c->Psi;
-  a.mus = c->mus;
-  a.Bm = c->Bm;
-  a.N = N;
-  a.D = D, a.H = H, a.HW = c->HW, a.S = c->S, a.S_perm = c->S_perm, a.L = c->L;
-  a.kcap = H < PRED_MAX_K ? H : PRED_MAX_K;
-  a.bg = c->bg_unit;
-  a.sigma2 = sssc ? dpar[DP_SIGMA2] : dpar[DP_SIGMA] * dpar[DP_SIGMA];
+  const PredLaunch l = fill_pred_args(c, a);
+  pred_sigma(c, dpar, a);
   a.add_noise = add_noise ? 1 : 0;
   q.y_true = c->pscore_y;
   q.query = c->pscore_q;
@@ -5939,18 +5988,14 @@ extern "C" int evoamd_predictive_score(evoamd_ctx *c, const double *y_true, cons
   double *partial = dd + n, *d_total = partial + 2 * (size_t)grid;
   q.count = c->pscore_i, q.nbad = q.count + n, a.status = q.count + 2 * n;
   q.list = c->pscore_list;
-  int R = 1;
-  while (64 * R < D) R <<= 1;
-  const size_t lds = PRED_WAVES * pred_lds_doubles(a.kcap, sssc) * sizeof(double);
   {
     SpanGuard g(c, KID_PRED_SCORE);
-    transpose_kernel<<<cdiv((i64)H * D, 256), 256, 0, c->stream>>>(c->W, D, H, c->pred_Wt);
+    pred_transpose_W(c);
     pred_score_visit_kernel<<<grid, 64 * PRED_WAVES, 0, c->stream>>>(q);
     pred_score_compact_kernel<<<1, PRED_COMPACT_THREADS, 0, c->stream>>>(a.status, N, q.list);
-    if (sssc)
-      launch_predictive_score<true>(c, q, R, grid, lds);
-    else
-      launch_predictive_score<false>(c, q, R, grid, lds);
+    pred_dispatch(l.R, sssc, [&](auto r, auto s) {
+      predictive_score_kernel<decltype(r)::value, decltype(s)::value><<<grid, 64 * PRED_WAVES, l.lds, c->stream>>>(q);
+    });
     pred_score_partials_kernel<<<cdiv((i64)grid, 256), 256, 0, c->stream>>>(q.logp_n, q.count, N, (i64)grid, partial);
     reduce_partials_kernel<<<1, 256, 0, c->stream>>>(partial, (i64)grid, d_total, 0);
     reduce_partials_kernel<<<1, 256, 0, c->stream>>>(partial + grid, (i64)grid, d_total + 1, 0);
@@ -5961,22 +6006,14 @@ extern "C" int evoamd_predictive_score(evoamd_ctx *c, const double *y_true, cons
   HIP_TRY(hipMemcpyAsync(ints.data(), c->pscore_i, 3 * n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   const int *status = ints.data() + 2 * n, *nbad = ints.data() + n;
-  int64_t cnt[4] = {0, 0, 0, 0};
-  for (i64 i = 0; i < N; i++) {
-    const int st = status[(size_t)i];
-    if ((st & 0xFF) == PRED_OVER_K)
-      return fail(EVOAMD_E_INVALID, "evoamd_predictive_score: datapoint n = %lld holds a state with k = %d active latents, "
-                  "at most %d are supported (PRED_MAX_K)", (long long)i, st >> 8, PRED_MAX_K);
-    cnt[0] += st == PRED_SINGULAR;
-    cnt[1] += st == PRED_SKIPPED;
-    cnt[2] += st == PRED_NOT_QUERIED;
-    cnt[3] += nbad[(size_t)i];
-  }
+  int64_t cnt[4] = {0, 0, 0, 0};  // the caller's counters are written once everything has arrived
+  TRY(pred_tally("evoamd_predictive_score", status, N, cnt, {PRED_NOT_QUERIED}));
+  for (size_t i = 0; i < n; i++) cnt[3] += nbad[i];
   if (per_entry) {
     HIP_TRY(hipMemcpyAsync(o.logp, q.logp, nd * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(o.pit, q.pit, nd * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   }
-  if (o.logp_n) HIP_TRY(hipMemcpyAsync(o.logp_n, q.logp_n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(fetch_if(c, o.logp_n, q.logp_n, n * sizeof(double)));
   HIP_TRY(hipMemcpyAsync(total, d_total, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (o.count) memcpy(o.count, ints.data(), n * sizeof(int));
@@ -6470,13 +6507,13 @@ extern "C" int evoamd_neighbour_bound(evoamd_ctx *c, int n_parents, unsigned fla
   std::vector<double> fp(N);
   HIP_TRY(hipMemcpyAsync(fp.data(), a.F_plus, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   const evoamd_nbound_out o = out ? *out : evoamd_nbound_out{};
-  if (o.F) HIP_TRY(hipMemcpyAsync(o.F, a.F, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (o.M) HIP_TRY(hipMemcpyAsync(o.M, a.M, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (o.best_score) HIP_TRY(hipMemcpyAsync(o.best_score, a.best_score, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (o.n_states) HIP_TRY(hipMemcpyAsync(o.n_states, a.n_states, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (o.n_capped) HIP_TRY(hipMemcpyAsync(o.n_capped, a.n_capped, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (o.best_parent) HIP_TRY(hipMemcpyAsync(o.best_parent, a.best_parent, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (o.best_flip) HIP_TRY(hipMemcpyAsync(o.best_flip, a.best_flip, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(fetch_if(c, o.F, a.F, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.M, a.M, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.best_score, a.best_score, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.n_states, a.n_states, N * sizeof(int)));
+  HIP_TRY(fetch_if(c, o.n_capped, a.n_capped, N * sizeof(int)));
+  HIP_TRY(fetch_if(c, o.best_parent, a.best_parent, N * sizeof(int)));
+  HIP_TRY(fetch_if(c, o.best_flip, a.best_flip, N * sizeof(int)));
   if (sssc)
     TRY(check_err(c));  // synchronises the stream
   else
@@ -6495,6 +6532,49 @@ extern "C" int evoamd_neighbour_bound(evoamd_ctx *c, int n_parents, unsigned fla
 // shape, the sizes), then the named stages: buffers, chains, fold, (admit) emission + candidate lpj + selection, fetch.
 // Without EVOAMD_AIS_ADMIT nothing of the EM state is written: B = Y W is (re)formed like by every lpj pass, nothing else.
 // ---------------------------------------------------------------------------------------
+// What evoamd_ais_loglik and evoamd_ais_posterior refuse alike, in this order (who: the caller's name in the texts): the
+// context and the chain counts in ais_admit, the schedule in ais_check_betas.  Two functions, because evoamd_ais_posterior
+// has refusals of its own (n_keep) between them.
+static int ais_admit(const evoamd_ctx *c, const char *who, int n_chains, int n_temps) {
+  if (!c->have_params) return fail(EVOAMD_E_INVALID, "%s: no Theta installed (set parameters first)", who);
+  if (!c->have_data) return fail(EVOAMD_E_INVALID, "%s: no data (upload data first)", who);
+  if (c->model != EVOAMD_MODEL_BSC)
+    return fail(EVOAMD_E_INVALID, "%s: ES3C is not supported (a collapsed Gibbs step needs a bordered k x k system per flip); the "
+                "call is for EBSC", who);
+  if (c->f32)
+    return fail(EVOAMD_E_INVALID, "%s is not available in the float32 mode (ebsc_f32): the chains run on the double B = Y W", who);
+  if (c->bg_unit) return fail(EVOAMD_E_INVALID, "%s: option background_unit is not supported (every latent is scanned)", who);
+  if (c->bsc_direct) return fail(EVOAMD_E_INVALID, "%s: bsc_direct keeps no G = W^T W, whose rows the Gibbs scan reads", who);
+  if (c->mask_infr)
+    return fail(EVOAMD_E_INVALID, "%s: incomplete data (masks resident) is not supported: the chains need one G for all datapoints", who);
+  if (c->H > 64 * AIS_MAX_NC)
+    return fail(EVOAMD_E_INVALID, "%s: H = %d, at most %d latents are supported (64 lanes x %d registers of c_j)", who, c->H,
+                64 * AIS_MAX_NC, AIS_MAX_NC);
+  if (n_chains < 1) return fail(EVOAMD_E_INVALID, "%s: n_chains = %d must be positive", who, n_chains);
+  if (n_temps < 1) return fail(EVOAMD_E_INVALID, "%s: n_temps = %d must be positive", who, n_temps);
+  return 0;
+}
+static int ais_check_betas(const char *who, int n_temps, const double *betas) {
+  if (!betas) return fail(EVOAMD_E_INVALID, "%s: betas is NULL", who);
+  if (betas[0] != 0.0) return fail(EVOAMD_E_INVALID, "%s: betas must start at 0 (betas[0] = %g)", who, betas[0]);
+  if (betas[n_temps] != 1.0) return fail(EVOAMD_E_INVALID, "%s: betas must end at 1 (betas[%d] = %g)", who, n_temps, betas[n_temps]);
+  for (int t = 1; t <= n_temps; t++)
+    if (!(betas[t] >= betas[t - 1]) || (t == 1 && !(betas[1] > 0.0)))
+      return fail(EVOAMD_E_INVALID, "%s: betas must not descend and must leave 0 at once (betas[%d] = %g after %g)", who, t, betas[t],
+                  betas[t - 1]);
+  return 0;
+}
+// the end of both fetch stages: waits for the stream, the chains' error word with the copies
+static int ais_wait(evoamd_ctx *c, const char *who) {
+  HIP_TRY(hipMemcpyAsync(c->h_err, c->err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->h_err[0] & EVO_ERR_BAD_ENTRY) {  // guard_index replaced a latent index that was out of range
+    HIP_TRY(hipMemsetAsync(c->err, 0, sizeof(int), c->stream));
+    return fail(EVOAMD_E_INVALID, "internal: %s: a latent index of a chain was out of range", who);
+  }
+  return 0;
+}
+
 struct AisPlan {
   bool reverse = false, admit = false;
   int C = 0, T = 0, nc = 1;  // nc: the chunk count the kernel is instantiated for (1, 2, 4, 8, 16)
@@ -6506,27 +6586,8 @@ static int ais_plan(const evoamd_ctx *c, int n_chains, int n_temps, const double
                     int Mprime, AisPlan &p) {
   REQUIRE(c && c->configured, "configure first");
   REQUIRE(!(flags & ~(unsigned)(EVOAMD_AIS_REVERSE | EVOAMD_AIS_ADMIT)), "evoamd_ais_loglik: unknown flag");
-  if (!c->have_params) return fail(EVOAMD_E_INVALID, "evoamd_ais_loglik: no Theta installed (set parameters first)");
-  if (!c->have_data) return fail(EVOAMD_E_INVALID, "evoamd_ais_loglik: no data (upload data first)");
-  REQUIRE(c->model == EVOAMD_MODEL_BSC, "evoamd_ais_loglik: ES3C is not supported (a collapsed Gibbs step needs a bordered k x k "
-                                        "system per flip); the call is for EBSC");
-  REQUIRE(!c->f32, "evoamd_ais_loglik is not available in the float32 mode (ebsc_f32): the chains run on the double B = Y W");
-  REQUIRE(!c->bg_unit, "evoamd_ais_loglik: option background_unit is not supported (every latent is scanned)");
-  REQUIRE(!c->bsc_direct, "evoamd_ais_loglik: bsc_direct keeps no G = W^T W, whose rows the Gibbs scan reads");
-  REQUIRE(!c->mask_infr, "evoamd_ais_loglik: incomplete data (masks resident) is not supported: the chains need one G for all datapoints");
-  if (c->H > 64 * AIS_MAX_NC)
-    return fail(EVOAMD_E_INVALID, "evoamd_ais_loglik: H = %d, at most %d latents are supported (64 lanes x %d registers of c_j)", c->H,
-                64 * AIS_MAX_NC, AIS_MAX_NC);
-  if (n_chains < 1) return fail(EVOAMD_E_INVALID, "evoamd_ais_loglik: n_chains = %d must be positive", n_chains);
-  if (n_temps < 1) return fail(EVOAMD_E_INVALID, "evoamd_ais_loglik: n_temps = %d must be positive", n_temps);
-  REQUIRE(betas, "evoamd_ais_loglik: betas is NULL");
-  if (betas[0] != 0.0) return fail(EVOAMD_E_INVALID, "evoamd_ais_loglik: betas must start at 0 (betas[0] = %g)", betas[0]);
-  if (betas[n_temps] != 1.0)
-    return fail(EVOAMD_E_INVALID, "evoamd_ais_loglik: betas must end at 1 (betas[%d] = %g)", n_temps, betas[n_temps]);
-  for (int t = 1; t <= n_temps; t++)
-    if (!(betas[t] >= betas[t - 1]) || (t == 1 && !(betas[1] > 0.0)))
-      return fail(EVOAMD_E_INVALID, "evoamd_ais_loglik: betas must not descend and must leave 0 at once (betas[%d] = %g after %g)", t,
-                  betas[t], betas[t - 1]);
+  TRY(ais_admit(c, "evoamd_ais_loglik", n_chains, n_temps));
+  TRY(ais_check_betas("evoamd_ais_loglik", n_temps, betas));
   p.reverse = (flags & EVOAMD_AIS_REVERSE) != 0, p.admit = (flags & EVOAMD_AIS_ADMIT) != 0;
   REQUIRE(!p.reverse || s_start, "evoamd_ais_loglik: EVOAMD_AIS_REVERSE needs s_start, the (N, HW) words of the starting states");
   REQUIRE(!(p.reverse && p.admit), "evoamd_ais_loglik: EVOAMD_AIS_ADMIT with EVOAMD_AIS_REVERSE: a reverse chain ends at the prior, "
@@ -6644,22 +6705,17 @@ static int ais_fetch(evoamd_ctx *c, const AisPlan &p, const evoamd_ais_out &o) {
   const size_t N = (size_t)c->N, NC = N * (size_t)p.C;
   std::vector<double> ll(N);
   HIP_TRY(hipMemcpyAsync(ll.data(), b.ll, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (o.ess) HIP_TRY(hipMemcpyAsync(o.ess, b.ess, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (o.log_w_mean) HIP_TRY(hipMemcpyAsync(o.log_w_mean, b.lw_mean, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (o.log_w_min) HIP_TRY(hipMemcpyAsync(o.log_w_min, b.lw_min, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (o.log_w_max) HIP_TRY(hipMemcpyAsync(o.log_w_max, b.lw_max, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (o.n_flips) HIP_TRY(hipMemcpyAsync(o.n_flips, b.n_flips, N * sizeof(i64), hipMemcpyDeviceToHost, c->stream));
-  if (o.log_w) HIP_TRY(hipMemcpyAsync(o.log_w, b.log_w, NC * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (o.final_words) HIP_TRY(hipMemcpyAsync(o.final_words, b.fin, NC * c->HW * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-  if (o.chain_flips) HIP_TRY(hipMemcpyAsync(o.chain_flips, b.flips, NC * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (p.admit && o.F_before) HIP_TRY(hipMemcpyAsync(o.F_before, b.F_before, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (p.admit && o.F_after) HIP_TRY(hipMemcpyAsync(o.F_after, b.F_after, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->h_err, c->err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->h_err[0] & EVO_ERR_BAD_ENTRY) {  // guard_index replaced a latent index that was out of range
-    HIP_TRY(hipMemsetAsync(c->err, 0, sizeof(int), c->stream));
-    return fail(EVOAMD_E_INVALID, "internal: evoamd_ais_loglik: a latent index of a chain was out of range");
-  }
+  HIP_TRY(fetch_if(c, o.ess, b.ess, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.log_w_mean, b.lw_mean, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.log_w_min, b.lw_min, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.log_w_max, b.lw_max, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.n_flips, b.n_flips, N * sizeof(i64)));
+  HIP_TRY(fetch_if(c, o.log_w, b.log_w, NC * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.final_words, b.fin, NC * c->HW * sizeof(u64)));
+  HIP_TRY(fetch_if(c, o.chain_flips, b.flips, NC * sizeof(int)));
+  if (p.admit) HIP_TRY(fetch_if(c, o.F_before, b.F_before, N * sizeof(double)));
+  if (p.admit) HIP_TRY(fetch_if(c, o.F_after, b.F_after, N * sizeof(double)));
+  TRY(ais_wait(c, "evoamd_ais_loglik"));
   if (o.ll) memcpy(o.ll, ll.data(), N * sizeof(double));
   if (o.sum) {
     double s = 0.0;
@@ -6702,30 +6758,10 @@ struct AisPostPlan {
 static int ais_post_plan(const evoamd_ctx *c, int n_chains, int n_temps, int n_keep, const double *betas, int64_t block_datapoints,
                          bool mean, AisPostPlan &p) {
   REQUIRE(c && c->configured, "configure first");
-  if (!c->have_params) return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: no Theta installed (set parameters first)");
-  if (!c->have_data) return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: no data (upload data first)");
-  REQUIRE(c->model == EVOAMD_MODEL_BSC, "evoamd_ais_posterior: ES3C is not supported (a collapsed Gibbs step needs a bordered k x k "
-                                        "system per flip); the call is for EBSC");
-  REQUIRE(!c->f32, "evoamd_ais_posterior is not available in the float32 mode (ebsc_f32): the chains run on the double B = Y W");
-  REQUIRE(!c->bg_unit, "evoamd_ais_posterior: option background_unit is not supported (every latent is scanned)");
-  REQUIRE(!c->bsc_direct, "evoamd_ais_posterior: bsc_direct keeps no G = W^T W, whose rows the Gibbs scan reads");
-  REQUIRE(!c->mask_infr,
-          "evoamd_ais_posterior: incomplete data (masks resident) is not supported: the chains need one G for all datapoints");
-  if (c->H > 64 * AIS_MAX_NC)
-    return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: H = %d, at most %d latents are supported (64 lanes x %d registers of c_j)", c->H,
-                64 * AIS_MAX_NC, AIS_MAX_NC);
-  if (n_chains < 1) return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: n_chains = %d must be positive", n_chains);
-  if (n_temps < 1) return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: n_temps = %d must be positive", n_temps);
+  TRY(ais_admit(c, "evoamd_ais_posterior", n_chains, n_temps));
   if (n_keep < 1) return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: n_keep = %d must be positive", n_keep);
   REQUIRE((i64)n_temps + n_keep < 2147483647LL, "evoamd_ais_posterior: n_temps + n_keep must fit in int32");
-  REQUIRE(betas, "evoamd_ais_posterior: betas is NULL");
-  if (betas[0] != 0.0) return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: betas must start at 0 (betas[0] = %g)", betas[0]);
-  if (betas[n_temps] != 1.0)
-    return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: betas must end at 1 (betas[%d] = %g)", n_temps, betas[n_temps]);
-  for (int t = 1; t <= n_temps; t++)
-    if (!(betas[t] >= betas[t - 1]) || (t == 1 && !(betas[1] > 0.0)))
-      return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: betas must not descend and must leave 0 at once (betas[%d] = %g after %g)", t,
-                  betas[t], betas[t - 1]);
+  TRY(ais_check_betas("evoamd_ais_posterior", n_temps, betas));
   REQUIRE((i64)c->N * n_chains < 2147483647LL, "evoamd_ais_posterior: N * n_chains must fit in int32");
   const size_t row = (size_t)n_chains * 64 * c->HW;  // doubles of one datapoint's rows
   const i64 fit = (i64)(AIS_POST_ROWS_BYTES / (row * sizeof(double)));
@@ -6846,32 +6882,23 @@ static int ais_post_mean_stage(evoamd_ctx *c, const AisPostPlan &p) {
 static int ais_post_fetch(evoamd_ctx *c, const AisPostPlan &p, const evoamd_ais_post_out &o) {
   const AisPostBufs b = ais_post_views(c, p);
   const size_t N = (size_t)c->N, NC = N * (size_t)p.C, H = (size_t)c->H;
-  auto get = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
-    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-  };
-  HIP_TRY(get(o.p, b.p, N * H * sizeof(double)));
-  HIP_TRY(get(o.p_se, b.p_se, N * H * sizeof(double)));
-  HIP_TRY(get(o.count, b.count, N * sizeof(double)));
-  HIP_TRY(get(o.map_lpj, b.map_lpj, N * sizeof(double)));
-  HIP_TRY(get(o.map_state, b.map_state, N * c->HW * sizeof(u64)));
-  HIP_TRY(get(o.ll, b.ll, N * sizeof(double)));
-  HIP_TRY(get(o.ess, b.ess, N * sizeof(double)));
-  HIP_TRY(get(o.log_w_mean, b.lw_mean, N * sizeof(double)));
-  HIP_TRY(get(o.log_w_min, b.lw_min, N * sizeof(double)));
-  HIP_TRY(get(o.log_w_max, b.lw_max, N * sizeof(double)));
-  HIP_TRY(get(o.n_flips, b.n_flips, N * sizeof(i64)));
-  if (p.mean) HIP_TRY(get(o.mean, b.mean, N * c->D * sizeof(double)));
-  HIP_TRY(get(o.log_w, b.log_w, NC * sizeof(double)));
-  HIP_TRY(get(o.chain_map_lpj, b.best_lpj, NC * sizeof(double)));
-  HIP_TRY(get(o.chain_map_state, b.best, NC * c->HW * sizeof(u64)));
-  HIP_TRY(get(o.chain_flips, b.flips, NC * sizeof(int)));
-  HIP_TRY(hipMemcpyAsync(c->h_err, c->err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->h_err[0] & EVO_ERR_BAD_ENTRY) {  // guard_index replaced a latent index that was out of range
-    HIP_TRY(hipMemsetAsync(c->err, 0, sizeof(int), c->stream));
-    return fail(EVOAMD_E_INVALID, "internal: evoamd_ais_posterior: a latent index of a chain was out of range");
-  }
-  return 0;
+  HIP_TRY(fetch_if(c, o.p, b.p, N * H * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.p_se, b.p_se, N * H * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.count, b.count, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.map_lpj, b.map_lpj, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.map_state, b.map_state, N * c->HW * sizeof(u64)));
+  HIP_TRY(fetch_if(c, o.ll, b.ll, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.ess, b.ess, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.log_w_mean, b.lw_mean, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.log_w_min, b.lw_min, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.log_w_max, b.lw_max, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.n_flips, b.n_flips, N * sizeof(i64)));
+  if (p.mean) HIP_TRY(fetch_if(c, o.mean, b.mean, N * c->D * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.log_w, b.log_w, NC * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.chain_map_lpj, b.best_lpj, NC * sizeof(double)));
+  HIP_TRY(fetch_if(c, o.chain_map_state, b.best, NC * c->HW * sizeof(u64)));
+  HIP_TRY(fetch_if(c, o.chain_flips, b.flips, NC * sizeof(int)));
+  return ais_wait(c, "evoamd_ais_posterior");
 }
 
 extern "C" int evoamd_ais_posterior(evoamd_ctx *c, int n_chains, int n_temps, int n_keep, const double *betas, uint64_t seed,
@@ -6888,122 +6915,66 @@ extern "C" int evoamd_ais_posterior(evoamd_ctx *c, int n_chains, int n_temps, in
 
 // posterior samples (kernels_posterior_sample.hpp): own buffers; of the EM state only B = Y W is (re)formed, like every lpj pass
 // ---------------------------------------------------------------------------------------
-template <bool SSSC>
-static void launch_posterior_sample(evoamd_ctx *c, const PsampArgs &q, int R, size_t lds) {
-  const unsigned grid = cdiv(q.p.N, PRED_WAVES);
-  switch (R) {
-    case 1: posterior_sample_kernel<1, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(q); break;
-    case 2: posterior_sample_kernel<2, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(q); break;
-    case 4: posterior_sample_kernel<4, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(q); break;
-    default: posterior_sample_kernel<8, SSSC><<<grid, 64 * PRED_WAVES, lds, c->stream>>>(q); break;
-  }
-}
-
 extern "C" int evoamd_posterior_sample(evoamd_ctx *c, int n_samples, uint64_t seed, uint64_t first_index, int keep_mask,
                                        int fill_all, int add_noise, int64_t counters[4]) {
-  REQUIRE(c && c->configured && c->have_data && c->have_params,
-          "evoamd_posterior_sample: configure, upload data and set parameters first");
-  REQUIRE(!c->f32, "evoamd_posterior_sample is not available in the float32 mode");
-  REQUIRE_KN(c);
+  TRY(readout_admit(c, "evoamd_posterior_sample"));
   REQUIRE(counters, "evoamd_posterior_sample: counters is NULL");
   REQUIRE(n_samples >= 1, "evoamd_posterior_sample: n_samples must be positive");
   const bool sssc = c->model == EVOAMD_MODEL_SSSC;
   const int all = PSAMP_KEEP_SLOT | PSAMP_KEEP_S | PSAMP_KEEP_Z | PSAMP_KEEP_Y;
   REQUIRE(keep_mask != 0 && (keep_mask & ~all) == 0, "evoamd_posterior_sample: keep_mask must name at least one of the outputs (bits 1, 2, 4, 8)");
   REQUIRE(sssc || !(keep_mask & PSAMP_KEEP_Z), "evoamd_posterior_sample: z is an ES3C output (EBSC: z = s)");
-  if (c->D > 64 * PRED_R_MAX)
-    return fail(EVOAMD_E_INVALID, "evoamd_posterior_sample: D = %d, at most %d observables are supported (64 lanes x %d registers)",
-                c->D, 64 * PRED_R_MAX, PRED_R_MAX);
+  TRY(pred_admit_D(c, "evoamd_posterior_sample"));
   HIP_TRY(hipSetDevice(c->device));
   const i64 N = c->N, T = n_samples;
   const int D = c->D, H = c->H, HW = c->HW;
   made_posterior_samples(c, -1);
   // ---- do the outputs fit?  Decided before anything is released, allocated or launched.
   const size_t nt = (size_t)N * (size_t)T;
-  {
-    size_t grow = 0, released = 0;
-    auto plan = [&](bool wanted, size_t have, size_t want, size_t elem) {
-      if (wanted && want > have) grow += want * elem, released += have * elem;
-    };
-    plan(keep_mask & PSAMP_KEEP_SLOT, c->ps_slot.size(), nt, sizeof(int));
-    plan(keep_mask & PSAMP_KEEP_S, c->ps_s.size(), nt * HW, sizeof(u64));
-    plan(keep_mask & PSAMP_KEEP_Z, c->ps_z.size(), nt * H, sizeof(double));
-    plan(keep_mask & PSAMP_KEEP_Y, c->ps_y.size(), nt * D, sizeof(double));
-    plan(true, c->ps_status.size(), (size_t)N, sizeof(int));
-    plan(true, c->pred_Wt.size(), (size_t)H * D, sizeof(double));
-    if (grow) {
-      size_t free_b = 0, total_b = 0;
-      HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-      if (grow > free_b + released)
-        return fail(EVOAMD_E_INVALID, "evoamd_posterior_sample: the outputs asked for need %zu bytes of device memory, %zu are free "
-                    "(fewer draws per call, or fewer arrays in keep)", grow, free_b + released);
-    }
-  }
+  FitList outputs;
+  if (keep_mask & PSAMP_KEEP_SLOT) outputs.add(c->ps_slot, nt);
+  if (keep_mask & PSAMP_KEEP_S) outputs.add(c->ps_s, nt * HW);
+  if (keep_mask & PSAMP_KEEP_Z) outputs.add(c->ps_z, nt * H);
+  if (keep_mask & PSAMP_KEEP_Y) outputs.add(c->ps_y, nt * D);
+  outputs.add(c->ps_status, (size_t)N);
+  outputs.add(c->pred_Wt, (size_t)H * D);
+  size_t avail;
+  TRY(outputs.measure(avail));
+  if (outputs.grow > avail)
+    return fail(EVOAMD_E_INVALID, "evoamd_posterior_sample: the outputs asked for need %zu bytes of device memory, %zu are free "
+                "(fewer draws per call, or fewer arrays in keep)", outputs.grow, avail);
   if (sssc) TRY(ensure_B(c));
-  if (keep_mask & PSAMP_KEEP_SLOT) TRY(c->ps_slot.ensure(c, nt));
-  if (keep_mask & PSAMP_KEEP_S) TRY(c->ps_s.ensure(c, nt * HW));
-  if (keep_mask & PSAMP_KEEP_Z) TRY(c->ps_z.ensure(c, nt * H));
-  if (keep_mask & PSAMP_KEEP_Y) TRY(c->ps_y.ensure(c, nt * D));
-  TRY(c->ps_status.ensure(c, (size_t)N));
-  TRY(c->pred_Wt.ensure(c, (size_t)H * D));
-  // the scalars of the current Theta (a device update leaves them in the scalar block only)
+  TRY(outputs.ensure_all(c));
   double dpar[DP_COUNT];
   HIP_TRY(hipMemcpyAsync(dpar, c->dpar, DP_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   PsampArgs q = {};
   PredArgs &a = q.p;
-  a.mask = c->mask_infr;
-  a.row_any = c->mask_infr ? c->row_any : nullptr;
-  a.lpj = c->lpj;
-  a.states = c->states;
-  a.Wt = c->pred_Wt;
-  a.G = c->G;
-  a.Psi = c->Psi;
-  a.mus = c->mus;
-  a.Bm = c->Bm;
-  a.N = N;
-  a.D = D, a.H = H, a.HW = HW, a.S = c->S, a.S_perm = c->S_perm, a.L = c->L;
-  a.kcap = H < PRED_MAX_K ? H : PRED_MAX_K;
-  a.bg = c->bg_unit;
-  a.sigma2 = sssc ? dpar[DP_SIGMA2] : dpar[DP_SIGMA] * dpar[DP_SIGMA];
+  const PredLaunch l = fill_pred_args(c, a);
+  q.sigma = pred_sigma(c, dpar, a);
   a.status = c->ps_status;
   q.Y = c->Y;
   q.ldY = c->ldY;
   q.T = T;
   q.seed = seed, q.first_index = first_index;
   q.fill_all = fill_all ? 1 : 0, q.add_noise = add_noise ? 1 : 0;
-  q.sigma = sssc ? sqrt(dpar[DP_SIGMA2]) : dpar[DP_SIGMA];
   q.slot = (keep_mask & PSAMP_KEEP_SLOT) ? c->ps_slot.get() : nullptr;
   q.s = (keep_mask & PSAMP_KEEP_S) ? c->ps_s.get() : nullptr;
   q.z = (keep_mask & PSAMP_KEEP_Z) ? c->ps_z.get() : nullptr;
   q.y = (keep_mask & PSAMP_KEEP_Y) ? c->ps_y.get() : nullptr;
-  int R = 1;
-  while (64 * R < D) R <<= 1;
-  const size_t lds = PRED_WAVES * pred_lds_doubles(a.kcap, sssc) * sizeof(double);
   {
     SpanGuard g(c, KID_POSTERIOR_SAMPLE);
-    transpose_kernel<<<cdiv((i64)H * D, 256), 256, 0, c->stream>>>(c->W, D, H, c->pred_Wt);
-    if (sssc)
-      launch_posterior_sample<true>(c, q, R, lds);
-    else
-      launch_posterior_sample<false>(c, q, R, lds);
+    pred_transpose_W(c);
+    pred_dispatch(l.R, sssc, [&](auto r, auto s) {
+      posterior_sample_kernel<decltype(r)::value, decltype(s)::value><<<cdiv(N, PRED_WAVES), 64 * PRED_WAVES, l.lds, c->stream>>>(q);
+    });
   }
   HIP_TRY(hipGetLastError());
   DBG_SYNC(c, "posterior_sample");
   std::vector<int> status((size_t)N);
   HIP_TRY(hipMemcpyAsync(status.data(), c->ps_status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  counters[0] = counters[1] = counters[2] = counters[3] = 0;
-  for (i64 n = 0; n < N; n++) {
-    const int st = status[(size_t)n];
-    if ((st & 0xFF) == PRED_OVER_K)
-      return fail(EVOAMD_E_INVALID, "evoamd_posterior_sample: datapoint n = %lld holds a state with k = %d active latents, "
-                  "at most %d are supported (PRED_MAX_K)", (long long)n, st >> 8, PRED_MAX_K);
-    counters[0] += st == PRED_SINGULAR;
-    counters[1] += st == PRED_SKIPPED;
-    counters[2] += st == PSAMP_NOT_PD;
-    counters[3] += st == PSAMP_BAD_WEIGHTS;
-  }
+  TRY(pred_tally("evoamd_posterior_sample", status.data(), N, counters, {PSAMP_NOT_PD, PSAMP_BAD_WEIGHTS}));
   c->ps_N = N, c->ps_T = T, c->ps_D = D, c->ps_H = H;
   made_posterior_samples(c, keep_mask);
   return 0;
@@ -7026,10 +6997,7 @@ extern "C" int evoamd_download_posterior_samples(evoamd_ctx *c, int what, void *
     default: return fail(EVOAMD_E_INVALID, "evoamd_download_posterior_samples: what must be EVOAMD_PSAMP_SLOT, _S, _Z or _Y");
   }
   REQUIRE(c->ps_keep & bit, "evoamd_download_posterior_samples: the last evoamd_posterior_sample did not keep this output");
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return download_view(c, out, src, bytes);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -7055,150 +7023,183 @@ static void launch_lle_proposal(evoamd_ctx *c, const LleArgs &a, size_t lds) {
   }
 }
 
-extern "C" int evoamd_loglik_estimate(evoamd_ctx *c, int n_samples, uint64_t seed, uint64_t first_index, double prior_mix,
-                                      int keep_draws, double *ll_out, double *F_out, double *mass_out, double *ess_out,
-                                      int32_t *n_outside_out, int64_t counters[2], double *sum_out) {
-  REQUIRE(c && c->configured && c->have_data && c->have_params,
-          "evoamd_loglik_estimate: configure, upload data and set parameters first");
-  REQUIRE(!c->f32, "evoamd_loglik_estimate is not available in the float32 mode");
-  REQUIRE_KN(c);
+// Plan (every refusal that reads the arguments and the geometry, the sizes), then the named stages: prepare (with the one
+// refusal that needs the device: do the buffers fit?), the passes (proposal -> candidate lpj -> fold), finish, fetch.
+struct LlePlan {
+  bool sssc = false, keep = false;
+  i64 T = 0;
+  int Hv = 0;  // latents that vary
+  double lam = 0.0;
+  unsigned nb = 1;                           // workgroups of the fold and the finish
+  size_t lds = 0, nt = 0;                    // LDS of the proposal kernel; N x T
+  size_t n_d = 0, n_i = 0, n_rho = 0;        // elements of lle_d / lle_i / lle_rho
+};
+
+static int lle_plan(const evoamd_ctx *c, int n_samples, double prior_mix, int keep_draws, const int64_t *counters,
+                    const double *sum_out, LlePlan &p) {
+  TRY(readout_admit(c, "evoamd_loglik_estimate"));
   REQUIRE(counters && sum_out, "evoamd_loglik_estimate: counters or sum_out is NULL");
   REQUIRE(n_samples >= 1, "evoamd_loglik_estimate: n_samples must be positive");
   REQUIRE(prior_mix > 0.0 && prior_mix <= 1.0, "evoamd_loglik_estimate: prior_mix must be in (0, 1]");
-  const bool sssc = c->model == EVOAMD_MODEL_SSSC;
-  const i64 N = c->N, T = n_samples;
-  const int H = c->H, HW = c->HW, Cmax = c->Cmax, Hv = H - (c->bg_unit ? 1 : 0);
-  if (HW > LLE_MAX_KH)
-    return fail(EVOAMD_E_INVALID, "evoamd_loglik_estimate: H = %d, at most %d latents are supported (64 lanes x %d registers)", H,
+  p.sssc = c->model == EVOAMD_MODEL_SSSC, p.keep = keep_draws != 0;
+  p.T = n_samples, p.Hv = c->H - (c->bg_unit ? 1 : 0), p.lam = prior_mix;
+  if (c->HW > LLE_MAX_KH)
+    return fail(EVOAMD_E_INVALID, "evoamd_loglik_estimate: H = %d, at most %d latents are supported (64 lanes x %d registers)", c->H,
                 64 * LLE_MAX_KH, LLE_MAX_KH);
-  REQUIRE(Hv >= 1, "evoamd_loglik_estimate: no latent varies");
-  const size_t lds = (size_t)LLE_WAVES * (size_t)(c->L + c->S) * sizeof(double);
-  if (lds > LLE_LDS_MAX)
+  REQUIRE(p.Hv >= 1, "evoamd_loglik_estimate: no latent varies");
+  p.lds = (size_t)LLE_WAVES * (size_t)(c->L + c->S) * sizeof(double);
+  if (p.lds > LLE_LDS_MAX)
     return fail(EVOAMD_E_INVALID, "evoamd_loglik_estimate: S_perm + 2 S = %d, at most %d weights and hashes fit the LDS slice of a "
                 "datapoint", c->L + c->S, (int)(LLE_LDS_MAX / (LLE_WAVES * sizeof(double))));
-  HIP_TRY(hipSetDevice(c->device));
-  made_loglik_draws(c, -1);
-  const size_t nt = (size_t)N * (size_t)T, nc = (size_t)N * (size_t)Cmax;
-  const unsigned nb = cdiv(N, 4);
-  // F | m | z | q | ll | mass | ess | all-zero lpj (N each) | sum (1) | partial (nb) | log r (N x Cmax)
-  const size_t need_d = 8 * (size_t)N + 1 + nb + nc;
-  const size_t need_i = 2 * (size_t)N + nc;  // status | n_outside | t (N x Cmax)
-  const size_t need_rho = (size_t)N * 64 * (size_t)lle_kh(HW);
-  // ---- do the buffers fit?  Decided before anything is released, allocated or launched.
-  {
-    size_t grow = 0, released = 0;
-    auto plan = [&](bool wanted, size_t have, size_t want, size_t elem) {
-      if (wanted && want > have) grow += want * elem, released += have * elem;
-    };
-    plan(keep_draws, c->lle_keep_s.size(), nt * HW, sizeof(u64));
-    plan(keep_draws, c->lle_keep_in.size(), nt, sizeof(uint8_t));
-    plan(keep_draws, c->lle_keep_d.size(), 2 * nt, sizeof(double));
-    plan(true, c->lle_d.size(), need_d, sizeof(double));
-    plan(true, c->lle_i.size(), need_i, sizeof(int));
-    plan(true, c->lle_flags.size(), (size_t)N, sizeof(unsigned));
-    plan(true, c->lle_rho.size(), need_rho, sizeof(double));
-    plan(true, c->lle_hash.size(), (size_t)N * c->S, sizeof(u64));
-    if (grow) {
-      size_t free_b = 0, total_b = 0;
-      HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-      if (grow > free_b + released)
-        return fail(EVOAMD_E_INVALID, "evoamd_loglik_estimate: the buffers asked for need %zu bytes of device memory, %zu are free "
-                    "(fewer draws per call, or keep_draws = 0)", grow, free_b + released);
-    }
-  }
+  const size_t N = (size_t)c->N, nc = N * (size_t)c->Cmax;
+  p.nt = N * (size_t)p.T;
+  p.nb = cdiv(c->N, 4);
+  p.n_d = 8 * N + 1 + p.nb + nc;  // F | m | z | q | ll | mass | ess | all-zero lpj (N each) | sum (1) | partial (nb) | log r (N x Cmax)
+  p.n_i = 2 * N + nc;             // status | n_outside | t (N x Cmax)
+  p.n_rho = N * 64 * (size_t)lle_kh(c->HW);
+  return 0;
+}
+
+// the views into the call's buffers
+struct LleBufs {
+  double *F, *run_m, *run_z, *run_q, *ll, *mass, *ess, *az, *sum, *part, *logr, *keep_logr, *keep_lpj;
+  int *status, *n_out, *tix;
+};
+static LleBufs lle_views(const evoamd_ctx *c, const LlePlan &p) {
+  const size_t N = (size_t)c->N;
+  LleBufs b;
+  b.F = c->lle_d, b.run_m = b.F + N, b.run_z = b.run_m + N, b.run_q = b.run_z + N, b.ll = b.run_q + N, b.mass = b.ll + N;
+  b.ess = b.mass + N, b.az = b.ess + N, b.sum = b.az + N, b.part = b.sum + 1, b.logr = b.part + p.nb;
+  b.status = c->lle_i, b.n_out = b.status + N, b.tix = b.n_out + N;
+  b.keep_logr = p.keep ? c->lle_keep_d.get() : nullptr, b.keep_lpj = p.keep ? b.keep_logr + p.nt : nullptr;
+  return b;
+}
+
+// ---- stage: every buffer (do they fit?  Decided before anything is released, allocated or launched), the candidate batch
+// given up, F of K^n and the lpj of the all-zero state
+static int lle_prepare(evoamd_ctx *c, const LlePlan &p) {
+  const size_t N = (size_t)c->N;
+  FitList bufs;
+  bufs.add(c->lle_d, p.n_d), bufs.add(c->lle_i, p.n_i), bufs.add(c->lle_flags, N);
+  bufs.add(c->lle_rho, p.n_rho), bufs.add(c->lle_hash, N * c->S);
+  if (p.keep) bufs.add(c->lle_keep_s, p.nt * c->HW), bufs.add(c->lle_keep_in, p.nt), bufs.add(c->lle_keep_d, 2 * p.nt);
+  size_t avail;
+  TRY(bufs.measure(avail));
+  if (bufs.grow > avail)
+    return fail(EVOAMD_E_INVALID, "evoamd_loglik_estimate: the buffers asked for need %zu bytes of device memory, %zu are free "
+                "(fewer draws per call, or keep_draws = 0)", bufs.grow, avail);
   TRY(ensure_B(c));
-  if (sssc) TRY(ensure_lists(c, N * (i64)Cmax));
-  TRY(c->lle_d.ensure(c, need_d));
-  TRY(c->lle_i.ensure(c, need_i));
-  TRY(c->lle_flags.ensure(c, (size_t)N));
-  TRY(c->lle_rho.ensure(c, need_rho));
-  TRY(c->lle_hash.ensure(c, (size_t)N * c->S));
-  if (keep_draws) {
-    TRY(c->lle_keep_s.ensure(c, nt * HW));
-    TRY(c->lle_keep_in.ensure(c, nt));
-    TRY(c->lle_keep_d.ensure(c, 2 * nt));
+  if (p.sssc) TRY(ensure_lists(c, c->N * (i64)c->Cmax));
+  TRY(bufs.ensure_all(c));
+  if (p.keep) {
     // a datapoint without an estimate keeps these: s zero, inside 0, log r and lpj NaN (all bits set); so does the lpj
     // of an inside draw
-    HIP_TRY(hipMemsetAsync(c->lle_keep_s, 0, nt * HW * sizeof(u64), c->stream));
-    HIP_TRY(hipMemsetAsync(c->lle_keep_in, 0, nt, c->stream));
-    HIP_TRY(hipMemsetAsync(c->lle_keep_d, 0xFF, 2 * nt * sizeof(double), c->stream));
+    HIP_TRY(hipMemsetAsync(c->lle_keep_s, 0, p.nt * c->HW * sizeof(u64), c->stream));
+    HIP_TRY(hipMemsetAsync(c->lle_keep_in, 0, p.nt, c->stream));
+    HIP_TRY(hipMemsetAsync(c->lle_keep_d, 0xFF, 2 * p.nt * sizeof(double), c->stream));
   }
-  HIP_TRY(hipMemsetAsync(c->lle_flags, 0, (size_t)N * sizeof(unsigned), c->stream));
-  double *dF = c->lle_d, *run_m = dF + N, *run_z = run_m + N, *run_q = run_z + N, *d_ll = run_q + N, *d_mass = d_ll + N;
-  double *d_ess = d_mass + N, *d_az = d_ess + N, *d_sum = d_az + N, *d_part = d_sum + 1, *d_logr = d_part + nb;
-  int *d_status = c->lle_i, *d_nout = d_status + N, *d_tix = d_nout + N;
-  double *keep_logr = keep_draws ? c->lle_keep_d.get() : nullptr, *keep_lpj = keep_draws ? keep_logr + nt : nullptr;
+  HIP_TRY(hipMemsetAsync(c->lle_flags, 0, N * sizeof(unsigned), c->stream));
+  const LleBufs b = lle_views(c, p);
   drop_cand_batch(c);  // from here on the candidate buffers hold importance draws
-  {
-    SpanGuard g(c, KID_LLE_FOLD);
-    posterior_score_kernel<<<cdiv(N, SCORE_WAVES), 64 * SCORE_WAVES, 0, c->stream>>>(c->lpj, c->states, N, c->L, c->S, c->S_perm, HW,
-                                                                                     dF, nullptr, nullptr, nullptr, nullptr);
-    allzero_lpj_kernel<<<cdiv(N, 256), 256, 0, c->stream>>>(c->yy, N, c->dpar, sssc, d_az, 1, c->lle_flags, c->err);
-    HIP_TRY(hipGetLastError());
-  }
+  SpanGuard g(c, KID_LLE_FOLD);
+  posterior_score_kernel<<<cdiv(c->N, SCORE_WAVES), 64 * SCORE_WAVES, 0, c->stream>>>(c->lpj, c->states, c->N, c->L, c->S, c->S_perm,
+                                                                                      c->HW, b.F, nullptr, nullptr, nullptr, nullptr);
+  allzero_lpj_kernel<<<cdiv(c->N, 256), 256, 0, c->stream>>>(c->yy, c->N, c->dpar, p.sssc, b.az, 1, c->lle_flags, c->err);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---- stage: the passes of at most Cmax draws each: proposal -> lpj of the outside draws -> fold
+static int lle_passes_stage(evoamd_ctx *c, const LlePlan &p, uint64_t seed, uint64_t first_index) {
+  const LleBufs b = lle_views(c, p);
+  const i64 N = c->N;
+  const int Cmax = c->Cmax;
   LleArgs a = {};
   a.lpj = c->lpj, a.states = c->states;
-  a.pies = sssc ? c->pies.get() : nullptr;
+  a.pies = p.sssc ? c->pies.get() : nullptr;
   a.dpar = c->dpar;
   a.row_any = c->mask_infr ? c->row_any.get() : nullptr;
-  a.N = N, a.T = T;
-  a.H = H, a.Hv = Hv, a.HW = HW, a.S = c->S, a.S_perm = c->S_perm, a.L = c->L, a.bg = c->bg_unit ? 1 : 0, a.Cmax = Cmax;
-  a.lam = prior_mix, a.oml = 1.0 - prior_mix;
+  a.N = N, a.T = p.T;
+  a.H = c->H, a.Hv = p.Hv, a.HW = c->HW, a.S = c->S, a.S_perm = c->S_perm, a.L = c->L, a.bg = c->bg_unit ? 1 : 0, a.Cmax = Cmax;
+  a.lam = p.lam, a.oml = 1.0 - p.lam;
   a.seed = seed, a.first_index = first_index;
   a.cand = c->cand, a.cand_dig = (c->use_digest && c->cand_dig) ? c->cand_dig.get() : nullptr, a.counts = c->cand_counts;
-  a.logr = d_logr, a.tix = d_tix, a.status = d_status, a.rho = c->lle_rho, a.hash = c->lle_hash;
-  a.keep_s = keep_draws ? c->lle_keep_s.get() : nullptr;
-  a.keep_inside = keep_draws ? c->lle_keep_in.get() : nullptr;
-  a.keep_logr = keep_logr;
+  a.logr = b.logr, a.tix = b.tix, a.status = b.status, a.rho = c->lle_rho, a.hash = c->lle_hash;
+  a.keep_s = p.keep ? c->lle_keep_s.get() : nullptr;
+  a.keep_inside = p.keep ? c->lle_keep_in.get() : nullptr;
+  a.keep_logr = b.keep_logr;
   const LevelHints lv;  // known_tag 2: nothing is known about the draws
-  for (i64 t0 = 0; t0 < T; t0 += Cmax) {
+  for (i64 t0 = 0; t0 < p.T; t0 += Cmax) {
     a.t0 = t0;
-    a.P = (int)std::min<i64>(Cmax, T - t0);
+    a.P = (int)std::min<i64>(Cmax, p.T - t0);
     {
       SpanGuard g(c, KID_LLE_PROPOSAL);
-      launch_lle_proposal(c, a, lds);
+      launch_lle_proposal(c, a, p.lds);
       HIP_TRY(hipGetLastError());
       DBG_SYNC(c, "loglik_estimate proposal");
     }
     on_cand_installed(c, /*near_parents=*/false);
     {
       SpanGuard g(c, KID_LLE_LPJ);
-      Batch b = {c->cand, c->cand_counts, c->Y, c->Bm, c->yy, N, Cmax, 0, c->cand_lpj, Cmax, 0, c->lle_flags, KID_LPJ_CAND, 1};
-      b.mask = c->mask_infr;
-      TRY(launch_lpj(c, b, lv));
+      Batch bt = {c->cand, c->cand_counts, c->Y, c->Bm, c->yy, N, Cmax, 0, c->cand_lpj, Cmax, 0, c->lle_flags, KID_LPJ_CAND, 1};
+      bt.mask = c->mask_infr;
+      TRY(launch_lpj(c, bt, lv));
     }
     SpanGuard g(c, KID_LLE_FOLD);
-    lle_fold_kernel<<<nb, 256, 0, c->stream>>>(c->cand_lpj, Cmax, c->cand_counts, d_logr, d_tix, d_az, N, T, t0 == 0, run_m, run_z,
-                                               run_q, d_nout, keep_lpj);
+    lle_fold_kernel<<<p.nb, 256, 0, c->stream>>>(c->cand_lpj, Cmax, c->cand_counts, b.logr, b.tix, b.az, N, p.T, t0 == 0, b.run_m,
+                                                 b.run_z, b.run_q, b.n_out, b.keep_lpj);
     HIP_TRY(hipGetLastError());
     DBG_SYNC(c, "loglik_estimate fold");
   }
-  {
-    SpanGuard g(c, KID_LLE_FOLD);
-    lle_finish_kernel<<<nb, 256, 0, c->stream>>>(dF, run_m, run_z, run_q, d_nout, d_status, N, log((double)T), d_ll, d_mass, d_ess,
-                                                 d_part);
-    reduce_partials_kernel<<<1, 256, 0, c->stream>>>(d_part, nb, d_sum, 0);
-    HIP_TRY(hipGetLastError());
-  }
-  std::vector<int> status((size_t)N);
-  HIP_TRY(hipMemcpyAsync(status.data(), d_status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (ll_out) HIP_TRY(hipMemcpyAsync(ll_out, d_ll, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (F_out) HIP_TRY(hipMemcpyAsync(F_out, dF, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (mass_out) HIP_TRY(hipMemcpyAsync(mass_out, d_mass, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (ess_out) HIP_TRY(hipMemcpyAsync(ess_out, d_ess, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (n_outside_out) HIP_TRY(hipMemcpyAsync(n_outside_out, d_nout, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(sum_out, d_sum, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (sssc)
+  return 0;
+}
+
+// ---- stage: the estimate of every datapoint and their sum
+static int lle_finish_stage(evoamd_ctx *c, const LlePlan &p) {
+  const LleBufs b = lle_views(c, p);
+  SpanGuard g(c, KID_LLE_FOLD);
+  lle_finish_kernel<<<p.nb, 256, 0, c->stream>>>(b.F, b.run_m, b.run_z, b.run_q, b.n_out, b.status, c->N, log((double)p.T), b.ll, b.mass,
+                                                 b.ess, b.part);
+  reduce_partials_kernel<<<1, 256, 0, c->stream>>>(b.part, p.nb, b.sum, 0);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---- stage: the outputs, each where the caller gave a buffer; the counts of the datapoints without an estimate
+static int lle_fetch(evoamd_ctx *c, const LlePlan &p, double *ll, double *F, double *mass, double *ess, int32_t *n_outside,
+                     int64_t counters[2], double *sum) {
+  const LleBufs b = lle_views(c, p);
+  const size_t N = (size_t)c->N;
+  std::vector<int> status(N);
+  HIP_TRY(hipMemcpyAsync(status.data(), b.status, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(fetch_if(c, ll, b.ll, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, F, b.F, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, mass, b.mass, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, ess, b.ess, N * sizeof(double)));
+  HIP_TRY(fetch_if(c, n_outside, b.n_out, N * sizeof(int)));
+  HIP_TRY(hipMemcpyAsync(sum, b.sum, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (p.sssc)
     TRY(check_err(c));  // synchronises the stream; a draw the levels refuse surfaces here
   else
     HIP_TRY(hipStreamSynchronize(c->stream));
   counters[0] = counters[1] = 0;
-  for (i64 n = 0; n < N; n++) {
-    counters[0] += status[(size_t)n] == LLE_BAD_WEIGHTS;
-    counters[1] += status[(size_t)n] == LLE_SKIPPED;
-  }
-  c->lle_N = N, c->lle_T = T, c->lle_H = H;
-  made_loglik_draws(c, keep_draws ? 1 : 0);
+  for (size_t n = 0; n < N; n++) counters[0] += status[n] == LLE_BAD_WEIGHTS, counters[1] += status[n] == LLE_SKIPPED;
+  return 0;
+}
+
+extern "C" int evoamd_loglik_estimate(evoamd_ctx *c, int n_samples, uint64_t seed, uint64_t first_index, double prior_mix,
+                                      int keep_draws, double *ll_out, double *F_out, double *mass_out, double *ess_out,
+                                      int32_t *n_outside_out, int64_t counters[2], double *sum_out) {
+  LlePlan p;
+  TRY(lle_plan(c, n_samples, prior_mix, keep_draws, counters, sum_out, p));
+  HIP_TRY(hipSetDevice(c->device));
+  made_loglik_draws(c, -1);
+  TRY(lle_prepare(c, p));
+  TRY(lle_passes_stage(c, p, seed, first_index));
+  TRY(lle_finish_stage(c, p));
+  TRY(lle_fetch(c, p, ll_out, F_out, mass_out, ess_out, n_outside_out, counters, sum_out));
+  c->lle_N = c->N, c->lle_T = p.T, c->lle_H = c->H;
+  made_loglik_draws(c, p.keep ? 1 : 0);
   return 0;
 }
 
@@ -7217,10 +7218,7 @@ extern "C" int evoamd_download_loglik_draws(evoamd_ctx *c, int what, void *out) 
     case EVOAMD_LLE_LPJ: src = c->lle_keep_d + nt, bytes = nt * sizeof(double); break;
     default: return fail(EVOAMD_E_INVALID, "evoamd_download_loglik_draws: what must be EVOAMD_LLE_S, _INSIDE, _LOG_R or _LPJ");
   }
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return download_view(c, out, src, bytes);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -7316,10 +7314,7 @@ extern "C" int evoamd_download_generated(evoamd_ctx *c, int what, void *out) {
       break;
     default: return fail(EVOAMD_E_INVALID, "evoamd_download_generated: what must be EVOAMD_GEN_Y, _S, _Z or _YMEAN");
   }
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return download_view(c, out, src, bytes);
 }
 
 // ---------------------------------------------------------------------------------------
