@@ -28,8 +28,8 @@ SWEEP_SWAP, SWEEP_NO_FLIP = 2, 4
 SWEEP_NEIGHBOURHOODS = {"flip": 0, "swap": SWEEP_SWAP | SWEEP_NO_FLIP, "both": SWEEP_SWAP}
 # evoamd_neighbour_bound: flags (EVOAMD_NBOUND_*)
 NBOUND_INCOMPLETE = 1
-# evoamd_ais_loglik: flags (EVOAMD_AIS_*)
-AIS_REVERSE, AIS_ADMIT = 1, 2
+# evoamd_ais_loglik: flags (EVOAMD_AIS_*); evoamd_ais_posterior_ex takes AIS_INCOMPLETE alone
+AIS_REVERSE, AIS_ADMIT, AIS_INCOMPLETE = 1, 2, 8
 
 # evoamd_posterior_sample: keep bits (EVOAMD_PSAMP_KEEP_*) and the output ids of evoamd_download_posterior_samples
 PSAMP_KEEP = {"slot": 1, "s": 2, "z": 4, "y": 8}
@@ -179,6 +179,7 @@ SIGNATURES = {
     "evoamd_neighbour_bound": (_I, [_vp, _I, ctypes.c_uint, ctypes.POINTER(NboundOut)]),
     "evoamd_ais_loglik": (_I, [_vp, _I, _I, _c_dp, _U64, _U64, ctypes.c_uint, _c_u64p, _I, ctypes.POINTER(AisOut)]),
     "evoamd_ais_posterior": (_I, [_vp, _I, _I, _I, _c_dp, _U64, _U64, _I64, ctypes.POINTER(AisPostOut)]),
+    "evoamd_ais_posterior_ex": (_I, [_vp, _I, _I, _I, _c_dp, _U64, _U64, _I64, ctypes.c_uint, ctypes.POINTER(AisPostOut)]),
     "evoamd_posterior_scores": (_I, [_vp, _c_dp, _c_dp, _c_i32p, _c_i32p, _c_dp]),
     "evoamd_remap_latents": (_I, [_vp, _c_i32p, _I, _c_i32p, ctypes.POINTER(_I64)]),
     "evoamd_adopt_remapped_states": (_I, [_vp]),

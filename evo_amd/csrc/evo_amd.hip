@@ -648,6 +648,7 @@ struct evoamd_ctx {
   DevBuf<u64> aisp_s;
   DevBuf<i64> aisp_nf;
   unsigned aisp_lds_set = 0;
+  unsigned ais_lds_set = 0;  // evoamd_ais_loglik on incomplete data: bit log2(NC) forward, 8 bits up reverse
   // evoamd_remap_latents: K^n in the new latent numbering and its digests, [index (H_new) | n_replaced (N)] and the sum;
   // grown on demand, NOT sized by the geometry: they survive the configure between the remap and
   // evoamd_adopt_remapped_states, which swaps them in and releases them.  remap_H = 0: nothing to adopt.
@@ -6528,14 +6529,16 @@ extern "C" int evoamd_neighbour_bound(evoamd_ctx *c, int n_parents, unsigned fla
 }
 
 // ---------------------------------------------------------------------------------------
-// annealed importance sampling (kernels_ais.hpp has the law): EBSC on complete data.  Plan (every refusal, the launch
+// annealed importance sampling (kernels_ais.hpp has the law): EBSC; incomplete data under EVOAMD_AIS_INCOMPLETE.  Plan (every refusal, the launch
 // shape, the sizes), then the named stages: buffers, chains, fold, (admit) emission + candidate lpj + selection, fetch.
 // Without EVOAMD_AIS_ADMIT nothing of the EM state is written: B = Y W is (re)formed like by every lpj pass, nothing else.
 // ---------------------------------------------------------------------------------------
 // What evoamd_ais_loglik and evoamd_ais_posterior refuse alike, in this order (who: the caller's name in the texts): the
 // context and the chain counts in ais_admit, the schedule in ais_check_betas.  Two functions, because evoamd_ais_posterior
 // has refusals of its own (n_keep) between them.
-static int ais_admit(const evoamd_ctx *c, const char *who, int n_chains, int n_temps) {
+// incomplete: the caller's EVOAMD_AIS_INCOMPLETE -- a permission: with masks resident the call takes the masked route
+// (*masked), without masks it changes nothing.
+static int ais_admit(const evoamd_ctx *c, const char *who, int n_chains, int n_temps, bool incomplete, bool *masked) {
   if (!c->have_params) return fail(EVOAMD_E_INVALID, "%s: no Theta installed (set parameters first)", who);
   if (!c->have_data) return fail(EVOAMD_E_INVALID, "%s: no data (upload data first)", who);
   if (c->model != EVOAMD_MODEL_BSC)
@@ -6545,13 +6548,23 @@ static int ais_admit(const evoamd_ctx *c, const char *who, int n_chains, int n_t
     return fail(EVOAMD_E_INVALID, "%s is not available in the float32 mode (ebsc_f32): the chains run on the double B = Y W", who);
   if (c->bg_unit) return fail(EVOAMD_E_INVALID, "%s: option background_unit is not supported (every latent is scanned)", who);
   if (c->bsc_direct) return fail(EVOAMD_E_INVALID, "%s: bsc_direct keeps no G = W^T W, whose rows the Gibbs scan reads", who);
-  if (c->mask_infr)
+  if (c->mask_infr && !incomplete)
     return fail(EVOAMD_E_INVALID, "%s: incomplete data (masks resident) is not supported: the chains need one G for all datapoints", who);
   if (c->H > 64 * AIS_MAX_NC)
     return fail(EVOAMD_E_INVALID, "%s: H = %d, at most %d latents are supported (64 lanes x %d registers of c_j)", who, c->H,
                 64 * AIS_MAX_NC, AIS_MAX_NC);
   if (n_chains < 1) return fail(EVOAMD_E_INVALID, "%s: n_chains = %d must be positive", who, n_chains);
   if (n_temps < 1) return fail(EVOAMD_E_INVALID, "%s: n_temps = %d must be positive", who, n_temps);
+  *masked = c->mask_infr != nullptr;
+  return 0;
+}
+// the masked route's LDS (per wavefront the rows of Hp doubles, the column and the list over D) against a CU's 160 KiB
+#define AIS_LDS_LIMIT (160u << 10)
+static int ais_check_masked_lds(const evoamd_ctx *c, const char *who, size_t lds) {
+  if (lds > AIS_LDS_LIMIT)
+    return fail(EVOAMD_E_INVALID, "%s: incomplete data with D = %d and H = %d needs %zu bytes of LDS per workgroup (per wavefront "
+                "the column and the list over D beside the rows over H), above the %u of a compute unit", who, c->D, c->H, lds,
+                AIS_LDS_LIMIT);
   return 0;
 }
 static int ais_check_betas(const char *who, int n_temps, const double *betas) {
@@ -6576,7 +6589,8 @@ static int ais_wait(evoamd_ctx *c, const char *who) {
 }
 
 struct AisPlan {
-  bool reverse = false, admit = false;
+  bool reverse = false, admit = false, masked = false;
+  size_t lds = 0;  // masked: dynamic LDS of the chain kernel
   int C = 0, T = 0, nc = 1;  // nc: the chunk count the kernel is instantiated for (1, 2, 4, 8, 16)
   unsigned grid = 1;
   size_t n_d = 0, n_i = 0, n_s = 0;  // elements of ais_d / ais_i / ais_s
@@ -6585,9 +6599,13 @@ struct AisPlan {
 static int ais_plan(const evoamd_ctx *c, int n_chains, int n_temps, const double *betas, unsigned flags, const uint64_t *s_start,
                     int Mprime, AisPlan &p) {
   REQUIRE(c && c->configured, "configure first");
-  REQUIRE(!(flags & ~(unsigned)(EVOAMD_AIS_REVERSE | EVOAMD_AIS_ADMIT)), "evoamd_ais_loglik: unknown flag");
-  TRY(ais_admit(c, "evoamd_ais_loglik", n_chains, n_temps));
+  REQUIRE(!(flags & ~(unsigned)(EVOAMD_AIS_REVERSE | EVOAMD_AIS_ADMIT | EVOAMD_AIS_INCOMPLETE)), "evoamd_ais_loglik: unknown flag");
+  TRY(ais_admit(c, "evoamd_ais_loglik", n_chains, n_temps, (flags & EVOAMD_AIS_INCOMPLETE) != 0, &p.masked));
   TRY(ais_check_betas("evoamd_ais_loglik", n_temps, betas));
+  if (p.masked) {
+    p.lds = ais_masked_lds_bytes(c->HW, c->D);
+    TRY(ais_check_masked_lds(c, "evoamd_ais_loglik", p.lds));
+  }
   p.reverse = (flags & EVOAMD_AIS_REVERSE) != 0, p.admit = (flags & EVOAMD_AIS_ADMIT) != 0;
   REQUIRE(!p.reverse || s_start, "evoamd_ais_loglik: EVOAMD_AIS_REVERSE needs s_start, the (N, HW) words of the starting states");
   REQUIRE(!(p.reverse && p.admit), "evoamd_ais_loglik: EVOAMD_AIS_ADMIT with EVOAMD_AIS_REVERSE: a reverse chain ends at the prior, "
@@ -6616,6 +6634,28 @@ static void ais_launch_chains(evoamd_ctx *c, const AisPlan &p, const AisArgs &a)
     case 4: ais_chain_kernel<4, REV><<<p.grid, 64 * AIS_WAVES, lds, c->stream>>>(a); break;
     case 8: ais_chain_kernel<8, REV><<<p.grid, 64 * AIS_WAVES, lds, c->stream>>>(a); break;
     default: ais_chain_kernel<AIS_MAX_NC, REV><<<p.grid, 64 * AIS_WAVES, lds, c->stream>>>(a); break;
+  }
+}
+
+// incomplete data: the MASKED instantiations; above 64 KiB the dynamic LDS limit is raised once per instantiation
+template <int NC, bool REV>
+static int ais_launch_masked_one(evoamd_ctx *c, const AisPlan &p, const AisArgs &a, unsigned bit) {
+  if (REV) bit <<= 8;
+  if (p.lds > (64u << 10) && !(c->ais_lds_set & bit)) {
+    HIP_TRY(hipFuncSetAttribute((const void *)ais_chain_kernel<NC, REV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)AIS_LDS_LIMIT));
+    c->ais_lds_set |= bit;
+  }
+  ais_chain_kernel<NC, REV, true><<<p.grid, 64 * AIS_WAVES, p.lds, c->stream>>>(a);
+  return 0;
+}
+template <bool REV>
+static int ais_launch_masked(evoamd_ctx *c, const AisPlan &p, const AisArgs &a) {
+  switch (p.nc) {
+    case 1: return ais_launch_masked_one<1, REV>(c, p, a, 1u);
+    case 2: return ais_launch_masked_one<2, REV>(c, p, a, 2u);
+    case 4: return ais_launch_masked_one<4, REV>(c, p, a, 4u);
+    case 8: return ais_launch_masked_one<8, REV>(c, p, a, 8u);
+    default: return ais_launch_masked_one<AIS_MAX_NC, REV>(c, p, a, 16u);
   }
 }
 
@@ -6660,8 +6700,11 @@ static int ais_chains_stage(evoamd_ctx *c, const AisPlan &p, const double *betas
   a.log_w = b.log_w, a.fin = b.fin, a.flips = b.flips, a.err = c->err;
   a.N = c->N, a.C = p.C, a.T = p.T, a.H = c->H, a.HW = c->HW;
   a.seed = seed, a.first_index = first_index;
+  if (p.masked) a.W = c->W, a.mask = c->mask_infr, a.D = c->D;
   SpanGuard g(c, KID_AIS);
-  if (p.reverse)
+  if (p.masked)
+    TRY(p.reverse ? ais_launch_masked<true>(c, p, a) : ais_launch_masked<false>(c, p, a));
+  else if (p.reverse)
     ais_launch_chains<true>(c, p, a);
   else
     ais_launch_chains<false>(c, p, a);
@@ -6742,12 +6785,14 @@ extern "C" int evoamd_ais_loglik(evoamd_ctx *c, int n_chains, int n_temps, const
 }
 
 // ---------------------------------------------------------------------------------------
-// posterior expectations from the AIS chains (kernels_ais_post.hpp has the law): EBSC on complete data.  Plan (every
+// posterior expectations from the AIS chains (kernels_ais_post.hpp has the law): EBSC; incomplete data under the flag
+// EVOAMD_AIS_INCOMPLETE of evoamd_ais_posterior_ex.  Plan (every
 // refusal, the launch shape, the block of datapoints, the sizes), then the named stages: buffers, chains + fold block by
 // block, the product for `mean`, fetch.  Nothing of the EM state is written, y_hat and its validity included: B = Y W is
 // (re)formed like by every lpj pass, nothing else.
 // ---------------------------------------------------------------------------------------
 struct AisPostPlan {
+  bool masked = false;
   int C = 0, T = 0, K = 0, nc = 1;  // nc: the chunk count the kernel is instantiated for (1, 2, 4, 8, 16)
   i64 block = 1;                    // datapoints per block
   bool mean = false;
@@ -6756,9 +6801,10 @@ struct AisPostPlan {
 };
 
 static int ais_post_plan(const evoamd_ctx *c, int n_chains, int n_temps, int n_keep, const double *betas, int64_t block_datapoints,
-                         bool mean, AisPostPlan &p) {
+                         unsigned flags, bool mean, AisPostPlan &p) {
   REQUIRE(c && c->configured, "configure first");
-  TRY(ais_admit(c, "evoamd_ais_posterior", n_chains, n_temps));
+  REQUIRE(!(flags & ~(unsigned)EVOAMD_AIS_INCOMPLETE), "evoamd_ais_posterior_ex: unknown flag");
+  TRY(ais_admit(c, "evoamd_ais_posterior", n_chains, n_temps, (flags & EVOAMD_AIS_INCOMPLETE) != 0, &p.masked));
   if (n_keep < 1) return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: n_keep = %d must be positive", n_keep);
   REQUIRE((i64)n_temps + n_keep < 2147483647LL, "evoamd_ais_posterior: n_temps + n_keep must fit in int32");
   TRY(ais_check_betas("evoamd_ais_posterior", n_temps, betas));
@@ -6772,7 +6818,8 @@ static int ais_post_plan(const evoamd_ctx *c, int n_chains, int n_temps, int n_k
   p.C = n_chains, p.T = n_temps, p.K = n_keep, p.mean = mean;
   while (p.nc < c->HW) p.nc <<= 1;
   p.block = std::min<i64>(block_datapoints > 0 ? block_datapoints : fit, c->N);
-  p.lds = ais_post_lds_bytes(c->HW);
+  p.lds = p.masked ? ais_post_masked_lds_bytes(c->HW, c->D) : ais_post_lds_bytes(c->HW);
+  if (p.masked) TRY(ais_check_masked_lds(c, "evoamd_ais_posterior", p.lds));
   const size_t N = (size_t)c->N, NC = N * (size_t)n_chains;
   p.n_d = (size_t)n_temps + 1 + 3 * NC + 2 * N * c->H + 7 * N + (mean ? N * c->D : 0);
   p.n_rows = (size_t)p.block * row;
@@ -6811,8 +6858,26 @@ static int ais_post_launch_one(evoamd_ctx *c, const AisPostPlan &p, const AisPos
   ais_post_chain_kernel<NC><<<grid, 64 * AIS_WAVES, p.lds, c->stream>>>(a);
   return 0;
 }
+// incomplete data: the MASKED instantiations (their bits of aisp_lds_set: 8 up)
+template <int NC>
+static int ais_post_launch_masked_one(evoamd_ctx *c, const AisPostPlan &p, const AisPostArgs &a, unsigned grid, unsigned bit) {
+  bit <<= 8;
+  if (p.lds > (64u << 10) && !(c->aisp_lds_set & bit)) {
+    HIP_TRY(hipFuncSetAttribute((const void *)ais_post_chain_kernel<NC, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)AIS_LDS_LIMIT));
+    c->aisp_lds_set |= bit;
+  }
+  ais_post_chain_kernel<NC, true><<<grid, 64 * AIS_WAVES, p.lds, c->stream>>>(a);
+  return 0;
+}
 static int ais_post_launch_chains(evoamd_ctx *c, const AisPostPlan &p, const AisPostArgs &a) {
   const unsigned grid = (unsigned)std::min<i64>(cdiv(a.nb * (i64)p.C, AIS_WAVES), (i64)c->n_cu * 64);
+  if (p.masked) switch (p.nc) {
+      case 1: return ais_post_launch_masked_one<1>(c, p, a, grid, 1u);
+      case 2: return ais_post_launch_masked_one<2>(c, p, a, grid, 2u);
+      case 4: return ais_post_launch_masked_one<4>(c, p, a, grid, 4u);
+      case 8: return ais_post_launch_masked_one<8>(c, p, a, grid, 8u);
+      default: return ais_post_launch_masked_one<AIS_MAX_NC>(c, p, a, grid, 16u);
+    }
   switch (p.nc) {
     case 1: return ais_post_launch_one<1>(c, p, a, grid, 1u);
     case 2: return ais_post_launch_one<2>(c, p, a, grid, 2u);
@@ -6843,6 +6908,7 @@ static int ais_post_chains_stage(evoamd_ctx *c, const AisPostPlan &p, const doub
   a.G = c->G, a.Gd = c->diag, a.dpar = c->dpar, a.betas = b.betas, a.rb = c->aisp_rows, a.err = c->err;
   a.C = p.C, a.T = p.T, a.K = p.K, a.H = c->H, a.HW = c->HW;
   a.seed = seed;
+  if (p.masked) a.W = c->W, a.D = c->D;
   AisPostFoldArgs f = {};
   f.log_w = b.log_w, f.best_lpj = b.best_lpj, f.best = b.best, f.flips = b.flips, f.rb = c->aisp_rows, f.dpar = c->dpar;
   f.wts = b.wts, f.p = b.p, f.p_se = b.p_se, f.count = b.count, f.map_lpj = b.map_lpj, f.ll = b.ll, f.ess = b.ess;
@@ -6854,6 +6920,7 @@ static int ais_post_chains_stage(evoamd_ctx *c, const AisPostPlan &p, const doub
     f.n0 = n0;
     const size_t i0 = (size_t)n0 * p.C;  // the chain kernel sees its block alone
     a.Bm = c->Bm + (size_t)n0 * c->H, a.yy = c->yy + n0, a.first_index = first_index + (uint64_t)n0;
+    if (p.masked) a.mask = c->mask_infr + (size_t)n0 * c->D;
     a.log_w = b.log_w + i0, a.best_lpj = b.best_lpj + i0, a.best = b.best + i0 * c->HW, a.flips = b.flips + i0;
     TRY(ais_post_launch_chains(c, p, a));
     HIP_TRY(hipGetLastError());
@@ -6903,9 +6970,15 @@ static int ais_post_fetch(evoamd_ctx *c, const AisPostPlan &p, const evoamd_ais_
 
 extern "C" int evoamd_ais_posterior(evoamd_ctx *c, int n_chains, int n_temps, int n_keep, const double *betas, uint64_t seed,
                                     uint64_t first_index, int64_t block_datapoints, const evoamd_ais_post_out *out) {
+  return evoamd_ais_posterior_ex(c, n_chains, n_temps, n_keep, betas, seed, first_index, block_datapoints, 0u, out);
+}
+
+extern "C" int evoamd_ais_posterior_ex(evoamd_ctx *c, int n_chains, int n_temps, int n_keep, const double *betas, uint64_t seed,
+                                       uint64_t first_index, int64_t block_datapoints, unsigned flags,
+                                       const evoamd_ais_post_out *out) {
   const evoamd_ais_post_out o = out ? *out : evoamd_ais_post_out{};
   AisPostPlan p;
-  TRY(ais_post_plan(c, n_chains, n_temps, n_keep, betas, block_datapoints, o.mean != nullptr, p));
+  TRY(ais_post_plan(c, n_chains, n_temps, n_keep, betas, block_datapoints, flags, o.mean != nullptr, p));
   HIP_TRY(hipSetDevice(c->device));
   TRY(ais_post_prepare(c, p));
   TRY(ais_post_chains_stage(c, p, betas, seed, first_index, o.rb));

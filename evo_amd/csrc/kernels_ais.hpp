@@ -1,4 +1,4 @@
-// Annealed importance sampling for EBSC on complete data (evoamd_ais_loglik): per datapoint, C Gibbs chains walk from the
+// Annealed importance sampling for EBSC (evoamd_ais_loglik; incomplete data under EVOAMD_AIS_INCOMPLETE, below): per datapoint, C Gibbs chains walk from the
 // prior to the posterior (forward: a stochastic LOWER bound on log p(y_n) - ljc) or from a given state back to the prior
 // (reverse: with an exact posterior sample as that state, a stochastic UPPER bound -- bidirectional Monte Carlo).  The
 // weight of a chain does not depend on K^n.  One wavefront per (datapoint, chain); no atomics on the outputs, every store a
@@ -42,6 +42,26 @@
 // Cost per chain and temperature: NC chunk rounds (an exp and a hash per latent) plus NC chunk rounds and one row of G
 // (8 H bytes) per accepted flip.  G is 8 MB at H = 1024: twice the 4 MiB L2 of an XCD, so a row comes from L2 or from the
 // 256 MiB Infinity Cache behind it, never from HBM once the call is under way.
+//
+// INCOMPLETE DATA (MASKED = true; masks resident and EVOAMD_AIS_INCOMPLETE): everything above stays -- the stream, the
+// start, the scan order, the conditional, l(s), log w, the fold, n_flips -- except where G comes from.
+//   B_n, yy_n  the resident ones: evoamd_upload_masks zeroes the entries of Y under False, so both are sums over the
+//              reliable entries already; values of y under False, NaN included, never enter.
+//   o, nd      the reliable d of datapoint n in ascending d (seed_list_reliable) and their number.
+//   G(n)_hj    = sum_{d in o, ascending} (W_dh W_dj): each product rounded, then added, starting from 0.0, contraction
+//              off.  NOT seed_gram_sweep's fma: the NumPy mirror reproduces the bits and NumPy has no fma.  The diagonal
+//              g(n)_jj is the same sum with h = j, formed once per datapoint.
+//   c_j        = B_nj - sum_{i in s, ascending} G(n)_ij; a flip of h subtracts or adds the row G(n)_h., one plain operation
+//              per j.  The row is formed when the flip happens, from W and the list o, with the column W_.h over o staged
+//              in LDS; no G(n) is stored.  A start with bits on forms one row per active latent in ascending order.
+//   nd = 0     G(n) = 0, B = 0, yy = 0: the chains are prior draws, log w = 0, ll_n = Hv log1p(exp(pil_bar)).  The datapoint
+//              is not skipped: it stays in the sum and in the count N.
+// Mapping: as above, with the diagonal in NC more registers per lane (the same unrolled chunks as c_j) and an accumulator
+// per chunk while a row is formed: d outer, chunks inner, so a row of W is read once, coalesced over j.  LDS per wavefront:
+// B_n. (Hp doubles), the column (D doubles) and the list (D ints); nothing per workgroup.  At H = 1024, D = 256 that is
+// 4 (8192 + 3072) = 44 KiB per workgroup: three workgroups per CU, three waves per SIMD.  Above 64 KiB (large D) the
+// launch needs hipFuncAttributeMaxDynamicSharedMemorySize; a geometry above the 160 KiB of a CU is refused by the host.
+// Cost of a flip: nd rows of W (8 H bytes each) instead of one row of G -- nd H / 64 multiply-adds per lane.
 #pragma once
 #include "common.hpp"
 #include "kernels_generate.hpp"
@@ -66,7 +86,18 @@ struct AisArgs {
   i64 N;
   int C, T, H, HW;
   u64 seed, first_index;
+  // incomplete data (MASKED) only
+  const double *W;      // (D, H)
+  const uint8_t *mask;  // (N, D) x_infr
+  int D;
 };
+
+// MASKED: the doubles a wavefront has in LDS beside its `rows` rows of Hp doubles -- the column (D doubles), then the list
+// (D ints, rounded up to a double)
+__host__ __device__ static inline size_t ais_masked_wave_doubles(int HW, int D, int rows) {
+  return (size_t)rows * 64 * HW + (size_t)D + (size_t)(D + 1) / 2;
+}
+static inline size_t ais_masked_lds_bytes(int HW, int D) { return (size_t)AIS_WAVES * ais_masked_wave_doubles(HW, D, 1) * sizeof(double); }
 
 __device__ __forceinline__ double ais_readlane(double v, int l) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
@@ -74,7 +105,35 @@ __device__ __forceinline__ double ais_readlane(double v, int l) {
   return __hiloint2double(hi, lo);
 }
 
-template <int NC, bool REV>
+// Incomplete data: row h of G(n) into acc (DIAG: its diagonal; h is not read), lane l the latents l, l + 64, ... -- the sum
+// over the list dl of the reliable d in its order, each product rounded, then added.  The column W_.h over the list goes
+// through col (LDS); the syncs keep a row's reads of col in front of the next row's writes.
+template <int NC, bool DIAG>
+__device__ __forceinline__ void ais_gram_row(const double *__restrict__ W, int D, int H, int HW, int *err, int lane, const int *dl,
+                                             double *col, int nd, int h, double (&acc)[NC]) {
+#pragma clang fp contract(off)
+  if (!DIAG) {
+    seed_wave_sync();
+    for (int i = lane; i < nd; i += 64) col[i] = W[(size_t)guard_index(dl[i], D, err) * H + h];
+    seed_wave_sync();
+  }
+#pragma unroll
+  for (int k = 0; k < NC; k++) acc[k] = 0.0;
+  for (int i = 0; i < nd; i++) {
+    const double *Wd = W + (size_t)guard_index(dl[i], D, err) * H;
+    const double cw = DIAG ? 0.0 : col[i];
+#pragma unroll
+    for (int k = 0; k < NC; k++) {
+      const int j = 64 * k + lane;
+      if (k < HW && j < H) {
+        const double w = Wd[j];
+        acc[k] = acc[k] + (DIAG ? w : cw) * w;
+      }
+    }
+  }
+}
+
+template <int NC, bool REV, bool MASKED = false>
 __global__ __launch_bounds__(64 * AIS_WAVES) void ais_chain_kernel(AisArgs a) {
 #pragma clang fp contract(off)
   const int lane = lane_id(), wave = wave_id_uniform();
@@ -82,11 +141,19 @@ __global__ __launch_bounds__(64 * AIS_WAVES) void ais_chain_kernel(AisArgs a) {
   const double pre1 = a.dpar[DP_PRE1], pilb = a.dpar[DP_PILBAR], pi = a.dpar[DP_PI];
   constexpr bool rev = REV;
   // LDS: G_jj for the workgroup (Hp doubles), then B_n. of each wavefront's datapoint (Hp doubles each)
+  // MASKED: per wavefront B_n., the column and the list; the diagonal of G(n) is in registers
   extern __shared__ double ais_lds[];
   const int Hp = 64 * HW;
   double *gd = ais_lds, *bn = ais_lds + (size_t)(1 + wave) * Hp;
-  for (int h = (int)threadIdx.x; h < Hp; h += (int)blockDim.x) gd[h] = h < H ? a.Gd[h] : 0.0;
-  __syncthreads();
+  [[maybe_unused]] double *col = nullptr;
+  [[maybe_unused]] int *dl = nullptr;
+  if constexpr (MASKED) {
+    bn = ais_lds + (size_t)wave * ais_masked_wave_doubles(HW, a.D, 1);
+    col = bn + Hp, dl = (int *)(col + a.D);
+  } else {
+    for (int h = (int)threadIdx.x; h < Hp; h += (int)blockDim.x) gd[h] = h < H ? a.Gd[h] : 0.0;
+    __syncthreads();
+  }
   const i64 items = a.N * (i64)C;
   for (i64 it = (i64)blockIdx.x * AIS_WAVES + wave; it < items; it += (i64)gridDim.x * AIS_WAVES) {
     const i64 n = it / C;
@@ -104,7 +171,11 @@ __global__ __launch_bounds__(64 * AIS_WAVES) void ais_chain_kernel(AisArgs a) {
       if (k < HW) bn[h] = c[k];
       word[k] = 0ull;
     }
+    [[maybe_unused]] int nd = 0;
+    [[maybe_unused]] double gdr[NC], row[NC];  // MASKED: g(n)_jj of the lane's latents; the row being applied
+    if constexpr (MASKED) nd = seed_list_reliable(a.mask + (size_t)n * a.D, a.D, lane, dl);
     seed_wave_sync();
+    if constexpr (MASKED) ais_gram_row<NC, true>(a.W, a.D, H, HW, a.err, lane, dl, col, nd, 0, gdr);
     // ---- the start
 #pragma unroll
     for (int k = 0; k < NC; k++) {
@@ -127,11 +198,17 @@ __global__ __launch_bounds__(64 * AIS_WAVES) void ais_chain_kernel(AisArgs a) {
         const int b = __builtin_ctzll(bits);
         bits &= bits - 1ull;
         const int i = guard_index(64 * k + b, H, a.err);
-        const double *Gi = a.G + (size_t)i * H;
+        if constexpr (MASKED) {
+          ais_gram_row<NC, false>(a.W, a.D, H, HW, a.err, lane, dl, col, nd, i, row);
 #pragma unroll
-        for (int kk = 0; kk < NC; kk++) {
-          const int j = 64 * kk + lane;
-          if (kk < HW && j < H) c[kk] = c[kk] - Gi[j];
+          for (int kk = 0; kk < NC; kk++) c[kk] = c[kk] - row[kk];
+        } else {
+          const double *Gi = a.G + (size_t)i * H;
+#pragma unroll
+          for (int kk = 0; kk < NC; kk++) {
+            const int j = 64 * kk + lane;
+            if (kk < HW && j < H) c[kk] = c[kk] - Gi[j];
+          }
         }
       }
     }
@@ -156,13 +233,19 @@ __global__ __launch_bounds__(64 * AIS_WAVES) void ais_chain_kernel(AisArgs a) {
     auto apply = [&](int k_flip, int b, bool was_on) {
 #pragma clang fp contract(off)
       const int h = guard_index(64 * k_flip + b, H, a.err);
-      const double *Gh = a.G + (size_t)h * H;
+      if constexpr (MASKED) {
+        ais_gram_row<NC, false>(a.W, a.D, H, HW, a.err, lane, dl, col, nd, h, row);
 #pragma unroll
-      for (int kk = 0; kk < NC; kk++) {
-        const int j = 64 * kk + lane;
-        if (kk < HW && j < H) {
-          const double g = Gh[j];
-          c[kk] = was_on ? c[kk] + g : c[kk] - g;
+        for (int kk = 0; kk < NC; kk++) c[kk] = was_on ? c[kk] + row[kk] : c[kk] - row[kk];
+      } else {
+        const double *Gh = a.G + (size_t)h * H;
+#pragma unroll
+        for (int kk = 0; kk < NC; kk++) {
+          const int j = 64 * kk + lane;
+          if (kk < HW && j < H) {
+            const double g = Gh[j];
+            c[kk] = was_on ? c[kk] + g : c[kk] - g;
+          }
         }
       }
       flips++;
@@ -179,7 +262,11 @@ __global__ __launch_bounds__(64 * AIS_WAVES) void ais_chain_kernel(AisArgs a) {
         const int h = 64 * k + lane;
         const bool valid = h < H;
         const double u = gen_u01(x0, purpose, base + (u64)(valid ? h : 0));
-        const double g = gd[h];
+        double g;
+        if constexpr (MASKED)
+          g = gdr[k];
+        else
+          g = gd[h];
         u64 open = ~0ull;  // the lanes not yet settled
         while (true) {
           const bool on = (word[k] >> lane) & 1ull;

@@ -1,8 +1,8 @@
 // Posterior expectations from annealed importance sampling (evoamd_ais_posterior): the forward chains of kernels_ais.hpp,
 // continued at beta = 1, give weighted marginals E_p[s_h | y_n] that do not start from K^n.  A forward chain with its weight
 // is a properly weighted sample of the true posterior; the self-normalised sum over the chains is a consistent estimate of
-// a posterior expectation, and every further Gibbs scan at beta = 1 keeps it so.  EBSC on complete data.  One wavefront per
-// (datapoint, chain); no atomics on the outputs, every store a plain vector store, every sum in a fixed order: two launches
+// a posterior expectation, and every further Gibbs scan at beta = 1 keeps it so.  EBSC; incomplete data: below.
+// One wavefront per (datapoint, chain); no atomics on the outputs, every store a plain vector store, every sum in a fixed order: two launches
 // give the same bits.  evo_amd/models/ais.py: ais_posterior_counter is the NumPy mirror -- keep the two and the tests in step.
 //
 // THE LAW (names, stream, start, c_j, l(s), K_t and log w as in kernels_ais.hpp, forward direction), per datapoint n, chain
@@ -35,6 +35,15 @@
 // that lpj alone put NC = 1 and NC = 4 one occupancy step below ais_chain_kernel<NC, false>.
 // The rows r_c. of a block of datapoints go to a buffer of at most AIS_POST_ROWS_BYTES; the host walks the datapoints in
 // blocks, chains then fold.  Nothing depends on the block size: every index of the stream is the datapoint's own.
+//
+// INCOMPLETE DATA (MASKED = true; masks resident and the flag EVOAMD_AIS_INCOMPLETE of evoamd_ais_posterior_ex): the law
+// above with the B_n, yy_n, the list o, G(n), its diagonal and c_j of kernels_ais.hpp's INCOMPLETE DATA -- a row of G(n)
+// is formed from W and the list when a flip happens, products rounded and added in ascending d.  R_c, best, n_flips and
+// the fold are unchanged; a datapoint without a reliable entry has p_nh = 1 / (1 + exp(-pil_bar)) for every h.  mean = p W^T
+// covers every entry, the missing ones included.
+// LDS: per wavefront B_n., R_c, the column (D doubles) and the list (D ints), then the best lpj and words; the diagonal is
+// in registers.  At H = 1024, D = 256: 4 (2 x 8192 + 3072) + 544 = 76.5 KiB per workgroup, two workgroups per CU, two
+// waves per SIMD.
 #pragma once
 #include "kernels_ais.hpp"
 
@@ -58,13 +67,22 @@ struct AisPostArgs {
   i64 nb;
   int C, T, K, H, HW;
   u64 seed, first_index;
+  // incomplete data (MASKED) only
+  const double *W;      // (D, H)
+  const uint8_t *mask;  // (nb, D) x_infr
+  int D;
 };
 
 static inline size_t ais_post_lds_bytes(int HW) {
   return (size_t)(1 + 2 * AIS_WAVES) * 64 * HW * sizeof(double) + (size_t)AIS_WAVES * (HW + 1) * sizeof(u64);
 }
 
-template <int NC>
+// MASKED: per wavefront B_n., R_c, the column and the list, and behind them the best lpj and words as above
+static inline size_t ais_post_masked_lds_bytes(int HW, int D) {
+  return (size_t)AIS_WAVES * ais_masked_wave_doubles(HW, D, 2) * sizeof(double) + (size_t)AIS_WAVES * (HW + 1) * sizeof(u64);
+}
+
+template <int NC, bool MASKED = false>
 __global__ __launch_bounds__(64 * AIS_WAVES) void ais_post_chain_kernel(AisPostArgs a) {
 #pragma clang fp contract(off)
   const int lane = lane_id(), wave = wave_id_uniform();
@@ -73,13 +91,24 @@ __global__ __launch_bounds__(64 * AIS_WAVES) void ais_post_chain_kernel(AisPostA
   // LDS: G_jj for the workgroup (Hp doubles), then B_n. and R_c of each wavefront (Hp doubles each), then per wavefront the
   // best lpj and the best state's words (the two registers of that lpj are what separates NC = 1 and 4 from the next lower
   // occupancy)
+  // MASKED: no G_jj (the diagonal of G(n) is in registers); per wavefront B_n., R_c, the column and the list
   extern __shared__ double ais_post_lds[];
   const int Hp = 64 * HW;
   double *gd = ais_post_lds, *bn = ais_post_lds + (size_t)(1 + 2 * wave) * Hp, *R = bn + Hp;
   double *bl = ais_post_lds + (size_t)(1 + 2 * AIS_WAVES) * Hp + (size_t)wave * (HW + 1);
+  [[maybe_unused]] double *col = nullptr;
+  [[maybe_unused]] int *dl = nullptr;
+  if constexpr (MASKED) {
+    const size_t per_wave = ais_masked_wave_doubles(HW, a.D, 2);
+    bn = ais_post_lds + (size_t)wave * per_wave, R = bn + Hp;
+    col = R + Hp, dl = (int *)(col + a.D);
+    bl = ais_post_lds + (size_t)AIS_WAVES * per_wave + (size_t)wave * (HW + 1);
+  }
   u64 *bw = (u64 *)(bl + 1);
-  for (int h = (int)threadIdx.x; h < Hp; h += (int)blockDim.x) gd[h] = h < H ? a.Gd[h] : 0.0;
-  __syncthreads();
+  if constexpr (!MASKED) {
+    for (int h = (int)threadIdx.x; h < Hp; h += (int)blockDim.x) gd[h] = h < H ? a.Gd[h] : 0.0;
+    __syncthreads();
+  }
   const i64 items = a.nb * (i64)C;
   for (i64 it = (i64)blockIdx.x * AIS_WAVES + wave; it < items; it += (i64)gridDim.x * AIS_WAVES) {
     const i64 n = it / C;
@@ -97,7 +126,11 @@ __global__ __launch_bounds__(64 * AIS_WAVES) void ais_post_chain_kernel(AisPostA
       if (k < HW) bn[h] = c[k], R[h] = 0.0;
       word[k] = 0ull;
     }
+    [[maybe_unused]] int nd = 0;
+    [[maybe_unused]] double gdr[NC], row[NC];  // MASKED: g(n)_jj of the lane's latents; the row being applied
+    if constexpr (MASKED) nd = seed_list_reliable(a.mask + (size_t)n * a.D, a.D, lane, dl);
     seed_wave_sync();
+    if constexpr (MASKED) ais_gram_row<NC, true>(a.W, a.D, H, HW, a.err, lane, dl, col, nd, 0, gdr);
     // ---- the start: an exact draw from the prior
 #pragma unroll
     for (int k = 0; k < NC; k++) {
@@ -114,11 +147,17 @@ __global__ __launch_bounds__(64 * AIS_WAVES) void ais_post_chain_kernel(AisPostA
         const int b = __builtin_ctzll(bits);
         bits &= bits - 1ull;
         const int i = guard_index(64 * k + b, H, a.err);
-        const double *Gi = a.G + (size_t)i * H;
+        if constexpr (MASKED) {
+          ais_gram_row<NC, false>(a.W, a.D, H, HW, a.err, lane, dl, col, nd, i, row);
 #pragma unroll
-        for (int kk = 0; kk < NC; kk++) {
-          const int j = 64 * kk + lane;
-          if (kk < HW && j < H) c[kk] = c[kk] - Gi[j];
+          for (int kk = 0; kk < NC; kk++) c[kk] = c[kk] - row[kk];
+        } else {
+          const double *Gi = a.G + (size_t)i * H;
+#pragma unroll
+          for (int kk = 0; kk < NC; kk++) {
+            const int j = 64 * kk + lane;
+            if (kk < HW && j < H) c[kk] = c[kk] - Gi[j];
+          }
         }
       }
     }
@@ -143,13 +182,19 @@ __global__ __launch_bounds__(64 * AIS_WAVES) void ais_post_chain_kernel(AisPostA
     auto apply = [&](int k_flip, int b, bool was_on) {
 #pragma clang fp contract(off)
       const int h = guard_index(64 * k_flip + b, H, a.err);
-      const double *Gh = a.G + (size_t)h * H;
+      if constexpr (MASKED) {
+        ais_gram_row<NC, false>(a.W, a.D, H, HW, a.err, lane, dl, col, nd, h, row);
 #pragma unroll
-      for (int kk = 0; kk < NC; kk++) {
-        const int j = 64 * kk + lane;
-        if (kk < HW && j < H) {
-          const double g = Gh[j];
-          c[kk] = was_on ? c[kk] + g : c[kk] - g;
+        for (int kk = 0; kk < NC; kk++) c[kk] = was_on ? c[kk] + row[kk] : c[kk] - row[kk];
+      } else {
+        const double *Gh = a.G + (size_t)h * H;
+#pragma unroll
+        for (int kk = 0; kk < NC; kk++) {
+          const int j = 64 * kk + lane;
+          if (kk < HW && j < H) {
+            const double g = Gh[j];
+            c[kk] = was_on ? c[kk] + g : c[kk] - g;
+          }
         }
       }
       flips++;
@@ -165,7 +210,11 @@ __global__ __launch_bounds__(64 * AIS_WAVES) void ais_post_chain_kernel(AisPostA
         const int h = 64 * k + lane;
         const bool valid = h < H;
         const double u = gen_u01(x0, purpose, base + (u64)(valid ? h : 0));
-        const double g = gd[h];
+        double g;
+        if constexpr (MASKED)
+          g = gdr[k];
+        else
+          g = gd[h];
         u64 open = ~0ull;  // the lanes not yet settled
         while (true) {
           const bool on = (word[k] >> lane) & 1ull;

@@ -470,7 +470,7 @@ class Engine:
         return res
 
     def ais_loglik(self, betas, n_chains=16, seed=0, first_index=0, reverse=False, s_start=None, keep_states=False,
-                   admit=False, Mprime=1):
+                   admit=False, Mprime=1, incomplete=False):
         """Annealed importance sampling under the Theta and data on the device (evoamd_ais_loglik; csrc/kernels_ais.hpp
         has the law, evo_amd.models.ais_log_likelihood_counter is the NumPy mirror).  ``betas``: the float64 schedule of
         T + 1 values from 0 to 1.  Returns a dict of (N,) arrays "ll" (forward: a lower bound on log p(y_n) - ljc in
@@ -482,7 +482,9 @@ class Engine:
         "S_nunique" and "S_sub" (sums over the datapoints, as vary_kn).  Without ``admit`` K^n, lpj, the candidate batch
         and the statistics rows are not written.  EvoAmdError naming the rule, before anything is written, for ES3C, the
         float32 mode, the background unit, bsc_direct, masks resident, H > 1024, n_chains < 1, betas that do not start at
-        0, end at 1 or that descend, reverse without s_start and admit with reverse."""
+        0, end at 1 or that descend, reverse without s_start and admit with reverse.  ``incomplete=True`` is a permission:
+        with masks resident the chains run on the datapoint's own G(n) over its reliable entries (the law's INCOMPLETE
+        DATA; a D whose column and list do not fit into LDS is refused), without masks it changes nothing."""
         from .models.generate import pack_words
         betas = np.ascontiguousarray(betas, dtype=np.float64)
         if betas.ndim != 1 or betas.size < 2:
@@ -513,7 +515,8 @@ class Engine:
         if admit:
             res["F_before"], res["F_after"] = np.empty(N), np.empty(N)
             out.F_before, out.F_after, out.admit_sums = dptr(res["F_before"]), dptr(res["F_after"]), dptr(sums)
-        flags = (_lib.AIS_REVERSE if reverse else 0) | (_lib.AIS_ADMIT if admit else 0)
+        flags = ((_lib.AIS_REVERSE if reverse else 0) | (_lib.AIS_ADMIT if admit else 0)
+                 | (_lib.AIS_INCOMPLETE if incomplete else 0))
         check(self.lib.evoamd_ais_loglik(
             self._h, C, T, dptr(betas), int(seed) & (2 ** 64 - 1), int(first_index) & (2 ** 64 - 1), flags,
             None if words is None else words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), int(Mprime), ctypes.byref(out)))
@@ -525,7 +528,8 @@ class Engine:
         res["sum"] = float(total[0])
         return res
 
-    def ais_posterior(self, betas, n_chains=16, n_keep=4, seed=0, first_index=0, mean=False, keep_chains=False, block=0):
+    def ais_posterior(self, betas, n_chains=16, n_keep=4, seed=0, first_index=0, mean=False, keep_chains=False, block=0,
+                      incomplete=False):
         """Posterior expectations that do not start from K^n, under the Theta and data on the device (evoamd_ais_posterior;
         csrc/kernels_ais_post.hpp has the law, evo_amd.models.ais_posterior_counter is the NumPy mirror): the forward
         chains of ais_loglik, continued by ``n_keep`` - 1 further scans at beta = 1, each chain weighted by its w.
@@ -539,7 +543,9 @@ class Engine:
         as 256 MiB hold); the results do not depend on it.  K^n, lpj, the candidate batch, the statistics rows and y_hat
         are not written.  EvoAmdError naming the rule, before anything is written, for ES3C, the float32 mode, the
         background unit, bsc_direct, masks resident, H > 1024, n_chains < 1, n_keep < 1, betas that do not start at 0, end
-        at 1 or that descend, and a block above 256 MiB."""
+        at 1 or that descend, and a block above 256 MiB.  ``incomplete=True`` (evoamd_ais_posterior_ex) is a permission:
+        with masks resident the chains run on the datapoint's own G(n) over its reliable entries, and "mean" covers every
+        entry, the missing ones included; without masks it changes nothing."""
         betas = np.ascontiguousarray(betas, dtype=np.float64)
         if betas.ndim != 1 or betas.size < 2:
             raise ValueError("betas must be a 1-d array of T + 1 >= 2 values")
@@ -566,8 +572,9 @@ class Engine:
             chain_words = np.empty((N * C, HW), dtype=np.uint64)
             out.log_w, out.chain_map_lpj, out.rb = dptr(res["log_w"]), dptr(res["chain_map_lpj"]), dptr(res["rb"])
             out.chain_flips, out.chain_map_state = i32ptr(res["chain_flips"]), u64p(chain_words)
-        check(self.lib.evoamd_ais_posterior(self._h, C, T, int(n_keep), dptr(betas), int(seed) & (2 ** 64 - 1),
-                                            int(first_index) & (2 ** 64 - 1), int(block), ctypes.byref(out)))
+        check(self.lib.evoamd_ais_posterior_ex(self._h, C, T, int(n_keep), dptr(betas), int(seed) & (2 ** 64 - 1),
+                                               int(first_index) & (2 ** 64 - 1), int(block),
+                                               _lib.AIS_INCOMPLETE if incomplete else 0, ctypes.byref(out)))
         # the MSB-first words as bytes are the np.packbits layout
         as_bytes = lambda w: np.ascontiguousarray(w.astype(">u8").view(np.uint8).reshape(w.shape[0], HW * 8)[:, :nb])  # noqa: E731
         res["map_state"] = as_bytes(map_words)

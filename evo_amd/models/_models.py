@@ -1347,9 +1347,9 @@ class Model:
 
     def ais_log_likelihood(self, model_params, my_suff_stat, my_data, n_chains=16, n_temps=128, betas=None, seed=None,
                            first_index=0, direction="forward", s_start=None, per_datapoint=False, keep_states=False,
-                           admit=False):
-        """Annealed importance sampling (Neal 2001): bounds on the log-likelihood that do not depend on K^n, for EBSC on
-        complete data (Engine.ais_loglik; csrc/kernels_ais.hpp has the law, evo_amd.models.ais_log_likelihood_counter is
+                           admit=False, incomplete=False):
+        """Annealed importance sampling (Neal 2001): bounds on the log-likelihood that do not depend on K^n, for EBSC
+        (incomplete data with ``incomplete=True``, below) (Engine.ais_loglik; csrc/kernels_ais.hpp has the law, evo_amd.models.ais_log_likelihood_counter is
         the NumPy mirror).  Per datapoint ``n_chains`` Gibbs chains walk through the temperatures ``betas`` (a float64
         array of T + 1 values from 0 to 1 that never descends; None: the sigmoid schedule of ``n_temps`` steps,
         evo_amd.models.sigmoid_schedule) between the prior and the posterior, one systematic scan over the latents per
@@ -1371,7 +1371,14 @@ class Model:
         shards concatenate to the single call, and chain c does not depend on ``n_chains``.  ``seed`` None: drawn from
         np.random; rank and world size enter it as in sample_posterior.  NotImplementedError for ES3C; ValueError for the
         float32 mode, the background unit, incomplete data, H > 1024, n_chains < 1, betas that do not start at 0, end at
-        1 or that descend, reverse without an ``s_start`` of shape (N, H) bool, and admit with reverse.  One all-reduce."""
+        1 or that descend, reverse without an ``s_start`` of shape (N, H) bool, and admit with reverse.  One all-reduce.
+        ``incomplete=True`` admits my_data["x_infr"] with False entries, a permission as for seed_resident_states: the
+        chains of datapoint n run on its own G(n) = W_o^T W_o over its reliable entries o, a row formed from W and the mask
+        when a flip happens (csrc/kernels_ais.hpp, INCOMPLETE DATA; the mirror takes ``x_infr``); values of y under False,
+        NaN included, never enter.  A datapoint without a reliable entry is not skipped: its chains are prior draws, log w =
+        0, and it stays in the sum and in N, so L = ljc + sum_n ll_n / N with the ljc of incomplete data.  ``admit`` runs
+        the masked candidate lpj and selection of every E-step.  With complete data the argument changes nothing; a D
+        whose column and list do not fit into LDS beside the rows over H is an EvoAmdError naming D and H."""
         from .ais import AIS_MAX_H, check_betas, sigmoid_schedule
         if self.model_name != "bsc":
             raise NotImplementedError("ais_log_likelihood is for EBSC: ES3C is out of scope (its importance estimate works, "
@@ -1380,7 +1387,7 @@ class Model:
             raise ValueError("ais_log_likelihood is not available in the float32 mode")
         if my_suff_stat["permanent"]["background"]:
             raise ValueError("ais_log_likelihood: the background unit is not supported")
-        if not self._complete(my_data):
+        if not incomplete and not self._complete(my_data):
             raise ValueError("ais_log_likelihood: incomplete data (x_infr with False entries) is not supported")
         if self.H > AIS_MAX_H:
             raise ValueError("ais_log_likelihood: H = %d, at most %d latents are supported" % (self.H, AIS_MAX_H))
@@ -1412,7 +1419,7 @@ class Model:
             self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
         info = eng.ais_loglik(betas, C, self.last_ais_seed, first_index, reverse=reverse, s_start=s_start if reverse else None,
                               keep_states=bool(keep_states), admit=bool(admit),
-                              Mprime=my_suff_stat["Mprime"] if admit else 1)
+                              Mprime=my_suff_stat["Mprime"] if admit else 1, incomplete=bool(incomplete))
         red = _reduce_array(self.comm, np.array([info.pop("sum"), float(N), info.pop("S_sub", 0.0)]))  # (the one all-reduce)
         L = theta["ljc"] + red[0] / red[1]
         if admit:
@@ -1425,8 +1432,9 @@ class Model:
         return L
 
     def ais_posterior(self, model_params, my_suff_stat, my_data, n_chains=16, n_temps=128, n_keep=4, betas=None, seed=None,
-                      first_index=0, mean=False, keep_chains=False):
-        """Posterior expectations beyond K^n, for EBSC on complete data with H <= 1024 (Engine.ais_posterior;
+                      first_index=0, mean=False, keep_chains=False, incomplete=False):
+        """Posterior expectations beyond K^n, for EBSC with H <= 1024 (incomplete data with ``incomplete=True``, below)
+        (Engine.ais_posterior;
         csrc/kernels_ais_post.hpp has the law, evo_amd.models.ais_posterior_counter is the NumPy mirror).  encode(...).p,
         reconstruct and predictive_moments are expectations under q_n, the posterior truncated to K^n; here the chains ARE
         the forward chains of ais_log_likelihood (same stream, start and schedule), continued: a chain with its weight is a
@@ -1443,10 +1451,13 @@ class Model:
         (N, C).  Chain c does not depend on ``n_chains``, shards by ``first_index`` concatenate, two calls give the same
         bits; ``seed`` None: drawn from np.random and left in ``self.last_ais_seed`` (rank and world size enter it as in
         ais_log_likelihood).  Nothing of the EM state is written -- not K^n, lpj, the candidate batch, the statistics rows
-        or y_hat -- and there is no collective.  Out of scope: reverse chains, admit, ES3C, incomplete data, resident
-        handles for p / mean, second moments, use of the marginals in the M-step.  NotImplementedError for ES3C;
-        ValueError for the float32 mode, the background unit, incomplete data, H > 1024, n_chains < 1, n_keep < 1 and
-        betas that do not start at 0, end at 1 or that descend."""
+        or y_hat -- and there is no collective.  Out of scope: reverse chains, admit, ES3C, resident handles for p / mean,
+        second moments, use of the marginals in the M-step.  NotImplementedError for ES3C; ValueError for the float32
+        mode, the background unit, incomplete data without ``incomplete=True``, H > 1024, n_chains < 1, n_keep < 1 and
+        betas that do not start at 0, end at 1 or that descend.  ``incomplete=True`` admits my_data["x_infr"] with False
+        entries as ais_log_likelihood does (the chains on G(n) over the reliable entries; y under False, NaN included,
+        never enters); "mean" = p W^T then covers EVERY entry, the missing ones included: the reconstruction of the
+        missing entries that does not go through K^n.  A datapoint without a reliable entry has the prior's marginals."""
         from .ais import AIS_MAX_H, check_betas, sigmoid_schedule
         if self.model_name != "bsc":
             raise NotImplementedError("ais_posterior is for EBSC: ES3C is out of scope (a collapsed Gibbs step would need a "
@@ -1455,7 +1466,7 @@ class Model:
             raise ValueError("ais_posterior is not available in the float32 mode")
         if my_suff_stat["permanent"]["background"]:
             raise ValueError("ais_posterior: the background unit is not supported")
-        if not self._complete(my_data):
+        if not incomplete and not self._complete(my_data):
             raise ValueError("ais_posterior: incomplete data (x_infr with False entries) is not supported")
         if self.H > AIS_MAX_H:
             raise ValueError("ais_posterior: H = %d, at most %d latents are supported" % (self.H, AIS_MAX_H))
@@ -1476,7 +1487,8 @@ class Model:
         self.E_step_precompute(theta, dict(my_suff_stat), my_data)
         if model_params is not self._dev_theta:
             self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
-        return eng.ais_posterior(betas, C, K, self.last_ais_seed, first_index, mean=bool(mean), keep_chains=bool(keep_chains))
+        return eng.ais_posterior(betas, C, K, self.last_ais_seed, first_index, mean=bool(mean), keep_chains=bool(keep_chains),
+                                 incomplete=bool(incomplete))
 
     def reconstruct(self, my_data, my_suff_stat, model_params):
         """(Re-)estimate the entries with my_data["x"] False from the posterior predictive distribution under

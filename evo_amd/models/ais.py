@@ -21,6 +21,12 @@ The mirror scans h sequentially; the kernel settles a chunk of 64 latents by bal
 operations are the kernel's in the kernel's order (separate NumPy operations, no fused forms).  ``final``, ``n_flips`` and
 the starting draw are bit-level wherever no decision is closer to its uniform than the rounding of B, G and exp (``margin``
 says how close the closest was); the real-valued outputs are formula-level.
+
+Incomplete data (``x_infr``, bool (N, D); Model.ais_log_likelihood / ais_posterior with incomplete=True): the same law with
+Y zeroed under False (so B_n and yy_n are sums over the reliable entries, and values under False, NaN included, never
+enter) and the datapoint's own G(n)_hj = sum over its reliable d, ascending, of (W_dh W_dj) -- each product rounded, then
+added, starting from 0.0: a loop over d, which is what the kernel does, so the rows agree bit for bit.  A datapoint without
+a reliable entry has G(n) = 0, B = 0, yy = 0: prior draws, log w = 0, ll = H log1p(exp(pil_bar)); it is not skipped.
 """
 import numpy as np
 
@@ -84,6 +90,38 @@ def _ell(pre1, yy, Bn, c, s):
     return pre1 * (yy - total)
 
 
+def _mask_data(Y, x_infr):
+    """(Y with zeros under False, the mask as bool (N, D)), or (Y, None) for complete data."""
+    if x_infr is None:
+        return Y, None
+    mask = np.asarray(x_infr)
+    if mask.shape != Y.shape or mask.dtype != np.bool_:
+        raise ValueError("ais: x_infr must be a bool array of the shape of Y")
+    return np.where(mask, Y, 0.0), mask
+
+
+def _datapoint_gram(W, G, Gd, o):
+    """(diagonal, row getter) of the G that the chains of one datapoint read.  ``o`` None (complete data): G itself.  Else
+    o lists the reliable d in ascending order and G(n)_hj = sum_{d in o} (W_dh W_dj), each product rounded, then added,
+    starting from 0.0 -- a loop over d.  A row is formed when a chain first asks for it and kept for the datapoint."""
+    if o is None:
+        return Gd, lambda h: G[h]
+    H = W.shape[1]
+    gd = np.zeros(H)
+    for d in o:
+        gd = gd + W[d] * W[d]
+    rows = {}
+
+    def row(h):
+        if h not in rows:
+            r = np.zeros(H)
+            for d in o:
+                r = r + W[d, h] * W[d]
+            rows[h] = r
+        return rows[h]
+    return gd, row
+
+
 def _u01_chains(x0, C, index):
     """u01(x0, AIS_PURPOSE + c, index) for c < C: x0 (1, 1), index uint64 (k,) -> float64 (C, k)."""
     salt = np.array([((AIS_PURPOSE + c) * 0xd1b54a32d192ed03 + 0x632be59bd9b4e019) & _M64 for c in range(C)], dtype=np.uint64)
@@ -108,13 +146,15 @@ def _fold(a):
 
 
 def ais_log_likelihood_counter(theta, Y, n_chains=16, n_temps=128, betas=None, seed=0, first_index=0, direction="forward",
-                               s_start=None, B=None, G=None):
+                               s_start=None, B=None, G=None, x_infr=None):
     """What Model.ais_log_likelihood returns in ``info`` with per_datapoint=True and keep_states=True, for stream seed
     ``seed`` (``model.last_ais_seed``): the (N,) arrays "ll", "ess", "log_w_mean", "log_w_min", "log_w_max", "n_flips"
     (int64), "log_w" (N, C), "final" (uint8, N x C x ceil(H / 8), np.packbits layout), and beside them "final_bool" (N, C,
     H), "start" (the starting states, bool (N, C, H)), "margin" (N, C) = the minimum over all decisions of the chain of
     |u - p| (the starting draw: |u - pi|) and "sum" = the sum of ll.  ``theta``: an EBSC Theta with "W" (D, H), "pi",
-    "sigma"; ``Y`` (N, D) complete data; ``B`` / ``G``: Y W and W^T W when the caller has them (else formed here)."""
+    "sigma"; ``Y`` (N, D) complete data; ``B`` / ``G``: Y W and W^T W when the caller has them (else formed here).
+    ``x_infr`` (bool (N, D)): incomplete data -- Y is used with zeros under False and the chains of datapoint n read its own
+    G(n) over its reliable entries (the module's docstring); ``G`` is then not read."""
     if direction not in ("forward", "reverse"):
         raise ValueError("ais: direction must be 'forward' or 'reverse'")
     rev = direction == "reverse"
@@ -124,7 +164,7 @@ def ais_log_likelihood_counter(theta, Y, n_chains=16, n_temps=128, betas=None, s
     betas = sigmoid_schedule(n_temps) if betas is None else check_betas(betas)
     T = betas.size - 1
     W = np.asarray(theta["W"], dtype=np.float64)
-    Y = np.asarray(Y, dtype=np.float64)
+    Y, mask = _mask_data(np.asarray(Y, dtype=np.float64), x_infr)
     N, H = Y.shape[0], W.shape[1]
     if H > AIS_MAX_H:
         raise ValueError("ais: H = %d, at most %d latents are supported" % (H, AIS_MAX_H))
@@ -134,9 +174,12 @@ def ais_log_likelihood_counter(theta, Y, n_chains=16, n_temps=128, betas=None, s
         s_start = np.asarray(s_start)
     pre1, pilb, pi = ais_scalars(theta)
     B = np.dot(Y, W) if B is None else np.asarray(B, dtype=np.float64)
-    G = np.dot(W.T, W) if G is None else np.asarray(G, dtype=np.float64)
+    if mask is not None:
+        G = Gd = None  # (every datapoint has its own)
+    else:
+        G = np.dot(W.T, W) if G is None else np.asarray(G, dtype=np.float64)
+        Gd = np.diag(G).copy()
     yy = (Y * Y).sum(axis=1)
-    Gd = np.diag(G).copy()
     seed, first_index = int(seed) & _M64, int(first_index) & _M64
     hs = np.arange(H, dtype=np.uint64)
     out = {"log_w": np.empty((N, C)), "final_bool": np.zeros((N, C, H), dtype=bool), "start": np.zeros((N, C, H), dtype=bool),
@@ -146,18 +189,19 @@ def ais_log_likelihood_counter(theta, Y, n_chains=16, n_temps=128, betas=None, s
     chain_flips = np.zeros((N, C), dtype=np.int64)
     lz0 = H * np.log1p(np.exp(pilb))
 
-    def scan(s, c, beta, u, order, flips, margin):
-        """One scan of all chains in place: s bool (C, H), c (C, H), u (C, H); flips and margin (C,) are updated."""
+    def scan(s, c, beta, u, order, flips, margin, gd, row):
+        """One scan of all chains in place: s bool (C, H), c (C, H), u (C, H); flips and margin (C,) are updated; gd, row:
+        the diagonal and the rows of the datapoint's G (_datapoint_gram)."""
         for h in order:
             on = s[:, h].copy()
-            p = ais_conditional(pre1, pilb, c[:, h], Gd[h], on, beta)
+            p = ais_conditional(pre1, pilb, c[:, h], gd[h], on, beta)
             np.minimum(margin, np.abs(u[:, h] - p), out=margin)
             nb = u[:, h] < p
             up, down = nb & ~on, on & ~nb
             if up.any():
-                c[up] = c[up] - G[h]     # (one subtraction per j)
+                c[up] = c[up] - row(h)     # (one subtraction per j)
             if down.any():
-                c[down] = c[down] + G[h]
+                c[down] = c[down] + row(h)
             s[:, h] = nb
             flips += up | down
 
@@ -175,18 +219,19 @@ def ais_log_likelihood_counter(theta, Y, n_chains=16, n_temps=128, betas=None, s
                 s = u < pi
                 margin = np.abs(u - pi).min(axis=1)
             out["start"][n] = s
+            gd, row = _datapoint_gram(W, G, Gd, None if mask is None else np.flatnonzero(mask[n]))
             c = np.repeat(B[n][None, :], C, axis=0)
             for i in np.flatnonzero(s.any(axis=0)):
-                c[s[:, i]] = c[s[:, i]] - G[i]
+                c[s[:, i]] = c[s[:, i]] - row(i)
             if not rev:
                 lw = np.zeros(C)
                 for t in range(1, T + 1):  # (the scan of t = T gives ``final``)
                     lw = lw + (betas[t] - betas[t - 1]) * _ell(pre1, yy[n], B[n], c, s)
-                    scan(s, c, betas[t], block(t + 1), fwd, flips, margin)
+                    scan(s, c, betas[t], block(t + 1), fwd, flips, margin, gd, row)
             else:
                 lw = (betas[T] - betas[T - 1]) * _ell(pre1, yy[n], B[n], c, s)
                 for t in range(T - 1, 0, -1):
-                    scan(s, c, betas[t], block(t + 1), bwd, flips, margin)
+                    scan(s, c, betas[t], block(t + 1), bwd, flips, margin, gd, row)
                     lw = lw + (betas[t] - betas[t - 1]) * _ell(pre1, yy[n], B[n], c, s)
             out["log_w"][n] = lw
             out["final_bool"][n] = s
@@ -209,7 +254,7 @@ def ais_log_likelihood_counter(theta, Y, n_chains=16, n_temps=128, betas=None, s
 
 
 def ais_posterior_counter(theta, Y, n_chains=16, n_temps=128, n_keep=4, betas=None, seed=0, first_index=0, mean=False, B=None,
-                          G=None):
+                          G=None, x_infr=None):
     """The NumPy mirror of Model.ais_posterior (csrc/kernels_ais_post.hpp states the law): the forward chains of
     ais_log_likelihood_counter, continued.  The scan at beta_T = 1 (uniform block T + 1) is the first KEPT scan; kept scans
     2 .. ``n_keep`` follow at beta = 1 with the uniform blocks T + 2, T + 3, ...; none of them enters w.  In every kept scan
@@ -228,7 +273,8 @@ def ais_posterior_counter(theta, Y, n_chains=16, n_temps=128, n_keep=4, betas=No
     "chain_map_state" (uint8 (N, C, ceil(H / 8))), "chain_flips" (N, C), beside them "chain_map_bool" (N, C, H), "map_bool"
     (N, H), "first_bool" and "first_flips" (the state and the flips after the first kept scan: ``final_bool`` and
     ``chain_flips`` of ais_log_likelihood_counter), "margin" (N, C; every decision of the chain, the kept scans included)
-    and, with ``mean``, "mean" (N, D) = p W^T."""
+    and, with ``mean``, "mean" (N, D) = p W^T.  ``x_infr`` (bool (N, D)): incomplete data, as ais_log_likelihood_counter takes
+    it; "mean" then covers every entry, the missing ones included."""
     C, K = int(n_chains), int(n_keep)
     if C < 1:
         raise ValueError("ais_posterior: n_chains must be positive")
@@ -237,15 +283,18 @@ def ais_posterior_counter(theta, Y, n_chains=16, n_temps=128, n_keep=4, betas=No
     betas = sigmoid_schedule(n_temps) if betas is None else check_betas(betas)
     T = betas.size - 1
     W = np.asarray(theta["W"], dtype=np.float64)
-    Y = np.asarray(Y, dtype=np.float64)
+    Y, mask = _mask_data(np.asarray(Y, dtype=np.float64), x_infr)
     N, H = Y.shape[0], W.shape[1]
     if H > AIS_MAX_H:
         raise ValueError("ais_posterior: H = %d, at most %d latents are supported" % (H, AIS_MAX_H))
     pre1, pilb, pi = ais_scalars(theta)
     B = np.dot(Y, W) if B is None else np.asarray(B, dtype=np.float64)
-    G = np.dot(W.T, W) if G is None else np.asarray(G, dtype=np.float64)
+    if mask is not None:
+        G = Gd = None  # (every datapoint has its own)
+    else:
+        G = np.dot(W.T, W) if G is None else np.asarray(G, dtype=np.float64)
+        Gd = np.diag(G).copy()
     yy = (Y * Y).sum(axis=1)
-    Gd = np.diag(G).copy()
     seed, first_index = int(seed) & _M64, int(first_index) & _M64
     hs = np.arange(H, dtype=np.uint64)
     out = {"log_w": np.empty((N, C)), "rb": np.empty((N, C, H)), "chain_map_lpj": np.empty((N, C)),
@@ -258,20 +307,21 @@ def ais_posterior_counter(theta, Y, n_chains=16, n_temps=128, n_keep=4, betas=No
     first_flips = np.zeros((N, C), dtype=np.int64)
     lz0 = H * np.log1p(np.exp(pilb))
 
-    def scan(s, c, beta, u, flips, margin, R):
-        """One ascending scan of all chains in place; R (C, H) or None: where the conditionals are added."""
+    def scan(s, c, beta, u, flips, margin, R, gd, row):
+        """One ascending scan of all chains in place; R (C, H) or None: where the conditionals are added; gd, row: the
+        diagonal and the rows of the datapoint's G (_datapoint_gram)."""
         for h in range(H):
             on = s[:, h].copy()
-            p = ais_conditional(pre1, pilb, c[:, h], Gd[h], on, beta)
+            p = ais_conditional(pre1, pilb, c[:, h], gd[h], on, beta)
             if R is not None:
                 R[:, h] = R[:, h] + p
             np.minimum(margin, np.abs(u[:, h] - p), out=margin)
             nb = u[:, h] < p
             up, down = nb & ~on, on & ~nb
             if up.any():
-                c[up] = c[up] - G[h]
+                c[up] = c[up] - row(h)
             if down.any():
-                c[down] = c[down] + G[h]
+                c[down] = c[down] + row(h)
             s[:, h] = nb
             flips += up | down
 
@@ -283,9 +333,10 @@ def ais_posterior_counter(theta, Y, n_chains=16, n_temps=128, n_keep=4, betas=No
             u = block(0)
             s = u < pi
             margin = np.abs(u - pi).min(axis=1)
+            gd, row = _datapoint_gram(W, G, Gd, None if mask is None else np.flatnonzero(mask[n]))
             c = np.repeat(B[n][None, :], C, axis=0)
             for i in np.flatnonzero(s.any(axis=0)):
-                c[s[:, i]] = c[s[:, i]] - G[i]
+                c[s[:, i]] = c[s[:, i]] - row(i)
             lw = np.zeros(C)
             R = np.zeros((C, H))
             best = np.full(C, -np.inf)
@@ -294,7 +345,7 @@ def ais_posterior_counter(theta, Y, n_chains=16, n_temps=128, n_keep=4, betas=No
                 if t <= T:
                     lw = lw + (betas[t] - betas[t - 1]) * _ell(pre1, yy[n], B[n], c, s)
                 kept = t >= T
-                scan(s, c, betas[min(t, T)], block(t + 1), flips, margin, R if kept else None)
+                scan(s, c, betas[min(t, T)], block(t + 1), flips, margin, R if kept else None, gd, row)
                 if kept:
                     lpj = s.sum(axis=1).astype(np.float64) * pilb + _ell(pre1, yy[n], B[n], c, s)
                     better = lpj > best  # (strictly: the earliest scan wins ties)

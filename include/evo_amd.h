@@ -502,7 +502,7 @@ typedef struct evoamd_nbound_out {
 int evoamd_neighbour_bound(evoamd_ctx *ctx, int n_parents, unsigned flags, const evoamd_nbound_out *out);
 
 /* Annealed importance sampling: stochastic lower and upper bounds on log p(y_n) - ljc that do not depend on K^n
- * (csrc/kernels_ais.hpp has the law; evo_amd.models.ais_log_likelihood_counter is the NumPy mirror).  EBSC on complete data.
+ * (csrc/kernels_ais.hpp has the law; evo_amd.models.ais_log_likelihood_counter is the NumPy mirror).  EBSC; incomplete data under EVOAMD_AIS_INCOMPLETE.
  * Per datapoint n_chains Gibbs chains of n_temps temperatures, one wavefront per (datapoint, chain); betas: the float64
  * schedule of n_temps + 1 values, 0 = betas[0] < betas[1] <= ... <= betas[n_temps] = 1 (host); seed / first_index: the
  * counter stream of evoamd_generate (datapoint n is index first_index + n of the data set; chain c draws under purpose
@@ -521,9 +521,17 @@ int evoamd_neighbour_bound(evoamd_ctx *ctx, int n_parents, unsigned flags, const
  * Deterministic: two calls give the same bits.  EVOAMD_E_INVALID before anything is written, each with its own text: an
  * unknown flag; no Theta or data; ES3C; the float32 mode (ebsc_f32); background_unit; bsc_direct; masks resident; H > 1024;
  * n_chains < 1; n_temps < 1; betas NULL, not starting at 0, not ending at 1, or descending; EVOAMD_AIS_REVERSE without
- * s_start; EVOAMD_AIS_ADMIT with EVOAMD_AIS_REVERSE, without K^n or with Mprime outside [1, S]. */
+ * s_start; EVOAMD_AIS_ADMIT with EVOAMD_AIS_REVERSE, without K^n or with Mprime outside [1, S].
+ * EVOAMD_AIS_INCOMPLETE: a permission, like EVOAMD_SEED_INCOMPLETE -- with masks resident (evoamd_upload_masks) the chains run
+ * on the datapoint's own G(n) = W_o^T W_o over its reliable entries o, a row formed from W and the mask when a flip happens
+ * (products rounded and added in ascending d; kernels_ais.hpp, INCOMPLETE DATA); B and yy are the resident, masked ones, so
+ * values of y under False never enter.  A datapoint without a reliable entry is not skipped: prior draws, log w = 0.  With
+ * EVOAMD_AIS_ADMIT the candidate lpj kernels and the selection run masked as in every E-step.  Without masks the flag
+ * changes nothing; masks without the flag are refused as before.  Refused with the flag: a D whose column and list (D
+ * doubles + D ints per wavefront) do not fit into the 160 KiB of a compute unit beside the rows over H. */
 #define EVOAMD_AIS_REVERSE 1u
 #define EVOAMD_AIS_ADMIT 2u
+#define EVOAMD_AIS_INCOMPLETE 8u /* (4u stays unassigned: callers have been promised "unknown flag" for it) */
 typedef struct evoamd_ais_out {
   double *ll;            /* (N) */
   double *ess;           /* (N) */
@@ -546,7 +554,7 @@ int evoamd_ais_loglik(evoamd_ctx *ctx, int n_chains, int n_temps, const double *
  * evoamd_ais_loglik, continued (csrc/kernels_ais_post.hpp has the law; evo_amd.models.ais_posterior_counter is the NumPy
  * mirror).  evoamd_posterior_codes, evoamd_reconstruct and evoamd_predictive_moments are expectations under q_n, the posterior
  * truncated to K^n, and evoamd_loglik_exact with marginals stops at H of about 30; this call goes beyond both: a forward chain
- * with its weight is a properly weighted sample of the TRUE posterior.  EBSC on complete data, H <= 1024.
+ * with its weight is a properly weighted sample of the TRUE posterior.  EBSC, H <= 1024; incomplete data: evoamd_ais_posterior_ex.
  * The chains are those of evoamd_ais_loglik with flags = 0 (same stream, start and schedule): the scan at betas[n_temps] = 1
  * is the first of n_keep >= 1 KEPT scans, the others follow at beta = 1 with the uniform blocks n_temps + 2, ...; in a kept
  * scan the conditional p(s_h = 1 | the rest) is added to R_c[h] when latent h is decided (Rao-Blackwell), r_ch = R_c[h] /
@@ -585,6 +593,11 @@ typedef struct evoamd_ais_post_out {
 } evoamd_ais_post_out;
 int evoamd_ais_posterior(evoamd_ctx *ctx, int n_chains, int n_temps, int n_keep, const double *betas, uint64_t seed,
                          uint64_t first_index, int64_t block_datapoints, const evoamd_ais_post_out *out);
+/* evoamd_ais_posterior with flags: 0 = that call; EVOAMD_AIS_INCOMPLETE admits resident masks as for evoamd_ais_loglik (the
+ * chains on G(n) of the reliable entries; mean = p W^T covers every entry, the missing ones included).  Any other flag, and
+ * a D that does not fit into LDS, is EVOAMD_E_INVALID before anything is written. */
+int evoamd_ais_posterior_ex(evoamd_ctx *ctx, int n_chains, int n_temps, int n_keep, const double *betas, uint64_t seed,
+                            uint64_t first_index, int64_t block_datapoints, unsigned flags, const evoamd_ais_post_out *out);
 
 /* Per-datapoint scores of the lpj rows and K^n resident on the device (after a seed, an upload or any pass), each output
  * (N) or NULL.  With m = max_s lpj_ns, w_s = exp(lpj_ns - m), z = sum_s w_s over the S_perm + S columns:

@@ -10,9 +10,12 @@ of ``--repeat`` calls with (min - max):
   result   L_lower, L_upper and their difference (seed r of the r-th repeat: the spread is the estimator's), the quartiles
            of ess in both directions, flips per chain and temperature;
   beside   F (posterior_scores), L^ of estimate_log_likelihood (T = 256 draws) in the same run: L_lower - F next to L^ - F;
-  admit    once, at the largest T: F before and after admit=True and S_sub.
+  admit    once, at the largest T: F before and after admit=True and S_sub;
+  masked   with ``--missing F[,F]``: the same forward and reverse calls with that share of the entries hidden (i.i.d. mask,
+           NaN under False, incomplete=True; K^n seeded and swept on the incomplete data, for F alone) beside the complete
+           calls of this run: wall, the "ais" span of ``--repeat`` calls, their ratio, n_flips per chain, the bracket width.
 
-    python tools/time_ais.py [--n-data 20000] [--refine 20] [--temps 32,128,512] [--chains 16] [--repeat 5]
+    python tools/time_ais.py [--n-data 20000] [--refine 20] [--temps 32,128,512] [--chains 16] [--repeat 5] [--missing 0.5,0.1]
 """
 import argparse
 import os
@@ -42,7 +45,10 @@ def main():
     ap.add_argument("--temps", default="32,128,512")
     ap.add_argument("--chains", type=int, default=16)
     ap.add_argument("--repeat", type=int, default=5, help="timed calls per figure (median, min - max)")
+    ap.add_argument("--missing", default="", help="fractions of hidden entries, e.g. 0.5,0.1: the masked calls (incomplete=True) "
+                                                  "beside the complete calls of the same run")
     args = ap.parse_args()
+    args.missing = [float(f) for f in args.missing.split(",") if f]
     temps = [int(t) for t in args.temps.split(",")]
     algo, D, H, S, _ = CONFIGS["c5"]
     N, C = args.n_data, args.chains
@@ -68,7 +74,9 @@ def main():
                                 quartiles(est["ess"])), flush=True)
     model.ais_log_likelihood(theta, suff, my_data, n_chains=2, n_temps=4, seed=1)  # warm-up: code objects, buffers
     model.ais_log_likelihood(theta, suff, my_data, n_chains=2, n_temps=4, seed=1, direction="reverse", s_start=s_true)
+    complete = {}  # T -> direction -> (median wall, the spans of --repeat further calls): what --missing is held against
     for T in temps:
+        complete[T] = {}
         rows = {"forward": ([], [], None), "reverse": ([], [], None)}
         for direction in ("forward", "reverse"):
             walls, Ls, info = [], [], None
@@ -79,16 +87,20 @@ def main():
                                                    s_start=s_true if direction == "reverse" else None, per_datapoint=True)
                 walls.append((time.perf_counter() - t0) * 1e3)
                 Ls.append(L)
-            eng.timing(("ais",))
-            eng.timing_reset()
-            model.ais_log_likelihood(theta, suff, my_data, n_chains=C, n_temps=T, seed=1, direction=direction,
-                                     s_start=s_true if direction == "reverse" else None)
-            span, n_spans = eng.kernel_time_ms("ais")
-            eng.timing(False)
+            spans = []
+            for r in range(args.repeat):
+                eng.timing(("ais",))
+                eng.timing_reset()
+                model.ais_log_likelihood(theta, suff, my_data, n_chains=C, n_temps=T, seed=1 + r, direction=direction,
+                                         s_start=s_true if direction == "reverse" else None)
+                span, n_spans = eng.kernel_time_ms("ais")
+                spans.append(span * n_spans)
+                eng.timing(False)
             rows[direction] = (walls, Ls, info)
-            print("T=%d %s %s: wall %s ms per call (median of %d), kernel span %.2f ms (%d span); ess quartiles %s; "
-                  "flips per chain and temperature %.3f" % (T, direction, tag, mmm(walls), args.repeat, span * n_spans, n_spans,
-                                                            quartiles(info["ess"]), info["n_flips"].mean() / (C * T)), flush=True)
+            complete[T][direction] = (float(np.median(walls)), spans)
+            print("T=%d %s %s: wall %s ms per call (median of %d), kernel span %s ms; ess quartiles %s; flips per chain and "
+                  "temperature %.3f, per chain %.3f" % (T, direction, tag, mmm(walls), args.repeat, mmm(spans), quartiles(info["ess"]),
+                                                        info["n_flips"].mean() / (C * T), info["n_flips"].mean() / C), flush=True)
         lo, up = rows["forward"][1], rows["reverse"][1]
         gap = [u - l for u, l in zip(up, lo)]
         print("T=%d %s: L_lower %s, L_upper %s, L_upper - L_lower %s; L_lower - F %.4f beside L^ - F %.4f" % (
@@ -99,6 +111,57 @@ def main():
     print("admit T=%d %s: mean F_n before %.4f, after %.4f (posterior_scores after: %.4f), S_sub %.4f, datapoints improved %d "
           "of %d" % (T, tag, float(info["F_before"].mean()), float(info["F_after"].mean()), float(np.mean(after["F"])),
                      info["S_sub"], int((info["F_after"] > info["F_before"]).sum()), N), flush=True)
+    for missing in args.missing:
+        masked(args, temps, theta, Y, s_true, missing, complete, tag)
+    eng.close()
+
+
+def masked(args, temps, theta, Y, s_true, missing, complete, tag):
+    """The same calls with ``missing`` of the entries hidden (an i.i.d. mask, NaN under False) and incomplete=True, on a
+    model of its own, beside the complete figures of this run (``complete``: T -> direction -> (wall, span))."""
+    algo, D, H, S, _ = CONFIGS["c5"]
+    N, C = args.n_data, args.chains
+    x_infr = np.random.RandomState(11).random_sample(Y.shape) >= missing
+    my_data = {"y": np.where(x_infr, Y, np.nan), "x_infr": x_infr, "x": x_infr.copy()}
+    model = BSC(D, H, S, rng="device", sync_host=False, seed=1)
+    eng = model.engine
+    suff = model.seed_resident_states(dict(theta), my_data, *EA, incomplete=True)
+    sweep = model.sweep_resident_states(dict(theta), suff, my_data, n_sweeps=8, incomplete=True)
+    F = float(model.posterior_scores(theta, suff, my_data)["F"].mean())
+    tag = "%s missing=%.2f" % (tag, missing)
+    print("masked start %s: mean F_n of the seeded and swept K^n %.4f (%d sweeps ran)" % (tag, F, sweep.n_done), flush=True)
+    kw = dict(incomplete=True)
+    model.ais_log_likelihood(theta, suff, my_data, n_chains=2, n_temps=4, seed=1, **kw)  # warm-up: code objects, buffers
+    model.ais_log_likelihood(theta, suff, my_data, n_chains=2, n_temps=4, seed=1, direction="reverse", s_start=s_true, **kw)
+    for T in temps:
+        Ls = {}
+        for direction in ("forward", "reverse"):
+            start = s_true if direction == "reverse" else None
+            walls, Ls[direction], info = [], [], None
+            for r in range(args.repeat):
+                eng.synchronize()
+                t0 = time.perf_counter()
+                L, info = model.ais_log_likelihood(theta, suff, my_data, n_chains=C, n_temps=T, seed=1 + r, direction=direction,
+                                                   s_start=start, per_datapoint=True, **kw)
+                walls.append((time.perf_counter() - t0) * 1e3)
+                Ls[direction].append(L)
+            spans = []
+            for r in range(args.repeat):
+                eng.timing(("ais",))
+                eng.timing_reset()
+                model.ais_log_likelihood(theta, suff, my_data, n_chains=C, n_temps=T, seed=1 + r, direction=direction, s_start=start,
+                                         **kw)
+                ms, n = eng.kernel_time_ms("ais")
+                spans.append(ms * n)
+                eng.timing(False)
+            wall_c, span_c = complete[T][direction]
+            print("masked T=%d %s %s: wall %s ms per call, kernel span %s ms; complete call of this run: wall %.4f ms, span %s ms; "
+                  "span ratio %.2f; ess quartiles %s; n_flips per chain %.3f" % (
+                      T, direction, tag, mmm(walls), mmm(spans), wall_c, mmm(span_c), float(np.median(spans)) / float(np.median(span_c)),
+                      quartiles(info["ess"]), info["n_flips"].mean() / C), flush=True)
+        gap = [u - l for u, l in zip(Ls["reverse"], Ls["forward"])]
+        print("masked T=%d %s: L_lower %s, L_upper %s, L_upper - L_lower %s; L_lower - (ljc + mean F_n) %.4f" % (
+            T, tag, mmm(Ls["forward"]), mmm(Ls["reverse"]), mmm(gap), float(np.median(Ls["forward"])) - (eng.ljc + F)), flush=True)
     eng.close()
 
 
