@@ -102,6 +102,13 @@ class AisPostOut(ctypes.Structure):
                 ("chain_map_lpj", _c_dp), ("chain_map_state", _c_u64p), ("chain_flips", _c_i32p)]
 
 
+class AisPostSelOut(ctypes.Structure):
+    """evoamd_ais_post_sel_out: evoamd_ais_post_out and the outputs of EVOAMD_AIS_ADMIT, each pointer may be NULL."""
+    _fields_ = [("post", AisPostOut), ("F_before", _c_dp), ("F_after", _c_dp), ("n_distinct", _c_i32p), ("n_new", _c_i32p),
+                ("n_proposed", _c_i32p), ("n_admitted", _c_i32p), ("map_held_before", _c_i32p), ("map_held_after", _c_i32p),
+                ("admit_sums", _c_dp)]
+
+
 class PredScoreOut(ctypes.Structure):
     """evoamd_pred_score_out: the outputs of evoamd_predictive_score, each pointer may be NULL (logp and pit together)."""
     _fields_ = [("logp", _c_dp), ("pit", _c_dp), ("logp_n", _c_dp), ("count", _c_i32p)]
@@ -180,6 +187,10 @@ SIGNATURES = {
     "evoamd_ais_loglik": (_I, [_vp, _I, _I, _c_dp, _U64, _U64, ctypes.c_uint, _c_u64p, _I, ctypes.POINTER(AisOut)]),
     "evoamd_ais_posterior": (_I, [_vp, _I, _I, _I, _c_dp, _U64, _U64, _I64, ctypes.POINTER(AisPostOut)]),
     "evoamd_ais_posterior_ex": (_I, [_vp, _I, _I, _I, _c_dp, _U64, _U64, _I64, ctypes.c_uint, ctypes.POINTER(AisPostOut)]),
+    "evoamd_ais_posterior_sel": (_I, [_vp, _I, _I, _I, _c_dp, _U64, _U64, _I64, ctypes.c_uint, ctypes.POINTER(_I64), _I64, _I,
+                                      ctypes.POINTER(AisPostSelOut)]),
+    "evoamd_ais_post_admit_probe": (_I, [_vp, _c_dp, _c_u64p, _I, ctypes.POINTER(_I64), _I64, _c_i32p, _c_i32p, _c_i32p,
+                                         _c_i32p, _c_u64p, ctypes.POINTER(_I)]),
     "evoamd_posterior_scores": (_I, [_vp, _c_dp, _c_dp, _c_i32p, _c_i32p, _c_dp]),
     "evoamd_remap_latents": (_I, [_vp, _c_i32p, _I, _c_i32p, ctypes.POINTER(_I64)]),
     "evoamd_adopt_remapped_states": (_I, [_vp]),

@@ -178,7 +178,7 @@ enum {  // internal kernel ids (see evoamd_kernel_name)
   KID_NBOUND,        // evoamd_neighbour_bound: the neighbourhood kernel (ES3C: with the transpose of GP) and the bound of the rows
   KID_PRED_SCORE,    // evoamd_predictive_score: the transpose of W, the visit list, the score kernel, its partials and their two reductions
   KID_AIS,           // evoamd_ais_loglik: the chain kernel and the fold over the chains (admit: the emission; its lpj and selection count in their own classes)
-  KID_AIS_POST,      // evoamd_ais_posterior: the chain kernel and the fold of every block of datapoints (the product for `mean` counts as gemm)
+  KID_AIS_POST,      // evoamd_ais_posterior: the chain kernel and the fold of every block of datapoints (the product for `mean` counts as gemm); _sel: the emission and the tally too
   KID_COUNT
 };
 
@@ -1869,11 +1869,15 @@ static bool gemm_vec_ok_f32(const float *p, int ld) { return (ld % 4) == 0 && ((
 
 // Ct / ldct: C^T as well where the parameter-sized kernel runs; returns whether it was written
 static bool launch_gemm_nn_raw(evoamd_ctx *c, const double *A, int lda, const double *B, int ldb, double *C, int ldc,
-                               i64 M, int Nc, int K, double *Ct = nullptr, int ldct = 0) {
+                               i64 M, int Nc, int K, double *Ct = nullptr, int ldct = 0, i64 route_M = 0) {
+  // route_M: the rows of the larger product that these M rows are some of; above 1024 that product takes the kernel below,
+  // and so does this one, with its order of summation
   if (M <= 1024 && Nc <= 1024 && K <= 1024) {  // parameter-sized: one wave per 16 x 16 block
-    c->route = {EVOAMD_ROUTE_NN_SMALL, 16, 1, 0, 0, 0, 0, 0};
-    gemm_nn_small_kernel<<<dim3(cdiv(Nc, 16), cdiv(M, 16)), 256, 0, c->stream>>>(A, lda, B, ldb, C, ldc, (int)M, Nc, K, Ct, ldct);
-    return Ct != nullptr;
+    if (route_M <= 1024) {
+      c->route = {EVOAMD_ROUTE_NN_SMALL, 16, 1, 0, 0, 0, 0, 0};
+      gemm_nn_small_kernel<<<dim3(cdiv(Nc, 16), cdiv(M, 16)), 256, 0, c->stream>>>(A, lda, B, ldb, C, ldc, (int)M, Nc, K, Ct, ldct);
+      return Ct != nullptr;
+    }
   }
   const int gx = (int)cdiv(Nc, GEMM_BN), gy = (int)cdiv(M, GEMM_BM);
   const int rows_per_xcd = (gy + 7) / 8;
@@ -6791,20 +6795,60 @@ extern "C" int evoamd_ais_loglik(evoamd_ctx *c, int n_chains, int n_temps, const
 // block, the product for `mean`, fetch.  Nothing of the EM state is written, y_hat and its validity included: B = Y W is
 // (re)formed like by every lpj pass, nothing else.
 // ---------------------------------------------------------------------------------------
+// evoamd_ais_posterior_sel: the rows of every per-datapoint output are the n listed datapoints in list order (n = N and
+// row = datapoint without a list); with admit the stages emission + candidate lpj + selection + tally follow the fold.
 struct AisPostPlan {
-  bool masked = false;
+  bool masked = false, listed = false, admit = false;
   int C = 0, T = 0, K = 0, nc = 1;  // nc: the chunk count the kernel is instantiated for (1, 2, 4, 8, 16)
-  i64 block = 1;                    // datapoints per block
+  i64 n = 0;                        // rows: listed datapoints, or N
+  i64 block = 1;                    // rows per block
   bool mean = false;
   size_t lds = 0;
-  size_t n_d = 0, n_rows = 0, n_i = 0, n_s = 0;  // elements of aisp_d / aisp_rows / aisp_i / aisp_s
+  size_t n_d = 0, n_rows = 0, n_i = 0, n_s = 0, n_nf = 0;  // elements of aisp_d / aisp_rows / aisp_i / aisp_s / aisp_nf
 };
 
+// the list of evoamd_ais_posterior_sel and of the probe: strictly ascending within [0, N); the first offender is named
+static int ais_post_check_index(const evoamd_ctx *c, const char *who, const int64_t *index, int64_t n_index) {
+  if (n_index < 0) return fail(EVOAMD_E_INVALID, "%s: n_index = %lld must not be negative", who, (long long)n_index);
+  if (!index) {
+    if (n_index > 0) return fail(EVOAMD_E_INVALID, "%s: index is NULL with n_index = %lld", who, (long long)n_index);
+    return 0;
+  }
+  for (int64_t i = 0; i < n_index; i++) {
+    if (index[i] < 0 || index[i] >= c->N)
+      return fail(EVOAMD_E_INVALID, "%s: index[%lld] = %lld is outside [0, N = %lld)", who, (long long)i, (long long)index[i], (long long)c->N);
+    if (i > 0 && index[i] == index[i - 1])
+      return fail(EVOAMD_E_INVALID, "%s: index[%lld] = %lld is repeated (a datapoint is listed once)", who, (long long)i, (long long)index[i]);
+    if (i > 0 && index[i] < index[i - 1])
+      return fail(EVOAMD_E_INVALID, "%s: index[%lld] = %lld descends (after %lld): the list is ascending", who, (long long)i,
+                  (long long)index[i], (long long)index[i - 1]);
+  }
+  return 0;
+}
+
+// sel: the call is evoamd_ais_posterior_sel (index / n_index / Mprime are read, EVOAMD_AIS_ADMIT is a known flag)
 static int ais_post_plan(const evoamd_ctx *c, int n_chains, int n_temps, int n_keep, const double *betas, int64_t block_datapoints,
-                         unsigned flags, bool mean, AisPostPlan &p) {
+                         unsigned flags, bool mean, AisPostPlan &p, bool sel = false, const int64_t *index = nullptr,
+                         int64_t n_index = 0, int Mprime = 1) {
   REQUIRE(c && c->configured, "configure first");
-  REQUIRE(!(flags & ~(unsigned)EVOAMD_AIS_INCOMPLETE), "evoamd_ais_posterior_ex: unknown flag");
+  if (sel)
+    REQUIRE(!(flags & ~(unsigned)(EVOAMD_AIS_INCOMPLETE | EVOAMD_AIS_ADMIT)), "evoamd_ais_posterior_sel: unknown flag");
+  else
+    REQUIRE(!(flags & ~(unsigned)EVOAMD_AIS_INCOMPLETE), "evoamd_ais_posterior_ex: unknown flag");
   TRY(ais_admit(c, "evoamd_ais_posterior", n_chains, n_temps, (flags & EVOAMD_AIS_INCOMPLETE) != 0, &p.masked));
+  p.n = c->N;
+  if (sel) {
+    TRY(ais_post_check_index(c, "evoamd_ais_posterior_sel", index, n_index));
+    p.listed = index != nullptr, p.admit = (flags & EVOAMD_AIS_ADMIT) != 0;
+    if (p.listed) p.n = n_index;
+    if (p.admit) {
+      if (c->kn_lost)
+        return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior_sel: EVOAMD_AIS_ADMIT needs K^n on the device (evoamd_init_states stopped "
+                    "at its round cap: upload or initialise K^n first)");
+      if (Mprime < 1 || Mprime > c->S)
+        return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior_sel: Mprime = %d must be in [1, S = %d]", Mprime, c->S);
+    }
+  }
   if (n_keep < 1) return fail(EVOAMD_E_INVALID, "evoamd_ais_posterior: n_keep = %d must be positive", n_keep);
   REQUIRE((i64)n_temps + n_keep < 2147483647LL, "evoamd_ais_posterior: n_temps + n_keep must fit in int32");
   TRY(ais_check_betas("evoamd_ais_posterior", n_temps, betas));
@@ -6817,35 +6861,45 @@ static int ais_post_plan(const evoamd_ctx *c, int n_chains, int n_temps, int n_k
                 (long long)std::max<i64>(block_datapoints, 1), n_chains, 64 * c->HW, (unsigned long long)(AIS_POST_ROWS_BYTES >> 20));
   p.C = n_chains, p.T = n_temps, p.K = n_keep, p.mean = mean;
   while (p.nc < c->HW) p.nc <<= 1;
-  p.block = std::min<i64>(block_datapoints > 0 ? block_datapoints : fit, c->N);
+  p.block = std::max<i64>(std::min<i64>(block_datapoints > 0 ? block_datapoints : fit, p.n), 1);
   p.lds = p.masked ? ais_post_masked_lds_bytes(c->HW, c->D) : ais_post_lds_bytes(c->HW);
   if (p.masked) TRY(ais_check_masked_lds(c, "evoamd_ais_posterior", p.lds));
-  const size_t N = (size_t)c->N, NC = N * (size_t)n_chains;
+  const size_t N = (size_t)p.n, NC = N * (size_t)n_chains;
   p.n_d = (size_t)n_temps + 1 + 3 * NC + 2 * N * c->H + 7 * N + (mean ? N * c->D : 0);
   p.n_rows = (size_t)p.block * row;
   p.n_i = NC;
   p.n_s = NC * c->HW + N * c->HW;
+  p.n_nf = N + (p.listed ? N : 0);  // n_flips | the list
+  if (p.admit) {  // F_before | F_after (n each) | F of every datapoint (N); key (n, C) | five counts and map_held twice (n each)
+    p.n_d += 2 * N + (size_t)c->N;
+    p.n_i += NC + 6 * N;
+  }
   return 0;
 }
 
-// the views into the call's buffers
+// the views into the call's buffers (N: the rows of the plan)
 struct AisPostBufs {
   double *betas, *log_w, *best_lpj, *wts, *p, *p_se, *count, *map_lpj, *ll, *ess, *lw_mean, *lw_min, *lw_max, *mean;
+  double *F_before, *F_after, *F_full;  // admit
   int *flips;
+  int *key, *n_distinct, *n_new, *n_proposed, *n_admitted, *held_before, *held_after;  // admit
   u64 *best, *map_state;
-  i64 *n_flips;
+  i64 *n_flips, *index;  // index: listed
 };
 static AisPostBufs ais_post_views(const evoamd_ctx *c, const AisPostPlan &p) {
-  const size_t N = (size_t)c->N, NC = N * (size_t)p.C, NH = N * (size_t)c->H;
+  const size_t N = (size_t)p.n, NC = N * (size_t)p.C, NH = N * (size_t)c->H;
   AisPostBufs b;
   // (p, p_se and mean first: the product for `mean` reads 16-byte vectors where the operands allow it)
   b.p = c->aisp_d, b.p_se = b.p + NH, b.mean = b.p_se + NH, b.betas = b.mean + (p.mean ? N * (size_t)c->D : 0);
   b.log_w = b.betas + p.T + 1, b.best_lpj = b.log_w + NC, b.wts = b.best_lpj + NC, b.count = b.wts + NC;
   b.map_lpj = b.count + N, b.ll = b.map_lpj + N, b.ess = b.ll + N, b.lw_mean = b.ess + N, b.lw_min = b.lw_mean + N;
   b.lw_max = b.lw_min + N;
+  b.F_before = b.lw_max + N, b.F_after = b.F_before + N, b.F_full = b.F_after + N;
   b.flips = c->aisp_i;
+  b.key = b.flips + NC, b.n_distinct = b.key + NC, b.n_new = b.n_distinct + N, b.n_proposed = b.n_new + N;
+  b.n_admitted = b.n_proposed + N, b.held_before = b.n_admitted + N, b.held_after = b.held_before + N;
   b.best = c->aisp_s, b.map_state = b.best + NC * c->HW;
-  b.n_flips = c->aisp_nf;
+  b.n_flips = c->aisp_nf, b.index = b.n_flips + N;
   return b;
 }
 
@@ -6854,6 +6908,12 @@ static int ais_post_launch_one(evoamd_ctx *c, const AisPostPlan &p, const AisPos
   if (p.lds > (64u << 10) && !(c->aisp_lds_set & bit)) {  // once per instantiation
     HIP_TRY(hipFuncSetAttribute((const void *)ais_post_chain_kernel<NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
     c->aisp_lds_set |= bit;
+  }
+  if constexpr (NC == 1) {  // (its LDS stays far below 64 KiB) without a list: the instantiation that reads no index
+    if (!a.index) {
+      ais_post_chain_kernel<1, false, true><<<grid, 64 * AIS_WAVES, p.lds, c->stream>>>(a);
+      return 0;
+    }
   }
   ais_post_chain_kernel<NC><<<grid, 64 * AIS_WAVES, p.lds, c->stream>>>(a);
   return 0;
@@ -6894,16 +6954,19 @@ static int ais_post_prepare(evoamd_ctx *c, const AisPostPlan &p) {
   TRY(c->aisp_rows.ensure(c, p.n_rows));
   TRY(c->aisp_i.ensure(c, p.n_i));
   TRY(c->aisp_s.ensure(c, p.n_s));
-  TRY(c->aisp_nf.ensure(c, (size_t)c->N));
+  TRY(c->aisp_nf.ensure(c, p.n_nf));
   return 0;
 }
 
 // ---- stage: block by block, the chains and the fold over them
 // (rb_host: where the caller wants the rows r_c., (N, C, H) on the host -- each block's leave before the next one overwrites them)
+// (index: the caller's list when the plan is listed -- the blocks then run over list positions, and the chain kernel reads
+// the source datapoint of a row from the list)
 static int ais_post_chains_stage(evoamd_ctx *c, const AisPostPlan &p, const double *betas, uint64_t seed, uint64_t first_index,
-                                 double *rb_host) {
+                                 double *rb_host, const int64_t *index = nullptr) {
   const AisPostBufs b = ais_post_views(c, p);
   HIP_TRY(hipMemcpyAsync(b.betas, betas, ((size_t)p.T + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (p.listed) HIP_TRY(hipMemcpyAsync(b.index, index, (size_t)p.n * sizeof(i64), hipMemcpyHostToDevice, c->stream));
   AisPostArgs a = {};
   a.G = c->G, a.Gd = c->diag, a.dpar = c->dpar, a.betas = b.betas, a.rb = c->aisp_rows, a.err = c->err;
   a.C = p.C, a.T = p.T, a.K = p.K, a.H = c->H, a.HW = c->HW;
@@ -6915,12 +6978,17 @@ static int ais_post_chains_stage(evoamd_ctx *c, const AisPostPlan &p, const doub
   f.lw_mean = b.lw_mean, f.lw_min = b.lw_min, f.lw_max = b.lw_max, f.map_state = b.map_state, f.n_flips = b.n_flips;
   f.C = p.C, f.H = c->H, f.HW = c->HW;
   SpanGuard g(c, KID_AIS_POST);
-  for (i64 n0 = 0; n0 < c->N; n0 += p.block) {
-    a.nb = f.nb = std::min<i64>(p.block, c->N - n0);
+  for (i64 n0 = 0; n0 < p.n; n0 += p.block) {
+    a.nb = f.nb = std::min<i64>(p.block, p.n - n0);
     f.n0 = n0;
     const size_t i0 = (size_t)n0 * p.C;  // the chain kernel sees its block alone
-    a.Bm = c->Bm + (size_t)n0 * c->H, a.yy = c->yy + n0, a.first_index = first_index + (uint64_t)n0;
-    if (p.masked) a.mask = c->mask_infr + (size_t)n0 * c->D;
+    if (p.listed) {  // ... of the list: the data are those of the whole shard
+      a.index = b.index + n0, a.Bm = c->Bm, a.yy = c->yy, a.first_index = first_index;
+      if (p.masked) a.mask = c->mask_infr;
+    } else {
+      a.Bm = c->Bm + (size_t)n0 * c->H, a.yy = c->yy + n0, a.first_index = first_index + (uint64_t)n0;
+      if (p.masked) a.mask = c->mask_infr + (size_t)n0 * c->D;
+    }
     a.log_w = b.log_w + i0, a.best_lpj = b.best_lpj + i0, a.best = b.best + i0 * c->HW, a.flips = b.flips + i0;
     TRY(ais_post_launch_chains(c, p, a));
     HIP_TRY(hipGetLastError());
@@ -6940,7 +7008,8 @@ static int ais_post_chains_stage(evoamd_ctx *c, const AisPostPlan &p, const doub
 static int ais_post_mean_stage(evoamd_ctx *c, const AisPostPlan &p) {
   const AisPostBufs b = ais_post_views(c, p);
   SpanGuard g(c, KID_GEMM);
-  launch_gemm_nn_raw(c, b.p, c->H, c->Wt, c->D, b.mean, c->D, c->N, c->D, c->H);
+  // (listed: the kernel the call over all N datapoints takes, so that a row has that call's bits)
+  launch_gemm_nn_raw(c, b.p, c->H, c->Wt, c->D, b.mean, c->D, p.n, c->D, c->H, nullptr, 0, p.listed ? c->N : 0);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -6948,7 +7017,7 @@ static int ais_post_mean_stage(evoamd_ctx *c, const AisPostPlan &p) {
 // ---- stage: the outputs, each where the caller gave a buffer
 static int ais_post_fetch(evoamd_ctx *c, const AisPostPlan &p, const evoamd_ais_post_out &o) {
   const AisPostBufs b = ais_post_views(c, p);
-  const size_t N = (size_t)c->N, NC = N * (size_t)p.C, H = (size_t)c->H;
+  const size_t N = (size_t)p.n, NC = N * (size_t)p.C, H = (size_t)c->H;
   HIP_TRY(fetch_if(c, o.p, b.p, N * H * sizeof(double)));
   HIP_TRY(fetch_if(c, o.p_se, b.p_se, N * H * sizeof(double)));
   HIP_TRY(fetch_if(c, o.count, b.count, N * sizeof(double)));
@@ -6984,6 +7053,128 @@ extern "C" int evoamd_ais_posterior_ex(evoamd_ctx *c, int n_chains, int n_temps,
   TRY(ais_post_chains_stage(c, p, betas, seed, first_index, o.rb));
   if (p.mean) TRY(ais_post_mean_stage(c, p));
   return ais_post_fetch(c, p, o);
+}
+
+// the arguments of the emission and of the tally, from the call's buffers (F_out / map_held: the caller names the side)
+static AisPostAdmitArgs ais_post_admit_args(const evoamd_ctx *c, const AisPostPlan &p, const AisPostBufs &b) {
+  AisPostAdmitArgs a = {};
+  a.best_lpj = b.best_lpj, a.best = b.best, a.index = p.listed ? b.index : nullptr, a.states = c->states;
+  a.cand = c->cand, a.cand_dig = (c->use_digest && c->cand_dig) ? c->cand_dig.get() : nullptr, a.cand_counts = c->cand_counts;
+  a.key = b.key, a.n_distinct = b.n_distinct, a.n_new = b.n_new, a.n_proposed = b.n_proposed, a.n_admitted = b.n_admitted;
+  a.n = p.n, a.C = p.C, a.S = c->S, a.HW = c->HW, a.Cmax = c->Cmax;
+  return a;
+}
+
+// the emission alone: cand_counts cleared (0 outside the list), then one wavefront per row
+static int ais_post_emit(evoamd_ctx *c, const AisPostAdmitArgs &a) {
+  SpanGuard g(c, KID_AIS_POST);
+  HIP_TRY(hipMemsetAsync(c->cand_counts, 0, (size_t)c->N * sizeof(int), c->stream));
+  if (a.n > 0) ais_post_admit_kernel<<<cdiv(a.n, AIS_POST_ADMIT_WAVES), 64 * AIS_POST_ADMIT_WAVES, 0, c->stream>>>(a);
+  HIP_TRY(hipGetLastError());
+  DBG_SYNC(c, "ais_post admit");
+  return 0;
+}
+
+// ---- stage (admit): the resident rows and F before, the emission, the tail of a sweep (candidate lpj, selection), F after
+// and the tally
+static int ais_post_admit_stage(evoamd_ctx *c, const AisPostPlan &p, int Mprime, double sums[2]) {
+  const AisPostBufs b = ais_post_views(c, p);
+  on_estep_route(c, /*fused=*/false);
+  TRY(estep_resident_pass(c));
+  posterior_score_kernel<<<cdiv(c->N, SCORE_WAVES), 64 * SCORE_WAVES, 0, c->stream>>>(c->lpj, c->states, c->N, c->L, c->S, c->S_perm,
+                                                                                      c->HW, b.F_full, nullptr, nullptr, nullptr, nullptr);
+  HIP_TRY(hipGetLastError());
+  AisPostAdmitArgs a = ais_post_admit_args(c, p, b);
+  a.F_full = b.F_full, a.F_out = b.F_before, a.map_held = b.held_before;
+  TRY(ais_post_emit(c, a));
+  on_cand_installed(c, /*near_parents=*/false);
+  TRY(eval_candidates(c));
+  made_cand_lpj(c);
+  TRY(estep_select(c, Mprime, sums));
+  posterior_score_kernel<<<cdiv(c->N, SCORE_WAVES), 64 * SCORE_WAVES, 0, c->stream>>>(c->lpj, c->states, c->N, c->L, c->S, c->S_perm,
+                                                                                      c->HW, b.F_full, nullptr, nullptr, nullptr, nullptr);
+  HIP_TRY(hipGetLastError());
+  a.F_out = b.F_after, a.map_held = b.held_after;
+  {
+    SpanGuard g(c, KID_AIS_POST);
+    ais_post_tally_kernel<<<cdiv(p.n, AIS_POST_ADMIT_WAVES), 64 * AIS_POST_ADMIT_WAVES, 0, c->stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    DBG_SYNC(c, "ais_post tally");
+  }
+  return 0;
+}
+
+extern "C" int evoamd_ais_posterior_sel(evoamd_ctx *c, int n_chains, int n_temps, int n_keep, const double *betas, uint64_t seed,
+                                        uint64_t first_index, int64_t block_datapoints, unsigned flags, const int64_t *index,
+                                        int64_t n_index, int Mprime, const evoamd_ais_post_sel_out *out) {
+  const evoamd_ais_post_sel_out o = out ? *out : evoamd_ais_post_sel_out{};
+  AisPostPlan p;
+  TRY(ais_post_plan(c, n_chains, n_temps, n_keep, betas, block_datapoints, flags, o.post.mean != nullptr, p, /*sel=*/true, index,
+                    n_index, Mprime));
+  if (o.admit_sums) o.admit_sums[0] = o.admit_sums[1] = 0.0;
+  if (p.n == 0) return 0;  // an empty list: nothing to run, nothing written
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(ais_post_prepare(c, p));
+  TRY(ais_post_chains_stage(c, p, betas, seed, first_index, o.post.rb, index));
+  if (p.mean) TRY(ais_post_mean_stage(c, p));
+  if (p.admit) {
+    double sums[2] = {0.0, 0.0};
+    TRY(ais_post_admit_stage(c, p, Mprime, sums));
+    if (o.admit_sums) o.admit_sums[0] = sums[0], o.admit_sums[1] = sums[1];
+    const AisPostBufs b = ais_post_views(c, p);
+    const size_t n = (size_t)p.n;
+    HIP_TRY(fetch_if(c, o.F_before, b.F_before, n * sizeof(double)));
+    HIP_TRY(fetch_if(c, o.F_after, b.F_after, n * sizeof(double)));
+    HIP_TRY(fetch_if(c, o.n_distinct, b.n_distinct, n * sizeof(int)));
+    HIP_TRY(fetch_if(c, o.n_new, b.n_new, n * sizeof(int)));
+    HIP_TRY(fetch_if(c, o.n_proposed, b.n_proposed, n * sizeof(int)));
+    HIP_TRY(fetch_if(c, o.n_admitted, b.n_admitted, n * sizeof(int)));
+    HIP_TRY(fetch_if(c, o.map_held_before, b.held_before, n * sizeof(int)));
+    HIP_TRY(fetch_if(c, o.map_held_after, b.held_after, n * sizeof(int)));
+  }
+  return ais_post_fetch(c, p, o.post);
+}
+
+// TEST-ONLY: the emission kernel alone on the caller's best_lpj (n, C) and best (n, C, HW words in the layout of K^n) for
+// the rows `index` (n_index of them; NULL: the N datapoints), against the resident K^n.  The result is the candidate batch
+// -- evaluated like any installed batch, so that evoamd_download_candidates reads it -- with the four count arrays (n
+// each) and, where digests are in use, the digests written beside the candidates (N, Cmax; rows beyond a count are not
+// written); *dig_used says whether.  Ties, non-finite values and duplicates cannot be had from the chains at will.
+extern "C" int evoamd_ais_post_admit_probe(evoamd_ctx *c, const double *best_lpj, const uint64_t *best, int n_chains,
+                                           const int64_t *index, int64_t n_index, int32_t *n_distinct, int32_t *n_new,
+                                           int32_t *n_proposed, int32_t *map_held, uint64_t *dig_out, int *dig_used) {
+  REQUIRE(c && c->configured, "configure first");
+  REQUIRE(best_lpj && best && n_distinct && n_new && n_proposed && map_held, "evoamd_ais_post_admit_probe: bad arguments");
+  REQUIRE(c->have_params && c->have_data, "evoamd_ais_post_admit_probe: Theta and data first (the batch is evaluated)");
+  REQUIRE(n_chains >= 1, "evoamd_ais_post_admit_probe: n_chains must be positive");
+  REQUIRE_KN(c);
+  TRY(ais_post_check_index(c, "evoamd_ais_post_admit_probe", index, n_index));
+  AisPostPlan p;
+  p.C = n_chains, p.listed = index != nullptr, p.n = p.listed ? n_index : c->N, p.admit = true;
+  const size_t n = (size_t)p.n, NC = n * (size_t)n_chains;
+  HIP_TRY(hipSetDevice(c->device));
+  TRY(c->aisp_d.ensure(c, 1 + 3 * NC + 2 * n * c->H + 9 * n + (size_t)c->N));
+  TRY(c->aisp_i.ensure(c, 2 * NC + 6 * n + 1));
+  TRY(c->aisp_s.ensure(c, NC * c->HW + n * c->HW + 1));
+  TRY(c->aisp_nf.ensure(c, 2 * n + 1));
+  const AisPostBufs b = ais_post_views(c, p);
+  HIP_TRY(hipMemcpyAsync(b.best_lpj, best_lpj, NC * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(b.best, best, NC * c->HW * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+  if (p.listed && n) HIP_TRY(hipMemcpyAsync(b.index, index, n * sizeof(i64), hipMemcpyHostToDevice, c->stream));
+  AisPostAdmitArgs a = ais_post_admit_args(c, p, b);
+  a.map_held = b.held_before;
+  TRY(ais_post_emit(c, a));
+  on_cand_installed(c, /*near_parents=*/false);
+  TRY(eval_candidates(c));
+  made_cand_lpj(c);
+  HIP_TRY(fetch_if(c, n_distinct, b.n_distinct, n * sizeof(int)));
+  HIP_TRY(fetch_if(c, n_new, b.n_new, n * sizeof(int)));
+  HIP_TRY(fetch_if(c, n_proposed, b.n_proposed, n * sizeof(int)));
+  HIP_TRY(fetch_if(c, map_held, b.held_before, n * sizeof(int)));
+  if (dig_used) *dig_used = a.cand_dig ? 1 : 0;
+  if (a.cand_dig) HIP_TRY(fetch_if(c, dig_out, a.cand_dig, (size_t)c->N * c->Cmax * sizeof(u64)));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 // posterior samples (kernels_posterior_sample.hpp): own buffers; of the EM state only B = Y W is (re)formed, like every lpj pass

@@ -36,6 +36,10 @@
 // The rows r_c. of a block of datapoints go to a buffer of at most AIS_POST_ROWS_BYTES; the host walks the datapoints in
 // blocks, chains then fold.  Nothing depends on the block size: every index of the stream is the datapoint's own.
 //
+// LISTED DATAPOINTS (evoamd_ais_posterior_sel with a list): work item (i, c) runs chain c of datapoint index[i] -- the first
+// hash, yy, the row of B and the row of the mask are that datapoint's, everything written is row i.  So row i has the bits of
+// row index[i] of the call without a list.  The blocks run over list positions; the fold needs no source index.
+//
 // INCOMPLETE DATA (MASKED = true; masks resident and the flag EVOAMD_AIS_INCOMPLETE of evoamd_ais_posterior_ex): the law
 // above with the B_n, yy_n, the list o, G(n), its diagonal and c_j of kernels_ais.hpp's INCOMPLETE DATA -- a row of G(n)
 // is formed from W and the list when a flip happens, products rounded and added in ascending d.  R_c, best, n_flips and
@@ -71,6 +75,9 @@ struct AisPostArgs {
   const double *W;      // (D, H)
   const uint8_t *mask;  // (nb, D) x_infr
   int D;
+  // listed datapoints: work item (i, c) runs the chain of datapoint index[i]; Bm, yy and mask are then those of the whole
+  // shard and first_index that of its first datapoint.  Null for every call without a list.
+  const i64 *index;     // (nb) ascending
 };
 
 static inline size_t ais_post_lds_bytes(int HW) {
@@ -82,7 +89,10 @@ static inline size_t ais_post_masked_lds_bytes(int HW, int D) {
   return (size_t)AIS_WAVES * ais_masked_wave_doubles(HW, D, 2) * sizeof(double) + (size_t)AIS_WAVES * (HW + 1) * sizeof(u64);
 }
 
-template <int NC, bool MASKED = false>
+// PLAIN: the instantiation never sees a list and does not read a.index.  It exists for NC = 1 on complete data alone: there
+// the two scalar registers of the pointer push the kernel over its SGPR budget (99 -> 106, 70 -> 73 VGPRs, 7 -> 6 waves
+// per SIMD); every other instantiation keeps its registers, scratch and LDS with the pointer and takes it at run time.
+template <int NC, bool MASKED = false, bool PLAIN = false>
 __global__ __launch_bounds__(64 * AIS_WAVES) void ais_post_chain_kernel(AisPostArgs a) {
 #pragma clang fp contract(off)
   const int lane = lane_id(), wave = wave_id_uniform();
@@ -111,8 +121,9 @@ __global__ __launch_bounds__(64 * AIS_WAVES) void ais_post_chain_kernel(AisPostA
   }
   const i64 items = a.nb * (i64)C;
   for (i64 it = (i64)blockIdx.x * AIS_WAVES + wave; it < items; it += (i64)gridDim.x * AIS_WAVES) {
-    const i64 n = it / C;
-    const int ch = (int)(it - n * C);
+    const i64 pos = it / C;  // the row of the outputs
+    const int ch = (int)(it - pos * C);
+    const i64 n = (!PLAIN && a.index) ? a.index[pos] : pos;  // (wave-uniform) the datapoint whose chain this is
     const u64 x0 = mix64(a.seed + 0x9e3779b97f4a7c15ull * (a.first_index + (u64)n + 1));
     const u64 purpose = AIS_PURPOSE + (u64)ch;
     const double yy = a.yy[n];
@@ -352,5 +363,161 @@ __global__ __launch_bounds__(64 * AIS_WAVES) void ais_post_fold_kernel(AisPostFo
     a.lw_mean[n] = sum / (double)C;
     a.lw_min[n] = lo, a.lw_max[n] = hi;
     a.n_flips[n] = nf;
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// ADMISSION (EVOAMD_AIS_ADMIT of evoamd_ais_posterior_sel): the best distinct states the chains of a datapoint visited become
+// its rows of the candidate batch; the model's own candidate lpj and selection follow (the host has the order of the stages).
+// evo_amd/models/ais.py: ais_admit_candidates_host is the NumPy mirror of the emission.
+//
+// THE LAW OF THE EMISSION, per listed datapoint i (source datapoint n = index[i], or i without a list), from best_lpj (C) and
+// best (C, HW) of its chains:
+//   ranking    a chain whose best_lpj is not finite (NaN, +inf, -inf) is left out of the walk and of every count.  The others
+//              rank by best_lpj descending, ties by ascending chain.
+//   walk       in rank order a state is dropped when it is all-zero, when it equals in all HW words the state of a chain
+//              ranked before it, or when K^n of datapoint n holds it (exact on the words, all S slots).  The others are NEW;
+//              the first Cmax of them are written to cand[(n Cmax + k) HW], k in rank order, with their digests where digests
+//              are in use, and cand_counts[n] = their number.  (The host clears cand_counts first: 0 outside the list.)
+//   counts     n_distinct = the states that are not all-zero and equal no state ranked before them; n_new = those of them K^n
+//              does not hold; n_proposed = min(n_new, Cmax); map_held = whether K^n holds map_state, the best state of the
+//              fold (chain 0 when its best_lpj is NaN, else the first chain with the greatest value that is not NaN).
+// ais_post_tally_kernel, after the selection: n_admitted = the proposed states K^n now holds, map_held again.
+//
+// Mapping: one wavefront per listed datapoint.  A chain's rank and its duplicate test run with the lanes over the other
+// chains (ballots), "K^n holds it" with the lanes over the S slots; the walk over the chains is wave-uniform.  The rank of
+// a new chain goes to key (C ints per datapoint, INT_MAX otherwise), from which its place among the new ones is one more
+// ballot count.  Every store is a plain vector store.
+// ---------------------------------------------------------------------------------------
+struct AisPostAdmitArgs {
+  const double *best_lpj;  // (n, C)
+  const u64 *best;         // (n, C, HW)
+  const i64 *index;        // (n) or null
+  const u64 *states;       // K^n (N, S, HW)
+  u64 *cand;               // (N, Cmax, HW)
+  u64 *cand_dig;           // (N, Cmax) or null
+  int *cand_counts;        // (N)
+  int *key;                // (n, C) scratch
+  int *n_distinct, *n_new, *n_proposed, *n_admitted, *map_held;  // (n) each; the emission leaves n_admitted alone
+  const double *F_full;    // (N) F of every datapoint, or null
+  double *F_out;           // (n) that of the listed ones
+  i64 n;
+  int C, S, HW, Cmax;
+};
+
+__device__ __forceinline__ bool ais_post_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
+
+// (wave-uniform) does K^n of one datapoint hold the state at `w`?  Lanes over the slots, exact on the words.
+__device__ __forceinline__ bool ais_post_kn_holds(const u64 *__restrict__ kn, int S, int HW, const u64 *__restrict__ w, int lane) {
+  bool any = false;
+  for (int s0 = 0; s0 < S; s0 += 64) {
+    const int s = s0 + lane;
+    bool eq = s < S;
+    const u64 *sp = kn + (size_t)(eq ? s : 0) * HW;
+    for (int j = 0; j < HW; j++) eq = eq && sp[j] == w[j];
+    any = any || __ballot(eq) != 0ull;
+  }
+  return any;
+}
+
+// (wave-uniform) the chain whose best state is map_state: the fold's rule
+__device__ __forceinline__ int ais_post_top_chain(const double *__restrict__ bl, int C, int lane) {
+  if (bl[0] != bl[0]) return 0;
+  double m = -INFINITY;
+  for (int c0 = 0; c0 < C; c0 += 64) {
+    const int cp = c0 + lane;
+    const double v = cp < C ? bl[cp] : -INFINITY;
+    if (v == v) m = fmax(m, v);
+  }
+  m = wave_max(m);
+  unsigned first = (unsigned)C;
+  for (int c0 = 0; c0 < C; c0 += 64) {
+    const int cp = c0 + lane;
+    if (cp < C && bl[cp] == m && (unsigned)cp < first) first = (unsigned)cp;
+  }
+  first = wave_min_u32(first);
+  return first < (unsigned)C ? (int)first : 0;
+}
+
+#define AIS_POST_ADMIT_WAVES 4
+__global__ __launch_bounds__(64 * AIS_POST_ADMIT_WAVES) void ais_post_admit_kernel(AisPostAdmitArgs a) {
+  const int lane = lane_id(), wave = wave_id_uniform();
+  const i64 i = (i64)blockIdx.x * AIS_POST_ADMIT_WAVES + wave;
+  if (i >= a.n) return;  // (wave-uniform)
+  const int C = a.C, S = a.S, HW = a.HW, Cmax = a.Cmax;
+  const i64 n = a.index ? a.index[i] : i;
+  const double *bl = a.best_lpj + (size_t)i * C;
+  const u64 *bs = a.best + (size_t)i * C * HW;
+  const u64 *kn = a.states + (size_t)n * S * HW;
+  int *key = a.key + (size_t)i * C;
+  int n_distinct = 0, n_new = 0;
+  for (int c = 0; c < C; c++) {  // (wave-uniform walk; the lanes are over the other chains)
+    const double lc = bl[c];
+    const u64 *wc = bs + (size_t)c * HW;
+    int rank = 0x7fffffff;
+    if (ais_post_finite(lc)) {
+      u64 any = 0ull;
+      for (int j = 0; j < HW; j++) any |= wc[j];
+      int before = 0;
+      bool dup = false;
+      for (int c0 = 0; c0 < C; c0 += 64) {
+        const int cp = c0 + lane;
+        const double lp = cp < C ? bl[cp] : NAN;
+        const bool ahead = ais_post_finite(lp) && (lp > lc || (lp == lc && cp < c));  // ranked before chain c
+        bool eq = ahead;
+        const u64 *wp = bs + (size_t)(ahead ? cp : 0) * HW;
+        for (int j = 0; j < HW; j++) eq = eq && wp[j] == wc[j];
+        before += __popcll(__ballot(ahead));
+        dup = dup || __ballot(eq) != 0ull;
+      }
+      if (any != 0ull && !dup) {
+        n_distinct++;
+        if (!ais_post_kn_holds(kn, S, HW, wc, lane)) n_new++, rank = before;
+      }
+    }
+    if (lane == 0) key[c] = rank;
+  }
+  seed_wave_sync();  // key, written by lane 0, is read by every lane
+  for (int c = 0; c < C; c++) {
+    const int rank = key[c];
+    if (rank == 0x7fffffff) continue;  // (wave-uniform)
+    int place = 0;  // the new chains ranked before this one
+    for (int c0 = 0; c0 < C; c0 += 64) {
+      const int cp = c0 + lane;
+      place += __popcll(__ballot(cp < C && key[cp] < rank));
+    }
+    if (place >= Cmax) continue;
+    const u64 *wc = bs + (size_t)c * HW;
+    u64 *dst = a.cand + ((size_t)n * Cmax + place) * HW;
+    for (int j = lane; j < HW; j += 64) dst[j] = wc[j];
+    if (a.cand_dig && lane == 0) a.cand_dig[(size_t)n * Cmax + place] = make_digest(wc, HW);
+  }
+  const bool held = ais_post_kn_holds(kn, S, HW, bs + (size_t)ais_post_top_chain(bl, C, lane) * HW, lane);
+  if (lane == 0) {
+    const int np = n_new < Cmax ? n_new : Cmax;
+    a.cand_counts[n] = np;
+    a.n_distinct[i] = n_distinct, a.n_new[i] = n_new, a.n_proposed[i] = np, a.map_held[i] = held ? 1 : 0;
+    if (a.F_full) a.F_out[i] = a.F_full[n];
+  }
+}
+
+// after the selection: the proposed states K^n now holds, and map_state again (the args of the emission, map_held the
+// array for `after`)
+__global__ __launch_bounds__(64 * AIS_POST_ADMIT_WAVES) void ais_post_tally_kernel(AisPostAdmitArgs a) {
+  const int lane = lane_id(), wave = wave_id_uniform();
+  const i64 i = (i64)blockIdx.x * AIS_POST_ADMIT_WAVES + wave;
+  if (i >= a.n) return;  // (wave-uniform)
+  const int C = a.C, S = a.S, HW = a.HW, Cmax = a.Cmax;
+  const i64 n = a.index ? a.index[i] : i;
+  const u64 *kn = a.states + (size_t)n * S * HW;
+  const int np = a.n_proposed[i];
+  int adm = 0;
+  for (int k = 0; k < np; k++)
+    if (ais_post_kn_holds(kn, S, HW, a.cand + ((size_t)n * Cmax + k) * HW, lane)) adm++;
+  const double *bl = a.best_lpj + (size_t)i * C;
+  const bool held = ais_post_kn_holds(kn, S, HW, a.best + ((size_t)i * C + ais_post_top_chain(bl, C, lane)) * HW, lane);
+  if (lane == 0) {
+    a.n_admitted[i] = adm, a.map_held[i] = held ? 1 : 0;
+    if (a.F_full) a.F_out[i] = a.F_full[n];
   }
 }

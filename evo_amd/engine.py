@@ -529,7 +529,7 @@ class Engine:
         return res
 
     def ais_posterior(self, betas, n_chains=16, n_keep=4, seed=0, first_index=0, mean=False, keep_chains=False, block=0,
-                      incomplete=False):
+                      incomplete=False, index=None, admit=False, Mprime=1):
         """Posterior expectations that do not start from K^n, under the Theta and data on the device (evoamd_ais_posterior;
         csrc/kernels_ais_post.hpp has the law, evo_amd.models.ais_posterior_counter is the NumPy mirror): the forward
         chains of ais_loglik, continued by ``n_keep`` - 1 further scans at beta = 1, each chain weighted by its w.
@@ -545,11 +545,30 @@ class Engine:
         background unit, bsc_direct, masks resident, H > 1024, n_chains < 1, n_keep < 1, betas that do not start at 0, end
         at 1 or that descend, and a block above 256 MiB.  ``incomplete=True`` (evoamd_ais_posterior_ex) is a permission:
         with masks resident the chains run on the datapoint's own G(n) over its reliable entries, and "mean" covers every
-        entry, the missing ones included; without masks it changes nothing."""
+        entry, the missing ones included; without masks it changes nothing.
+
+        ``index`` (evoamd_ais_posterior_sel): a 1-d integer array of datapoints of this context, strictly ascending within
+        [0, N) -- the chains run for these alone and every per-datapoint array has len(index) rows in list order, row i bit
+        for bit row index[i] of the call without ``index`` at the same seed (``first_index`` keeps its meaning: the stream
+        of row i is that of data set index first_index + index[i]).  ValueError naming the first offender otherwise.  An
+        empty list returns empty arrays without a library call.
+        ``admit=True``: after the chains, per listed datapoint the chains' best states -- ranked by chain_map_lpj, the
+        all-zero state, repeats and states K^n holds dropped, at most Cmax (csrc/kernels_ais_post.hpp, ADMISSION;
+        evo_amd.models.ais_admit_candidates_host is the mirror) -- become the candidate batch (count 0 elsewhere), and the
+        model's candidate lpj and the selection with ``Mprime`` run as in an E-step.  Adds "F_before", "F_after",
+        "n_distinct", "n_new", "n_proposed", "n_admitted" (int32), "map_held_before", "map_held_after" (bool), one row per
+        listed datapoint, and the scalars "S_nunique" and "S_sub" (sums over the datapoints, as vary_kn).  Needs K^n on
+        the device and Mprime in [1, S].  Out of scope: ``index`` for ais_loglik, ES3C, the float32 mode, the background
+        unit, H > 1024, resident handles for p / mean, choosing the list on the device."""
         betas = np.ascontiguousarray(betas, dtype=np.float64)
         if betas.ndim != 1 or betas.size < 2:
             raise ValueError("betas must be a 1-d array of T + 1 >= 2 values")
         N, H, D, C, T = self.N, self.H, self.D, int(n_chains), betas.size - 1
+        idx = None
+        if index is not None:
+            from .models.ais import check_index
+            idx = check_index(index, N)
+            N = idx.size  # the rows of every output
         HW, nb = (H + 63) // 64, (H + 7) // 8
         u64p = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))  # noqa: E731
         res = {"p": np.empty((N, H)), "p_se": np.empty((N, H))}
@@ -572,14 +591,63 @@ class Engine:
             chain_words = np.empty((N * C, HW), dtype=np.uint64)
             out.log_w, out.chain_map_lpj, out.rb = dptr(res["log_w"]), dptr(res["chain_map_lpj"]), dptr(res["rb"])
             out.chain_flips, out.chain_map_state = i32ptr(res["chain_flips"]), u64p(chain_words)
-        check(self.lib.evoamd_ais_posterior_ex(self._h, C, T, int(n_keep), dptr(betas), int(seed) & (2 ** 64 - 1),
-                                               int(first_index) & (2 ** 64 - 1), int(block),
-                                               _lib.AIS_INCOMPLETE if incomplete else 0, ctypes.byref(out)))
+        flags = _lib.AIS_INCOMPLETE if incomplete else 0
+        if idx is None and not admit:
+            check(self.lib.evoamd_ais_posterior_ex(self._h, C, T, int(n_keep), dptr(betas), int(seed) & (2 ** 64 - 1),
+                                                   int(first_index) & (2 ** 64 - 1), int(block), flags, ctypes.byref(out)))
+        else:
+            sel = _lib.AisPostSelOut()
+            sel.post = out
+            sums = np.zeros(2)
+            if admit:
+                res["F_before"], res["F_after"] = np.empty(N), np.empty(N)
+                sel.F_before, sel.F_after, sel.admit_sums = dptr(res["F_before"]), dptr(res["F_after"]), dptr(sums)
+                counts = ("n_distinct", "n_new", "n_proposed", "n_admitted", "map_held_before", "map_held_after")
+                for name in counts:
+                    res[name] = np.zeros(N, dtype=np.int32)
+                    setattr(sel, name, i32ptr(res[name]))
+            if idx is None or idx.size:  # (an empty list: empty arrays, no library call)
+                check(self.lib.evoamd_ais_posterior_sel(
+                    self._h, C, T, int(n_keep), dptr(betas), int(seed) & (2 ** 64 - 1), int(first_index) & (2 ** 64 - 1),
+                    int(block), flags | (_lib.AIS_ADMIT if admit else 0),
+                    None if idx is None else idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), 0 if idx is None else idx.size,
+                    int(Mprime), ctypes.byref(sel)))
+            if admit:
+                for name in ("map_held_before", "map_held_after"):
+                    res[name] = res[name].astype(np.bool_)
+                res["S_nunique"], res["S_sub"] = float(sums[0]), float(sums[1])
         # the MSB-first words as bytes are the np.packbits layout
         as_bytes = lambda w: np.ascontiguousarray(w.astype(">u8").view(np.uint8).reshape(w.shape[0], HW * 8)[:, :nb])  # noqa: E731
         res["map_state"] = as_bytes(map_words)
         if chain_words is not None:
             res["chain_map_state"] = as_bytes(chain_words).reshape(N, C, nb)
+        return res
+
+    def ais_post_admit_probe(self, chain_map_lpj, chain_map_state, index=None):
+        """TEST-ONLY (evoamd_ais_post_admit_probe): the emission kernel of ais_posterior(admit=True) alone, on the caller's
+        ``chain_map_lpj`` (n, C) and ``chain_map_state`` (bool (n, C, H)) for the rows ``index`` (None: the N datapoints),
+        against the resident K^n.  The candidate batch is left installed and evaluated (download_candidates() reads it).
+        Returns a dict: "n_distinct", "n_new", "n_proposed" (int32 (n,)), "map_held" (bool (n,)) and "digests" (uint64 (N,
+        Cmax), rows below a datapoint's count; None when the context keeps no digests)."""
+        from .models.ais import check_index
+        from .models.generate import pack_words
+        lpj = np.ascontiguousarray(chain_map_lpj, dtype=np.float64)
+        st = np.asarray(chain_map_state, dtype=np.bool_)
+        idx = None if index is None else check_index(index, self.N)
+        n = self.N if idx is None else idx.size
+        C = lpj.shape[1]
+        assert lpj.shape == (n, C) and st.shape == (n, C, self.H), (lpj.shape, st.shape)
+        words = np.ascontiguousarray(pack_words(st.reshape(n * C, self.H)))
+        res = {name: np.zeros(n, dtype=np.int32) for name in ("n_distinct", "n_new", "n_proposed", "map_held")}
+        dig = np.zeros((self.N, self.Cmax), dtype=np.uint64)
+        used = ctypes.c_int(0)
+        check(self.lib.evoamd_ais_post_admit_probe(
+            self._h, dptr(lpj), words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), C,
+            None if idx is None else idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), 0 if idx is None else idx.size,
+            i32ptr(res["n_distinct"]), i32ptr(res["n_new"]), i32ptr(res["n_proposed"]), i32ptr(res["map_held"]),
+            dig.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(used)))
+        res["map_held"] = res["map_held"].astype(np.bool_)
+        res["digests"] = dig if used.value else None
         return res
 
     SCORES = ("F", "entropy", "best", "k_best", "k_mean")

@@ -9,3 +9,4 @@ from .posterior_sample import sample_posterior_counter  # noqa: F401
 from .loglik_estimate import estimate_log_likelihood_counter, proposal_of  # noqa: F401
 from .remap import remap_theta  # noqa: F401
 from .ais import ais_conditional, ais_log_likelihood_counter, ais_posterior_counter, ais_scalars, sigmoid_schedule  # noqa: F401
+from .ais import ais_admit_candidates_host, state_digest  # noqa: F401

@@ -1432,7 +1432,7 @@ class Model:
         return L
 
     def ais_posterior(self, model_params, my_suff_stat, my_data, n_chains=16, n_temps=128, n_keep=4, betas=None, seed=None,
-                      first_index=0, mean=False, keep_chains=False, incomplete=False):
+                      first_index=0, mean=False, keep_chains=False, incomplete=False, index=None, admit=False):
         """Posterior expectations beyond K^n, for EBSC with H <= 1024 (incomplete data with ``incomplete=True``, below)
         (Engine.ais_posterior;
         csrc/kernels_ais_post.hpp has the law, evo_amd.models.ais_posterior_counter is the NumPy mirror).  encode(...).p,
@@ -1451,14 +1451,33 @@ class Model:
         (N, C).  Chain c does not depend on ``n_chains``, shards by ``first_index`` concatenate, two calls give the same
         bits; ``seed`` None: drawn from np.random and left in ``self.last_ais_seed`` (rank and world size enter it as in
         ais_log_likelihood).  Nothing of the EM state is written -- not K^n, lpj, the candidate batch, the statistics rows
-        or y_hat -- and there is no collective.  Out of scope: reverse chains, admit, ES3C, resident handles for p / mean,
+        or y_hat -- and there is no collective (``admit``: RESCUE below).  Out of scope: reverse chains, ES3C, resident handles for p / mean,
         second moments, use of the marginals in the M-step.  NotImplementedError for ES3C; ValueError for the float32
         mode, the background unit, incomplete data without ``incomplete=True``, H > 1024, n_chains < 1, n_keep < 1 and
         betas that do not start at 0, end at 1 or that descend.  ``incomplete=True`` admits my_data["x_infr"] with False
         entries as ais_log_likelihood does (the chains on G(n) over the reliable entries; y under False, NaN included,
         never enters); "mean" = p W^T then covers EVERY entry, the missing ones included: the reconstruction of the
-        missing entries that does not go through K^n.  A datapoint without a reliable entry has the prior's marginals."""
-        from .ais import AIS_MAX_H, check_betas, sigmoid_schedule
+        missing entries that does not go through K^n.  A datapoint without a reliable entry has the prior's marginals.
+
+        RESCUE.  ``index``: a 1-d integer array of this rank's datapoints, strictly ascending within [0, N_loc) (ValueError
+        naming the first offender otherwise) -- the chains run for these alone, at a cost linear in len(index), and every
+        per-datapoint array has len(index) rows in list order; row i is bit for bit row index[i] of the call without
+        ``index`` at the same seed (``first_index`` keeps its meaning and is added to index[i]).  An empty list is legal:
+        empty arrays, no library call.  ``admit=True`` hands what the chains found to K^n: per listed datapoint the chains'
+        best states, ranked by their lpj (ties to the lower chain), without the all-zero state, repeats and states K^n
+        holds, at most Cmax of them, become the candidate batch (nothing for the other datapoints); the model's own
+        candidate lpj kernels and the usual selection with my_suff_stat["Mprime"] follow (masked with ``incomplete``), as
+        for ais_log_likelihood(admit=True), which takes the FINAL states of the FIRST chains unranked.  The result gains
+        "F_before", "F_after" (the bound per listed datapoint without ljc), "n_distinct" (distinct non-zero best states),
+        "n_new" (those K^n did not hold), "n_proposed" = min(n_new, Cmax), "n_admitted" (the proposed states K^n holds
+        afterwards), "map_held_before", "map_held_after" (bool: K^n holds map_state) and "S_sub" (the substitutions,
+        all-reduced and normalised like E_step's: the one collective, entered with an empty list too); with sync_host K^n
+        and lpj are copied back.  Without ``admit`` the call still writes nothing of the EM state and has no collective.
+        The call does not choose the list (Model.posterior_scores gives F per datapoint to choose by), does not repeat
+        itself, and a state it admits may be displaced by a later E-step like any other.  Out of scope: ``index`` for
+        ais_log_likelihood, ES3C, the float32 mode, the background unit, H > 1024, resident handles for p / mean, choosing
+        the list on the device."""
+        from .ais import AIS_MAX_H, check_betas, check_index, sigmoid_schedule
         if self.model_name != "bsc":
             raise NotImplementedError("ais_posterior is for EBSC: ES3C is out of scope (a collapsed Gibbs step would need a "
                                       "bordered k x k system per flip)")
@@ -1482,13 +1501,23 @@ class Model:
         yr = my_data.get("y_reconstructed")
         if isinstance(yr, ResidentReconstruction) and yr.resident and not yr.materialised:
             yr.rows()  # setting the parameters below drops the device copy of an unread reconstruction: fetch it first
-        eng = self._prepare(my_suff_stat, my_data, upload_states=False)  # (the chains read no K^n)
+        if index is not None:
+            index = check_index(index, my_data["y"].shape[0])
+        eng = self._prepare(my_suff_stat, my_data, upload_states=bool(admit))  # (the chains read no K^n)
         theta = dict(model_params)  # (the precompute stores its derived keys and zeroes the reset counters: on copies)
         self.E_step_precompute(theta, dict(my_suff_stat), my_data)
         if model_params is not self._dev_theta:
             self._dev_theta = None  # the device now holds THIS Theta, not the one a device_mstep step left there
-        return eng.ais_posterior(betas, C, K, self.last_ais_seed, first_index, mean=bool(mean), keep_chains=bool(keep_chains),
-                                 incomplete=bool(incomplete))
+        info = eng.ais_posterior(betas, C, K, self.last_ais_seed, first_index, mean=bool(mean), keep_chains=bool(keep_chains),
+                                 incomplete=bool(incomplete), index=index, admit=bool(admit),
+                                 Mprime=my_suff_stat["Mprime"] if admit else 1)
+        if admit:
+            info.pop("S_nunique")
+            red = _reduce_array(self.comm, np.array([info["S_sub"], float(my_data["y"].shape[0])]))  # (the one all-reduce)
+            info["S_sub"] = red[0] / red[1]
+            if self.sync_host:
+                self.sync_to_host(my_suff_stat)
+        return info
 
     def reconstruct(self, my_data, my_suff_stat, model_params):
         """(Re-)estimate the entries with my_data["x"] False from the posterior predictive distribution under

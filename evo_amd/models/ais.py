@@ -253,8 +253,25 @@ def ais_log_likelihood_counter(theta, Y, n_chains=16, n_temps=128, betas=None, s
     return out
 
 
+def check_index(index, N):
+    """The list of Model.ais_posterior(index=...): a 1-d integer array, strictly ascending within [0, N) -> int64, C-contiguous.
+    ValueError naming the first offender."""
+    idx = np.asarray(index)
+    if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
+        raise ValueError("ais_posterior: index must be a 1-d integer array")
+    idx = np.ascontiguousarray(idx, dtype=np.int64)
+    for i, v in enumerate(idx):
+        if v < 0 or v >= N:
+            raise ValueError("ais_posterior: index[%d] = %d is outside [0, N = %d)" % (i, v, N))
+        if i and v == idx[i - 1]:
+            raise ValueError("ais_posterior: index[%d] = %d is repeated" % (i, v))
+        if i and v < idx[i - 1]:
+            raise ValueError("ais_posterior: index[%d] = %d descends (after %d): the list is ascending" % (i, v, idx[i - 1]))
+    return idx
+
+
 def ais_posterior_counter(theta, Y, n_chains=16, n_temps=128, n_keep=4, betas=None, seed=0, first_index=0, mean=False, B=None,
-                          G=None, x_infr=None):
+                          G=None, x_infr=None, index=None):
     """The NumPy mirror of Model.ais_posterior (csrc/kernels_ais_post.hpp states the law): the forward chains of
     ais_log_likelihood_counter, continued.  The scan at beta_T = 1 (uniform block T + 1) is the first KEPT scan; kept scans
     2 .. ``n_keep`` follow at beta = 1 with the uniform blocks T + 2, T + 3, ...; none of them enters w.  In every kept scan
@@ -274,7 +291,9 @@ def ais_posterior_counter(theta, Y, n_chains=16, n_temps=128, n_keep=4, betas=No
     (N, H), "first_bool" and "first_flips" (the state and the flips after the first kept scan: ``final_bool`` and
     ``chain_flips`` of ais_log_likelihood_counter), "margin" (N, C; every decision of the chain, the kept scans included)
     and, with ``mean``, "mean" (N, D) = p W^T.  ``x_infr`` (bool (N, D)): incomplete data, as ais_log_likelihood_counter takes
-    it; "mean" then covers every entry, the missing ones included."""
+    it; "mean" then covers every entry, the missing ones included.  ``index``: the listed datapoints of
+    Model.ais_posterior(index=...) -- only these rows of ``Y`` are walked, each with the stream of data set index first_index
+    + index[i], and every array has len(index) rows in list order."""
     C, K = int(n_chains), int(n_keep)
     if C < 1:
         raise ValueError("ais_posterior: n_chains must be positive")
@@ -284,7 +303,7 @@ def ais_posterior_counter(theta, Y, n_chains=16, n_temps=128, n_keep=4, betas=No
     T = betas.size - 1
     W = np.asarray(theta["W"], dtype=np.float64)
     Y, mask = _mask_data(np.asarray(Y, dtype=np.float64), x_infr)
-    N, H = Y.shape[0], W.shape[1]
+    H = W.shape[1]
     if H > AIS_MAX_H:
         raise ValueError("ais_posterior: H = %d, at most %d latents are supported" % (H, AIS_MAX_H))
     pre1, pilb, pi = ais_scalars(theta)
@@ -295,6 +314,11 @@ def ais_posterior_counter(theta, Y, n_chains=16, n_temps=128, n_keep=4, betas=No
         G = np.dot(W.T, W) if G is None else np.asarray(G, dtype=np.float64)
         Gd = np.diag(G).copy()
     yy = (Y * Y).sum(axis=1)
+    src = np.arange(Y.shape[0], dtype=np.int64) if index is None else check_index(index, Y.shape[0])
+    Y, B, yy = Y[src], B[src], yy[src]  # (a row of B = Y W and of yy depends on its own datapoint alone)
+    if mask is not None:
+        mask = mask[src]
+    N = src.size
     seed, first_index = int(seed) & _M64, int(first_index) & _M64
     hs = np.arange(H, dtype=np.uint64)
     out = {"log_w": np.empty((N, C)), "rb": np.empty((N, C, H)), "chain_map_lpj": np.empty((N, C)),
@@ -327,7 +351,7 @@ def ais_posterior_counter(theta, Y, n_chains=16, n_temps=128, n_keep=4, betas=No
 
     with np.errstate(over="ignore"):  # the hashes wrap mod 2^64
         for n in range(N):
-            x0 = _first_hash(seed, np.array([(first_index + n) & _M64], dtype=np.uint64))
+            x0 = _first_hash(seed, np.array([(first_index + int(src[n])) & _M64], dtype=np.uint64))
             block = lambda b: _u01_chains(x0, C, np.uint64(b * H) + hs)  # noqa: E731
             flips = np.zeros(C, dtype=np.int64)
             u = block(0)
@@ -391,3 +415,50 @@ def ais_posterior_counter(theta, Y, n_chains=16, n_temps=128, n_keep=4, betas=No
     if mean:
         out["mean"] = np.dot(out["p"], W.T)
     return out
+
+
+def state_digest(state):
+    """The digest the device keeps beside a packed state (csrc/common.hpp): bits 0 .. 7 the number of active latents
+    (saturated at 255), bits 8 + 14 j .. 8 + 14 j + 13 the j-th active latent in ascending order, j < 4."""
+    on = np.flatnonzero(np.asarray(state, dtype=bool))
+    d = min(len(on), 255)
+    for j, h in enumerate(on[:4]):
+        d |= int(h) << (8 + 14 * j)
+    return d
+
+
+def ais_admit_candidates_host(chain_map_lpj, chain_map_state, kn_states, Cmax):
+    """The NumPy mirror of the emission of Model.ais_posterior(admit=True) for ONE datapoint (csrc/kernels_ais_post.hpp,
+    ADMISSION, states the law).  ``chain_map_lpj`` (C,), ``chain_map_state`` bool (C, H): the chains' best states;
+    ``kn_states`` bool (S, H): K^n of the datapoint.  A chain whose lpj is not finite is left out of the walk and of every
+    count.  The others rank by lpj descending, ties by ascending chain; in that order a state is dropped when it is
+    all-zero, when it equals the state of a chain ranked before it, or when K^n holds it; the first ``Cmax`` of the rest
+    are the candidates.  Returns (candidates bool (k, H) in order, counts) with counts = {"n_distinct": the states that are
+    not all-zero and repeat no state ranked before them, "n_new": those of them K^n does not hold, "n_proposed": k =
+    min(n_new, Cmax), "map_held": whether K^n holds map_state, the best state of the fold (chain 0 when its lpj is NaN,
+    else the first chain with the greatest lpj that is not NaN), "chains": the chain of every candidate}."""
+    lpj = np.asarray(chain_map_lpj, dtype=np.float64)
+    st = np.asarray(chain_map_state, dtype=bool)
+    kn = np.asarray(kn_states, dtype=bool).reshape(-1, st.shape[1])
+    key = lambda row: np.packbits(row).tobytes()  # noqa: E731
+    held = {key(row) for row in kn}
+    order = sorted((c for c in range(len(lpj)) if np.isfinite(lpj[c])), key=lambda c: (-lpj[c], c))
+    seen, new = set(), []
+    n_distinct = 0
+    for c in order:
+        k = key(st[c])
+        if not st[c].any() or k in seen:
+            continue
+        seen.add(k)
+        n_distinct += 1
+        if k not in held:
+            new.append(c)
+    top = 0
+    if not np.isnan(lpj[0]):
+        for c in range(1, len(lpj)):
+            if lpj[c] > lpj[top]:
+                top = c
+    taken = new[:int(Cmax)]
+    counts = {"n_distinct": n_distinct, "n_new": len(new), "n_proposed": len(taken), "map_held": key(st[top]) in held,
+              "chains": taken}
+    return st[taken].reshape(len(taken), st.shape[1]), counts

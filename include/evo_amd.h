@@ -599,6 +599,49 @@ int evoamd_ais_posterior(evoamd_ctx *ctx, int n_chains, int n_temps, int n_keep,
 int evoamd_ais_posterior_ex(evoamd_ctx *ctx, int n_chains, int n_temps, int n_keep, const double *betas, uint64_t seed,
                             uint64_t first_index, int64_t block_datapoints, unsigned flags, const evoamd_ais_post_out *out);
 
+/* "Rescue": evoamd_ais_posterior_ex on LISTED datapoints, and the best distinct states its chains visited handed to K^n.
+ * index (n_index int64, strictly ascending, each in [0, N)): the chains run for these datapoints only, and every output
+ * of evoamd_ais_post_out has n_index rows in list order -- row i is bit for bit row index[i] of the call without a list
+ * at the same seed (the stream of row i is that of data set index first_index + index[i]; blocks run over list
+ * positions).  index NULL (n_index 0): all N datapoints.  n_index = 0 with a list: nothing runs, nothing is written.
+ * flags: EVOAMD_AIS_INCOMPLETE as for _ex; EVOAMD_AIS_ADMIT: after the chains and the fold (csrc/kernels_ais_post.hpp,
+ * ADMISSION, has the law; evo_amd.models.ais_admit_candidates_host is the NumPy mirror of the emission) the resident
+ * rows are evaluated, then per listed datapoint the chains' best states -- ranked by their lpj descending, ties to the
+ * lower chain, chains with a lpj that is not finite left out; the all-zero state, repeats of a state ranked before and
+ * states K^n holds dropped; at most Cmax -- become its rows of the candidate batch (count 0 for every other datapoint),
+ * the candidate lpj kernels and the selection with Mprime run as in every E-step (masked with masks resident), and
+ * the outputs below are written, n rows each (n = n_index, or N): F_before / F_after (the bound of K^n without ljc),
+ * n_distinct (distinct non-zero best states), n_new (those K^n did not hold), n_proposed = min(n_new, Cmax),
+ * n_admitted (the proposed states K^n holds after the selection), map_held_before / map_held_after (0 / 1: K^n holds
+ * map_state), admit_sums (2: the selection's sums as evoamd_vary_kn).  Without EVOAMD_AIS_ADMIT nothing of the EM state
+ * is written and the added outputs are not touched.
+ * EVOAMD_E_INVALID before anything is written, each with its own text: everything evoamd_ais_posterior_ex refuses; any
+ * other flag; n_index < 0; an index outside [0, N), repeated or descending (the first offender is named); with
+ * EVOAMD_AIS_ADMIT K^n not on the device and Mprime outside [1, S]. */
+typedef struct evoamd_ais_post_sel_out {
+  evoamd_ais_post_out post;  /* rows: the listed datapoints */
+  double *F_before;          /* (n), EVOAMD_AIS_ADMIT, like the rest */
+  double *F_after;           /* (n) */
+  int32_t *n_distinct;       /* (n) */
+  int32_t *n_new;            /* (n) */
+  int32_t *n_proposed;       /* (n) */
+  int32_t *n_admitted;       /* (n) */
+  int32_t *map_held_before;  /* (n) */
+  int32_t *map_held_after;   /* (n) */
+  double *admit_sums;        /* (2) */
+} evoamd_ais_post_sel_out;
+int evoamd_ais_posterior_sel(evoamd_ctx *ctx, int n_chains, int n_temps, int n_keep, const double *betas, uint64_t seed,
+                             uint64_t first_index, int64_t block_datapoints, unsigned flags, const int64_t *index,
+                             int64_t n_index, int Mprime, const evoamd_ais_post_sel_out *out);
+/* TEST-ONLY: the emission kernel of EVOAMD_AIS_ADMIT alone, on the caller's best_lpj (n, n_chains) and best (n, n_chains,
+ * ceil(H / 64) words in the layout of K^n) for the rows index (n = n_index; NULL: the N datapoints), against the
+ * resident K^n.  It leaves the candidate batch installed and evaluated (evoamd_download_candidates reads it) and
+ * returns n_distinct, n_new, n_proposed, map_held (n each), the candidates' digests (dig_out (N, Cmax), rows below a
+ * datapoint's count) where digests are in use, and whether they are (*dig_used). */
+int evoamd_ais_post_admit_probe(evoamd_ctx *ctx, const double *best_lpj, const uint64_t *best, int n_chains,
+                                const int64_t *index, int64_t n_index, int32_t *n_distinct, int32_t *n_new,
+                                int32_t *n_proposed, int32_t *map_held, uint64_t *dig_out, int *dig_used);
+
 /* Per-datapoint scores of the lpj rows and K^n resident on the device (after a seed, an upload or any pass), each output
  * (N) or NULL.  With m = max_s lpj_ns, w_s = exp(lpj_ns - m), z = sum_s w_s over the S_perm + S columns:
  * F_out = m + log z (the bound per datapoint without ljc, the counterpart of ll_out of evoamd_loglik_exact);
@@ -1142,7 +1185,7 @@ enum {
   EVOAMD_K_NBOUND = 33,        /* evoamd_neighbour_bound: the neighbourhood kernel (ES3C: with the transpose of GP) and the bound of the rows */
   EVOAMD_K_PRED_SCORE = 34,    /* evoamd_predictive_score: the transpose of W, the visit list, the score kernel, its partials and their reductions */
   EVOAMD_K_AIS = 35,           /* evoamd_ais_loglik: the chain kernel, the fold over the chains and (admit) the emission */
-  EVOAMD_K_AIS_POST = 36,      /* evoamd_ais_posterior: the chain kernel and the fold of every block of datapoints (the product for mean counts as gemm) */
+  EVOAMD_K_AIS_POST = 36,      /* evoamd_ais_posterior: the chain kernel and the fold of every block of datapoints (the product for mean counts as gemm); _sel: the emission and the tally too */
   EVOAMD_K_COUNT = 37
 };
 /* on = bit mask of kernel classes to time (bit k = class k; -1 = all, 0 = off).  Each timed span
