@@ -1322,7 +1322,7 @@ __global__ __launch_bounds__(256) void sssc_mstep_prepare_kernel(
       bak[DH + HH + i] = mus[i];
       bak[DH + HH + H + i] = pies[i];
     }
-    if (t < DP_COUNT) bak[DH + HH + 2 * H + t] = dpar[t];
+    for (i64 e = t; e < DP_COUNT; e += HH) bak[DH + HH + 2 * H + e] = dpar[e];  // (H H < DP_COUNT below H = 4)
   }
   const bool lm = (learn & L_MUS) != 0;
   const double mi = lm ? xsz[i] * 1.0 / (xs[i] + 2.220446049250313e-16) : mus[i];  // eps_mus

@@ -446,6 +446,13 @@ CAND_LPJ = {
     "bsc_direct": ("bsc", 9, 10, 64, 12, {"bsc_direct": 1}, 306, None),
     "es_mixed_k": ("sssc", 5, 12, 96, 12, {}, 307, (0, 1, 2, 3, 4, 5, 8, 9, 64, 65)),
     "es_mixed_k_nodigest": ("sssc", 5, 12, 96, 12, {"state_digest": 0}, 308, (0, 1, 2, 3, 4, 5, 8, 9, 64, 65)),
+    # the lower edge: H = 1 (odd: the plain EBSC kernel; ES3C: no pair of latents exists, the pair table is one dummy
+    # entry), H = 2 (the Gram kernel's smallest H; one pair), H = 3 on the word path
+    "bsc_h1": ("bsc", 9, 3, 1, 2, {}, 309, None),
+    "bsc_h2": ("bsc", 9, 3, 2, 4, {}, 310, None),
+    "es_h1": ("sssc", 9, 3, 1, 2, {}, 311, (0, 1)),
+    "es_h2": ("sssc", 9, 3, 2, 4, {}, 312, (0, 1, 2)),
+    "es_h3_nodigest": ("sssc", 9, 3, 3, 4, {"state_digest": 0}, 313, (0, 1, 2, 3)),
 }
 
 

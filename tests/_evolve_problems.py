@@ -29,6 +29,8 @@ FAST = {
     "h200_spl8": Fast(200, 300, 0, 0, 16, 2, 1, "bsc"),
     "h128_spl16_64_parents": Fast(128, 1024, 0, 0, 64, 1, 0, "bsc"),  # n_parents at its limit
     "h520_hw9": Fast(520, 20, 0, 0, 5, 3, 1, "bsc"),               # past the loop that keeps eight words in flight
+    "h1": Fast(1, 2, 0, 0, 1, 1, 1, "bsc"),                        # one latent: every flip is the same one; S = 2^H
+    "h2": Fast(2, 3, 0, 0, 2, 2, 1, "sssc"),                       # n_children = H: both positions of either parent
 }
 
 General = namedtuple("General", "H S S_perm bg mutation n_parents n_children n_gen fit sparseness p_bf Cmax zero_parent")
@@ -43,6 +45,14 @@ def _general_cases():
         g["%s_h64" % op] = General(64, 20, 0, 0, op, 4, 2, 2, 1, 2.5, 0.05, None, False)
         g["%s_h65" % op] = General(65, 65, 1, 0, op, 5, 2, 2, i % 2, 2.5, 0.05, None, False)
         g["%s_h130" % op] = General(130, 12, 0, 0, op, 4, 3, 3, 1, 3.0, 0.03, None, False)
+    # the lower edge: H = 2 (randint(1, H) of the crossover has one value; S = 2^H - 1, so at most one state is new),
+    # H = 3 and, for randflip, H = 1 with S = 2^H (every child is the other known state, or a duplicate: counts stay 0).
+    # sparseflip: (sparseness, p_bf) = (1.0, 0.25) at H = 2 and (1.5, 0.25) at H = 3 keep p0 and p1 of every parent with
+    # 0 < |s| < H inside (0, 1) (test_evolve_counter_host.py evaluates the mirror's formula)
+    for i, op in enumerate(OPERATORS):
+        g["%s_h2" % op] = General(2, 3, 0, 0, op, 2, 1, 2, 1, 1.0, 0.25, None, False)
+        g["%s_h3" % op] = General(3, 5, i % 2, 0, op, 3, 2, 2, 1, 1.5, 0.25, None, False)
+    g["randflip_h1"] = General(1, 2, 0, 0, "randflip", 1, 1, 1, 1, 0.0, 0.0, None, False)
     g["randflip_h65_bg"] = General(65, 16, 0, 1, "randflip", 4, 8, 2, 1, 0.0, 0.0, None, False)
     g["cross_sparseflip_h65_bg"] = General(65, 16, 0, 1, "cross_sparseflip", 4, 1, 2, 1, 2.5, 0.05, None, False)
     g["cross_p9_72_children"] = General(64, 12, 0, 0, "cross", 9, 1, 1, 1, 0.0, 0.0, None, False)
@@ -60,6 +70,7 @@ def _general_cases():
 
 GENERAL = _general_cases()
 CASES = dict(FAST, **GENERAL)
+TINY = tuple(sorted(k for k, v in CASES.items() if v.H <= 3))  # added later: seeds of their own, the others keep theirs
 
 
 def per_generation(c):
@@ -76,7 +87,9 @@ def cmax(name):
 
 
 def seed_of(name):
-    return 1000 + sorted(CASES).index(name)
+    if name in TINY:
+        return 2000 + TINY.index(name)
+    return 1000 + sorted(k for k in CASES if k not in TINY).index(name)
 
 
 # ---- K^n ---------------------------------------------------------------------------------------------------------------
@@ -103,7 +116,7 @@ def make_kn(rng, S, H, S_perm, bg, zero_parent=False):
     small = Hd <= 12
     if small:
         table = np.array([[(i >> (Hd - 1 - h)) & 1 for h in range(Hd)] for i in range(2 ** Hd)], dtype=bool)
-        assert S <= table.shape[0] - 1
+        assert S <= table.shape[0] - (1 if nonzero else 0)  # (S = 2^Hd: the whole table, the all-zero state included)
     kmax = min(6, max(1, Hd // 3))
     for n in range(N):
         if small:

@@ -54,13 +54,19 @@ PROBLEMS = {
     "bsc_s300": ("ebsc", "mid", 33, 32, 20, 300, 0, "rand30", 113),
     # x != x_infr on the EBSC side (select_rec_kernel, Wp = Es^T Yrec)
     "bsc_keep": ("ebsc", "mid", 37, 33, 12, 10, 0, "keep", 114),
+    # the lower edge of the latent space (the "sparse" pool holds all 2^H = 4 states, S = 3 of them per datapoint): an
+    # H x H grid of four threads, one pair of latents, 2 x 2 systems; D = 8 H: a lazy update writes its backup in
+    # sssc_mstep_prepare_kernel, whose four live threads are fewer than the 16 scalars of the block it saves
+    "es_h2": ("es3c", "sparse", 37, 16, 2, 3, 0, "rand30", 115),
+    "bsc_h2": ("ebsc", "sparse", 37, 9, 2, 3, 0, "rand30", 116),
 }
 ES_PROBLEMS = tuple(k for k, v in PROBLEMS.items() if v[0] == "es3c")
 BSC_PROBLEMS = tuple(k for k, v in PROBLEMS.items() if v[0] == "ebsc")
 # the Theta part runs on these: every H x H system of their update is under COND_CAP at the N above, so none had to
 # be raised (test_masked_problems.py asserts it).  cond(xpt_szsz), cond(xpt_ss + eps I): es_d65 8.1, 9.1; es_h64 15.9,
-# 25.6.  cond(Wq): bsc_d65 8.5; bsc_perm 5.3.
-THETA_PROBLEMS = ("es_d65", "es_h64", "bsc_d65", "bsc_perm")
+# 25.6.  cond(Wq): bsc_d65 8.5; bsc_perm 5.3.  The tiny problems: es_h2 1.6, 3.0; cond(Wq) of bsc_h2 1.1.
+THETA_PROBLEMS = ("es_d65", "es_h64", "bsc_d65", "bsc_perm", "es_h2", "bsc_h2")
+TINY = ("es_h2", "bsc_h2")
 GRID_STRIDE = 7  # es_grid: the oracle's lpj on every 7th datapoint only (the whole oracle would take a minute)
 
 # rows of the `edge` pattern

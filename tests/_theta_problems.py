@@ -51,7 +51,29 @@ PROBLEMS = {
     "bsc_s300": ("ebsc", "mid", 33, 32, 20, 300, 0, 214, ""),
     "bsc_clamp": ("ebsc", "mid", 37, 25, 12, 10, 0, 215, "clamp"),
     "bsc_bg": ("ebsc", "mid", 41, 25, 12, 10, 0, 216, "bg"),
+    # ---- the lower edge: H = 1 ... 4 (the "sparse" pool holds all 2^H states) ----
+    # H H = 1: one live thread of sssc_mstep_prepare_kernel saves W (8 trips), Psi, mus, pies and all DP_COUNT = 16 scalars
+    # of the lazy-Theta backup; 1 x 1 inverses; S = 2^H: K^n is the whole state space
+    "es_h1": ("es3c", "sparse", 37, 8, 1, 2, 0, 221, ""),
+    # a single state per datapoint: every posterior is a point mass
+    "es_h1_s1": ("es3c", "sparse", 37, 8, 1, 1, 0, 222, ""),
+    # D = 8 H exactly: the last D of BACKUP_IN_UPDATE; H H = 4 live threads, DP_SIGMA2 (index 6) beyond them
+    "es_h2": ("es3c", "sparse", 37, 16, 2, 3, 0, 223, ""),
+    # D = 8 H + 1: BACKUP_SIDE_KERNEL at the same H
+    "es_h2_d17": ("es3c", "sparse", 37, 17, 2, 3, 0, 224, ""),
+    # D = 1: W is one row; S = 2^H
+    "es_h2_d1": ("es3c", "sparse", 37, 1, 2, 4, 0, 225, ""),
+    # H H = 9 < DP_COUNT: the scalars 9 .. 15 beyond the live threads; non-symmetric Psi and sums
+    "es_h3": ("es3c", "sparse", 37, 24, 3, 5, 0, 226, "nonsym"),
+    # H H = 16 = DP_COUNT: the first size at which one scalar per live thread is enough
+    "es_h4": ("es3c", "sparse", 37, 9, 4, 7, 0, 227, ""),
+    # N = 1: every sum is one datapoint's
+    "es_n1": ("es3c", "sparse", 1, 8, 2, 4, 0, 228, ""),
+    # 1 x 1 Wq
+    "bsc_h1": ("ebsc", "sparse", 37, 5, 1, 2, 0, 231, ""),
+    "bsc_h2": ("ebsc", "sparse", 37, 5, 2, 3, 0, 232, ""),
 }
+TINY = tuple(k for k, v in PROBLEMS.items() if v[4] <= 4)
 ES_PROBLEMS = tuple(k for k, v in PROBLEMS.items() if v[0] == "es3c")
 BSC_PROBLEMS = tuple(k for k, v in PROBLEMS.items() if v[0] == "ebsc")
 CLAMP_PROBLEMS = tuple(k for k, v in PROBLEMS.items() if v[8] == "clamp")
@@ -62,7 +84,9 @@ LARGE = tuple(k for k, v in PROBLEMS.items() if v[4] >= 128)
 # the sparse problems needed a pool of 8 H states and N in the thousands before every latent carried posterior mass: with
 # the pool of 512, es_h257 had cond(xpt_szsz) = 3.9e16).  cond(xpt_szsz), cond(xpt_ss + eps I): es_h12 4.1, 7.7; es_d100
 # 5.1, 8.1; es_nonsym 3.6, 9.5; es_h33 19.2, 23.7; es_h128 24.8, 21.8; es_h130 21.3, 22.5; es_h257 17.2, 16.1; es_bg 3.8,
-# 8.9.  cond(Wq): bsc_h12 7.7; bsc_h65 5.2; bsc_h130 6.1; bsc_s300 3.6; bsc_bg 15.8.
+# 8.9.  cond(Wq): bsc_h12 7.7; bsc_h65 5.2; bsc_h130 6.1; bsc_s300 3.6; bsc_bg 15.8.  The tiny problems: es_h1, es_h1_s1
+# 1, 1 (1 x 1 systems); es_h2 3.1, 1.6; es_h2_d17 2.4, 1.8; es_h2_d1 1.6, 1.7; es_h3 2.2, 1.8; es_h4 1.7, 2.9; es_n1 2.7,
+# 2.1; cond(Wq): bsc_h1 1; bsc_h2 1.3.
 
 ES_KEYS = ("W", "pies", "mus", "Psi", "sigma2")
 BSC_KEYS = ("W", "pi", "sigma")
@@ -291,6 +315,58 @@ def solver(H, spd=1, block=0):
 def backup_route(p):
     """BackupRoute of mstep_device(theta_to_host=False) with a non-empty learn set."""
     return "in_update" if p["algo"] == "es3c" and p["D"] <= BACKUP_RATIO * p["H"] else "side_kernel"
+
+
+DP_COUNT = 16     # kernels_mstep.hpp: doubles of the scalar block, the last segment of the lazy-Theta backup
+DP_SIGMA2 = 6     # ... and sigma2's place in it (DP_PI = 4 and DP_SIGMA = 5 are EBSC's: set_params_sssc leaves them 0)
+
+
+def backup_layout(p):
+    """Offsets of the segments of theta_bak (theta_segs: W | Psi | mus | pies | scalar block; EBSC: W | scalar block)."""
+    D, H = p["D"], p["H"]
+    if p["algo"] == "ebsc":
+        return {"W": 0, "dpar": D * H, "end": D * H + DP_COUNT}
+    at = {"W": 0, "Psi": D * H, "mus": D * H + H * H, "pies": D * H + H * H + H, "dpar": D * H + H * H + 2 * H}
+    at["end"] = at["dpar"] + DP_COUNT
+    return at
+
+
+def backup_image(p):
+    """What theta_bak holds after a complete backup of the ES3C problem p's Theta, slot by slot; None where the passes
+    over K^n write (counters, Fs, ljc_prev) or where only the device's rounding is known (1 / sigma2, ljc)."""
+    th, at = p["theta"], backup_layout(p)
+    img = [None] * at["end"]
+    for k in ("W", "Psi", "mus", "pies"):
+        v = np.asarray(th[k], dtype=np.float64).ravel()
+        img[at[k]:at[k] + v.size] = [float(x) for x in v]
+    for i in (0, 1, 4, 5):  # DP_PRE1, DP_PILBAR, DP_PI, DP_SIGMA: EBSC's
+        img[at["dpar"] + i] = 0.0
+    img[at["dpar"] + DP_SIGMA2] = float(th["sigma2"])
+    return img
+
+
+def backup_prelude():
+    """es_h2_d17 with another sigma2.  evoamd_configure keeps theta_bak across a change of geometry (DevBuf::ensure only
+    grows), so a lazy update of this problem (side-kernel route: a complete backup of 58 doubles) on the same context
+    decides what the slots hold that an in-update backup of es_h1 (27 doubles) or es_h2 (56) fails to write: the
+    restore test does not depend on what fresh device memory happens to contain."""
+    p = dict(make_problem("es_h2_d17"))
+    p["theta"] = dict(p["theta"], sigma2=np.float64(2.7))
+    return p
+
+
+def second_theta(p):
+    """Theta' for a second lazy update on the same context: every scalar and vector differs from the problem's Theta."""
+    th = {k: np.array(v) for k, v in p["theta"].items()}
+    if p["algo"] == "es3c":
+        th["sigma2"] = np.float64(0.85)
+        th["mus"] = th["mus"] * 0.5 + 0.25
+        th["pies"] = 0.5 - th["pies"]  # (0.1, 0.4) again
+        th["W"] = th["W"] * 1.25
+    else:
+        th["pi"], th["sigma"] = np.float64(0.3), np.float64(1.6)
+        th["W"] = th["W"] * 1.25
+    return th
 
 
 def contraction_flops(algo, N, D, H):

@@ -266,7 +266,19 @@ def test_candidate_lpj_cases_take_the_routes_they_name():
         if model == "bsc":
             routes[name] = ep.gram2_eligible(H, Cmax, opts.get("state_digest", 1), opts.get("bsc_direct", 0))
     assert routes == {"bsc_h_odd": False, "bsc_hw3_nodigest": False, "bsc_hw3_digest": True, "bsc_c1_h10": False,
-                      "bsc_c1_h8": True, "bsc_direct": False}
+                      "bsc_c1_h8": True, "bsc_direct": False, "bsc_h1": False, "bsc_h2": True}  # (H = 1 is odd)
+    for name, H, ks in (("es_h1", 1, {0, 1}), ("es_h2", 2, {0, 1, 2}), ("es_h3_nodigest", 3, {0, 1, 2, 3})):
+        p = ep.make_cand_problem(name)
+        k = p["cand"].sum(axis=-1)
+        valid = np.arange(p["Cmax"])[None, :] < p["counts"][:, None]
+        assert p["H"] == H and set(k[valid].tolist()) == ks, name  # every state size the space has, all-on included
+        assert p["counts"].min() < p["Cmax"] == p["counts"][0], name
+        assert H * (H - 1) // 2 == {1: 0, 2: 1, 3: 3}[H]  # pairs of latents
+    assert ep.uses_digests(3, 0) is False
+    for name, H in (("bsc_h1", 1), ("bsc_h2", 2)):
+        p = ep.make_cand_problem(name)
+        k = p["cand"].sum(axis=-1)
+        assert p["H"] == H and set(k[np.arange(p["Cmax"])[None, :] < p["counts"][:, None]].tolist()) == set(range(H + 1)), name
     assert (ep.CAND_LPJ["bsc_h_odd"][3] % 2, (ep.CAND_LPJ["bsc_hw3_nodigest"][3] + 63) // 64) == (1, 3)
     for name in ("es_mixed_k", "es_mixed_k_nodigest"):
         p = ep.make_cand_problem(name)

@@ -342,6 +342,68 @@ def test_generations_match_oracle_law(mutation, S_perm, n_gen, n_par, n_child):
             assert abs(a - b) / np.sqrt(pool * (1 - pool) * (1.0 / N + 1.0 / n_or)) < Z_MAX, (sizes_mi, sizes_or)
 
 
+# ---- the lower edge of the latent space ----------------------------------------------------------------------------------------
+def test_tiny_cases_are_in_the_tables():
+    assert vp.FAST["h1"] == vp.Fast(1, 2, 0, 0, 1, 1, 1, "bsc") and vp.FAST["h2"] == vp.Fast(2, 3, 0, 0, 2, 2, 1, "sssc")
+    for i, op in enumerate(vp.OPERATORS):
+        c = vp.GENERAL["%s_h2" % op]
+        assert (c.H, c.S, c.S_perm, c.n_parents, c.n_children, c.n_gen) == (2, 3, 0, 2, 1, 2), op
+        c = vp.GENERAL["%s_h3" % op]
+        assert (c.H, c.S, c.S_perm) == (3, 5, i % 2) and c.S_perm == vp.GENERAL["%s_h5" % op].S_perm, op
+    c = vp.GENERAL["randflip_h1"]
+    assert (c.H, c.S, c.mutation) == (1, 2, "randflip")
+    assert set(vp.TINY) == {"h1", "h2", "randflip_h1"} | {"%s_h%d" % (op, H) for op in vp.OPERATORS for H in (2, 3)}
+    # the cases that were there before keep their seeds
+    assert vp.seed_of("cross_h130") == 1000 and vp.seed_of("sparseflip_zero_parent") == 1000 + len(vp.CASES) - len(vp.TINY) - 1
+    assert len({vp.seed_of(n) for n in vp.CASES}) == len(vp.CASES)
+
+
+@pytest.mark.parametrize("H", [1, 2, 3])
+def test_make_kn_builds_distinct_rows_up_to_the_whole_state_space(H):
+    """S = 2^H - 1 and S = 2^H (and, with the permanent all-zero state, S = 2^H - 1 non-zero rows): every datapoint holds
+    S distinct rows, and at S = 2^H all of them."""
+    for S, S_perm in ((2 ** H - 1, 0), (2 ** H, 0), (2 ** H - 1, 1)):
+        if S < 1:
+            continue
+        ss = vp.make_kn(np.random.RandomState(H), S, H, S_perm, 0)
+        assert ss.shape == (vp.N, S, H)
+        for n in range(vp.N):
+            assert len({r.tobytes() for r in ss[n]}) == S, (H, S, n)
+            if S_perm:
+                assert ss[n].any(axis=1).all(), (H, S, n)
+    for name in vp.TINY:  # ... and the cases' own K^n, every datapoint
+        p = vp.make_problem(name)
+        for n in range(vp.N):
+            assert len({r.tobytes() for r in p["ss"][n]}) == p["S"], (name, n)
+
+
+def test_tiny_operators_degenerate_as_named():
+    """H = 2: the crossover's cut has one value; sparseflip's p0 and p1 lie inside (0, 1) for every parent the formula does
+    not pin (a parent of H latents has alpha = 0, so p1 = 0, and no 0 to flip; a parent of none has no 1); H = 1, S = 2:
+    no child is new."""
+    for name in ("cross_h2", "cross_randflip_h2", "cross_sparseflip_h2"):
+        _, _, info = _mirror(name)
+        cuts = np.concatenate([np.ravel(g["cuts"]) for d in info["draws"] for g in d if "cuts" in g])
+        assert cuts.size and set(cuts.tolist()) == {1}, name
+    for name in ("sparseflip_h2", "cross_sparseflip_h2", "sparseflip_h3", "cross_sparseflip_h3"):
+        c = vp.CASES[name]
+        for s_abs in range(c.H + 1):
+            p0, p1 = ec.sparse_probabilities(c.H, s_abs, c.sparseness, c.p_bf)
+            if s_abs < c.H:
+                assert 0.0 < float(p0) < 1.0, (name, s_abs, p0)
+            if 0 < s_abs < c.H:
+                assert 0.0 < float(p1) < 1.0, (name, s_abs, p1)
+        assert float(ec.sparse_probabilities(c.H, c.H, c.sparseness, c.p_bf)[1]) == 0.0
+    cand, counts, _ = _mirror("randflip_h1")
+    assert not counts.any()
+    cand, counts, _ = _mirror("h1")  # the fast kernel does not de-duplicate: one child, the other state
+    p = vp.make_problem("h1")
+    assert np.all(counts == 1) and np.all(cand[:, 0, 0] != p["ss"][np.arange(vp.N), _mirror("h1")[2]["parents"][:, 0], 0])
+    for name in vp.TINY:
+        if name not in vp.FAST and vp.CASES[name].H > 1:
+            assert _mirror(name)[1].any(), name  # something new is found: the comparison on the GPU is not vacuous
+
+
 # ---- every case of the parity tables ---------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _mirror(name):

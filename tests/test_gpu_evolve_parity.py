@@ -79,6 +79,29 @@ def _same_batches(a, b, label, lpj_exact):
         np.testing.assert_allclose(a[2][v], b[2][v], rtol=1e-12, err_msg=label)
 
 
+@pytest.mark.parametrize("mutation", ["cross", "cross_randflip", "cross_sparseflip"])
+def test_crossover_is_refused_at_one_latent(engine, mutation):
+    """H = 1 has no cut point (randint(1, H) is empty): evoamd_evolve_states refuses by name, changes nothing in the
+    context (the validity words before and after are the same) and the next call on it is served: randflip_h1 still
+    gives the mirror's batch."""
+    from evo_amd.engine import EvoAmdError
+    p = dict(vp.make_problem("randflip_h1"), Cmax=2)  # (room for the 2 x 1 children of two crossed parents: no other refusal)
+    assert p["H"] == 1 and p["S"] == 2
+    try:
+        (first,) = _device(engine, p, 1, 1)
+        before = engine.debug_validity()
+        with pytest.raises(EvoAmdError, match="crossover needs H >= 2"):
+            engine.evolve_states(mutation, 2, 1, 1, p["seed"], True, 1.0, 0.25)
+        assert engine.debug_validity() == before
+        again = _evolve(engine, p)
+    finally:
+        engine.set_option("state_digest", 1)
+        engine.set_option("background_unit", 0)
+    _same_batches(first, again, "randflip_h1 after the refused %s" % mutation, True)
+    m_cand, m_counts, _ = vp.run_mirror(p, lambda n, slot0, new: first[2][n, slot0:slot0 + new.shape[0]])
+    assert np.array_equal(first[1], m_counts) and not m_counts.any()  # S = 2^H: no child is new
+
+
 @pytest.mark.parametrize("name", list(vp.CASES))
 def test_children_match_the_mirror(engine, name):
     from evo_amd.variational import eas_counter as ec

@@ -623,6 +623,42 @@ def test_es3c_tile_aligned_shapes_against_oracle(engine, D, H, S, N, device_mste
 
 
 @pytest.mark.parametrize("device_mstep", [False, True])
+@pytest.mark.parametrize("D,H,S", [(3, 1, 2), (4, 2, 3), (5, 3, 5), (6, 4, 7)])
+@pytest.mark.parametrize("algo", ["ebsc", "es3c"])
+def test_tiny_latent_space_against_oracle(engine, algo, D, H, S, device_mstep):
+    """Three chained EM steps at H = 1 ... 4 (N = 23) on the reference rng against oracle.evo_oracle.bsc_step /
+    sssc_step: an H x H grid smaller than a wave, no pair of latents at H = 1, 1 x 1 inverses, and at H = 1, S = 2 a
+    K^n that is the whole state space, so that the EA finds nothing new ("No new and unique states", nu == 0).
+    Tolerances: those of test_es3c_tile_aligned_shapes_against_oracle.  The oracle's update never enters its
+    LinAlgError branch (pinv + np.random noise) on these seeds: test_tiny_step_problems.py runs the same three steps on
+    the CPU and bounds the condition number of every H x H system they solve (28 at the most, es3c H = 3 step 2)."""
+    import _tiny_step_problems as ts
+    from evo_amd.models import BSC, SSSC
+    from evo_amd.variational import init_states
+    Y, theta0 = ts.make_case(algo, D, H, S)
+    ss0, run = ts.oracle_run(algo, D, H, S)
+    my_data = {"y": Y, "x_infr": np.ones_like(Y, dtype=bool)}
+    np.random.seed(ts.SEED_STATES)
+    suff = init_states(*ts.init_args(H, S))
+    assert np.array_equal(suff["ss"], ss0)
+    model = (BSC if algo == "ebsc" else SSSC)(D, H, S, engine=engine, device_mstep=device_mstep)
+    th = ts.copy_theta(theta0)
+    for t, ref in enumerate(run):
+        np.random.seed(ts.SEED_STEP + t)
+        F, nu, nsub, th = model.step(th, suff, my_data)
+        print("tiny %s D %d H %d S %d step %d: F %.12f (oracle %.12f) nu %.3f nsub %.3f" % (algo, D, H, S, t, F, ref["F"], nu, nsub))
+        np.testing.assert_allclose(F, ref["F"], rtol=1e-9, err_msg="F step %d" % t)
+        assert (nu, nsub) == (ref["nu"], ref["nsub"]), t
+        if S == 2 ** H:
+            assert nu == 0
+        assert np.array_equal(suff["ss"], ref["ss"]), "K^n differs at step %d" % t
+        for k in (BSC_KEYS if algo == "ebsc" else SSSC_KEYS):
+            want = np.asarray(ref["theta"][k])
+            np.testing.assert_allclose(th[k], want, rtol=1e-6, atol=1e-7 * max(1.0, float(np.abs(want).max())),
+                                       err_msg="%s step %d" % (k, t))
+
+
+@pytest.mark.parametrize("device_mstep", [False, True])
 def test_es3c_step_with_duplicated_latent_against_oracle(engine, device_mstep):
     """Full EM steps from a Theta whose Psi holds a duplicated latent (5 a copy of 2: exactly singular Psi_A for every
     state that holds both, sssc.py:278-301) on a K^n dense enough that such states carry three to nine latents: candidates (level chains), selection, statistics and the Theta update all run in the kernels' exact mode
@@ -1137,20 +1173,28 @@ def test_lazy_theta_is_the_same_theta(engine, algo):
         np.testing.assert_allclose(out[0][1][k], out[1][1][k], rtol=1e-9, atol=1e-12, err_msg=k)
 
 
-@pytest.mark.parametrize("algo", ["ebsc", "es3c"])
-def test_lazy_theta_singular_update_restores_the_estep_theta(engine, algo):
+@pytest.mark.parametrize("algo,shape", [
+    pytest.param("ebsc", (20, 24, 12), id="ebsc"), pytest.param("es3c", (20, 24, 12), id="es3c"),
+    # D = 8 H / D <= 8 H with H H = 4 / 9 < DP_COUNT: the ES3C backup written by the update's first kernel
+    pytest.param("ebsc", (8, 2, 3), id="ebsc-8-2-3"), pytest.param("es3c", (8, 2, 3), id="es3c-8-2-3"),
+    pytest.param("ebsc", (12, 3, 5), id="ebsc-12-3-5"), pytest.param("es3c", (12, 3, 5), id="es3c-12-3-5")])
+def test_lazy_theta_singular_update_restores_the_estep_theta(engine, algo, shape):
     """with lazy_theta=True the host holds no copy of the Theta an E-step ran with, and the device update
     overwrites it in place -- the singular-update fallback used to download what the FAILED update had left behind and
     ran the statistics and the reference's host formulas on that.  Now the library keeps the E-step's parameters in a
     device backup and the fallback re-installs them.  Two lazy steps, then a step whose device update is reported
     singular (forced: the real update has run and overwritten Theta, which is exactly the state the fallback meets):
-    F and Theta^new must equal the eager run, whose fallback reads the host copy."""
+    F and Theta^new must equal the eager run, whose fallback reads the host copy.  (D, H, S) = shape; below H = 4 the
+    ES3C backup's scalar block is wider than the H H threads that write it.  While each thread saved one scalar only,
+    es3c-8-2-3 got back whatever the unwritten slot of the backup held, sigma2 = 0.0 in the run on record: the host
+    precompute divided by zero and the statistics pass refused with "exactly singular k x k system"."""
     from evo_amd import engine as eng_mod
     from evo_amd.models import BSC, SSSC
     from evo_amd.models._models import LazyTheta
     from evo_amd.variational import init_states
     rng = np.random.RandomState(14)
-    D, H, S, N = 20, 24, 12, 300
+    (D, H, S), N = shape, 300
+    n_parents = min(4, S - 1)
     Y = rng.normal(size=(N, D))
     my_data = {"y": Y, "x_infr": np.ones_like(Y, dtype=bool)}
     cls = BSC if algo == "ebsc" else SSSC
@@ -1160,7 +1204,7 @@ def test_lazy_theta_singular_update_restores_the_estep_theta(engine, algo):
         np.random.seed(9)
         model = cls(D, H, S, rng="device", sync_host=False, engine=engine, seed=5, device_mstep=True, lazy_theta=lazy)
         theta = model.check_params(model.standard_init(my_data))
-        suff = init_states(N, S, H, "fit", "randflip", 4, 1, 1)
+        suff = init_states(N, S, H, "fit", "randflip", n_parents, 1, 1)
         calls = {"n": 0}
 
         def forced(to_learn, reconstruct=False, theta_to_host=True):
@@ -1220,6 +1264,61 @@ def test_device_mstep_absorbs_singular_update(engine, algo):
         assert np.isfinite(res[1][1][k]).all(), k
         # the fallback goes through pinv of a singular sum + 5e-5-scale noise: agreement at 1e-4 of the scale
         a, b = res[1][1][k], res[0][1][k]
+        np.testing.assert_allclose(a, b, rtol=1e-4, atol=1e-4 * max(1.0, float(np.abs(b).max())), err_msg=k)
+
+
+@pytest.mark.parametrize("algo", ["ebsc", "es3c"])
+def test_device_mstep_absorbs_singular_update_at_three_latents_with_lazy_theta(engine, algo):
+    """The same at H = 3, S = 3 with lazy_theta=True, where the singular update is a real one and meets a Theta the host
+    has no copy of.  Step 1: every latent is in one state, the update is well posed and Theta^new stays on the device.
+    Then latent 2 is silenced in every K^n; step 2's H x H system is exactly singular: status 3 from the SPD
+    elimination, the pivoted repeat, status 1, restore_theta_backup where the host holds no copy (counted here), the
+    reference's host formulas.  Against the host-M-step path on the same np.random draws, at the tolerance of the test
+    above."""
+    from evo_amd.models import BSC, SSSC
+    from evo_amd.models._models import LazyTheta
+    from evo_amd.variational import init_states
+    rng = np.random.RandomState(18)
+    D, H, S, N = 7, 3, 3, 40
+    Y = rng.normal(size=(N, D))
+    my_data = {"y": Y, "x_infr": np.ones_like(Y, dtype=bool)}
+    res, restores, pending = [], [], []  # pending: Theta was on the device alone when mstep_device was called
+    real, real_mstep = engine.restore_theta_backup, engine.mstep_device
+    for mode in (False, True):
+        np.random.seed(5)
+        model = (BSC if algo == "ebsc" else SSSC)(D, H, S, engine=engine, device_mstep=mode, lazy_theta=mode)
+        theta = model.check_params(model.standard_init(my_data))
+        suff = init_states(N, S, H, "fit", "randflip", 2, 1, 1)
+        suff["ss"][:] = np.eye(3, dtype=bool)[None]  # every latent in one state
+        suff["mutation_algorithm"] = lambda parents, n_children, sparseness, p_bf: _flip_not_last(parents, n_children, H)
+        engine.restore_theta_backup = lambda: (restores.append(mode), real())[1]
+        if mode:
+            engine.mstep_device = lambda *a, **kw: (pending.append(isinstance(theta, LazyTheta) and not theta.materialised),
+                                                    real_mstep(*a, **kw))[1]
+        try:
+            np.random.seed(6)
+            F1, _, _, theta = model.step(theta, suff, my_data)
+            if mode:
+                assert isinstance(theta, LazyTheta) and not theta.materialised and not restores
+            suff["ss"][:] = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]], dtype=bool)[None]  # latent 2 never fires
+            np.random.seed(7)
+            F2, _, _, theta = model.step(theta, suff, my_data)
+        finally:
+            del engine.restore_theta_backup
+            if mode:
+                del engine.mstep_device
+        assert not suff["ss"][:, :, H - 1].any()
+        res.append((F1, F2, {k: np.array(v) for k, v in theta.items()}))
+    # EBSC: Theta is still on the device alone when step 2's update fails, and the backup brings it back.  ES3C on the
+    # reference rng: the host EA asks Theta for piH = sum(pies), which downloads it BEFORE the update -- the fallback then
+    # holds a host copy and needs no restore (the ES3C restore at H = 3 is
+    # test_lazy_theta_singular_update_restores_the_estep_theta[es3c-12-3-5], on the device rng)
+    assert pending == ([False, True] if algo == "ebsc" else [False, False])
+    assert restores == ([True] if algo == "ebsc" else [])
+    np.testing.assert_allclose(res[1][:2], res[0][:2], rtol=1e-10)
+    for k in (BSC_KEYS if algo == "ebsc" else SSSC_KEYS):
+        assert np.isfinite(res[1][2][k]).all(), k
+        a, b = res[1][2][k], res[0][2][k]
         np.testing.assert_allclose(a, b, rtol=1e-4, atol=1e-4 * max(1.0, float(np.abs(b).max())), err_msg=k)
 
 

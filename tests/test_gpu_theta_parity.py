@@ -203,17 +203,41 @@ def _same(a, b, what):
     _close(a, b, tp.BASE_RTOL, what + (" [same bits]" if np.array_equal(a, b) else ""))
 
 
-@pytest.mark.parametrize("name", ["es_h12", "es_d100", "bsc_h12"])
+IN_UPDATE = ("es_h12", "es_h1", "es_h2", "es_h3", "es_h4")
+
+
+def _fill_backup(engine):
+    """A lazy update of tp.backup_prelude() (es_h2_d17 with sigma2 = 2.7, the side-kernel route): theta_bak, which
+    configure keeps, then holds that problem's 58 doubles whatever ran before."""
+    q = tp.backup_prelude()
+    assert tp.backup_route(q) == "side_kernel"
+    _setup(engine, q)
+    engine.lpj_resident()
+    _, dpar = engine.mstep_device(tp.ES_KEYS, theta_to_host=False)
+    assert dpar["status"] == 0.0
+    engine.restore_theta_backup()
+    assert engine.get_params_sssc()["sigma2"] == 2.7
+
+
+@pytest.mark.parametrize("name", ["es_h12", "es_d100", "bsc_h12", "es_h1", "es_h2", "es_h2_d17", "es_h3", "es_h4", "bsc_h2"])
 def test_publish_and_backup_routes(engine, name):
     """PUBLISH_MAIN (Theta in the mailbox), PUBLISH_FOLDED with the backup (in the update for D <= 8 H, the side kernel
     above, always for EBSC), and both again with option theta_copy_engine (PUBLISH_COPY_ENGINE for the eager call): the
     same Theta^new, scalar block and tail; after every lazy call restore_theta_backup brings the input Theta back bit for
-    bit, and the pass over K^n under it repeats the first pass bit for bit."""
+    bit, and the pass over K^n under it repeats the first pass bit for bit.
+
+    The in-update backup is written by the H H live threads of sssc_mstep_prepare_kernel.  While each saved the scalar of
+    its own index only, H = 1 kept DP_PRE1 alone and H = 2 the scalars 0 .. 3, so the restore read sigma2 (index 6) from
+    a slot of theta_bak that call had not written.  _fill_backup decides what that slot holds (test_theta_problems.py
+    restates it): W[8, 1] = -0.0969... of the prelude for es_h1, the prelude's DP_PI = 0.0 for es_h2.  Before the fix the
+    restore returned sigma2 = -0.09697344284776688 (es_h1) and 0.0 (es_h2) for the 1.3 installed."""
     p = tp.make_problem(name)
     keys, theta = _keys(p), p["theta"]
-    assert tp.backup_route(p) == ("side_kernel" if name != "es_h12" else "in_update")
+    assert tp.backup_route(p) == ("in_update" if name in IN_UPDATE else "side_kernel")
     runs = {}
     try:
+        if name in tp.TINY:
+            _fill_backup(engine)
         ljc, lpj, acc = _first_pass(engine, p)
         want = tp.oracle_update(p, acc, keys)
         for dma in (0, 1):
@@ -233,6 +257,22 @@ def test_publish_and_backup_routes(engine, name):
                 assert _set_params(engine, p, back) == ljc
                 engine.lpj_resident()
                 np.testing.assert_array_equal(engine.download_lpj(), lpj, err_msg="%s %s: lpj after the restore" % (name, label))
+        # a second Theta on the same context: the backup must be this call's, not one that was right the first time
+        th2 = tp.second_theta(p)
+        assert all(not np.array_equal(th2[k], theta[k]) for k in keys if k != "Psi")
+        ljc2 = _set_params(engine, p, th2)
+        engine.lpj_resident()
+        lpj2 = engine.download_lpj()
+        assert ljc2 != ljc and not np.array_equal(lpj2, lpj)
+        _, dpar = engine.mstep_device(keys, theta_to_host=False)
+        assert dpar["status"] == 0.0 and dpar["ljc_estep"] == ljc2, name
+        engine.restore_theta_backup()
+        back = _get(engine, p)
+        for k in keys:
+            np.testing.assert_array_equal(back[k], th2[k], err_msg="%s: restored %s of the second Theta" % (name, k))
+        assert _set_params(engine, p, back) == ljc2
+        engine.lpj_resident()
+        np.testing.assert_array_equal(engine.download_lpj(), lpj2, err_msg="%s: lpj after the second restore" % name)
     finally:
         _restore(engine, ("theta_copy_engine",))
     t0, d0, g0 = runs["eager"]

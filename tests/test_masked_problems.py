@@ -54,6 +54,27 @@ def test_sizes_reach_their_edges():
     assert all(P[n]["S_perm"] == 0 for n in mp.PROBLEMS if n != "bsc_perm")
 
 
+def test_tiny_problems():
+    """es_h2 / bsc_h2: the shapes, S = 3 distinct states of the 4 in every datapoint, an observed entry in every datapoint,
+    both latents in use, the in-update backup route for es_h2 (D = 8 H), and a finite oracle."""
+    import _theta_problems as tp
+    shapes = {n: tuple(mp.PROBLEMS[n][:8]) for n in mp.TINY}
+    assert shapes == {"es_h2": ("es3c", "sparse", 37, 16, 2, 3, 0, "rand30"), "bsc_h2": ("ebsc", "sparse", 37, 9, 2, 3, 0, "rand30")}
+    assert set(mp.TINY) <= set(mp.THETA_PROBLEMS)
+    for name in mp.TINY:
+        p, o, _ = _oracle(name)
+        assert p["x_infr"].any(axis=1).all() and np.array_equal(p["x"], p["x_infr"]), name
+        assert (~p["x_infr"]).any(), name
+        for n in range(p["N"]):
+            assert len({row.tobytes() for row in p["ss"][n]}) == p["S"], (name, n)
+        assert p["ss"].any(axis=(0, 1)).all(), name
+        assert np.isfinite(o["lpj"]).all() and all(np.isfinite(np.asarray(v)).all() for v in o["sums"].values()), name
+        th = mp.oracle_update(p, o["sums"])
+        assert all(np.isfinite(np.asarray(v)).all() for v in th.values()), name
+    assert tp.backup_route(mp.make_problem("es_h2")) == "in_update" and tp.backup_route(mp.make_problem("bsc_h2")) == "side_kernel"
+    assert mp.make_problem("es_h2")["H"] ** 2 <= tp.DP_SIGMA2 < tp.DP_COUNT  # sigma2 beyond the live threads
+
+
 @pytest.mark.parametrize("name", list(mp.PROBLEMS))
 def test_mask_pattern(name):
     p = mp.make_problem(name)

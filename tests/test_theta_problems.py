@@ -84,6 +84,61 @@ def test_problems_reach_their_branches():
             assert len({row.tobytes() for row in p["ss"][n]}) == p["S"], (name, n)
 
 
+def test_tiny_problems_reach_the_lower_edge():
+    """H = 1 ... 4: the live threads of sssc_mstep_prepare_kernel (H H) against the DP_COUNT scalars its backup saves, both
+    backup routes at H = 2, S = 2^H, a single state, D = 1, N = 1, and K^n rows that stay distinct in EVERY datapoint."""
+    P = {n: tp.make_problem(n) for n in tp.TINY}
+    assert set(P) == {"es_h1", "es_h1_s1", "es_h2", "es_h2_d17", "es_h2_d1", "es_h3", "es_h4", "es_n1", "bsc_h1", "bsc_h2"}
+    shape = {n: (p["N"], p["D"], p["H"], p["S"]) for n, p in P.items()}
+    assert shape == {"es_h1": (37, 8, 1, 2), "es_h1_s1": (37, 8, 1, 1), "es_h2": (37, 16, 2, 3), "es_h2_d17": (37, 17, 2, 3),
+                     "es_h2_d1": (37, 1, 2, 4), "es_h3": (37, 24, 3, 5), "es_h4": (37, 9, 4, 7), "es_n1": (1, 8, 2, 4),
+                     "bsc_h1": (37, 5, 1, 2), "bsc_h2": (37, 5, 2, 3)}
+    assert all(p["profile"] == "sparse" and p["S_perm"] == 0 and not p["background"] for p in P.values())
+    dp_count = int(re.search(r"\bDP_COUNT = (\d+)", _src("kernels_mstep.hpp")).group(1))
+    sigma2_at = int(re.search(r"\bDP_SIGMA2 = (\d+),", _src("kernels_mstep.hpp")).group(1))
+    assert (dp_count, sigma2_at) == (tp.DP_COUNT, tp.DP_SIGMA2) == (16, 6)
+    # live threads of the prepare kernel against the scalar block: below H = 4 one scalar per thread is not enough
+    for name, live in (("es_h1", 1), ("es_h2", 4), ("es_h3", 9), ("es_h4", 16)):
+        assert P[name]["H"] ** 2 == live, name
+    assert 1 <= sigma2_at and 4 <= sigma2_at < 9 < dp_count == 16  # sigma2 beyond the live threads at H = 1 and H = 2
+    # routes: in the update up to D = 8 H, the side kernel one above; always the side kernel for EBSC
+    for name in tp.TINY:
+        want = "in_update" if name.startswith("es_") and name != "es_h2_d17" else "side_kernel"
+        assert tp.backup_route(P[name]) == want, name
+    assert P["es_h2"]["D"] == tp.BACKUP_RATIO * P["es_h2"]["H"] and P["es_h2_d17"]["D"] == tp.BACKUP_RATIO * 2 + 1
+    # the prelude of the restore test (test_gpu_theta_parity.py): es_h2_d17's backup covers the slots of es_h1 and es_h2
+    # from which a restore reads sigma2, with values that are not the expected one
+    filler = tp.backup_prelude()
+    lay = tp.backup_layout(filler)
+    assert filler["theta"]["sigma2"] != P["es_h2"]["theta"]["sigma2"] == 1.3
+    for name in ("es_h1", "es_h2"):
+        slot = tp.backup_layout(P[name])["dpar"] + tp.DP_SIGMA2
+        assert tp.backup_layout(P[name])["end"] <= lay["end"] == 58, name
+        held = tp.backup_image(filler)[slot]
+        print("%s: the backup slot of sigma2 (%d) holds %r after the prelude" % (name, slot, held))
+        assert held is not None and held != 1.3, (name, slot, held)
+    # the state space
+    for name in ("es_h1", "es_h2_d1", "es_n1", "bsc_h1"):
+        assert P[name]["S"] == 2 ** P[name]["H"], name
+    assert P["es_h1_s1"]["S"] == 1 and P["es_h2_d1"]["D"] == 1 and P["es_n1"]["N"] == 1
+    for name, p in P.items():
+        for n in range(p["N"]):
+            assert len({row.tobytes() for row in p["ss"][n]}) == p["S"], (name, n)
+        if p["N"] > 1:
+            assert p["ss"].any(axis=(0, 1)).all(), name  # every latent in some state
+    # es_h3: non-symmetric Psi and sums, as for es_nonsym
+    Psi, s = P["es_h3"]["theta"]["Psi"], tp.oracle("es_h3")["sums"]
+    assert np.abs(Psi - Psi.T).max() > 1e-2
+    assert np.abs(s["xpt_szsz"] - s["xpt_szsz"].T).max() > MARGIN * tp.THETA_RTOL * np.abs(s["xpt_szsz"]).max()
+    assert np.abs(s["s_sz_outer"] - s["s_sz_outer"].T).max() > MARGIN * tp.THETA_RTOL * np.abs(s["s_sz_outer"]).max()
+    # every oracle result is finite
+    for name, p in P.items():
+        o = tp.oracle(name)
+        assert np.isfinite(o["lpj"]).all(), name
+        th = tp.oracle_update(p, o["sums"], tp.LEARN_SETS[p["algo"]]["all"])
+        assert all(np.isfinite(np.asarray(v)).all() for v in th.values()), name
+
+
 def test_learn_sets_of_every_problem():
     es, bsc = tp.LEARN_SETS["es3c"], tp.LEARN_SETS["ebsc"]
     assert [tuple(sorted(v)) for v in es.values()] == [tuple(sorted(v)) for v in (
@@ -247,6 +302,44 @@ def test_sensitive_to_a_transposed_ebsc_W(name):
     Wq = tp.oracle(name)["sums"]["Wq"]
     assert np.abs(Wq - Wq.T).max() <= 1e-12 * np.abs(Wq).max()
     _proof(name, "wt_as_w", "W")
+
+
+# the mistakes that make sense at tiny H, at the same margin.  bsc_h2's one mistake is wt_as_w; inv_T needs a
+# non-symmetric xpt_szsz, which es_h3 ("nonsym") has and es_h2 has not (test_mistakes_that_cannot_show_...).
+TINY_PROOFS = [(name, kind, key) for name in ("es_h2", "es_h3")
+               for kind, key in (("old_mus_in_psi", "Psi"), ("mus_row", "Psi"), ("psi_matmul", "Psi"), ("old_wtw", "sigma2"),
+                                 ("inv_T", "W")) if (name, kind) != ("es_h2", "inv_T")] + [("bsc_h2", "wt_as_w", "W")]
+
+
+@pytest.mark.parametrize("name,kind,key", TINY_PROOFS)
+def test_tiny_problems_reject_a_wrong_update(name, kind, key):
+    _proof(name, kind, key)
+
+
+def test_mistakes_that_cannot_show_at_one_latent():
+    """H = 1: a 1 x 1 matmul is the element-wise product (psi_matmul), mus[None, :] is mus[:, None] (mus_row) and a 1 x 1
+    inverse is its own transpose (inv_T): these three give the oracle's update exactly, so es_h1 proves nothing about
+    them (es_h2 and es_h3 do).  What does show at H = 1 keeps the margin.  EBSC at H = 1: W^T (1 x D) stored where W
+    (D x 1) belongs is the same memory."""
+    p = tp.make_problem("es_h1")
+    s = tp.oracle("es_h1")["sums"]
+    good = tp.oracle_update(p, s, _all(p), clamp=False)
+    for kind in ("psi_matmul", "mus_row", "inv_T"):
+        bad = tp.wrong_update(p, s, kind)
+        for k in good:
+            assert _excess(bad[k], good[k]) <= 1e-3, (kind, k)  # rounding of a second evaluation at the most
+    _proof("es_h1", "old_mus_in_psi", "Psi")
+    _proof("es_h1", "old_wtw", "sigma2")
+    p = tp.make_problem("bsc_h1")
+    s = tp.oracle("bsc_h1")["sums"]
+    good = tp.oracle_update(p, s, _all(p), clamp=False)
+    assert np.array_equal(tp.wrong_update(p, s, "wt_as_w")["W"], good["W"])
+    # es_h2: Psi is symmetric (the plain recipe), and so is xpt_szsz up to rounding: inv(.)^T is inv(.), at any H
+    p = tp.make_problem("es_h2")
+    s = tp.oracle("es_h2")["sums"]
+    assert np.abs(s["xpt_szsz"] - s["xpt_szsz"].T).max() <= 1e-12 * np.abs(s["xpt_szsz"]).max()
+    good = tp.oracle_update(p, s, _all(p), clamp=False)
+    assert _excess(tp.wrong_update(p, s, "inv_T")["W"], good["W"]) <= 1e-3
 
 
 def test_sensitive_to_the_background_override():
